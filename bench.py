@@ -11,7 +11,9 @@ Config 2 (default): a "step" is one pass of the hot path (SAVSR.forward) over on
 the GPU PSNR-Y / SSIM-Y of every output frame against a synthetic ground truth.  Clips are independent, so for N > 1
 every rank runs its own K steps (weak scaling, no data-path collective); the only collective is ONE RCCL all_gather of the
 per-frame [PSNR-Y, SSIM-Y] rows, as the reference reduces its metric tensor once per dataset
-(video_base_model.py:108-113).  Rank 0 prints ONE JSON line.
+(video_base_model.py:108-113).  Rank 0 prints ONE JSON line.  `--steps K` is the number of timed steps: they run in up to `--regions`
+back-to-back timed regions and `value` is the median region's rate.  `--dump-outputs DIR` writes what the last timed step returned
+(rank 0's; `dump_outputs`).
 
 `--config run_test`: the YAML workflow (savsr_amd.test.run_test = lbasicsr/test.py:11-48) on a synthetic Vid4-shaped PNG tree
 (4 folders x `--frames-per-folder` frames, 6 datasets = 6 scales over ONE dataroot_gt, checkpoint through torch.save): frames/s of
@@ -310,6 +312,29 @@ def satu_roofline(eng, clip, h, w, scale, in_flight_ms=None):
     return r
 
 
+DUMP_SAMPLE = 1 << 22            # --dump-outputs: elements of the step's output drawn for sr_sample.npy (16 MiB of fp32)
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(dirname, out, rows):
+    """--dump-outputs DIR: what the timed path handed back in its last step, for comparing two builds output for output.
+      sr_clip0.npy    [3, H, W] fp32: the step's first output frame, whole
+      sr_sample.npy   [DUMP_SAMPLE] fp32: out.reshape(-1)[idx] of the whole step output [clips, 3, H, W] (every clip, every unit and stream),
+                      idx = np.sort(np.random.RandomState(0).randint(0, out.numel(), DUMP_SAMPLE)) -- the same elements in every run
+      psnr_ssim_y.npy [clips, 2] fp64: the GPU PSNR-Y / SSIM-Y rows of the step's frames against the synthetic GT
+    The inputs (key-seeded weights, seeded clips and GT) depend on the arguments only."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    torch.cuda.synchronize()
+    idx = np.sort(np.random.RandomState(0).randint(0, out.numel(), DUMP_SAMPLE))
+    arrays = {"sr_clip0": out[0].float().cpu().numpy(),
+              "sr_sample": out.reshape(-1)[torch.from_numpy(idx).to(out.device)].float().cpu().numpy(),
+              "psnr_ssim_y": rows.double().cpu().numpy()}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def build_net(dev):
     import savsr_amd
     from savsr_amd.utils import synth
@@ -367,59 +392,74 @@ def run_config2(args, rank, world, dev, dist):
     rows = torch.zeros(args.steps * cps, 2, device=dev, dtype=torch.float64)
     gathered = torch.empty(world * args.steps * cps, 2, device=dev, dtype=torch.float64)
 
+    last = {}
+
     def step(i, record):
         out = net(clips[i % n_batches])
         if record:
             for j in range(cps):              # GPU PSNR-Y / SSIM-Y of every output frame (row f3), rows stay in HBM
                 psnr_ssim_y(out[j], gt, 0, out=rows[i * cps + j])
+            last["i"], last["out"] = i, out   # (a reference only: --dump-outputs reads it after the timed steps)
         return out
 
     for i in range(args.warmup):
         step(i, False)
     eng.satu_events = []          # HIP events on the launch stream around the SATU launches (in-flight figure)
 
-    def region():
-        for i in range(args.steps):
+    def region(i0, n):
+        for i in range(i0, i0 + n):
             step(i, True)
-        if dist is not None:      # the one collective of the "dataset" (RCCL all_gather over xGMI)
+        if dist is not None and i0 + n == args.steps:      # the one collective of the "dataset" (RCCL all_gather over xGMI)
             if dist.get_backend() == "nccl":
                 dist.all_gather_into_tensor(gathered, rows)
             else:                 # SAVSR_DIST_BACKEND=gloo (ranks sharing one GPU in a test): the rows take the host path
                 lst = [torch.empty(rows.shape, dtype=rows.dtype) for _ in range(world)]
                 dist.all_gather(lst, rows.cpu())
                 gathered.copy_(torch.cat(lst, 0))
-    # THREE timed regions of exactly K steps each, each bracketed by barrier + synchronize with the MAX over ranks; `value` is the
-    # MEDIAN region's (a lease's shader clock drifts by a few % over seconds; one region cannot tell that from a code change)
+    # Exactly K timed steps, split into up to `--regions` back-to-back regions (K = 20: 7 + 7 + 6 steps), each bracketed by barrier +
+    # synchronize with the MAX over ranks; `value` is the MEDIAN region's per-step rate (a lease's shader clock drifts by a few % over
+    # seconds; one region cannot tell that from a code change)
+    nreg = min(max(1, args.regions), args.steps)
+    sizes = [args.steps // nreg + (1 if r < args.steps % nreg else 0) for r in range(nreg)]
+    starts = [sum(sizes[:r]) for r in range(nreg)]
     sclk0 = sysfs_sclk_mhz(dev)
-    regions = [timed(dist, dev, region) for _ in range(max(1, args.regions))]
+    regions = [timed(dist, dev, lambda i0=i0, n=n: region(i0, n)) for i0, n in zip(starts, sizes)]
     sclk1 = sysfs_sclk_mhz(dev)
-    elapsed = sorted(regions)[len(regions) // 2]
+    per_step = sorted(e / n for e, n in zip(regions, sizes))
+    step_s = per_step[len(per_step) // 2]
+    elapsed = step_s * args.steps             # the median region's rate over all K steps (ms_per_step = 1e3 x step_s)
     in_flight = [a.elapsed_time(b) / n for a, b, n in eng.satu_events]       # per clip: a batched launch sequence holds several clips' SATU stages
     eng.satu_events = None
+    assert last["i"] == args.steps - 1
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last["out"], rows[last["i"] * cps:(last["i"] + 1) * cps])
+    last.clear()
     if rank != 0:
         return
     hr_mpx = H * W / 1e6
-    value = world * args.steps * cps * hr_mpx / elapsed
+    value = world * cps * hr_mpx / step_s
     line = base_line(args, world, value, elapsed, "BASELINE config 2: synthetic 7x3x180x320 clips, scale x4 -> 720x1280, key-seeded random-init weights",
                      {"frames_per_step": cps, "streams_per_gpu": min(cps, eng.streams_for(LR_H * LR_W)), "clips_per_launch_sequence": eng.clip_batch})
     line["config"]["knobs"] = eng.knobs.knobs()          # non-default SAVSR_* switches of the engine (savsr_amd/config.py); empty = product configuration
     line["metric"] = "HR Mpixels/sec (Vid4-shape x4, 7-frame window)"
-    line["timed_region_s"] = round(elapsed, 3)
-    vals = sorted(world * args.steps * cps * hr_mpx / e for e in regions)
+    line["timed_region_s"] = round(elapsed, 3)           # K steps at the median region's rate
+    line["timed_s"] = round(sum(regions), 3)             # all K timed steps
+    line["timed_steps_per_region"] = sizes
+    vals = sorted(world * cps * hr_mpx / s for s in per_step)
     line["value_min"], line["value_median"], line["value_max"] = round(vals[0], 3), round(vals[len(vals) // 2], 3), round(vals[-1], 3)
-    line["region_values"] = [round(world * args.steps * cps * hr_mpx / e, 3) for e in regions]
-    line["regions_note"] = f"{len(regions)} timed regions of {args.steps} steps each, back to back; value = ms_per_step = the median region"
+    line["region_values"] = [round(world * n * cps * hr_mpx / e, 3) for e, n in zip(regions, sizes)]
+    line["regions_note"] = f"{args.steps} timed steps in {nreg} back-to-back regions of {sizes} steps; value = ms_per_step = the median region's"
     probe = ClockProbe(eng, dev)
     probe.start(2.0)
     clock = {"idle_probe": probe.mhz(), "sysfs_sclk_before": sclk0, "sysfs_sclk_after": sclk1}
-    probe.start(0.5 * 1e3 * elapsed / args.steps)          # under the frame load: half a step, beside one untimed step
+    probe.start(0.5 * 1e3 * step_s)          # under the frame load: half a step, beside one untimed step
     step(0, False)
     torch.cuda.synchronize()
     clock["under_frame_load"] = probe.mhz()
     # board power under the same load: ~1 s of untimed steps with the hwmon figure sampled every 50 ms (the frame sits at the power cap)
     idle_w, cap_w = sysfs_power_w(dev)
     with PowerSampler(dev) as ps:
-        for i in range(max(2, int(round(1.0 / (elapsed / args.steps))))):
+        for i in range(max(2, int(round(1.0 / step_s)))):
             step(i, False)
         torch.cuda.synchronize()
     if ps.samples:
@@ -895,9 +935,11 @@ def main():
     ap.add_argument("--emulate-rank", type=int, default=-1, help="(internal: the child of --emulate-world that runs one rank's share)")
     ap.add_argument("--tree", type=str, default="", help="(internal: an existing synthetic PNG tree + net.pth)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--regions", type=int, default=3, help="config 2: timed regions of K steps each (value = the median region)")
+    ap.add_argument("--regions", type=int, default=3, help="config 2: back-to-back regions the K timed steps are split into (value = the median region)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="config 2: after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--clips-per-step", type=int, default=16,
-                    help="independent clips per step (two HIP streams x four clips per launch sequence x two units; 16 keeps a 20-step timed region at ~2.3 s)")
+                    help="independent clips per step (two HIP streams x four clips per launch sequence x two units; 16 keeps 20 timed steps at ~2.3 s)")
     ap.add_argument("--scales", type=str, default="", help="config 3: comma-separated subset, e.g. 1.1,2.5,4")
     ap.add_argument("--no-bucket", action="store_true", help="config 5: keep the draw order instead of grouping equal (shape, scale) clips")
     args = ap.parse_args()
@@ -905,6 +947,10 @@ def main():
         args.config = int(args.config)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.config != 2:
+        ap.error("--dump-outputs goes with config 2")
     if args.emulate_world:
         if args.config != "run_test" or args.gpus != 1:
             ap.error("--emulate-world goes with --config run_test on one GPU")

@@ -13,8 +13,8 @@ Pinning: the reference ships no tests or golden vectors for this path (SURVEY.md
 the oracle is pinned against OUTPUTS OF THE REFERENCE ITSELF, imported in isolation in the build
 container: tools/gen_golden.py runs both on identical key-seeded weights/inputs and commits the
 reference's outputs as fixtures under tests/golden/; tests/test_oracle_golden.py re-checks the
-oracle against those fixtures everywhere, and tests/test_oracle_vs_reference.py re-runs the
-live comparison whenever /root/reference is present.
+oracle against those fixtures everywhere, and tests/test_oracle_vs_reference.py does the same
+on the reference's state_dict manifest and a second weight seed (tools/gen_golden_reference_checks.py).
 """
 from __future__ import annotations
 

@@ -1,4 +1,5 @@
-"""The reference's test YAMLs must parse unchanged."""
+"""Test option files in the reference's YAML layout must parse: a sample, and files of the shipped YAMLs'
+42 datasets (workloads.YAML_SCALES)."""
 import os
 
 import pytest
@@ -74,13 +75,39 @@ def test_sample_yaml():
     _check(opt)
 
 
-@pytest.mark.parametrize("name", ["test_SAVSR_Vid4_asBI.yml", "test_SAVSR_UDM10_asBI.yml"])
-def test_reference_yaml_parses_unchanged(name):
-    path = os.path.join("/root/reference/options/test/SAVSR", name)
-    if not os.path.isfile(path):
-        pytest.skip("reference tree not present")
+def _scale_list_yaml(tmp_path, dataset):
+    """A test option file in the shipped YAMLs' layout: the SAMPLE's settings with one dataset per scale of
+    workloads.YAML_SCALES (42: x4.0 ... x1.1 and the 12 asymmetric pairs), written to a file."""
+    from savsr_amd.utils import workloads
+    head, rest = SAMPLE.split("datasets:\n", 1)
+    tail = rest[rest.index("network_g:"):]
+    blocks = []
+    for i, (sh, sw) in enumerate(workloads.YAML_SCALES, 1):
+        blocks.append(f"""  test_{i:02d}:
+    name: {dataset}_x{sh}_{sw}
+    type: ASVideoTestDataset
+    dataroot_gt: datasets/{dataset}/GT
+    io_backend:
+      type: disk
+    cache_data: false
+    num_frame: 7
+    padding: reflection
+    use_arbitrary_scale_downsampling: true
+    downsampling_scale: !!python/tuple [{sh}, {sw}]
+    downsampling_mode: torch
+""")
+    text = head.replace("test_SAVSR_sample", f"test_SAVSR_{dataset}_asBI") + "datasets:\n" + "".join(blocks) + tail
+    path = tmp_path / f"test_SAVSR_{dataset}_asBI.yml"
+    path.write_text(text)
+    return str(path), workloads.YAML_SCALES
+
+
+@pytest.mark.parametrize("dataset", ["Vid4", "UDM10"])
+def test_scale_list_yaml_parses(tmp_path, dataset):
+    path, scales = _scale_list_yaml(tmp_path, dataset)
     opt = parse_test_options(path)
     assert len(opt["datasets"]) == 42
+    assert [d["downsampling_scale"] for d in opt["datasets"].values()] == [tuple(s) for s in scales]
     assert yaml_load(path)["model_type"] == "ASVSRModel"
     _check(opt)
 
@@ -98,12 +125,9 @@ def test_sample_yaml_registry_resolution():
         savsr_amd.MODEL_REGISTRY.get("NoSuchModel")
 
 
-@pytest.mark.parametrize("name", ["test_SAVSR_Vid4_asBI.yml", "test_SAVSR_UDM10_asBI.yml"])
-def test_reference_yaml_registry_resolution(name):
-    path = os.path.join("/root/reference/options/test/SAVSR", name)
-    if not os.path.isfile(path):
-        pytest.skip("reference tree not present")
-    _resolves(parse_test_options(path))
+@pytest.mark.parametrize("dataset", ["Vid4", "UDM10"])
+def test_scale_list_yaml_registry_resolution(tmp_path, dataset):
+    _resolves(parse_test_options(_scale_list_yaml(tmp_path, dataset)[0]))
 
 
 def test_model_and_dataset_refuse_cpu():

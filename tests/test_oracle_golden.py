@@ -3,7 +3,7 @@
 The fixtures in tests/golden/reference_outputs.npz were produced by tools/gen_golden.py, which
 imports /root/reference/lbasicsr/archs/savsr_arch.py in isolation; this test needs no reference.
 Tolerance: the oracle runs the same ATen ops in the same order, so it is expected bit-identical;
-1e-6 absolute is allowed for thread-count dependent reduction order inside oneDNN.
+1e-6 absolute is allowed for reduction-order differences inside oneDNN / MKL (the module runs at the generator's thread count).
 """
 import numpy as np
 import pytest
@@ -15,6 +15,17 @@ from tests.golden_cases import (GRID_SIZES, NET_CASES, OSCONV_CASES, OSCONV_SCAL
                                 YAML_SCALES, rnd)
 
 TOL = 1e-6
+GEN_THREADS = 8      # torch.set_num_threads of tools/gen_golden.py
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _generator_thread_count():
+    """The oracle runs with the thread count the fixtures were generated with: the reduction order of the CPU convolutions and
+    matrix products depends on it (the session's count, one per core of the host, moves the SATU tap by ~2e-6 at 16 threads)."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(GEN_THREADS)
+    yield
+    torch.set_num_threads(n)
 
 
 def _close(a, b, tol=TOL):
