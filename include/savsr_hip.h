@@ -17,9 +17,10 @@
  *     are channel-planar ([C][h][w]);
  *   - output sizes H, W are computed by the CALLER with Python round() so that get_HW
  *     (savsr_arch.py:745-751) stays bit-exact;
- *   - specialisation: the SATU entry points (savsr_satu_*) and savsr_pack_windows are built for the shipped configuration of the
- *     reference constructor (savsr_arch.py:576-589): num_feat = 64, slid_win = 3, num_in_ch = 3.  The conv / OSConv entry points
- *     take any channel counts that are multiples of 16 (32 for 1x1).  A checkpoint trained with another num_feat does not run.
+ *   - specialisation: the tuned SATU entry points (savsr_satu_*, savsr_tail_*) and savsr_pack_windows are built for the shipped
+ *     configuration of the reference constructor (savsr_arch.py:576-589): num_feat = 64, slid_win = 3, num_in_ch = 3.  The
+ *     width-generic SATU (savsr_satu_nf_*, ABI 29) serves num_feat = 32 (and 64, for cross-checks); the conv / OSConv entry points
+ *     take any channel counts that are multiples of 16 (32 for 1x1).  Checkpoints with another num_feat, or num_in_ch != 3, do not run.
  */
 #ifndef SAVSR_HIP_H
 #define SAVSR_HIP_H
@@ -31,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 28
+#define SAVSR_ABI_VERSION 29
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -334,6 +335,34 @@ int savsr_satu_hr_tail_q(const savsr_satu_weights* wt, const float* lrcat, int h
                          float* q9, int64_t q_plane, float* seam, int64_t seam_floats, void* stream);
 int savsr_tail_gather_q(const float* q9, int64_t q_plane, const float* seam, int64_t seam_floats, const float* tail_b, const float* center,
                         int h, int w, int H, int W, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 29) Width-generic SATU, the tail-projected 27-plane form above for num_feat C in {32, 64} (satu_nf.hip; C = 64 only
+ * to cross-check the tuned kernels).  Same algebra, same phase table / expanded table (savsr_satu_phase_table,
+ * savsr_satu_expand_table: their coordinate MLP does not depend on C) and the same savsr_tail_gather behind it.
+ *   savsr_satu_nf_lr_stage: kernel_conv + LeakyReLU(0.1) + sta_conv + the three projections (:226-228, 297-313, 319-320) ->
+ *                           LRcat [h][w][64 + C/2]: (Wt27 Wa sta | Wt27 Wb x) in savsr_satu_lr_stage_tail's row order, then the
+ *                           C-stack (C_m x)[j] at (C/8) m + j.  The [25 C] kernel map is never written.
+ *   savsr_satu_nf_hr      : bilinear gathers at off / soff, expert mixing (K = C/2), -> P: [27] planes of [H][W], out_plane apart.
+ * Both only enqueue (no allocation) and are capturable; an unsupported C or shape returns SAVSR_E_ARG.  The HR stage reads `table`
+ * when n_uh * n_uw <= 256 and `ptab` otherwise, as savsr_satu_hr_tail does. */
+typedef struct savsr_satu_nf_weights {  /* device pointers packed by the caller (savsr_amd/packing.py::_pack_satu_nf) */
+    int32_t C;                           /* num_feat */
+    int32_t reserved;
+    const void*  kconv_w;   /* split-bf16 image [25 tap][C/32 cg][C/16 ks][2 part][64 lanes][8]: row 32 cg + (lane & 31) of tap `tap`,
+                               k = 16 ks + 8 (lane >> 5) + j  (:227) */
+    const float* kconv_b;   /* [25 tap][C] */
+    const void*  proj_w;    /* split-bf16 image: C/16 groups of Wt27 Wa (k = 32 (g / 2) + 16 (g % 2) + 8 (j / 4) + 4 (lane >> 5) + j % 4),
+                               then 1 + ceil(C / 64) tiles x C/16 groups of [Wt27 Wb ; C-stack rows zero-padded to 32] (k = 16 ks + 8 (lane >> 5) + j) */
+    const float* wbe;       /* fp32 [4 n][C/8 j][32 p]: (Wt27 Wb E_n)[p][j] */
+    const float* fusion_b;  /* fp32 [32]: Wt27 b */
+} savsr_satu_nf_weights;
+int savsr_satu_nf_lrcat_floats(int C);   /* floats per LRcat record, 64 + C/2, for an instantiated C; -1 otherwise (host only) */
+int savsr_satu_nf_lr_stage(const savsr_satu_nf_weights* wt, const float* x, const float* st,
+                           int32_t pix, int32_t row_px, int h, int w, float* lrcat, void* stream);
+int savsr_satu_nf_hr(const savsr_satu_nf_weights* wt, const float* lrcat, int h, int w,
+                     const float* table, int n_uh, int n_uw, const int32_t* idx_h, const int32_t* idx_w, const float* ptab,
+                     const float* gyn, const float* gxn, int H, int W, float* out, int64_t out_plane, void* stream);
 
 /* tail conv 3x3 64->3 + bias at HR plus the bilinear residual of the (unpadded) centre frame
  * (savsr_arch.py:738-739).  feat: [64] planes of [H][W], feat_plane floats apart; center: [3][h][w];

@@ -18,7 +18,7 @@ MAX_SRC = 5
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID = 0, 1, 2, 3
 SATU_LRCAT = 160
 SATU_TABLE = 8
-ABI_VERSION = 28
+ABI_VERSION = 29
 CONV_DIRECT, CONV_DIRECT_THROUGHPUT, CONV_WINOGRAD_Y, CONV_WINOGRAD_Y_THROUGHPUT = 0, 2, 3, 4
 CONV_WY_FORMS = (CONV_WINOGRAD_Y, CONV_WINOGRAD_Y_THROUGHPUT)
 SATU_LRCAT_TAIL = 96
@@ -67,6 +67,12 @@ class SatuWeights(C.Structure):
         ("head_w", fptr), ("head_b", fptr), ("kconv_w", fptr), ("kconv_b", fptr),
         ("proj_w", fptr), ("wbe_w", fptr), ("fusion_b", fptr),
     ]
+
+
+class SatuNfWeights(C.Structure):
+    """savsr_satu_nf_weights: the width-generic SATU (ABI 29), num_feat C in {32, 64}."""
+    _fields_ = [("C", C.c_int32), ("reserved", C.c_int32), ("kconv_w", fptr), ("kconv_b", fptr), ("proj_w", fptr), ("wbe", fptr),
+                ("fusion_b", fptr)]
 
 
 class SatuTiling(C.Structure):
@@ -125,6 +131,10 @@ SIGNATURES = {
     "savsr_satu_hr_tail_q": (C.c_int, [C.POINTER(SatuWeights), fptr, C.c_int, C.c_int, fptr, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr,
                                        C.c_int, C.c_int, C.POINTER(SatuTiling), fptr, fptr, C.c_int64, fptr, C.c_int64, C.c_void_p]),
     "savsr_tail_gather_q": (C.c_int, [fptr, C.c_int64, fptr, C.c_int64, fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr, C.c_void_p]),
+    "savsr_satu_nf_lrcat_floats": (C.c_int, [C.c_int]),
+    "savsr_satu_nf_lr_stage": (C.c_int, [C.POINTER(SatuNfWeights), fptr, fptr, C.c_int32, C.c_int32, C.c_int, C.c_int, fptr, C.c_void_p]),
+    "savsr_satu_nf_hr": (C.c_int, [C.POINTER(SatuNfWeights), fptr, C.c_int, C.c_int, fptr, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr,
+                                   C.c_int, C.c_int, fptr, C.c_int64, C.c_void_p]),
     "savsr_resize_aa_axis": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, C.c_int, fptr, C.c_void_p]),
     "savsr_metrics_blocks": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "savsr_metrics_psnr_ssim_y": (C.c_int, [fptr, C.c_int64, fptr, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -45,8 +45,8 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             _lib.check(self.lib.savsr_prepare_device(), "savsr_prepare_device")
         self.cfg = dict(cfg)
         self.nf = cfg["num_feat"]
-        if self.nf != 64:
-            raise RuntimeError("the HIP SATU kernels are specialised for num_feat == 64")
+        if self.nf not in (32, 64):
+            raise RuntimeError(self.num_feat_limit(self.nf))
         if cfg["slid_win"] != 3 or cfg["num_in_ch"] != 3:
             raise RuntimeError("the input-window packing is specialised for slid_win == 3, num_in_ch == 3")
         self.pw: Dict[str, tuple] = {}      # conv key -> (wimage, bias, cout, cin, ks)
@@ -86,7 +86,9 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self.use_graphs = kn.graphs
         # SATU in the row-summed tail form (savsr_satu_hr_tail_q + savsr_tail_gather_q: 9 planes + seams between the HR stage and the
         # tail instead of 27 planes); SAVSR_SATU_Q=0: the 27-plane form
-        self.satu_q = kn.satu_q
+        self.satu_q = kn.satu_q and self.nf == 64
+        # num_feat != 64: the width-generic SATU (savsr_satu_nf_*, 27-plane form, records of satu_nf_rec floats); 64: the tuned kernels
+        self.satu_nf_rec = int(self.lib.savsr_satu_nf_lrcat_floats(self.nf)) if self.nf != 64 else 0
         # static-weight 3x3 convs in the Winograd F(2,3)-along-y form (SAVSR_CONV_WINOGRAD_Y); SAVSR_CONV_WY=0: the direct kernel everywhere
         self.conv_wy = kn.conv_wy
         # OSConv weight generation as ONE launch (savsr_osconv_attn_desc.fused: the routing recomputed in every aggregation workgroup; bit-identical).
@@ -105,6 +107,15 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self._siblings: List["HipEngine"] = []
         self._streams: List[torch.cuda.Stream] = []
         self._pack_all({k: v.detach() for k, v in state.items()})
+
+    @staticmethod
+    def num_feat_limit(nf: int) -> str:
+        """Why a checkpoint of this num_feat does not run (engine build)."""
+        msg = f"num_feat = {nf} is not supported: the HIP SATU kernels are built for num_feat 64 (tuned) and 32 (savsr_satu_nf_*)"
+        if nf > 64:
+            msg += (f"; beyond that, OSConv weight generation (savsr_osconv_weights_batch) takes cin <= 320 and hidden <= 32, and the pyramid "
+                    f"fusion's OSConvs at num_feat = {nf} have cin = {5 * nf}")
+        return msg
 
     NB_MAX = 4                  # (class default; the instance reads the library's batch limits: 24 convs / 8 OSConvs per launch => 4 clips)
 
@@ -144,6 +155,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         e.iter_win, e.fwd_idx, e.bwd_idx = self.iter_win, self.fwd_idx, self.bwd_idx
         e.satu_tail_t, e.satu_w_tail = self.satu_tail_t, self.satu_w_tail
         e.satu_tailq_t, e.satu_w_tailq, e.satu_q = self.satu_tailq_t, self.satu_w_tailq, self.satu_q
+        e.satu_nf_t, e.satu_nf_w, e.satu_nf_rec = self.satu_nf_t, self.satu_nf_w, self.satu_nf_rec
         e.nb, e._bstride, e.clip_batch, e.clip_batch_max_px = 1, {}, self.clip_batch, self.clip_batch_max_px
         e.n_streams, e.n_streams_large, e.streams_large_px = self.n_streams, self.n_streams_large, self.streams_large_px
         e.form_nb = 1
@@ -271,6 +283,12 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self._select(lq.shape, scale)
         c = self._stage_body(lq, scale)
         out = torch.empty(3, c["H"], c["W"], device=self.dev)
+        if self.nf != 64:
+            lrcat = self.satu_nf_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"])
+            self._stage_satu(c, scale)
+            return {"satu_lr_us": timer(lambda: self.satu_nf_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"])),
+                    "satu_hr_us": timer(lambda: self.satu_nf_hr(lrcat, c["h"], c["w"], scale, c["p27"], c["plane"])),
+                    "tail_us": timer(lambda: self._stage_tail(c, lq, out))}
         q = self.satu_q
         lrcat = self.satu_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], tail_form=True, q=q)
         self._stage_satu(c, scale)
@@ -386,6 +404,11 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
 
     def _stage_satu_impl(self, c: dict, scale):
         """SATU in the tail-projected form (savsr_arch.py:315-376 with the channel contraction of :738 folded in): -> P [27][H][W]."""
+        if self.nf != 64:              # the width-generic kernels (27-plane form)
+            for b in range(self.nb):
+                lrcat = self.satu_nf_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], b=b)
+                self.satu_nf_hr(lrcat, c["h"], c["w"], scale, c["p27"], c["plane"], b=b)
+            return
         for b in range(self.nb):       # (per-clip kernels: looped over the clips of a batched launch sequence)
             if self.satu_q:        # row-summed form: the HR stage adds the horizontal taps itself -> 9 planes + seams
                 lrcat = self.satu_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], tail_form=True, q=True, b=b)
@@ -447,7 +470,8 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         if taps is not None:                    # channel-last [hp][wp][64] tensors; SATU output planar
             taps["align_feat"] = c["align"].t
             taps["h_feat"] = c["hfeat"].t
-            taps["satu"] = self._satu_standalone(c, scale)
+            if self.nf == 64:               # (STAUpsample's own output: a tap of the tuned 64-wide kernels only; other widths leave it out)
+                taps["satu"] = self._satu_standalone(c, scale)
             if self.satu_q:     # the 27-plane form beside the row-summed one the frame runs (taps only)
                 c["p27"] = self.sbuf("satu.p27", _lib.TAIL_PLANES, c["plane"])
                 self.satu_hr(self.satu_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], tail_form=True), c["h"], c["w"], scale, c["p27"], c["plane"], tail_form=True)
@@ -505,7 +529,9 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             h_, w_ = int(lq.shape[-2]), int(lq.shape[-1])
             H_, W_ = get_hw(h_, w_, scale)
             plane_ = self.hr_plane(H_, W_)
-            if self.satu_q:
+            if self.nf != 64:      # (no plan to measure: this evaluates the tables outside the capture)
+                self.satu_nf_hr(self.buf("satu.lrcat_nf", h_, w_, self.satu_nf_rec), h_, w_, scale, self.sbuf("satu.p27", _lib.TAIL_PLANES, plane_), plane_)
+            elif self.satu_q:
                 self.satu_hr(self.buf("satu.lrcat_tailq", h_, w_, _lib.SATU_LRCAT_TAIL), h_, w_, scale, self.sbuf("satu.q9", 9, plane_), plane_,
                              tail_form=True, seam=self.sbuf("satu.seam", self.seam_floats(H_, W_)))
             else:

@@ -447,6 +447,24 @@ class Launcher:
         launch(ax["tiling_tail"])
         return out
 
+    def satu_nf_lr(self, x: Src, st: Src, row_px: int, h: int, w: int, b: int = 0) -> torch.Tensor:
+        """LR stage of the width-generic SATU (num_feat != 64; savsr_satu_nf_lr_stage) -> LRcat [h][w][satu_nf_rec]."""
+        assert x.pix == st.pix
+        lrcat = self.buf("satu.lrcat_nf", h, w, self.satu_nf_rec)
+        _lib.check(self.lib.savsr_satu_nf_lr_stage(C.byref(self.satu_nf_w), x.ptr + b * x.bs, st.ptr + b * st.bs, x.pix, row_px, h, w,
+                                                   lrcat.data_ptr() + b * self._bs(lrcat), self._stream()), "savsr_satu_nf_lr_stage")
+        return lrcat
+
+    def satu_nf_hr(self, lrcat: torch.Tensor, h: int, w: int, scale, out: torch.Tensor, out_plane: Optional[int] = None, b: int = 0):
+        """HR stage of the width-generic SATU (savsr_satu_nf_hr) -> the 27 tail-projected planes P, out_plane floats apart."""
+        ax = self.satu_axes(h, w, scale)
+        plane = out_plane if out_plane is not None else ax["H"] * ax["W"]
+        _lib.check(self.lib.savsr_satu_nf_hr(C.byref(self.satu_nf_w), lrcat.data_ptr() + b * self._bs(lrcat), h, w, ax["table"].data_ptr(),
+                                             ax["n_uh"], ax["n_uw"], ax["ih"].data_ptr(), ax["iw"].data_ptr(), _ptr(ax["ptab"]),
+                                             ax["gyn"].data_ptr(), ax["gxn"].data_ptr(), ax["H"], ax["W"], out.data_ptr() + b * self._bs(out), plane,
+                                             self._stream()), "savsr_satu_nf_hr")
+        return out
+
     def satu(self, x: Src, st: Src, row_px: int, h: int, w: int, scale, out: torch.Tensor, out_plane: Optional[int] = None):
         """STAUpsample.forward (savsr_arch.py:315-376).  x, st: channel-last crops (row pitch row_px
         pixels) of [..][..][64] maps; out: [64][H][W] planar."""

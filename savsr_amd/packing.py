@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ._lib import SatuWeights
+from ._lib import SatuNfWeights, SatuWeights
 
 BN_EPS = 1e-5
 MAX_SUM_BLOCKS = 256     # workgroups of one savsr_channel_sums launch
@@ -169,6 +169,37 @@ def acc_row(r: int, half: int) -> int:
     return (r & 3) + 8 * (r >> 2) + 4 * half
 
 
+def tail_rows27(sd, c: int, row_of=lambda ky, kx, o: 3 * (3 * ky + kx) + o) -> np.ndarray:
+    """Wt27 [32][c] (float64): the 3x3 tail conv's weights (savsr_arch.py:738) regrouped by output row p = row_of(ky, kx, o); rows 27 .. 31 zero."""
+    tw = sd["tail.weight"].to("cpu", torch.float64).numpy()                          # [3 o][c][3 ky][3 kx]
+    wt27 = np.zeros((32, c), dtype=np.float64)
+    for ky in range(3):
+        for kx in range(3):
+            for o in range(3):
+                wt27[row_of(ky, kx, o)] = tw[o, :, ky, kx]
+    return wt27
+
+
+def fold_satu_nf(sd, c: int) -> Dict[str, np.ndarray]:
+    """The matrices of the width-generic tail-projected SATU (savsr_satu_nf_*), folded in float64 (savsr_arch.py:315-376, :738):
+      kconv [25 c][c], kconv_b [25 c]   kernel_conv (row n = 25 ch + tap, :227), unchanged
+      ta [32][c] = Wt27 Wa              applies to sta (fusion's first half, :374)
+      tb [32][c] = Wt27 Wb              applies to x
+      cstack [c/2][c]                   C_m rows at (c/8) m + j (weight_compress, :232-235)
+      wbe [4][c/8][32] = (Wt27 Wb E_n)[p][j] as [n][j][p]   (weight_expand, :238-241)
+      fb [32] = Wt27 b                  (fusion bias)"""
+    p = "upsample."
+    g = lambda k: sd[p + k].to("cpu", torch.float64).numpy()
+    wt27 = tail_rows27(sd, c)
+    fus = g("fusion.weight").reshape(c, 2 * c)
+    wa, wb = fus[:, :c], fus[:, c:]                                                   # cat((sta, fea)), :374
+    expd = g("weight_expand").reshape(4, c, c // 8)                                   # E_n[c][j]
+    tb = wt27 @ wb
+    return dict(kconv=g("kernel_conv.0.weight").reshape(25 * c, c), kconv_b=g("kernel_conv.0.bias"),
+                ta=wt27 @ wa, tb=tb, cstack=g("weight_compress").reshape(c // 2, c),
+                wbe=np.einsum("pc,ncj->njp", tb, expd), fb=wt27 @ g("fusion.bias"))
+
+
 class WeightPacking:
     """Mixin of HipEngine: state_dict -> device-resident kernel operands (`pw`, `pw_wy`, `osc`, `se`, `satu_*`, `tail_*`)."""
 
@@ -201,6 +232,19 @@ class WeightPacking:
     def _add_conv(self, sd, key: str, bn: Optional[str] = None):
         w, b = self._fold(sd, key, bn)
         self._register(key, w, b)
+
+    def _add_conv_padded(self, sd, key: str, bn: Optional[str], cin_p: int, cout_p: int):
+        """A conv with zero input / output channels appended up to (cin_p, cout_p): the conv kernels take multiples of 16 input channels.
+        An appended output channel is 0 (zero weights, zero bias; ReLU(0) = 0) and an appended input channel meets zero weights."""
+        w, b = self._fold(sd, key, bn)
+        cout, cin, ks, _ = w.shape
+        wp = torch.zeros(cout_p, cin_p, ks, ks)
+        wp[:cout, :cin] = w
+        bp = None
+        if b is not None:
+            bp = torch.zeros(cout_p)
+            bp[:cout] = b
+        self._register(key, wp, bp)
 
     def _add_window_conv(self, sd, d: str):
         """conv_c (3->64) and conv_sup (6->64) of one direction fused into a 16 -> 128 conv over
@@ -251,10 +295,75 @@ class WeightPacking:
             out[name] = t
         return out
 
+    def _pack_satu_heads(self, sd) -> dict:
+        """The coordinate MLP (body, routing / offset / st_offset heads, savsr_arch.py:242-257): 64 hidden units at every num_feat."""
+        p = "upsample."
+        head_w = torch.cat([sd[p + "routing.0.weight"], sd[p + "offset.weight"], sd[p + "st_offset.weight"]], 0)
+        head_b = torch.cat([sd[p + "routing.0.bias"], sd[p + "offset.bias"], sd[p + "st_offset.bias"]], 0)
+        return dict(body0_w=self._dev(sd[p + "body.0.weight"].reshape(64, 4)), body0_b=self._dev(sd[p + "body.0.bias"]),
+                    body2_w=self._dev(sd[p + "body.2.weight"].reshape(64, 64).t()), body2_b=self._dev(sd[p + "body.2.bias"]),
+                    head_w=self._dev(head_w.reshape(8, 64)), head_b=self._dev(head_b))
+
+    def _pack_satu_nf(self, sd, c: int):
+        """The width-generic SATU (savsr_satu_nf_*, num_feat = c): fold_satu_nf's float64 products rounded to fp32, the LR-side matrices
+        then split to (hi, lo) bf16 pairs in MFMA lane order (include/savsr_hip.h, savsr_satu_nf_weights); wbe and fb stay fp32."""
+        m = fold_satu_nf(sd, c)
+        lane = np.arange(64)
+        li, lh = lane & 31, lane >> 5
+        jj = np.arange(8)
+        ncg, nks, nct = c // 32, c // 16, (c // 2 + 31) // 32
+        # kconv groups [tap][cg][ks][lane][j] = Wk[25 (32 cg + (lane & 31)) + tap][16 ks + 8 (lane >> 5) + j]
+        tap = np.arange(25)[:, None, None, None, None]
+        cg = np.arange(ncg)[None, :, None, None, None]
+        ks = np.arange(nks)[None, None, :, None, None]
+        n_idx = 25 * (32 * cg + li[None, None, None, :, None]) + tap
+        k_idx = 16 * ks + 8 * lh[None, None, None, :, None] + jj[None, None, None, None, :]
+        n_idx, k_idx = np.broadcast_arrays(n_idx, k_idx)
+        kconv = m["kconv"][n_idx, k_idx].astype(np.float32)
+        kconv_b = m["kconv_b"].reshape(c, 25).T.astype(np.float32)                    # [tap][ch]
+        # Wt27 Wa: k step g consumes sta's accumulator registers 8 (g % 2) .. + 7 of channel group g // 2
+        pa = np.zeros((nks, 64, 8), dtype=np.float64)
+        for gi in range(nks):
+            ch = 32 * (gi // 2) + 16 * (gi % 2) + 8 * (jj[None, :] >> 2) + 4 * lh[:, None] + (jj[None, :] & 3)
+            pa[gi] = m["ta"][li[:, None], ch]
+        # x side: tile 0 = Wt27 Wb, tiles 1 .. nct = the C-stack, zero-padded to whole 32-row tiles; k = 16 ks + 8 (lane >> 5) + j
+        xm = np.zeros((32 * (1 + nct), c), dtype=np.float64)
+        xm[:32] = m["tb"]
+        xm[32:32 + c // 2] = m["cstack"]
+        px = np.zeros((1 + nct, nks, 64, 8), dtype=np.float64)
+        for t in range(1 + nct):
+            for ksi in range(nks):
+                px[t, ksi] = xm[32 * t + li[:, None], 16 * ksi + 8 * lh[:, None] + jj[None, :]]
+        proj = np.concatenate([pa.reshape(-1), px.reshape(-1)]).astype(np.float32)
+        t_ = lambda a: self._dev(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)))
+        img = lambda a: self._dev(split_bf16_image(torch.from_numpy(np.ascontiguousarray(a.reshape(-1)))), torch.int16)
+        self.satu_nf_t = dict(kconv_w=img(kconv), kconv_b=t_(kconv_b), proj_w=img(proj), wbe=t_(m["wbe"]), fusion_b=t_(m["fb"]))
+        w = SatuNfWeights()
+        w.C = c
+        for k, v in self.satu_nf_t.items():
+            setattr(w, k, v.data_ptr())
+        self.satu_nf_w = w
+
     def _pack_satu(self, sd):
         p = "upsample."
         c = self.nf
         f32 = torch.float32
+        if c != 64:
+            # the width-generic SATU; the phase table's weights (savsr_satu_phase_table reads the body / head pointers only) travel in a
+            # savsr_satu_weights whose other pointers name the generic form's tensors
+            self._pack_satu_nf(sd, c)
+            self.satu_t = self._pack_satu_heads(sd)
+            sw = SatuWeights()
+            for k, v in self.satu_t.items():
+                setattr(sw, k, v.data_ptr())
+            for k, v in (("kconv_w", "kconv_w"), ("kconv_b", "kconv_b"), ("proj_w", "proj_w"), ("wbe_w", "wbe"), ("fusion_b", "fusion_b")):
+                setattr(sw, k, self.satu_nf_t[v].data_ptr())
+            self.satu_w = sw
+            self.satu_tail_t, self.satu_w_tail, self.satu_tailq_t, self.satu_w_tailq = None, None, None, None      # (the tuned 64-wide forms)
+            self.tail_w = self._dev(sd["tail.weight"].reshape(3, c * 9))
+            self.tail_b = self._dev(sd["tail.bias"])
+            return
+        self.satu_nf_t, self.satu_nf_w = None, None
         wk = sd[p + "kernel_conv.0.weight"].to("cpu", f32).reshape(25 * c, c).numpy()     # [n = 25 ch + tap][k]
         bk = sd[p + "kernel_conv.0.bias"].to("cpu", f32).numpy()
         lane = np.arange(64)
@@ -313,7 +422,7 @@ class WeightPacking:
         for k, v in self.satu_t.items():
             setattr(sw, k, v.data_ptr())
         self.satu_w = sw
-        self.tail_w = self._dev(sd["tail.weight"].reshape(3, 64 * 9))
+        self.tail_w = self._dev(sd["tail.weight"].reshape(3, c * 9))
         self.tail_b = self._dev(sd["tail.bias"])
         # ---- tail-projected form (include/savsr_hip.h, savsr_satu_*_tail): the 3x3 tail conv's channel contraction
         # Wt27[p][c] (rows 27..31 zero) multiplied into fusion / expand / the LR projections in float64.  Two row orders:
@@ -405,10 +514,18 @@ class WeightPacking:
                               self._dev(sd[a + ".3.weight"].reshape(-1, cm)), self._dev(sd[a + ".3.bias"]), cm)
             self._add_conv(sd, f"RG.{g}.conv")
             m = f"adapt.{g}.mask"
-            self._add_conv(sd, m + ".0", bn=m + ".1")
-            self._add_conv(sd, m + ".4", bn=m + ".5")
-            self._add_conv(sd, m + ".7", bn=m + ".8")
-            self._add_conv(sd, m + ".11", bn=m + ".12")
+            q = sd[m + ".0.weight"].shape[0]                                         # num_feat / 4 (:189-204)
+            if q % 16 == 0:
+                self._add_conv(sd, m + ".0", bn=m + ".1")
+                self._add_conv(sd, m + ".4", bn=m + ".5")
+                self._add_conv(sd, m + ".7", bn=m + ".8")
+                self._add_conv(sd, m + ".11", bn=m + ".12")
+            else:                   # (num_feat = 32: 8 mask channels, carried as 16 -- osadapt takes the width from the packed conv)
+                qp = (q + 15) // 16 * 16
+                self._add_conv_padded(sd, m + ".0", m + ".1", self.nf, qp)
+                self._add_conv_padded(sd, m + ".4", m + ".5", qp, qp)
+                self._add_conv_padded(sd, m + ".7", m + ".8", qp, qp)
+                self._add_conv_padded(sd, m + ".11", m + ".12", qp, 1)
             self._add_osconv(sd, f"adapt.{g}.adapt")
         self._add_conv(sd, "conv_last")
         self.gamma = float(sd["gamma"].reshape(-1)[0])
