@@ -19,8 +19,11 @@
  *     (savsr_arch.py:745-751) stays bit-exact;
  *   - specialisation: the tuned SATU entry points (savsr_satu_*, savsr_tail_*) and savsr_pack_windows are built for the shipped
  *     configuration of the reference constructor (savsr_arch.py:576-589): num_feat = 64, slid_win = 3, num_in_ch = 3.  The
- *     width-generic SATU (savsr_satu_nf_*, ABI 29) serves num_feat = 32 (and 64, for cross-checks); the conv / OSConv entry points
- *     take any channel counts that are multiples of 16 (32 for 1x1).  Checkpoints with another num_feat, or num_in_ch != 3, do not run.
+ *     width-generic SATU (savsr_satu_nf_*, ABI 29) serves num_feat = 32 and, since ABI 30, every checkpoint with num_in_ch != 3
+ *     (num_in_ch 1 .. 3: the tail's 9 num_in_ch rows live in the 32-row MFMA tile of the LRcat record; savsr_satu_nf_hr_planes +
+ *     savsr_tail_gather_nch); savsr_pack_windows_nch (ABI 30) packs windows of any odd slid_win >= 3 with num_in_ch * slid_win <= 32.
+ *     The conv / OSConv entry points take any channel counts that are multiples of 16 (32 for 1x1).  Checkpoints with another
+ *     num_feat, num_in_ch >= 4 or another window do not run.
  */
 #ifndef SAVSR_HIP_H
 #define SAVSR_HIP_H
@@ -32,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 29
+#define SAVSR_ABI_VERSION 30
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -225,6 +228,11 @@ int savsr_upsample2x(const float* in, float* out, int c, int h, int w, void* str
  * padding (:670-690) folded in.  lq: [T][3][h][w] planar -> out: [T-2][hp][wp][16] channel-last,
  * channels = frame t | frame t-1 | frame t+1 | 7 zeros for window centre t = position + 1. */
 int savsr_pack_windows(const float* lq, float* out, int T, int h, int w, int hp, int wp, void* stream);
+/* (ABI 30) The same for nch = num_in_ch channels and an odd window of sw >= 3 frames, nch * sw <= 32 (savsr_arch.py:448-454 with
+ * c = nch, win_size = sw; :661-668; :670-690).  lq: [T][nch][h][w] planar -> out: [T-sw+1][hp][wp][RW] channel-last, RW = 16 if
+ * nch * sw <= 16, else 32; channels = frame t | the sw-1 support frames in ascending time order (sup_index, :450-454), nch each |
+ * zeros, for window centre t = position + sw/2.  At nch = 3, sw = 3 the output equals savsr_pack_windows'. */
+int savsr_pack_windows_nch(const float* lq, float* out, int T, int nch, int sw, int h, int w, int hp, int wp, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * SATU = STAUpsample.forward (savsr_arch.py:315-376), restructured:
@@ -363,6 +371,19 @@ int savsr_satu_nf_lr_stage(const savsr_satu_nf_weights* wt, const float* x, cons
 int savsr_satu_nf_hr(const savsr_satu_nf_weights* wt, const float* lrcat, int h, int w,
                      const float* table, int n_uh, int n_uw, const int32_t* idx_h, const int32_t* idx_w, const float* ptab,
                      const float* gyn, const float* gxn, int H, int W, float* out, int64_t out_plane, void* stream);
+/* (ABI 30) num_in_ch = nch checkpoints: the tail conv (savsr_arch.py:738, 64 -> nch) leaves 9 nch live rows in Wt, row
+ * p = nch (3 ky + kx) + o (rows 9 nch .. 31 zero: packing.py::fold_satu_nf).
+ *   savsr_satu_nf_hr_planes: savsr_satu_nf_hr computing and writing the first `planes` (9, 18 or 27) planes only; each plane equals
+ *                            the 27-plane call's bit for bit, and nothing beyond them is written (at 720x1280, 9 planes instead of 27
+ *                            save ~66 MB of writes per frame).  savsr_satu_nf_hr is this entry with planes = 27.
+ *   savsr_tail_gather_nch  : the rest of :738-739 for nch output channels: the nine shifted taps of P[nch (3 ky + kx) + o], the tail
+ *                            bias and the bilinear residual (F.interpolate, :739) of the unpadded centre frame center [nch][h][w] ->
+ *                            out [nch][H][W] contiguous.  At nch = 3 it agrees with savsr_tail_gather to rounding. */
+int savsr_satu_nf_hr_planes(const savsr_satu_nf_weights* wt, const float* lrcat, int h, int w,
+                            const float* table, int n_uh, int n_uw, const int32_t* idx_h, const int32_t* idx_w, const float* ptab,
+                            const float* gyn, const float* gxn, int H, int W, float* out, int64_t out_plane, int planes, void* stream);
+int savsr_tail_gather_nch(const float* planes, int64_t p_plane, int nch, const float* tail_b, const float* center,
+                          int h, int w, int H, int W, float* out, void* stream);
 
 /* tail conv 3x3 64->3 + bias at HR plus the bilinear residual of the (unpadded) centre frame
  * (savsr_arch.py:738-739).  feat: [64] planes of [H][W], feat_plane floats apart; center: [3][h][w];

@@ -18,7 +18,7 @@ MAX_SRC = 5
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID = 0, 1, 2, 3
 SATU_LRCAT = 160
 SATU_TABLE = 8
-ABI_VERSION = 29
+ABI_VERSION = 30
 CONV_DIRECT, CONV_DIRECT_THROUGHPUT, CONV_WINOGRAD_Y, CONV_WINOGRAD_Y_THROUGHPUT = 0, 2, 3, 4
 CONV_WY_FORMS = (CONV_WINOGRAD_Y, CONV_WINOGRAD_Y_THROUGHPUT)
 SATU_LRCAT_TAIL = 96
@@ -111,6 +111,7 @@ SIGNATURES = {
     "savsr_avgpool2": (C.c_int, [fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "savsr_upsample2x": (C.c_int, [fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "savsr_pack_windows": (C.c_int, [fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "savsr_pack_windows_nch": (C.c_int, [fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "savsr_satu_phase_table": (C.c_int, [C.POINTER(SatuWeights), fptr, C.c_int, fptr, C.c_int, C.c_float, C.c_float,
                                          fptr, C.c_void_p]),
     "savsr_satu_lr_stage": (C.c_int, [C.POINTER(SatuWeights), fptr, fptr, C.c_int32, C.c_int32, C.c_int, C.c_int,
@@ -135,6 +136,9 @@ SIGNATURES = {
     "savsr_satu_nf_lr_stage": (C.c_int, [C.POINTER(SatuNfWeights), fptr, fptr, C.c_int32, C.c_int32, C.c_int, C.c_int, fptr, C.c_void_p]),
     "savsr_satu_nf_hr": (C.c_int, [C.POINTER(SatuNfWeights), fptr, C.c_int, C.c_int, fptr, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr,
                                    C.c_int, C.c_int, fptr, C.c_int64, C.c_void_p]),
+    "savsr_satu_nf_hr_planes": (C.c_int, [C.POINTER(SatuNfWeights), fptr, C.c_int, C.c_int, fptr, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr,
+                                          C.c_int, C.c_int, fptr, C.c_int64, C.c_int, C.c_void_p]),
+    "savsr_tail_gather_nch": (C.c_int, [fptr, C.c_int64, C.c_int, fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr, C.c_void_p]),
     "savsr_resize_aa_axis": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, C.c_int, fptr, C.c_void_p]),
     "savsr_metrics_blocks": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "savsr_metrics_psnr_ssim_y": (C.c_int, [fptr, C.c_int64, fptr, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -75,6 +75,37 @@ __global__ __launch_bounds__(256) void pack_windows_kernel(const float* __restri
     }
 }
 
+// The same windows for any channel count and odd window size (savsr_arch.py:448-454 with c = nch, win_size = sw; generate_it :661-668;
+// pad_spatial :681-690).  lq: [T][nch][h][w] planar; out: [T-sw+1][hp][wp][RW] channel-last, position q <-> window centre
+// t = q + sw/2: ch [0, nch) = frame t (x_c), then the sw-1 support frames in ascending time order, nch channels each (the
+// sup_index order of :450-454, reshaped frame-major at :454), then zeros up to RW (16 or 32 floats per pixel).
+__global__ __launch_bounds__(256) void pack_windows_nch_kernel(const float* __restrict__ lq, float* __restrict__ out, int T, int nch, int sw, int rw,
+                                                               int h, int w, int hp, int wp) {
+    const int r4 = rw >> 2, live = nch * sw, half = sw >> 1;
+    const long long n = (long long)(T - sw + 1) * hp * wp * r4;          // float4 units
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const int q4 = (int)(i % r4);
+        const long long pi = i / r4;
+        const int x = (int)(pi % wp);
+        const int y = (int)((pi / wp) % hp);
+        const int q = (int)(pi / ((long long)wp * hp));
+        const int sx = x < w ? x : 2 * (w - 1) - x;
+        const int sy = y < h ? y : 2 * (h - 1) - y;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int ch = 4 * q4 + j;
+            if (ch < live) {
+                const int slot = ch / nch, comp = ch - nch * slot;
+                const int k = slot - 1;                                   // support index (slot 0: the centre frame)
+                const int off = slot == 0 ? 0 : (k < half ? k - half : k - half + 1);
+                v[j] = lq[(((long long)(q + half + off) * nch + comp) * h + sy) * w + sx];
+            }
+        }
+        reinterpret_cast<f32x4*>(out)[i] = v;
+    }
+}
+
 // bench.py's clock probe: one wave, no LDS; per window: shader clock = (s_memtime delta) / (s_memrealtime delta) x 100 MHz
 __global__ __launch_bounds__(64) void clock_probe_kernel(long long* out, int window_ticks, int windows) {
     for (int wi = 0; wi < windows; ++wi) {
@@ -128,4 +159,15 @@ extern "C" int savsr_pack_windows(const float* lq, float* out, int T, int h, int
     if (reinterpret_cast<uintptr_t>(out) & 15) { set_error("pack_windows: out must be 16-byte aligned"); return SAVSR_E_ALIGN; }
     hipLaunchKernelGGL(pack_windows_kernel, dim3(grid_for((long long)(T - 2) * hp * wp * 4)), dim3(256), 0, static_cast<hipStream_t>(stream), lq, out, T, h, w, hp, wp);
     return check_launch("pack_windows_kernel");
+}
+
+extern "C" int savsr_pack_windows_nch(const float* lq, float* out, int T, int nch, int sw, int h, int w, int hp, int wp, void* stream) {
+    if (!lq || !out) return fail_arg("pack_windows_nch: null pointer");
+    if (nch < 1 || sw < 3 || !(sw & 1) || nch * sw > 32) return fail_arg("pack_windows_nch: nch >= 1, slid_win odd and >= 3, nch * slid_win <= 32");
+    if (T < sw || h < 2 || w < 2 || hp < h || wp < w || hp > h + 1 || wp > w + 1) return fail_arg("pack_windows_nch: shape");
+    if (reinterpret_cast<uintptr_t>(out) & 15) { set_error("pack_windows_nch: out must be 16-byte aligned"); return SAVSR_E_ALIGN; }
+    const int rw = nch * sw <= 16 ? 16 : 32;
+    hipLaunchKernelGGL(pack_windows_nch_kernel, dim3(grid_for((long long)(T - sw + 1) * hp * wp * (rw / 4))), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       lq, out, T, nch, sw, rw, h, w, hp, wp);
+    return check_launch("pack_windows_nch_kernel");
 }

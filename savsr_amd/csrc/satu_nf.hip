@@ -236,21 +236,24 @@ __device__ __forceinline__ NfTaps nf_taps(float gxn, float gyn, float onx, float
     return t;
 }
 
-// P[acc_row(r, hh)] += wgt * rec[32 hh + base + r] for the 27 rows that exist
-__device__ __forceinline__ void nf_gather_rows(float (&P)[27], const float* rec, int base, float wgt) {
+// P[acc_row(r, hh)] += wgt * rec[32 hh + base + r] for the NP rows that are computed (27, or 9 nch: rows 9 nch .. 31 of Wt are zero)
+template <int NP>
+__device__ __forceinline__ void nf_gather_rows(float (&P)[NP], const float* rec, int base, float wgt) {
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            if (8 * g + 4 * hh >= 27) continue;
+            if (8 * g + 4 * hh >= NP) continue;
             const f32x4 v = *reinterpret_cast<const f32x4*>(rec + 32 * hh + base + 4 * g);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                if (8 * g + 4 * hh + i < 27) P[8 * g + 4 * hh + i] = fmaf(wgt, v[i], P[8 * g + 4 * hh + i]);
+                if (8 * g + 4 * hh + i < NP) P[8 * g + 4 * hh + i] = fmaf(wgt, v[i], P[8 * g + 4 * hh + i]);
         }
 }
 
-template <int C>
+// NP: planes computed and written -- 27 (savsr_satu_nf_hr), or the 9 nch live ones of an nch-channel checkpoint (savsr_satu_nf_hr_planes).
+// Every plane's arithmetic is independent of NP: plane p of an NP-plane launch equals plane p of the 27-plane one bit for bit.
+template <int C, int NP>
 __global__ __launch_bounds__(256) void satu_nf_hr_kernel(const NfHrParams p) {
     using G = Nf<C>;
     constexpr int J = C / 8;                                           // compressed channels per expert
@@ -274,9 +277,9 @@ __global__ __launch_bounds__(256) void satu_nf_hr_kernel(const NfHrParams p) {
     const float gxn = p.gxn[Xc], gyn = p.gyn[Y];
     const NfTaps to = nf_taps(gxn, gyn, oo[0], oo[1], p.h, p.w);
     const NfTaps ts = nf_taps(gxn, gyn, oo[2], oo[3], p.h, p.w);
-    float P[27];
+    float P[NP];
 #pragma unroll
-    for (int q = 0; q < 27; ++q) P[q] = p.wt.fusion_b[q];
+    for (int q = 0; q < NP; ++q) P[q] = p.wt.fusion_b[q];
     float z[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) z[j] = 0.f;
@@ -309,12 +312,52 @@ __global__ __launch_bounds__(256) void satu_nf_hr_kernel(const NfHrParams p) {
             const float u = rr[n] * z[j];
             const float* we = p.wt.wbe + (n * J + j) * 32;
 #pragma unroll
-            for (int q = 0; q < 27; ++q) P[q] = fmaf(we[q], u, P[q]);
+            for (int q = 0; q < NP; ++q) P[q] = fmaf(we[q], u, P[q]);
         }
     if (!valid) return;
     float* o = p.out + (long long)Y * p.W + X;
 #pragma unroll
-    for (int q = 0; q < 27; ++q) o[q * p.out_plane] = P[q];
+    for (int q = 0; q < NP; ++q) o[q * p.out_plane] = P[q];
+}
+
+// What is left of savsr_arch.py:738-739 for an nch-channel tail (nch = num_in_ch in 1 .. 3) after an NP = 9 nch HR stage:
+//     out[o][Y][X] = tail_b[o] + sum_{ky,kx} P[nch (3 ky + kx) + o][Y + ky - 1][X + kx - 1]  (zero outside)  + bilinear(center[o])
+// One thread = one pixel of one output channel (grid z = nch), summed in savsr_tail_gather's order (ky, then kx); at nch = 3 the two
+// agree to rounding.
+__device__ __forceinline__ void nf_bil_src(int dst, float scale, int in_size, int& i0, int& i1, float& l1) {
+    float s = scale * ((float)dst + 0.5f) - 0.5f;                      // area_pixel_compute_source_index (F.interpolate, align_corners=False)
+    if (s < 0.f) s = 0.f;
+    i0 = (int)s;
+    if (i0 > in_size - 1) i0 = in_size - 1;
+    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
+    l1 = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
+}
+
+__global__ __launch_bounds__(256) void tail_gather_nch_kernel(const float* __restrict__ P, long long PP, int nch, const float* __restrict__ bias,
+                                                              const float* __restrict__ center, int h, int w, int H, int W, float* __restrict__ out) {
+    const int X = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int Y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int o = blockIdx.z;
+    if (X >= W || Y >= H) return;
+    float acc = 0.f;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+        const int yy = Y + ky - 1;
+        if (yy < 0 || yy >= H) continue;
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            const int xx = X + kx - 1;
+            if (xx >= 0 && xx < W) acc += P[(long long)(nch * (3 * ky + kx) + o) * PP + (long long)yy * W + xx];
+        }
+    }
+    int y0, y1, x0, x1;
+    float ly, lx;
+    nf_bil_src(Y, (float)h / (float)H, h, y0, y1, ly);
+    nf_bil_src(X, (float)w / (float)W, w, x0, x1, lx);
+    const float* c = center + (long long)o * h * w;
+    const float top = (1.f - lx) * c[y0 * w + x0] + lx * c[y0 * w + x1];
+    const float bot = (1.f - lx) * c[y1 * w + x0] + lx * c[y1 * w + x1];
+    out[(long long)o * H * W + (long long)Y * W + X] = (acc + bias[o]) + ((1.f - ly) * top + ly * bot);
 }
 
 template <int C>
@@ -332,10 +375,10 @@ int nf_lr(const savsr_satu_nf_weights* wt, const float* x, const float* st, int3
     return check_launch("satu_nf_lr_kernel");
 }
 
-template <int C>
+template <int C, int NP = 27>
 int nf_hr(const NfHrParams& p, void* stream) {
     dim3 grid((p.W + 63) / 64, (p.H + 3) / 4);
-    hipLaunchKernelGGL((satu_nf_hr_kernel<C>), grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    hipLaunchKernelGGL((satu_nf_hr_kernel<C, NP>), grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
     return check_launch("satu_nf_hr_kernel");
 }
 
@@ -370,6 +413,13 @@ extern "C" int savsr_satu_nf_lr_stage(const savsr_satu_nf_weights* wt, const flo
 extern "C" int savsr_satu_nf_hr(const savsr_satu_nf_weights* wt, const float* lrcat, int h, int w, const float* table, int n_uh, int n_uw,
                                 const int32_t* idx_h, const int32_t* idx_w, const float* ptab, const float* gyn, const float* gxn, int H, int W,
                                 float* out, int64_t out_plane, void* stream) {
+    return savsr_satu_nf_hr_planes(wt, lrcat, h, w, table, n_uh, n_uw, idx_h, idx_w, ptab, gyn, gxn, H, W, out, out_plane, 27, stream);
+}
+
+extern "C" int savsr_satu_nf_hr_planes(const savsr_satu_nf_weights* wt, const float* lrcat, int h, int w, const float* table, int n_uh, int n_uw,
+                                       const int32_t* idx_h, const int32_t* idx_w, const float* ptab, const float* gyn, const float* gxn, int H, int W,
+                                       float* out, int64_t out_plane, int planes, void* stream) {
+    if (planes != 9 && planes != 18 && planes != 27) return fail_arg("satu_nf_hr: planes (9 num_in_ch: 9, 18 or 27)");
     if (!nf_weights_ok(wt) || !lrcat || !table || !idx_h || !idx_w || !gyn || !gxn || !out) return fail_arg("satu_nf_hr: null pointer");
     if (savsr_satu_nf_lrcat_floats(wt->C) < 0) return fail_arg("satu_nf_hr: num_feat C (built for 32 and 64)");
     if (h < 2 || w < 2 || H < 1 || W < 1 || n_uh < 1 || n_uw < 1 || out_plane < (int64_t)H * W)
@@ -384,6 +434,16 @@ extern "C" int savsr_satu_nf_hr(const savsr_satu_nf_weights* wt, const float* lr
     p.wt = *wt; p.lrcat = lrcat; p.h = h; p.w = w; p.table = table; p.n_uw = n_uw; p.idx_h = idx_h; p.idx_w = idx_w;
     p.ptab = small ? nullptr : ptab;
     p.gyn = gyn; p.gxn = gxn; p.H = H; p.W = W; p.out = out; p.out_plane = out_plane;
-    if (wt->C == 32) return nf_hr<32>(p, stream);
-    return nf_hr<64>(p, stream);
+    if (wt->C == 32) return planes == 9 ? nf_hr<32, 9>(p, stream) : planes == 18 ? nf_hr<32, 18>(p, stream) : nf_hr<32, 27>(p, stream);
+    return planes == 9 ? nf_hr<64, 9>(p, stream) : planes == 18 ? nf_hr<64, 18>(p, stream) : nf_hr<64, 27>(p, stream);
+}
+
+extern "C" int savsr_tail_gather_nch(const float* planes, int64_t p_plane, int nch, const float* b, const float* center, int h, int wd, int H, int W,
+                                     float* out, void* stream) {
+    if (!planes || !b || !center || !out) return fail_arg("tail_gather_nch: null pointer");
+    if (nch < 1 || nch > 3) return fail_arg("tail_gather_nch: nch in 1 .. 3");
+    if (h < 1 || wd < 1 || H < 1 || W < 1 || p_plane < (int64_t)H * W) return fail_arg("tail_gather_nch: shape");
+    dim3 grid((W + 63) / 64, (H + 3) / 4, nch);
+    hipLaunchKernelGGL(tail_gather_nch_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), planes, (long long)p_plane, nch, b, center, h, wd, H, W, out);
+    return check_launch("tail_gather_nch_kernel");
 }

@@ -28,7 +28,7 @@ from .cache import ContextCache
 from .config import EngineConfig
 from .launch import MAX_SUM_BLOCKS, Launcher, Src, _ptr      # noqa: F401
 from .packing import (BN_EPS, CONV_TH, CONV_TW, WeightPacking, acc_row, conv_pack_geometry, conv_pack_index, conv_wy_pack_index, get_hw,      # noqa: F401  (re-exported:
-                      pack_conv_part, pack_conv_weight, pack_conv_weight_wy, satu_axis_tables, split_bf16_image)                            # tests and tools import them from here)
+                      pack_conv_part, pack_conv_weight, pack_conv_weight_wy, satu_axis_tables, split_bf16_image, window_record)                            # tests and tools import them from here)
 
 
 class HipEngine(WeightPacking, ContextCache, Launcher):
@@ -47,8 +47,11 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self.nf = cfg["num_feat"]
         if self.nf not in (32, 64):
             raise RuntimeError(self.num_feat_limit(self.nf))
-        if cfg["slid_win"] != 3 or cfg["num_in_ch"] != 3:
-            raise RuntimeError("the input-window packing is specialised for slid_win == 3, num_in_ch == 3")
+        why = self.window_limit(cfg)
+        if why is not None:
+            raise RuntimeError(why)
+        self.nch, self.sw = cfg["num_in_ch"], cfg["slid_win"]
+        self.rw = window_record(self.nch, self.sw)                 # floats per pixel of a packed input window
         self.pw: Dict[str, tuple] = {}      # conv key -> (wimage, bias, cout, cin, ks)
         self.pw_wy: Dict[str, torch.Tensor] = {}      # conv key -> Winograd-y weight image (static 3x3 convs with cout % 64 == 0)
         self.osc: Dict[str, dict] = {}      # osconv key -> tensors
@@ -86,9 +89,12 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self.use_graphs = kn.graphs
         # SATU in the row-summed tail form (savsr_satu_hr_tail_q + savsr_tail_gather_q: 9 planes + seams between the HR stage and the
         # tail instead of 27 planes); SAVSR_SATU_Q=0: the 27-plane form
-        self.satu_q = kn.satu_q and self.nf == 64
-        # num_feat != 64: the width-generic SATU (savsr_satu_nf_*, 27-plane form, records of satu_nf_rec floats); 64: the tuned kernels
-        self.satu_nf_rec = int(self.lib.savsr_satu_nf_lrcat_floats(self.nf)) if self.nf != 64 else 0
+        self.satu_q = kn.satu_q and self.nf == 64 and self.nch == 3
+        # num_feat != 64 or num_in_ch != 3: the width-generic SATU (savsr_satu_nf_*, records of satu_nf_rec floats) writing 9 num_in_ch planes
+        # (tail_planes; 27 at num_in_ch = 3); num_feat 64 with 3 channels: the tuned kernels
+        self.satu_generic = self.nf != 64 or self.nch != 3
+        self.tail_planes = 9 * self.nch
+        self.satu_nf_rec = int(self.lib.savsr_satu_nf_lrcat_floats(self.nf)) if self.satu_generic else 0
         # static-weight 3x3 convs in the Winograd F(2,3)-along-y form (SAVSR_CONV_WINOGRAD_Y); SAVSR_CONV_WY=0: the direct kernel everywhere
         self.conv_wy = kn.conv_wy
         # OSConv weight generation as ONE launch (savsr_osconv_attn_desc.fused: the routing recomputed in every aggregation workgroup; bit-identical).
@@ -116,6 +122,26 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             msg += (f"; beyond that, OSConv weight generation (savsr_osconv_weights_batch) takes cin <= 320 and hidden <= 32, and the pyramid "
                     f"fusion's OSConvs at num_feat = {nf} have cin = {5 * nf}")
         return msg
+
+    @staticmethod
+    def window_limit(cfg: dict) -> Optional[str]:
+        """Why a checkpoint of this num_in_ch / slid_win / fusion_win does not run (engine build); None when it does."""
+        nch, sw, fw = cfg["num_in_ch"], cfg["slid_win"], cfg["fusion_win"]
+        if not 1 <= nch <= 3:
+            return (f"num_in_ch = {nch} is not supported: the SATU / tail fold keeps the tail conv's 9 * num_in_ch rows inside the 32-row MFMA "
+                    f"tile of the LRcat record, so num_in_ch <= 3")
+        if sw < 3 or sw % 2 == 0:
+            return (f"slid_win = {sw} is not supported: the window is the centre frame with the same number of support frames on each side, "
+                    f"so slid_win is odd and >= 3 (at slid_win = 1 the reference builds conv_sup with 0 input channels)")
+        if nch * sw > 32:
+            return f"num_in_ch * slid_win = {nch * sw} is not supported: the packed input window holds at most 32 channels per pixel"
+        from .archs.savsr_arch import iteration_window
+        center = cfg["num_frame"] // 2 if cfg["center_frame_idx"] is None else cfg["center_frame_idx"]
+        iw = iteration_window(cfg["num_frame"], cfg["interval"], center)
+        if (iw - fw + 1) // 2 >= 1 and iw - sw + 1 < fw:
+            return (f"the pyramid level takes fusion_win = {fw} inputs but the propagation yields iter_win - slid_win + 1 = {iw - sw + 1}: "
+                    f"the reference's WindowUnit_l2.forward raises an IndexError for this configuration")
+        return None
 
     NB_MAX = 4                  # (class default; the instance reads the library's batch limits: 24 convs / 8 OSConvs per launch => 4 clips)
 
@@ -146,6 +172,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         in flight on two HIP streams."""
         e = HipEngine.__new__(HipEngine)
         e.lib, e.dev, e.cfg, e.nf = self.lib, self.dev, self.cfg, self.nf
+        e.nch, e.sw, e.rw, e.satu_generic, e.tail_planes = self.nch, self.sw, self.rw, self.satu_generic, self.tail_planes
         e.knobs = self.knobs
         e.NB_MAX = self.NB_MAX
         e.pw, e.se, e._keep = self.pw, self.se, self._keep
@@ -278,12 +305,12 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
     # ------------------------------------------------------------------ diagnostics
     def time_satu_parts(self, lq: torch.Tensor, scale, timer) -> dict:
         """Diagnostics (tools/scale_sweep.py, bench.py): the SATU LR / HR launches and the tail of the product path, each timed
-        alone by `timer(fn) -> us` on the tensors of a real frame.  lq: [T, 3, h, w] on the device."""
+        alone by `timer(fn) -> us` on the tensors of a real frame.  lq: [T, num_in_ch, h, w] on the device."""
         lq = lq.contiguous()
         self._select(lq.shape, scale)
         c = self._stage_body(lq, scale)
-        out = torch.empty(3, c["H"], c["W"], device=self.dev)
-        if self.nf != 64:
+        out = torch.empty(self.nch, c["H"], c["W"], device=self.dev)
+        if self.satu_generic:
             lrcat = self.satu_nf_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"])
             self._stage_satu(c, scale)
             return {"satu_lr_us": timer(lambda: self.satu_nf_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"])),
@@ -304,15 +331,15 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             return self._stage_body_impl(lq, scale)
 
     def _stage_body_impl(self, lq: torch.Tensor, scale) -> dict:
-        """Everything up to the SATU inputs (savsr_arch.py:692-734).  lq: [T, 3, h, w] on device."""
+        """Everything up to the SATU inputs (savsr_arch.py:692-734).  lq: [T, num_in_ch, h, w] on device."""
         cfg, nf = self.cfg, self.nf
-        if lq.dim() == 5:          # [nb, T, 3, h, w]: nb clips of one (shape, scale) in one launch sequence (see `nb`)
+        if lq.dim() == 5:          # [nb, T, num_in_ch, h, w]: nb clips of one (shape, scale) in one launch sequence (see `nb`)
             assert lq.shape[0] == self.nb and lq.is_contiguous() and cfg["interval"] == 0
         else:
             assert self.nb == 1
         T, cin, h_in, w_in = lq.shape[-4:]
         clip_bytes = 4 * T * cin * h_in * w_in
-        assert T == cfg["num_frame"] and cin == cfg["num_in_ch"] == 3
+        assert T == cfg["num_frame"] and cin == cfg["num_in_ch"] == self.nch
         if self.census is not None:
             k = "frames_tp" if self.conv_algo == _lib.CONV_DIRECT_THROUGHPUT else "frames_b1"
             self.census[k] = self.census.get(k, 0) + self.nb
@@ -321,11 +348,13 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         hp, wp = h_in + (h_in & 1), w_in + (w_in & 1)              # pad_spatial to even (savsr_arch.py:670-690)
         st = self._stream()
         sw, fw = cfg["slid_win"], cfg["fusion_win"]
+        rw = self.rw
         if cfg["interval"] == 0:
-            wins = self.buf("windows", T - 2, hp, wp, 16)
+            wins = self.buf("windows", T - sw + 1, hp, wp, rw)
             for b in range(self.nb):
-                _lib.check(self.lib.savsr_pack_windows(lq.data_ptr() + b * clip_bytes, wins.data_ptr() + b * self._bs(wins), T, h_in, w_in, hp, wp, st), "savsr_pack_windows")
-            win_b = win_f = lambda t: Src(wins, 16, 16, 0, float_off=(t - 1) * hp * wp * 16, bs=self._bs(wins))
+                self._pack_windows(lq.data_ptr() + b * clip_bytes, wins.data_ptr() + b * self._bs(wins), T, h_in, w_in, hp, wp, st)
+            # window q is centred at frame t = q + sw // 2
+            win_b = win_f = lambda t: Src(wins, rw, rw, 0, float_off=(t - sw // 2) * hp * wp * rw, bs=self._bs(wins))
             T = self.iter_win
         else:
             # frame_sample (:638-659, :699): each direction walks its own sub-sequence of the clip -- gathered (a device copy of
@@ -333,14 +362,14 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             T = self.iter_win
             packs = []
             for tag, idx in (("f", self.fwd_idx), ("b", self.bwd_idx)):
-                sel = self.buf("frames_" + tag, T, 3, h_in, w_in)
+                sel = self.buf("frames_" + tag, T, cin, h_in, w_in)
                 for k, fi in enumerate(idx[:T]):
                     sel[k].copy_(lq[fi])
-                wb = self.buf("windows_" + tag, T - 2, hp, wp, 16)
-                _lib.check(self.lib.savsr_pack_windows(sel.data_ptr(), wb.data_ptr(), T, h_in, w_in, hp, wp, st), "savsr_pack_windows")
+                wb = self.buf("windows_" + tag, T - sw + 1, hp, wp, rw)
+                self._pack_windows(sel.data_ptr(), wb.data_ptr(), T, h_in, w_in, hp, wp, st)
                 packs.append(wb)
-            win_f = lambda t, wb=packs[0]: Src(wb, 16, 16, 0, float_off=(t - 1) * hp * wp * 16)
-            win_b = lambda t, wb=packs[1]: Src(wb, 16, 16, 0, float_off=(t - 1) * hp * wp * 16)
+            win_f = lambda t, wb=packs[0]: Src(wb, rw, rw, 0, float_off=(t - sw // 2) * hp * wp * rw)
+            win_b = lambda t, wb=packs[1]: Src(wb, rw, rw, 0, float_off=(t - sw // 2) * hp * wp * rw)
         steps = T - sw + 1
         zero = self.buf("zero", hp, wp, nf)
         if self.nb == 1:
@@ -395,16 +424,25 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             d["q9"] = self.sbuf("satu.q9", 9, plane)
             d["seam"] = self.sbuf("satu.seam", self.seam_floats(H, W))
         else:                # (the 27 planes -- 99.5 MB at 720x1280 -- exist only in the 27-plane form; taps allocate them on demand)
-            d["p27"] = self.sbuf("satu.p27", _lib.TAIL_PLANES, plane)
+            d["p27"] = self.sbuf("satu.p27", self.tail_planes, plane)      # (9 num_in_ch planes of the width-generic form)
         return d
+
+    def _pack_windows(self, lq_ptr: int, out_ptr: int, T: int, h: int, w: int, hp: int, wp: int, st: int) -> None:
+        """Input windows of one clip (savsr_arch.py:448-454, :661-668, :670-690): the shipped 3-channel, 3-frame form through its own
+        kernel, every other num_in_ch / slid_win through savsr_pack_windows_nch."""
+        if self.nch == 3 and self.sw == 3:
+            _lib.check(self.lib.savsr_pack_windows(lq_ptr, out_ptr, T, h, w, hp, wp, st), "savsr_pack_windows")
+        else:
+            _lib.check(self.lib.savsr_pack_windows_nch(lq_ptr, out_ptr, T, self.nch, self.sw, h, w, hp, wp, st), "savsr_pack_windows_nch")
 
     def _stage_satu(self, c: dict, scale):
         with HipEngine._StageStream(self):
             return self._stage_satu_impl(c, scale)
 
     def _stage_satu_impl(self, c: dict, scale):
-        """SATU in the tail-projected form (savsr_arch.py:315-376 with the channel contraction of :738 folded in): -> P [27][H][W]."""
-        if self.nf != 64:              # the width-generic kernels (27-plane form)
+        """SATU in the tail-projected form (savsr_arch.py:315-376 with the channel contraction of :738 folded in): -> P [27][H][W]
+        (the width-generic form: [9 num_in_ch][H][W])."""
+        if self.satu_generic:          # the width-generic kernels
             for b in range(self.nb):
                 lrcat = self.satu_nf_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], b=b)
                 self.satu_nf_hr(lrcat, c["h"], c["w"], scale, c["p27"], c["plane"], b=b)
@@ -423,12 +461,17 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
 
     def _stage_tail_impl(self, c: dict, lq: torch.Tensor, out: torch.Tensor):
         """What is left of :738-739: the nine shifted taps per colour, the tail bias, the bilinear residual."""
-        cfg = self.cfg
+        cfg, nch = self.cfg, self.nch
         T = lq.shape[-4]
         center = T // 2 if cfg["center_frame_idx"] is None else cfg["center_frame_idx"]
-        clip_bytes, out_bytes = 4 * T * 3 * c["h"] * c["w"], 4 * 3 * c["H"] * c["W"]      # (lq [nb, T, 3, h, w] and out [nb, 3, H, W] are contiguous)
+        # (lq [nb, T, nch, h, w] and out [nb, nch, H, W] are contiguous)
+        clip_bytes, out_bytes = 4 * T * nch * c["h"] * c["w"], 4 * nch * c["H"] * c["W"]
         for b in range(self.nb):
-            cptr = lq.data_ptr() + b * clip_bytes + 4 * center * 3 * c["h"] * c["w"]    # unpadded centre frame (:696)
+            cptr = lq.data_ptr() + b * clip_bytes + 4 * center * nch * c["h"] * c["w"]    # unpadded centre frame (:696)
+            if nch != 3:           # the 9 nch planes of the width-generic HR stage
+                _lib.check(self.lib.savsr_tail_gather_nch(c["p27"].data_ptr() + b * self._bs(c["p27"]), c["plane"], nch, self.tail_b.data_ptr(), cptr,
+                                                          c["h"], c["w"], c["H"], c["W"], out.data_ptr() + b * out_bytes, self._stream()), "savsr_tail_gather_nch")
+                continue
             if self.satu_q:
                 _lib.check(self.lib.savsr_tail_gather_q(c["q9"].data_ptr() + b * self._bs(c["q9"]), c["plane"], c["seam"].data_ptr() + b * self._bs(c["seam"]),
                                                         c["seam"].numel(), self.tail_b.data_ptr(), cptr,
@@ -444,8 +487,8 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         return o[:, : c["H"] * c["W"]].view(self.nf, c["H"], c["W"])
 
     def forward_one(self, lq: torch.Tensor, scale, out: torch.Tensor, taps: Optional[dict] = None):
-        """Eager launch sequence.  lq: [T, 3, h, w] fp32 contiguous on device; out: [3, H, W] (or [nb, T, 3, h, w] -> [nb, 3, H, W]: nb clips
-        of one (shape, scale) in one launch sequence)."""
+        """Eager launch sequence.  lq: [T, c, h, w] fp32 contiguous on device (c = num_in_ch); out: [c, H, W] (or [nb, T, c, h, w] ->
+        [nb, c, H, W]: nb clips of one (shape, scale) in one launch sequence)."""
         self.nb = int(lq.shape[0]) if lq.dim() == 5 else 1
         assert self.nb <= self.NB_MAX and (self.nb == 1 or taps is None)
         try:
@@ -470,12 +513,12 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         if taps is not None:                    # channel-last [hp][wp][64] tensors; SATU output planar
             taps["align_feat"] = c["align"].t
             taps["h_feat"] = c["hfeat"].t
-            if self.nf == 64:               # (STAUpsample's own output: a tap of the tuned 64-wide kernels only; other widths leave it out)
+            if not self.satu_generic:       # (STAUpsample's own output: a tap of the tuned 64-wide kernels only; the generic form leaves it out)
                 taps["satu"] = self._satu_standalone(c, scale)
             if self.satu_q:     # the 27-plane form beside the row-summed one the frame runs (taps only)
                 c["p27"] = self.sbuf("satu.p27", _lib.TAIL_PLANES, c["plane"])
                 self.satu_hr(self.satu_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], tail_form=True), c["h"], c["w"], scale, c["p27"], c["plane"], tail_form=True)
-            taps["p27"] = c["p27"][:, : c["H"] * c["W"]].view(_lib.TAIL_PLANES, c["H"], c["W"])
+            taps["p27"] = c["p27"][:, : c["H"] * c["W"]].view(-1, c["H"], c["W"])      # (9 num_in_ch planes)
         self._stage_tail(c, lq, out)
         return out
 
@@ -487,7 +530,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         SAVSR_CONV_DIRECT_THROUGHPUT -- the direct kernel's results bit for bit, its own captured graphs.  (Round 4: a launch's conv FORM --
         direct or Winograd-y -- depends on its tile count and on this mode (conv_launch), so a frame in throughput mode can differ from the
         one-clip flow by the two forms' rounding, ~1e-5; each mode is bitwise reproducible.)
-        lq [nb, T, 3, h, w] / out [nb, 3, H, W]: nb clips of one (shape, scale) in ONE launch sequence (see `nb`), its own context and graphs."""
+        lq [nb, T, c, h, w] / out [nb, c, H, W]: nb clips of one (shape, scale) in ONE launch sequence (see `nb`), its own context and graphs."""
         self.nb = int(lq.shape[0]) if lq.dim() == 5 else 1
         assert self.nb <= self.NB_MAX
         try:
@@ -529,8 +572,8 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             h_, w_ = int(lq.shape[-2]), int(lq.shape[-1])
             H_, W_ = get_hw(h_, w_, scale)
             plane_ = self.hr_plane(H_, W_)
-            if self.nf != 64:      # (no plan to measure: this evaluates the tables outside the capture)
-                self.satu_nf_hr(self.buf("satu.lrcat_nf", h_, w_, self.satu_nf_rec), h_, w_, scale, self.sbuf("satu.p27", _lib.TAIL_PLANES, plane_), plane_)
+            if self.satu_generic:  # (no plan to measure: this evaluates the tables outside the capture)
+                self.satu_nf_hr(self.buf("satu.lrcat_nf", h_, w_, self.satu_nf_rec), h_, w_, scale, self.sbuf("satu.p27", self.tail_planes, plane_), plane_)
             elif self.satu_q:
                 self.satu_hr(self.buf("satu.lrcat_tailq", h_, w_, _lib.SATU_LRCAT_TAIL), h_, w_, scale, self.sbuf("satu.q9", 9, plane_), plane_,
                              tail_form=True, seam=self.sbuf("satu.seam", self.seam_floats(H_, W_)))
@@ -626,8 +669,8 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         return [self] + self._siblings
 
     def forward_many(self, items) -> List[torch.Tensor]:
-        """A stream of independent clips of MIXED shapes / scales (BASELINE config 5): items = [(lq [T, 3, h, w], (sh, sw))] ->
-        [out [3, H, W]].  Clip i runs on HIP stream i % n_streams with that stream's sibling engine, so small clips (whose ~360
+        """A stream of independent clips of MIXED shapes / scales (BASELINE config 5): items = [(lq [T, c, h, w], (sh, sw))] ->
+        [out [c, H, W]] (c = num_in_ch).  Clip i runs on HIP stream i % n_streams with that stream's sibling engine, so small clips (whose ~360
         launches are latency-bound) overlap.  Every clip's result is that of the throughput flow (`_set_flow`) whatever
         the grouping: forward_many(items)[i] == forward_many([items[i]])[0] bit for bit; against the one-clip latency flow of `forward` it
         agrees to the conv forms' rounding (~1e-5) where a launch takes another form."""
@@ -635,7 +678,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             outs = []
             for lq, sc in items:
                 lq = lq.to(torch.float32).contiguous()
-                o = torch.empty((3,) + get_hw(lq.shape[-2], lq.shape[-1], sc), device=self.dev, dtype=torch.float32)
+                o = torch.empty((self.nch,) + get_hw(lq.shape[-2], lq.shape[-1], sc), device=self.dev, dtype=torch.float32)
                 self._set_flow(lq, True)
                 outs.append(self.forward_one(lq, sc, o))
             return outs
@@ -678,11 +721,11 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             with torch.cuda.stream(self._streams[k]):
                 if len(unit) == 1:
                     i = unit[0]
-                    outs[i] = torch.empty(3, H, W, device=self.dev, dtype=torch.float32)
+                    outs[i] = torch.empty(self.nch, H, W, device=self.dev, dtype=torch.float32)
                     engines[k]._forward_graphed(items[i][0].to(torch.float32).contiguous(), sc, outs[i], throughput=True)
                 else:
                     lqb = torch.stack([items[i][0].to(torch.float32) for i in unit], 0)
-                    outb = torch.empty(len(unit), 3, H, W, device=self.dev, dtype=torch.float32)
+                    outb = torch.empty(len(unit), self.nch, H, W, device=self.dev, dtype=torch.float32)
                     engines[k]._forward_graphed(lqb, sc, outb, throughput=True)
                     for j, i in enumerate(unit):
                         outs[i] = outb[j]
@@ -693,13 +736,15 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         return outs
 
     def forward(self, lq: torch.Tensor, scale, taps: Optional[dict] = None) -> torch.Tensor:
-        """lq: [b, T, 3, h, w] -> [b, 3, H, W] (savsr_arch.py:692-742)."""
+        """lq: [b, T, c, h, w] -> [b, c, H, W], c = num_in_ch (savsr_arch.py:692-742)."""
         if lq.device != self.dev:
             raise RuntimeError(f"input on {lq.device}, engine on {self.dev}")
         lq = lq.to(torch.float32).contiguous()
-        b, _, _, h, w = lq.shape
+        b, t, c, h, w = lq.shape
+        if t != self.cfg["num_frame"] or c != self.nch:
+            raise ValueError(f"expected lq [b, {self.cfg['num_frame']}, {self.nch}, h, w] (num_frame, num_in_ch), got {tuple(lq.shape)}")
         H, W = get_hw(h, w, scale)
-        out = torch.empty(b, 3, H, W, device=self.dev, dtype=torch.float32)
+        out = torch.empty(b, self.nch, H, W, device=self.dev, dtype=torch.float32)
         if b >= 2 and self.n_streams >= 2 and self.use_graphs and taps is None:
             # clips are independent (no cross-clip state, savsr_arch.py:705-706): keep n_streams of them in flight
             # on separate HIP streams so one clip's load/store-bound kernel phases overlap another's MFMA phases

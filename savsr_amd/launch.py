@@ -456,13 +456,17 @@ class Launcher:
         return lrcat
 
     def satu_nf_hr(self, lrcat: torch.Tensor, h: int, w: int, scale, out: torch.Tensor, out_plane: Optional[int] = None, b: int = 0):
-        """HR stage of the width-generic SATU (savsr_satu_nf_hr) -> the 27 tail-projected planes P, out_plane floats apart."""
+        """HR stage of the width-generic SATU -> the tail-projected planes P, out_plane floats apart: 27 (savsr_satu_nf_hr) at num_in_ch = 3,
+        the 9 num_in_ch live ones (savsr_satu_nf_hr_planes) otherwise."""
         ax = self.satu_axes(h, w, scale)
         plane = out_plane if out_plane is not None else ax["H"] * ax["W"]
-        _lib.check(self.lib.savsr_satu_nf_hr(C.byref(self.satu_nf_w), lrcat.data_ptr() + b * self._bs(lrcat), h, w, ax["table"].data_ptr(),
-                                             ax["n_uh"], ax["n_uw"], ax["ih"].data_ptr(), ax["iw"].data_ptr(), _ptr(ax["ptab"]),
-                                             ax["gyn"].data_ptr(), ax["gxn"].data_ptr(), ax["H"], ax["W"], out.data_ptr() + b * self._bs(out), plane,
-                                             self._stream()), "savsr_satu_nf_hr")
+        args = (C.byref(self.satu_nf_w), lrcat.data_ptr() + b * self._bs(lrcat), h, w, ax["table"].data_ptr(),
+                ax["n_uh"], ax["n_uw"], ax["ih"].data_ptr(), ax["iw"].data_ptr(), _ptr(ax["ptab"]),
+                ax["gyn"].data_ptr(), ax["gxn"].data_ptr(), ax["H"], ax["W"], out.data_ptr() + b * self._bs(out), plane)
+        if self.tail_planes == _lib.TAIL_PLANES:
+            _lib.check(self.lib.savsr_satu_nf_hr(*args, self._stream()), "savsr_satu_nf_hr")
+        else:
+            _lib.check(self.lib.savsr_satu_nf_hr_planes(*args, self.tail_planes, self._stream()), "savsr_satu_nf_hr_planes")
         return out
 
     def satu(self, x: Src, st: Src, row_px: int, h: int, w: int, scale, out: torch.Tensor, out_plane: Optional[int] = None):

@@ -74,6 +74,11 @@ class VideoBaseModel(BaseModel):
         super().__init__(opt)
         if self.is_train:
             raise NotImplementedError("savsr_amd implements the test flow only (is_train: false)")
+        nch = opt["network_g"].get("num_in_ch", 3)
+        if nch != 3:
+            raise NotImplementedError(f"network_g num_in_ch = {nch}: the reference's test pipeline reads 3-channel (RGB) frames and computes "
+                                      f"its metrics on them, so {nch}-channel metrics are not supported; run such a checkpoint through the "
+                                      f"Python module (SAVSR.forward / forward_many)")
         self.net_g = build_network(opt["network_g"]).eval()
         load_path = opt["path"].get("pretrain_network_g")
         if load_path is not None:                                     # sr_model.py:36-39

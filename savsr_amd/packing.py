@@ -169,15 +169,26 @@ def acc_row(r: int, half: int) -> int:
     return (r & 3) + 8 * (r >> 2) + 4 * half
 
 
-def tail_rows27(sd, c: int, row_of=lambda ky, kx, o: 3 * (3 * ky + kx) + o) -> np.ndarray:
-    """Wt27 [32][c] (float64): the 3x3 tail conv's weights (savsr_arch.py:738) regrouped by output row p = row_of(ky, kx, o); rows 27 .. 31 zero."""
-    tw = sd["tail.weight"].to("cpu", torch.float64).numpy()                          # [3 o][c][3 ky][3 kx]
+def tail_rows27(sd, c: int, row_of=None) -> np.ndarray:
+    """Wt27 [32][c] (float64): the 3x3 tail conv's weights (savsr_arch.py:738, c -> nch = num_in_ch outputs) regrouped by output row
+    p = row_of(ky, kx, o), by default nch (3 ky + kx) + o; rows 9 nch .. 31 zero (27 .. 31 for the shipped nch = 3)."""
+    tw = sd["tail.weight"].to("cpu", torch.float64).numpy()                          # [nch o][c][3 ky][3 kx]
+    nch = tw.shape[0]
+    if nch > 3:
+        raise ValueError(f"num_in_ch = {nch}: the 9 num_in_ch tail rows must fit the 32-row MFMA tile of the LRcat record (num_in_ch <= 3)")
+    if row_of is None:
+        row_of = lambda ky, kx, o: nch * (3 * ky + kx) + o      # noqa: E731
     wt27 = np.zeros((32, c), dtype=np.float64)
     for ky in range(3):
         for kx in range(3):
-            for o in range(3):
+            for o in range(nch):
                 wt27[row_of(ky, kx, o)] = tw[o, :, ky, kx]
     return wt27
+
+
+def window_record(nch: int, sw: int) -> int:
+    """Floats per pixel of a packed input window (savsr_pack_windows_nch): nch * sw live channels rounded up to 16 or 32."""
+    return 16 if nch * sw <= 16 else 32
 
 
 def fold_satu_nf(sd, c: int) -> Dict[str, np.ndarray]:
@@ -198,6 +209,19 @@ def fold_satu_nf(sd, c: int) -> Dict[str, np.ndarray]:
     return dict(kconv=g("kernel_conv.0.weight").reshape(25 * c, c), kconv_b=g("kernel_conv.0.bias"),
                 ta=wt27 @ wa, tb=tb, cstack=g("weight_compress").reshape(c // 2, c),
                 wbe=np.einsum("pc,ncj->njp", tb, expd), fb=wt27 @ g("fusion.bias"))
+
+
+def fuse_window_conv(sd, d: str, nch: int, sw: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """conv_c (nch -> nf) and conv_sup (nch (sw - 1) -> nf) of one direction fused into one RW -> 2 nf conv over the packed window
+    tensor (channels: frame t | the support frames in sup_index order | zeros; RW = window_record), savsr_arch.py:429-431,456-457.
+    (nch = 3, sw = 3: the 16 -> 128 conv over frame t | t-1 | t+1 | zeros.)"""
+    wc, bc = sd[d + ".conv_c.weight"].cpu().float(), sd[d + ".conv_c.bias"].cpu().float()
+    ws, bs = sd[d + ".conv_sup.weight"].cpu().float(), sd[d + ".conv_sup.bias"].cpu().float()
+    nf = wc.shape[0]
+    w = torch.zeros(2 * nf, window_record(nch, sw), 3, 3)
+    w[:nf, 0:nch] = wc
+    w[nf:, nch:nch * sw] = ws
+    return w, torch.cat([bc, bs])
 
 
 class WeightPacking:
@@ -247,15 +271,7 @@ class WeightPacking:
         self._register(key, wp, bp)
 
     def _add_window_conv(self, sd, d: str):
-        """conv_c (3->64) and conv_sup (6->64) of one direction fused into a 16 -> 128 conv over
-        the packed window tensor (channels: frame t | t-1 | t+1 | zeros), savsr_arch.py:429-431,456-457."""
-        nf = self.nf
-        wc, bc = sd[d + ".conv_c.weight"].cpu().float(), sd[d + ".conv_c.bias"].cpu().float()
-        ws, bs = sd[d + ".conv_sup.weight"].cpu().float(), sd[d + ".conv_sup.bias"].cpu().float()
-        w = torch.zeros(2 * nf, 16, 3, 3)
-        w[:nf, 0:3] = wc
-        w[nf:, 3:9] = ws
-        self._register(d + ".win", w, torch.cat([bc, bs]))
+        self._register(d + ".win", *fuse_window_conv(sd, d, self.cfg["num_in_ch"], self.cfg["slid_win"]))
 
     def _add_osconv(self, sd, key: str):
         bank = sd[key + ".weight"].to(self.dev, torch.float32)    # [K, cout, cin, 3, 3]
@@ -348,8 +364,8 @@ class WeightPacking:
         p = "upsample."
         c = self.nf
         f32 = torch.float32
-        if c != 64:
-            # the width-generic SATU; the phase table's weights (savsr_satu_phase_table reads the body / head pointers only) travel in a
+        if c != 64 or self.cfg["num_in_ch"] != 3:
+            # the width-generic SATU (num_feat 32, or any num_in_ch != 3: Wt with 9 num_in_ch live rows); the phase table's weights (savsr_satu_phase_table reads the body / head pointers only) travel in a
             # savsr_satu_weights whose other pointers name the generic form's tensors
             self._pack_satu_nf(sd, c)
             self.satu_t = self._pack_satu_heads(sd)
@@ -360,7 +376,7 @@ class WeightPacking:
                 setattr(sw, k, self.satu_nf_t[v].data_ptr())
             self.satu_w = sw
             self.satu_tail_t, self.satu_w_tail, self.satu_tailq_t, self.satu_w_tailq = None, None, None, None      # (the tuned 64-wide forms)
-            self.tail_w = self._dev(sd["tail.weight"].reshape(3, c * 9))
+            self.tail_w = self._dev(sd["tail.weight"].reshape(-1, c * 9))
             self.tail_b = self._dev(sd["tail.bias"])
             return
         self.satu_nf_t, self.satu_nf_w = None, None
