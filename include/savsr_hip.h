@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 30
+#define SAVSR_ABI_VERSION 31
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -390,6 +390,23 @@ int savsr_tail_gather_nch(const float* planes, int64_t p_plane, int nch, const f
  * out: [3][H][W] contiguous. */
 int savsr_tail_residual(const float* feat, int64_t feat_plane, const float* tail_w /* [3][64][3][3] */, const float* tail_b,
                         const float* center, int h, int w, int H, int W, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 31) The sequence path's conversions (video.hip; SAVSR.upscale_video).  Not fused into the SATU / tail
+ * kernels.  The slot -> frame list `idx` is a HOST array of n_idx int32 (1 .. SAVSR_VIDEO_MAX_SLOTS), copied into the kernel
+ * arguments when the call enqueues: nb windows of num_frame frames each, in clip order (generate_frame_indices,
+ * lbasicsr/data/data_util.py:63-112).  Every index must lie in [0, n_frames).
+ * savsr_video_gather_u8:  frames [n_frames][h][w][c] uint8 (c = 1 .. 3 interleaved channels) -> out [n_idx][c][h][w] fp32, slot k =
+ *                         frame idx[k] / 255 -- bit for bit numpy's float32(u8) / 255.0 (read_img_seq / img2tensor, data_util.py:29-60)
+ *                         through a 256-entry table the compiler evaluates.  One pass: each byte is read once per slot that names it.
+ * savsr_video_gather_f32: frames [n_frames][c][h][w] fp32 -> out [n_idx][c][h][w], a copy of frame idx[k] per slot.
+ * savsr_video_quantize_u8: in [n][c][H][W] fp32 contiguous -> out [n][H][W][c] uint8: clamp(0, 1), x 255.0f, rintf (round half to
+ *                         even) -- tensor2img(x, rgb2bgr=False), lbasicsr/utils/img_util.py:66-90.  16-byte stores when H * W % 16 == 0
+ *                         and both pointers are 16-byte aligned. */
+#define SAVSR_VIDEO_MAX_SLOTS 64
+int savsr_video_gather_u8(const uint8_t* frames, int n_frames, int c, int h, int w, const int32_t* idx, int n_idx, float* out, void* stream);
+int savsr_video_gather_f32(const float* frames, int n_frames, int c, int h, int w, const int32_t* idx, int n_idx, float* out, void* stream);
+int savsr_video_quantize_u8(const float* in, int n, int c, int H, int W, uint8_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * PSNR-Y / SSIM-Y of one output frame with the reference's numerics (SURVEY section 8, row f3 -- the step after the

@@ -256,6 +256,15 @@ class SAVSR(nn.Module):
         with torch.no_grad():
             return self.engine().forward_many(list(zip(clips, [tuple(s) if not isinstance(s, (int, float)) else (s, s) for s in scales])))
 
+    def upscale_video(self, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float") -> torch.Tensor:
+        """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
+        (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
+        reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
+        Returns [N, c, H, W] fp32, or with out="uint8" [N, H, W, c] uint8 = tensor2img(frame, rgb2bgr=False) of each fp32 frame.
+        Arguments are checked before anything runs on the GPU.  Streaming form: savsr_amd.VideoUpscaler."""
+        from ..video import upscale_video
+        return upscale_video(self, frames, scale, padding, out)
+
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:
             raise RuntimeError("savsr_amd.SAVSR implements the inference path only; call .eval() first")

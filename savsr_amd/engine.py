@@ -735,6 +735,72 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             o.record_stream(cur)       # allocated under a side stream, handed to the caller's: its block is not recycled on the side stream while `cur` still reads it
         return outs
 
+    def forward_video(self, frames: torch.Tensor, windows: List[List[int]], scale, out_u8: bool = False) -> torch.Tensor:
+        """The sequence path (SAVSR.upscale_video): frames [N, h, w, c] uint8 or [N, c, h, w] fp32 on the device, windows[i] = the
+        num_frame frame indices of output frame i in clip order (harness.window_indices) -> [len(windows), c, H, W] fp32, or
+        [len(windows), H, W, c] uint8 (out_u8: tensor2img(x, rgb2bgr=False) per frame, savsr_video_quantize_u8).
+        Launch units and streams are forward_many's (up to `clip_batch` consecutive windows per unit where the LR frame is eligible,
+        balanced; units dealt round-robin over `streams_for` streams; throughput flow), so frame i equals forward_many on the gathered
+        window i bit for bit.  A unit's windows are gathered from `frames` by savsr_video_gather_u8 / _f32 into a unit-sized fp32 clip
+        batch on the unit's stream; nothing is gathered or converted on the host."""
+        if frames.device != self.dev:
+            raise RuntimeError(f"input on {frames.device}, engine on {self.dev}")
+        u8 = frames.dtype == torch.uint8
+        frames = frames.contiguous() if u8 else frames.to(torch.float32).contiguous()
+        N = int(frames.shape[0])
+        h, w, c = (int(v) for v in frames.shape[1:]) if u8 else (int(frames.shape[2]), int(frames.shape[3]), int(frames.shape[1]))
+        T = self.cfg["num_frame"]
+        if c != self.nch:
+            raise ValueError(f"frames have {c} channels, the network num_in_ch = {self.nch}")
+        for win in windows:
+            if len(win) != T or min(win) < 0 or max(win) >= N:
+                raise ValueError(f"window {win}: {T} indices in [0, {N}) expected")
+        H, W = get_hw(h, w, scale)
+        n = len(windows)
+        out = (torch.empty(n, H, W, c, device=self.dev, dtype=torch.uint8) if out_u8 else
+               torch.empty(n, c, H, W, device=self.dev, dtype=torch.float32))
+        if n == 0:
+            return out
+        if T > _lib.VIDEO_MAX_SLOTS:
+            raise ValueError(f"num_frame = {T}: the window gather takes at most {_lib.VIDEO_MAX_SLOTS} frames per launch")
+        cb = self.clip_batch if (self.use_graphs and self.cfg["interval"] == 0 and h * w <= self.clip_batch_max_px) else 1
+        cb = max(1, min(cb, _lib.VIDEO_MAX_SLOTS // T))
+        k_units = -(-n // cb)
+        base, rem = n // k_units, n % k_units
+        units, a = [], 0
+        for u in range(k_units):             # balanced, as forward_many's (10 windows -> 3 + 3 + 2 + 2)
+            m = base + (1 if u < rem else 0)
+            units.append((a, a + m))
+            a += m
+        ns = min(self.streams_for(h * w), len(units)) if self.use_graphs else 1
+        engines = self._ensure_streams(ns)
+        cur = torch.cuda.current_stream()
+        for k in range(ns):
+            self._streams[k].wait_stream(cur)
+        gather = self.lib.savsr_video_gather_u8 if u8 else self.lib.savsr_video_gather_f32
+        for u, (i0, i1) in enumerate(units):
+            k = u % ns
+            st = self._streams[k]
+            nb = i1 - i0
+            idx = [f for win in windows[i0:i1] for f in win]
+            with torch.cuda.stream(st):
+                lqb = torch.empty(nb, T, c, h, w, device=self.dev, dtype=torch.float32)
+                _lib.check(gather(frames.data_ptr(), N, c, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), lqb.data_ptr(), st.cuda_stream),
+                           "savsr_video_gather")
+                o = torch.empty(nb, c, H, W, device=self.dev, dtype=torch.float32) if out_u8 else out[i0:i1]
+                lq_u, o_u = (lqb[0], o[0]) if nb == 1 else (lqb, o)
+                if self.use_graphs:
+                    engines[k]._forward_graphed(lq_u, scale, o_u, throughput=True)
+                else:                          # SAVSR_GRAPHS=0 (diagnostics): forward_many's eager flow, one window at a time
+                    self._set_flow(lq_u, True)
+                    self.forward_one(lq_u, scale, o_u)
+                if out_u8:
+                    _lib.check(self.lib.savsr_video_quantize_u8(o.data_ptr(), nb, c, H, W, out[i0:i1].data_ptr(), st.cuda_stream),
+                               "savsr_video_quantize_u8")
+        for k in range(ns):
+            cur.wait_stream(self._streams[k])
+        return out
+
     def forward(self, lq: torch.Tensor, scale, taps: Optional[dict] = None) -> torch.Tensor:
         """lq: [b, T, c, h, w] -> [b, c, H, W], c = num_in_ch (savsr_arch.py:692-742)."""
         if lq.device != self.dev:

@@ -1,0 +1,209 @@
+"""Whole LR videos in, SR videos out: the sequence path behind `SAVSR.upscale_video` and `VideoUpscaler`.
+
+Output frame i is what the reference pipeline gives for it: the frame's window by generate_frame_indices with the chosen padding
+(lbasicsr/data/data_util.py:63-112, `harness.window_indices`), then SAVSR.forward on that window; with out="uint8", tensor2img's
+clamp / x255 / round half to even (lbasicsr/utils/img_util.py:66-90) without the BGR swap.  The frames stay on the device: the
+windows are gathered there (savsr_video_gather_u8 / _f32) and the uint8 result is quantised there (savsr_video_quantize_u8), see
+HipEngine.forward_video.
+
+Every argument is checked here, on the host, before anything is enqueued on the GPU.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Tuple
+
+import torch
+
+from .harness import window_indices
+
+PADDING_MODES = ("replicate", "reflection", "reflection_circle", "circle")
+OUT_KINDS = ("float", "uint8")
+
+
+def as_scale(scale) -> Tuple[float, float]:
+    """A float (symmetric) or an (sh, sw) pair -> (sh, sw) floats."""
+    if isinstance(scale, (int, float)) and not isinstance(scale, bool):
+        sc = (float(scale), float(scale))
+    else:
+        try:
+            sh, sw = scale
+            sc = (float(sh), float(sw))
+        except (TypeError, ValueError):
+            raise ValueError(f"scale must be a number or an (sh, sw) pair, got {scale!r}") from None
+    if not (sc[0] > 0 and sc[1] > 0):
+        raise ValueError(f"scale must be positive, got {sc}")
+    return sc
+
+
+def check_padding(padding: str) -> None:
+    if padding not in PADDING_MODES:
+        raise ValueError(f"padding = {padding!r} is not a mode of generate_frame_indices: one of {', '.join(PADDING_MODES)}")
+
+
+def check_length(n: int, num_frame: int, padding: str) -> None:
+    """Every frame's window lies inside the video (the refusal of datasets.py for a too-short folder, in the same words)."""
+    if n < 1:
+        raise ValueError("the video has no frames")
+    for i in range(n):
+        win = window_indices(i, n, num_frame, padding)
+        if min(win) < 0 or max(win) >= n:
+            raise ValueError(f"video has {n} frames: too few for a {num_frame}-frame '{padding}' window")
+
+
+def frame_layout(frames: torch.Tensor, nch: int) -> Tuple[int, int, int]:
+    """(N, h, w) of a video tensor: [N, h, w, c] uint8 (GPU or host) or [N, c, h, w] float on the GPU; refuses anything else."""
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError(f"frames must be a torch.Tensor, got {type(frames).__name__}")
+    if frames.dim() != 4:
+        raise ValueError(f"frames must be [N, h, w, c] uint8 or [N, c, h, w] float, got {frames.dim()} dimensions")
+    if frames.dtype == torch.uint8:
+        n, h, w, c = frames.shape
+    elif frames.is_floating_point():
+        if not frames.is_cuda:
+            raise ValueError("float frames must be on the GPU ([N, c, h, w]); host frames go as [N, h, w, c] uint8")
+        n, c, h, w = frames.shape
+    else:
+        raise ValueError(f"frames must be uint8 or float, got {frames.dtype}")
+    if c != nch:
+        raise ValueError(f"frames have {c} channels, the network takes num_in_ch = {nch}")
+    if h < 2 or w < 2:
+        raise ValueError(f"SAVSR needs h, w >= 2, got {h} x {w}")
+    return int(n), int(h), int(w)
+
+
+def _to_device(frames: torch.Tensor, device: torch.device) -> torch.Tensor:
+    if frames.device == device:
+        return frames
+    if frames.is_cuda:
+        raise RuntimeError(f"frames on {frames.device}, network on {device}")
+    from ._xfer import h2d
+    return h2d(frames.contiguous(), device)
+
+
+def _check_net(net) -> None:
+    if net.training:
+        raise RuntimeError("savsr_amd.SAVSR implements the inference path only; call .eval() first")
+
+
+def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float") -> torch.Tensor:
+    """SAVSR.upscale_video (see there)."""
+    _check_net(net)
+    check_padding(padding)
+    if out not in OUT_KINDS:
+        raise ValueError(f"out = {out!r}: one of {', '.join(OUT_KINDS)}")
+    sc = as_scale(net.scale if scale is None else scale)
+    n, _, _ = frame_layout(frames, net.cfg["num_in_ch"])
+    T = net.num_frame
+    check_length(n, T, padding)
+    dev = net.gamma.device
+    if dev.type != "cuda":
+        raise RuntimeError("savsr_amd runs on an AMD GPU only: move the network to the GPU (net.cuda()) first")
+    windows = [window_indices(i, n, T, padding) for i in range(n)]
+    with torch.no_grad():
+        return net.engine().forward_video(_to_device(frames, dev), windows, sc, out == "uint8")
+
+
+class VideoUpscaler:
+    """Streaming form of SAVSR.upscale_video for long videos and decoders:
+
+        up = VideoUpscaler(net, scale=4, padding="reflection", out="uint8")
+        for chunk in decoder:                 # [k, h, w, c] uint8 (host or GPU) or [k, c, h, w] float on the GPU
+            emit(up.push(chunk))              # the SR frames whose windows are complete
+        emit(up.finish())                     # the rest (with reflection the last num_frame // 2 need the end of the video)
+
+    Concatenated, the outputs are bit for bit upscale_video on the whole video, for any chunking (a frame's output depends on its
+    window only).  The device keeps the past frames a later window may still name -- at most num_frame - 1 (num_frame for the two
+    circle modes, whose last windows reach num_frame - 1 frames back) -- plus the current chunk."""
+
+    def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float"):
+        _check_net(net)
+        check_padding(padding)
+        if out not in OUT_KINDS:
+            raise ValueError(f"out = {out!r}: one of {', '.join(OUT_KINDS)}")
+        self.net, self.padding, self.out = net, padding, out
+        self.scale = as_scale(net.scale if scale is None else scale)
+        self.T = net.num_frame
+        self.half = self.T // 2
+        self._buf: Optional[torch.Tensor] = None      # frames [base, seen) on the device
+        self._base = 0                                # video index of _buf[0]
+        self.seen = 0                                 # frames pushed
+        self.done = 0                                 # frames returned
+        self._shape: Optional[tuple] = None           # (dtype is uint8, h, w)
+        self._finished = False
+
+    def _ready(self, i: int) -> bool:
+        """Frame i's window is known whatever the video's length turns out to be (>= seen)."""
+        if i + self.half >= self.seen:
+            return False
+        return max(window_indices(i, i + self.half + 1, self.T, self.padding)) < self.seen
+
+    def _keep_from(self) -> int:
+        """Oldest frame a window not returned yet may name, for every length the video can still have."""
+        lo = self.seen
+        for i in range(self.done, self.seen + self.half + 1):
+            for n in range(max(self.seen, i + 1), max(self.seen, i + 1) + self.half + 1):
+                lo = min(lo, min(window_indices(i, n, self.T, self.padding)))
+        return max(lo, 0)
+
+    def _run(self, upto: int, n_total: Optional[int]) -> torch.Tensor:
+        """SR frames [done, upto); windows at the video length n_total (None: not known yet, every window needed is interior)."""
+        n = n_total if n_total is not None else upto + self.half + 1
+        windows = [[j - self._base for j in window_indices(i, n, self.T, self.padding)] for i in range(self.done, upto)]
+        with torch.no_grad():
+            res = self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8")
+        self.done = upto
+        return res
+
+    def push(self, frames: torch.Tensor) -> torch.Tensor:
+        if self._finished:
+            raise RuntimeError("push() after finish()")
+        k, h, w = frame_layout(frames, self.net.cfg["num_in_ch"])
+        shape = (frames.dtype == torch.uint8, h, w)
+        if self._shape is not None and shape != self._shape:
+            raise ValueError(f"chunk of {'uint8' if shape[0] else 'float'} {h} x {w} frames after {'uint8' if self._shape[0] else 'float'} "
+                             f"{self._shape[1]} x {self._shape[2]} ones")
+        dev = self.net.gamma.device
+        if dev.type != "cuda":
+            raise RuntimeError("savsr_amd runs on an AMD GPU only: move the network to the GPU (net.cuda()) first")
+        self._shape = shape
+        new = _to_device(frames, dev)
+        new = new.contiguous() if shape[0] else new.to(torch.float32).contiguous()
+        self._buf = new if self._buf is None else torch.cat([self._buf, new], 0)
+        self.seen += k
+        upto = self.done
+        while upto < self.seen and self._ready(upto):
+            upto += 1
+        res = self._run(upto, None) if upto > self.done else self._empty()
+        lo = self._keep_from()
+        if lo > self._base:
+            self._buf = self._buf[lo - self._base:]        # (a view: the next push's cat copies it)
+            self._base = lo
+        return res
+
+    def finish(self) -> torch.Tensor:
+        if self._finished:
+            raise RuntimeError("finish() called twice")
+        self._finished = True
+        if self.seen == 0:
+            raise ValueError("the video has no frames")
+        check_length(self.seen, self.T, self.padding)
+        res = self._run(self.seen, self.seen) if self.done < self.seen else self._empty()
+        self._buf = None
+        return res
+
+    def _empty(self) -> torch.Tensor:
+        from .packing import get_hw
+        u8, h, w = self._shape
+        H, W = get_hw(h, w, self.scale)
+        c = self.net.cfg["num_in_ch"]
+        dev = self.net.gamma.device
+        if self.out == "uint8":
+            return torch.empty(0, H, W, c, dtype=torch.uint8, device=dev)
+        return torch.empty(0, c, H, W, dtype=torch.float32, device=dev)
+
+
+def window_lists(n: int, num_frame: int, padding: str) -> List[List[int]]:
+    """Every frame's window of an n-frame video (generate_frame_indices)."""
+    check_padding(padding)
+    check_length(n, num_frame, padding)
+    return [window_indices(i, n, num_frame, padding) for i in range(n)]
