@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 31
+#define SAVSR_ABI_VERSION 32
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -156,6 +156,12 @@ int savsr_conv2d_max_batch(void);
  * them).  Host arithmetic only -- the plan the launcher applies; -1 for shapes the form does not take. */
 int64_t savsr_conv_wy_tile_count(int h, int w, int cout, int nconv, int algo);
 int savsr_conv2d_batch(const savsr_conv_desc* descs, int n, void* stream);
+/* (ABI 32) The precision mode "fp16" (SAVSR.set_precision): the same descriptors, forms, tiles and batch rules as savsr_conv2d_batch, with
+ * fp16 operands -- the activations rounded to fp16 (RNE) in the staging (after the Winograd-y input transform, in fp32), `wpacked` an fp16
+ * image: ONE part of savsr_conv_packed_elems / savsr_conv_wy_packed_elems elements holding fp16(W) (fp16(U)) at position p of
+ * savsr_conv_pack_index / savsr_conv_wy_pack_index, no hi/lo interleave; unaddressed entries zero.  One v_mfma_f32_32x32x16_f16 per
+ * product, fp32 accumulation, the same fp32 epilogue.  Operands beyond +-65504 become infinities: the caller checks its weights. */
+int savsr_conv2d_batch_f16(const savsr_conv_desc* descs, int n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-channel partial sums for the global average pools (AdaptiveAvgPool2d(1),
@@ -203,6 +209,9 @@ int savsr_osconv_weights(const savsr_osconv_attn_desc* d, void* stream);
  * launches (the two propagation directions of a ResidualBlock pair, savsr_arch.py:399-415, x up to four clips of a batched launch sequence). */
 int savsr_osconv_weights_max_batch(void);     /* 8 */
 int savsr_osconv_weights_batch(const savsr_osconv_attn_desc* descs, int n, void* stream);
+/* (ABI 32) The same, with wimg_out receiving the fp16 image savsr_conv2d_batch_f16 consumes: W'' computed in fp32 exactly as above and
+ * rounded once to fp16 (RNE), one part (half the bytes of the split image; the same buffer may serve both). */
+int savsr_osconv_weights_batch_f16(const savsr_osconv_attn_desc* descs, int n, void* stream);
 
 /* RCAN ChannelAttention gate (savsr_arch.py:514-520): gate = sigmoid(W2 ReLU(W1 mean + b1) + b2) */
 int savsr_se_gate(const float* partial, int nblk, float inv_n, const float* w1, const float* b1,

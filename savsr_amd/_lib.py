@@ -18,7 +18,7 @@ MAX_SRC = 5
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID = 0, 1, 2, 3
 SATU_LRCAT = 160
 SATU_TABLE = 8
-ABI_VERSION = 31
+ABI_VERSION = 32
 CONV_DIRECT, CONV_DIRECT_THROUGHPUT, CONV_WINOGRAD_Y, CONV_WINOGRAD_Y_THROUGHPUT = 0, 2, 3, 4
 CONV_WY_FORMS = (CONV_WINOGRAD_Y, CONV_WINOGRAD_Y_THROUGHPUT)
 SATU_LRCAT_TAIL = 96
@@ -101,9 +101,11 @@ SIGNATURES = {
     "savsr_conv_pool_blocks": (C.c_int, [C.c_int, C.c_int]),
     "savsr_conv2d": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
     "savsr_conv2d_batch": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_void_p]),
+    "savsr_conv2d_batch_f16": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_void_p]),
     "savsr_channel_sums": (C.c_int, [C.POINTER(fptr), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int64, C.c_int, fptr, C.c_void_p]),
     "savsr_osconv_weights": (C.c_int, [C.POINTER(OSConvAttnDesc), C.c_void_p]),
     "savsr_osconv_weights_batch": (C.c_int, [C.POINTER(OSConvAttnDesc), C.c_int, C.c_void_p]),
+    "savsr_osconv_weights_batch_f16": (C.c_int, [C.POINTER(OSConvAttnDesc), C.c_int, C.c_void_p]),
     "savsr_se_gate": (C.c_int, [fptr, C.c_int, C.c_float, fptr, fptr, fptr, fptr, C.c_int, C.c_int, fptr, C.c_void_p]),
     "savsr_scale_residual": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int, C.c_int64, C.c_void_p]),
     "savsr_se_scale_residual": (C.c_int, [fptr, C.c_int, C.c_float, fptr, fptr, fptr, fptr, C.c_int, C.c_int, fptr, fptr, fptr, C.c_int64, C.c_void_p]),

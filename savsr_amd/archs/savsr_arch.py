@@ -217,6 +217,17 @@ class SAVSR(nn.Module):
         self._engine = None
         self._engine_sig = None
         self._sig_tensors = None
+        self.precision = "fp32"
+
+    PRECISIONS = ("fp32", "fp16")
+
+    def set_precision(self, precision: str):
+        """Operand precision of the convs: "fp32" (default: split-bf16 products, fp32-equivalent) or "fp16" (operands of every static,
+        OSConv, OSAdapt-mask, pyramid and trunk conv rounded to fp16, one fp16 MFMA per product, fp32 accumulation; SATU, tail, gates
+        and pools unchanged).  Module state like set_scale: not in state_dict(), kept across load_state_dict / .to()."""
+        if precision not in self.PRECISIONS:
+            raise ValueError(f"precision must be one of {self.PRECISIONS}, got {precision!r}")
+        self.precision = precision
 
     def set_scale(self, scale: Union[tuple, float, int]):
         """savsr_arch.py:635-636; a bare number means a symmetric scale."""
@@ -246,6 +257,7 @@ class SAVSR(nn.Module):
             self._engine = HipEngine(self.state_dict(), self.cfg, self.gamma.device)
             self._sig_tensors = list(self.state_dict(keep_vars=True).values())
             self._engine_sig = self._signature()
+        self._engine.set_precision(self.precision)
         return self._engine
 
     def forward_many(self, clips, scales):

@@ -45,8 +45,12 @@ struct MultiConvParams {
     int wy_tiles, wy_full, wy_strip_l2;   // Winograd-y form: tiles per (conv, cob) = wy_full full tiles (ty * ntx + tx) + strip tiles over the image's last rows, each 2^wy_strip_l2 row pairs x (8 >> wy_strip_l2) segments (conv_wy.hip)
 };
 
-int launch_conv_wy(const MultiConvParams& mp, hipStream_t st);      // conv_wy.hip: the Winograd F(2,3)-along-y form (3x3, cout % 64 == 0)
+int launch_conv_wy(const MultiConvParams& mp, hipStream_t st, bool f16);      // conv_wy.hip: the Winograd F(2,3)-along-y form (3x3, cout % 64 == 0); f16: fp16 operands
 int conv_wy_prepare_device();
+
+// fp16 operands of the precision mode "fp16" (savsr_conv2d_batch_f16, savsr_osconv_weights_batch_f16): same lane maps as the bf16 fragments
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 // global accesses as (uniform base, 32-bit byte offset): one VGPR per address instead of a 64-bit pair
 // (savsr_conv2d validates that every tensor of a launch spans < 2 GiB).  The explicit global address space matters: the

@@ -78,7 +78,10 @@ __device__ __forceinline__ void stamp(int on, int slot) {
 // as run-time switches the diagnostics cost scalar registers (and spills) in every step of the product kernel.
 // (A straight-line epilogue variant as conv_wy_kernel<true> was built and measured in round 6: 0.4-2.9 % per launch, nothing on the frame or on
 // config 5 -- this kernel is 4 % of the GPU time -- and not kept: profiles/r06_ab_conv_direct_fast_epilogue.log.)
-template <int KS, int NT, int PXT, bool DIAG>
+// F16: the fp16-operand form of the precision mode "fp16" (savsr_conv2d_batch_f16): activations are staged as ONE fp16 (RNE) plane in the
+// hi plane's place, the weight image is one fp16 part (its pieces DMA'd into the hi slots of the same LDS layout), and each step issues one
+// v_mfma_f32_32x32x16_f16 per accumulator instead of three bf16 ones.  Accumulation and epilogue are those of the split form.
+template <int KS, int NT, int PXT, bool DIAG, bool F16>
 __global__ __launch_bounds__(512) void conv_bf16x3_kernel(const MultiConvParams mp) {
     constexpr int TH = CONV_TH * PXT, NTHR = 64 * CONV_TH;   // wave w owns tile rows w, w + 8, .. (PXT of them)
     constexpr int TAPS = KS * KS, HALO = KS / 2;
@@ -87,6 +90,7 @@ __global__ __launch_bounds__(512) void conv_bf16x3_kernel(const MultiConvParams 
     constexpr int B_PART = KSTEPS * 2 * NPX;                 // 16-B units per part (hi or lo)
     constexpr int B_UNITS = 2 * B_PART;
     constexpr int W_UNITS = TAPS * KSTEPS * NT * 2 * 64;     // 16-B units per phase
+    constexpr int W_IMG = F16 ? W_UNITS / 2 : W_UNITS;        // 16-B units per phase of the global image (F16: one part)
     constexpr int PER = KSTEPS * 4;                          // float4 items per pixel and phase
     constexpr int B_ITEMS = NPX * PER;                       // 4 lanes read one pixel's 64 B: 16 lines per wave load
     constexpr int B_IT = (B_ITEMS + NTHR - 1) / NTHR;
@@ -178,7 +182,7 @@ __global__ __launch_bounds__(512) void conv_bf16x3_kernel(const MultiConvParams 
         st_cb = 0;
         st_base = uni_ptr(mp.c[ti.conv].src[0]);
         st_pix = uni(mp.c[ti.conv].src_pix[0]);
-        st_w = reinterpret_cast<const f32x4*>(mp.c[ti.conv].wimg) + (long long)ti.cob * mp.nchunk * W_UNITS;
+        st_w = reinterpret_cast<const f32x4*>(mp.c[ti.conv].wimg) + (long long)ti.cob * mp.nchunk * W_IMG;
 #if CONV_BUF
         st_x0 = ti.x0;
         st_y0 = ti.y0;
@@ -200,7 +204,7 @@ __global__ __launch_bounds__(512) void conv_bf16x3_kernel(const MultiConvParams 
     };
     auto stage_advance = [&]() {
         st_cb += KC;
-        st_w += W_UNITS;
+        st_w += W_IMG;
         if (st_cb >= mp.src_ch) {
             st_cb = 0;
             ++st_src;
@@ -220,9 +224,10 @@ __global__ __launch_bounds__(512) void conv_bf16x3_kernel(const MultiConvParams 
     // that count is exact, and nothing touches the value before its store.
     auto issue_w = [&](int g, int wbuf) {
         const int e = tid + g * NTHR;
-        if (e < W_UNITS) {                                              // wave-uniform (W_UNITS is a multiple of 64)
+        if (e < W_IMG) {                                                // wave-uniform (W_IMG is a multiple of 64)
+            // (F16: image piece k = one (tap, kstep, t) group lands in the hi slot 2 k of the LDS slab)
             const unsigned dst = __builtin_amdgcn_readfirstlane(
-                (unsigned)(uintptr_t)(smem + 2 * B_UNITS + wbuf * W_UNITS + g * NTHR + wave * 64));
+                (unsigned)(uintptr_t)(smem + 2 * B_UNITS + wbuf * W_UNITS + (F16 ? 2 : 1) * (g * NTHR + wave * 64)));
             unsigned keep;
 #if CONV_BUF
             asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
@@ -263,6 +268,13 @@ __global__ __launch_bounds__(512) void conv_bf16x3_kernel(const MultiConvParams 
             const int e = tid + i * NTHR;
             if (e < B_ITEMS) {
                 const int pl = e / PER, c8 = e - pl * PER, q = c8 >> 1, sub = c8 & 1;   // q = kstep * 2 + khalf
+                if constexpr (F16) {
+                    f16x4 h;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) h[j] = (_Float16)srcreg[i][j];
+                    *(reinterpret_cast<bf16x4*>(bl + q * NPX + pl) + sub) = __builtin_bit_cast(bf16x4, h);
+                    return;
+                }
                 bf16x4 hi, lo;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -336,12 +348,12 @@ __global__ __launch_bounds__(512) void conv_bf16x3_kernel(const MultiConvParams 
 #pragma unroll
         for (int r = 0; r < PXT; ++r) {
             f.bh[r] = bbase[bo + r * CONV_TH * IC];
-            f.bl[r] = bbase[B_PART + bo + r * CONV_TH * IC];
+            if (!F16) f.bl[r] = bbase[B_PART + bo + r * CONV_TH * IC];
         }
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             f.ah[t] = abase[((s * NT + t) * 2 + 0) * 64];
-            f.al[t] = abase[((s * NT + t) * 2 + 1) * 64];
+            if (!F16) f.al[t] = abase[((s * NT + t) * 2 + 1) * 64];
         }
     };
 
@@ -436,6 +448,10 @@ __global__ __launch_bounds__(512) void conv_bf16x3_kernel(const MultiConvParams 
                 for (int r = 0; r < R; ++r)
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
+                        if (F16) {
+                            if (part == 2) acc[r][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fr.ah[t]), __builtin_bit_cast(f16x8, fr.bh[r]), acc[r][t], 0, 0, 0);
+                            continue;
+                        }
                         if (part == 0) acc[r][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr.al[t], fr.bh[r], acc[r][t], 0, 0, 0);
                         if (part == 1) acc[r][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr.ah[t], fr.bl[r], acc[r][t], 0, 0, 0);
                         if (part == 2) acc[r][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr.ah[t], fr.bh[r], acc[r][t], 0, 0, 0);
@@ -475,10 +491,10 @@ __global__ __launch_bounds__(512) void conv_bf16x3_kernel(const MultiConvParams 
                     if (s >= LB0 && s - LB0 < B_IT) issue_b(s - LB0);
                     mma_part(f[s % RING], 2);
 #pragma unroll
-                    for (int i = 0; i < 3 * R * NT; ++i) {
+                    for (int i = 0; i < (F16 ? 1 : 3) * R * NT; ++i) {
                         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
-                        __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);      // up to 3 vector instructions
-                        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);      // up to one DS write
+                        __builtin_amdgcn_sched_group_barrier(0x002, F16 ? 9 : 3, 0);      // up to 3 vector instructions (F16: the step's work behind a third of the MFMAs)
+                        __builtin_amdgcn_sched_group_barrier(0x200, F16 ? 3 : 1, 0);      // up to one DS write
                     }
                     __builtin_amdgcn_sched_barrier(0);
                     continue;
@@ -810,28 +826,30 @@ constexpr size_t conv_lds_bytes() {
     return 16ull * 2 * (2 * KSTEPS * 2 * NPX + TAPS * KSTEPS * NT * 2 * 64) + (PXT > 1 ? 0ull : 4ull * CONV_TH * 32 * 36);
 }
 
-template <int KS, int NT, int PXT, bool DIAG>
+template <int KS, int NT, int PXT, bool DIAG, bool F16>
 static int launch_conv_impl(const MultiConvParams& mp, hipStream_t st) {
     constexpr size_t lds = conv_lds_bytes<KS, NT, PXT>();
     static_assert(lds <= 160 * 1024, "LDS budget");
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_bf16x3_kernel<KS, NT, PXT, DIAG>), (int)lds, "conv")) return rc;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_bf16x3_kernel<KS, NT, PXT, DIAG, F16>), (int)lds, "conv")) return rc;
     const int total = mp.nconv * mp.ncob * mp.ntx * mp.nty;
     const int grid = total < CONV_PERSISTENT_BLOCKS ? total : CONV_PERSISTENT_BLOCKS;   // one resident workgroup per CU
-    hipLaunchKernelGGL((conv_bf16x3_kernel<KS, NT, PXT, DIAG>), dim3(grid), dim3(64 * CONV_TH), lds, st, mp);
+    hipLaunchKernelGGL((conv_bf16x3_kernel<KS, NT, PXT, DIAG, F16>), dim3(grid), dim3(64 * CONV_TH), lds, st, mp);
     return check_launch("conv_bf16x3_kernel");
 }
 
 template <int KS, int NT, int PXT>
-static int launch_conv(const MultiConvParams& mp, hipStream_t st) {
+static int launch_conv(const MultiConvParams& mp, hipStream_t st, bool f16) {
+    if (f16) return launch_conv_impl<KS, NT, PXT, false, true>(mp, st);      // (the instrumented kernels exist in the split form only)
 #ifdef SAVSR_DIAG
-    if (g_conv_diag_host) return launch_conv_impl<KS, NT, PXT, true>(mp, st);
+    if (g_conv_diag_host) return launch_conv_impl<KS, NT, PXT, true, false>(mp, st);
 #endif
-    return launch_conv_impl<KS, NT, PXT, false>(mp, st);
+    return launch_conv_impl<KS, NT, PXT, false, false>(mp, st);
 }
 
 template <int KS, int NT, int PXT>
 static int conv_attr() {
-    return ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_bf16x3_kernel<KS, NT, PXT, false>), (int)conv_lds_bytes<KS, NT, PXT>(), "conv");
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_bf16x3_kernel<KS, NT, PXT, false, false>), (int)conv_lds_bytes<KS, NT, PXT>(), "conv")) return rc;
+    return ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_bf16x3_kernel<KS, NT, PXT, false, true>), (int)conv_lds_bytes<KS, NT, PXT>(), "conv");
 }
 // every product instantiation's dynamic-LDS attribute on the current device (savsr_prepare_device)
 int conv_prepare_device() {
@@ -880,6 +898,7 @@ extern "C" int64_t savsr_conv_packed_elems(int cout, int cin, int ksize) {
 // Position of W[co][ci][tap] inside ONE part of the image (in elements); the hi part of a
 // (cob, chunk, tap, kstep, t) group is followed by its lo part, so the bf16 image index is
 //   group * 1024 + part * 512 + (index % 512)   with group = index / 512.
+// The fp16 image (savsr_conv2d_batch_f16) is one part: fp16(W) at the index itself.
 extern "C" int64_t savsr_conv_pack_index(int cout, int cin, int ksize, int co, int ci, int tap) {
     const int kc = conv_kc(ksize), cot = conv_cot(cout), nt = cot / 32, ksteps = kc / 16;
     const int64_t nchunk = cin / kc;
@@ -968,7 +987,7 @@ extern "C" int64_t savsr_conv_wy_tile_count(int h, int w, int cout, int nconv, i
 
 extern "C" int savsr_conv2d_max_batch(void) { return CONV_MAX_BATCH; }
 
-extern "C" int savsr_conv2d_batch(const savsr_conv_desc* descs, int n, void* stream) {
+static int conv2d_batch(const savsr_conv_desc* descs, int n, void* stream, bool f16) {
     if (!descs) return fail_arg("conv: null descriptor");
     if (n < 1 || n > CONV_MAX_BATCH) return fail_arg("conv: batch size must be 1..24 (savsr_conv2d_max_batch())");
     MultiConvParams mp;
@@ -996,7 +1015,7 @@ extern "C" int savsr_conv2d_batch(const savsr_conv_desc* descs, int n, void* str
         if (d->ksize != 3 || d->cout % 64) return fail_arg("conv: algo WINOGRAD_Y needs ksize 3 and cout a multiple of 64");
         mp.nty = (d->h + 15) / 16;
         wy_tile_plan(d->h, n * mp.ncob, d->algo, mp);
-        return launch_conv_wy(mp, st);
+        return launch_conv_wy(mp, st, f16);
     }
     if (d->algo != SAVSR_CONV_DIRECT && d->algo != SAVSR_CONV_DIRECT_THROUGHPUT) return fail_arg("conv: unknown algo");
     const bool wide = cot == 64;
@@ -1008,19 +1027,23 @@ extern "C" int savsr_conv2d_batch(const savsr_conv_desc* descs, int n, void* str
         // 230 8-row tiles (26 vs 19-22 us), with other streams' launches beside it the aggregate is faster (bench +2.4 %)
         if (d->cout % 64 == 0 && n * mp.ncob * mp.ntx * nty2 >= (d->algo == SAVSR_CONV_DIRECT_THROUGHPUT ? CONV_WIDE_MIN_TILES_TP : CONV_WIDE_MIN_TILES)) {
             mp.nty = nty2;
-            return launch_conv<3, 2, 2>(mp, st);
+            return launch_conv<3, 2, 2>(mp, st, f16);
         }
-        return launch_conv<3, 2, 1>(mp, st);
+        return launch_conv<3, 2, 1>(mp, st, f16);
     }
-    if (d->ksize == 3) return launch_conv<3, 1, 1>(mp, st);
+    if (d->ksize == 3) return launch_conv<3, 1, 1>(mp, st, f16);
     if (wide && d->cout % 64 == 0) {               // 1x1: 16-row tiles from the same tile counts up (half the barriers and fragment reads per pixel)
         const int nty2 = (d->h + 2 * CONV_TH - 1) / (2 * CONV_TH);
         if (n * mp.ncob * mp.ntx * nty2 >= (d->algo == SAVSR_CONV_DIRECT_THROUGHPUT ? CONV_WIDE_MIN_TILES_TP : CONV_WIDE_MIN_TILES)) {
             mp.nty = nty2;
-            return launch_conv<1, 2, 2>(mp, st);
+            return launch_conv<1, 2, 2>(mp, st, f16);
         }
     }
-    return wide ? launch_conv<1, 2, 1>(mp, st) : launch_conv<1, 1, 1>(mp, st);
+    return wide ? launch_conv<1, 2, 1>(mp, st, f16) : launch_conv<1, 1, 1>(mp, st, f16);
 }
+
+extern "C" int savsr_conv2d_batch(const savsr_conv_desc* descs, int n, void* stream) { return conv2d_batch(descs, n, stream, false); }
+// (ABI 32) the precision mode "fp16": the same launches on fp16 operands; wpacked is the fp16 image of the form `algo` selects
+extern "C" int savsr_conv2d_batch_f16(const savsr_conv_desc* descs, int n, void* stream) { return conv2d_batch(descs, n, stream, true); }
 
 extern "C" int savsr_conv2d(const savsr_conv_desc* d, void* stream) { return savsr_conv2d_batch(d, 1, stream); }

@@ -95,13 +95,25 @@ __device__ __forceinline__ void wy_split_store(const f32x4& v, bf16x4* hi_dst, b
     *hi_dst = hi;
     *lo_dst = lo;
 }
+// fp16-operand form (conv_wy_kernel<.., true>): one fp16 (RNE) plane in the hi plane's place; the lo plane is neither written nor read
+__device__ __forceinline__ void wy_f16_store(const f32x4& v, bf16x4* hi_dst) {
+    f16x4 h;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) h[j] = (_Float16)v[j];
+    *hi_dst = __builtin_bit_cast(bf16x4, h);
+}
 
+// F16: the fp16-operand form of the precision mode "fp16" (savsr_conv2d_batch_f16): the staging converts the transformed rows to fp16 once and
+// stores only the hi plane, the weight image is one fp16 part (half the slab: 12 of the 24 pieces of a half, into the hi slots of the same LDS
+// layout), and each (position, kx, channel block) step issues ONE v_mfma_f32_32x32x16_f16 instead of three bf16 ones.  Products of fp16
+// operands are exact in fp32; accumulation, transforms and epilogue are those of the split form.
 // FAST: every conv of the launch has an activation of the max form (none / ReLU / LeakyReLU with 0 <= slope <= 1), no per-pixel mask and no second
 // residual -- all conv launches of the network but OSAdapt's final one.  The epilogue is then straight-line code: no activation dispatch, no
 // joins whose phi copies cost 8 v_mov each (the generic epilogue carries ~480 of them and is half of the kernel's vector instructions).
-template <bool FAST>
+template <bool FAST, bool F16>
 __global__ __launch_bounds__(512) void conv_wy_kernel(const MultiConvParams mp) {
     using namespace wy;
+    constexpr int WPH = F16 ? W_PHASE / 2 : W_PHASE, WHF = F16 ? W_HALF / 2 : W_HALF;      // 16-B units of the weight IMAGE per phase / half
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     bf16x8* smem = reinterpret_cast<bf16x8*>(smem_raw);       // [8 waves][V_WAVE] | [2][W_HALF] | epilogue slices
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, px = lane & 31;
@@ -191,7 +203,7 @@ __global__ __launch_bounds__(512) void conv_wy_kernel(const MultiConvParams mp) 
         st_cb = 0;
         st_base = uni_ptr(mp.c[ti.conv].src[0]);
         st_pix = uni(mp.c[ti.conv].src_pix[0]);
-        st_w = reinterpret_cast<const bf16x8*>(mp.c[ti.conv].wimg) + (long long)ti.cob * mp.nchunk * W_PHASE;
+        st_w = reinterpret_cast<const bf16x8*>(mp.c[ti.conv].wimg) + (long long)ti.cob * mp.nchunk * WPH;
         st_row0 = uni(ti.y0 + 2 * wave_s - 1);                // image row of d0 (scalar)
 #if WY_BUF
         st_x0 = ti.x0;
@@ -210,7 +222,7 @@ __global__ __launch_bounds__(512) void conv_wy_kernel(const MultiConvParams mp) 
     };
     auto stage_advance = [&]() {
         st_cb += 16;
-        st_w += W_PHASE;
+        st_w += WPH;
         if (st_cb >= mp.src_ch) {
             st_cb = 0;
             ++st_src;
@@ -276,15 +288,16 @@ __global__ __launch_bounds__(512) void conv_wy_kernel(const MultiConvParams mp) 
     // Transform + split + store.  Half B of a phase builds positions {0, 1} of the NEXT phase from the rows in d / dx (V0 = d0 - d2, V1 = d1 + d2) and, in
     // place, the fp32 values of positions {2, 3} (V2 = d2 - d1 -> d[r][0], V3 = d1 - d3 -> d[r][1]: the other two row registers are dead from
     // there on -- 18 instead of 36 staging registers live across the tile epilogue); half A of the next phase only splits and stores those.
+    auto vstore = [&](const f32x4& v, unsigned off) {
+        if constexpr (F16) wy_f16_store(v, vptr(off));
+        else wy_split_store(v, vptr(off), vptr(off + PLANE_B));
+    };
     auto store_pair = [&](int r, int hf, const f32x4& va, const f32x4& vb) {
-        const unsigned p0 = vst0 + (unsigned)(r * 256 + (hf * 2 + 0) * 2 * PLANE_B);
-        wy_split_store(va, vptr(p0), vptr(p0 + PLANE_B));
-        const unsigned p1 = vst0 + (unsigned)(r * 256 + (hf * 2 + 1) * 2 * PLANE_B);
-        wy_split_store(vb, vptr(p1), vptr(p1 + PLANE_B));
+        vstore(va, vst0 + (unsigned)(r * 256 + (hf * 2 + 0) * 2 * PLANE_B));
+        vstore(vb, vst0 + (unsigned)(r * 256 + (hf * 2 + 1) * 2 * PLANE_B));
     };
     auto store_one = [&](int r, int hf, int vr, const f32x4& v) {
-        const unsigned p0 = vst0 + (unsigned)(r * 256 + (hf * 2 + vr) * 2 * PLANE_B);
-        wy_split_store(v, vptr(p0), vptr(p0 + PLANE_B));
+        vstore(v, vst0 + (unsigned)(r * 256 + (hf * 2 + vr) * 2 * PLANE_B));
     };
     auto store_v0 = [&](int r) { store_one(r, 0, 0, d[r][0] - d[r][2]); };          // (half B, piece 1) position 0 out; d0 is dead from here
     auto store_v1 = [&](int r) {                                                     // (half B, piece 2) position 1 out, positions 2, 3 kept in place
@@ -310,8 +323,7 @@ __global__ __launch_bounds__(512) void conv_wy_kernel(const MultiConvParams mp) 
         const bool mine = lane < 32 && (hf == 0 ? grp < 2 : (grp == 2 || grp == 1));
         const int vr = hf == 0 ? grp : (grp == 2 ? 0 : 1);
         if (mine) {
-            const unsigned pp = vst_t + (unsigned)((hf * 2 + vr) * 2 * PLANE_B);
-            wy_split_store(v, vptr(pp), vptr(pp + PLANE_B));
+            vstore(v, vst_t + (unsigned)((hf * 2 + vr) * 2 * PLANE_B));
         }
     };
     auto store_vt01 = [&]() {                                 // (half B) positions 0, 1 out; dx <- this lane's value of positions 2, 3
@@ -323,17 +335,19 @@ __global__ __launch_bounds__(512) void conv_wy_kernel(const MultiConvParams mp) 
     // weight slab half hf of the cursor's phase: 24 pieces of 1 KiB, 3 per wave, straight into LDS (the packed image IS the LDS image)
     bf16x8* wlds = smem + 8 * V_WAVE;
     [[maybe_unused]] const unsigned lane16 = (unsigned)lane * 16u;
+    // F16: the half's 12 fp16 pieces go to the hi slots of the same LDS layout, piece j * 8 + w by wave w (waves 0-3 take a second one)
     auto issue_w = [&](int j, int hf) {
-        const int piece = wave_s * 3 + j;
-        const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(wlds + hf * W_HALF + piece * 64));
+        const int piece = F16 ? j * 8 + wave_s : wave_s * 3 + j;
+        if (F16 && piece >= 12) return;                       // (wave-uniform)
+        const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(wlds + hf * W_HALF + piece * (F16 ? 128 : 64)));
         unsigned keep;
 #if WY_BUF
         // scalar 64-bit piece address + one constant per-lane byte offset (the cursor is scalar: no 64-bit vector address per piece)
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(lane16), "s"(st_w + hf * W_HALF + piece * 64), "s"(dst) : "memory");
+                     : "=&s"(keep) : "v"(lane16), "s"(st_w + hf * WHF + piece * 64), "s"(dst) : "memory");
 #else
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(st_w + hf * W_HALF + piece * 64 + lane), "s"(dst) : "memory");
+                     : "=&s"(keep) : "v"(st_w + hf * WHF + piece * 64 + lane), "s"(dst) : "memory");
 #endif
     };
 
@@ -347,11 +361,11 @@ __global__ __launch_bounds__(512) void conv_wy_kernel(const MultiConvParams mp) 
     auto load_b = [&](int hf, int s, FragB& fr) {             // s = vr * 3 + kx
         const int vr = s / 3, kx = s - 3 * vr;
         fr.bh = vrd[((hf * 2 + vr) * 2 + 0) * V_PLANE + kx];
-        fr.bl = vrd[((hf * 2 + vr) * 2 + 1) * V_PLANE + kx];
+        if (!F16) fr.bl = vrd[((hf * 2 + vr) * 2 + 1) * V_PLANE + kx];
     };
     auto load_a = [&](int hf, int s, int t, FragA& fr) {
         fr.ah = wrd[hf * W_HALF + ((s * 2 + t) * 2 + 0) * 64];
-        fr.al = wrd[hf * W_HALF + ((s * 2 + t) * 2 + 1) * 64];
+        if (!F16) fr.al = wrd[hf * W_HALF + ((s * 2 + t) * 2 + 1) * 64];
     };
 
     int tile = blockIdx.x;
@@ -426,7 +440,9 @@ __global__ __launch_bounds__(512) void conv_wy_kernel(const MultiConvParams mp) 
                 auto mma3 = [&](int pz, int t, int sb) {
                     const FragA& a = fa[t];
                     const FragB& b = fb[sb];
-                    if (MM) {
+                    if (MM && F16) {
+                        acc[pz][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a.ah), __builtin_bit_cast(f16x8, b.bh), acc[pz][t], 0, 0, 0);
+                    } else if (MM) {
                         acc[pz][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.al, b.bh, acc[pz][t], 0, 0, 0);
                         acc[pz][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.ah, b.bl, acc[pz][t], 0, 0, 0);
                         acc[pz][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.ah, b.bh, acc[pz][t], 0, 0, 0);
@@ -446,7 +462,16 @@ __global__ __launch_bounds__(512) void conv_wy_kernel(const MultiConvParams mp) 
                         pieces(hf, s);
                         load_a(hf, s + 1, 0, fa[0]);
                         mma3(pz, 1, s & 1);
-                        if (MM) {
+                        if (MM && F16) {
+#pragma unroll
+                            for (int i = 0; i < 2; ++i) {                  // (F16: two MFMAs per step carry the step's staging work)
+                                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                                if (i == 1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                                __builtin_amdgcn_sched_group_barrier(0x002, 3 * WY_VALU, 0);
+                                __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
+                                __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+                            }
+                        } else if (MM) {
 #pragma unroll
                             for (int i = 0; i < 6; ++i) {
                                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
@@ -466,7 +491,7 @@ __global__ __launch_bounds__(512) void conv_wy_kernel(const MultiConvParams mp) 
                         pieces(hf, 5);
                         if (MM) {
 #pragma unroll
-                            for (int i = 0; i < 3; ++i) {
+                            for (int i = 0; i < (F16 ? 1 : 3); ++i) {
                                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                                 __builtin_amdgcn_sched_group_barrier(0x002, 10, 0);
                                 __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
@@ -682,7 +707,7 @@ __global__ __launch_bounds__(512) void conv_wy_kernel(const MultiConvParams mp) 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the last phases re-stage unconditionally: no LDS-DMA may be in flight when the LDS is released
 }
 
-int launch_conv_wy(const MultiConvParams& mp, hipStream_t st) {
+int launch_conv_wy(const MultiConvParams& mp, hipStream_t st, bool f16) {
     if (int rc = conv_wy_prepare_device()) return rc;
     const int total = mp.nconv * mp.ncob * mp.wy_tiles;
     const int grid = total < CONV_PERSISTENT_BLOCKS ? total : CONV_PERSISTENT_BLOCKS;
@@ -692,13 +717,18 @@ int launch_conv_wy(const MultiConvParams& mp, hipStream_t st) {
         const bool as_max = c.act == SAVSR_ACT_NONE || c.act == SAVSR_ACT_RELU || (c.act == SAVSR_ACT_LRELU && c.slope >= 0.f && c.slope <= 1.f);
         fast = as_max && !c.mul_px && !c.res2;
     }
-    if (fast) hipLaunchKernelGGL(conv_wy_kernel<true>, dim3(grid), dim3(wy::NTHR), wy::LDS_BYTES, st, mp);
-    else hipLaunchKernelGGL(conv_wy_kernel<false>, dim3(grid), dim3(wy::NTHR), wy::LDS_BYTES, st, mp);
+    if (f16) {
+        if (fast) hipLaunchKernelGGL((conv_wy_kernel<true, true>), dim3(grid), dim3(wy::NTHR), wy::LDS_BYTES, st, mp);
+        else hipLaunchKernelGGL((conv_wy_kernel<false, true>), dim3(grid), dim3(wy::NTHR), wy::LDS_BYTES, st, mp);
+    } else if (fast) hipLaunchKernelGGL((conv_wy_kernel<true, false>), dim3(grid), dim3(wy::NTHR), wy::LDS_BYTES, st, mp);
+    else hipLaunchKernelGGL((conv_wy_kernel<false, false>), dim3(grid), dim3(wy::NTHR), wy::LDS_BYTES, st, mp);
     return check_launch("conv_wy_kernel");
 }
 int conv_wy_prepare_device() {
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_wy_kernel<true>), (int)wy::LDS_BYTES, "conv_wy")) return rc;
-    return ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_wy_kernel<false>), (int)wy::LDS_BYTES, "conv_wy");
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_wy_kernel<true, false>), (int)wy::LDS_BYTES, "conv_wy")) return rc;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_wy_kernel<false, false>), (int)wy::LDS_BYTES, "conv_wy")) return rc;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_wy_kernel<true, true>), (int)wy::LDS_BYTES, "conv_wy")) return rc;
+    return ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_wy_kernel<false, true>), (int)wy::LDS_BYTES, "conv_wy");
 }
 
 }  // namespace savsr
@@ -717,7 +747,7 @@ extern "C" int64_t savsr_conv_wy_packed_elems(int cout, int cin) {
     return (int64_t)(cout / 64) * (cin / 16) * 12 * 16 * 64;
 }
 // Position of U[pos][co][ci][kx] (pos = Winograd position 0..3) inside ONE part; the hi part of a (.., t) group of 512 elements is
-// followed by its lo part, as in savsr_conv_pack_index.
+// followed by its lo part, as in savsr_conv_pack_index.  The fp16 image (savsr_conv2d_batch_f16) is one part: fp16(U) at this position.
 extern "C" int64_t savsr_conv_wy_pack_index(int cout, int cin, int co, int ci, int pos, int kx) {
     const int64_t nchunk = cin / 16;
     const int cob = co / 64, col = co % 64, t = col / 32, row = col % 32;

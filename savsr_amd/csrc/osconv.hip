@@ -237,6 +237,10 @@ __device__ __forceinline__ void osconv_route_in_workgroup(const savsr_osconv_att
 // then  W''[co][ci][tap] = fa[co] ca[ci] sa[tap] sum_k ka[k] W[k][co][ci][tap]  (:156-163,171
 // folded, :148-149) for this workgroup's slice, split to (hi, lo) bf16 and written in the conv
 // weight-image order.
+// F16 (the precision mode "fp16", savsr_osconv_weights_batch_f16): the same fp32 W'' rounded ONCE to fp16 (RNE), one part at the pack index.
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+template <bool F16>
 __global__ __launch_bounds__(512) void osconv_aggregate_kernel(const OscBatch bt) {
     const savsr_osconv_attn_desc& d = bt.d[blockIdx.y];
     extern __shared__ float sm[];
@@ -369,8 +373,15 @@ __global__ __launch_bounds__(512) void osconv_aggregate_kernel(const OscBatch bt
     const float* ca = gates + ci0;
     s0[0] *= gco * ca[0]; s0[1] *= gco * ca[1]; s0[2] *= gco * ca[2]; s0[3] *= gco * ca[3];
     s1[0] *= gco * ca[4]; s1[1] *= gco * ca[5]; s1[2] *= gco * ca[6]; s1[3] *= gco * ca[7];
-    bf16x8 hi, lo;
     const float x[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
+    if constexpr (F16) {
+        f16x8 h;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) h[j] = (_Float16)x[j];
+        reinterpret_cast<f16x8*>(d.wimg_out)[group * 64 + ln] = h;
+        return;
+    }
+    bf16x8 hi, lo;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const __bf16 h = (__bf16)x[j];
@@ -386,6 +397,7 @@ __global__ __launch_bounds__(512) void osconv_aggregate_kernel(const OscBatch bt
 // aggregated and gated taps g_ky = fa[co] ca[ci] sa[ky, kx] sum_k ka[k] W[k][co][ci][ky][kx] -- the spatial gate sa is applied BEFORE the transform, it
 // depends on ky -- then U0 = g0, U1 = (g0 + g1 + g2) / 2, U2 = (g0 - g1 + g2) / 2, U3 = g2, split and written in the order of
 // savsr_conv_wy_pack_index.  One thread = one float4 half of an 8-element lane unit of (cob, chunk, kx, t): 3 x knum x 16 B of bank data per thread.
+template <bool F16>
 __global__ __launch_bounds__(512) void osconv_aggregate_wy_kernel(const OscBatch bt) {
     const savsr_osconv_attn_desc& d = bt.d[blockIdx.y];
     extern __shared__ float sm[];
@@ -534,6 +546,13 @@ __global__ __launch_bounds__(512) void osconv_aggregate_wy_kernel(const OscBatch
     for (int pos = 0; pos < 4; ++pos) {
         const int hf = pos >> 1, vr = pos & 1;
         const long long group = ((((long long)(cob * nchunk + chunk) * 2 + hf) * 6 + (vr * 3 + kx)) * nt + t);
+        if constexpr (F16) {
+            f16x4 h;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) h[j] = (_Float16)uu[pos][j];
+            reinterpret_cast<f16x4*>(d.wimg_out)[(group * 64 + ln) * 2 + h4] = h;      // units of 8 B
+            continue;
+        }
         bf16x4 hi, lo;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -713,7 +732,7 @@ static int check_osconv_desc(const savsr_osconv_attn_desc* d) {
 
 extern "C" int savsr_osconv_weights_max_batch(void) { return OSC_MAX_BATCH; }
 
-extern "C" int savsr_osconv_weights_batch(const savsr_osconv_attn_desc* descs, int n, void* stream) {
+static int osconv_weights_batch(const savsr_osconv_attn_desc* descs, int n, void* stream, bool f16) {
     if (!descs) return fail_arg("osconv_weights: null descriptor");
     if (n < 1 || n > OSC_MAX_BATCH) return fail_arg("osconv_weights: batch size must be 1..savsr_osconv_weights_max_batch()");
     OscBatch bt;
@@ -743,12 +762,18 @@ extern "C" int savsr_osconv_weights_batch(const savsr_osconv_attn_desc* descs, i
     if (d->wy) {
         if (d->cout % 64 || d->cin % 16) return fail_arg("osconv_weights: the Winograd-y image needs cout % 64 == 0 and cin % 16 == 0");
         const long long nitems = (long long)(d->cout / 64) * (d->cin / 16) * 3 * 2 * 64 * 2;
-        hipLaunchKernelGGL(osconv_aggregate_wy_kernel, dim3((unsigned)((nitems + 511) / 512), n), dim3(512), lds, st, bt);
+        if (f16) hipLaunchKernelGGL(osconv_aggregate_wy_kernel<true>, dim3((unsigned)((nitems + 511) / 512), n), dim3(512), lds, st, bt);
+        else hipLaunchKernelGGL(osconv_aggregate_wy_kernel<false>, dim3((unsigned)((nitems + 511) / 512), n), dim3(512), lds, st, bt);
         return check_launch("osconv_aggregate_wy_kernel");
     }
-    hipLaunchKernelGGL(osconv_aggregate_kernel, dim3((unsigned)((d->nunits + 511) / 512), n), dim3(512), lds, st, bt);
+    if (f16) hipLaunchKernelGGL(osconv_aggregate_kernel<true>, dim3((unsigned)((d->nunits + 511) / 512), n), dim3(512), lds, st, bt);
+    else hipLaunchKernelGGL(osconv_aggregate_kernel<false>, dim3((unsigned)((d->nunits + 511) / 512), n), dim3(512), lds, st, bt);
     return check_launch("osconv_aggregate_kernel");
 }
+
+extern "C" int savsr_osconv_weights_batch(const savsr_osconv_attn_desc* descs, int n, void* stream) { return osconv_weights_batch(descs, n, stream, false); }
+// (ABI 32) the precision mode "fp16": wimg_out receives the fp16 image (one part, savsr_conv_pack_index / savsr_conv_wy_pack_index)
+extern "C" int savsr_osconv_weights_batch_f16(const savsr_osconv_attn_desc* descs, int n, void* stream) { return osconv_weights_batch(descs, n, stream, true); }
 
 extern "C" int savsr_osconv_weights(const savsr_osconv_attn_desc* d, void* stream) { return savsr_osconv_weights_batch(d, 1, stream); }
 

@@ -54,6 +54,12 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self.rw = window_record(self.nch, self.sw)                 # floats per pixel of a packed input window
         self.pw: Dict[str, tuple] = {}      # conv key -> (wimage, bias, cout, cin, ks)
         self.pw_wy: Dict[str, torch.Tensor] = {}      # conv key -> Winograd-y weight image (static 3x3 convs with cout % 64 == 0)
+        # Precision mode (set_precision): "fp32" = the split-bf16 products; "fp16" = fp16 operands in every conv launch (savsr_conv2d_batch_f16,
+        # savsr_osconv_weights_batch_f16), everything else unchanged.  The fp16 images of the static convs are built on the first fp16 forward.
+        self.precision = "fp32"
+        self.pw16: Dict[str, torch.Tensor] = {}       # conv key -> fp16 image (direct form)
+        self.pw16_wy: Dict[str, torch.Tensor] = {}    # conv key -> fp16 Winograd-y image
+        self._conv_src: Dict[str, tuple] = {}         # conv key -> how its weight derives from the state_dict (packing.py::_conv_weight)
         self.osc: Dict[str, dict] = {}      # osconv key -> tensors
         self.se: Dict[str, tuple] = {}
         self._keep: List[torch.Tensor] = []
@@ -177,6 +183,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         e.NB_MAX = self.NB_MAX
         e.pw, e.se, e._keep = self.pw, self.se, self._keep
         e.pw_wy, e.conv_wy, e.wy_min_tiles, e.wy_min_tiles_tp = self.pw_wy, self.conv_wy, self.wy_min_tiles, self.wy_min_tiles_tp
+        e.precision, e.pw16, e.pw16_wy, e._conv_src, e._sd_ref = self.precision, self.pw16, self.pw16_wy, self._conv_src, self._sd_ref
         e.reuse_buffers, e.osconv_fused = self.reuse_buffers, self.osconv_fused
         e.satu_t, e.satu_w, e.tail_w, e.tail_b, e.gamma, e.n_l2 = self.satu_t, self.satu_w, self.tail_w, self.tail_b, self.gamma, self.n_l2
         e.iter_win, e.fwd_idx, e.bwd_idx = self.iter_win, self.fwd_idx, self.bwd_idx
@@ -201,6 +208,26 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         e._hr_choice, e._hr_table = self._hr_choice, self._hr_table
         e._siblings, e._streams = [], []
         return e
+
+    PRECISIONS = ("fp32", "fp16")
+
+    def set_precision(self, mode: str) -> None:
+        """The operand precision of the conv launches, for this engine and its stream siblings (SAVSR.set_precision)."""
+        if mode not in self.PRECISIONS:
+            raise ValueError(f"precision must be one of {self.PRECISIONS}, got {mode!r}")
+        self.precision = mode
+        for e in self._siblings:
+            e.precision = mode
+
+    def _ensure_precision(self) -> None:
+        """Before a frame is issued (never inside a capture): the fp16 images exist when the mode needs them."""
+        if self.precision == "fp16" and not self.pw16:
+            self._build_f16()
+
+    def _graph_key(self, throughput: bool):
+        """Key of a context's captured graphs: the flow and, for fp16, the precision (a graph is never replayed in the other mode; the
+        context's buffers are shared)."""
+        return throughput if self.precision == "fp32" else (throughput, self.precision)
 
     # ------------------------------------------------------------------ network pieces
     def residual_blocks(self, groups: List[Tuple[str, List[Src], str]], hp: int, wp: int, scale, use_osconv: bool) -> List[List[Src]]:
@@ -489,6 +516,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
     def forward_one(self, lq: torch.Tensor, scale, out: torch.Tensor, taps: Optional[dict] = None):
         """Eager launch sequence.  lq: [T, c, h, w] fp32 contiguous on device (c = num_in_ch); out: [c, H, W] (or [nb, T, c, h, w] ->
         [nb, c, H, W]: nb clips of one (shape, scale) in one launch sequence)."""
+        self._ensure_precision()
         self.nb = int(lq.shape[0]) if lq.dim() == 5 else 1
         assert self.nb <= self.NB_MAX and (self.nb == 1 or taps is None)
         try:
@@ -552,11 +580,12 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         if sc["graphs"] is None:
             sc["graphs"] = {}
         self._set_flow(lq, throughput)
-        g = sc["graphs"].get(throughput)
+        gk = self._graph_key(throughput)
+        g = sc["graphs"].get(gk)
         if g is None:
-            used = sc.setdefault("uses", {}).get(throughput, 0)
+            used = sc.setdefault("uses", {}).get(gk, 0)
             if used < self.capture_after:            # the context's first frames: eager (see capture_after)
-                sc["uses"][throughput] = used + 1
+                sc["uses"][gk] = used + 1
                 self.host_stats["eager_frames"] += 1
                 return self._forward_one(lq, scale, out)
             s_in = torch.empty_like(lq)
@@ -613,7 +642,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             if g[3].get("ptab") is not None and not sc.get("ptab_charged"):
                 self._charge(sc, g[3]["ptab"].numel() * 4)               # (the per-pixel table lives as long as a graph that names it)
                 sc["ptab_charged"] = True
-            sc["graphs"][throughput] = g
+            sc["graphs"][gk] = g
         s_in, s_out, graphs = g[:3]
         s_in.copy_(lq)
         graphs[0].replay()
@@ -674,6 +703,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         launches are latency-bound) overlap.  Every clip's result is that of the throughput flow (`_set_flow`) whatever
         the grouping: forward_many(items)[i] == forward_many([items[i]])[0] bit for bit; against the one-clip latency flow of `forward` it
         agrees to the conv forms' rounding (~1e-5) where a launch takes another form."""
+        self._ensure_precision()
         if not self.use_graphs:            # SAVSR_GRAPHS=0 (diagnostics): the same flow issued eagerly, one clip after the other
             outs = []
             for lq, sc in items:
@@ -743,6 +773,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         balanced; units dealt round-robin over `streams_for` streams; throughput flow), so frame i equals forward_many on the gathered
         window i bit for bit.  A unit's windows are gathered from `frames` by savsr_video_gather_u8 / _f32 into a unit-sized fp32 clip
         batch on the unit's stream; nothing is gathered or converted on the host."""
+        self._ensure_precision()
         if frames.device != self.dev:
             raise RuntimeError(f"input on {frames.device}, engine on {self.dev}")
         u8 = frames.dtype == torch.uint8
@@ -803,6 +834,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
 
     def forward(self, lq: torch.Tensor, scale, taps: Optional[dict] = None) -> torch.Tensor:
         """lq: [b, T, c, h, w] -> [b, c, H, W], c = num_in_ch (savsr_arch.py:692-742)."""
+        self._ensure_precision()
         if lq.device != self.dev:
             raise RuntimeError(f"input on {lq.device}, engine on {self.dev}")
         lq = lq.to(torch.float32).contiguous()

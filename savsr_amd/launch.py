@@ -70,9 +70,13 @@ class Launcher:
                   pool: Optional[Tuple[torch.Tensor, int, int]] = None) -> ConvDesc:
         """pool = (partial tensor, column offset, row stride): fused global-average-pool partials of the output."""
         wpk, bias, cout, cin, ks, *rest = weights if weights is not None else self.pw[key]
+        f16 = self.precision == "fp16"
+        if f16 and weights is None:
+            wpk = self.pw16[key]                             # (precision "fp16": the static conv's fp16 image, _build_f16)
+        pw_wy = self.pw16_wy if f16 else self.pw_wy
         d = ConvDesc()
         d.algo = rest[0] if rest else self.conv_algo
-        d._wy = self.pw_wy[key].data_ptr() if (weights is None and key in self.pw_wy) else None      # (a Python attribute, not a field of the C struct)
+        d._wy = pw_wy[key].data_ptr() if (weights is None and key in pw_wy) else None      # (a Python attribute, not a field of the C struct)
         assert len(srcs) <= _lib.MAX_SRC and all(s.ch == srcs[0].ch for s in srcs)
         assert cin == len(srcs) * srcs[0].ch, (key, cin, len(srcs), srcs[0].ch)
         assert out.ch == cout, (key, out.ch, cout)
@@ -125,6 +129,7 @@ class Launcher:
     def conv_launch(self, descs: List[ConvDesc], label: str = "conv"):
         """Independent convs of identical geometry, up to 6 per launch and clip (savsr_conv2d_batch; x nb clips of a batched launch sequence)."""
         st = self._stream()
+        fn = self.lib.savsr_conv2d_batch_f16 if self.precision == "fp16" else self.lib.savsr_conv2d_batch
         for i in range(0, len(descs), 6):
             chunk = descs[i:i + 6]
             per_clip = len(chunk)
@@ -144,7 +149,7 @@ class Launcher:
             if self.census is not None:      # diagnostics (bench.py): matrix work of this launch, by the form it takes
                 self._count_conv(chunk)
             arr = (ConvDesc * len(chunk))(*chunk)
-            _lib.check(self.lib.savsr_conv2d_batch(arr, len(chunk), st), f"savsr_conv2d_batch[{label}]")
+            _lib.check(fn(arr, len(chunk), st), f"savsr_conv2d_batch[{label}]")
 
     def _count_conv(self, chunk) -> None:
         """Census of one conv launch for bench.py's matrix-utilisation figures.  `alg` = 2 x MACs of the convs as the reference states them;
@@ -222,6 +227,8 @@ class Launcher:
         """Weight generation of independent OSConvs of identical geometry, up to 6 per set of launches
         (savsr_osconv_weights_batch); returns the conv `weights` tuples."""
         st = self._stream()
+        # (precision "fp16": the fp16 image goes into the same buffers -- half their bytes -- and is consumed by savsr_conv2d_batch_f16)
+        fn = self.lib.savsr_osconv_weights_batch_f16 if self.precision == "fp16" else self.lib.savsr_osconv_weights_batch
         per = max(1, int(self.lib.savsr_osconv_weights_max_batch()) // self.nb)      # OSConvs per set of launches when every one of them goes out once per clip
         for i in range(0, len(descs), per):
             chunk = descs[i:i + per]
@@ -236,7 +243,7 @@ class Launcher:
                         clips.append(n)
                 chunk = clips
             arr = (OSConvAttnDesc * len(chunk))(*chunk)
-            _lib.check(self.lib.savsr_osconv_weights_batch(arr, len(chunk), st), f"savsr_osconv_weights_batch[{keys[i]}]")
+            _lib.check(fn(arr, len(chunk), st), f"savsr_osconv_weights_batch[{keys[i]}]")
         return [(self.osc[k]["wdyn_wy"], None, self.osc[k]["cout"], self.osc[k]["cin"], 3, self._wy_algo()) if dsc.wy else
                 (self.osc[k]["wdyn"], None, self.osc[k]["cout"], self.osc[k]["cin"], 3) for k, dsc in zip(keys, descs)]
 

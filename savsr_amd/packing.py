@@ -164,6 +164,48 @@ def pack_conv_weight_wy(w: torch.Tensor, device: Optional[torch.device] = None) 
     return split_bf16_image(_scatter_image(idx, total, u, "wy", (cout, cin), device))
 
 
+FP16_MAX = 65504.0      # largest finite fp16: the operand range of the precision mode "fp16"
+
+
+def _f16_image(idx: np.ndarray, total: int, values: np.ndarray) -> torch.Tensor:
+    """int16 view of an fp16 image: zeros[total] with float16(values) (RNE, straight from float64 by numpy) scattered to idx."""
+    out = np.zeros(total, dtype=np.float16)
+    out[idx] = np.asarray(values, dtype=np.float64).reshape(-1).astype(np.float16)
+    return torch.from_numpy(out.view(np.int16))
+
+
+def pack_conv_weight_f16(w: torch.Tensor) -> torch.Tensor:
+    """[cout, cin, k, k] -> fp16 weight image (int16 tensor on the host) for savsr_conv2d_batch_f16: ONE part, fp16(W) at position p of
+    savsr_conv_pack_index, no hi/lo interleave."""
+    cout, cin, ks, _ = w.shape
+    idx, total = conv_pack_index(cout, cin, ks)
+    return _f16_image(idx, total, w.detach().to("cpu", torch.float64).numpy())
+
+
+def wy_transform_f64(w: torch.Tensor) -> np.ndarray:
+    """[cout, cin, 3, 3] -> the F(2,3)-along-y weight transform U [4 pos][cout][cin][3 kx] in float64 (pack_conv_weight_wy's arithmetic)."""
+    g = w.detach().to("cpu", torch.float64)
+    g0, g1, g2 = g[:, :, 0], g[:, :, 1], g[:, :, 2]
+    return torch.stack([g0, 0.5 * (g0 + g1 + g2), 0.5 * (g0 - g1 + g2), g2], 0).numpy()
+
+
+def pack_conv_weight_wy_f16(w: torch.Tensor) -> torch.Tensor:
+    """[cout, cin, 3, 3] -> fp16 Winograd-y weight image (int16 tensor on the host): U in float64, rounded ONCE to fp16, at position p of
+    savsr_conv_wy_pack_index."""
+    cout, cin, ks, _ = w.shape
+    assert ks == 3
+    idx, total = conv_wy_pack_index(cout, cin)
+    return _f16_image(idx, total, wy_transform_f64(w))
+
+
+def check_f16_range(name: str, a: np.ndarray) -> None:
+    """Refuse an operand outside the fp16 range (it would become an infinity in the precision mode "fp16"), naming it."""
+    m = float(np.abs(a).max()) if a.size else 0.0
+    if not m <= FP16_MAX:
+        raise ValueError(f"precision 'fp16': {name} has a weight of magnitude {m:.6g}, beyond the fp16 range (+-{FP16_MAX:g}); "
+                         f"run this checkpoint with precision 'fp32'")
+
+
 def acc_row(r: int, half: int) -> int:
     """Row of register r of a 32x32 MFMA accumulator for lane half `half`."""
     return (r & 3) + 8 * (r >> 2) + 4 * half
@@ -254,12 +296,10 @@ class WeightPacking:
             self.pw_wy[key] = self._dev(pack_conv_weight_wy(wd, self.dev), torch.int16)
 
     def _add_conv(self, sd, key: str, bn: Optional[str] = None):
-        w, b = self._fold(sd, key, bn)
-        self._register(key, w, b)
+        self._conv_src[key] = ("conv", key, bn)
+        self._register(key, *self._fold(sd, key, bn))
 
-    def _add_conv_padded(self, sd, key: str, bn: Optional[str], cin_p: int, cout_p: int):
-        """A conv with zero input / output channels appended up to (cin_p, cout_p): the conv kernels take multiples of 16 input channels.
-        An appended output channel is 0 (zero weights, zero bias; ReLU(0) = 0) and an appended input channel meets zero weights."""
+    def _padded(self, sd, key: str, bn: Optional[str], cin_p: int, cout_p: int):
         w, b = self._fold(sd, key, bn)
         cout, cin, ks, _ = w.shape
         wp = torch.zeros(cout_p, cin_p, ks, ks)
@@ -268,10 +308,50 @@ class WeightPacking:
         if b is not None:
             bp = torch.zeros(cout_p)
             bp[:cout] = b
-        self._register(key, wp, bp)
+        return wp, bp
+
+    def _add_conv_padded(self, sd, key: str, bn: Optional[str], cin_p: int, cout_p: int):
+        """A conv with zero input / output channels appended up to (cin_p, cout_p): the conv kernels take multiples of 16 input channels.
+        An appended output channel is 0 (zero weights, zero bias; ReLU(0) = 0) and an appended input channel meets zero weights."""
+        self._conv_src[key] = ("padded", key, bn, cin_p, cout_p)
+        self._register(key, *self._padded(sd, key, bn, cin_p, cout_p))
 
     def _add_window_conv(self, sd, d: str):
+        self._conv_src[d + ".win"] = ("win", d)
         self._register(d + ".win", *fuse_window_conv(sd, d, self.cfg["num_in_ch"], self.cfg["slid_win"]))
+
+    def _conv_weight(self, src: tuple) -> torch.Tensor:
+        """The fp32 weight [cout, cin, k, k] a static conv was registered with, derived again from the state_dict (no copy is kept)."""
+        sd = self._sd_ref
+        if src[0] == "conv":
+            return self._fold(sd, src[1], src[2])[0]
+        if src[0] == "padded":
+            return self._padded(sd, *src[1:])[0]
+        return fuse_window_conv(sd, src[1], self.cfg["num_in_ch"], self.cfg["slid_win"])[0]
+
+    def _build_f16(self) -> None:
+        """The fp16 weight images of the static convs (precision "fp16"), built once, on the first fp16 forward: fp16(W) and, where the
+        Winograd-y image exists, fp16(U) with U in float64 -- both rounded once.  Refuses any operand beyond +-65504, naming its conv;
+        an OSConv's dynamic weights are gated averages of its bank (every gate in (0, 1), the kernel weights a softmax): |W''| <= max |bank|,
+        |U| <= 1.5 max |bank|."""
+        if self.pw16:
+            return
+        imgs, imgs_wy = {}, {}
+        for key, src in self._conv_src.items():
+            w = self._conv_weight(src)
+            check_f16_range(f"conv {key!r}", w.numpy())
+            imgs[key] = pack_conv_weight_f16(w)
+            if key in self.pw_wy:
+                u = wy_transform_f64(w)
+                check_f16_range(f"conv {key!r} (Winograd-y transform)", u)
+                imgs_wy[key] = _f16_image(*conv_wy_pack_index(w.shape[0], w.shape[1]), u)
+        for key in self.osc:
+            bank = self._sd_ref[key + ".weight"].detach().to("cpu", torch.float64).numpy()
+            check_f16_range(f"OSConv {key!r}", bank * (1.5 if self.osc[key]["cout"] % 64 == 0 else 1.0))
+        for key, img in imgs.items():
+            self.pw16[key] = self._dev(img, torch.int16)
+        for key, img in imgs_wy.items():
+            self.pw16_wy[key] = self._dev(img, torch.int16)
 
     def _add_osconv(self, sd, key: str):
         bank = sd[key + ".weight"].to(self.dev, torch.float32)    # [K, cout, cin, 3, 3]
@@ -487,6 +567,7 @@ class WeightPacking:
 
     def _pack_all(self, sd):
         cfg = self.cfg
+        self._sd_ref = sd          # (the module's own tensors: the lazily built fp16 images are derived from them, _build_f16)
         for d in ("f2p_win", "p2f_win"):
             self._add_window_conv(sd, d)
             for k in range(cfg["w1_num_block"]):

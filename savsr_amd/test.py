@@ -33,9 +33,12 @@ from .models import build_model
 from .options import parse_test_options
 
 
-def run_test(opt: Union[str, dict], root_path: str = ".", model=None) -> List[dict]:
+def run_test(opt: Union[str, dict], root_path: str = ".", model=None, precision: str = "fp32") -> List[dict]:
     """model: an already built model (build_model(opt)) to run the datasets through -- several YAMLs / passes over one set of
-    weights then share its engine (captured graphs, packed weights); None builds one from `opt` as test.py:35 does."""
+    weights then share its engine (captured graphs, packed weights); None builds one from `opt` as test.py:35 does.
+    precision: the network's conv operand precision (SAVSR.set_precision), "fp32" or "fp16"."""
+    if precision not in ("fp32", "fp16"):
+        raise ValueError(f"precision must be 'fp32' or 'fp16', got {precision!r}")
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if isinstance(opt, str):
@@ -74,6 +77,8 @@ def run_test(opt: Union[str, dict], root_path: str = ".", model=None) -> List[di
             if "path" in opt:
                 model.opt.setdefault("path", {}).update({k: v for k, v in opt["path"].items() if k != "pretrain_network_g"})
             model.opt["rank"], model.opt["world_size"], model.opt["dist"] = opt["rank"], opt["world_size"], opt["dist"]
+        net = model.net_g.module if hasattr(model.net_g, "module") else model.net_g
+        net.set_precision(precision)
         save_img = opt["val"].get("save_img", False)
         if hasattr(model, "validate_job") and all(hasattr(ds, "units") for ds in test_sets) and os.environ.get("SAVSR_JOB_PLAN", "1") != "0":
             # all datasets of the YAML as one job: (dataset, folder) units cut over the ranks, ONE gather of the metric rows (models.validate_job)
@@ -143,14 +148,20 @@ def format_check(rows: List[dict]) -> str:
     return "\n".join(out)
 
 
-def main(argv=None) -> int:
+def build_parser():
     import argparse
     ap = argparse.ArgumentParser(prog="python -m savsr_amd.test", description=__doc__.split("\n")[0])
     ap.add_argument("-opt", required=True, help="options/test/SAVSR/*.yml (unchanged)")
     ap.add_argument("--root", default=".", help="root for results/ (lbasicsr/test.py uses the repo root)")
     ap.add_argument("--check-readme", action="store_true", help="compare every dataset with the reference's published PSNR-Y / SSIM-Y")
-    a = ap.parse_args(argv)
-    results = run_test(a.opt, a.root)
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "fp16"],
+                    help="conv operand precision (default fp32; fp16 trades a small drift for speed, DESIGN.md section 3)")
+    return ap
+
+
+def main(argv=None) -> int:
+    a = build_parser().parse_args(argv)
+    results = run_test(a.opt, a.root, precision=a.precision)
     if int(os.environ.get("RANK", "0")) != 0:
         return 0
     for r in results:

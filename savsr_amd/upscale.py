@@ -33,6 +33,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--chunk", type=int, default=16, help="frames per push (default 16)")
     p.add_argument("--writers", type=int, default=0, help=f"PNG encoder threads (default: the usable CPUs, at most {MAX_WRITERS})")
     p.add_argument("--device", default="cuda:0")
+    p.add_argument("--precision", default="fp32", choices=["fp32", "fp16"],
+                   help="conv operand precision (default fp32; fp16: faster, ~1e-3 drift, see DESIGN.md section 3)")
     return p
 
 
@@ -93,6 +95,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     from .video import VideoUpscaler, check_length
 
     net = load_net(a)
+    net.set_precision(a.precision)
     check_length(len(paths), net.num_frame, a.padding)        # (before the GPU is touched)
     dev = torch.device(a.device)
     net = net.to(dev)

@@ -1,0 +1,126 @@
+"""Goldens of the precision mode "fp16" (SAVSR.set_precision): a CPU emulation of what the fp16 conv kernels compute, and its drift
+against the fp32 outputs, case table in tests/precision_cases.py.
+
+The emulation runs the oracle with its convs wrapped: exactly the convs the engine sends through savsr_conv2d_batch_f16 get fp16 (RNE)
+operands and float64 products -- every static 3x3 / 1x1 conv of the propagation, pyramid, trunk and OSAdapt mask, and the OSConvs, whose
+operands are the input x and W'' = fa ca sa sum_k ka W computed in fp32 and rounded once (the engine folds the channel gate into the
+weights).  SATU (kernel_conv, the coordinate heads, fusion), the tail, the SE and attention MLPs keep fp32 operands.  oracle/ itself is
+unchanged.  Writes tests/golden/precision_outputs.npz:
+    <case>/fp32, <case>/fp16emu             outputs [c, H, W]
+    <case>/drift                            [max-abs, mean-abs] of fp16emu against fp32
+    <case>/manifest                         manifest_hash of the state_dict the case's weights were synthesised for
+    gt/psnr_fp32, gt/psnr_fp16emu           PSNR-Y of GT_CASE against the synthetic GT (tests/precision_cases.py)
+
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_precision.py
+"""
+import os
+import sys
+import types
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from oracle import savsr_oracle as O  # noqa: E402
+from savsr_amd.archs.savsr_arch import SAVSR  # noqa: E402
+from savsr_amd.utils import synth  # noqa: E402
+from tests.golden_cases import manifest_hash  # noqa: E402
+from tests.precision_cases import CLIP_SEED, GT_CASE, PRECISION_CASES, WEIGHT_SEED, psnr_y, synth_gt  # noqa: E402
+
+GOLD = os.path.join(ROOT, "tests", "golden")
+_ORIG_CONV, _ORIG_OSCONV, _ORIG_BN = O._conv, O.osconv2d, O._bn_eval
+MASK_BN = {".mask.0": ".mask.1", ".mask.4": ".mask.5", ".mask.7": ".mask.8", ".mask.11": ".mask.12"}      # OSAdapt: BN folded into the conv
+
+
+def f16(t: torch.Tensor) -> torch.Tensor:
+    return t.to(torch.float32).to(torch.float16).to(torch.float64)
+
+
+def conv_f16(x, w, b, padding, groups=1):
+    y = F.conv2d(f16(x), f16(w), None, stride=1, padding=padding, groups=groups)
+    if b is not None:
+        y = y + b.to(torch.float64).view(1, -1, 1, 1)
+    return y.to(torch.float32)
+
+
+def fp32_operands(pfx: str) -> bool:
+    """Convs that are not conv-kernel launches in the engine: SATU, the tail, the SE / attention MLPs."""
+    return pfx.startswith("upsample") or pfx == "tail" or ".attention" in pfx
+
+
+def emu_conv(sd, pfx, x, padding):
+    if fp32_operands(pfx):
+        return _ORIG_CONV(sd, pfx, x, padding)
+    w, b = sd[pfx + ".weight"], sd.get(pfx + ".bias")
+    for tail, bn_tail in MASK_BN.items():
+        if pfx.endswith(tail):           # the engine's operand is the BN-folded weight (packing.py::_fold); emu_bn skips that BN
+            bn = pfx[: -len(tail)] + bn_tail
+            sc = sd[bn + ".weight"] / torch.sqrt(sd[bn + ".running_var"] + O_BN_EPS)
+            w = w * sc.view(-1, 1, 1, 1)
+            b = ((b if b is not None else torch.zeros_like(sc)) - sd[bn + ".running_mean"]) * sc + sd[bn + ".bias"]
+    return conv_f16(x, w, b, padding)
+
+
+O_BN_EPS = 1e-5
+
+
+def emu_bn(sd, pfx, x):
+    if any(pfx.endswith(t) for t in MASK_BN.values()):
+        return x
+    return _ORIG_BN(sd, pfx, x)
+
+
+def emu_osconv(sd, pfx, x, scale):
+    """osconv2d with the engine's folding: conv(fp16(x), fp16(W'')), W''[co][ci][tap] = fa[co] ca[ci] sa[tap] sum_k ka[k] W[k] in fp32."""
+    b, cin, h, w = x.shape
+    weight = sd[pfx + ".weight"]
+    cout = weight.size(1)
+    s = torch.cat((torch.ones(1, 1) / scale[0], torch.ones(1, 1) / scale[1]), 1).repeat(b, 1)
+    v = torch.cat([s, F.adaptive_avg_pool2d(x, 1).view(b, -1)], dim=1)
+    v = F.relu(F.linear(v, sd[pfx + ".scale_routing.0.weight"], sd[pfx + ".scale_routing.0.bias"]))
+    v = F.relu(F.linear(v, sd[pfx + ".scale_routing.2.weight"], sd[pfx + ".scale_routing.2.bias"]))
+    ca, fa, sa, ka = O.scale_attention(sd, pfx + ".attention", v.view(b, cin, 1, 1))
+    outs = []
+    for i in range(b):
+        agg = torch.sum(sa[i:i + 1] * ka[i:i + 1] * weight.unsqueeze(0), dim=1)[0]          # [cout, cin, 3, 3]
+        wpp = agg * fa[i].view(cout, 1, 1, 1) * ca[i].view(1, cin, 1, 1)
+        outs.append(conv_f16(x[i:i + 1], wpp, None, 1))
+    return torch.cat(outs, 0)
+
+
+def run(sd, lq, scale, cfg, emulate: bool):
+    O._conv, O.osconv2d, O._bn_eval = (emu_conv, emu_osconv, emu_bn) if emulate else (_ORIG_CONV, _ORIG_OSCONV, _ORIG_BN)
+    try:
+        return O.forward(sd, lq, scale, cfg)[0]
+    finally:
+        O._conv, O.osconv2d, O._bn_eval = _ORIG_CONV, _ORIG_OSCONV, _ORIG_BN
+
+
+def main():
+    torch.set_num_threads(8)
+    out = {}
+    with torch.no_grad():
+        for name, kw, h, w, sc in PRECISION_CASES:
+            net = SAVSR(**kw)
+            sd = synth.synth_state_dict(synth.manifest_of(net.state_dict()), seed=WEIGHT_SEED)
+            cfg = dict(net.cfg)
+            lq = synth.synth_clip(7, cfg["num_in_ch"], h, w, seed=CLIP_SEED)
+            ref = run(sd, lq, sc, cfg, False).numpy()
+            emu = run(sd, lq, sc, cfg, True).numpy()
+            d = np.abs(emu.astype(np.float64) - ref)
+            out[f"{name}/fp32"], out[f"{name}/fp16emu"] = ref, emu
+            out[f"{name}/drift"] = np.array([d.max(), d.mean()])
+            out[f"{name}/manifest"] = np.array(manifest_hash(synth.manifest_of(net.state_dict())))
+            print(name, tuple(ref.shape), "max-abs %.3e mean-abs %.3e" % (d.max(), d.mean()), flush=True)
+            if name == GT_CASE:
+                gt = synth_gt(ref)
+                out["gt/psnr_fp32"], out["gt/psnr_fp16emu"] = np.array(psnr_y(ref, gt)), np.array(psnr_y(emu, gt))
+                print("  PSNR-Y vs synthetic GT: fp32 %.6f fp16emu %.6f" % (psnr_y(ref, gt), psnr_y(emu, gt)))
+    np.savez_compressed(os.path.join(GOLD, "precision_outputs.npz"), **out)
+    print("wrote", os.path.getsize(os.path.join(GOLD, "precision_outputs.npz")) / 1e3, "KB")
+
+
+if __name__ == "__main__":
+    main()
