@@ -28,7 +28,7 @@ struct ConvParams {
 #define SAVSR_CONV_MAX_BATCH 24
 #endif
 constexpr int CONV_MAX_BATCH = SAVSR_CONV_MAX_BATCH;     // convs of identical geometry per launch: 6 (both propagation directions x 3 streams of a block) x up to 4 CLIPS of one
-                                       // (shape, scale) batched into the launches (round 5: 3, round 6: 4); 24 x 160 B of descriptors + 36 B = 3 876 B < the 4 KB a kernel argument may have
+                                       // (shape, scale) batched into the launches (round 5: 3, round 6: 4); 24 x 160 B of descriptors + 48 B = 3 888 B <= the 4 KB a kernel argument may have
 constexpr int CONV_WIDE_MIN_TILES = 200;       // 16-row tiles are used when a launch has at least this many of them ...
 constexpr int CONV_WIDE_MIN_TILES_TP = 100;    // ... or this many in throughput mode (SAVSR_CONV_DIRECT_THROUGHPUT)
 #ifndef SAVSR_CONV_BLOCKS
@@ -44,6 +44,7 @@ struct MultiConvParams {
     int nconv, ncob, ntx, nty;        // tile id = ((conv * ncob + cob) * nty + ty) * ntx + tx
     int wy_tiles, wy_full, wy_strip_l2;   // Winograd-y form: tiles per (conv, cob) = wy_full full tiles (ty * ntx + tx) + strip tiles over the image's last rows, each 2^wy_strip_l2 row pairs x (8 >> wy_strip_l2) segments (conv_wy.hip)
 };
+static_assert(sizeof(MultiConvParams) <= 4096, "MultiConvParams is passed by value as the conv kernels' argument: at most 4 KB");
 
 int launch_conv_wy(const MultiConvParams& mp, hipStream_t st, bool f16);      // conv_wy.hip: the Winograd F(2,3)-along-y form (3x3, cout % 64 == 0); f16: fp16 operands
 int conv_wy_prepare_device();

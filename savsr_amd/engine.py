@@ -60,19 +60,26 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self.pw16: Dict[str, torch.Tensor] = {}       # conv key -> fp16 image (direct form)
         self.pw16_wy: Dict[str, torch.Tensor] = {}    # conv key -> fp16 Winograd-y image
         self._conv_src: Dict[str, tuple] = {}         # conv key -> how its weight derives from the state_dict (packing.py::_conv_weight)
+        # Per-stream state: a sibling engine (clone_for_stream) owns its own `osc` scratch, `se_gate`, what _init_caches creates (buffer
+        # contexts, hr_sched), `nb` / `_bstride` / `form_nb`, `conv_algo`, `satu_events` / `_st`, `_siblings` / `_streams` and the lazily made
+        # `_cap_stream` / `_side_stream`.  EVERY other attribute is shared with the siblings by reference (packed weights, knobs, HR plans,
+        # census, host_stats, ...): a new shared attribute needs nothing in clone_for_stream, a new per-stream one is reset there.
         self.osc: Dict[str, dict] = {}      # osconv key -> tensors
         self.se: Dict[str, tuple] = {}
         self._keep: List[torch.Tensor] = []
         self._init_caches()
         self.satu_events: Optional[list] = None     # bench.py: (start, end, clips) HIP events around the SATU stage(s) of a launch sequence
         self._st: Optional[int] = None              # cached stream handle while a frame's launches are being issued (_stream)
+        self._cap_stream: Optional[torch.cuda.Stream] = None      # capture stream (_capture) and table stream (_plan_hr_tiling), made on first use
+        self._side_stream: Optional[torch.cuda.Stream] = None
         # Clips of ONE (shape, scale) batched into the launches (round 5).  A small clip is launch-latency-bound -- 330 dependent launches at ~11 us
         # each whatever its size (tools/probe_small_clips.py) -- and more than three streams do not help (a conv workgroup holds its CU's LDS).  With
         # nb clips in one launch sequence every named buffer holds nb copies (`_bstride`: bytes between them), every conv / OSConv descriptor is
-        # issued once per clip INSIDE the same batched launch (savsr_conv2d_batch takes 18 convs since ABI 26) and the per-clip kernels (SE gate,
+        # issued once per clip INSIDE the same batched launch (savsr_conv2d_batch takes 24 convs since ABI 27) and the per-clip kernels (SE gate,
         # SATU, tail, ...) are looped: 151 + 63 + nb x ~116 launches for nb clips instead of nb x 330.  Results are those of a one-clip launch
-        # sequence of the SAME flow bit for bit (the convs of a batched launch are independent and their form is chosen by `form_nb`, not `nb`).  forward_many groups equal (shape, scale) clips up to
-        # SAVSR_CLIP_BATCH (default 3) when the LR frame has at most SAVSR_CLIP_BATCH_MAX_PX pixels.
+        # sequence of the SAME flow bit for bit (the convs of a batched launch are independent and their form is chosen by `form_nb`, not `nb`).
+        # Which clips share a launch sequence: clip_unit (up to SAVSR_CLIP_BATCH, default 4, clips of one (shape, scale) when the LR frame has at
+        # most SAVSR_CLIP_BATCH_MAX_PX pixels).
         self.nb = 1
         # Clips the conv-form rule of a launch counts (conv_launch): `clip_batch` for every frame of the throughput flow whose shape is eligible for
         # batching, 1 otherwise -- whatever `nb` the launch sequence at hand really carries.  A unit of 1, 2 or 3 clips of a folder therefore takes
@@ -93,12 +100,13 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self._hr_choice: Dict[tuple, int] = {}      # (h, w, sh, sw) -> timed choice of the HR kernel's wave split; shared with the sibling engines
         self._hr_table = self._load_hr_plans()      # scale -> plan measured once per build of the SATU kernels (savsr_amd/hr_plans.json)
         self.use_graphs = kn.graphs
-        # SATU in the row-summed tail form (savsr_satu_hr_tail_q + savsr_tail_gather_q: 9 planes + seams between the HR stage and the
-        # tail instead of 27 planes); SAVSR_SATU_Q=0: the 27-plane form
-        self.satu_q = kn.satu_q and self.nf == 64 and self.nch == 3
-        # num_feat != 64 or num_in_ch != 3: the width-generic SATU (savsr_satu_nf_*, records of satu_nf_rec floats) writing 9 num_in_ch planes
-        # (tail_planes; 27 at num_in_ch = 3); num_feat 64 with 3 channels: the tuned kernels
+        # The SATU -> tail form every frame runs, chosen here once (the per-form methods _satu_lrcat ... _tail_clip dispatch on it):
+        #   "q"    row-summed: savsr_satu_hr_tail_q writes 9 planes + seams, savsr_tail_gather_q (num_feat 64, 3 channels)
+        #   "p27"  the tuned kernels' 27 tail-projected planes, savsr_tail_gather (SAVSR_SATU_Q=0)
+        #   "nf"   width-generic savsr_satu_nf_* (num_feat != 64 or num_in_ch != 3; records of satu_nf_rec floats): 9 num_in_ch planes
+        #          (tail_planes; 27 at num_in_ch = 3), savsr_tail_gather / savsr_tail_gather_nch
         self.satu_generic = self.nf != 64 or self.nch != 3
+        self.satu_form = "nf" if self.satu_generic else ("q" if kn.satu_q else "p27")
         self.tail_planes = 9 * self.nch
         self.satu_nf_rec = int(self.lib.savsr_satu_nf_lrcat_floats(self.nf)) if self.satu_generic else 0
         # static-weight 3x3 convs in the Winograd F(2,3)-along-y form (SAVSR_CONV_WINOGRAD_Y); SAVSR_CONV_WY=0: the direct kernel everywhere
@@ -119,6 +127,8 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self._siblings: List["HipEngine"] = []
         self._streams: List[torch.cuda.Stream] = []
         self._pack_all({k: v.detach() for k, v in state.items()})
+
+    satu_q = property(lambda self: self.satu_form == "q", doc="The row-summed SATU form (bench.py, tools/time_satu.py).")
 
     @staticmethod
     def num_feat_limit(nf: int) -> str:
@@ -173,40 +183,20 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             return {}
 
     def clone_for_stream(self) -> "HipEngine":
-        """A sibling engine that shares every read-only packed weight with this one but owns its
-        dynamic state (OSConv scratch / weight images, buffers, SATU tables, graphs), so two clips can be
-        in flight on two HIP streams."""
+        """A sibling engine for another HIP stream: a shallow copy of this one -- packed weights, knobs, HR plans, census and host_stats
+        shared by reference -- whose per-stream state (listed in __init__) is its own, so two launch units can be in flight on two streams."""
         e = HipEngine.__new__(HipEngine)
-        e.lib, e.dev, e.cfg, e.nf = self.lib, self.dev, self.cfg, self.nf
-        e.nch, e.sw, e.rw, e.satu_generic, e.tail_planes = self.nch, self.sw, self.rw, self.satu_generic, self.tail_planes
-        e.knobs = self.knobs
-        e.NB_MAX = self.NB_MAX
-        e.pw, e.se, e._keep = self.pw, self.se, self._keep
-        e.pw_wy, e.conv_wy, e.wy_min_tiles, e.wy_min_tiles_tp = self.pw_wy, self.conv_wy, self.wy_min_tiles, self.wy_min_tiles_tp
-        e.precision, e.pw16, e.pw16_wy, e._conv_src, e._sd_ref = self.precision, self.pw16, self.pw16_wy, self._conv_src, self._sd_ref
-        e.reuse_buffers, e.osconv_fused = self.reuse_buffers, self.osconv_fused
-        e.satu_t, e.satu_w, e.tail_w, e.tail_b, e.gamma, e.n_l2 = self.satu_t, self.satu_w, self.tail_w, self.tail_b, self.gamma, self.n_l2
-        e.iter_win, e.fwd_idx, e.bwd_idx = self.iter_win, self.fwd_idx, self.bwd_idx
-        e.satu_tail_t, e.satu_w_tail = self.satu_tail_t, self.satu_w_tail
-        e.satu_tailq_t, e.satu_w_tailq, e.satu_q = self.satu_tailq_t, self.satu_w_tailq, self.satu_q
-        e.satu_nf_t, e.satu_nf_w, e.satu_nf_rec = self.satu_nf_t, self.satu_nf_w, self.satu_nf_rec
-        e.nb, e._bstride, e.clip_batch, e.clip_batch_max_px = 1, {}, self.clip_batch, self.clip_batch_max_px
-        e.n_streams, e.n_streams_large, e.streams_large_px = self.n_streams, self.n_streams_large, self.streams_large_px
-        e.form_nb = 1
-        e.osc = {}
-        for k, ent in self.osc.items():
-            c = dict(ent)
-            c.update(e._osc_scratch(ent["cin"], ent["cout"], ent["knum"], ent["nunits"] * 8))
-            e.osc[k] = c
+        e.__dict__.update(self.__dict__)
+        # the per-stream state, and nothing else (_bstride first: _osc_scratch records the clip strides of the new scratch in it)
+        e.nb, e._bstride, e.form_nb, e.conv_algo = 1, {}, 1, _lib.CONV_DIRECT
+        e.osc = {k: dict(ent, **e._osc_scratch(ent["cin"], ent["cout"], ent["knum"], ent["nunits"] * 8)) for k, ent in self.osc.items()}
         e.se_gate = torch.empty_like(self.se_gate)
-        e._init_caches()
+        e._init_caches()               # its own buffer contexts and hr_sched; the byte budget, SATU axis tables and count caps stay shared
         e.max_shapes, e.max_scales, e._budget, e._axes = self.max_shapes, self.max_scales, self._budget, self._axes
         self._budget["engines"].append(weakref.ref(e))
-        e.satu_events, e.use_graphs, e.census, e._st = None, self.use_graphs, self.census, None
-        e.capture_after, e.host_stats = self.capture_after, self.host_stats
-        e.conv_algo = _lib.CONV_DIRECT
-        e._hr_choice, e._hr_table = self._hr_choice, self._hr_table
+        e.satu_events, e._st = None, None
         e._siblings, e._streams = [], []
+        e._cap_stream = e._side_stream = None
         return e
 
     PRECISIONS = ("fp32", "fp16")
@@ -337,19 +327,10 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self._select(lq.shape, scale)
         c = self._stage_body(lq, scale)
         out = torch.empty(self.nch, c["H"], c["W"], device=self.dev)
-        if self.satu_generic:
-            lrcat = self.satu_nf_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"])
-            self._stage_satu(c, scale)
-            return {"satu_lr_us": timer(lambda: self.satu_nf_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"])),
-                    "satu_hr_us": timer(lambda: self.satu_nf_hr(lrcat, c["h"], c["w"], scale, c["p27"], c["plane"])),
-                    "tail_us": timer(lambda: self._stage_tail(c, lq, out))}
-        q = self.satu_q
-        lrcat = self.satu_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], tail_form=True, q=q)
+        lrcat = self._satu_lr_clip(c)
         self._stage_satu(c, scale)
-        hr = (lambda: self.satu_hr(lrcat, c["h"], c["w"], scale, c["q9"], c["plane"], tail_form=True, seam=c["seam"])) if q else \
-            (lambda: self.satu_hr(lrcat, c["h"], c["w"], scale, c["p27"], c["plane"], tail_form=True))
-        return {"satu_lr_us": timer(lambda: self.satu_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], tail_form=True, q=q)),
-                "satu_hr_us": timer(hr),
+        return {"satu_lr_us": timer(lambda: self._satu_lr_clip(c)),
+                "satu_hr_us": timer(lambda: self._satu_hr_clip(lrcat, c, scale)),
                 "tail_us": timer(lambda: self._stage_tail(c, lq, out))}
 
     # ------------------------------------------------------------------ whole frame
@@ -445,14 +426,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         hfeat = self.conv("conv_last", [hcur], self.full(self.buf("hfeat", hp, wp, nf)), hp, wp, res1=share)   # :733-734
         self.seal_buffers()                              # the LR buffer plan of this shape is final (align / hfeat / SATU buffers are never shared)
         H, W = get_hw(h_in, w_in, scale)
-        plane = self.hr_plane(H, W)
-        d = dict(align=align, hfeat=hfeat, wp=wp, h=h_in, w=w_in, H=H, W=W, plane=plane)
-        if self.satu_q:
-            d["q9"] = self.sbuf("satu.q9", 9, plane)
-            d["seam"] = self.sbuf("satu.seam", self.seam_floats(H, W))
-        else:                # (the 27 planes -- 99.5 MB at 720x1280 -- exist only in the 27-plane form; taps allocate them on demand)
-            d["p27"] = self.sbuf("satu.p27", self.tail_planes, plane)      # (9 num_in_ch planes of the width-generic form)
-        return d
+        return dict(align=align, hfeat=hfeat, wp=wp, h=h_in, w=w_in, H=H, W=W, **self._satu_outputs(H, W))
 
     def _pack_windows(self, lq_ptr: int, out_ptr: int, T: int, h: int, w: int, hp: int, wp: int, st: int) -> None:
         """Input windows of one clip (savsr_arch.py:448-454, :661-668, :670-690): the shipped 3-channel, 3-frame form through its own
@@ -462,50 +436,88 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         else:
             _lib.check(self.lib.savsr_pack_windows_nch(lq_ptr, out_ptr, T, self.nch, self.sw, h, w, hp, wp, st), "savsr_pack_windows_nch")
 
+    # ------------------------------------------------------------------ SATU -> tail, per form (`satu_form`; `form` = another form's for taps)
+    _LRCAT = {"q": "satu.lrcat_tailq", "p27": "satu.lrcat_tail", "nf": "satu.lrcat_nf"}
+
+    def _satu_lrcat(self, h: int, w: int, form: Optional[str] = None) -> torch.Tensor:
+        """The LRcat buffer of a form's LR stage: the one spelling of its name and record (satu_lr / satu_nf_lr write it)."""
+        form = form or self.satu_form
+        return self.buf(self._LRCAT[form], h, w, self.satu_nf_rec if form == "nf" else _lib.SATU_LRCAT_TAIL)
+
+    def _satu_outputs(self, H: int, W: int, form: Optional[str] = None) -> dict:
+        """What a form's HR stage writes and its tail reads: q9 + seam, or p27 with tail_planes rows (the 27 planes -- 99.5 MB at 720x1280
+        -- exist only where a form needs them)."""
+        plane = self.hr_plane(H, W)
+        if (form or self.satu_form) == "q":
+            return dict(plane=plane, q9=self.sbuf("satu.q9", 9, plane), seam=self.sbuf("satu.seam", self.seam_floats(H, W)))
+        return dict(plane=plane, p27=self.sbuf("satu.p27", self.tail_planes, plane))
+
+    def _satu_lr_clip(self, c: dict, b: int = 0, form: Optional[str] = None) -> torch.Tensor:
+        """LR stage of clip b of a launch sequence (crops of :737 via (row pitch, h, w)) -> its LRcat buffer."""
+        form = form or self.satu_form
+        if form == "nf":
+            return self.satu_nf_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], b=b)
+        return self.satu_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], tail_form=True, q=form == "q", b=b)
+
+    def _satu_hr_clip(self, lrcat: torch.Tensor, c: dict, scale, b: int = 0, form: Optional[str] = None):
+        """HR stage of clip b into the form's outputs (the row-summed form adds the tail's horizontal taps itself: 9 planes + seams)."""
+        form = form or self.satu_form
+        if form == "nf":
+            self.satu_nf_hr(lrcat, c["h"], c["w"], scale, c["p27"], c["plane"], b=b)
+        elif form == "q":
+            self.satu_hr(lrcat, c["h"], c["w"], scale, c["q9"], c["plane"], tail_form=True, seam=c["seam"], b=b)
+        else:
+            self.satu_hr(lrcat, c["h"], c["w"], scale, c["p27"], c["plane"], tail_form=True, b=b)
+
+    def _satu_clip(self, c: dict, scale, b: int = 0, form: Optional[str] = None):
+        """LR then HR stage of clip b."""
+        self._satu_hr_clip(self._satu_lr_clip(c, b, form), c, scale, b, form)
+
+    def _satu_prepare(self, h: int, w: int, scale):
+        """The HR stage on the form's own LRcat / output buffers, outside a capture: the SATU tables of (size, scale) and, where one is
+        needed, the measured choice of the HR launch plan (the buffers' contents do not matter)."""
+        c = dict(h=h, w=w)
+        lrcat = self._satu_lrcat(h, w)
+        c.update(self._satu_outputs(*get_hw(h, w, scale)))
+        self._satu_hr_clip(lrcat, c, scale)
+
+    def _tail_clip(self, c: dict, lq: torch.Tensor, out: torch.Tensor, b: int = 0):
+        """What is left of :738-739 for clip b (lq [nb, T, nch, h, w] and out [nb, nch, H, W] contiguous): the nine shifted taps per colour,
+        the tail bias, the bilinear residual."""
+        nch, h, w, H, W = self.nch, c["h"], c["w"], c["H"], c["W"]
+        T = lq.shape[-4]
+        center = T // 2 if self.cfg["center_frame_idx"] is None else self.cfg["center_frame_idx"]
+        cptr = lq.data_ptr() + 4 * (b * T + center) * nch * h * w          # unpadded centre frame (:696)
+        optr = out.data_ptr() + 4 * b * nch * H * W
+        tb, st = self.tail_b.data_ptr(), self._stream()
+        if self.satu_form == "q":
+            q9, seam = c["q9"], c["seam"]
+            _lib.check(self.lib.savsr_tail_gather_q(q9.data_ptr() + b * self._bs(q9), c["plane"], seam.data_ptr() + b * self._bs(seam), seam.numel(),
+                                                    tb, cptr, h, w, H, W, optr, st), "savsr_tail_gather_q")
+            return
+        p = c["p27"].data_ptr() + b * self._bs(c["p27"])
+        if nch != 3:           # the 9 nch planes of the width-generic HR stage
+            _lib.check(self.lib.savsr_tail_gather_nch(p, c["plane"], nch, tb, cptr, h, w, H, W, optr, st), "savsr_tail_gather_nch")
+        else:
+            _lib.check(self.lib.savsr_tail_gather(p, c["plane"], tb, cptr, h, w, H, W, optr, st), "savsr_tail_gather")
+
     def _stage_satu(self, c: dict, scale):
         with HipEngine._StageStream(self):
             return self._stage_satu_impl(c, scale)
 
     def _stage_satu_impl(self, c: dict, scale):
-        """SATU in the tail-projected form (savsr_arch.py:315-376 with the channel contraction of :738 folded in): -> P [27][H][W]
-        (the width-generic form: [9 num_in_ch][H][W])."""
-        if self.satu_generic:          # the width-generic kernels
-            for b in range(self.nb):
-                lrcat = self.satu_nf_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], b=b)
-                self.satu_nf_hr(lrcat, c["h"], c["w"], scale, c["p27"], c["plane"], b=b)
-            return
-        for b in range(self.nb):       # (per-clip kernels: looped over the clips of a batched launch sequence)
-            if self.satu_q:        # row-summed form: the HR stage adds the horizontal taps itself -> 9 planes + seams
-                lrcat = self.satu_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], tail_form=True, q=True, b=b)
-                self.satu_hr(lrcat, c["h"], c["w"], scale, c["q9"], c["plane"], tail_form=True, seam=c["seam"], b=b)
-                continue
-            lrcat = self.satu_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], tail_form=True, b=b)       # crops of :737 via (row pitch, h, w)
-            self.satu_hr(lrcat, c["h"], c["w"], scale, c["p27"], c["plane"], tail_form=True, b=b)
+        """SATU in the tail-projected form (savsr_arch.py:315-376 with the channel contraction of :738 folded in), per clip of the launch
+        sequence."""
+        for b in range(self.nb):
+            self._satu_clip(c, scale, b)
 
     def _stage_tail(self, c: dict, lq: torch.Tensor, out: torch.Tensor):
         with HipEngine._StageStream(self):
             return self._stage_tail_impl(c, lq, out)
 
     def _stage_tail_impl(self, c: dict, lq: torch.Tensor, out: torch.Tensor):
-        """What is left of :738-739: the nine shifted taps per colour, the tail bias, the bilinear residual."""
-        cfg, nch = self.cfg, self.nch
-        T = lq.shape[-4]
-        center = T // 2 if cfg["center_frame_idx"] is None else cfg["center_frame_idx"]
-        # (lq [nb, T, nch, h, w] and out [nb, nch, H, W] are contiguous)
-        clip_bytes, out_bytes = 4 * T * nch * c["h"] * c["w"], 4 * nch * c["H"] * c["W"]
         for b in range(self.nb):
-            cptr = lq.data_ptr() + b * clip_bytes + 4 * center * nch * c["h"] * c["w"]    # unpadded centre frame (:696)
-            if nch != 3:           # the 9 nch planes of the width-generic HR stage
-                _lib.check(self.lib.savsr_tail_gather_nch(c["p27"].data_ptr() + b * self._bs(c["p27"]), c["plane"], nch, self.tail_b.data_ptr(), cptr,
-                                                          c["h"], c["w"], c["H"], c["W"], out.data_ptr() + b * out_bytes, self._stream()), "savsr_tail_gather_nch")
-                continue
-            if self.satu_q:
-                _lib.check(self.lib.savsr_tail_gather_q(c["q9"].data_ptr() + b * self._bs(c["q9"]), c["plane"], c["seam"].data_ptr() + b * self._bs(c["seam"]),
-                                                        c["seam"].numel(), self.tail_b.data_ptr(), cptr,
-                                                        c["h"], c["w"], c["H"], c["W"], out.data_ptr() + b * out_bytes, self._stream()), "savsr_tail_gather_q")
-                continue
-            _lib.check(self.lib.savsr_tail_gather(c["p27"].data_ptr() + b * self._bs(c["p27"]), c["plane"], self.tail_b.data_ptr(), cptr,
-                                                  c["h"], c["w"], c["H"], c["W"], out.data_ptr() + b * out_bytes, self._stream()), "savsr_tail_gather")
+            self._tail_clip(c, lq, out, b)
 
     def _satu_standalone(self, c: dict, scale) -> torch.Tensor:
         """STAUpsample.forward as such ([64][H][W]; tests / taps only -- the product path never materialises it)."""
@@ -541,11 +553,11 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         if taps is not None:                    # channel-last [hp][wp][64] tensors; SATU output planar
             taps["align_feat"] = c["align"].t
             taps["h_feat"] = c["hfeat"].t
-            if not self.satu_generic:       # (STAUpsample's own output: a tap of the tuned 64-wide kernels only; the generic form leaves it out)
+            if self.satu_form != "nf":      # (STAUpsample's own output: a tap of the tuned 64-wide kernels only; the generic form leaves it out)
                 taps["satu"] = self._satu_standalone(c, scale)
-            if self.satu_q:     # the 27-plane form beside the row-summed one the frame runs (taps only)
-                c["p27"] = self.sbuf("satu.p27", _lib.TAIL_PLANES, c["plane"])
-                self.satu_hr(self.satu_lr(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], tail_form=True), c["h"], c["w"], scale, c["p27"], c["plane"], tail_form=True)
+            if "p27" not in c:              # the 27-plane form beside the row-summed one the frame runs (taps only)
+                c.update(self._satu_outputs(c["H"], c["W"], "p27"))
+                self._satu_clip(c, scale, 0, "p27")
             taps["p27"] = c["p27"][:, : c["H"] * c["W"]].view(-1, c["H"], c["W"])      # (9 num_in_ch planes)
         self._stage_tail(c, lq, out)
         return out
@@ -572,8 +584,12 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         shared every launch when the shape is eligible for batching (`form_nb`).  Each flow is bitwise reproducible and independent of the
         grouping; the two differ from each other by the conv forms' rounding (~1e-5)."""
         self.conv_algo = _lib.CONV_DIRECT_THROUGHPUT if throughput else _lib.CONV_DIRECT
-        h, w = int(lq.shape[-2]), int(lq.shape[-1])
-        self.form_nb = self.clip_batch if (throughput and self.cfg["interval"] == 0 and h * w <= self.clip_batch_max_px) else 1
+        self.form_nb = self.clip_unit(int(lq.shape[-2]), int(lq.shape[-1])) if throughput else 1
+
+    def clip_unit(self, h: int, w: int) -> int:
+        """Clips of one (shape, scale) that share a launch sequence (see `nb`) for LR frames of h x w: `clip_batch` where the frame is small
+        enough to be launch-latency-bound, 1 otherwise (and for clips sampled with an interval)."""
+        return self.clip_batch if (self.cfg["interval"] == 0 and h * w <= self.clip_batch_max_px) else 1
 
     def _forward_graphed_impl(self, lq: torch.Tensor, scale, out: torch.Tensor, throughput: bool = False):
         sc = self._select(lq.shape, scale)
@@ -598,17 +614,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             # exactly once, into the capture, and the buffers it names are allocated there (arena chunks from the graphs' pool).
             import time as _time
             _t0 = _time.perf_counter()
-            h_, w_ = int(lq.shape[-2]), int(lq.shape[-1])
-            H_, W_ = get_hw(h_, w_, scale)
-            plane_ = self.hr_plane(H_, W_)
-            if self.satu_generic:  # (no plan to measure: this evaluates the tables outside the capture)
-                self.satu_nf_hr(self.buf("satu.lrcat_nf", h_, w_, self.satu_nf_rec), h_, w_, scale, self.sbuf("satu.p27", self.tail_planes, plane_), plane_)
-            elif self.satu_q:
-                self.satu_hr(self.buf("satu.lrcat_tailq", h_, w_, _lib.SATU_LRCAT_TAIL), h_, w_, scale, self.sbuf("satu.q9", 9, plane_), plane_,
-                             tail_form=True, seam=self.sbuf("satu.seam", self.seam_floats(H_, W_)))
-            else:
-                self.satu_hr(self.buf("satu.lrcat_tail", h_, w_, _lib.SATU_LRCAT_TAIL), h_, w_, scale,
-                             self.sbuf("satu.p27", _lib.TAIL_PLANES, plane_), plane_, tail_form=True)
+            self._satu_prepare(int(lq.shape[-2]), int(lq.shape[-1]), scale)
             # (no host synchronisation here: the capture stream waits for this one -- `_capture` --, and a plan that had to be MEASURED has
             # synchronised on its own events.  A sync per new context stalled the host behind the units already queued on this stream, 38 ms a
             # time with three streams in flight: 2.6 s of a 6.5 s cold pass of the YAML workflow, during which the other streams got nothing new.)
@@ -662,7 +668,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         (device-wide synchronize + gc.collect() + empty_cache() per graph: tens of ms, and the emptied cache turns the next
         shape's allocations into fresh hipMallocs) -- a YAML sweep captures one graph set per (folder, scale, stream)."""
         cur = torch.cuda.current_stream()
-        if getattr(self, "_cap_stream", None) is None:
+        if self._cap_stream is None:
             self._cap_stream = torch.cuda.Stream(device=self.dev)
         cap = self._cap_stream
         cap.wait_stream(cur)
@@ -697,6 +703,19 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             self._streams.append(torch.cuda.Stream(device=self.dev))
         return [self] + self._siblings
 
+    def _fan_out(self, units: list, ns: int, run) -> None:
+        """Deal launch units round-robin over `ns` HIP streams: unit u is issued by run(engine, unit) under stream u % ns with that stream's
+        engine (this one or a sibling).  The streams first wait for the caller's stream; the caller's stream then waits for all of them."""
+        engines = self._ensure_streams(ns)
+        cur = torch.cuda.current_stream()
+        for k in range(ns):
+            self._streams[k].wait_stream(cur)
+        for u, unit in enumerate(units):
+            with torch.cuda.stream(self._streams[u % ns]):
+                run(engines[u % ns], unit)
+        for k in range(ns):
+            cur.wait_stream(self._streams[k])
+
     def forward_many(self, items) -> List[torch.Tensor]:
         """A stream of independent clips of MIXED shapes / scales (BASELINE config 5): items = [(lq [T, c, h, w], (sh, sw))] ->
         [out [c, H, W]] (c = num_in_ch).  Clip i runs on HIP stream i % n_streams with that stream's sibling engine, so small clips (whose ~360
@@ -712,55 +731,40 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
                 self._set_flow(lq, True)
                 outs.append(self.forward_one(lq, sc, o))
             return outs
-        # (a lone clip, or SAVSR_STREAMS=1, takes the throughput flow too: what forward_many returns for a clip does not depend on how many
-        # came with it or on how many streams carry them)
-        # Launch units: clips of equal (shape, scale) whose LR frame is small enough to be launch-latency-bound go out up to `clip_batch` at a
-        # time in ONE launch sequence (see `nb`); everything else one clip per unit, as before.  Units are dealt round-robin over the streams.
-        units: List[List[int]] = []
-        if self.clip_batch > 1 and self.cfg["interval"] == 0:
-            from collections import OrderedDict
-            groups: "OrderedDict[tuple, List[int]]" = OrderedDict()
-            for i, (lq, sc) in enumerate(items):
-                if lq.shape[-2] * lq.shape[-1] <= self.clip_batch_max_px:
-                    groups.setdefault((tuple(lq.shape), float(sc[0]), float(sc[1])), []).append(i)
-                else:
-                    units.append([i])
-            for idxs in groups.values():       # balanced units (10 clips -> 3 + 3 + 2 + 2, not 3 + 3 + 3 + 1: a lone clip would need a capture of its own)
-                k = -(-len(idxs) // self.clip_batch)
-                base, rem, a = len(idxs) // k, len(idxs) % k, 0
-                for u in range(k):
-                    n = base + (1 if u < rem else 0)
-                    units.append(idxs[a:a + n])
-                    a += n
-            units.sort(key=lambda u: u[0])
-        else:
-            units = [[i] for i in range(len(items))]
-        ns = min(self.streams_for(sum(lq.shape[-2] * lq.shape[-1] for lq, _ in items) / len(items)), len(units))
-        engines = self._ensure_streams(max(ns, 1))
-        cur = torch.cuda.current_stream()
-        outs: List[Optional[torch.Tensor]] = [None] * len(items)
         for lq, sc in items:
             if lq.device != self.dev:
                 raise RuntimeError(f"input on {lq.device}, engine on {self.dev}")
-        for k in range(ns):
-            self._streams[k].wait_stream(cur)
-        for u, unit in enumerate(units):
-            k = u % ns
+        # (a lone clip, or SAVSR_STREAMS=1, takes the throughput flow too: what forward_many returns for a clip does not depend on how many
+        # came with it or on how many streams carry them)
+        # Launch units: clips of equal (shape, scale) go out up to clip_unit at a time in ONE launch sequence (see `nb`), in balanced units;
+        # everything else one clip per unit.
+        units: List[List[int]] = []
+        groups: Dict[tuple, List[int]] = {}
+        for i, (lq, sc) in enumerate(items):
+            if self.clip_unit(lq.shape[-2], lq.shape[-1]) > 1:
+                groups.setdefault((tuple(lq.shape), float(sc[0]), float(sc[1])), []).append(i)
+            else:
+                units.append([i])
+        for idxs in groups.values():
+            units += [idxs[a:b] for a, b in balanced_units(len(idxs), self.clip_batch)]
+        units.sort(key=lambda u: u[0])
+        outs: List[Optional[torch.Tensor]] = [None] * len(items)
+
+        def run(eng: "HipEngine", unit: List[int]):
             sc = items[unit[0]][1]
             H, W = get_hw(items[unit[0]][0].shape[-2], items[unit[0]][0].shape[-1], sc)
-            with torch.cuda.stream(self._streams[k]):
-                if len(unit) == 1:
-                    i = unit[0]
-                    outs[i] = torch.empty(self.nch, H, W, device=self.dev, dtype=torch.float32)
-                    engines[k]._forward_graphed(items[i][0].to(torch.float32).contiguous(), sc, outs[i], throughput=True)
-                else:
-                    lqb = torch.stack([items[i][0].to(torch.float32) for i in unit], 0)
-                    outb = torch.empty(len(unit), self.nch, H, W, device=self.dev, dtype=torch.float32)
-                    engines[k]._forward_graphed(lqb, sc, outb, throughput=True)
-                    for j, i in enumerate(unit):
-                        outs[i] = outb[j]
-        for k in range(ns):
-            cur.wait_stream(self._streams[k])
+            if len(unit) == 1:
+                i = unit[0]
+                outs[i] = torch.empty(self.nch, H, W, device=self.dev, dtype=torch.float32)
+                eng._forward_graphed(items[i][0].to(torch.float32).contiguous(), sc, outs[i], throughput=True)
+            else:
+                lqb = torch.stack([items[i][0].to(torch.float32) for i in unit], 0)
+                outb = torch.empty(len(unit), self.nch, H, W, device=self.dev, dtype=torch.float32)
+                eng._forward_graphed(lqb, sc, outb, throughput=True)
+                for j, i in enumerate(unit):
+                    outs[i] = outb[j]
+        self._fan_out(units, min(self.streams_for(sum(lq.shape[-2] * lq.shape[-1] for lq, _ in items) / len(items)), len(units)), run)
+        cur = torch.cuda.current_stream()
         for o in {id(t._base if t._base is not None else t): (t._base if t._base is not None else t) for t in outs if t is not None}.values():
             o.record_stream(cur)       # allocated under a side stream, handed to the caller's: its block is not recycled on the side stream while `cur` still reads it
         return outs
@@ -769,10 +773,10 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         """The sequence path (SAVSR.upscale_video): frames [N, h, w, c] uint8 or [N, c, h, w] fp32 on the device, windows[i] = the
         num_frame frame indices of output frame i in clip order (harness.window_indices) -> [len(windows), c, H, W] fp32, or
         [len(windows), H, W, c] uint8 (out_u8: tensor2img(x, rgb2bgr=False) per frame, savsr_video_quantize_u8).
-        Launch units and streams are forward_many's (up to `clip_batch` consecutive windows per unit where the LR frame is eligible,
-        balanced; units dealt round-robin over `streams_for` streams; throughput flow), so frame i equals forward_many on the gathered
-        window i bit for bit.  A unit's windows are gathered from `frames` by savsr_video_gather_u8 / _f32 into a unit-sized fp32 clip
-        batch on the unit's stream; nothing is gathered or converted on the host."""
+        Launch units and streams are forward_many's (up to `clip_unit` consecutive windows per unit, balanced; units dealt round-robin over
+        `streams_for` streams; throughput flow), so frame i equals forward_many on the gathered window i bit for bit.  A unit's windows are
+        gathered from `frames` by savsr_video_gather_u8 / _f32 into a unit-sized fp32 clip batch on the unit's stream; nothing is gathered
+        or converted on the host."""
         self._ensure_precision()
         if frames.device != self.dev:
             raise RuntimeError(f"input on {frames.device}, engine on {self.dev}")
@@ -794,42 +798,27 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             return out
         if T > _lib.VIDEO_MAX_SLOTS:
             raise ValueError(f"num_frame = {T}: the window gather takes at most {_lib.VIDEO_MAX_SLOTS} frames per launch")
-        cb = self.clip_batch if (self.use_graphs and self.cfg["interval"] == 0 and h * w <= self.clip_batch_max_px) else 1
-        cb = max(1, min(cb, _lib.VIDEO_MAX_SLOTS // T))
-        k_units = -(-n // cb)
-        base, rem = n // k_units, n % k_units
-        units, a = [], 0
-        for u in range(k_units):             # balanced, as forward_many's (10 windows -> 3 + 3 + 2 + 2)
-            m = base + (1 if u < rem else 0)
-            units.append((a, a + m))
-            a += m
-        ns = min(self.streams_for(h * w), len(units)) if self.use_graphs else 1
-        engines = self._ensure_streams(ns)
-        cur = torch.cuda.current_stream()
-        for k in range(ns):
-            self._streams[k].wait_stream(cur)
+        cb = self.clip_unit(h, w) if self.use_graphs else 1
+        units = balanced_units(n, max(1, min(cb, _lib.VIDEO_MAX_SLOTS // T)))
         gather = self.lib.savsr_video_gather_u8 if u8 else self.lib.savsr_video_gather_f32
-        for u, (i0, i1) in enumerate(units):
-            k = u % ns
-            st = self._streams[k]
+
+        def run(eng: "HipEngine", unit: Tuple[int, int]):
+            i0, i1 = unit
             nb = i1 - i0
+            st = torch.cuda.current_stream().cuda_stream
             idx = [f for win in windows[i0:i1] for f in win]
-            with torch.cuda.stream(st):
-                lqb = torch.empty(nb, T, c, h, w, device=self.dev, dtype=torch.float32)
-                _lib.check(gather(frames.data_ptr(), N, c, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), lqb.data_ptr(), st.cuda_stream),
-                           "savsr_video_gather")
-                o = torch.empty(nb, c, H, W, device=self.dev, dtype=torch.float32) if out_u8 else out[i0:i1]
-                lq_u, o_u = (lqb[0], o[0]) if nb == 1 else (lqb, o)
-                if self.use_graphs:
-                    engines[k]._forward_graphed(lq_u, scale, o_u, throughput=True)
-                else:                          # SAVSR_GRAPHS=0 (diagnostics): forward_many's eager flow, one window at a time
-                    self._set_flow(lq_u, True)
-                    self.forward_one(lq_u, scale, o_u)
-                if out_u8:
-                    _lib.check(self.lib.savsr_video_quantize_u8(o.data_ptr(), nb, c, H, W, out[i0:i1].data_ptr(), st.cuda_stream),
-                               "savsr_video_quantize_u8")
-        for k in range(ns):
-            cur.wait_stream(self._streams[k])
+            lqb = torch.empty(nb, T, c, h, w, device=self.dev, dtype=torch.float32)
+            _lib.check(gather(frames.data_ptr(), N, c, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), lqb.data_ptr(), st), "savsr_video_gather")
+            o = torch.empty(nb, c, H, W, device=self.dev, dtype=torch.float32) if out_u8 else out[i0:i1]
+            lq_u, o_u = (lqb[0], o[0]) if nb == 1 else (lqb, o)
+            if self.use_graphs:
+                eng._forward_graphed(lq_u, scale, o_u, throughput=True)
+            else:                          # SAVSR_GRAPHS=0 (diagnostics): forward_many's eager flow, one window at a time (one stream)
+                eng._set_flow(lq_u, True)
+                eng.forward_one(lq_u, scale, o_u)
+            if out_u8:
+                _lib.check(self.lib.savsr_video_quantize_u8(o.data_ptr(), nb, c, H, W, out[i0:i1].data_ptr(), st), "savsr_video_quantize_u8")
+        self._fan_out(units, min(self.streams_for(h * w), len(units)) if self.use_graphs else 1, run)
         return out
 
     def forward(self, lq: torch.Tensor, scale, taps: Optional[dict] = None) -> torch.Tensor:
@@ -846,23 +835,21 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         if b >= 2 and self.n_streams >= 2 and self.use_graphs and taps is None:
             # clips are independent (no cross-clip state, savsr_arch.py:705-706): keep n_streams of them in flight
             # on separate HIP streams so one clip's load/store-bound kernel phases overlap another's MFMA phases
-            # ... and up to `clip_batch` consecutive clips per launch sequence (see `nb`): the batch shares one (shape, scale)
-            cb = self.clip_batch if (self.cfg["interval"] == 0 and h * w <= self.clip_batch_max_px) else 1
+            # ... and up to `clip_unit` consecutive clips per launch sequence (see `nb`): the batch shares one (shape, scale).  Consecutive
+            # units of clip_unit clips, not balanced ones (16 -> 4 + 4 + 4 + 4, 10 -> 4 + 4 + 2).
+            cb = self.clip_unit(h, w)
             units = [(i0, min(i0 + cb, b)) for i0 in range(0, b, cb)]
             ns = min(self.streams_for(h * w), len(units))
-            engines = self._ensure_streams(ns)
-            cur = torch.cuda.current_stream()
-            for k in range(ns):
-                self._streams[k].wait_stream(cur)
-                engines[k].satu_events = self.satu_events
-            for u, (i0, i1) in enumerate(units):
-                with torch.cuda.stream(self._streams[u % ns]):
-                    if i1 - i0 == 1:
-                        engines[u % ns]._forward_graphed(lq[i0], scale, out[i0], throughput=True)
-                    else:                # (contiguous slices of the batch: no copy)
-                        engines[u % ns]._forward_graphed(lq[i0:i1], scale, out[i0:i1], throughput=True)
-            for k in range(ns):
-                cur.wait_stream(self._streams[k])
+            for e in self._ensure_streams(ns)[:ns]:       # (bench.py: the SATU stages of every stream's units are timed)
+                e.satu_events = self.satu_events
+
+            def run(eng: "HipEngine", unit: Tuple[int, int]):
+                i0, i1 = unit
+                if i1 - i0 == 1:
+                    eng._forward_graphed(lq[i0], scale, out[i0], throughput=True)
+                else:                # (contiguous slices of the batch: no copy)
+                    eng._forward_graphed(lq[i0:i1], scale, out[i0:i1], throughput=True)
+            self._fan_out(units, ns, run)
             return out
         self.conv_algo, self.form_nb = _lib.CONV_DIRECT, 1
         for i in range(b):      # samples are independent (OSConv groups=b, savsr_arch.py:166-167)
@@ -871,3 +858,15 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             else:
                 self.forward_one(lq[i], scale, out[i], taps if i == 0 else None)
         return out
+
+
+def balanced_units(n: int, cap: int) -> List[Tuple[int, int]]:
+    """[start, end) ranges of n items in the fewest units of at most `cap` items, their sizes as even as possible, larger ones first:
+    10 items at cap 3 -> 3 + 3 + 2 + 2, not 3 + 3 + 3 + 1 (a lone clip would need a capture of its own)."""
+    k = -(-n // cap)
+    units, a = [], 0
+    for u in range(k):
+        m = n // k + (1 if u < n % k else 0)
+        units.append((a, a + m))
+        a += m
+    return units

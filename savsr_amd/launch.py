@@ -302,7 +302,7 @@ class Launcher:
         # The tables depend on (size, scale, weights) only, not on anything the compute stream holds: they are evaluated and read
         # back on a side stream, so the read-back's host wait does not stand behind the frames still in flight.
         cur = torch.cuda.current_stream()
-        if getattr(self, "_side_stream", None) is None:
+        if self._side_stream is None:
             self._side_stream = torch.cuda.Stream(device=self.dev)
         with torch.cuda.stream(self._side_stream):
             # (allocated under the side stream: a block the allocator recycles from the compute stream could still have work
@@ -377,7 +377,7 @@ class Launcher:
         the row-summed form (savsr_satu_hr_tail_q)."""
         assert x.pix == st.pix
         if tail_form:
-            lrcat = self.buf("satu.lrcat_tailq" if q else "satu.lrcat_tail", h, w, _lib.SATU_LRCAT_TAIL)
+            lrcat = self._satu_lrcat(h, w, "q" if q else "p27")
             fn, wts = self.lib.savsr_satu_lr_stage_tail, (self.satu_w_tailq if q else self.satu_w_tail)
         else:
             lrcat = self.buf("satu.lrcat", h, w, _lib.SATU_LRCAT)
@@ -457,7 +457,7 @@ class Launcher:
     def satu_nf_lr(self, x: Src, st: Src, row_px: int, h: int, w: int, b: int = 0) -> torch.Tensor:
         """LR stage of the width-generic SATU (num_feat != 64; savsr_satu_nf_lr_stage) -> LRcat [h][w][satu_nf_rec]."""
         assert x.pix == st.pix
-        lrcat = self.buf("satu.lrcat_nf", h, w, self.satu_nf_rec)
+        lrcat = self._satu_lrcat(h, w, "nf")
         _lib.check(self.lib.savsr_satu_nf_lr_stage(C.byref(self.satu_nf_w), x.ptr + b * x.bs, st.ptr + b * st.bs, x.pix, row_px, h, w,
                                                    lrcat.data_ptr() + b * self._bs(lrcat), self._stream()), "savsr_satu_nf_lr_stage")
         return lrcat

@@ -167,8 +167,7 @@ class VideoBaseModel(BaseModel):
             # clips per launch sequence only where the engine batches them (small frames); large frames keep the one-clip-per-stream rule
             if many and hasattr(eng, "streams_for"):
                 streams = max(1, int(eng.streams_for(h * w)))             # (fewer launch units in flight for large frames)
-            unit = max(1, int(getattr(eng, "clip_batch", 1))) if (many and h * w <= int(getattr(eng, "clip_batch_max_px", 0))
-                                                                  and eng.cfg.get("interval", 0) == 0) else 1
+            unit = int(eng.clip_unit(h, w)) if (many and hasattr(eng, "clip_unit")) else 1
             for a, b in (chunk_block(k1 - k, streams, unit) if many else [(i, i + 1) for i in range(k1 - k)]):
                 k0, k_end = k + a, k + b
                 vals = [first if idx == mine[k] else dataset[idx] for idx in mine[k0:k_end]]

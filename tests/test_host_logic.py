@@ -367,3 +367,27 @@ def test_engine_config_reads_every_switch_once(monkeypatch):
     for mod in ("engine", "cache", "launch", "packing"):
         src = open(os.path.join(root, "savsr_amd", mod + ".py")).read()
         assert "os.environ" not in src and "getenv" not in src, mod
+
+
+def test_balanced_units_and_clip_unit():
+    """The launch units of forward_many / forward_video: the fewest units of at most `cap` clips, sizes as even as possible (larger first);
+    and the one rule of which clips may share a launch sequence."""
+    assert E.balanced_units(10, 3) == [(0, 3), (3, 6), (6, 8), (8, 10)]             # 3 + 3 + 2 + 2, not 3 + 3 + 3 + 1
+    assert E.balanced_units(10, 4) == [(0, 4), (4, 7), (7, 10)]
+    assert E.balanced_units(16, 4) == [(0, 4), (4, 8), (8, 12), (12, 16)]
+    assert E.balanced_units(0, 4) == []
+    assert E.balanced_units(2, 4) == [(0, 2)] and E.balanced_units(1, 4) == [(0, 1)]
+    assert E.balanced_units(3, 1) == [(0, 1), (1, 2), (2, 3)]
+    for n in range(40):
+        for cap in range(1, 6):
+            u = E.balanced_units(n, cap)
+            sizes = [b - a for a, b in u]
+            assert sum(sizes) == n and all(b == c for (_, b), (c, _) in zip(u, u[1:])) and (not u or u[0][0] == 0)
+            assert len(u) == -(-n // cap) and all(1 <= s <= cap for s in sizes) and sizes == sorted(sizes, reverse=True)
+            assert not sizes or sizes[0] - sizes[-1] <= 1
+    from types import SimpleNamespace
+    eng = SimpleNamespace(clip_batch=4, clip_batch_max_px=70400, cfg={"interval": 0})
+    unit = lambda h, w: E.HipEngine.clip_unit(eng, h, w)
+    assert unit(180, 320) == 4 and unit(200, 352) == 4 and unit(201, 352) == 1
+    eng.cfg["interval"] = 1                                                           # clips sampled with an interval are never batched
+    assert unit(180, 320) == 1
