@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 32
+#define SAVSR_ABI_VERSION 33
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -416,6 +416,24 @@ int savsr_tail_residual(const float* feat, int64_t feat_plane, const float* tail
 int savsr_video_gather_u8(const uint8_t* frames, int n_frames, int c, int h, int w, const int32_t* idx, int n_idx, float* out, void* stream);
 int savsr_video_gather_f32(const float* frames, int n_frames, int c, int h, int w, const int32_t* idx, int n_idx, float* out, void* stream);
 int savsr_video_quantize_u8(const float* in, int n, int c, int H, int W, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 33) Geometric self-ensemble (ensemble.hip; SAVSR.set_self_ensemble).  Variant k = 0 .. 7: fw = k & 1 flips
+ * the width, fh = (k >> 1) & 1 the height, t = k >> 2 transposes the last two dims; forward = the flips then the transpose, inverse = the
+ * transpose then the flips (lbasicsr/models/sr_model.py:141-190).  Both entries only enqueue and allocate nothing; arguments are checked
+ * before the device is touched (SAVSR_E_ARG + savsr_last_error() for a null pointer, c outside 1 .. 3, k outside 0 .. 7, a bad index list).
+ * savsr_ensemble_gather_u8 / _f32: the arguments of savsr_video_gather_u8 / _f32 plus the variant k: out [n_idx][c][h][w] fp32 of variant k,
+ *                         [n_idx][c][w][h] when t is set (through an LDS tile).  Same byte table as the video gather: variant 0 is
+ *                         savsr_video_gather_* bit for bit.
+ * savsr_ensemble_merge:   the 8 network outputs of one clip, variant k at base + offs[k] floats (offs: a HOST array of 8 signed element
+ *                         offsets, so the outputs may lie in different tensors): k < 4 [c][H][W], k >= 4 [c][W][H].  Undoes every
+ *                         variant and writes ((((o0 + o1) + o2) + ... ) + o7) * 0.125f in fp32 in that order: out [c][H][W] fp32, or with
+ *                         out_u8 = 1 [H][W][c] uint8 quantised by savsr_video_quantize_u8's rule.  One pass: 8 reads + 1 write. */
+int savsr_ensemble_gather_u8(const uint8_t* frames, int n_frames, int c, int h, int w, const int32_t* idx, int n_idx, int k, float* out,
+                             void* stream);
+int savsr_ensemble_gather_f32(const float* frames, int n_frames, int c, int h, int w, const int32_t* idx, int n_idx, int k, float* out,
+                              void* stream);
+int savsr_ensemble_merge(const float* base, const int64_t* offs, int c, int H, int W, int out_u8, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * PSNR-Y / SSIM-Y of one output frame with the reference's numerics (SURVEY section 8, row f3 -- the step after the

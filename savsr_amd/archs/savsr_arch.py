@@ -218,6 +218,7 @@ class SAVSR(nn.Module):
         self._engine_sig = None
         self._sig_tensors = None
         self.precision = "fp32"
+        self.self_ensemble = False
 
     PRECISIONS = ("fp32", "fp16")
 
@@ -228,6 +229,13 @@ class SAVSR(nn.Module):
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision must be one of {self.PRECISIONS}, got {precision!r}")
         self.precision = precision
+
+    def set_self_ensemble(self, on: bool = True):
+        """Geometric self-ensemble ("+" results, EDSR+ / RCAN+): every clip runs in its 8 flip / transpose variants -- a transposed one at the
+        swapped scale (sw, sh) -- and the output is the mean of the 8 inverse-transformed outputs (DESIGN.md section 11).  Off by default;
+        covers forward, forward_many, upscale_video and VideoUpscaler, and composes with set_precision.  Module state like set_precision: not
+        in state_dict(), kept across load_state_dict / .to()."""
+        self.self_ensemble = bool(on)
 
     def set_scale(self, scale: Union[tuple, float, int]):
         """savsr_arch.py:635-636; a bare number means a symmetric scale."""
@@ -266,14 +274,16 @@ class SAVSR(nn.Module):
         if self.training:
             raise RuntimeError("savsr_amd.SAVSR implements the inference path only; call .eval() first")
         with torch.no_grad():
-            return self.engine().forward_many(list(zip(clips, [tuple(s) if not isinstance(s, (int, float)) else (s, s) for s in scales])))
+            return self.engine().forward_many(list(zip(clips, [tuple(s) if not isinstance(s, (int, float)) else (s, s) for s in scales])),
+                                              ensemble=self.self_ensemble)
 
     def upscale_video(self, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float") -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
         Returns [N, c, H, W] fp32, or with out="uint8" [N, H, W, c] uint8 = tensor2img(frame, rgb2bgr=False) of each fp32 frame.
-        Arguments are checked before anything runs on the GPU.  Streaming form: savsr_amd.VideoUpscaler."""
+        With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
+        GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
         return upscale_video(self, frames, scale, padding, out)
 
@@ -282,5 +292,7 @@ class SAVSR(nn.Module):
             raise RuntimeError("savsr_amd.SAVSR implements the inference path only; call .eval() first")
         if x.dim() != 5:
             raise ValueError("expected lq of shape [b, t, c, h, w]")
+        if taps is not None and self.self_ensemble:
+            raise ValueError("taps are single-pass diagnostics: set_self_ensemble(False) to collect them")
         with torch.no_grad():
-            return self.engine().forward(x, self.scale, taps)
+            return self.engine().forward(x, self.scale, taps, ensemble=self.self_ensemble)

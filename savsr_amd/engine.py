@@ -716,12 +716,22 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         for k in range(ns):
             cur.wait_stream(self._streams[k])
 
-    def forward_many(self, items) -> List[torch.Tensor]:
+    def forward_many(self, items, ensemble: bool = False) -> List[torch.Tensor]:
         """A stream of independent clips of MIXED shapes / scales (BASELINE config 5): items = [(lq [T, c, h, w], (sh, sw))] ->
         [out [c, H, W]] (c = num_in_ch).  Clip i runs on HIP stream i % n_streams with that stream's sibling engine, so small clips (whose ~360
         launches are latency-bound) overlap.  Every clip's result is that of the throughput flow (`_set_flow`) whatever
         the grouping: forward_many(items)[i] == forward_many([items[i]])[0] bit for bit; against the one-clip latency flow of `forward` it
-        agrees to the conv forms' rounding (~1e-5) where a launch takes another form."""
+        agrees to the conv forms' rounding (~1e-5) where a launch takes another form.
+        ensemble=True: every clip is the self-ensemble of its 8 variants (`_ensemble`)."""
+        if ensemble:
+            clips = []
+            for lq, sc in items:
+                if lq.device != self.dev:
+                    raise RuntimeError(f"input on {lq.device}, engine on {self.dev}")
+                o = torch.empty((self.nch,) + get_hw(lq.shape[-2], lq.shape[-1], sc), device=self.dev, dtype=torch.float32)
+                clips.append((lq.to(torch.float32).contiguous(), list(range(int(lq.shape[0]))), tuple(sc), o))
+            self._ensemble(clips, False)
+            return [cl[3] for cl in clips]
         self._ensure_precision()
         if not self.use_graphs:            # SAVSR_GRAPHS=0 (diagnostics): the same flow issued eagerly, one clip after the other
             outs = []
@@ -769,14 +779,14 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             o.record_stream(cur)       # allocated under a side stream, handed to the caller's: its block is not recycled on the side stream while `cur` still reads it
         return outs
 
-    def forward_video(self, frames: torch.Tensor, windows: List[List[int]], scale, out_u8: bool = False) -> torch.Tensor:
+    def forward_video(self, frames: torch.Tensor, windows: List[List[int]], scale, out_u8: bool = False, ensemble: bool = False) -> torch.Tensor:
         """The sequence path (SAVSR.upscale_video): frames [N, h, w, c] uint8 or [N, c, h, w] fp32 on the device, windows[i] = the
         num_frame frame indices of output frame i in clip order (harness.window_indices) -> [len(windows), c, H, W] fp32, or
         [len(windows), H, W, c] uint8 (out_u8: tensor2img(x, rgb2bgr=False) per frame, savsr_video_quantize_u8).
         Launch units and streams are forward_many's (up to `clip_unit` consecutive windows per unit, balanced; units dealt round-robin over
         `streams_for` streams; throughput flow), so frame i equals forward_many on the gathered window i bit for bit.  A unit's windows are
         gathered from `frames` by savsr_video_gather_u8 / _f32 into a unit-sized fp32 clip batch on the unit's stream; nothing is gathered
-        or converted on the host."""
+        or converted on the host.  ensemble=True: frame i is the self-ensemble of window i (`_ensemble`, gathered by savsr_ensemble_gather_*)."""
         self._ensure_precision()
         if frames.device != self.dev:
             raise RuntimeError(f"input on {frames.device}, engine on {self.dev}")
@@ -798,6 +808,9 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             return out
         if T > _lib.VIDEO_MAX_SLOTS:
             raise ValueError(f"num_frame = {T}: the window gather takes at most {_lib.VIDEO_MAX_SLOTS} frames per launch")
+        if ensemble:
+            self._ensemble([(frames, win, tuple(scale), out[i]) for i, win in enumerate(windows)], out_u8)
+            return out
         cb = self.clip_unit(h, w) if self.use_graphs else 1
         units = balanced_units(n, max(1, min(cb, _lib.VIDEO_MAX_SLOTS // T)))
         gather = self.lib.savsr_video_gather_u8 if u8 else self.lib.savsr_video_gather_f32
@@ -821,8 +834,11 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self._fan_out(units, min(self.streams_for(h * w), len(units)) if self.use_graphs else 1, run)
         return out
 
-    def forward(self, lq: torch.Tensor, scale, taps: Optional[dict] = None) -> torch.Tensor:
-        """lq: [b, T, c, h, w] -> [b, c, H, W], c = num_in_ch (savsr_arch.py:692-742)."""
+    def forward(self, lq: torch.Tensor, scale, taps: Optional[dict] = None, ensemble: bool = False) -> torch.Tensor:
+        """lq: [b, T, c, h, w] -> [b, c, H, W], c = num_in_ch (savsr_arch.py:692-742).  ensemble=True: every clip is the self-ensemble of its
+        8 variants (`_ensemble`; taps are single-pass diagnostics and refused with it)."""
+        if ensemble and taps is not None:
+            raise ValueError("taps are single-pass diagnostics: switch the self-ensemble off to collect them")
         self._ensure_precision()
         if lq.device != self.dev:
             raise RuntimeError(f"input on {lq.device}, engine on {self.dev}")
@@ -832,6 +848,10 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             raise ValueError(f"expected lq [b, {self.cfg['num_frame']}, {self.nch}, h, w] (num_frame, num_in_ch), got {tuple(lq.shape)}")
         H, W = get_hw(h, w, scale)
         out = torch.empty(b, self.nch, H, W, device=self.dev, dtype=torch.float32)
+        if ensemble:
+            frames = lq.view(b * t, c, h, w)
+            self._ensemble([(frames, list(range(i * t, (i + 1) * t)), tuple(scale), out[i]) for i in range(b)], False)
+            return out
         if b >= 2 and self.n_streams >= 2 and self.use_graphs and taps is None:
             # clips are independent (no cross-clip state, savsr_arch.py:705-706): keep n_streams of them in flight
             # on separate HIP streams so one clip's load/store-bound kernel phases overlap another's MFMA phases
@@ -858,6 +878,52 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             else:
                 self.forward_one(lq[i], scale, out[i], taps if i == 0 else None)
         return out
+
+    # ------------------------------------------------------------------ self-ensemble (SAVSR.set_self_ensemble)
+    ENSEMBLE_CLIPS = 8          # clips whose 8 variants go through one forward_many call (64 outputs alive at a time)
+
+    @staticmethod
+    def ensemble_plan(h: int, w: int, scale) -> List[Tuple[Tuple[int, int], Tuple[float, float]]]:
+        """Variant k = 0 .. 7 of an h x w clip at (sh, sw): (LR size, scale) the network runs it at.  Bits: k & 1 flips the width, k >> 1 & 1
+        the height, k >> 2 transposes -- a transposed clip runs at the swapped scale (sw, sh), so its output is the [W, H] transpose of the
+        plain [H, W] one (get_hw is symmetric under the swap)."""
+        sh, sw = float(scale[0]), float(scale[1])
+        return [((w, h), (sw, sh)) if k >> 2 else ((h, w), (sh, sw)) for k in range(8)]
+
+    def _ensemble(self, clips, out_u8: bool) -> None:
+        """Geometric self-ensemble of independent clips.  clips = [(frames, window, (sh, sw), out)]: frames [N, h, w, c] uint8 or [N, c, h, w]
+        fp32 on the device, window = the num_frame frame indices of the clip, out = [c, H, W] fp32 or (out_u8) [H, W, c] uint8.
+        Each clip is gathered in its 8 variants (savsr_ensemble_gather_*, on this stream), the variants of up to ENSEMBLE_CLIPS clips run as
+        ONE forward_many batch -- its grouping puts the 4 plain variants of a small clip in one launch sequence and the 4 transposed ones in
+        another, large frames run 8 units -- and every clip's 8 outputs are merged (savsr_ensemble_merge, fused quantisation for uint8).
+        Variant k's output is forward_many([T_k(clip)], [s_k])[0] bit for bit.  The merge runs on this stream after forward_many has made it
+        wait for every unit's stream (events, no device sync); the outputs were record_stream'ed to it there.  The gathered clips are
+        allocated on this stream and read on the unit streams, which it has waited for before it frees them."""
+        T = self.cfg["num_frame"]
+        st = torch.cuda.current_stream().cuda_stream
+        for g0 in range(0, len(clips), self.ENSEMBLE_CLIPS):
+            group = clips[g0:g0 + self.ENSEMBLE_CLIPS]
+            items = []
+            for frames, win, sc, _ in group:
+                u8 = frames.dtype == torch.uint8
+                N = int(frames.shape[0])
+                h, w, c = (int(v) for v in frames.shape[1:]) if u8 else (int(frames.shape[2]), int(frames.shape[3]), int(frames.shape[1]))
+                if c != self.nch or len(win) != T:
+                    raise ValueError(f"ensemble clip of {len(win)} frames x {c} channels: num_frame = {T}, num_in_ch = {self.nch} expected")
+                gather = self.lib.savsr_ensemble_gather_u8 if u8 else self.lib.savsr_ensemble_gather_f32
+                idx = (_lib.C.c_int32 * T)(*win)
+                for k, ((hk, wk), sk) in enumerate(self.ensemble_plan(h, w, sc)):
+                    lq = torch.empty(T, c, hk, wk, device=self.dev, dtype=torch.float32)
+                    _lib.check(gather(frames.data_ptr(), N, c, h, w, idx, T, k, lq.data_ptr(), st), "savsr_ensemble_gather")
+                    items.append((lq, sk))
+            res = self.forward_many(items)
+            for j, (_, _, sc, out) in enumerate(group):
+                outs = res[8 * j: 8 * j + 8]
+                c, H, W = (int(v) for v in outs[0].shape)
+                ptrs = [o.data_ptr() for o in outs]
+                base = min(ptrs)
+                offs = (_lib.C.c_int64 * 8)(*[(p - base) // 4 for p in ptrs])
+                _lib.check(self.lib.savsr_ensemble_merge(base, offs, c, H, W, int(out_u8), out.data_ptr(), st), "savsr_ensemble_merge")
 
 
 def balanced_units(n: int, cap: int) -> List[Tuple[int, int]]:

@@ -33,10 +33,11 @@ from .models import build_model
 from .options import parse_test_options
 
 
-def run_test(opt: Union[str, dict], root_path: str = ".", model=None, precision: str = "fp32") -> List[dict]:
+def run_test(opt: Union[str, dict], root_path: str = ".", model=None, precision: str = "fp32", self_ensemble: bool = False) -> List[dict]:
     """model: an already built model (build_model(opt)) to run the datasets through -- several YAMLs / passes over one set of
     weights then share its engine (captured graphs, packed weights); None builds one from `opt` as test.py:35 does.
-    precision: the network's conv operand precision (SAVSR.set_precision), "fp32" or "fp16"."""
+    precision: the network's conv operand precision (SAVSR.set_precision), "fp32" or "fp16".
+    self_ensemble: the geometric self-ensemble of every frame (SAVSR.set_self_ensemble; the flow reaches it through forward_many)."""
     if precision not in ("fp32", "fp16"):
         raise ValueError(f"precision must be 'fp32' or 'fp16', got {precision!r}")
     rank = int(os.environ.get("RANK", "0"))
@@ -79,6 +80,10 @@ def run_test(opt: Union[str, dict], root_path: str = ".", model=None, precision:
             model.opt["rank"], model.opt["world_size"], model.opt["dist"] = opt["rank"], opt["world_size"], opt["dist"]
         net = model.net_g.module if hasattr(model.net_g, "module") else model.net_g
         net.set_precision(precision)
+        if hasattr(net, "set_self_ensemble"):
+            net.set_self_ensemble(self_ensemble)
+        elif self_ensemble:
+            raise ValueError(f"self_ensemble: {type(net).__name__} has no set_self_ensemble")
         save_img = opt["val"].get("save_img", False)
         if hasattr(model, "validate_job") and all(hasattr(ds, "units") for ds in test_sets) and os.environ.get("SAVSR_JOB_PLAN", "1") != "0":
             # all datasets of the YAML as one job: (dataset, folder) units cut over the ranks, ONE gather of the metric rows (models.validate_job)
@@ -156,12 +161,22 @@ def build_parser():
     ap.add_argument("--check-readme", action="store_true", help="compare every dataset with the reference's published PSNR-Y / SSIM-Y")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "fp16"],
                     help="conv operand precision (default fp32; fp16 trades a small drift for speed, DESIGN.md section 3)")
+    ap.add_argument("--self-ensemble", action="store_true",
+                    help="average the 8 flip / transpose variants of every frame (8x the work; DESIGN.md section 11)")
     return ap
 
 
+def parse_args(argv=None):
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if a.self_ensemble and a.check_readme:
+        ap.error("--check-readme compares with the published single-pass tables: it cannot be combined with --self-ensemble")
+    return a
+
+
 def main(argv=None) -> int:
-    a = build_parser().parse_args(argv)
-    results = run_test(a.opt, a.root, precision=a.precision)
+    a = parse_args(argv)
+    results = run_test(a.opt, a.root, precision=a.precision, self_ensemble=a.self_ensemble)
     if int(os.environ.get("RANK", "0")) != 0:
         return 0
     for r in results:

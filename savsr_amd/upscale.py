@@ -2,6 +2,7 @@
 
     python -m savsr_amd.upscale -i <lr_frames/> -o <sr_frames/> --scale 4 --checkpoint <net.pth>
     python -m savsr_amd.upscale -i <lr_frames/> -o <sr_frames/> --scale 3.5 2.5 --padding reflection --opt <test.yml>
+    python -m savsr_amd.upscale -i <lr_frames/> -o <sr_frames/> --scale 4 --checkpoint <net.pth> --self-ensemble
 
 Frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on the
 FrameStore pool (savsr_amd.io), pushed through VideoUpscaler in chunks (uint8 in, uint8 out: the windows, the network and the
@@ -35,6 +36,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--precision", default="fp32", choices=["fp32", "fp16"],
                    help="conv operand precision (default fp32; fp16: faster, ~1e-3 drift, see DESIGN.md section 3)")
+    p.add_argument("--self-ensemble", action="store_true",
+                   help="average the 8 flip / transpose variants of every window (8x the work; DESIGN.md section 11)")
     return p
 
 
@@ -96,6 +99,7 @@ def main(argv: Optional[List[str]] = None) -> int:
 
     net = load_net(a)
     net.set_precision(a.precision)
+    net.set_self_ensemble(a.self_ensemble)
     check_length(len(paths), net.num_frame, a.padding)        # (before the GPU is touched)
     dev = torch.device(a.device)
     net = net.to(dev)

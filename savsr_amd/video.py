@@ -100,7 +100,7 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         raise RuntimeError("savsr_amd runs on an AMD GPU only: move the network to the GPU (net.cuda()) first")
     windows = [window_indices(i, n, T, padding) for i in range(n)]
     with torch.no_grad():
-        return net.engine().forward_video(_to_device(frames, dev), windows, sc, out == "uint8")
+        return net.engine().forward_video(_to_device(frames, dev), windows, sc, out == "uint8", ensemble=net.self_ensemble)
 
 
 class VideoUpscaler:
@@ -112,8 +112,9 @@ class VideoUpscaler:
         emit(up.finish())                     # the rest (with reflection the last num_frame // 2 need the end of the video)
 
     Concatenated, the outputs are bit for bit upscale_video on the whole video, for any chunking (a frame's output depends on its
-    window only).  The device keeps the past frames a later window may still name -- at most num_frame - 1 (num_frame for the two
-    circle modes, whose last windows reach num_frame - 1 frames back) -- plus the current chunk."""
+    window only).  The network's self-ensemble switch is read once, here, like the scale.  The device keeps the past frames a later
+    window may still name -- at most num_frame - 1 (num_frame for the two circle modes, whose last windows reach num_frame - 1 frames
+    back) -- plus the current chunk."""
 
     def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float"):
         _check_net(net)
@@ -122,6 +123,7 @@ class VideoUpscaler:
             raise ValueError(f"out = {out!r}: one of {', '.join(OUT_KINDS)}")
         self.net, self.padding, self.out = net, padding, out
         self.scale = as_scale(net.scale if scale is None else scale)
+        self.ensemble = net.self_ensemble          # (read once, like the scale: every chunk runs the same flow)
         self.T = net.num_frame
         self.half = self.T // 2
         self._buf: Optional[torch.Tensor] = None      # frames [base, seen) on the device
@@ -150,7 +152,7 @@ class VideoUpscaler:
         n = n_total if n_total is not None else upto + self.half + 1
         windows = [[j - self._base for j in window_indices(i, n, self.T, self.padding)] for i in range(self.done, upto)]
         with torch.no_grad():
-            res = self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8")
+            res = self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble)
         self.done = upto
         return res
 
