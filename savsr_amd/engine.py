@@ -2,8 +2,10 @@
 
 `HipEngine` = the launch sequence that replaces `SAVSR.forward` (/root/reference/lbasicsr/archs/savsr_arch.py:692-742): the stage
 functions (bidirectional propagation, pyramid fusion, RCAN trunk + OSAdapt, SATU, tail), their capture into hipGraphs per
-(shape, scale), the fan-out of independent clips over HIP streams and the batching of equal clips into the launches.  What it stands
-on lives next door:
+(shape, scale), the fan-out of independent clips over HIP streams and the batching of equal clips into the launches.  The entry points
+`forward`, `forward_many` and `forward_video` differ in how they cut their clips into launch units (`chunk_units`, `many_units`,
+`video_units`) and in where a unit's clips come from; `_fan_out` deals the units over the streams, `_run_unit` runs one, and `_flow` owns
+the state (`nb`, `form_nb`, `conv_algo`) a frame's launches depend on.  What it stands on lives next door:
 
     packing.py   WeightPacking   state_dict -> split-bf16 weight images, OSConv banks, SATU matrices (once per engine)
     cache.py     ContextCache    (shape, scale) buffer contexts, arena, liveness plan, byte budget, eviction limbo
@@ -17,7 +19,10 @@ from __future__ import annotations
 
 import gc
 import os
+import sys
+import time
 import weakref
+from contextlib import contextmanager
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -322,16 +327,17 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
     # ------------------------------------------------------------------ diagnostics
     def time_satu_parts(self, lq: torch.Tensor, scale, timer) -> dict:
         """Diagnostics (tools/scale_sweep.py, bench.py): the SATU LR / HR launches and the tail of the product path, each timed
-        alone by `timer(fn) -> us` on the tensors of a real frame.  lq: [T, num_in_ch, h, w] on the device."""
+        alone by `timer(fn) -> us` on the tensors of a real frame of the latency flow.  lq: [T, num_in_ch, h, w] on the device."""
         lq = lq.contiguous()
-        self._select(lq.shape, scale)
-        c = self._stage_body(lq, scale)
-        out = torch.empty(self.nch, c["H"], c["W"], device=self.dev)
-        lrcat = self._satu_lr_clip(c)
-        self._stage_satu(c, scale)
-        return {"satu_lr_us": timer(lambda: self._satu_lr_clip(c)),
-                "satu_hr_us": timer(lambda: self._satu_hr_clip(lrcat, c, scale)),
-                "tail_us": timer(lambda: self._stage_tail(c, lq, out))}
+        with self._frame(lq, False):
+            self._select(lq.shape, scale)
+            c = self._stage_body(lq, scale)
+            out = torch.empty(self.nch, c["H"], c["W"], device=self.dev)
+            lrcat = self._satu_lr_clip(c)
+            self._stage_satu(c, scale)
+            return {"satu_lr_us": timer(lambda: self._satu_lr_clip(c)),
+                    "satu_hr_us": timer(lambda: self._satu_hr_clip(lrcat, c, scale)),
+                    "tail_us": timer(lambda: self._stage_tail(c, lq, out))}
 
     # ------------------------------------------------------------------ whole frame
     def _stage_body(self, lq: torch.Tensor, scale) -> dict:
@@ -525,16 +531,13 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self.satu(c["hfeat"], c["align"], c["wp"], c["h"], c["w"], scale, o, c["plane"])
         return o[:, : c["H"] * c["W"]].view(self.nf, c["H"], c["W"])
 
-    def forward_one(self, lq: torch.Tensor, scale, out: torch.Tensor, taps: Optional[dict] = None):
+    def forward_one(self, lq: torch.Tensor, scale, out: torch.Tensor, taps: Optional[dict] = None, throughput: bool = False):
         """Eager launch sequence.  lq: [T, c, h, w] fp32 contiguous on device (c = num_in_ch); out: [c, H, W] (or [nb, T, c, h, w] ->
-        [nb, c, H, W]: nb clips of one (shape, scale) in one launch sequence)."""
-        self._ensure_precision()
-        self.nb = int(lq.shape[0]) if lq.dim() == 5 else 1
-        assert self.nb <= self.NB_MAX and (self.nb == 1 or taps is None)
-        try:
+        [nb, c, H, W]: nb clips of one (shape, scale) in one launch sequence).  throughput: the frame's flow (`_flow`) -- the latency flow
+        unless asked otherwise, whatever ran on this engine before."""
+        with self._frame(lq, throughput):
+            assert self.nb == 1 or taps is None
             return self._forward_one(lq, scale, out, taps)
-        finally:
-            self.nb = 1
 
     def _forward_one(self, lq: torch.Tensor, scale, out: torch.Tensor, taps: Optional[dict] = None):
         self._select(lq.shape, scale)
@@ -543,14 +546,8 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         except BaseException:
             self._abort_frame()
             raise
-        if self.satu_events is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        self._stage_satu(c, scale)
-        if self.satu_events is not None:
-            ev1.record()
-            self.satu_events.append((ev0, ev1, self.nb))
-        if taps is not None:                    # channel-last [hp][wp][64] tensors; SATU output planar
+        self._satu_timed(lambda: self._stage_satu(c, scale))
+        if taps is not None:                   # channel-last [hp][wp][64] tensors; SATU output planar
             taps["align_feat"] = c["align"].t
             taps["h_feat"] = c["hfeat"].t
             if self.satu_form != "nf":      # (STAUpsample's own output: a tap of the tuned 64-wide kernels only; the generic form leaves it out)
@@ -571,20 +568,39 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         direct or Winograd-y -- depends on its tile count and on this mode (conv_launch), so a frame in throughput mode can differ from the
         one-clip flow by the two forms' rounding, ~1e-5; each mode is bitwise reproducible.)
         lq [nb, T, c, h, w] / out [nb, c, H, W]: nb clips of one (shape, scale) in ONE launch sequence (see `nb`), its own context and graphs."""
-        self.nb = int(lq.shape[0]) if lq.dim() == 5 else 1
-        assert self.nb <= self.NB_MAX
-        try:
+        with self._frame(lq, throughput):
             return self._forward_graphed_impl(lq, scale, out, throughput)
-        finally:
-            self.nb = 1
 
-    def _set_flow(self, lq: torch.Tensor, throughput: bool) -> None:
-        """The two flows of a frame.  Latency (one clip in flight, `net(lq)` with b = 1): 8-row direct conv tiles, Winograd-y from 200 tiles.
+    def _frame(self, lq: torch.Tensor, throughput: bool):
+        """What every frame passes through before its launches (eager, captured or replayed; never inside a capture): the fp16 images exist
+        when the mode needs them, and the `with` block runs in the flow of lq's clips ([T, c, h, w] or [nb, T, c, h, w])."""
+        self._ensure_precision()
+        nb = int(lq.shape[0]) if lq.dim() == 5 else 1
+        assert nb <= self.NB_MAX
+        return self._flow(nb, throughput, int(lq.shape[-2]), int(lq.shape[-1]))
+
+    @contextmanager
+    def _flow(self, nb: int, throughput: bool, h: int, w: int):
+        """The one owner of the flow state: inside the block `nb`, `form_nb` and `conv_algo` -- which decide the kernels a launch takes and the
+        size of the buffers -- are those of a launch sequence of nb clips of h x w LR pixels; after it they are what they were before,
+        exceptions included.  The two flows of a frame.
+        Latency (one clip in flight, `net(lq)` with b = 1): 8-row direct conv tiles, Winograd-y from 200 tiles.
         Throughput (several clips in flight: b >= 2, forward_many): 16-row tiles, Winograd-y from 100 tiles, counted as if `clip_batch` clips
         shared every launch when the shape is eligible for batching (`form_nb`).  Each flow is bitwise reproducible and independent of the
         grouping; the two differ from each other by the conv forms' rounding (~1e-5)."""
-        self.conv_algo = _lib.CONV_DIRECT_THROUGHPUT if throughput else _lib.CONV_DIRECT
-        self.form_nb = self.clip_unit(int(lq.shape[-2]), int(lq.shape[-1])) if throughput else 1
+        prev = self.nb, self.form_nb, self.conv_algo
+        self.nb, self.form_nb, self.conv_algo = ((nb, HipEngine.clip_unit(self, h, w), _lib.CONV_DIRECT_THROUGHPUT) if throughput else
+                                                 (nb, 1, _lib.CONV_DIRECT))          # (class-qualified: the host test runs this on a stub)
+        try:
+            yield
+        finally:
+            self.nb, self.form_nb, self.conv_algo = prev
+
+    def _set_flow(self, lq: torch.Tensor, throughput: bool) -> None:
+        """Select the flow of lq's clips and leave it selected, for stage functions called one by one outside a frame (tests, tools)."""
+        with self._flow(self.nb, throughput, int(lq.shape[-2]), int(lq.shape[-1])):
+            selected = self.form_nb, self.conv_algo
+        self.form_nb, self.conv_algo = selected
 
     def clip_unit(self, h: int, w: int) -> int:
         """Clips of one (shape, scale) that share a launch sequence (see `nb`) for LR frames of h x w: `clip_batch` where the frame is small
@@ -595,7 +611,6 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         sc = self._select(lq.shape, scale)
         if sc["graphs"] is None:
             sc["graphs"] = {}
-        self._set_flow(lq, throughput)
         gk = self._graph_key(throughput)
         g = sc["graphs"].get(gk)
         if g is None:
@@ -612,20 +627,19 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             # buffers (their contents do not matter: no control flow of the HR kernel depends on the feature values).  The kernels'
             # LDS attributes were set by savsr_prepare_device.  There is no eager run of the frame: the launch sequence is issued
             # exactly once, into the capture, and the buffers it names are allocated there (arena chunks from the graphs' pool).
-            import time as _time
-            _t0 = _time.perf_counter()
+            _t0 = time.perf_counter()
             self._satu_prepare(int(lq.shape[-2]), int(lq.shape[-1]), scale)
             # (no host synchronisation here: the capture stream waits for this one -- `_capture` --, and a plan that had to be MEASURED has
             # synchronised on its own events.  A sync per new context stalled the host behind the units already queued on this stream, 38 ms a
             # time with three streams in flight: 2.6 s of a 6.5 s cold pass of the YAML workflow, during which the other streams got nothing new.)
-            _t1 = _time.perf_counter()
+            _t1 = time.perf_counter()
             graphs = [torch.cuda.CUDAGraph() for _ in range(3)]
             ev = self.satu_events
             self.satu_events = None
             box = {}
             try:
                 self._capture(graphs[0], None, lambda: box.update(c=self._stage_body(s_in, scale)))
-                _t2 = _time.perf_counter()
+                _t2 = time.perf_counter()
                 self._capture(graphs[1], graphs[0].pool(), lambda: self._stage_satu(box["c"], scale))
                 self._capture(graphs[2], graphs[0].pool(), lambda: self._stage_tail(box["c"], s_in, s_out))
             except BaseException:
@@ -634,13 +648,13 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             finally:
                 self.satu_events = ev
             self._charge(sc, s_in.numel() * 4 + s_out.numel() * 4)
-            _t3 = _time.perf_counter()
+            _t3 = time.perf_counter()
             self.host_stats["captures"] += 1
             self.host_stats["plan_s"] += _t1 - _t0
             self.host_stats["capture_s"] += _t3 - _t1
             if self.knobs.profile_capture:
                 print(f"[capture] {tuple(lq.shape)} x{scale}: plan {1e3 * (_t1 - _t0):.1f} ms, body {1e3 * (_t2 - _t1):.1f} ms "
-                      f"(python launches {1e3 * box.get('t_launch', 0):.1f}), satu+tail {1e3 * (_t3 - _t2):.1f} ms", file=__import__("sys").stderr, flush=True)
+                      f"(python launches {1e3 * box.get('t_launch', 0):.1f}), satu+tail {1e3 * (_t3 - _t2):.1f} ms", file=sys.stderr, flush=True)
             # The captured launches bake in the raw device pointers of this (size, scale)'s SATU tables (phase table, per-pixel
             # expansion, row / column index and coordinate arrays).  Replays never go through satu_axes(), so its LRU neither sees
             # them nor may it free them: the graph tuple owns a reference and the tables live exactly as long as the graph does.
@@ -652,16 +666,20 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         s_in, s_out, graphs = g[:3]
         s_in.copy_(lq)
         graphs[0].replay()
-        if self.satu_events is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        graphs[1].replay()
-        if self.satu_events is not None:
-            ev1.record()
-            self.satu_events.append((ev0, ev1, self.nb))      # (start, end, clips whose SATU stages lie between them)
+        self._satu_timed(graphs[1].replay)
         graphs[2].replay()
         out.copy_(s_out)
         return out
+
+    def _satu_timed(self, fn) -> None:
+        """fn() = the SATU stage of a launch sequence, launched or replayed -- between two HIP events where bench.py asks for them."""
+        if self.satu_events is None:
+            return fn()
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        fn()
+        ev1.record()
+        self.satu_events.append((ev0, ev1, self.nb))      # (start, end, clips whose SATU stages lie between them)
 
     def _capture(self, graph: "torch.cuda.CUDAGraph", pool, fn) -> None:
         """Record fn()'s launches into `graph` on a side stream.  This is torch.cuda.graph() without its entry ritual
@@ -696,87 +714,72 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         """HIP streams (launch units in flight) for frames of `px` LR pixels on average."""
         return self.n_streams_large if px >= self.streams_large_px else self.n_streams
 
-    def _ensure_streams(self, ns: int):
+    def _fan_out(self, units: list, px: float, run) -> None:
+        """Deal launch units round-robin over ns HIP streams: unit u is issued by run(engine, unit) under stream u % ns with that stream's
+        engine (this one or a sibling).  ns = `streams_for(px)` for LR frames of `px` pixels on average, at most one per unit; 1 with
+        SAVSR_GRAPHS=0 (diagnostics: one unit after the other).  The streams first wait for the caller's stream, which then waits for all of
+        them.  A tensor run returns -- allocated under its stream, for the caller -- is record_stream'ed to the caller's stream: its block
+        is not recycled on the side stream while the caller's still reads it."""
+        self._ensure_precision()      # (on the caller's stream, which every unit's stream waits for: the engines share the fp16 images)
+        ns = min(self.streams_for(px), len(units)) if self.use_graphs else 1
         while len(self._siblings) < ns - 1:
             self._siblings.append(self.clone_for_stream())
         while len(self._streams) < ns:
             self._streams.append(torch.cuda.Stream(device=self.dev))
-        return [self] + self._siblings
-
-    def _fan_out(self, units: list, ns: int, run) -> None:
-        """Deal launch units round-robin over `ns` HIP streams: unit u is issued by run(engine, unit) under stream u % ns with that stream's
-        engine (this one or a sibling).  The streams first wait for the caller's stream; the caller's stream then waits for all of them."""
-        engines = self._ensure_streams(ns)
+        engines, streams = ([self] + self._siblings)[:ns], self._streams[:ns]
+        for e in engines:             # (bench.py: the SATU stages of every stream's units are timed)
+            e.satu_events = self.satu_events
         cur = torch.cuda.current_stream()
-        for k in range(ns):
-            self._streams[k].wait_stream(cur)
+        for s in streams:
+            s.wait_stream(cur)
         for u, unit in enumerate(units):
-            with torch.cuda.stream(self._streams[u % ns]):
-                run(engines[u % ns], unit)
-        for k in range(ns):
-            cur.wait_stream(self._streams[k])
+            with torch.cuda.stream(streams[u % ns]):
+                made = run(engines[u % ns], unit)
+            if made is not None:
+                made.record_stream(cur)
+        for s in streams:
+            cur.wait_stream(s)
+
+    def _run_unit(self, lq_u: torch.Tensor, scale, out_u: torch.Tensor) -> None:
+        """One launch unit of the throughput flow on this engine under the current stream: lq_u [nb, T, c, h, w] fp32 contiguous -> out_u
+        [nb, c, H, W].  One clip runs as [T, c, h, w] -> [c, H, W] (the one-clip context and graphs); SAVSR_GRAPHS=0: the same flow, eagerly."""
+        if lq_u.shape[0] == 1:
+            lq_u, out_u = lq_u[0], out_u[0]
+        (self._forward_graphed if self.use_graphs else self.forward_one)(lq_u, scale, out_u, throughput=True)
+
+    def _input(self, t: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+        """An input as the kernels read it (`dtype`, contiguous); it has to be on the engine's device already."""
+        if t.device != self.dev:
+            raise RuntimeError(f"input on {t.device}, engine on {self.dev}")
+        return t.to(dtype).contiguous()
 
     def forward_many(self, items, ensemble: bool = False) -> List[torch.Tensor]:
         """A stream of independent clips of MIXED shapes / scales (BASELINE config 5): items = [(lq [T, c, h, w], (sh, sw))] ->
-        [out [c, H, W]] (c = num_in_ch).  Clip i runs on HIP stream i % n_streams with that stream's sibling engine, so small clips (whose ~360
-        launches are latency-bound) overlap.  Every clip's result is that of the throughput flow (`_set_flow`) whatever
+        [out [c, H, W]] (c = num_in_ch).  Launch unit u (`many_units`) runs on HIP stream u % ns with that stream's sibling engine (`_fan_out`), so
+        small clips (whose ~360 launches are latency-bound) overlap.  Every clip's result is that of the throughput flow (`_flow`) whatever
         the grouping: forward_many(items)[i] == forward_many([items[i]])[0] bit for bit; against the one-clip latency flow of `forward` it
         agrees to the conv forms' rounding (~1e-5) where a launch takes another form.
         ensemble=True: every clip is the self-ensemble of its 8 variants (`_ensemble`)."""
+        items = [(self._input(lq), sc) for lq, sc in items]
         if ensemble:
-            clips = []
-            for lq, sc in items:
-                if lq.device != self.dev:
-                    raise RuntimeError(f"input on {lq.device}, engine on {self.dev}")
-                o = torch.empty((self.nch,) + get_hw(lq.shape[-2], lq.shape[-1], sc), device=self.dev, dtype=torch.float32)
-                clips.append((lq.to(torch.float32).contiguous(), list(range(int(lq.shape[0]))), tuple(sc), o))
+            clips = [(lq, list(range(int(lq.shape[0]))), tuple(sc),
+                      torch.empty((self.nch,) + get_hw(lq.shape[-2], lq.shape[-1], sc), device=self.dev, dtype=torch.float32)) for lq, sc in items]
             self._ensemble(clips, False)
             return [cl[3] for cl in clips]
-        self._ensure_precision()
-        if not self.use_graphs:            # SAVSR_GRAPHS=0 (diagnostics): the same flow issued eagerly, one clip after the other
-            outs = []
-            for lq, sc in items:
-                lq = lq.to(torch.float32).contiguous()
-                o = torch.empty((self.nch,) + get_hw(lq.shape[-2], lq.shape[-1], sc), device=self.dev, dtype=torch.float32)
-                self._set_flow(lq, True)
-                outs.append(self.forward_one(lq, sc, o))
-            return outs
-        for lq, sc in items:
-            if lq.device != self.dev:
-                raise RuntimeError(f"input on {lq.device}, engine on {self.dev}")
         # (a lone clip, or SAVSR_STREAMS=1, takes the throughput flow too: what forward_many returns for a clip does not depend on how many
-        # came with it or on how many streams carry them)
-        # Launch units: clips of equal (shape, scale) go out up to clip_unit at a time in ONE launch sequence (see `nb`), in balanced units;
-        # everything else one clip per unit.
-        units: List[List[int]] = []
-        groups: Dict[tuple, List[int]] = {}
-        for i, (lq, sc) in enumerate(items):
-            if self.clip_unit(lq.shape[-2], lq.shape[-1]) > 1:
-                groups.setdefault((tuple(lq.shape), float(sc[0]), float(sc[1])), []).append(i)
-            else:
-                units.append([i])
-        for idxs in groups.values():
-            units += [idxs[a:b] for a, b in balanced_units(len(idxs), self.clip_batch)]
-        units.sort(key=lambda u: u[0])
+        # came with it or on how many streams carry them; SAVSR_GRAPHS=0 issues that flow eagerly, one clip per unit)
+        units = many_units([(lq.shape, sc) for lq, sc in items], self.clip_unit if self.use_graphs else (lambda h, w: 1), self.clip_batch)
         outs: List[Optional[torch.Tensor]] = [None] * len(items)
 
         def run(eng: "HipEngine", unit: List[int]):
             sc = items[unit[0]][1]
-            H, W = get_hw(items[unit[0]][0].shape[-2], items[unit[0]][0].shape[-1], sc)
-            if len(unit) == 1:
-                i = unit[0]
-                outs[i] = torch.empty(self.nch, H, W, device=self.dev, dtype=torch.float32)
-                eng._forward_graphed(items[i][0].to(torch.float32).contiguous(), sc, outs[i], throughput=True)
-            else:
-                lqb = torch.stack([items[i][0].to(torch.float32) for i in unit], 0)
-                outb = torch.empty(len(unit), self.nch, H, W, device=self.dev, dtype=torch.float32)
-                eng._forward_graphed(lqb, sc, outb, throughput=True)
-                for j, i in enumerate(unit):
-                    outs[i] = outb[j]
-        self._fan_out(units, min(self.streams_for(sum(lq.shape[-2] * lq.shape[-1] for lq, _ in items) / len(items)), len(units)), run)
-        cur = torch.cuda.current_stream()
-        for o in {id(t._base if t._base is not None else t): (t._base if t._base is not None else t) for t in outs if t is not None}.values():
-            o.record_stream(cur)       # allocated under a side stream, handed to the caller's: its block is not recycled on the side stream while `cur` still reads it
+            lqb = torch.stack([items[i][0] for i in unit], 0) if len(unit) > 1 else items[unit[0]][0][None]          # (a lone clip: no copy)
+            outb = torch.empty((len(unit), self.nch) + get_hw(lqb.shape[-2], lqb.shape[-1], sc), device=self.dev, dtype=torch.float32)
+            eng._run_unit(lqb, sc, outb)
+            for j, i in enumerate(unit):
+                outs[i] = outb[j]
+            return outb
+        self._fan_out(units, sum(lq.shape[-2] * lq.shape[-1] for lq, _ in items) / max(1, len(items)), run)
         return outs
 
     def forward_video(self, frames: torch.Tensor, windows: List[List[int]], scale, out_u8: bool = False, ensemble: bool = False) -> torch.Tensor:
@@ -787,13 +790,8 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         `streams_for` streams; throughput flow), so frame i equals forward_many on the gathered window i bit for bit.  A unit's windows are
         gathered from `frames` by savsr_video_gather_u8 / _f32 into a unit-sized fp32 clip batch on the unit's stream; nothing is gathered
         or converted on the host.  ensemble=True: frame i is the self-ensemble of window i (`_ensemble`, gathered by savsr_ensemble_gather_*)."""
-        self._ensure_precision()
-        if frames.device != self.dev:
-            raise RuntimeError(f"input on {frames.device}, engine on {self.dev}")
-        u8 = frames.dtype == torch.uint8
-        frames = frames.contiguous() if u8 else frames.to(torch.float32).contiguous()
-        N = int(frames.shape[0])
-        h, w, c = (int(v) for v in frames.shape[1:]) if u8 else (int(frames.shape[2]), int(frames.shape[3]), int(frames.shape[1]))
+        u8, N, c, h, w = _frames_layout(frames)
+        frames = self._input(frames, torch.uint8 if u8 else torch.float32)
         T = self.cfg["num_frame"]
         if c != self.nch:
             raise ValueError(f"frames have {c} channels, the network num_in_ch = {self.nch}")
@@ -811,8 +809,6 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         if ensemble:
             self._ensemble([(frames, win, tuple(scale), out[i]) for i, win in enumerate(windows)], out_u8)
             return out
-        cb = self.clip_unit(h, w) if self.use_graphs else 1
-        units = balanced_units(n, max(1, min(cb, _lib.VIDEO_MAX_SLOTS // T)))
         gather = self.lib.savsr_video_gather_u8 if u8 else self.lib.savsr_video_gather_f32
 
         def run(eng: "HipEngine", unit: Tuple[int, int]):
@@ -823,15 +819,11 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             lqb = torch.empty(nb, T, c, h, w, device=self.dev, dtype=torch.float32)
             _lib.check(gather(frames.data_ptr(), N, c, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), lqb.data_ptr(), st), "savsr_video_gather")
             o = torch.empty(nb, c, H, W, device=self.dev, dtype=torch.float32) if out_u8 else out[i0:i1]
-            lq_u, o_u = (lqb[0], o[0]) if nb == 1 else (lqb, o)
-            if self.use_graphs:
-                eng._forward_graphed(lq_u, scale, o_u, throughput=True)
-            else:                          # SAVSR_GRAPHS=0 (diagnostics): forward_many's eager flow, one window at a time (one stream)
-                eng._set_flow(lq_u, True)
-                eng.forward_one(lq_u, scale, o_u)
+            eng._run_unit(lqb, scale, o)
             if out_u8:
                 _lib.check(self.lib.savsr_video_quantize_u8(o.data_ptr(), nb, c, H, W, out[i0:i1].data_ptr(), st), "savsr_video_quantize_u8")
-        self._fan_out(units, min(self.streams_for(h * w), len(units)) if self.use_graphs else 1, run)
+        # (SAVSR_GRAPHS=0: forward_many's eager flow, one window per unit)
+        self._fan_out(video_units(n, T, self.clip_unit(h, w) if self.use_graphs else 1), h * w, run)
         return out
 
     def forward(self, lq: torch.Tensor, scale, taps: Optional[dict] = None, ensemble: bool = False) -> torch.Tensor:
@@ -839,10 +831,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         8 variants (`_ensemble`; taps are single-pass diagnostics and refused with it)."""
         if ensemble and taps is not None:
             raise ValueError("taps are single-pass diagnostics: switch the self-ensemble off to collect them")
-        self._ensure_precision()
-        if lq.device != self.dev:
-            raise RuntimeError(f"input on {lq.device}, engine on {self.dev}")
-        lq = lq.to(torch.float32).contiguous()
+        lq = self._input(lq)
         b, t, c, h, w = lq.shape
         if t != self.cfg["num_frame"] or c != self.nch:
             raise ValueError(f"expected lq [b, {self.cfg['num_frame']}, {self.nch}, h, w] (num_frame, num_in_ch), got {tuple(lq.shape)}")
@@ -853,30 +842,16 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             self._ensemble([(frames, list(range(i * t, (i + 1) * t)), tuple(scale), out[i]) for i in range(b)], False)
             return out
         if b >= 2 and self.n_streams >= 2 and self.use_graphs and taps is None:
-            # clips are independent (no cross-clip state, savsr_arch.py:705-706): keep n_streams of them in flight
-            # on separate HIP streams so one clip's load/store-bound kernel phases overlap another's MFMA phases
-            # ... and up to `clip_unit` consecutive clips per launch sequence (see `nb`): the batch shares one (shape, scale).  Consecutive
-            # units of clip_unit clips, not balanced ones (16 -> 4 + 4 + 4 + 4, 10 -> 4 + 4 + 2).
-            cb = self.clip_unit(h, w)
-            units = [(i0, min(i0 + cb, b)) for i0 in range(0, b, cb)]
-            ns = min(self.streams_for(h * w), len(units))
-            for e in self._ensure_streams(ns)[:ns]:       # (bench.py: the SATU stages of every stream's units are timed)
-                e.satu_events = self.satu_events
-
-            def run(eng: "HipEngine", unit: Tuple[int, int]):
-                i0, i1 = unit
-                if i1 - i0 == 1:
-                    eng._forward_graphed(lq[i0], scale, out[i0], throughput=True)
-                else:                # (contiguous slices of the batch: no copy)
-                    eng._forward_graphed(lq[i0:i1], scale, out[i0:i1], throughput=True)
-            self._fan_out(units, ns, run)
+            # clips are independent (no cross-clip state, savsr_arch.py:705-706): keep n_streams of them in flight on separate HIP streams so one
+            # clip's load/store-bound kernel phases overlap another's MFMA phases ... and up to `clip_unit` consecutive clips per launch sequence
+            # (see `nb`): the batch shares one (shape, scale).  Units: `chunk_units`, contiguous slices of the batch (no copy)
+            self._fan_out(chunk_units(b, self.clip_unit(h, w)), h * w, lambda eng, u: eng._run_unit(lq[u[0]:u[1]], scale, out[u[0]:u[1]]))
             return out
-        self.conv_algo, self.form_nb = _lib.CONV_DIRECT, 1
-        for i in range(b):      # samples are independent (OSConv groups=b, savsr_arch.py:166-167)
+        for i in range(b):      # the latency flow; samples are independent (OSConv groups=b, savsr_arch.py:166-167)
             if self.use_graphs and taps is None:
                 self._forward_graphed(lq[i], scale, out[i])
             else:
-                self.forward_one(lq[i], scale, out[i], taps if i == 0 else None)
+                self.forward_one(lq[i], scale, out[i], taps if i == 0 else None, throughput=False)
         return out
 
     # ------------------------------------------------------------------ self-ensemble (SAVSR.set_self_ensemble)
@@ -905,9 +880,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             group = clips[g0:g0 + self.ENSEMBLE_CLIPS]
             items = []
             for frames, win, sc, _ in group:
-                u8 = frames.dtype == torch.uint8
-                N = int(frames.shape[0])
-                h, w, c = (int(v) for v in frames.shape[1:]) if u8 else (int(frames.shape[2]), int(frames.shape[3]), int(frames.shape[1]))
+                u8, N, c, h, w = _frames_layout(frames)
                 if c != self.nch or len(win) != T:
                     raise ValueError(f"ensemble clip of {len(win)} frames x {c} channels: num_frame = {T}, num_in_ch = {self.nch} expected")
                 gather = self.lib.savsr_ensemble_gather_u8 if u8 else self.lib.savsr_ensemble_gather_f32
@@ -936,3 +909,29 @@ def balanced_units(n: int, cap: int) -> List[Tuple[int, int]]:
         units.append((a, a + m))
         a += m
     return units
+
+
+def chunk_units(n: int, cap: int) -> List[Tuple[int, int]]:
+    """`forward`'s launch units: consecutive [start, end) chunks of `cap` clips, not balanced (16 at 4 -> 4 + 4 + 4 + 4, 10 at 4 -> 4 + 4 + 2)."""
+    return [(a, min(a + cap, n)) for a in range(0, n, cap)]
+
+
+def many_units(clips, clip_unit, clip_batch: int) -> List[List[int]]:
+    """`forward_many`'s launch units (lists of clip indices) for clips = [(shape, (sh, sw))]: the clips that may share a launch sequence
+    (clip_unit(h, w) > 1) grouped by (shape, scale), every group cut into balanced units of at most `clip_batch`; every other clip a
+    group of its own; the units ordered by their first clip."""
+    groups: Dict[object, List[int]] = {}
+    for i, (shape, sc) in enumerate(clips):
+        groups.setdefault((tuple(shape), float(sc[0]), float(sc[1])) if clip_unit(shape[-2], shape[-1]) > 1 else i, []).append(i)
+    return sorted((idxs[a:b] for idxs in groups.values() for a, b in balanced_units(len(idxs), clip_batch)), key=lambda u: u[0])
+
+
+def video_units(n: int, T: int, cb: int) -> List[Tuple[int, int]]:
+    """`forward_video`'s launch units: balanced ranges of at most `cb` consecutive windows of T frames that fit one gather launch."""
+    return balanced_units(n, max(1, min(cb, _lib.VIDEO_MAX_SLOTS // T)))
+
+
+def _frames_layout(frames: torch.Tensor) -> Tuple[bool, int, int, int, int]:
+    """(uint8?, N, c, h, w) of a frame stack: [N, h, w, c] uint8 or [N, c, h, w] float."""
+    N, a, b, d = (int(v) for v in frames.shape)
+    return (True, N, d, a, b) if frames.dtype == torch.uint8 else (False, N, a, b, d)

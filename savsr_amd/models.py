@@ -130,7 +130,7 @@ class VideoBaseModel(BaseModel):
         Frames are independent units (the hidden state restarts per window, savsr_arch.py:705-706): instead of one frame at a time
         (video_base_model.py:51-53) they go through the network several at a time, each launch unit on its own HIP stream
         (SAVSR.forward_many) -- the launch-latency-bound parts of one frame run under another's convolutions.  Every frame takes the
-        throughput flow of the engine (HipEngine._set_flow), whose result for a frame does not depend on the frames that came with it:
+        throughput flow of the engine (HipEngine._flow), whose result for a frame does not depend on the frames that came with it:
         metric tables and saved images are identical for every world size and partition.
         next_folder: (dataset, folder) the caller runs next -- its files are decoded in the background meanwhile."""
         from .metrics_gpu import psnr_ssim_y
@@ -167,7 +167,7 @@ class VideoBaseModel(BaseModel):
             # clips per launch sequence only where the engine batches them (small frames); large frames keep the one-clip-per-stream rule
             if many and hasattr(eng, "streams_for"):
                 streams = max(1, int(eng.streams_for(h * w)))             # (fewer launch units in flight for large frames)
-            unit = int(eng.clip_unit(h, w)) if (many and hasattr(eng, "clip_unit")) else 1
+            unit = int(eng.clip_unit(h, w)) if many else 1
             for a, b in (chunk_block(k1 - k, streams, unit) if many else [(i, i + 1) for i in range(k1 - k)]):
                 k0, k_end = k + a, k + b
                 vals = [first if idx == mine[k] else dataset[idx] for idx in mine[k0:k_end]]

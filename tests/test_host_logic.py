@@ -391,3 +391,48 @@ def test_balanced_units_and_clip_unit():
     assert unit(180, 320) == 4 and unit(200, 352) == 4 and unit(201, 352) == 1
     eng.cfg["interval"] = 1                                                           # clips sampled with an interval are never batched
     assert unit(180, 320) == 1
+    eng.cfg["interval"] = 0
+    # forward: consecutive chunks of clip_unit clips, NOT balanced
+    assert E.chunk_units(16, 4) == [(0, 4), (4, 8), (8, 12), (12, 16)]
+    assert E.chunk_units(10, 4) == [(0, 4), (4, 8), (8, 10)]
+    assert E.chunk_units(5, 1) == [(i, i + 1) for i in range(5)]
+    # forward_many: clips 0, 2, 3, 5, 6 of one small shape and scale (a group of five: 3 + 2), 1 too large to batch, 4 the small shape at
+    # another scale (a group of one); units ordered by their first clip
+    small, large = (7, 3, 180, 320), (7, 3, 540, 960)
+    clips = [(small, (4, 4)), (large, (4, 4)), (small, (4, 4)), (small, (4.0, 4.0)), (small, (2.5, 4)), (small, (4, 4)), (small, (4, 4))]
+    assert E.many_units(clips, unit, 4) == [[0, 2, 3], [1], [4], [5, 6]]
+    assert E.many_units(clips, lambda h, w: 1, 4) == [[i] for i in range(7)]            # (SAVSR_GRAPHS=0: one clip per unit)
+    assert E.many_units([], unit, 4) == []
+    # forward_video: balanced, capped by the frames one gather launch takes
+    from savsr_amd import _lib
+    assert E.video_units(10, 7, 4) == E.balanced_units(10, 4) == [(0, 4), (4, 7), (7, 10)]
+    assert E.video_units(10, 7, 1) == [(i, i + 1) for i in range(10)]
+    assert _lib.VIDEO_MAX_SLOTS // 33 <= 1 and E.video_units(3, 33, 4) == [(0, 1), (1, 2), (2, 3)]
+
+
+def test_flow_owner_sets_and_restores_the_flow_state():
+    """HipEngine._flow is the one owner of `nb`, `form_nb`, `conv_algo`: inside the block they are those of the frame's flow, after it --
+    left normally or by an exception -- what they were before."""
+    from types import SimpleNamespace
+    from savsr_amd import _lib
+    eng = SimpleNamespace(clip_batch=4, clip_batch_max_px=70400, cfg={"interval": 0}, nb=1, form_nb=1, conv_algo=_lib.CONV_DIRECT)
+    state = lambda: (eng.nb, eng.form_nb, eng.conv_algo)
+    for before in ((1, 1, _lib.CONV_DIRECT), (1, 4, _lib.CONV_DIRECT_THROUGHPUT), (3, 1, _lib.CONV_DIRECT_THROUGHPUT)):
+        for nb, throughput, h, w in ((3, True, 180, 320), (1, True, 180, 320), (1, True, 201, 352), (2, False, 180, 320), (1, False, 540, 960)):
+            want = (nb, E.HipEngine.clip_unit(eng, h, w) if throughput else 1, _lib.CONV_DIRECT_THROUGHPUT if throughput else _lib.CONV_DIRECT)
+            eng.nb, eng.form_nb, eng.conv_algo = before
+            with E.HipEngine._flow(eng, nb, throughput, h, w):
+                assert state() == want
+                with E.HipEngine._flow(eng, 1, False, h, w):                            # (nested: the inner block restores the outer flow)
+                    assert state() == (1, 1, _lib.CONV_DIRECT)
+                assert state() == want
+            assert state() == before
+            with pytest.raises(KeyError):
+                with E.HipEngine._flow(eng, nb, throughput, h, w):
+                    assert state() == want
+                    raise KeyError("a launch failed")
+            assert state() == before
+    with E.HipEngine._flow(eng, 3, True, 180, 320):                                       # (the values, written out)
+        assert state() == (3, 4, _lib.CONV_DIRECT_THROUGHPUT)
+    with E.HipEngine._flow(eng, 1, True, 201, 352):
+        assert state() == (1, 1, _lib.CONV_DIRECT_THROUGHPUT)
