@@ -5,6 +5,10 @@ Host helpers (integer grids, index maps of the weight-image layouts, split-bf16 
 the convs (:191-204), every conv as a split-bf16 image in MFMA lane order (direct and, for static 3x3 convs, Winograd-y), the OSConv
 kernel banks + routing / attention matrices (:139-172), the SATU matrices with the tail conv's channel contraction folded in
 (:315-376, :738).  Pure data movement + RNE conversions; include/savsr_hip.h documents every layout.
+
+SATU, every form: ONE float64 fold (`fold_satu_nf`; the forms differ in the row order of Wt, `tail_rows27`), ONE set of lane layouts
+(`lanes_*`, `bias_acc_order`), pure host packers sd -> {name: host tensor} (`pack_satu_heads`, `pack_satu_nf`, `pack_satu_tuned`; testable
+without a GPU, tests/test_satu_packing.py); `WeightPacking._pack_satu` only uploads them and fills the structs (`struct_of`).
 """
 from __future__ import annotations
 
@@ -16,7 +20,6 @@ import torch
 from ._lib import SatuNfWeights, SatuWeights
 
 BN_EPS = 1e-5
-MAX_SUM_BLOCKS = 256     # workgroups of one savsr_channel_sums launch
 
 
 # ----------------------------------------------------------------------------- host helpers (integer / grid logic)
@@ -151,15 +154,20 @@ def conv_wy_pack_index(cout: int, cin: int):
     return _WY_IDX_CACHE[key]
 
 
+def _wy_transform(g: torch.Tensor) -> torch.Tensor:
+    """The F(2,3) weight transform over the tap ROWS g_ky of a float64 [cout][cin][3 ky][3 kx] weight: U0 = g0, U1 = (g0 + g1 + g2) / 2,
+    U2 = (g0 - g1 + g2) / 2, U3 = g2, per kx -> [4 pos][cout][cin][3 kx]."""
+    g0, g1, g2 = g[:, :, 0], g[:, :, 1], g[:, :, 2]
+    return torch.stack([g0, 0.5 * (g0 + g1 + g2), 0.5 * (g0 - g1 + g2), g2], 0)
+
+
 def pack_conv_weight_wy(w: torch.Tensor, device: Optional[torch.device] = None) -> torch.Tensor:
-    """[cout, cin, 3, 3] -> split-bf16 Winograd-y weight image (SAVSR_CONV_WINOGRAD_Y): the F(2,3) weight transform over the tap ROWS
-    g_ky in float64 -- U0 = g0, U1 = (g0 + g1 + g2) / 2, U2 = (g0 - g1 + g2) / 2, U3 = g2, per kx -- rounded to fp32, then (hi, lo)."""
+    """[cout, cin, 3, 3] -> split-bf16 Winograd-y weight image (SAVSR_CONV_WINOGRAD_Y): _wy_transform in float64 (on `device`), rounded to
+    fp32, then (hi, lo)."""
     cout, cin, ks, _ = w.shape
     assert ks == 3
     dev = device if device is not None and device.type != "cpu" else torch.device("cpu")
-    g = w.detach().to(dev, torch.float64)                                  # [co][ci][ky][kx]
-    g0, g1, g2 = g[:, :, 0], g[:, :, 1], g[:, :, 2]
-    u = torch.stack([g0, 0.5 * (g0 + g1 + g2), 0.5 * (g0 - g1 + g2), g2], 0).to(torch.float32)      # [pos][co][ci][kx]
+    u = _wy_transform(w.detach().to(dev, torch.float64)).to(torch.float32)
     idx, total = conv_wy_pack_index(cout, cin)
     return split_bf16_image(_scatter_image(idx, total, u, "wy", (cout, cin), device))
 
@@ -184,9 +192,7 @@ def pack_conv_weight_f16(w: torch.Tensor) -> torch.Tensor:
 
 def wy_transform_f64(w: torch.Tensor) -> np.ndarray:
     """[cout, cin, 3, 3] -> the F(2,3)-along-y weight transform U [4 pos][cout][cin][3 kx] in float64 (pack_conv_weight_wy's arithmetic)."""
-    g = w.detach().to("cpu", torch.float64)
-    g0, g1, g2 = g[:, :, 0], g[:, :, 1], g[:, :, 2]
-    return torch.stack([g0, 0.5 * (g0 + g1 + g2), 0.5 * (g0 - g1 + g2), g2], 0).numpy()
+    return _wy_transform(w.detach().to("cpu", torch.float64)).numpy()
 
 
 def pack_conv_weight_wy_f16(w: torch.Tensor) -> torch.Tensor:
@@ -233,24 +239,129 @@ def window_record(nch: int, sw: int) -> int:
     return 16 if nch * sw <= 16 else 32
 
 
-def fold_satu_nf(sd, c: int) -> Dict[str, np.ndarray]:
-    """The matrices of the width-generic tail-projected SATU (savsr_satu_nf_*), folded in float64 (savsr_arch.py:315-376, :738):
+def row_q(ky: int, kx: int, o: int) -> int:
+    """Row order of the row-summed tail form (savsr_satu_hr_tail_q, 3 channels): the three kx of group g = 3 ky + o at MFMA rows
+    acc_row(3 gi + kx, half), groups 0 .. 4 in lane half 0 (gi = g), 5 .. 8 in half 1 (gi = g - 5)."""
+    g = 3 * ky + o
+    return acc_row(3 * g + kx, 0) if g < 5 else acc_row(3 * (g - 5) + kx, 1)
+
+
+def fold_satu_nf(sd, c: int, row_of=None, tail: bool = True) -> Dict[str, np.ndarray]:
+    """The matrices of every SATU form in float64 (savsr_arch.py:315-376, :738); Wt = tail_rows27(sd, c, row_of) [32][c] for the
+    tail-projected forms (savsr_satu_nf_*, savsr_satu_*_tail with row_of = None, savsr_satu_hr_tail_q with row_q), the identity [c][c]
+    (nothing multiplied) for the plain form, tail = False:
       kconv [25 c][c], kconv_b [25 c]   kernel_conv (row n = 25 ch + tap, :227), unchanged
-      ta [32][c] = Wt27 Wa              applies to sta (fusion's first half, :374)
-      tb [32][c] = Wt27 Wb              applies to x
+      ta [rows][c] = Wt Wa              applies to sta (fusion's first half, :374)
+      tb [rows][c] = Wt Wb              applies to x
       cstack [c/2][c]                   C_m rows at (c/8) m + j (weight_compress, :232-235)
-      wbe [4][c/8][32] = (Wt27 Wb E_n)[p][j] as [n][j][p]   (weight_expand, :238-241)
-      fb [32] = Wt27 b                  (fusion bias)"""
+      wbe [4][c/8][rows] = (Wt Wb E_n)[p][j] as [n][j][p]   (weight_expand, :238-241)
+      fb [rows] = Wt b                  (fusion bias)"""
     p = "upsample."
     g = lambda k: sd[p + k].to("cpu", torch.float64).numpy()
-    wt27 = tail_rows27(sd, c)
+    wt27 = tail_rows27(sd, c, row_of) if tail else None
+    wt = lambda a: wt27 @ a if tail else a
     fus = g("fusion.weight").reshape(c, 2 * c)
     wa, wb = fus[:, :c], fus[:, c:]                                                   # cat((sta, fea)), :374
     expd = g("weight_expand").reshape(4, c, c // 8)                                   # E_n[c][j]
-    tb = wt27 @ wb
+    tb = wt(wb)
     return dict(kconv=g("kernel_conv.0.weight").reshape(25 * c, c), kconv_b=g("kernel_conv.0.bias"),
-                ta=wt27 @ wa, tb=tb, cstack=g("weight_compress").reshape(c // 2, c),
-                wbe=np.einsum("pc,ncj->njp", tb, expd), fb=wt27 @ g("fusion.bias"))
+                ta=wt(wa), tb=tb, cstack=g("weight_compress").reshape(c // 2, c),
+                wbe=np.einsum("pc,ncj->njp", tb, expd), fb=wt(g("fusion.bias")))
+
+
+# ----------------------------------------------------------------------------- MFMA lane layouts of the SATU images (include/savsr_hip.h,
+# savsr_satu_weights / savsr_satu_nf_weights): pure index maps, every one [..][64 lanes][8 j] with the lane's row at (lane & 31)
+_LANE, _J = np.arange(64)[:, None], np.arange(8)[None, :]
+_LI, _LH = _LANE & 31, _LANE >> 5
+
+
+def lanes_a(m: np.ndarray, r0: int = 0) -> np.ndarray:
+    """A-operand k steps of the 32-row tile at r0: [K/16 ks][lane][j] = m[r0 + (lane & 31)][16 ks + 8 (lane >> 5) + j]."""
+    ks = np.arange(m.shape[1] // 16)[:, None, None]
+    return m[r0 + _LI, 16 * ks + 8 * _LH + _J]
+
+
+def lanes_acc(m: np.ndarray, r0: int = 0) -> np.ndarray:
+    """k steps in accumulator order (the B operand is an accumulator: k step g consumes registers 8 (g % 2) .. + 7 of channel group g / 2):
+    [K/16 g][lane][j] = m[r0 + (lane & 31)][32 (g / 2) + 16 (g % 2) + 8 (j >> 2) + 4 (lane >> 5) + (j & 3)]."""
+    g = np.arange(m.shape[1] // 16)[:, None, None]
+    return m[r0 + _LI, 32 * (g // 2) + 16 * (g % 2) + 8 * (_J >> 2) + 4 * _LH + (_J & 3)]
+
+
+def lanes_kconv(wk: np.ndarray, c: int) -> np.ndarray:
+    """kernel_conv groups of width c: [25 tap][c/32 cg][c/16 ks][lane][j] = wk[25 (32 cg + (lane & 31)) + tap][16 ks + 8 (lane >> 5) + j]."""
+    tap, cg, ks = np.arange(25)[:, None, None, None, None], np.arange(c // 32)[:, None, None, None], np.arange(c // 16)[:, None, None]
+    return wk[25 * (32 * cg + _LI) + tap, 16 * ks + 8 * _LH + _J]
+
+
+def lanes_wbe(wbe: np.ndarray, r0: int = 0) -> np.ndarray:
+    """The tuned (W E_n) tile at row r0 of wbe [4 n][rows][8 j]: [2 ks][lane][j] = wbe[2 ks + (lane >> 5)][r0 + (lane & 31)][j]
+    (k = 16 ks + 8 (lane >> 5) + j = 8 n + j)."""
+    ks = np.arange(2)[:, None, None]
+    return wbe[2 * ks + _LH, r0 + _LI, _J]
+
+
+def bias_acc_order(b: np.ndarray) -> np.ndarray:
+    """A bias of 32 T rows in accumulator-register order: [2 half][16 t + r] = b[32 t + acc_row(r, half)], r < 16."""
+    half, t, r = np.arange(2)[:, None, None], np.arange(len(b) // 32)[:, None], np.arange(16)
+    return b[32 * t + acc_row(r, half)].reshape(2, -1)
+
+
+# ----------------------------------------------------------------------------- SATU host packers: state_dict -> {name: host tensor}
+def _f32(a: np.ndarray) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+
+
+def _img(*parts: np.ndarray) -> torch.Tensor:
+    """The split-bf16 image of the parts, each rounded to fp32, one after the other."""
+    return split_bf16_image(torch.from_numpy(np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1) for a in parts])))
+
+
+def pack_satu_heads(sd) -> Dict[str, torch.Tensor]:
+    """The coordinate MLP (body, routing / offset / st_offset heads, savsr_arch.py:242-257): 64 hidden units at every num_feat."""
+    p = "upsample."
+    head_w = torch.cat([sd[p + "routing.0.weight"], sd[p + "offset.weight"], sd[p + "st_offset.weight"]], 0)
+    head_b = torch.cat([sd[p + "routing.0.bias"], sd[p + "offset.bias"], sd[p + "st_offset.bias"]], 0)
+    return dict(body0_w=sd[p + "body.0.weight"].reshape(64, 4), body0_b=sd[p + "body.0.bias"],
+                body2_w=sd[p + "body.2.weight"].reshape(64, 64).t(), body2_b=sd[p + "body.2.bias"],
+                head_w=head_w.reshape(8, 64), head_b=head_b)
+
+
+def _pack_kconv(m: Dict[str, np.ndarray], c: int) -> Dict[str, torch.Tensor]:
+    return dict(kconv_w=_img(lanes_kconv(m["kconv"], c)), kconv_b=_f32(m["kconv_b"].reshape(c, 25).T))      # bias [tap][ch]
+
+
+def pack_satu_nf(sd, c: int) -> Dict[str, torch.Tensor]:
+    """savsr_satu_nf_weights (num_feat = c): fold_satu_nf's products rounded to fp32, the LR-side matrices then split to (hi, lo) bf16
+    pairs in lane order; wbe and fb stay fp32.  proj_w = Wt27 Wa in accumulator order, then the x side as A-operand tiles: tile 0 =
+    Wt27 Wb, tiles 1 .. = the C-stack, zero-padded to whole 32-row tiles."""
+    m = fold_satu_nf(sd, c)
+    xm = np.zeros((32 + (c // 2 + 31) // 32 * 32, c), dtype=np.float64)
+    xm[:32], xm[32:32 + c // 2] = m["tb"], m["cstack"]
+    return dict(**_pack_kconv(m, c), proj_w=_img(lanes_acc(m["ta"]), *(lanes_a(xm, r) for r in range(0, len(xm), 32))),
+                wbe=_f32(m["wbe"]), fusion_b=_f32(m["fb"]))
+
+
+def pack_satu_tuned(sd, form: str) -> Dict[str, torch.Tensor]:
+    """savsr_satu_weights of a tuned 64-wide form (3 channels): "plain" (savsr_satu_lr_stage / _hr_upsample: Wa | Wb | C-stack, Wb E_n and
+    b un-projected, two 32-row tiles each, plus the kernel_conv images every form shares), "p27" (savsr_satu_*_tail) or "q"
+    (savsr_satu_hr_tail_q, rows by row_q): proj_w = (Wt Wa | Wt Wb | C-stack), wbe_w = (Wt Wb E_n) as MFMA tiles, fusion_b = Wt b."""
+    m = fold_satu_nf(sd, 64, row_q if form == "q" else None, tail=form != "plain")
+    tiles = range(0, len(m["fb"]), 32)
+    wbe = m["wbe"].transpose(0, 2, 1)                                                 # [n][p][j]
+    t = dict(proj_w=_img(*(lanes_acc(m["ta"], r) for r in tiles), *(lanes_a(m["tb"], r) for r in tiles), lanes_a(m["cstack"])),
+             wbe_w=_img(*(lanes_wbe(wbe, r) for r in tiles)), fusion_b=_f32(bias_acc_order(m["fb"])))
+    return dict(**_pack_kconv(m, 64), **t) if form == "plain" else t
+
+
+def struct_of(cls, *tensors: Dict[str, torch.Tensor], rename: Optional[Dict[str, str]] = None, **fields):
+    """A ctypes struct of device pointers: field rename.get(k, k) = the address of tensors[..][k]; later dicts win.  The struct holds raw
+    addresses: the caller keeps the tensors referenced."""
+    w = cls(**fields)
+    for d in tensors:
+        for k, v in d.items():
+            setattr(w, (rename or {}).get(k, k), v.data_ptr())
+    return w
 
 
 def fuse_window_conv(sd, d: str, nch: int, sw: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -391,179 +502,36 @@ class WeightPacking:
             out[name] = t
         return out
 
-    def _pack_satu_heads(self, sd) -> dict:
-        """The coordinate MLP (body, routing / offset / st_offset heads, savsr_arch.py:242-257): 64 hidden units at every num_feat."""
-        p = "upsample."
-        head_w = torch.cat([sd[p + "routing.0.weight"], sd[p + "offset.weight"], sd[p + "st_offset.weight"]], 0)
-        head_b = torch.cat([sd[p + "routing.0.bias"], sd[p + "offset.bias"], sd[p + "st_offset.bias"]], 0)
-        return dict(body0_w=self._dev(sd[p + "body.0.weight"].reshape(64, 4)), body0_b=self._dev(sd[p + "body.0.bias"]),
-                    body2_w=self._dev(sd[p + "body.2.weight"].reshape(64, 64).t()), body2_b=self._dev(sd[p + "body.2.bias"]),
-                    head_w=self._dev(head_w.reshape(8, 64)), head_b=self._dev(head_b))
+    def _upload(self, host: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        return {k: self._dev(v, torch.int16 if v.dtype == torch.int16 else torch.float32) for k, v in host.items()}
 
     def _pack_satu_nf(self, sd, c: int):
-        """The width-generic SATU (savsr_satu_nf_*, num_feat = c): fold_satu_nf's float64 products rounded to fp32, the LR-side matrices
-        then split to (hi, lo) bf16 pairs in MFMA lane order (include/savsr_hip.h, savsr_satu_nf_weights); wbe and fb stay fp32."""
-        m = fold_satu_nf(sd, c)
-        lane = np.arange(64)
-        li, lh = lane & 31, lane >> 5
-        jj = np.arange(8)
-        ncg, nks, nct = c // 32, c // 16, (c // 2 + 31) // 32
-        # kconv groups [tap][cg][ks][lane][j] = Wk[25 (32 cg + (lane & 31)) + tap][16 ks + 8 (lane >> 5) + j]
-        tap = np.arange(25)[:, None, None, None, None]
-        cg = np.arange(ncg)[None, :, None, None, None]
-        ks = np.arange(nks)[None, None, :, None, None]
-        n_idx = 25 * (32 * cg + li[None, None, None, :, None]) + tap
-        k_idx = 16 * ks + 8 * lh[None, None, None, :, None] + jj[None, None, None, None, :]
-        n_idx, k_idx = np.broadcast_arrays(n_idx, k_idx)
-        kconv = m["kconv"][n_idx, k_idx].astype(np.float32)
-        kconv_b = m["kconv_b"].reshape(c, 25).T.astype(np.float32)                    # [tap][ch]
-        # Wt27 Wa: k step g consumes sta's accumulator registers 8 (g % 2) .. + 7 of channel group g // 2
-        pa = np.zeros((nks, 64, 8), dtype=np.float64)
-        for gi in range(nks):
-            ch = 32 * (gi // 2) + 16 * (gi % 2) + 8 * (jj[None, :] >> 2) + 4 * lh[:, None] + (jj[None, :] & 3)
-            pa[gi] = m["ta"][li[:, None], ch]
-        # x side: tile 0 = Wt27 Wb, tiles 1 .. nct = the C-stack, zero-padded to whole 32-row tiles; k = 16 ks + 8 (lane >> 5) + j
-        xm = np.zeros((32 * (1 + nct), c), dtype=np.float64)
-        xm[:32] = m["tb"]
-        xm[32:32 + c // 2] = m["cstack"]
-        px = np.zeros((1 + nct, nks, 64, 8), dtype=np.float64)
-        for t in range(1 + nct):
-            for ksi in range(nks):
-                px[t, ksi] = xm[32 * t + li[:, None], 16 * ksi + 8 * lh[:, None] + jj[None, :]]
-        proj = np.concatenate([pa.reshape(-1), px.reshape(-1)]).astype(np.float32)
-        t_ = lambda a: self._dev(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)))
-        img = lambda a: self._dev(split_bf16_image(torch.from_numpy(np.ascontiguousarray(a.reshape(-1)))), torch.int16)
-        self.satu_nf_t = dict(kconv_w=img(kconv), kconv_b=t_(kconv_b), proj_w=img(proj), wbe=t_(m["wbe"]), fusion_b=t_(m["fb"]))
-        w = SatuNfWeights()
-        w.C = c
-        for k, v in self.satu_nf_t.items():
-            setattr(w, k, v.data_ptr())
-        self.satu_nf_w = w
+        """The width-generic SATU (savsr_satu_nf_*, num_feat = c)."""
+        self.satu_nf_t = self._upload(pack_satu_nf(sd, c))
+        self.satu_nf_w = struct_of(SatuNfWeights, self.satu_nf_t, C=c)
 
     def _pack_satu(self, sd):
-        p = "upsample."
+        """Every SATU operand of this engine's form.  The *_t dicts keep the tensors the structs point at."""
         c = self.nf
-        f32 = torch.float32
+        heads = self._upload(pack_satu_heads(sd))
+        self.tail_w = self._dev(sd["tail.weight"].reshape(-1, c * 9))
+        self.tail_b = self._dev(sd["tail.bias"])
         if c != 64 or self.cfg["num_in_ch"] != 3:
-            # the width-generic SATU (num_feat 32, or any num_in_ch != 3: Wt with 9 num_in_ch live rows); the phase table's weights (savsr_satu_phase_table reads the body / head pointers only) travel in a
-            # savsr_satu_weights whose other pointers name the generic form's tensors
+            # the width-generic SATU (num_feat 32, or any num_in_ch != 3: Wt with 9 num_in_ch live rows); the phase table's weights
+            # (savsr_satu_phase_table reads the body / head pointers only) travel in a savsr_satu_weights whose other pointers name the
+            # generic form's tensors
             self._pack_satu_nf(sd, c)
-            self.satu_t = self._pack_satu_heads(sd)
-            sw = SatuWeights()
-            for k, v in self.satu_t.items():
-                setattr(sw, k, v.data_ptr())
-            for k, v in (("kconv_w", "kconv_w"), ("kconv_b", "kconv_b"), ("proj_w", "proj_w"), ("wbe_w", "wbe"), ("fusion_b", "fusion_b")):
-                setattr(sw, k, self.satu_nf_t[v].data_ptr())
-            self.satu_w = sw
+            self.satu_t = heads
+            self.satu_w = struct_of(SatuWeights, heads, self.satu_nf_t, rename={"wbe": "wbe_w"})
             self.satu_tail_t, self.satu_w_tail, self.satu_tailq_t, self.satu_w_tailq = None, None, None, None      # (the tuned 64-wide forms)
-            self.tail_w = self._dev(sd["tail.weight"].reshape(-1, c * 9))
-            self.tail_b = self._dev(sd["tail.bias"])
             return
         self.satu_nf_t, self.satu_nf_w = None, None
-        wk = sd[p + "kernel_conv.0.weight"].to("cpu", f32).reshape(25 * c, c).numpy()     # [n = 25 ch + tap][k]
-        bk = sd[p + "kernel_conv.0.bias"].to("cpu", f32).numpy()
-        lane = np.arange(64)
-        li, lh = lane & 31, lane >> 5
-        jj = np.arange(8)
-        # kconv part [tap][cg][ks][lane][j] = Wk[25 (32 cg + (lane & 31)) + tap][16 ks + 8 (lane >> 5) + j]
-        tap = np.arange(25)[:, None, None, None, None]
-        cg = np.arange(2)[None, :, None, None, None]
-        ks = np.arange(4)[None, None, :, None, None]
-        n_idx = 25 * (32 * cg + li[None, None, None, :, None]) + tap
-        k_idx = 16 * ks + 8 * lh[None, None, None, :, None] + jj[None, None, None, None, :]
-        n_idx, k_idx = np.broadcast_arrays(n_idx, k_idx)
-        kconv = wk[n_idx, k_idx].astype(np.float32)                                  # [25,2,4,64,8]
-        kconv_b = bk.reshape(c, 25).T.copy()                                          # [tap][ch]
-        fus = sd[p + "fusion.weight"].to("cpu", f32).reshape(c, 2 * c).numpy()
-        wa, wb = fus[:, :c], fus[:, c:]                                              # cat((sta, fea)), :374
-        comp = sd[p + "weight_compress"].to("cpu", f32).reshape(4, 8, c).numpy()     # C_m[j][c]
-        expd = sd[p + "weight_expand"].to("cpu", f32).reshape(4, c, 8).numpy()       # E_n[c][j]
-        # projections, one 512-element group per (matrix tile, k step): [lane][j]
-        pa = np.zeros((2, 4, 64, 8), dtype=np.float32)
-        pb = np.zeros((2, 4, 64, 8), dtype=np.float32)
-        pc = np.zeros((4, 64, 8), dtype=np.float32)
-        for t in range(2):
-            for kidx in range(4):
-                cgi, s = kidx // 2, kidx % 2
-                # k order of an accumulator used as B operand: row 16 s + 8 (j >> 2) + 4 half + (j & 3)
-                ch = 32 * cgi + 16 * s + 8 * (jj[None, :] >> 2) + 4 * lh[:, None] + (jj[None, :] & 3)
-                pa[t, kidx] = wa[(32 * t + li)[:, None], ch]
-            for ksi in range(4):
-                pb[t, ksi] = wb[(32 * t + li)[:, None], 16 * ksi + 8 * lh[:, None] + jj[None, :]]
-        cstack = comp.reshape(32, c)                                                  # row 8 m + j (natural order in the record)
-        for ksi in range(4):
-            pc[ksi] = cstack[li[:, None], 16 * ksi + 8 * lh[:, None] + jj[None, :]]
-        proj = np.concatenate([pa.reshape(-1), pb.reshape(-1), pc.reshape(-1)])
-        wbe = np.einsum("oc,ncj->noj", wb.astype(np.float64), expd.astype(np.float64)).astype(np.float32)   # (Wb E_n)[co][j]
-        wbe_p = np.zeros((2, 2, 64, 8), dtype=np.float32)                            # [t][ks][lane][j], k = 16 ks + 8 kh + j = 8 n + j
-        for t in range(2):
-            for ksi in range(2):
-                wbe_p[t, ksi] = wbe[(2 * ksi + lh)[:, None], (32 * t + li)[:, None], jj[None, :]]
-        fb = sd[p + "fusion.bias"].to("cpu", f32).numpy()
-        fb_p = np.zeros((2, 32), dtype=np.float32)
-        for hh in range(2):
-            for t in range(2):
-                for r in range(16):
-                    fb_p[hh, 16 * t + r] = fb[32 * t + acc_row(r, hh)]
-        head_w = torch.cat([sd[p + "routing.0.weight"], sd[p + "offset.weight"], sd[p + "st_offset.weight"]], 0)
-        head_b = torch.cat([sd[p + "routing.0.bias"], sd[p + "offset.bias"], sd[p + "st_offset.bias"]], 0)
-        t_ = lambda a: self._dev(torch.from_numpy(np.ascontiguousarray(a)))
-        img = lambda a: self._dev(split_bf16_image(torch.from_numpy(np.ascontiguousarray(a.reshape(-1)))), torch.int16)
-        self.satu_t = dict(
-            body0_w=self._dev(sd[p + "body.0.weight"].reshape(64, 4)), body0_b=self._dev(sd[p + "body.0.bias"]),
-            body2_w=self._dev(sd[p + "body.2.weight"].reshape(64, 64).t()), body2_b=self._dev(sd[p + "body.2.bias"]),
-            head_w=self._dev(head_w.reshape(8, 64)), head_b=self._dev(head_b),
-            kconv_w=img(kconv), kconv_b=t_(kconv_b), proj_w=img(proj), wbe_w=img(wbe_p), fusion_b=t_(fb_p))
-        sw = SatuWeights()
-        for k, v in self.satu_t.items():
-            setattr(sw, k, v.data_ptr())
-        self.satu_w = sw
-        self.tail_w = self._dev(sd["tail.weight"].reshape(3, c * 9))
-        self.tail_b = self._dev(sd["tail.bias"])
-        # ---- tail-projected form (include/savsr_hip.h, savsr_satu_*_tail): the 3x3 tail conv's channel contraction
-        # Wt27[p][c] (rows 27..31 zero) multiplied into fusion / expand / the LR projections in float64.  Two row orders:
-        # p = 3 (3 ky + kx) + o (savsr_satu_hr_tail + savsr_tail_gather), and the row-summed form's (savsr_satu_hr_tail_q: the three kx
-        # of group g = 3 ky + o at MFMA rows acc_row(3 gi + kx, half), groups 0 .. 4 in lane half 0, 5 .. 8 in half 1)
-        tw = sd["tail.weight"].to("cpu", torch.float64).numpy()                          # [3 o][64 c][3 ky][3 kx]
-
-        def fold(row_of):
-            wt27 = np.zeros((32, c), dtype=np.float64)
-            for ky in range(3):
-                for kx in range(3):
-                    for o in range(3):
-                        wt27[row_of(ky, kx, o)] = tw[o, :, ky, kx]
-            ta = (wt27 @ wa.astype(np.float64)).astype(np.float32)                           # [32][64] applies to sta
-            tb = (wt27 @ wb.astype(np.float64)).astype(np.float32)                           # [32][64] applies to x
-            pa1 = np.zeros((1, 4, 64, 8), dtype=np.float32)
-            pb1 = np.zeros((1, 4, 64, 8), dtype=np.float32)
-            for kidx in range(4):
-                cgi, s_ = kidx // 2, kidx % 2
-                ch = 32 * cgi + 16 * s_ + 8 * (jj[None, :] >> 2) + 4 * lh[:, None] + (jj[None, :] & 3)
-                pa1[0, kidx] = ta[li[:, None], ch]
-                pb1[0, kidx] = tb[li[:, None], 16 * kidx + 8 * lh[:, None] + jj[None, :]]
-            proj1 = np.concatenate([pa1.reshape(-1), pb1.reshape(-1), pc.reshape(-1)])
-            twbe = np.einsum("pc,ncj->npj", wt27 @ wb.astype(np.float64), expd.astype(np.float64)).astype(np.float32)   # (Wt27 Wb E_n)[p][j]
-            twbe_p = np.zeros((1, 2, 64, 8), dtype=np.float32)
-            for ksi in range(2):
-                twbe_p[0, ksi] = twbe[(2 * ksi + lh)[:, None], li[:, None], jj[None, :]]
-            tfb = (wt27 @ fb.astype(np.float64)).astype(np.float32)
-            tfb_p = np.zeros((2, 16), dtype=np.float32)
-            for hh in range(2):
-                for r in range(16):
-                    tfb_p[hh, r] = tfb[acc_row(r, hh)]
-            tens = dict(proj_w=img(proj1), wbe_w=img(twbe_p), fusion_b=t_(tfb_p))
-            swt = SatuWeights()
-            for k, v in self.satu_t.items():
-                setattr(swt, k, v.data_ptr())
-            for k, v in tens.items():
-                setattr(swt, k, v.data_ptr())
-            return tens, swt
-
-        def row_q(ky, kx, o):
-            g = 3 * ky + o
-            return acc_row(3 * g + kx, 0) if g < 5 else acc_row(3 * (g - 5) + kx, 1)
-        self.satu_tail_t, self.satu_w_tail = fold(lambda ky, kx, o: 3 * (3 * ky + kx) + o)
-        self.satu_tailq_t, self.satu_w_tailq = fold(row_q)
+        self.satu_t = {**heads, **self._upload(pack_satu_tuned(sd, "plain"))}
+        self.satu_w = struct_of(SatuWeights, self.satu_t)
+        # the tail-projected forms (include/savsr_hip.h, savsr_satu_*_tail): heads and kernel_conv of the plain form, the rest projected
+        self.satu_tail_t, self.satu_tailq_t = self._upload(pack_satu_tuned(sd, "p27")), self._upload(pack_satu_tuned(sd, "q"))
+        self.satu_w_tail = struct_of(SatuWeights, self.satu_t, self.satu_tail_t)
+        self.satu_w_tailq = struct_of(SatuWeights, self.satu_t, self.satu_tailq_t)
 
     def _pack_all(self, sd):
         cfg = self.cfg

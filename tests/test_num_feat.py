@@ -77,11 +77,11 @@ def _grid_sample64(x, offset, scale):
     return F.grid_sample(x, g.double(), mode="bilinear", padding_mode="zeros", align_corners=True)
 
 
-def lr_planes_float64(sd, nf, x, st):
+def lr_planes_float64(sd, nf, x, st, row_of=None):
     """float64 LR side of the tail-projected SATU from fold_satu_nf's products: (Wt27 Wa sta [32], Wt27 Wb x [32], C-stack x [nf/2]),
-    each [1][rows][h][w].  x, st: [1][nf][h][w]."""
+    each [1][rows][h][w].  x, st: [1][nf][h][w]; row_of: the row order of Wt27 (default: the 27-plane forms')."""
     from savsr_amd.packing import fold_satu_nf
-    m = fold_satu_nf(sd, nf)
+    m = fold_satu_nf(sd, nf, row_of)
     _, _, h, w = x.shape
     x64, st64 = x[0].double().reshape(nf, -1), st[0].double().reshape(nf, -1)
     k = torch.from_numpy(m["kconv"]) @ st64 + torch.from_numpy(m["kconv_b"])[:, None]
@@ -91,15 +91,15 @@ def lr_planes_float64(sd, nf, x, st):
             (torch.from_numpy(m["cstack"]) @ x64).reshape(1, nf // 2, h, w))
 
 
-def p32_float64(sd, nf, x, st, sc):
+def p32_float64(sd, nf, x, st, sc, row_of=None):
     """The 32 tail-projected planes P (rows 27 .. 31 zero) in float64: two bilinear gathers of the LR planes, expert mixing, Wt27 b."""
     from savsr_amd.packing import fold_satu_nf
-    m = fold_satu_nf(sd, nf)
+    m = fold_satu_nf(sd, nf, row_of)
     _, _, h, w = x.shape
     H, W = O.get_hw(h, w, sc)
     with torch.no_grad():
         off, soff, r = O.satu_heads(sd, "upsample", h, w, sc)
-    a, b, cs = lr_planes_float64(sd, nf, x, st)
+    a, b, cs = lr_planes_float64(sd, nf, x, st, row_of)
     ga, gb, gc = _grid_sample64(a, soff, sc)[0], _grid_sample64(b, off, sc)[0], _grid_sample64(cs, off, sc)[0]
     rr = r[0].double()                                                           # [4][H][W]
     J = nf // 8
