@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 33
+#define SAVSR_ABI_VERSION 34
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -228,6 +228,24 @@ int savsr_se_scale_residual(const float* partial, int nblk, float inv_n, const f
 int savsr_se_scale_residual_batch(const float* partial, int nblk, float inv_n, const float* w1, const float* b1,
                                   const float* w2, const float* b2, int c, int cmid, const float* r, const float* x, float* out,
                                   int64_t npx, int nclip, int64_t partial_stride, int64_t r_stride, int64_t x_stride, int64_t out_stride, void* stream);
+
+/* (ABI 34) The RCAB (savsr_arch.py:527-549) with the SE gate folded into conv.2's weights.  The gate needs the global mean of conv.2's
+ * output, and the mean of a zero-padded 3x3 conv's output is a function of its input r1 = ReLU(conv.0(x)):
+ *   mean r2[co] = b[co] + (1/n) sum W[co][ci][ky][kx] S[ci][ky][kx],  S = r1[ci] summed over the pixels tap (ky, kx) sees = the channel's
+ *   total (partial: conv.0's pool partials, [nblk][c]) less one border row and / or column, plus the corner both took away (read from r1,
+ *   [h][w][pix] channel-last).
+ * a [cmid][c * 9] = w1 W and cz [cmid] = w1 b + b1 are the gate's first layer composed with the conv on the host; w2 [c][cmid], b2 [c].
+ * Per clip:  z = ReLU(a S * inv_n + cz),  g = sigmoid(w2 z + b2)  -> gate_out [c];  bias_out [c] = g * bias;  wimg_out = the weight image
+ * of g[co] * master: master is ONE fp32 part in the element order of savsr_conv_pack_index (wy == 0) or savsr_conv_wy_pack_index (wy != 0,
+ * c % 64 == 0: the transform U of W rounded to fp32), written as the split-bf16 image (hi, lo) or, f16 != 0, rounded once to fp16 -- what
+ * savsr_conv2d_batch(_f16) takes as `wpacked` with `bias_out` as bias and res1 = x:  out = x + g (.) conv.2(r1).
+ * c in {16, 32, 64}, cmid <= 16.  Clip b's partial / r1 / wimg_out / bias_out / gate_out lie b * the given byte strides (multiples of 16)
+ * behind clip 0's.  Every summation order is fixed: the same bits in every workgroup, for any clip count and on any stream. */
+int savsr_rcab_gate_weights_batch(const float* partial, int nblk, float inv_n, const float* r1, int h, int w, int pix,
+                                  const float* a, const float* cz, const float* w2, const float* b2, int c, int cmid,
+                                  const float* master, const float* bias, int wy, int f16, void* wimg_out, float* bias_out, float* gate_out,
+                                  int nclip, int64_t partial_stride, int64_t r1_stride, int64_t wimg_stride, int64_t bias_stride,
+                                  int64_t gate_stride, void* stream);
 
 /* nn.AvgPool2d(2) (savsr_arch.py:193): [h][w][c] -> [h/2][w/2][c], h and w even, contiguous. */
 int savsr_avgpool2(const float* in, float* out, int c, int h, int w, void* stream);

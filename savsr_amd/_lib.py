@@ -18,7 +18,7 @@ MAX_SRC = 5
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID = 0, 1, 2, 3
 SATU_LRCAT = 160
 SATU_TABLE = 8
-ABI_VERSION = 33
+ABI_VERSION = 34
 CONV_DIRECT, CONV_DIRECT_THROUGHPUT, CONV_WINOGRAD_Y, CONV_WINOGRAD_Y_THROUGHPUT = 0, 2, 3, 4
 CONV_WY_FORMS = (CONV_WINOGRAD_Y, CONV_WINOGRAD_Y_THROUGHPUT)
 SATU_LRCAT_TAIL = 96
@@ -111,6 +111,9 @@ SIGNATURES = {
     "savsr_se_scale_residual": (C.c_int, [fptr, C.c_int, C.c_float, fptr, fptr, fptr, fptr, C.c_int, C.c_int, fptr, fptr, fptr, C.c_int64, C.c_void_p]),
     "savsr_se_scale_residual_batch": (C.c_int, [fptr, C.c_int, C.c_float, fptr, fptr, fptr, fptr, C.c_int, C.c_int, fptr, fptr, fptr, C.c_int64, C.c_int,
                                                 C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "savsr_rcab_gate_weights_batch": (C.c_int, [fptr, C.c_int, C.c_float, fptr, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr, C.c_int, C.c_int,
+                                                fptr, fptr, C.c_int, C.c_int, fptr, fptr, fptr, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                                C.c_int64, C.c_void_p]),
     "savsr_avgpool2": (C.c_int, [fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "savsr_upsample2x": (C.c_int, [fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "savsr_pack_windows": (C.c_int, [fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -34,6 +34,7 @@ class EngineConfig:
     wy_min_tiles_tp: int = 100             # SAVSR_WY_MIN_TILES_TP: ... and in the throughput flow
     satu_q: bool = True                    # SAVSR_SATU_Q: SATU HR stage in the row-summed tail form (9 planes + seams); 0: the 27-plane form
     osconv_fused: bool = False             # SAVSR_OSCONV_FUSED: OSConv weight generation as one launch (measured slower: DESIGN.md section 9)
+    rcab_fold: int = 1                     # SAVSR_RCAB_FOLD: the RCAB's SE gate evaluated from conv.0's output and folded into conv.2's weights (no scale-residual pass) -- 1: in the throughput flow (+3.2 % on the bench line), 2: in the latency flow too (one clip in flight: 8.55 -> 8.68 ms, the gate launch is longer than the pass it replaces), 0: conv, conv, savsr_se_scale_residual_batch everywhere
     reuse_buffers: bool = True             # SAVSR_REUSE_BUFFERS: liveness-planned LR buffers; 0: every name its own memory
     # ---- caches ----------------------------------------------------------------------------------------------------------------
     cache_shapes: int = 256                # SAVSR_CACHE_SHAPES: LR shapes resident per engine (count cap; the byte budget normally decides)
@@ -66,6 +67,7 @@ class EngineConfig:
             wy_min_tiles_tp=int(e("SAVSR_WY_MIN_TILES_TP", "100")),
             satu_q=_flag("SAVSR_SATU_Q", True),
             osconv_fused=_flag("SAVSR_OSCONV_FUSED", False),
+            rcab_fold=min(2, max(0, int(e("SAVSR_RCAB_FOLD", "1")))),
             reuse_buffers=_flag("SAVSR_REUSE_BUFFERS", True),
             cache_shapes=max(1, int(e("SAVSR_CACHE_SHAPES", "256"))),
             cache_scales=max(1, int(e("SAVSR_CACHE_SCALES", "48"))),

@@ -683,6 +683,194 @@ __global__ __launch_bounds__(1024) void se_scale_residual_kernel(const float* pa
     for (long long i = i0 + SE_UNROLL * stride; i < n4; i += stride) apply(i, r[i], x[i]);
 }
 
+// The RCAB with its SE gate folded into conv.2's weights (savsr_arch.py:514-524,527-549; ABI 34, savsr_rcab_gate_weights_batch).
+// The gate needs the global mean of r2 = conv.2(r1), and the mean of a zero-padded 3x3 conv's output is a function of its INPUT:
+//   mean r2[co] = b[co] + (1/n) sum_{ci,ky,kx} W[co][ci][ky][kx] S[ci][ky][kx],   S = sum of r1[ci] over the pixels tap (ky, kx) sees
+//               = the channel's total, less one border row and / or one border column, plus the corner both took away.
+// The total comes from conv.0's pool partials, the four border lines and corners are read from r1 (256 KB at 180x320), and the gate's
+// first layer arrives pre-composed with the conv (a = w1 W as [cmid][c * 9], cz = w1 b + b1: packing.py::rcab_fold_tables), so the gate is
+// known BEFORE conv.2 runs:  out = conv_{g (.) W}(r1) + g b + x  through conv.2's own epilogue -- no pass over r2 / x / out.
+// One launch: every workgroup evaluates the gate (~0.3 MB of L2 reads at 180x320; every summation order is fixed by the 1024-thread
+// mapping alone, so all workgroups, grids, clip counts and streams get the same bits), then scales its slice of the fp32 master image
+// (one part in the element order of the conv's weight image, direct or Winograd-y) by g[co] and writes the split-bf16 / fp16 image.
+// blockIdx.y = clip of a batched launch sequence; the `*_bs` are BYTES from one clip's operand to the next.
+struct RcabGateParams {
+    const float* partial;       // conv.0's pool partials [nblk][c]
+    const float* r1;            // conv.0's output [h][w][pix], channels 0 .. c - 1
+    const float* a;             // [cmid][c * 9]
+    const float* cz;            // [cmid]
+    const float* w2;            // [c][cmid]
+    const float* b2;            // [c]
+    const float* master;        // [nunits * 8] fp32, image order of ONE part
+    const float* bias;          // [c] conv.2's bias
+    void* wimg_out;
+    float* bias_out;            // [c] g b
+    float* gate_out;            // [c] g (observable)
+    long long nunits, part_bs, r1_bs, wimg_bs, bias_bs, gate_bs;
+    float inv_n;
+    int nblk, h, w, pix, c, cmid, taps;      // taps: 9 = direct image, 12 = Winograd-y image
+};
+// fl(a b): a product the compiler does not contract into a neighbouring add / subtract
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+constexpr int RG_LINES = 5, RG_MAXC = 64, RG_WAVES = 16;      // total | top row | bottom row | left column | right column
+
+template <bool F16>
+__global__ __launch_bounds__(1024) void rcab_gate_weights_kernel(const RcabGateParams p) {
+    __shared__ __attribute__((aligned(16))) float red[RG_WAVES * RG_LINES * RG_MAXC];
+    __shared__ float line[RG_LINES * RG_MAXC];
+    __shared__ float crn[4 * RG_MAXC];
+    __shared__ float S[9 * RG_MAXC];
+    __shared__ float z[RG_WAVES];
+    __shared__ float g[RG_MAXC];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = p.c, h = p.h, w = p.w, pix = p.pix;
+    const long long cb = blockIdx.y;
+    const float* partial = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.partial) + cb * p.part_bs);
+    const float* r1 = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.r1) + cb * p.r1_bs);
+    // what does not depend on the gate goes out first and lands under the reduction: this thread's unit of the master image ...
+    const long long unit = (long long)blockIdx.x * 1024 + tid;
+    const bool live = unit < p.nunits;
+    f32x4 m0 = {0.f, 0.f, 0.f, 0.f}, m1 = m0;
+    if (live) {
+        const f32x4* mp = reinterpret_cast<const f32x4*>(p.master + unit * 8);
+        m0 = mp[0];
+        m1 = mp[1];
+    }
+    // ... the pre-composed first layer (wave m < cmid owns hidden unit m: c * 9 <= 576 = 9 x 64 columns) and the second (thread o < c owns output o)
+    constexpr int AQ = 9 * RG_MAXC / 64;
+    float av[AQ], czv = 0.f;
+#pragma unroll
+    for (int q = 0; q < AQ; ++q) {
+        const int i = lane + 64 * q;
+        av[q] = (wave < p.cmid && i < 9 * c) ? p.a[wave * 9 * c + i] : 0.f;
+    }
+    if (wave < p.cmid) czv = p.cz[wave];
+    float w2v[RG_WAVES], b2v = 0.f;
+#pragma unroll
+    for (int k = 0; k < RG_WAVES; ++k) w2v[k] = (tid < c && k < p.cmid) ? p.w2[tid * p.cmid + k] : 0.f;
+    if (tid < c) b2v = p.b2[tid];
+    // ... and the four corner pixels (k = 2 bottom + right)
+    float cv = 0.f;
+    if (tid < 4 * c) {
+        const int k = tid / c, ch = tid - k * c;
+        const long long px = (long long)((k >> 1) ? h - 1 : 0) * w + ((k & 1) ? w - 1 : 0);
+        cv = r1[px * pix + ch];
+    }
+    // the five line sums per channel quad: thread (slot, cg) walks records slot, slot + PL, .. of every line in index order ...
+    const int G = c >> 2, cg = tid % G, slot = tid / G, PL = 1024 / G;
+    f32x4 acc[RG_LINES];
+#pragma unroll
+    for (int l = 0; l < RG_LINES; ++l) acc[l] = f32x4{0.f, 0.f, 0.f, 0.f};
+    auto add = [](f32x4& s, const f32x4& v) { s[0] += v[0]; s[1] += v[1]; s[2] += v[2]; s[3] += v[3]; };
+#pragma unroll 4
+    for (int b = slot; b < p.nblk; b += PL) add(acc[0], *reinterpret_cast<const f32x4*>(partial + (long long)b * c + 4 * cg));
+    const float* bot = r1 + (long long)(h - 1) * w * pix;
+#pragma unroll 4
+    for (int x = slot; x < w; x += PL) {
+        add(acc[1], *reinterpret_cast<const f32x4*>(r1 + (long long)x * pix + 4 * cg));
+        add(acc[2], *reinterpret_cast<const f32x4*>(bot + (long long)x * pix + 4 * cg));
+    }
+    const float* rgt = r1 + (long long)(w - 1) * pix;
+#pragma unroll 4
+    for (int y = slot; y < h; y += PL) {
+        add(acc[3], *reinterpret_cast<const f32x4*>(r1 + (long long)y * w * pix + 4 * cg));
+        add(acc[4], *reinterpret_cast<const f32x4*>(rgt + (long long)y * w * pix + 4 * cg));
+    }
+    // ... then across the wave's 64 / G slots (butterfly), and across the 16 waves in wave order through LDS
+#pragma unroll
+    for (int l = 0; l < RG_LINES; ++l)
+        for (int o = G; o < 64; o <<= 1) {
+            acc[l][0] += __shfl_xor(acc[l][0], o, 64); acc[l][1] += __shfl_xor(acc[l][1], o, 64);
+            acc[l][2] += __shfl_xor(acc[l][2], o, 64); acc[l][3] += __shfl_xor(acc[l][3], o, 64);
+        }
+    if (lane < G)
+#pragma unroll
+        for (int l = 0; l < RG_LINES; ++l) *reinterpret_cast<f32x4*>(red + (wave * RG_LINES + l) * c + 4 * lane) = acc[l];
+    if (tid < 4 * c) crn[tid] = cv;
+    __syncthreads();
+    if (tid < RG_LINES * c) {
+        const int l = tid / c, ch = tid - l * c;
+        float s = 0.f;
+#pragma unroll
+        for (int wv = 0; wv < RG_WAVES; ++wv) s += red[(wv * RG_LINES + l) * c + ch];
+        line[tid] = s;
+    }
+    __syncthreads();
+    // S[ci][ky][kx]: tap ky = 0 never sees the bottom row, ky = 2 never the top row; kx = 0 never the right column, kx = 2 never the left
+    if (tid < 9 * c) {
+        const int ci = tid / 9, t = tid - 9 * ci, ky = t / 3, kx = t - 3 * ky;
+        float s = line[ci];
+        if (ky == 0) s -= line[2 * c + ci];
+        if (ky == 2) s -= line[c + ci];
+        if (kx == 0) s -= line[4 * c + ci];
+        if (kx == 2) s -= line[3 * c + ci];
+        if (ky == 0 && kx == 0) s += crn[3 * c + ci];
+        if (ky == 0 && kx == 2) s += crn[2 * c + ci];
+        if (ky == 2 && kx == 0) s += crn[c + ci];
+        if (ky == 2 && kx == 2) s += crn[ci];
+        S[tid] = s;
+    }
+    __syncthreads();
+    if (wave < p.cmid) {                                  // z = ReLU(a S / n + cz): per lane in column order, then across the wave
+        float s = 0.f;
+#pragma unroll
+        for (int q = 0; q < AQ; ++q) {
+            const int i = lane + 64 * q;
+            if (i < 9 * c) s += av[q] * S[i];
+        }
+        s = wave_sum(s);
+        if (lane == 0) z[wave] = fmaxf(s * p.inv_n + czv, 0.f);
+    }
+    __syncthreads();
+    if (tid < c) {
+        float s = b2v;
+#pragma unroll
+        for (int k = 0; k < RG_WAVES; ++k)
+            if (k < p.cmid) s += w2v[k] * z[k];
+        const float gv = sigmoidf_(s);
+        g[tid] = gv;
+        if (blockIdx.x == 0) {
+            reinterpret_cast<float*>(reinterpret_cast<char*>(p.gate_out) + cb * p.gate_bs)[tid] = gv;
+            reinterpret_cast<float*>(reinterpret_cast<char*>(p.bias_out) + cb * p.bias_bs)[tid] = gv * p.bias[tid];
+        }
+    }
+    __syncthreads();
+    // ---- this workgroup's slice of the image: one 8-element lane unit per thread, all of output channel co ----
+    if (!live) return;
+    const int cot = conv_cot(c), nt = cot / 32;
+    const long long group = unit >> 6;                    // (cob, chunk, tap | (hf, vr, kx), t)
+    const int ln = (int)(unit & 63), row = ln & 31;
+    const int t = (int)(group % nt);
+    const int cob = (int)(group / ((long long)(c / 16) * p.taps * nt));
+    const int co = cob * cot + 32 * t + row;
+    const float gc = co < c ? g[co] : 0.f;
+    // one ROUNDED fp32 product per element, then the split: no contraction of the product into the split's subtraction (the image is
+    // split(fl(g master)), what a host restatement computes)
+    const float x[8] = {mul_rounded(gc, m0[0]), mul_rounded(gc, m0[1]), mul_rounded(gc, m0[2]), mul_rounded(gc, m0[3]),
+                        mul_rounded(gc, m1[0]), mul_rounded(gc, m1[1]), mul_rounded(gc, m1[2]), mul_rounded(gc, m1[3])};
+    char* out = reinterpret_cast<char*>(p.wimg_out) + cb * p.wimg_bs;
+    if constexpr (F16) {
+        f16x8 hv;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) hv[j] = (_Float16)x[j];
+        reinterpret_cast<f16x8*>(out)[unit] = hv;
+        return;
+    }
+    bf16x8 hi, lo;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const __bf16 hh = (__bf16)x[j];
+        hi[j] = hh;
+        lo[j] = (__bf16)(x[j] - (float)hh);
+    }
+    bf16x8* img = reinterpret_cast<bf16x8*>(out);
+    img[group * 128 + ln] = hi;
+    img[group * 128 + 64 + ln] = lo;
+}
+
 // out[px][c] = r[px][c] * gate[c] + x[px][c]   (savsr_arch.py:524,548-549), c == 64 contiguous
 __global__ __launch_bounds__(256) void scale_residual_kernel(const f32x4* __restrict__ r, const float* __restrict__ gate,
                                                              const f32x4* __restrict__ x, f32x4* __restrict__ out, long long n4, int c4) {
@@ -808,6 +996,34 @@ extern "C" int savsr_se_scale_residual_batch(const float* partial, int nblk, flo
 extern "C" int savsr_se_scale_residual(const float* partial, int nblk, float inv_n, const float* w1, const float* b1, const float* w2,
                                        const float* b2, int c, int cmid, const float* r, const float* x, float* out, int64_t npx, void* stream) {
     return savsr_se_scale_residual_batch(partial, nblk, inv_n, w1, b1, w2, b2, c, cmid, r, x, out, npx, 1, 0, 0, 0, 0, stream);
+}
+
+extern "C" int savsr_rcab_gate_weights_batch(const float* partial, int nblk, float inv_n, const float* r1, int h, int w, int pix, const float* a,
+                                             const float* cz, const float* w2, const float* b2, int c, int cmid, const float* master, const float* bias,
+                                             int wy, int f16, void* wimg_out, float* bias_out, float* gate_out, int nclip, int64_t partial_stride,
+                                             int64_t r1_stride, int64_t wimg_stride, int64_t bias_stride, int64_t gate_stride, void* stream) {
+    if (!partial || !r1 || !a || !cz || !w2 || !b2 || !master || !bias || !wimg_out || !bias_out || !gate_out) return fail_arg("rcab_gate_weights: null pointer");
+    if ((c != 16 && c != 32 && c != 64) || cmid < 1 || cmid > RG_WAVES || nblk < 1 || h < 1 || w < 1 || pix < c || (pix & 3) || (int64_t)h * w * pix >= (int64_t)1 << 31)
+        return fail_arg("rcab_gate_weights: shape (c 16 / 32 / 64, cmid <= 16, pix >= c a multiple of 4)");
+    if (wy && c % 64) return fail_arg("rcab_gate_weights: the Winograd-y image needs c % 64 == 0");
+    if (nclip < 1 || nclip > 64 || ((partial_stride | r1_stride | wimg_stride | bias_stride | gate_stride) & 15) ||
+        (nclip > 1 && (wimg_stride == 0 || bias_stride == 0 || gate_stride == 0)))
+        return fail_arg("rcab_gate_weights: 1..64 clips, strides multiples of 16 bytes, distinct outputs");
+    if ((reinterpret_cast<uintptr_t>(partial) | reinterpret_cast<uintptr_t>(r1) | reinterpret_cast<uintptr_t>(master) | reinterpret_cast<uintptr_t>(wimg_out)) & 15) {
+        set_error("rcab_gate_weights: partial / r1 / master / wimg_out must be 16-byte aligned");
+        return SAVSR_E_ALIGN;
+    }
+    RcabGateParams p;
+    p.partial = partial; p.r1 = r1; p.a = a; p.cz = cz; p.w2 = w2; p.b2 = b2; p.master = master; p.bias = bias;
+    p.wimg_out = wimg_out; p.bias_out = bias_out; p.gate_out = gate_out;
+    p.nunits = (wy ? savsr_conv_wy_packed_elems(c, c) : savsr_conv_packed_elems(c, c, 3)) / 8;
+    p.part_bs = partial_stride; p.r1_bs = r1_stride; p.wimg_bs = wimg_stride; p.bias_bs = bias_stride; p.gate_bs = gate_stride;
+    p.inv_n = inv_n; p.nblk = nblk; p.h = h; p.w = w; p.pix = pix; p.c = c; p.cmid = cmid; p.taps = wy ? 12 : 9;
+    if (p.nunits < 1) return fail_arg("rcab_gate_weights: image size");
+    const dim3 grid((unsigned)((p.nunits + 1023) / 1024), (unsigned)nclip);
+    if (f16) hipLaunchKernelGGL(rcab_gate_weights_kernel<true>, grid, dim3(1024), 0, static_cast<hipStream_t>(stream), p);
+    else hipLaunchKernelGGL(rcab_gate_weights_kernel<false>, grid, dim3(1024), 0, static_cast<hipStream_t>(stream), p);
+    return check_launch("rcab_gate_weights_kernel");
 }
 
 extern "C" int savsr_scale_residual(const float* r, const float* gate, const float* x, float* out, int c, int64_t npx, void* stream) {

@@ -65,12 +65,16 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self.pw16: Dict[str, torch.Tensor] = {}       # conv key -> fp16 image (direct form)
         self.pw16_wy: Dict[str, torch.Tensor] = {}    # conv key -> fp16 Winograd-y image
         self._conv_src: Dict[str, tuple] = {}         # conv key -> how its weight derives from the state_dict (packing.py::_conv_weight)
-        # Per-stream state: a sibling engine (clone_for_stream) owns its own `osc` scratch, `se_gate`, what _init_caches creates (buffer
+        # Per-stream state: a sibling engine (clone_for_stream) owns its own `osc` / `rcab_scr` scratch, `se_gate`, what _init_caches creates (buffer
         # contexts, hr_sched), `nb` / `_bstride` / `form_nb`, `conv_algo`, `satu_events` / `_st`, `_siblings` / `_streams` and the lazily made
         # `_cap_stream` / `_side_stream`.  EVERY other attribute is shared with the siblings by reference (packed weights, knobs, HR plans,
         # census, host_stats, ...): a new shared attribute needs nothing in clone_for_stream, a new per-stream one is reset there.
         self.osc: Dict[str, dict] = {}      # osconv key -> tensors
         self.se: Dict[str, tuple] = {}
+        self.rcab_w: Dict[str, dict] = {}     # RCAB prefix -> what the folded form reads (packing.py::_add_rcab_fold)
+        # RCAB with the SE gate folded into conv.2's weights (savsr_rcab_gate_weights_batch): 1 = in the throughput flow, 2 = in both flows,
+        # 0 = conv, conv, SE pass everywhere (SAVSR_RCAB_FOLD; `rcab`)
+        self.rcab_fold = kn.rcab_fold
         self._keep: List[torch.Tensor] = []
         self._init_caches()
         self.satu_events: Optional[list] = None     # bench.py: (start, end, clips) HIP events around the SATU stage(s) of a launch sequence
@@ -196,6 +200,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         e.nb, e._bstride, e.form_nb, e.conv_algo = 1, {}, 1, _lib.CONV_DIRECT
         e.osc = {k: dict(ent, **e._osc_scratch(ent["cin"], ent["cout"], ent["knum"], ent["nunits"] * 8)) for k, ent in self.osc.items()}
         e.se_gate = torch.empty_like(self.se_gate)
+        e.rcab_scr = e._rcab_scratch()
         e._init_caches()               # its own buffer contexts and hr_sched; the byte budget, SATU axis tables and count caps stay shared
         e.max_shapes, e.max_scales, e._budget, e._axes = self.max_shapes, self.max_scales, self._budget, self._axes
         self._budget["engines"].append(weakref.ref(e))
@@ -287,10 +292,18 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         return [u[3] for u in units]
 
     def rcab(self, pfx: str, x: Src, out: Src, hp: int, wp: int, tag: str) -> Src:
-        """savsr_arch.py:527-549."""
+        """savsr_arch.py:527-549.  `rcab_fold`: the gate is evaluated from conv.0's output (its pool partials and border lines) and multiplied
+        into conv.2's weights and bias, whose epilogue then writes out = x + g (.) conv.2(r1) itself -- no pass over r2, x and out.  By default in the throughput flow only:
+        with one clip in flight the gate launch (a handful of workgroups) takes longer than the 44 MB pass it replaces."""
         nf = self.nf
-        r1 = self.conv(pfx + ".0", [x], self.full(self.buf(f"{tag}.t1", hp, wp, nf)), hp, wp, ACT_RELU)
         part = self.pool_buf("se", hp, wp, nf)
+        if self.rcab_fold >= 2 or (self.rcab_fold == 1 and self.conv_algo == _lib.CONV_DIRECT_THROUGHPUT):
+            assert x.pix == nf and out.pix == nf
+            r1 = self.conv(pfx + ".0", [x], self.full(self.buf(f"{tag}.t1", hp, wp, nf)), hp, wp, ACT_RELU, pool=(part, 0, nf))
+            # (the form of the conv launch below decides the image's, as for an OSConv)
+            wd = self.rcab_gate_weights(pfx, r1, part, hp, wp, wy=self.osconv_wy(1, nf, hp, wp))
+            return self.conv(pfx + ".2", [r1], out, hp, wp, ACT_NONE, res1=x, weights=wd)
+        r1 = self.conv(pfx + ".0", [x], self.full(self.buf(f"{tag}.t1", hp, wp, nf)), hp, wp, ACT_RELU)
         r2 = self.conv(pfx + ".2", [r1], self.full(self.buf(f"{tag}.t2", hp, wp, nf)), hp, wp, ACT_NONE, pool=(part, 0, nf))
         nblk = self.pool_rows(hp, wp)
         w1, b1, w2, b2, cm = self.se[pfx]

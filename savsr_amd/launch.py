@@ -94,9 +94,10 @@ class Launcher:
         d.out, d.out_pix = out.ptr, out.pix
         if pool is not None:
             d.pool, d.pool_stride = pool[0].data_ptr() + 4 * pool[1], pool[2]
-        if self.nb > 1:      # bytes from clip b's operand to clip b + 1's (Python attribute): sources, out, res1, res2, mul_px, pool, weights
+        if self.nb > 1:      # bytes from clip b's operand to clip b + 1's (Python attribute): sources, out, res1, res2, mul_px, pool, weights, their bias
             d._bs = ([s.bs for s in srcs], out.bs, res1.bs if res1 is not None else 0, res2.bs if res2 is not None else 0, self._bs(mul_px),
-                     self._bs(pool[0]) if pool is not None else 0, self._bs(wpk) if weights is not None else 0)
+                     self._bs(pool[0]) if pool is not None else 0, self._bs(wpk) if weights is not None else 0,
+                     self._bs(bias) if weights is not None else 0)
             assert out.bs > 0, (key, "a batched launch writes one output per clip")
         return d
 
@@ -106,7 +107,7 @@ class Launcher:
         if b == 0:
             return d
         n = ConvDesc.from_buffer_copy(d)
-        src_bs, out_bs, r1_bs, r2_bs, mp_bs, pool_bs, w_bs = d._bs
+        src_bs, out_bs, r1_bs, r2_bs, mp_bs, pool_bs, w_bs, bias_bs = d._bs
         for i in range(d.nsrc):
             n.src[i] = d.src[i] + b * src_bs[i]
         n.out = d.out + b * out_bs
@@ -119,6 +120,8 @@ class Launcher:
         if d.pool:
             n.pool = d.pool + b * pool_bs
         n.wpacked = d.wpacked + b * w_bs
+        if d.bias:
+            n.bias = d.bias + b * bias_bs
         n._wy = getattr(d, "_wy", None)
         return n
 
@@ -249,6 +252,19 @@ class Launcher:
 
     def osconv_weights(self, key: str, srcs: List[Src], h: int, w: int, scale, pooled: bool = False, wy: bool = False):
         return self.osconv_launch([key], [self.osconv_desc(key, srcs, h, w, scale, pooled, wy)])[0]
+
+    def rcab_gate_weights(self, pfx: str, r1: Src, part: torch.Tensor, h: int, w: int, wy: bool = False):
+        """The folded RCAB's weight generation (savsr_rcab_gate_weights_batch, one launch for all clips of the launch sequence): the SE gate
+        g from conv.0's output r1 and its pool partials, then g (.) conv.2's master image and g b into the stream's scratch; returns the
+        conv `weights` tuple (the gate itself stays readable in rcab_scr["gate"])."""
+        e, s, nf = self.rcab_w[pfx], self.rcab_scr, self.nf
+        assert r1.ch == nf and (not wy or e["master_wy"] is not None)
+        _lib.check(self.lib.savsr_rcab_gate_weights_batch(
+            part.data_ptr(), self.pool_rows(h, w), 1.0 / (h * w), r1.ptr, h, w, r1.pix, e["a"].data_ptr(), e["cz"].data_ptr(), e["w2"].data_ptr(),
+            e["b2"].data_ptr(), nf, e["cm"], (e["master_wy"] if wy else e["master"]).data_ptr(), e["bias"].data_ptr(), int(wy),
+            int(self.precision == "fp16"), s["wimg"].data_ptr(), s["bias"].data_ptr(), s["gate"].data_ptr(), self.nb, self._bs(part), r1.bs,
+            self._bs(s["wimg"]), self._bs(s["bias"]), self._bs(s["gate"]), self._stream()), "savsr_rcab_gate_weights_batch")
+        return (s["wimg"], s["bias"], nf, nf, 3, self._wy_algo()) if wy else (s["wimg"], s["bias"], nf, nf, 3)
 
     # ------------------------------------------------------------------ SATU
     def satu_axes(self, h: int, w: int, scale):

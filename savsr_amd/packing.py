@@ -161,15 +161,52 @@ def _wy_transform(g: torch.Tensor) -> torch.Tensor:
     return torch.stack([g0, 0.5 * (g0 + g1 + g2), 0.5 * (g0 - g1 + g2), g2], 0)
 
 
-def pack_conv_weight_wy(w: torch.Tensor, device: Optional[torch.device] = None) -> torch.Tensor:
-    """[cout, cin, 3, 3] -> split-bf16 Winograd-y weight image (SAVSR_CONV_WINOGRAD_Y): _wy_transform in float64 (on `device`), rounded to
-    fp32, then (hi, lo)."""
+def pack_conv_part_wy(w: torch.Tensor, device: Optional[torch.device] = None) -> torch.Tensor:
+    """[cout, cin, 3, 3] -> fp32 tensor of one part of the Winograd-y image (zero padded), lane order: _wy_transform in float64 (on
+    `device`), rounded once to fp32."""
     cout, cin, ks, _ = w.shape
     assert ks == 3
     dev = device if device is not None and device.type != "cpu" else torch.device("cpu")
     u = _wy_transform(w.detach().to(dev, torch.float64)).to(torch.float32)
     idx, total = conv_wy_pack_index(cout, cin)
-    return split_bf16_image(_scatter_image(idx, total, u, "wy", (cout, cin), device))
+    return _scatter_image(idx, total, u, "wy", (cout, cin), device)
+
+
+def pack_conv_weight_wy(w: torch.Tensor, device: Optional[torch.device] = None) -> torch.Tensor:
+    """[cout, cin, 3, 3] -> split-bf16 Winograd-y weight image (SAVSR_CONV_WINOGRAD_Y): pack_conv_part_wy, then (hi, lo)."""
+    return split_bf16_image(pack_conv_part_wy(w, device))
+
+
+# ----------------------------------------------------------------------------- the RCAB's SE gate folded into conv.2 (savsr_rcab_gate_weights_batch)
+def tap_sums_border(r1: torch.Tensor) -> torch.Tensor:
+    """S [c][3 ky][3 kx] of a [c][h][w] map: its sum over the pixels tap (ky, kx) of a zero-padded 3x3 conv sees, in the border form the
+    kernel evaluates -- the channel's total, less the bottom (ky = 0) / top (ky = 2) row and the right (kx = 0) / left (kx = 2) column,
+    plus the corner both took away.  In r1's dtype (the tests run it in float64)."""
+    tot = r1.sum((1, 2))
+    rows = {0: r1[:, -1].sum(1), 2: r1[:, 0].sum(1)}                 # the row tap ky never sees
+    cols = {0: r1[:, :, -1].sum(1), 2: r1[:, :, 0].sum(1)}
+    crn = {(0, 0): r1[:, -1, -1], (0, 2): r1[:, -1, 0], (2, 0): r1[:, 0, -1], (2, 2): r1[:, 0, 0]}
+    s = tot[:, None, None].repeat(1, 3, 3)
+    for ky in range(3):
+        for kx in range(3):
+            if ky in rows:
+                s[:, ky, kx] -= rows[ky]
+            if kx in cols:
+                s[:, ky, kx] -= cols[kx]
+            if (ky, kx) in crn:
+                s[:, ky, kx] += crn[(ky, kx)]
+    return s
+
+
+def rcab_fold_tables(w: torch.Tensor, b: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The SE gate's first layer composed with conv.2 (w [c, c, 3, 3], b [c]; w1 [cmid, c], b1 [cmid]), in the `A` form: with S the
+    tap sums of conv.2's INPUT (tap_sums_border) and n = h w,  w1 mean(conv.2) + b1 = A S / n + cz,  A = w1 W.reshape(c, c 9) as
+    [cmid][c * 9] (column ci * 9 + 3 ky + kx), cz = w1 b + b1.  float64 products, rounded once to fp32."""
+    c = w.shape[0]
+    w1d = w1.detach().to("cpu", torch.float64).reshape(-1, c)
+    a = w1d @ w.detach().to("cpu", torch.float64).reshape(c, -1)
+    cz = w1d @ b.detach().to("cpu", torch.float64) + b1.detach().to("cpu", torch.float64)
+    return a.to(torch.float32).contiguous(), cz.to(torch.float32).contiguous()
 
 
 FP16_MAX = 65504.0      # largest finite fp16: the operand range of the precision mode "fp16"
@@ -502,6 +539,35 @@ class WeightPacking:
             out[name] = t
         return out
 
+    def _add_rcab_fold(self, sd, r: str):
+        """What savsr_rcab_gate_weights_batch reads for one RCAB (`rcab_w`): the fp32 master parts of conv `.2` in the element order of the
+        direct and -- where the Winograd-y image exists -- the Winograd-y image, its bias, and the gate's layers (rcab_fold_tables)."""
+        w, b = self._fold(sd, r + ".2", None)
+        w1, b1, w2, b2, cm = self.se[r]
+        a, cz = rcab_fold_tables(w, b, sd[r + ".3.attention.1.weight"], sd[r + ".3.attention.1.bias"])
+        wd = w.to(self.dev)
+        self.rcab_w[r] = dict(a=self._dev(a), cz=self._dev(cz), w2=w2, b2=b2, cm=cm, bias=self.pw[r + ".2"][1], master=self._dev(pack_conv_part(wd, self.dev)),
+                            master_wy=self._dev(pack_conv_part_wy(wd, self.dev)) if (r + ".2") in self.pw_wy else None)
+
+    def _rcab_scratch(self) -> dict:
+        """Per-engine scratch of the folded RCABs, reused by every RCAB of the stream (each conv.2 has read its image before the next gate
+        launch overwrites it: stream order): the generated image (the larger, Winograd-y, size where that form exists), g b and g, NB_MAX
+        copies each -- one per clip of a batched launch sequence, as _osc_scratch."""
+        c, nb = self.nf, self.NB_MAX
+        elems = conv_pack_index(c, c, 3)[1]
+        if c % 64 == 0:
+            elems = max(elems, conv_wy_pack_index(c, c)[1])
+        out = {}
+        for name, n, dt in (("wimg", 2 * elems, torch.int16), ("bias", c, torch.float32), ("gate", c, torch.float32)):
+            unit = 4 if dt == torch.float32 else 2
+            pitch = ((n * unit + 255) // 256) * 256 // unit          # copies stay 256-byte aligned
+            full = torch.empty(nb * pitch, device=self.dev, dtype=dt)
+            self._keep.append(full)
+            t = full[:n]
+            self._bstride[t.data_ptr()] = pitch * unit
+            out[name] = t
+        return out
+
     def _upload(self, host: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         return {k: self._dev(v, torch.int16 if v.dtype == torch.int16 else torch.float32) for k, v in host.items()}
 
@@ -577,6 +643,7 @@ class WeightPacking:
                 cm = sd[a + ".1.weight"].shape[0]
                 self.se[r] = (self._dev(sd[a + ".1.weight"].reshape(cm, -1)), self._dev(sd[a + ".1.bias"]),
                               self._dev(sd[a + ".3.weight"].reshape(-1, cm)), self._dev(sd[a + ".3.bias"]), cm)
+                self._add_rcab_fold(sd, r)
             self._add_conv(sd, f"RG.{g}.conv")
             m = f"adapt.{g}.mask"
             q = sd[m + ".0.weight"].shape[0]                                         # num_feat / 4 (:189-204)
@@ -596,3 +663,4 @@ class WeightPacking:
         self.gamma = float(sd["gamma"].reshape(-1)[0])
         self._pack_satu(sd)
         self.se_gate = torch.empty(self.nf, device=self.dev)
+        self.rcab_scr = self._rcab_scratch()
