@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 34
+#define SAVSR_ABI_VERSION 35
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -434,6 +434,23 @@ int savsr_tail_residual(const float* feat, int64_t feat_plane, const float* tail
 int savsr_video_gather_u8(const uint8_t* frames, int n_frames, int c, int h, int w, const int32_t* idx, int n_idx, float* out, void* stream);
 int savsr_video_gather_f32(const float* frames, int n_frames, int c, int h, int w, const int32_t* idx, int n_idx, float* out, void* stream);
 int savsr_video_quantize_u8(const float* in, int n, int c, int H, int W, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 35) Planar YUV 4:2:0 on either side of the sequence path (yuv.hip; SAVSR.upscale_video with pixel_format / out = "i420", the
+ * Y4M path of python -m savsr_amd.upscale).  An I420 frame of an h x w picture is h * w Y bytes, then ch * cw U
+ * (Cb) bytes, then ch * cw V (Cr) bytes, ch = (h + 1) / 2, cw = (w + 1) / 2; frames lie back to back.  Colour: ITU-R BT.601, limited
+ * range, the constants of rgb2ycbcr / ycbcr2rgb (lbasicsr/utils/color_util.py:5-35, 71-97).  Both are float32 with a fixed operation
+ * order and no fused multiply-add: savsr_amd/yuv.py restates them in numpy bit for bit.  Both only enqueue and allocate nothing;
+ * arguments are checked before the device is touched (SAVSR_E_ARG + savsr_last_error()).
+ * savsr_video_gather_i420:   frames [n_frames] I420 -> out [n_idx][3][h][w] fp32 planar RGB in [0, 1], slot k = frame idx[k] (the index
+ *                         list of savsr_video_gather_u8).  Chroma replicated over its 2 x 2 block; per sample a 256-entry table the
+ *                         compiler evaluates; R = y + rv, G = (y + gu) + gv, B = y + bu, clamped to [0, 1], not rounded to 8 bits.
+ *                         Dword loads / 16-byte stores when w % 4 == 0, frames 4-byte and out 16-byte aligned.
+ * savsr_video_quantize_i420: in [n][3][H][W] fp32 contiguous -> out [n] I420 frames: clamp(0, 1); Y per pixel; Cb / Cr from the mean RGB
+ *                         of the block's in-image pixels (1, 2 or 4); rintf (round half to even).  16-byte loads / dword stores when
+ *                         W % 4 == 0, in 16-byte and out 4-byte aligned. */
+int savsr_video_gather_i420(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, float* out, void* stream);
+int savsr_video_quantize_i420(const float* in, int n, int H, int W, uint8_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 33) Geometric self-ensemble (ensemble.hip; SAVSR.set_self_ensemble).  Variant k = 0 .. 7: fw = k & 1 flips

@@ -277,15 +277,20 @@ class SAVSR(nn.Module):
             return self.engine().forward_many(list(zip(clips, [tuple(s) if not isinstance(s, (int, float)) else (s, s) for s in scales])),
                                               ensemble=self.self_ensemble)
 
-    def upscale_video(self, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float") -> torch.Tensor:
+    def upscale_video(self, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
+                      size=None) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
         Returns [N, c, H, W] fp32, or with out="uint8" [N, H, W, c] uint8 = tensor2img(frame, rgb2bgr=False) of each fp32 frame.
+        pixel_format="i420", size=(h, w): frames are [N, i420_bytes(h, w)] uint8 (GPU or host), planar YUV 4:2:0 as in a Y4M file
+        (savsr_amd/yuv.py: BT.601 limited range, the reference's rgb2ycbcr / ycbcr2rgb), converted to fp32 RGB on the GPU without an
+        8-bit rounding; num_in_ch = 3.  out="i420", with either input format: [N, i420_bytes(H, W)] uint8, the fp32 frames converted and
+        rounded once, in YUV.
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
-        return upscale_video(self, frames, scale, padding, out)
+        return upscale_video(self, frames, scale, padding, out, pixel_format, size)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

@@ -1,0 +1,248 @@
+// Planar YUV 4:2:0 (I420) on either side of the network (ABI 35): I420 frames -> the fp32 planar RGB clip batch the engine stages, and
+// the fp32 result -> I420 frames for an encoder or a Y4M pipe.  The I420 counterparts of savsr_video_gather_u8 / _quantize_u8
+// (video.hip); like them not fused into the SATU / tail kernels (satu.hip, tail.hip and common.hpp stay as they are, and with them
+// savsr_source_hash_satu() and savsr_amd/hr_plans.json).
+//
+//   rgb2ycbcr / ycbcr2rgb   lbasicsr/utils/color_util.py:5-35, 71-97   ITU-R BT.601, limited range, Matlab's rounded constants
+//
+// savsr_amd/yuv.py restates both kernels in numpy and is what they are tested against, bit for bit: float32, a fixed operation order
+// and no fused multiply-add (contraction is off for this whole file).
+//
+// I420 frame of an h x w picture: h * w Y bytes, ch * cw U bytes, ch * cw V bytes, ch = (h + 1) / 2, cw = (w + 1) / 2.
+#include "common.hpp"
+
+#include <cstdint>
+
+#pragma clang fp contract(off)
+
+namespace savsr {
+namespace {
+
+// The one coefficient table of this file (yuv.py: BT601).  to-RGB entries per 8-bit step with the result in [0, 1], offsets in 8-bit
+// steps; to-YCbCr rows in 8-bit steps per unit of RGB.
+struct YuvMatrix {
+    double y, rv, gu, gv, bu, off_r, off_g, off_b;     // ycbcr2rgb
+    float ky[3], kcb[3], kcr[3], oy, oc;               // rgb2ycbcr
+};
+constexpr YuvMatrix kBt601 = {0.00456621, 0.00625893, -0.00153632, -0.00318811, 0.00791071, -222.921, 135.576, -276.836,
+                              {65.481f, 128.553f, 24.966f}, {-37.797f, -74.203f, 112.0f}, {112.0f, -93.786f, -18.214f}, 16.0f, 128.0f};
+
+// Per-sample terms of ycbcr2rgb (yuv.py: to_rgb_tables): the float64 product, plus the channel's offset / 255 where it is folded in,
+// rounded once to float32 -- a constant expression, so the compiler evaluates it in IEEE double exactly as numpy does.
+//   R = y + rv      G = (y + gu) + gv      B = y + bu
+enum { T_Y = 0, T_RV, T_GU, T_GV, T_BU, T_COUNT };
+struct YuvTables { float v[T_COUNT][256]; };
+constexpr YuvTables make_tables(const YuvMatrix& m) {
+    YuvTables t{};
+    for (int i = 0; i < 256; ++i) {
+        t.v[T_Y][i] = static_cast<float>(i * m.y);
+        t.v[T_RV][i] = static_cast<float>(i * m.rv + m.off_r / 255.0);
+        t.v[T_GU][i] = static_cast<float>(i * m.gu + m.off_g / 255.0);
+        t.v[T_GV][i] = static_cast<float>(i * m.gv);
+        t.v[T_BU][i] = static_cast<float>(i * m.bu + m.off_b / 255.0);
+    }
+    return t;
+}
+constexpr YuvTables kTablesValue = make_tables(kBt601);
+__constant__ YuvTables kYuvToRgb = kTablesValue;
+
+struct YuvIdx { int32_t f[SAVSR_VIDEO_MAX_SLOTS]; };     // slot -> frame, by value in the kernel arguments
+
+inline unsigned blocks_for(long long units) { return (unsigned)((units + 255) / 256); }
+
+__device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
+
+// One pixel of slot `o` (planes npx apart) from its three samples.
+__device__ __forceinline__ void put_rgb(const float (*lut)[256], uint32_t y, uint32_t u, uint32_t v, float& r, float& g, float& b) {
+    const float ty = lut[T_Y][y];
+    r = clamp01(ty + lut[T_RV][v]);
+    g = clamp01((ty + lut[T_GU][u]) + lut[T_GV][v]);
+    b = clamp01(ty + lut[T_BU][u]);
+}
+
+// I420 frames [N][fb] -> fp32 planar RGB slots [n][3][h][w], slot k = frame idx.f[k].  A thread owns a block of 2 rows so that a chroma
+// sample is read once.  VEC: 2 rows x 4 pixels -- a Y dword per row and 2 + 2 chroma bytes in, one float4 per plane row out (w % 4 == 0,
+// 4-byte aligned frames, 16-byte aligned out: then every Y row is dword aligned and every chroma row 2-byte aligned); otherwise 2 x 2
+// pixels with byte loads and scalar stores.
+template <bool VEC>
+__global__ __launch_bounds__(256) void gather_i420_kernel(const uint8_t* __restrict__ src, int h, int w, long long fb, YuvIdx idx,
+                                                          float* __restrict__ out) {
+    __shared__ float lut[T_COUNT][256];
+#pragma unroll
+    for (int t = 0; t < T_COUNT; ++t) lut[t][threadIdx.x] = kYuvToRgb.v[t][threadIdx.x];
+    __syncthreads();
+    const int k = blockIdx.y;
+    const long long npx = (long long)h * w;
+    const int ch = (h + 1) / 2, cw = (w + 1) / 2;
+    const uint8_t* fy = src + (long long)idx.f[k] * fb;
+    const uint8_t* fu = fy + npx;
+    const uint8_t* fv = fu + (long long)ch * cw;
+    float* o = out + (long long)k * 3 * npx;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const int wq = w / 4;                                   // 4-pixel groups per row
+        if (g >= (long long)ch * wq) return;
+        const int cy = (int)(g / wq), x0 = (int)(g % wq) * 4;
+        const long long coff = (long long)cy * cw + x0 / 2;
+        const uint32_t uu = *reinterpret_cast<const uint16_t*>(fu + coff);
+        const uint32_t vv = *reinterpret_cast<const uint16_t*>(fv + coff);
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            const int y = 2 * cy + dy;
+            if (y >= h) break;
+            const long long p = (long long)y * w + x0;
+            const uint32_t yy = *reinterpret_cast<const uint32_t*>(fy + p);
+            f32x4 r, gg, b;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float pr, pg, pb;
+                put_rgb(lut, (yy >> (8 * e)) & 255u, (uu >> (8 * (e >> 1))) & 255u, (vv >> (8 * (e >> 1))) & 255u, pr, pg, pb);
+                r[e] = pr; gg[e] = pg; b[e] = pb;
+            }
+            *reinterpret_cast<f32x4*>(o + p) = r;
+            *reinterpret_cast<f32x4*>(o + npx + p) = gg;
+            *reinterpret_cast<f32x4*>(o + 2 * npx + p) = b;
+        }
+    } else {
+        if (g >= (long long)ch * cw) return;
+        const int cy = (int)(g / cw), cx = (int)(g % cw);
+        const uint32_t u = fu[(long long)cy * cw + cx], v = fv[(long long)cy * cw + cx];
+        for (int dy = 0; dy < 2 && 2 * cy + dy < h; ++dy) {
+            for (int dx = 0; dx < 2 && 2 * cx + dx < w; ++dx) {
+                const long long p = (long long)(2 * cy + dy) * w + 2 * cx + dx;
+                float pr, pg, pb;
+                put_rgb(lut, fy[p], u, v, pr, pg, pb);
+                o[p] = pr; o[npx + p] = pg; o[2 * npx + p] = pb;
+            }
+        }
+    }
+}
+
+// rgb2ycbcr's rows in 8-bit steps: every product and every sum rounded to float32 (yuv.py: _row).  Plain operators under this file's
+// `fp contract(off)`: the header's __fmul_rn / __fadd_rn are compiled with contraction allowed and fuse again once inlined.
+__device__ __forceinline__ uint32_t row3_u8(float k0, float k1, float k2, float off, float r, float g, float b) {
+    return (uint32_t)rintf(((r * k0 + g * k1) + b * k2) + off);
+}
+__device__ __forceinline__ uint32_t luma_u8(float r, float g, float b) { return row3_u8(kBt601.ky[0], kBt601.ky[1], kBt601.ky[2], kBt601.oy, r, g, b); }
+__device__ __forceinline__ uint32_t cb_u8(float r, float g, float b) { return row3_u8(kBt601.kcb[0], kBt601.kcb[1], kBt601.kcb[2], kBt601.oc, r, g, b); }
+__device__ __forceinline__ uint32_t cr_u8(float r, float g, float b) { return row3_u8(kBt601.kcr[0], kBt601.kcr[1], kBt601.kcr[2], kBt601.oc, r, g, b); }
+
+// fp32 planar RGB [n][3][H][W] -> I420 frames [n][fb]: clamp(0, 1); Y per pixel; Cb / Cr from the mean RGB of the block's in-image
+// pixels -- ((a + b) + (c + d)) * 0.25 with a b the upper row, (a + b) * 0.5 for a pair, the pixel alone (yuv.py: _block_mean); rintf
+// (round half to even).  VEC: a thread owns 2 rows x 4 pixels -- one float4 per plane row in (nontemporal: the result is read once), a Y
+// dword per row and 2 + 2 chroma bytes out (W % 4 == 0, 16-byte aligned in, 4-byte aligned out); otherwise 2 x 2 pixels, scalar.
+template <bool VEC>
+__global__ __launch_bounds__(256) void quantize_i420_kernel(const float* __restrict__ in, int H, int W, long long fb, uint8_t* __restrict__ out) {
+    const int k = blockIdx.y;
+    const long long npx = (long long)H * W;
+    const int ch = (H + 1) / 2, cw = (W + 1) / 2;
+    const float* src = in + (long long)k * 3 * npx;
+    uint8_t* fy = out + (long long)k * fb;
+    uint8_t* fu = fy + npx;
+    uint8_t* fv = fu + (long long)ch * cw;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const int wq = W / 4;
+        if (g >= (long long)ch * wq) return;
+        const int cy = (int)(g / wq), x0 = (int)(g % wq) * 4;
+        const bool two = 2 * cy + 1 < H;
+        f32x4 px[2][3];
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            if (dy == 1 && !two) break;
+            const long long p = (long long)(2 * cy + dy) * W + x0;
+            uint32_t yy = 0u;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + c * npx + p));
+#pragma unroll
+                for (int e = 0; e < 4; ++e) px[dy][c][e] = clamp01(x[e]);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) yy |= luma_u8(px[dy][0][e], px[dy][1][e], px[dy][2][e]) << (8 * e);
+            *reinterpret_cast<uint32_t*>(fy + p) = yy;
+        }
+        uint32_t uu = 0u, vv = 0u;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float m[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float top = px[0][c][2 * j] + px[0][c][2 * j + 1];
+                m[c] = two ? (top + (px[1][c][2 * j] + px[1][c][2 * j + 1])) * 0.25f : top * 0.5f;
+            }
+            uu |= cb_u8(m[0], m[1], m[2]) << (8 * j);
+            vv |= cr_u8(m[0], m[1], m[2]) << (8 * j);
+        }
+        const long long coff = (long long)cy * cw + x0 / 2;
+        *reinterpret_cast<uint16_t*>(fu + coff) = (uint16_t)uu;
+        *reinterpret_cast<uint16_t*>(fv + coff) = (uint16_t)vv;
+    } else {
+        if (g >= (long long)ch * cw) return;
+        const int cy = (int)(g / cw), cx = (int)(g % cw);
+        const bool two_y = 2 * cy + 1 < H, two_x = 2 * cx + 1 < W;
+        float q[2][2][3];
+        for (int dy = 0; dy < 2; ++dy) {
+            for (int dx = 0; dx < 2; ++dx) {
+                if ((dy && !two_y) || (dx && !two_x)) continue;
+                const long long p = (long long)(2 * cy + dy) * W + 2 * cx + dx;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) q[dy][dx][c] = clamp01(src[c * npx + p]);
+                fy[p] = (uint8_t)luma_u8(q[dy][dx][0], q[dy][dx][1], q[dy][dx][2]);
+            }
+        }
+        float m[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (two_x && two_y) m[c] = ((q[0][0][c] + q[0][1][c]) + (q[1][0][c] + q[1][1][c])) * 0.25f;
+            else if (two_x) m[c] = (q[0][0][c] + q[0][1][c]) * 0.5f;
+            else if (two_y) m[c] = (q[0][0][c] + q[1][0][c]) * 0.5f;
+            else m[c] = q[0][0][c];
+        }
+        fu[(long long)cy * cw + cx] = (uint8_t)cb_u8(m[0], m[1], m[2]);
+        fv[(long long)cy * cw + cx] = (uint8_t)cr_u8(m[0], m[1], m[2]);
+    }
+}
+
+int load_idx(const int32_t* idx, int n, int n_frames, YuvIdx* gi, const char* what) {
+    if (!idx) { set_error("%s: null index list", what); return SAVSR_E_ARG; }
+    if (n < 1 || n > SAVSR_VIDEO_MAX_SLOTS) { set_error("%s: %d slots (1 .. %d)", what, n, SAVSR_VIDEO_MAX_SLOTS); return SAVSR_E_ARG; }
+    for (int i = 0; i < n; ++i) {
+        if (idx[i] < 0 || idx[i] >= n_frames) { set_error("%s: slot %d names frame %d of %d", what, i, idx[i], n_frames); return SAVSR_E_ARG; }
+        gi->f[i] = idx[i];
+    }
+    return 0;
+}
+
+inline long long i420_bytes(int h, int w) { return (long long)h * w + 2LL * ((h + 1) / 2) * ((w + 1) / 2); }
+
+}  // namespace
+}  // namespace savsr
+
+using namespace savsr;
+
+extern "C" int savsr_video_gather_i420(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, float* out, void* stream) {
+    if (!frames || !out) return fail_arg("video_gather_i420: null pointer");
+    if (h < 1 || w < 1 || n_frames < 1) return fail_arg("video_gather_i420: h, w, n_frames >= 1");
+    YuvIdx gi;
+    if (int rc = load_idx(idx, n_idx, n_frames, &gi, "video_gather_i420")) return rc;
+    const bool vec = w % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    const long long units = (long long)((h + 1) / 2) * (vec ? w / 4 : (w + 1) / 2);
+    const dim3 grid(blocks_for(units), n_idx);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (vec) hipLaunchKernelGGL((gather_i420_kernel<true>), grid, dim3(256), 0, st, frames, h, w, i420_bytes(h, w), gi, out);
+    else hipLaunchKernelGGL((gather_i420_kernel<false>), grid, dim3(256), 0, st, frames, h, w, i420_bytes(h, w), gi, out);
+    return check_launch("gather_i420_kernel");
+}
+
+extern "C" int savsr_video_quantize_i420(const float* in, int n, int H, int W, uint8_t* out, void* stream) {
+    if (!in || !out) return fail_arg("video_quantize_i420: null pointer");
+    if (n < 1 || n > 65535 || H < 1 || W < 1) return fail_arg("video_quantize_i420: n in 1 .. 65535, H, W >= 1");
+    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0;
+    const long long units = (long long)((H + 1) / 2) * (vec ? W / 4 : (W + 1) / 2);
+    const dim3 grid(blocks_for(units), n);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (vec) hipLaunchKernelGGL((quantize_i420_kernel<true>), grid, dim3(256), 0, st, in, H, W, i420_bytes(H, W), out);
+    else hipLaunchKernelGGL((quantize_i420_kernel<false>), grid, dim3(256), 0, st, in, H, W, i420_bytes(H, W), out);
+    return check_launch("quantize_i420_kernel");
+}

@@ -34,6 +34,7 @@ from .config import EngineConfig
 from .launch import MAX_SUM_BLOCKS, Launcher, Src, _ptr      # noqa: F401
 from .packing import (BN_EPS, CONV_TH, CONV_TW, WeightPacking, acc_row, conv_pack_geometry, conv_pack_index, conv_wy_pack_index, get_hw,      # noqa: F401  (re-exported:
                       pack_conv_part, pack_conv_weight, pack_conv_weight_wy, satu_axis_tables, split_bf16_image, window_record)                            # tests and tools import them from here)
+from .yuv import i420_bytes
 
 
 class HipEngine(WeightPacking, ContextCache, Launcher):
@@ -795,15 +796,28 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self._fan_out(units, sum(lq.shape[-2] * lq.shape[-1] for lq, _ in items) / max(1, len(items)), run)
         return outs
 
-    def forward_video(self, frames: torch.Tensor, windows: List[List[int]], scale, out_u8: bool = False, ensemble: bool = False) -> torch.Tensor:
+    def forward_video(self, frames: torch.Tensor, windows: List[List[int]], scale, out_u8: bool = False, ensemble: bool = False,
+                      i420: Optional[Tuple[int, int]] = None, out_i420: bool = False) -> torch.Tensor:
         """The sequence path (SAVSR.upscale_video): frames [N, h, w, c] uint8 or [N, c, h, w] fp32 on the device, windows[i] = the
         num_frame frame indices of output frame i in clip order (harness.window_indices) -> [len(windows), c, H, W] fp32, or
         [len(windows), H, W, c] uint8 (out_u8: tensor2img(x, rgb2bgr=False) per frame, savsr_video_quantize_u8).
         Launch units and streams are forward_many's (up to `clip_unit` consecutive windows per unit, balanced; units dealt round-robin over
         `streams_for` streams; throughput flow), so frame i equals forward_many on the gathered window i bit for bit.  A unit's windows are
         gathered from `frames` by savsr_video_gather_u8 / _f32 into a unit-sized fp32 clip batch on the unit's stream; nothing is gathered
-        or converted on the host.  ensemble=True: frame i is the self-ensemble of window i (`_ensemble`, gathered by savsr_ensemble_gather_*)."""
-        u8, N, c, h, w = _frames_layout(frames)
+        or converted on the host.  ensemble=True: frame i is the self-ensemble of window i (`_ensemble`, gathered by savsr_ensemble_gather_*).
+        i420=(h, w): frames are [N, i420_bytes(h, w)] uint8, planar YUV 4:2:0 (savsr_amd/yuv.py), gathered by savsr_video_gather_i420 where
+        the uint8 gather runs; out_i420: the result is [len(windows), i420_bytes(H, W)] uint8, quantised by savsr_video_quantize_i420 where
+        the uint8 quantisation runs.  With the ensemble, I420 frames are converted once to fp32 planar RGB (the same gather with the
+        identity list) and take the fp32 path, and an I420 result is the fp32 merge followed by the quantisation."""
+        if out_u8 and out_i420:
+            raise ValueError("one output kind: uint8 or I420")
+        if i420 is not None:
+            h, w = (int(v) for v in i420)
+            if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != i420_bytes(h, w):
+                raise ValueError(f"I420 frames of {h} x {w} are [N, {i420_bytes(h, w)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+            u8, N, c = True, int(frames.shape[0]), 3
+        else:
+            u8, N, c, h, w = _frames_layout(frames)
         frames = self._input(frames, torch.uint8 if u8 else torch.float32)
         T = self.cfg["num_frame"]
         if c != self.nch:
@@ -813,28 +827,55 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
                 raise ValueError(f"window {win}: {T} indices in [0, {N}) expected")
         H, W = get_hw(h, w, scale)
         n = len(windows)
-        out = (torch.empty(n, H, W, c, device=self.dev, dtype=torch.uint8) if out_u8 else
-               torch.empty(n, c, H, W, device=self.dev, dtype=torch.float32))
+        if out_i420:
+            out = torch.empty(n, i420_bytes(H, W), device=self.dev, dtype=torch.uint8)
+        else:
+            out = (torch.empty(n, H, W, c, device=self.dev, dtype=torch.uint8) if out_u8 else
+                   torch.empty(n, c, H, W, device=self.dev, dtype=torch.float32))
         if n == 0:
             return out
         if T > _lib.VIDEO_MAX_SLOTS:
             raise ValueError(f"num_frame = {T}: the window gather takes at most {_lib.VIDEO_MAX_SLOTS} frames per launch")
+        if i420 is not None:
+            def gather(idx, dst, st):
+                _lib.check(self.lib.savsr_video_gather_i420(frames.data_ptr(), N, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), dst.data_ptr(), st),
+                           "savsr_video_gather_i420")
+        else:
+            fn = self.lib.savsr_video_gather_u8 if u8 else self.lib.savsr_video_gather_f32
+
+            def gather(idx, dst, st):
+                _lib.check(fn(frames.data_ptr(), N, c, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), dst.data_ptr(), st), "savsr_video_gather")
+
+        def quantize(src, dst, st):
+            for a in range(0, int(src.shape[0]), 65535):          # (the entries take 1 .. 65535 frames)
+                nb = min(65535, int(src.shape[0]) - a)
+                if out_i420:
+                    _lib.check(self.lib.savsr_video_quantize_i420(src[a:a + nb].data_ptr(), nb, H, W, dst[a:a + nb].data_ptr(), st), "savsr_video_quantize_i420")
+                else:
+                    _lib.check(self.lib.savsr_video_quantize_u8(src[a:a + nb].data_ptr(), nb, c, H, W, dst[a:a + nb].data_ptr(), st), "savsr_video_quantize_u8")
         if ensemble:
-            self._ensemble([(frames, win, tuple(scale), out[i]) for i, win in enumerate(windows)], out_u8)
+            st = torch.cuda.current_stream().cuda_stream
+            if i420 is not None:
+                rgb = torch.empty(N, 3, h, w, device=self.dev, dtype=torch.float32)
+                for a in range(0, N, _lib.VIDEO_MAX_SLOTS):
+                    gather(list(range(a, min(N, a + _lib.VIDEO_MAX_SLOTS))), rgb[a:], st)
+                frames = rgb
+            merged = torch.empty(n, c, H, W, device=self.dev, dtype=torch.float32) if out_i420 else out
+            self._ensemble([(frames, win, tuple(scale), merged[i]) for i, win in enumerate(windows)], out_u8)
+            if out_i420:
+                quantize(merged, out, st)
             return out
-        gather = self.lib.savsr_video_gather_u8 if u8 else self.lib.savsr_video_gather_f32
 
         def run(eng: "HipEngine", unit: Tuple[int, int]):
             i0, i1 = unit
             nb = i1 - i0
             st = torch.cuda.current_stream().cuda_stream
-            idx = [f for win in windows[i0:i1] for f in win]
             lqb = torch.empty(nb, T, c, h, w, device=self.dev, dtype=torch.float32)
-            _lib.check(gather(frames.data_ptr(), N, c, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), lqb.data_ptr(), st), "savsr_video_gather")
-            o = torch.empty(nb, c, H, W, device=self.dev, dtype=torch.float32) if out_u8 else out[i0:i1]
+            gather([f for win in windows[i0:i1] for f in win], lqb, st)
+            o = torch.empty(nb, c, H, W, device=self.dev, dtype=torch.float32) if (out_u8 or out_i420) else out[i0:i1]
             eng._run_unit(lqb, scale, o)
-            if out_u8:
-                _lib.check(self.lib.savsr_video_quantize_u8(o.data_ptr(), nb, c, H, W, out[i0:i1].data_ptr(), st), "savsr_video_quantize_u8")
+            if out_u8 or out_i420:
+                quantize(o, out[i0:i1], st)
         # (SAVSR_GRAPHS=0: forward_many's eager flow, one window per unit)
         self._fan_out(video_units(n, T, self.clip_unit(h, w) if self.use_graphs else 1), h * w, run)
         return out

@@ -1,30 +1,48 @@
-"""Command-line upscaler: a folder of LR frames (PNG) in, a folder of SR frames (PNG, same file names) out.
+"""Command-line upscaler: LR frames in, SR frames out, as a folder of PNGs or as YUV4MPEG2 (.y4m) video on a file or a pipe.
 
     python -m savsr_amd.upscale -i <lr_frames/> -o <sr_frames/> --scale 4 --checkpoint <net.pth>
     python -m savsr_amd.upscale -i <lr_frames/> -o <sr_frames/> --scale 3.5 2.5 --padding reflection --opt <test.yml>
     python -m savsr_amd.upscale -i <lr_frames/> -o <sr_frames/> --scale 4 --checkpoint <net.pth> --self-ensemble
+    python -m savsr_amd.upscale -i in.y4m -o out.y4m --scale 4 --checkpoint <net.pth>
+    ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o - --scale 4 --checkpoint <net.pth> | ffmpeg -i - out.mp4
 
-Frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on the
-FrameStore pool (savsr_amd.io), pushed through VideoUpscaler in chunks (uint8 in, uint8 out: the windows, the network and the
-quantisation run on the GPU) and encoded on a writer pool of this tool's own (at most 16 threads).  It ends with one line: frames,
-seconds, frames/s.
+PNG folder: frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on
+the FrameStore pool (savsr_amd.io), pushed through VideoUpscaler in chunks (uint8 in, uint8 out: the windows, the network and the
+quantisation run on the GPU) and encoded on a writer pool of this tool's own (at most 16 threads).
+
+Y4M (a name ending in .y4m, or - for stdin / stdout; savsr_amd/y4m.py): planar YUV 4:2:0 bytes go to the GPU and come back as they are
+(pixel_format / out = "i420": colour conversion, chroma resampling and the one rounding happen there, savsr_amd/yuv.py).  On a pipe the
+video's length is not known, so a video too short for the window is refused when the input ends.  The SR frames are copied into pinned
+buffers and written by one ordered writer thread while the next chunk runs.  The two kinds mix: .y4m in, folder out writes %08d.png;
+folder in, .y4m out takes its frame rate from --fps.
+
+It ends with one line: frames, seconds, frames/s (on stderr when the video goes to stdout).
 """
 from __future__ import annotations
 
 import argparse
 import os
+import queue
 import sys
+import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional
 
 MAX_WRITERS = 16
+PINNED_BUFFERS = 3          # SR chunks in flight between the GPU and the Y4M writer thread
+
+
+def is_y4m(path: str) -> bool:
+    return path == "-" or path.lower().endswith(".y4m")
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="python -m savsr_amd.upscale", description="Upscale a folder of LR video frames (PNG) with SAVSR.")
-    p.add_argument("-i", "--input", required=True, help="folder of LR frames (PNG), taken in sorted order")
-    p.add_argument("-o", "--output", required=True, help="output folder (created); SR frames keep the input file names")
+    p = argparse.ArgumentParser(prog="python -m savsr_amd.upscale", description="Upscale LR video frames (a folder of PNGs, or YUV4MPEG2) with SAVSR.")
+    p.add_argument("-i", "--input", required=True, help="folder of LR frames (PNG), taken in sorted order; or a .y4m file; or - (Y4M on stdin)")
+    p.add_argument("-o", "--output", required=True,
+                   help="output folder (created; SR frames keep the input file names, %%08d.png for a Y4M input); or a .y4m file; or - (Y4M on stdout)")
+    p.add_argument("--fps", default=None, metavar="N[:D]", help="frame rate of a Y4M output made from a PNG folder (default 25:1)")
     p.add_argument("--scale", type=float, nargs="+", required=True, metavar="S", help="s, or sh sw")
     p.add_argument("--padding", default="reflection", choices=["replicate", "reflection", "reflection_circle", "circle"],
                    help="window padding at the ends of the video (generate_frame_indices); default reflection")
@@ -53,6 +71,14 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--chunk must be >= 1")
     if a.writers < 0 or a.writers > MAX_WRITERS:
         p.error(f"--writers must be in 0 .. {MAX_WRITERS}")
+    a.y4m_in, a.y4m_out = is_y4m(a.input), is_y4m(a.output)
+    if a.fps is not None and (a.y4m_in or not a.y4m_out):
+        p.error("--fps goes with a PNG folder in and Y4M out (a Y4M input carries its frame rate, PNGs have none)")
+    from .y4m import parse_fps
+    try:
+        a.fps = parse_fps(a.fps) if a.fps is not None else (25, 1)
+    except ValueError as e:
+        p.error(f"--fps: {e}")
     return a
 
 
@@ -86,53 +112,161 @@ def load_net(a: argparse.Namespace):
     return net.eval()
 
 
+class Y4MSink:
+    """SR frames [k, i420_bytes] on the GPU -> the Y4M writer: an asynchronous copy into one of PINNED_BUFFERS pinned host buffers on
+    the caller's stream, then one writer thread that waits for the copy's event and writes the frames in order.  emit() blocks only
+    when every buffer is still waiting to be written."""
+
+    def __init__(self, writer, capacity: int):
+        self.writer, self.capacity = writer, max(1, capacity)
+        self.todo: "queue.Queue" = queue.Queue()
+        self.free: "queue.Queue" = queue.Queue()
+        self.made = 0
+        self.error: Optional[BaseException] = None
+        self.thread = threading.Thread(target=self._loop, name="savsr-upscale-y4m", daemon=True)
+        self.thread.start()
+
+    def _buffer(self, k: int):
+        import torch
+        buf = None
+        if self.made < PINNED_BUFFERS:
+            self.made += 1
+        else:
+            buf = self.free.get()
+        if buf is None or buf.shape[0] < k:
+            buf = torch.empty(max(k, self.capacity), self.writer.frame_bytes, dtype=torch.uint8).pin_memory()
+        return buf
+
+    def emit(self, sr) -> int:
+        import torch
+        k = int(sr.shape[0])
+        if k:
+            buf = self._buffer(k)
+            buf[:k].copy_(sr, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            self.todo.put((buf, k, done))
+        return k
+
+    def _loop(self) -> None:
+        while True:
+            item = self.todo.get()
+            if item is None:
+                return
+            buf, k, done = item
+            try:
+                if self.error is None:
+                    done.synchronize()
+                    self.writer.write(buf[:k].numpy())
+            except BaseException as e:          # (kept for close(); the buffers keep circulating so that emit() never hangs)
+                self.error = e
+            self.free.put(buf)
+
+    def close(self) -> None:
+        self.todo.put(None)
+        self.thread.join()
+        if self.error is None:
+            self.writer.f.flush()
+        else:
+            raise self.error
+
+
+class PngSink:
+    """SR frames [k, H, W, 3] uint8 on the GPU -> PNG files, encoded on a pool of writer threads."""
+
+    def __init__(self, folder: str, names: Optional[List[str]], n_writers: int):
+        os.makedirs(folder, exist_ok=True)
+        self.folder, self.names, self.count = folder, names, 0
+        self.pool = ThreadPoolExecutor(max_workers=n_writers, thread_name_prefix="savsr-upscale-png")
+        self.pending: list = []
+
+    @staticmethod
+    def _save(img, path: str) -> None:
+        from PIL import Image
+        Image.fromarray(img).save(path)
+
+    def emit(self, sr) -> int:
+        host = sr.cpu().numpy()
+        for j in range(host.shape[0]):
+            name = self.names[self.count] if self.names is not None else f"{self.count:08d}.png"
+            self.pending.append(self.pool.submit(self._save, host[j], os.path.join(self.folder, name)))
+            self.count += 1
+        while len(self.pending) > 4 * MAX_WRITERS:          # bound the queue of encoded-but-unwritten frames
+            self.pending.pop(0).result()
+        return host.shape[0]
+
+    def close(self) -> None:
+        for f in self.pending:
+            f.result()
+        self.pool.shutdown()
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     a = parse_args(argv)
-    paths = list_frames(a.input)
+    paths = None if a.y4m_in else list_frames(a.input)
     import numpy as np
     import torch
-    from PIL import Image
 
-    from .io import FrameStore
+    from .packing import get_hw
     from .utils.host import effective_cpus
     from .video import VideoUpscaler, check_length
+    from .y4m import Y4MReader, Y4MWriter, scaled_aspect
 
     net = load_net(a)
     net.set_precision(a.precision)
     net.set_self_ensemble(a.self_ensemble)
-    check_length(len(paths), net.num_frame, a.padding)        # (before the GPU is touched)
-    dev = torch.device(a.device)
-    net = net.to(dev)
-    os.makedirs(a.output, exist_ok=True)
-    names = [os.path.basename(p) for p in paths]
-    store = FrameStore()
-    writers = ThreadPoolExecutor(max_workers=a.writers or max(1, min(MAX_WRITERS, effective_cpus())), thread_name_prefix="savsr-upscale-png")
-    pending = []
+    if paths is not None:
+        check_length(len(paths), net.num_frame, a.padding)        # (before the GPU is touched; a Y4M stream's length: at its end)
+    fin = fout = None
+    try:
+        if a.y4m_in:
+            if a.input != "-" and not os.path.isfile(a.input):
+                raise SystemExit(f"input file {a.input!r} does not exist")
+            fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
+            reader = Y4MReader(fin)
+            h, w = reader.height, reader.width
+            fps, interlace, aspect = reader.fps, reader.interlace, reader.aspect
+            chunks = (torch.from_numpy(c) for c in reader.chunks(a.chunk))
+        else:
+            from .io import FrameStore
+            store = FrameStore()
+            h = w = None
+            if a.y4m_out:                           # (the Y4M header needs the SR size before the first frame: the PNG's header gives it)
+                from PIL import Image
+                with Image.open(paths[0]) as im:
+                    w, h = im.size
+            fps, interlace, aspect = a.fps, "p", (0, 0)
 
-    def save(img: np.ndarray, path: str) -> None:
-        Image.fromarray(img).save(path)
-
-    def emit(sr: torch.Tensor, first: int) -> int:
-        host = sr.cpu().numpy()
-        for j in range(host.shape[0]):
-            pending.append(writers.submit(save, host[j], os.path.join(a.output, names[first + j])))
-        while len(pending) > 4 * MAX_WRITERS:          # bound the queue of encoded-but-unwritten frames
-            pending.pop(0).result()
-        return first + host.shape[0]
-
-    t0 = time.perf_counter()
-    up = VideoUpscaler(net, a.scale, a.padding, out="uint8")
-    store.request(paths)
-    done = 0
-    for c0 in range(0, len(paths), a.chunk):
-        chunk = np.stack([store.host(p) for p in paths[c0:c0 + a.chunk]], 0)
-        done = emit(up.push(torch.from_numpy(chunk)), done)
-    done = emit(up.finish(), done)
-    for f in pending:
-        f.result()
-    writers.shutdown()
-    dt = time.perf_counter() - t0
-    print(f"upscaled {done} frames in {dt:.2f} s: {done / dt:.2f} frames/s", flush=True)
+            def png_chunks():
+                store.request(paths)
+                for c0 in range(0, len(paths), a.chunk):
+                    yield torch.from_numpy(np.stack([store.host(p) for p in paths[c0:c0 + a.chunk]], 0))
+            chunks = png_chunks()
+        dev = torch.device(a.device)
+        net = net.to(dev)
+        if a.y4m_out:
+            H, W = get_hw(h, w, a.scale)
+            fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
+            sink = Y4MSink(Y4MWriter(fout, W, H, fps, interlace, scaled_aspect(aspect, (h, w), (H, W))), a.chunk + net.num_frame)
+        else:
+            sink = PngSink(a.output, None if paths is None else [os.path.basename(p) for p in paths],
+                           a.writers or max(1, min(MAX_WRITERS, effective_cpus())))
+        t0 = time.perf_counter()
+        up = VideoUpscaler(net, a.scale, a.padding, out="i420" if a.y4m_out else "uint8", pixel_format="i420" if a.y4m_in else "rgb",
+                           size=(h, w) if a.y4m_in else None)
+        done = 0
+        try:
+            for chunk in chunks:
+                done += sink.emit(up.push(chunk))
+            done += sink.emit(up.finish())
+        finally:
+            sink.close()
+        dt = time.perf_counter() - t0
+    finally:
+        for f, std in ((fin, sys.stdin.buffer), (fout, sys.stdout.buffer)):
+            if f is not None and f is not std:
+                f.close()
+    print(f"upscaled {done} frames in {dt:.2f} s: {done / dt:.2f} frames/s", file=sys.stderr if a.output == "-" else sys.stdout, flush=True)
     return 0
 
 

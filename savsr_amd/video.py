@@ -4,7 +4,8 @@ Output frame i is what the reference pipeline gives for it: the frame's window b
 (lbasicsr/data/data_util.py:63-112, `harness.window_indices`), then SAVSR.forward on that window; with out="uint8", tensor2img's
 clamp / x255 / round half to even (lbasicsr/utils/img_util.py:66-90) without the BGR swap.  The frames stay on the device: the
 windows are gathered there (savsr_video_gather_u8 / _f32) and the uint8 result is quantised there (savsr_video_quantize_u8), see
-HipEngine.forward_video.
+HipEngine.forward_video.  pixel_format="i420" / out="i420": planar YUV 4:2:0 frames in / out (savsr_amd/yuv.py is the format and its
+numerics), converted on the device on either side of the network (savsr_video_gather_i420 / savsr_video_quantize_i420).
 
 Every argument is checked here, on the host, before anything is enqueued on the GPU.
 """
@@ -15,9 +16,11 @@ from typing import List, Optional, Tuple
 import torch
 
 from .harness import window_indices
+from .yuv import i420_bytes
 
 PADDING_MODES = ("replicate", "reflection", "reflection_circle", "circle")
-OUT_KINDS = ("float", "uint8")
+OUT_KINDS = ("float", "uint8", "i420")
+PIXEL_FORMATS = ("rgb", "i420")
 
 
 def as_scale(scale) -> Tuple[float, float]:
@@ -71,6 +74,42 @@ def frame_layout(frames: torch.Tensor, nch: int) -> Tuple[int, int, int]:
     return int(n), int(h), int(w)
 
 
+def check_pixel_format(pixel_format: str, size) -> Optional[Tuple[int, int]]:
+    """(h, w) of I420 frames, None for RGB ones; refuses an unknown format, I420 without a size and a size without I420."""
+    if pixel_format not in PIXEL_FORMATS:
+        raise ValueError(f"pixel_format = {pixel_format!r}: one of {', '.join(PIXEL_FORMATS)}")
+    if pixel_format == "rgb":
+        if size is not None:
+            raise ValueError("size = (h, w) goes with pixel_format = 'i420'; RGB frames carry their size in their shape")
+        return None
+    try:
+        h, w = size
+        ok = int(h) == h and int(w) == w
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"pixel_format = 'i420' needs size = (h, w), got {size!r}")
+    if h < 2 or w < 2:
+        raise ValueError(f"SAVSR needs h, w >= 2, got {h} x {w}")
+    return int(h), int(w)
+
+
+def i420_layout(frames: torch.Tensor, size: Tuple[int, int], nch: int) -> int:
+    """N of an I420 video tensor: [N, i420_bytes(h, w)] uint8 (GPU or host); refuses anything else."""
+    h, w = size
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError(f"frames must be a torch.Tensor, got {type(frames).__name__}")
+    if nch != 3:
+        raise ValueError(f"I420 frames are colour frames, the network takes num_in_ch = {nch}")
+    if frames.dtype != torch.uint8:
+        raise ValueError(f"I420 frames must be uint8, got {frames.dtype}")
+    if frames.dim() != 2:
+        raise ValueError(f"I420 frames must be [N, i420_bytes(h, w)] uint8, got {frames.dim()} dimensions")
+    if int(frames.shape[1]) != i420_bytes(h, w):
+        raise ValueError(f"I420 frames of {h} x {w} have {i420_bytes(h, w)} bytes, got {int(frames.shape[1])}")
+    return int(frames.shape[0])
+
+
 def _to_device(frames: torch.Tensor, device: torch.device) -> torch.Tensor:
     if frames.device == device:
         return frames
@@ -85,14 +124,22 @@ def _check_net(net) -> None:
         raise RuntimeError("savsr_amd.SAVSR implements the inference path only; call .eval() first")
 
 
-def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float") -> torch.Tensor:
+def check_out(out: str, nch: int) -> None:
+    if out not in OUT_KINDS:
+        raise ValueError(f"out = {out!r}: one of {', '.join(OUT_KINDS)}")
+    if out == "i420" and nch != 3:
+        raise ValueError(f"out = 'i420' holds colour frames, the network gives num_in_ch = {nch}")
+
+
+def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
+                  size=None) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
-    if out not in OUT_KINDS:
-        raise ValueError(f"out = {out!r}: one of {', '.join(OUT_KINDS)}")
+    check_out(out, net.cfg["num_in_ch"])
+    i420 = check_pixel_format(pixel_format, size)
     sc = as_scale(net.scale if scale is None else scale)
-    n, _, _ = frame_layout(frames, net.cfg["num_in_ch"])
+    n = i420_layout(frames, i420, net.cfg["num_in_ch"]) if i420 else frame_layout(frames, net.cfg["num_in_ch"])[0]
     T = net.num_frame
     check_length(n, T, padding)
     dev = net.gamma.device
@@ -100,14 +147,16 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         raise RuntimeError("savsr_amd runs on an AMD GPU only: move the network to the GPU (net.cuda()) first")
     windows = [window_indices(i, n, T, padding) for i in range(n)]
     with torch.no_grad():
-        return net.engine().forward_video(_to_device(frames, dev), windows, sc, out == "uint8", ensemble=net.self_ensemble)
+        return net.engine().forward_video(_to_device(frames, dev), windows, sc, out == "uint8", ensemble=net.self_ensemble, i420=i420,
+                                          out_i420=out == "i420")
 
 
 class VideoUpscaler:
     """Streaming form of SAVSR.upscale_video for long videos and decoders:
 
         up = VideoUpscaler(net, scale=4, padding="reflection", out="uint8")
-        for chunk in decoder:                 # [k, h, w, c] uint8 (host or GPU) or [k, c, h, w] float on the GPU
+        for chunk in decoder:                 # [k, h, w, c] uint8 (host or GPU) or [k, c, h, w] float on the GPU;
+                                              # with pixel_format="i420", size=(h, w): [k, i420_bytes(h, w)] uint8
             emit(up.push(chunk))              # the SR frames whose windows are complete
         emit(up.finish())                     # the rest (with reflection the last num_frame // 2 need the end of the video)
 
@@ -116,11 +165,11 @@ class VideoUpscaler:
     window may still name -- at most num_frame - 1 (num_frame for the two circle modes, whose last windows reach num_frame - 1 frames
     back) -- plus the current chunk."""
 
-    def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float"):
+    def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb", size=None):
         _check_net(net)
         check_padding(padding)
-        if out not in OUT_KINDS:
-            raise ValueError(f"out = {out!r}: one of {', '.join(OUT_KINDS)}")
+        check_out(out, net.cfg["num_in_ch"])
+        self.i420 = check_pixel_format(pixel_format, size)        # (h, w) of I420 chunks, None for RGB ones
         self.net, self.padding, self.out = net, padding, out
         self.scale = as_scale(net.scale if scale is None else scale)
         self.ensemble = net.self_ensemble          # (read once, like the scale: every chunk runs the same flow)
@@ -152,14 +201,18 @@ class VideoUpscaler:
         n = n_total if n_total is not None else upto + self.half + 1
         windows = [[j - self._base for j in window_indices(i, n, self.T, self.padding)] for i in range(self.done, upto)]
         with torch.no_grad():
-            res = self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble)
+            res = self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble, i420=self.i420,
+                                                  out_i420=self.out == "i420")
         self.done = upto
         return res
 
     def push(self, frames: torch.Tensor) -> torch.Tensor:
         if self._finished:
             raise RuntimeError("push() after finish()")
-        k, h, w = frame_layout(frames, self.net.cfg["num_in_ch"])
+        if self.i420:
+            k, (h, w) = i420_layout(frames, self.i420, self.net.cfg["num_in_ch"]), self.i420
+        else:
+            k, h, w = frame_layout(frames, self.net.cfg["num_in_ch"])
         shape = (frames.dtype == torch.uint8, h, w)
         if self._shape is not None and shape != self._shape:
             raise ValueError(f"chunk of {'uint8' if shape[0] else 'float'} {h} x {w} frames after {'uint8' if self._shape[0] else 'float'} "
@@ -199,6 +252,8 @@ class VideoUpscaler:
         H, W = get_hw(h, w, self.scale)
         c = self.net.cfg["num_in_ch"]
         dev = self.net.gamma.device
+        if self.out == "i420":
+            return torch.empty(0, i420_bytes(H, W), dtype=torch.uint8, device=dev)
         if self.out == "uint8":
             return torch.empty(0, H, W, c, dtype=torch.uint8, device=dev)
         return torch.empty(0, c, H, W, dtype=torch.float32, device=dev)

@@ -1,0 +1,178 @@
+"""YUV4MPEG2 (.y4m) on any binary file object, non-seekable ones (pipes, stdin / stdout) included: the way to hand raw video to and
+from another program (ffmpeg -f yuv4mpegpipe, x264, a player) without a library.
+
+    YUV4MPEG2 W320 H180 F25:1 Ip A1:1 C420jpeg\\n          header: tags W H F I A C X, separated by single spaces
+    FRAME\\n<h * w Y bytes><ch * cw U bytes><ch * cw V bytes>   per frame (an I420 frame, savsr_amd/yuv.py); FRAME may carry parameters
+
+8-bit 4:2:0 only: C420, C420jpeg, C420mpeg2, C420paldv and a missing C tag (= 420) are read; every other tag is refused by name.  The
+three 420 tags differ in chroma siting only, which is accepted and ignored (yuv.py's nearest / box pair is centre-sited); the writer
+tags its output C420jpeg.
+"""
+from __future__ import annotations
+
+from fractions import Fraction
+from typing import Iterator, Optional, Tuple
+
+import numpy as np
+
+from .yuv import i420_bytes
+
+MAGIC = b"YUV4MPEG2"
+C420_TAGS = ("420", "420jpeg", "420mpeg2", "420paldv")
+MAX_LINE = 4096          # a header or FRAME line longer than this is not Y4M
+
+
+def _ratio(tag: str, val: str) -> Tuple[int, int]:
+    try:
+        a, b = val.split(":")
+        a, b = int(a), int(b)
+    except ValueError:
+        raise ValueError(f"y4m: bad header tag {tag}{val!r}: two integers a:b expected") from None
+    if a < 0 or b < 0:
+        raise ValueError(f"y4m: bad header tag {tag}{val!r}: two integers a:b expected")
+    return a, b
+
+
+def parse_fps(text: str) -> Tuple[int, int]:
+    """'N' or 'N:D' -> (N, D), both positive."""
+    try:
+        n, _, d = text.partition(":")
+        fps = (int(n), int(d) if d else 1)
+    except ValueError:
+        raise ValueError(f"frame rate {text!r}: N or N:D with positive integers expected") from None
+    if fps[0] < 1 or fps[1] < 1:
+        raise ValueError(f"frame rate {text!r}: N or N:D with positive integers expected")
+    return fps
+
+
+def scaled_aspect(aspect: Tuple[int, int], lr: Tuple[int, int], hr: Tuple[int, int]) -> Tuple[int, int]:
+    """Pixel aspect a:b of the SR video such that the display aspect of the LR video is kept under an asymmetric scale:
+    A' = Fraction(a * w * H, b * W * h), reduced, for LR (h, w) and HR (H, W).  0:0 (unknown) stays 0:0."""
+    a, b = aspect
+    if a == 0 or b == 0:
+        return 0, 0
+    (h, w), (H, W) = lr, hr
+    f = Fraction(a * w * H, b * W * h)
+    return f.numerator, f.denominator
+
+
+def _read_exact(f, n: int) -> bytes:
+    """Up to n bytes: fewer only at the end of the stream (a raw pipe returns what it has; keep reading)."""
+    parts, got = [], 0
+    while got < n:
+        b = f.read(n - got)
+        if not b:
+            break
+        parts.append(b)
+        got += len(b)
+    return parts[0] if len(parts) == 1 else b"".join(parts)
+
+
+def _read_line(f) -> bytes:
+    """One line including its newline, b"" at the end of the stream; byte by byte where the object has no readline."""
+    if hasattr(f, "readline"):
+        return f.readline(MAX_LINE)
+    out = bytearray()
+    while len(out) < MAX_LINE:
+        b = f.read(1)
+        if not b:
+            break
+        out += b
+        if b == b"\n":
+            break
+    return bytes(out)
+
+
+class Y4MReader:
+    """Reads the header on construction (width, height, fps, interlace, aspect, colorspace), then `chunks(k)` yields the frames as
+    uint8 arrays [m, i420_bytes(height, width)], m = k but for the last."""
+
+    def __init__(self, f):
+        self.f = f
+        line = _read_line(f)
+        if not line.startswith(MAGIC + b" ") or not line.endswith(b"\n"):
+            raise ValueError("y4m: not a YUV4MPEG2 stream (no 'YUV4MPEG2 ' header line)")
+        self.width: Optional[int] = None
+        self.height: Optional[int] = None
+        self.fps: Tuple[int, int] = (25, 1)
+        self.interlace = "p"
+        self.aspect: Tuple[int, int] = (0, 0)
+        self.colorspace = "420"
+        for tag in line[len(MAGIC):].decode("ascii", errors="replace").split():
+            key, val = tag[0], tag[1:]
+            if key in "WH":
+                try:
+                    size = int(val)
+                except ValueError:
+                    size = 0
+                if size < 1:
+                    raise ValueError(f"y4m: bad header tag {tag!r}: a positive integer expected")
+                if key == "W":
+                    self.width = size
+                else:
+                    self.height = size
+            elif key == "F":
+                self.fps = _ratio("F", val)
+            elif key == "I":
+                self.interlace = val
+            elif key == "A":
+                self.aspect = _ratio("A", val)
+            elif key == "C":
+                if val not in C420_TAGS:
+                    raise ValueError(f"y4m: colour space tag 'C{val}' is not supported: 8-bit 4:2:0 only ({', '.join('C' + t for t in C420_TAGS)})")
+                self.colorspace = val
+            elif key == "X":
+                pass                                  # comments / extensions (XYSCSS=..., XCOLORRANGE=...): ignored
+            else:
+                raise ValueError(f"y4m: unknown header tag {tag!r}")
+        if self.width is None or self.height is None:
+            raise ValueError("y4m: the header names no W / H")
+        self.frame_bytes = i420_bytes(self.height, self.width)
+        self.frames_read = 0
+
+    def _frame_into(self, row: np.ndarray) -> bool:
+        line = _read_line(self.f)
+        if not line:
+            return False
+        i = self.frames_read
+        if not (line.startswith(b"FRAME") and line.endswith(b"\n") and line[5:6] in (b" ", b"\n")):
+            raise ValueError(f"y4m: frame {i}: 'FRAME' line expected, got {line[:16]!r}")
+        data = _read_exact(self.f, self.frame_bytes)
+        if len(data) != self.frame_bytes:
+            raise ValueError(f"y4m: frame {i} is truncated: {len(data)} of {self.frame_bytes} bytes")
+        row[:] = np.frombuffer(data, np.uint8)
+        self.frames_read += 1
+        return True
+
+    def chunks(self, k: int) -> Iterator[np.ndarray]:
+        if k < 1:
+            raise ValueError("chunks of k >= 1 frames")
+        while True:
+            buf = np.empty((k, self.frame_bytes), np.uint8)
+            m = 0
+            while m < k and self._frame_into(buf[m]):
+                m += 1
+            if m:
+                yield buf[:m]
+            if m < k:
+                return
+
+
+class Y4MWriter:
+    """Writes the header on construction, then `write(frames)` appends uint8 frames [m, i420_bytes(height, width)]."""
+
+    def __init__(self, f, width: int, height: int, fps: Tuple[int, int] = (25, 1), interlace: str = "p", aspect: Tuple[int, int] = (0, 0)):
+        if width < 1 or height < 1:
+            raise ValueError(f"y4m: W, H >= 1, got {width} x {height}")
+        self.f, self.width, self.height = f, int(width), int(height)
+        self.frame_bytes = i420_bytes(self.height, self.width)
+        self.header = f"YUV4MPEG2 W{self.width} H{self.height} F{fps[0]}:{fps[1]} I{interlace} A{aspect[0]}:{aspect[1]} C420jpeg\n".encode("ascii")
+        f.write(self.header)
+
+    def write(self, frames: np.ndarray) -> None:
+        frames = np.ascontiguousarray(frames)
+        if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != self.frame_bytes:
+            raise ValueError(f"y4m: frames of {self.height} x {self.width} are [m, {self.frame_bytes}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+        for row in frames:
+            self.f.write(b"FRAME\n")
+            self.f.write(memoryview(row))

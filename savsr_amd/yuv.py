@@ -1,0 +1,132 @@
+"""Planar YUV 4:2:0 (I420) <-> RGB, the host restatement that specifies savsr_video_gather_i420 / savsr_video_quantize_i420 (yuv.hip).
+
+The colour matrix is the reference's (lbasicsr/utils/color_util.py, `rgb2ycbcr` / `ycbcr2rgb`: ITU-R BT.601, limited range, Matlab's
+rounded constants), the same whose Y row metrics.py uses for PSNR-Y.  8-bit 4:2:0 only; `BT601` is the one coefficient table here
+(`kBt601` is its twin in yuv.hip), so another matrix or range is another table.
+
+I420 frame of an h x w picture: h * w Y bytes, then ch * cw U (Cb) bytes, then ch * cw V (Cr) bytes, ch = (h + 1) // 2,
+cw = (w + 1) // 2 -- the frame as it lies in a Y4M file.  A video is a uint8 array [N, i420_bytes(h, w)].
+
+Both directions are float32 with a fixed operation order and no fused multiply-add, so that numpy and the kernels agree bit for bit:
+
+  i420_to_rgb   per-sample tables (a float64 product, plus the channel's offset where it is folded in, rounded once to float32: what
+                a C++ constant expression gives), summed in float32 in a fixed order, clamped to [0, 1]; chroma replicated over its
+                2 x 2 block.  Not rounded to 8 bits.
+  rgb_to_i420   RGB clamped to [0, 1]; Y per pixel; Cb / Cr from the mean RGB of the block's in-image pixels (1, 2 or 4: the
+                divisor is a power of two); every product and every sum rounded to float32; round half to even (tensor2img's rule).
+"""
+from __future__ import annotations
+
+from typing import Tuple
+
+import numpy as np
+
+# BT.601 limited range, the reference's constants.  to_rgb: ycbcr2rgb's matrix entries (per 8-bit step, result in [0, 1]) and its
+# offsets (in 8-bit steps, / 255 -> [0, 1]).  to_ycbcr: rgb2ycbcr's rows (8-bit steps per unit of RGB in [0, 1]) and offsets.
+BT601 = {
+    "to_rgb": {"y": 0.00456621, "rv": 0.00625893, "gu": -0.00153632, "gv": -0.00318811, "bu": 0.00791071,
+               "offset": (-222.921, 135.576, -276.836)},
+    "to_ycbcr": {"y": (65.481, 128.553, 24.966), "cb": (-37.797, -74.203, 112.0), "cr": (112.0, -93.786, -18.214),
+                 "offset": (16.0, 128.0, 128.0)},
+}
+
+
+def chroma_hw(h: int, w: int) -> Tuple[int, int]:
+    return (h + 1) // 2, (w + 1) // 2
+
+
+def i420_bytes(h: int, w: int) -> int:
+    ch, cw = chroma_hw(h, w)
+    return h * w + 2 * ch * cw
+
+
+def _check_size(h: int, w: int) -> None:
+    if int(h) != h or int(w) != w or h < 1 or w < 1:
+        raise ValueError(f"size must be (h, w) with h, w >= 1, got ({h!r}, {w!r})")
+
+
+def split_planes(frames: np.ndarray, h: int, w: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """[N, i420_bytes(h, w)] uint8 -> views Y [N, h, w], U [N, ch, cw], V [N, ch, cw]."""
+    _check_size(h, w)
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != i420_bytes(h, w):
+        raise ValueError(f"I420 frames of {h} x {w} are [N, {i420_bytes(h, w)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+    ch, cw = chroma_hw(h, w)
+    n = frames.shape[0]
+    y = frames[:, :h * w].reshape(n, h, w)
+    u = frames[:, h * w:h * w + ch * cw].reshape(n, ch, cw)
+    v = frames[:, h * w + ch * cw:].reshape(n, ch, cw)
+    return y, u, v
+
+
+def to_rgb_tables(m: dict = BT601) -> dict:
+    """The five per-sample float32 tables of i420_to_rgb: "y" (no offset) and the four chroma terms, each with its channel's offset
+    folded in (R's in "rv", G's in "gu", B's in "bu").  float64 product and sum, one rounding to float32."""
+    t = m["to_rgb"]
+    s = np.arange(256, dtype=np.float64)
+    o = [v / 255.0 for v in t["offset"]]
+    return {"y": (s * t["y"]).astype(np.float32),
+            "rv": (s * t["rv"] + o[0]).astype(np.float32),
+            "gu": (s * t["gu"] + o[1]).astype(np.float32),
+            "gv": (s * t["gv"]).astype(np.float32),
+            "bu": (s * t["bu"] + o[2]).astype(np.float32)}
+
+
+def i420_to_rgb(frames_u8: np.ndarray, h: int, w: int) -> np.ndarray:
+    """[N, i420_bytes(h, w)] uint8 -> float32 [N, 3, h, w] in [0, 1]:  R = y + rv,  G = (y + gu) + gv,  B = y + bu  on the table values."""
+    y, u, v = split_planes(frames_u8, h, w)
+    t = to_rgb_tables()
+    u = np.repeat(np.repeat(u, 2, axis=1), 2, axis=2)[:, :h, :w]
+    v = np.repeat(np.repeat(v, 2, axis=1), 2, axis=2)[:, :h, :w]
+    ty = t["y"][y]
+    r = ty + t["rv"][v]
+    g = (ty + t["gu"][u]) + t["gv"][v]
+    b = ty + t["bu"][u]
+    out = np.stack([r, g, b], 1)
+    return np.fmin(np.fmax(out, np.float32(0.0)), np.float32(1.0)).astype(np.float32)
+
+
+def _clamp01(x: np.ndarray) -> np.ndarray:
+    x = np.asarray(x)
+    if x.dtype != np.float32 or x.ndim != 4 or x.shape[1] != 3:
+        raise ValueError(f"RGB frames are [N, 3, H, W] float32, got {x.dtype} {tuple(x.shape)}")
+    return np.fmin(np.fmax(x, np.float32(0.0)), np.float32(1.0))      # (fmaxf / fminf: a NaN becomes 0)
+
+
+def _row(p: np.ndarray, coef, offset: float) -> np.ndarray:
+    """((r * a + g * b) + b * c) + offset in float32, every product and sum rounded."""
+    a, b, c = (np.float32(v) for v in coef)
+    return ((p[:, 0] * a + p[:, 1] * b) + p[:, 2] * c) + np.float32(offset)
+
+
+def _block_mean(p: np.ndarray) -> np.ndarray:
+    """Mean of every 2 x 2 block's in-image pixels, [N, 3, H, W] -> [N, 3, ch, cw]:  ((a + b) + (c + d)) * 0.25 with a b the block's
+    upper row and c d its lower; (a + b) * 0.5 for a pair (the last row of an odd H, the last column of an odd W); the pixel alone."""
+    n, c, H, W = p.shape
+    ch, cw = chroma_hw(H, W)
+    he, we = H // 2 * 2, W // 2 * 2
+    m = np.empty((n, c, ch, cw), np.float32)
+    m[:, :, :H // 2, :W // 2] = ((p[:, :, 0:he:2, 0:we:2] + p[:, :, 0:he:2, 1:we:2]) +
+                                 (p[:, :, 1:he:2, 0:we:2] + p[:, :, 1:he:2, 1:we:2])) * np.float32(0.25)
+    if W % 2:
+        m[:, :, :H // 2, -1] = (p[:, :, 0:he:2, W - 1] + p[:, :, 1:he:2, W - 1]) * np.float32(0.5)
+    if H % 2:
+        m[:, :, -1, :W // 2] = (p[:, :, H - 1, 0:we:2] + p[:, :, H - 1, 1:we:2]) * np.float32(0.5)
+    if W % 2 and H % 2:
+        m[:, :, -1, -1] = p[:, :, H - 1, W - 1]
+    return m
+
+
+def ycbcr_f32(x: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The float32 values rgb_to_i420 rounds: Y [N, H, W], Cb and Cr [N, ch, cw], in 8-bit steps."""
+    p = _clamp01(x)
+    t = BT601["to_ycbcr"]
+    m = _block_mean(p)
+    return _row(p, t["y"], t["offset"][0]), _row(m, t["cb"], t["offset"][1]), _row(m, t["cr"], t["offset"][2])
+
+
+def rgb_to_i420(x_f32: np.ndarray) -> np.ndarray:
+    """float32 [N, 3, H, W] -> uint8 [N, i420_bytes(H, W)].  After the clamp Y lies in 16 .. 235 and chroma in 16 .. 240: no clip."""
+    y, cb, cr = ycbcr_f32(x_f32)
+    n = y.shape[0]
+    return np.concatenate([np.rint(v).astype(np.uint8).reshape(n, -1) for v in (y, cb, cr)], 1)

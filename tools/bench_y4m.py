@@ -1,0 +1,229 @@
+"""Raw YUV 4:2:0 in and out, measured.  Every leg is a process of its own under its own time limit; a leg that
+fails, times out or dies ends the run (nothing more is started on the GPU) and what the earlier legs gave is kept.
+
+  kernels   savsr_video_gather_i420 / _quantize_i420 beside savsr_video_gather_u8 / _quantize_u8 of the same build, in one process,
+            interleaved rounds, at 180x320 and 720x1280: us, the fraction of 8 TB/s on 4*3*h*w + 1.5*h*w bytes, and the ratio to the RGB
+            kernel's time (they move the same fp32 bytes and half the uint8 bytes; 1.2x is allowed for the two-row coupling)
+  ceiling   upscale_video on preloaded I420 frames, I420 out (frames/s): what the CLI could reach
+  cli       python -m savsr_amd.upscale on one synthetic video, PNG folder -> PNG folder against .y4m -> .y4m, A/B/A/B; files under
+            --workdir (name the disk it lies on beside the figures: tmpfs or a scratch disk)
+  psnr      PSNR-Y of (I420 -> device path -> I420) and of (I420 -> host 8-bit RGB -> the uint8 RGB path -> host 8-bit YUV), each
+            against the float result of the I420 input converted in float64.  Synthetic weights: the ranking of the two paths is what
+            the figure shows, not a quality claim.
+
+    python3 tools/bench_y4m.py --out profiles/bench_y4m.json [--workdir /dev/shm]
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_BYTES_PER_S = 8e12
+LEG_TIMEOUT_S = {"kernels": 240, "ceiling": 420, "cli": 420, "psnr": 420}
+
+
+def _net(dev):
+    from savsr_amd.archs.savsr_arch import SAVSR
+    from savsr_amd.utils import synth
+    net = SAVSR()
+    net.load_state_dict(synth.synth_state_dict(synth.manifest_of(net.state_dict()), seed=0), strict=True)
+    return net.to(dev).eval()
+
+
+def _video_i420(n, h, w):
+    """A smooth seeded video in I420 (random bytes are the worst case of no codec; PNG encoding time depends on the content)."""
+    import numpy as np
+    from savsr_amd import yuv
+    from savsr_amd.utils import synth
+    clip = synth.synth_clip(n, 3, h, w, seed=3)[0].numpy().astype(np.float32)
+    return yuv.rgb_to_i420(clip)
+
+
+def leg_kernels(a):
+    import ctypes as C
+    import torch
+    from savsr_amd import _lib
+    from savsr_amd.yuv import i420_bytes
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    rows = []
+    for h, w in ((180, 320), (720, 1280)):
+        n, idx = 16, list(range(7))
+        arr = (C.c_int32 * 7)(*idx)
+        rgb8 = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, device=dev)
+        i420 = torch.randint(0, 256, (n, i420_bytes(h, w)), dtype=torch.uint8, device=dev)
+        slots = torch.empty(7, 3, h, w, device=dev)
+        x = torch.rand(7, 3, h, w, device=dev)
+        q8 = torch.empty(7, h, w, 3, dtype=torch.uint8, device=dev)
+        q420 = torch.empty(7, i420_bytes(h, w), dtype=torch.uint8, device=dev)
+        fns = {
+            "savsr_video_gather_u8": lambda: lib.savsr_video_gather_u8(rgb8.data_ptr(), n, 3, h, w, arr, 7, slots.data_ptr(), st),
+            "savsr_video_gather_i420": lambda: lib.savsr_video_gather_i420(i420.data_ptr(), n, h, w, arr, 7, slots.data_ptr(), st),
+            "savsr_video_quantize_u8": lambda: lib.savsr_video_quantize_u8(x.data_ptr(), 7, 3, h, w, q8.data_ptr(), st),
+            "savsr_video_quantize_i420": lambda: lib.savsr_video_quantize_i420(x.data_ptr(), 7, h, w, q420.data_ptr(), st),
+        }
+        us = {k: [] for k in fns}
+        for k, fn in fns.items():
+            assert fn() == 0, k
+        torch.cuda.synchronize()
+        for _ in range(a.rounds):                       # interleaved rounds: every kernel sees the same clocks
+            for k, fn in fns.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.iters):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                us[k].append(1e3 * e0.elapsed_time(e1) / a.iters)
+        med = {k: statistics.median(v) for k, v in us.items()}
+        for k in fns:
+            byte_side = 1.5 if k.endswith("i420") else 3.0
+            nbytes = 7 * (4 * 3 + byte_side) * h * w
+            row = {"kernel": k, "size": [h, w], "frames": 7, "us": round(med[k], 2), "us_per_frame": round(med[k] / 7, 3),
+                   "mb": round(nbytes / 1e6, 2), "hbm_frac": round(nbytes / (med[k] * 1e-6) / HBM_BYTES_PER_S, 3)}
+            if k.endswith("i420"):
+                row["vs_rgb_kernel"] = round(med[k] / med[k.replace("i420", "u8")], 3)
+            rows.append(row)
+    return {"kernels": rows, "rounds": a.rounds, "iters": a.iters, "timing": "HIP events around `iters` back-to-back launches (launch rate included)"}
+
+
+def leg_ceiling(a):
+    import torch
+    dev = torch.device("cuda:0")
+    net = _net(dev)
+    sc = (a.scale, a.scale)
+    frames = torch.from_numpy(_video_i420(a.frames, a.h, a.w)).to(dev)
+    ts = []
+    with torch.no_grad():
+        net.upscale_video(frames, scale=sc, out="i420", pixel_format="i420", size=(a.h, a.w))
+        torch.cuda.synchronize()
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            r = net.upscale_video(frames, scale=sc, out="i420", pixel_format="i420", size=(a.h, a.w))
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+            del r
+    return {"ceiling_fps": round(a.frames / statistics.median(ts), 2), "ceiling_fps_all": [round(a.frames / t, 2) for t in ts]}
+
+
+def leg_cli(a):
+    """No GPU in this process: it prepares the files and runs the CLI, one child at a time."""
+    import numpy as np
+    from PIL import Image
+    from savsr_amd import io as sio, y4m, yuv
+    from savsr_amd.archs.savsr_arch import SAVSR
+    from savsr_amd.utils import synth
+    net = SAVSR()
+    net.load_state_dict(synth.synth_state_dict(synth.manifest_of(net.state_dict()), seed=0), strict=True)
+    frames = _video_i420(a.frames, a.h, a.w)
+    rgb8 = np.rint(yuv.i420_to_rgb(frames, a.h, a.w) * np.float32(255.0)).astype(np.uint8).transpose(0, 2, 3, 1)
+    res = {"png_fps": [], "y4m_fps": [], "workdir": a.workdir or tempfile.gettempdir()}
+    with tempfile.TemporaryDirectory(dir=a.workdir) as td:
+        src_png, src_y4m, ckpt = os.path.join(td, "lr"), os.path.join(td, "lr.y4m"), os.path.join(td, "net.pth")
+        os.makedirs(src_png)
+        for i in range(a.frames):
+            Image.fromarray(np.ascontiguousarray(rgb8[i])).save(os.path.join(src_png, f"{i:08d}.png"))
+        with open(src_y4m, "wb") as f:
+            y4m.Y4MWriter(f, a.w, a.h, (25, 1), "p", (1, 1)).write(frames)
+        sio.save_network(net, ckpt)
+        for rep in range(a.reps):
+            for kind, src, dst in (("png", src_png, os.path.join(td, f"sr{rep}")), ("y4m", src_y4m, os.path.join(td, f"sr{rep}.y4m"))):
+                r = subprocess.run([sys.executable, "-m", "savsr_amd.upscale", "-i", src, "-o", dst, "--scale", str(a.scale), "--checkpoint", ckpt],
+                                   cwd=ROOT, capture_output=True, text=True, timeout=180)
+                if r.returncode != 0:
+                    raise SystemExit(f"CLI {kind} failed ({r.returncode}): {r.stderr[-2000:]}")
+                res[f"{kind}_fps"].append(float(r.stdout.strip().splitlines()[-1].split(":")[-1].split()[0]))
+    res["png_fps_median"], res["y4m_fps_median"] = statistics.median(res["png_fps"]), statistics.median(res["y4m_fps"])
+    res["y4m_vs_png"] = round(res["y4m_fps_median"] / res["png_fps_median"], 3)
+    return {"cli": res}
+
+
+def leg_psnr(a):
+    import numpy as np
+    import torch
+    from savsr_amd import yuv
+    dev = torch.device("cuda:0")
+    net = _net(dev)
+    sc = (a.scale, a.scale)
+    n = min(a.frames, 16)
+    frames = _video_i420(n, a.h, a.w)
+    m, t = yuv.BT601["to_rgb"], yuv.BT601["to_ycbcr"]
+    y, u, v = (p.astype(np.float64) for p in yuv.split_planes(frames, a.h, a.w))
+    u, v = (np.repeat(np.repeat(p, 2, 1), 2, 2)[:, :a.h, :a.w] for p in (u, v))
+    exact = np.clip(np.stack([y * m["y"] + v * m["rv"] + m["offset"][0] / 255, y * m["y"] + u * m["gu"] + v * m["gv"] + m["offset"][1] / 255,
+                              y * m["y"] + u * m["bu"] + m["offset"][2] / 255], 1), 0, 1)                    # float64 RGB of the samples
+    with torch.no_grad():
+        ref = net.upscale_video(torch.from_numpy(exact.astype(np.float32)).to(dev), scale=sc).cpu().numpy().astype(np.float64)
+        dev_path = net.upscale_video(torch.from_numpy(frames), scale=sc, out="i420", pixel_format="i420", size=(a.h, a.w)).cpu().numpy()
+        rgb8 = np.rint(yuv.i420_to_rgb(frames, a.h, a.w) * np.float32(255.0)).astype(np.uint8).transpose(0, 2, 3, 1)
+        sr8 = net.upscale_video(torch.from_numpy(np.ascontiguousarray(rgb8)), scale=sc, out="uint8").cpu().numpy()
+    host_path = yuv.rgb_to_i420(np.ascontiguousarray(sr8.transpose(0, 3, 1, 2)).astype(np.float32) / np.float32(255.0))
+    H, W = ref.shape[2:]
+    ref_y = np.tensordot(np.clip(ref, 0, 1), np.array(t["y"]), axes=([1], [0])) + t["offset"][0]          # float64 Y, not rounded
+
+    def psnr_y(i420):
+        yy = yuv.split_planes(i420, H, W)[0].astype(np.float64)
+        return round(float(10 * np.log10(255.0 ** 2 / np.mean((yy - ref_y) ** 2))), 3)
+    return {"psnr_y": {"device_path_db": psnr_y(dev_path), "host_8bit_rgb_path_db": psnr_y(host_path), "frames": n,
+                       "note": "against the float result in float64; synthetic weights"}}
+
+
+LEGS = {"kernels": leg_kernels, "ceiling": leg_ceiling, "cli": leg_cli, "psnr": leg_psnr}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=100)
+    ap.add_argument("--h", type=int, default=180)
+    ap.add_argument("--w", type=int, default=320)
+    ap.add_argument("--scale", type=float, default=4.0)
+    ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--workdir", default=None, help="where the CLI legs keep their files (default: the temporary directory)")
+    ap.add_argument("--legs", default="kernels,ceiling,cli,psnr")
+    ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)          # (a child process: run one leg, print its JSON)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.leg:
+        print(json.dumps(LEGS[a.leg](a)), flush=True)
+        return 0
+    res = {"workload": f"{a.frames} frames {a.h}x{a.w} x{a.scale:g}", "legs": {}}
+    rc = 0
+    for leg in a.legs.split(","):
+        cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg] + [x for k in ("frames", "h", "w", "scale", "reps", "rounds", "iters")
+                                                                          for x in (f"--{k}", str(getattr(a, k)))]
+        if a.workdir:
+            cmd += ["--workdir", a.workdir]
+        try:
+            r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=LEG_TIMEOUT_S[leg])
+        except subprocess.TimeoutExpired:
+            res["legs"][leg] = {"error": f"time limit of {LEG_TIMEOUT_S[leg]} s"}
+            rc = 1
+            break
+        if r.returncode != 0:
+            res["legs"][leg] = {"error": f"exit {r.returncode}", "stderr": r.stderr[-1500:]}
+            rc = 1
+            break                                   # nothing more is started after a leg that failed
+        res["legs"][leg] = json.loads(r.stdout.strip().splitlines()[-1])
+        print(leg, json.dumps(res["legs"][leg]), flush=True)
+    if "ceiling" in res["legs"] and "cli" in res["legs"] and "error" not in res["legs"]["cli"] and "error" not in res["legs"]["ceiling"]:
+        res["y4m_cli_vs_ceiling"] = round(res["legs"]["cli"]["cli"]["y4m_fps_median"] / res["legs"]["ceiling"]["ceiling_fps"], 3)
+    print(json.dumps(res), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    return rc
+
+
+if __name__ == "__main__":
+    sys.exit(main())
