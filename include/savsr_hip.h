@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 35
+#define SAVSR_ABI_VERSION 36
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -451,6 +451,22 @@ int savsr_video_quantize_u8(const float* in, int n, int c, int H, int W, uint8_t
  *                         W % 4 == 0, in 16-byte and out 4-byte aligned. */
 int savsr_video_gather_i420(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, float* out, void* stream);
 int savsr_video_quantize_i420(const float* in, int n, int H, int W, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 36) The scene-cut detector's scores (scene.hip; savsr_amd.pair_sad / detect_cuts, upscale_video(cuts="auto"), DESIGN.md
+ * section 1; savsr_amd/scenes.py restates them in numpy).  sad_out[k] (k = 0 .. n_frames - 2, int64 on the device) = the sum of absolute
+ * differences of the 8-bit samples of frames k and k + 1: an exact integer, whatever the grid (integer atomics).  The entries zero
+ * sad_out themselves (hipMemsetAsync on `stream`), only enqueue, allocate nothing and are capturable; arguments are checked before the
+ * device is touched (SAVSR_E_ARG + savsr_last_error()).  n_frames = 1 is accepted and enqueues nothing (there is no pair).
+ * savsr_video_pair_sad_u8:   frames [n_frames][h][w][c] uint8 (c = 1 .. 3): every byte, S = c * h * w samples per pair.
+ * savsr_video_pair_sad_i420: frames [n_frames] I420 (the layout of savsr_video_gather_i420): the h * w Y bytes only.
+ * savsr_video_pair_sad_f32:  frames [n_frames][c][h][w] fp32: every value quantised by savsr_video_quantize_u8's rule first (clamp to
+ *                         [0, 1], x 255.0f, rintf; NaN -> 0), S = c * h * w.
+ * 16-byte loads from both frames where the two frame pointers and the tail allow (a byte / float head and tail otherwise: odd sizes
+ * and unaligned bases are served), 4 bytes per v_sad_u8, a wave reduction and one 64-bit vector atomic per workgroup. */
+int savsr_video_pair_sad_u8(const uint8_t* frames, int n_frames, int c, int h, int w, int64_t* sad_out, void* stream);
+int savsr_video_pair_sad_i420(const uint8_t* frames, int n_frames, int h, int w, int64_t* sad_out, void* stream);
+int savsr_video_pair_sad_f32(const float* frames, int n_frames, int c, int h, int w, int64_t* sad_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 33) Geometric self-ensemble (ensemble.hip; SAVSR.set_self_ensemble).  Variant k = 0 .. 7: fw = k & 1 flips

@@ -5,6 +5,7 @@
     python -m savsr_amd.upscale -i <lr_frames/> -o <sr_frames/> --scale 4 --checkpoint <net.pth> --self-ensemble
     python -m savsr_amd.upscale -i in.y4m -o out.y4m --scale 4 --checkpoint <net.pth>
     ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o - --scale 4 --checkpoint <net.pth> | ffmpeg -i - out.mp4
+    python -m savsr_amd.upscale -i in.y4m -o out.y4m --scale 4 --checkpoint <net.pth> --cuts auto --cuts-out cuts.txt
 
 PNG folder: frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on
 the FrameStore pool (savsr_amd.io), pushed through VideoUpscaler in chunks (uint8 in, uint8 out: the windows, the network and the
@@ -16,7 +17,11 @@ video's length is not known, so a video too short for the window is refused when
 buffers and written by one ordered writer thread while the next chunk runs.  The two kinds mix: .y4m in, folder out writes %08d.png;
 folder in, .y4m out takes its frame rate from --fps.
 
-It ends with one line: frames, seconds, frames/s (on stderr when the video goes to stdout).
+--cuts: edited footage.  Windows stop at scene cuts (every scene is upscaled as a video of its own, savsr_amd/scenes.py): auto finds
+them on the GPU as the frames arrive (--scene-threshold, per cent of the largest possible frame change; ffmpeg scdet's rule and default,
+not validated on real footage), K,K,... or @FILE (one frame index per line) gives them.  --cuts-out FILE writes the cuts used, one per line.
+
+It ends with one line: frames, seconds, frames/s (on stderr when the video goes to stdout); with --cuts, the scene count as well.
 """
 from __future__ import annotations
 
@@ -56,7 +61,35 @@ def build_parser() -> argparse.ArgumentParser:
                    help="conv operand precision (default fp32; fp16: faster, ~1e-3 drift, see DESIGN.md section 3)")
     p.add_argument("--self-ensemble", action="store_true",
                    help="average the 8 flip / transpose variants of every window (8x the work; DESIGN.md section 11)")
+    p.add_argument("--cuts", default=None, metavar="auto|K,K,...|@FILE",
+                   help="scene cuts (first frame of every new scene): auto = found on the GPU, a comma-separated list, or @FILE with one index "
+                        "per line; windows stop at cuts")
+    p.add_argument("--scene-threshold", type=float, default=10.0, metavar="X",
+                   help="--cuts auto: a cut is a frame change of at least X per cent of the largest possible one (default 10, ffmpeg scdet's)")
+    p.add_argument("--cuts-out", default=None, metavar="FILE", help="write the cut list actually used, one frame index per line")
     return p
+
+
+def parse_cuts(text: str):
+    """--cuts: "auto", "K,K,..." or "@FILE" (one index per line, blank lines skipped) -> "auto" or a checked list of ints."""
+    from .scenes import check_cuts
+    if text == "auto":
+        return text
+    if text.startswith("@"):
+        try:
+            with open(text[1:]) as f:
+                items = [ln.strip() for ln in f if ln.strip()]
+        except OSError as e:
+            raise ValueError(f"cannot read {text[1:]!r}: {e}") from None
+    else:
+        items = [t.strip() for t in text.split(",") if t.strip()]
+        if not items:
+            raise ValueError("an empty list: give auto, K,K,... or @FILE")
+    try:
+        cuts = [int(t) for t in items]
+    except ValueError:
+        raise ValueError(f"frame indices are integers, got {items!r}") from None
+    return check_cuts(cuts, None)
 
 
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
@@ -71,6 +104,15 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--chunk must be >= 1")
     if a.writers < 0 or a.writers > MAX_WRITERS:
         p.error(f"--writers must be in 0 .. {MAX_WRITERS}")
+    if a.cuts is not None:
+        from .scenes import check_threshold
+        try:
+            a.cuts = parse_cuts(a.cuts)
+            check_threshold(a.scene_threshold)
+        except ValueError as e:
+            p.error(f"--cuts / --scene-threshold: {e}")
+    elif a.cuts_out is not None:
+        p.error("--cuts-out goes with --cuts")
     a.y4m_in, a.y4m_out = is_y4m(a.input), is_y4m(a.output)
     if a.fps is not None and (a.y4m_in or not a.y4m_out):
         p.error("--fps goes with a PNG folder in and Y4M out (a Y4M input carries its frame rate, PNGs have none)")
@@ -215,8 +257,11 @@ def main(argv: Optional[List[str]] = None) -> int:
     net = load_net(a)
     net.set_precision(a.precision)
     net.set_self_ensemble(a.self_ensemble)
-    if paths is not None:
+    if paths is not None and a.cuts is None:
         check_length(len(paths), net.num_frame, a.padding)        # (before the GPU is touched; a Y4M stream's length: at its end)
+    elif paths is not None and a.cuts != "auto":
+        from .scenes import check_cuts
+        check_cuts(a.cuts, len(paths))
     fin = fout = None
     try:
         if a.y4m_in:
@@ -253,7 +298,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                            a.writers or max(1, min(MAX_WRITERS, effective_cpus())))
         t0 = time.perf_counter()
         up = VideoUpscaler(net, a.scale, a.padding, out="i420" if a.y4m_out else "uint8", pixel_format="i420" if a.y4m_in else "rgb",
-                           size=(h, w) if a.y4m_in else None)
+                           size=(h, w) if a.y4m_in else None, cuts=a.cuts, scene_threshold=a.scene_threshold)
         done = 0
         try:
             for chunk in chunks:
@@ -266,7 +311,13 @@ def main(argv: Optional[List[str]] = None) -> int:
         for f, std in ((fin, sys.stdin.buffer), (fout, sys.stdout.buffer)):
             if f is not None and f is not std:
                 f.close()
-    print(f"upscaled {done} frames in {dt:.2f} s: {done / dt:.2f} frames/s", file=sys.stderr if a.output == "-" else sys.stdout, flush=True)
+    scenes = ""
+    if a.cuts is not None:
+        scenes = f", {len(up.cuts) + 1} scenes"
+        if a.cuts_out is not None:
+            with open(a.cuts_out, "w") as f:
+                f.writelines(f"{k}\n" for k in up.cuts)
+    print(f"upscaled {done} frames in {dt:.2f} s: {done / dt:.2f} frames/s{scenes}", file=sys.stderr if a.output == "-" else sys.stdout, flush=True)
     return 0
 
 

@@ -7,11 +7,15 @@ windows are gathered there (savsr_video_gather_u8 / _f32) and the uint8 result i
 HipEngine.forward_video.  pixel_format="i420" / out="i420": planar YUV 4:2:0 frames in / out (savsr_amd/yuv.py is the format and its
 numerics), converted on the device on either side of the network (savsr_video_gather_i420 / savsr_video_quantize_i420).
 
+cuts=[k, ...] / cuts="auto": the video is a sequence of scenes and every scene is treated as a video of its own (savsr_amd/scenes.py:
+windows stop at cuts); "auto" finds the cuts on the device (savsr_video_pair_sad_*, then scdet's rule on the host).  cuts=None runs
+exactly the lines it ran before cuts existed.
+
 Every argument is checked here, on the host, before anything is enqueued on the GPU.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -131,8 +135,100 @@ def check_out(out: str, nch: int) -> None:
         raise ValueError(f"out = 'i420' holds colour frames, the network gives num_in_ch = {nch}")
 
 
+def _is_auto(cuts) -> bool:
+    return isinstance(cuts, str) and cuts == "auto"
+
+
+def check_cuts_arg(cuts) -> None:
+    """cuts is None, "auto" or a sequence of frame indices (the indices themselves: scenes.check_cuts, once the length is known)."""
+    if cuts is None or _is_auto(cuts):
+        return
+    if isinstance(cuts, (str, bytes)):
+        raise ValueError(f"cuts = {cuts!r}: None, 'auto' or a sequence of frame indices")
+    from .scenes import check_cuts
+    check_cuts(cuts, None)
+
+
+def _sad_layout(frames: torch.Tensor, i420: Optional[Tuple[int, int]]) -> Tuple[int, int, int, int]:
+    """(N, c, h, w) of the frames the detector compares (c = 0: I420); no network here, so any c in 1 .. 3 and any h, w >= 1."""
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError(f"frames must be a torch.Tensor, got {type(frames).__name__}")
+    if i420:
+        h, w = i420
+        if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != i420_bytes(h, w):
+            raise ValueError(f"I420 frames of {h} x {w} are [N, {i420_bytes(h, w)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+        n, c = int(frames.shape[0]), 0
+    else:
+        if frames.dim() != 4:
+            raise ValueError(f"frames must be [N, h, w, c] uint8 or [N, c, h, w] float, got {frames.dim()} dimensions")
+        if frames.dtype == torch.uint8:
+            n, h, w, c = (int(v) for v in frames.shape)
+        elif frames.is_floating_point():
+            if not frames.is_cuda:
+                raise ValueError("float frames must be on the GPU ([N, c, h, w]); host frames go as [N, h, w, c] uint8")
+            n, c, h, w = (int(v) for v in frames.shape)
+        else:
+            raise ValueError(f"frames must be uint8 or float, got {frames.dtype}")
+        if not 1 <= c <= 3:
+            raise ValueError(f"frames have {c} channels: 1 .. 3")
+        if h < 1 or w < 1:
+            raise ValueError(f"frames of {h} x {w}")
+    if n < 1:
+        raise ValueError("the video has no frames")
+    return n, c, h, w
+
+
+def _pair_sad_device(frames: torch.Tensor, i420: Optional[Tuple[int, int]]) -> torch.Tensor:
+    """savsr_video_pair_sad_* on frames already on the GPU: int64 [N - 1] there, enqueued on the current stream (no sync)."""
+    from . import _lib
+    n, c, h, w = _sad_layout(frames, i420)
+    lib = _lib.load()
+    u8 = frames.dtype == torch.uint8
+    frames = frames.contiguous() if u8 else frames.to(torch.float32).contiguous()
+    with torch.cuda.device(frames.device):
+        sad = torch.empty(n - 1, dtype=torch.int64, device=frames.device)
+        st = torch.cuda.current_stream().cuda_stream
+        if i420:
+            _lib.check(lib.savsr_video_pair_sad_i420(frames.data_ptr(), n, h, w, sad.data_ptr(), st), "savsr_video_pair_sad_i420")
+        elif u8:
+            _lib.check(lib.savsr_video_pair_sad_u8(frames.data_ptr(), n, c, h, w, sad.data_ptr(), st), "savsr_video_pair_sad_u8")
+        else:
+            _lib.check(lib.savsr_video_pair_sad_f32(frames.data_ptr(), n, c, h, w, sad.data_ptr(), st), "savsr_video_pair_sad_f32")
+    return sad
+
+
+def _sad_device(frames: torch.Tensor) -> torch.device:
+    if frames.is_cuda:
+        return frames.device
+    if not torch.cuda.is_available():
+        raise RuntimeError("savsr_amd runs on an AMD GPU only: the detector's scores are computed there")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def pair_sad(frames: torch.Tensor, pixel_format: str = "rgb", size=None) -> torch.Tensor:
+    """The scene detector's scores: int64 [N - 1] on the GPU, entry j = the sum of absolute differences of the 8-bit samples of frames j
+    and j + 1 (savsr_amd.scenes.pair_sad is the specification).  frames as for SAVSR.upscale_video, with any c in 1 .. 3: [N, h, w, c]
+    uint8 (GPU or host; every byte), [N, c, h, w] float on the GPU (every value after the uint8 output's quantisation), or with
+    pixel_format="i420", size=(h, w): [N, i420_bytes(h, w)] uint8 (the Y plane only)."""
+    i420 = check_pixel_format(pixel_format, size)
+    _sad_layout(frames, i420)
+    return _pair_sad_device(_to_device(frames, _sad_device(frames)), i420)
+
+
+def detect_cuts(frames: torch.Tensor, threshold=10.0, pixel_format: str = "rgb", size=None) -> List[int]:
+    """The scene cuts of a video: the frames k whose change from frame k - 1, damped by the previous pair's, is at least `threshold`
+    per cent of the largest possible one (ffmpeg scdet's rule in exact integer arithmetic, savsr_amd.scenes.cuts_from_sad, on pair_sad's
+    scores; one device -> host copy of N - 1 integers).  The default threshold is scdet's and is not validated on real footage."""
+    from .scenes import check_threshold, cuts_from_sad, sad_samples
+    check_threshold(threshold)
+    i420 = check_pixel_format(pixel_format, size)
+    _sad_layout(frames, i420)
+    sad = pair_sad(frames, pixel_format, size)
+    return cuts_from_sad(sad.cpu().tolist(), sad_samples(frames.shape, pixel_format, size), threshold)
+
+
 def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
-                  size=None) -> torch.Tensor:
+                  size=None, cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
@@ -141,13 +237,29 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     sc = as_scale(net.scale if scale is None else scale)
     n = i420_layout(frames, i420, net.cfg["num_in_ch"]) if i420 else frame_layout(frames, net.cfg["num_in_ch"])[0]
     T = net.num_frame
-    check_length(n, T, padding)
+    if cuts is None:
+        check_length(n, T, padding)
+    else:
+        from . import scenes
+        check_cuts_arg(cuts)
+        scenes.check_threshold(scene_threshold)
+        if n < 1:
+            raise ValueError("the video has no frames")
+        if not _is_auto(cuts):
+            cuts = scenes.check_cuts(cuts, n)
     dev = net.gamma.device
     if dev.type != "cuda":
         raise RuntimeError("savsr_amd runs on an AMD GPU only: move the network to the GPU (net.cuda()) first")
-    windows = [window_indices(i, n, T, padding) for i in range(n)]
+    frames = _to_device(frames, dev)
+    if cuts is None:
+        windows = [window_indices(i, n, T, padding) for i in range(n)]
+    else:
+        if _is_auto(cuts):
+            sad = _pair_sad_device(frames, i420).cpu().tolist()
+            cuts = scenes.cuts_from_sad(sad, scenes.sad_samples(frames.shape, pixel_format, size), scene_threshold)
+        windows = scenes.scene_windows(n, cuts, T, padding)
     with torch.no_grad():
-        return net.engine().forward_video(_to_device(frames, dev), windows, sc, out == "uint8", ensemble=net.self_ensemble, i420=i420,
+        return net.engine().forward_video(frames, windows, sc, out == "uint8", ensemble=net.self_ensemble, i420=i420,
                                           out_i420=out == "i420")
 
 
@@ -163,12 +275,27 @@ class VideoUpscaler:
     Concatenated, the outputs are bit for bit upscale_video on the whole video, for any chunking (a frame's output depends on its
     window only).  The network's self-ensemble switch is read once, here, like the scale.  The device keeps the past frames a later
     window may still name -- at most num_frame - 1 (num_frame for the two circle modes, whose last windows reach num_frame - 1 frames
-    back) -- plus the current chunk."""
+    back) -- plus the current chunk.
 
-    def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb", size=None):
+    cuts=[k, ...] (global frame indices) or cuts="auto" (each push scores its new pairs on the device, the pair with the previous
+    push's last frame included, and decides with `scene_threshold`): windows stop at cuts as in upscale_video(cuts=...), and `up.cuts`
+    lists the cuts among the frames pushed so far.  A frame is returned once its window is the same however the video continues -- a cut
+    may still come anywhere after the last pushed frame (savsr_amd.scenes.ScenePlan); the frames kept are bounded as without cuts."""
+
+    def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb", size=None,
+                 cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0):
         _check_net(net)
         check_padding(padding)
         check_out(out, net.cfg["num_in_ch"])
+        self._plan = None                          # scenes.ScenePlan when cuts are given; None: the path without cuts, as it was
+        if cuts is not None:
+            from . import scenes
+            check_cuts_arg(cuts)
+            self._threshold = scenes.check_threshold(scene_threshold)
+            self._auto = _is_auto(cuts)
+            self._given = [] if self._auto else scenes.check_cuts(cuts, None)       # explicit cuts not reached yet
+            self._prev_sad = 0                     # the last pair's score (scdet's damping term), carried from push to push
+            self._plan = scenes.ScenePlan(net.num_frame, padding)
         self.i420 = check_pixel_format(pixel_format, size)        # (h, w) of I420 chunks, None for RGB ones
         self.net, self.padding, self.out = net, padding, out
         self.scale = as_scale(net.scale if scale is None else scale)
@@ -181,6 +308,11 @@ class VideoUpscaler:
         self.done = 0                                 # frames returned
         self._shape: Optional[tuple] = None           # (dtype is uint8, h, w)
         self._finished = False
+
+    @property
+    def cuts(self) -> Optional[List[int]]:
+        """The cuts among the frames pushed so far (None without cuts=)."""
+        return None if self._plan is None else list(self._plan.cuts)
 
     def _ready(self, i: int) -> bool:
         """Frame i's window is known whatever the video's length turns out to be (>= seen)."""
@@ -224,6 +356,8 @@ class VideoUpscaler:
         new = _to_device(frames, dev)
         new = new.contiguous() if shape[0] else new.to(torch.float32).contiguous()
         self._buf = new if self._buf is None else torch.cat([self._buf, new], 0)
+        if self._plan is not None:
+            return self._push_scenes(k)
         self.seen += k
         upto = self.done
         while upto < self.seen and self._ready(upto):
@@ -235,12 +369,58 @@ class VideoUpscaler:
             self._base = lo
         return res
 
+    def _new_cuts(self, k: int) -> List[int]:
+        """The cuts among the k frames just appended to the buffer."""
+        lo, hi = self.seen, self.seen + k
+        if not self._auto:
+            n = sum(1 for c in self._given if c < hi)
+            new, self._given = self._given[:n], self._given[n:]
+            return new
+        first = max(lo, 1)                          # frame `first`'s pair starts at the previous push's last frame, still in the buffer
+        if hi - first < 1:
+            return []
+        from .scenes import cuts_from_sad, sad_samples
+        sad = _pair_sad_device(self._buf[first - 1 - self._base:], self.i420).cpu().tolist()
+        new = cuts_from_sad(sad, sad_samples(self._buf.shape, "i420" if self.i420 else "rgb", self.i420), self._threshold, first, self._prev_sad)
+        self._prev_sad = sad[-1]
+        return new
+
+    def _run_windows(self, windows: List[List[int]]) -> torch.Tensor:
+        if not windows:
+            return self._empty()
+        windows = [[j - self._base for j in win] for win in windows]
+        with torch.no_grad():
+            return self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble, i420=self.i420,
+                                                   out_i420=self.out == "i420")
+
+    def _push_scenes(self, k: int) -> torch.Tensor:
+        plan = self._plan
+        plan.push(k, self._new_cuts(k))
+        self.seen = plan.seen
+        res = self._run_windows(plan.take())
+        self.done = plan.done
+        lo = plan.keep_from()
+        if self._auto:
+            lo = min(lo, self.seen - 1)            # the next push's first pair
+        if lo > self._base:
+            self._buf = self._buf[lo - self._base:]
+            self._base = lo
+        return res
+
     def finish(self) -> torch.Tensor:
         if self._finished:
             raise RuntimeError("finish() called twice")
         self._finished = True
         if self.seen == 0:
             raise ValueError("the video has no frames")
+        if self._plan is not None:
+            if self._given:
+                raise ValueError(f"cut {self._given[0]}: a cut is the first frame of a new scene, 0 < k < {self.seen}")
+            self._plan.end()
+            res = self._run_windows(self._plan.take())
+            self.done = self._plan.done
+            self._buf = None
+            return res
         check_length(self.seen, self.T, self.padding)
         res = self._run(self.seen, self.seen) if self.done < self.seen else self._empty()
         self._buf = None
