@@ -84,16 +84,30 @@ __device__ long long g_wy_stamps[256 * 8 * 8];
 #define WY_MARK(i) do { } while (0)
 #endif
 
+// (hi, lo) split of four fp32 values: hh = bf16(v) (RNE), lo = bf16(v - float(hh)).  Written per PAIR of values: one v_cvt_pk_bf16_f32 makes the
+// pair's hi words, and float(hh) is read back out of THAT register (low word << 16, high word masked) -- 12 vector instructions per four values
+// (2 cvt, 4 unpack, 4 sub, 2 cvt).  Left to itself hipcc converts every value a second time on its own (v_cvt_pk_bf16_f32 v, junk) to get
+// float(hh): 16 per four values.  The empty asm keeps it from looking through the packed register; it emits nothing.
+// (The subtractions stay one v_sub_f32 per value: packed fp32 beside MFMAs holds the issue port as long as the two instructions it replaces,
+// and hipcc unpacks most v_pk_add_f32 it selects there again -- DESIGN.md section 4a, which also says how to re-check the 12 after a compiler update.)
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void wy_split_store(const f32x4& v, bf16x4* hi_dst, bf16x4* lo_dst) {
-    bf16x4 hi, lo;
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    const f32x2 a[2] = {{v[0], v[1]}, {v[2], v[3]}};
+    u32x2 hi, lo;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const __bf16 hh = (__bf16)v[j];
-        hi[j] = hh;
-        lo[j] = (__bf16)(v[j] - (float)hh);
+    for (int p = 0; p < 2; ++p) hi[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(a[p], bf16x2));
+    // (both conversions in front of the first unpack: a v_cvt_pk result read by the very next instruction costs an s_nop on gfx950)
+    asm("" : "+v"(hi[0]), "+v"(hi[1]));
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const f32x2 back = {__builtin_bit_cast(float, hi[p] << 16), __builtin_bit_cast(float, hi[p] & 0xffff0000u)};
+        const f32x2 rest = {a[p][0] - back[0], a[p][1] - back[1]};
+        lo[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(rest, bf16x2));
     }
-    *hi_dst = hi;
-    *lo_dst = lo;
+    *hi_dst = __builtin_bit_cast(bf16x4, hi);
+    *lo_dst = __builtin_bit_cast(bf16x4, lo);
 }
 // fp16-operand form (conv_wy_kernel<.., true>): one fp16 (RNE) plane in the hi plane's place; the lo plane is neither written nor read
 __device__ __forceinline__ void wy_f16_store(const f32x4& v, bf16x4* hi_dst) {
@@ -515,7 +529,30 @@ __global__ __launch_bounds__(512) void conv_wy_kernel(const MultiConvParams mp) 
                     WY_MARK(WY_KSEC(hf * 3 + 2));
                 }
             };
-            if (rows_in) phase(std::true_type{}); else phase(std::false_type{});
+            // A wave whose row pair lies below the image has no matrix work and nobody reads its V region.  While the cursor's NEXT phase belongs to
+            // such a row pair too -- the rest of this tile, a following tile in which the wave is dead again, or no phase at all -- its phase is
+            // the shared work alone: its pieces of both weight halves, the cursor and the two barriers; no row loads, no transform, no split, no
+            // V stores, and its V region keeps whatever it held.  Only the last phase in front of a tile in which the wave has rows stages, in the
+            // full form.  The test is on the STAGED tile's rows (y0 + 2 wave_s of tile + gridDim.x), all scalar.  Waves with matrix work always
+            // stage, zeros included: a branch would cut their steps' scheduling regions.
+            auto phase_dead = [&]() {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) issue_w(j, 1);
+                stage_next();
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (nothing younger than the DMAs is in flight: wait for all)
+                __syncthreads();
+#pragma unroll
+                for (int j = 0; j < 3; ++j) issue_w(j, 0);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+            };
+            auto next_tile_rows_in = [&]() {
+                if (tile + (int)gridDim.x >= total) return false;
+                return decode(tile + (int)gridDim.x).y0 + 2 * wave_s < H;
+            };
+            if (rows_in) phase(std::true_type{});
+            else if (chunk + 1 == mp.nchunk && next_tile_rows_in()) phase(std::false_type{});
+            else phase_dead();
         }
 
         // ---- epilogue: as the direct kernel's (conv_mfma.hip): transpose through the wave's LDS slice 32 channels at a time, whole
