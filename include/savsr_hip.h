@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 36
+#define SAVSR_ABI_VERSION 37
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -451,6 +451,27 @@ int savsr_video_quantize_u8(const float* in, int n, int c, int H, int W, uint8_t
  *                         W % 4 == 0, in 16-byte and out 4-byte aligned. */
 int savsr_video_gather_i420(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, float* out, void* stream);
 int savsr_video_quantize_i420(const float* in, int n, int H, int W, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 37) The same two conversions with the colour space as an argument (yuv.hip; colour / out_colour of SAVSR.upscale_video, --colour /
+ * --out-colour of python -m savsr_amd.upscale).  colour = one of SAVSR_YUV_*:
+ *   BT601       ITU-R BT.601 limited range with the reference's rounded constants: what the two entries above run, which are the
+ *               colour = SAVSR_YUV_BT601 case of the same kernels
+ *   BT709       Kr = 0.2126, Kb = 0.0722, limited range (Y 16 .. 235, chroma 16 .. 240): what players assume of untagged HD video
+ *   BT601_FULL  Kr = 0.299, Kb = 0.114, full range (JFIF; Y4M's XCOLORRANGE=FULL)
+ *   BT709_FULL  Kr = 0.2126, Kb = 0.0722, full range
+ * The three are built in float64 from (Kr, Kb, range): Kg = 1 - Kr - Kb, Cb = (B - Y') / (2 (1 - Kb)), Cr = (R - Y') / (2 (1 - Kr)),
+ * Y = 16 + 219 Y' and C = 128 + 224 C' limited, Y = 255 Y' and C = 128 + 255 C' full (savsr_amd/yuv.py `matrix` is the formula and
+ * restates both kernels bit for bit).  Frame layout, index list, arithmetic, vector / scalar variants and alignment rules are those of
+ * savsr_video_gather_i420 / savsr_video_quantize_i420; full range clips the rounded samples to 0 .. 255 (pure red / blue give a chroma
+ * of 255.5).  The input and the output side are independent: BT.601 in, BT.709 out converts between the two at no extra cost.  A colour
+ * outside 0 .. 3 is SAVSR_E_ARG, before the device is touched. */
+#define SAVSR_YUV_BT601 0
+#define SAVSR_YUV_BT709 1
+#define SAVSR_YUV_BT601_FULL 2
+#define SAVSR_YUV_BT709_FULL 3
+int savsr_video_gather_yuv420(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, int colour, float* out, void* stream);
+int savsr_video_quantize_yuv420(const float* in, int n, int H, int W, int colour, uint8_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 36) The scene-cut detector's scores (scene.hip; savsr_amd.pair_sad / detect_cuts, upscale_video(cuts="auto"), DESIGN.md

@@ -278,7 +278,7 @@ class SAVSR(nn.Module):
                                               ensemble=self.self_ensemble)
 
     def upscale_video(self, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
-                      size=None, cuts=None, scene_threshold=10.0) -> torch.Tensor:
+                      size=None, cuts=None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -287,6 +287,11 @@ class SAVSR(nn.Module):
         (savsr_amd/yuv.py: BT.601 limited range, the reference's rgb2ycbcr / ycbcr2rgb), converted to fp32 RGB on the GPU without an
         8-bit rounding; num_in_ch = 3.  out="i420", with either input format: [N, i420_bytes(H, W)] uint8, the fp32 frames converted and
         rounded once, in YUV.
+        colour: the colour space of I420 input, one of savsr_amd.yuv.COLOURS: "bt601" (the default: BT.601 limited range), "bt709"
+        (limited range; what players take untagged HD video for), "bt601-full", "bt709-full" (full range, Y4M's XCOLORRANGE=FULL).
+        out_colour: that of I420 output; None = the same as colour.  The two sides are independent (the network works in RGB), so
+        colour="bt601", out_colour="bt709" also converts an SD source into what an HD player expects.  colour goes with
+        pixel_format="i420" and out_colour with out="i420".
         cuts: None (one scene), a strictly increasing list of frame indices 0 < k < N (frame k starts a new scene), or "auto" (found on
         the GPU: savsr_amd.detect_cuts with scene_threshold, in per cent of the largest possible frame change; the default is ffmpeg
         scdet's and is not validated on real footage).  Windows stop at cuts: the result is, bit for bit, upscale_video on every scene
@@ -294,7 +299,7 @@ class SAVSR(nn.Module):
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
-        return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold)
+        return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold, colour, out_colour)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

@@ -1,9 +1,13 @@
-// Planar YUV 4:2:0 (I420) on either side of the network (ABI 35): I420 frames -> the fp32 planar RGB clip batch the engine stages, and
-// the fp32 result -> I420 frames for an encoder or a Y4M pipe.  The I420 counterparts of savsr_video_gather_u8 / _quantize_u8
+// Planar YUV 4:2:0 (I420) on either side of the network (ABI 35; the colour space as an argument: ABI 37): I420 frames -> the fp32 planar
+// RGB clip batch the engine stages, and the fp32 result -> I420 frames for an encoder or a Y4M pipe.  The I420 counterparts of savsr_video_gather_u8 / _quantize_u8
 // (video.hip); like them not fused into the SATU / tail kernels (satu.hip, tail.hip and common.hpp stay as they are, and with them
 // savsr_source_hash_satu() and savsr_amd/hr_plans.json).
 //
 //   rgb2ycbcr / ycbcr2rgb   lbasicsr/utils/color_util.py:5-35, 71-97   ITU-R BT.601, limited range, Matlab's rounded constants
+//
+// That is colour space 0 (SAVSR_YUV_BT601) and what the entries without a colour argument run.  1 .. 3 are BT.709 limited, BT.601 full
+// (JFIF) and BT.709 full, built from (Kr, Kb, range) by make_matrix; the arithmetic is the same for all four, and full range clips the
+// rounded samples to 0 .. 255 (pure red / blue give a chroma of 255.5, which rounds to 256).
 //
 // savsr_amd/yuv.py restates both kernels in numpy and is what they are tested against, bit for bit: float32, a fixed operation order
 // and no fused multiply-add (contraction is off for this whole file).
@@ -18,14 +22,45 @@
 namespace savsr {
 namespace {
 
-// The one coefficient table of this file (yuv.py: BT601).  to-RGB entries per 8-bit step with the result in [0, 1], offsets in 8-bit
+// A colour space's coefficient table (yuv.py: matrix).  to-RGB entries per 8-bit step with the result in [0, 1], offsets in 8-bit
 // steps; to-YCbCr rows in 8-bit steps per unit of RGB.
 struct YuvMatrix {
     double y, rv, gu, gv, bu, off_r, off_g, off_b;     // ycbcr2rgb
     float ky[3], kcb[3], kcr[3], oy, oc;               // rgb2ycbcr
+    bool full;                                         // full range: the rounded samples are clipped to 0 .. 255
 };
 constexpr YuvMatrix kBt601 = {0.00456621, 0.00625893, -0.00153632, -0.00318811, 0.00791071, -222.921, 135.576, -276.836,
-                              {65.481f, 128.553f, 24.966f}, {-37.797f, -74.203f, 112.0f}, {112.0f, -93.786f, -18.214f}, 16.0f, 128.0f};
+                              {65.481f, 128.553f, 24.966f}, {-37.797f, -74.203f, 112.0f}, {112.0f, -93.786f, -18.214f}, 16.0f, 128.0f, false};
+
+// The table of luma weights (Kr, Kb) and a range (yuv.py: _build, the same float64 expressions in the same order; a constant expression
+// is evaluated in IEEE double without contraction, as Python evaluates them).  Kg = 1 - Kr - Kb, Cb = (B - Y') / (2 (1 - Kb)),
+// Cr = (R - Y') / (2 (1 - Kr)); Y = oy + sy Y', C = 128 + sc C' with (sy, oy, sc) = (219, 16, 224) limited, (255, 0, 255) full.
+constexpr YuvMatrix make_matrix(double kr, double kb, bool full) {
+    const double sy = full ? 255.0 : 219.0, oy = full ? 0.0 : 16.0, sc = full ? 255.0 : 224.0;
+    const double kg = (1.0 - kr) - kb;
+    const double db = 2.0 * (1.0 - kb), dr = 2.0 * (1.0 - kr);
+    YuvMatrix m{};
+    m.y = 1.0 / sy;
+    m.rv = dr / sc;
+    m.gu = -((db * kb) / (kg * sc));
+    m.gv = -((dr * kr) / (kg * sc));
+    m.bu = db / sc;
+    const double base = -(oy * m.y);
+    m.off_r = (base - 128.0 * m.rv) * 255.0;
+    m.off_g = ((base - 128.0 * m.gu) - 128.0 * m.gv) * 255.0;
+    m.off_b = (base - 128.0 * m.bu) * 255.0;
+    m.ky[0] = static_cast<float>(sy * kr); m.ky[1] = static_cast<float>(sy * kg); m.ky[2] = static_cast<float>(sy * kb);
+    m.kcb[0] = static_cast<float>(-((sc * kr) / db)); m.kcb[1] = static_cast<float>(-((sc * kg) / db)); m.kcb[2] = static_cast<float>(sc * 0.5);
+    m.kcr[0] = static_cast<float>(sc * 0.5); m.kcr[1] = static_cast<float>(-((sc * kg) / dr)); m.kcr[2] = static_cast<float>(-((sc * kb) / dr));
+    m.oy = static_cast<float>(oy);
+    m.oc = 128.0f;
+    m.full = full;
+    return m;
+}
+// By colour id (savsr_hip.h: SAVSR_YUV_*; yuv.py: COLOURS).
+enum { N_COLOURS = 4 };
+struct YuvMatrices { YuvMatrix m[N_COLOURS]; };
+constexpr YuvMatrices kYuv = {{kBt601, make_matrix(0.2126, 0.0722, false), make_matrix(0.299, 0.114, true), make_matrix(0.2126, 0.0722, true)}};
 
 // Per-sample terms of ycbcr2rgb (yuv.py: to_rgb_tables): the float64 product, plus the channel's offset / 255 where it is folded in,
 // rounded once to float32 -- a constant expression, so the compiler evaluates it in IEEE double exactly as numpy does.
@@ -43,8 +78,14 @@ constexpr YuvTables make_tables(const YuvMatrix& m) {
     }
     return t;
 }
-constexpr YuvTables kTablesValue = make_tables(kBt601);
-__constant__ YuvTables kYuvToRgb = kTablesValue;
+struct YuvTablesAll { YuvTables c[N_COLOURS]; };
+constexpr YuvTablesAll make_all_tables() {
+    YuvTablesAll a{};
+    for (int c = 0; c < N_COLOURS; ++c) a.c[c] = make_tables(kYuv.m[c]);
+    return a;
+}
+constexpr YuvTablesAll kTablesValue = make_all_tables();
+__constant__ YuvTablesAll kYuvToRgb = kTablesValue;              // 4 x 5 KiB
 
 struct YuvIdx { int32_t f[SAVSR_VIDEO_MAX_SLOTS]; };     // slot -> frame, by value in the kernel arguments
 
@@ -63,13 +104,13 @@ __device__ __forceinline__ void put_rgb(const float (*lut)[256], uint32_t y, uin
 // I420 frames [N][fb] -> fp32 planar RGB slots [n][3][h][w], slot k = frame idx.f[k].  A thread owns a block of 2 rows so that a chroma
 // sample is read once.  VEC: 2 rows x 4 pixels -- a Y dword per row and 2 + 2 chroma bytes in, one float4 per plane row out (w % 4 == 0,
 // 4-byte aligned frames, 16-byte aligned out: then every Y row is dword aligned and every chroma row 2-byte aligned); otherwise 2 x 2
-// pixels with byte loads and scalar stores.
+// pixels with byte loads and scalar stores.  `colour` (0 .. N_COLOURS - 1, checked by the entry) picks the five tables staged in LDS.
 template <bool VEC>
-__global__ __launch_bounds__(256) void gather_i420_kernel(const uint8_t* __restrict__ src, int h, int w, long long fb, YuvIdx idx,
+__global__ __launch_bounds__(256) void gather_i420_kernel(const uint8_t* __restrict__ src, int h, int w, long long fb, YuvIdx idx, int colour,
                                                           float* __restrict__ out) {
     __shared__ float lut[T_COUNT][256];
 #pragma unroll
-    for (int t = 0; t < T_COUNT; ++t) lut[t][threadIdx.x] = kYuvToRgb.v[t][threadIdx.x];
+    for (int t = 0; t < T_COUNT; ++t) lut[t][threadIdx.x] = kYuvToRgb.c[colour].v[t][threadIdx.x];
     __syncthreads();
     const int k = blockIdx.y;
     const long long npx = (long long)h * w;
@@ -120,18 +161,32 @@ __global__ __launch_bounds__(256) void gather_i420_kernel(const uint8_t* __restr
 
 // rgb2ycbcr's rows in 8-bit steps: every product and every sum rounded to float32 (yuv.py: _row).  Plain operators under this file's
 // `fp contract(off)`: the header's __fmul_rn / __fadd_rn are compiled with contraction allowed and fuse again once inlined.
+// CLIP (full range): the rounded value clipped to 0 .. 255 (yuv.py: rgb_to_i420); limited range stays inside 16 .. 240 by itself.
+template <bool CLIP>
 __device__ __forceinline__ uint32_t row3_u8(float k0, float k1, float k2, float off, float r, float g, float b) {
-    return (uint32_t)rintf(((r * k0 + g * k1) + b * k2) + off);
+    const float v = rintf(((r * k0 + g * k1) + b * k2) + off);
+    return (uint32_t)(CLIP ? fminf(fmaxf(v, 0.f), 255.f) : v);
 }
-__device__ __forceinline__ uint32_t luma_u8(float r, float g, float b) { return row3_u8(kBt601.ky[0], kBt601.ky[1], kBt601.ky[2], kBt601.oy, r, g, b); }
-__device__ __forceinline__ uint32_t cb_u8(float r, float g, float b) { return row3_u8(kBt601.kcb[0], kBt601.kcb[1], kBt601.kcb[2], kBt601.oc, r, g, b); }
-__device__ __forceinline__ uint32_t cr_u8(float r, float g, float b) { return row3_u8(kBt601.kcr[0], kBt601.kcr[1], kBt601.kcr[2], kBt601.oc, r, g, b); }
+// The rows of colour space C: the coefficients are constants of the instantiation (immediates in the code).
+template <int C> __device__ __forceinline__ uint32_t luma_u8(float r, float g, float b) {
+    constexpr YuvMatrix m = kYuv.m[C];
+    return row3_u8<m.full>(m.ky[0], m.ky[1], m.ky[2], m.oy, r, g, b);
+}
+template <int C> __device__ __forceinline__ uint32_t cb_u8(float r, float g, float b) {
+    constexpr YuvMatrix m = kYuv.m[C];
+    return row3_u8<m.full>(m.kcb[0], m.kcb[1], m.kcb[2], m.oc, r, g, b);
+}
+template <int C> __device__ __forceinline__ uint32_t cr_u8(float r, float g, float b) {
+    constexpr YuvMatrix m = kYuv.m[C];
+    return row3_u8<m.full>(m.kcr[0], m.kcr[1], m.kcr[2], m.oc, r, g, b);
+}
 
 // fp32 planar RGB [n][3][H][W] -> I420 frames [n][fb]: clamp(0, 1); Y per pixel; Cb / Cr from the mean RGB of the block's in-image
 // pixels -- ((a + b) + (c + d)) * 0.25 with a b the upper row, (a + b) * 0.5 for a pair, the pixel alone (yuv.py: _block_mean); rintf
 // (round half to even).  VEC: a thread owns 2 rows x 4 pixels -- one float4 per plane row in (nontemporal: the result is read once), a Y
 // dword per row and 2 + 2 chroma bytes out (W % 4 == 0, 16-byte aligned in, 4-byte aligned out); otherwise 2 x 2 pixels, scalar.
-template <bool VEC>
+// C: the colour space, a template argument so that its rows stay immediates.
+template <bool VEC, int C>
 __global__ __launch_bounds__(256) void quantize_i420_kernel(const float* __restrict__ in, int H, int W, long long fb, uint8_t* __restrict__ out) {
     const int k = blockIdx.y;
     const long long npx = (long long)H * W;
@@ -159,7 +214,7 @@ __global__ __launch_bounds__(256) void quantize_i420_kernel(const float* __restr
                 for (int e = 0; e < 4; ++e) px[dy][c][e] = clamp01(x[e]);
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) yy |= luma_u8(px[dy][0][e], px[dy][1][e], px[dy][2][e]) << (8 * e);
+            for (int e = 0; e < 4; ++e) yy |= luma_u8<C>(px[dy][0][e], px[dy][1][e], px[dy][2][e]) << (8 * e);
             *reinterpret_cast<uint32_t*>(fy + p) = yy;
         }
         uint32_t uu = 0u, vv = 0u;
@@ -171,8 +226,8 @@ __global__ __launch_bounds__(256) void quantize_i420_kernel(const float* __restr
                 const float top = px[0][c][2 * j] + px[0][c][2 * j + 1];
                 m[c] = two ? (top + (px[1][c][2 * j] + px[1][c][2 * j + 1])) * 0.25f : top * 0.5f;
             }
-            uu |= cb_u8(m[0], m[1], m[2]) << (8 * j);
-            vv |= cr_u8(m[0], m[1], m[2]) << (8 * j);
+            uu |= cb_u8<C>(m[0], m[1], m[2]) << (8 * j);
+            vv |= cr_u8<C>(m[0], m[1], m[2]) << (8 * j);
         }
         const long long coff = (long long)cy * cw + x0 / 2;
         *reinterpret_cast<uint16_t*>(fu + coff) = (uint16_t)uu;
@@ -188,7 +243,7 @@ __global__ __launch_bounds__(256) void quantize_i420_kernel(const float* __restr
                 const long long p = (long long)(2 * cy + dy) * W + 2 * cx + dx;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) q[dy][dx][c] = clamp01(src[c * npx + p]);
-                fy[p] = (uint8_t)luma_u8(q[dy][dx][0], q[dy][dx][1], q[dy][dx][2]);
+                fy[p] = (uint8_t)luma_u8<C>(q[dy][dx][0], q[dy][dx][1], q[dy][dx][2]);
             }
         }
         float m[3];
@@ -199,8 +254,8 @@ __global__ __launch_bounds__(256) void quantize_i420_kernel(const float* __restr
             else if (two_y) m[c] = (q[0][0][c] + q[1][0][c]) * 0.5f;
             else m[c] = q[0][0][c];
         }
-        fu[(long long)cy * cw + cx] = (uint8_t)cb_u8(m[0], m[1], m[2]);
-        fv[(long long)cy * cw + cx] = (uint8_t)cr_u8(m[0], m[1], m[2]);
+        fu[(long long)cy * cw + cx] = (uint8_t)cb_u8<C>(m[0], m[1], m[2]);
+        fv[(long long)cy * cw + cx] = (uint8_t)cr_u8<C>(m[0], m[1], m[2]);
     }
 }
 
@@ -216,33 +271,75 @@ int load_idx(const int32_t* idx, int n, int n_frames, YuvIdx* gi, const char* wh
 
 inline long long i420_bytes(int h, int w) { return (long long)h * w + 2LL * ((h + 1) / 2) * ((w + 1) / 2); }
 
+int check_colour(int colour, const char* what) {
+    if (colour < 0 || colour >= N_COLOURS) { set_error("invalid argument: %s: colour %d (0 .. %d)", what, colour, N_COLOURS - 1); return SAVSR_E_ARG; }
+    return 0;
+}
+
+int fail(const char* what, const char* msg) {
+    set_error("invalid argument: %s: %s", what, msg);
+    return SAVSR_E_ARG;
+}
+
+// The two entries of either kernel: `what` names the one called in its messages.
+int gather_yuv420(const char* what, const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, int colour, float* out,
+                  void* stream) {
+    if (!frames || !out) return fail(what, "null pointer");
+    if (h < 1 || w < 1 || n_frames < 1) return fail(what, "h, w, n_frames >= 1");
+    if (int rc = check_colour(colour, what)) return rc;
+    YuvIdx gi;
+    if (int rc = load_idx(idx, n_idx, n_frames, &gi, what)) return rc;
+    const bool vec = w % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    const long long units = (long long)((h + 1) / 2) * (vec ? w / 4 : (w + 1) / 2);
+    const dim3 grid(blocks_for(units), n_idx);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (vec) hipLaunchKernelGGL((gather_i420_kernel<true>), grid, dim3(256), 0, st, frames, h, w, i420_bytes(h, w), gi, colour, out);
+    else hipLaunchKernelGGL((gather_i420_kernel<false>), grid, dim3(256), 0, st, frames, h, w, i420_bytes(h, w), gi, colour, out);
+    return check_launch("gather_i420_kernel");
+}
+
+template <int C>
+void launch_quantize(bool vec, dim3 grid, hipStream_t st, const float* in, int H, int W, uint8_t* out) {
+    if (vec) hipLaunchKernelGGL((quantize_i420_kernel<true, C>), grid, dim3(256), 0, st, in, H, W, i420_bytes(H, W), out);
+    else hipLaunchKernelGGL((quantize_i420_kernel<false, C>), grid, dim3(256), 0, st, in, H, W, i420_bytes(H, W), out);
+}
+
+int quantize_yuv420(const char* what, const float* in, int n, int H, int W, int colour, uint8_t* out, void* stream) {
+    if (!in || !out) return fail(what, "null pointer");
+    if (n < 1 || n > 65535 || H < 1 || W < 1) return fail(what, "n in 1 .. 65535, H, W >= 1");
+    if (int rc = check_colour(colour, what)) return rc;
+    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0;
+    const long long units = (long long)((H + 1) / 2) * (vec ? W / 4 : (W + 1) / 2);
+    const dim3 grid(blocks_for(units), n);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (colour) {
+        case 0: launch_quantize<0>(vec, grid, st, in, H, W, out); break;
+        case 1: launch_quantize<1>(vec, grid, st, in, H, W, out); break;
+        case 2: launch_quantize<2>(vec, grid, st, in, H, W, out); break;
+        default: launch_quantize<3>(vec, grid, st, in, H, W, out); break;
+    }
+    return check_launch("quantize_i420_kernel");
+}
+
 }  // namespace
 }  // namespace savsr
 
 using namespace savsr;
 
+extern "C" int savsr_video_gather_yuv420(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, int colour, float* out,
+                                         void* stream) {
+    return gather_yuv420("video_gather_yuv420", frames, n_frames, h, w, idx, n_idx, colour, out, stream);
+}
+
+extern "C" int savsr_video_quantize_yuv420(const float* in, int n, int H, int W, int colour, uint8_t* out, void* stream) {
+    return quantize_yuv420("video_quantize_yuv420", in, n, H, W, colour, out, stream);
+}
+
+// The entries of ABI 35: colour space 0.
 extern "C" int savsr_video_gather_i420(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, float* out, void* stream) {
-    if (!frames || !out) return fail_arg("video_gather_i420: null pointer");
-    if (h < 1 || w < 1 || n_frames < 1) return fail_arg("video_gather_i420: h, w, n_frames >= 1");
-    YuvIdx gi;
-    if (int rc = load_idx(idx, n_idx, n_frames, &gi, "video_gather_i420")) return rc;
-    const bool vec = w % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-    const long long units = (long long)((h + 1) / 2) * (vec ? w / 4 : (w + 1) / 2);
-    const dim3 grid(blocks_for(units), n_idx);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (vec) hipLaunchKernelGGL((gather_i420_kernel<true>), grid, dim3(256), 0, st, frames, h, w, i420_bytes(h, w), gi, out);
-    else hipLaunchKernelGGL((gather_i420_kernel<false>), grid, dim3(256), 0, st, frames, h, w, i420_bytes(h, w), gi, out);
-    return check_launch("gather_i420_kernel");
+    return gather_yuv420("video_gather_i420", frames, n_frames, h, w, idx, n_idx, SAVSR_YUV_BT601, out, stream);
 }
 
 extern "C" int savsr_video_quantize_i420(const float* in, int n, int H, int W, uint8_t* out, void* stream) {
-    if (!in || !out) return fail_arg("video_quantize_i420: null pointer");
-    if (n < 1 || n > 65535 || H < 1 || W < 1) return fail_arg("video_quantize_i420: n in 1 .. 65535, H, W >= 1");
-    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0;
-    const long long units = (long long)((H + 1) / 2) * (vec ? W / 4 : (W + 1) / 2);
-    const dim3 grid(blocks_for(units), n);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (vec) hipLaunchKernelGGL((quantize_i420_kernel<true>), grid, dim3(256), 0, st, in, H, W, i420_bytes(H, W), out);
-    else hipLaunchKernelGGL((quantize_i420_kernel<false>), grid, dim3(256), 0, st, in, H, W, i420_bytes(H, W), out);
-    return check_launch("quantize_i420_kernel");
+    return quantize_yuv420("video_quantize_i420", in, n, H, W, SAVSR_YUV_BT601, out, stream);
 }

@@ -34,7 +34,7 @@ from .config import EngineConfig
 from .launch import MAX_SUM_BLOCKS, Launcher, Src, _ptr      # noqa: F401
 from .packing import (BN_EPS, CONV_TH, CONV_TW, WeightPacking, acc_row, conv_pack_geometry, conv_pack_index, conv_wy_pack_index, get_hw,      # noqa: F401  (re-exported:
                       pack_conv_part, pack_conv_weight, pack_conv_weight_wy, satu_axis_tables, split_bf16_image, window_record)                            # tests and tools import them from here)
-from .yuv import i420_bytes
+from .yuv import COLOURS, i420_bytes
 
 
 class HipEngine(WeightPacking, ContextCache, Launcher):
@@ -797,7 +797,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         return outs
 
     def forward_video(self, frames: torch.Tensor, windows: List[List[int]], scale, out_u8: bool = False, ensemble: bool = False,
-                      i420: Optional[Tuple[int, int]] = None, out_i420: bool = False) -> torch.Tensor:
+                      i420: Optional[Tuple[int, int]] = None, out_i420: bool = False, colour: int = 0, out_colour: int = 0) -> torch.Tensor:
         """The sequence path (SAVSR.upscale_video): frames [N, h, w, c] uint8 or [N, c, h, w] fp32 on the device, windows[i] = the
         num_frame frame indices of output frame i in clip order (harness.window_indices) -> [len(windows), c, H, W] fp32, or
         [len(windows), H, W, c] uint8 (out_u8: tensor2img(x, rgb2bgr=False) per frame, savsr_video_quantize_u8).
@@ -805,12 +805,15 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         `streams_for` streams; throughput flow), so frame i equals forward_many on the gathered window i bit for bit.  A unit's windows are
         gathered from `frames` by savsr_video_gather_u8 / _f32 into a unit-sized fp32 clip batch on the unit's stream; nothing is gathered
         or converted on the host.  ensemble=True: frame i is the self-ensemble of window i (`_ensemble`, gathered by savsr_ensemble_gather_*).
-        i420=(h, w): frames are [N, i420_bytes(h, w)] uint8, planar YUV 4:2:0 (savsr_amd/yuv.py), gathered by savsr_video_gather_i420 where
-        the uint8 gather runs; out_i420: the result is [len(windows), i420_bytes(H, W)] uint8, quantised by savsr_video_quantize_i420 where
-        the uint8 quantisation runs.  With the ensemble, I420 frames are converted once to fp32 planar RGB (the same gather with the
-        identity list) and take the fp32 path, and an I420 result is the fp32 merge followed by the quantisation."""
+        i420=(h, w): frames are [N, i420_bytes(h, w)] uint8, planar YUV 4:2:0 (savsr_amd/yuv.py), gathered by savsr_video_gather_yuv420 where
+        the uint8 gather runs; out_i420: the result is [len(windows), i420_bytes(H, W)] uint8, quantised by savsr_video_quantize_yuv420 where
+        the uint8 quantisation runs.  colour / out_colour: the colour space ids (positions in yuv.COLOURS) of the I420 input / output.  With
+        the ensemble, I420 frames are converted once to fp32 planar RGB (the same gather with the identity list) and take the fp32 path,
+        and an I420 result is the fp32 merge followed by the quantisation."""
         if out_u8 and out_i420:
             raise ValueError("one output kind: uint8 or I420")
+        if not (0 <= colour < len(COLOURS) and 0 <= out_colour < len(COLOURS)):
+            raise ValueError(f"colour ids {colour}, {out_colour}: 0 .. {len(COLOURS) - 1} ({', '.join(COLOURS)})")
         if i420 is not None:
             h, w = (int(v) for v in i420)
             if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != i420_bytes(h, w):
@@ -838,8 +841,8 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             raise ValueError(f"num_frame = {T}: the window gather takes at most {_lib.VIDEO_MAX_SLOTS} frames per launch")
         if i420 is not None:
             def gather(idx, dst, st):
-                _lib.check(self.lib.savsr_video_gather_i420(frames.data_ptr(), N, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), dst.data_ptr(), st),
-                           "savsr_video_gather_i420")
+                _lib.check(self.lib.savsr_video_gather_yuv420(frames.data_ptr(), N, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), colour,
+                                                              dst.data_ptr(), st), "savsr_video_gather_yuv420")
         else:
             fn = self.lib.savsr_video_gather_u8 if u8 else self.lib.savsr_video_gather_f32
 
@@ -850,7 +853,8 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             for a in range(0, int(src.shape[0]), 65535):          # (the entries take 1 .. 65535 frames)
                 nb = min(65535, int(src.shape[0]) - a)
                 if out_i420:
-                    _lib.check(self.lib.savsr_video_quantize_i420(src[a:a + nb].data_ptr(), nb, H, W, dst[a:a + nb].data_ptr(), st), "savsr_video_quantize_i420")
+                    _lib.check(self.lib.savsr_video_quantize_yuv420(src[a:a + nb].data_ptr(), nb, H, W, out_colour, dst[a:a + nb].data_ptr(), st),
+                               "savsr_video_quantize_yuv420")
                 else:
                     _lib.check(self.lib.savsr_video_quantize_u8(src[a:a + nb].data_ptr(), nb, c, H, W, dst[a:a + nb].data_ptr(), st), "savsr_video_quantize_u8")
         if ensemble:

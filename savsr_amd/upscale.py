@@ -6,6 +6,7 @@
     python -m savsr_amd.upscale -i in.y4m -o out.y4m --scale 4 --checkpoint <net.pth>
     ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o - --scale 4 --checkpoint <net.pth> | ffmpeg -i - out.mp4
     python -m savsr_amd.upscale -i in.y4m -o out.y4m --scale 4 --checkpoint <net.pth> --cuts auto --cuts-out cuts.txt
+    python -m savsr_amd.upscale -i sd.y4m -o hd.y4m --scale 4 --checkpoint <net.pth> --colour auto --out-colour auto
 
 PNG folder: frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on
 the FrameStore pool (savsr_amd.io), pushed through VideoUpscaler in chunks (uint8 in, uint8 out: the windows, the network and the
@@ -17,11 +18,21 @@ video's length is not known, so a video too short for the window is refused when
 buffers and written by one ordered writer thread while the next chunk runs.  The two kinds mix: .y4m in, folder out writes %08d.png;
 folder in, .y4m out takes its frame rate from --fps.
 
+--colour / --out-colour: the colour space of the Y4M input / output, one of bt601, bt709 (limited range), bt601-full, bt709-full.  The
+defaults (bt601, and the same for the output) are what this tool has always done, so an existing command line writes the bytes it
+wrote.  Y4M has no tag for the matrix, and every player and encoder takes an untagged HD stream for BT.709: `auto` follows that
+convention (BT.709 if w >= 1280 or h > 576, else BT.601, on the frame size of that side -- players' rule for untagged streams, not a
+tuned number) and takes the range from the input's XCOLORRANGE tag (limited without one).  For SD -> HD work give
+--colour auto --out-colour auto: the SD source is read as BT.601 and the HD result is written as the BT.709 a player will assume, at
+no extra cost and without another 8-bit rounding (the network works in RGB).  The output carries XCOLORRANGE when it is full range or
+when either flag was given.
+
 --cuts: edited footage.  Windows stop at scene cuts (every scene is upscaled as a video of its own, savsr_amd/scenes.py): auto finds
 them on the GPU as the frames arrive (--scene-threshold, per cent of the largest possible frame change; ffmpeg scdet's rule and default,
 not validated on real footage), K,K,... or @FILE (one frame index per line) gives them.  --cuts-out FILE writes the cuts used, one per line.
 
-It ends with one line: frames, seconds, frames/s (on stderr when the video goes to stdout); with --cuts, the scene count as well.
+It ends with one line: frames, seconds, frames/s (on stderr when the video goes to stdout); with --cuts, the scene count as well; with
+--colour / --out-colour, the two colour spaces.
 """
 from __future__ import annotations
 
@@ -34,12 +45,38 @@ import time
 from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional
 
+from .yuv import COLOURS
+
 MAX_WRITERS = 16
 PINNED_BUFFERS = 3          # SR chunks in flight between the GPU and the Y4M writer thread
 
 
 def is_y4m(path: str) -> bool:
     return path == "-" or path.lower().endswith(".y4m")
+
+
+def auto_colour(h: int, w: int, full: bool) -> str:
+    """The colour space players assume of an untagged h x w stream: BT.709 if w >= 1280 or h > 576, else BT.601; `full`: its range."""
+    return ("bt709" if w >= 1280 or h > 576 else "bt601") + ("-full" if full else "")
+
+
+def resolve_colours(colour: str, out_colour: str, lr, hr, in_range: Optional[str]):
+    """--colour / --out-colour -> (colour of the Y4M input or None, colour of the Y4M output or None).  lr / hr: (h, w) of a Y4M input /
+    output, None for a PNG folder on that side; in_range: the input's XCOLORRANGE ("full", "limited" or None = limited).  An output
+    `auto` takes the range the input was read with (limited for PNGs); `same` is the input's colour space (bt601 for PNGs)."""
+    from .yuv import is_full_range
+    cin = None
+    if lr is not None:
+        cin = auto_colour(lr[0], lr[1], in_range == "full") if colour == "auto" else colour
+    cout = None
+    if hr is not None:
+        if out_colour == "same":
+            cout = cin or "bt601"
+        elif out_colour == "auto":
+            cout = auto_colour(hr[0], hr[1], cin is not None and is_full_range(cin))
+        else:
+            cout = out_colour
+    return cin, cout
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -61,6 +98,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="conv operand precision (default fp32; fp16: faster, ~1e-3 drift, see DESIGN.md section 3)")
     p.add_argument("--self-ensemble", action="store_true",
                    help="average the 8 flip / transpose variants of every window (8x the work; DESIGN.md section 11)")
+    p.add_argument("--colour", default=None, choices=list(COLOURS) + ["auto"],
+                   help="colour space of a Y4M input (default bt601, limited range).  auto: the range from the input's XCOLORRANGE tag (limited "
+                        "without one) and the matrix players assume of an untagged stream of that size: bt709 if w >= 1280 or h > 576, else bt601")
+    p.add_argument("--out-colour", default=None, choices=list(COLOURS) + ["auto", "same"],
+                   help="colour space of a Y4M output (default same: the input's; bt601 for a PNG folder).  auto: the input's range and the matrix "
+                        "players assume at the output size.  For SD -> HD give --colour auto --out-colour auto: an untagged HD stream is shown as "
+                        "BT.709, so a BT.601 one has shifted colours")
     p.add_argument("--cuts", default=None, metavar="auto|K,K,...|@FILE",
                    help="scene cuts (first frame of every new scene): auto = found on the GPU, a comma-separated list, or @FILE with one index "
                         "per line; windows stop at cuts")
@@ -116,6 +160,13 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     a.y4m_in, a.y4m_out = is_y4m(a.input), is_y4m(a.output)
     if a.fps is not None and (a.y4m_in or not a.y4m_out):
         p.error("--fps goes with a PNG folder in and Y4M out (a Y4M input carries its frame rate, PNGs have none)")
+    if a.colour is not None and not a.y4m_in:
+        p.error("--colour goes with a Y4M input (PNG frames are RGB)")
+    if a.out_colour is not None and not a.y4m_out:
+        p.error("--out-colour goes with a Y4M output (PNG frames are RGB)")
+    a.colour_flags = a.colour is not None or a.out_colour is not None       # (either given: the output is tagged, the summary names them)
+    a.colour = a.colour or "bt601"
+    a.out_colour = a.out_colour or "same"
     from .y4m import parse_fps
     try:
         a.fps = parse_fps(a.fps) if a.fps is not None else (25, 1)
@@ -253,6 +304,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     from .utils.host import effective_cpus
     from .video import VideoUpscaler, check_length
     from .y4m import Y4MReader, Y4MWriter, scaled_aspect
+    from .yuv import is_full_range
 
     net = load_net(a)
     net.set_precision(a.precision)
@@ -270,7 +322,7 @@ def main(argv: Optional[List[str]] = None) -> int:
             fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
             reader = Y4MReader(fin)
             h, w = reader.height, reader.width
-            fps, interlace, aspect = reader.fps, reader.interlace, reader.aspect
+            fps, interlace, aspect, in_range = reader.fps, reader.interlace, reader.aspect, reader.colour_range
             chunks = (torch.from_numpy(c) for c in reader.chunks(a.chunk))
         else:
             from .io import FrameStore
@@ -280,7 +332,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                 from PIL import Image
                 with Image.open(paths[0]) as im:
                     w, h = im.size
-            fps, interlace, aspect = a.fps, "p", (0, 0)
+            fps, interlace, aspect, in_range = a.fps, "p", (0, 0), None
 
             def png_chunks():
                 store.request(paths)
@@ -289,16 +341,21 @@ def main(argv: Optional[List[str]] = None) -> int:
             chunks = png_chunks()
         dev = torch.device(a.device)
         net = net.to(dev)
+        hr = get_hw(h, w, a.scale) if a.y4m_out else None
+        colour, out_colour = resolve_colours(a.colour, a.out_colour, (h, w) if a.y4m_in else None, hr, in_range)
         if a.y4m_out:
-            H, W = get_hw(h, w, a.scale)
+            H, W = hr
             fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
-            sink = Y4MSink(Y4MWriter(fout, W, H, fps, interlace, scaled_aspect(aspect, (h, w), (H, W))), a.chunk + net.num_frame)
+            full = is_full_range(out_colour)
+            tag = ("full" if full else "limited") if (full or a.colour_flags) else None
+            sink = Y4MSink(Y4MWriter(fout, W, H, fps, interlace, scaled_aspect(aspect, (h, w), (H, W)), tag), a.chunk + net.num_frame)
         else:
             sink = PngSink(a.output, None if paths is None else [os.path.basename(p) for p in paths],
                            a.writers or max(1, min(MAX_WRITERS, effective_cpus())))
         t0 = time.perf_counter()
         up = VideoUpscaler(net, a.scale, a.padding, out="i420" if a.y4m_out else "uint8", pixel_format="i420" if a.y4m_in else "rgb",
-                           size=(h, w) if a.y4m_in else None, cuts=a.cuts, scene_threshold=a.scene_threshold)
+                           size=(h, w) if a.y4m_in else None, cuts=a.cuts, scene_threshold=a.scene_threshold, colour=colour or "bt601",
+                           out_colour=out_colour)
         done = 0
         try:
             for chunk in chunks:
@@ -317,6 +374,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         if a.cuts_out is not None:
             with open(a.cuts_out, "w") as f:
                 f.writelines(f"{k}\n" for k in up.cuts)
+    if a.colour_flags:
+        scenes += f", colour {colour or 'rgb'} -> {out_colour or 'rgb'}"
     print(f"upscaled {done} frames in {dt:.2f} s: {done / dt:.2f} frames/s{scenes}", file=sys.stderr if a.output == "-" else sys.stdout, flush=True)
     return 0
 

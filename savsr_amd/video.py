@@ -20,7 +20,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 import torch
 
 from .harness import window_indices
-from .yuv import i420_bytes
+from .yuv import check_colour, i420_bytes
 
 PADDING_MODES = ("replicate", "reflection", "reflection_circle", "circle")
 OUT_KINDS = ("float", "uint8", "i420")
@@ -96,6 +96,18 @@ def check_pixel_format(pixel_format: str, size) -> Optional[Tuple[int, int]]:
     if h < 2 or w < 2:
         raise ValueError(f"SAVSR needs h, w >= 2, got {h} x {w}")
     return int(h), int(w)
+
+
+def check_colours(colour, out_colour, pixel_format: str, out: str) -> Tuple[int, int]:
+    """The colour space ids (yuv.COLOURS) of the I420 input and output.  `colour` goes with pixel_format = 'i420' and `out_colour` with
+    out = 'i420'; out_colour = None: the same as colour."""
+    cid = check_colour(colour, "colour")
+    ocid = cid if out_colour is None else check_colour(out_colour, "out_colour")
+    if cid != 0 and pixel_format != "i420":
+        raise ValueError(f"colour = {colour!r} goes with pixel_format = 'i420': it is the colour space of I420 input (RGB frames have none)")
+    if out_colour is not None and out != "i420":
+        raise ValueError(f"out_colour = {out_colour!r} goes with out = 'i420': it is the colour space of I420 output")
+    return cid, ocid
 
 
 def i420_layout(frames: torch.Tensor, size: Tuple[int, int], nch: int) -> int:
@@ -228,12 +240,14 @@ def detect_cuts(frames: torch.Tensor, threshold=10.0, pixel_format: str = "rgb",
 
 
 def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
-                  size=None, cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0) -> torch.Tensor:
+                  size=None, cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601",
+                  out_colour: Optional[str] = None) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
     check_out(out, net.cfg["num_in_ch"])
     i420 = check_pixel_format(pixel_format, size)
+    cid, ocid = check_colours(colour, out_colour, pixel_format, out)
     sc = as_scale(net.scale if scale is None else scale)
     n = i420_layout(frames, i420, net.cfg["num_in_ch"]) if i420 else frame_layout(frames, net.cfg["num_in_ch"])[0]
     T = net.num_frame
@@ -260,7 +274,7 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         windows = scenes.scene_windows(n, cuts, T, padding)
     with torch.no_grad():
         return net.engine().forward_video(frames, windows, sc, out == "uint8", ensemble=net.self_ensemble, i420=i420,
-                                          out_i420=out == "i420")
+                                          out_i420=out == "i420", colour=cid, out_colour=ocid)
 
 
 class VideoUpscaler:
@@ -277,13 +291,15 @@ class VideoUpscaler:
     window may still name -- at most num_frame - 1 (num_frame for the two circle modes, whose last windows reach num_frame - 1 frames
     back) -- plus the current chunk.
 
+    colour / out_colour: the colour spaces of I420 chunks in / out, as in upscale_video.
+
     cuts=[k, ...] (global frame indices) or cuts="auto" (each push scores its new pairs on the device, the pair with the previous
     push's last frame included, and decides with `scene_threshold`): windows stop at cuts as in upscale_video(cuts=...), and `up.cuts`
     lists the cuts among the frames pushed so far.  A frame is returned once its window is the same however the video continues -- a cut
     may still come anywhere after the last pushed frame (savsr_amd.scenes.ScenePlan); the frames kept are bounded as without cuts."""
 
     def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb", size=None,
-                 cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0):
+                 cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None):
         _check_net(net)
         check_padding(padding)
         check_out(out, net.cfg["num_in_ch"])
@@ -297,6 +313,7 @@ class VideoUpscaler:
             self._prev_sad = 0                     # the last pair's score (scdet's damping term), carried from push to push
             self._plan = scenes.ScenePlan(net.num_frame, padding)
         self.i420 = check_pixel_format(pixel_format, size)        # (h, w) of I420 chunks, None for RGB ones
+        self._colours = check_colours(colour, out_colour, pixel_format, out)      # colour space ids of the I420 input / output
         self.net, self.padding, self.out = net, padding, out
         self.scale = as_scale(net.scale if scale is None else scale)
         self.ensemble = net.self_ensemble          # (read once, like the scale: every chunk runs the same flow)
@@ -334,7 +351,7 @@ class VideoUpscaler:
         windows = [[j - self._base for j in window_indices(i, n, self.T, self.padding)] for i in range(self.done, upto)]
         with torch.no_grad():
             res = self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble, i420=self.i420,
-                                                  out_i420=self.out == "i420")
+                                                  out_i420=self.out == "i420", colour=self._colours[0], out_colour=self._colours[1])
         self.done = upto
         return res
 
@@ -391,7 +408,7 @@ class VideoUpscaler:
         windows = [[j - self._base for j in win] for win in windows]
         with torch.no_grad():
             return self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble, i420=self.i420,
-                                                   out_i420=self.out == "i420")
+                                                   out_i420=self.out == "i420", colour=self._colours[0], out_colour=self._colours[1])
 
     def _push_scenes(self, k: int) -> torch.Tensor:
         plan = self._plan

@@ -6,7 +6,8 @@ from another program (ffmpeg -f yuv4mpegpipe, x264, a player) without a library.
 
 8-bit 4:2:0 only: C420, C420jpeg, C420mpeg2, C420paldv and a missing C tag (= 420) are read; every other tag is refused by name.  The
 three 420 tags differ in chroma siting only, which is accepted and ignored (yuv.py's nearest / box pair is centre-sited); the writer
-tags its output C420jpeg.
+tags its output C420jpeg.  XCOLORRANGE=FULL / XCOLORRANGE=LIMITED (ffmpeg's extension tag) is read into `colour_range` and written on
+request; the format has no tag for the matrix (BT.601 / BT.709), which is the caller's to know or to guess from the frame size.
 """
 from __future__ import annotations
 
@@ -20,6 +21,7 @@ from .yuv import i420_bytes
 MAGIC = b"YUV4MPEG2"
 C420_TAGS = ("420", "420jpeg", "420mpeg2", "420paldv")
 MAX_LINE = 4096          # a header or FRAME line longer than this is not Y4M
+COLOUR_RANGES = ("full", "limited")
 
 
 def _ratio(tag: str, val: str) -> Tuple[int, int]:
@@ -84,8 +86,9 @@ def _read_line(f) -> bytes:
 
 
 class Y4MReader:
-    """Reads the header on construction (width, height, fps, interlace, aspect, colorspace), then `chunks(k)` yields the frames as
-    uint8 arrays [m, i420_bytes(height, width)], m = k but for the last."""
+    """Reads the header on construction (width, height, fps, interlace, aspect, colorspace, colour_range), then `chunks(k)` yields the
+    frames as uint8 arrays [m, i420_bytes(height, width)], m = k but for the last.  colour_range: "full" / "limited" of an
+    XCOLORRANGE=FULL / =LIMITED tag, None without one."""
 
     def __init__(self, f):
         self.f = f
@@ -98,6 +101,7 @@ class Y4MReader:
         self.interlace = "p"
         self.aspect: Tuple[int, int] = (0, 0)
         self.colorspace = "420"
+        self.colour_range: Optional[str] = None
         for tag in line[len(MAGIC):].decode("ascii", errors="replace").split():
             key, val = tag[0], tag[1:]
             if key in "WH":
@@ -121,8 +125,9 @@ class Y4MReader:
                 if val not in C420_TAGS:
                     raise ValueError(f"y4m: colour space tag 'C{val}' is not supported: 8-bit 4:2:0 only ({', '.join('C' + t for t in C420_TAGS)})")
                 self.colorspace = val
-            elif key == "X":
-                pass                                  # comments / extensions (XYSCSS=..., XCOLORRANGE=...): ignored
+            elif key == "X":                          # comments / extensions (XYSCSS=...): ignored, but for the range
+                if val in ("COLORRANGE=FULL", "COLORRANGE=LIMITED"):
+                    self.colour_range = val[11:].lower()
             else:
                 raise ValueError(f"y4m: unknown header tag {tag!r}")
         if self.width is None or self.height is None:
@@ -159,14 +164,19 @@ class Y4MReader:
 
 
 class Y4MWriter:
-    """Writes the header on construction, then `write(frames)` appends uint8 frames [m, i420_bytes(height, width)]."""
+    """Writes the header on construction, then `write(frames)` appends uint8 frames [m, i420_bytes(height, width)].
+    colour_range = "full" / "limited": the header also carries XCOLORRANGE=FULL / =LIMITED (None: no such tag)."""
 
-    def __init__(self, f, width: int, height: int, fps: Tuple[int, int] = (25, 1), interlace: str = "p", aspect: Tuple[int, int] = (0, 0)):
+    def __init__(self, f, width: int, height: int, fps: Tuple[int, int] = (25, 1), interlace: str = "p", aspect: Tuple[int, int] = (0, 0),
+                 colour_range: Optional[str] = None):
         if width < 1 or height < 1:
             raise ValueError(f"y4m: W, H >= 1, got {width} x {height}")
+        if colour_range is not None and colour_range not in COLOUR_RANGES:
+            raise ValueError(f"y4m: colour_range = {colour_range!r}: None or one of {', '.join(COLOUR_RANGES)}")
         self.f, self.width, self.height = f, int(width), int(height)
         self.frame_bytes = i420_bytes(self.height, self.width)
-        self.header = f"YUV4MPEG2 W{self.width} H{self.height} F{fps[0]}:{fps[1]} I{interlace} A{aspect[0]}:{aspect[1]} C420jpeg\n".encode("ascii")
+        self.header = (f"YUV4MPEG2 W{self.width} H{self.height} F{fps[0]}:{fps[1]} I{interlace} A{aspect[0]}:{aspect[1]} C420jpeg"
+                       f"{'' if colour_range is None else ' XCOLORRANGE=' + colour_range.upper()}\n").encode("ascii")
         f.write(self.header)
 
     def write(self, frames: np.ndarray) -> None:

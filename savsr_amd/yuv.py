@@ -1,8 +1,9 @@
 """Planar YUV 4:2:0 (I420) <-> RGB, the host restatement that specifies savsr_video_gather_i420 / savsr_video_quantize_i420 (yuv.hip).
 
-The colour matrix is the reference's (lbasicsr/utils/color_util.py, `rgb2ycbcr` / `ycbcr2rgb`: ITU-R BT.601, limited range, Matlab's
-rounded constants), the same whose Y row metrics.py uses for PSNR-Y.  8-bit 4:2:0 only; `BT601` is the one coefficient table here
-(`kBt601` is its twin in yuv.hip), so another matrix or range is another table.
+The default colour matrix is the reference's (lbasicsr/utils/color_util.py, `rgb2ycbcr` / `ycbcr2rgb`: ITU-R BT.601, limited range,
+Matlab's rounded constants: `BT601`), the same whose Y row metrics.py uses for PSNR-Y.  8-bit 4:2:0 only.  `COLOURS` names the four
+colour spaces served (`colour=`; the position is the id of the C ABI) and `matrix(name)` gives each one's coefficient table: BT601
+itself for "bt601", built from (Kr, Kb, range) for the others (`kYuv` is the twin in yuv.hip, the same float64 expressions).
 
 I420 frame of an h x w picture: h * w Y bytes, then ch * cw U (Cb) bytes, then ch * cw V (Cr) bytes, ch = (h + 1) // 2,
 cw = (w + 1) // 2 -- the frame as it lies in a Y4M file.  A video is a uint8 array [N, i420_bytes(h, w)].
@@ -13,7 +14,8 @@ Both directions are float32 with a fixed operation order and no fused multiply-a
                 a C++ constant expression gives), summed in float32 in a fixed order, clamped to [0, 1]; chroma replicated over its
                 2 x 2 block.  Not rounded to 8 bits.
   rgb_to_i420   RGB clamped to [0, 1]; Y per pixel; Cb / Cr from the mean RGB of the block's in-image pixels (1, 2 or 4: the
-                divisor is a power of two); every product and every sum rounded to float32; round half to even (tensor2img's rule).
+                divisor is a power of two); every product and every sum rounded to float32; round half to even (tensor2img's rule);
+                full range only: clipped to 0 .. 255 after the rounding (pure red has Cr = 255.5, pure blue Cb = 255.5 -> 256).
 """
 from __future__ import annotations
 
@@ -29,6 +31,58 @@ BT601 = {
     "to_ycbcr": {"y": (65.481, 128.553, 24.966), "cb": (-37.797, -74.203, 112.0), "cr": (112.0, -93.786, -18.214),
                  "offset": (16.0, 128.0, 128.0)},
 }
+
+
+# The colour spaces of `colour=`, in the order of their integer id in the C ABI (SAVSR_YUV_*): name -> (Kr, Kb, full range).  "bt601" is
+# the BT601 table above as it stands (its constants are rounded, so it is not rebuilt from Kr, Kb); "bt601-full" is JFIF's exact form.
+COLOURS = ("bt601", "bt709", "bt601-full", "bt709-full")
+_SPACES = {"bt709": (0.2126, 0.0722, False), "bt601-full": (0.299, 0.114, True), "bt709-full": (0.2126, 0.0722, True)}
+
+
+def check_colour(colour, what: str = "colour") -> int:
+    """The id of a colour space name (its position in COLOURS); refuses anything else, naming the list."""
+    if not isinstance(colour, str) or colour not in COLOURS:
+        raise ValueError(f"{what} = {colour!r}: one of {', '.join(COLOURS)}")
+    return COLOURS.index(colour)
+
+
+def is_full_range(colour: str) -> bool:
+    return colour != "bt601" and _SPACES[COLOURS[check_colour(colour)]][2]
+
+
+def _build(kr: float, kb: float, full: bool) -> dict:
+    """A table of BT601's shape from the luma weights and the range, in float64.  With Kg = 1 - Kr - Kb, Y' = Kr R + Kg G + Kb B,
+    Cb = (B - Y') / (2 (1 - Kb)), Cr = (R - Y') / (2 (1 - Kr)); 8-bit samples Y = oy + sy Y', C = 128 + sc C'  (limited: sy = 219,
+    oy = 16, sc = 224; full: sy = 255, oy = 0, sc = 255).  Every entry is the expression below as written, evaluated left to right
+    inside its parentheses: make_matrix in yuv.hip evaluates the same ones, so that the two tables agree to the last bit."""
+    sy, oy, sc = (255.0, 0.0, 255.0) if full else (219.0, 16.0, 224.0)
+    kg = (1.0 - kr) - kb
+    db, dr = 2.0 * (1.0 - kb), 2.0 * (1.0 - kr)
+    y = 1.0 / sy
+    rv = dr / sc
+    gu = -((db * kb) / (kg * sc))
+    gv = -((dr * kr) / (kg * sc))
+    bu = db / sc
+    base = -(oy * y)
+    return {
+        "to_rgb": {"y": y, "rv": rv, "gu": gu, "gv": gv, "bu": bu,
+                   "offset": ((base - 128.0 * rv) * 255.0, ((base - 128.0 * gu) - 128.0 * gv) * 255.0, (base - 128.0 * bu) * 255.0)},
+        "to_ycbcr": {"y": (sy * kr, sy * kg, sy * kb),
+                     "cb": (-((sc * kr) / db), -((sc * kg) / db), sc * 0.5),
+                     "cr": (sc * 0.5, -((sc * kg) / dr), -((sc * kb) / dr)),
+                     "offset": (oy, 128.0, 128.0)},
+    }
+
+
+_MATRICES = {"bt601": BT601}
+
+
+def matrix(colour: str = "bt601") -> dict:
+    """The coefficient table of a colour space, of BT601's shape: BT601 itself for "bt601", `_build` of (Kr, Kb, range) otherwise."""
+    name = COLOURS[check_colour(colour)]
+    if name not in _MATRICES:
+        _MATRICES[name] = _build(*_SPACES[name])
+    return _MATRICES[name]
 
 
 def chroma_hw(h: int, w: int) -> Tuple[int, int]:
@@ -72,10 +126,10 @@ def to_rgb_tables(m: dict = BT601) -> dict:
             "bu": (s * t["bu"] + o[2]).astype(np.float32)}
 
 
-def i420_to_rgb(frames_u8: np.ndarray, h: int, w: int) -> np.ndarray:
+def i420_to_rgb(frames_u8: np.ndarray, h: int, w: int, colour: str = "bt601") -> np.ndarray:
     """[N, i420_bytes(h, w)] uint8 -> float32 [N, 3, h, w] in [0, 1]:  R = y + rv,  G = (y + gu) + gv,  B = y + bu  on the table values."""
     y, u, v = split_planes(frames_u8, h, w)
-    t = to_rgb_tables()
+    t = to_rgb_tables(matrix(colour))
     u = np.repeat(np.repeat(u, 2, axis=1), 2, axis=2)[:, :h, :w]
     v = np.repeat(np.repeat(v, 2, axis=1), 2, axis=2)[:, :h, :w]
     ty = t["y"][y]
@@ -117,16 +171,20 @@ def _block_mean(p: np.ndarray) -> np.ndarray:
     return m
 
 
-def ycbcr_f32(x: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+def ycbcr_f32(x: np.ndarray, colour: str = "bt601") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """The float32 values rgb_to_i420 rounds: Y [N, H, W], Cb and Cr [N, ch, cw], in 8-bit steps."""
     p = _clamp01(x)
-    t = BT601["to_ycbcr"]
+    t = matrix(colour)["to_ycbcr"]
     m = _block_mean(p)
     return _row(p, t["y"], t["offset"][0]), _row(m, t["cb"], t["offset"][1]), _row(m, t["cr"], t["offset"][2])
 
 
-def rgb_to_i420(x_f32: np.ndarray) -> np.ndarray:
-    """float32 [N, 3, H, W] -> uint8 [N, i420_bytes(H, W)].  After the clamp Y lies in 16 .. 235 and chroma in 16 .. 240: no clip."""
-    y, cb, cr = ycbcr_f32(x_f32)
+def rgb_to_i420(x_f32: np.ndarray, colour: str = "bt601") -> np.ndarray:
+    """float32 [N, 3, H, W] -> uint8 [N, i420_bytes(H, W)].  Limited range: after the clamp Y lies in 16 .. 235 and chroma in
+    16 .. 240, no clip.  Full range: chroma reaches 255.5, which rounds to 256, so the rounded values are clipped to 0 .. 255."""
+    y, cb, cr = ycbcr_f32(x_f32, colour)
     n = y.shape[0]
-    return np.concatenate([np.rint(v).astype(np.uint8).reshape(n, -1) for v in (y, cb, cr)], 1)
+    planes = [np.rint(v) for v in (y, cb, cr)]
+    if is_full_range(colour):
+        planes = [np.fmin(np.fmax(v, np.float32(0.0)), np.float32(255.0)) for v in planes]
+    return np.concatenate([v.astype(np.uint8).reshape(n, -1) for v in planes], 1)

@@ -3,7 +3,8 @@ fails, times out or dies ends the run (nothing more is started on the GPU) and w
 
   kernels   savsr_video_gather_i420 / _quantize_i420 beside savsr_video_gather_u8 / _quantize_u8 of the same build, in one process,
             interleaved rounds, at 180x320 and 720x1280: us, the fraction of 8 TB/s on 4*3*h*w + 1.5*h*w bytes, and the ratio to the RGB
-            kernel's time (they move the same fp32 bytes and half the uint8 bytes; 1.2x is allowed for the two-row coupling)
+            kernel's time (they move the same fp32 bytes and half the uint8 bytes; 1.2x is allowed for the two-row coupling); and
+            savsr_video_gather_yuv420 / _quantize_yuv420 with each of the four colour ids (id 0 is the kernel of the _i420 entries)
   ceiling   upscale_video on preloaded I420 frames, I420 out (frames/s): what the CLI could reach
   cli       python -m savsr_amd.upscale on one synthetic video, PNG folder -> PNG folder against .y4m -> .y4m, A/B/A/B; files under
             --workdir (name the disk it lies on beside the figures: tmpfs or a scratch disk)
@@ -50,7 +51,7 @@ def leg_kernels(a):
     import ctypes as C
     import torch
     from savsr_amd import _lib
-    from savsr_amd.yuv import i420_bytes
+    from savsr_amd.yuv import COLOURS, i420_bytes
     lib = _lib.load()
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
@@ -70,6 +71,9 @@ def leg_kernels(a):
             "savsr_video_quantize_u8": lambda: lib.savsr_video_quantize_u8(x.data_ptr(), 7, 3, h, w, q8.data_ptr(), st),
             "savsr_video_quantize_i420": lambda: lib.savsr_video_quantize_i420(x.data_ptr(), 7, h, w, q420.data_ptr(), st),
         }
+        for c, name in enumerate(COLOURS):
+            fns[f"savsr_video_gather_yuv420 {name}"] = lambda c=c: lib.savsr_video_gather_yuv420(i420.data_ptr(), n, h, w, arr, 7, c, slots.data_ptr(), st)
+            fns[f"savsr_video_quantize_yuv420 {name}"] = lambda c=c: lib.savsr_video_quantize_yuv420(x.data_ptr(), 7, h, w, c, q420.data_ptr(), st)
         us = {k: [] for k in fns}
         for k, fn in fns.items():
             assert fn() == 0, k
@@ -85,12 +89,13 @@ def leg_kernels(a):
                 us[k].append(1e3 * e0.elapsed_time(e1) / a.iters)
         med = {k: statistics.median(v) for k, v in us.items()}
         for k in fns:
-            byte_side = 1.5 if k.endswith("i420") else 3.0
+            byte_side = 1.5 if "420" in k else 3.0
             nbytes = 7 * (4 * 3 + byte_side) * h * w
             row = {"kernel": k, "size": [h, w], "frames": 7, "us": round(med[k], 2), "us_per_frame": round(med[k] / 7, 3),
                    "mb": round(nbytes / 1e6, 2), "hbm_frac": round(nbytes / (med[k] * 1e-6) / HBM_BYTES_PER_S, 3)}
-            if k.endswith("i420"):
-                row["vs_rgb_kernel"] = round(med[k] / med[k.replace("i420", "u8")], 3)
+            if "420" in k:
+                row["vs_rgb_kernel"] = round(med[k] / med[k.split()[0].replace("yuv420", "u8").replace("i420", "u8")], 3)
+            row["us_rounds"] = [round(v, 2) for v in us[k]]          # (the spread between the rounds of this run)
             rows.append(row)
     return {"kernels": rows, "rounds": a.rounds, "iters": a.iters, "timing": "HIP events around `iters` back-to-back launches (launch rate included)"}
 
