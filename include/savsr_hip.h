@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 37
+#define SAVSR_ABI_VERSION 38
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -488,6 +488,29 @@ int savsr_video_quantize_yuv420(const float* in, int n, int H, int W, int colour
 int savsr_video_pair_sad_u8(const uint8_t* frames, int n_frames, int c, int h, int w, int64_t* sad_out, void* stream);
 int savsr_video_pair_sad_i420(const uint8_t* frames, int n_frames, int h, int w, int64_t* sad_out, void* stream);
 int savsr_video_pair_sad_f32(const float* frames, int n_frames, int c, int h, int w, int64_t* sad_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 38) 10- and 12-bit 4:2:0 (yuv.hip, scene.hip; depth / out_depth of SAVSR.upscale_video, --out-depth of python -m savsr_amd.upscale,
+ * DESIGN.md section 1).  A frame is the I420 frame above with every sample a little-endian 16-bit word, as it lies in a Y4M file tagged
+ * C420p10 / C420p12: 2 * (h * w + 2 * ch * cw) bytes, frames back to back; `frames` / `out` stay byte pointers and must be 2-byte aligned
+ * (an odd one is SAVSR_E_ARG).  depth = 10 or 12; colour = SAVSR_YUV_BT601 or SAVSR_YUV_BT709: high depth is defined for limited range
+ * only (a sample is the 8-bit one times k = 2^(depth - 8); full range scales by 2^depth - 1 and has no definition here).  Anything else is
+ * SAVSR_E_ARG + savsr_last_error(), before the device is touched.  The entries only enqueue, allocate nothing and are capturable;
+ * savsr_amd/yuv.py (`i420_to_rgb` / `rgb_to_i420` with depth=) and scenes.py (`pair_sad` with depth=) restate them bit for bit.
+ * savsr_video_gather_yuv420_16:   savsr_video_gather_yuv420's slots and index list.  No tables: with c = float(coef / k) and
+ *                         o = float(offset / 255), Yt = y c_y, R = (Yt + v c_rv) + o_R, G = ((Yt + u c_gu) + v c_gv) + o_G,
+ *                         B = (Yt + u c_bu) + o_B in float32 without fused multiply-add, clamped to [0, 1]; a sample above
+ *                         2^depth - 1 reads as 2^depth - 1.  8-byte Y loads / 16-byte stores when w % 4 == 0, frames 8-byte and out
+ *                         16-byte aligned; 16-bit loads otherwise.
+ * savsr_video_quantize_yuv420_16: savsr_video_quantize_yuv420's float32 value of every sample times k (exact), then rintf (half to even);
+ *                         Y in 16 k .. 235 k, chroma in 16 k .. 240 k, no clip.  16-byte loads / 8-byte Y stores when W % 4 == 0, in
+ *                         16-byte and out 8-byte aligned; 16-bit stores otherwise.
+ * savsr_video_pair_sad_i420_16:   savsr_video_pair_sad_i420 on the Y samples' 8 most significant bits, min(s, 2^depth - 1) >> (depth - 8):
+ *                         the scores have the 8-bit scale, so a 10-bit video whose samples are an 8-bit video's x 4 gives that video's. */
+int savsr_video_gather_yuv420_16(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, int colour, int depth, float* out,
+                                 void* stream);
+int savsr_video_quantize_yuv420_16(const float* in, int n, int H, int W, int colour, int depth, uint8_t* out, void* stream);
+int savsr_video_pair_sad_i420_16(const uint8_t* frames, int n_frames, int h, int w, int depth, int64_t* sad_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 33) Geometric self-ensemble (ensemble.hip; SAVSR.set_self_ensemble).  Variant k = 0 .. 7: fw = k & 1 flips

@@ -278,7 +278,8 @@ class SAVSR(nn.Module):
                                               ensemble=self.self_ensemble)
 
     def upscale_video(self, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
-                      size=None, cuts=None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None) -> torch.Tensor:
+                      size=None, cuts=None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None, depth: int = 8,
+                      out_depth: Optional[int] = None) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -292,6 +293,11 @@ class SAVSR(nn.Module):
         out_colour: that of I420 output; None = the same as colour.  The two sides are independent (the network works in RGB), so
         colour="bt601", out_colour="bt709" also converts an SD source into what an HD player expects.  colour goes with
         pixel_format="i420" and out_colour with out="i420".
+        depth: the bit depth of I420 input, 8, 10 or 12.  10 and 12: frames are [N, 2 * i420_bytes(h, w)] uint8, every sample a
+        little-endian 16-bit word (Y4M's C420p10 / C420p12), from a 2-byte aligned base pointer.  out_depth: that of I420 output;
+        None = the same as depth (8 for RGB input).  The two are independent: depth=8, out_depth=10 keeps the two bits of the fp32
+        result that the 8-bit rounding throws away, which is what a 10-bit HEVC / AV1 encoder wants.  10 and 12 bits are defined for
+        the limited-range colour spaces (bt601, bt709) only.
         cuts: None (one scene), a strictly increasing list of frame indices 0 < k < N (frame k starts a new scene), or "auto" (found on
         the GPU: savsr_amd.detect_cuts with scene_threshold, in per cent of the largest possible frame change; the default is ffmpeg
         scdet's and is not validated on real footage).  Windows stop at cuts: the result is, bit for bit, upscale_video on every scene
@@ -299,7 +305,7 @@ class SAVSR(nn.Module):
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
-        return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold, colour, out_colour)
+        return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold, colour, out_colour, depth, out_depth)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

@@ -7,6 +7,8 @@
 //   I420 frames        the Y plane only                             S = h * w
 //   fp32 CHW frames    every value after savsr_video_quantize_u8's  S = c * h * w
 //                      rule (clamp(0, 1) * 255.0f, rintf; NaN -> 0)
+//   10- / 12-bit I420  the Y plane only, every 16-bit sample as its     S = h * w
+//   (ABI 38)           8 most significant bits: min(s, 2^d - 1) >> (d - 8)
 #include "common.hpp"
 
 #include <cstdint>
@@ -135,6 +137,61 @@ __global__ __launch_bounds__(SAD_THREADS) void pair_sad_f32_kernel(const float* 
     block_add(acc, sad + blockIdx.y);
 }
 
+// |a.lo - b.lo| + |a.hi - b.hi| + acc over the two 16-bit halves of a dword: one v_sad_u16
+__device__ __forceinline__ uint32_t sad2(uint32_t a, uint32_t b, uint32_t acc) {
+#if __has_builtin(__builtin_amdgcn_sad_u16)
+    return __builtin_amdgcn_sad_u16(a, b, acc);
+#else
+    return acc + absdiff(a & 0xffffu, b & 0xffffu) + absdiff(a >> 16, b >> 16);
+#endif
+}
+
+// Two 16-bit samples of a dword -> their 8 most significant bits of `d`, each in its half: min(s, top) >> shift.
+__device__ __forceinline__ uint32_t msb8x2(uint32_t x, uint32_t top, int shift) {
+    return (min(x & 0xffffu, top) >> shift) | ((min(x >> 16, top) >> shift) << 16);
+}
+
+// High-depth frames `stride` bytes apart, the first `len` 16-bit samples of each compared (the Y plane); pair blockIdx.y = frames (k, k + 1).
+// VEC: frames and stride 16-byte aligned: 16-byte loads (8 samples) from both frames over len / 8 chunks, the len % 8 samples left over by
+// workgroup 0's first lanes.  Otherwise a sample per lane and iteration (any 2-byte aligned base, any size).
+template <bool VEC>
+__global__ __launch_bounds__(SAD_THREADS) void pair_sad_u16_kernel(const uint8_t* __restrict__ frames, long long stride, long long len, uint32_t top,
+                                                                   int shift, unsigned long long* __restrict__ sad) {
+    const uint8_t* fa = frames + (long long)blockIdx.y * stride;
+    const uint16_t* a = reinterpret_cast<const uint16_t*>(fa);
+    const uint16_t* b = reinterpret_cast<const uint16_t*>(fa + stride);
+    uint32_t acc = 0;
+    if (VEC) {
+        const long long nchunk = len >> 3;
+        const long long c0 = (long long)blockIdx.x * (SAD_THREADS * SAD_VEC_ITERS) + threadIdx.x;
+        u32x4 x[SAD_VEC_ITERS], y[SAD_VEC_ITERS];
+#pragma unroll
+        for (int it = 0; it < SAD_VEC_ITERS; ++it) {
+            const long long ch = c0 + it * SAD_THREADS;
+            x[it] = y[it] = u32x4{0u, 0u, 0u, 0u};
+            if (ch < nchunk) {
+                x[it] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a) + ch);
+                y[it] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(b) + ch);
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < SAD_VEC_ITERS; ++it) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc = sad2(msb8x2(x[it][e], top, shift), msb8x2(y[it][e], top, shift), acc);
+        }
+        const long long t = (nchunk << 3) + threadIdx.x;
+        if (blockIdx.x == 0 && threadIdx.x < 8 && t < len) acc += absdiff(min((uint32_t)a[t], top) >> shift, min((uint32_t)b[t], top) >> shift);
+    } else {
+        const long long i0 = (long long)blockIdx.x * (SAD_THREADS * SAD_ONE_ITERS) + threadIdx.x;
+#pragma unroll 4
+        for (int it = 0; it < SAD_ONE_ITERS; ++it) {
+            const long long i = i0 + it * SAD_THREADS;
+            if (i < len) acc += absdiff(min((uint32_t)a[i], top) >> shift, min((uint32_t)b[i], top) >> shift);
+        }
+    }
+    block_add(acc, sad + blockIdx.y);
+}
+
 inline unsigned sad_blocks(long long units, int per_thread) {
     const long long per_block = (long long)SAD_THREADS * per_thread;
     const long long nb = (units + per_block - 1) / per_block;
@@ -206,6 +263,34 @@ extern "C" int savsr_video_pair_sad_f32(const float* frames, int n_frames, int c
         if (vec) hipLaunchKernelGGL((pair_sad_f32_kernel<true>), dim3(gx, np), dim3(SAD_THREADS), 0, st, f, nfl, s);
         else hipLaunchKernelGGL((pair_sad_f32_kernel<false>), dim3(gx, np), dim3(SAD_THREADS), 0, st, f, nfl, s);
         if (int rc = check_launch("pair_sad_f32_kernel")) return rc;
+    }
+    return 0;
+}
+
+// ABI 38: 10- / 12-bit I420 frames (little-endian 16-bit samples): the Y plane's samples as their 8 most significant bits, so the scores
+// have savsr_video_pair_sad_i420's scale.
+extern "C" int savsr_video_pair_sad_i420_16(const uint8_t* frames, int n_frames, int h, int w, int depth, int64_t* sad_out, void* stream) {
+    if (!frames || (!sad_out && n_frames > 1)) return fail_arg("video_pair_sad_i420_16: null pointer");
+    if (h < 1 || w < 1 || n_frames < 1) return fail_arg("video_pair_sad_i420_16: h, w, n_frames >= 1");
+    if (depth != 10 && depth != 12) return fail_arg("video_pair_sad_i420_16: depth 10 or 12 (8 bits: savsr_video_pair_sad_i420)");
+    if (reinterpret_cast<uintptr_t>(frames) & 1) return fail_arg("video_pair_sad_i420_16: frames must be 2-byte aligned (16-bit samples)");
+    if (reinterpret_cast<uintptr_t>(sad_out) & 7) return fail_arg("video_pair_sad_i420_16: sad_out must be 8-byte aligned");
+    const int n_pairs = n_frames - 1;
+    if (n_pairs == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = zero_scores(sad_out, n_pairs, st, "video_pair_sad_i420_16")) return rc;
+    const long long ch = (h + 1) / 2, cw = (w + 1) / 2;
+    const long long len = (long long)h * w, stride = 2 * (len + 2 * ch * cw);
+    const bool vec = stride % 16 == 0 && (reinterpret_cast<uintptr_t>(frames) & 15) == 0 && len >= 8;
+    const unsigned gx = vec ? sad_blocks(len >> 3, SAD_VEC_ITERS) : sad_blocks(len, SAD_ONE_ITERS);
+    const uint32_t top = (1u << depth) - 1u;
+    for (int p0 = 0; p0 < n_pairs; p0 += SAD_MAX_PAIRS_Y) {
+        const int np = n_pairs - p0 < SAD_MAX_PAIRS_Y ? n_pairs - p0 : SAD_MAX_PAIRS_Y;
+        const uint8_t* f = frames + (long long)p0 * stride;
+        unsigned long long* s = reinterpret_cast<unsigned long long*>(sad_out) + p0;
+        if (vec) hipLaunchKernelGGL((pair_sad_u16_kernel<true>), dim3(gx, np), dim3(SAD_THREADS), 0, st, f, stride, len, top, depth - 8, s);
+        else hipLaunchKernelGGL((pair_sad_u16_kernel<false>), dim3(gx, np), dim3(SAD_THREADS), 0, st, f, stride, len, top, depth - 8, s);
+        if (int rc = check_launch("pair_sad_u16_kernel")) return rc;
     }
     return 0;
 }

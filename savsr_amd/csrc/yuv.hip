@@ -321,6 +321,193 @@ int quantize_yuv420(const char* what, const float* in, int n, int H, int W, int 
     return check_launch("quantize_i420_kernel");
 }
 
+
+// ---- 10 and 12 bits (ABI 38) -----------------------------------------------------------------------------------------------------------
+// A frame is the 8-bit frame's planes with every sample a little-endian 16-bit word (Y4M's C420p10 / C420p12): fb = 2 * i420_bytes.  Limited
+// range only (colour spaces 0 and 1): a sample is the 8-bit one times k = 2^(d - 8), so the constants are the 8-bit ones scaled by a power
+// of two.  yuv.py's "High depth" is the specification, bit for bit.  No LDS tables: the input is arithmetic, not a lookup.
+enum { N_COLOURS_16 = 2, N_DEPTHS_16 = 2 };      // colour spaces 0, 1; depths 10, 12
+
+// to_rgb_coefficients: c = float32(coef / k), o = float32(offset / 255) -- constant expressions, evaluated in IEEE double as numpy does.
+struct ToRgb16 { float y, rv, gu, gv, bu, o_r, o_g, o_b; };
+constexpr ToRgb16 make_to_rgb16(const YuvMatrix& m, double k) {
+    return ToRgb16{static_cast<float>(m.y / k), static_cast<float>(m.rv / k), static_cast<float>(m.gu / k), static_cast<float>(m.gv / k),
+                   static_cast<float>(m.bu / k), static_cast<float>(m.off_r / 255.0), static_cast<float>(m.off_g / 255.0),
+                   static_cast<float>(m.off_b / 255.0)};
+}
+struct ToRgb16All { ToRgb16 c[N_COLOURS_16][N_DEPTHS_16]; };
+__constant__ ToRgb16All kToRgb16 = {{{make_to_rgb16(kYuv.m[0], 4.0), make_to_rgb16(kYuv.m[0], 16.0)},
+                                     {make_to_rgb16(kYuv.m[1], 4.0), make_to_rgb16(kYuv.m[1], 16.0)}}};
+
+// One pixel from its three samples (already limited to 2^d - 1):  Yt = y c_y,  R = (Yt + v c_rv) + o_R,  G = ((Yt + u c_gu) + v c_gv) + o_G,
+// B = (Yt + u c_bu) + o_B, every product and sum rounded to float32 (contraction is off).
+__device__ __forceinline__ void put_rgb16(const ToRgb16& c, uint32_t y, uint32_t u, uint32_t v, float& r, float& g, float& b) {
+    const float fy = (float)y, fu = (float)u, fv = (float)v;
+    const float yt = fy * c.y;
+    r = clamp01((yt + fv * c.rv) + c.o_r);
+    g = clamp01(((yt + fu * c.gu) + fv * c.gv) + c.o_g);
+    b = clamp01((yt + fu * c.bu) + c.o_b);
+}
+
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// High-depth frames [N][fb] -> fp32 planar RGB slots [n][3][h][w], slot k = frame idx.f[k]; a sample above top = 2^d - 1 reads as top.  A
+// thread owns 2 rows so that a chroma sample is read once.  VEC: 2 rows x 4 pixels -- 8 bytes of Y per row and 4 + 4 chroma bytes in, one
+// float4 per plane row out (w % 4 == 0, 8-byte aligned frames, 16-byte aligned out: then fb, every Y row and the chroma planes' rows keep
+// that alignment); otherwise 2 x 2 pixels with 16-bit loads and scalar stores (any 2-byte aligned frames).  ci, di: the row of kToRgb16.
+template <bool VEC>
+__global__ __launch_bounds__(256) void gather_i420_16_kernel(const uint8_t* __restrict__ src, int h, int w, long long fb, YuvIdx idx, int ci, int di,
+                                                             uint32_t top, float* __restrict__ out) {
+    const ToRgb16 c = kToRgb16.c[ci][di];
+    const int k = blockIdx.y;
+    const long long npx = (long long)h * w;
+    const int ch = (h + 1) / 2, cw = (w + 1) / 2;
+    const uint16_t* fy = reinterpret_cast<const uint16_t*>(src + (long long)idx.f[k] * fb);
+    const uint16_t* fu = fy + npx;
+    const uint16_t* fv = fu + (long long)ch * cw;
+    float* o = out + (long long)k * 3 * npx;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const int wq = w / 4;
+        if (g >= (long long)ch * wq) return;
+        const int cy = (int)(g / wq), x0 = (int)(g % wq) * 4;
+        const long long coff = (long long)cy * cw + x0 / 2;
+        const uint32_t uu = *reinterpret_cast<const uint32_t*>(fu + coff);
+        const uint32_t vv = *reinterpret_cast<const uint32_t*>(fv + coff);
+        uint32_t us[2], vs[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            us[j] = min((uu >> (16 * j)) & 0xffffu, top);
+            vs[j] = min((vv >> (16 * j)) & 0xffffu, top);
+        }
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            const int y = 2 * cy + dy;
+            if (y >= h) break;
+            const long long p = (long long)y * w + x0;
+            const u32x2 yy = *reinterpret_cast<const u32x2*>(fy + p);
+            f32x4 r, gg, b;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float pr, pg, pb;
+                put_rgb16(c, min((yy[e >> 1] >> (16 * (e & 1))) & 0xffffu, top), us[e >> 1], vs[e >> 1], pr, pg, pb);
+                r[e] = pr; gg[e] = pg; b[e] = pb;
+            }
+            *reinterpret_cast<f32x4*>(o + p) = r;
+            *reinterpret_cast<f32x4*>(o + npx + p) = gg;
+            *reinterpret_cast<f32x4*>(o + 2 * npx + p) = b;
+        }
+    } else {
+        if (g >= (long long)ch * cw) return;
+        const int cy = (int)(g / cw), cx = (int)(g % cw);
+        const uint32_t u = min((uint32_t)fu[(long long)cy * cw + cx], top), v = min((uint32_t)fv[(long long)cy * cw + cx], top);
+        for (int dy = 0; dy < 2 && 2 * cy + dy < h; ++dy) {
+            for (int dx = 0; dx < 2 && 2 * cx + dx < w; ++dx) {
+                const long long p = (long long)(2 * cy + dy) * w + 2 * cx + dx;
+                float pr, pg, pb;
+                put_rgb16(c, min((uint32_t)fy[p], top), u, v, pr, pg, pb);
+                o[p] = pr; o[npx + p] = pg; o[2 * npx + p] = pb;
+            }
+        }
+    }
+}
+
+// rint(row * k): the 8-bit row's float32 value (yuv.py: _row) times k = 2^(d - 8), exact, then half to even.  Limited range stays inside
+// 16 k .. 240 k by itself: no clip.
+__device__ __forceinline__ uint32_t row3_u16(const float (&kk)[3], float off, float k, float r, float g, float b) {
+    return (uint32_t)rintf((((r * kk[0] + g * kk[1]) + b * kk[2]) + off) * k);
+}
+
+// fp32 planar RGB [n][3][H][W] -> high-depth frames [n][fb], quantize_i420_kernel's arithmetic with the rows scaled by k before the rounding.
+// VEC: a thread owns 2 rows x 4 pixels -- one float4 per plane row in (nontemporal: the result is read once), 8 bytes of Y per row and
+// 4 + 4 chroma bytes out (W % 4 == 0, 16-byte aligned in, 8-byte aligned out); otherwise 2 x 2 pixels with 16-bit stores.  C: the colour
+// space (0 or 1), a template argument so that its rows stay immediates.
+template <bool VEC, int C>
+__global__ __launch_bounds__(256) void quantize_i420_16_kernel(const float* __restrict__ in, int H, int W, long long fb, float k,
+                                                               uint8_t* __restrict__ out) {
+    constexpr YuvMatrix m = kYuv.m[C];
+    static_assert(!m.full, "high depth is defined for limited range only");
+    const int f = blockIdx.y;
+    const long long npx = (long long)H * W;
+    const int ch = (H + 1) / 2, cw = (W + 1) / 2;
+    const float* src = in + (long long)f * 3 * npx;
+    uint16_t* fy = reinterpret_cast<uint16_t*>(out + (long long)f * fb);
+    uint16_t* fu = fy + npx;
+    uint16_t* fv = fu + (long long)ch * cw;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const int wq = W / 4;
+        if (g >= (long long)ch * wq) return;
+        const int cy = (int)(g / wq), x0 = (int)(g % wq) * 4;
+        const bool two = 2 * cy + 1 < H;
+        f32x4 px[2][3];
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            if (dy == 1 && !two) break;
+            const long long p = (long long)(2 * cy + dy) * W + x0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + c * npx + p));
+#pragma unroll
+                for (int e = 0; e < 4; ++e) px[dy][c][e] = clamp01(x[e]);
+            }
+            u32x2 yy = {0u, 0u};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) yy[e >> 1] |= row3_u16(m.ky, m.oy, k, px[dy][0][e], px[dy][1][e], px[dy][2][e]) << (16 * (e & 1));
+            *reinterpret_cast<u32x2*>(fy + p) = yy;
+        }
+        uint32_t uu = 0u, vv = 0u;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float mean[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float top = px[0][c][2 * j] + px[0][c][2 * j + 1];
+                mean[c] = two ? (top + (px[1][c][2 * j] + px[1][c][2 * j + 1])) * 0.25f : top * 0.5f;
+            }
+            uu |= row3_u16(m.kcb, m.oc, k, mean[0], mean[1], mean[2]) << (16 * j);
+            vv |= row3_u16(m.kcr, m.oc, k, mean[0], mean[1], mean[2]) << (16 * j);
+        }
+        const long long coff = (long long)cy * cw + x0 / 2;
+        *reinterpret_cast<uint32_t*>(fu + coff) = uu;
+        *reinterpret_cast<uint32_t*>(fv + coff) = vv;
+    } else {
+        if (g >= (long long)ch * cw) return;
+        const int cy = (int)(g / cw), cx = (int)(g % cw);
+        const bool two_y = 2 * cy + 1 < H, two_x = 2 * cx + 1 < W;
+        float q[2][2][3];
+        for (int dy = 0; dy < 2; ++dy) {
+            for (int dx = 0; dx < 2; ++dx) {
+                if ((dy && !two_y) || (dx && !two_x)) continue;
+                const long long p = (long long)(2 * cy + dy) * W + 2 * cx + dx;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) q[dy][dx][c] = clamp01(src[c * npx + p]);
+                fy[p] = (uint16_t)row3_u16(m.ky, m.oy, k, q[dy][dx][0], q[dy][dx][1], q[dy][dx][2]);
+            }
+        }
+        float mean[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (two_x && two_y) mean[c] = ((q[0][0][c] + q[0][1][c]) + (q[1][0][c] + q[1][1][c])) * 0.25f;
+            else if (two_x) mean[c] = (q[0][0][c] + q[0][1][c]) * 0.5f;
+            else if (two_y) mean[c] = (q[0][0][c] + q[1][0][c]) * 0.5f;
+            else mean[c] = q[0][0][c];
+        }
+        fu[(long long)cy * cw + cx] = (uint16_t)row3_u16(m.kcb, m.oc, k, mean[0], mean[1], mean[2]);
+        fv[(long long)cy * cw + cx] = (uint16_t)row3_u16(m.kcr, m.oc, k, mean[0], mean[1], mean[2]);
+    }
+}
+
+// depth 10 / 12 and a limited-range colour space, or the refusal that names the rule
+int check_depth16(int colour, int depth, const char* what) {
+    if (depth != 10 && depth != 12) { set_error("invalid argument: %s: depth %d (10 or 12; 8 bits: the entries without _16)", what, depth); return SAVSR_E_ARG; }
+    if (colour < 0 || colour >= N_COLOURS_16) {
+        set_error("invalid argument: %s: colour %d (0 .. %d: 10 and 12 bits are defined for limited range only)", what, colour, N_COLOURS_16 - 1);
+        return SAVSR_E_ARG;
+    }
+    return 0;
+}
+
 }  // namespace
 }  // namespace savsr
 
@@ -342,4 +529,50 @@ extern "C" int savsr_video_gather_i420(const uint8_t* frames, int n_frames, int 
 
 extern "C" int savsr_video_quantize_i420(const float* in, int n, int H, int W, uint8_t* out, void* stream) {
     return quantize_yuv420("video_quantize_i420", in, n, H, W, SAVSR_YUV_BT601, out, stream);
+}
+
+// ABI 38: 10- and 12-bit frames, little-endian 16-bit samples in the I420 plane order.
+extern "C" int savsr_video_gather_yuv420_16(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, int colour, int depth,
+                                            float* out, void* stream) {
+    const char* what = "video_gather_yuv420_16";
+    if (!frames || !out) return fail(what, "null pointer");
+    if (h < 1 || w < 1 || n_frames < 1) return fail(what, "h, w, n_frames >= 1");
+    if (int rc = check_depth16(colour, depth, what)) return rc;
+    if (reinterpret_cast<uintptr_t>(frames) & 1) return fail(what, "frames must be 2-byte aligned (16-bit samples)");
+    if (reinterpret_cast<uintptr_t>(out) & 3) return fail(what, "out must be 4-byte aligned");
+    YuvIdx gi;
+    if (int rc = load_idx(idx, n_idx, n_frames, &gi, what)) return rc;
+    const bool vec = w % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    const long long units = (long long)((h + 1) / 2) * (vec ? w / 4 : (w + 1) / 2);
+    const dim3 grid(blocks_for(units), n_idx);
+    const long long fb = 2 * i420_bytes(h, w);
+    const int di = depth == 10 ? 0 : 1;
+    const uint32_t top = (1u << depth) - 1u;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (vec) hipLaunchKernelGGL((gather_i420_16_kernel<true>), grid, dim3(256), 0, st, frames, h, w, fb, gi, colour, di, top, out);
+    else hipLaunchKernelGGL((gather_i420_16_kernel<false>), grid, dim3(256), 0, st, frames, h, w, fb, gi, colour, di, top, out);
+    return check_launch("gather_i420_16_kernel");
+}
+
+extern "C" int savsr_video_quantize_yuv420_16(const float* in, int n, int H, int W, int colour, int depth, uint8_t* out, void* stream) {
+    const char* what = "video_quantize_yuv420_16";
+    if (!in || !out) return fail(what, "null pointer");
+    if (n < 1 || n > 65535 || H < 1 || W < 1) return fail(what, "n in 1 .. 65535, H, W >= 1");
+    if (int rc = check_depth16(colour, depth, what)) return rc;
+    if (reinterpret_cast<uintptr_t>(out) & 1) return fail(what, "out must be 2-byte aligned (16-bit samples)");
+    if (reinterpret_cast<uintptr_t>(in) & 3) return fail(what, "in must be 4-byte aligned");
+    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0;
+    const long long units = (long long)((H + 1) / 2) * (vec ? W / 4 : (W + 1) / 2);
+    const dim3 grid(blocks_for(units), n);
+    const long long fb = 2 * i420_bytes(H, W);
+    const float k = (float)(1 << (depth - 8));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (colour == 0) {
+        if (vec) hipLaunchKernelGGL((quantize_i420_16_kernel<true, 0>), grid, dim3(256), 0, st, in, H, W, fb, k, out);
+        else hipLaunchKernelGGL((quantize_i420_16_kernel<false, 0>), grid, dim3(256), 0, st, in, H, W, fb, k, out);
+    } else {
+        if (vec) hipLaunchKernelGGL((quantize_i420_16_kernel<true, 1>), grid, dim3(256), 0, st, in, H, W, fb, k, out);
+        else hipLaunchKernelGGL((quantize_i420_16_kernel<false, 1>), grid, dim3(256), 0, st, in, H, W, fb, k, out);
+    }
+    return check_launch("quantize_i420_16_kernel");
 }

@@ -797,7 +797,8 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         return outs
 
     def forward_video(self, frames: torch.Tensor, windows: List[List[int]], scale, out_u8: bool = False, ensemble: bool = False,
-                      i420: Optional[Tuple[int, int]] = None, out_i420: bool = False, colour: int = 0, out_colour: int = 0) -> torch.Tensor:
+                      i420: Optional[Tuple[int, int]] = None, out_i420: bool = False, colour: int = 0, out_colour: int = 0, depth: int = 8,
+                      out_depth: int = 8) -> torch.Tensor:
         """The sequence path (SAVSR.upscale_video): frames [N, h, w, c] uint8 or [N, c, h, w] fp32 on the device, windows[i] = the
         num_frame frame indices of output frame i in clip order (harness.window_indices) -> [len(windows), c, H, W] fp32, or
         [len(windows), H, W, c] uint8 (out_u8: tensor2img(x, rgb2bgr=False) per frame, savsr_video_quantize_u8).
@@ -809,15 +810,22 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         the uint8 gather runs; out_i420: the result is [len(windows), i420_bytes(H, W)] uint8, quantised by savsr_video_quantize_yuv420 where
         the uint8 quantisation runs.  colour / out_colour: the colour space ids (positions in yuv.COLOURS) of the I420 input / output.  With
         the ensemble, I420 frames are converted once to fp32 planar RGB (the same gather with the identity list) and take the fp32 path,
-        and an I420 result is the fp32 merge followed by the quantisation."""
+        and an I420 result is the fp32 merge followed by the quantisation.  depth / out_depth = 10, 12: the I420 frames in / out hold 16-bit
+        samples ([N, 2 * i420_bytes] uint8, limited range only); savsr_video_gather_yuv420_16 / savsr_video_quantize_yuv420_16 run where the
+        8-bit entries do, and nothing else changes."""
         if out_u8 and out_i420:
             raise ValueError("one output kind: uint8 or I420")
+        for what, d, on, cs in (("depth", depth, i420 is not None, colour), ("out_depth", out_depth, out_i420, out_colour)):
+            if d not in (8, 10, 12) or (d != 8 and not on):
+                raise ValueError(f"{what} = {d!r}: 8, 10 or 12, and 10 / 12 with I420 frames on that side only")
+            if d != 8 and cs not in (0, 1):
+                raise ValueError(f"{what} = {d} with colour id {cs}: 10 and 12 bits are defined for limited range only ({COLOURS[0]}, {COLOURS[1]})")
         if not (0 <= colour < len(COLOURS) and 0 <= out_colour < len(COLOURS)):
             raise ValueError(f"colour ids {colour}, {out_colour}: 0 .. {len(COLOURS) - 1} ({', '.join(COLOURS)})")
         if i420 is not None:
             h, w = (int(v) for v in i420)
-            if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != i420_bytes(h, w):
-                raise ValueError(f"I420 frames of {h} x {w} are [N, {i420_bytes(h, w)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+            if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != i420_bytes(h, w, depth):
+                raise ValueError(f"I420 frames of {h} x {w} are [N, {i420_bytes(h, w, depth)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
             u8, N, c = True, int(frames.shape[0]), 3
         else:
             u8, N, c, h, w = _frames_layout(frames)
@@ -831,7 +839,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         H, W = get_hw(h, w, scale)
         n = len(windows)
         if out_i420:
-            out = torch.empty(n, i420_bytes(H, W), device=self.dev, dtype=torch.uint8)
+            out = torch.empty(n, i420_bytes(H, W, out_depth), device=self.dev, dtype=torch.uint8)
         else:
             out = (torch.empty(n, H, W, c, device=self.dev, dtype=torch.uint8) if out_u8 else
                    torch.empty(n, c, H, W, device=self.dev, dtype=torch.float32))
@@ -839,7 +847,11 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             return out
         if T > _lib.VIDEO_MAX_SLOTS:
             raise ValueError(f"num_frame = {T}: the window gather takes at most {_lib.VIDEO_MAX_SLOTS} frames per launch")
-        if i420 is not None:
+        if i420 is not None and depth != 8:
+            def gather(idx, dst, st):
+                _lib.check(self.lib.savsr_video_gather_yuv420_16(frames.data_ptr(), N, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), colour,
+                                                                 depth, dst.data_ptr(), st), "savsr_video_gather_yuv420_16")
+        elif i420 is not None:
             def gather(idx, dst, st):
                 _lib.check(self.lib.savsr_video_gather_yuv420(frames.data_ptr(), N, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), colour,
                                                               dst.data_ptr(), st), "savsr_video_gather_yuv420")
@@ -852,7 +864,10 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         def quantize(src, dst, st):
             for a in range(0, int(src.shape[0]), 65535):          # (the entries take 1 .. 65535 frames)
                 nb = min(65535, int(src.shape[0]) - a)
-                if out_i420:
+                if out_i420 and out_depth != 8:
+                    _lib.check(self.lib.savsr_video_quantize_yuv420_16(src[a:a + nb].data_ptr(), nb, H, W, out_colour, out_depth,
+                                                                       dst[a:a + nb].data_ptr(), st), "savsr_video_quantize_yuv420_16")
+                elif out_i420:
                     _lib.check(self.lib.savsr_video_quantize_yuv420(src[a:a + nb].data_ptr(), nb, H, W, out_colour, dst[a:a + nb].data_ptr(), st),
                                "savsr_video_quantize_yuv420")
                 else:

@@ -7,7 +7,7 @@ a + window_indices(i - a, b - a, num_frame, mode), mode = the call's padding if 
 the segments.
 
 The detector: per pair of consecutive frames the sum of absolute differences of their 8-bit samples (`pair_sad`, the specification of
-savsr_video_pair_sad_u8 / _i420 / _f32 in csrc/scene.hip), then ffmpeg scdet's rule in exact arithmetic (`cuts_from_sad`).
+savsr_video_pair_sad_u8 / _i420 / _i420_16 / _f32 in csrc/scene.hip), then ffmpeg scdet's rule in exact arithmetic (`cuts_from_sad`).
 
 `ScenePlan` is the streaming form's bookkeeping (VideoUpscaler with cuts): which frames can be returned, with which windows, and which
 past frames must be kept, when cuts and the end of the video are only known up to the last pushed frame.
@@ -24,7 +24,7 @@ import numpy as np
 
 from .harness import window_indices
 from .video import check_length, check_padding, check_pixel_format
-from .yuv import i420_bytes
+from .yuv import check_depth, i420_bytes, split_planes
 
 
 # ---- the detector --------------------------------------------------------------------------------------------------------------------
@@ -34,12 +34,18 @@ def quantize_u8(x: np.ndarray) -> np.ndarray:
     return np.rint(np.fmin(np.fmax(x, np.float32(0)), np.float32(1)) * np.float32(255)).astype(np.uint8)
 
 
-def _samples_of(frames, pixel_format: str, size) -> np.ndarray:
+def _samples_of(frames, pixel_format: str, size, depth: int = 8) -> np.ndarray:
     """[N, S] uint8: the samples the detector compares, frame by frame."""
     i420 = check_pixel_format(pixel_format, size)
     if hasattr(frames, "detach"):
         frames = frames.detach().cpu().numpy()
     frames = np.asarray(frames)
+    if depth != 8:
+        depth = check_depth(depth)
+        if not i420:
+            raise ValueError(f"depth = {depth} goes with pixel_format = 'i420': it is the bit depth of I420 input")
+        y = split_planes(frames, i420[0], i420[1], depth)[0]
+        return (np.minimum(y, np.uint16((1 << depth) - 1)) >> (depth - 8)).astype(np.uint8).reshape(y.shape[0], -1)
     if i420:
         h, w = i420
         if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != i420_bytes(h, w):
@@ -64,11 +70,12 @@ def sad_samples(shape: Sequence[int], pixel_format: str = "rgb", size=None) -> i
     return int(shape[1]) * int(shape[2]) * int(shape[3])
 
 
-def pair_sad(frames, pixel_format: str = "rgb", size=None) -> np.ndarray:
+def pair_sad(frames, pixel_format: str = "rgb", size=None, depth: int = 8) -> np.ndarray:
     """int64 [N - 1]: entry j is the sum of absolute differences of the 8-bit samples of frames j and j + 1.
     [N, h, w, c] uint8: every byte.  I420 ([N, i420_bytes(h, w)] uint8, size=(h, w)): the Y plane only.  [N, c, h, w] float: every value
-    after `quantize_u8`."""
-    s = _samples_of(frames, pixel_format, size).astype(np.int64)
+    after `quantize_u8`.  depth = 10, 12 (I420 frames of 16-bit samples, [N, 2 * i420_bytes(h, w)] uint8): the Y plane's samples as their 8
+    most significant bits, min(s, 2^depth - 1) >> (depth - 8), so the scores -- and with them the threshold -- keep the 8-bit scale."""
+    s = _samples_of(frames, pixel_format, size, depth).astype(np.int64)
     if s.shape[0] < 1:
         raise ValueError("the video has no frames")
     return np.abs(s[1:] - s[:-1]).sum(axis=1, dtype=np.int64)

@@ -7,6 +7,7 @@
     ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o - --scale 4 --checkpoint <net.pth> | ffmpeg -i - out.mp4
     python -m savsr_amd.upscale -i in.y4m -o out.y4m --scale 4 --checkpoint <net.pth> --cuts auto --cuts-out cuts.txt
     python -m savsr_amd.upscale -i sd.y4m -o hd.y4m --scale 4 --checkpoint <net.pth> --colour auto --out-colour auto
+    python -m savsr_amd.upscale -i in8.y4m -o out10.y4m --scale 4 --checkpoint <net.pth> --out-depth 10
 
 PNG folder: frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on
 the FrameStore pool (savsr_amd.io), pushed through VideoUpscaler in chunks (uint8 in, uint8 out: the windows, the network and the
@@ -26,6 +27,11 @@ tuned number) and takes the range from the input's XCOLORRANGE tag (limited with
 --colour auto --out-colour auto: the SD source is read as BT.601 and the HD result is written as the BT.709 a player will assume, at
 no extra cost and without another 8-bit rounding (the network works in RGB).  The output carries XCOLORRANGE when it is full range or
 when either flag was given.
+
+--out-depth: the bit depth of a Y4M output, 8, 10, 12 or same (the default: the input's; 8 for a PNG folder).  A 10- or 12-bit Y4M input
+(C420p10 / C420p12, what `ffmpeg -f yuv4mpegpipe` emits for a 10-bit source) is read as it is; its depth comes from the header.  8-bit in,
+--out-depth 10 costs nothing extra in the network and keeps the two bits the 8-bit rounding throws away (what HEVC / AV1 encoders take
+by default is yuv420p10).  10 and 12 bits go with limited range only: a full-range colour space on a high-depth side is refused.
 
 --cuts: edited footage.  Windows stop at scene cuts (every scene is upscaled as a video of its own, savsr_amd/scenes.py): auto finds
 them on the GPU as the frames arrive (--scene-threshold, per cent of the largest possible frame change; ffmpeg scdet's rule and default,
@@ -105,6 +111,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="colour space of a Y4M output (default same: the input's; bt601 for a PNG folder).  auto: the input's range and the matrix "
                         "players assume at the output size.  For SD -> HD give --colour auto --out-colour auto: an untagged HD stream is shown as "
                         "BT.709, so a BT.601 one has shifted colours")
+    p.add_argument("--out-depth", default=None, choices=["8", "10", "12", "same"],
+                   help="bit depth of a Y4M output (default same: the input's; 8 for a PNG folder).  10 / 12 write C420p10 / C420p12, limited range "
+                        "only; 8-bit in, 10 out keeps the precision the 8-bit rounding loses")
     p.add_argument("--cuts", default=None, metavar="auto|K,K,...|@FILE",
                    help="scene cuts (first frame of every new scene): auto = found on the GPU, a comma-separated list, or @FILE with one index "
                         "per line; windows stop at cuts")
@@ -164,6 +173,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--colour goes with a Y4M input (PNG frames are RGB)")
     if a.out_colour is not None and not a.y4m_out:
         p.error("--out-colour goes with a Y4M output (PNG frames are RGB)")
+    if a.out_depth is not None and not a.y4m_out:
+        p.error("--out-depth goes with a Y4M output (PNG frames are 8-bit RGB)")
+    a.out_depth = None if a.out_depth in (None, "same") else int(a.out_depth)          # (None: the input's)
     a.colour_flags = a.colour is not None or a.out_colour is not None       # (either given: the output is tagged, the summary names them)
     a.colour = a.colour or "bt601"
     a.out_colour = a.out_colour or "same"
@@ -320,14 +332,15 @@ def main(argv: Optional[List[str]] = None) -> int:
             if a.input != "-" and not os.path.isfile(a.input):
                 raise SystemExit(f"input file {a.input!r} does not exist")
             fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
-            reader = Y4MReader(fin)
-            h, w = reader.height, reader.width
+            reader = Y4MReader(fin, high_depth=True)
+            h, w, depth = reader.height, reader.width, reader.depth
             fps, interlace, aspect, in_range = reader.fps, reader.interlace, reader.aspect, reader.colour_range
             chunks = (torch.from_numpy(c) for c in reader.chunks(a.chunk))
         else:
             from .io import FrameStore
             store = FrameStore()
             h = w = None
+            depth = 8
             if a.y4m_out:                           # (the Y4M header needs the SR size before the first frame: the PNG's header gives it)
                 from PIL import Image
                 with Image.open(paths[0]) as im:
@@ -343,19 +356,25 @@ def main(argv: Optional[List[str]] = None) -> int:
         net = net.to(dev)
         hr = get_hw(h, w, a.scale) if a.y4m_out else None
         colour, out_colour = resolve_colours(a.colour, a.out_colour, (h, w) if a.y4m_in else None, hr, in_range)
+        out_depth = (depth if a.out_depth is None else a.out_depth) if a.y4m_out else None
+        from .video import check_depths
+        try:                                        # (before the output is opened: a full-range colour with 10 / 12 bits is refused)
+            check_depths(depth, out_depth, "i420" if a.y4m_in else "rgb", "i420" if a.y4m_out else "uint8", colour or "bt601", out_colour)
+        except ValueError as e:
+            raise SystemExit(f"--colour / --out-colour / --out-depth: {e}") from None
         if a.y4m_out:
             H, W = hr
             fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
             full = is_full_range(out_colour)
             tag = ("full" if full else "limited") if (full or a.colour_flags) else None
-            sink = Y4MSink(Y4MWriter(fout, W, H, fps, interlace, scaled_aspect(aspect, (h, w), (H, W)), tag), a.chunk + net.num_frame)
+            sink = Y4MSink(Y4MWriter(fout, W, H, fps, interlace, scaled_aspect(aspect, (h, w), (H, W)), tag, depth=out_depth), a.chunk + net.num_frame)
         else:
             sink = PngSink(a.output, None if paths is None else [os.path.basename(p) for p in paths],
                            a.writers or max(1, min(MAX_WRITERS, effective_cpus())))
         t0 = time.perf_counter()
         up = VideoUpscaler(net, a.scale, a.padding, out="i420" if a.y4m_out else "uint8", pixel_format="i420" if a.y4m_in else "rgb",
                            size=(h, w) if a.y4m_in else None, cuts=a.cuts, scene_threshold=a.scene_threshold, colour=colour or "bt601",
-                           out_colour=out_colour)
+                           out_colour=out_colour, depth=depth, out_depth=out_depth)
         done = 0
         try:
             for chunk in chunks:
@@ -376,6 +395,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                 f.writelines(f"{k}\n" for k in up.cuts)
     if a.colour_flags:
         scenes += f", colour {colour or 'rgb'} -> {out_colour or 'rgb'}"
+    if depth != 8 or (out_depth or 8) != 8:
+        scenes += f", {depth} -> {out_depth or 8} bits"
     print(f"upscaled {done} frames in {dt:.2f} s: {done / dt:.2f} frames/s{scenes}", file=sys.stderr if a.output == "-" else sys.stdout, flush=True)
     return 0
 

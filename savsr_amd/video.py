@@ -5,7 +5,9 @@ Output frame i is what the reference pipeline gives for it: the frame's window b
 clamp / x255 / round half to even (lbasicsr/utils/img_util.py:66-90) without the BGR swap.  The frames stay on the device: the
 windows are gathered there (savsr_video_gather_u8 / _f32) and the uint8 result is quantised there (savsr_video_quantize_u8), see
 HipEngine.forward_video.  pixel_format="i420" / out="i420": planar YUV 4:2:0 frames in / out (savsr_amd/yuv.py is the format and its
-numerics), converted on the device on either side of the network (savsr_video_gather_i420 / savsr_video_quantize_i420).
+numerics), converted on the device on either side of the network (savsr_video_gather_i420 / savsr_video_quantize_i420).  depth /
+out_depth = 10, 12: the frames hold little-endian 16-bit samples ([N, 2 * i420_bytes(h, w)] uint8, Y4M's C420p10 / C420p12;
+savsr_video_gather_yuv420_16 / savsr_video_quantize_yuv420_16), limited range only.
 
 cuts=[k, ...] / cuts="auto": the video is a sequence of scenes and every scene is treated as a video of its own (savsr_amd/scenes.py:
 windows stop at cuts); "auto" finds the cuts on the device (savsr_video_pair_sad_*, then scdet's rule on the host).  cuts=None runs
@@ -20,7 +22,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 import torch
 
 from .harness import window_indices
-from .yuv import check_colour, i420_bytes
+from .yuv import check_colour, check_depth, check_depth_colour, i420_bytes
 
 PADDING_MODES = ("replicate", "reflection", "reflection_circle", "circle")
 OUT_KINDS = ("float", "uint8", "i420")
@@ -110,8 +112,33 @@ def check_colours(colour, out_colour, pixel_format: str, out: str) -> Tuple[int,
     return cid, ocid
 
 
-def i420_layout(frames: torch.Tensor, size: Tuple[int, int], nch: int) -> int:
-    """N of an I420 video tensor: [N, i420_bytes(h, w)] uint8 (GPU or host); refuses anything else."""
+def check_depths(depth, out_depth, pixel_format: str, out: str, colour: str = "bt601", out_colour: Optional[str] = None) -> Tuple[int, int]:
+    """The bit depths (8, 10 or 12) of the I420 input and output.  `depth` goes with pixel_format = 'i420' and `out_depth` with
+    out = 'i420'; out_depth = None: the same as depth (8 for RGB input).  10 and 12 bits are defined for the limited-range colour
+    spaces only."""
+    d = check_depth(depth, "depth")
+    od = None if out_depth is None else check_depth(out_depth, "out_depth")
+    if d != 8 and pixel_format != "i420":
+        raise ValueError(f"depth = {d} goes with pixel_format = 'i420': it is the bit depth of I420 input (RGB frames carry theirs in their dtype)")
+    if od is not None and out != "i420":
+        raise ValueError(f"out_depth = {od} goes with out = 'i420': it is the bit depth of I420 output")
+    if od is None:
+        od = d if out == "i420" else 8
+    check_depth_colour(d, colour, "depth", "colour")
+    if out == "i420":
+        check_depth_colour(od, colour if out_colour is None else out_colour, "out_depth", "out_colour")
+    return d, od
+
+
+def check_sample_alignment(frames: torch.Tensor, depth: int) -> None:
+    """10- and 12-bit frames are read as 16-bit words: their base pointer must be 2-byte aligned (a frame's byte size is always even)."""
+    if depth > 8 and frames.numel() and frames.data_ptr() % 2:
+        raise ValueError(f"{depth}-bit I420 frames hold 16-bit samples: the base pointer {frames.data_ptr():#x} is not 2-byte aligned "
+                         f"(an odd storage offset of a uint8 view); copy the frames (.clone()) first")
+
+
+def i420_layout(frames: torch.Tensor, size: Tuple[int, int], nch: int, depth: int = 8) -> int:
+    """N of an I420 video tensor: [N, i420_bytes(h, w, depth)] uint8 (GPU or host); refuses anything else."""
     h, w = size
     if not isinstance(frames, torch.Tensor):
         raise TypeError(f"frames must be a torch.Tensor, got {type(frames).__name__}")
@@ -121,7 +148,11 @@ def i420_layout(frames: torch.Tensor, size: Tuple[int, int], nch: int) -> int:
         raise ValueError(f"I420 frames must be uint8, got {frames.dtype}")
     if frames.dim() != 2:
         raise ValueError(f"I420 frames must be [N, i420_bytes(h, w)] uint8, got {frames.dim()} dimensions")
-    if int(frames.shape[1]) != i420_bytes(h, w):
+    if depth != 8:
+        if int(frames.shape[1]) != i420_bytes(h, w, depth):
+            raise ValueError(f"{depth}-bit I420 frames of {h} x {w} have {i420_bytes(h, w, depth)} bytes (16-bit samples), got {int(frames.shape[1])}")
+        check_sample_alignment(frames, depth)
+    elif int(frames.shape[1]) != i420_bytes(h, w):
         raise ValueError(f"I420 frames of {h} x {w} have {i420_bytes(h, w)} bytes, got {int(frames.shape[1])}")
     return int(frames.shape[0])
 
@@ -161,14 +192,18 @@ def check_cuts_arg(cuts) -> None:
     check_cuts(cuts, None)
 
 
-def _sad_layout(frames: torch.Tensor, i420: Optional[Tuple[int, int]]) -> Tuple[int, int, int, int]:
+def _sad_layout(frames: torch.Tensor, i420: Optional[Tuple[int, int]], depth: int = 8) -> Tuple[int, int, int, int]:
     """(N, c, h, w) of the frames the detector compares (c = 0: I420); no network here, so any c in 1 .. 3 and any h, w >= 1."""
     if not isinstance(frames, torch.Tensor):
         raise TypeError(f"frames must be a torch.Tensor, got {type(frames).__name__}")
+    if depth != 8 and not i420:
+        raise ValueError(f"depth = {depth} goes with pixel_format = 'i420': it is the bit depth of I420 input (RGB frames carry theirs in their dtype)")
     if i420:
         h, w = i420
-        if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != i420_bytes(h, w):
-            raise ValueError(f"I420 frames of {h} x {w} are [N, {i420_bytes(h, w)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+        if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != i420_bytes(h, w, depth):
+            raise ValueError(f"{'' if depth == 8 else f'{depth}-bit '}I420 frames of {h} x {w} are [N, {i420_bytes(h, w, depth)}] uint8, "
+                             f"got {frames.dtype} {tuple(frames.shape)}")
+        check_sample_alignment(frames, depth)
         n, c = int(frames.shape[0]), 0
     else:
         if frames.dim() != 4:
@@ -190,17 +225,19 @@ def _sad_layout(frames: torch.Tensor, i420: Optional[Tuple[int, int]]) -> Tuple[
     return n, c, h, w
 
 
-def _pair_sad_device(frames: torch.Tensor, i420: Optional[Tuple[int, int]]) -> torch.Tensor:
+def _pair_sad_device(frames: torch.Tensor, i420: Optional[Tuple[int, int]], depth: int = 8) -> torch.Tensor:
     """savsr_video_pair_sad_* on frames already on the GPU: int64 [N - 1] there, enqueued on the current stream (no sync)."""
     from . import _lib
-    n, c, h, w = _sad_layout(frames, i420)
+    n, c, h, w = _sad_layout(frames, i420, depth)
     lib = _lib.load()
     u8 = frames.dtype == torch.uint8
     frames = frames.contiguous() if u8 else frames.to(torch.float32).contiguous()
     with torch.cuda.device(frames.device):
         sad = torch.empty(n - 1, dtype=torch.int64, device=frames.device)
         st = torch.cuda.current_stream().cuda_stream
-        if i420:
+        if i420 and depth != 8:
+            _lib.check(lib.savsr_video_pair_sad_i420_16(frames.data_ptr(), n, h, w, depth, sad.data_ptr(), st), "savsr_video_pair_sad_i420_16")
+        elif i420:
             _lib.check(lib.savsr_video_pair_sad_i420(frames.data_ptr(), n, h, w, sad.data_ptr(), st), "savsr_video_pair_sad_i420")
         elif u8:
             _lib.check(lib.savsr_video_pair_sad_u8(frames.data_ptr(), n, c, h, w, sad.data_ptr(), st), "savsr_video_pair_sad_u8")
@@ -217,39 +254,43 @@ def _sad_device(frames: torch.Tensor) -> torch.device:
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def pair_sad(frames: torch.Tensor, pixel_format: str = "rgb", size=None) -> torch.Tensor:
+def pair_sad(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8) -> torch.Tensor:
     """The scene detector's scores: int64 [N - 1] on the GPU, entry j = the sum of absolute differences of the 8-bit samples of frames j
     and j + 1 (savsr_amd.scenes.pair_sad is the specification).  frames as for SAVSR.upscale_video, with any c in 1 .. 3: [N, h, w, c]
     uint8 (GPU or host; every byte), [N, c, h, w] float on the GPU (every value after the uint8 output's quantisation), or with
-    pixel_format="i420", size=(h, w): [N, i420_bytes(h, w)] uint8 (the Y plane only)."""
+    pixel_format="i420", size=(h, w): [N, i420_bytes(h, w)] uint8 (the Y plane only).  depth = 10, 12 (I420 only): frames of 16-bit samples,
+    [N, 2 * i420_bytes(h, w)] uint8, compared by their 8 most significant bits, so the scores keep the 8-bit scale."""
     i420 = check_pixel_format(pixel_format, size)
-    _sad_layout(frames, i420)
-    return _pair_sad_device(_to_device(frames, _sad_device(frames)), i420)
+    depth = check_depth(depth)
+    _sad_layout(frames, i420, depth)
+    return _pair_sad_device(_to_device(frames, _sad_device(frames)), i420, depth)
 
 
-def detect_cuts(frames: torch.Tensor, threshold=10.0, pixel_format: str = "rgb", size=None) -> List[int]:
+def detect_cuts(frames: torch.Tensor, threshold=10.0, pixel_format: str = "rgb", size=None, depth: int = 8) -> List[int]:
     """The scene cuts of a video: the frames k whose change from frame k - 1, damped by the previous pair's, is at least `threshold`
     per cent of the largest possible one (ffmpeg scdet's rule in exact integer arithmetic, savsr_amd.scenes.cuts_from_sad, on pair_sad's
     scores; one device -> host copy of N - 1 integers).  The default threshold is scdet's and is not validated on real footage."""
     from .scenes import check_threshold, cuts_from_sad, sad_samples
     check_threshold(threshold)
     i420 = check_pixel_format(pixel_format, size)
-    _sad_layout(frames, i420)
-    sad = pair_sad(frames, pixel_format, size)
+    depth = check_depth(depth)
+    _sad_layout(frames, i420, depth)
+    sad = pair_sad(frames, pixel_format, size, depth)
     return cuts_from_sad(sad.cpu().tolist(), sad_samples(frames.shape, pixel_format, size), threshold)
 
 
 def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
                   size=None, cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601",
-                  out_colour: Optional[str] = None) -> torch.Tensor:
+                  out_colour: Optional[str] = None, depth: int = 8, out_depth: Optional[int] = None) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
     check_out(out, net.cfg["num_in_ch"])
     i420 = check_pixel_format(pixel_format, size)
     cid, ocid = check_colours(colour, out_colour, pixel_format, out)
+    d, od = check_depths(depth, out_depth, pixel_format, out, colour, out_colour)
     sc = as_scale(net.scale if scale is None else scale)
-    n = i420_layout(frames, i420, net.cfg["num_in_ch"]) if i420 else frame_layout(frames, net.cfg["num_in_ch"])[0]
+    n = i420_layout(frames, i420, net.cfg["num_in_ch"], d) if i420 else frame_layout(frames, net.cfg["num_in_ch"])[0]
     T = net.num_frame
     if cuts is None:
         check_length(n, T, padding)
@@ -269,12 +310,12 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         windows = [window_indices(i, n, T, padding) for i in range(n)]
     else:
         if _is_auto(cuts):
-            sad = _pair_sad_device(frames, i420).cpu().tolist()
+            sad = _pair_sad_device(frames, i420, d).cpu().tolist()
             cuts = scenes.cuts_from_sad(sad, scenes.sad_samples(frames.shape, pixel_format, size), scene_threshold)
         windows = scenes.scene_windows(n, cuts, T, padding)
     with torch.no_grad():
         return net.engine().forward_video(frames, windows, sc, out == "uint8", ensemble=net.self_ensemble, i420=i420,
-                                          out_i420=out == "i420", colour=cid, out_colour=ocid)
+                                          out_i420=out == "i420", colour=cid, out_colour=ocid, depth=d, out_depth=od)
 
 
 class VideoUpscaler:
@@ -291,7 +332,8 @@ class VideoUpscaler:
     window may still name -- at most num_frame - 1 (num_frame for the two circle modes, whose last windows reach num_frame - 1 frames
     back) -- plus the current chunk.
 
-    colour / out_colour: the colour spaces of I420 chunks in / out, as in upscale_video.
+    colour / out_colour: the colour spaces of I420 chunks in / out, as in upscale_video.  depth / out_depth: their bit depths (10, 12:
+    chunks of [k, 2 * i420_bytes(h, w)] uint8, 16-bit samples), as in upscale_video.
 
     cuts=[k, ...] (global frame indices) or cuts="auto" (each push scores its new pairs on the device, the pair with the previous
     push's last frame included, and decides with `scene_threshold`): windows stop at cuts as in upscale_video(cuts=...), and `up.cuts`
@@ -299,7 +341,8 @@ class VideoUpscaler:
     may still come anywhere after the last pushed frame (savsr_amd.scenes.ScenePlan); the frames kept are bounded as without cuts."""
 
     def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb", size=None,
-                 cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None):
+                 cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None,
+                 depth: int = 8, out_depth: Optional[int] = None):
         _check_net(net)
         check_padding(padding)
         check_out(out, net.cfg["num_in_ch"])
@@ -314,6 +357,7 @@ class VideoUpscaler:
             self._plan = scenes.ScenePlan(net.num_frame, padding)
         self.i420 = check_pixel_format(pixel_format, size)        # (h, w) of I420 chunks, None for RGB ones
         self._colours = check_colours(colour, out_colour, pixel_format, out)      # colour space ids of the I420 input / output
+        self._depths = check_depths(depth, out_depth, pixel_format, out, colour, out_colour)      # bit depths of the I420 input / output
         self.net, self.padding, self.out = net, padding, out
         self.scale = as_scale(net.scale if scale is None else scale)
         self.ensemble = net.self_ensemble          # (read once, like the scale: every chunk runs the same flow)
@@ -351,7 +395,8 @@ class VideoUpscaler:
         windows = [[j - self._base for j in window_indices(i, n, self.T, self.padding)] for i in range(self.done, upto)]
         with torch.no_grad():
             res = self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble, i420=self.i420,
-                                                  out_i420=self.out == "i420", colour=self._colours[0], out_colour=self._colours[1])
+                                                  out_i420=self.out == "i420", colour=self._colours[0], out_colour=self._colours[1],
+                                                  depth=self._depths[0], out_depth=self._depths[1])
         self.done = upto
         return res
 
@@ -359,7 +404,7 @@ class VideoUpscaler:
         if self._finished:
             raise RuntimeError("push() after finish()")
         if self.i420:
-            k, (h, w) = i420_layout(frames, self.i420, self.net.cfg["num_in_ch"]), self.i420
+            k, (h, w) = i420_layout(frames, self.i420, self.net.cfg["num_in_ch"], self._depths[0]), self.i420
         else:
             k, h, w = frame_layout(frames, self.net.cfg["num_in_ch"])
         shape = (frames.dtype == torch.uint8, h, w)
@@ -397,7 +442,7 @@ class VideoUpscaler:
         if hi - first < 1:
             return []
         from .scenes import cuts_from_sad, sad_samples
-        sad = _pair_sad_device(self._buf[first - 1 - self._base:], self.i420).cpu().tolist()
+        sad = _pair_sad_device(self._buf[first - 1 - self._base:], self.i420, self._depths[0]).cpu().tolist()
         new = cuts_from_sad(sad, sad_samples(self._buf.shape, "i420" if self.i420 else "rgb", self.i420), self._threshold, first, self._prev_sad)
         self._prev_sad = sad[-1]
         return new
@@ -408,7 +453,8 @@ class VideoUpscaler:
         windows = [[j - self._base for j in win] for win in windows]
         with torch.no_grad():
             return self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble, i420=self.i420,
-                                                   out_i420=self.out == "i420", colour=self._colours[0], out_colour=self._colours[1])
+                                                   out_i420=self.out == "i420", colour=self._colours[0], out_colour=self._colours[1],
+                                                   depth=self._depths[0], out_depth=self._depths[1])
 
     def _push_scenes(self, k: int) -> torch.Tensor:
         plan = self._plan
@@ -450,7 +496,7 @@ class VideoUpscaler:
         c = self.net.cfg["num_in_ch"]
         dev = self.net.gamma.device
         if self.out == "i420":
-            return torch.empty(0, i420_bytes(H, W), dtype=torch.uint8, device=dev)
+            return torch.empty(0, i420_bytes(H, W, self._depths[1]), dtype=torch.uint8, device=dev)
         if self.out == "uint8":
             return torch.empty(0, H, W, c, dtype=torch.uint8, device=dev)
         return torch.empty(0, c, H, W, dtype=torch.float32, device=dev)

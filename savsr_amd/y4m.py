@@ -8,6 +8,10 @@ from another program (ffmpeg -f yuv4mpegpipe, x264, a player) without a library.
 three 420 tags differ in chroma siting only, which is accepted and ignored (yuv.py's nearest / box pair is centre-sited); the writer
 tags its output C420jpeg.  XCOLORRANGE=FULL / XCOLORRANGE=LIMITED (ffmpeg's extension tag) is read into `colour_range` and written on
 request; the format has no tag for the matrix (BT.601 / BT.709), which is the caller's to know or to guess from the frame size.
+
+10 and 12 bits: Y4MReader(f, high_depth=True) also reads C420p10 and C420p12, whose frames hold little-endian 16-bit samples in the same
+plane order (2 * i420_bytes bytes, still handed out as uint8 rows; `depth` says which).  The reader refuses them unless asked to, so that
+a caller written against one byte per sample never receives two; Y4MWriter(..., depth=10 | 12) writes them.
 """
 from __future__ import annotations
 
@@ -20,6 +24,7 @@ from .yuv import i420_bytes
 
 MAGIC = b"YUV4MPEG2"
 C420_TAGS = ("420", "420jpeg", "420mpeg2", "420paldv")
+C420_HIGH_TAGS = {"420p10": 10, "420p12": 12}        # tag -> bit depth (Y4MReader with high_depth=True, Y4MWriter with depth=)
 MAX_LINE = 4096          # a header or FRAME line longer than this is not Y4M
 COLOUR_RANGES = ("full", "limited")
 
@@ -88,10 +93,12 @@ def _read_line(f) -> bytes:
 class Y4MReader:
     """Reads the header on construction (width, height, fps, interlace, aspect, colorspace, colour_range), then `chunks(k)` yields the
     frames as uint8 arrays [m, i420_bytes(height, width)], m = k but for the last.  colour_range: "full" / "limited" of an
-    XCOLORRANGE=FULL / =LIMITED tag, None without one."""
+    XCOLORRANGE=FULL / =LIMITED tag, None without one.  high_depth=True: C420p10 / C420p12 are read as well; `depth` is 8, 10 or 12 and
+    the rows of a 10- or 12-bit stream are [m, 2 * i420_bytes(height, width)] uint8 (little-endian 16-bit samples)."""
 
-    def __init__(self, f):
+    def __init__(self, f, high_depth: bool = False):
         self.f = f
+        self.depth = 8
         line = _read_line(f)
         if not line.startswith(MAGIC + b" ") or not line.endswith(b"\n"):
             raise ValueError("y4m: not a YUV4MPEG2 stream (no 'YUV4MPEG2 ' header line)")
@@ -122,7 +129,12 @@ class Y4MReader:
             elif key == "A":
                 self.aspect = _ratio("A", val)
             elif key == "C":
-                if val not in C420_TAGS:
+                if high_depth and val in C420_HIGH_TAGS:
+                    self.depth, self.colorspace = C420_HIGH_TAGS[val], val
+                elif high_depth and val not in C420_TAGS:
+                    raise ValueError(f"y4m: colour space tag 'C{val}' is not supported: 4:2:0 at 8, 10 or 12 bits only "
+                                     f"({', '.join('C' + t for t in C420_TAGS + tuple(C420_HIGH_TAGS))})")
+                elif val not in C420_TAGS:
                     raise ValueError(f"y4m: colour space tag 'C{val}' is not supported: 8-bit 4:2:0 only ({', '.join('C' + t for t in C420_TAGS)})")
                 self.colorspace = val
             elif key == "X":                          # comments / extensions (XYSCSS=...): ignored, but for the range
@@ -132,7 +144,7 @@ class Y4MReader:
                 raise ValueError(f"y4m: unknown header tag {tag!r}")
         if self.width is None or self.height is None:
             raise ValueError("y4m: the header names no W / H")
-        self.frame_bytes = i420_bytes(self.height, self.width)
+        self.frame_bytes = i420_bytes(self.height, self.width, self.depth)
         self.frames_read = 0
 
     def _frame_into(self, row: np.ndarray) -> bool:
@@ -165,17 +177,21 @@ class Y4MReader:
 
 class Y4MWriter:
     """Writes the header on construction, then `write(frames)` appends uint8 frames [m, i420_bytes(height, width)].
-    colour_range = "full" / "limited": the header also carries XCOLORRANGE=FULL / =LIMITED (None: no such tag)."""
+    colour_range = "full" / "limited": the header also carries XCOLORRANGE=FULL / =LIMITED (None: no such tag).  depth = 10, 12: the
+    stream is tagged C420p10 / C420p12 and its frames are [m, 2 * i420_bytes(height, width)] uint8 (little-endian 16-bit samples)."""
 
     def __init__(self, f, width: int, height: int, fps: Tuple[int, int] = (25, 1), interlace: str = "p", aspect: Tuple[int, int] = (0, 0),
-                 colour_range: Optional[str] = None):
+                 colour_range: Optional[str] = None, depth: int = 8):
         if width < 1 or height < 1:
             raise ValueError(f"y4m: W, H >= 1, got {width} x {height}")
         if colour_range is not None and colour_range not in COLOUR_RANGES:
             raise ValueError(f"y4m: colour_range = {colour_range!r}: None or one of {', '.join(COLOUR_RANGES)}")
-        self.f, self.width, self.height = f, int(width), int(height)
-        self.frame_bytes = i420_bytes(self.height, self.width)
-        self.header = (f"YUV4MPEG2 W{self.width} H{self.height} F{fps[0]}:{fps[1]} I{interlace} A{aspect[0]}:{aspect[1]} C420jpeg"
+        if depth != 8 and depth not in C420_HIGH_TAGS.values():
+            raise ValueError(f"y4m: depth = {depth!r}: one of 8, 10, 12")
+        self.f, self.width, self.height, self.depth = f, int(width), int(height), int(depth)
+        self.frame_bytes = i420_bytes(self.height, self.width, self.depth)
+        ctag = "420jpeg" if depth == 8 else f"420p{self.depth}"
+        self.header = (f"YUV4MPEG2 W{self.width} H{self.height} F{fps[0]}:{fps[1]} I{interlace} A{aspect[0]}:{aspect[1]} C{ctag}"
                        f"{'' if colour_range is None else ' XCOLORRANGE=' + colour_range.upper()}\n").encode("ascii")
         f.write(self.header)
 

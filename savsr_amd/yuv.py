@@ -1,7 +1,8 @@
 """Planar YUV 4:2:0 (I420) <-> RGB, the host restatement that specifies savsr_video_gather_i420 / savsr_video_quantize_i420 (yuv.hip).
 
 The default colour matrix is the reference's (lbasicsr/utils/color_util.py, `rgb2ycbcr` / `ycbcr2rgb`: ITU-R BT.601, limited range,
-Matlab's rounded constants: `BT601`), the same whose Y row metrics.py uses for PSNR-Y.  8-bit 4:2:0 only.  `COLOURS` names the four
+Matlab's rounded constants: `BT601`), the same whose Y row metrics.py uses for PSNR-Y.  4:2:0 only, at 8, 10 or 12 bits (`depth=`;
+10 and 12 with the limited-range colour spaces only, see "High depth" below).  `COLOURS` names the four
 colour spaces served (`colour=`; the position is the id of the C ABI) and `matrix(name)` gives each one's coefficient table: BT601
 itself for "bt601", built from (Kr, Kb, range) for the others (`kYuv` is the twin in yuv.hip, the same float64 expressions).
 
@@ -16,6 +17,18 @@ Both directions are float32 with a fixed operation order and no fused multiply-a
   rgb_to_i420   RGB clamped to [0, 1]; Y per pixel; Cb / Cr from the mean RGB of the block's in-image pixels (1, 2 or 4: the
                 divisor is a power of two); every product and every sum rounded to float32; round half to even (tensor2img's rule);
                 full range only: clipped to 0 .. 255 after the rounding (pure red has Cr = 255.5, pure blue Cb = 255.5 -> 256).
+
+High depth (d = 10 or 12, k = 2^(d - 8); the specification of savsr_video_gather_yuv420_16 / savsr_video_quantize_yuv420_16).  A frame is
+the 8-bit frame's planes with every sample a little-endian 16-bit word, as it lies in a Y4M file tagged C420p10 / C420p12: a video is a
+uint8 array [N, 2 * i420_bytes(h, w)] (`i420_bytes(h, w, d)`), never a uint16 one.  Limited range only: a sample is the 8-bit one times k
+(Y = 16 k .. 235 k), so every constant is the 8-bit table's, scaled by a power of two; full range at depth d scales by 2^d - 1 instead
+and has no definition here.
+
+  i420_to_rgb   no tables: with c = float32(coef / k) and o = float32(offset / 255), Yt = s_y * c_y, R = (Yt + s_v * c_rv) + o_R,
+                G = ((Yt + s_u * c_gu) + s_v * c_gv) + o_G, B = (Yt + s_u * c_bu) + o_B in float32, every product and sum rounded;
+                clamped to [0, 1].  A sample above 2^d - 1 is read as 2^d - 1.  At most five roundings of values below 2.5, so the result
+                lies within 5 * 2.5 * 2^-24 < 1e-6 of the float64 closed form.
+  rgb_to_i420   rint(ycbcr_f32 * k), half to even (the product by k is exact); Y in 16 k .. 235 k and chroma in 16 k .. 240 k, no clip.
 """
 from __future__ import annotations
 
@@ -85,13 +98,33 @@ def matrix(colour: str = "bt601") -> dict:
     return _MATRICES[name]
 
 
+DEPTHS = (8, 10, 12)
+
+
+def check_depth(depth, what: str = "depth") -> int:
+    """A bit depth as an int; refuses anything but 8, 10 and 12, naming the list."""
+    if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or int(depth) not in DEPTHS:
+        raise ValueError(f"{what} = {depth!r}: one of {', '.join(str(d) for d in DEPTHS)}")
+    return int(depth)
+
+
+def check_depth_colour(depth, colour: str, what: str = "depth", cwhat: str = "colour") -> int:
+    """check_depth, and the rule that 10 and 12 bits are defined for the limited-range colour spaces only."""
+    d = check_depth(depth, what)
+    if d > 8 and is_full_range(colour):
+        raise ValueError(f"{what} = {d} with {cwhat} = {colour!r}: 10 and 12 bits are defined for limited range only (bt601, bt709); "
+                         f"full range at depth d scales by 2^d - 1 and is not implemented")
+    return d
+
+
 def chroma_hw(h: int, w: int) -> Tuple[int, int]:
     return (h + 1) // 2, (w + 1) // 2
 
 
-def i420_bytes(h: int, w: int) -> int:
+def i420_bytes(h: int, w: int, depth: int = 8) -> int:
+    """Bytes of a frame: a byte per sample at 8 bits, a 16-bit word at 10 and 12."""
     ch, cw = chroma_hw(h, w)
-    return h * w + 2 * ch * cw
+    return (h * w + 2 * ch * cw) * (1 if depth == 8 else 2)
 
 
 def _check_size(h: int, w: int) -> None:
@@ -99,11 +132,17 @@ def _check_size(h: int, w: int) -> None:
         raise ValueError(f"size must be (h, w) with h, w >= 1, got ({h!r}, {w!r})")
 
 
-def split_planes(frames: np.ndarray, h: int, w: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """[N, i420_bytes(h, w)] uint8 -> views Y [N, h, w], U [N, ch, cw], V [N, ch, cw]."""
+def split_planes(frames: np.ndarray, h: int, w: int, depth: int = 8) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """[N, i420_bytes(h, w, depth)] uint8 -> Y [N, h, w], U [N, ch, cw], V [N, ch, cw]: uint8 views at 8 bits, the little-endian 16-bit
+    samples as uint16 arrays at 10 and 12."""
     _check_size(h, w)
     frames = np.asarray(frames)
-    if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != i420_bytes(h, w):
+    if depth != 8:
+        depth = check_depth(depth)
+        if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != i420_bytes(h, w, depth):
+            raise ValueError(f"{depth}-bit I420 frames of {h} x {w} are [N, {i420_bytes(h, w, depth)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+        frames = np.ascontiguousarray(frames).view("<u2")
+    elif frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != i420_bytes(h, w):
         raise ValueError(f"I420 frames of {h} x {w} are [N, {i420_bytes(h, w)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
     ch, cw = chroma_hw(h, w)
     n = frames.shape[0]
@@ -126,8 +165,35 @@ def to_rgb_tables(m: dict = BT601) -> dict:
             "bu": (s * t["bu"] + o[2]).astype(np.float32)}
 
 
-def i420_to_rgb(frames_u8: np.ndarray, h: int, w: int, colour: str = "bt601") -> np.ndarray:
-    """[N, i420_bytes(h, w)] uint8 -> float32 [N, 3, h, w] in [0, 1]:  R = y + rv,  G = (y + gu) + gv,  B = y + bu  on the table values."""
+def to_rgb_coefficients(colour: str, depth: int) -> dict:
+    """The float32 constants of the high-depth i420_to_rgb: the five to-RGB entries divided by k = 2^(depth - 8) (exact) and the three
+    offsets / 255, each rounded once to float32."""
+    t = matrix(colour)["to_rgb"]
+    k = float(1 << (check_depth_colour(depth, colour) - 8))
+    c = {name: np.float32(t[name] / k) for name in ("y", "rv", "gu", "gv", "bu")}
+    c["offset"] = tuple(np.float32(v / 255.0) for v in t["offset"])
+    return c
+
+
+def _i420_to_rgb_16(frames_u8: np.ndarray, h: int, w: int, colour: str, depth: int) -> np.ndarray:
+    c = to_rgb_coefficients(colour, depth)
+    top = np.uint16((1 << depth) - 1)
+    y, u, v = (np.minimum(p, top).astype(np.float32) for p in split_planes(frames_u8, h, w, depth))
+    u = np.repeat(np.repeat(u, 2, axis=1), 2, axis=2)[:, :h, :w]
+    v = np.repeat(np.repeat(v, 2, axis=1), 2, axis=2)[:, :h, :w]
+    yt = y * c["y"]
+    r = (yt + v * c["rv"]) + c["offset"][0]
+    g = ((yt + u * c["gu"]) + v * c["gv"]) + c["offset"][1]
+    b = (yt + u * c["bu"]) + c["offset"][2]
+    out = np.stack([r, g, b], 1)
+    return np.fmin(np.fmax(out, np.float32(0.0)), np.float32(1.0)).astype(np.float32)
+
+
+def i420_to_rgb(frames_u8: np.ndarray, h: int, w: int, colour: str = "bt601", depth: int = 8) -> np.ndarray:
+    """[N, i420_bytes(h, w, depth)] uint8 -> float32 [N, 3, h, w] in [0, 1].  depth = 8:  R = y + rv,  G = (y + gu) + gv,  B = y + bu  on
+    the table values; 10 and 12: float32 arithmetic on the samples (the module's "High depth")."""
+    if depth != 8:
+        return _i420_to_rgb_16(frames_u8, h, w, colour, depth)
     y, u, v = split_planes(frames_u8, h, w)
     t = to_rgb_tables(matrix(colour))
     u = np.repeat(np.repeat(u, 2, axis=1), 2, axis=2)[:, :h, :w]
@@ -179,9 +245,15 @@ def ycbcr_f32(x: np.ndarray, colour: str = "bt601") -> Tuple[np.ndarray, np.ndar
     return _row(p, t["y"], t["offset"][0]), _row(m, t["cb"], t["offset"][1]), _row(m, t["cr"], t["offset"][2])
 
 
-def rgb_to_i420(x_f32: np.ndarray, colour: str = "bt601") -> np.ndarray:
-    """float32 [N, 3, H, W] -> uint8 [N, i420_bytes(H, W)].  Limited range: after the clamp Y lies in 16 .. 235 and chroma in
-    16 .. 240, no clip.  Full range: chroma reaches 255.5, which rounds to 256, so the rounded values are clipped to 0 .. 255."""
+def rgb_to_i420(x_f32: np.ndarray, colour: str = "bt601", depth: int = 8) -> np.ndarray:
+    """float32 [N, 3, H, W] -> uint8 [N, i420_bytes(H, W, depth)].  Limited range: after the clamp Y lies in 16 .. 235 and chroma in
+    16 .. 240, no clip.  Full range: chroma reaches 255.5, which rounds to 256, so the rounded values are clipped to 0 .. 255.
+    depth = 10, 12 (limited range only): rint(ycbcr_f32 * 2^(depth - 8)), written as little-endian 16-bit samples."""
+    if depth != 8:
+        k = np.float32(1 << (check_depth_colour(depth, colour) - 8))
+        planes = [np.rint(v * k) for v in ycbcr_f32(x_f32, colour)]
+        n = planes[0].shape[0]
+        return np.concatenate([v.astype("<u2").reshape(n, -1) for v in planes], 1).view(np.uint8)
     y, cb, cr = ycbcr_f32(x_f32, colour)
     n = y.shape[0]
     planes = [np.rint(v) for v in (y, cb, cr)]

@@ -5,6 +5,11 @@ fails, times out or dies ends the run (nothing more is started on the GPU) and w
             interleaved rounds, at 180x320 and 720x1280: us, the fraction of 8 TB/s on 4*3*h*w + 1.5*h*w bytes, and the ratio to the RGB
             kernel's time (they move the same fp32 bytes and half the uint8 bytes; 1.2x is allowed for the two-row coupling); and
             savsr_video_gather_yuv420 / _quantize_yuv420 with each of the four colour ids (id 0 is the kernel of the _i420 entries)
+  depth     savsr_video_gather_yuv420_16 / _quantize_yuv420_16 (10 and 12 bits) beside the 8-bit savsr_video_gather_yuv420 /
+            _quantize_yuv420 of the same build, in one process, interleaved rounds, at 180x320 and 720x1280: us, the fraction of 8 TB/s
+            on 4*3*h*w + 3*h*w bytes, and the ratio to the 8-bit kernel's time beside the ratio of the bytes moved, (12 + 3) / (12 + 1.5)
+            = 1.11 -- a measured ratio well above it means the 16-bit access pattern is wrong.  No time is fixed in advance.
+            `--legs depth --out profiles/bench_y4m_depth.json`
   ceiling   upscale_video on preloaded I420 frames, I420 out (frames/s): what the CLI could reach
   cli       python -m savsr_amd.upscale on one synthetic video, PNG folder -> PNG folder against .y4m -> .y4m, A/B/A/B; files under
             --workdir (name the disk it lies on beside the figures: tmpfs or a scratch disk)
@@ -27,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_BYTES_PER_S = 8e12
-LEG_TIMEOUT_S = {"kernels": 240, "ceiling": 420, "cli": 420, "psnr": 420}
+LEG_TIMEOUT_S = {"kernels": 240, "depth": 240, "ceiling": 420, "cli": 420, "psnr": 420}
 
 
 def _net(dev):
@@ -98,6 +103,58 @@ def leg_kernels(a):
             row["us_rounds"] = [round(v, 2) for v in us[k]]          # (the spread between the rounds of this run)
             rows.append(row)
     return {"kernels": rows, "rounds": a.rounds, "iters": a.iters, "timing": "HIP events around `iters` back-to-back launches (launch rate included)"}
+
+
+def leg_depth(a):
+    import ctypes as C
+    import torch
+    from savsr_amd import _lib
+    from savsr_amd.yuv import i420_bytes
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    rows = []
+    for h, w in ((180, 320), (720, 1280)):
+        n, idx = 16, list(range(7))
+        arr = (C.c_int32 * 7)(*idx)
+        f8 = torch.randint(0, 256, (n, i420_bytes(h, w)), dtype=torch.uint8, device=dev)
+        f16 = {d: torch.randint(0, 1 << d, (n, i420_bytes(h, w)), dtype=torch.int16, device=dev).view(torch.uint8).view(n, -1) for d in (10, 12)}
+        assert all(int(f.shape[1]) == i420_bytes(h, w, d) for d, f in f16.items())
+        slots = torch.empty(7, 3, h, w, device=dev)
+        x = torch.rand(7, 3, h, w, device=dev)
+        q8 = torch.empty(7, i420_bytes(h, w), dtype=torch.uint8, device=dev)
+        q16 = torch.empty(7, i420_bytes(h, w, 10), dtype=torch.uint8, device=dev)
+        fns = {"savsr_video_gather_yuv420": lambda: lib.savsr_video_gather_yuv420(f8.data_ptr(), n, h, w, arr, 7, 1, slots.data_ptr(), st),
+               "savsr_video_quantize_yuv420": lambda: lib.savsr_video_quantize_yuv420(x.data_ptr(), 7, h, w, 1, q8.data_ptr(), st)}
+        for d in (10, 12):
+            fns[f"savsr_video_gather_yuv420_16 {d}"] = lambda d=d: lib.savsr_video_gather_yuv420_16(f16[d].data_ptr(), n, h, w, arr, 7, 1, d, slots.data_ptr(), st)
+            fns[f"savsr_video_quantize_yuv420_16 {d}"] = lambda d=d: lib.savsr_video_quantize_yuv420_16(x.data_ptr(), 7, h, w, 1, d, q16.data_ptr(), st)
+        us = {k: [] for k in fns}
+        for k, fn in fns.items():
+            assert fn() == 0, k
+        torch.cuda.synchronize()
+        for _ in range(a.rounds):                       # interleaved rounds: every kernel sees the same clocks
+            for k, fn in fns.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.iters):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                us[k].append(1e3 * e0.elapsed_time(e1) / a.iters)
+        med = {k: statistics.median(v) for k, v in us.items()}
+        for k in fns:
+            high = "_16" in k
+            nbytes = 7 * (4 * 3 + (3.0 if high else 1.5)) * h * w
+            row = {"kernel": k, "size": [h, w], "frames": 7, "us": round(med[k], 2), "us_per_frame": round(med[k] / 7, 3),
+                   "mb": round(nbytes / 1e6, 2), "hbm_frac": round(nbytes / (med[k] * 1e-6) / HBM_BYTES_PER_S, 3)}
+            if high:
+                row["vs_8bit_kernel"] = round(med[k] / med[k.split()[0][:-3]], 3)
+                row["byte_ratio"] = round((12 + 3.0) / (12 + 1.5), 3)
+            row["us_rounds"] = [round(v, 2) for v in us[k]]
+            rows.append(row)
+    return {"kernels": rows, "rounds": a.rounds, "iters": a.iters, "colour": "bt709",
+            "timing": "HIP events around `iters` back-to-back launches (launch rate included)"}
 
 
 def leg_ceiling(a):
@@ -181,7 +238,7 @@ def leg_psnr(a):
                        "note": "against the float result in float64; synthetic weights"}}
 
 
-LEGS = {"kernels": leg_kernels, "ceiling": leg_ceiling, "cli": leg_cli, "psnr": leg_psnr}
+LEGS = {"kernels": leg_kernels, "depth": leg_depth, "ceiling": leg_ceiling, "cli": leg_cli, "psnr": leg_psnr}
 
 
 def main():
