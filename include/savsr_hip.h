@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 38
+#define SAVSR_ABI_VERSION 39
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -511,6 +511,34 @@ int savsr_video_gather_yuv420_16(const uint8_t* frames, int n_frames, int h, int
                                  void* stream);
 int savsr_video_quantize_yuv420_16(const float* in, int n, int H, int W, int colour, int depth, uint8_t* out, void* stream);
 int savsr_video_pair_sad_i420_16(const uint8_t* frames, int n_frames, int h, int w, int depth, int64_t* sad_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 39) 4:2:2 and 4:4:4 beside 4:2:0, at 8, 10 and 12 bits (yuv.hip, scene.hip; pixel_format / out = "i422", "i444" of
+ * SAVSR.upscale_video, --out-chroma of python -m savsr_amd.upscale).  One entry per side serves every
+ * (chroma, depth): chroma = one of SAVSR_CHROMA_*, depth = 8, 10 or 12.  A frame of an h x w picture is h * w Y samples, then ch * cw U
+ * samples, then ch * cw V samples, (ch, cw) = ((h + 1) / 2, (w + 1) / 2) for 4:2:0, (h, (w + 1) / 2) for 4:2:2, (h, w) for 4:4:4; a byte
+ * per sample at depth 8, a little-endian 16-bit word at 10 / 12 (2-byte aligned pointers; samples above 2^depth - 1 read as 2^depth - 1),
+ * frames back to back.  The arithmetic is 4:2:0's with another block shape: to RGB a chroma sample serves its 1 x 2 (4:2:2) or 1 x 1
+ * (4:4:4) block; from RGB, Cb / Cr come from (a + b) * 0.5 of a 4:2:2 pair (the pixel alone in the last column of an odd W) and from the
+ * pixel's own clamped RGB in 4:4:4.  Chroma is centre-sited as in 4:2:0; MPEG-2's horizontally cosited 4:2:2 is not modelled.
+ * savsr_amd/yuv.py (`chroma=`) restates all of it bit for bit.  SAVSR_CHROMA_420 runs the kernels of the entries above and gives their
+ * bytes.  Refused with SAVSR_E_ARG + savsr_last_error() before the device is touched: a chroma outside 0 .. 2, a depth other than
+ * 8 / 10 / 12, a full-range colour at depth 10 / 12, a null pointer, an odd frame pointer at depth 10 / 12, an index outside the frames.
+ * savsr_video_gather_yuvp:   frames -> out [n_idx][3][h][w] fp32 planar RGB, slot k = frame idx[k].  A thread owns 4 pixels of one row
+ *                         (a Y dword or 8 bytes, the 2 or 4 chroma samples under them in one access, one 16-byte store per plane) when
+ *                         w % 4 == 0, frames 4-byte (8-byte at depth 10 / 12) and out 16-byte aligned: every plane row then keeps the
+ *                         alignment of its access (yuv.hip lists the offsets); a chroma sample and its pixels per thread otherwise.
+ * savsr_video_quantize_yuvp: in [n][3][H][W] fp32 contiguous -> out [n] frames; the vector form under the same conditions, the input
+ *                         loaded nontemporally.
+ * savsr_video_pair_sad_yuvp: savsr_video_pair_sad_i420 / _i420_16 on frames of the given layout: the Y plane is the first h * w samples
+ *                         of a frame in every layout, so this is the same kernels with another frame stride. */
+#define SAVSR_CHROMA_420 0
+#define SAVSR_CHROMA_422 1
+#define SAVSR_CHROMA_444 2
+int savsr_video_gather_yuvp(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, int colour, int depth, int chroma,
+                            float* out, void* stream);
+int savsr_video_quantize_yuvp(const float* in, int n, int H, int W, int colour, int depth, int chroma, uint8_t* out, void* stream);
+int savsr_video_pair_sad_yuvp(const uint8_t* frames, int n_frames, int h, int w, int depth, int chroma, int64_t* sad_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 33) Geometric self-ensemble (ensemble.hip; SAVSR.set_self_ensemble).  Variant k = 0 .. 7: fw = k & 1 flips

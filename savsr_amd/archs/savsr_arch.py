@@ -298,6 +298,10 @@ class SAVSR(nn.Module):
         None = the same as depth (8 for RGB input).  The two are independent: depth=8, out_depth=10 keeps the two bits of the fp32
         result that the 8-bit rounding throws away, which is what a 10-bit HEVC / AV1 encoder wants.  10 and 12 bits are defined for
         the limited-range colour spaces (bt601, bt709) only.
+        pixel_format="i422" / "i444", out="i422" / "i444": planar YUV 4:2:2 / 4:4:4 (Y4M's C422 / C444 and their p10 / p12 forms), frames
+        of savsr_amd.yuv.frame_bytes(h, w, depth, chroma) bytes; size, colour, out_colour, depth and out_depth apply to them as to I420.
+        The two sides are independent: pixel_format="i420", out="i444" keeps the network's full-resolution chroma, and RGB in with
+        out="i422" is allowed.  Chroma is centre-sited in every layout (MPEG-2's cosited 4:2:2 is not modelled).
         cuts: None (one scene), a strictly increasing list of frame indices 0 < k < N (frame k starts a new scene), or "auto" (found on
         the GPU: savsr_amd.detect_cuts with scene_threshold, in per cent of the largest possible frame change; the default is ffmpeg
         scdet's and is not validated on real footage).  Windows stop at cuts: the result is, bit for bit, upscale_video on every scene

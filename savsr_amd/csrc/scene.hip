@@ -9,6 +9,9 @@
 //                      rule (clamp(0, 1) * 255.0f, rintf; NaN -> 0)
 //   10- / 12-bit I420  the Y plane only, every 16-bit sample as its     S = h * w
 //   (ABI 38)           8 most significant bits: min(s, 2^d - 1) >> (d - 8)
+//   4:2:2 / 4:4:4      the Y plane only, as for I420 at the same depth: the Y   S = h * w
+//   (ABI 39)           plane is the first h * w samples of a frame in every layout, so savsr_video_pair_sad_yuvp is host work only
+//                      (another frame stride for the same kernels)
 #include "common.hpp"
 
 #include <cstdint>
@@ -222,6 +225,25 @@ int launch_bytes(const uint8_t* frames, int n_frames, long long stride, long lon
     return 0;
 }
 
+// high-depth frames `stride` bytes apart, the first `len` 16-bit samples of each compared (the 10- / 12-bit entries)
+int launch_words(const uint8_t* frames, int n_frames, long long stride, long long len, int depth, int64_t* sad_out, hipStream_t st, const char* what) {
+    const int n_pairs = n_frames - 1;
+    if (n_pairs == 0) return 0;
+    if (int rc = zero_scores(sad_out, n_pairs, st, what)) return rc;
+    const bool vec = stride % 16 == 0 && (reinterpret_cast<uintptr_t>(frames) & 15) == 0 && len >= 8;
+    const unsigned gx = vec ? sad_blocks(len >> 3, SAD_VEC_ITERS) : sad_blocks(len, SAD_ONE_ITERS);
+    const uint32_t top = (1u << depth) - 1u;
+    for (int p0 = 0; p0 < n_pairs; p0 += SAD_MAX_PAIRS_Y) {
+        const int np = n_pairs - p0 < SAD_MAX_PAIRS_Y ? n_pairs - p0 : SAD_MAX_PAIRS_Y;
+        const uint8_t* f = frames + (long long)p0 * stride;
+        unsigned long long* s = reinterpret_cast<unsigned long long*>(sad_out) + p0;
+        if (vec) hipLaunchKernelGGL((pair_sad_u16_kernel<true>), dim3(gx, np), dim3(SAD_THREADS), 0, st, f, stride, len, top, depth - 8, s);
+        else hipLaunchKernelGGL((pair_sad_u16_kernel<false>), dim3(gx, np), dim3(SAD_THREADS), 0, st, f, stride, len, top, depth - 8, s);
+        if (int rc = check_launch("pair_sad_u16_kernel")) return rc;
+    }
+    return 0;
+}
+
 }  // namespace
 }  // namespace savsr
 
@@ -275,22 +297,23 @@ extern "C" int savsr_video_pair_sad_i420_16(const uint8_t* frames, int n_frames,
     if (depth != 10 && depth != 12) return fail_arg("video_pair_sad_i420_16: depth 10 or 12 (8 bits: savsr_video_pair_sad_i420)");
     if (reinterpret_cast<uintptr_t>(frames) & 1) return fail_arg("video_pair_sad_i420_16: frames must be 2-byte aligned (16-bit samples)");
     if (reinterpret_cast<uintptr_t>(sad_out) & 7) return fail_arg("video_pair_sad_i420_16: sad_out must be 8-byte aligned");
-    const int n_pairs = n_frames - 1;
-    if (n_pairs == 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = zero_scores(sad_out, n_pairs, st, "video_pair_sad_i420_16")) return rc;
     const long long ch = (h + 1) / 2, cw = (w + 1) / 2;
-    const long long len = (long long)h * w, stride = 2 * (len + 2 * ch * cw);
-    const bool vec = stride % 16 == 0 && (reinterpret_cast<uintptr_t>(frames) & 15) == 0 && len >= 8;
-    const unsigned gx = vec ? sad_blocks(len >> 3, SAD_VEC_ITERS) : sad_blocks(len, SAD_ONE_ITERS);
-    const uint32_t top = (1u << depth) - 1u;
-    for (int p0 = 0; p0 < n_pairs; p0 += SAD_MAX_PAIRS_Y) {
-        const int np = n_pairs - p0 < SAD_MAX_PAIRS_Y ? n_pairs - p0 : SAD_MAX_PAIRS_Y;
-        const uint8_t* f = frames + (long long)p0 * stride;
-        unsigned long long* s = reinterpret_cast<unsigned long long*>(sad_out) + p0;
-        if (vec) hipLaunchKernelGGL((pair_sad_u16_kernel<true>), dim3(gx, np), dim3(SAD_THREADS), 0, st, f, stride, len, top, depth - 8, s);
-        else hipLaunchKernelGGL((pair_sad_u16_kernel<false>), dim3(gx, np), dim3(SAD_THREADS), 0, st, f, stride, len, top, depth - 8, s);
-        if (int rc = check_launch("pair_sad_u16_kernel")) return rc;
-    }
-    return 0;
+    const long long len = (long long)h * w;
+    return launch_words(frames, n_frames, 2 * (len + 2 * ch * cw), len, depth, sad_out, static_cast<hipStream_t>(stream), "video_pair_sad_i420_16");
+}
+
+// ABI 39: frames of any chroma layout (SAVSR_CHROMA_*) and depth (8, 10, 12): the Y plane, h * w samples at the start of a frame of
+// h * w + 2 * ch * cw samples.  Host work only: the kernels above with the layout's frame stride.
+extern "C" int savsr_video_pair_sad_yuvp(const uint8_t* frames, int n_frames, int h, int w, int depth, int chroma, int64_t* sad_out, void* stream) {
+    if (chroma < SAVSR_CHROMA_420 || chroma > SAVSR_CHROMA_444) return fail_arg("video_pair_sad_yuvp: chroma 0 (4:2:0), 1 (4:2:2) or 2 (4:4:4)");
+    if (depth != 8 && depth != 10 && depth != 12) return fail_arg("video_pair_sad_yuvp: depth 8, 10 or 12");
+    if (!frames || (!sad_out && n_frames > 1)) return fail_arg("video_pair_sad_yuvp: null pointer");
+    if (h < 1 || w < 1 || n_frames < 1) return fail_arg("video_pair_sad_yuvp: h, w, n_frames >= 1");
+    if (depth != 8 && (reinterpret_cast<uintptr_t>(frames) & 1)) return fail_arg("video_pair_sad_yuvp: frames must be 2-byte aligned (16-bit samples)");
+    if (reinterpret_cast<uintptr_t>(sad_out) & 7) return fail_arg("video_pair_sad_yuvp: sad_out must be 8-byte aligned");
+    const long long ch = chroma == SAVSR_CHROMA_420 ? (h + 1) / 2 : h, cw = chroma == SAVSR_CHROMA_444 ? w : (w + 1) / 2;
+    const long long len = (long long)h * w, samples = len + 2 * ch * cw;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (depth == 8) return launch_bytes(frames, n_frames, samples, len, sad_out, st, "video_pair_sad_yuvp");
+    return launch_words(frames, n_frames, 2 * samples, len, depth, sad_out, st, "video_pair_sad_yuvp");
 }

@@ -13,6 +13,7 @@
 // and no fused multiply-add (contraction is off for this whole file).
 //
 // I420 frame of an h x w picture: h * w Y bytes, ch * cw U bytes, ch * cw V bytes, ch = (h + 1) / 2, cw = (w + 1) / 2.
+// ABI 38 adds 10 and 12 bits (16-bit samples), ABI 39 the 4:2:2 and 4:4:4 layouts at every depth (further down).
 #include "common.hpp"
 
 #include <cstdint>
@@ -508,6 +509,350 @@ int check_depth16(int colour, int depth, const char* what) {
     return 0;
 }
 
+
+// ---- 4:2:2 and 4:4:4 (ABI 39) -----------------------------------------------------------------------------------------------------------
+// The same arithmetic with another block shape (yuv.py: "Chroma layouts"): a frame is h * w Y samples, then ch * cw U, then ch * cw V with
+// (ch, cw) = (h, (w + 1) / 2) in 4:2:2 and (h, w) in 4:4:4.  SX is the layout's horizontal subsampling (2: 4:2:2, 1: 4:4:4); neither layout
+// shares chroma between rows, so a thread owns pixels of one row only.  VEC: 4 pixels -- a Y dword (8 bits) or 8 bytes (16 bits), the
+// 4 / SX chroma samples under them in one access per plane, one float4 per plane row.  Otherwise one chroma sample and its SX pixels
+// with sample-sized accesses.  What VEC needs is 4:2:0's: w % 4 == 0, frames 4-byte (8 bits) / 8-byte (16 bits) aligned, the fp32 side
+// 16-byte aligned.  With w = 4 q, in bytes from the frame's start (s = bytes per sample):
+//   4:4:4   fb = 12 q h s; U at 4 q h s, V at 8 q h s; every row of every plane is 4 q s long       -> every 4-pixel group 4 s-aligned
+//   4:2:2   fb = 8 q h s;  U at 4 q h s, V at 6 q h s; a chroma row is 2 q s long, a group's pair
+//           of chroma samples lies 2 s (x0 / 4) into it                                              -> every chroma pair 2 s-aligned
+// so the Y access (4 s bytes) and the 4:4:4 chroma access (4 s bytes) are naturally aligned, and the 4:2:2 chroma access (2 s bytes) is too.
+template <int SX> __device__ __forceinline__ int chroma_w(int w) { return SX == 2 ? (w + 1) / 2 : w; }
+inline long long yuvp_bytes(int h, int w, int sx) { return (long long)h * w + 2LL * h * (sx == 2 ? (w + 1) / 2 : w); }
+
+template <int SX, bool VEC>
+__global__ __launch_bounds__(256) void gather_yuvp_kernel(const uint8_t* __restrict__ src, int h, int w, long long fb, YuvIdx idx, int colour,
+                                                          float* __restrict__ out) {
+    __shared__ float lut[T_COUNT][256];
+#pragma unroll
+    for (int t = 0; t < T_COUNT; ++t) lut[t][threadIdx.x] = kYuvToRgb.c[colour].v[t][threadIdx.x];
+    __syncthreads();
+    const int k = blockIdx.y;
+    const long long npx = (long long)h * w;
+    const int cw = chroma_w<SX>(w);
+    const uint8_t* fy = src + (long long)idx.f[k] * fb;
+    const uint8_t* fu = fy + npx;
+    const uint8_t* fv = fu + (long long)h * cw;
+    float* o = out + (long long)k * 3 * npx;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const int wq = w / 4;
+        if (g >= (long long)h * wq) return;
+        const int y = (int)(g / wq), x0 = (int)(g % wq) * 4;
+        const long long p = (long long)y * w + x0;
+        const long long coff = (long long)y * cw + x0 / SX;
+        uint32_t uu, vv;
+        if (SX == 2) {
+            uu = *reinterpret_cast<const uint16_t*>(fu + coff);
+            vv = *reinterpret_cast<const uint16_t*>(fv + coff);
+        } else {
+            uu = *reinterpret_cast<const uint32_t*>(fu + coff);
+            vv = *reinterpret_cast<const uint32_t*>(fv + coff);
+        }
+        const uint32_t yy = *reinterpret_cast<const uint32_t*>(fy + p);
+        f32x4 r, gg, b;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float pr, pg, pb;
+            put_rgb(lut, (yy >> (8 * e)) & 255u, (uu >> (8 * (e / SX))) & 255u, (vv >> (8 * (e / SX))) & 255u, pr, pg, pb);
+            r[e] = pr; gg[e] = pg; b[e] = pb;
+        }
+        *reinterpret_cast<f32x4*>(o + p) = r;
+        *reinterpret_cast<f32x4*>(o + npx + p) = gg;
+        *reinterpret_cast<f32x4*>(o + 2 * npx + p) = b;
+    } else {
+        if (g >= (long long)h * cw) return;
+        const int cy = (int)(g / cw), cx = (int)(g % cw);
+        const uint32_t u = fu[(long long)cy * cw + cx], v = fv[(long long)cy * cw + cx];
+        for (int dx = 0; dx < SX && SX * cx + dx < w; ++dx) {
+            const long long p = (long long)cy * w + SX * cx + dx;
+            float pr, pg, pb;
+            put_rgb(lut, fy[p], u, v, pr, pg, pb);
+            o[p] = pr; o[npx + p] = pg; o[2 * npx + p] = pb;
+        }
+    }
+}
+
+// fp32 planar RGB [n][3][H][W] -> 4:2:2 / 4:4:4 frames [n][fb]: quantize_i420_kernel's arithmetic; Cb / Cr from (a + b) * 0.5 of a 4:2:2
+// pair, the pixel alone in the last column of an odd W, the pixel's own clamped RGB in 4:4:4.  C: the colour space, a template argument.
+template <int SX, bool VEC, int C>
+__global__ __launch_bounds__(256) void quantize_yuvp_kernel(const float* __restrict__ in, int H, int W, long long fb, uint8_t* __restrict__ out) {
+    const int k = blockIdx.y;
+    const long long npx = (long long)H * W;
+    const int cw = chroma_w<SX>(W);
+    const float* src = in + (long long)k * 3 * npx;
+    uint8_t* fy = out + (long long)k * fb;
+    uint8_t* fu = fy + npx;
+    uint8_t* fv = fu + (long long)H * cw;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const int wq = W / 4;
+        if (g >= (long long)H * wq) return;
+        const int y = (int)(g / wq), x0 = (int)(g % wq) * 4;
+        const long long p = (long long)y * W + x0;
+        f32x4 px[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + c * npx + p));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) px[c][e] = clamp01(x[e]);
+        }
+        uint32_t yy = 0u, uu = 0u, vv = 0u;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) yy |= luma_u8<C>(px[0][e], px[1][e], px[2][e]) << (8 * e);
+        *reinterpret_cast<uint32_t*>(fy + p) = yy;
+#pragma unroll
+        for (int j = 0; j < 4 / SX; ++j) {
+            float m[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) m[c] = SX == 2 ? (px[c][2 * j] + px[c][2 * j + 1]) * 0.5f : px[c][j];
+            uu |= cb_u8<C>(m[0], m[1], m[2]) << (8 * j);
+            vv |= cr_u8<C>(m[0], m[1], m[2]) << (8 * j);
+        }
+        const long long coff = (long long)y * cw + x0 / SX;
+        if (SX == 2) {
+            *reinterpret_cast<uint16_t*>(fu + coff) = (uint16_t)uu;
+            *reinterpret_cast<uint16_t*>(fv + coff) = (uint16_t)vv;
+        } else {
+            *reinterpret_cast<uint32_t*>(fu + coff) = uu;
+            *reinterpret_cast<uint32_t*>(fv + coff) = vv;
+        }
+    } else {
+        if (g >= (long long)H * cw) return;
+        const int cy = (int)(g / cw), cx = (int)(g % cw);
+        const bool two = SX == 2 && 2 * cx + 1 < W;
+        float q[2][3];
+        for (int dx = 0; dx < (two ? 2 : 1); ++dx) {
+            const long long p = (long long)cy * W + SX * cx + dx;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) q[dx][c] = clamp01(src[c * npx + p]);
+            fy[p] = (uint8_t)luma_u8<C>(q[dx][0], q[dx][1], q[dx][2]);
+        }
+        float m[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) m[c] = two ? (q[0][c] + q[1][c]) * 0.5f : q[0][c];
+        fu[(long long)cy * cw + cx] = (uint8_t)cb_u8<C>(m[0], m[1], m[2]);
+        fv[(long long)cy * cw + cx] = (uint8_t)cr_u8<C>(m[0], m[1], m[2]);
+    }
+}
+
+// The 10- / 12-bit forms: gather_i420_16_kernel's / quantize_i420_16_kernel's arithmetic on the blocks above.  VEC: 8 bytes of Y and
+// 4 (4:2:2) or 8 (4:4:4) bytes per chroma plane.
+template <int SX, bool VEC>
+__global__ __launch_bounds__(256) void gather_yuvp_16_kernel(const uint8_t* __restrict__ src, int h, int w, long long fb, YuvIdx idx, int ci, int di,
+                                                             uint32_t top, float* __restrict__ out) {
+    const ToRgb16 c = kToRgb16.c[ci][di];
+    const int k = blockIdx.y;
+    const long long npx = (long long)h * w;
+    const int cw = chroma_w<SX>(w);
+    const uint16_t* fy = reinterpret_cast<const uint16_t*>(src + (long long)idx.f[k] * fb);
+    const uint16_t* fu = fy + npx;
+    const uint16_t* fv = fu + (long long)h * cw;
+    float* o = out + (long long)k * 3 * npx;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const int wq = w / 4;
+        if (g >= (long long)h * wq) return;
+        const int y = (int)(g / wq), x0 = (int)(g % wq) * 4;
+        const long long p = (long long)y * w + x0;
+        const long long coff = (long long)y * cw + x0 / SX;
+        u32x2 uu = {0u, 0u}, vv = {0u, 0u};
+        if (SX == 2) {
+            uu[0] = *reinterpret_cast<const uint32_t*>(fu + coff);
+            vv[0] = *reinterpret_cast<const uint32_t*>(fv + coff);
+        } else {
+            uu = *reinterpret_cast<const u32x2*>(fu + coff);
+            vv = *reinterpret_cast<const u32x2*>(fv + coff);
+        }
+        const u32x2 yy = *reinterpret_cast<const u32x2*>(fy + p);
+        f32x4 r, gg, b;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int j = e / SX;                                   // the chroma sample over pixel e
+            float pr, pg, pb;
+            put_rgb16(c, min((yy[e >> 1] >> (16 * (e & 1))) & 0xffffu, top), min((uu[j >> 1] >> (16 * (j & 1))) & 0xffffu, top),
+                      min((vv[j >> 1] >> (16 * (j & 1))) & 0xffffu, top), pr, pg, pb);
+            r[e] = pr; gg[e] = pg; b[e] = pb;
+        }
+        *reinterpret_cast<f32x4*>(o + p) = r;
+        *reinterpret_cast<f32x4*>(o + npx + p) = gg;
+        *reinterpret_cast<f32x4*>(o + 2 * npx + p) = b;
+    } else {
+        if (g >= (long long)h * cw) return;
+        const int cy = (int)(g / cw), cx = (int)(g % cw);
+        const uint32_t u = min((uint32_t)fu[(long long)cy * cw + cx], top), v = min((uint32_t)fv[(long long)cy * cw + cx], top);
+        for (int dx = 0; dx < SX && SX * cx + dx < w; ++dx) {
+            const long long p = (long long)cy * w + SX * cx + dx;
+            float pr, pg, pb;
+            put_rgb16(c, min((uint32_t)fy[p], top), u, v, pr, pg, pb);
+            o[p] = pr; o[npx + p] = pg; o[2 * npx + p] = pb;
+        }
+    }
+}
+
+template <int SX, bool VEC, int C>
+__global__ __launch_bounds__(256) void quantize_yuvp_16_kernel(const float* __restrict__ in, int H, int W, long long fb, float k,
+                                                               uint8_t* __restrict__ out) {
+    constexpr YuvMatrix m = kYuv.m[C];
+    static_assert(!m.full, "high depth is defined for limited range only");
+    const int f = blockIdx.y;
+    const long long npx = (long long)H * W;
+    const int cw = chroma_w<SX>(W);
+    const float* src = in + (long long)f * 3 * npx;
+    uint16_t* fy = reinterpret_cast<uint16_t*>(out + (long long)f * fb);
+    uint16_t* fu = fy + npx;
+    uint16_t* fv = fu + (long long)H * cw;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const int wq = W / 4;
+        if (g >= (long long)H * wq) return;
+        const int y = (int)(g / wq), x0 = (int)(g % wq) * 4;
+        const long long p = (long long)y * W + x0;
+        f32x4 px[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + c * npx + p));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) px[c][e] = clamp01(x[e]);
+        }
+        u32x2 yy = {0u, 0u}, uu = {0u, 0u}, vv = {0u, 0u};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) yy[e >> 1] |= row3_u16(m.ky, m.oy, k, px[0][e], px[1][e], px[2][e]) << (16 * (e & 1));
+        *reinterpret_cast<u32x2*>(fy + p) = yy;
+#pragma unroll
+        for (int j = 0; j < 4 / SX; ++j) {
+            float mean[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) mean[c] = SX == 2 ? (px[c][2 * j] + px[c][2 * j + 1]) * 0.5f : px[c][j];
+            uu[j >> 1] |= row3_u16(m.kcb, m.oc, k, mean[0], mean[1], mean[2]) << (16 * (j & 1));
+            vv[j >> 1] |= row3_u16(m.kcr, m.oc, k, mean[0], mean[1], mean[2]) << (16 * (j & 1));
+        }
+        const long long coff = (long long)y * cw + x0 / SX;
+        if (SX == 2) {
+            *reinterpret_cast<uint32_t*>(fu + coff) = uu[0];
+            *reinterpret_cast<uint32_t*>(fv + coff) = vv[0];
+        } else {
+            *reinterpret_cast<u32x2*>(fu + coff) = uu;
+            *reinterpret_cast<u32x2*>(fv + coff) = vv;
+        }
+    } else {
+        if (g >= (long long)H * cw) return;
+        const int cy = (int)(g / cw), cx = (int)(g % cw);
+        const bool two = SX == 2 && 2 * cx + 1 < W;
+        float q[2][3];
+        for (int dx = 0; dx < (two ? 2 : 1); ++dx) {
+            const long long p = (long long)cy * W + SX * cx + dx;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) q[dx][c] = clamp01(src[c * npx + p]);
+            fy[p] = (uint16_t)row3_u16(m.ky, m.oy, k, q[dx][0], q[dx][1], q[dx][2]);
+        }
+        float mean[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) mean[c] = two ? (q[0][c] + q[1][c]) * 0.5f : q[0][c];
+        fu[(long long)cy * cw + cx] = (uint16_t)row3_u16(m.kcb, m.oc, k, mean[0], mean[1], mean[2]);
+        fv[(long long)cy * cw + cx] = (uint16_t)row3_u16(m.kcr, m.oc, k, mean[0], mean[1], mean[2]);
+    }
+}
+
+// The high-depth entries' bodies: `what` names the entry called in its messages.
+int gather_yuv420_16(const char* what, const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, int colour, int depth,
+                     float* out, void* stream) {
+    if (!frames || !out) return fail(what, "null pointer");
+    if (h < 1 || w < 1 || n_frames < 1) return fail(what, "h, w, n_frames >= 1");
+    if (int rc = check_depth16(colour, depth, what)) return rc;
+    if (reinterpret_cast<uintptr_t>(frames) & 1) return fail(what, "frames must be 2-byte aligned (16-bit samples)");
+    if (reinterpret_cast<uintptr_t>(out) & 3) return fail(what, "out must be 4-byte aligned");
+    YuvIdx gi;
+    if (int rc = load_idx(idx, n_idx, n_frames, &gi, what)) return rc;
+    const bool vec = w % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    const long long units = (long long)((h + 1) / 2) * (vec ? w / 4 : (w + 1) / 2);
+    const dim3 grid(blocks_for(units), n_idx);
+    const long long fb = 2 * i420_bytes(h, w);
+    const int di = depth == 10 ? 0 : 1;
+    const uint32_t top = (1u << depth) - 1u;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (vec) hipLaunchKernelGGL((gather_i420_16_kernel<true>), grid, dim3(256), 0, st, frames, h, w, fb, gi, colour, di, top, out);
+    else hipLaunchKernelGGL((gather_i420_16_kernel<false>), grid, dim3(256), 0, st, frames, h, w, fb, gi, colour, di, top, out);
+    return check_launch("gather_i420_16_kernel");
+}
+
+int quantize_yuv420_16(const char* what, const float* in, int n, int H, int W, int colour, int depth, uint8_t* out, void* stream) {
+    if (!in || !out) return fail(what, "null pointer");
+    if (n < 1 || n > 65535 || H < 1 || W < 1) return fail(what, "n in 1 .. 65535, H, W >= 1");
+    if (int rc = check_depth16(colour, depth, what)) return rc;
+    if (reinterpret_cast<uintptr_t>(out) & 1) return fail(what, "out must be 2-byte aligned (16-bit samples)");
+    if (reinterpret_cast<uintptr_t>(in) & 3) return fail(what, "in must be 4-byte aligned");
+    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0;
+    const long long units = (long long)((H + 1) / 2) * (vec ? W / 4 : (W + 1) / 2);
+    const dim3 grid(blocks_for(units), n);
+    const long long fb = 2 * i420_bytes(H, W);
+    const float k = (float)(1 << (depth - 8));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (colour == 0) {
+        if (vec) hipLaunchKernelGGL((quantize_i420_16_kernel<true, 0>), grid, dim3(256), 0, st, in, H, W, fb, k, out);
+        else hipLaunchKernelGGL((quantize_i420_16_kernel<false, 0>), grid, dim3(256), 0, st, in, H, W, fb, k, out);
+    } else {
+        if (vec) hipLaunchKernelGGL((quantize_i420_16_kernel<true, 1>), grid, dim3(256), 0, st, in, H, W, fb, k, out);
+        else hipLaunchKernelGGL((quantize_i420_16_kernel<false, 1>), grid, dim3(256), 0, st, in, H, W, fb, k, out);
+    }
+    return check_launch("quantize_i420_16_kernel");
+}
+
+// ---- ABI 39: the entries of every chroma layout ---------------------------------------------------------------------------------------
+int check_chroma_depth(int chroma, int depth, const char* what) {
+    if (chroma < SAVSR_CHROMA_420 || chroma > SAVSR_CHROMA_444) {
+        set_error("invalid argument: %s: chroma %d (0 = 4:2:0, 1 = 4:2:2, 2 = 4:4:4)", what, chroma);
+        return SAVSR_E_ARG;
+    }
+    if (depth != 8 && depth != 10 && depth != 12) { set_error("invalid argument: %s: depth %d (8, 10 or 12)", what, depth); return SAVSR_E_ARG; }
+    return 0;
+}
+
+template <int SX>
+void launch_gather_yuvp(bool vec, dim3 grid, hipStream_t st, const uint8_t* frames, int h, int w, long long fb, const YuvIdx& gi, int colour,
+                        int depth, float* out) {
+    if (depth == 8) {
+        if (vec) hipLaunchKernelGGL((gather_yuvp_kernel<SX, true>), grid, dim3(256), 0, st, frames, h, w, fb, gi, colour, out);
+        else hipLaunchKernelGGL((gather_yuvp_kernel<SX, false>), grid, dim3(256), 0, st, frames, h, w, fb, gi, colour, out);
+    } else {
+        const int di = depth == 10 ? 0 : 1;
+        const uint32_t top = (1u << depth) - 1u;
+        if (vec) hipLaunchKernelGGL((gather_yuvp_16_kernel<SX, true>), grid, dim3(256), 0, st, frames, h, w, fb, gi, colour, di, top, out);
+        else hipLaunchKernelGGL((gather_yuvp_16_kernel<SX, false>), grid, dim3(256), 0, st, frames, h, w, fb, gi, colour, di, top, out);
+    }
+}
+
+template <int SX, int C>
+void launch_quantize_yuvp(bool vec, dim3 grid, hipStream_t st, const float* in, int H, int W, long long fb, uint8_t* out) {
+    if (vec) hipLaunchKernelGGL((quantize_yuvp_kernel<SX, true, C>), grid, dim3(256), 0, st, in, H, W, fb, out);
+    else hipLaunchKernelGGL((quantize_yuvp_kernel<SX, false, C>), grid, dim3(256), 0, st, in, H, W, fb, out);
+}
+template <int SX, int C>
+void launch_quantize_yuvp_16(bool vec, dim3 grid, hipStream_t st, const float* in, int H, int W, long long fb, float k, uint8_t* out) {
+    if (vec) hipLaunchKernelGGL((quantize_yuvp_16_kernel<SX, true, C>), grid, dim3(256), 0, st, in, H, W, fb, k, out);
+    else hipLaunchKernelGGL((quantize_yuvp_16_kernel<SX, false, C>), grid, dim3(256), 0, st, in, H, W, fb, k, out);
+}
+template <int SX>
+void launch_quantize_yuvp_any(bool vec, dim3 grid, hipStream_t st, const float* in, int H, int W, long long fb, int colour, int depth,
+                              uint8_t* out) {
+    if (depth == 8) {
+        switch (colour) {
+            case 0: launch_quantize_yuvp<SX, 0>(vec, grid, st, in, H, W, fb, out); break;
+            case 1: launch_quantize_yuvp<SX, 1>(vec, grid, st, in, H, W, fb, out); break;
+            case 2: launch_quantize_yuvp<SX, 2>(vec, grid, st, in, H, W, fb, out); break;
+            default: launch_quantize_yuvp<SX, 3>(vec, grid, st, in, H, W, fb, out); break;
+        }
+    } else {
+        const float k = (float)(1 << (depth - 8));
+        if (colour == 0) launch_quantize_yuvp_16<SX, 0>(vec, grid, st, in, H, W, fb, k, out);
+        else launch_quantize_yuvp_16<SX, 1>(vec, grid, st, in, H, W, fb, k, out);
+    }
+}
+
 }  // namespace
 }  // namespace savsr
 
@@ -534,45 +879,62 @@ extern "C" int savsr_video_quantize_i420(const float* in, int n, int H, int W, u
 // ABI 38: 10- and 12-bit frames, little-endian 16-bit samples in the I420 plane order.
 extern "C" int savsr_video_gather_yuv420_16(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, int colour, int depth,
                                             float* out, void* stream) {
-    const char* what = "video_gather_yuv420_16";
-    if (!frames || !out) return fail(what, "null pointer");
-    if (h < 1 || w < 1 || n_frames < 1) return fail(what, "h, w, n_frames >= 1");
-    if (int rc = check_depth16(colour, depth, what)) return rc;
-    if (reinterpret_cast<uintptr_t>(frames) & 1) return fail(what, "frames must be 2-byte aligned (16-bit samples)");
-    if (reinterpret_cast<uintptr_t>(out) & 3) return fail(what, "out must be 4-byte aligned");
-    YuvIdx gi;
-    if (int rc = load_idx(idx, n_idx, n_frames, &gi, what)) return rc;
-    const bool vec = w % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-    const long long units = (long long)((h + 1) / 2) * (vec ? w / 4 : (w + 1) / 2);
-    const dim3 grid(blocks_for(units), n_idx);
-    const long long fb = 2 * i420_bytes(h, w);
-    const int di = depth == 10 ? 0 : 1;
-    const uint32_t top = (1u << depth) - 1u;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (vec) hipLaunchKernelGGL((gather_i420_16_kernel<true>), grid, dim3(256), 0, st, frames, h, w, fb, gi, colour, di, top, out);
-    else hipLaunchKernelGGL((gather_i420_16_kernel<false>), grid, dim3(256), 0, st, frames, h, w, fb, gi, colour, di, top, out);
-    return check_launch("gather_i420_16_kernel");
+    return gather_yuv420_16("video_gather_yuv420_16", frames, n_frames, h, w, idx, n_idx, colour, depth, out, stream);
 }
 
 extern "C" int savsr_video_quantize_yuv420_16(const float* in, int n, int H, int W, int colour, int depth, uint8_t* out, void* stream) {
-    const char* what = "video_quantize_yuv420_16";
+    return quantize_yuv420_16("video_quantize_yuv420_16", in, n, H, W, colour, depth, out, stream);
+}
+
+// ABI 39: one entry per side for every (chroma layout, depth).  chroma = SAVSR_CHROMA_420 runs the kernels above.
+extern "C" int savsr_video_gather_yuvp(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, int colour, int depth,
+                                       int chroma, float* out, void* stream) {
+    const char* what = "video_gather_yuvp";
+    if (int rc = check_chroma_depth(chroma, depth, what)) return rc;
+    if (!frames || !out) return fail(what, "null pointer");
+    if (h < 1 || w < 1 || n_frames < 1) return fail(what, "h, w, n_frames >= 1");
+    if (depth == 8) { if (int rc = check_colour(colour, what)) return rc; }
+    else if (int rc = check_depth16(colour, depth, what)) return rc;
+    if (depth != 8 && (reinterpret_cast<uintptr_t>(frames) & 1)) return fail(what, "frames must be 2-byte aligned (16-bit samples)");
+    if (reinterpret_cast<uintptr_t>(out) & 3) return fail(what, "out must be 4-byte aligned");
+    if (chroma == SAVSR_CHROMA_420) {
+        return depth == 8 ? gather_yuv420(what, frames, n_frames, h, w, idx, n_idx, colour, out, stream)
+                          : gather_yuv420_16(what, frames, n_frames, h, w, idx, n_idx, colour, depth, out, stream);
+    }
+    YuvIdx gi;
+    if (int rc = load_idx(idx, n_idx, n_frames, &gi, what)) return rc;
+    const int sx = chroma == SAVSR_CHROMA_422 ? 2 : 1;
+    const uintptr_t fmask = depth == 8 ? 3 : 7;
+    const bool vec = w % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & fmask) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    const long long units = (long long)h * (vec ? w / 4 : (sx == 2 ? (w + 1) / 2 : w));
+    const dim3 grid(blocks_for(units), n_idx);
+    const long long fb = yuvp_bytes(h, w, sx) * (depth == 8 ? 1 : 2);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (sx == 2) launch_gather_yuvp<2>(vec, grid, st, frames, h, w, fb, gi, colour, depth, out);
+    else launch_gather_yuvp<1>(vec, grid, st, frames, h, w, fb, gi, colour, depth, out);
+    return check_launch(depth == 8 ? "gather_yuvp_kernel" : "gather_yuvp_16_kernel");
+}
+
+extern "C" int savsr_video_quantize_yuvp(const float* in, int n, int H, int W, int colour, int depth, int chroma, uint8_t* out, void* stream) {
+    const char* what = "video_quantize_yuvp";
+    if (int rc = check_chroma_depth(chroma, depth, what)) return rc;
     if (!in || !out) return fail(what, "null pointer");
     if (n < 1 || n > 65535 || H < 1 || W < 1) return fail(what, "n in 1 .. 65535, H, W >= 1");
-    if (int rc = check_depth16(colour, depth, what)) return rc;
-    if (reinterpret_cast<uintptr_t>(out) & 1) return fail(what, "out must be 2-byte aligned (16-bit samples)");
+    if (depth == 8) { if (int rc = check_colour(colour, what)) return rc; }
+    else if (int rc = check_depth16(colour, depth, what)) return rc;
+    if (depth != 8 && (reinterpret_cast<uintptr_t>(out) & 1)) return fail(what, "out must be 2-byte aligned (16-bit samples)");
     if (reinterpret_cast<uintptr_t>(in) & 3) return fail(what, "in must be 4-byte aligned");
-    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0;
-    const long long units = (long long)((H + 1) / 2) * (vec ? W / 4 : (W + 1) / 2);
-    const dim3 grid(blocks_for(units), n);
-    const long long fb = 2 * i420_bytes(H, W);
-    const float k = (float)(1 << (depth - 8));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (colour == 0) {
-        if (vec) hipLaunchKernelGGL((quantize_i420_16_kernel<true, 0>), grid, dim3(256), 0, st, in, H, W, fb, k, out);
-        else hipLaunchKernelGGL((quantize_i420_16_kernel<false, 0>), grid, dim3(256), 0, st, in, H, W, fb, k, out);
-    } else {
-        if (vec) hipLaunchKernelGGL((quantize_i420_16_kernel<true, 1>), grid, dim3(256), 0, st, in, H, W, fb, k, out);
-        else hipLaunchKernelGGL((quantize_i420_16_kernel<false, 1>), grid, dim3(256), 0, st, in, H, W, fb, k, out);
+    if (chroma == SAVSR_CHROMA_420) {
+        return depth == 8 ? quantize_yuv420(what, in, n, H, W, colour, out, stream) : quantize_yuv420_16(what, in, n, H, W, colour, depth, out, stream);
     }
-    return check_launch("quantize_i420_16_kernel");
+    const int sx = chroma == SAVSR_CHROMA_422 ? 2 : 1;
+    const uintptr_t omask = depth == 8 ? 3 : 7;
+    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & omask) == 0;
+    const long long units = (long long)H * (vec ? W / 4 : (sx == 2 ? (W + 1) / 2 : W));
+    const dim3 grid(blocks_for(units), n);
+    const long long fb = yuvp_bytes(H, W, sx) * (depth == 8 ? 1 : 2);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (sx == 2) launch_quantize_yuvp_any<2>(vec, grid, st, in, H, W, fb, colour, depth, out);
+    else launch_quantize_yuvp_any<1>(vec, grid, st, in, H, W, fb, colour, depth, out);
+    return check_launch(depth == 8 ? "quantize_yuvp_kernel" : "quantize_yuvp_16_kernel");
 }

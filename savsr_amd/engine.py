@@ -34,7 +34,7 @@ from .config import EngineConfig
 from .launch import MAX_SUM_BLOCKS, Launcher, Src, _ptr      # noqa: F401
 from .packing import (BN_EPS, CONV_TH, CONV_TW, WeightPacking, acc_row, conv_pack_geometry, conv_pack_index, conv_wy_pack_index, get_hw,      # noqa: F401  (re-exported:
                       pack_conv_part, pack_conv_weight, pack_conv_weight_wy, satu_axis_tables, split_bf16_image, window_record)                            # tests and tools import them from here)
-from .yuv import COLOURS, i420_bytes
+from .yuv import CHROMAS, COLOURS, frame_bytes, layout_name
 
 
 class HipEngine(WeightPacking, ContextCache, Launcher):
@@ -798,7 +798,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
 
     def forward_video(self, frames: torch.Tensor, windows: List[List[int]], scale, out_u8: bool = False, ensemble: bool = False,
                       i420: Optional[Tuple[int, int]] = None, out_i420: bool = False, colour: int = 0, out_colour: int = 0, depth: int = 8,
-                      out_depth: int = 8) -> torch.Tensor:
+                      out_depth: int = 8, chroma: int = 0, out_chroma: int = 0) -> torch.Tensor:
         """The sequence path (SAVSR.upscale_video): frames [N, h, w, c] uint8 or [N, c, h, w] fp32 on the device, windows[i] = the
         num_frame frame indices of output frame i in clip order (harness.window_indices) -> [len(windows), c, H, W] fp32, or
         [len(windows), H, W, c] uint8 (out_u8: tensor2img(x, rgb2bgr=False) per frame, savsr_video_quantize_u8).
@@ -806,13 +806,14 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         `streams_for` streams; throughput flow), so frame i equals forward_many on the gathered window i bit for bit.  A unit's windows are
         gathered from `frames` by savsr_video_gather_u8 / _f32 into a unit-sized fp32 clip batch on the unit's stream; nothing is gathered
         or converted on the host.  ensemble=True: frame i is the self-ensemble of window i (`_ensemble`, gathered by savsr_ensemble_gather_*).
-        i420=(h, w): frames are [N, i420_bytes(h, w)] uint8, planar YUV 4:2:0 (savsr_amd/yuv.py), gathered by savsr_video_gather_yuv420 where
-        the uint8 gather runs; out_i420: the result is [len(windows), i420_bytes(H, W)] uint8, quantised by savsr_video_quantize_yuv420 where
+        i420=(h, w): frames are [N, i420_bytes(h, w)] uint8, planar YUV 4:2:0 (savsr_amd/yuv.py), gathered by savsr_video_gather_yuvp where
+        the uint8 gather runs; out_i420: the result is [len(windows), i420_bytes(H, W)] uint8, quantised by savsr_video_quantize_yuvp where
         the uint8 quantisation runs.  colour / out_colour: the colour space ids (positions in yuv.COLOURS) of the I420 input / output.  With
         the ensemble, I420 frames are converted once to fp32 planar RGB (the same gather with the identity list) and take the fp32 path,
         and an I420 result is the fp32 merge followed by the quantisation.  depth / out_depth = 10, 12: the I420 frames in / out hold 16-bit
-        samples ([N, 2 * i420_bytes] uint8, limited range only); savsr_video_gather_yuv420_16 / savsr_video_quantize_yuv420_16 run where the
-        8-bit entries do, and nothing else changes."""
+        samples ([N, 2 * i420_bytes] uint8, limited range only), and nothing else changes.  chroma / out_chroma: the chroma layout ids
+        (positions in yuv.CHROMAS: 4:2:0, 4:2:2, 4:4:4) of the YUV input / output, [N, frame_bytes(h, w, depth, chroma)] uint8.  The two
+        entries serve every (layout, depth); at 4:2:0 they run the kernels of savsr_video_gather_yuv420(_16) / _quantize_yuv420(_16)."""
         if out_u8 and out_i420:
             raise ValueError("one output kind: uint8 or I420")
         for what, d, on, cs in (("depth", depth, i420 is not None, colour), ("out_depth", out_depth, out_i420, out_colour)):
@@ -822,10 +823,15 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
                 raise ValueError(f"{what} = {d} with colour id {cs}: 10 and 12 bits are defined for limited range only ({COLOURS[0]}, {COLOURS[1]})")
         if not (0 <= colour < len(COLOURS) and 0 <= out_colour < len(COLOURS)):
             raise ValueError(f"colour ids {colour}, {out_colour}: 0 .. {len(COLOURS) - 1} ({', '.join(COLOURS)})")
+        for what, cid, on in (("chroma", chroma, i420 is not None), ("out_chroma", out_chroma, out_i420)):
+            if cid not in range(len(CHROMAS)) or (cid != 0 and not on):
+                raise ValueError(f"{what} = {cid!r}: 0 .. {len(CHROMAS) - 1} ({', '.join(CHROMAS)}), and not 0 with YUV frames on that side only")
+        lay, out_lay = CHROMAS[chroma], CHROMAS[out_chroma]
         if i420 is not None:
             h, w = (int(v) for v in i420)
-            if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != i420_bytes(h, w, depth):
-                raise ValueError(f"I420 frames of {h} x {w} are [N, {i420_bytes(h, w, depth)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+            if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != frame_bytes(h, w, depth, lay):
+                raise ValueError(f"{layout_name(lay)} frames of {h} x {w} are [N, {frame_bytes(h, w, depth, lay)}] uint8, "
+                                 f"got {frames.dtype} {tuple(frames.shape)}")
             u8, N, c = True, int(frames.shape[0]), 3
         else:
             u8, N, c, h, w = _frames_layout(frames)
@@ -839,7 +845,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         H, W = get_hw(h, w, scale)
         n = len(windows)
         if out_i420:
-            out = torch.empty(n, i420_bytes(H, W, out_depth), device=self.dev, dtype=torch.uint8)
+            out = torch.empty(n, frame_bytes(H, W, out_depth, out_lay), device=self.dev, dtype=torch.uint8)
         else:
             out = (torch.empty(n, H, W, c, device=self.dev, dtype=torch.uint8) if out_u8 else
                    torch.empty(n, c, H, W, device=self.dev, dtype=torch.float32))
@@ -847,14 +853,10 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             return out
         if T > _lib.VIDEO_MAX_SLOTS:
             raise ValueError(f"num_frame = {T}: the window gather takes at most {_lib.VIDEO_MAX_SLOTS} frames per launch")
-        if i420 is not None and depth != 8:
+        if i420 is not None:
             def gather(idx, dst, st):
-                _lib.check(self.lib.savsr_video_gather_yuv420_16(frames.data_ptr(), N, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), colour,
-                                                                 depth, dst.data_ptr(), st), "savsr_video_gather_yuv420_16")
-        elif i420 is not None:
-            def gather(idx, dst, st):
-                _lib.check(self.lib.savsr_video_gather_yuv420(frames.data_ptr(), N, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), colour,
-                                                              dst.data_ptr(), st), "savsr_video_gather_yuv420")
+                _lib.check(self.lib.savsr_video_gather_yuvp(frames.data_ptr(), N, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), colour, depth,
+                                                            chroma, dst.data_ptr(), st), "savsr_video_gather_yuvp")
         else:
             fn = self.lib.savsr_video_gather_u8 if u8 else self.lib.savsr_video_gather_f32
 
@@ -864,12 +866,9 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         def quantize(src, dst, st):
             for a in range(0, int(src.shape[0]), 65535):          # (the entries take 1 .. 65535 frames)
                 nb = min(65535, int(src.shape[0]) - a)
-                if out_i420 and out_depth != 8:
-                    _lib.check(self.lib.savsr_video_quantize_yuv420_16(src[a:a + nb].data_ptr(), nb, H, W, out_colour, out_depth,
-                                                                       dst[a:a + nb].data_ptr(), st), "savsr_video_quantize_yuv420_16")
-                elif out_i420:
-                    _lib.check(self.lib.savsr_video_quantize_yuv420(src[a:a + nb].data_ptr(), nb, H, W, out_colour, dst[a:a + nb].data_ptr(), st),
-                               "savsr_video_quantize_yuv420")
+                if out_i420:
+                    _lib.check(self.lib.savsr_video_quantize_yuvp(src[a:a + nb].data_ptr(), nb, H, W, out_colour, out_depth, out_chroma,
+                                                                  dst[a:a + nb].data_ptr(), st), "savsr_video_quantize_yuvp")
                 else:
                     _lib.check(self.lib.savsr_video_quantize_u8(src[a:a + nb].data_ptr(), nb, c, H, W, dst[a:a + nb].data_ptr(), st), "savsr_video_quantize_u8")
         if ensemble:

@@ -7,7 +7,7 @@ a + window_indices(i - a, b - a, num_frame, mode), mode = the call's padding if 
 the segments.
 
 The detector: per pair of consecutive frames the sum of absolute differences of their 8-bit samples (`pair_sad`, the specification of
-savsr_video_pair_sad_u8 / _i420 / _i420_16 / _f32 in csrc/scene.hip), then ffmpeg scdet's rule in exact arithmetic (`cuts_from_sad`).
+savsr_video_pair_sad_u8 / _i420 / _i420_16 / _yuvp / _f32 in csrc/scene.hip), then ffmpeg scdet's rule in exact arithmetic (`cuts_from_sad`).
 
 `ScenePlan` is the streaming form's bookkeeping (VideoUpscaler with cuts): which frames can be returned, with which windows, and which
 past frames must be kept, when cuts and the end of the video are only known up to the last pushed frame.
@@ -23,8 +23,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from .harness import window_indices
-from .video import check_length, check_padding, check_pixel_format
-from .yuv import check_depth, i420_bytes, split_planes
+from .video import check_length, check_padding, check_pixel_format, chroma_of
+from .yuv import check_depth, frame_bytes, layout_name, split_planes
 
 
 # ---- the detector --------------------------------------------------------------------------------------------------------------------
@@ -43,13 +43,15 @@ def _samples_of(frames, pixel_format: str, size, depth: int = 8) -> np.ndarray:
     if depth != 8:
         depth = check_depth(depth)
         if not i420:
-            raise ValueError(f"depth = {depth} goes with pixel_format = 'i420': it is the bit depth of I420 input")
-        y = split_planes(frames, i420[0], i420[1], depth)[0]
+            raise ValueError(f"depth = {depth} goes with pixel_format = 'i420', 'i422' or 'i444': it is the bit depth of YUV input")
+        y = split_planes(frames, i420[0], i420[1], depth, chroma_of(pixel_format))[0]
         return (np.minimum(y, np.uint16((1 << depth) - 1)) >> (depth - 8)).astype(np.uint8).reshape(y.shape[0], -1)
     if i420:
         h, w = i420
-        if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != i420_bytes(h, w):
-            raise ValueError(f"I420 frames of {h} x {w} are [N, {i420_bytes(h, w)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+        chroma = chroma_of(pixel_format)
+        if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != frame_bytes(h, w, 8, chroma):
+            raise ValueError(f"{layout_name(chroma)} frames of {h} x {w} are [N, {frame_bytes(h, w, 8, chroma)}] uint8, "
+                             f"got {frames.dtype} {tuple(frames.shape)}")
         return frames[:, :h * w]
     if frames.ndim != 4:
         raise ValueError(f"frames must be [N, h, w, c] uint8 or [N, c, h, w] float, got {frames.ndim} dimensions")
@@ -61,7 +63,7 @@ def _samples_of(frames, pixel_format: str, size, depth: int = 8) -> np.ndarray:
 
 
 def sad_samples(shape: Sequence[int], pixel_format: str = "rgb", size=None) -> int:
-    """S, the samples compared per pair: c * h * w of RGB frames (either layout), h * w (the Y plane) of I420 frames."""
+    """S, the samples compared per pair: c * h * w of RGB frames (either layout), h * w (the Y plane) of YUV frames (i420, i422, i444)."""
     i420 = check_pixel_format(pixel_format, size)
     if i420:
         return i420[0] * i420[1]
@@ -74,7 +76,8 @@ def pair_sad(frames, pixel_format: str = "rgb", size=None, depth: int = 8) -> np
     """int64 [N - 1]: entry j is the sum of absolute differences of the 8-bit samples of frames j and j + 1.
     [N, h, w, c] uint8: every byte.  I420 ([N, i420_bytes(h, w)] uint8, size=(h, w)): the Y plane only.  [N, c, h, w] float: every value
     after `quantize_u8`.  depth = 10, 12 (I420 frames of 16-bit samples, [N, 2 * i420_bytes(h, w)] uint8): the Y plane's samples as their 8
-    most significant bits, min(s, 2^depth - 1) >> (depth - 8), so the scores -- and with them the threshold -- keep the 8-bit scale."""
+    most significant bits, min(s, 2^depth - 1) >> (depth - 8), so the scores -- and with them the threshold -- keep the 8-bit scale.
+    pixel_format = "i422" / "i444": the Y plane of those layouts (the first h * w samples of a frame), exactly as for I420."""
     s = _samples_of(frames, pixel_format, size, depth).astype(np.int64)
     if s.shape[0] < 1:
         raise ValueError("the video has no frames")

@@ -8,13 +8,14 @@
     python -m savsr_amd.upscale -i in.y4m -o out.y4m --scale 4 --checkpoint <net.pth> --cuts auto --cuts-out cuts.txt
     python -m savsr_amd.upscale -i sd.y4m -o hd.y4m --scale 4 --checkpoint <net.pth> --colour auto --out-colour auto
     python -m savsr_amd.upscale -i in8.y4m -o out10.y4m --scale 4 --checkpoint <net.pth> --out-depth 10
+    ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out444p10.y4m --scale 4 --checkpoint <net.pth> --out-chroma 444
 
 PNG folder: frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on
 the FrameStore pool (savsr_amd.io), pushed through VideoUpscaler in chunks (uint8 in, uint8 out: the windows, the network and the
 quantisation run on the GPU) and encoded on a writer pool of this tool's own (at most 16 threads).
 
 Y4M (a name ending in .y4m, or - for stdin / stdout; savsr_amd/y4m.py): planar YUV 4:2:0 bytes go to the GPU and come back as they are
-(pixel_format / out = "i420": colour conversion, chroma resampling and the one rounding happen there, savsr_amd/yuv.py).  On a pipe the
+(pixel_format / out = "i420", "i422" or "i444": colour conversion, chroma resampling and the one rounding happen there, savsr_amd/yuv.py).  On a pipe the
 video's length is not known, so a video too short for the window is refused when the input ends.  The SR frames are copied into pinned
 buffers and written by one ordered writer thread while the next chunk runs.  The two kinds mix: .y4m in, folder out writes %08d.png;
 folder in, .y4m out takes its frame rate from --fps.
@@ -32,6 +33,11 @@ when either flag was given.
 (C420p10 / C420p12, what `ffmpeg -f yuv4mpegpipe` emits for a 10-bit source) is read as it is; its depth comes from the header.  8-bit in,
 --out-depth 10 costs nothing extra in the network and keeps the two bits the 8-bit rounding throws away (what HEVC / AV1 encoders take
 by default is yuv420p10).  10 and 12 bits go with limited range only: a full-range colour space on a high-depth side is refused.
+
+--out-chroma: the chroma layout of a Y4M output, 420, 422, 444 or same (the default: the input's; 4:2:0 for a PNG folder).  A 4:2:2 or
+4:4:4 Y4M input (C422, C444 and their p10 / p12 forms) is read as it is; its layout comes from the header.  The two sides are
+independent: 4:2:0 in, --out-chroma 444 writes the network's full-resolution chroma instead of box-filtering it 2 x 2.  Chroma is
+centre-sited in every layout; the cosited convention of MPEG-2 4:2:2 is not modelled.
 
 --cuts: edited footage.  Windows stop at scene cuts (every scene is upscaled as a video of its own, savsr_amd/scenes.py): auto finds
 them on the GPU as the frames arrive (--scene-threshold, per cent of the largest possible frame change; ffmpeg scdet's rule and default,
@@ -114,6 +120,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--out-depth", default=None, choices=["8", "10", "12", "same"],
                    help="bit depth of a Y4M output (default same: the input's; 8 for a PNG folder).  10 / 12 write C420p10 / C420p12, limited range "
                         "only; 8-bit in, 10 out keeps the precision the 8-bit rounding loses")
+    p.add_argument("--out-chroma", default=None, choices=["420", "422", "444", "same"],
+                   help="chroma layout of a Y4M output (default same: the input's; 420 for a PNG folder).  422 / 444 write C422 / C444 "
+                        "(C422p10 ... with --out-depth 10 / 12); 444 keeps the network's full-resolution chroma")
     p.add_argument("--cuts", default=None, metavar="auto|K,K,...|@FILE",
                    help="scene cuts (first frame of every new scene): auto = found on the GPU, a comma-separated list, or @FILE with one index "
                         "per line; windows stop at cuts")
@@ -175,7 +184,10 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--out-colour goes with a Y4M output (PNG frames are RGB)")
     if a.out_depth is not None and not a.y4m_out:
         p.error("--out-depth goes with a Y4M output (PNG frames are 8-bit RGB)")
+    if a.out_chroma is not None and not a.y4m_out:
+        p.error("--out-chroma goes with a Y4M output (PNG frames are RGB)")
     a.out_depth = None if a.out_depth in (None, "same") else int(a.out_depth)          # (None: the input's)
+    a.out_chroma = None if a.out_chroma in (None, "same") else a.out_chroma            # (None: the input's)
     a.colour_flags = a.colour is not None or a.out_colour is not None       # (either given: the output is tagged, the summary names them)
     a.colour = a.colour or "bt601"
     a.out_colour = a.out_colour or "same"
@@ -316,7 +328,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     from .utils.host import effective_cpus
     from .video import VideoUpscaler, check_length
     from .y4m import Y4MReader, Y4MWriter, scaled_aspect
-    from .yuv import is_full_range
+    from .yuv import CHROMAS, FORMAT_OF, is_full_range
 
     net = load_net(a)
     net.set_precision(a.precision)
@@ -332,15 +344,15 @@ def main(argv: Optional[List[str]] = None) -> int:
             if a.input != "-" and not os.path.isfile(a.input):
                 raise SystemExit(f"input file {a.input!r} does not exist")
             fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
-            reader = Y4MReader(fin, high_depth=True)
-            h, w, depth = reader.height, reader.width, reader.depth
+            reader = Y4MReader(fin, high_depth=True, layouts=CHROMAS)
+            h, w, depth, chroma = reader.height, reader.width, reader.depth, reader.chroma
             fps, interlace, aspect, in_range = reader.fps, reader.interlace, reader.aspect, reader.colour_range
             chunks = (torch.from_numpy(c) for c in reader.chunks(a.chunk))
         else:
             from .io import FrameStore
             store = FrameStore()
             h = w = None
-            depth = 8
+            depth, chroma = 8, "420"
             if a.y4m_out:                           # (the Y4M header needs the SR size before the first frame: the PNG's header gives it)
                 from PIL import Image
                 with Image.open(paths[0]) as im:
@@ -357,9 +369,11 @@ def main(argv: Optional[List[str]] = None) -> int:
         hr = get_hw(h, w, a.scale) if a.y4m_out else None
         colour, out_colour = resolve_colours(a.colour, a.out_colour, (h, w) if a.y4m_in else None, hr, in_range)
         out_depth = (depth if a.out_depth is None else a.out_depth) if a.y4m_out else None
+        out_chroma = (chroma if a.out_chroma is None else a.out_chroma) if a.y4m_out else None
+        fmt_in, fmt_out = FORMAT_OF[chroma] if a.y4m_in else "rgb", FORMAT_OF[out_chroma] if a.y4m_out else "uint8"
         from .video import check_depths
         try:                                        # (before the output is opened: a full-range colour with 10 / 12 bits is refused)
-            check_depths(depth, out_depth, "i420" if a.y4m_in else "rgb", "i420" if a.y4m_out else "uint8", colour or "bt601", out_colour)
+            check_depths(depth, out_depth, fmt_in, fmt_out, colour or "bt601", out_colour)
         except ValueError as e:
             raise SystemExit(f"--colour / --out-colour / --out-depth: {e}") from None
         if a.y4m_out:
@@ -367,12 +381,13 @@ def main(argv: Optional[List[str]] = None) -> int:
             fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
             full = is_full_range(out_colour)
             tag = ("full" if full else "limited") if (full or a.colour_flags) else None
-            sink = Y4MSink(Y4MWriter(fout, W, H, fps, interlace, scaled_aspect(aspect, (h, w), (H, W)), tag, depth=out_depth), a.chunk + net.num_frame)
+            sink = Y4MSink(Y4MWriter(fout, W, H, fps, interlace, scaled_aspect(aspect, (h, w), (H, W)), tag, depth=out_depth, chroma=out_chroma),
+                           a.chunk + net.num_frame)
         else:
             sink = PngSink(a.output, None if paths is None else [os.path.basename(p) for p in paths],
                            a.writers or max(1, min(MAX_WRITERS, effective_cpus())))
         t0 = time.perf_counter()
-        up = VideoUpscaler(net, a.scale, a.padding, out="i420" if a.y4m_out else "uint8", pixel_format="i420" if a.y4m_in else "rgb",
+        up = VideoUpscaler(net, a.scale, a.padding, out=fmt_out, pixel_format=fmt_in,
                            size=(h, w) if a.y4m_in else None, cuts=a.cuts, scene_threshold=a.scene_threshold, colour=colour or "bt601",
                            out_colour=out_colour, depth=depth, out_depth=out_depth)
         done = 0
@@ -397,6 +412,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         scenes += f", colour {colour or 'rgb'} -> {out_colour or 'rgb'}"
     if depth != 8 or (out_depth or 8) != 8:
         scenes += f", {depth} -> {out_depth or 8} bits"
+    if chroma != "420" or (out_chroma or "420") != "420":
+        scenes += f", chroma {chroma if a.y4m_in else 'rgb'} -> {out_chroma or 'rgb'}"
     print(f"upscaled {done} frames in {dt:.2f} s: {done / dt:.2f} frames/s{scenes}", file=sys.stderr if a.output == "-" else sys.stdout, flush=True)
     return 0
 

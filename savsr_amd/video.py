@@ -7,7 +7,9 @@ windows are gathered there (savsr_video_gather_u8 / _f32) and the uint8 result i
 HipEngine.forward_video.  pixel_format="i420" / out="i420": planar YUV 4:2:0 frames in / out (savsr_amd/yuv.py is the format and its
 numerics), converted on the device on either side of the network (savsr_video_gather_i420 / savsr_video_quantize_i420).  depth /
 out_depth = 10, 12: the frames hold little-endian 16-bit samples ([N, 2 * i420_bytes(h, w)] uint8, Y4M's C420p10 / C420p12;
-savsr_video_gather_yuv420_16 / savsr_video_quantize_yuv420_16), limited range only.
+savsr_video_gather_yuv420_16 / savsr_video_quantize_yuv420_16), limited range only.  pixel_format / out = "i422", "i444": the 4:2:2 and
+4:4:4 layouts of the same planes ([N, yuv.frame_bytes(h, w, depth, chroma)] uint8), with everything above applying to them as well; the
+two sides are independent.  Every YUV side goes through one entry, savsr_video_gather_yuvp / savsr_video_quantize_yuvp.
 
 cuts=[k, ...] / cuts="auto": the video is a sequence of scenes and every scene is treated as a video of its own (savsr_amd/scenes.py:
 windows stop at cuts); "auto" finds the cuts on the device (savsr_video_pair_sad_*, then scdet's rule on the host).  cuts=None runs
@@ -22,11 +24,18 @@ from typing import List, Optional, Sequence, Tuple, Union
 import torch
 
 from .harness import window_indices
-from .yuv import check_colour, check_depth, check_depth_colour, i420_bytes
+from .yuv import CHROMA_OF, CHROMAS, check_colour, check_depth, check_depth_colour, frame_bytes, i420_bytes, layout_name
 
 PADDING_MODES = ("replicate", "reflection", "reflection_circle", "circle")
-OUT_KINDS = ("float", "uint8", "i420")
-PIXEL_FORMATS = ("rgb", "i420")
+OUT_KINDS = ("float", "uint8", "i420", "i422", "i444")
+PIXEL_FORMATS = ("rgb", "i420", "i422", "i444")
+YUV_FORMATS = ("i420", "i422", "i444")          # planar YUV in the three chroma layouts (yuv.CHROMAS), as pixel_format and as out
+_YUV_LIST = "'i420', 'i422' or 'i444'"
+
+
+def chroma_of(fmt: str) -> str:
+    """The chroma layout ("420", "422", "444") of a YUV pixel format / output kind; "420" for the others (no YUV on that side)."""
+    return CHROMA_OF.get(fmt, "420")
 
 
 def as_scale(scale) -> Tuple[float, float]:
@@ -81,12 +90,12 @@ def frame_layout(frames: torch.Tensor, nch: int) -> Tuple[int, int, int]:
 
 
 def check_pixel_format(pixel_format: str, size) -> Optional[Tuple[int, int]]:
-    """(h, w) of I420 frames, None for RGB ones; refuses an unknown format, I420 without a size and a size without I420."""
+    """(h, w) of YUV frames (i420, i422, i444), None for RGB ones; refuses an unknown format, YUV without a size and a size without YUV."""
     if pixel_format not in PIXEL_FORMATS:
         raise ValueError(f"pixel_format = {pixel_format!r}: one of {', '.join(PIXEL_FORMATS)}")
     if pixel_format == "rgb":
         if size is not None:
-            raise ValueError("size = (h, w) goes with pixel_format = 'i420'; RGB frames carry their size in their shape")
+            raise ValueError(f"size = (h, w) goes with pixel_format = {_YUV_LIST}; RGB frames carry their size in their shape")
         return None
     try:
         h, w = size
@@ -94,7 +103,7 @@ def check_pixel_format(pixel_format: str, size) -> Optional[Tuple[int, int]]:
     except (TypeError, ValueError):
         ok = False
     if not ok:
-        raise ValueError(f"pixel_format = 'i420' needs size = (h, w), got {size!r}")
+        raise ValueError(f"pixel_format = {pixel_format!r} needs size = (h, w), got {size!r}")
     if h < 2 or w < 2:
         raise ValueError(f"SAVSR needs h, w >= 2, got {h} x {w}")
     return int(h), int(w)
@@ -105,10 +114,10 @@ def check_colours(colour, out_colour, pixel_format: str, out: str) -> Tuple[int,
     out = 'i420'; out_colour = None: the same as colour."""
     cid = check_colour(colour, "colour")
     ocid = cid if out_colour is None else check_colour(out_colour, "out_colour")
-    if cid != 0 and pixel_format != "i420":
-        raise ValueError(f"colour = {colour!r} goes with pixel_format = 'i420': it is the colour space of I420 input (RGB frames have none)")
-    if out_colour is not None and out != "i420":
-        raise ValueError(f"out_colour = {out_colour!r} goes with out = 'i420': it is the colour space of I420 output")
+    if cid != 0 and pixel_format not in YUV_FORMATS:
+        raise ValueError(f"colour = {colour!r} goes with pixel_format = {_YUV_LIST}: it is the colour space of YUV input (RGB frames have none)")
+    if out_colour is not None and out not in YUV_FORMATS:
+        raise ValueError(f"out_colour = {out_colour!r} goes with out = {_YUV_LIST}: it is the colour space of YUV output")
     return cid, ocid
 
 
@@ -118,42 +127,45 @@ def check_depths(depth, out_depth, pixel_format: str, out: str, colour: str = "b
     spaces only."""
     d = check_depth(depth, "depth")
     od = None if out_depth is None else check_depth(out_depth, "out_depth")
-    if d != 8 and pixel_format != "i420":
-        raise ValueError(f"depth = {d} goes with pixel_format = 'i420': it is the bit depth of I420 input (RGB frames carry theirs in their dtype)")
-    if od is not None and out != "i420":
-        raise ValueError(f"out_depth = {od} goes with out = 'i420': it is the bit depth of I420 output")
+    if d != 8 and pixel_format not in YUV_FORMATS:
+        raise ValueError(f"depth = {d} goes with pixel_format = {_YUV_LIST}: it is the bit depth of YUV input (RGB frames carry theirs in their dtype)")
+    if od is not None and out not in YUV_FORMATS:
+        raise ValueError(f"out_depth = {od} goes with out = {_YUV_LIST}: it is the bit depth of YUV output")
     if od is None:
-        od = d if out == "i420" else 8
+        od = d if out in YUV_FORMATS else 8
     check_depth_colour(d, colour, "depth", "colour")
-    if out == "i420":
+    if out in YUV_FORMATS:
         check_depth_colour(od, colour if out_colour is None else out_colour, "out_depth", "out_colour")
     return d, od
 
 
-def check_sample_alignment(frames: torch.Tensor, depth: int) -> None:
+def check_sample_alignment(frames: torch.Tensor, depth: int, chroma: str = "420") -> None:
     """10- and 12-bit frames are read as 16-bit words: their base pointer must be 2-byte aligned (a frame's byte size is always even)."""
     if depth > 8 and frames.numel() and frames.data_ptr() % 2:
-        raise ValueError(f"{depth}-bit I420 frames hold 16-bit samples: the base pointer {frames.data_ptr():#x} is not 2-byte aligned "
+        raise ValueError(f"{depth}-bit {layout_name(chroma)} frames hold 16-bit samples: the base pointer {frames.data_ptr():#x} is not 2-byte aligned "
                          f"(an odd storage offset of a uint8 view); copy the frames (.clone()) first")
 
 
-def i420_layout(frames: torch.Tensor, size: Tuple[int, int], nch: int, depth: int = 8) -> int:
-    """N of an I420 video tensor: [N, i420_bytes(h, w, depth)] uint8 (GPU or host); refuses anything else."""
+def i420_layout(frames: torch.Tensor, size: Tuple[int, int], nch: int, depth: int = 8, chroma: str = "420") -> int:
+    """N of a YUV video tensor: [N, frame_bytes(h, w, depth, chroma)] uint8 (GPU or host); refuses anything else, naming the layout and
+    the byte count it expects."""
     h, w = size
+    name, fb = layout_name(chroma), frame_bytes(h, w, depth, chroma)
     if not isinstance(frames, torch.Tensor):
         raise TypeError(f"frames must be a torch.Tensor, got {type(frames).__name__}")
     if nch != 3:
-        raise ValueError(f"I420 frames are colour frames, the network takes num_in_ch = {nch}")
+        raise ValueError(f"{name} frames are colour frames, the network takes num_in_ch = {nch}")
     if frames.dtype != torch.uint8:
-        raise ValueError(f"I420 frames must be uint8, got {frames.dtype}")
+        raise ValueError(f"{name} frames must be uint8, got {frames.dtype}")
     if frames.dim() != 2:
-        raise ValueError(f"I420 frames must be [N, i420_bytes(h, w)] uint8, got {frames.dim()} dimensions")
+        raise ValueError(f"{name} frames must be [N, {'i420_bytes(h, w)' if chroma == '420' else 'frame_bytes(h, w, depth, chroma)'}] uint8, "
+                         f"got {frames.dim()} dimensions")
     if depth != 8:
-        if int(frames.shape[1]) != i420_bytes(h, w, depth):
-            raise ValueError(f"{depth}-bit I420 frames of {h} x {w} have {i420_bytes(h, w, depth)} bytes (16-bit samples), got {int(frames.shape[1])}")
-        check_sample_alignment(frames, depth)
-    elif int(frames.shape[1]) != i420_bytes(h, w):
-        raise ValueError(f"I420 frames of {h} x {w} have {i420_bytes(h, w)} bytes, got {int(frames.shape[1])}")
+        if int(frames.shape[1]) != fb:
+            raise ValueError(f"{depth}-bit {name} frames of {h} x {w} have {fb} bytes (16-bit samples), got {int(frames.shape[1])}")
+        check_sample_alignment(frames, depth, chroma)
+    elif int(frames.shape[1]) != fb:
+        raise ValueError(f"{name} frames of {h} x {w} have {fb} bytes, got {int(frames.shape[1])}")
     return int(frames.shape[0])
 
 
@@ -174,8 +186,8 @@ def _check_net(net) -> None:
 def check_out(out: str, nch: int) -> None:
     if out not in OUT_KINDS:
         raise ValueError(f"out = {out!r}: one of {', '.join(OUT_KINDS)}")
-    if out == "i420" and nch != 3:
-        raise ValueError(f"out = 'i420' holds colour frames, the network gives num_in_ch = {nch}")
+    if out in YUV_FORMATS and nch != 3:
+        raise ValueError(f"out = {out!r} holds colour frames, the network gives num_in_ch = {nch}")
 
 
 def _is_auto(cuts) -> bool:
@@ -192,18 +204,18 @@ def check_cuts_arg(cuts) -> None:
     check_cuts(cuts, None)
 
 
-def _sad_layout(frames: torch.Tensor, i420: Optional[Tuple[int, int]], depth: int = 8) -> Tuple[int, int, int, int]:
-    """(N, c, h, w) of the frames the detector compares (c = 0: I420); no network here, so any c in 1 .. 3 and any h, w >= 1."""
+def _sad_layout(frames: torch.Tensor, i420: Optional[Tuple[int, int]], depth: int = 8, chroma: str = "420") -> Tuple[int, int, int, int]:
+    """(N, c, h, w) of the frames the detector compares (c = 0: YUV); no network here, so any c in 1 .. 3 and any h, w >= 1."""
     if not isinstance(frames, torch.Tensor):
         raise TypeError(f"frames must be a torch.Tensor, got {type(frames).__name__}")
     if depth != 8 and not i420:
-        raise ValueError(f"depth = {depth} goes with pixel_format = 'i420': it is the bit depth of I420 input (RGB frames carry theirs in their dtype)")
+        raise ValueError(f"depth = {depth} goes with pixel_format = {_YUV_LIST}: it is the bit depth of YUV input (RGB frames carry theirs in their dtype)")
     if i420:
         h, w = i420
-        if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != i420_bytes(h, w, depth):
-            raise ValueError(f"{'' if depth == 8 else f'{depth}-bit '}I420 frames of {h} x {w} are [N, {i420_bytes(h, w, depth)}] uint8, "
-                             f"got {frames.dtype} {tuple(frames.shape)}")
-        check_sample_alignment(frames, depth)
+        if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != frame_bytes(h, w, depth, chroma):
+            raise ValueError(f"{'' if depth == 8 else f'{depth}-bit '}{layout_name(chroma)} frames of {h} x {w} are "
+                             f"[N, {frame_bytes(h, w, depth, chroma)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+        check_sample_alignment(frames, depth, chroma)
         n, c = int(frames.shape[0]), 0
     else:
         if frames.dim() != 4:
@@ -225,17 +237,20 @@ def _sad_layout(frames: torch.Tensor, i420: Optional[Tuple[int, int]], depth: in
     return n, c, h, w
 
 
-def _pair_sad_device(frames: torch.Tensor, i420: Optional[Tuple[int, int]], depth: int = 8) -> torch.Tensor:
+def _pair_sad_device(frames: torch.Tensor, i420: Optional[Tuple[int, int]], depth: int = 8, chroma: str = "420") -> torch.Tensor:
     """savsr_video_pair_sad_* on frames already on the GPU: int64 [N - 1] there, enqueued on the current stream (no sync)."""
     from . import _lib
-    n, c, h, w = _sad_layout(frames, i420, depth)
+    n, c, h, w = _sad_layout(frames, i420, depth, chroma)
     lib = _lib.load()
     u8 = frames.dtype == torch.uint8
     frames = frames.contiguous() if u8 else frames.to(torch.float32).contiguous()
     with torch.cuda.device(frames.device):
         sad = torch.empty(n - 1, dtype=torch.int64, device=frames.device)
         st = torch.cuda.current_stream().cuda_stream
-        if i420 and depth != 8:
+        if i420 and chroma != "420":
+            _lib.check(lib.savsr_video_pair_sad_yuvp(frames.data_ptr(), n, h, w, depth, CHROMAS.index(chroma), sad.data_ptr(), st),
+                       "savsr_video_pair_sad_yuvp")
+        elif i420 and depth != 8:
             _lib.check(lib.savsr_video_pair_sad_i420_16(frames.data_ptr(), n, h, w, depth, sad.data_ptr(), st), "savsr_video_pair_sad_i420_16")
         elif i420:
             _lib.check(lib.savsr_video_pair_sad_i420(frames.data_ptr(), n, h, w, sad.data_ptr(), st), "savsr_video_pair_sad_i420")
@@ -259,11 +274,13 @@ def pair_sad(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: 
     and j + 1 (savsr_amd.scenes.pair_sad is the specification).  frames as for SAVSR.upscale_video, with any c in 1 .. 3: [N, h, w, c]
     uint8 (GPU or host; every byte), [N, c, h, w] float on the GPU (every value after the uint8 output's quantisation), or with
     pixel_format="i420", size=(h, w): [N, i420_bytes(h, w)] uint8 (the Y plane only).  depth = 10, 12 (I420 only): frames of 16-bit samples,
-    [N, 2 * i420_bytes(h, w)] uint8, compared by their 8 most significant bits, so the scores keep the 8-bit scale."""
+    [N, 2 * i420_bytes(h, w)] uint8, compared by their 8 most significant bits, so the scores keep the 8-bit scale.  pixel_format="i422" /
+    "i444": frames of those layouts; the Y plane only, as for I420."""
     i420 = check_pixel_format(pixel_format, size)
     depth = check_depth(depth)
-    _sad_layout(frames, i420, depth)
-    return _pair_sad_device(_to_device(frames, _sad_device(frames)), i420, depth)
+    chroma = chroma_of(pixel_format)
+    _sad_layout(frames, i420, depth, chroma)
+    return _pair_sad_device(_to_device(frames, _sad_device(frames)), i420, depth, chroma)
 
 
 def detect_cuts(frames: torch.Tensor, threshold=10.0, pixel_format: str = "rgb", size=None, depth: int = 8) -> List[int]:
@@ -274,7 +291,7 @@ def detect_cuts(frames: torch.Tensor, threshold=10.0, pixel_format: str = "rgb",
     check_threshold(threshold)
     i420 = check_pixel_format(pixel_format, size)
     depth = check_depth(depth)
-    _sad_layout(frames, i420, depth)
+    _sad_layout(frames, i420, depth, chroma_of(pixel_format))
     sad = pair_sad(frames, pixel_format, size, depth)
     return cuts_from_sad(sad.cpu().tolist(), sad_samples(frames.shape, pixel_format, size), threshold)
 
@@ -290,7 +307,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     cid, ocid = check_colours(colour, out_colour, pixel_format, out)
     d, od = check_depths(depth, out_depth, pixel_format, out, colour, out_colour)
     sc = as_scale(net.scale if scale is None else scale)
-    n = i420_layout(frames, i420, net.cfg["num_in_ch"], d) if i420 else frame_layout(frames, net.cfg["num_in_ch"])[0]
+    chroma, out_chroma = chroma_of(pixel_format), chroma_of(out)
+    n = i420_layout(frames, i420, net.cfg["num_in_ch"], d, chroma) if i420 else frame_layout(frames, net.cfg["num_in_ch"])[0]
     T = net.num_frame
     if cuts is None:
         check_length(n, T, padding)
@@ -310,12 +328,13 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         windows = [window_indices(i, n, T, padding) for i in range(n)]
     else:
         if _is_auto(cuts):
-            sad = _pair_sad_device(frames, i420, d).cpu().tolist()
+            sad = _pair_sad_device(frames, i420, d, chroma).cpu().tolist()
             cuts = scenes.cuts_from_sad(sad, scenes.sad_samples(frames.shape, pixel_format, size), scene_threshold)
         windows = scenes.scene_windows(n, cuts, T, padding)
     with torch.no_grad():
         return net.engine().forward_video(frames, windows, sc, out == "uint8", ensemble=net.self_ensemble, i420=i420,
-                                          out_i420=out == "i420", colour=cid, out_colour=ocid, depth=d, out_depth=od)
+                                          out_i420=out in YUV_FORMATS, colour=cid, out_colour=ocid, depth=d, out_depth=od,
+                                          chroma=CHROMAS.index(chroma), out_chroma=CHROMAS.index(out_chroma))
 
 
 class VideoUpscaler:
@@ -333,7 +352,8 @@ class VideoUpscaler:
     back) -- plus the current chunk.
 
     colour / out_colour: the colour spaces of I420 chunks in / out, as in upscale_video.  depth / out_depth: their bit depths (10, 12:
-    chunks of [k, 2 * i420_bytes(h, w)] uint8, 16-bit samples), as in upscale_video.
+    chunks of [k, 2 * i420_bytes(h, w)] uint8, 16-bit samples), as in upscale_video.  pixel_format / out = "i422", "i444": chunks of
+    [k, yuv.frame_bytes(h, w, depth, chroma)] uint8 in those layouts, as in upscale_video.
 
     cuts=[k, ...] (global frame indices) or cuts="auto" (each push scores its new pairs on the device, the pair with the previous
     push's last frame included, and decides with `scene_threshold`): windows stop at cuts as in upscale_video(cuts=...), and `up.cuts`
@@ -355,7 +375,9 @@ class VideoUpscaler:
             self._given = [] if self._auto else scenes.check_cuts(cuts, None)       # explicit cuts not reached yet
             self._prev_sad = 0                     # the last pair's score (scdet's damping term), carried from push to push
             self._plan = scenes.ScenePlan(net.num_frame, padding)
-        self.i420 = check_pixel_format(pixel_format, size)        # (h, w) of I420 chunks, None for RGB ones
+        self.i420 = check_pixel_format(pixel_format, size)        # (h, w) of YUV chunks, None for RGB ones
+        self._chromas = (chroma_of(pixel_format), chroma_of(out))      # chroma layouts of the YUV input / output
+        self._fmt = pixel_format
         self._colours = check_colours(colour, out_colour, pixel_format, out)      # colour space ids of the I420 input / output
         self._depths = check_depths(depth, out_depth, pixel_format, out, colour, out_colour)      # bit depths of the I420 input / output
         self.net, self.padding, self.out = net, padding, out
@@ -395,8 +417,9 @@ class VideoUpscaler:
         windows = [[j - self._base for j in window_indices(i, n, self.T, self.padding)] for i in range(self.done, upto)]
         with torch.no_grad():
             res = self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble, i420=self.i420,
-                                                  out_i420=self.out == "i420", colour=self._colours[0], out_colour=self._colours[1],
-                                                  depth=self._depths[0], out_depth=self._depths[1])
+                                                  out_i420=self.out in YUV_FORMATS, colour=self._colours[0], out_colour=self._colours[1],
+                                                  depth=self._depths[0], out_depth=self._depths[1], chroma=CHROMAS.index(self._chromas[0]),
+                                                  out_chroma=CHROMAS.index(self._chromas[1]))
         self.done = upto
         return res
 
@@ -404,7 +427,7 @@ class VideoUpscaler:
         if self._finished:
             raise RuntimeError("push() after finish()")
         if self.i420:
-            k, (h, w) = i420_layout(frames, self.i420, self.net.cfg["num_in_ch"], self._depths[0]), self.i420
+            k, (h, w) = i420_layout(frames, self.i420, self.net.cfg["num_in_ch"], self._depths[0], self._chromas[0]), self.i420
         else:
             k, h, w = frame_layout(frames, self.net.cfg["num_in_ch"])
         shape = (frames.dtype == torch.uint8, h, w)
@@ -442,8 +465,8 @@ class VideoUpscaler:
         if hi - first < 1:
             return []
         from .scenes import cuts_from_sad, sad_samples
-        sad = _pair_sad_device(self._buf[first - 1 - self._base:], self.i420, self._depths[0]).cpu().tolist()
-        new = cuts_from_sad(sad, sad_samples(self._buf.shape, "i420" if self.i420 else "rgb", self.i420), self._threshold, first, self._prev_sad)
+        sad = _pair_sad_device(self._buf[first - 1 - self._base:], self.i420, self._depths[0], self._chromas[0]).cpu().tolist()
+        new = cuts_from_sad(sad, sad_samples(self._buf.shape, self._fmt, self.i420), self._threshold, first, self._prev_sad)
         self._prev_sad = sad[-1]
         return new
 
@@ -453,8 +476,9 @@ class VideoUpscaler:
         windows = [[j - self._base for j in win] for win in windows]
         with torch.no_grad():
             return self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble, i420=self.i420,
-                                                   out_i420=self.out == "i420", colour=self._colours[0], out_colour=self._colours[1],
-                                                   depth=self._depths[0], out_depth=self._depths[1])
+                                                   out_i420=self.out in YUV_FORMATS, colour=self._colours[0], out_colour=self._colours[1],
+                                                   depth=self._depths[0], out_depth=self._depths[1], chroma=CHROMAS.index(self._chromas[0]),
+                                                   out_chroma=CHROMAS.index(self._chromas[1]))
 
     def _push_scenes(self, k: int) -> torch.Tensor:
         plan = self._plan
@@ -495,8 +519,8 @@ class VideoUpscaler:
         H, W = get_hw(h, w, self.scale)
         c = self.net.cfg["num_in_ch"]
         dev = self.net.gamma.device
-        if self.out == "i420":
-            return torch.empty(0, i420_bytes(H, W, self._depths[1]), dtype=torch.uint8, device=dev)
+        if self.out in YUV_FORMATS:
+            return torch.empty(0, frame_bytes(H, W, self._depths[1], self._chromas[1]), dtype=torch.uint8, device=dev)
         if self.out == "uint8":
             return torch.empty(0, H, W, c, dtype=torch.uint8, device=dev)
         return torch.empty(0, c, H, W, dtype=torch.float32, device=dev)

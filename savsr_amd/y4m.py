@@ -12,6 +12,12 @@ request; the format has no tag for the matrix (BT.601 / BT.709), which is the ca
 10 and 12 bits: Y4MReader(f, high_depth=True) also reads C420p10 and C420p12, whose frames hold little-endian 16-bit samples in the same
 plane order (2 * i420_bytes bytes, still handed out as uint8 rows; `depth` says which).  The reader refuses them unless asked to, so that
 a caller written against one byte per sample never receives two; Y4MWriter(..., depth=10 | 12) writes them.
+
+4:2:2 and 4:4:4: Y4MReader(f, layouts=("420", "422", "444")) also reads C422 and C444, and with high_depth=True C422p10, C422p12, C444p10
+and C444p12; `chroma` says which layout the stream has and `frame_bytes` is yuv.frame_bytes(height, width, depth, chroma).  An opt-in
+like high_depth, for the same reason.  Y4MWriter(..., chroma="422" | "444") writes them.  Chroma siting is not modelled (centre-sited
+in every layout, yuv.py): C422 means MPEG-2's horizontally cosited chroma to some tools, which is accepted and ignored as the three
+C420 variants are.  C444alpha, Cmono, C411 and 14- / 16-bit tags stay refused by name.
 """
 from __future__ import annotations
 
@@ -20,11 +26,14 @@ from typing import Iterator, Optional, Tuple
 
 import numpy as np
 
-from .yuv import i420_bytes
+from .yuv import CHROMAS, check_chroma, frame_bytes
 
 MAGIC = b"YUV4MPEG2"
 C420_TAGS = ("420", "420jpeg", "420mpeg2", "420paldv")
 C420_HIGH_TAGS = {"420p10": 10, "420p12": 12}        # tag -> bit depth (Y4MReader with high_depth=True, Y4MWriter with depth=)
+# 4:2:2 / 4:4:4 tags -> (chroma layout, bit depth); the high-depth ones need high_depth=True as well (Y4MReader with layouts=)
+CHROMA_TAGS = {"422": ("422", 8), "444": ("444", 8)}
+CHROMA_HIGH_TAGS = {f"{c}p{d}": (c, d) for c in ("422", "444") for d in (10, 12)}
 MAX_LINE = 4096          # a header or FRAME line longer than this is not Y4M
 COLOUR_RANGES = ("full", "limited")
 
@@ -94,11 +103,21 @@ class Y4MReader:
     """Reads the header on construction (width, height, fps, interlace, aspect, colorspace, colour_range), then `chunks(k)` yields the
     frames as uint8 arrays [m, i420_bytes(height, width)], m = k but for the last.  colour_range: "full" / "limited" of an
     XCOLORRANGE=FULL / =LIMITED tag, None without one.  high_depth=True: C420p10 / C420p12 are read as well; `depth` is 8, 10 or 12 and
-    the rows of a 10- or 12-bit stream are [m, 2 * i420_bytes(height, width)] uint8 (little-endian 16-bit samples)."""
+    the rows of a 10- or 12-bit stream are [m, 2 * i420_bytes(height, width)] uint8 (little-endian 16-bit samples).
+    layouts: the chroma layouts (yuv.CHROMAS) the caller takes; with "422" / "444" in it C422 / C444 (and, with high_depth, their p10 /
+    p12 forms) are read too, `chroma` is the stream's layout and the rows are [m, yuv.frame_bytes(height, width, depth, chroma)].
+    The default reads 4:2:0 only and words every refusal as it did before layouts existed."""
 
-    def __init__(self, f, high_depth: bool = False):
+    def __init__(self, f, high_depth: bool = False, layouts=("420",)):
         self.f = f
         self.depth = 8
+        self.chroma = "420"
+        layouts = tuple(layouts)
+        for c in layouts:
+            check_chroma(c, "layouts")
+        if "420" not in layouts:
+            raise ValueError(f"y4m: layouts = {layouts!r} must include '420' (a stream without a C tag is 4:2:0)")
+        more = tuple(c for c in CHROMAS if c in layouts and c != "420")
         line = _read_line(f)
         if not line.startswith(MAGIC + b" ") or not line.endswith(b"\n"):
             raise ValueError("y4m: not a YUV4MPEG2 stream (no 'YUV4MPEG2 ' header line)")
@@ -131,6 +150,15 @@ class Y4MReader:
             elif key == "C":
                 if high_depth and val in C420_HIGH_TAGS:
                     self.depth, self.colorspace = C420_HIGH_TAGS[val], val
+                elif val in CHROMA_TAGS and CHROMA_TAGS[val][0] in more:
+                    self.chroma = CHROMA_TAGS[val][0]
+                elif high_depth and val in CHROMA_HIGH_TAGS and CHROMA_HIGH_TAGS[val][0] in more:
+                    self.chroma, self.depth = CHROMA_HIGH_TAGS[val]
+                elif more and val not in C420_TAGS:
+                    ok = C420_TAGS + (tuple(C420_HIGH_TAGS) if high_depth else ()) + more + \
+                        (tuple(t for t, (c, _) in CHROMA_HIGH_TAGS.items() if c in more) if high_depth else ())
+                    raise ValueError(f"y4m: colour space tag 'C{val}' is not supported: {', '.join('4:' + c[1] + ':' + c[2] for c in ('420',) + more)} "
+                                     f"at {'8, 10 or 12 bits' if high_depth else '8 bits'} only ({', '.join('C' + t for t in ok)})")
                 elif high_depth and val not in C420_TAGS:
                     raise ValueError(f"y4m: colour space tag 'C{val}' is not supported: 4:2:0 at 8, 10 or 12 bits only "
                                      f"({', '.join('C' + t for t in C420_TAGS + tuple(C420_HIGH_TAGS))})")
@@ -144,7 +172,7 @@ class Y4MReader:
                 raise ValueError(f"y4m: unknown header tag {tag!r}")
         if self.width is None or self.height is None:
             raise ValueError("y4m: the header names no W / H")
-        self.frame_bytes = i420_bytes(self.height, self.width, self.depth)
+        self.frame_bytes = frame_bytes(self.height, self.width, self.depth, self.chroma)
         self.frames_read = 0
 
     def _frame_into(self, row: np.ndarray) -> bool:
@@ -178,19 +206,25 @@ class Y4MReader:
 class Y4MWriter:
     """Writes the header on construction, then `write(frames)` appends uint8 frames [m, i420_bytes(height, width)].
     colour_range = "full" / "limited": the header also carries XCOLORRANGE=FULL / =LIMITED (None: no such tag).  depth = 10, 12: the
-    stream is tagged C420p10 / C420p12 and its frames are [m, 2 * i420_bytes(height, width)] uint8 (little-endian 16-bit samples)."""
+    stream is tagged C420p10 / C420p12 and its frames are [m, 2 * i420_bytes(height, width)] uint8 (little-endian 16-bit samples).
+    chroma = "422", "444": the stream is tagged C422 / C444 (C422p10 ... at depth 10 / 12) and its frames are
+    [m, yuv.frame_bytes(height, width, depth, chroma)] uint8."""
 
     def __init__(self, f, width: int, height: int, fps: Tuple[int, int] = (25, 1), interlace: str = "p", aspect: Tuple[int, int] = (0, 0),
-                 colour_range: Optional[str] = None, depth: int = 8):
+                 colour_range: Optional[str] = None, depth: int = 8, chroma: str = "420"):
         if width < 1 or height < 1:
             raise ValueError(f"y4m: W, H >= 1, got {width} x {height}")
         if colour_range is not None and colour_range not in COLOUR_RANGES:
             raise ValueError(f"y4m: colour_range = {colour_range!r}: None or one of {', '.join(COLOUR_RANGES)}")
         if depth != 8 and depth not in C420_HIGH_TAGS.values():
             raise ValueError(f"y4m: depth = {depth!r}: one of 8, 10, 12")
-        self.f, self.width, self.height, self.depth = f, int(width), int(height), int(depth)
-        self.frame_bytes = i420_bytes(self.height, self.width, self.depth)
-        ctag = "420jpeg" if depth == 8 else f"420p{self.depth}"
+        try:
+            check_chroma(chroma)
+        except ValueError as e:
+            raise ValueError(f"y4m: {e}") from None
+        self.f, self.width, self.height, self.depth, self.chroma = f, int(width), int(height), int(depth), chroma
+        self.frame_bytes = frame_bytes(self.height, self.width, self.depth, chroma)
+        ctag = ("420jpeg" if chroma == "420" else chroma) if depth == 8 else f"{chroma}p{self.depth}"
         self.header = (f"YUV4MPEG2 W{self.width} H{self.height} F{fps[0]}:{fps[1]} I{interlace} A{aspect[0]}:{aspect[1]} C{ctag}"
                        f"{'' if colour_range is None else ' XCOLORRANGE=' + colour_range.upper()}\n").encode("ascii")
         f.write(self.header)

@@ -1,4 +1,5 @@
-"""Planar YUV 4:2:0 (I420) <-> RGB, the host restatement that specifies savsr_video_gather_i420 / savsr_video_quantize_i420 (yuv.hip).
+"""Planar YUV 4:2:0 (I420) <-> RGB, the host restatement that specifies savsr_video_gather_i420 / savsr_video_quantize_i420 (yuv.hip);
+with `chroma=` also 4:2:2 and 4:4:4 (savsr_video_gather_yuvp / savsr_video_quantize_yuvp, see "Chroma layouts" below).
 
 The default colour matrix is the reference's (lbasicsr/utils/color_util.py, `rgb2ycbcr` / `ycbcr2rgb`: ITU-R BT.601, limited range,
 Matlab's rounded constants: `BT601`), the same whose Y row metrics.py uses for PSNR-Y.  4:2:0 only, at 8, 10 or 12 bits (`depth=`;
@@ -29,6 +30,14 @@ and has no definition here.
                 clamped to [0, 1].  A sample above 2^d - 1 is read as 2^d - 1.  At most five roundings of values below 2.5, so the result
                 lies within 5 * 2.5 * 2^-24 < 1e-6 of the float64 closed form.
   rgb_to_i420   rint(ycbcr_f32 * k), half to even (the product by k is exact); Y in 16 k .. 235 k and chroma in 16 k .. 240 k, no clip.
+
+Chroma layouts (`chroma=` "420", "422" or "444"; the position in CHROMAS is the id of the C ABI, SAVSR_CHROMA_*).  A frame holds h * w Y
+samples, then ch * cw U samples, then ch * cw V samples with (ch, cw) = `chroma_hw(h, w, chroma)`: (ceil(h / 2), ceil(w / 2)) for 4:2:0,
+(h, ceil(w / 2)) for 4:2:2 and (h, w) for 4:4:4; `frame_bytes(h, w, depth, chroma)` bytes, the samples as wide as above.  The arithmetic
+is 4:2:0's with another block shape and nothing else: to RGB, chroma sample (cy, cx) serves pixels (cy, 2 cx .. 2 cx + 1) in 4:2:2 and
+pixel (cy, cx) in 4:4:4 (nearest replication); from RGB, Cb / Cr come from the mean RGB of the block's in-image pixels, (a + b) * 0.5
+for a 4:2:2 pair, the pixel alone in the last column of an odd W, and the pixel's own clamped RGB in 4:4:4 (no mean).  Chroma is
+centre-sited like the 4:2:0 pair; the horizontally cosited convention of MPEG-2 4:2:2 is not modelled.
 """
 from __future__ import annotations
 
@@ -117,8 +126,31 @@ def check_depth_colour(depth, colour: str, what: str = "depth", cwhat: str = "co
     return d
 
 
-def chroma_hw(h: int, w: int) -> Tuple[int, int]:
-    return (h + 1) // 2, (w + 1) // 2
+# The chroma layouts of `chroma=`, in the order of their integer id in the C ABI (SAVSR_CHROMA_*), and the pixel format / output kind
+# each one goes by in the public interface.
+CHROMAS = ("420", "422", "444")
+FORMAT_OF = {"420": "i420", "422": "i422", "444": "i444"}
+CHROMA_OF = {v: k for k, v in FORMAT_OF.items()}
+
+
+def check_chroma(chroma, what: str = "chroma") -> int:
+    """The id of a chroma layout name (its position in CHROMAS); refuses anything else, naming the list."""
+    if not isinstance(chroma, str) or chroma not in CHROMAS:
+        raise ValueError(f"{what} = {chroma!r}: one of {', '.join(CHROMAS)}")
+    return CHROMAS.index(chroma)
+
+
+def chroma_hw(h: int, w: int, chroma: str = "420") -> Tuple[int, int]:
+    """(ch, cw) of a chroma plane: both halved (rounded up) in 4:2:0, the width alone in 4:2:2, neither in 4:4:4."""
+    if chroma == "420":
+        return (h + 1) // 2, (w + 1) // 2
+    return (h, (w + 1) // 2) if CHROMAS[check_chroma(chroma)] == "422" else (h, w)
+
+
+def frame_bytes(h: int, w: int, depth: int = 8, chroma: str = "420") -> int:
+    """Bytes of a frame in the given layout: a byte per sample at 8 bits, a 16-bit word at 10 and 12."""
+    ch, cw = chroma_hw(h, w, chroma)
+    return (h * w + 2 * ch * cw) * (1 if depth == 8 else 2)
 
 
 def i420_bytes(h: int, w: int, depth: int = 8) -> int:
@@ -127,24 +159,31 @@ def i420_bytes(h: int, w: int, depth: int = 8) -> int:
     return (h * w + 2 * ch * cw) * (1 if depth == 8 else 2)
 
 
+def layout_name(chroma: str) -> str:
+    """What the messages call a frame of the layout: I420, I422, I444."""
+    return "I" + chroma
+
+
 def _check_size(h: int, w: int) -> None:
     if int(h) != h or int(w) != w or h < 1 or w < 1:
         raise ValueError(f"size must be (h, w) with h, w >= 1, got ({h!r}, {w!r})")
 
 
-def split_planes(frames: np.ndarray, h: int, w: int, depth: int = 8) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """[N, i420_bytes(h, w, depth)] uint8 -> Y [N, h, w], U [N, ch, cw], V [N, ch, cw]: uint8 views at 8 bits, the little-endian 16-bit
-    samples as uint16 arrays at 10 and 12."""
+def split_planes(frames: np.ndarray, h: int, w: int, depth: int = 8, chroma: str = "420") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """[N, frame_bytes(h, w, depth, chroma)] uint8 -> Y [N, h, w], U [N, ch, cw], V [N, ch, cw]: uint8 views at 8 bits, the little-endian
+    16-bit samples as uint16 arrays at 10 and 12."""
     _check_size(h, w)
+    check_chroma(chroma)
     frames = np.asarray(frames)
+    fb, name = frame_bytes(h, w, depth, chroma), layout_name(chroma)
     if depth != 8:
         depth = check_depth(depth)
-        if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != i420_bytes(h, w, depth):
-            raise ValueError(f"{depth}-bit I420 frames of {h} x {w} are [N, {i420_bytes(h, w, depth)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+        if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != fb:
+            raise ValueError(f"{depth}-bit {name} frames of {h} x {w} are [N, {fb}] uint8, got {frames.dtype} {tuple(frames.shape)}")
         frames = np.ascontiguousarray(frames).view("<u2")
-    elif frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != i420_bytes(h, w):
-        raise ValueError(f"I420 frames of {h} x {w} are [N, {i420_bytes(h, w)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
-    ch, cw = chroma_hw(h, w)
+    elif frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != fb:
+        raise ValueError(f"{name} frames of {h} x {w} are [N, {fb}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+    ch, cw = chroma_hw(h, w, chroma)
     n = frames.shape[0]
     y = frames[:, :h * w].reshape(n, h, w)
     u = frames[:, h * w:h * w + ch * cw].reshape(n, ch, cw)
@@ -175,12 +214,21 @@ def to_rgb_coefficients(colour: str, depth: int) -> dict:
     return c
 
 
-def _i420_to_rgb_16(frames_u8: np.ndarray, h: int, w: int, colour: str, depth: int) -> np.ndarray:
+def replicate_chroma(p: np.ndarray, h: int, w: int, chroma: str = "420") -> np.ndarray:
+    """A chroma plane [N, ch, cw] -> [N, h, w] by nearest replication over the layout's block: 2 x 2, 1 x 2, or the plane itself."""
+    if chroma == "444":
+        return p
+    if chroma == "422":
+        return np.repeat(p, 2, axis=2)[:, :, :w]
+    return np.repeat(np.repeat(p, 2, axis=1), 2, axis=2)[:, :h, :w]
+
+
+def _i420_to_rgb_16(frames_u8: np.ndarray, h: int, w: int, colour: str, depth: int, chroma: str = "420") -> np.ndarray:
     c = to_rgb_coefficients(colour, depth)
     top = np.uint16((1 << depth) - 1)
-    y, u, v = (np.minimum(p, top).astype(np.float32) for p in split_planes(frames_u8, h, w, depth))
-    u = np.repeat(np.repeat(u, 2, axis=1), 2, axis=2)[:, :h, :w]
-    v = np.repeat(np.repeat(v, 2, axis=1), 2, axis=2)[:, :h, :w]
+    y, u, v = (np.minimum(p, top).astype(np.float32) for p in split_planes(frames_u8, h, w, depth, chroma))
+    u = replicate_chroma(u, h, w, chroma)
+    v = replicate_chroma(v, h, w, chroma)
     yt = y * c["y"]
     r = (yt + v * c["rv"]) + c["offset"][0]
     g = ((yt + u * c["gu"]) + v * c["gv"]) + c["offset"][1]
@@ -189,15 +237,16 @@ def _i420_to_rgb_16(frames_u8: np.ndarray, h: int, w: int, colour: str, depth: i
     return np.fmin(np.fmax(out, np.float32(0.0)), np.float32(1.0)).astype(np.float32)
 
 
-def i420_to_rgb(frames_u8: np.ndarray, h: int, w: int, colour: str = "bt601", depth: int = 8) -> np.ndarray:
-    """[N, i420_bytes(h, w, depth)] uint8 -> float32 [N, 3, h, w] in [0, 1].  depth = 8:  R = y + rv,  G = (y + gu) + gv,  B = y + bu  on
-    the table values; 10 and 12: float32 arithmetic on the samples (the module's "High depth")."""
+def i420_to_rgb(frames_u8: np.ndarray, h: int, w: int, colour: str = "bt601", depth: int = 8, chroma: str = "420") -> np.ndarray:
+    """[N, frame_bytes(h, w, depth, chroma)] uint8 -> float32 [N, 3, h, w] in [0, 1].  depth = 8:  R = y + rv,  G = (y + gu) + gv,
+    B = y + bu  on the table values; 10 and 12: float32 arithmetic on the samples (the module's "High depth").  chroma: the layout
+    (the module's "Chroma layouts"); the default is I420."""
     if depth != 8:
-        return _i420_to_rgb_16(frames_u8, h, w, colour, depth)
-    y, u, v = split_planes(frames_u8, h, w)
+        return _i420_to_rgb_16(frames_u8, h, w, colour, depth, chroma)
+    y, u, v = split_planes(frames_u8, h, w, 8, chroma)
     t = to_rgb_tables(matrix(colour))
-    u = np.repeat(np.repeat(u, 2, axis=1), 2, axis=2)[:, :h, :w]
-    v = np.repeat(np.repeat(v, 2, axis=1), 2, axis=2)[:, :h, :w]
+    u = replicate_chroma(u, h, w, chroma)
+    v = replicate_chroma(v, h, w, chroma)
     ty = t["y"][y]
     r = ty + t["rv"][v]
     g = (ty + t["gu"][u]) + t["gv"][v]
@@ -219,10 +268,20 @@ def _row(p: np.ndarray, coef, offset: float) -> np.ndarray:
     return ((p[:, 0] * a + p[:, 1] * b) + p[:, 2] * c) + np.float32(offset)
 
 
-def _block_mean(p: np.ndarray) -> np.ndarray:
+def _block_mean(p: np.ndarray, chroma: str = "420") -> np.ndarray:
     """Mean of every 2 x 2 block's in-image pixels, [N, 3, H, W] -> [N, 3, ch, cw]:  ((a + b) + (c + d)) * 0.25 with a b the block's
-    upper row and c d its lower; (a + b) * 0.5 for a pair (the last row of an odd H, the last column of an odd W); the pixel alone."""
+    upper row and c d its lower; (a + b) * 0.5 for a pair (the last row of an odd H, the last column of an odd W); the pixel alone.
+    4:2:2: (a + b) * 0.5 over a row's pairs, the pixel alone in the last column of an odd W.  4:4:4: the pixels themselves."""
     n, c, H, W = p.shape
+    if chroma == "444":
+        return p
+    if chroma == "422":
+        we = W // 2 * 2
+        m = np.empty((n, c, H, (W + 1) // 2), np.float32)
+        m[:, :, :, :W // 2] = (p[:, :, :, 0:we:2] + p[:, :, :, 1:we:2]) * np.float32(0.5)
+        if W % 2:
+            m[:, :, :, -1] = p[:, :, :, W - 1]
+        return m
     ch, cw = chroma_hw(H, W)
     he, we = H // 2 * 2, W // 2 * 2
     m = np.empty((n, c, ch, cw), np.float32)
@@ -237,24 +296,26 @@ def _block_mean(p: np.ndarray) -> np.ndarray:
     return m
 
 
-def ycbcr_f32(x: np.ndarray, colour: str = "bt601") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+def ycbcr_f32(x: np.ndarray, colour: str = "bt601", chroma: str = "420") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """The float32 values rgb_to_i420 rounds: Y [N, H, W], Cb and Cr [N, ch, cw], in 8-bit steps."""
+    check_chroma(chroma)
     p = _clamp01(x)
     t = matrix(colour)["to_ycbcr"]
-    m = _block_mean(p)
+    m = _block_mean(p, chroma)
     return _row(p, t["y"], t["offset"][0]), _row(m, t["cb"], t["offset"][1]), _row(m, t["cr"], t["offset"][2])
 
 
-def rgb_to_i420(x_f32: np.ndarray, colour: str = "bt601", depth: int = 8) -> np.ndarray:
-    """float32 [N, 3, H, W] -> uint8 [N, i420_bytes(H, W, depth)].  Limited range: after the clamp Y lies in 16 .. 235 and chroma in
-    16 .. 240, no clip.  Full range: chroma reaches 255.5, which rounds to 256, so the rounded values are clipped to 0 .. 255.
-    depth = 10, 12 (limited range only): rint(ycbcr_f32 * 2^(depth - 8)), written as little-endian 16-bit samples."""
+def rgb_to_i420(x_f32: np.ndarray, colour: str = "bt601", depth: int = 8, chroma: str = "420") -> np.ndarray:
+    """float32 [N, 3, H, W] -> uint8 [N, frame_bytes(H, W, depth, chroma)].  Limited range: after the clamp Y lies in 16 .. 235 and
+    chroma in 16 .. 240, no clip.  Full range: chroma reaches 255.5, which rounds to 256, so the rounded values are clipped to 0 .. 255.
+    depth = 10, 12 (limited range only): rint(ycbcr_f32 * 2^(depth - 8)), written as little-endian 16-bit samples.  chroma: the layout
+    (the module's "Chroma layouts"); the default is I420."""
     if depth != 8:
         k = np.float32(1 << (check_depth_colour(depth, colour) - 8))
-        planes = [np.rint(v * k) for v in ycbcr_f32(x_f32, colour)]
+        planes = [np.rint(v * k) for v in ycbcr_f32(x_f32, colour, chroma)]
         n = planes[0].shape[0]
         return np.concatenate([v.astype("<u2").reshape(n, -1) for v in planes], 1).view(np.uint8)
-    y, cb, cr = ycbcr_f32(x_f32, colour)
+    y, cb, cr = ycbcr_f32(x_f32, colour, chroma)
     n = y.shape[0]
     planes = [np.rint(v) for v in (y, cb, cr)]
     if is_full_range(colour):

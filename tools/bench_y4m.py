@@ -10,6 +10,11 @@ fails, times out or dies ends the run (nothing more is started on the GPU) and w
             on 4*3*h*w + 3*h*w bytes, and the ratio to the 8-bit kernel's time beside the ratio of the bytes moved, (12 + 3) / (12 + 1.5)
             = 1.11 -- a measured ratio well above it means the 16-bit access pattern is wrong.  No time is fixed in advance.
             `--legs depth --out profiles/bench_y4m_depth.json`
+  chroma    savsr_video_gather_yuvp / _quantize_yuvp at 4:2:2 and 4:4:4 beside the 4:2:0 kernels of the same build (chroma = 0 of the same
+            entries), at 8 and 10 bits, in one process, interleaved rounds, at 720x1280: us, bytes in and out, GB/s = (bytes in + bytes
+            out) / time.  The layouts move different bytes per pixel, so the GB/s are compared, not the times; the 4:2:0 kernels are
+            timed twice in every round and the spread between their two readings is the margin (`margin_gbs`).  No time is fixed in
+            advance.  `--legs chroma --out profiles/bench_y4m_chroma.json`
   ceiling   upscale_video on preloaded I420 frames, I420 out (frames/s): what the CLI could reach
   cli       python -m savsr_amd.upscale on one synthetic video, PNG folder -> PNG folder against .y4m -> .y4m, A/B/A/B; files under
             --workdir (name the disk it lies on beside the figures: tmpfs or a scratch disk)
@@ -32,7 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_BYTES_PER_S = 8e12
-LEG_TIMEOUT_S = {"kernels": 240, "depth": 240, "ceiling": 420, "cli": 420, "psnr": 420}
+LEG_TIMEOUT_S = {"kernels": 240, "depth": 240, "chroma": 240, "ceiling": 420, "cli": 420, "psnr": 420}
 
 
 def _net(dev):
@@ -157,6 +162,60 @@ def leg_depth(a):
             "timing": "HIP events around `iters` back-to-back launches (launch rate included)"}
 
 
+def leg_chroma(a):
+    import ctypes as C
+    import torch
+    from savsr_amd import _lib
+    from savsr_amd.yuv import CHROMAS, frame_bytes
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    h, w, n = 720, 1280, 16
+    arr = (C.c_int32 * 7)(*range(7))
+    slots = torch.empty(7, 3, h, w, device=dev)
+    x = torch.rand(7, 3, h, w, device=dev)
+    fns, nbytes = {}, {}
+    keep = []                                       # (the buffers the closures below read and write)
+    for depth in (8, 10):
+        for cid, chroma in enumerate(CHROMAS):
+            fb = frame_bytes(h, w, depth, chroma)
+            src = torch.randint(0, 256 if depth == 8 else 4, (n, fb), dtype=torch.uint8, device=dev)      # (in-range samples at either depth)
+            dst = torch.empty(7, fb, dtype=torch.uint8, device=dev)
+            keep += [src, dst]
+            for tag in (("a", "b") if cid == 0 else ("",)):          # the yardstick is read twice in every round
+                name = f"{chroma} {depth}-bit" + (f" ({tag})" if tag else "")
+                fns[f"gather {name}"] = lambda s_=src, d=depth, c=cid: lib.savsr_video_gather_yuvp(s_.data_ptr(), n, h, w, arr, 7, 1, d, c, slots.data_ptr(), st)
+                fns[f"quantize {name}"] = lambda o=dst, d=depth, c=cid: lib.savsr_video_quantize_yuvp(x.data_ptr(), 7, h, w, 1, d, c, o.data_ptr(), st)
+                nbytes[f"gather {name}"] = (7 * fb, 7 * 12 * h * w)
+                nbytes[f"quantize {name}"] = (7 * 12 * h * w, 7 * fb)
+    us = {k: [] for k in fns}
+    for k, fn in fns.items():
+        assert fn() == 0, k
+    torch.cuda.synchronize()
+    for _ in range(a.rounds):                           # interleaved rounds: every kernel sees the same clocks
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us[k].append(1e3 * e0.elapsed_time(e1) / a.iters)
+    med = {k: statistics.median(v) for k, v in us.items()}
+    gbs = {k: sum(nbytes[k]) / (med[k] * 1e-6) / 1e9 for k in fns}
+    rows = []
+    for k in fns:
+        side, _, depth = k.split()[:3]
+        ya, yb = gbs[f"{side} 420 {depth} (a)"], gbs[f"{side} 420 {depth} (b)"]
+        row = {"kernel": k, "size": [h, w], "frames": 7, "us": round(med[k], 2), "bytes_in": nbytes[k][0], "bytes_out": nbytes[k][1],
+               "gbs": round(gbs[k], 1), "gbs_420": round(min(ya, yb), 1), "margin_gbs": round(abs(ya - yb), 1),
+               "below_420_by_more_than_the_margin": bool(gbs[k] < min(ya, yb) - abs(ya - yb)),
+               "us_rounds": [round(v, 2) for v in us[k]]}
+        rows.append(row)
+    return {"kernels": rows, "rounds": a.rounds, "iters": a.iters, "colour": "bt709",
+            "timing": "HIP events around `iters` back-to-back launches (launch rate included)"}
+
+
 def leg_ceiling(a):
     import torch
     dev = torch.device("cuda:0")
@@ -238,7 +297,7 @@ def leg_psnr(a):
                        "note": "against the float result in float64; synthetic weights"}}
 
 
-LEGS = {"kernels": leg_kernels, "depth": leg_depth, "ceiling": leg_ceiling, "cli": leg_cli, "psnr": leg_psnr}
+LEGS = {"kernels": leg_kernels, "depth": leg_depth, "chroma": leg_chroma, "ceiling": leg_ceiling, "cli": leg_cli, "psnr": leg_psnr}
 
 
 def main():
