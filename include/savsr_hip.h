@@ -521,7 +521,7 @@ int savsr_video_pair_sad_i420_16(const uint8_t* frames, int n_frames, int h, int
  * frames back to back.  The arithmetic is 4:2:0's with another block shape: to RGB a chroma sample serves its 1 x 2 (4:2:2) or 1 x 1
  * (4:4:4) block; from RGB, Cb / Cr come from (a + b) * 0.5 of a 4:2:2 pair (the pixel alone in the last column of an odd W) and from the
  * pixel's own clamped RGB in 4:4:4.  Chroma is centre-sited as in 4:2:0; MPEG-2's horizontally cosited 4:2:2 is not modelled.
- * savsr_amd/yuv.py (`chroma=`) restates all of it bit for bit.  SAVSR_CHROMA_420 runs the kernels of the entries above and gives their
+ * savsr_amd/yuv.py (`chroma=`) restates all of it bit for bit.  SAVSR_CHROMA_420 is the 4:2:0 of the entries above and gives their
  * bytes.  Refused with SAVSR_E_ARG + savsr_last_error() before the device is touched: a chroma outside 0 .. 2, a depth other than
  * 8 / 10 / 12, a full-range colour at depth 10 / 12, a null pointer, an odd frame pointer at depth 10 / 12, an index outside the frames.
  * savsr_video_gather_yuvp:   frames -> out [n_idx][3][h][w] fp32 planar RGB, slot k = frame idx[k].  A thread owns 4 pixels of one row

@@ -154,9 +154,8 @@ def frame_bytes(h: int, w: int, depth: int = 8, chroma: str = "420") -> int:
 
 
 def i420_bytes(h: int, w: int, depth: int = 8) -> int:
-    """Bytes of a frame: a byte per sample at 8 bits, a 16-bit word at 10 and 12."""
-    ch, cw = chroma_hw(h, w)
-    return (h * w + 2 * ch * cw) * (1 if depth == 8 else 2)
+    """Bytes of a 4:2:0 frame: frame_bytes of the default layout."""
+    return frame_bytes(h, w, depth)
 
 
 def layout_name(chroma: str) -> str:
@@ -223,18 +222,26 @@ def replicate_chroma(p: np.ndarray, h: int, w: int, chroma: str = "420") -> np.n
     return np.repeat(np.repeat(p, 2, axis=1), 2, axis=2)[:, :h, :w]
 
 
+def _full_planes(frames_u8: np.ndarray, h: int, w: int, depth: int, chroma: str) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """split_planes with both chroma planes replicated to [N, h, w]."""
+    y, u, v = split_planes(frames_u8, h, w, depth, chroma)
+    return y, replicate_chroma(u, h, w, chroma), replicate_chroma(v, h, w, chroma)
+
+
+def _stack01(r: np.ndarray, g: np.ndarray, b: np.ndarray) -> np.ndarray:
+    out = np.stack([r, g, b], 1)
+    return np.fmin(np.fmax(out, np.float32(0.0)), np.float32(1.0)).astype(np.float32)
+
+
 def _i420_to_rgb_16(frames_u8: np.ndarray, h: int, w: int, colour: str, depth: int, chroma: str = "420") -> np.ndarray:
     c = to_rgb_coefficients(colour, depth)
     top = np.uint16((1 << depth) - 1)
-    y, u, v = (np.minimum(p, top).astype(np.float32) for p in split_planes(frames_u8, h, w, depth, chroma))
-    u = replicate_chroma(u, h, w, chroma)
-    v = replicate_chroma(v, h, w, chroma)
+    y, u, v = (np.minimum(p, top).astype(np.float32) for p in _full_planes(frames_u8, h, w, depth, chroma))
     yt = y * c["y"]
     r = (yt + v * c["rv"]) + c["offset"][0]
     g = ((yt + u * c["gu"]) + v * c["gv"]) + c["offset"][1]
     b = (yt + u * c["bu"]) + c["offset"][2]
-    out = np.stack([r, g, b], 1)
-    return np.fmin(np.fmax(out, np.float32(0.0)), np.float32(1.0)).astype(np.float32)
+    return _stack01(r, g, b)
 
 
 def i420_to_rgb(frames_u8: np.ndarray, h: int, w: int, colour: str = "bt601", depth: int = 8, chroma: str = "420") -> np.ndarray:
@@ -243,16 +250,13 @@ def i420_to_rgb(frames_u8: np.ndarray, h: int, w: int, colour: str = "bt601", de
     (the module's "Chroma layouts"); the default is I420."""
     if depth != 8:
         return _i420_to_rgb_16(frames_u8, h, w, colour, depth, chroma)
-    y, u, v = split_planes(frames_u8, h, w, 8, chroma)
+    y, u, v = _full_planes(frames_u8, h, w, 8, chroma)
     t = to_rgb_tables(matrix(colour))
-    u = replicate_chroma(u, h, w, chroma)
-    v = replicate_chroma(v, h, w, chroma)
     ty = t["y"][y]
     r = ty + t["rv"][v]
     g = (ty + t["gu"][u]) + t["gv"][v]
     b = ty + t["bu"][u]
-    out = np.stack([r, g, b], 1)
-    return np.fmin(np.fmax(out, np.float32(0.0)), np.float32(1.0)).astype(np.float32)
+    return _stack01(r, g, b)
 
 
 def _clamp01(x: np.ndarray) -> np.ndarray:
@@ -313,11 +317,9 @@ def rgb_to_i420(x_f32: np.ndarray, colour: str = "bt601", depth: int = 8, chroma
     if depth != 8:
         k = np.float32(1 << (check_depth_colour(depth, colour) - 8))
         planes = [np.rint(v * k) for v in ycbcr_f32(x_f32, colour, chroma)]
-        n = planes[0].shape[0]
-        return np.concatenate([v.astype("<u2").reshape(n, -1) for v in planes], 1).view(np.uint8)
-    y, cb, cr = ycbcr_f32(x_f32, colour, chroma)
-    n = y.shape[0]
-    planes = [np.rint(v) for v in (y, cb, cr)]
-    if is_full_range(colour):
-        planes = [np.fmin(np.fmax(v, np.float32(0.0)), np.float32(255.0)) for v in planes]
-    return np.concatenate([v.astype(np.uint8).reshape(n, -1) for v in planes], 1)
+    else:
+        planes = [np.rint(v) for v in ycbcr_f32(x_f32, colour, chroma)]
+        if is_full_range(colour):
+            planes = [np.fmin(np.fmax(v, np.float32(0.0)), np.float32(255.0)) for v in planes]
+    n = planes[0].shape[0]
+    return np.concatenate([v.astype(np.uint8 if depth == 8 else "<u2").reshape(n, -1) for v in planes], 1).view(np.uint8)

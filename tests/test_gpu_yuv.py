@@ -21,8 +21,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = torch.device("cuda:0")
 GOLDEN_SIZES = [(2, 2), (3, 5), (8, 10), (9, 14), (17, 33)]
-SIZES = GOLDEN_SIZES + [(180, 320), (181, 319), (720, 1280), (715, 1273)]
-OFFSETS = [(0, 0), (1, 0), (4, 0), (0, 1), (0, 4), (1, 1)]          # (bytes on the uint8 side, floats on the fp32 side)
+# (5 x 3, 8 x 12, 64 x 64, 18 x 20: with the golden ones the shapes of the other layouts' and depths' tests -- an odd last row and column, the
+# vector path, more than one workgroup of it, and with the 2-byte offset a w % 4 == 0 image on the scalar path)
+SIZES = GOLDEN_SIZES + [(5, 3), (8, 12), (64, 64), (18, 20), (180, 320), (181, 319), (720, 1280), (715, 1273)]
+OFFSETS = [(0, 0), (1, 0), (4, 0), (0, 1), (0, 4), (1, 1), (2, 0)]  # (bytes on the uint8 side, floats on the fp32 side)
 
 
 def _lib():
