@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 39
+#define SAVSR_ABI_VERSION 40
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -539,6 +539,37 @@ int savsr_video_gather_yuvp(const uint8_t* frames, int n_frames, int h, int w, c
                             float* out, void* stream);
 int savsr_video_quantize_yuvp(const float* in, int n, int H, int W, int colour, int depth, int chroma, uint8_t* out, void* stream);
 int savsr_video_pair_sad_yuvp(const uint8_t* frames, int n_frames, int h, int w, int depth, int chroma, int64_t* sad_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 40) Chroma siting and linear chroma reconstruction (yuv.hip; siting / out_siting of SAVSR.upscale_video, --siting / --out-siting of
+ * python -m savsr_amd.upscale).  The arguments of savsr_video_gather_yuvp / savsr_video_quantize_yuvp with
+ * siting = one of SAVSR_SITING_* after chroma.  NONE is "not modelled": the nearest-up / box-down pair of the entries above, their
+ * kernels and their bytes.  Otherwise chroma sample (cy, cx) lies at luma position
+ *   CENTRE    x = 2 cx + 0.5, y = 2 cy + 0.5 (4:2:0), y = cy (4:2:2)      JPEG, MPEG-1; Y4M's C420jpeg
+ *   LEFT      x = 2 cx,       y = 2 cy + 0.5 (4:2:0), y = cy (4:2:2)      MPEG-2, H.264, HEVC 4:2:0, every standard 4:2:2; C420mpeg2
+ *   TOPLEFT   x = 2 cx,       y = 2 cy (4:2:0 only)                       C420paldv, as ffmpeg maps it
+ * 4:4:4 has nothing to resample: any siting there runs the entries above.  Refused with SAVSR_E_ARG + savsr_last_error() before the
+ * device is touched: a siting outside 0 .. 3, TOPLEFT with SAVSR_CHROMA_422 (no vertical subsampling; LEFT is its cosited form), and
+ * everything savsr_video_gather_yuvp / _quantize_yuvp refuse.  savsr_amd/yuv.py (`siting=`) restates both bit for bit.
+ * savsr_video_gather_yuvs:   chroma at every luma pixel is the separable linear interpolation between the two nearest samples, edge
+ *                         samples replicated, samples above 2^depth - 1 clipped first.  Per subsampled axis, pixels 2 c and 2 c + 1:
+ *                         centre-sited (3 C[c] + C[c - 1]) / 4 and (3 C[c] + C[c + 1]) / 4; cosited C[c] and (C[c] + C[c + 1]) / 2 -- an
+ *                         integer numerator times 2^-4 (4:2:0) or 2^-2 (4:2:2), exact in float32.  Then the arithmetic of
+ *                         savsr_video_gather_yuv420_16 at every depth, 8 included (k = 1, all four colour spaces; no tables): within
+ *                         1e-6 of the float64 closed form.  Constant chroma planes give the RGB of SITING_NONE bit for bit at 10 / 12
+ *                         bits and within 1e-6 at 8.  Vector / scalar forms and alignment rules of savsr_video_gather_yuvp.
+ * savsr_video_quantize_yuvs: NONE and CENTRE are savsr_video_quantize_yuvp (the box is the centre-sited filter).  Cosited axes take
+ *                         h3(l, c, r) = ((l + r) + (c + c)) * 0.25f with every tap index clamped into the image: Hrow(y) = h3 of the
+ *                         clamped RGB at x = 2 cx - 1, 2 cx, 2 cx + 1.  LEFT: Hrow(y) in 4:2:2, (Hrow(2 cy) + Hrow(2 cy + 1)) * 0.5f in
+ *                         4:2:0 (Hrow(2 cy) alone on the last row of an odd H).  TOPLEFT: h3(Hrow(2 cy - 1), Hrow(2 cy), Hrow(2 cy + 1)),
+ *                         rows clamped.  Y, the rows, the rounding and the full-range clip are savsr_video_quantize_yuvp's. */
+#define SAVSR_SITING_NONE 0
+#define SAVSR_SITING_CENTRE 1
+#define SAVSR_SITING_LEFT 2
+#define SAVSR_SITING_TOPLEFT 3
+int savsr_video_gather_yuvs(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, int colour, int depth, int chroma,
+                            int siting, float* out, void* stream);
+int savsr_video_quantize_yuvs(const float* in, int n, int H, int W, int colour, int depth, int chroma, int siting, uint8_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 33) Geometric self-ensemble (ensemble.hip; SAVSR.set_self_ensemble).  Variant k = 0 .. 7: fw = k & 1 flips

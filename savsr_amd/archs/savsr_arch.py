@@ -279,7 +279,7 @@ class SAVSR(nn.Module):
 
     def upscale_video(self, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
                       size=None, cuts=None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None, depth: int = 8,
-                      out_depth: Optional[int] = None) -> torch.Tensor:
+                      out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -301,7 +301,13 @@ class SAVSR(nn.Module):
         pixel_format="i422" / "i444", out="i422" / "i444": planar YUV 4:2:2 / 4:4:4 (Y4M's C422 / C444 and their p10 / p12 forms), frames
         of savsr_amd.yuv.frame_bytes(h, w, depth, chroma) bytes; size, colour, out_colour, depth and out_depth apply to them as to I420.
         The two sides are independent: pixel_format="i420", out="i444" keeps the network's full-resolution chroma, and RGB in with
-        out="i422" is allowed.  Chroma is centre-sited in every layout (MPEG-2's cosited 4:2:2 is not modelled).
+        out="i422" is allowed.
+        siting: where the chroma samples of 4:2:0 / 4:2:2 input lie, None or one of savsr_amd.yuv.SITINGS: "centre" (JPEG, MPEG-1; Y4M's
+        C420jpeg), "left" (MPEG-2, H.264, HEVC 4:2:0 and every standard 4:2:2; C420mpeg2), "topleft" (C420paldv; 4:2:0 only).  With a
+        siting, chroma is reconstructed by linear interpolation at the positions it names; None (the default) models none and replicates
+        the nearest sample, as ever.  out_siting: that of YUV output; "left" / "topleft" filter cosited axes with [1 2 1] / 4, None and
+        "centre" take the block mean.  The two are independent; siting goes with a YUV pixel_format and out_siting with a YUV out, and
+        4:4:4 has nothing to resample (any siting gives the bytes of None).
         cuts: None (one scene), a strictly increasing list of frame indices 0 < k < N (frame k starts a new scene), or "auto" (found on
         the GPU: savsr_amd.detect_cuts with scene_threshold, in per cent of the largest possible frame change; the default is ffmpeg
         scdet's and is not validated on real footage).  Windows stop at cuts: the result is, bit for bit, upscale_video on every scene
@@ -309,7 +315,8 @@ class SAVSR(nn.Module):
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
-        return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold, colour, out_colour, depth, out_depth)
+        return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold, colour, out_colour, depth, out_depth,
+                             siting, out_siting)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

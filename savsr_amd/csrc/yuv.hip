@@ -18,11 +18,18 @@
 // rounded samples to 0 .. 255 (pure red / blue give a chroma of 255.5, which rounds to 256).  10 and 12 bits are defined for limited range
 // only (colour spaces 0 and 1): a sample is the 8-bit one times k, so the constants are the 8-bit ones scaled by a power of two.
 //
+// Chroma siting (savsr_video_gather_yuvs / _quantize_yuvs; yuv.py's "Chroma siting" is the specification): the kernels above read chroma by
+// nearest replication and write it through a box, which models no siting.  gather_linear_kernel interpolates chroma linearly at the
+// positions a siting gives the samples and quantize_cosited_kernel filters cosited axes with [1 2 1] / 4; they serve the <2, 2> and
+// <2, 1> blocks and keep the thread ownership and the vector / scalar split of the two kernels above, whose code and instantiations they
+// leave alone (siting 0, 4:4:4 and the centre-sited quantiser run those).
+//
 // savsr_amd/yuv.py restates both kernels in numpy and is what they are tested against, bit for bit: float32, a fixed operation order
 // and no fused multiply-add (contraction is off for this whole file).
 #include "common.hpp"
 
 #include <cstdint>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -113,6 +120,21 @@ constexpr ToRgb16 make_to_rgb16(const YuvMatrix& m, double k) {
 struct ToRgb16All { ToRgb16 c[N_COLOURS_16][N_DEPTHS_16]; };
 __constant__ ToRgb16All kToRgb16 = {{{make_to_rgb16(kYuv.m[0], 4.0), make_to_rgb16(kYuv.m[0], 16.0)},
                                      {make_to_rgb16(kYuv.m[1], 4.0), make_to_rgb16(kYuv.m[1], 16.0)}}};
+
+// The linear gather: to_rgb_coefficients for every colour space at depth 8 (k = 1) beside the limited-range rows at 10 and 12, where the
+// two full-range rows are never read (the entry refuses them).  A table of its own, so that kToRgb16 and its readers stay as they are.
+enum { N_DEPTHS = 3 };                           // 8, 10, 12
+struct ToRgbLinAll { ToRgb16 c[N_COLOURS][N_DEPTHS]; };
+constexpr ToRgbLinAll make_to_rgb_lin() {
+    ToRgbLinAll a{};
+    for (int c = 0; c < N_COLOURS; ++c) {
+        a.c[c][0] = make_to_rgb16(kYuv.m[c], 1.0);
+        a.c[c][1] = make_to_rgb16(kYuv.m[c], 4.0);
+        a.c[c][2] = make_to_rgb16(kYuv.m[c], 16.0);
+    }
+    return a;
+}
+__constant__ ToRgbLinAll kToRgbLin = make_to_rgb_lin();
 
 // ---- Samples ---------------------------------------------------------------------------------------------------------------------------
 // N consecutive samples of type S in one access of N * sizeof(S) bytes: 2 (a 16-bit access), 4 (a dword) or 8 (a u32x2).  What VEC needs
@@ -263,6 +285,140 @@ __global__ __launch_bounds__(256) void gather_kernel(const uint8_t* __restrict__
     }
 }
 
+// ---- To RGB, chroma interpolated linearly (yuv.py: interpolate_chroma, _i420_to_rgb_sited) -------------------------------------------------
+// The policy: Rgb16's arithmetic on fractional chroma at every depth, 8 included (S = uint8_t, top = 255, row [colour][0] of kToRgbLin).
+template <class S> struct RgbLin {
+    typedef S Sample;
+    int ci, di;
+    uint32_t top;
+    struct Pixel {
+        ToRgb16 k;
+        uint32_t top;
+        __device__ __forceinline__ uint32_t clip(uint32_t s) const { return min(s, top); }
+        __device__ __forceinline__ void rgb(uint32_t y, float fu, float fv, float (&c)[3]) const {
+            const float yt = (float)y * k.y;
+            c[0] = clamp01((yt + fv * k.rv) + k.o_r);
+            c[1] = clamp01(((yt + fu * k.gu) + fv * k.gv) + k.o_g);
+            c[2] = clamp01((yt + fu * k.bu) + k.o_b);
+        }
+    };
+    __device__ __forceinline__ Pixel begin() const { return Pixel{kToRgbLin.c[ci][di], top}; }
+};
+
+// One subsampled axis, as an integer numerator over 4.  Pixel 2 c from C[c - 1] and C[c], pixel 2 c + 1 from C[c] and C[c + 1]:
+//   centre-sited (the sample lies at 2 c + 0.5)   (3 C[c] + C[c - 1]) / 4      (3 C[c] + C[c + 1]) / 4
+//   cosited      (the sample lies at 2 c)         C[c]                         (C[c] + C[c + 1]) / 2
+template <bool COS> __device__ __forceinline__ uint32_t lerp_even(uint32_t prev, uint32_t cur) { return COS ? 4u * cur : 3u * cur + prev; }
+template <bool COS> __device__ __forceinline__ uint32_t lerp_odd(uint32_t cur, uint32_t next) { return COS ? 2u * cur + 2u * next : 3u * cur + next; }
+
+// The numerators of one chroma plane for a thread's SY rows x NP pixels, the pixels under chroma samples (cy, c0 .. c0 + NP / 2 - 1): over
+// 16 in 4:2:0, over 4 in 4:2:2; at most 4095 * 16.  Every neighbour's index is clamped into the plane (edge samples replicated), so every
+// access lies inside it; NP = 4 reads the thread's pair in one access (the alignment table above holds for every chroma row).
+template <int SY, bool CX, bool CY, int NP, class S, class Px>
+__device__ __forceinline__ void chroma_numerators(const S* __restrict__ pl, int ch, int cw, int cy, int c0, const Px& px, uint32_t (&num)[SY][NP]) {
+    constexpr int NC = NP / 2;
+    auto row = [&](int r, uint32_t (&hn)[NP]) {
+        const S* p = pl + (long long)r * cw;
+        uint32_t c[NC + 2];                                     // C[c0 - 1], C[c0 .. c0 + NC - 1], C[c0 + NC]
+        if constexpr (NC == 2) {
+            uint32_t t[2];
+            load_samples(p + c0, t);
+            c[1] = t[0];
+            c[2] = t[1];
+        } else {
+            c[1] = p[c0];
+        }
+        c[0] = CX ? 0u : (uint32_t)p[max(c0 - 1, 0)];           // (a cosited axis has no use for the sample before)
+        c[NC + 1] = p[min(c0 + NC, cw - 1)];
+#pragma unroll
+        for (int j = 0; j < NC + 2; ++j) c[j] = px.clip(c[j]);
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            hn[2 * j] = lerp_even<CX>(c[j], c[j + 1]);
+            hn[2 * j + 1] = lerp_odd<CX>(c[j + 1], c[j + 2]);
+        }
+    };
+    uint32_t mid[NP];
+    row(cy, mid);
+    if constexpr (SY == 1) {
+#pragma unroll
+        for (int e = 0; e < NP; ++e) num[0][e] = mid[e];
+    } else {
+        uint32_t up[NP] = {}, dn[NP];
+        if constexpr (!CY) row(max(cy - 1, 0), up);
+        row(min(cy + 1, ch - 1), dn);
+#pragma unroll
+        for (int e = 0; e < NP; ++e) {
+            num[0][e] = lerp_even<CY>(up[e], mid[e]);
+            num[1][e] = lerp_odd<CY>(mid[e], dn[e]);
+        }
+    }
+}
+
+// gather_kernel with chroma at every pixel interpolated between the two nearest samples per subsampled axis; CX / CY: that axis is cosited.
+// Same units and ownership: a thread converts the SY rows x 4 (VEC) or x 2 pixels under its chroma samples and reads, beside them, the
+// sample before (a centre-sited axis) and after them in the row, and the chroma row above (centre-sited) and below.
+template <int SY, bool VEC, bool CX, bool CY, class P>
+__global__ __launch_bounds__(256) void gather_linear_kernel(const uint8_t* __restrict__ src, int h, int w, long long fb, YuvIdx idx, P pol,
+                                                            float* __restrict__ out) {
+    typedef typename P::Sample S;
+    constexpr int SX = 2;
+    constexpr float SCALE = SY == 2 ? 0.0625f : 0.25f;
+    const typename P::Pixel px = pol.begin();
+    const int k = blockIdx.y;
+    const long long npx = (long long)h * w;
+    const int ch = (h + SY - 1) / SY, cw = (w + SX - 1) / SX;
+    const S* fy = reinterpret_cast<const S*>(src + (long long)idx.f[k] * fb);
+    const S* fu = fy + npx;
+    const S* fv = fu + (long long)ch * cw;
+    float* o = out + (long long)k * 3 * npx;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const int wq = w / 4;
+        if (g >= (long long)ch * wq) return;
+        const int cy = (int)(g / wq), x0 = (int)(g % wq) * 4;
+        uint32_t nu[SY][4], nv[SY][4];
+        chroma_numerators<SY, CX, CY, 4>(fu, ch, cw, cy, x0 / SX, px, nu);
+        chroma_numerators<SY, CX, CY, 4>(fv, ch, cw, cy, x0 / SX, px, nv);
+#pragma unroll
+        for (int dy = 0; dy < SY; ++dy) {
+            const int y = SY * cy + dy;
+            if (SY > 1 && y >= h) break;
+            const long long p = (long long)y * w + x0;
+            uint32_t yy[4];
+            load_samples(fy + p, yy);
+            f32x4 rgb[3];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float c[3];
+                px.rgb(px.clip(yy[e]), (float)nu[dy][e] * SCALE, (float)nv[dy][e] * SCALE, c);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) rgb[q][e] = c[q];
+            }
+#pragma unroll
+            for (int q = 0; q < 3; ++q) *reinterpret_cast<f32x4*>(o + q * npx + p) = rgb[q];
+        }
+    } else {
+        if (g >= (long long)ch * cw) return;
+        const int cy = (int)(g / cw), cx = (int)(g % cw);
+        uint32_t nu[SY][2], nv[SY][2];
+        chroma_numerators<SY, CX, CY, 2>(fu, ch, cw, cy, cx, px, nu);
+        chroma_numerators<SY, CX, CY, 2>(fv, ch, cw, cy, cx, px, nv);
+#pragma unroll
+        for (int dy = 0; dy < SY; ++dy) {
+#pragma unroll
+            for (int dx = 0; dx < SX; ++dx) {
+                if (SY * cy + dy >= h || SX * cx + dx >= w) continue;
+                const long long p = (long long)(SY * cy + dy) * w + SX * cx + dx;
+                float c[3];
+                px.rgb(px.clip(fy[p]), (float)nu[dy][dx] * SCALE, (float)nv[dy][dx] * SCALE, c);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) o[q * npx + p] = c[q];
+            }
+        }
+    }
+}
+
 // ---- From RGB --------------------------------------------------------------------------------------------------------------------------
 // rgb2ycbcr's rows in 8-bit steps: every product and every sum rounded to float32 (yuv.py: _row).  Plain operators under this file's
 // `fp contract(off)`: the header's __fmul_rn / __fadd_rn are compiled with contraction allowed and fuse again once inlined.
@@ -371,6 +527,120 @@ __global__ __launch_bounds__(256) void quantize_kernel(const float* __restrict__
         float m[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) m[c] = block_mean<SX, SY>(two_x, two_y, [&](int dy, int dx) { return q[dy][dx][c]; });
+        fu[(long long)cy * cw + cx] = (S)Q::cb(k, m[0], m[1], m[2]);
+        fv[(long long)cy * cw + cx] = (S)Q::cr(k, m[0], m[1], m[2]);
+    }
+}
+
+// ---- From RGB, cosited chroma (yuv.py: filter_chroma_rgb) ----------------------------------------------------------------------------------
+// [1 2 1] / 4 along a cosited axis, in float32 in this order.
+__device__ __forceinline__ float h3(float l, float c, float r) { return ((l + r) + (c + c)) * 0.25f; }
+
+// quantize_kernel with Cb / Cr from horizontally cosited chroma ("left"; TOP: vertically too, "topleft").  Hrow(y) = h3 of the clamped RGB
+// at x = 2 cx - 1, 2 cx, 2 cx + 1, every index clamped into the image; 4:2:2: Hrow(y); 4:2:0 left: (Hrow(2 cy) + Hrow(2 cy + 1)) * 0.5,
+// Hrow(2 cy) alone on the last row of an odd H; topleft: h3 of Hrow at rows 2 cy - 1, 2 cy, 2 cy + 1, clamped.  Same units and ownership:
+// a thread writes the Y of its SY rows x 4 (VEC) or x 2 pixels and the chroma samples over them, and reads beside its own pixels the one
+// left of them and, for TOP, the row above with plain loads (a neighbour's lines).  A clamped row or column repeats a value the thread
+// already holds, and the same operations on the same values give the same bits, so those are reused and not loaded again.
+template <int SY, bool VEC, bool TOP, class Q>
+__global__ __launch_bounds__(256) void quantize_cosited_kernel(const float* __restrict__ in, int H, int W, long long fb, float k, uint8_t* __restrict__ out) {
+    static_assert(SY == 2 || !TOP, "4:2:2 has no vertical subsampling");
+    typedef typename Q::Sample S;
+    constexpr int SX = 2;
+    const int f = blockIdx.y;
+    const long long npx = (long long)H * W;
+    const int ch = (H + SY - 1) / SY, cw = (W + SX - 1) / SX;
+    const float* src = in + (long long)f * 3 * npx;
+    S* fy = reinterpret_cast<S*>(out + (long long)f * fb);
+    S* fu = fy + npx;
+    S* fv = fu + (long long)ch * cw;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    auto at = [&](int c, int y, int x) { return clamp01(src[c * npx + (long long)y * W + x]); };
+    // the chroma sample's RGB from Hrow of its rows: own[dy], and for TOP the row above
+    auto vertical = [&](bool two_y, float up, float h0, float h1) {
+        if constexpr (SY == 1) return h0;
+        else if constexpr (TOP) return h3(up, h0, two_y ? h1 : h0);
+        else return two_y ? (h0 + h1) * 0.5f : h0;
+    };
+    if (VEC) {
+        constexpr int NC = 2;
+        const int wq = W / 4;
+        if (g >= (long long)ch * wq) return;
+        const int cy = (int)(g / wq), x0 = (int)(g % wq) * 4;
+        const bool two_y = SY == 2 && 2 * cy + 1 < H;
+        const int xl = max(x0 - 1, 0);
+        float own[SY][3][NC] = {}, up[3][NC];
+#pragma unroll
+        for (int dy = 0; dy < SY; ++dy) {
+            if (dy == 1 && !two_y) break;
+            const int y = SY * cy + dy;
+            const long long p = (long long)y * W + x0;
+            f32x4 px[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + c * npx + p));
+#pragma unroll
+                for (int e = 0; e < 4; ++e) px[c][e] = clamp01(x[e]);
+            }
+            uint32_t yy[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) yy[e] = Q::y(k, px[0][e], px[1][e], px[2][e]);
+            store_samples(fy + p, yy);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                own[dy][c][0] = h3(at(c, y, xl), px[c][0], px[c][1]);
+                own[dy][c][1] = h3(px[c][1], px[c][2], px[c][3]);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (TOP && cy > 0) {
+                const int y = 2 * cy - 1;
+                const f32x4 x = *reinterpret_cast<const f32x4*>(src + c * npx + (long long)y * W + x0);
+                up[c][0] = h3(at(c, y, xl), clamp01(x[0]), clamp01(x[1]));
+                up[c][1] = h3(clamp01(x[1]), clamp01(x[2]), clamp01(x[3]));
+            } else {
+                up[c][0] = own[0][c][0];
+                up[c][1] = own[0][c][1];
+            }
+        }
+        uint32_t u[NC], v[NC];
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            float m[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) m[c] = vertical(two_y, up[c][j], own[0][c][j], own[SY - 1][c][j]);
+            u[j] = Q::cb(k, m[0], m[1], m[2]);
+            v[j] = Q::cr(k, m[0], m[1], m[2]);
+        }
+        const long long coff = (long long)cy * cw + x0 / SX;
+        store_samples(fu + coff, u);
+        store_samples(fv + coff, v);
+    } else {
+        if (g >= (long long)ch * cw) return;
+        const int cy = (int)(g / cw), cx = (int)(g % cw);
+        const bool two_y = SY == 2 && 2 * cy + 1 < H, two_x = 2 * cx + 1 < W;
+        const int xl = max(2 * cx - 1, 0), xc = 2 * cx, xr = two_x ? xc + 1 : xc;
+        float own[SY][3] = {}, up[3];
+#pragma unroll
+        for (int dy = 0; dy < SY; ++dy) {
+            if (dy == 1 && !two_y) break;
+            const int y = SY * cy + dy;
+            float q[2][3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                q[0][c] = at(c, y, xc);
+                q[1][c] = at(c, y, xr);
+                own[dy][c] = h3(at(c, y, xl), q[0][c], q[1][c]);
+            }
+            fy[(long long)y * W + xc] = (S)Q::y(k, q[0][0], q[0][1], q[0][2]);
+            if (two_x) fy[(long long)y * W + xr] = (S)Q::y(k, q[1][0], q[1][1], q[1][2]);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) up[c] = (TOP && cy > 0) ? h3(at(c, 2 * cy - 1, xl), at(c, 2 * cy - 1, xc), at(c, 2 * cy - 1, xr)) : own[0][c];
+        float m[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) m[c] = vertical(two_y, up[c], own[0][c], own[SY - 1][c]);
         fu[(long long)cy * cw + cx] = (S)Q::cb(k, m[0], m[1], m[2]);
         fv[(long long)cy * cw + cx] = (S)Q::cr(k, m[0], m[1], m[2]);
     }
@@ -513,6 +783,101 @@ int quantize(const char* what, Rules rules, const float* in, int n, int H, int W
     return check_launch("quantize_kernel");
 }
 
+// ---- Chroma siting: the bodies of savsr_video_gather_yuvs / _quantize_yuvs -------------------------------------------------------------------
+// A siting the layout has, or the refusal that names the rule; after check_layout, before anything else.
+int check_siting(const char* what, int chroma, int siting) {
+    if (siting < SAVSR_SITING_NONE || siting > SAVSR_SITING_TOPLEFT) {
+        set_error("invalid argument: %s: siting %d (0 = not modelled, 1 = centre, 2 = left, 3 = topleft)", what, siting);
+        return SAVSR_E_ARG;
+    }
+    if (siting == SAVSR_SITING_TOPLEFT && chroma == SAVSR_CHROMA_422) {
+        set_error("invalid argument: %s: siting 3 (topleft) with chroma 1 (4:2:2): 4:2:2 has no vertical subsampling, its cosited form is siting 2 (left)", what);
+        return SAVSR_E_ARG;
+    }
+    return 0;
+}
+
+int gather_sited(const char* what, const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, int colour, int depth, int chroma,
+                 int siting, float* out, void* stream) {
+    if (int rc = check_layout(what, RULES_LAYOUT, depth, chroma)) return rc;
+    if (int rc = check_siting(what, chroma, siting)) return rc;
+    // not modelled, or nothing to resample: the nearest gather, its instantiations and its bytes
+    if (siting == SAVSR_SITING_NONE || chroma == SAVSR_CHROMA_444)
+        return gather(what, RULES_LAYOUT, frames, n_frames, h, w, idx, n_idx, colour, depth, chroma, out, stream);
+    if (!frames || !out) return fail(what, "null pointer");
+    if (h < 1 || w < 1 || n_frames < 1) return fail(what, "h, w, n_frames >= 1");
+    if (int rc = check_depth_colour(what, RULES_LAYOUT, colour, depth)) return rc;
+    if (depth != 8 && !aligned(frames, 2)) return fail(what, "frames must be 2-byte aligned (16-bit samples)");
+    if (!aligned(out, 4)) return fail(what, "out must be 4-byte aligned");
+    YuvIdx gi;
+    if (int rc = load_idx(idx, n_idx, n_frames, &gi, what)) return rc;
+    const Plan pl = plan(h, w, n_idx, depth, chroma, frames, out);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int di = depth == 8 ? 0 : depth == 10 ? 1 : 2;
+    const uint32_t top = (1u << depth) - 1u;
+    auto launch = [&](auto sy, auto cx, auto cy) {
+        constexpr int SY = decltype(sy)::value;
+        constexpr bool CX = decltype(cx)::value, CY = decltype(cy)::value;
+        auto go = [&](auto pol) {
+            typedef decltype(pol) P;
+            if (pl.vec) hipLaunchKernelGGL((gather_linear_kernel<SY, true, CX, CY, P>), pl.grid, dim3(256), 0, st, frames, h, w, pl.fb, gi, pol, out);
+            else hipLaunchKernelGGL((gather_linear_kernel<SY, false, CX, CY, P>), pl.grid, dim3(256), 0, st, frames, h, w, pl.fb, gi, pol, out);
+        };
+        if (depth == 8) go(RgbLin<uint8_t>{colour, di, top});
+        else go(RgbLin<uint16_t>{colour, di, top});
+    };
+    typedef std::integral_constant<int, 1> One;
+    typedef std::integral_constant<int, 2> Two;
+    if (chroma == SAVSR_CHROMA_422) {                           // (the vertical axis is not subsampled: CY has no meaning)
+        if (siting == SAVSR_SITING_CENTRE) launch(One{}, std::false_type{}, std::false_type{});
+        else launch(One{}, std::true_type{}, std::false_type{});
+    } else if (siting == SAVSR_SITING_CENTRE) {
+        launch(Two{}, std::false_type{}, std::false_type{});
+    } else if (siting == SAVSR_SITING_LEFT) {
+        launch(Two{}, std::true_type{}, std::false_type{});
+    } else {
+        launch(Two{}, std::true_type{}, std::true_type{});
+    }
+    return check_launch("gather_linear_kernel");
+}
+
+int quantize_sited(const char* what, const float* in, int n, int H, int W, int colour, int depth, int chroma, int siting, uint8_t* out, void* stream) {
+    if (int rc = check_layout(what, RULES_LAYOUT, depth, chroma)) return rc;
+    if (int rc = check_siting(what, chroma, siting)) return rc;
+    // not modelled, centre-sited (the box is its filter) or nothing to resample: the box quantiser, its instantiations and its bytes
+    if (siting <= SAVSR_SITING_CENTRE || chroma == SAVSR_CHROMA_444)
+        return quantize(what, RULES_LAYOUT, in, n, H, W, colour, depth, chroma, out, stream);
+    if (!in || !out) return fail(what, "null pointer");
+    if (n < 1 || n > 65535 || H < 1 || W < 1) return fail(what, "n in 1 .. 65535, H, W >= 1");
+    if (int rc = check_depth_colour(what, RULES_LAYOUT, colour, depth)) return rc;
+    if (depth != 8 && !aligned(out, 2)) return fail(what, "out must be 2-byte aligned (16-bit samples)");
+    if (!aligned(in, 4)) return fail(what, "in must be 4-byte aligned");
+    const Plan pl = plan(H, W, n, depth, chroma, out, in);
+    const float k = (float)(1 << (depth - 8));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    auto launch = [&](auto q) {
+        typedef decltype(q) Q;
+        auto go = [&](auto sy, auto top) {
+            constexpr int SY = decltype(sy)::value;
+            constexpr bool TOP = decltype(top)::value;
+            if (pl.vec) hipLaunchKernelGGL((quantize_cosited_kernel<SY, true, TOP, Q>), pl.grid, dim3(256), 0, st, in, H, W, pl.fb, k, out);
+            else hipLaunchKernelGGL((quantize_cosited_kernel<SY, false, TOP, Q>), pl.grid, dim3(256), 0, st, in, H, W, pl.fb, k, out);
+        };
+        if (chroma == SAVSR_CHROMA_422) go(std::integral_constant<int, 1>{}, std::false_type{});
+        else if (siting == SAVSR_SITING_LEFT) go(std::integral_constant<int, 2>{}, std::false_type{});
+        else go(std::integral_constant<int, 2>{}, std::true_type{});
+    };
+    switch (depth == 8 ? colour : N_COLOURS + colour) {
+        case 0: launch(Quant8<0>{}); break;
+        case 1: launch(Quant8<1>{}); break;
+        case 2: launch(Quant8<2>{}); break;
+        case 3: launch(Quant8<3>{}); break;
+        case N_COLOURS: launch(Quant16<0>{}); break;
+        default: launch(Quant16<1>{}); break;
+    }
+    return check_launch("quantize_cosited_kernel");
+}
+
 }  // namespace
 }  // namespace savsr
 
@@ -555,4 +920,15 @@ extern "C" int savsr_video_gather_yuvp(const uint8_t* frames, int n_frames, int 
 
 extern "C" int savsr_video_quantize_yuvp(const float* in, int n, int H, int W, int colour, int depth, int chroma, uint8_t* out, void* stream) {
     return quantize("video_quantize_yuvp", RULES_LAYOUT, in, n, H, W, colour, depth, chroma, out, stream);
+}
+
+// Every (chroma layout, depth) with the chroma siting (SAVSR_SITING_*): linear chroma reconstruction in, cosited filters out.
+extern "C" int savsr_video_gather_yuvs(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, int colour, int depth,
+                                       int chroma, int siting, float* out, void* stream) {
+    return gather_sited("video_gather_yuvs", frames, n_frames, h, w, idx, n_idx, colour, depth, chroma, siting, out, stream);
+}
+
+extern "C" int savsr_video_quantize_yuvs(const float* in, int n, int H, int W, int colour, int depth, int chroma, int siting, uint8_t* out,
+                                         void* stream) {
+    return quantize_sited("video_quantize_yuvs", in, n, H, W, colour, depth, chroma, siting, out, stream);
 }

@@ -34,7 +34,7 @@ from .config import EngineConfig
 from .launch import MAX_SUM_BLOCKS, Launcher, Src, _ptr      # noqa: F401
 from .packing import (BN_EPS, CONV_TH, CONV_TW, WeightPacking, acc_row, conv_pack_geometry, conv_pack_index, conv_wy_pack_index, get_hw,      # noqa: F401  (re-exported:
                       pack_conv_part, pack_conv_weight, pack_conv_weight_wy, satu_axis_tables, split_bf16_image, window_record)                            # tests and tools import them from here)
-from .yuv import CHROMAS, COLOURS, frame_bytes, layout_name
+from .yuv import CHROMAS, COLOURS, SITINGS, frame_bytes, layout_name
 
 
 class HipEngine(WeightPacking, ContextCache, Launcher):
@@ -798,7 +798,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
 
     def forward_video(self, frames: torch.Tensor, windows: List[List[int]], scale, out_u8: bool = False, ensemble: bool = False,
                       i420: Optional[Tuple[int, int]] = None, out_i420: bool = False, colour: int = 0, out_colour: int = 0, depth: int = 8,
-                      out_depth: int = 8, chroma: int = 0, out_chroma: int = 0) -> torch.Tensor:
+                      out_depth: int = 8, chroma: int = 0, out_chroma: int = 0, siting: int = 0, out_siting: int = 0) -> torch.Tensor:
         """The sequence path (SAVSR.upscale_video): frames [N, h, w, c] uint8 or [N, c, h, w] fp32 on the device, windows[i] = the
         num_frame frame indices of output frame i in clip order (harness.window_indices) -> [len(windows), c, H, W] fp32, or
         [len(windows), H, W, c] uint8 (out_u8: tensor2img(x, rgb2bgr=False) per frame, savsr_video_quantize_u8).
@@ -806,14 +806,16 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         `streams_for` streams; throughput flow), so frame i equals forward_many on the gathered window i bit for bit.  A unit's windows are
         gathered from `frames` by savsr_video_gather_u8 / _f32 into a unit-sized fp32 clip batch on the unit's stream; nothing is gathered
         or converted on the host.  ensemble=True: frame i is the self-ensemble of window i (`_ensemble`, gathered by savsr_ensemble_gather_*).
-        i420=(h, w): frames are [N, i420_bytes(h, w)] uint8, planar YUV 4:2:0 (savsr_amd/yuv.py), gathered by savsr_video_gather_yuvp where
-        the uint8 gather runs; out_i420: the result is [len(windows), i420_bytes(H, W)] uint8, quantised by savsr_video_quantize_yuvp where
+        i420=(h, w): frames are [N, i420_bytes(h, w)] uint8, planar YUV 4:2:0 (savsr_amd/yuv.py), gathered by savsr_video_gather_yuvs where
+        the uint8 gather runs; out_i420: the result is [len(windows), i420_bytes(H, W)] uint8, quantised by savsr_video_quantize_yuvs where
         the uint8 quantisation runs.  colour / out_colour: the colour space ids (positions in yuv.COLOURS) of the I420 input / output.  With
         the ensemble, I420 frames are converted once to fp32 planar RGB (the same gather with the identity list) and take the fp32 path,
         and an I420 result is the fp32 merge followed by the quantisation.  depth / out_depth = 10, 12: the I420 frames in / out hold 16-bit
         samples ([N, 2 * i420_bytes] uint8, limited range only), and nothing else changes.  chroma / out_chroma: the chroma layout ids
         (positions in yuv.CHROMAS: 4:2:0, 4:2:2, 4:4:4) of the YUV input / output, [N, frame_bytes(h, w, depth, chroma)] uint8.  The two
-        entries serve every (layout, depth); at 4:2:0 they run the kernels of savsr_video_gather_yuv420(_16) / _quantize_yuv420(_16)."""
+        entries serve every (layout, depth); at 4:2:0 they run the kernels of savsr_video_gather_yuv420(_16) / _quantize_yuv420(_16).
+        siting / out_siting: the chroma siting ids of the YUV input / output (0 = not modelled, else the position in yuv.SITINGS plus one);
+        the two call sites go through savsr_video_gather_yuvs / _quantize_yuvs, which at 0 run the kernels of the _yuvp entries."""
         if out_u8 and out_i420:
             raise ValueError("one output kind: uint8 or I420")
         for what, d, on, cs in (("depth", depth, i420 is not None, colour), ("out_depth", out_depth, out_i420, out_colour)):
@@ -826,6 +828,11 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         for what, cid, on in (("chroma", chroma, i420 is not None), ("out_chroma", out_chroma, out_i420)):
             if cid not in range(len(CHROMAS)) or (cid != 0 and not on):
                 raise ValueError(f"{what} = {cid!r}: 0 .. {len(CHROMAS) - 1} ({', '.join(CHROMAS)}), and not 0 with YUV frames on that side only")
+        for what, sid, on, cid in (("siting", siting, i420 is not None, chroma), ("out_siting", out_siting, out_i420, out_chroma)):
+            if sid not in range(len(SITINGS) + 1) or (sid != 0 and not on):
+                raise ValueError(f"{what} = {sid!r}: 0 (not modelled) or 1 .. {len(SITINGS)} ({', '.join(SITINGS)}), and not 0 with YUV frames on that side only")
+            if sid == 3 and CHROMAS[cid] == "422":
+                raise ValueError(f"{what} = 3 (topleft) with 4:2:2 chroma: 4:2:2 has no vertical subsampling; its cosited form is 2 (left)")
         lay, out_lay = CHROMAS[chroma], CHROMAS[out_chroma]
         if i420 is not None:
             h, w = (int(v) for v in i420)
@@ -855,8 +862,8 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             raise ValueError(f"num_frame = {T}: the window gather takes at most {_lib.VIDEO_MAX_SLOTS} frames per launch")
         if i420 is not None:
             def gather(idx, dst, st):
-                _lib.check(self.lib.savsr_video_gather_yuvp(frames.data_ptr(), N, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), colour, depth,
-                                                            chroma, dst.data_ptr(), st), "savsr_video_gather_yuvp")
+                _lib.check(self.lib.savsr_video_gather_yuvs(frames.data_ptr(), N, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), colour, depth,
+                                                            chroma, siting, dst.data_ptr(), st), "savsr_video_gather_yuvs")
         else:
             fn = self.lib.savsr_video_gather_u8 if u8 else self.lib.savsr_video_gather_f32
 
@@ -867,8 +874,8 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             for a in range(0, int(src.shape[0]), 65535):          # (the entries take 1 .. 65535 frames)
                 nb = min(65535, int(src.shape[0]) - a)
                 if out_i420:
-                    _lib.check(self.lib.savsr_video_quantize_yuvp(src[a:a + nb].data_ptr(), nb, H, W, out_colour, out_depth, out_chroma,
-                                                                  dst[a:a + nb].data_ptr(), st), "savsr_video_quantize_yuvp")
+                    _lib.check(self.lib.savsr_video_quantize_yuvs(src[a:a + nb].data_ptr(), nb, H, W, out_colour, out_depth, out_chroma, out_siting,
+                                                                  dst[a:a + nb].data_ptr(), st), "savsr_video_quantize_yuvs")
                 else:
                     _lib.check(self.lib.savsr_video_quantize_u8(src[a:a + nb].data_ptr(), nb, c, H, W, dst[a:a + nb].data_ptr(), st), "savsr_video_quantize_u8")
         if ensemble:

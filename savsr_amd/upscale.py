@@ -8,6 +8,7 @@
     python -m savsr_amd.upscale -i in.y4m -o out.y4m --scale 4 --checkpoint <net.pth> --cuts auto --cuts-out cuts.txt
     python -m savsr_amd.upscale -i sd.y4m -o hd.y4m --scale 4 --checkpoint <net.pth> --colour auto --out-colour auto
     python -m savsr_amd.upscale -i in8.y4m -o out10.y4m --scale 4 --checkpoint <net.pth> --out-depth 10
+    ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o - --scale 4 --checkpoint <net.pth> --siting auto --out-siting same | ffmpeg -i - out.mp4
     ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out444p10.y4m --scale 4 --checkpoint <net.pth> --out-chroma 444
 
 PNG folder: frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on
@@ -36,8 +37,15 @@ by default is yuv420p10).  10 and 12 bits go with limited range only: a full-ran
 
 --out-chroma: the chroma layout of a Y4M output, 420, 422, 444 or same (the default: the input's; 4:2:0 for a PNG folder).  A 4:2:2 or
 4:4:4 Y4M input (C422, C444 and their p10 / p12 forms) is read as it is; its layout comes from the header.  The two sides are
-independent: 4:2:0 in, --out-chroma 444 writes the network's full-resolution chroma instead of box-filtering it 2 x 2.  Chroma is
-centre-sited in every layout; the cosited convention of MPEG-2 4:2:2 is not modelled.
+independent: 4:2:0 in, --out-chroma 444 writes the network's full-resolution chroma instead of box-filtering it 2 x 2.
+
+--siting / --out-siting: where the chroma samples of a 4:2:0 / 4:2:2 Y4M input / output lie: centre (JPEG, MPEG-1; C420jpeg), left
+(MPEG-2, H.264, HEVC 4:2:0 and every standard 4:2:2; C420mpeg2: what `ffmpeg -f yuv4mpegpipe` tags such streams) or topleft (C420paldv;
+4:2:0 only).  With a siting, input chroma is interpolated linearly at the positions it names and output chroma is filtered to them
+(savsr_amd/yuv.py).  The defaults are none: nearest replication in, block mean out, so an existing command line writes the bytes it
+wrote.  --siting auto takes what the input's C tag names (none for a plain C420, a missing tag, C422, C444 and the p10 / p12 tags) and
+says on stderr what it resolved to; --out-siting same is whatever the input side resolved to.  An 8-bit 4:2:0 output is tagged
+C420mpeg2 / C420paldv for left / topleft and C420jpeg otherwise.
 
 --cuts: edited footage.  Windows stop at scene cuts (every scene is upscaled as a video of its own, savsr_amd/scenes.py): auto finds
 them on the GPU as the frames arrive (--scene-threshold, per cent of the largest possible frame change; ffmpeg scdet's rule and default,
@@ -57,7 +65,7 @@ import time
 from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional
 
-from .yuv import COLOURS
+from .yuv import COLOURS, SITINGS
 
 MAX_WRITERS = 16
 PINNED_BUFFERS = 3          # SR chunks in flight between the GPU and the Y4M writer thread
@@ -89,6 +97,27 @@ def resolve_colours(colour: str, out_colour: str, lr, hr, in_range: Optional[str
         else:
             cout = out_colour
     return cin, cout
+
+
+def resolve_sitings(siting: str, out_siting: str, tag_siting: Optional[str], chroma: Optional[str], out_chroma: Optional[str]):
+    """--siting / --out-siting -> (siting of the Y4M input, siting of the Y4M output), each None or one of yuv.SITINGS.  tag_siting: what
+    the input's C tag names (Y4MReader.siting); chroma / out_chroma: the layout of a Y4M input / output, None for a PNG folder on that
+    side.  `auto` is the tag's; `same` is what the input side resolved to.  4:4:4 has nothing to resample: a siting there resolves to
+    None.  topleft on a 4:2:2 side is refused (ValueError)."""
+    from .yuv import check_siting
+    sin = None
+    if chroma is not None:
+        sin = tag_siting if siting == "auto" else (None if siting == "none" else siting)
+        if chroma == "444":
+            sin = None
+        check_siting(sin, chroma, "--siting")
+    sout = None
+    if out_chroma is not None:
+        sout = sin if out_siting == "same" else (None if out_siting == "none" else out_siting)
+        if out_chroma == "444":
+            sout = None
+        check_siting(sout, out_chroma, "--out-siting")
+    return sin, sout
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -123,6 +152,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--out-chroma", default=None, choices=["420", "422", "444", "same"],
                    help="chroma layout of a Y4M output (default same: the input's; 420 for a PNG folder).  422 / 444 write C422 / C444 "
                         "(C422p10 ... with --out-depth 10 / 12); 444 keeps the network's full-resolution chroma")
+    p.add_argument("--siting", default=None, choices=["none", "auto"] + list(SITINGS),
+                   help="chroma siting of a 4:2:0 / 4:2:2 Y4M input (default none: not modelled, nearest replication).  auto: what the input's "
+                        "C tag names (C420jpeg centre, C420mpeg2 left, C420paldv topleft, none otherwise), reported on stderr; with a siting, "
+                        "chroma is interpolated linearly at its positions")
+    p.add_argument("--out-siting", default=None, choices=["none", "same"] + list(SITINGS),
+                   help="chroma siting of a 4:2:0 / 4:2:2 Y4M output (default none: block mean).  same: what the input side resolved to; "
+                        "left / topleft filter cosited axes with [1 2 1] / 4 and tag an 8-bit 4:2:0 output C420mpeg2 / C420paldv")
     p.add_argument("--cuts", default=None, metavar="auto|K,K,...|@FILE",
                    help="scene cuts (first frame of every new scene): auto = found on the GPU, a comma-separated list, or @FILE with one index "
                         "per line; windows stop at cuts")
@@ -186,6 +222,12 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--out-depth goes with a Y4M output (PNG frames are 8-bit RGB)")
     if a.out_chroma is not None and not a.y4m_out:
         p.error("--out-chroma goes with a Y4M output (PNG frames are RGB)")
+    if a.siting is not None and not a.y4m_in:
+        p.error("--siting goes with a Y4M input (PNG frames are RGB)")
+    if a.out_siting is not None and not a.y4m_out:
+        p.error("--out-siting goes with a Y4M output (PNG frames are RGB)")
+    a.siting = a.siting or "none"
+    a.out_siting = a.out_siting or "none"
     a.out_depth = None if a.out_depth in (None, "same") else int(a.out_depth)          # (None: the input's)
     a.out_chroma = None if a.out_chroma in (None, "same") else a.out_chroma            # (None: the input's)
     a.colour_flags = a.colour is not None or a.out_colour is not None       # (either given: the output is tagged, the summary names them)
@@ -347,12 +389,13 @@ def main(argv: Optional[List[str]] = None) -> int:
             reader = Y4MReader(fin, high_depth=True, layouts=CHROMAS)
             h, w, depth, chroma = reader.height, reader.width, reader.depth, reader.chroma
             fps, interlace, aspect, in_range = reader.fps, reader.interlace, reader.aspect, reader.colour_range
+            tag_siting = reader.siting
             chunks = (torch.from_numpy(c) for c in reader.chunks(a.chunk))
         else:
             from .io import FrameStore
             store = FrameStore()
             h = w = None
-            depth, chroma = 8, "420"
+            depth, chroma, tag_siting = 8, "420", None
             if a.y4m_out:                           # (the Y4M header needs the SR size before the first frame: the PNG's header gives it)
                 from PIL import Image
                 with Image.open(paths[0]) as im:
@@ -376,12 +419,19 @@ def main(argv: Optional[List[str]] = None) -> int:
             check_depths(depth, out_depth, fmt_in, fmt_out, colour or "bt601", out_colour)
         except ValueError as e:
             raise SystemExit(f"--colour / --out-colour / --out-depth: {e}") from None
+        try:
+            siting, out_siting = resolve_sitings(a.siting, a.out_siting, tag_siting, chroma if a.y4m_in else None, out_chroma)
+        except ValueError as e:
+            raise SystemExit(f"--siting / --out-siting: {e}") from None
+        if a.siting == "auto":
+            print(f"--siting auto: C{reader.colorspace} -> {siting or 'none'}", file=sys.stderr, flush=True)
         if a.y4m_out:
             H, W = hr
             fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
             full = is_full_range(out_colour)
             tag = ("full" if full else "limited") if (full or a.colour_flags) else None
-            sink = Y4MSink(Y4MWriter(fout, W, H, fps, interlace, scaled_aspect(aspect, (h, w), (H, W)), tag, depth=out_depth, chroma=out_chroma),
+            sink = Y4MSink(Y4MWriter(fout, W, H, fps, interlace, scaled_aspect(aspect, (h, w), (H, W)), tag, depth=out_depth, chroma=out_chroma,
+                                     siting=out_siting),
                            a.chunk + net.num_frame)
         else:
             sink = PngSink(a.output, None if paths is None else [os.path.basename(p) for p in paths],
@@ -389,7 +439,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         t0 = time.perf_counter()
         up = VideoUpscaler(net, a.scale, a.padding, out=fmt_out, pixel_format=fmt_in,
                            size=(h, w) if a.y4m_in else None, cuts=a.cuts, scene_threshold=a.scene_threshold, colour=colour or "bt601",
-                           out_colour=out_colour, depth=depth, out_depth=out_depth)
+                           out_colour=out_colour, depth=depth, out_depth=out_depth, siting=siting, out_siting=out_siting)
         done = 0
         try:
             for chunk in chunks:
@@ -414,6 +464,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         scenes += f", {depth} -> {out_depth or 8} bits"
     if chroma != "420" or (out_chroma or "420") != "420":
         scenes += f", chroma {chroma if a.y4m_in else 'rgb'} -> {out_chroma or 'rgb'}"
+    if siting is not None or out_siting is not None:
+        scenes += f", siting {siting or 'none'} -> {out_siting or 'none'}"
     print(f"upscaled {done} frames in {dt:.2f} s: {done / dt:.2f} frames/s{scenes}", file=sys.stderr if a.output == "-" else sys.stdout, flush=True)
     return 0
 

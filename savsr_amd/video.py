@@ -9,7 +9,9 @@ numerics), converted on the device on either side of the network (savsr_video_ga
 out_depth = 10, 12: the frames hold little-endian 16-bit samples ([N, 2 * i420_bytes(h, w)] uint8, Y4M's C420p10 / C420p12;
 savsr_video_gather_yuv420_16 / savsr_video_quantize_yuv420_16), limited range only.  pixel_format / out = "i422", "i444": the 4:2:2 and
 4:4:4 layouts of the same planes ([N, yuv.frame_bytes(h, w, depth, chroma)] uint8), with everything above applying to them as well; the
-two sides are independent.  Every YUV side goes through one entry, savsr_video_gather_yuvp / savsr_video_quantize_yuvp.
+two sides are independent.  siting / out_siting: the chroma siting of the YUV input / output (yuv.SITINGS; linear chroma reconstruction in,
+cosited filters out; None = not modelled: nearest up, box down).  Every YUV side goes through one entry, savsr_video_gather_yuvs /
+savsr_video_quantize_yuvs.
 
 cuts=[k, ...] / cuts="auto": the video is a sequence of scenes and every scene is treated as a video of its own (savsr_amd/scenes.py:
 windows stop at cuts); "auto" finds the cuts on the device (savsr_video_pair_sad_*, then scdet's rule on the host).  cuts=None runs
@@ -24,7 +26,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 import torch
 
 from .harness import window_indices
-from .yuv import CHROMA_OF, CHROMAS, check_colour, check_depth, check_depth_colour, frame_bytes, i420_bytes, layout_name
+from .yuv import CHROMA_OF, CHROMAS, check_colour, check_depth, check_depth_colour, check_siting, frame_bytes, i420_bytes, layout_name
 
 PADDING_MODES = ("replicate", "reflection", "reflection_circle", "circle")
 OUT_KINDS = ("float", "uint8", "i420", "i422", "i444")
@@ -137,6 +139,18 @@ def check_depths(depth, out_depth, pixel_format: str, out: str, colour: str = "b
     if out in YUV_FORMATS:
         check_depth_colour(od, colour if out_colour is None else out_colour, "out_depth", "out_colour")
     return d, od
+
+
+def check_sitings(siting, out_siting, pixel_format: str, out: str) -> Tuple[int, int]:
+    """The chroma siting ids (0 = None: not modelled; else the position in yuv.SITINGS plus one) of the YUV input and output.  `siting`
+    goes with a YUV pixel_format and `out_siting` with a YUV out; the two are independent (out_siting = None is not "the same")."""
+    sid = check_siting(siting, chroma_of(pixel_format), "siting")
+    osid = check_siting(out_siting, chroma_of(out), "out_siting")
+    if siting is not None and pixel_format not in YUV_FORMATS:
+        raise ValueError(f"siting = {siting!r} goes with pixel_format = {_YUV_LIST}: it is the chroma siting of YUV input (RGB frames have no chroma planes)")
+    if out_siting is not None and out not in YUV_FORMATS:
+        raise ValueError(f"out_siting = {out_siting!r} goes with out = {_YUV_LIST}: it is the chroma siting of YUV output")
+    return sid, osid
 
 
 def check_sample_alignment(frames: torch.Tensor, depth: int, chroma: str = "420") -> None:
@@ -298,7 +312,8 @@ def detect_cuts(frames: torch.Tensor, threshold=10.0, pixel_format: str = "rgb",
 
 def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
                   size=None, cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601",
-                  out_colour: Optional[str] = None, depth: int = 8, out_depth: Optional[int] = None) -> torch.Tensor:
+                  out_colour: Optional[str] = None, depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None,
+                  out_siting: Optional[str] = None) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
@@ -306,6 +321,7 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     i420 = check_pixel_format(pixel_format, size)
     cid, ocid = check_colours(colour, out_colour, pixel_format, out)
     d, od = check_depths(depth, out_depth, pixel_format, out, colour, out_colour)
+    sid, osid = check_sitings(siting, out_siting, pixel_format, out)
     sc = as_scale(net.scale if scale is None else scale)
     chroma, out_chroma = chroma_of(pixel_format), chroma_of(out)
     n = i420_layout(frames, i420, net.cfg["num_in_ch"], d, chroma) if i420 else frame_layout(frames, net.cfg["num_in_ch"])[0]
@@ -334,7 +350,7 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     with torch.no_grad():
         return net.engine().forward_video(frames, windows, sc, out == "uint8", ensemble=net.self_ensemble, i420=i420,
                                           out_i420=out in YUV_FORMATS, colour=cid, out_colour=ocid, depth=d, out_depth=od,
-                                          chroma=CHROMAS.index(chroma), out_chroma=CHROMAS.index(out_chroma))
+                                          chroma=CHROMAS.index(chroma), out_chroma=CHROMAS.index(out_chroma), siting=sid, out_siting=osid)
 
 
 class VideoUpscaler:
@@ -353,7 +369,8 @@ class VideoUpscaler:
 
     colour / out_colour: the colour spaces of I420 chunks in / out, as in upscale_video.  depth / out_depth: their bit depths (10, 12:
     chunks of [k, 2 * i420_bytes(h, w)] uint8, 16-bit samples), as in upscale_video.  pixel_format / out = "i422", "i444": chunks of
-    [k, yuv.frame_bytes(h, w, depth, chroma)] uint8 in those layouts, as in upscale_video.
+    [k, yuv.frame_bytes(h, w, depth, chroma)] uint8 in those layouts, as in upscale_video.  siting / out_siting: the chroma siting of YUV
+    chunks in / out, as in upscale_video.
 
     cuts=[k, ...] (global frame indices) or cuts="auto" (each push scores its new pairs on the device, the pair with the previous
     push's last frame included, and decides with `scene_threshold`): windows stop at cuts as in upscale_video(cuts=...), and `up.cuts`
@@ -362,7 +379,7 @@ class VideoUpscaler:
 
     def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb", size=None,
                  cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None,
-                 depth: int = 8, out_depth: Optional[int] = None):
+                 depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None):
         _check_net(net)
         check_padding(padding)
         check_out(out, net.cfg["num_in_ch"])
@@ -380,6 +397,7 @@ class VideoUpscaler:
         self._fmt = pixel_format
         self._colours = check_colours(colour, out_colour, pixel_format, out)      # colour space ids of the I420 input / output
         self._depths = check_depths(depth, out_depth, pixel_format, out, colour, out_colour)      # bit depths of the I420 input / output
+        self._sitings = check_sitings(siting, out_siting, pixel_format, out)      # chroma siting ids of the YUV input / output
         self.net, self.padding, self.out = net, padding, out
         self.scale = as_scale(net.scale if scale is None else scale)
         self.ensemble = net.self_ensemble          # (read once, like the scale: every chunk runs the same flow)
@@ -419,7 +437,8 @@ class VideoUpscaler:
             res = self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble, i420=self.i420,
                                                   out_i420=self.out in YUV_FORMATS, colour=self._colours[0], out_colour=self._colours[1],
                                                   depth=self._depths[0], out_depth=self._depths[1], chroma=CHROMAS.index(self._chromas[0]),
-                                                  out_chroma=CHROMAS.index(self._chromas[1]))
+                                                  out_chroma=CHROMAS.index(self._chromas[1]), siting=self._sitings[0],
+                                                  out_siting=self._sitings[1])
         self.done = upto
         return res
 
@@ -478,7 +497,8 @@ class VideoUpscaler:
             return self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble, i420=self.i420,
                                                    out_i420=self.out in YUV_FORMATS, colour=self._colours[0], out_colour=self._colours[1],
                                                    depth=self._depths[0], out_depth=self._depths[1], chroma=CHROMAS.index(self._chromas[0]),
-                                                   out_chroma=CHROMAS.index(self._chromas[1]))
+                                                   out_chroma=CHROMAS.index(self._chromas[1]), siting=self._sitings[0],
+                                                  out_siting=self._sitings[1])
 
     def _push_scenes(self, k: int) -> torch.Tensor:
         plan = self._plan

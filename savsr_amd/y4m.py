@@ -5,8 +5,9 @@ from another program (ffmpeg -f yuv4mpegpipe, x264, a player) without a library.
     FRAME\\n<h * w Y bytes><ch * cw U bytes><ch * cw V bytes>   per frame (an I420 frame, savsr_amd/yuv.py); FRAME may carry parameters
 
 8-bit 4:2:0 only: C420, C420jpeg, C420mpeg2, C420paldv and a missing C tag (= 420) are read; every other tag is refused by name.  The
-three 420 tags differ in chroma siting only, which is accepted and ignored (yuv.py's nearest / box pair is centre-sited); the writer
-tags its output C420jpeg.  XCOLORRANGE=FULL / XCOLORRANGE=LIMITED (ffmpeg's extension tag) is read into `colour_range` and written on
+three 420 tags differ in chroma siting only: the reader hands it out as `siting` ("centre", "left", "topleft" of yuv.SITINGS, ffmpeg's
+mapping of the three; None for a plain C420, a missing tag and every other tag, which carry none) and converts nothing itself; the
+writer tags its output C420jpeg unless told another siting (Y4MWriter(..., siting=)).  XCOLORRANGE=FULL / XCOLORRANGE=LIMITED (ffmpeg's extension tag) is read into `colour_range` and written on
 request; the format has no tag for the matrix (BT.601 / BT.709), which is the caller's to know or to guess from the frame size.
 
 10 and 12 bits: Y4MReader(f, high_depth=True) also reads C420p10 and C420p12, whose frames hold little-endian 16-bit samples in the same
@@ -15,9 +16,9 @@ a caller written against one byte per sample never receives two; Y4MWriter(..., 
 
 4:2:2 and 4:4:4: Y4MReader(f, layouts=("420", "422", "444")) also reads C422 and C444, and with high_depth=True C422p10, C422p12, C444p10
 and C444p12; `chroma` says which layout the stream has and `frame_bytes` is yuv.frame_bytes(height, width, depth, chroma).  An opt-in
-like high_depth, for the same reason.  Y4MWriter(..., chroma="422" | "444") writes them.  Chroma siting is not modelled (centre-sited
-in every layout, yuv.py): C422 means MPEG-2's horizontally cosited chroma to some tools, which is accepted and ignored as the three
-C420 variants are.  C444alpha, Cmono, C411 and 14- / 16-bit tags stay refused by name.
+like high_depth, for the same reason.  Y4MWriter(..., chroma="422" | "444") writes them.  These tags and the p10 / p12 ones name no
+siting (`siting` is None): C422 means MPEG-2's horizontally cosited chroma to most tools, which is the caller's to say
+(siting="left" of yuv.py).  C444alpha, Cmono, C411 and 14- / 16-bit tags stay refused by name.
 """
 from __future__ import annotations
 
@@ -26,10 +27,11 @@ from typing import Iterator, Optional, Tuple
 
 import numpy as np
 
-from .yuv import CHROMAS, check_chroma, frame_bytes
+from .yuv import CHROMAS, SITINGS, check_chroma, frame_bytes
 
 MAGIC = b"YUV4MPEG2"
 C420_TAGS = ("420", "420jpeg", "420mpeg2", "420paldv")
+C420_SITINGS = {"420jpeg": "centre", "420mpeg2": "left", "420paldv": "topleft"}        # ffmpeg's reading of the three; no other tag names one
 C420_HIGH_TAGS = {"420p10": 10, "420p12": 12}        # tag -> bit depth (Y4MReader with high_depth=True, Y4MWriter with depth=)
 # 4:2:2 / 4:4:4 tags -> (chroma layout, bit depth); the high-depth ones need high_depth=True as well (Y4MReader with layouts=)
 CHROMA_TAGS = {"422": ("422", 8), "444": ("444", 8)}
@@ -106,7 +108,9 @@ class Y4MReader:
     the rows of a 10- or 12-bit stream are [m, 2 * i420_bytes(height, width)] uint8 (little-endian 16-bit samples).
     layouts: the chroma layouts (yuv.CHROMAS) the caller takes; with "422" / "444" in it C422 / C444 (and, with high_depth, their p10 /
     p12 forms) are read too, `chroma` is the stream's layout and the rows are [m, yuv.frame_bytes(height, width, depth, chroma)].
-    The default reads 4:2:0 only and words every refusal as it did before layouts existed."""
+    The default reads 4:2:0 only and words every refusal as it did before layouts existed.
+    siting (read-only): the chroma siting the C tag names, "centre" (C420jpeg), "left" (C420mpeg2) or "topleft" (C420paldv); None for
+    a plain C420, a missing tag and every other tag."""
 
     def __init__(self, f, high_depth: bool = False, layouts=("420",)):
         self.f = f
@@ -128,6 +132,7 @@ class Y4MReader:
         self.aspect: Tuple[int, int] = (0, 0)
         self.colorspace = "420"
         self.colour_range: Optional[str] = None
+        self._siting: Optional[str] = None
         for tag in line[len(MAGIC):].decode("ascii", errors="replace").split():
             key, val = tag[0], tag[1:]
             if key in "WH":
@@ -165,6 +170,7 @@ class Y4MReader:
                 elif val not in C420_TAGS:
                     raise ValueError(f"y4m: colour space tag 'C{val}' is not supported: 8-bit 4:2:0 only ({', '.join('C' + t for t in C420_TAGS)})")
                 self.colorspace = val
+                self._siting = C420_SITINGS.get(val)
             elif key == "X":                          # comments / extensions (XYSCSS=...): ignored, but for the range
                 if val in ("COLORRANGE=FULL", "COLORRANGE=LIMITED"):
                     self.colour_range = val[11:].lower()
@@ -174,6 +180,10 @@ class Y4MReader:
             raise ValueError("y4m: the header names no W / H")
         self.frame_bytes = frame_bytes(self.height, self.width, self.depth, self.chroma)
         self.frames_read = 0
+
+    @property
+    def siting(self) -> Optional[str]:
+        return self._siting
 
     def _frame_into(self, row: np.ndarray) -> bool:
         line = _read_line(self.f)
@@ -208,10 +218,11 @@ class Y4MWriter:
     colour_range = "full" / "limited": the header also carries XCOLORRANGE=FULL / =LIMITED (None: no such tag).  depth = 10, 12: the
     stream is tagged C420p10 / C420p12 and its frames are [m, 2 * i420_bytes(height, width)] uint8 (little-endian 16-bit samples).
     chroma = "422", "444": the stream is tagged C422 / C444 (C422p10 ... at depth 10 / 12) and its frames are
-    [m, yuv.frame_bytes(height, width, depth, chroma)] uint8."""
+    [m, yuv.frame_bytes(height, width, depth, chroma)] uint8.  siting: the chroma siting of the frames (yuv.SITINGS or None); an 8-bit
+    4:2:0 stream is tagged C420mpeg2 for "left", C420paldv for "topleft" and C420jpeg otherwise; no other header has a tag for it."""
 
     def __init__(self, f, width: int, height: int, fps: Tuple[int, int] = (25, 1), interlace: str = "p", aspect: Tuple[int, int] = (0, 0),
-                 colour_range: Optional[str] = None, depth: int = 8, chroma: str = "420"):
+                 colour_range: Optional[str] = None, depth: int = 8, chroma: str = "420", siting: Optional[str] = None):
         if width < 1 or height < 1:
             raise ValueError(f"y4m: W, H >= 1, got {width} x {height}")
         if colour_range is not None and colour_range not in COLOUR_RANGES:
@@ -222,9 +233,12 @@ class Y4MWriter:
             check_chroma(chroma)
         except ValueError as e:
             raise ValueError(f"y4m: {e}") from None
+        if siting is not None and siting not in SITINGS:
+            raise ValueError(f"y4m: siting = {siting!r}: None or one of {', '.join(SITINGS)}")
         self.f, self.width, self.height, self.depth, self.chroma = f, int(width), int(height), int(depth), chroma
         self.frame_bytes = frame_bytes(self.height, self.width, self.depth, chroma)
-        ctag = ("420jpeg" if chroma == "420" else chroma) if depth == 8 else f"{chroma}p{self.depth}"
+        tag420 = {"left": "420mpeg2", "topleft": "420paldv"}.get(siting, "420jpeg")
+        ctag = (tag420 if chroma == "420" else chroma) if depth == 8 else f"{chroma}p{self.depth}"
         self.header = (f"YUV4MPEG2 W{self.width} H{self.height} F{fps[0]}:{fps[1]} I{interlace} A{aspect[0]}:{aspect[1]} C{ctag}"
                        f"{'' if colour_range is None else ' XCOLORRANGE=' + colour_range.upper()}\n").encode("ascii")
         f.write(self.header)

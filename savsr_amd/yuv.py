@@ -1,5 +1,6 @@
 """Planar YUV 4:2:0 (I420) <-> RGB, the host restatement that specifies savsr_video_gather_i420 / savsr_video_quantize_i420 (yuv.hip);
-with `chroma=` also 4:2:2 and 4:4:4 (savsr_video_gather_yuvp / savsr_video_quantize_yuvp, see "Chroma layouts" below).
+with `chroma=` also 4:2:2 and 4:4:4 (savsr_video_gather_yuvp / savsr_video_quantize_yuvp, see "Chroma layouts" below) and with `siting=`
+the chroma siting and a linear chroma reconstruction (savsr_video_gather_yuvs / savsr_video_quantize_yuvs, see "Chroma siting" below).
 
 The default colour matrix is the reference's (lbasicsr/utils/color_util.py, `rgb2ycbcr` / `ycbcr2rgb`: ITU-R BT.601, limited range,
 Matlab's rounded constants: `BT601`), the same whose Y row metrics.py uses for PSNR-Y.  4:2:0 only, at 8, 10 or 12 bits (`depth=`;
@@ -36,8 +37,34 @@ samples, then ch * cw U samples, then ch * cw V samples with (ch, cw) = `chroma_
 (h, ceil(w / 2)) for 4:2:2 and (h, w) for 4:4:4; `frame_bytes(h, w, depth, chroma)` bytes, the samples as wide as above.  The arithmetic
 is 4:2:0's with another block shape and nothing else: to RGB, chroma sample (cy, cx) serves pixels (cy, 2 cx .. 2 cx + 1) in 4:2:2 and
 pixel (cy, cx) in 4:4:4 (nearest replication); from RGB, Cb / Cr come from the mean RGB of the block's in-image pixels, (a + b) * 0.5
-for a 4:2:2 pair, the pixel alone in the last column of an odd W, and the pixel's own clamped RGB in 4:4:4 (no mean).  Chroma is
-centre-sited like the 4:2:0 pair; the horizontally cosited convention of MPEG-2 4:2:2 is not modelled.
+for a 4:2:2 pair, the pixel alone in the last column of an odd W, and the pixel's own clamped RGB in 4:4:4 (no mean).  That pair --
+nearest up, box down -- is what `siting=None` runs; it models no chroma siting.
+
+Chroma siting (`siting=` None or one of SITINGS; the position in SITINGS plus one is the id of the C ABI, SAVSR_SITING_*, 0 = None;
+the specification of savsr_video_gather_yuvs / savsr_video_quantize_yuvs).  Where chroma sample (cy, cx) lies, in luma pixel coordinates:
+
+    siting      4:2:0 x      4:2:0 y      4:2:2 x      4:2:2 y
+    centre      2 cx + 0.5   2 cy + 0.5   2 cx + 0.5   cy           JPEG, MPEG-1 (Y4M's C420jpeg)
+    left        2 cx         2 cy + 0.5   2 cx         cy           MPEG-2, H.264, HEVC 4:2:0 and every standard 4:2:2 (C420mpeg2)
+    topleft     2 cx         2 cy         refused      refused      (C420paldv, as ffmpeg maps it); 4:2:2 has no vertical subsampling
+
+4:4:4 has nothing to resample: any siting there runs the code of siting=None and gives its bytes.
+
+  i420_to_rgb   chroma at every luma pixel is the separable linear interpolation between the two nearest chroma samples at the positions
+                above, edge samples replicated, samples above 2^d - 1 clipped first (`interpolate_chroma`).  Per subsampled axis, for
+                pixel 2 c and pixel 2 c + 1:  centre (3 C[c] + C[c - 1]) / 4 and (3 C[c] + C[c + 1]) / 4;  cosited C[c] and
+                (C[c] + C[c + 1]) / 2.  The value is an integer numerator (at most 4095 * 16) times 2^-4 (4:2:0) or 2^-2 (4:2:2): exact
+                in float32 whatever the order.  It then takes the coefficient arithmetic of "High depth" at every depth, 8 included
+                (k = 1, so all four colour spaces at 8 bits; limited range only at 10 / 12 as ever): the same bound, within
+                5 * 2.5 * 2^-24 < 1e-6 of the float64 closed form.  Constant chroma planes therefore give the RGB of siting=None bit for
+                bit at 10 / 12 bits and within 1e-6 at 8 bits (the table path and the coefficient path round differently).
+  rgb_to_i420   None and "centre" are `_block_mean`, bit for bit: the box is the centre-sited filter.  Cosited axes take [1 2 1] / 4:
+                h3(l, c, r) = ((l + r) + (c + c)) * 0.25 in float32, every tap index clamped into the image (`filter_chroma_rgb`).
+                left, 4:2:2: h3(p[y, 2 cx - 1], p[y, 2 cx], p[y, 2 cx + 1]) = Hrow(y).  left, 4:2:0: (Hrow(2 cy) + Hrow(2 cy + 1)) * 0.5,
+                Hrow(2 cy) alone on the last row of an odd H.  topleft, 4:2:0: ((Hrow(2 cy - 1) + Hrow(2 cy + 1)) + (Hrow(2 cy) +
+                Hrow(2 cy))) * 0.25, rows clamped.  `_row`, the product by k, rint and the full-range clip follow as without a siting.
+
+Filters longer than linear, PAL-DV's alternating Cb / Cr lines (read as topleft, as ffmpeg does), interlaced 4:2:0 and 4:1:1 are not modelled.
 """
 from __future__ import annotations
 
@@ -147,6 +174,22 @@ def chroma_hw(h: int, w: int, chroma: str = "420") -> Tuple[int, int]:
     return (h, (w + 1) // 2) if CHROMAS[check_chroma(chroma)] == "422" else (h, w)
 
 
+# The chroma sitings of `siting=`; the id of the C ABI (SAVSR_SITING_*) is the position plus one, 0 (None) = not modelled.
+SITINGS = ("centre", "left", "topleft")
+
+
+def check_siting(siting, chroma: str = "420", what: str = "siting") -> int:
+    """The C-ABI id of a siting: 0 for None, the position in SITINGS plus one otherwise; refuses anything else, naming the list, and
+    "topleft" with 4:2:2, naming the rule."""
+    if siting is None:
+        return 0
+    if not isinstance(siting, str) or siting not in SITINGS:
+        raise ValueError(f"{what} = {siting!r}: None or one of {', '.join(SITINGS)}")
+    if siting == "topleft" and CHROMAS[check_chroma(chroma)] == "422":
+        raise ValueError(f"{what} = 'topleft' with 4:2:2 chroma: 4:2:2 has no vertical subsampling; its cosited form is 'left'")
+    return SITINGS.index(siting) + 1
+
+
 def frame_bytes(h: int, w: int, depth: int = 8, chroma: str = "420") -> int:
     """Bytes of a frame in the given layout: a byte per sample at 8 bits, a 16-bit word at 10 and 12."""
     ch, cw = chroma_hw(h, w, chroma)
@@ -222,6 +265,40 @@ def replicate_chroma(p: np.ndarray, h: int, w: int, chroma: str = "420") -> np.n
     return np.repeat(np.repeat(p, 2, axis=1), 2, axis=2)[:, :h, :w]
 
 
+def _lerp_axis(c: np.ndarray, n: int, axis: int, cosited: bool) -> np.ndarray:
+    """Integer numerators over 4 of the linear interpolation along one subsampled axis, ceil(n / 2) samples -> n pixels, the edge samples
+    replicated.  Pixel 2 c: 3 C[c] + C[c - 1] (centre), 4 C[c] (cosited); pixel 2 c + 1: 3 C[c] + C[c + 1], 2 C[c] + 2 C[c + 1]."""
+    nc = c.shape[axis]
+    i = np.arange(n) // 2
+    odd = (np.arange(n) % 2).astype(bool)
+    cur = np.take(c, i, axis)
+    shape = [1] * c.ndim
+    shape[axis] = n
+    odd = odd.reshape(shape)
+    nxt = np.take(c, np.minimum(i + 1, nc - 1), axis)
+    if cosited:
+        return np.where(odd, 2 * cur + 2 * nxt, 4 * cur)
+    prv = np.take(c, np.maximum(i - 1, 0), axis)
+    return 3 * cur + np.where(odd, nxt, prv)
+
+
+def interpolate_chroma(plane: np.ndarray, h: int, w: int, chroma: str, siting: str) -> np.ndarray:
+    """A chroma plane [N, ch, cw] of integer samples -> float32 [N, h, w]: the chroma at every luma pixel under the siting (the module's
+    "Chroma siting"), an integer numerator times 2^-4 (4:2:0) or 2^-2 (4:2:2), exact.  4:4:4: the plane's own values."""
+    sid = check_siting(siting, chroma)
+    if sid == 0:
+        raise ValueError(f"siting = None models no siting: one of {', '.join(SITINGS)} (replicate_chroma is the nearest reading)")
+    p = np.asarray(plane).astype(np.int64)
+    if p.ndim != 3 or p.shape[1:] != chroma_hw(h, w, chroma):
+        raise ValueError(f"a {layout_name(chroma)} chroma plane of {h} x {w} is [N, {', '.join(str(v) for v in chroma_hw(h, w, chroma))}], got {tuple(p.shape)}")
+    if chroma == "444":
+        return p.astype(np.float32)
+    num = _lerp_axis(p, w, 2, siting != "centre")
+    if chroma == "422":
+        return num.astype(np.float32) * np.float32(0.25)
+    return _lerp_axis(num, h, 1, siting == "topleft").astype(np.float32) * np.float32(0.0625)
+
+
 def _full_planes(frames_u8: np.ndarray, h: int, w: int, depth: int, chroma: str) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """split_planes with both chroma planes replicated to [N, h, w]."""
     y, u, v = split_planes(frames_u8, h, w, depth, chroma)
@@ -244,10 +321,27 @@ def _i420_to_rgb_16(frames_u8: np.ndarray, h: int, w: int, colour: str, depth: i
     return _stack01(r, g, b)
 
 
-def i420_to_rgb(frames_u8: np.ndarray, h: int, w: int, colour: str = "bt601", depth: int = 8, chroma: str = "420") -> np.ndarray:
+def _i420_to_rgb_sited(frames_u8: np.ndarray, h: int, w: int, colour: str, depth: int, chroma: str, siting: str) -> np.ndarray:
+    """The coefficient arithmetic of _i420_to_rgb_16 at any depth on linearly interpolated chroma."""
+    c = to_rgb_coefficients(colour, depth)
+    top = (1 << depth) - 1
+    y, u, v = (np.minimum(p, top) for p in split_planes(frames_u8, h, w, depth, chroma))
+    y = y.astype(np.float32)
+    u, v = interpolate_chroma(u, h, w, chroma, siting), interpolate_chroma(v, h, w, chroma, siting)
+    yt = y * c["y"]
+    r = (yt + v * c["rv"]) + c["offset"][0]
+    g = ((yt + u * c["gu"]) + v * c["gv"]) + c["offset"][1]
+    b = (yt + u * c["bu"]) + c["offset"][2]
+    return _stack01(r, g, b)
+
+
+def i420_to_rgb(frames_u8: np.ndarray, h: int, w: int, colour: str = "bt601", depth: int = 8, chroma: str = "420", siting=None) -> np.ndarray:
     """[N, frame_bytes(h, w, depth, chroma)] uint8 -> float32 [N, 3, h, w] in [0, 1].  depth = 8:  R = y + rv,  G = (y + gu) + gv,
     B = y + bu  on the table values; 10 and 12: float32 arithmetic on the samples (the module's "High depth").  chroma: the layout
-    (the module's "Chroma layouts"); the default is I420."""
+    (the module's "Chroma layouts"); the default is I420.  siting: None (nearest replication, the lines above) or one of SITINGS: chroma
+    interpolated linearly at the siting's positions, then the coefficient arithmetic at every depth (the module's "Chroma siting")."""
+    if check_siting(siting, chroma) and chroma != "444":
+        return _i420_to_rgb_sited(frames_u8, h, w, colour, check_depth(depth), chroma, siting)
     if depth != 8:
         return _i420_to_rgb_16(frames_u8, h, w, colour, depth, chroma)
     y, u, v = _full_planes(frames_u8, h, w, 8, chroma)
@@ -300,25 +394,57 @@ def _block_mean(p: np.ndarray, chroma: str = "420") -> np.ndarray:
     return m
 
 
-def ycbcr_f32(x: np.ndarray, colour: str = "bt601", chroma: str = "420") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """The float32 values rgb_to_i420 rounds: Y [N, H, W], Cb and Cr [N, ch, cw], in 8-bit steps."""
+def _h3(l: np.ndarray, c: np.ndarray, r: np.ndarray) -> np.ndarray:
+    """[1 2 1] / 4 in float32: ((l + r) + (c + c)) * 0.25."""
+    return ((l + r) + (c + c)) * np.float32(0.25)
+
+
+def filter_chroma_rgb(p: np.ndarray, chroma: str = "420", siting=None) -> np.ndarray:
+    """The RGB a chroma sample is computed from, [N, 3, H, W] float32 (clamped) -> [N, 3, ch, cw]: `_block_mean` for None and "centre"
+    (the box is the centre-sited filter), [1 2 1] / 4 with clamped taps along every cosited axis (the module's "Chroma siting")."""
+    sid = check_siting(siting, chroma)
+    if chroma == "444" or sid < 2:
+        return _block_mean(p, chroma)
+    p = np.asarray(p)
+    if p.dtype != np.float32 or p.ndim != 4:
+        raise ValueError(f"RGB frames are [N, 3, H, W] float32, got {p.dtype} {tuple(p.shape)}")
+    H, W = p.shape[2:]
+    ch, cw = chroma_hw(H, W, chroma)
+    xs = 2 * np.arange(cw)
+    hr = _h3(p[:, :, :, np.maximum(xs - 1, 0)], p[:, :, :, xs], p[:, :, :, np.minimum(xs + 1, W - 1)])          # Hrow of every row
+    if chroma == "422":
+        return hr
+    ys = 2 * np.arange(ch)
+    if siting == "topleft":
+        return _h3(hr[:, :, np.maximum(ys - 1, 0)], hr[:, :, ys], hr[:, :, np.minimum(ys + 1, H - 1)])
+    m = np.empty(hr.shape[:2] + (ch, cw), np.float32)
+    m[:, :, :H // 2] = (hr[:, :, 0:H // 2 * 2:2] + hr[:, :, 1:H // 2 * 2:2]) * np.float32(0.5)
+    if H % 2:
+        m[:, :, -1] = hr[:, :, H - 1]
+    return m
+
+
+def ycbcr_f32(x: np.ndarray, colour: str = "bt601", chroma: str = "420", siting=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The float32 values rgb_to_i420 rounds: Y [N, H, W], Cb and Cr [N, ch, cw], in 8-bit steps.  siting: where the chroma samples lie
+    (filter_chroma_rgb); None and "centre" are the block mean."""
     check_chroma(chroma)
     p = _clamp01(x)
     t = matrix(colour)["to_ycbcr"]
-    m = _block_mean(p, chroma)
+    m = filter_chroma_rgb(p, chroma, siting)
     return _row(p, t["y"], t["offset"][0]), _row(m, t["cb"], t["offset"][1]), _row(m, t["cr"], t["offset"][2])
 
 
-def rgb_to_i420(x_f32: np.ndarray, colour: str = "bt601", depth: int = 8, chroma: str = "420") -> np.ndarray:
+def rgb_to_i420(x_f32: np.ndarray, colour: str = "bt601", depth: int = 8, chroma: str = "420", siting=None) -> np.ndarray:
     """float32 [N, 3, H, W] -> uint8 [N, frame_bytes(H, W, depth, chroma)].  Limited range: after the clamp Y lies in 16 .. 235 and
     chroma in 16 .. 240, no clip.  Full range: chroma reaches 255.5, which rounds to 256, so the rounded values are clipped to 0 .. 255.
     depth = 10, 12 (limited range only): rint(ycbcr_f32 * 2^(depth - 8)), written as little-endian 16-bit samples.  chroma: the layout
-    (the module's "Chroma layouts"); the default is I420."""
+    (the module's "Chroma layouts"); the default is I420.  siting: where the chroma samples lie (the module's "Chroma siting"); None and
+    "centre" are the block mean."""
     if depth != 8:
         k = np.float32(1 << (check_depth_colour(depth, colour) - 8))
-        planes = [np.rint(v * k) for v in ycbcr_f32(x_f32, colour, chroma)]
+        planes = [np.rint(v * k) for v in ycbcr_f32(x_f32, colour, chroma, siting)]
     else:
-        planes = [np.rint(v) for v in ycbcr_f32(x_f32, colour, chroma)]
+        planes = [np.rint(v) for v in ycbcr_f32(x_f32, colour, chroma, siting)]
         if is_full_range(colour):
             planes = [np.fmin(np.fmax(v, np.float32(0.0)), np.float32(255.0)) for v in planes]
     n = planes[0].shape[0]

@@ -15,6 +15,13 @@ fails, times out or dies ends the run (nothing more is started on the GPU) and w
             out) / time.  The layouts move different bytes per pixel, so the GB/s are compared, not the times; the 4:2:0 kernels are
             timed twice in every round and the spread between their two readings is the margin (`margin_gbs`).  No time is fixed in
             advance.  `--legs chroma --out profiles/bench_y4m_chroma.json`
+  siting    savsr_video_gather_yuvs / _quantize_yuvs (linear chroma reconstruction in, cosited filters out) at every siting of 4:2:0 and
+            4:2:2 beside that layout's nearest / box kernel (siting 0 of the same entries), at 8 and 10 bits, 720x1280, 7 frames, in one
+            process, interleaved rounds: us, bytes in and out, GB/s.  The nearest kernel is timed twice in every round and the spread
+            between its two readings is the margin.  The same leg computes on the CPU, from yuv.py alone, what the feature is worth on a
+            synthetic picture (`value_psnr`): smooth seeded fields plus chroma edges, subsampled by a float64 left-cosited [1 2 1] / 4,
+            reconstructed by today's nearest reading and by siting="left"; PSNR of the reconstructed chroma.  Synthetic: no real footage.
+            `--legs siting --out profiles/bench_y4m_siting.json`
   ceiling   upscale_video on preloaded I420 frames, I420 out (frames/s): what the CLI could reach
   cli       python -m savsr_amd.upscale on one synthetic video, PNG folder -> PNG folder against .y4m -> .y4m, A/B/A/B; files under
             --workdir (name the disk it lies on beside the figures: tmpfs or a scratch disk)
@@ -37,7 +44,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_BYTES_PER_S = 8e12
-LEG_TIMEOUT_S = {"kernels": 240, "depth": 240, "chroma": 240, "ceiling": 420, "cli": 420, "psnr": 420}
+LEG_TIMEOUT_S = {"kernels": 240, "depth": 240, "chroma": 240, "siting": 300, "ceiling": 420, "cli": 420, "psnr": 420}
 
 
 def _net(dev):
@@ -216,6 +223,104 @@ def leg_chroma(a):
             "timing": "HIP events around `iters` back-to-back launches (launch rate included)"}
 
 
+def siting_value_psnr(h=360, w=640, seed=11):
+    """On the CPU, from yuv.py alone: full-resolution chroma (smooth seeded fields plus vertical, horizontal and diagonal edges), subsampled
+    to 4:2:0 as an MPEG-2 / H.264 encoder's input is -- float64 [1 2 1] / 4 at x = 2 cx (left-cosited), the mean of rows 2 cy, 2 cy + 1 --
+    and rounded to 8 bits; then reconstructed by nearest replication (siting=None) and by siting="left".  PSNR of the two reconstructions
+    against the full-resolution planes, peak 255."""
+    import numpy as np
+    from savsr_amd import yuv
+    rng = np.random.RandomState(seed)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    planes = []
+    for _ in range(2):
+        f = np.full((h, w), 128.0)
+        for _ in range(6):                              # smooth fields
+            fy, fx, ph, amp = rng.uniform(0.5, 6) / h, rng.uniform(0.5, 6) / w, rng.uniform(0, 2 * np.pi), rng.uniform(4, 14)
+            f += amp * np.sin(2 * np.pi * (fy * yy + fx * xx) + ph)
+        for _ in range(10):                             # chroma edges: half planes at random angles
+            ang, off, step = rng.uniform(0, np.pi), rng.uniform(0.2, 0.8), rng.uniform(-45, 45)
+            f += step * ((np.cos(ang) * xx / w + np.sin(ang) * yy / h) > off * (abs(np.cos(ang)) + abs(np.sin(ang))))
+        planes.append(np.clip(f, 16, 240))
+    ch, cw = yuv.chroma_hw(h, w)
+    xs, ys = 2 * np.arange(cw), 2 * np.arange(ch)
+
+    def down(p):
+        hr = (p[:, np.maximum(xs - 1, 0)] + 2 * p[:, xs] + p[:, np.minimum(xs + 1, w - 1)]) / 4.0
+        return np.rint((hr[ys] + hr[np.minimum(ys + 1, h - 1)]) / 2.0).astype(np.uint8)
+
+    def psnr(rec):
+        mse = np.mean([(r.astype(np.float64) - p) ** 2 for r, p in zip(rec, planes)])
+        return round(float(10 * np.log10(255.0 ** 2 / mse)), 2)
+    sub = [down(p)[None] for p in planes]
+    near = psnr([yuv.replicate_chroma(c, h, w)[0] for c in sub])
+    out = {"size": [h, w], "seed": seed, "nearest_db": near}
+    for siting in yuv.SITINGS:
+        out[f"{siting}_db"] = psnr([yuv.interpolate_chroma(c, h, w, "420", siting)[0] for c in sub])
+    out["left_minus_nearest_db"] = round(out["left_db"] - near, 2)
+    out["note"] = "synthetic picture, chroma planes only, 8-bit 4:2:0 subsampled left-cosited; no real footage"
+    return out
+
+
+def leg_siting(a):
+    import ctypes as C
+    import torch
+    from savsr_amd import _lib
+    from savsr_amd.yuv import CHROMAS, SITINGS, frame_bytes
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    h, w, n = 720, 1280, 16
+    arr = (C.c_int32 * 7)(*range(7))
+    slots = torch.empty(7, 3, h, w, device=dev)
+    x = torch.rand(7, 3, h, w, device=dev)
+    fns, nbytes = {}, {}
+    keep = []                                       # (the buffers the closures below read and write)
+    for depth in (8, 10):
+        for cid, chroma in enumerate(CHROMAS[:2]):
+            fb = frame_bytes(h, w, depth, chroma)
+            src = torch.randint(0, 256 if depth == 8 else 4, (n, fb), dtype=torch.uint8, device=dev)      # (in-range samples at either depth)
+            dst = torch.empty(7, fb, dtype=torch.uint8, device=dev)
+            keep += [src, dst]
+            sitings = [(i + 1, s) for i, s in enumerate(SITINGS) if not (chroma == "422" and s == "topleft")]
+            # the yardstick (siting 0: the nearest / box kernel) first and last in every round; quantiser siting 1 is the box kernel itself
+            for sid, tag in [(0, "nearest (a)")] + sitings + [(0, "nearest (b)")]:
+                name = f"{chroma} {depth}-bit {tag}"
+                fns[f"gather {name}"] = lambda s_=src, d=depth, c=cid, i=sid: lib.savsr_video_gather_yuvs(s_.data_ptr(), n, h, w, arr, 7, 1, d, c, i,
+                                                                                                          slots.data_ptr(), st)
+                nbytes[f"gather {name}"] = (7 * fb, 7 * 12 * h * w)
+                if sid != 1:
+                    fns[f"quantize {name}"] = lambda o=dst, d=depth, c=cid, i=sid: lib.savsr_video_quantize_yuvs(x.data_ptr(), 7, h, w, 1, d, c, i,
+                                                                                                                o.data_ptr(), st)
+                    nbytes[f"quantize {name}"] = (7 * 12 * h * w, 7 * fb)
+    us = {k: [] for k in fns}
+    for k, fn in fns.items():
+        assert fn() == 0, k
+    torch.cuda.synchronize()
+    for _ in range(a.rounds):                           # interleaved rounds: every kernel sees the same clocks
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us[k].append(1e3 * e0.elapsed_time(e1) / a.iters)
+    med = {k: statistics.median(v) for k, v in us.items()}
+    gbs = {k: sum(nbytes[k]) / (med[k] * 1e-6) / 1e9 for k in fns}
+    rows = []
+    for k in fns:
+        side, chroma, depth = k.split()[:3]
+        ya, yb = gbs[f"{side} {chroma} {depth} nearest (a)"], gbs[f"{side} {chroma} {depth} nearest (b)"]
+        rows.append({"kernel": k, "size": [h, w], "frames": 7, "us": round(med[k], 2), "bytes_in": nbytes[k][0], "bytes_out": nbytes[k][1],
+                     "gbs": round(gbs[k], 1), "gbs_nearest": round(min(ya, yb), 1), "margin_gbs": round(abs(ya - yb), 1),
+                     "below_nearest_pct": round(100.0 * (1.0 - gbs[k] / min(ya, yb)), 1),
+                     "below_nearest_by_more_than_the_margin": bool(gbs[k] < min(ya, yb) - abs(ya - yb)),
+                     "us_rounds": [round(v, 2) for v in us[k]]})
+    return {"kernels": rows, "rounds": a.rounds, "iters": a.iters, "colour": "bt709", "value_psnr": siting_value_psnr(),
+            "timing": "HIP events around `iters` back-to-back launches (launch rate included)"}
+
+
 def leg_ceiling(a):
     import torch
     dev = torch.device("cuda:0")
@@ -297,7 +402,7 @@ def leg_psnr(a):
                        "note": "against the float result in float64; synthetic weights"}}
 
 
-LEGS = {"kernels": leg_kernels, "depth": leg_depth, "chroma": leg_chroma, "ceiling": leg_ceiling, "cli": leg_cli, "psnr": leg_psnr}
+LEGS = {"kernels": leg_kernels, "depth": leg_depth, "chroma": leg_chroma, "siting": leg_siting, "ceiling": leg_ceiling, "cli": leg_cli, "psnr": leg_psnr}
 
 
 def main():
