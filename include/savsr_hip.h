@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 40
+#define SAVSR_ABI_VERSION 41
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -570,6 +570,43 @@ int savsr_video_pair_sad_yuvp(const uint8_t* frames, int n_frames, int h, int w,
 int savsr_video_gather_yuvs(const uint8_t* frames, int n_frames, int h, int w, const int32_t* idx, int n_idx, int colour, int depth, int chroma,
                             int siting, float* out, void* stream);
 int savsr_video_quantize_yuvs(const float* in, int n, int H, int W, int colour, int depth, int chroma, int siting, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 41) Luma-only checkpoints (num_in_ch = 1) on planar YUV and grey-scale video (luma.hip; chroma_filter = "bicubic" and
+ * pixel_format / out = "y400" of SAVSR.upscale_video, --chroma-filter of python -m savsr_amd.upscale).  The Y plane
+ * goes through the network; Cb / Cr go from samples to samples through a separable, siting-aware cubic at the network's scale.  Samples
+ * are bytes at depth 8 and little-endian 16-bit words at 10 / 12 (a sample above 2^depth - 1 reads as 2^depth - 1); frame pointers stay
+ * byte pointers.  All float32 with a fixed operation order and no fused multiply-add: savsr_amd/yuv.py (`luma_to_unit`, `unit_to_luma`,
+ * `chroma_axis_table`, `resample_chroma`) restates the three bit for bit.  They only enqueue, allocate nothing and are capturable.
+ * Refused before the device is touched, with savsr_last_error() naming the reason: SAVSR_E_ARG for a null pointer, a size below 1, a
+ * depth other than 8 / 10 / 12, a frame stride smaller than the plane, a plane that does not lie inside its frame, a bad index list;
+ * SAVSR_E_ALIGN for 16-bit samples behind an odd pointer, frame stride or plane offset.
+ * savsr_video_gather_luma:   the Y plane (the first h * w samples) of frames `frame_bytes` bytes apart -> out [n_idx][1][h][w] fp32, slot
+ *                         k = float(min(s, 2^depth - 1)) / float(255 * 2^(depth - 8)) of frame idx[k] (the index list of
+ *                         savsr_video_gather_u8): one IEEE division, savsr_video_gather_u8's value at depth 8; the same rule whatever
+ *                         the colour space.  4 samples per access / one 16-byte store when w % 4 == 0, frames and frame_bytes 4-byte
+ *                         (8-byte at depth 10 / 12) and out 16-byte aligned; a sample per access otherwise.
+ * savsr_video_quantize_luma: in [n][1][H][W] fp32 contiguous -> the Y plane of n frames `out_frame_bytes` bytes apart:
+ *                         rintf(clamp(v, 0, 1) * (255 * 2^(depth - 8))), half to even, NaN -> 0; savsr_video_quantize_u8's rule at depth
+ *                         8.  The vector form under the same conditions, the input loaded nontemporally.
+ * savsr_video_resample_chroma: one plane of n frames: ch x cw samples at src + f * src_frame_bytes + src_plane_offset -> cH x cW samples
+ *                         at dst + f * dst_frame_bytes + dst_plane_offset.  ymin / ysize / wy[cH][taps_y] and xmin / xsize /
+ *                         wx[cW][taps_x]: DEVICE arrays, the per-output windows and float32 weights of the two axes as for
+ *                         savsr_resize_aa_axis (savsr_amd/yuv.py `chroma_axis_table`).  Samples clipped to 2^depth_in - 1; width first
+ *                         (acc + w * s in tap order), then height over the filtered rows, x 2^(depth_out - depth_in), rintf, clipped
+ *                         to 0 .. 2^depth_out - 1.  Both axes in one launch: a workgroup owns 16 x 64 output samples and stages the
+ *                         filtered input rows they need in LDS, 32 rows (8 KiB) at a time; a tile that needs more rows loops, so any
+ *                         taps_y is served.  Table indices are clamped into the plane: no table causes an access outside it.  A
+ *                         window that runs past the plane (no table of chroma_axis_table does) re-reads the last column on the
+ *                         horizontal axis and drops the taps beyond the last row on the vertical one.  4 samples per store when cW % 4 == 0 and dst,
+ *                         its stride and offset are 4-byte (8-byte at depth 10 / 12) aligned. */
+int savsr_video_gather_luma(const uint8_t* frames, int n_frames, int64_t frame_bytes, int h, int w, int depth, const int32_t* idx, int n_idx,
+                            float* out, void* stream);
+int savsr_video_quantize_luma(const float* in, int n, int H, int W, int depth, uint8_t* out, int64_t out_frame_bytes, void* stream);
+int savsr_video_resample_chroma(const uint8_t* src, int n, int64_t src_frame_bytes, int64_t src_plane_offset, int ch, int cw, int depth_in,
+                                uint8_t* dst, int64_t dst_frame_bytes, int64_t dst_plane_offset, int cH, int cW, int depth_out,
+                                const int32_t* ymin, const int32_t* ysize, const float* wy, int taps_y, const int32_t* xmin,
+                                const int32_t* xsize, const float* wx, int taps_x, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 33) Geometric self-ensemble (ensemble.hip; SAVSR.set_self_ensemble).  Variant k = 0 .. 7: fw = k & 1 flips

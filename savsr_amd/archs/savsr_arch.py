@@ -279,7 +279,8 @@ class SAVSR(nn.Module):
 
     def upscale_video(self, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
                       size=None, cuts=None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None, depth: int = 8,
-                      out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None) -> torch.Tensor:
+                      out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
+                      chroma_filter: Optional[str] = None) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -308,6 +309,14 @@ class SAVSR(nn.Module):
         the nearest sample, as ever.  out_siting: that of YUV output; "left" / "topleft" filter cosited axes with [1 2 1] / 4, None and
         "centre" take the block mean.  The two are independent; siting goes with a YUV pixel_format and out_siting with a YUV out, and
         4:4:4 has nothing to resample (any siting gives the bytes of None).
+        chroma_filter: None or "bicubic", for a luma-only checkpoint (num_in_ch = 1) on YUV video: pixel_format and out in "i420" / "i422" /
+        "i444" are then accepted; the Y plane goes through the network (Y / 255 of the codes at 8 bits, the extra bits kept at 10 / 12,
+        whatever the colour space: it is not converted, so out_colour must equal colour) and every output frame's U and V are resampled
+        from its own input frame at the network's scale by a siting-aware Keys bicubic, samples to samples (savsr_amd/yuv.py
+        "Luma-only checkpoints"); depth, out_depth, the out layout, siting and out_siting apply.  out="float" / "uint8" return the luma
+        alone ([N, 1, H, W] / [N, H, W, 1]).  pixel_format / out = "y400": grey-scale frames, the Y plane alone (Y4M's Cmono), of
+        yuv.frame_bytes(h, w, depth, "400") bytes, for num_in_ch = 1 only and without chroma_filter; YUV in, "y400" out drops the chroma,
+        "y400" in, a chroma layout out is refused.  None (the default) runs what ran before the argument existed.
         cuts: None (one scene), a strictly increasing list of frame indices 0 < k < N (frame k starts a new scene), or "auto" (found on
         the GPU: savsr_amd.detect_cuts with scene_threshold, in per cent of the largest possible frame change; the default is ffmpeg
         scdet's and is not validated on real footage).  Windows stop at cuts: the result is, bit for bit, upscale_video on every scene
@@ -316,7 +325,7 @@ class SAVSR(nn.Module):
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
         return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold, colour, out_colour, depth, out_depth,
-                             siting, out_siting)
+                             siting, out_siting, chroma_filter)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

@@ -25,6 +25,7 @@ import weakref
 from contextlib import contextmanager
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -135,6 +136,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         # third (config 5: 329 clips/s with 3 streams, 311 with 2)
         self.n_streams_large, self.streams_large_px = kn.streams_large, kn.streams_large_px
         self._siblings: List["HipEngine"] = []
+        self._luma_tables: Dict[tuple, tuple] = {}      # chroma resampler tables on the device (`_chroma_tables`)
         self._streams: List[torch.cuda.Stream] = []
         self._pack_all({k: v.detach() for k, v in state.items()})
 
@@ -904,6 +906,121 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         # (SAVSR_GRAPHS=0: forward_many's eager flow, one window per unit)
         self._fan_out(video_units(n, T, self.clip_unit(h, w) if self.use_graphs else 1), h * w, run)
         return out
+
+    def _chroma_tables(self, h: int, w: int, H: int, W: int, lay: str, out_lay: str, siting: Optional[str], out_siting: Optional[str]):
+        """yuv.chroma_tables on the device, cached per (h, w, H, W, layouts, sitings): ((ymin, ysize, wy, taps_y), (xmin, xsize, wx, taps_x)).
+        One entry per distinct key, a few KB each, kept for the engine's life: a video has one key; a caller that streams many distinct
+        shapes through one engine grows it by that much."""
+        key = (h, w, H, W, lay, out_lay, siting, out_siting)
+        t = self._luma_tables.get(key)
+        if t is None:
+            from .yuv import chroma_tables
+            t = tuple((torch.from_numpy(a).to(self.dev), torch.from_numpy(b).to(self.dev), torch.from_numpy(np.ascontiguousarray(c)).to(self.dev),
+                       int(c.shape[1])) for a, b, c in chroma_tables(h, w, H, W, lay, out_lay, siting, out_siting))
+            self._luma_tables[key] = t
+        return t
+
+    def forward_video_luma(self, frames: torch.Tensor, windows: List[List[int]], scale, size: Tuple[int, int], out: str = "float",
+                           ensemble: bool = False, depth: int = 8, out_depth: int = 8, chroma: str = "420", out_chroma: str = "420",
+                           siting: Optional[str] = None, out_siting: Optional[str] = None) -> torch.Tensor:
+        """The sequence path of a luma-only network (num_in_ch = 1) on planar YUV or grey-scale frames (upscale_video with
+        chroma_filter="bicubic" or pixel_format="y400"; savsr_amd/yuv.py "Luma-only checkpoints" is the specification).  frames
+        [N, frame_bytes(h, w, depth, chroma)] uint8 on the device, chroma one of yuv.CHROMAS or yuv.MONO; windows as for forward_video.
+        The Y planes of a unit's windows are gathered by savsr_video_gather_luma where forward_video's gather runs (the unit's stream; the
+        same units, clip_batch, flow and graphs) and the network's fp32 result is quantised into the Y plane of the output frames by
+        savsr_video_quantize_luma.  out: "float" -> [n, 1, H, W] fp32 and "uint8" -> [n, H, W, 1] uint8, the luma alone; "yuv" ->
+        [n, frame_bytes(H, W, out_depth, out_chroma)] uint8, whose U and V planes are resampled from the window's centre frame -- the
+        output frame's own input frame -- by savsr_video_resample_chroma on the caller's stream (out_chroma = yuv.MONO: no chroma planes).
+        ensemble=True: the Y planes are converted once to fp32 (the same gather with the identity list) and take `_ensemble`'s fp32 path;
+        chroma never enters the ensemble."""
+        from .yuv import MONO
+        if self.nch != 1:
+            raise ValueError(f"the luma path serves num_in_ch = 1 networks, this one has num_in_ch = {self.nch}")
+        if out not in ("float", "uint8", "yuv"):
+            raise ValueError(f"out = {out!r}: 'float', 'uint8' or 'yuv'")
+        for what, d in (("depth", depth), ("out_depth", out_depth)):
+            if d not in (8, 10, 12):
+                raise ValueError(f"{what} = {d!r}: 8, 10 or 12")
+        for what, lay_ in (("chroma", chroma), ("out_chroma", out_chroma)):
+            if lay_ != MONO and lay_ not in CHROMAS:
+                raise ValueError(f"{what} = {lay_!r}: one of {', '.join(CHROMAS)} or {MONO}")
+        if out == "yuv" and chroma == MONO and out_chroma != MONO:
+            raise ValueError("grey-scale frames have no chroma planes to resample")
+        h, w = (int(v) for v in size)
+        fb = frame_bytes(h, w, depth, chroma)
+        if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != fb:
+            raise ValueError(f"frames of {h} x {w} are [N, {fb}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+        frames = self._input(frames, torch.uint8)
+        N, T = int(frames.shape[0]), self.cfg["num_frame"]
+        for win in windows:
+            if len(win) != T or min(win) < 0 or max(win) >= N:
+                raise ValueError(f"window {win}: {T} indices in [0, {N}) expected")
+        H, W = get_hw(h, w, scale)
+        n = len(windows)
+        if out == "yuv":
+            ofb, od = frame_bytes(H, W, out_depth, out_chroma), out_depth
+            res = torch.empty(n, ofb, device=self.dev, dtype=torch.uint8)
+        elif out == "uint8":
+            ofb, od = H * W, 8
+            res = torch.empty(n, H, W, 1, device=self.dev, dtype=torch.uint8)
+        else:
+            res = torch.empty(n, 1, H, W, device=self.dev, dtype=torch.float32)
+        if n == 0:
+            return res
+        if T > _lib.VIDEO_MAX_SLOTS:
+            raise ValueError(f"num_frame = {T}: the window gather takes at most {_lib.VIDEO_MAX_SLOTS} frames per launch")
+
+        def gather(idx, dst, st):
+            _lib.check(self.lib.savsr_video_gather_luma(frames.data_ptr(), N, fb, h, w, depth, (_lib.C.c_int32 * len(idx))(*idx), len(idx),
+                                                        dst.data_ptr(), st), "savsr_video_gather_luma")
+
+        def quantize(src, dst, st):
+            for a in range(0, int(src.shape[0]), 65535):          # (the entry takes 1 .. 65535 frames)
+                nb = min(65535, int(src.shape[0]) - a)
+                _lib.check(self.lib.savsr_video_quantize_luma(src[a:a + nb].data_ptr(), nb, H, W, od, dst[a:a + nb].data_ptr(), ofb, st),
+                           "savsr_video_quantize_luma")
+        if out == "yuv" and out_chroma != MONO:
+            # U and V of output frame i from its own input frame, the window's centre: runs of consecutive centres share a launch
+            (ym, ys, wy, ty), (xm, xs, wx, tx) = self._chroma_tables(h, w, H, W, chroma, out_chroma, siting, out_siting)
+            from .yuv import chroma_hw
+            (ch, cw), (cH, cW) = chroma_hw(h, w, chroma), chroma_hw(H, W, out_chroma)
+            si, so = (1 if depth == 8 else 2), (1 if out_depth == 8 else 2)
+            st = torch.cuda.current_stream().cuda_stream
+            centres = [win[T // 2] for win in windows]
+            a = 0
+            while a < n:
+                b = a + 1
+                while b < n and centres[b] == centres[b - 1] + 1 and b - a < 65535:
+                    b += 1
+                for plane in range(2):
+                    _lib.check(self.lib.savsr_video_resample_chroma(
+                        frames[centres[a]:].data_ptr(), b - a, fb, (h * w + plane * ch * cw) * si, ch, cw, depth, res[a:].data_ptr(), ofb,
+                        (H * W + plane * cH * cW) * so, cH, cW, out_depth, ym.data_ptr(), ys.data_ptr(), wy.data_ptr(), ty, xm.data_ptr(),
+                        xs.data_ptr(), wx.data_ptr(), tx, st), "savsr_video_resample_chroma")
+                a = b
+        if ensemble:
+            st = torch.cuda.current_stream().cuda_stream
+            luma = torch.empty(N, 1, h, w, device=self.dev, dtype=torch.float32)
+            for a in range(0, N, _lib.VIDEO_MAX_SLOTS):
+                gather(list(range(a, min(N, a + _lib.VIDEO_MAX_SLOTS))), luma[a:], st)
+            merged = res if out == "float" else torch.empty(n, 1, H, W, device=self.dev, dtype=torch.float32)
+            self._ensemble([(luma, win, tuple(scale), merged[i]) for i, win in enumerate(windows)], False)
+            if out != "float":
+                quantize(merged, res, st)
+            return res
+
+        def run(eng: "HipEngine", unit: Tuple[int, int]):
+            i0, i1 = unit
+            nb = i1 - i0
+            st = torch.cuda.current_stream().cuda_stream
+            lqb = torch.empty(nb, T, 1, h, w, device=self.dev, dtype=torch.float32)
+            gather([f for win in windows[i0:i1] for f in win], lqb, st)
+            o = res[i0:i1] if out == "float" else torch.empty(nb, 1, H, W, device=self.dev, dtype=torch.float32)
+            eng._run_unit(lqb, scale, o)
+            if out != "float":
+                quantize(o, res[i0:i1], st)
+        self._fan_out(video_units(n, T, self.clip_unit(h, w) if self.use_graphs else 1), h * w, run)
+        return res
 
     def forward(self, lq: torch.Tensor, scale, taps: Optional[dict] = None, ensemble: bool = False) -> torch.Tensor:
         """lq: [b, T, c, h, w] -> [b, c, H, W], c = num_in_ch (savsr_arch.py:692-742).  ensemble=True: every clip is the self-ensemble of its

@@ -24,7 +24,7 @@ import numpy as np
 
 from .harness import window_indices
 from .video import check_length, check_padding, check_pixel_format, chroma_of
-from .yuv import check_depth, frame_bytes, layout_name, split_planes
+from .yuv import LUMA_FORMAT, MONO, check_depth, frame_bytes, layout_name, luma_plane, split_planes
 
 
 # ---- the detector --------------------------------------------------------------------------------------------------------------------
@@ -40,6 +40,9 @@ def _samples_of(frames, pixel_format: str, size, depth: int = 8) -> np.ndarray:
     if hasattr(frames, "detach"):
         frames = frames.detach().cpu().numpy()
     frames = np.asarray(frames)
+    if i420 and pixel_format == LUMA_FORMAT:          # grey-scale frames: the Y plane is the frame
+        y = luma_plane(frames, i420[0], i420[1], check_depth(depth), MONO)
+        return (np.minimum(y, (1 << depth) - 1) >> (depth - 8)).astype(np.uint8).reshape(y.shape[0], -1)
     if depth != 8:
         depth = check_depth(depth)
         if not i420:

@@ -9,6 +9,7 @@
     python -m savsr_amd.upscale -i sd.y4m -o hd.y4m --scale 4 --checkpoint <net.pth> --colour auto --out-colour auto
     python -m savsr_amd.upscale -i in8.y4m -o out10.y4m --scale 4 --checkpoint <net.pth> --out-depth 10
     ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o - --scale 4 --checkpoint <net.pth> --siting auto --out-siting same | ffmpeg -i - out.mp4
+    python -m savsr_amd.upscale -i in.y4m -o out.y4m --scale 4 --opt <luma_test.yml> --chroma-filter bicubic
     ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out444p10.y4m --scale 4 --checkpoint <net.pth> --out-chroma 444
 
 PNG folder: frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on
@@ -46,6 +47,11 @@ independent: 4:2:0 in, --out-chroma 444 writes the network's full-resolution chr
 wrote.  --siting auto takes what the input's C tag names (none for a plain C420, a missing tag, C422, C444 and the p10 / p12 tags) and
 says on stderr what it resolved to; --out-siting same is whatever the input side resolved to.  An 8-bit 4:2:0 output is tagged
 C420mpeg2 / C420paldv for left / topleft and C420jpeg otherwise.
+
+--chroma-filter bicubic: a luma-only checkpoint (num_in_ch = 1, from --opt) on a Y4M input: the Y plane goes through the network and
+Cb / Cr are resampled from each frame's own chroma planes at the network's scale by a siting-aware bicubic (savsr_amd/yuv.py "Luma-only
+checkpoints"); --out-depth, --out-chroma, --siting and --out-siting apply, the colour space is kept.  The default, none, is what this tool
+has always done.  A grey-scale input (Cmono, Cmono10, Cmono12) needs such a checkpoint and no filter, and is written as grey-scale.
 
 --cuts: edited footage.  Windows stop at scene cuts (every scene is upscaled as a video of its own, savsr_amd/scenes.py): auto finds
 them on the GPU as the frames arrive (--scene-threshold, per cent of the largest possible frame change; ffmpeg scdet's rule and default,
@@ -159,6 +165,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--out-siting", default=None, choices=["none", "same"] + list(SITINGS),
                    help="chroma siting of a 4:2:0 / 4:2:2 Y4M output (default none: block mean).  same: what the input side resolved to; "
                         "left / topleft filter cosited axes with [1 2 1] / 4 and tag an 8-bit 4:2:0 output C420mpeg2 / C420paldv")
+    p.add_argument("--chroma-filter", default="none", choices=["none", "bicubic"],
+                   help="luma-only checkpoints (num_in_ch = 1) on Y4M video: bicubic resamples Cb / Cr from the input's chroma planes at the "
+                        "network's scale while Y goes through the network (default none)")
     p.add_argument("--cuts", default=None, metavar="auto|K,K,...|@FILE",
                    help="scene cuts (first frame of every new scene): auto = found on the GPU, a comma-separated list, or @FILE with one index "
                         "per line; windows stop at cuts")
@@ -226,6 +235,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--siting goes with a Y4M input (PNG frames are RGB)")
     if a.out_siting is not None and not a.y4m_out:
         p.error("--out-siting goes with a Y4M output (PNG frames are RGB)")
+    a.chroma_filter = None if a.chroma_filter == "none" else a.chroma_filter
+    if a.chroma_filter is not None and not (a.y4m_in and a.y4m_out):
+        p.error("--chroma-filter goes with a Y4M input and a Y4M output (the chroma planes come from the one and go to the other)")
     a.siting = a.siting or "none"
     a.out_siting = a.out_siting or "none"
     a.out_depth = None if a.out_depth in (None, "same") else int(a.out_depth)          # (None: the input's)
@@ -266,6 +278,10 @@ def load_net(a: argparse.Namespace):
     else:
         net = SAVSR()
         sio.load_network(net, a.checkpoint, True, "params")
+    if net.cfg["num_in_ch"] == 1 and a.y4m_in and a.y4m_out:
+        return net.eval()          # (a luma-only checkpoint: main() asks for --chroma-filter or a grey-scale input once the header is read)
+    if a.chroma_filter is not None:
+        raise SystemExit(f"--chroma-filter = {a.chroma_filter!r} with num_in_ch = {net.cfg['num_in_ch']}: chroma goes through such a network")
     if net.cfg["num_in_ch"] != 3:
         raise SystemExit(f"num_in_ch = {net.cfg['num_in_ch']}: the CLI decodes RGB frames; run such a checkpoint through SAVSR.upscale_video")
     return net.eval()
@@ -370,7 +386,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     from .utils.host import effective_cpus
     from .video import VideoUpscaler, check_length
     from .y4m import Y4MReader, Y4MWriter, scaled_aspect
-    from .yuv import CHROMAS, FORMAT_OF, is_full_range
+    from .yuv import CHROMAS, FORMAT_OF, LUMA_FORMAT, MONO, is_full_range
 
     net = load_net(a)
     net.set_precision(a.precision)
@@ -386,8 +402,16 @@ def main(argv: Optional[List[str]] = None) -> int:
             if a.input != "-" and not os.path.isfile(a.input):
                 raise SystemExit(f"input file {a.input!r} does not exist")
             fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
-            reader = Y4MReader(fin, high_depth=True, layouts=CHROMAS)
+            reader = Y4MReader(fin, high_depth=True, layouts=CHROMAS, mono=True)
             h, w, depth, chroma = reader.height, reader.width, reader.depth, reader.chroma
+            nch = net.cfg["num_in_ch"]
+            if chroma == MONO and nch != 1:
+                raise SystemExit(f"the input is grey-scale (C{reader.colorspace}): it needs a luma-only checkpoint (num_in_ch = 1), this one has "
+                                 f"num_in_ch = {nch}")
+            if chroma == MONO and a.out_chroma is not None:
+                raise SystemExit(f"--out-chroma = {a.out_chroma!r} with a grey-scale input: it has no chroma planes; the output is grey-scale")
+            if nch == 1 and chroma != MONO and a.chroma_filter is None:
+                raise SystemExit("num_in_ch = 1 with a colour Y4M input: give --chroma-filter bicubic (Y through the network, Cb / Cr resampled)")
             fps, interlace, aspect, in_range = reader.fps, reader.interlace, reader.aspect, reader.colour_range
             tag_siting = reader.siting
             chunks = (torch.from_numpy(c) for c in reader.chunks(a.chunk))
@@ -413,14 +437,16 @@ def main(argv: Optional[List[str]] = None) -> int:
         colour, out_colour = resolve_colours(a.colour, a.out_colour, (h, w) if a.y4m_in else None, hr, in_range)
         out_depth = (depth if a.out_depth is None else a.out_depth) if a.y4m_out else None
         out_chroma = (chroma if a.out_chroma is None else a.out_chroma) if a.y4m_out else None
-        fmt_in, fmt_out = FORMAT_OF[chroma] if a.y4m_in else "rgb", FORMAT_OF[out_chroma] if a.y4m_out else "uint8"
+        fmt_of = dict(FORMAT_OF, **{MONO: LUMA_FORMAT})
+        fmt_in, fmt_out = fmt_of[chroma] if a.y4m_in else "rgb", fmt_of[out_chroma] if a.y4m_out else "uint8"
         from .video import check_depths
         try:                                        # (before the output is opened: a full-range colour with 10 / 12 bits is refused)
             check_depths(depth, out_depth, fmt_in, fmt_out, colour or "bt601", out_colour)
         except ValueError as e:
             raise SystemExit(f"--colour / --out-colour / --out-depth: {e}") from None
         try:
-            siting, out_siting = resolve_sitings(a.siting, a.out_siting, tag_siting, chroma if a.y4m_in else None, out_chroma)
+            siting, out_siting = resolve_sitings(a.siting, a.out_siting, tag_siting, chroma if a.y4m_in and chroma != MONO else None,
+                                                 None if out_chroma == MONO else out_chroma)
         except ValueError as e:
             raise SystemExit(f"--siting / --out-siting: {e}") from None
         if a.siting == "auto":
@@ -438,8 +464,10 @@ def main(argv: Optional[List[str]] = None) -> int:
                            a.writers or max(1, min(MAX_WRITERS, effective_cpus())))
         t0 = time.perf_counter()
         up = VideoUpscaler(net, a.scale, a.padding, out=fmt_out, pixel_format=fmt_in,
-                           size=(h, w) if a.y4m_in else None, cuts=a.cuts, scene_threshold=a.scene_threshold, colour=colour or "bt601",
-                           out_colour=out_colour, depth=depth, out_depth=out_depth, siting=siting, out_siting=out_siting)
+                           size=(h, w) if a.y4m_in else None, cuts=a.cuts, scene_threshold=a.scene_threshold,
+                           colour="bt601" if chroma == MONO else colour or "bt601",          # (grey-scale frames carry no colour space)
+                           out_colour=None if out_chroma == MONO else out_colour, depth=depth, out_depth=out_depth, siting=siting, out_siting=out_siting,
+                           chroma_filter=a.chroma_filter)
         done = 0
         try:
             for chunk in chunks:

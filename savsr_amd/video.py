@@ -17,6 +17,12 @@ cuts=[k, ...] / cuts="auto": the video is a sequence of scenes and every scene i
 windows stop at cuts); "auto" finds the cuts on the device (savsr_video_pair_sad_*, then scdet's rule on the host).  cuts=None runs
 exactly the lines it ran before cuts existed.
 
+chroma_filter="bicubic" with a num_in_ch = 1 network (a luma-only checkpoint): YUV frames in and out are accepted; the Y plane goes
+through the network (savsr_video_gather_luma / savsr_video_quantize_luma) and every output frame's U and V are resampled from its own
+input frame at the network's scale (savsr_video_resample_chroma; savsr_amd/yuv.py "Luma-only checkpoints" is the specification).
+pixel_format / out = "y400": grey-scale frames, the Y plane alone (Y4M's Cmono), for such a network; it needs no chroma_filter.
+chroma_filter=None runs exactly the lines it ran before the argument existed.
+
 Every argument is checked here, on the host, before anything is enqueued on the GPU.
 """
 from __future__ import annotations
@@ -26,18 +32,26 @@ from typing import List, Optional, Sequence, Tuple, Union
 import torch
 
 from .harness import window_indices
-from .yuv import CHROMA_OF, CHROMAS, check_colour, check_depth, check_depth_colour, check_siting, frame_bytes, i420_bytes, layout_name
+from .yuv import (CHROMA_OF, CHROMAS, LUMA_FORMAT, MONO, SITINGS, check_chroma_filter, check_colour, check_depth, check_depth_colour, check_siting, frame_bytes,
+                  i420_bytes, layout_name)
 
 PADDING_MODES = ("replicate", "reflection", "reflection_circle", "circle")
 OUT_KINDS = ("float", "uint8", "i420", "i422", "i444")
 PIXEL_FORMATS = ("rgb", "i420", "i422", "i444")
 YUV_FORMATS = ("i420", "i422", "i444")          # planar YUV in the three chroma layouts (yuv.CHROMAS), as pixel_format and as out
+# "y400": grey-scale frames, the Y plane alone, for luma-only networks; accepted beside the two lists above, which stay as they were
+SAMPLE_FORMATS = YUV_FORMATS + (LUMA_FORMAT,)   # frames of planar samples with a bit depth
 _YUV_LIST = "'i420', 'i422' or 'i444'"
 
 
 def chroma_of(fmt: str) -> str:
     """The chroma layout ("420", "422", "444") of a YUV pixel format / output kind; "420" for the others (no YUV on that side)."""
     return CHROMA_OF.get(fmt, "420")
+
+
+def layout_of(fmt: str) -> str:
+    """chroma_of, with yuv.MONO ("400") for grey-scale frames ("y400")."""
+    return MONO if fmt == LUMA_FORMAT else chroma_of(fmt)
 
 
 def as_scale(scale) -> Tuple[float, float]:
@@ -93,7 +107,7 @@ def frame_layout(frames: torch.Tensor, nch: int) -> Tuple[int, int, int]:
 
 def check_pixel_format(pixel_format: str, size) -> Optional[Tuple[int, int]]:
     """(h, w) of YUV frames (i420, i422, i444), None for RGB ones; refuses an unknown format, YUV without a size and a size without YUV."""
-    if pixel_format not in PIXEL_FORMATS:
+    if pixel_format not in PIXEL_FORMATS and pixel_format != LUMA_FORMAT:
         raise ValueError(f"pixel_format = {pixel_format!r}: one of {', '.join(PIXEL_FORMATS)}")
     if pixel_format == "rgb":
         if size is not None:
@@ -129,14 +143,14 @@ def check_depths(depth, out_depth, pixel_format: str, out: str, colour: str = "b
     spaces only."""
     d = check_depth(depth, "depth")
     od = None if out_depth is None else check_depth(out_depth, "out_depth")
-    if d != 8 and pixel_format not in YUV_FORMATS:
+    if d != 8 and pixel_format not in SAMPLE_FORMATS:
         raise ValueError(f"depth = {d} goes with pixel_format = {_YUV_LIST}: it is the bit depth of YUV input (RGB frames carry theirs in their dtype)")
-    if od is not None and out not in YUV_FORMATS:
+    if od is not None and out not in SAMPLE_FORMATS:
         raise ValueError(f"out_depth = {od} goes with out = {_YUV_LIST}: it is the bit depth of YUV output")
     if od is None:
-        od = d if out in YUV_FORMATS else 8
+        od = d if out in SAMPLE_FORMATS else 8
     check_depth_colour(d, colour, "depth", "colour")
-    if out in YUV_FORMATS:
+    if out in SAMPLE_FORMATS:
         check_depth_colour(od, colour if out_colour is None else out_colour, "out_depth", "out_colour")
     return d, od
 
@@ -160,14 +174,14 @@ def check_sample_alignment(frames: torch.Tensor, depth: int, chroma: str = "420"
                          f"(an odd storage offset of a uint8 view); copy the frames (.clone()) first")
 
 
-def i420_layout(frames: torch.Tensor, size: Tuple[int, int], nch: int, depth: int = 8, chroma: str = "420") -> int:
+def i420_layout(frames: torch.Tensor, size: Tuple[int, int], nch: int, depth: int = 8, chroma: str = "420", luma: bool = False) -> int:
     """N of a YUV video tensor: [N, frame_bytes(h, w, depth, chroma)] uint8 (GPU or host); refuses anything else, naming the layout and
-    the byte count it expects."""
+    the byte count it expects.  luma: the luma-only path (`luma_mode`), where the network takes num_in_ch = 1 and chroma may be yuv.MONO."""
     h, w = size
     name, fb = layout_name(chroma), frame_bytes(h, w, depth, chroma)
     if not isinstance(frames, torch.Tensor):
         raise TypeError(f"frames must be a torch.Tensor, got {type(frames).__name__}")
-    if nch != 3:
+    if nch != 3 and not (luma and nch == 1):
         raise ValueError(f"{name} frames are colour frames, the network takes num_in_ch = {nch}")
     if frames.dtype != torch.uint8:
         raise ValueError(f"{name} frames must be uint8, got {frames.dtype}")
@@ -197,11 +211,38 @@ def _check_net(net) -> None:
         raise RuntimeError("savsr_amd.SAVSR implements the inference path only; call .eval() first")
 
 
-def check_out(out: str, nch: int) -> None:
-    if out not in OUT_KINDS:
+def check_out(out: str, nch: int, chroma_filter: Optional[str] = None) -> None:
+    if out not in OUT_KINDS and out != LUMA_FORMAT:
         raise ValueError(f"out = {out!r}: one of {', '.join(OUT_KINDS)}")
-    if out in YUV_FORMATS and nch != 3:
-        raise ValueError(f"out = {out!r} holds colour frames, the network gives num_in_ch = {nch}")
+    if out in YUV_FORMATS and nch != 3 and not (nch == 1 and chroma_filter is not None):
+        raise ValueError(f"out = {out!r} holds colour frames, the network gives num_in_ch = {nch}"
+                         f"{' (a luma-only network writes them with chroma_filter = ' + repr('bicubic') + ')' if nch == 1 else ''}")
+
+
+def luma_mode(nch: int, chroma_filter: Optional[str], pixel_format: str, out: str, colour: str, out_colour: Optional[str]) -> bool:
+    """Whether the call takes the luma-only path: a num_in_ch = 1 network with chroma_filter or grey-scale ("y400") frames on either side.
+    Refuses, by name, what that path cannot do.  False: the call runs the lines it ran before chroma_filter existed."""
+    check_chroma_filter(chroma_filter)
+    if chroma_filter is not None and nch != 1:
+        raise ValueError(f"chroma_filter = {chroma_filter!r} with num_in_ch = {nch}: chroma goes through such a network; the filter is for "
+                         f"luma-only networks (num_in_ch = 1)")
+    for what, fmt in (("pixel_format", pixel_format), ("out", out)):
+        if fmt == LUMA_FORMAT and nch != 1:
+            raise ValueError(f"{what} = {fmt!r} holds grey-scale frames, the network takes num_in_ch = {nch}")
+    if nch != 1 or not (chroma_filter is not None or LUMA_FORMAT in (pixel_format, out)):
+        return False
+    if pixel_format not in SAMPLE_FORMATS:
+        if out in SAMPLE_FORMATS:
+            raise ValueError(f"out = {out!r} from a luma-only network goes with pixel_format = {_YUV_LIST} or {LUMA_FORMAT!r}: RGB-layout frames "
+                             f"have no planes to take the chroma from")
+        raise ValueError(f"chroma_filter = {chroma_filter!r} goes with pixel_format = {_YUV_LIST}: {pixel_format!r} frames have no chroma planes "
+                         f"to resample")
+    if pixel_format == LUMA_FORMAT and out in YUV_FORMATS:
+        raise ValueError(f"pixel_format = {LUMA_FORMAT!r} frames have no chroma planes: out = {out!r} cannot be made from them")
+    if out_colour is not None and out_colour != colour:
+        raise ValueError(f"colour = {colour!r}, out_colour = {out_colour!r}: a luma-only network never forms RGB, so the samples keep their "
+                         f"colour space")
+    return True
 
 
 def _is_auto(cuts) -> bool:
@@ -261,7 +302,13 @@ def _pair_sad_device(frames: torch.Tensor, i420: Optional[Tuple[int, int]], dept
     with torch.cuda.device(frames.device):
         sad = torch.empty(n - 1, dtype=torch.int64, device=frames.device)
         st = torch.cuda.current_stream().cuda_stream
-        if i420 and chroma != "420":
+        if i420 and chroma == MONO:
+            # grey-scale frames are [N, h, w, 1] frames of their samples' 8 most significant bits (host work only: no kernel of their own)
+            if depth != 8:
+                words = frames.view(torch.int16).to(torch.int32) & 0xFFFF
+                frames = (words.clamp_(max=(1 << depth) - 1) >> (depth - 8)).to(torch.uint8)
+            _lib.check(lib.savsr_video_pair_sad_u8(frames.data_ptr(), n, 1, h, w, sad.data_ptr(), st), "savsr_video_pair_sad_u8")
+        elif i420 and chroma != "420":
             _lib.check(lib.savsr_video_pair_sad_yuvp(frames.data_ptr(), n, h, w, depth, CHROMAS.index(chroma), sad.data_ptr(), st),
                        "savsr_video_pair_sad_yuvp")
         elif i420 and depth != 8:
@@ -292,7 +339,7 @@ def pair_sad(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: 
     "i444": frames of those layouts; the Y plane only, as for I420."""
     i420 = check_pixel_format(pixel_format, size)
     depth = check_depth(depth)
-    chroma = chroma_of(pixel_format)
+    chroma = layout_of(pixel_format)
     _sad_layout(frames, i420, depth, chroma)
     return _pair_sad_device(_to_device(frames, _sad_device(frames)), i420, depth, chroma)
 
@@ -305,7 +352,7 @@ def detect_cuts(frames: torch.Tensor, threshold=10.0, pixel_format: str = "rgb",
     check_threshold(threshold)
     i420 = check_pixel_format(pixel_format, size)
     depth = check_depth(depth)
-    _sad_layout(frames, i420, depth, chroma_of(pixel_format))
+    _sad_layout(frames, i420, depth, layout_of(pixel_format))
     sad = pair_sad(frames, pixel_format, size, depth)
     return cuts_from_sad(sad.cpu().tolist(), sad_samples(frames.shape, pixel_format, size), threshold)
 
@@ -313,18 +360,19 @@ def detect_cuts(frames: torch.Tensor, threshold=10.0, pixel_format: str = "rgb",
 def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
                   size=None, cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601",
                   out_colour: Optional[str] = None, depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None,
-                  out_siting: Optional[str] = None) -> torch.Tensor:
+                  out_siting: Optional[str] = None, chroma_filter: Optional[str] = None) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
-    check_out(out, net.cfg["num_in_ch"])
+    check_out(out, net.cfg["num_in_ch"], chroma_filter)
     i420 = check_pixel_format(pixel_format, size)
     cid, ocid = check_colours(colour, out_colour, pixel_format, out)
     d, od = check_depths(depth, out_depth, pixel_format, out, colour, out_colour)
     sid, osid = check_sitings(siting, out_siting, pixel_format, out)
+    luma = luma_mode(net.cfg["num_in_ch"], chroma_filter, pixel_format, out, colour, out_colour)
     sc = as_scale(net.scale if scale is None else scale)
-    chroma, out_chroma = chroma_of(pixel_format), chroma_of(out)
-    n = i420_layout(frames, i420, net.cfg["num_in_ch"], d, chroma) if i420 else frame_layout(frames, net.cfg["num_in_ch"])[0]
+    chroma, out_chroma = layout_of(pixel_format), layout_of(out)
+    n = i420_layout(frames, i420, net.cfg["num_in_ch"], d, chroma, luma) if i420 else frame_layout(frames, net.cfg["num_in_ch"])[0]
     T = net.num_frame
     if cuts is None:
         check_length(n, T, padding)
@@ -347,6 +395,10 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
             sad = _pair_sad_device(frames, i420, d, chroma).cpu().tolist()
             cuts = scenes.cuts_from_sad(sad, scenes.sad_samples(frames.shape, pixel_format, size), scene_threshold)
         windows = scenes.scene_windows(n, cuts, T, padding)
+    if luma:
+        with torch.no_grad():
+            return net.engine().forward_video_luma(frames, windows, sc, i420, "yuv" if out in SAMPLE_FORMATS else out, ensemble=net.self_ensemble,
+                                                   depth=d, out_depth=od, chroma=chroma, out_chroma=out_chroma, siting=siting, out_siting=out_siting)
     with torch.no_grad():
         return net.engine().forward_video(frames, windows, sc, out == "uint8", ensemble=net.self_ensemble, i420=i420,
                                           out_i420=out in YUV_FORMATS, colour=cid, out_colour=ocid, depth=d, out_depth=od,
@@ -379,10 +431,11 @@ class VideoUpscaler:
 
     def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb", size=None,
                  cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None,
-                 depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None):
+                 depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
+                 chroma_filter: Optional[str] = None):
         _check_net(net)
         check_padding(padding)
-        check_out(out, net.cfg["num_in_ch"])
+        check_out(out, net.cfg["num_in_ch"], chroma_filter)
         self._plan = None                          # scenes.ScenePlan when cuts are given; None: the path without cuts, as it was
         if cuts is not None:
             from . import scenes
@@ -393,11 +446,13 @@ class VideoUpscaler:
             self._prev_sad = 0                     # the last pair's score (scdet's damping term), carried from push to push
             self._plan = scenes.ScenePlan(net.num_frame, padding)
         self.i420 = check_pixel_format(pixel_format, size)        # (h, w) of YUV chunks, None for RGB ones
-        self._chromas = (chroma_of(pixel_format), chroma_of(out))      # chroma layouts of the YUV input / output
+        self._chromas = (layout_of(pixel_format), layout_of(out))      # chroma layouts of the YUV input / output
         self._fmt = pixel_format
         self._colours = check_colours(colour, out_colour, pixel_format, out)      # colour space ids of the I420 input / output
         self._depths = check_depths(depth, out_depth, pixel_format, out, colour, out_colour)      # bit depths of the I420 input / output
         self._sitings = check_sitings(siting, out_siting, pixel_format, out)      # chroma siting ids of the YUV input / output
+        # the luma-only path (a num_in_ch = 1 network with chroma_filter or grey-scale frames): decided once, here
+        self._luma = luma_mode(net.cfg["num_in_ch"], chroma_filter, pixel_format, out, colour, out_colour)
         self.net, self.padding, self.out = net, padding, out
         self.scale = as_scale(net.scale if scale is None else scale)
         self.ensemble = net.self_ensemble          # (read once, like the scale: every chunk runs the same flow)
@@ -429,10 +484,21 @@ class VideoUpscaler:
                 lo = min(lo, min(window_indices(i, n, self.T, self.padding)))
         return max(lo, 0)
 
+    def _forward_luma(self, windows: List[List[int]]) -> torch.Tensor:
+        """The luma-only path on the buffered frames: Y through the network, U / V from each window's centre frame, which the buffer holds."""
+        sit = [None if s == 0 else SITINGS[s - 1] for s in self._sitings]
+        with torch.no_grad():
+            return self.net.engine().forward_video_luma(self._buf, windows, self.scale, self.i420, "yuv" if self.out in SAMPLE_FORMATS else self.out,
+                                                        ensemble=self.ensemble, depth=self._depths[0], out_depth=self._depths[1],
+                                                        chroma=self._chromas[0], out_chroma=self._chromas[1], siting=sit[0], out_siting=sit[1])
+
     def _run(self, upto: int, n_total: Optional[int]) -> torch.Tensor:
         """SR frames [done, upto); windows at the video length n_total (None: not known yet, every window needed is interior)."""
         n = n_total if n_total is not None else upto + self.half + 1
         windows = [[j - self._base for j in window_indices(i, n, self.T, self.padding)] for i in range(self.done, upto)]
+        if self._luma:
+            self.done = upto
+            return self._forward_luma(windows)
         with torch.no_grad():
             res = self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble, i420=self.i420,
                                                   out_i420=self.out in YUV_FORMATS, colour=self._colours[0], out_colour=self._colours[1],
@@ -446,7 +512,7 @@ class VideoUpscaler:
         if self._finished:
             raise RuntimeError("push() after finish()")
         if self.i420:
-            k, (h, w) = i420_layout(frames, self.i420, self.net.cfg["num_in_ch"], self._depths[0], self._chromas[0]), self.i420
+            k, (h, w) = i420_layout(frames, self.i420, self.net.cfg["num_in_ch"], self._depths[0], self._chromas[0], self._luma), self.i420
         else:
             k, h, w = frame_layout(frames, self.net.cfg["num_in_ch"])
         shape = (frames.dtype == torch.uint8, h, w)
@@ -493,6 +559,8 @@ class VideoUpscaler:
         if not windows:
             return self._empty()
         windows = [[j - self._base for j in win] for win in windows]
+        if self._luma:
+            return self._forward_luma(windows)
         with torch.no_grad():
             return self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble, i420=self.i420,
                                                    out_i420=self.out in YUV_FORMATS, colour=self._colours[0], out_colour=self._colours[1],
@@ -539,7 +607,7 @@ class VideoUpscaler:
         H, W = get_hw(h, w, self.scale)
         c = self.net.cfg["num_in_ch"]
         dev = self.net.gamma.device
-        if self.out in YUV_FORMATS:
+        if self.out in SAMPLE_FORMATS:
             return torch.empty(0, frame_bytes(H, W, self._depths[1], self._chromas[1]), dtype=torch.uint8, device=dev)
         if self.out == "uint8":
             return torch.empty(0, H, W, c, dtype=torch.uint8, device=dev)

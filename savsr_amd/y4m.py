@@ -19,6 +19,10 @@ and C444p12; `chroma` says which layout the stream has and `frame_bytes` is yuv.
 like high_depth, for the same reason.  Y4MWriter(..., chroma="422" | "444") writes them.  These tags and the p10 / p12 ones name no
 siting (`siting` is None): C422 means MPEG-2's horizontally cosited chroma to most tools, which is the caller's to say
 (siting="left" of yuv.py).  C444alpha, Cmono, C411 and 14- / 16-bit tags stay refused by name.
+
+Grey-scale: Y4MReader(f, mono=True) also reads Cmono, and with high_depth=True Cmono10 and Cmono12: `chroma` is "400" (yuv.MONO) and a
+frame is the Y plane alone, yuv.frame_bytes(height, width, depth, "400") bytes.  An opt-in of its own, like high_depth, so every refusal
+above keeps its words without it.  Y4MWriter(..., chroma="400") writes them.
 """
 from __future__ import annotations
 
@@ -27,7 +31,7 @@ from typing import Iterator, Optional, Tuple
 
 import numpy as np
 
-from .yuv import CHROMAS, SITINGS, check_chroma, frame_bytes
+from .yuv import CHROMAS, MONO, SITINGS, check_chroma, frame_bytes
 
 MAGIC = b"YUV4MPEG2"
 C420_TAGS = ("420", "420jpeg", "420mpeg2", "420paldv")
@@ -36,6 +40,8 @@ C420_HIGH_TAGS = {"420p10": 10, "420p12": 12}        # tag -> bit depth (Y4MRead
 # 4:2:2 / 4:4:4 tags -> (chroma layout, bit depth); the high-depth ones need high_depth=True as well (Y4MReader with layouts=)
 CHROMA_TAGS = {"422": ("422", 8), "444": ("444", 8)}
 CHROMA_HIGH_TAGS = {f"{c}p{d}": (c, d) for c in ("422", "444") for d in (10, 12)}
+MONO_TAGS = {"mono": 8}                              # grey-scale tag -> bit depth (Y4MReader with mono=True, Y4MWriter with chroma="400")
+MONO_HIGH_TAGS = {"mono10": 10, "mono12": 12}        # (with high_depth=True as well)
 MAX_LINE = 4096          # a header or FRAME line longer than this is not Y4M
 COLOUR_RANGES = ("full", "limited")
 
@@ -110,9 +116,11 @@ class Y4MReader:
     p12 forms) are read too, `chroma` is the stream's layout and the rows are [m, yuv.frame_bytes(height, width, depth, chroma)].
     The default reads 4:2:0 only and words every refusal as it did before layouts existed.
     siting (read-only): the chroma siting the C tag names, "centre" (C420jpeg), "left" (C420mpeg2) or "topleft" (C420paldv); None for
-    a plain C420, a missing tag and every other tag."""
+    a plain C420, a missing tag and every other tag.
+    mono=True: Cmono (and, with high_depth, Cmono10 / Cmono12) is read as well: `chroma` is "400" and the rows are the Y planes alone,
+    [m, yuv.frame_bytes(height, width, depth, "400")] uint8."""
 
-    def __init__(self, f, high_depth: bool = False, layouts=("420",)):
+    def __init__(self, f, high_depth: bool = False, layouts=("420",), mono: bool = False):
         self.f = f
         self.depth = 8
         self.chroma = "420"
@@ -153,7 +161,9 @@ class Y4MReader:
             elif key == "A":
                 self.aspect = _ratio("A", val)
             elif key == "C":
-                if high_depth and val in C420_HIGH_TAGS:
+                if mono and (val in MONO_TAGS or (high_depth and val in MONO_HIGH_TAGS)):
+                    self.chroma, self.depth = MONO, MONO_TAGS.get(val) or MONO_HIGH_TAGS[val]
+                elif high_depth and val in C420_HIGH_TAGS:
                     self.depth, self.colorspace = C420_HIGH_TAGS[val], val
                 elif val in CHROMA_TAGS and CHROMA_TAGS[val][0] in more:
                     self.chroma = CHROMA_TAGS[val][0]
@@ -218,7 +228,8 @@ class Y4MWriter:
     colour_range = "full" / "limited": the header also carries XCOLORRANGE=FULL / =LIMITED (None: no such tag).  depth = 10, 12: the
     stream is tagged C420p10 / C420p12 and its frames are [m, 2 * i420_bytes(height, width)] uint8 (little-endian 16-bit samples).
     chroma = "422", "444": the stream is tagged C422 / C444 (C422p10 ... at depth 10 / 12) and its frames are
-    [m, yuv.frame_bytes(height, width, depth, chroma)] uint8.  siting: the chroma siting of the frames (yuv.SITINGS or None); an 8-bit
+    [m, yuv.frame_bytes(height, width, depth, chroma)] uint8.  chroma = "400": grey-scale, tagged Cmono (Cmono10 / Cmono12), the frames
+    are the Y planes alone.  siting: the chroma siting of the frames (yuv.SITINGS or None); an 8-bit
     4:2:0 stream is tagged C420mpeg2 for "left", C420paldv for "topleft" and C420jpeg otherwise; no other header has a tag for it."""
 
     def __init__(self, f, width: int, height: int, fps: Tuple[int, int] = (25, 1), interlace: str = "p", aspect: Tuple[int, int] = (0, 0),
@@ -230,7 +241,8 @@ class Y4MWriter:
         if depth != 8 and depth not in C420_HIGH_TAGS.values():
             raise ValueError(f"y4m: depth = {depth!r}: one of 8, 10, 12")
         try:
-            check_chroma(chroma)
+            if chroma != MONO:
+                check_chroma(chroma)
         except ValueError as e:
             raise ValueError(f"y4m: {e}") from None
         if siting is not None and siting not in SITINGS:
@@ -239,6 +251,8 @@ class Y4MWriter:
         self.frame_bytes = frame_bytes(self.height, self.width, self.depth, chroma)
         tag420 = {"left": "420mpeg2", "topleft": "420paldv"}.get(siting, "420jpeg")
         ctag = (tag420 if chroma == "420" else chroma) if depth == 8 else f"{chroma}p{self.depth}"
+        if chroma == MONO:
+            ctag = "mono" if depth == 8 else f"mono{self.depth}"
         self.header = (f"YUV4MPEG2 W{self.width} H{self.height} F{fps[0]}:{fps[1]} I{interlace} A{aspect[0]}:{aspect[1]} C{ctag}"
                        f"{'' if colour_range is None else ' XCOLORRANGE=' + colour_range.upper()}\n").encode("ascii")
         f.write(self.header)

@@ -191,7 +191,10 @@ def check_siting(siting, chroma: str = "420", what: str = "siting") -> int:
 
 
 def frame_bytes(h: int, w: int, depth: int = 8, chroma: str = "420") -> int:
-    """Bytes of a frame in the given layout: a byte per sample at 8 bits, a 16-bit word at 10 and 12."""
+    """Bytes of a frame in the given layout: a byte per sample at 8 bits, a 16-bit word at 10 and 12.  chroma = "400" (MONO): the Y plane
+    alone, a grey-scale frame (the module's "Luma-only checkpoints")."""
+    if chroma == MONO:
+        return h * w * (1 if depth == 8 else 2)
     ch, cw = chroma_hw(h, w, chroma)
     return (h * w + 2 * ch * cw) * (1 if depth == 8 else 2)
 
@@ -202,8 +205,8 @@ def i420_bytes(h: int, w: int, depth: int = 8) -> int:
 
 
 def layout_name(chroma: str) -> str:
-    """What the messages call a frame of the layout: I420, I422, I444."""
-    return "I" + chroma
+    """What the messages call a frame of the layout: I420, I422, I444; Y400 for grey-scale frames (MONO)."""
+    return "Y400" if chroma == MONO else "I" + chroma
 
 
 def _check_size(h: int, w: int) -> None:
@@ -449,3 +452,196 @@ def rgb_to_i420(x_f32: np.ndarray, colour: str = "bt601", depth: int = 8, chroma
             planes = [np.fmin(np.fmax(v, np.float32(0.0)), np.float32(255.0)) for v in planes]
     n = planes[0].shape[0]
     return np.concatenate([v.astype(np.uint8 if depth == 8 else "<u2").reshape(n, -1) for v in planes], 1).view(np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Luma-only checkpoints (num_in_ch = 1) on YUV and grey-scale video: the specification of luma.hip -- savsr_video_gather_luma,
+# savsr_video_quantize_luma and savsr_video_resample_chroma -- and of upscale_video(chroma_filter="bicubic").  Y goes through the network,
+# Cb / Cr go from samples to samples through a separable, siting-aware Keys cubic at the network's scale.
+#
+#   luma in    min(s, 2^d - 1) as float32, divided by float32(255 k), k = 2^(d - 8): one IEEE float32 division.  A Y-only model is trained
+#              on Y / 255 of limited-range codes (rgb2ycbcr(y_only=True)); the same rule is applied whatever the colour id -- the colour
+#              space is documented, not converted (a luma-only network never forms RGB).  At 8 bits: savsr_video_gather_u8's value.
+#   luma out   rint(clamp(v, 0, 1) * float32(255 k)), half to even, NaN -> 0.  At 8 bits: savsr_video_quantize_u8's rule.
+#   chroma     `chroma_axis_table` per axis, then `resample_chroma`: width first, then height, float32 in tap order without fused
+#              multiply-add, x 2^(D - d), rint, clip to 0 .. 2^D - 1 (the cubic overshoots).
+#
+# MONO = "400" is the layout of a grey-scale frame (Y4M's Cmono): the Y plane alone.
+MONO = "400"
+LUMA_FORMAT = "y400"
+CHROMA_FILTERS = ("bicubic",)
+_SUB = {"420": (2, 2), "422": (1, 2), "444": (1, 1)}          # (vertical, horizontal) luma samples per chroma sample
+
+
+def check_chroma_filter(chroma_filter) -> None:
+    """chroma_filter is None or one of CHROMA_FILTERS; refuses anything else, naming the list."""
+    if chroma_filter is not None and (not isinstance(chroma_filter, str) or chroma_filter not in CHROMA_FILTERS):
+        raise ValueError(f"chroma_filter = {chroma_filter!r}: None or one of {', '.join(CHROMA_FILTERS)}")
+
+
+def subsampling(chroma: str) -> Tuple[int, int]:
+    """(vertical, horizontal) luma samples per chroma sample of a layout: (2, 2), (1, 2), (1, 1)."""
+    return _SUB[CHROMAS[check_chroma(chroma)]]
+
+
+def luma_to_unit(samples: np.ndarray, depth: int = 8) -> np.ndarray:
+    """Y samples -> the float32 values a luma-only network reads: float32(min(s, 2^d - 1)) / float32(255 * 2^(d - 8))."""
+    d = check_depth(depth)
+    s = np.minimum(np.asarray(samples).astype(np.int64), (1 << d) - 1).astype(np.float32)
+    return s / np.float32(255 << (d - 8))
+
+
+def unit_to_luma(v: np.ndarray, depth: int = 8) -> np.ndarray:
+    """The network's float32 luma -> Y samples (uint8 at 8 bits, uint16 at 10 / 12): rint(clamp(v, 0, 1) * float32(255 * 2^(d - 8))),
+    half to even; fmax / fmin, so a NaN becomes 0."""
+    d = check_depth(depth)
+    v = np.asarray(v, dtype=np.float32)
+    q = np.rint(np.fmin(np.fmax(v, np.float32(0.0)), np.float32(1.0)) * np.float32(255 << (d - 8)))
+    return q.astype(np.uint8 if d == 8 else np.uint16)
+
+
+def _cosited(siting, axis: str) -> bool:
+    """Whether a siting puts the chroma samples on luma samples along an axis: "left" and "topleft" along x, "topleft" along y."""
+    if siting is not None and (not isinstance(siting, str) or siting not in SITINGS):
+        raise ValueError(f"siting = {siting!r}: None or one of {', '.join(SITINGS)}")
+    if axis not in ("x", "y"):
+        raise ValueError(f"axis = {axis!r}: 'x' or 'y'")
+    return siting == "topleft" or (siting == "left" and axis == "x")
+
+
+def _keys(x: np.ndarray) -> np.ndarray:
+    """The Keys cubic with a = -0.5, float64."""
+    ax = np.abs(x)
+    ax2, ax3 = ax * ax, ax * ax * ax
+    a = -0.5
+    return np.where(ax <= 1, (a + 2) * ax3 - (a + 3) * ax2 + 1, np.where(ax <= 2, a * ax3 - 5 * a * ax2 + 8 * a * ax - 4 * a, 0.0))
+
+
+def chroma_axis_table(n_in_luma: int, n_out_luma: int, sub_in: int, sub_out: int, siting_in=None, siting_out=None, axis: str = "x"):
+    """(xmin[int32], xsize[int32], weights[float32][max_taps]) of one axis of the chroma resampler: ceil(n_in_luma / sub_in) input samples
+    -> ceil(n_out_luma / sub_out) output samples.  Output sample j lies at HR luma position P = sub_out j + o_out, input sample c at LR
+    luma position sub_in c + o_in, o = (sub - 1) / 2 for a centre-sited or unmodelled (None) axis and 0 for a cosited one (`axis` says
+    which axis of the siting this is): interpolate_chroma's positions.  The luma grids are related by pixel centres and the actual sizes,
+    p = (P + 0.5) n_in_luma / n_out_luma - 0.5, so the position among the input samples is u = (p - o_in) / sub_in.  With
+    rho = sub_out n_in_luma / (n_out_luma sub_in) input samples per output sample and aa = min(1, 1 / rho): the Keys cubic (a = -0.5) of
+    (u - tap) aa over ceil(4 / aa) + 2 taps from floor(u) - ksize // 2 + 1, normalised to sum 1; taps outside the plane fold onto the
+    pixels inside by core.py's border rule (-1 -> 0, -2 -> 1, n -> n - 1; applied again where a plane is shorter than the reach):
+    resize_gpu.core_tables with a general position.  float64 throughout, each folded weight rounded to float32 once; taps of weight 0
+    at either end of a window are dropped, so an axis with u == j exactly gives the single weight 1.0."""
+    for v in (n_in_luma, n_out_luma):
+        if int(v) != v or v < 1:
+            raise ValueError(f"luma sizes must be integers >= 1, got ({n_in_luma!r}, {n_out_luma!r})")
+    if sub_in not in (1, 2) or sub_out not in (1, 2):
+        raise ValueError(f"sub_in, sub_out = {sub_in!r}, {sub_out!r}: 1 or 2 luma samples per chroma sample")
+    n_in_luma, n_out_luma = int(n_in_luma), int(n_out_luma)
+    o_in = 0.0 if _cosited(siting_in, axis) else (sub_in - 1) / 2.0
+    o_out = 0.0 if _cosited(siting_out, axis) else (sub_out - 1) / 2.0
+    n_in, n_out = -(-n_in_luma // sub_in), -(-n_out_luma // sub_out)
+    rho = (sub_out * n_in_luma) / (n_out_luma * sub_in)
+    aa = min(1.0, 1.0 / rho)
+    ksize = int(np.ceil(4.0 / aa)) + 2
+    rows, xmin, xsize = [], np.zeros(n_out, np.int32), np.zeros(n_out, np.int32)
+    for j in range(n_out):
+        p = ((sub_out * j + o_out) + 0.5) * n_in_luma / n_out_luma - 0.5
+        u = (p - o_in) / sub_in
+        base = int(np.floor(u)) - ksize // 2 + 1
+        taps = base + np.arange(ksize)
+        wt = _keys((u - taps) * aa)
+        wt = wt / wt.sum()
+        folded = np.zeros(n_in, np.float64)
+        for t, v in zip(taps, wt):
+            t = int(t)
+            while t < 0 or t >= n_in:
+                t = -t - 1 if t < 0 else 2 * n_in - 1 - t
+            folded[t] += v
+        nz = np.nonzero(folded)[0]
+        lo, hi = int(nz[0]), int(nz[-1])
+        xmin[j], xsize[j] = lo, hi - lo + 1
+        rows.append(folded[lo:hi + 1].astype(np.float32))
+    weights = np.zeros((n_out, int(xsize.max())), np.float32)
+    for j, r in enumerate(rows):
+        weights[j, :len(r)] = r
+    return xmin, xsize, weights
+
+
+def chroma_tables(h: int, w: int, H: int, W: int, chroma: str, out_chroma: str, siting=None, out_siting=None):
+    """(table_y, table_x) of `chroma_axis_table` for an h x w -> H x W picture and the two layouts and sitings."""
+    check_siting(siting, chroma, "siting")
+    check_siting(out_siting, out_chroma, "out_siting")
+    (sy, sx), (oy, ox) = subsampling(chroma), subsampling(out_chroma)
+    return (chroma_axis_table(h, H, sy, oy, siting, out_siting, "y"), chroma_axis_table(w, W, sx, ox, siting, out_siting, "x"))
+
+
+def dense_axis(table, n_in: int) -> np.ndarray:
+    """The [out][in] float32 matrix of an axis table."""
+    xmin, xsize, wt = table
+    m = np.zeros((len(xmin), n_in), np.float32)
+    for j in range(len(xmin)):
+        m[j, xmin[j]:xmin[j] + xsize[j]] = wt[j, :xsize[j]]
+    return m
+
+
+def _filter_axis(x: np.ndarray, table, axis: int) -> np.ndarray:
+    """acc = w0 s0, then acc = acc + wi si in tap order, float32, every product and sum rounded; taps beyond an output's xsize skipped."""
+    xmin, xsize, wt = table
+    shape = [1] * x.ndim
+    shape[axis] = len(xmin)
+    n = x.shape[axis]
+    acc = None
+    for t in range(wt.shape[1]):
+        prod = wt[:, t].reshape(shape) * np.take(x, np.minimum(xmin + t, n - 1), axis)
+        acc = prod if acc is None else np.where((t < xsize).reshape(shape), acc + prod, acc)
+    return acc.astype(np.float32)
+
+
+def resample_chroma(plane: np.ndarray, table_y, table_x, depth_in: int = 8, depth_out: int = 8) -> np.ndarray:
+    """Chroma samples [..., ch, cw] -> [..., cH, cW] (uint8 at depth_out = 8, uint16 at 10 / 12): samples clipped to 2^d - 1; the width
+    through table_x, then the height through table_y over the filtered rows (`_filter_axis`); x 2^(D - d) (exact); rint, half to even;
+    clipped to 0 .. 2^D - 1."""
+    d, D = check_depth(depth_in, "depth_in"), check_depth(depth_out, "depth_out")
+    p = np.asarray(plane)
+    if p.ndim < 2 or not np.issubdtype(p.dtype, np.integer):
+        raise ValueError(f"a chroma plane is [..., ch, cw] of integer samples, got {p.dtype} {tuple(p.shape)}")
+    s = np.minimum(p.astype(np.int64), (1 << d) - 1).astype(np.float32)
+    v = _filter_axis(_filter_axis(s, table_x, s.ndim - 1), table_y, s.ndim - 2)
+    v = np.rint(v * np.float32(2.0 ** (D - d)))
+    v = np.fmin(np.fmax(v, np.float32(0.0)), np.float32((1 << D) - 1))
+    return v.astype(np.uint8 if D == 8 else np.uint16)
+
+
+def luma_plane(frames: np.ndarray, h: int, w: int, depth: int = 8, chroma: str = "420") -> np.ndarray:
+    """The Y samples [N, h, w] of frames [N, frame_bytes(h, w, depth, chroma)] uint8 (chroma = MONO: grey-scale frames)."""
+    frames = np.asarray(frames)
+    fb = frame_bytes(h, w, check_depth(depth), chroma)
+    if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != fb:
+        raise ValueError(f"frames of {h} x {w} are [N, {fb}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+    s = 1 if depth == 8 else 2
+    y = np.ascontiguousarray(frames[:, :h * w * s])
+    return (y if depth == 8 else y.view("<u2")).reshape(frames.shape[0], h, w)
+
+
+def luma_only_frames(frames: np.ndarray, h: int, w: int, sr_luma_unit: np.ndarray, depth: int = 8, out_depth=None, chroma: str = "420",
+                     out_chroma=None, siting=None, out_siting=None) -> np.ndarray:
+    """The output frames of a luma-only network on YUV video: frames [N, frame_bytes(h, w, depth, chroma)] uint8 and the network's
+    float32 luma [N, 1, H, W] (or [N, H, W]) -> uint8 [N, frame_bytes(H, W, out_depth, out_chroma)].  Y = unit_to_luma of the network's
+    result; U and V = resample_chroma of the same input frame's planes.  out_chroma = MONO drops the chroma; chroma = MONO has none to
+    give, so only MONO comes out of it."""
+    D = check_depth(depth if out_depth is None else out_depth, "out_depth")
+    out_chroma = chroma if out_chroma is None else out_chroma
+    sr = np.asarray(sr_luma_unit, dtype=np.float32)
+    if sr.ndim == 4 and sr.shape[1] == 1:
+        sr = sr[:, 0]
+    n = np.asarray(frames).shape[0]
+    if sr.ndim != 3 or sr.shape[0] != n:
+        raise ValueError(f"the network's luma is [N, 1, H, W] float32 for N = {n} frames, got {tuple(np.asarray(sr_luma_unit).shape)}")
+    H, W = sr.shape[1:]
+    planes = [unit_to_luma(sr, D)]
+    if out_chroma != MONO:
+        if chroma == MONO:
+            raise ValueError(f"grey-scale frames have no chroma planes: out_chroma = {out_chroma!r} cannot be made from them")
+        ty, tx = chroma_tables(h, w, H, W, chroma, out_chroma, siting, out_siting)
+        _, u, v = split_planes(frames, h, w, depth, chroma)
+        planes += [resample_chroma(u, ty, tx, depth, D), resample_chroma(v, ty, tx, depth, D)]
+    else:
+        luma_plane(frames, h, w, depth, chroma)          # (the shape check)
+    return np.concatenate([np.ascontiguousarray(q.astype(np.uint8 if D == 8 else "<u2")).reshape(n, -1).view(np.uint8) for q in planes], 1)

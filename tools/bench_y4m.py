@@ -22,6 +22,11 @@ fails, times out or dies ends the run (nothing more is started on the GPU) and w
             synthetic picture (`value_psnr`): smooth seeded fields plus chroma edges, subsampled by a float64 left-cosited [1 2 1] / 4,
             reconstructed by today's nearest reading and by siting="left"; PSNR of the reconstructed chroma.  Synthetic: no real footage.
             `--legs siting --out profiles/bench_y4m_siting.json`
+  luma      savsr_video_gather_luma / _quantize_luma / _resample_chroma (luma-only checkpoints) at 8 and 10 bits, 7 frames, in one process,
+            interleaved rounds: the two luma kernels at 720x1280 beside savsr_video_gather_yuvp / _quantize_yuvp at 4:2:0, which are read
+            twice in every round (their spread is the margin); the resampler at x4 from 180x320 for 4:2:0 -> 4:2:0 and 4:2:0 -> 4:4:4 (one
+            call per plane; the figure is U and V together).  us, bytes in and out, GB/s = (bytes in + bytes out) / time.  No speed is
+            fixed in advance.  `--legs luma --out profiles/bench_y4m_luma.json`
   ceiling   upscale_video on preloaded I420 frames, I420 out (frames/s): what the CLI could reach
   cli       python -m savsr_amd.upscale on one synthetic video, PNG folder -> PNG folder against .y4m -> .y4m, A/B/A/B; files under
             --workdir (name the disk it lies on beside the figures: tmpfs or a scratch disk)
@@ -44,7 +49,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_BYTES_PER_S = 8e12
-LEG_TIMEOUT_S = {"kernels": 240, "depth": 240, "chroma": 240, "siting": 300, "ceiling": 420, "cli": 420, "psnr": 420}
+LEG_TIMEOUT_S = {"kernels": 240, "depth": 240, "chroma": 240, "siting": 300, "luma": 240, "ceiling": 420, "cli": 420, "psnr": 420}
 
 
 def _net(dev):
@@ -321,6 +326,87 @@ def leg_siting(a):
             "timing": "HIP events around `iters` back-to-back launches (launch rate included)"}
 
 
+def leg_luma(a):
+    import ctypes as C
+    import torch
+    from savsr_amd import _lib
+    from savsr_amd.yuv import chroma_hw, chroma_tables, frame_bytes
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    h, w, n = 720, 1280, 16
+    lh, lw = 180, 320
+    arr = (C.c_int32 * 7)(*range(7))
+    slots3, slots1 = torch.empty(7, 3, h, w, device=dev), torch.empty(7, 1, h, w, device=dev)
+    x3, x1 = torch.rand(7, 3, h, w, device=dev), torch.rand(7, 1, h, w, device=dev)
+    fns, nbytes, keep = {}, {}, []
+    for depth in (8, 10):
+        s = 1 if depth == 8 else 2
+        fb = frame_bytes(h, w, depth, "420")
+        src = torch.randint(0, 256 if depth == 8 else 4, (n, fb), dtype=torch.uint8, device=dev)          # (in-range samples at either depth)
+        dst = torch.empty(7, fb, dtype=torch.uint8, device=dev)
+        keep += [src, dst]
+        for tag in ("a", "b"):                          # the yardstick is read twice in every round
+            fns[f"gather yuvp 420 {depth}-bit ({tag})"] = lambda s_=src, d=depth: lib.savsr_video_gather_yuvp(s_.data_ptr(), n, h, w, arr, 7, 1, d, 0, slots3.data_ptr(), st)
+            fns[f"quantize yuvp 420 {depth}-bit ({tag})"] = lambda o=dst, d=depth: lib.savsr_video_quantize_yuvp(x3.data_ptr(), 7, h, w, 1, d, 0, o.data_ptr(), st)
+            nbytes[f"gather yuvp 420 {depth}-bit ({tag})"] = (7 * fb, 7 * 12 * h * w)
+            nbytes[f"quantize yuvp 420 {depth}-bit ({tag})"] = (7 * 12 * h * w, 7 * fb)
+        fns[f"gather luma {depth}-bit"] = lambda s_=src, d=depth, fb=fb: lib.savsr_video_gather_luma(s_.data_ptr(), n, fb, h, w, d, arr, 7, slots1.data_ptr(), st)
+        fns[f"quantize luma {depth}-bit"] = lambda o=dst, d=depth, fb=fb: lib.savsr_video_quantize_luma(x1.data_ptr(), 7, h, w, d, o.data_ptr(), fb, st)
+        nbytes[f"gather luma {depth}-bit"] = (7 * h * w * s, 7 * 4 * h * w)
+        nbytes[f"quantize luma {depth}-bit"] = (7 * 4 * h * w, 7 * h * w * s)
+        lfb = frame_bytes(lh, lw, depth, "420")
+        lsrc = torch.randint(0, 256 if depth == 8 else 4, (7, lfb), dtype=torch.uint8, device=dev)
+        keep.append(lsrc)
+        ch, cw = chroma_hw(lh, lw, "420")
+        for out_chroma in ("420", "444"):
+            tabs = [[torch.from_numpy(v).to(dev) for v in t] for t in chroma_tables(lh, lw, h, w, "420", out_chroma)]
+            ofb = frame_bytes(h, w, depth, out_chroma)
+            cH, cW = chroma_hw(h, w, out_chroma)
+            odst = torch.empty(7, ofb, dtype=torch.uint8, device=dev)
+            keep += [tabs, odst]
+
+            def resample(s_=lsrc, o=odst, d=depth, s=s, t=tabs, lfb=lfb, ofb=ofb, cH=cH, cW=cW):
+                rc = 0
+                for plane in range(2):
+                    rc |= lib.savsr_video_resample_chroma(s_.data_ptr(), 7, lfb, (lh * lw + plane * ch * cw) * s, ch, cw, d, o.data_ptr(), ofb,
+                                                          (h * w + plane * cH * cW) * s, cH, cW, d, t[0][0].data_ptr(), t[0][1].data_ptr(),
+                                                          t[0][2].data_ptr(), int(t[0][2].shape[1]), t[1][0].data_ptr(), t[1][1].data_ptr(),
+                                                          t[1][2].data_ptr(), int(t[1][2].shape[1]), st)
+                return rc
+            fns[f"resample 420->{out_chroma} {depth}-bit"] = resample
+            nbytes[f"resample 420->{out_chroma} {depth}-bit"] = (7 * 2 * ch * cw * s, 7 * 2 * cH * cW * s)
+    us = {k: [] for k in fns}
+    for k, fn in fns.items():
+        assert fn() == 0, k
+    torch.cuda.synchronize()
+    for _ in range(a.rounds):                           # interleaved rounds: every kernel sees the same clocks
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us[k].append(1e3 * e0.elapsed_time(e1) / a.iters)
+    med = {k: statistics.median(v) for k, v in us.items()}
+    gbs = {k: sum(nbytes[k]) / (med[k] * 1e-6) / 1e9 for k in fns}
+    rows = []
+    for k in fns:
+        side, depth = k.split()[0], [t for t in k.split() if t.endswith("-bit")][0]
+        row = {"kernel": k, "frames": 7, "us": round(med[k], 2), "bytes_in": nbytes[k][0], "bytes_out": nbytes[k][1], "gbs": round(gbs[k], 1),
+               "us_rounds": [round(v, 2) for v in us[k]]}
+        if side != "resample":
+            ya, yb = gbs[f"{side} yuvp 420 {depth} (a)"], gbs[f"{side} yuvp 420 {depth} (b)"]
+            row.update(size=[h, w], gbs_yuvp_420=round(min(ya, yb), 1), margin_gbs=round(abs(ya - yb), 1),
+                       below_yuvp_by_more_than_the_margin=bool(gbs[k] < min(ya, yb) - abs(ya - yb)))
+        else:
+            row.update(size=[lh, lw], out_size=[h, w], launches=2)
+        rows.append(row)
+    return {"kernels": rows, "rounds": a.rounds, "iters": a.iters,
+            "timing": "HIP events around `iters` back-to-back launches (launch rate included); a resample reading is its two launches, U and V"}
+
+
 def leg_ceiling(a):
     import torch
     dev = torch.device("cuda:0")
@@ -402,7 +488,7 @@ def leg_psnr(a):
                        "note": "against the float result in float64; synthetic weights"}}
 
 
-LEGS = {"kernels": leg_kernels, "depth": leg_depth, "chroma": leg_chroma, "siting": leg_siting, "ceiling": leg_ceiling, "cli": leg_cli, "psnr": leg_psnr}
+LEGS = {"kernels": leg_kernels, "depth": leg_depth, "chroma": leg_chroma, "siting": leg_siting, "luma": leg_luma, "ceiling": leg_ceiling, "cli": leg_cli, "psnr": leg_psnr}
 
 
 def main():
