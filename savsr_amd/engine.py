@@ -35,7 +35,8 @@ from .config import EngineConfig
 from .launch import MAX_SUM_BLOCKS, Launcher, Src, _ptr      # noqa: F401
 from .packing import (BN_EPS, CONV_TH, CONV_TW, WeightPacking, acc_row, conv_pack_geometry, conv_pack_index, conv_wy_pack_index, get_hw,      # noqa: F401  (re-exported:
                       pack_conv_part, pack_conv_weight, pack_conv_weight_wy, satu_axis_tables, split_bf16_image, window_record)                            # tests and tools import them from here)
-from .yuv import CHROMAS, COLOURS, SITINGS, frame_bytes, layout_name
+from .video import VideoSpec, video_spec
+from .yuv import CHROMAS, COLOURS, SITINGS, chroma_hw, layout_name
 
 
 class HipEngine(WeightPacking, ContextCache, Launcher):
@@ -798,50 +799,38 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         self._fan_out(units, sum(lq.shape[-2] * lq.shape[-1] for lq, _ in items) / max(1, len(items)), run)
         return outs
 
-    def forward_video(self, frames: torch.Tensor, windows: List[List[int]], scale, out_u8: bool = False, ensemble: bool = False,
-                      i420: Optional[Tuple[int, int]] = None, out_i420: bool = False, colour: int = 0, out_colour: int = 0, depth: int = 8,
-                      out_depth: int = 8, chroma: int = 0, out_chroma: int = 0, siting: int = 0, out_siting: int = 0) -> torch.Tensor:
-        """The sequence path (SAVSR.upscale_video): frames [N, h, w, c] uint8 or [N, c, h, w] fp32 on the device, windows[i] = the
-        num_frame frame indices of output frame i in clip order (harness.window_indices) -> [len(windows), c, H, W] fp32, or
-        [len(windows), H, W, c] uint8 (out_u8: tensor2img(x, rgb2bgr=False) per frame, savsr_video_quantize_u8).
+    def forward_video(self, frames: torch.Tensor, windows: List[List[int]], scale, spec: Optional[VideoSpec] = None,
+                      ensemble: bool = False) -> torch.Tensor:
+        """The sequence path (SAVSR.upscale_video, VideoUpscaler): frames on the device, as `spec` (a video.VideoSpec, taken on trust:
+        there is no invalid one) says -- packed, [N, h, w, c] uint8 or [N, c, h, w] fp32, or planar, [N, spec.inp.frame_bytes(h, w)] uint8
+        with (h, w) = spec.size; windows[i] = the num_frame frame indices of output frame i in clip order (harness.window_indices) ->
+        [len(windows), c, H, W] fp32, [len(windows), H, W, c] uint8 (tensor2img(x, rgb2bgr=False) per frame) or
+        [len(windows), spec.out.frame_bytes(H, W)] uint8 planar frames (`spec.out_kind`).  spec=None: packed frames in, fp32 out.
         Launch units and streams are forward_many's (up to `clip_unit` consecutive windows per unit, balanced; units dealt round-robin over
         `streams_for` streams; throughput flow), so frame i equals forward_many on the gathered window i bit for bit.  A unit's windows are
-        gathered from `frames` by savsr_video_gather_u8 / _f32 into a unit-sized fp32 clip batch on the unit's stream; nothing is gathered
-        or converted on the host.  ensemble=True: frame i is the self-ensemble of window i (`_ensemble`, gathered by savsr_ensemble_gather_*).
-        i420=(h, w): frames are [N, i420_bytes(h, w)] uint8, planar YUV 4:2:0 (savsr_amd/yuv.py), gathered by savsr_video_gather_yuvs where
-        the uint8 gather runs; out_i420: the result is [len(windows), i420_bytes(H, W)] uint8, quantised by savsr_video_quantize_yuvs where
-        the uint8 quantisation runs.  colour / out_colour: the colour space ids (positions in yuv.COLOURS) of the I420 input / output.  With
-        the ensemble, I420 frames are converted once to fp32 planar RGB (the same gather with the identity list) and take the fp32 path,
-        and an I420 result is the fp32 merge followed by the quantisation.  depth / out_depth = 10, 12: the I420 frames in / out hold 16-bit
-        samples ([N, 2 * i420_bytes] uint8, limited range only), and nothing else changes.  chroma / out_chroma: the chroma layout ids
-        (positions in yuv.CHROMAS: 4:2:0, 4:2:2, 4:4:4) of the YUV input / output, [N, frame_bytes(h, w, depth, chroma)] uint8.  The two
-        entries serve every (layout, depth); at 4:2:0 they run the kernels of savsr_video_gather_yuv420(_16) / _quantize_yuv420(_16).
-        siting / out_siting: the chroma siting ids of the YUV input / output (0 = not modelled, else the position in yuv.SITINGS plus one);
-        the two call sites go through savsr_video_gather_yuvs / _quantize_yuvs, which at 0 run the kernels of the _yuvp entries."""
-        if out_u8 and out_i420:
-            raise ValueError("one output kind: uint8 or I420")
-        for what, d, on, cs in (("depth", depth, i420 is not None, colour), ("out_depth", out_depth, out_i420, out_colour)):
-            if d not in (8, 10, 12) or (d != 8 and not on):
-                raise ValueError(f"{what} = {d!r}: 8, 10 or 12, and 10 / 12 with I420 frames on that side only")
-            if d != 8 and cs not in (0, 1):
-                raise ValueError(f"{what} = {d} with colour id {cs}: 10 and 12 bits are defined for limited range only ({COLOURS[0]}, {COLOURS[1]})")
-        if not (0 <= colour < len(COLOURS) and 0 <= out_colour < len(COLOURS)):
-            raise ValueError(f"colour ids {colour}, {out_colour}: 0 .. {len(COLOURS) - 1} ({', '.join(COLOURS)})")
-        for what, cid, on in (("chroma", chroma, i420 is not None), ("out_chroma", out_chroma, out_i420)):
-            if cid not in range(len(CHROMAS)) or (cid != 0 and not on):
-                raise ValueError(f"{what} = {cid!r}: 0 .. {len(CHROMAS) - 1} ({', '.join(CHROMAS)}), and not 0 with YUV frames on that side only")
-        for what, sid, on, cid in (("siting", siting, i420 is not None, chroma), ("out_siting", out_siting, out_i420, out_chroma)):
-            if sid not in range(len(SITINGS) + 1) or (sid != 0 and not on):
-                raise ValueError(f"{what} = {sid!r}: 0 (not modelled) or 1 .. {len(SITINGS)} ({', '.join(SITINGS)}), and not 0 with YUV frames on that side only")
-            if sid == 3 and CHROMAS[cid] == "422":
-                raise ValueError(f"{what} = 3 (topleft) with 4:2:2 chroma: 4:2:2 has no vertical subsampling; its cosited form is 2 (left)")
-        lay, out_lay = CHROMAS[chroma], CHROMAS[out_chroma]
-        if i420 is not None:
-            h, w = (int(v) for v in i420)
-            if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != frame_bytes(h, w, depth, lay):
-                raise ValueError(f"{layout_name(lay)} frames of {h} x {w} are [N, {frame_bytes(h, w, depth, lay)}] uint8, "
-                                 f"got {frames.dtype} {tuple(frames.shape)}")
-            u8, N, c = True, int(frames.shape[0]), 3
+        gathered from `frames` into a unit-sized fp32 clip batch on the unit's stream and its result is quantised there; nothing is gathered
+        or converted on the host.  The two sides differ in one gather and one quantiser each, chosen once:
+            packed           savsr_video_gather_u8 / _f32                        savsr_video_quantize_u8
+            planar YUV       savsr_video_gather_yuvs: any layout, depth,          savsr_video_quantize_yuvs
+                             colour space and siting -> fp32 planar RGB
+            luma-only        savsr_video_gather_luma: the Y plane of YUV or       savsr_video_quantize_luma: into the Y plane of the
+            (spec.luma)      grey-scale frames, c = 1                             output frames, or of [n, H, W, 1] uint8
+        On the luma-only path the U and V planes of planar output frames never pass the network: `_resample_chroma` fills them first, on
+        the caller's stream (savsr_amd/yuv.py "Luma-only checkpoints" is the specification).
+        ensemble=True: frame i is the self-ensemble of window i (`_ensemble`, gathered by savsr_ensemble_gather_*).  Planar frames are
+        converted once to fp32 (the same gather with the identity list) and take the fp32 path; the merge quantises packed uint8 itself,
+        every other quantiser runs after the fp32 merge.  Chroma never enters the ensemble of a luma-only network."""
+        if spec is None:
+            spec = video_spec(self.nch)
+        elif not isinstance(spec, VideoSpec):
+            raise ValueError(f"spec must be a savsr_amd.video.VideoSpec (video.video_spec builds one), got {type(spec).__name__}")
+        src, dst, kind, luma = spec.inp, spec.out, spec.out_kind, spec.luma
+        if src.planar:
+            h, w = spec.size
+            fb = src.frame_bytes(h, w)
+            if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != fb:
+                raise ValueError(f"{layout_name(src.layout)} frames of {h} x {w} are [N, {fb}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+            u8, N, c = True, int(frames.shape[0]), 1 if luma else 3
         else:
             u8, N, c, h, w = _frames_layout(frames)
         frames = self._input(frames, torch.uint8 if u8 else torch.float32)
@@ -853,43 +842,63 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
                 raise ValueError(f"window {win}: {T} indices in [0, {N}) expected")
         H, W = get_hw(h, w, scale)
         n = len(windows)
-        if out_i420:
-            out = torch.empty(n, frame_bytes(H, W, out_depth, out_lay), device=self.dev, dtype=torch.uint8)
+        if kind == "planar":
+            out = torch.empty(n, dst.frame_bytes(H, W), device=self.dev, dtype=torch.uint8)
         else:
-            out = (torch.empty(n, H, W, c, device=self.dev, dtype=torch.uint8) if out_u8 else
+            out = (torch.empty(n, H, W, c, device=self.dev, dtype=torch.uint8) if kind == "uint8" else
                    torch.empty(n, c, H, W, device=self.dev, dtype=torch.float32))
         if n == 0:
             return out
         if T > _lib.VIDEO_MAX_SLOTS:
             raise ValueError(f"num_frame = {T}: the window gather takes at most {_lib.VIDEO_MAX_SLOTS} frames per launch")
-        if i420 is not None:
-            def gather(idx, dst, st):
-                _lib.check(self.lib.savsr_video_gather_yuvs(frames.data_ptr(), N, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), colour, depth,
-                                                            chroma, siting, dst.data_ptr(), st), "savsr_video_gather_yuvs")
+        idx_t = _lib.C.c_int32
+        if luma:
+            def gather(idx, to, st):
+                _lib.check(self.lib.savsr_video_gather_luma(frames.data_ptr(), N, fb, h, w, src.depth, (idx_t * len(idx))(*idx), len(idx), to.data_ptr(), st),
+                           "savsr_video_gather_luma")
+        elif src.planar:
+            colour, chroma, siting = _yuv_ids(src)
+
+            def gather(idx, to, st):
+                _lib.check(self.lib.savsr_video_gather_yuvs(frames.data_ptr(), N, h, w, (idx_t * len(idx))(*idx), len(idx), colour, src.depth, chroma,
+                                                            siting, to.data_ptr(), st), "savsr_video_gather_yuvs")
         else:
             fn = self.lib.savsr_video_gather_u8 if u8 else self.lib.savsr_video_gather_f32
 
-            def gather(idx, dst, st):
-                _lib.check(fn(frames.data_ptr(), N, c, h, w, (_lib.C.c_int32 * len(idx))(*idx), len(idx), dst.data_ptr(), st), "savsr_video_gather")
+            def gather(idx, to, st):
+                _lib.check(fn(frames.data_ptr(), N, c, h, w, (idx_t * len(idx))(*idx), len(idx), to.data_ptr(), st), "savsr_video_gather")
+        if luma:
+            od, ofb = (dst.depth, dst.frame_bytes(H, W)) if kind == "planar" else (8, H * W)          # (uint8: Y planes with nothing between them)
 
-        def quantize(src, dst, st):
-            for a in range(0, int(src.shape[0]), 65535):          # (the entries take 1 .. 65535 frames)
-                nb = min(65535, int(src.shape[0]) - a)
-                if out_i420:
-                    _lib.check(self.lib.savsr_video_quantize_yuvs(src[a:a + nb].data_ptr(), nb, H, W, out_colour, out_depth, out_chroma, out_siting,
-                                                                  dst[a:a + nb].data_ptr(), st), "savsr_video_quantize_yuvs")
-                else:
-                    _lib.check(self.lib.savsr_video_quantize_u8(src[a:a + nb].data_ptr(), nb, c, H, W, dst[a:a + nb].data_ptr(), st), "savsr_video_quantize_u8")
+            def quantize_frames(x, to, nb, st):
+                _lib.check(self.lib.savsr_video_quantize_luma(x.data_ptr(), nb, H, W, od, to.data_ptr(), ofb, st), "savsr_video_quantize_luma")
+        elif kind == "planar":
+            out_colour, out_chroma, out_siting = _yuv_ids(dst)
+
+            def quantize_frames(x, to, nb, st):
+                _lib.check(self.lib.savsr_video_quantize_yuvs(x.data_ptr(), nb, H, W, out_colour, dst.depth, out_chroma, out_siting, to.data_ptr(), st),
+                           "savsr_video_quantize_yuvs")
+        else:
+            def quantize_frames(x, to, nb, st):
+                _lib.check(self.lib.savsr_video_quantize_u8(x.data_ptr(), nb, c, H, W, to.data_ptr(), st), "savsr_video_quantize_u8")
+
+        def quantize(x, to, st):
+            for a in range(0, int(x.shape[0]), 65535):          # (the entries take 1 .. 65535 frames)
+                nb = min(65535, int(x.shape[0]) - a)
+                quantize_frames(x[a:a + nb], to[a:a + nb], nb, st)
+        if luma and kind == "planar" and dst.yuv:
+            self._resample_chroma(frames, windows, out, src, dst, h, w, H, W)
         if ensemble:
             st = torch.cuda.current_stream().cuda_stream
-            if i420 is not None:
-                rgb = torch.empty(N, 3, h, w, device=self.dev, dtype=torch.float32)
+            if src.planar:
+                f32 = torch.empty(N, c, h, w, device=self.dev, dtype=torch.float32)
                 for a in range(0, N, _lib.VIDEO_MAX_SLOTS):
-                    gather(list(range(a, min(N, a + _lib.VIDEO_MAX_SLOTS))), rgb[a:], st)
-                frames = rgb
-            merged = torch.empty(n, c, H, W, device=self.dev, dtype=torch.float32) if out_i420 else out
-            self._ensemble([(frames, win, tuple(scale), merged[i]) for i, win in enumerate(windows)], out_u8)
-            if out_i420:
+                    gather(list(range(a, min(N, a + _lib.VIDEO_MAX_SLOTS))), f32[a:], st)
+                frames = f32
+            fused = kind == "uint8" and not luma          # the merge quantises packed uint8 itself
+            merged = out if kind == "float" or fused else torch.empty(n, c, H, W, device=self.dev, dtype=torch.float32)
+            self._ensemble([(frames, win, tuple(scale), merged[i]) for i, win in enumerate(windows)], fused)
+            if merged is not out:
                 quantize(merged, out, st)
             return out
 
@@ -899,9 +908,9 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             st = torch.cuda.current_stream().cuda_stream
             lqb = torch.empty(nb, T, c, h, w, device=self.dev, dtype=torch.float32)
             gather([f for win in windows[i0:i1] for f in win], lqb, st)
-            o = torch.empty(nb, c, H, W, device=self.dev, dtype=torch.float32) if (out_u8 or out_i420) else out[i0:i1]
+            o = out[i0:i1] if kind == "float" else torch.empty(nb, c, H, W, device=self.dev, dtype=torch.float32)
             eng._run_unit(lqb, scale, o)
-            if out_u8 or out_i420:
+            if kind != "float":
                 quantize(o, out[i0:i1], st)
         # (SAVSR_GRAPHS=0: forward_many's eager flow, one window per unit)
         self._fan_out(video_units(n, T, self.clip_unit(h, w) if self.use_graphs else 1), h * w, run)
@@ -920,107 +929,28 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             self._luma_tables[key] = t
         return t
 
-    def forward_video_luma(self, frames: torch.Tensor, windows: List[List[int]], scale, size: Tuple[int, int], out: str = "float",
-                           ensemble: bool = False, depth: int = 8, out_depth: int = 8, chroma: str = "420", out_chroma: str = "420",
-                           siting: Optional[str] = None, out_siting: Optional[str] = None) -> torch.Tensor:
-        """The sequence path of a luma-only network (num_in_ch = 1) on planar YUV or grey-scale frames (upscale_video with
-        chroma_filter="bicubic" or pixel_format="y400"; savsr_amd/yuv.py "Luma-only checkpoints" is the specification).  frames
-        [N, frame_bytes(h, w, depth, chroma)] uint8 on the device, chroma one of yuv.CHROMAS or yuv.MONO; windows as for forward_video.
-        The Y planes of a unit's windows are gathered by savsr_video_gather_luma where forward_video's gather runs (the unit's stream; the
-        same units, clip_batch, flow and graphs) and the network's fp32 result is quantised into the Y plane of the output frames by
-        savsr_video_quantize_luma.  out: "float" -> [n, 1, H, W] fp32 and "uint8" -> [n, H, W, 1] uint8, the luma alone; "yuv" ->
-        [n, frame_bytes(H, W, out_depth, out_chroma)] uint8, whose U and V planes are resampled from the window's centre frame -- the
-        output frame's own input frame -- by savsr_video_resample_chroma on the caller's stream (out_chroma = yuv.MONO: no chroma planes).
-        ensemble=True: the Y planes are converted once to fp32 (the same gather with the identity list) and take `_ensemble`'s fp32 path;
-        chroma never enters the ensemble."""
-        from .yuv import MONO
-        if self.nch != 1:
-            raise ValueError(f"the luma path serves num_in_ch = 1 networks, this one has num_in_ch = {self.nch}")
-        if out not in ("float", "uint8", "yuv"):
-            raise ValueError(f"out = {out!r}: 'float', 'uint8' or 'yuv'")
-        for what, d in (("depth", depth), ("out_depth", out_depth)):
-            if d not in (8, 10, 12):
-                raise ValueError(f"{what} = {d!r}: 8, 10 or 12")
-        for what, lay_ in (("chroma", chroma), ("out_chroma", out_chroma)):
-            if lay_ != MONO and lay_ not in CHROMAS:
-                raise ValueError(f"{what} = {lay_!r}: one of {', '.join(CHROMAS)} or {MONO}")
-        if out == "yuv" and chroma == MONO and out_chroma != MONO:
-            raise ValueError("grey-scale frames have no chroma planes to resample")
-        h, w = (int(v) for v in size)
-        fb = frame_bytes(h, w, depth, chroma)
-        if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != fb:
-            raise ValueError(f"frames of {h} x {w} are [N, {fb}] uint8, got {frames.dtype} {tuple(frames.shape)}")
-        frames = self._input(frames, torch.uint8)
-        N, T = int(frames.shape[0]), self.cfg["num_frame"]
-        for win in windows:
-            if len(win) != T or min(win) < 0 or max(win) >= N:
-                raise ValueError(f"window {win}: {T} indices in [0, {N}) expected")
-        H, W = get_hw(h, w, scale)
-        n = len(windows)
-        if out == "yuv":
-            ofb, od = frame_bytes(H, W, out_depth, out_chroma), out_depth
-            res = torch.empty(n, ofb, device=self.dev, dtype=torch.uint8)
-        elif out == "uint8":
-            ofb, od = H * W, 8
-            res = torch.empty(n, H, W, 1, device=self.dev, dtype=torch.uint8)
-        else:
-            res = torch.empty(n, 1, H, W, device=self.dev, dtype=torch.float32)
-        if n == 0:
-            return res
-        if T > _lib.VIDEO_MAX_SLOTS:
-            raise ValueError(f"num_frame = {T}: the window gather takes at most {_lib.VIDEO_MAX_SLOTS} frames per launch")
-
-        def gather(idx, dst, st):
-            _lib.check(self.lib.savsr_video_gather_luma(frames.data_ptr(), N, fb, h, w, depth, (_lib.C.c_int32 * len(idx))(*idx), len(idx),
-                                                        dst.data_ptr(), st), "savsr_video_gather_luma")
-
-        def quantize(src, dst, st):
-            for a in range(0, int(src.shape[0]), 65535):          # (the entry takes 1 .. 65535 frames)
-                nb = min(65535, int(src.shape[0]) - a)
-                _lib.check(self.lib.savsr_video_quantize_luma(src[a:a + nb].data_ptr(), nb, H, W, od, dst[a:a + nb].data_ptr(), ofb, st),
-                           "savsr_video_quantize_luma")
-        if out == "yuv" and out_chroma != MONO:
-            # U and V of output frame i from its own input frame, the window's centre: runs of consecutive centres share a launch
-            (ym, ys, wy, ty), (xm, xs, wx, tx) = self._chroma_tables(h, w, H, W, chroma, out_chroma, siting, out_siting)
-            from .yuv import chroma_hw
-            (ch, cw), (cH, cW) = chroma_hw(h, w, chroma), chroma_hw(H, W, out_chroma)
-            si, so = (1 if depth == 8 else 2), (1 if out_depth == 8 else 2)
-            st = torch.cuda.current_stream().cuda_stream
-            centres = [win[T // 2] for win in windows]
-            a = 0
-            while a < n:
-                b = a + 1
-                while b < n and centres[b] == centres[b - 1] + 1 and b - a < 65535:
-                    b += 1
-                for plane in range(2):
-                    _lib.check(self.lib.savsr_video_resample_chroma(
-                        frames[centres[a]:].data_ptr(), b - a, fb, (h * w + plane * ch * cw) * si, ch, cw, depth, res[a:].data_ptr(), ofb,
-                        (H * W + plane * cH * cW) * so, cH, cW, out_depth, ym.data_ptr(), ys.data_ptr(), wy.data_ptr(), ty, xm.data_ptr(),
-                        xs.data_ptr(), wx.data_ptr(), tx, st), "savsr_video_resample_chroma")
-                a = b
-        if ensemble:
-            st = torch.cuda.current_stream().cuda_stream
-            luma = torch.empty(N, 1, h, w, device=self.dev, dtype=torch.float32)
-            for a in range(0, N, _lib.VIDEO_MAX_SLOTS):
-                gather(list(range(a, min(N, a + _lib.VIDEO_MAX_SLOTS))), luma[a:], st)
-            merged = res if out == "float" else torch.empty(n, 1, H, W, device=self.dev, dtype=torch.float32)
-            self._ensemble([(luma, win, tuple(scale), merged[i]) for i, win in enumerate(windows)], False)
-            if out != "float":
-                quantize(merged, res, st)
-            return res
-
-        def run(eng: "HipEngine", unit: Tuple[int, int]):
-            i0, i1 = unit
-            nb = i1 - i0
-            st = torch.cuda.current_stream().cuda_stream
-            lqb = torch.empty(nb, T, 1, h, w, device=self.dev, dtype=torch.float32)
-            gather([f for win in windows[i0:i1] for f in win], lqb, st)
-            o = res[i0:i1] if out == "float" else torch.empty(nb, 1, H, W, device=self.dev, dtype=torch.float32)
-            eng._run_unit(lqb, scale, o)
-            if out != "float":
-                quantize(o, res[i0:i1], st)
-        self._fan_out(video_units(n, T, self.clip_unit(h, w) if self.use_graphs else 1), h * w, run)
-        return res
+    def _resample_chroma(self, frames: torch.Tensor, windows: List[List[int]], out: torch.Tensor, src, dst, h: int, w: int, H: int, W: int) -> None:
+        """The U and V planes of the luma-only path's output frames, on the caller's stream: output frame i takes them from its own input
+        frame, the centre of window i, resampled to the output's layout and depth at the network's scale (savsr_video_resample_chroma with
+        `_chroma_tables`); runs of consecutive centres share a launch, one per plane."""
+        T, n = self.cfg["num_frame"], len(windows)
+        (ym, ys, wy, ty), (xm, xs, wx, tx) = self._chroma_tables(h, w, H, W, src.layout, dst.layout, src.siting, dst.siting)
+        (ch, cw), (cH, cW) = chroma_hw(h, w, src.layout), chroma_hw(H, W, dst.layout)
+        fb, ofb = src.frame_bytes(h, w), dst.frame_bytes(H, W)
+        si, so = (1 if src.depth == 8 else 2), (1 if dst.depth == 8 else 2)
+        st = torch.cuda.current_stream().cuda_stream
+        centres = [win[T // 2] for win in windows]
+        a = 0
+        while a < n:
+            b = a + 1
+            while b < n and centres[b] == centres[b - 1] + 1 and b - a < 65535:
+                b += 1
+            for plane in range(2):
+                _lib.check(self.lib.savsr_video_resample_chroma(
+                    frames[centres[a]:].data_ptr(), b - a, fb, (h * w + plane * ch * cw) * si, ch, cw, src.depth, out[a:].data_ptr(), ofb,
+                    (H * W + plane * cH * cW) * so, cH, cW, dst.depth, ym.data_ptr(), ys.data_ptr(), wy.data_ptr(), ty, xm.data_ptr(),
+                    xs.data_ptr(), wx.data_ptr(), tx, st), "savsr_video_resample_chroma")
+            a = b
 
     def forward(self, lq: torch.Tensor, scale, taps: Optional[dict] = None, ensemble: bool = False) -> torch.Tensor:
         """lq: [b, T, c, h, w] -> [b, c, H, W], c = num_in_ch (savsr_arch.py:692-742).  ensemble=True: every clip is the self-ensemble of its
@@ -1125,6 +1055,12 @@ def many_units(clips, clip_unit, clip_batch: int) -> List[List[int]]:
 def video_units(n: int, T: int, cb: int) -> List[Tuple[int, int]]:
     """`forward_video`'s launch units: balanced ranges of at most `cb` consecutive windows of T frames that fit one gather launch."""
     return balanced_units(n, max(1, min(cb, _lib.VIDEO_MAX_SLOTS // T)))
+
+
+def _yuv_ids(side) -> Tuple[int, int, int]:
+    """(colour space, chroma layout, siting) of a planar YUV side (video.Side) as the C ABI numbers them: the positions in yuv.COLOURS and
+    yuv.CHROMAS; the siting's position in yuv.SITINGS plus one, 0 = not modelled."""
+    return COLOURS.index(side.colour), CHROMAS.index(side.layout), 0 if side.siting is None else SITINGS.index(side.siting) + 1
 
 
 def _frames_layout(frames: torch.Tensor) -> Tuple[bool, int, int, int, int]:

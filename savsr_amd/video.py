@@ -3,13 +3,17 @@
 Output frame i is what the reference pipeline gives for it: the frame's window by generate_frame_indices with the chosen padding
 (lbasicsr/data/data_util.py:63-112, `harness.window_indices`), then SAVSR.forward on that window; with out="uint8", tensor2img's
 clamp / x255 / round half to even (lbasicsr/utils/img_util.py:66-90) without the BGR swap.  The frames stay on the device: the
-windows are gathered there (savsr_video_gather_u8 / _f32) and the uint8 result is quantised there (savsr_video_quantize_u8), see
-HipEngine.forward_video.  pixel_format="i420" / out="i420": planar YUV 4:2:0 frames in / out (savsr_amd/yuv.py is the format and its
-numerics), converted on the device on either side of the network (savsr_video_gather_i420 / savsr_video_quantize_i420).  depth /
-out_depth = 10, 12: the frames hold little-endian 16-bit samples ([N, 2 * i420_bytes(h, w)] uint8, Y4M's C420p10 / C420p12;
-savsr_video_gather_yuv420_16 / savsr_video_quantize_yuv420_16), limited range only.  pixel_format / out = "i422", "i444": the 4:2:2 and
-4:4:4 layouts of the same planes ([N, yuv.frame_bytes(h, w, depth, chroma)] uint8), with everything above applying to them as well; the
-two sides are independent.  siting / out_siting: the chroma siting of the YUV input / output (yuv.SITINGS; linear chroma reconstruction in,
+windows are gathered there and the result is quantised there, by one path for every kind of frame, HipEngine.forward_video.
+
+What the frames on either side of the network are -- pixel_format / out, size, depth / out_depth, colour / out_colour, siting /
+out_siting, chroma_filter and the network's num_in_ch -- is one value, a `VideoSpec`: `video_spec` checks the arguments, once, in a fixed
+order, and everything behind it (upscale_video, VideoUpscaler, the cut detector, the engine) reads the spec and checks nothing again.  It
+holds names only; the integer ids of the C ABI are computed beside the calls that take them.
+pixel_format="i420" / out="i420": planar YUV 4:2:0 frames in / out (savsr_amd/yuv.py is the format and its numerics), converted on the
+device on either side of the network.  depth / out_depth = 10, 12: the frames hold little-endian 16-bit samples
+([N, 2 * i420_bytes(h, w)] uint8, Y4M's C420p10 / C420p12), limited range only.  pixel_format / out = "i422", "i444": the 4:2:2 and 4:4:4
+layouts of the same planes ([N, yuv.frame_bytes(h, w, depth, chroma)] uint8), with everything above applying to them as well; the two
+sides are independent.  siting / out_siting: the chroma siting of the YUV input / output (yuv.SITINGS; linear chroma reconstruction in,
 cosited filters out; None = not modelled: nearest up, box down).  Every YUV side goes through one entry, savsr_video_gather_yuvs /
 savsr_video_quantize_yuvs.
 
@@ -21,18 +25,19 @@ chroma_filter="bicubic" with a num_in_ch = 1 network (a luma-only checkpoint): Y
 through the network (savsr_video_gather_luma / savsr_video_quantize_luma) and every output frame's U and V are resampled from its own
 input frame at the network's scale (savsr_video_resample_chroma; savsr_amd/yuv.py "Luma-only checkpoints" is the specification).
 pixel_format / out = "y400": grey-scale frames, the Y plane alone (Y4M's Cmono), for such a network; it needs no chroma_filter.
-chroma_filter=None runs exactly the lines it ran before the argument existed.
+chroma_filter=None refuses what it refused before the argument existed.
 
 Every argument is checked here, on the host, before anything is enqueued on the GPU.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
 from .harness import window_indices
-from .yuv import (CHROMA_OF, CHROMAS, LUMA_FORMAT, MONO, SITINGS, check_chroma_filter, check_colour, check_depth, check_depth_colour, check_siting, frame_bytes,
+from .yuv import (CHROMA_OF, CHROMAS, LUMA_FORMAT, MONO, check_chroma_filter, check_colour, check_depth, check_depth_colour, check_siting, frame_bytes,
                   i420_bytes, layout_name)
 
 PADDING_MODES = ("replicate", "reflection", "reflection_circle", "circle")
@@ -245,6 +250,83 @@ def luma_mode(nch: int, chroma_filter: Optional[str], pixel_format: str, out: st
     return True
 
 
+@dataclass(frozen=True)
+class Side:
+    """The frames on one side of the network, by name: the pixel format / output kind ("rgb", "float", "uint8", "i420", "i422", "i444",
+    "y400"), the layout of its planes ("420", "422", "444", yuv.MONO; None for packed frames), the bit depth, the colour space and the
+    chroma siting (None: not modelled).  A record without checks of its own: `video_spec` is what makes a checked pair of them."""
+    fmt: str
+    layout: Optional[str]
+    depth: int
+    colour: str
+    siting: Optional[str]
+
+    @property
+    def yuv(self) -> bool:
+        """Planar YUV frames (i420, i422, i444): the side has chroma planes, a colour space and a siting."""
+        return self.fmt in YUV_FORMATS
+
+    @property
+    def planar(self) -> bool:
+        """Frames of planar samples with a bit depth, [N, frame_bytes] uint8: YUV or grey-scale."""
+        return self.fmt in SAMPLE_FORMATS
+
+    def frame_bytes(self, h: int, w: int) -> int:
+        return frame_bytes(h, w, self.depth, self.layout)
+
+
+def _resolve(nch: int, out: str, pixel_format: str, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter):
+    """The fields of the VideoSpec of these arguments, after every check of them, in the order and the words the checks always had."""
+    check_out(out, nch, chroma_filter)
+    size = check_pixel_format(pixel_format, size)
+    check_colours(colour, out_colour, pixel_format, out)
+    d, od = check_depths(depth, out_depth, pixel_format, out, colour, out_colour)
+    check_sitings(siting, out_siting, pixel_format, out)
+    luma = luma_mode(nch, chroma_filter, pixel_format, out, colour, out_colour)
+    return (nch, Side(pixel_format, layout_of(pixel_format) if size else None, d, colour, siting),
+            Side(out, layout_of(out) if out in SAMPLE_FORMATS else None, od, colour if out_colour is None else out_colour, out_siting),
+            size, luma, chroma_filter)
+
+
+@dataclass(frozen=True)
+class VideoSpec:
+    """Everything about the frames of a video call, on both sides of the network, checked: what `upscale_video`, `VideoUpscaler`, the
+    cut detector and `HipEngine.forward_video` read.  Names only; the ids of the C ABI are computed next to the calls that take them.
+    Built by `video_spec`; building one any other way runs the same checks on its fields, so there is no invalid VideoSpec."""
+    nch: int                                  # the network's num_in_ch: the channels of packed frames
+    inp: Side
+    out: Side
+    size: Optional[Tuple[int, int]]           # (h, w) of planar input frames; None: packed ones, which carry it in their shape
+    luma: bool                                # the luma-only path (`luma_mode`)
+    chroma_filter: Optional[str]
+
+    def __post_init__(self):
+        fields = (self.nch, self.inp, self.out, self.size, self.luma, self.chroma_filter)
+        if not isinstance(self.inp, Side) or not isinstance(self.out, Side) or _resolve(
+                self.nch, self.out.fmt, self.inp.fmt, self.size, self.inp.colour, self.out.colour if self.out.yuv else None, self.inp.depth,
+                self.out.depth if self.out.planar else None, self.inp.siting, self.out.siting, self.chroma_filter) != fields:
+            raise ValueError(f"not the VideoSpec of its own arguments (video_spec builds one): {fields}")
+
+    @property
+    def out_kind(self) -> str:
+        """What the engine returns: "float" [n, c, H, W], "uint8" [n, H, W, c] or "planar" [n, out.frame_bytes(H, W)] uint8."""
+        return "planar" if self.out.planar else self.out.fmt
+
+    def frames_hw(self, frames: torch.Tensor) -> Tuple[int, int, int]:
+        """(N, h, w) of a video tensor of the input side (`i420_layout` / `frame_layout`: refuses anything else)."""
+        if self.size:
+            return (i420_layout(frames, self.size, self.nch, self.inp.depth, self.inp.layout, self.luma),) + self.size
+        return frame_layout(frames, self.nch)
+
+
+def video_spec(nch: int, out: str = "float", pixel_format: str = "rgb", size=None, colour: str = "bt601", out_colour: Optional[str] = None,
+               depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
+               chroma_filter: Optional[str] = None) -> VideoSpec:
+    """The VideoSpec of the format arguments of `upscale_video` / `VideoUpscaler` for a num_in_ch = nch network; refuses, by name, what
+    they refuse."""
+    return VideoSpec(*_resolve(nch, out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter))
+
+
 def _is_auto(cuts) -> bool:
     return isinstance(cuts, str) and cuts == "auto"
 
@@ -259,17 +341,19 @@ def check_cuts_arg(cuts) -> None:
     check_cuts(cuts, None)
 
 
-def _sad_layout(frames: torch.Tensor, i420: Optional[Tuple[int, int]], depth: int = 8, chroma: str = "420") -> Tuple[int, int, int, int]:
-    """(N, c, h, w) of the frames the detector compares (c = 0: YUV); no network here, so any c in 1 .. 3 and any h, w >= 1."""
+def _sad_layout(frames: torch.Tensor, side: Side, size: Optional[Tuple[int, int]]) -> Tuple[int, int, int, int]:
+    """(N, c, h, w) of the frames the detector compares (c = 0: planar ones, `size` = their (h, w)); no network here, so any c in 1 .. 3
+    and any h, w >= 1."""
+    depth, chroma = side.depth, side.layout
     if not isinstance(frames, torch.Tensor):
         raise TypeError(f"frames must be a torch.Tensor, got {type(frames).__name__}")
-    if depth != 8 and not i420:
+    if depth != 8 and not size:
         raise ValueError(f"depth = {depth} goes with pixel_format = {_YUV_LIST}: it is the bit depth of YUV input (RGB frames carry theirs in their dtype)")
-    if i420:
-        h, w = i420
-        if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != frame_bytes(h, w, depth, chroma):
+    if size:
+        h, w = size
+        if frames.dtype != torch.uint8 or frames.dim() != 2 or int(frames.shape[1]) != side.frame_bytes(h, w):
             raise ValueError(f"{'' if depth == 8 else f'{depth}-bit '}{layout_name(chroma)} frames of {h} x {w} are "
-                             f"[N, {frame_bytes(h, w, depth, chroma)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
+                             f"[N, {side.frame_bytes(h, w)}] uint8, got {frames.dtype} {tuple(frames.shape)}")
         check_sample_alignment(frames, depth, chroma)
         n, c = int(frames.shape[0]), 0
     else:
@@ -292,34 +376,41 @@ def _sad_layout(frames: torch.Tensor, i420: Optional[Tuple[int, int]], depth: in
     return n, c, h, w
 
 
-def _pair_sad_device(frames: torch.Tensor, i420: Optional[Tuple[int, int]], depth: int = 8, chroma: str = "420") -> torch.Tensor:
-    """savsr_video_pair_sad_* on frames already on the GPU: int64 [N - 1] there, enqueued on the current stream (no sync)."""
+def _pair_sad_device(frames: torch.Tensor, side: Side, size: Optional[Tuple[int, int]]) -> torch.Tensor:
+    """savsr_video_pair_sad_* on frames of the input side already on the GPU: int64 [N - 1] there, enqueued on the current stream (no sync)."""
     from . import _lib
-    n, c, h, w = _sad_layout(frames, i420, depth, chroma)
+    n, c, h, w = _sad_layout(frames, side, size)
+    depth, chroma = side.depth, side.layout
     lib = _lib.load()
     u8 = frames.dtype == torch.uint8
     frames = frames.contiguous() if u8 else frames.to(torch.float32).contiguous()
     with torch.cuda.device(frames.device):
         sad = torch.empty(n - 1, dtype=torch.int64, device=frames.device)
         st = torch.cuda.current_stream().cuda_stream
-        if i420 and chroma == MONO:
+        if size and chroma == MONO:
             # grey-scale frames are [N, h, w, 1] frames of their samples' 8 most significant bits (host work only: no kernel of their own)
             if depth != 8:
                 words = frames.view(torch.int16).to(torch.int32) & 0xFFFF
                 frames = (words.clamp_(max=(1 << depth) - 1) >> (depth - 8)).to(torch.uint8)
             _lib.check(lib.savsr_video_pair_sad_u8(frames.data_ptr(), n, 1, h, w, sad.data_ptr(), st), "savsr_video_pair_sad_u8")
-        elif i420 and chroma != "420":
+        elif size and chroma != "420":
             _lib.check(lib.savsr_video_pair_sad_yuvp(frames.data_ptr(), n, h, w, depth, CHROMAS.index(chroma), sad.data_ptr(), st),
                        "savsr_video_pair_sad_yuvp")
-        elif i420 and depth != 8:
+        elif size and depth != 8:
             _lib.check(lib.savsr_video_pair_sad_i420_16(frames.data_ptr(), n, h, w, depth, sad.data_ptr(), st), "savsr_video_pair_sad_i420_16")
-        elif i420:
+        elif size:
             _lib.check(lib.savsr_video_pair_sad_i420(frames.data_ptr(), n, h, w, sad.data_ptr(), st), "savsr_video_pair_sad_i420")
         elif u8:
             _lib.check(lib.savsr_video_pair_sad_u8(frames.data_ptr(), n, c, h, w, sad.data_ptr(), st), "savsr_video_pair_sad_u8")
         else:
             _lib.check(lib.savsr_video_pair_sad_f32(frames.data_ptr(), n, c, h, w, sad.data_ptr(), st), "savsr_video_pair_sad_f32")
     return sad
+
+
+def _sad_side(pixel_format: str, size, depth) -> Tuple[Side, Optional[Tuple[int, int]]]:
+    """The input side and the frame size the public detector calls name (the detector reads no colour space and no siting)."""
+    size = check_pixel_format(pixel_format, size)
+    return Side(pixel_format, layout_of(pixel_format) if size else None, check_depth(depth), "bt601", None), size
 
 
 def _sad_device(frames: torch.Tensor) -> torch.device:
@@ -337,11 +428,9 @@ def pair_sad(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: 
     pixel_format="i420", size=(h, w): [N, i420_bytes(h, w)] uint8 (the Y plane only).  depth = 10, 12 (I420 only): frames of 16-bit samples,
     [N, 2 * i420_bytes(h, w)] uint8, compared by their 8 most significant bits, so the scores keep the 8-bit scale.  pixel_format="i422" /
     "i444": frames of those layouts; the Y plane only, as for I420."""
-    i420 = check_pixel_format(pixel_format, size)
-    depth = check_depth(depth)
-    chroma = layout_of(pixel_format)
-    _sad_layout(frames, i420, depth, chroma)
-    return _pair_sad_device(_to_device(frames, _sad_device(frames)), i420, depth, chroma)
+    side, size = _sad_side(pixel_format, size, depth)
+    _sad_layout(frames, side, size)
+    return _pair_sad_device(_to_device(frames, _sad_device(frames)), side, size)
 
 
 def detect_cuts(frames: torch.Tensor, threshold=10.0, pixel_format: str = "rgb", size=None, depth: int = 8) -> List[int]:
@@ -350,9 +439,7 @@ def detect_cuts(frames: torch.Tensor, threshold=10.0, pixel_format: str = "rgb",
     scores; one device -> host copy of N - 1 integers).  The default threshold is scdet's and is not validated on real footage."""
     from .scenes import check_threshold, cuts_from_sad, sad_samples
     check_threshold(threshold)
-    i420 = check_pixel_format(pixel_format, size)
-    depth = check_depth(depth)
-    _sad_layout(frames, i420, depth, layout_of(pixel_format))
+    _sad_layout(frames, *_sad_side(pixel_format, size, depth))
     sad = pair_sad(frames, pixel_format, size, depth)
     return cuts_from_sad(sad.cpu().tolist(), sad_samples(frames.shape, pixel_format, size), threshold)
 
@@ -364,15 +451,9 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
-    check_out(out, net.cfg["num_in_ch"], chroma_filter)
-    i420 = check_pixel_format(pixel_format, size)
-    cid, ocid = check_colours(colour, out_colour, pixel_format, out)
-    d, od = check_depths(depth, out_depth, pixel_format, out, colour, out_colour)
-    sid, osid = check_sitings(siting, out_siting, pixel_format, out)
-    luma = luma_mode(net.cfg["num_in_ch"], chroma_filter, pixel_format, out, colour, out_colour)
+    spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter)
     sc = as_scale(net.scale if scale is None else scale)
-    chroma, out_chroma = layout_of(pixel_format), layout_of(out)
-    n = i420_layout(frames, i420, net.cfg["num_in_ch"], d, chroma, luma) if i420 else frame_layout(frames, net.cfg["num_in_ch"])[0]
+    n = spec.frames_hw(frames)[0]
     T = net.num_frame
     if cuts is None:
         check_length(n, T, padding)
@@ -392,17 +473,11 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         windows = [window_indices(i, n, T, padding) for i in range(n)]
     else:
         if _is_auto(cuts):
-            sad = _pair_sad_device(frames, i420, d, chroma).cpu().tolist()
+            sad = _pair_sad_device(frames, spec.inp, spec.size).cpu().tolist()
             cuts = scenes.cuts_from_sad(sad, scenes.sad_samples(frames.shape, pixel_format, size), scene_threshold)
         windows = scenes.scene_windows(n, cuts, T, padding)
-    if luma:
-        with torch.no_grad():
-            return net.engine().forward_video_luma(frames, windows, sc, i420, "yuv" if out in SAMPLE_FORMATS else out, ensemble=net.self_ensemble,
-                                                   depth=d, out_depth=od, chroma=chroma, out_chroma=out_chroma, siting=siting, out_siting=out_siting)
     with torch.no_grad():
-        return net.engine().forward_video(frames, windows, sc, out == "uint8", ensemble=net.self_ensemble, i420=i420,
-                                          out_i420=out in YUV_FORMATS, colour=cid, out_colour=ocid, depth=d, out_depth=od,
-                                          chroma=CHROMAS.index(chroma), out_chroma=CHROMAS.index(out_chroma), siting=sid, out_siting=osid)
+        return net.engine().forward_video(frames, windows, sc, spec, ensemble=net.self_ensemble)
 
 
 class VideoUpscaler:
@@ -435,7 +510,7 @@ class VideoUpscaler:
                  chroma_filter: Optional[str] = None):
         _check_net(net)
         check_padding(padding)
-        check_out(out, net.cfg["num_in_ch"], chroma_filter)
+        check_out(out, net.cfg["num_in_ch"], chroma_filter)          # (speaks before the cuts, video_spec after them: the order of refusals)
         self._plan = None                          # scenes.ScenePlan when cuts are given; None: the path without cuts, as it was
         if cuts is not None:
             from . import scenes
@@ -445,14 +520,9 @@ class VideoUpscaler:
             self._given = [] if self._auto else scenes.check_cuts(cuts, None)       # explicit cuts not reached yet
             self._prev_sad = 0                     # the last pair's score (scdet's damping term), carried from push to push
             self._plan = scenes.ScenePlan(net.num_frame, padding)
-        self.i420 = check_pixel_format(pixel_format, size)        # (h, w) of YUV chunks, None for RGB ones
-        self._chromas = (layout_of(pixel_format), layout_of(out))      # chroma layouts of the YUV input / output
-        self._fmt = pixel_format
-        self._colours = check_colours(colour, out_colour, pixel_format, out)      # colour space ids of the I420 input / output
-        self._depths = check_depths(depth, out_depth, pixel_format, out, colour, out_colour)      # bit depths of the I420 input / output
-        self._sitings = check_sitings(siting, out_siting, pixel_format, out)      # chroma siting ids of the YUV input / output
-        # the luma-only path (a num_in_ch = 1 network with chroma_filter or grey-scale frames): decided once, here
-        self._luma = luma_mode(net.cfg["num_in_ch"], chroma_filter, pixel_format, out, colour, out_colour)
+        # the frames on both sides, checked once, here; the luma-only path (`luma_mode`) is decided with them
+        self.spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter)
+        self.i420 = self.spec.size                 # (h, w) of planar chunks, None for packed ones
         self.net, self.padding, self.out = net, padding, out
         self.scale = as_scale(net.scale if scale is None else scale)
         self.ensemble = net.self_ensemble          # (read once, like the scale: every chunk runs the same flow)
@@ -484,37 +554,22 @@ class VideoUpscaler:
                 lo = min(lo, min(window_indices(i, n, self.T, self.padding)))
         return max(lo, 0)
 
-    def _forward_luma(self, windows: List[List[int]]) -> torch.Tensor:
-        """The luma-only path on the buffered frames: Y through the network, U / V from each window's centre frame, which the buffer holds."""
-        sit = [None if s == 0 else SITINGS[s - 1] for s in self._sitings]
+    def _forward(self, windows: List[List[int]]) -> torch.Tensor:
+        """The SR frames of windows into the buffered frames."""
         with torch.no_grad():
-            return self.net.engine().forward_video_luma(self._buf, windows, self.scale, self.i420, "yuv" if self.out in SAMPLE_FORMATS else self.out,
-                                                        ensemble=self.ensemble, depth=self._depths[0], out_depth=self._depths[1],
-                                                        chroma=self._chromas[0], out_chroma=self._chromas[1], siting=sit[0], out_siting=sit[1])
+            return self.net.engine().forward_video(self._buf, windows, self.scale, self.spec, ensemble=self.ensemble)
 
     def _run(self, upto: int, n_total: Optional[int]) -> torch.Tensor:
         """SR frames [done, upto); windows at the video length n_total (None: not known yet, every window needed is interior)."""
         n = n_total if n_total is not None else upto + self.half + 1
-        windows = [[j - self._base for j in window_indices(i, n, self.T, self.padding)] for i in range(self.done, upto)]
-        if self._luma:
-            self.done = upto
-            return self._forward_luma(windows)
-        with torch.no_grad():
-            res = self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble, i420=self.i420,
-                                                  out_i420=self.out in YUV_FORMATS, colour=self._colours[0], out_colour=self._colours[1],
-                                                  depth=self._depths[0], out_depth=self._depths[1], chroma=CHROMAS.index(self._chromas[0]),
-                                                  out_chroma=CHROMAS.index(self._chromas[1]), siting=self._sitings[0],
-                                                  out_siting=self._sitings[1])
+        res = self._forward([[j - self._base for j in window_indices(i, n, self.T, self.padding)] for i in range(self.done, upto)])
         self.done = upto
         return res
 
     def push(self, frames: torch.Tensor) -> torch.Tensor:
         if self._finished:
             raise RuntimeError("push() after finish()")
-        if self.i420:
-            k, (h, w) = i420_layout(frames, self.i420, self.net.cfg["num_in_ch"], self._depths[0], self._chromas[0], self._luma), self.i420
-        else:
-            k, h, w = frame_layout(frames, self.net.cfg["num_in_ch"])
+        k, h, w = self.spec.frames_hw(frames)
         shape = (frames.dtype == torch.uint8, h, w)
         if self._shape is not None and shape != self._shape:
             raise ValueError(f"chunk of {'uint8' if shape[0] else 'float'} {h} x {w} frames after {'uint8' if self._shape[0] else 'float'} "
@@ -550,23 +605,13 @@ class VideoUpscaler:
         if hi - first < 1:
             return []
         from .scenes import cuts_from_sad, sad_samples
-        sad = _pair_sad_device(self._buf[first - 1 - self._base:], self.i420, self._depths[0], self._chromas[0]).cpu().tolist()
-        new = cuts_from_sad(sad, sad_samples(self._buf.shape, self._fmt, self.i420), self._threshold, first, self._prev_sad)
+        sad = _pair_sad_device(self._buf[first - 1 - self._base:], self.spec.inp, self.i420).cpu().tolist()
+        new = cuts_from_sad(sad, sad_samples(self._buf.shape, self.spec.inp.fmt, self.i420), self._threshold, first, self._prev_sad)
         self._prev_sad = sad[-1]
         return new
 
     def _run_windows(self, windows: List[List[int]]) -> torch.Tensor:
-        if not windows:
-            return self._empty()
-        windows = [[j - self._base for j in win] for win in windows]
-        if self._luma:
-            return self._forward_luma(windows)
-        with torch.no_grad():
-            return self.net.engine().forward_video(self._buf, windows, self.scale, self.out == "uint8", ensemble=self.ensemble, i420=self.i420,
-                                                   out_i420=self.out in YUV_FORMATS, colour=self._colours[0], out_colour=self._colours[1],
-                                                   depth=self._depths[0], out_depth=self._depths[1], chroma=CHROMAS.index(self._chromas[0]),
-                                                   out_chroma=CHROMAS.index(self._chromas[1]), siting=self._sitings[0],
-                                                  out_siting=self._sitings[1])
+        return self._forward([[j - self._base for j in win] for win in windows]) if windows else self._empty()
 
     def _push_scenes(self, k: int) -> torch.Tensor:
         plan = self._plan
@@ -607,9 +652,9 @@ class VideoUpscaler:
         H, W = get_hw(h, w, self.scale)
         c = self.net.cfg["num_in_ch"]
         dev = self.net.gamma.device
-        if self.out in SAMPLE_FORMATS:
-            return torch.empty(0, frame_bytes(H, W, self._depths[1], self._chromas[1]), dtype=torch.uint8, device=dev)
-        if self.out == "uint8":
+        if self.spec.out_kind == "planar":
+            return torch.empty(0, self.spec.out.frame_bytes(H, W), dtype=torch.uint8, device=dev)
+        if self.spec.out_kind == "uint8":
             return torch.empty(0, H, W, c, dtype=torch.uint8, device=dev)
         return torch.empty(0, c, H, W, dtype=torch.float32, device=dev)
 

@@ -282,7 +282,20 @@ def test_python_refusals(net3):  # noqa: F811
         with pytest.raises(ValueError, match="out_siting = 'left' goes with out = 'i420', 'i422' or 'i444'"):
             make(frames=f, pixel_format="i420", out="uint8", out_siting="left", **kw)
     eng = net3.engine()
-    with pytest.raises(ValueError, match=r"siting = 4: 0 \(not modelled\) or 1 .. 3"):
-        eng.forward_video(f.to(DEV), [[0] * 7], SC_, i420=LR, siting=4)
-    with pytest.raises(ValueError, match=r"out_siting = 2: .* with YUV frames on that side only"):
-        eng.forward_video(f.to(DEV), [[0] * 7], SC_, i420=LR, out_siting=2)
+    # at the engine's door: what it takes is a VideoSpec, and there is none with an unknown siting or an out_siting without YUV output,
+    # through the factory or around it; anything else in its place is refused before anything is enqueued
+    import dataclasses
+    from savsr_amd.video import video_spec
+    good = video_spec(3, pixel_format="i420", size=LR, siting="left")
+    with pytest.raises(ValueError, match="siting = 'mpeg2': None or one of centre, left, topleft"):
+        eng.forward_video(f.to(DEV), [[0] * 7], SC_, video_spec(3, pixel_format="i420", size=LR, siting="mpeg2"))
+    with pytest.raises(ValueError, match="out_siting = 'left' goes with out = 'i420', 'i422' or 'i444'"):
+        eng.forward_video(f.to(DEV), [[0] * 7], SC_, video_spec(3, pixel_format="i420", size=LR, out_siting="left"))
+    with pytest.raises(ValueError, match="siting = 4: None or one of centre, left, topleft"):
+        eng.forward_video(f.to(DEV), [[0] * 7], SC_, dataclasses.replace(good, inp=dataclasses.replace(good.inp, siting=4)))
+    with pytest.raises(ValueError, match="out_siting = 'left' goes with out = 'i420', 'i422' or 'i444'"):
+        eng.forward_video(f.to(DEV), [[0] * 7], SC_, dataclasses.replace(good, out=dataclasses.replace(good.out, siting="left")))
+    for not_a_spec in (dict(pixel_format="i420", size=LR, siting=1), good.inp, 1, True):
+        with pytest.raises(ValueError, match="spec must be a savsr_amd.video.VideoSpec"):
+            eng.forward_video(f.to(DEV), [[0] * 7], SC_, not_a_spec)
+    assert eng.forward_video(f.to(DEV), [[0] * 7], SC_, good).shape == (1, 3) + get_hw(*LR, SC_)          # (and takes the one that is)
