@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 41
+#define SAVSR_ABI_VERSION 42
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -607,6 +607,30 @@ int savsr_video_resample_chroma(const uint8_t* src, int n, int64_t src_frame_byt
                                 uint8_t* dst, int64_t dst_frame_bytes, int64_t dst_plane_offset, int cH, int cW, int depth_out,
                                 const int32_t* ymin, const int32_t* ysize, const float* wy, int taps_y, const int32_t* xmin,
                                 const int32_t* xsize, const float* wx, int taps_x, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 42) The active-picture detector's line sums (active.hip; savsr_amd.line_sums / detect_active_area, upscale_video(crop="auto"),
+ * --crop auto of python -m savsr_amd.upscale): per matrix of a batch the sum of the 8-bit samples of every row and
+ * of every column, exact integers from one read of the samples (savsr_amd/active.py `line_sums` restates them; cropdetect's rule runs on
+ * the host, `active_rect`).  row_sums [n][rows] and col_sums [n][cols] are 32-bit cells, zeroed by the call on the same stream.  The
+ * entries only enqueue, allocate nothing, do not synchronise and are capturable.  Refused before the device is touched, with
+ * savsr_last_error() naming the reason: SAVSR_E_ARG for a null pointer, n, rows or a width below 1, a line longer than 4194240 samples, a
+ * frame stride smaller than the matrix, a depth other than 10 / 12 (_u16); SAVSR_E_ALIGN for 16-bit samples behind an odd pointer or stride
+ * and floats behind a pointer that is not 4-byte aligned.  16-byte loads when the base pointer, the frame stride and a row's bytes are
+ * multiples of 16, a sample per access otherwise (any pointer, stride and size).
+ * savsr_video_line_sums_u8:  n matrices of rows x row_bytes bytes, frame_bytes apart: packed [n][h][w][c] uint8 frames as h x (w * c) (the
+ *                         caller folds the c byte columns of a pixel into its column: `line_sums` on [N, h, w, c] frames) and the Y plane
+ *                         of 8-bit planar frames as h x w at the start of a frame (`line_sums` with pixel_format= and size=).
+ * savsr_video_line_sums_u16: n matrices of rows x cols little-endian 16-bit samples, frame_bytes apart: the Y plane of 10- / 12-bit planar
+ *                         frames, every sample as min(s, 2^depth - 1) >> (depth - 8) (`line_sums` with depth=).
+ * savsr_video_line_sums_f32: n_mats contiguous matrices of rows x cols fp32, the planes of [N][c][h][w] frames: every value quantised by
+ *                         savsr_video_quantize_u8's rule first (clamp to [0, 1], x 255.0f, rintf, NaN -> 0); the caller sums the c planes
+ *                         of a frame (`line_sums` on float frames). */
+int savsr_video_line_sums_u8(const uint8_t* frames, int n, int64_t frame_bytes, int rows, int row_bytes, uint32_t* row_sums, uint32_t* col_sums,
+                             void* stream);
+int savsr_video_line_sums_u16(const uint8_t* frames, int n, int64_t frame_bytes, int rows, int cols, int depth, uint32_t* row_sums,
+                              uint32_t* col_sums, void* stream);
+int savsr_video_line_sums_f32(const float* mats, int n_mats, int rows, int cols, uint32_t* row_sums, uint32_t* col_sums, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 33) Geometric self-ensemble (ensemble.hip; SAVSR.set_self_ensemble).  Variant k = 0 .. 7: fw = k & 1 flips

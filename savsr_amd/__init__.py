@@ -5,6 +5,6 @@ from .archs.savsr_arch import SAVSR  # noqa: F401
 from . import datasets as _datasets, models as _models  # noqa: F401,E402  (register ASVideoTestDataset / ASVSRModel)
 from .datasets import build_dataset  # noqa: F401,E402
 from .models import build_model  # noqa: F401,E402
-from .video import VideoUpscaler, detect_cuts, pair_sad  # noqa: F401,E402
+from .video import VideoUpscaler, detect_active_area, detect_cuts, line_sums, pair_sad  # noqa: F401,E402
 
 __version__ = "0.1.0"

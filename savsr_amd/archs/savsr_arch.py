@@ -280,7 +280,7 @@ class SAVSR(nn.Module):
     def upscale_video(self, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
                       size=None, cuts=None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None, depth: int = 8,
                       out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
-                      chroma_filter: Optional[str] = None) -> torch.Tensor:
+                      chroma_filter: Optional[str] = None, crop=None, crop_limit=24, bars: str = "keep") -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -321,11 +321,19 @@ class SAVSR(nn.Module):
         the GPU: savsr_amd.detect_cuts with scene_threshold, in per cent of the largest possible frame change; the default is ffmpeg
         scdet's and is not validated on real footage).  Windows stop at cuts: the result is, bit for bit, upscale_video on every scene
         alone, concatenated, a scene too short for `padding` taking "replicate" (savsr_amd/scenes.py); with cuts only N >= 1 is required.
+        crop: None, a rect (y0, x0, ah, aw) or "auto", for letterboxed, pillarboxed and window-boxed video.  The frames are cropped to the
+        rect before anything else looks at them: the result is, bit for bit, upscale_video on the video cropped by hand
+        (savsr_amd.active.crop_frames) with every other argument the same, so the bars cost no network time and do not move the network's
+        global pools.  A rect lies inside the frame with ah, aw >= 2 and sits on the input layout's chroma block (an off-block rect is
+        refused with the aligned one it could have been).  "auto": savsr_amd.detect_active_area on the whole video with crop_limit, the
+        largest mean of a black line on the 8-bit scale (ffmpeg cropdetect's rule and default; not validated on real footage).
+        bars="keep" (the default) returns full-size frames, the picture at savsr_amd.active.place's corner in nominal black
+        (active.insert_frames); bars="drop" returns the picture alone, get_hw(ah, aw, scale).  None (the default) runs what ran before.
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
         return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold, colour, out_colour, depth, out_depth,
-                             siting, out_siting, chroma_filter)
+                             siting, out_siting, chroma_filter, crop, crop_limit, bars)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

@@ -10,6 +10,7 @@
     python -m savsr_amd.upscale -i in8.y4m -o out10.y4m --scale 4 --checkpoint <net.pth> --out-depth 10
     ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o - --scale 4 --checkpoint <net.pth> --siting auto --out-siting same | ffmpeg -i - out.mp4
     python -m savsr_amd.upscale -i in.y4m -o out.y4m --scale 4 --opt <luma_test.yml> --chroma-filter bicubic
+    python -m savsr_amd.upscale -i letterboxed_sd.y4m -o hd.y4m --scale 4 --checkpoint <net.pth> --crop auto --colour auto --out-colour auto
     ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out444p10.y4m --scale 4 --checkpoint <net.pth> --out-chroma 444
 
 PNG folder: frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on
@@ -56,6 +57,13 @@ has always done.  A grey-scale input (Cmono, Cmono10, Cmono12) needs such a chec
 --cuts: edited footage.  Windows stop at scene cuts (every scene is upscaled as a video of its own, savsr_amd/scenes.py): auto finds
 them on the GPU as the frames arrive (--scene-threshold, per cent of the largest possible frame change; ffmpeg scdet's rule and default,
 not validated on real footage), K,K,... or @FILE (one frame index per line) gives them.  --cuts-out FILE writes the cuts used, one per line.
+
+--crop: letterboxed, pillarboxed and window-boxed footage.  The frames are cropped to the active picture before anything else sees
+them (savsr_amd/active.py), so the bars cost no network time and stay out of the network's global pools.  auto makes a first pass over a
+.y4m file or a PNG folder in --chunk-sized pieces (line sums on the GPU, a running maximum there), applies ffmpeg cropdetect's rule with
+--crop-limit (the largest mean of a black line on the 8-bit scale; cropdetect's default, 24, not validated on real footage) and reports
+the rect on stderr; on stdin there is no second pass, so give Y0,X0,H,W there.  --bars keep (the default) writes full-size frames with
+the picture in nominal black; --bars drop writes the picture alone, and a Y4M output then carries the picture's size.
 
 It ends with one line: frames, seconds, frames/s (on stderr when the video goes to stdout); with --cuts, the scene count as well; with
 --colour / --out-colour, the two colour spaces.
@@ -174,7 +182,29 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--scene-threshold", type=float, default=10.0, metavar="X",
                    help="--cuts auto: a cut is a frame change of at least X per cent of the largest possible one (default 10, ffmpeg scdet's)")
     p.add_argument("--cuts-out", default=None, metavar="FILE", help="write the cut list actually used, one frame index per line")
+    p.add_argument("--crop", default=None, metavar="auto|Y0,X0,H,W",
+                   help="upscale the active picture alone: auto = found on the GPU in a first pass over the input (a file or a folder), or the "
+                        "rect's top-left corner and size in LR pixels")
+    p.add_argument("--crop-limit", type=float, default=None, metavar="X",
+                   help="--crop auto: a row or column whose mean stays at or below X (8-bit scale) in every frame is bar (default 24, ffmpeg "
+                        "cropdetect's; not validated on real footage)")
+    p.add_argument("--bars", default=None, choices=["keep", "drop"],
+                   help="--crop: keep = full-size output, the picture in nominal black (default); drop = the picture alone")
     return p
+
+
+def parse_crop(text: str):
+    """--crop: "auto" or "Y0,X0,H,W" -> "auto" or a rect of ints (the frame size is checked once it is known)."""
+    from .active import check_rect
+    if text == "auto":
+        return text
+    try:
+        rect = tuple(int(t.strip()) for t in text.split(","))
+    except ValueError:
+        raise ValueError(f"auto or Y0,X0,H,W with integers, got {text!r}") from None
+    if len(rect) != 4:
+        raise ValueError(f"auto or Y0,X0,H,W, got {text!r}")
+    return check_rect(rect, None, None, None)
 
 
 def parse_cuts(text: str):
@@ -220,6 +250,22 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error(f"--cuts / --scene-threshold: {e}")
     elif a.cuts_out is not None:
         p.error("--cuts-out goes with --cuts")
+    if a.crop is not None:
+        from .active import DEFAULT_LIMIT, check_limit
+        try:
+            a.crop = parse_crop(a.crop)
+            check_limit(DEFAULT_LIMIT if a.crop_limit is None else a.crop_limit)
+        except ValueError as e:
+            p.error(f"--crop / --crop-limit: {e}")
+        if a.crop_limit is not None and a.crop != "auto":
+            p.error("--crop-limit goes with --crop auto (an explicit rect needs no detector)")
+        if a.crop == "auto" and a.input == "-":
+            p.error("--crop auto needs a first pass over the input, which stdin does not allow: give the rect, --crop Y0,X0,H,W "
+                    "(ffmpeg cropdetect or savsr_amd.detect_active_area find it)")
+    elif a.crop_limit is not None or a.bars is not None:
+        p.error("--crop-limit and --bars go with --crop")
+    a.crop_limit = 24 if a.crop_limit is None else a.crop_limit
+    a.bars = a.bars or "keep"
     a.y4m_in, a.y4m_out = is_y4m(a.input), is_y4m(a.output)
     if a.fps is not None and (a.y4m_in or not a.y4m_out):
         p.error("--fps goes with a PNG folder in and Y4M out (a Y4M input carries its frame rate, PNGs have none)")
@@ -376,6 +422,45 @@ class PngSink:
         self.pool.shutdown()
 
 
+def written_lr(h, w, rect, bars: str):
+    """The LR size behind the frames actually written: the rect's with --bars drop, the frame's otherwise.  The output's size, its pixel
+    aspect and its `auto` colour space follow from it."""
+    return (h, w) if rect is None or bars == "keep" else (rect[2], rect[3])
+
+
+def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev):
+    """--crop auto's first pass: savsr_amd.line_sums over the input in --chunk-sized pieces with a running maximum on the device, then
+    cropdetect's rule and the alignment to the input layout's chroma block.  chunks: the PNG folder's chunk iterator; None: the .y4m file
+    named by --input, read through a reader of its own."""
+    import torch
+
+    from . import active
+    from .video import layout_of, line_sums
+    from .y4m import Y4MReader
+    from .yuv import CHROMAS
+    top = None
+    f = None
+    try:
+        if chunks is None:
+            f = open(a.input, "rb")
+            chunks = (torch.from_numpy(c) for c in Y4MReader(f, high_depth=True, layouts=CHROMAS, mono=True).chunks(a.chunk))
+        with torch.cuda.device(dev):
+            for chunk in chunks:
+                c = 1 if size else int(chunk.shape[3])
+                h, w = size if size else (int(chunk.shape[1]), int(chunk.shape[2]))
+                rows, cols = line_sums(chunk.to(dev), fmt_in, size, depth)
+                now = torch.cat([rows.amax(0), cols.amax(0)])
+                top = now if top is None else torch.maximum(top, now)
+    finally:
+        if f is not None:
+            f.close()
+    if top is None:
+        raise SystemExit("the video has no frames")
+    top = top.cpu().tolist()
+    s_row, s_col = active.line_samples(h, w, c)
+    return active.align_rect(active.active_rect(top[:h], top[h:], s_row, s_col, a.crop_limit), layout_of(fmt_in) if size else None)
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     a = parse_args(argv)
     paths = None if a.y4m_in else list_frames(a.input)
@@ -433,12 +518,28 @@ def main(argv: Optional[List[str]] = None) -> int:
             chunks = png_chunks()
         dev = torch.device(a.device)
         net = net.to(dev)
-        hr = get_hw(h, w, a.scale) if a.y4m_out else None
+        fmt_of = dict(FORMAT_OF, **{MONO: LUMA_FORMAT})
+        fmt_in = fmt_of[chroma] if a.y4m_in else "rgb"
+        rect = a.crop
+        if rect == "auto":                          # the first pass: line sums chunk by chunk, a running maximum on the device
+            rect = detect_crop(a, chunks if paths is not None else None, fmt_in, (h, w) if a.y4m_in else None, depth, dev)
+            if paths is not None:
+                chunks = png_chunks()
+            print(f"--crop auto: active picture {rect[2]} x {rect[3]} at ({rect[0]}, {rect[1]}): --crop {','.join(str(v) for v in rect)}",
+                  file=sys.stderr, flush=True)
+        elif rect is not None and h is not None:
+            from .active import check_rect
+            from .video import layout_of
+            try:
+                rect = check_rect(rect, h, w, layout_of(fmt_in) if a.y4m_in else None)
+            except ValueError as e:
+                raise SystemExit(f"--crop: {e}") from None
+        lr = written_lr(h, w, rect, a.bars)
+        hr = get_hw(lr[0], lr[1], a.scale) if a.y4m_out else None
         colour, out_colour = resolve_colours(a.colour, a.out_colour, (h, w) if a.y4m_in else None, hr, in_range)
         out_depth = (depth if a.out_depth is None else a.out_depth) if a.y4m_out else None
         out_chroma = (chroma if a.out_chroma is None else a.out_chroma) if a.y4m_out else None
-        fmt_of = dict(FORMAT_OF, **{MONO: LUMA_FORMAT})
-        fmt_in, fmt_out = fmt_of[chroma] if a.y4m_in else "rgb", fmt_of[out_chroma] if a.y4m_out else "uint8"
+        fmt_out = fmt_of[out_chroma] if a.y4m_out else "uint8"
         from .video import check_depths
         try:                                        # (before the output is opened: a full-range colour with 10 / 12 bits is refused)
             check_depths(depth, out_depth, fmt_in, fmt_out, colour or "bt601", out_colour)
@@ -456,7 +557,7 @@ def main(argv: Optional[List[str]] = None) -> int:
             fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
             full = is_full_range(out_colour)
             tag = ("full" if full else "limited") if (full or a.colour_flags) else None
-            sink = Y4MSink(Y4MWriter(fout, W, H, fps, interlace, scaled_aspect(aspect, (h, w), (H, W)), tag, depth=out_depth, chroma=out_chroma,
+            sink = Y4MSink(Y4MWriter(fout, W, H, fps, interlace, scaled_aspect(aspect, lr, (H, W)), tag, depth=out_depth, chroma=out_chroma,
                                      siting=out_siting),
                            a.chunk + net.num_frame)
         else:
@@ -467,7 +568,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                            size=(h, w) if a.y4m_in else None, cuts=a.cuts, scene_threshold=a.scene_threshold,
                            colour="bt601" if chroma == MONO else colour or "bt601",          # (grey-scale frames carry no colour space)
                            out_colour=None if out_chroma == MONO else out_colour, depth=depth, out_depth=out_depth, siting=siting, out_siting=out_siting,
-                           chroma_filter=a.chroma_filter)
+                           chroma_filter=a.chroma_filter, crop=rect, bars=a.bars)
         done = 0
         try:
             for chunk in chunks:

@@ -27,6 +27,12 @@ input frame at the network's scale (savsr_video_resample_chroma; savsr_amd/yuv.p
 pixel_format / out = "y400": grey-scale frames, the Y plane alone (Y4M's Cmono), for such a network; it needs no chroma_filter.
 chroma_filter=None refuses what it refused before the argument existed.
 
+crop=(y0, x0, ah, aw) / crop="auto": letterboxed video.  The frames are cropped to the rect before anything else looks at them, so the
+call is, bit for bit, the call on the hand-cropped video (savsr_amd/active.py); "auto" finds the rect on the device
+(savsr_video_line_sums_*, then cropdetect's rule on the host).  bars="keep" puts the result back into full-size frames of nominal black,
+bars="drop" returns the picture alone.  The crop and the re-insertion are strided copies through torch views.  crop=None runs exactly
+the lines it ran before.
+
 Every argument is checked here, on the host, before anything is enqueued on the GPU.
 """
 from __future__ import annotations
@@ -444,16 +450,169 @@ def detect_cuts(frames: torch.Tensor, threshold=10.0, pixel_format: str = "rgb",
     return cuts_from_sad(sad.cpu().tolist(), sad_samples(frames.shape, pixel_format, size), threshold)
 
 
+# ---- the active picture (savsr_amd/active.py is the specification) ----------------------------------------------------------------------
+def _line_sums_device(frames: torch.Tensor, side: Side, size: Optional[Tuple[int, int]]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """savsr_video_line_sums_* on frames of the input side already on the GPU: int64 ([N, h], [N, w]) there, enqueued on the current stream
+    (no sync).  Every frame kind is host work over the three entries: which matrix, which stride, and the folding of their sums."""
+    from . import _lib
+    n, c, h, w = _sad_layout(frames, side, size)
+    depth = side.depth
+    lib = _lib.load()
+    u8 = frames.dtype == torch.uint8
+    frames = frames.contiguous() if u8 else frames.to(torch.float32).contiguous()
+    with torch.cuda.device(frames.device):
+        st = torch.cuda.current_stream().cuda_stream
+        mats, width = (n, w) if size else ((n, w * c) if u8 else (n * c, w))
+        cells = torch.empty(mats * (h + width), dtype=torch.int32, device=frames.device)          # (one buffer: the entry zeroes it in one memset)
+        rows, cols = cells[:mats * h].view(mats, h), cells[mats * h:].view(mats, width)
+        if size and depth != 8:
+            _lib.check(lib.savsr_video_line_sums_u16(frames.data_ptr(), n, side.frame_bytes(h, w), h, w, depth, rows.data_ptr(), cols.data_ptr(), st),
+                       "savsr_video_line_sums_u16")
+        elif size:
+            _lib.check(lib.savsr_video_line_sums_u8(frames.data_ptr(), n, side.frame_bytes(h, w), h, w, rows.data_ptr(), cols.data_ptr(), st),
+                       "savsr_video_line_sums_u8")
+        elif u8:
+            _lib.check(lib.savsr_video_line_sums_u8(frames.data_ptr(), n, h * w * c, h, w * c, rows.data_ptr(), cols.data_ptr(), st),
+                       "savsr_video_line_sums_u8")
+            cols = cols.view(n, w, c)          # (a cell is below 2^32: as int64 before the channels are folded)
+        else:
+            _lib.check(lib.savsr_video_line_sums_f32(frames.data_ptr(), n * c, h, w, rows.data_ptr(), cols.data_ptr(), st), "savsr_video_line_sums_f32")
+            rows, cols = rows.view(n, c, h), cols.view(n, c, w)
+        rows, cols = (t.to(torch.int64) & 0xFFFFFFFF for t in (rows, cols))          # the cells are unsigned
+        if not size and u8:
+            cols = cols.sum(2)
+        elif not size:
+            rows, cols = rows.sum(1), cols.sum(1)
+    return rows, cols
+
+
+def line_sums(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The active-picture detector's line sums: int64 ([N, h], [N, w]) on the GPU, per frame the sum of the 8-bit samples of every row
+    and of every column (savsr_amd.active.line_sums is the specification), on the caller's current stream, without a sync.  frames as for
+    `pair_sad`, and the same samples: every byte of [N, h, w, c] uint8 frames (GPU or host), every value of [N, c, h, w] float frames on the
+    GPU after the uint8 output's quantisation, the Y plane of planar frames (pixel_format=, size=(h, w); at depth 10 / 12 a sample's 8
+    most significant bits)."""
+    side, size = _sad_side(pixel_format, size, depth)
+    _sad_layout(frames, side, size)
+    return _line_sums_device(_to_device(frames, _sad_device(frames)), side, size)
+
+
+def _detect_device(frames: torch.Tensor, side: Side, size: Optional[Tuple[int, int]], limit) -> Tuple[int, int, int, int]:
+    """The aligned active rect of frames of the input side on the GPU: the line sums, their maxima over the frames on the device, one
+    device -> host copy of h + w integers, then active_rect and align_rect on the host."""
+    from . import active
+    n, c, h, w = _sad_layout(frames, side, size)
+    rows, cols = _line_sums_device(frames, side, size)
+    top = torch.cat([rows.amax(0), cols.amax(0)]).cpu().tolist()
+    s_row, s_col = active.line_samples(h, w, max(c, 1))
+    return active.align_rect(active.active_rect(top[:h], top[h:], s_row, s_col, limit), side.layout)
+
+
+def detect_active_area(frames: torch.Tensor, limit=24, pixel_format: str = "rgb", size=None, depth: int = 8) -> Tuple[int, int, int, int]:
+    """The active picture (y0, x0, ah, aw) of a letterboxed, pillarboxed or window-boxed video: ffmpeg cropdetect's rule in exact integer
+    arithmetic (savsr_amd.active.active_rect) on `line_sums`: a row or column whose mean sample stays at or below `limit` (the 8-bit
+    scale) in every frame is bar, the picture spans the first to the last line that is not; the offsets are then moved outwards to the
+    chroma block of the layout (active.align_rect).  No picture, or one below 2 x 2: the whole frame.  The default limit is cropdetect's
+    and is not validated on real footage."""
+    from . import active
+    active.check_limit(limit)
+    side, size = _sad_side(pixel_format, size, depth)
+    _sad_layout(frames, side, size)
+    return _detect_device(_to_device(frames, _sad_device(frames)), side, size, limit)
+
+
+def _plane_table(h: int, w: int, side: Side):
+    """[(byte offset, rows, row bytes, vertical block, horizontal block)] of the planes of a planar h x w frame of `side`."""
+    from .active import block_of
+    from .yuv import chroma_hw
+    s = 1 if side.depth == 8 else 2
+    table = [(0, h, w * s, 1, 1)]
+    if side.layout != MONO:
+        ch, cw = chroma_hw(h, w, side.layout)
+        bv, bh = block_of(side.layout)
+        table += [(h * w * s, ch, cw * s, bv, bh), ((h * w + ch * cw) * s, ch, cw * s, bv, bh)]
+    return table
+
+
+def _crop_device(frames: torch.Tensor, rect, side: Side, hw: Tuple[int, int]) -> torch.Tensor:
+    """active.crop_frames on a device tensor: strided copies through views.  Planar frames: every plane sliced at the rect divided by its
+    block and the slices concatenated (bytes; a 16-bit sample is two of them, so the offsets stay even)."""
+    y0, x0, ah, aw = rect
+    if not side.planar:
+        if frames.dtype == torch.uint8:
+            return frames[:, y0:y0 + ah, x0:x0 + aw].contiguous()
+        return frames[:, :, y0:y0 + ah, x0:x0 + aw].contiguous()
+    h, w = hw
+    n, s = frames.shape[0], 1 if side.depth == 8 else 2
+    parts = []
+    for (off, ph, pb, _, _), (_, qh, qb, bv, bh) in zip(_plane_table(h, w, side), _plane_table(ah, aw, side)):
+        py, px = y0 // bv, (x0 // bh) * s
+        parts.append(frames[:, off:off + ph * pb].view(n, ph, pb)[:, py:py + qh, px:px + qb].reshape(n, qh * qb))
+    return torch.cat(parts, 1)
+
+
+def _insert_device(sr: torch.Tensor, placed, spec: "VideoSpec") -> torch.Tensor:
+    """active.insert_frames on a device tensor: full-size frames of active.bars_frame with the picture's planes copied in at (Y0, X0)
+    divided by each plane's block."""
+    from .active import bars_frame
+    Hf, Wf, Ha, Wa, Y0, X0 = placed
+    out, n = spec.out, sr.shape[0]
+    bars = torch.from_numpy(bars_frame(Hf, Wf, out.fmt, out.depth, out.colour, spec.nch)).to(sr.device)
+    full = bars.unsqueeze(0).repeat(n, *([1] * bars.dim()))
+    if out.fmt == "float":
+        full[:, :, Y0:Y0 + Ha, X0:X0 + Wa] = sr
+    elif not out.planar:
+        full[:, Y0:Y0 + Ha, X0:X0 + Wa] = sr
+    else:
+        s = 1 if out.depth == 8 else 2
+        for (off, ph, pb, bv, bh), (aoff, qh, qb, _, _) in zip(_plane_table(Hf, Wf, out), _plane_table(Ha, Wa, out)):
+            py, px = Y0 // bv, (X0 // bh) * s
+            full[:, off:off + ph * pb].view(n, ph, pb)[:, py:py + qh, px:px + qb] = sr[:, aoff:aoff + qh * qb].view(n, qh, qb)
+    return full
+
+
+def _check_crop_args(crop, crop_limit, bars, auto_ok: bool = True):
+    """crop is None, "auto" or a rect; bars / crop_limit go with a crop.  The rect itself: active.check_rect, once the frame size is known."""
+    from . import active
+    if crop is None:
+        if bars != "keep":
+            raise ValueError(f"bars = {bars!r} goes with crop=: without a crop there are no bars to keep or drop")
+        if isinstance(crop_limit, bool) or crop_limit != active.DEFAULT_LIMIT:
+            raise ValueError(f"crop_limit = {crop_limit!r} goes with crop=: it is the limit of the detector behind crop='auto'")
+        return None
+    active.check_bars(bars)
+    active.check_limit(crop_limit)
+    if isinstance(crop, str):
+        if crop != "auto":
+            raise ValueError(f"crop = {crop!r}: None, 'auto' or a rect (y0, x0, ah, aw) of ints")
+        if not auto_ok:
+            raise ValueError("crop = 'auto' in VideoUpscaler: the decision needs the whole video; detect the rect first "
+                             "(savsr_amd.detect_active_area) and give it, or use python -m savsr_amd.upscale --crop auto")
+        return crop
+    return active.check_rect(crop, None, None, None)
+
+
+def _cropped_spec(spec: "VideoSpec", rect) -> "VideoSpec":
+    """The VideoSpec of the cropped frames: the same sides at the rect's size."""
+    from dataclasses import replace
+    return replace(spec, size=(rect[2], rect[3])) if spec.size else spec
+
+
 def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
                   size=None, cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601",
                   out_colour: Optional[str] = None, depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None,
-                  out_siting: Optional[str] = None, chroma_filter: Optional[str] = None) -> torch.Tensor:
+                  out_siting: Optional[str] = None, chroma_filter: Optional[str] = None, crop=None, crop_limit=24,
+                  bars: str = "keep") -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
     spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter)
     sc = as_scale(net.scale if scale is None else scale)
-    n = spec.frames_hw(frames)[0]
+    n, h, w = spec.frames_hw(frames)
+    crop = _check_crop_args(crop, crop_limit, bars)
+    if crop is not None and crop != "auto":
+        from . import active
+        crop = active.check_rect(crop, h, w, spec.inp.layout)
     T = net.num_frame
     if cuts is None:
         check_length(n, T, padding)
@@ -469,15 +628,27 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     if dev.type != "cuda":
         raise RuntimeError("savsr_amd runs on an AMD GPU only: move the network to the GPU (net.cuda()) first")
     frames = _to_device(frames, dev)
+    full = spec
+    if crop == "auto":
+        crop = _detect_device(frames, spec.inp, spec.size, crop_limit)
+    if crop == (0, 0, h, w):          # the whole frame: the uncropped path
+        crop = None
+    if crop is not None:               # the crop comes first: everything below sees the cropped video
+        frames = _crop_device(frames, crop, spec.inp, (h, w))
+        spec = _cropped_spec(spec, crop)
     if cuts is None:
         windows = [window_indices(i, n, T, padding) for i in range(n)]
     else:
         if _is_auto(cuts):
             sad = _pair_sad_device(frames, spec.inp, spec.size).cpu().tolist()
-            cuts = scenes.cuts_from_sad(sad, scenes.sad_samples(frames.shape, pixel_format, size), scene_threshold)
+            cuts = scenes.cuts_from_sad(sad, scenes.sad_samples(frames.shape, pixel_format, spec.size), scene_threshold)
         windows = scenes.scene_windows(n, cuts, T, padding)
     with torch.no_grad():
-        return net.engine().forward_video(frames, windows, sc, spec, ensemble=net.self_ensemble)
+        res = net.engine().forward_video(frames, windows, sc, spec, ensemble=net.self_ensemble)
+        if crop is not None and bars == "keep":
+            from . import active
+            res = _insert_device(res, active.place(crop, h, w, sc, full.out.layout), full)
+        return res
 
 
 class VideoUpscaler:
@@ -502,12 +673,16 @@ class VideoUpscaler:
     cuts=[k, ...] (global frame indices) or cuts="auto" (each push scores its new pairs on the device, the pair with the previous
     push's last frame included, and decides with `scene_threshold`): windows stop at cuts as in upscale_video(cuts=...), and `up.cuts`
     lists the cuts among the frames pushed so far.  A frame is returned once its window is the same however the video continues -- a cut
-    may still come anywhere after the last pushed frame (savsr_amd.scenes.ScenePlan); the frames kept are bounded as without cuts."""
+    may still come anywhere after the last pushed frame (savsr_amd.scenes.ScenePlan); the frames kept are bounded as without cuts.
+
+    crop=(y0, x0, ah, aw), bars="keep" / "drop": as in upscale_video, with an explicit rect only ("auto" needs the whole video: detect
+    first with savsr_amd.detect_active_area).  Chunks are checked against the full frame size and cropped as they arrive, so the device
+    buffer holds cropped frames; `spec` is the VideoSpec of the cropped size."""
 
     def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb", size=None,
                  cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None,
                  depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
-                 chroma_filter: Optional[str] = None):
+                 chroma_filter: Optional[str] = None, crop=None, bars: str = "keep"):
         _check_net(net)
         check_padding(padding)
         check_out(out, net.cfg["num_in_ch"], chroma_filter)          # (speaks before the cuts, video_spec after them: the order of refusals)
@@ -522,7 +697,13 @@ class VideoUpscaler:
             self._plan = scenes.ScenePlan(net.num_frame, padding)
         # the frames on both sides, checked once, here; the luma-only path (`luma_mode`) is decided with them
         self.spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter)
-        self.i420 = self.spec.size                 # (h, w) of planar chunks, None for packed ones
+        self._full = self.spec                     # the spec of the chunks as pushed; `spec` becomes the cropped size's with a crop
+        self._rect = _check_crop_args(crop, 24, bars, auto_ok=False)          # the rect to crop every chunk to; None: no crop, as it was
+        self._place = None                         # active.place's six numbers with bars="keep", once the frame size is known
+        self.bars = bars
+        if self._rect is not None and self.spec.size:
+            self._set_rect(*self.spec.size)
+        self.i420 = self.spec.size                 # (h, w) of the planar frames the engine sees, None for packed ones
         self.net, self.padding, self.out = net, padding, out
         self.scale = as_scale(net.scale if scale is None else scale)
         self.ensemble = net.self_ensemble          # (read once, like the scale: every chunk runs the same flow)
@@ -534,6 +715,16 @@ class VideoUpscaler:
         self.done = 0                                 # frames returned
         self._shape: Optional[tuple] = None           # (dtype is uint8, h, w)
         self._finished = False
+
+    def _set_rect(self, h: int, w: int) -> None:
+        """The rect against the full frame size, known now: refused if it does not fit; the whole frame is the uncropped path."""
+        from . import active
+        rect = active.check_rect(self._rect, h, w, self._full.inp.layout)
+        if rect == (0, 0, h, w):
+            self._rect = None
+            return
+        self._rect, self._hw = rect, (h, w)
+        self.spec = _cropped_spec(self._full, rect)
 
     @property
     def cuts(self) -> Optional[List[int]]:
@@ -557,7 +748,11 @@ class VideoUpscaler:
     def _forward(self, windows: List[List[int]]) -> torch.Tensor:
         """The SR frames of windows into the buffered frames."""
         with torch.no_grad():
-            return self.net.engine().forward_video(self._buf, windows, self.scale, self.spec, ensemble=self.ensemble)
+            res = self.net.engine().forward_video(self._buf, windows, self.scale, self.spec, ensemble=self.ensemble)
+            if self._rect is not None and self.bars == "keep":
+                from . import active
+                res = _insert_device(res, active.place(self._rect, *self._hw, self.scale, self._full.out.layout), self._full)
+            return res
 
     def _run(self, upto: int, n_total: Optional[int]) -> torch.Tensor:
         """SR frames [done, upto); windows at the video length n_total (None: not known yet, every window needed is interior)."""
@@ -569,17 +764,21 @@ class VideoUpscaler:
     def push(self, frames: torch.Tensor) -> torch.Tensor:
         if self._finished:
             raise RuntimeError("push() after finish()")
-        k, h, w = self.spec.frames_hw(frames)
+        k, h, w = self._full.frames_hw(frames)
         shape = (frames.dtype == torch.uint8, h, w)
         if self._shape is not None and shape != self._shape:
             raise ValueError(f"chunk of {'uint8' if shape[0] else 'float'} {h} x {w} frames after {'uint8' if self._shape[0] else 'float'} "
                              f"{self._shape[1]} x {self._shape[2]} ones")
+        if self._shape is None and self._rect is not None and not self._full.size:
+            self._set_rect(h, w)                   # (packed chunks carry the frame size: the rect is checked against the first one's)
         dev = self.net.gamma.device
         if dev.type != "cuda":
             raise RuntimeError("savsr_amd runs on an AMD GPU only: move the network to the GPU (net.cuda()) first")
         self._shape = shape
         new = _to_device(frames, dev)
         new = new.contiguous() if shape[0] else new.to(torch.float32).contiguous()
+        if self._rect is not None:
+            new = _crop_device(new, self._rect, self._full.inp, (h, w))
         self._buf = new if self._buf is None else torch.cat([self._buf, new], 0)
         if self._plan is not None:
             return self._push_scenes(k)
@@ -649,6 +848,8 @@ class VideoUpscaler:
     def _empty(self) -> torch.Tensor:
         from .packing import get_hw
         u8, h, w = self._shape
+        if self._rect is not None and self.bars == "drop":
+            h, w = self._rect[2:]
         H, W = get_hw(h, w, self.scale)
         c = self.net.cfg["num_in_ch"]
         dev = self.net.gamma.device
