@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 42
+#define SAVSR_ABI_VERSION 43
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -631,6 +631,30 @@ int savsr_video_line_sums_u8(const uint8_t* frames, int n, int64_t frame_bytes, 
 int savsr_video_line_sums_u16(const uint8_t* frames, int n, int64_t frame_bytes, int rows, int cols, int depth, uint32_t* row_sums,
                               uint32_t* col_sums, void* stream);
 int savsr_video_line_sums_f32(const float* mats, int n_mats, int rows, int cols, uint32_t* row_sums, uint32_t* col_sums, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 43) The motion-adaptive deinterlacer (deinterlace.hip; savsr_amd.deinterlace, upscale_video(fields=...), VideoUpscaler(fields=...),
+ * --fields of python -m savsr_amd.upscale): interlaced frames -> progressive frames at the field rate by ffmpeg
+ * yadif's rule in 32-bit integers (savsr_amd/deinterlace.py `deinterlace_matrix` restates it sample by sample; the kernels equal it bit
+ * for bit).  One matrix (a plane, or the h x (w * c) bytes of packed frames) of every frame per call: matrix k of the n_frames resident
+ * frames starts at frames + k * frame_bytes + plane_offset, its rows follow each other directly.  Source frames [from, to) become the
+ * 2 * (to - from) output frames at out + o * out_frame_bytes + out_plane_offset: frame 2 (n - from) + f keeps the rows of parity f
+ * (order 0, top field first) or 1 - f (order 1) of source frame n and interpolates the others from frames n, max(n - 1, 0) and
+ * min(n + 1, n_frames - 1), so a streaming caller passes its context frames and the range.  The source and the output must not overlap.
+ * The entries only enqueue (one launch), allocate nothing, do not synchronise and are capturable.  Refused before the device is touched
+ * with SAVSR_E_ARG, savsr_last_error() naming the reason: a null pointer, n_frames < 1, rows < 2 (or above 524280), an empty row, a step
+ * outside 1 .. 4 or not dividing row_bytes, an order other than 0 / 1, a range outside 0 <= from < to <= n_frames, a negative plane offset,
+ * a frame stride smaller than the offset plus the plane (either side); _u16: a depth other than 10 / 12, an odd pointer, stride or offset.
+ * 16-byte accesses when the plane pointers, the frame strides and a row's bytes of both sides are multiples of 16, a sample per access
+ * otherwise (any pointer, stride and size).
+ * savsr_video_deinterlace_u8:  matrices of rows x row_bytes bytes with pixel step `step` (1: a plane; c: packed [n][h][w][c] frames, so
+ *                           that a channel only meets itself).
+ * savsr_video_deinterlace_u16: matrices of rows x cols little-endian 16-bit samples, read as min(s, 2^depth - 1); kept rows are copied
+ *                           as they are. */
+int savsr_video_deinterlace_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes, int step,
+                               int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
+int savsr_video_deinterlace_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int depth,
+                                int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 33) Geometric self-ensemble (ensemble.hip; SAVSR.set_self_ensemble).  Variant k = 0 .. 7: fw = k & 1 flips

@@ -6,5 +6,6 @@ from . import datasets as _datasets, models as _models  # noqa: F401,E402  (regi
 from .datasets import build_dataset  # noqa: F401,E402
 from .models import build_model  # noqa: F401,E402
 from .video import VideoUpscaler, detect_active_area, detect_cuts, line_sums, pair_sad  # noqa: F401,E402
+from . import deinterlace  # noqa: F401,E402  (the specification module; calling it is savsr_amd.video.deinterlace, the GPU function)
 
 __version__ = "0.1.0"

@@ -1,0 +1,310 @@
+// The motion-adaptive deinterlacer (ABI 43): N interlaced frames -> 2N progressive ones, ffmpeg yadif's rule in 32-bit integers
+// (savsr_amd/deinterlace.py `deinterlace_matrix` is the specification, sample by sample; the kernels equal it bit for bit).  Output frame
+// 2n + f keeps the rows of parity p (f for tff, 1 - f for bff) of source frame n and interpolates the others from cur = n, prev =
+// max(n - 1, 0), next = min(n + 1, n_frames - 1).  A stencil over three frames: per interpolated sample 2 rows of cur with +-3 pixel
+// steps of halo, 3 rows of the field's two temporal neighbours p2 / n2 and 2 rows each of prev and next.
+//
+//   _u8    matrices of rows x row_bytes bytes with a pixel step (1 for a plane, c for packed h x (w * c) frames)
+//   _u16   matrices of rows x cols little-endian 16-bit samples, every sample read as min(s, 2^depth - 1); step 1
+//
+// One launch per call, grid = (column tile, row tile, output frame).  A lane owns one interpolated row piece and copies the kept row
+// above it (and the last row below it, where that one is kept): the copy costs no load, the kept row is the lane's `c` / `e` row.
+// Vector form (plane base pointers, frame strides and row pitches of both sides multiples of 16 bytes): a lane owns 16 bytes; the +-3 step
+// neighbours of the directional search come from the two 16-byte chunks beside its own in the `c` and `e` rows (overlapping loads that
+// the neighbouring lanes issue as well, so they are L1 / L2 hits; 18 loads and 2 stores of 16 bytes per lane, all loads issued before
+// the first use, no LDS).  The pixel step is a template argument, so every sample is a constant bit field of a register.  One-sample
+// form (any pointer, stride and size): a lane owns one sample.  Absolute differences are v_sad_u8 / v_sad_u16 on single samples.
+#include "common.hpp"
+
+#include <cstdint>
+
+namespace savsr {
+namespace {
+
+constexpr int DI_THREADS = 256;
+constexpr int DI_TILE_IROWS = 16;                   // interpolated rows of a vector tile: DI_TILE_ROWS = 32 rows of the matrix
+constexpr int DI_TILE_BYTES = 256;                  // bytes of a vector tile's row: 16 lanes x 16 bytes
+constexpr int DI_ONE_IROWS = 4;                     // interpolated rows of a one-sample tile (one per wave)
+constexpr int DI_ONE_COLS = 64;                     // samples of a one-sample tile's row
+constexpr int DI_MAX_Z = 65535;                     // grid.z
+constexpr int DI_MAX_ROWS = 65535 * 2 * DI_ONE_IROWS;          // grid.y of the one-sample form
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+template <int BYTES>
+__device__ __forceinline__ int absdiff(int a, int b) {
+    if constexpr (BYTES == 1) {
+#if __has_builtin(__builtin_amdgcn_sad_u8)
+        return (int)__builtin_amdgcn_sad_u8((uint32_t)a, (uint32_t)b, 0u);
+#else
+        return a > b ? a - b : b - a;
+#endif
+    } else {
+#if __has_builtin(__builtin_amdgcn_sad_u16)
+        return (int)__builtin_amdgcn_sad_u16((uint32_t)a, (uint32_t)b, 0u);
+#else
+        return a > b ? a - b : b - a;
+#endif
+    }
+}
+
+// The samples one interpolated sample reads.  u / l: the rows above and below in cur at x + (k - 3) * step, k = 0 .. 6.
+struct Taps {
+    int u[7], l[7];
+    int p2y, n2y, p2m, n2m, p2p, n2p;          // p2 / n2 at rows y, y - 2, y + 2
+    int pu, pl, nu, nl;                       // prev and next at the rows above and below
+};
+
+template <int BYTES>
+__device__ __forceinline__ int check(const Taps& t, int j, int& score, int& pred, bool allowed) {
+    // CHECK(j): u[x + (j - 1) s] with l[x - (j + 1) s], u[x + j s] with l[x - j s], u[x + (j + 1) s] with l[x - (j - 1) s]
+    const int sc = absdiff<BYTES>(t.u[3 + j - 1], t.l[3 - j - 1]) + absdiff<BYTES>(t.u[3 + j], t.l[3 - j]) + absdiff<BYTES>(t.u[3 + j + 1], t.l[3 - j + 1]);
+    const bool taken = allowed && sc < score;
+    score = taken ? sc : score;
+    pred = taken ? (t.u[3 + j] + t.l[3 - j]) >> 1 : pred;
+    return taken;
+}
+
+// deinterlace.py's rule for one sample.  edge: x - 3 s >= 0 and x + 3 s <= C - 1; inner: y - 2 >= 0 and y + 2 <= R - 1.
+template <int BYTES>
+__device__ __forceinline__ int yadif(const Taps& t, bool edge, bool inner) {
+    const int c = t.u[3], e = t.l[3];
+    const int d = (t.p2y + t.n2y) >> 1;
+    const int t0 = absdiff<BYTES>(t.p2y, t.n2y);
+    const int t1 = (absdiff<BYTES>(t.pu, c) + absdiff<BYTES>(t.pl, e)) >> 1;
+    const int t2 = (absdiff<BYTES>(t.nu, c) + absdiff<BYTES>(t.nl, e)) >> 1;
+    int diff = max(max(t0 >> 1, t1), t2);
+    int pred = (c + e) >> 1;
+    int score = absdiff<BYTES>(t.u[2], t.l[2]) + absdiff<BYTES>(c, e) + absdiff<BYTES>(t.u[4], t.l[4]) - 1;
+    const bool m1 = check<BYTES>(t, -1, score, pred, edge);
+    check<BYTES>(t, -2, score, pred, m1);
+    const bool p1 = check<BYTES>(t, 1, score, pred, edge);
+    check<BYTES>(t, 2, score, pred, p1);
+    const int b = (t.p2m + t.n2m) >> 1, f = (t.p2p + t.n2p) >> 1;
+    const int mx = max(max(d - e, d - c), min(b - c, f - e));
+    const int mn = min(min(d - e, d - c), max(b - c, f - e));
+    diff = inner ? max(max(diff, mn), -mx) : diff;
+    return min(max(pred, d - diff), d + diff);
+}
+
+// What a launch works on.  Rows are `pitch` bytes apart on both sides.
+struct Job {
+    const uint8_t* src;          // plane of resident frame 0
+    uint8_t* dst;                // plane of output frame 0
+    long long src_stride, dst_stride, pitch;
+    int n_frames, from, rows, cols, order, top;          // cols: samples of a row; top: 2^depth - 1
+};
+
+// The rows and frames of output frame `o` of the launch and interpolated row index `ri`: false if there is no such row.
+struct Where {
+    const uint8_t *cur, *prev, *next, *p2, *n2;
+    uint8_t* out;
+    int y, up, dn, ym, yp;
+    bool inner;
+};
+
+__device__ __forceinline__ bool locate(const Job& jb, int o, int ri, Where& w) {
+    const int n = jb.from + (o >> 1), f = o & 1;
+    const int p = jb.order == 0 ? f : 1 - f;
+    const int y = 2 * ri + (1 - p);
+    if (y >= jb.rows) return false;
+    const int np = n > 0 ? n - 1 : 0, nn = n + 1 < jb.n_frames ? n + 1 : jb.n_frames - 1;
+    w.cur = jb.src + (long long)n * jb.src_stride;
+    w.prev = jb.src + (long long)np * jb.src_stride;
+    w.next = jb.src + (long long)nn * jb.src_stride;
+    w.p2 = f == 0 ? w.prev : w.cur;
+    w.n2 = f == 0 ? w.cur : w.next;
+    w.out = jb.dst + (long long)o * jb.dst_stride;
+    w.y = y;
+    w.up = y > 0 ? y - 1 : y + 1;
+    w.dn = y < jb.rows - 1 ? y + 1 : y - 1;
+    w.inner = y - 2 >= 0 && y + 2 <= jb.rows - 1;
+    w.ym = w.inner ? y - 2 : y;          // (not used by the result when !inner: any row that exists)
+    w.yp = w.inner ? y + 2 : y;
+    return true;
+}
+
+// Sample i of a run of dwords: a constant bit field once the loops are unrolled.
+template <int BYTES>
+__device__ __forceinline__ int field(const uint32_t* w, int i, int top) {
+    if constexpr (BYTES == 1) return (int)((w[i >> 2] >> (8 * (i & 3))) & 255u);
+    else return min((int)((w[i >> 1] >> (16 * (i & 1))) & 0xffffu), top);
+}
+
+__device__ __forceinline__ u32x4 load16(const uint8_t* row, long long chunk) { return *(reinterpret_cast<const u32x4*>(row) + chunk); }
+
+// Vector form: lane = (interpolated row ri = tile + (tid >> 4), 16-byte chunk = tile + (tid & 15)).
+template <int BYTES, int STEP>
+__global__ __launch_bounds__(DI_THREADS) void deinterlace_vec_kernel(Job jb) {
+    constexpr int SPL = 16 / BYTES;          // samples of a chunk
+    const int chunks = (int)(jb.pitch >> 4);
+    const int chunk = (int)blockIdx.x * 16 + ((int)threadIdx.x & 15);
+    const int ri = (int)blockIdx.y * DI_TILE_IROWS + ((int)threadIdx.x >> 4);
+    Where w;
+    if (chunk >= chunks || !locate(jb, (int)blockIdx.z, ri, w)) return;
+    const long long P = jb.pitch;
+    const int cl = chunk > 0 ? chunk - 1 : chunk, cr = chunk + 1 < chunks ? chunk + 1 : chunk;          // (clamped: read, never used, at the row's ends)
+    uint32_t U[12], L[12];
+    {
+        const uint8_t *ru = w.cur + w.up * P, *rl = w.cur + w.dn * P;
+        const u32x4 a0 = load16(ru, cl), a1 = load16(ru, chunk), a2 = load16(ru, cr);
+        const u32x4 b0 = load16(rl, cl), b1 = load16(rl, chunk), b2 = load16(rl, cr);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            U[k] = a0[k]; U[4 + k] = a1[k]; U[8 + k] = a2[k];
+            L[k] = b0[k]; L[4 + k] = b1[k]; L[8 + k] = b2[k];
+        }
+    }
+    uint32_t Q[10][4];          // p2 / n2 at rows y, y - 2, y + 2; prev and next at the rows above and below
+    {
+        const u32x4 v0 = load16(w.p2 + w.y * P, chunk), v1 = load16(w.n2 + w.y * P, chunk);
+        const u32x4 v2 = load16(w.p2 + w.ym * P, chunk), v3 = load16(w.n2 + w.ym * P, chunk);
+        const u32x4 v4 = load16(w.p2 + w.yp * P, chunk), v5 = load16(w.n2 + w.yp * P, chunk);
+        const u32x4 v6 = load16(w.prev + w.up * P, chunk), v7 = load16(w.prev + w.dn * P, chunk);
+        const u32x4 v8 = load16(w.next + w.up * P, chunk), v9 = load16(w.next + w.dn * P, chunk);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            Q[0][k] = v0[k]; Q[1][k] = v1[k]; Q[2][k] = v2[k]; Q[3][k] = v3[k]; Q[4][k] = v4[k];
+            Q[5][k] = v5[k]; Q[6][k] = v6[k]; Q[7][k] = v7[k]; Q[8][k] = v8[k]; Q[9][k] = v9[k];
+        }
+    }
+    const int x0 = chunk * SPL;
+    uint32_t res[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) {
+        Taps t;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+            t.u[k] = field<BYTES>(U, SPL + i + (k - 3) * STEP, jb.top);
+            t.l[k] = field<BYTES>(L, SPL + i + (k - 3) * STEP, jb.top);
+        }
+        t.p2y = field<BYTES>(Q[0], i, jb.top); t.n2y = field<BYTES>(Q[1], i, jb.top);
+        t.p2m = field<BYTES>(Q[2], i, jb.top); t.n2m = field<BYTES>(Q[3], i, jb.top);
+        t.p2p = field<BYTES>(Q[4], i, jb.top); t.n2p = field<BYTES>(Q[5], i, jb.top);
+        t.pu = field<BYTES>(Q[6], i, jb.top);  t.pl = field<BYTES>(Q[7], i, jb.top);
+        t.nu = field<BYTES>(Q[8], i, jb.top);  t.nl = field<BYTES>(Q[9], i, jb.top);
+        const int x = x0 + i;
+        const int v = yadif<BYTES>(t, x - 3 * STEP >= 0 && x + 3 * STEP <= jb.cols - 1, w.inner);
+        if constexpr (BYTES == 1) res[i >> 2] |= (uint32_t)v << (8 * (i & 3));
+        else res[i >> 1] |= (uint32_t)v << (16 * (i & 1));
+    }
+    *(reinterpret_cast<u32x4*>(w.out + w.y * P) + chunk) = u32x4{res[0], res[1], res[2], res[3]};
+    // the kept rows, as they are: the row above, and the matrix's last row where it lies below
+    if (w.y > 0) *(reinterpret_cast<u32x4*>(w.out + (w.y - 1) * P) + chunk) = u32x4{U[4], U[5], U[6], U[7]};
+    if (w.y + 1 == jb.rows - 1) *(reinterpret_cast<u32x4*>(w.out + (w.y + 1) * P) + chunk) = u32x4{L[4], L[5], L[6], L[7]};
+}
+
+template <int BYTES>
+__device__ __forceinline__ int raw_at(const uint8_t* row, int x) {
+    if constexpr (BYTES == 1) return row[x];
+    else return reinterpret_cast<const uint16_t*>(row)[x];
+}
+
+template <int BYTES>
+__device__ __forceinline__ void put_at(uint8_t* row, int x, int v) {
+    if constexpr (BYTES == 1) row[x] = (uint8_t)v;
+    else reinterpret_cast<uint16_t*>(row)[x] = (uint16_t)v;
+}
+
+// One-sample form: lane = (interpolated row ri = tile + wave, sample x = tile + lane).
+template <int BYTES>
+__global__ __launch_bounds__(DI_THREADS) void deinterlace_one_kernel(Job jb, int step) {
+    const int x = (int)blockIdx.x * DI_ONE_COLS + ((int)threadIdx.x & 63);
+    const int ri = (int)blockIdx.y * DI_ONE_IROWS + ((int)threadIdx.x >> 6);
+    Where w;
+    if (x >= jb.cols || !locate(jb, (int)blockIdx.z, ri, w)) return;
+    const long long P = jb.pitch;
+    const uint8_t *ru = w.cur + w.up * P, *rl = w.cur + w.dn * P;
+    const bool edge = x - 3 * step >= 0 && x + 3 * step <= jb.cols - 1;
+    Taps t;
+    const int cu = raw_at<BYTES>(ru, x), cl = raw_at<BYTES>(rl, x);          // (unclipped: the kept rows' copies)
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        const int xk = edge ? x + (k - 3) * step : x;          // (without the search only the middle tap is read)
+        t.u[k] = min(raw_at<BYTES>(ru, xk), jb.top);
+        t.l[k] = min(raw_at<BYTES>(rl, xk), jb.top);
+    }
+    t.p2y = min(raw_at<BYTES>(w.p2 + w.y * P, x), jb.top);  t.n2y = min(raw_at<BYTES>(w.n2 + w.y * P, x), jb.top);
+    t.p2m = min(raw_at<BYTES>(w.p2 + w.ym * P, x), jb.top); t.n2m = min(raw_at<BYTES>(w.n2 + w.ym * P, x), jb.top);
+    t.p2p = min(raw_at<BYTES>(w.p2 + w.yp * P, x), jb.top); t.n2p = min(raw_at<BYTES>(w.n2 + w.yp * P, x), jb.top);
+    t.pu = min(raw_at<BYTES>(w.prev + w.up * P, x), jb.top); t.pl = min(raw_at<BYTES>(w.prev + w.dn * P, x), jb.top);
+    t.nu = min(raw_at<BYTES>(w.next + w.up * P, x), jb.top); t.nl = min(raw_at<BYTES>(w.next + w.dn * P, x), jb.top);
+    put_at<BYTES>(w.out + w.y * P, x, yadif<BYTES>(t, edge, w.inner));
+    if (w.y > 0) put_at<BYTES>(w.out + (w.y - 1) * P, x, cu);
+    if (w.y + 1 == jb.rows - 1) put_at<BYTES>(w.out + (w.y + 1) * P, x, cl);
+}
+
+template <int BYTES>
+int launch_deinterlace(Job jb, int step, int n_out, hipStream_t st) {
+    const bool vec = ((reinterpret_cast<uintptr_t>(jb.src) | reinterpret_cast<uintptr_t>(jb.dst)) & 15) == 0 && jb.src_stride % 16 == 0 &&
+                     jb.dst_stride % 16 == 0 && jb.pitch % 16 == 0;
+    const int irows = (jb.rows + 1) / 2;          // of the field with more interpolated rows; the other one's last tile row may be empty
+    for (int o0 = 0; o0 < n_out; o0 += DI_MAX_Z - 1) {          // (an even count per launch: a launch starts at field 0 of a source frame)
+        const int no = n_out - o0 < DI_MAX_Z - 1 ? n_out - o0 : DI_MAX_Z - 1;
+        Job part = jb;
+        part.from = jb.from + o0 / 2;
+        part.dst = jb.dst + (long long)o0 * jb.dst_stride;
+        if (vec) {
+            const dim3 grid((unsigned)((jb.pitch + DI_TILE_BYTES - 1) / DI_TILE_BYTES), (unsigned)((irows + DI_TILE_IROWS - 1) / DI_TILE_IROWS), (unsigned)no);
+            if (BYTES == 2) hipLaunchKernelGGL((deinterlace_vec_kernel<2, 1>), grid, dim3(DI_THREADS), 0, st, part);
+            else if (step == 1) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 1>), grid, dim3(DI_THREADS), 0, st, part);
+            else if (step == 2) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 2>), grid, dim3(DI_THREADS), 0, st, part);
+            else if (step == 3) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 3>), grid, dim3(DI_THREADS), 0, st, part);
+            else hipLaunchKernelGGL((deinterlace_vec_kernel<1, 4>), grid, dim3(DI_THREADS), 0, st, part);
+        } else {
+            const dim3 grid((unsigned)((jb.cols + DI_ONE_COLS - 1) / DI_ONE_COLS), (unsigned)((irows + DI_ONE_IROWS - 1) / DI_ONE_IROWS), (unsigned)no);
+            hipLaunchKernelGGL((deinterlace_one_kernel<BYTES>), grid, dim3(DI_THREADS), 0, st, part, step);
+        }
+        if (int rc = check_launch(vec ? "deinterlace_vec_kernel" : "deinterlace_one_kernel")) return rc;
+    }
+    return 0;
+}
+
+// The checks the two entries share; 0 or SAVSR_E_ARG with the message set.  row_bytes: of the matrix on both sides.
+int check_deinterlace(const char* who, const void* frames, const void* out, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows,
+                      int64_t row_bytes, int order, int from, int to, int64_t out_frame_bytes, int64_t out_plane_offset) {
+    char msg[160];
+    const char* why = nullptr;
+    if (!frames || !out) why = "null pointer";
+    else if (n_frames < 1) why = "n_frames >= 1";
+    else if (rows < 2) why = "rows >= 2 (a matrix of one row has no second field)";
+    else if (rows > DI_MAX_ROWS) why = "rows <= 524280";
+    else if (row_bytes < 1) why = "a row holds at least one sample";
+    else if (order != 0 && order != 1) why = "order 0 (tff) or 1 (bff)";
+    else if (from < 0 || to > n_frames || from >= to) why = "the range needs 0 <= from < to <= n_frames";
+    else if (plane_offset < 0 || out_plane_offset < 0) why = "plane offsets >= 0";
+    else if (frame_bytes < plane_offset + (int64_t)rows * row_bytes) why = "frame_bytes smaller than plane_offset plus the rows x row_bytes plane";
+    else if (out_frame_bytes < out_plane_offset + (int64_t)rows * row_bytes) why = "out_frame_bytes smaller than out_plane_offset plus the rows x row_bytes plane";
+    if (!why) return 0;
+    snprintf(msg, sizeof msg, "%s: %s", who, why);
+    return fail_arg(msg);
+}
+
+}  // namespace
+}  // namespace savsr
+
+using namespace savsr;
+
+extern "C" int savsr_video_deinterlace_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes,
+                                          int step, int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
+                                          void* stream) {
+    if (int rc = check_deinterlace("video_deinterlace_u8", frames, out, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to,
+                                   out_frame_bytes, out_plane_offset))
+        return rc;
+    if (step < 1 || step > 4 || row_bytes % step) return fail_arg("video_deinterlace_u8: step 1 .. 4 and a divisor of row_bytes");
+    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, row_bytes, order, 255};
+    return launch_deinterlace<1>(jb, step, 2 * (to - from), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int savsr_video_deinterlace_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols,
+                                           int depth, int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
+                                           void* stream) {
+    if (int rc = check_deinterlace("video_deinterlace_u16", frames, out, n_frames, frame_bytes, plane_offset, rows, 2 * (int64_t)cols, order, from, to,
+                                   out_frame_bytes, out_plane_offset))
+        return rc;
+    if (depth != 10 && depth != 12) return fail_arg("video_deinterlace_u16: depth 10 or 12 (8 bits: savsr_video_deinterlace_u8)");
+    if (((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(out)) & 1) || ((frame_bytes | plane_offset | out_frame_bytes | out_plane_offset) & 1))
+        return fail_arg("video_deinterlace_u16: frames, out, the frame strides and the plane offsets must be 2-byte aligned (16-bit samples)");
+    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, 2ll * cols, n_frames, from, rows, cols, order, (1 << depth) - 1};
+    return launch_deinterlace<2>(jb, 1, 2 * (to - from), static_cast<hipStream_t>(stream));
+}

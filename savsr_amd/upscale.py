@@ -10,6 +10,7 @@
     python -m savsr_amd.upscale -i in8.y4m -o out10.y4m --scale 4 --checkpoint <net.pth> --out-depth 10
     ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o - --scale 4 --checkpoint <net.pth> --siting auto --out-siting same | ffmpeg -i - out.mp4
     python -m savsr_amd.upscale -i in.y4m -o out.y4m --scale 4 --opt <luma_test.yml> --chroma-filter bicubic
+    ffmpeg -i pal_dv.avi -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out50p.y4m --scale 4 --checkpoint <net.pth> --fields auto
     python -m savsr_amd.upscale -i letterboxed_sd.y4m -o hd.y4m --scale 4 --checkpoint <net.pth> --crop auto --colour auto --out-colour auto
     ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out444p10.y4m --scale 4 --checkpoint <net.pth> --out-chroma 444
 
@@ -65,6 +66,14 @@ them (savsr_amd/active.py), so the bars cost no network time and stay out of the
 the rect on stderr; on stdin there is no second pass, so give Y0,X0,H,W there.  --bars keep (the default) writes full-size frames with
 the picture in nominal black; --bars drop writes the picture alone, and a Y4M output then carries the picture's size.
 
+--fields: interlaced footage (PAL / NTSC broadcast, DV, DVD video that is not film).  The frames are deinterlaced on the GPU into
+progressive frames at the field rate before anything else sees them (savsr_amd/deinterlace.py: ffmpeg yadif's rule; every source frame
+gives two), so the network's windows, --cuts and --crop work on pictures and not on woven fields; K in --cuts K,... and Y0,X0,H,W index and
+measure the deinterlaced video.  tff / bff name the field order, auto takes it from the Y4M input's I tag (It -> tff, Ib -> bff, Ip ->
+progressive; Im, mixed, is refused).  The output is then tagged Ip at twice the frame rate, and a PNG folder holds twice the files
+(%08d.png).  The default, progressive, is what this tool has always done: the frames go through as they are and the I tag is passed on;
+for an input tagged It / Ib / Im one line on stderr says so.  There is no inverse telecine.
+
 It ends with one line: frames, seconds, frames/s (on stderr when the video goes to stdout); with --cuts, the scene count as well; with
 --colour / --out-colour, the two colour spaces.
 """
@@ -79,6 +88,7 @@ import time
 from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional
 
+from .deinterlace import FIELD_FLAGS, FIELD_ORDERS, resolve_fields
 from .yuv import COLOURS, SITINGS
 
 MAX_WRITERS = 16
@@ -188,6 +198,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--crop-limit", type=float, default=None, metavar="X",
                    help="--crop auto: a row or column whose mean stays at or below X (8-bit scale) in every frame is bar (default 24, ffmpeg "
                         "cropdetect's; not validated on real footage)")
+    p.add_argument("--fields", default=None, choices=list(FIELD_FLAGS),
+                   help="interlaced input: deinterlace on the GPU first, every frame giving two progressive ones at the field rate.  tff / bff: "
+                        "the field order; auto: from the Y4M input's I tag (It, Ib; Im is refused); progressive (default): frames go through as "
+                        "they are, the I tag is passed on")
     p.add_argument("--bars", default=None, choices=["keep", "drop"],
                    help="--crop: keep = full-size output, the picture in nominal black (default); drop = the picture alone")
     return p
@@ -267,6 +281,11 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     a.crop_limit = 24 if a.crop_limit is None else a.crop_limit
     a.bars = a.bars or "keep"
     a.y4m_in, a.y4m_out = is_y4m(a.input), is_y4m(a.output)
+    if not a.y4m_in:
+        try:
+            resolve_fields(a.fields, None, (25, 1))          # (a Y4M input: once its header is read)
+        except ValueError as e:
+            p.error(str(e))
     if a.fps is not None and (a.y4m_in or not a.y4m_out):
         p.error("--fps goes with a PNG folder in and Y4M out (a Y4M input carries its frame rate, PNGs have none)")
     if a.colour is not None and not a.y4m_in:
@@ -428,18 +447,28 @@ def written_lr(h, w, rect, bars: str):
     return (h, w) if rect is None or bars == "keep" else (rect[2], rect[3])
 
 
-def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev):
+def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev, order: Optional[str] = None):
     """--crop auto's first pass: savsr_amd.line_sums over the input in --chunk-sized pieces with a running maximum on the device, then
     cropdetect's rule and the alignment to the input layout's chroma block.  chunks: the PNG folder's chunk iterator; None: the .y4m file
-    named by --input, read through a reader of its own."""
+    named by --input, read through a reader of its own.  order: --fields' field order; the sums are then taken on the deinterlaced frames
+    (a video.FieldSplitter of this pass's own), as the second pass will crop them."""
     import torch
 
     from . import active
-    from .video import layout_of, line_sums
+    from .video import FieldSplitter, _sad_side, layout_of, line_sums
     from .y4m import Y4MReader
     from .yuv import CHROMAS
     top = None
     f = None
+    split = None if order is None else FieldSplitter(order, *_sad_side(fmt_in, size, depth))
+
+    def fold(frames):
+        nonlocal top
+        if int(frames.shape[0]):
+            rows, cols = line_sums(frames, fmt_in, size, depth)
+            now = torch.cat([rows.amax(0), cols.amax(0)])
+            top = now if top is None else torch.maximum(top, now)
+
     try:
         if chunks is None:
             f = open(a.input, "rb")
@@ -448,9 +477,10 @@ def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, de
             for chunk in chunks:
                 c = 1 if size else int(chunk.shape[3])
                 h, w = size if size else (int(chunk.shape[1]), int(chunk.shape[2]))
-                rows, cols = line_sums(chunk.to(dev), fmt_in, size, depth)
-                now = torch.cat([rows.amax(0), cols.amax(0)])
-                top = now if top is None else torch.maximum(top, now)
+                fold(chunk.to(dev) if split is None else split.push(chunk.to(dev)))
+            last = None if split is None else split.finish()
+            if last is not None:
+                fold(last)
     finally:
         if f is not None:
             f.close()
@@ -476,11 +506,12 @@ def main(argv: Optional[List[str]] = None) -> int:
     net = load_net(a)
     net.set_precision(a.precision)
     net.set_self_ensemble(a.self_ensemble)
+    n_png = None if paths is None else len(paths) * (2 if a.fields in FIELD_ORDERS else 1)          # (--fields: two frames per file)
     if paths is not None and a.cuts is None:
-        check_length(len(paths), net.num_frame, a.padding)        # (before the GPU is touched; a Y4M stream's length: at its end)
+        check_length(n_png, net.num_frame, a.padding)             # (before the GPU is touched; a Y4M stream's length: at its end)
     elif paths is not None and a.cuts != "auto":
         from .scenes import check_cuts
-        check_cuts(a.cuts, len(paths))
+        check_cuts(a.cuts, n_png)
     fin = fout = None
     try:
         if a.y4m_in:
@@ -516,13 +547,19 @@ def main(argv: Optional[List[str]] = None) -> int:
                 for c0 in range(0, len(paths), a.chunk):
                     yield torch.from_numpy(np.stack([store.host(p) for p in paths[c0:c0 + a.chunk]], 0))
             chunks = png_chunks()
+        try:                                        # --fields and the input's I tag: the field order, the output's I tag and frame rate
+            order, interlace, fps, note = resolve_fields(a.fields, interlace if a.y4m_in else None, fps)
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
+        if note is not None:
+            print(note, file=sys.stderr, flush=True)
         dev = torch.device(a.device)
         net = net.to(dev)
         fmt_of = dict(FORMAT_OF, **{MONO: LUMA_FORMAT})
         fmt_in = fmt_of[chroma] if a.y4m_in else "rgb"
         rect = a.crop
         if rect == "auto":                          # the first pass: line sums chunk by chunk, a running maximum on the device
-            rect = detect_crop(a, chunks if paths is not None else None, fmt_in, (h, w) if a.y4m_in else None, depth, dev)
+            rect = detect_crop(a, chunks if paths is not None else None, fmt_in, (h, w) if a.y4m_in else None, depth, dev, order)
             if paths is not None:
                 chunks = png_chunks()
             print(f"--crop auto: active picture {rect[2]} x {rect[3]} at ({rect[0]}, {rect[1]}): --crop {','.join(str(v) for v in rect)}",
@@ -561,14 +598,14 @@ def main(argv: Optional[List[str]] = None) -> int:
                                      siting=out_siting),
                            a.chunk + net.num_frame)
         else:
-            sink = PngSink(a.output, None if paths is None else [os.path.basename(p) for p in paths],
+            sink = PngSink(a.output, None if paths is None or order is not None else [os.path.basename(p) for p in paths],
                            a.writers or max(1, min(MAX_WRITERS, effective_cpus())))
         t0 = time.perf_counter()
         up = VideoUpscaler(net, a.scale, a.padding, out=fmt_out, pixel_format=fmt_in,
                            size=(h, w) if a.y4m_in else None, cuts=a.cuts, scene_threshold=a.scene_threshold,
                            colour="bt601" if chroma == MONO else colour or "bt601",          # (grey-scale frames carry no colour space)
                            out_colour=None if out_chroma == MONO else out_colour, depth=depth, out_depth=out_depth, siting=siting, out_siting=out_siting,
-                           chroma_filter=a.chroma_filter, crop=rect, bars=a.bars)
+                           chroma_filter=a.chroma_filter, crop=rect, bars=a.bars, fields=order)
         done = 0
         try:
             for chunk in chunks:
@@ -595,6 +632,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         scenes += f", chroma {chroma if a.y4m_in else 'rgb'} -> {out_chroma or 'rgb'}"
     if siting is not None or out_siting is not None:
         scenes += f", siting {siting or 'none'} -> {out_siting or 'none'}"
+    if order is not None:
+        scenes += f", fields {order}"
     print(f"upscaled {done} frames in {dt:.2f} s: {done / dt:.2f} frames/s{scenes}", file=sys.stderr if a.output == "-" else sys.stdout, flush=True)
     return 0
 

@@ -33,6 +33,11 @@ call is, bit for bit, the call on the hand-cropped video (savsr_amd/active.py); 
 bars="drop" returns the picture alone.  The crop and the re-insertion are strided copies through torch views.  crop=None runs exactly
 the lines it ran before.
 
+fields="tff" / "bff": interlaced video.  The N frames become 2N progressive frames at the field rate before anything else looks at
+them -- before the crop -- so the call is, bit for bit, the call on `deinterlace(frames, fields, ...)` (savsr_amd/deinterlace.py is the
+specification: ffmpeg yadif's rule in integers; savsr_video_deinterlace_u8 / _u16 once per plane).  fields=None runs exactly the lines it
+ran before.
+
 Every argument is checked here, on the host, before anything is enqueued on the GPU.
 """
 from __future__ import annotations
@@ -598,17 +603,124 @@ def _cropped_spec(spec: "VideoSpec", rect) -> "VideoSpec":
     return replace(spec, size=(rect[2], rect[3])) if spec.size else spec
 
 
+# ---- interlaced video (savsr_amd/deinterlace.py is the specification) -----------------------------------------------------------------------
+def _check_fields(fields) -> Optional[str]:
+    if fields is None:
+        return None
+    from .deinterlace import check_order
+    check_order(fields, "fields")
+    return fields
+
+
+def _field_frames(frames: torch.Tensor, side: Side, size: Optional[Tuple[int, int]]) -> Tuple[int, int, int, int]:
+    """(N, c, h, w) of frames the deinterlacer takes (`_sad_layout`'s, N = 0 allowed); refuses float frames and frames whose matrices
+    have one row."""
+    from .deinterlace import check_frame_rows
+    if isinstance(frames, torch.Tensor) and not size and frames.is_floating_point():
+        raise ValueError("float frames have no integer samples to deinterlace: give [N, h, w, c] uint8 or planar frames (quantise first)")
+    if isinstance(frames, torch.Tensor) and frames.dim() and int(frames.shape[0]) == 0:
+        n, c, h, w = (0,) + _sad_layout(frames.new_zeros((1,) + tuple(frames.shape[1:])), side, size)[1:]
+    else:
+        n, c, h, w = _sad_layout(frames, side, size)
+    check_frame_rows(h, side.layout)
+    return n, c, h, w
+
+
+def _deinterlace_device(frames: torch.Tensor, order: str, side: Side, size: Optional[Tuple[int, int]], lo: int = 0, hi: Optional[int] = None) -> torch.Tensor:
+    """savsr_video_deinterlace_* on resident frames of the input side on the GPU: the 2 (hi - lo) progressive frames of source frames
+    [lo, hi) (default: all), prev / next taken among the resident frames and clamped there.  One call per plane, on the current stream."""
+    from . import _lib
+    from .deinterlace import FIELD_ORDERS
+    n, c, h, w = _field_frames(frames, side, size)
+    hi = n if hi is None else hi
+    frames = frames.contiguous()
+    out = frames.new_empty((2 * (hi - lo),) + tuple(frames.shape[1:]))
+    if hi <= lo:
+        return out
+    lib = _lib.load()
+    oid = FIELD_ORDERS.index(order)
+    with torch.cuda.device(frames.device):
+        st = torch.cuda.current_stream().cuda_stream
+        if not size:
+            _lib.check(lib.savsr_video_deinterlace_u8(frames.data_ptr(), n, h * w * c, 0, h, w * c, c, oid, lo, hi, out.data_ptr(), h * w * c, 0, st),
+                       "savsr_video_deinterlace_u8")
+            return out
+        fb = side.frame_bytes(h, w)
+        for off, ph, pb, _, _ in _plane_table(h, w, side):
+            if side.depth == 8:
+                _lib.check(lib.savsr_video_deinterlace_u8(frames.data_ptr(), n, fb, off, ph, pb, 1, oid, lo, hi, out.data_ptr(), fb, off, st),
+                           "savsr_video_deinterlace_u8")
+            else:
+                _lib.check(lib.savsr_video_deinterlace_u16(frames.data_ptr(), n, fb, off, ph, pb // 2, side.depth, oid, lo, hi, out.data_ptr(), fb, off, st),
+                           "savsr_video_deinterlace_u16")
+    return out
+
+
+def deinterlace(frames: torch.Tensor, order: str, pixel_format: str = "rgb", size=None, depth: int = 8) -> torch.Tensor:
+    """Interlaced video as progressive frames at the field rate: 2N frames on the GPU in the format of the N given ones
+    (savsr_amd.deinterlace.deinterlace_frames is the specification, bit for bit), on the caller's current stream, without a sync.  Output
+    frame 2n + f keeps field f of source frame n (order "tff": the top field is the earlier one; "bff": the bottom one) and interpolates
+    the other rows by ffmpeg yadif's rule.  frames: [N, h, w, c] uint8 (GPU or host, c in 1 .. 3), or with pixel_format "i420", "i422",
+    "i444", "y400" and size=(h, w): [N, frame_bytes] uint8, every plane on its own, 16-bit samples at depth 10 / 12.  Float frames are
+    refused, and so are frames of one row (three for 4:2:0: the chroma planes need two)."""
+    from .deinterlace import check_order
+    check_order(order)
+    side, size = _sad_side(pixel_format, size, depth)
+    _field_frames(frames, side, size)
+    return _deinterlace_device(_to_device(frames, _sad_device(frames)), order, side, size)
+
+
+class FieldSplitter:
+    """The streaming deinterlacer behind VideoUpscaler(fields=...): push(source frames on the GPU) returns the progressive frames that are
+    final, finish() the last source frame's two.  The second field of the last pushed frame needs the frame after it, so one source frame
+    is held back; with the frame before it (the temporal context) the device keeps at most two source frames between pushes (copies of
+    their own, so that the chunk they came with is released).  Concatenated, the outputs are `deinterlace` on the whole video for any
+    chunking.  finish() without a pushed frame returns None."""
+
+    def __init__(self, order: str, side: Side, size: Optional[Tuple[int, int]]):
+        self.order, self.side, self.size = _check_fields(order), side, size
+        self._src: Optional[torch.Tensor] = None          # source frames [seen - len, seen): the context frame, then the ones not done
+        self._todo = 0                                    # how many of them are not deinterlaced yet (they are the last ones)
+
+    def push(self, frames: torch.Tensor) -> torch.Tensor:
+        k = int(frames.shape[0])
+        src = frames.contiguous() if self._src is None else torch.cat([self._src, frames], 0)
+        n = int(src.shape[0])
+        lo, hi = n - self._todo - k, n - 1                # all but the last frame, whose next is not known yet
+        res = _deinterlace_device(src, self.order, self.side, self.size, lo, max(hi, lo))
+        if hi > lo:
+            self._src, self._todo = src[max(hi - 1, 0):].clone(), 1          # (a copy of two frames: the chunk's storage is released)
+        else:
+            self._src, self._todo = src, self._todo + k
+        return res
+
+    @property
+    def held(self) -> int:
+        """Source frames on the device between pushes: at most two."""
+        return 0 if self._src is None else int(self._src.shape[0])
+
+    def finish(self) -> Optional[torch.Tensor]:
+        src, self._src = self._src, None
+        if src is None or self._todo == 0:          # nothing was pushed (or finish() ran before)
+            return None
+        n = int(src.shape[0])
+        return _deinterlace_device(src, self.order, self.side, self.size, n - self._todo, n)
+
+
 def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
                   size=None, cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601",
                   out_colour: Optional[str] = None, depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None,
                   out_siting: Optional[str] = None, chroma_filter: Optional[str] = None, crop=None, crop_limit=24,
-                  bars: str = "keep") -> torch.Tensor:
+                  bars: str = "keep", fields: Optional[str] = None) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
     spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter)
     sc = as_scale(net.scale if scale is None else scale)
     n, h, w = spec.frames_hw(frames)
+    if _check_fields(fields) is not None:          # everything below sees the progressive video of 2N frames
+        _field_frames(frames, spec.inp, spec.size)
+        n *= 2
     crop = _check_crop_args(crop, crop_limit, bars)
     if crop is not None and crop != "auto":
         from . import active
@@ -628,6 +740,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     if dev.type != "cuda":
         raise RuntimeError("savsr_amd runs on an AMD GPU only: move the network to the GPU (net.cuda()) first")
     frames = _to_device(frames, dev)
+    if fields is not None:             # deinterlacing comes first, before the crop
+        frames = _deinterlace_device(frames, fields, spec.inp, spec.size)
     full = spec
     if crop == "auto":
         crop = _detect_device(frames, spec.inp, spec.size, crop_limit)
@@ -677,12 +791,18 @@ class VideoUpscaler:
 
     crop=(y0, x0, ah, aw), bars="keep" / "drop": as in upscale_video, with an explicit rect only ("auto" needs the whole video: detect
     first with savsr_amd.detect_active_area).  Chunks are checked against the full frame size and cropped as they arrive, so the device
-    buffer holds cropped frames; `spec` is the VideoSpec of the cropped size."""
+    buffer holds cropped frames; `spec` is the VideoSpec of the cropped size.
+
+    fields="tff" / "bff": interlaced chunks, as in upscale_video.  Every source frame becomes two progressive frames as soon as the frame
+    after it has been pushed (its second field reads that frame), so push() holds the last source frame back and finish() flushes it with
+    next = cur; the cuts, the crop and the windows operate on the progressive frames as they are produced, and explicit cuts index them.
+    Concatenated, the outputs are upscale_video(fields=...) on the whole video for any chunking.  Beside the frames kept without fields
+    the device keeps at most two more source frames between pushes: the held frame and the one before it (savsr_amd.video.FieldSplitter)."""
 
     def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb", size=None,
                  cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None,
                  depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
-                 chroma_filter: Optional[str] = None, crop=None, bars: str = "keep"):
+                 chroma_filter: Optional[str] = None, crop=None, bars: str = "keep", fields: Optional[str] = None):
         _check_net(net)
         check_padding(padding)
         check_out(out, net.cfg["num_in_ch"], chroma_filter)          # (speaks before the cuts, video_spec after them: the order of refusals)
@@ -698,6 +818,7 @@ class VideoUpscaler:
         # the frames on both sides, checked once, here; the luma-only path (`luma_mode`) is decided with them
         self.spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter)
         self._full = self.spec                     # the spec of the chunks as pushed; `spec` becomes the cropped size's with a crop
+        self._split = None if _check_fields(fields) is None else FieldSplitter(fields, self.spec.inp, self.spec.size)          # None: as it was
         self._rect = _check_crop_args(crop, 24, bars, auto_ok=False)          # the rect to crop every chunk to; None: no crop, as it was
         self._place = None                         # active.place's six numbers with bars="keep", once the frame size is known
         self.bars = bars
@@ -764,6 +885,23 @@ class VideoUpscaler:
     def push(self, frames: torch.Tensor) -> torch.Tensor:
         if self._finished:
             raise RuntimeError("push() after finish()")
+        if self._split is not None:                # interlaced chunks: the progressive frames that are final go on as a chunk of their own
+            _field_frames(frames, self._full.inp, self._full.size)
+            k, h, w = self._full.frames_hw(frames)
+            dev = self.net.gamma.device
+            if dev.type != "cuda":
+                raise RuntimeError("savsr_amd runs on an AMD GPU only: move the network to the GPU (net.cuda()) first")
+            if self._shape is not None and (True, h, w) != self._shape:
+                raise ValueError(f"chunk of uint8 {h} x {w} frames after uint8 {self._shape[1]} x {self._shape[2]} ones")
+            frames = self._split.push(_to_device(frames, dev))
+            if int(frames.shape[0]) == 0:          # (a first push of one frame: nothing is final yet)
+                if self._shape is None and self._rect is not None and not self._full.size:
+                    self._set_rect(h, w)
+                self._shape = (True, h, w)
+                return self._empty()
+        return self._push(frames)
+
+    def _push(self, frames: torch.Tensor) -> torch.Tensor:
         k, h, w = self._full.frames_hw(frames)
         shape = (frames.dtype == torch.uint8, h, w)
         if self._shape is not None and shape != self._shape:
@@ -830,6 +968,13 @@ class VideoUpscaler:
         if self._finished:
             raise RuntimeError("finish() called twice")
         self._finished = True
+        last = None if self._split is None else self._split.finish()          # the held source frame's two fields, then the end as ever
+        if last is not None:
+            head = self._push(last)
+            return torch.cat([head, self._finish()], 0)
+        return self._finish()
+
+    def _finish(self) -> torch.Tensor:
         if self.seen == 0:
             raise ValueError("the video has no frames")
         if self._plan is not None:

@@ -64,7 +64,9 @@ the specification of savsr_video_gather_yuvs / savsr_video_quantize_yuvs).  Wher
                 Hrow(2 cy) alone on the last row of an odd H.  topleft, 4:2:0: ((Hrow(2 cy - 1) + Hrow(2 cy + 1)) + (Hrow(2 cy) +
                 Hrow(2 cy))) * 0.25, rows clamped.  `_row`, the product by k, rint and the full-range clip follow as without a siting.
 
-Filters longer than linear, PAL-DV's alternating Cb / Cr lines (read as topleft, as ffmpeg does), interlaced 4:2:0 and 4:1:1 are not modelled.
+Filters longer than linear, PAL-DV's alternating Cb / Cr lines (read as topleft, as ffmpeg does), the vertical chroma positions of
+interlaced 4:2:0 (savsr_amd/deinterlace.py turns the fields into progressive frames first; the planes are then read as progressive ones) and
+4:1:1 are not modelled.
 """
 from __future__ import annotations
 

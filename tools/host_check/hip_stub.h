@@ -1,0 +1,43 @@
+// Host stand-ins for the few HIP names csrc/deinterlace.hip uses, so that its device functions compile unchanged into a stand-alone host
+// program (tools/check_deinterlace_host.py): a launch runs the kernel body one thread at a time over the grid.  Host only; nothing here
+// is loaded into Python or run on a GPU.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#define __device__
+#define __global__
+#define __forceinline__ inline
+#define __launch_bounds__(x)
+#define __restrict__
+struct dim3 {
+    unsigned x, y, z;
+    dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {}
+};
+static dim3 threadIdx, blockIdx;
+using std::max;
+using std::min;
+typedef void* hipStream_t;
+#define SAVSR_E_ARG (-1)
+static char g_last_error[256];
+namespace savsr {
+inline int fail_arg(const char* what) {
+    snprintf(g_last_error, sizeof g_last_error, "invalid argument: %s", what);
+    return SAVSR_E_ARG;
+}
+inline int check_launch(const char*) { return 0; }
+}  // namespace savsr
+template <class F>
+void run_grid(F body, dim3 grid, dim3 block) {
+    for (unsigned z = 0; z < grid.z; ++z)
+        for (unsigned y = 0; y < grid.y; ++y)
+            for (unsigned x = 0; x < grid.x; ++x)
+                for (unsigned t = 0; t < block.x; ++t) {
+                    blockIdx = dim3(x, y, z);
+                    threadIdx = dim3(t, 0, 0);
+                    body();
+                }
+}
+#define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) run_grid([&]() { kernel(__VA_ARGS__); }, grid, block)
