@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 43
+#define SAVSR_ABI_VERSION 44
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -655,6 +655,36 @@ int savsr_video_deinterlace_u8(const uint8_t* frames, int n_frames, int64_t fram
                                int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
 int savsr_video_deinterlace_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int depth,
                                 int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 44) Inverse 3:2 pulldown (pulldown.hip; savsr_amd.field_scores, savsr_amd.remove_pulldown, upscale_video(pulldown=...),
+ * VideoUpscaler(pulldown=...), --pulldown of python -m savsr_amd.upscale): the field-match scores and the weave of
+ * telecined film (savsr_amd/pulldown.py `field_scores` and `weave` restate them; the kernels equal them bit for bit; the match, the
+ * decimation and the cadence-free rule itself are host work on these scores and on savsr_video_pair_sad_*).  Matrices are addressed as for
+ * savsr_video_deinterlace_*: matrix k of the n_frames resident frames starts at frames + k * frame_bytes + plane_offset, its rows follow
+ * each other directly; the first field is the rows of parity `order` (0: top field first, 1: bottom field first).  The entries only
+ * enqueue, allocate nothing, do not synchronise and are capturable.  Refused before the device is touched with SAVSR_E_ARG,
+ * savsr_last_error() naming the reason: a null pointer, n_frames < 1, rows < 1, an empty row, a plane above 2147418112 bytes, an order
+ * other than 0 / 1, a range outside 0 <= from <= to <= n_frames (from == to: nothing is done), a negative plane offset, a frame stride
+ * smaller than the offset plus the plane, an `out` of scores that is not 8-byte aligned; _u16: a depth other than 10 / 12, an odd pointer,
+ * stride or offset.  16-byte accesses when the plane pointers, the frame strides and a row's bytes are multiples of 16, a sample per
+ * access otherwise (any pointer, stride and size).
+ * savsr_video_field_scores_u8:  out[2 (n - from) + j], n in [from, to): the sum over the second field's rows y, 1 <= y <= rows - 2, and all
+ *                           x of |a - b| + |c - b| - |a - c|, a / c = frame n at rows y - 1 / y + 1, b = row y of frame max(n - 1, 0)
+ *                           (j = 0) or of frame n (j = 1); zeros when rows < 3.  `out` is zeroed by one hipMemsetAsync on `stream` first.
+ *                           A streaming caller passes its context frame and the range.
+ * savsr_video_field_scores_u16: the same on rows x cols little-endian 16-bit samples, each read as min(s, 2^depth - 1) >> (depth - 8).
+ * savsr_video_weave:        output frame n - from at out + (n - from) * out_frame_bytes + out_plane_offset: the rows of parity `order` of
+ *                           frame n, the others of frame n + delta[n - from] clamped into [0, n_frames).  delta: a DEVICE table of
+ *                           to - from int32, -1 or 0; the entry cannot see it, so the kernel clamps the frame index: a wrong table reads
+ *                           a wrong frame, never outside the buffer.  A byte copy, so it serves every depth (row_bytes = 2 * cols at
+ *                           10 / 12 bits); one launch per plane.  The source and the output must not overlap. */
+int savsr_video_field_scores_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes, int order,
+                                int from, int to, int64_t* out, void* stream);
+int savsr_video_field_scores_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int depth,
+                                 int order, int from, int to, int64_t* out, void* stream);
+int savsr_video_weave(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes, int order, int from,
+                      int to, const int32_t* delta, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 33) Geometric self-ensemble (ensemble.hip; SAVSR.set_self_ensemble).  Variant k = 0 .. 7: fw = k & 1 flips

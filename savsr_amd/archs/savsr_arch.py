@@ -280,7 +280,8 @@ class SAVSR(nn.Module):
     def upscale_video(self, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
                       size=None, cuts=None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None, depth: int = 8,
                       out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
-                      chroma_filter: Optional[str] = None, crop=None, crop_limit=24, bars: str = "keep", fields: Optional[str] = None) -> torch.Tensor:
+                      chroma_filter: Optional[str] = None, crop=None, crop_limit=24, bars: str = "keep", fields: Optional[str] = None,
+                      pulldown: Optional[str] = None, pulldown_cycle: int = 5) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -334,11 +335,18 @@ class SAVSR(nn.Module):
         the result is, bit for bit, upscale_video on savsr_amd.deinterlace(frames, fields, ...) with every other argument the same, so the
         length check, the crop, the cuts (explicit ones index the 2N frames: a cut at source frame k is 2k) and the windows all see the
         progressive video.  uint8 and planar frames only (float frames have no integer samples).  None (the default) runs what ran before.
+        pulldown: None, "tff" or "bff", for telecined film (3:2 pulldown) with that field order; pulldown_cycle (default 5): one frame in
+        so many is the repeated one.  The N frames become the N - N // pulldown_cycle film frames before anything else looks at them
+        (savsr_amd.pulldown: every frame keeps its first field and takes the second from itself or its predecessor, whichever combs less;
+        of every cycle the woven frame closest to its predecessor is dropped; on the GPU, two host synchronisations): the result is, bit
+        for bit, upscale_video on savsr_amd.remove_pulldown(frames, pulldown, ...) with every other argument the same, and explicit cuts
+        index the film frames.  Not together with fields.  No cadence tracking; see savsr_amd/pulldown.py for the limits.  None (the
+        default) runs what ran before.
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
         return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold, colour, out_colour, depth, out_depth,
-                             siting, out_siting, chroma_filter, crop, crop_limit, bars, fields)
+                             siting, out_siting, chroma_filter, crop, crop_limit, bars, fields, pulldown, pulldown_cycle)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

@@ -1,0 +1,327 @@
+// Inverse 3:2 pulldown (ABI 44): the field-match scores and the weave of telecined film (savsr_amd/pulldown.py `field_scores` and `weave`
+// are the specification; the kernels equal them bit for bit, the match and the decimation are decided on the host in exact arithmetic).
+// The first field is the rows of parity p (0 for tff, 1 for bff), the second field the rows of parity 1 - p.
+//
+// Scores.  Source frame n has two candidates for its second field: j = 0 the second field of frame max(n - 1, 0), j = 1 its own.  A
+// candidate's score is the sum over the second field's rows y, 1 <= y <= rows - 2 (y = 1 + p + 2 s, s = 0 .. (rows - 1 - p) / 2 - 1),
+// and all x of |a - b| + |c - b| - |a - c|, a = F[n][y - 1], c = F[n][y + 1], b the candidate's sample: never negative, and an exact
+// integer in any order, so the grid shape and the atomics change nothing in the result.
+//
+//   _u8    matrices of rows x row_bytes bytes (a plane, or the h x (w * c) bytes of packed frames: only vertical neighbours meet)
+//   _u16   matrices of rows x cols little-endian 16-bit samples, every sample read as min(s, 2^depth - 1) >> (depth - 8)
+//
+// One launch per call after one hipMemsetAsync of the scores; grid = (lane tiles over scored rows x row pieces, frame).  Vector form
+// (plane base pointer, frame stride and row bytes multiples of 16): a lane owns 16 bytes of one second-field row and issues its four
+// 16-byte nontemporal loads (a, c, the frame's own b and the previous frame's b) before the first use; v_sad_u8 per dword, |a - c|
+// shared by both candidates; no LDS staging of rows: the rows above and below are read by the two neighbouring scored rows as well and
+// come from L2.  One-sample form (any pointer, stride and row length): a lane owns PD_ONE_ITERS samples.  Lane sums are 32-bit, reduced
+// over the wave by __shfl_xor, over the workgroup through 8 LDS words, then one 64-bit vector atomic per workgroup and candidate.
+//
+// Weave.  Output frame o of source frame n = from + o: the rows of parity p from frame n, the others from frame clamp(n + delta[o], 0,
+// n_frames - 1); delta is a device table the entry cannot see, so the kernel clamps.  A byte copy at every depth: a 16-byte form and a
+// byte form, one launch per plane.
+#include "common.hpp"
+
+#include <cstdint>
+
+namespace savsr {
+namespace {
+
+constexpr int PD_THREADS = 256;
+constexpr int PD_ONE_ITERS = 8;                     // samples (bytes, for the weave) per lane in the one-sample forms
+constexpr int PD_MAX_Y = 65535;                     // grid.y: frames per launch
+constexpr long long PD_MAX_PLANE = 0x7fff0000ll;    // bytes of a plane: the lane tiles of a frame fit grid.x and 32-bit counts
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// |a.b0 - b.b0| + ... + |a.b3 - b.b3| + acc over the four bytes of a dword: one v_sad_u8
+__device__ __forceinline__ uint32_t pd_sad4(uint32_t a, uint32_t b, uint32_t acc) {
+#if __has_builtin(__builtin_amdgcn_sad_u8)
+    return __builtin_amdgcn_sad_u8(a, b, acc);
+#else
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int d = (int)((a >> (8 * e)) & 255u) - (int)((b >> (8 * e)) & 255u);
+        acc += (uint32_t)(d < 0 ? -d : d);
+    }
+    return acc;
+#endif
+}
+
+// |a.lo - b.lo| + |a.hi - b.hi| + acc over the two 16-bit halves of a dword: one v_sad_u16
+__device__ __forceinline__ uint32_t pd_sad2(uint32_t a, uint32_t b, uint32_t acc) {
+#if __has_builtin(__builtin_amdgcn_sad_u16)
+    return __builtin_amdgcn_sad_u16(a, b, acc);
+#else
+    const uint32_t al = a & 0xffffu, bl = b & 0xffffu, ah = a >> 16, bh = b >> 16;
+    return acc + (al > bl ? al - bl : bl - al) + (ah > bh ? ah - bh : bh - ah);
+#endif
+}
+
+__device__ __forceinline__ uint32_t pd_absdiff(uint32_t a, uint32_t b) { return a > b ? a - b : b - a; }
+
+// Two 16-bit samples of a dword -> their 8 most significant bits of `depth`, each in its half: min(s, top) >> shift.
+__device__ __forceinline__ uint32_t pd_msb8x2(uint32_t x, uint32_t top, int shift) {
+    return (min(x & 0xffffu, top) >> shift) | ((min(x >> 16, top) >> shift) << 16);
+}
+
+// What a score launch works on.  Rows are `pitch` bytes apart.
+struct ScoreJob {
+    const uint8_t* src;          // the matrix of resident frame 0
+    long long stride, pitch;     // bytes between frames / rows
+    int n_frames, from, cols;    // cols: samples of a row
+    int y0, srows;               // the scored rows: y0 + 2 s, s = 0 .. srows - 1
+    uint32_t top;                // 2^depth - 1
+    int shift;                   // depth - 8
+};
+
+// The two lane sums of a workgroup -> one 64-bit vector atomic per candidate on cell[0] / cell[1].  A lane sum is at most
+// PD_ONE_ITERS (or 16, the bytes of a vector lane's row piece) x 3 x 255 <= 12240, a workgroup's at most 256 x 12240 < 2^22: the 32-bit
+// partials cannot overflow whatever the frame size, because a lane never holds more than one row piece.
+__device__ __forceinline__ void pd_block_add(uint32_t acc0, uint32_t acc1, unsigned long long* cell) {
+#ifdef SAVSR_HOST_CHECK          // the host check runs one thread at a time: every thread adds its own sums
+    if (acc0) atomicAdd(cell, (unsigned long long)acc0);
+    if (acc1) atomicAdd(cell + 1, (unsigned long long)acc1);
+#else
+    __shared__ uint32_t part[2][PD_THREADS / 64];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        acc0 += __shfl_xor(acc0, o, 64);
+        acc1 += __shfl_xor(acc1, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        part[0][threadIdx.x >> 6] = acc0;
+        part[1][threadIdx.x >> 6] = acc1;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        unsigned long long s = 0;
+#pragma unroll
+        for (int i = 0; i < PD_THREADS / 64; ++i) s += part[threadIdx.x][i];
+        if (s) atomicAdd(cell + threadIdx.x, s);
+    }
+#endif
+}
+
+// Vector form: lane = (scored row s, 16-byte chunk) = (idx / chunks, idx % chunks), idx = blockIdx.x * PD_THREADS + threadIdx.x; frame
+// blockIdx.y of the launch.  BYTES: of a sample.
+template <int BYTES>
+__global__ __launch_bounds__(PD_THREADS) void field_scores_vec_kernel(ScoreJob jb, unsigned long long* __restrict__ out) {
+    const uint32_t chunks = (uint32_t)(jb.pitch >> 4);
+    const uint32_t idx = blockIdx.x * PD_THREADS + threadIdx.x;
+    const uint32_t s = idx / chunks, chunk = idx - s * chunks;
+    uint32_t acc0 = 0, acc1 = 0;
+    if (s < (uint32_t)jb.srows) {
+        const int n = jb.from + (int)blockIdx.y;
+        const int np = n > 0 ? n - 1 : 0;
+        const long long y = jb.y0 + 2ll * s;
+        const uint8_t* cur = jb.src + (long long)n * jb.stride + y * jb.pitch;
+        const uint8_t* prev = jb.src + (long long)np * jb.stride + y * jb.pitch;
+        const u32x4 a = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(cur - jb.pitch) + chunk);
+        const u32x4 c = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(cur + jb.pitch) + chunk);
+        const u32x4 b1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(cur) + chunk);
+        const u32x4 b0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(prev) + chunk);
+        uint32_t ac = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if constexpr (BYTES == 1) {
+                ac = pd_sad4(a[e], c[e], ac);
+                acc0 = pd_sad4(c[e], b0[e], pd_sad4(a[e], b0[e], acc0));
+                acc1 = pd_sad4(c[e], b1[e], pd_sad4(a[e], b1[e], acc1));
+            } else {
+                const uint32_t ae = pd_msb8x2(a[e], jb.top, jb.shift), ce = pd_msb8x2(c[e], jb.top, jb.shift);
+                const uint32_t p0 = pd_msb8x2(b0[e], jb.top, jb.shift), p1 = pd_msb8x2(b1[e], jb.top, jb.shift);
+                ac = pd_sad2(ae, ce, ac);
+                acc0 = pd_sad2(ce, p0, pd_sad2(ae, p0, acc0));
+                acc1 = pd_sad2(ce, p1, pd_sad2(ae, p1, acc1));
+            }
+        }
+        acc0 -= ac;          // per sample |a - b| + |c - b| >= |a - c|: the sums stay >= 0
+        acc1 -= ac;
+    }
+    pd_block_add(acc0, acc1, out + 2 * blockIdx.y);
+}
+
+template <int BYTES>
+__device__ __forceinline__ uint32_t pd_sample(const uint8_t* row, uint32_t x, uint32_t top, int shift) {
+    if constexpr (BYTES == 1) return row[x];
+    else return min((uint32_t)reinterpret_cast<const uint16_t*>(row)[x], top) >> shift;
+}
+
+// One-sample form: sample i = (scored row, x) = (i / cols, i % cols), i = blockIdx.x * (PD_THREADS * PD_ONE_ITERS) + it * PD_THREADS + tid.
+template <int BYTES>
+__global__ __launch_bounds__(PD_THREADS) void field_scores_one_kernel(ScoreJob jb, unsigned long long* __restrict__ out) {
+    const int n = jb.from + (int)blockIdx.y;
+    const int np = n > 0 ? n - 1 : 0;
+    const uint8_t* cur = jb.src + (long long)n * jb.stride;
+    const uint8_t* prev = jb.src + (long long)np * jb.stride;
+    const uint32_t total = (uint32_t)jb.srows * (uint32_t)jb.cols;
+    const uint32_t i0 = blockIdx.x * (PD_THREADS * PD_ONE_ITERS) + threadIdx.x;
+    uint32_t acc0 = 0, acc1 = 0;
+#pragma unroll 2
+    for (int it = 0; it < PD_ONE_ITERS; ++it) {
+        const uint32_t i = i0 + it * PD_THREADS;
+        if (i < total) {
+            const uint32_t s = i / (uint32_t)jb.cols, x = i - s * (uint32_t)jb.cols;
+            const long long off = (jb.y0 + 2ll * s) * jb.pitch;
+            const uint32_t a = pd_sample<BYTES>(cur + off - jb.pitch, x, jb.top, jb.shift), c = pd_sample<BYTES>(cur + off + jb.pitch, x, jb.top, jb.shift);
+            const uint32_t b0 = pd_sample<BYTES>(prev + off, x, jb.top, jb.shift), b1 = pd_sample<BYTES>(cur + off, x, jb.top, jb.shift);
+            const uint32_t ac = pd_absdiff(a, c);
+            acc0 += pd_absdiff(a, b0) + pd_absdiff(c, b0) - ac;
+            acc1 += pd_absdiff(a, b1) + pd_absdiff(c, b1) - ac;
+        }
+    }
+    pd_block_add(acc0, acc1, out + 2 * blockIdx.y);
+}
+
+inline unsigned pd_blocks(long long units, int per_block) { return (unsigned)((units + per_block - 1) / per_block); }
+
+template <int BYTES>
+int launch_scores(ScoreJob jb, int n_out, int64_t* out, hipStream_t st, const char* what) {
+    hipError_t e = hipMemsetAsync(out, 0, sizeof(int64_t) * 2 * (size_t)n_out, st);
+    if (e != hipSuccess) { set_error("%s: hipMemsetAsync failed: %s", what, hipGetErrorString(e)); return (int)e; }
+    if (jb.srows < 1) return 0;          // fewer than three rows, or no second-field row between two others: zeros
+    const bool vec = (reinterpret_cast<uintptr_t>(jb.src) & 15) == 0 && jb.stride % 16 == 0 && jb.pitch % 16 == 0;
+    const unsigned gx = vec ? pd_blocks((long long)jb.srows * (jb.pitch >> 4), PD_THREADS)
+                            : pd_blocks((long long)jb.srows * jb.cols, PD_THREADS * PD_ONE_ITERS);
+    for (int f0 = 0; f0 < n_out; f0 += PD_MAX_Y) {
+        const int nf = n_out - f0 < PD_MAX_Y ? n_out - f0 : PD_MAX_Y;
+        ScoreJob part = jb;
+        part.from = jb.from + f0;
+        unsigned long long* cells = reinterpret_cast<unsigned long long*>(out) + 2ll * f0;
+        if (vec) hipLaunchKernelGGL((field_scores_vec_kernel<BYTES>), dim3(gx, (unsigned)nf), dim3(PD_THREADS), 0, st, part, cells);
+        else hipLaunchKernelGGL((field_scores_one_kernel<BYTES>), dim3(gx, (unsigned)nf), dim3(PD_THREADS), 0, st, part, cells);
+        if (int rc = check_launch(vec ? "field_scores_vec_kernel" : "field_scores_one_kernel")) return rc;
+    }
+    return 0;
+}
+
+// What a weave launch works on.  Rows are `pitch` bytes apart on both sides.
+struct WeaveJob {
+    const uint8_t* src;          // the plane of resident frame 0
+    uint8_t* dst;                // the plane of output frame 0
+    const int32_t* delta;        // device: one of -1, 0 per output frame of the launch
+    long long src_stride, dst_stride, pitch;
+    int n_frames, from, rows, parity;
+};
+
+// The source row of output row y of output frame o: frame n where y has the first field's parity, else frame clamp(n + delta[o]).
+__device__ __forceinline__ const uint8_t* weave_row(const WeaveJob& jb, int o, uint32_t y) {
+    const int n = jb.from + o;
+    int m = n;
+    if ((int)(y & 1u) != jb.parity) {
+        m = n + jb.delta[o];
+        m = m < 0 ? 0 : (m > jb.n_frames - 1 ? jb.n_frames - 1 : m);
+    }
+    return jb.src + (long long)m * jb.src_stride + (long long)y * jb.pitch;
+}
+
+// 16-byte form: lane = (row, chunk) = (idx / chunks, idx % chunks); output frame blockIdx.y of the launch.
+__global__ __launch_bounds__(PD_THREADS) void weave_vec_kernel(WeaveJob jb) {
+    const uint32_t chunks = (uint32_t)(jb.pitch >> 4);
+    const uint32_t idx = blockIdx.x * PD_THREADS + threadIdx.x;
+    const uint32_t y = idx / chunks, chunk = idx - y * chunks;
+    if (y >= (uint32_t)jb.rows) return;
+    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(weave_row(jb, (int)blockIdx.y, y)) + chunk);
+    *(reinterpret_cast<u32x4*>(jb.dst + (long long)blockIdx.y * jb.dst_stride + (long long)y * jb.pitch) + chunk) = v;
+}
+
+// Byte form: byte i = (row, x) = (i / pitch, i % pitch), PD_ONE_ITERS bytes per lane.
+__global__ __launch_bounds__(PD_THREADS) void weave_one_kernel(WeaveJob jb) {
+    const uint32_t pitch = (uint32_t)jb.pitch, total = (uint32_t)jb.rows * pitch;
+    const uint32_t i0 = blockIdx.x * (PD_THREADS * PD_ONE_ITERS) + threadIdx.x;
+    uint8_t* dst = jb.dst + (long long)blockIdx.y * jb.dst_stride;
+#pragma unroll 2
+    for (int it = 0; it < PD_ONE_ITERS; ++it) {
+        const uint32_t i = i0 + it * PD_THREADS;
+        if (i < total) {
+            const uint32_t y = i / pitch, x = i - y * pitch;
+            dst[i] = weave_row(jb, (int)blockIdx.y, y)[x];
+        }
+    }
+}
+
+// The checks of a matrix inside resident frames; nullptr or the reason.
+const char* check_matrix(const void* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int64_t row_bytes, int order, int from,
+                         int to) {
+    if (!frames) return "null pointer";
+    if (n_frames < 1) return "n_frames >= 1";
+    if (rows < 1) return "rows >= 1";
+    if (row_bytes < 1) return "a row holds at least one sample";
+    if ((long long)rows * row_bytes > PD_MAX_PLANE) return "a plane of at most 2147418112 bytes";
+    if (order != 0 && order != 1) return "order 0 (tff) or 1 (bff)";
+    if (from < 0 || to > n_frames || from > to) return "the range needs 0 <= from <= to <= n_frames";
+    if (plane_offset < 0) return "plane offsets >= 0";
+    if (frame_bytes < plane_offset + (int64_t)rows * row_bytes) return "frame_bytes smaller than plane_offset plus the rows x row_bytes plane";
+    return nullptr;
+}
+
+int refuse(const char* who, const char* why) {
+    char msg[192];
+    snprintf(msg, sizeof msg, "%s: %s", who, why);
+    return fail_arg(msg);
+}
+
+ScoreJob score_job(const uint8_t* frames, int64_t frame_bytes, int64_t plane_offset, int n_frames, int from, int rows, int64_t row_bytes, int cols,
+                   int order, int depth) {
+    const int srows = rows - 1 - order > 0 ? (rows - 1 - order) / 2 : 0;
+    return ScoreJob{frames + plane_offset, frame_bytes, row_bytes, n_frames, from, cols, 1 + order, srows, (1u << depth) - 1u, depth - 8};
+}
+
+}  // namespace
+}  // namespace savsr
+
+using namespace savsr;
+
+extern "C" int savsr_video_field_scores_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes,
+                                           int order, int from, int to, int64_t* out, void* stream) {
+    const char* who = "video_field_scores_u8";
+    if (const char* why = check_matrix(frames, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to)) return refuse(who, why);
+    if (!out && to > from) return refuse(who, "null pointer");
+    if (reinterpret_cast<uintptr_t>(out) & 7) return refuse(who, "out must be 8-byte aligned");
+    if (to == from) return 0;
+    return launch_scores<1>(score_job(frames, frame_bytes, plane_offset, n_frames, from, rows, row_bytes, row_bytes, order, 8), to - from, out,
+                            static_cast<hipStream_t>(stream), who);
+}
+
+extern "C" int savsr_video_field_scores_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols,
+                                            int depth, int order, int from, int to, int64_t* out, void* stream) {
+    const char* who = "video_field_scores_u16";
+    if (const char* why = check_matrix(frames, n_frames, frame_bytes, plane_offset, rows, 2 * (int64_t)cols, order, from, to)) return refuse(who, why);
+    if (depth != 10 && depth != 12) return refuse(who, "depth 10 or 12 (8 bits: savsr_video_field_scores_u8)");
+    if ((reinterpret_cast<uintptr_t>(frames) & 1) || ((frame_bytes | plane_offset) & 1))
+        return refuse(who, "frames, the frame stride and the plane offset must be 2-byte aligned (16-bit samples)");
+    if (!out && to > from) return refuse(who, "null pointer");
+    if (reinterpret_cast<uintptr_t>(out) & 7) return refuse(who, "out must be 8-byte aligned");
+    if (to == from) return 0;
+    return launch_scores<2>(score_job(frames, frame_bytes, plane_offset, n_frames, from, rows, 2 * (int64_t)cols, cols, order, depth), to - from, out,
+                            static_cast<hipStream_t>(stream), who);
+}
+
+extern "C" int savsr_video_weave(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes, int order,
+                                 int from, int to, const int32_t* delta, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
+                                 void* stream) {
+    const char* who = "video_weave";
+    if (const char* why = check_matrix(frames, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to)) return refuse(who, why);
+    if (to > from && (!delta || !out)) return refuse(who, "null pointer");
+    if (reinterpret_cast<uintptr_t>(delta) & 3) return refuse(who, "delta must be 4-byte aligned");
+    if (out_plane_offset < 0) return refuse(who, "plane offsets >= 0");
+    if (out_frame_bytes < out_plane_offset + (int64_t)rows * row_bytes) return refuse(who, "out_frame_bytes smaller than out_plane_offset plus the rows x row_bytes plane");
+    if (to == from) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    WeaveJob jb{frames + plane_offset, out + out_plane_offset, delta, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, order};
+    const bool vec = ((reinterpret_cast<uintptr_t>(jb.src) | reinterpret_cast<uintptr_t>(jb.dst)) & 15) == 0 && frame_bytes % 16 == 0 &&
+                     out_frame_bytes % 16 == 0 && row_bytes % 16 == 0;
+    const unsigned gx = vec ? pd_blocks((long long)rows * (row_bytes >> 4), PD_THREADS) : pd_blocks((long long)rows * row_bytes, PD_THREADS * PD_ONE_ITERS);
+    for (int f0 = 0; f0 < to - from; f0 += PD_MAX_Y) {
+        const int nf = to - from - f0 < PD_MAX_Y ? to - from - f0 : PD_MAX_Y;
+        WeaveJob part = jb;
+        part.from = from + f0;
+        part.delta = delta + f0;
+        part.dst = jb.dst + (long long)f0 * out_frame_bytes;
+        if (vec) hipLaunchKernelGGL(weave_vec_kernel, dim3(gx, (unsigned)nf), dim3(PD_THREADS), 0, st, part);
+        else hipLaunchKernelGGL(weave_one_kernel, dim3(gx, (unsigned)nf), dim3(PD_THREADS), 0, st, part);
+        if (int rc = check_launch(vec ? "weave_vec_kernel" : "weave_one_kernel")) return rc;
+    }
+    return 0;
+}

@@ -17,8 +17,8 @@ as min(s, 2^d - 1); kept rows are copied as they are.
 
 How far ffmpeg is followed: the arithmetic of an interior sample is yadif's.  The two border conditions (x +- 3s, y +- 2) and the
 mirrored up / dn rows are this project's; ffmpeg's edge handling differs in the outermost rows and columns.  ffmpeg is not available
-where this was written, so nothing here is pinned to its output.  There is no inverse telecine (3:2 pulldown material becomes 60p with
-repeated pictures), the temporal taps read across scene cuts as yadif's do (there the clamp widens and the spatial prediction stands),
+where this was written, so nothing here is pinned to its output.  Telecined film is not for this module (3:2 pulldown material becomes 60p with
+repeated pictures: savsr_amd/pulldown.py, `pulldown=`, recovers the film frames instead), the temporal taps read across scene cuts as yadif's do (there the clamp widens and the spatial prediction stands),
 and the rule is yadif's, not bwdif or a learned one.
 
 `savsr_amd.deinterlace` names this module and, called, the GPU function: `savsr_amd.deinterlace(frames, order, ...)` is

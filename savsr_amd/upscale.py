@@ -72,7 +72,16 @@ gives two), so the network's windows, --cuts and --crop work on pictures and not
 measure the deinterlaced video.  tff / bff name the field order, auto takes it from the Y4M input's I tag (It -> tff, Ib -> bff, Ip ->
 progressive; Im, mixed, is refused).  The output is then tagged Ip at twice the frame rate, and a PNG folder holds twice the files
 (%08d.png).  The default, progressive, is what this tool has always done: the frames go through as they are and the I tag is passed on;
-for an input tagged It / Ib / Im one line on stderr says so.  There is no inverse telecine.
+for an input tagged It / Ib / Im one line on stderr says so.  Telecined film is not interlaced video: see --pulldown.
+
+--pulldown: telecined film (3:2 pulldown: most NTSC film DVDs and broadcast film; four film frames lie in five video frames as the fields
+AA BB BC CD DD).  The film frames are recovered on the GPU before anything else sees them (savsr_amd/pulldown.py: every frame keeps its
+first field and takes the second from itself or from the frame before it, whichever combs less; of every --pulldown-cycle (default 5)
+woven frames the one closest to its predecessor is dropped), so the network runs 4 frames for every 5 read; K in --cuts K,... indexes the
+film frames.  tff / bff name the field order, auto takes it from the Y4M input's I tag as --fields auto does (Im is refused).  The
+output is tagged Ip at (cycle - 1) / cycle of the frame rate (30000:1001 -> 24000:1001), and a PNG folder holds the kept frames
+(%08d.png).  Not together with --fields tff / bff / auto: they are two answers to one question.  There is no cadence tracking: a cadence
+broken by an edit costs one real frame in that cycle, and a frame that matches neither neighbour stays combed.
 
 It ends with one line: frames, seconds, frames/s (on stderr when the video goes to stdout); with --cuts, the scene count as well; with
 --colour / --out-colour, the two colour spaces.
@@ -89,6 +98,7 @@ from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional
 
 from .deinterlace import FIELD_FLAGS, FIELD_ORDERS, resolve_fields
+from .pulldown import DEFAULT_CYCLE, PULLDOWN_FLAGS, check_cycle, resolve_pulldown
 from .yuv import COLOURS, SITINGS
 
 MAX_WRITERS = 16
@@ -202,6 +212,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="interlaced input: deinterlace on the GPU first, every frame giving two progressive ones at the field rate.  tff / bff: "
                         "the field order; auto: from the Y4M input's I tag (It, Ib; Im is refused); progressive (default): frames go through as "
                         "they are, the I tag is passed on")
+    p.add_argument("--pulldown", default=None, choices=list(PULLDOWN_FLAGS),
+                   help="telecined film (3:2 pulldown): recover the film frames on the GPU first, 4 for every 5 read.  tff / bff: the field "
+                        "order; auto: from the Y4M input's I tag (It, Ib; Im is refused); none (default): frames go through as they are")
+    p.add_argument("--pulldown-cycle", type=int, default=None, metavar="N",
+                   help="--pulldown: one frame in every N is the repeated one and is dropped (default 5; 2 .. 25)")
     p.add_argument("--bars", default=None, choices=["keep", "drop"],
                    help="--crop: keep = full-size output, the picture in nominal black (default); drop = the picture alone")
     return p
@@ -286,6 +301,19 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             resolve_fields(a.fields, None, (25, 1))          # (a Y4M input: once its header is read)
         except ValueError as e:
             p.error(str(e))
+    if a.pulldown in (None, "none"):
+        if a.pulldown_cycle is not None:
+            p.error("--pulldown-cycle goes with --pulldown auto, tff or bff")
+    elif a.fields in ("auto",) + FIELD_ORDERS:
+        p.error(f"--pulldown {a.pulldown} together with --fields {a.fields}: they are two answers to one question (telecined film, whose "
+                f"frames are recovered, or interlaced video, whose fields are interpolated); give one of them")
+    a.pulldown_cycle = DEFAULT_CYCLE if a.pulldown_cycle is None else a.pulldown_cycle
+    try:
+        check_cycle(a.pulldown_cycle, "--pulldown-cycle")
+        if not a.y4m_in:
+            resolve_pulldown(a.pulldown, None, (25, 1), a.pulldown_cycle)          # (a Y4M input: once its header is read)
+    except ValueError as e:
+        p.error(str(e))
     if a.fps is not None and (a.y4m_in or not a.y4m_out):
         p.error("--fps goes with a PNG folder in and Y4M out (a Y4M input carries its frame rate, PNGs have none)")
     if a.colour is not None and not a.y4m_in:
@@ -447,20 +475,23 @@ def written_lr(h, w, rect, bars: str):
     return (h, w) if rect is None or bars == "keep" else (rect[2], rect[3])
 
 
-def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev, order: Optional[str] = None):
+def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev, order: Optional[str] = None, film: Optional[str] = None):
     """--crop auto's first pass: savsr_amd.line_sums over the input in --chunk-sized pieces with a running maximum on the device, then
     cropdetect's rule and the alignment to the input layout's chroma block.  chunks: the PNG folder's chunk iterator; None: the .y4m file
     named by --input, read through a reader of its own.  order: --fields' field order; the sums are then taken on the deinterlaced frames
-    (a video.FieldSplitter of this pass's own), as the second pass will crop them."""
+    (a video.FieldSplitter of this pass's own), as the second pass will crop them.  film: --pulldown's field order; the sums are then taken
+    on the recovered film frames (a video.PulldownRemover of this pass's own)."""
     import torch
 
     from . import active
-    from .video import FieldSplitter, _sad_side, layout_of, line_sums
+    from .video import FieldSplitter, PulldownRemover, _sad_side, layout_of, line_sums
     from .y4m import Y4MReader
     from .yuv import CHROMAS
     top = None
     f = None
     split = None if order is None else FieldSplitter(order, *_sad_side(fmt_in, size, depth))
+    if film is not None:
+        split = PulldownRemover(film, *_sad_side(fmt_in, size, depth), a.pulldown_cycle)
 
     def fold(frames):
         nonlocal top
@@ -507,6 +538,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     net.set_precision(a.precision)
     net.set_self_ensemble(a.self_ensemble)
     n_png = None if paths is None else len(paths) * (2 if a.fields in FIELD_ORDERS else 1)          # (--fields: two frames per file)
+    if paths is not None and a.pulldown in FIELD_ORDERS:
+        n_png -= n_png // a.pulldown_cycle                        # (--pulldown: one frame of every cycle is dropped)
     if paths is not None and a.cuts is None:
         check_length(n_png, net.num_frame, a.padding)             # (before the GPU is touched; a Y4M stream's length: at its end)
     elif paths is not None and a.cuts != "auto":
@@ -547,19 +580,28 @@ def main(argv: Optional[List[str]] = None) -> int:
                 for c0 in range(0, len(paths), a.chunk):
                     yield torch.from_numpy(np.stack([store.host(p) for p in paths[c0:c0 + a.chunk]], 0))
             chunks = png_chunks()
-        try:                                        # --fields and the input's I tag: the field order, the output's I tag and frame rate
-            order, interlace, fps, note = resolve_fields(a.fields, interlace if a.y4m_in else None, fps)
+        try:                                        # --pulldown and the input's I tag: the field order, the output's I tag and frame rate
+            film, film_tag, film_fps, film_note = resolve_pulldown(a.pulldown, interlace if a.y4m_in else None, fps, a.pulldown_cycle)
         except ValueError as e:
             raise SystemExit(str(e)) from None
-        if note is not None:
-            print(note, file=sys.stderr, flush=True)
+        if film_note is not None:
+            print(film_note, file=sys.stderr, flush=True)
+        if film is not None:                        # (the fields are matched, not interpolated: --fields has nothing left to say)
+            order, interlace, fps = None, film_tag, film_fps
+        else:
+            try:                                    # --fields and the input's I tag: the field order, the output's I tag and frame rate
+                order, interlace, fps, note = resolve_fields(a.fields, interlace if a.y4m_in else None, fps)
+            except ValueError as e:
+                raise SystemExit(str(e)) from None
+            if note is not None:
+                print(note, file=sys.stderr, flush=True)
         dev = torch.device(a.device)
         net = net.to(dev)
         fmt_of = dict(FORMAT_OF, **{MONO: LUMA_FORMAT})
         fmt_in = fmt_of[chroma] if a.y4m_in else "rgb"
         rect = a.crop
         if rect == "auto":                          # the first pass: line sums chunk by chunk, a running maximum on the device
-            rect = detect_crop(a, chunks if paths is not None else None, fmt_in, (h, w) if a.y4m_in else None, depth, dev, order)
+            rect = detect_crop(a, chunks if paths is not None else None, fmt_in, (h, w) if a.y4m_in else None, depth, dev, order, film)
             if paths is not None:
                 chunks = png_chunks()
             print(f"--crop auto: active picture {rect[2]} x {rect[3]} at ({rect[0]}, {rect[1]}): --crop {','.join(str(v) for v in rect)}",
@@ -598,14 +640,14 @@ def main(argv: Optional[List[str]] = None) -> int:
                                      siting=out_siting),
                            a.chunk + net.num_frame)
         else:
-            sink = PngSink(a.output, None if paths is None or order is not None else [os.path.basename(p) for p in paths],
+            sink = PngSink(a.output, None if paths is None or order is not None or film is not None else [os.path.basename(p) for p in paths],
                            a.writers or max(1, min(MAX_WRITERS, effective_cpus())))
         t0 = time.perf_counter()
         up = VideoUpscaler(net, a.scale, a.padding, out=fmt_out, pixel_format=fmt_in,
                            size=(h, w) if a.y4m_in else None, cuts=a.cuts, scene_threshold=a.scene_threshold,
                            colour="bt601" if chroma == MONO else colour or "bt601",          # (grey-scale frames carry no colour space)
                            out_colour=None if out_chroma == MONO else out_colour, depth=depth, out_depth=out_depth, siting=siting, out_siting=out_siting,
-                           chroma_filter=a.chroma_filter, crop=rect, bars=a.bars, fields=order)
+                           chroma_filter=a.chroma_filter, crop=rect, bars=a.bars, fields=order, pulldown=film, pulldown_cycle=a.pulldown_cycle)
         done = 0
         try:
             for chunk in chunks:
@@ -634,6 +676,10 @@ def main(argv: Optional[List[str]] = None) -> int:
         scenes += f", siting {siting or 'none'} -> {out_siting or 'none'}"
     if order is not None:
         scenes += f", fields {order}"
+    if film is not None:
+        info = up.pulldown_info
+        scenes += (f", pulldown {film}: {len(info['matches'])} frames in, {len(info['kept'])} out, {info['matches'].count(-1)} matched from "
+                   f"their predecessor")
     print(f"upscaled {done} frames in {dt:.2f} s: {done / dt:.2f} frames/s{scenes}", file=sys.stderr if a.output == "-" else sys.stdout, flush=True)
     return 0
 

@@ -38,6 +38,12 @@ them -- before the crop -- so the call is, bit for bit, the call on `deinterlace
 specification: ffmpeg yadif's rule in integers; savsr_video_deinterlace_u8 / _u16 once per plane).  fields=None runs exactly the lines it
 ran before.
 
+pulldown="tff" / "bff": telecined film (3:2 pulldown).  The N frames become the N - N // pulldown_cycle film frames before anything else
+looks at them -- where fields= comes, which it excludes -- so the call is, bit for bit, the call on `remove_pulldown(frames, pulldown, ...)`
+(savsr_amd/pulldown.py is the specification: savsr_video_field_scores_* and a host decision match the fields, savsr_video_weave puts them
+together, savsr_video_pair_sad_* and a host decision drop the repeated frame of every cycle).  pulldown=None runs exactly the lines it
+ran before.
+
 Every argument is checked here, on the host, before anything is enqueued on the GPU.
 """
 from __future__ import annotations
@@ -707,11 +713,203 @@ class FieldSplitter:
         return _deinterlace_device(src, self.order, self.side, self.size, n - self._todo, n)
 
 
+# ---- telecined film (savsr_amd/pulldown.py is the specification) -----------------------------------------------------------------------------
+def _check_pulldown(pulldown, cycle, fields) -> Optional[str]:
+    """pulldown is None or a field order; pulldown_cycle goes with it, and fields= does not."""
+    from .pulldown import DEFAULT_CYCLE, check_cycle
+    if pulldown is None:
+        if isinstance(cycle, bool) or cycle != DEFAULT_CYCLE:
+            raise ValueError(f"pulldown_cycle = {cycle!r} goes with pulldown=: it is the decimation cycle of the pulldown removal")
+        return None
+    from .deinterlace import check_order
+    check_order(pulldown, "pulldown")
+    if fields is not None:
+        raise ValueError(f"pulldown = {pulldown!r} together with fields = {fields!r}: they are two answers to one question (telecined film, "
+                         f"whose frames are recovered, or interlaced video, whose fields are interpolated); give one of them")
+    check_cycle(cycle, "pulldown_cycle")
+    return pulldown
+
+
+def _field_scores_device(frames: torch.Tensor, order: str, side: Side, size: Optional[Tuple[int, int]], lo: int = 0, hi: Optional[int] = None) -> torch.Tensor:
+    """savsr_video_field_scores_* on resident frames of the input side on the GPU: int64 [hi - lo, 2] there for source frames [lo, hi)
+    (default: all), the previous frame taken among the resident ones and clamped there; enqueued on the current stream (no sync).  Every
+    byte of packed frames, the Y plane of planar ones."""
+    from . import _lib
+    from .deinterlace import FIELD_ORDERS
+    n, c, h, w = _field_frames(frames, side, size)
+    hi = n if hi is None else hi
+    frames = frames.contiguous()
+    lib = _lib.load()
+    oid = FIELD_ORDERS.index(order)
+    with torch.cuda.device(frames.device):
+        out = torch.empty(max(hi - lo, 0), 2, dtype=torch.int64, device=frames.device)
+        if hi <= lo:
+            return out
+        st = torch.cuda.current_stream().cuda_stream
+        if not size:
+            _lib.check(lib.savsr_video_field_scores_u8(frames.data_ptr(), n, h * w * c, 0, h, w * c, oid, lo, hi, out.data_ptr(), st),
+                       "savsr_video_field_scores_u8")
+        elif side.depth == 8:
+            _lib.check(lib.savsr_video_field_scores_u8(frames.data_ptr(), n, side.frame_bytes(h, w), 0, h, w, oid, lo, hi, out.data_ptr(), st),
+                       "savsr_video_field_scores_u8")
+        else:
+            _lib.check(lib.savsr_video_field_scores_u16(frames.data_ptr(), n, side.frame_bytes(h, w), 0, h, w, side.depth, oid, lo, hi, out.data_ptr(), st),
+                       "savsr_video_field_scores_u16")
+    return out
+
+
+def _weave_device(frames: torch.Tensor, order: str, delta: torch.Tensor, side: Side, size: Optional[Tuple[int, int]], lo: int = 0,
+                  hi: Optional[int] = None) -> torch.Tensor:
+    """savsr_video_weave on resident frames of the input side on the GPU: the hi - lo woven frames of source frames [lo, hi) (default:
+    all) with the device table delta (int32 [hi - lo], -1 | 0).  One call per plane, on the current stream."""
+    from . import _lib
+    from .deinterlace import FIELD_ORDERS
+    n, c, h, w = _field_frames(frames, side, size)
+    hi = n if hi is None else hi
+    frames = frames.contiguous()
+    out = frames.new_empty((max(hi - lo, 0),) + tuple(frames.shape[1:]))
+    if hi <= lo:
+        return out
+    if delta.dtype != torch.int32 or delta.device != frames.device or delta.numel() != hi - lo or not delta.is_contiguous():
+        raise ValueError(f"delta must be {hi - lo} contiguous int32 on {frames.device}, got {delta.dtype} {tuple(delta.shape)} on {delta.device}")
+    lib = _lib.load()
+    oid = FIELD_ORDERS.index(order)
+    with torch.cuda.device(frames.device):
+        st = torch.cuda.current_stream().cuda_stream
+        if not size:
+            table = [(0, h, w * c)]
+            fb = h * w * c
+        else:
+            table = [t[:3] for t in _plane_table(h, w, side)]
+            fb = side.frame_bytes(h, w)
+        for off, ph, pb in table:
+            _lib.check(lib.savsr_video_weave(frames.data_ptr(), n, fb, off, ph, pb, oid, lo, hi, delta.data_ptr(), out.data_ptr(), fb, off, st),
+                       "savsr_video_weave")
+    return out
+
+
+def field_scores(frames: torch.Tensor, order: str, pixel_format: str = "rgb", size=None, depth: int = 8) -> torch.Tensor:
+    """The field matcher's scores: int64 [N, 2] on the GPU (savsr_amd.pulldown.frame_scores is the specification, bit for bit), on the
+    caller's current stream, without a sync.  Entry [n, j] is the comb measure of frame n with its second field (the rows of the other
+    parity than `order`'s first field) taken from frame max(n - 1, 0) (j = 0) or from itself (j = 1).  frames as for `deinterlace`:
+    [N, h, w, c] uint8 (every byte), or planar frames with pixel_format=, size=(h, w) (the Y plane; at depth 10 / 12 a sample's 8 most
+    significant bits).  Float frames are refused."""
+    from .deinterlace import check_order
+    check_order(order)
+    side, size = _sad_side(pixel_format, size, depth)
+    _field_frames(frames, side, size)
+    return _field_scores_device(_to_device(frames, _sad_device(frames)), order, side, size)
+
+
+def _delta_device(matches: List[int], device: torch.device) -> torch.Tensor:
+    from ._xfer import h2d
+    return h2d(torch.tensor(matches, dtype=torch.int32), device)
+
+
+def _remove_pulldown_device(frames: torch.Tensor, order: str, side: Side, size: Optional[Tuple[int, int]], cycle: int):
+    """pulldown.remove_pulldown_frames on frames of the input side on the GPU: (the kept woven frames, info).  Two host synchronisations:
+    the scores come down for the match, the woven frames' pair SADs for the decimation."""
+    from . import pulldown as pd
+    n = _field_frames(frames, side, size)[0]
+    if n < 1:
+        raise ValueError("the video has no frames")
+    scores = _field_scores_device(frames, order, side, size).cpu()
+    matches = pd.matches_from_scores(scores.numpy())
+    woven = _weave_device(frames, order, _delta_device(matches, frames.device), side, size)
+    sad = [-1] + _pair_sad_device(woven, side, size).cpu().tolist()
+    kept = pd.kept_from_drops(n, pd.drops_from_sad(sad, cycle))
+    out = woven.index_select(0, torch.tensor(kept, dtype=torch.int64).to(woven.device))
+    return out, {"scores": scores.numpy(), "matches": matches, "sad": torch.tensor(sad, dtype=torch.int64).numpy(), "kept": kept}
+
+
+def remove_pulldown(frames: torch.Tensor, order: str, pixel_format: str = "rgb", size=None, depth: int = 8, cycle: int = 5, return_info: bool = False):
+    """Telecined film (3:2 pulldown) as its film frames: N - N // cycle frames on the GPU in the format of the N given ones
+    (savsr_amd.pulldown.remove_pulldown_frames is the specification, bit for bit).  Every frame keeps its first field (order "tff": the
+    top rows) and takes the second one from itself or from the frame before it, whichever combs less (`field_scores`); of every `cycle`
+    woven frames the one closest to its predecessor (`pair_sad`) is dropped.  frames as for `deinterlace`.  return_info=True: (frames,
+    info), info = {"scores", "matches", "sad", "kept"} as in the specification.  Two host synchronisations per call."""
+    from .deinterlace import check_order
+    from .pulldown import check_cycle
+    check_order(order)
+    cycle = check_cycle(cycle)
+    side, size = _sad_side(pixel_format, size, depth)
+    _field_frames(frames, side, size)
+    out, info = _remove_pulldown_device(_to_device(frames, _sad_device(frames)), order, side, size, cycle)
+    return (out, info) if return_info else out
+
+
+class PulldownRemover:
+    """The streaming pulldown removal behind VideoUpscaler(pulldown=...): push(source frames on the GPU) returns the film frames that are
+    final, finish() the partial last cycle whole (None if there is none).  The match is causal, so a pushed frame is woven at once, with
+    the previous push's last source frame as its context; woven frames wait until their cycle of `cycle` is complete, then the kept ones
+    go on.  Between pushes the device keeps one source frame, at most cycle - 1 woven frames and the last woven frame (the next SAD's
+    predecessor): `held` <= cycle + 1, copies of their own, so that the chunk they came with is released.  Concatenated, the outputs are
+    `remove_pulldown` on the whole video for any chunking; `info` has the matches and the kept indices so far."""
+
+    def __init__(self, order: str, side: Side, size: Optional[Tuple[int, int]], cycle: int = 5):
+        from .deinterlace import check_order
+        from .pulldown import check_cycle
+        check_order(order, "pulldown")
+        self.order, self.side, self.size, self.cycle = order, side, size, check_cycle(cycle, "pulldown_cycle")
+        self._ctx: Optional[torch.Tensor] = None           # the last source frame pushed
+        self._last: Optional[torch.Tensor] = None          # the last woven frame
+        self._pend: Optional[torch.Tensor] = None          # the woven frames of the incomplete cycle, frames [_base, seen)
+        self._pend_sad: List[int] = []                     # their pair SADs with their predecessors
+        self._base = 0
+        self.seen = 0
+        self.matches: List[int] = []
+        self.kept: List[int] = []
+
+    @property
+    def held(self) -> int:
+        """Frames on the device between pushes: at most cycle + 1."""
+        return sum(0 if t is None else int(t.shape[0]) for t in (self._ctx, self._last, self._pend))
+
+    @property
+    def info(self) -> dict:
+        return {"matches": list(self.matches), "kept": list(self.kept)}
+
+    def push(self, frames: torch.Tensor) -> torch.Tensor:
+        from . import pulldown as pd
+        k = int(frames.shape[0])
+        if k == 0:
+            return frames
+        src = frames.contiguous() if self._ctx is None else torch.cat([self._ctx, frames], 0)
+        n = int(src.shape[0])
+        matches = pd.matches_from_scores(_field_scores_device(src, self.order, self.side, self.size, n - k, n).cpu().numpy())
+        woven = _weave_device(src, self.order, _delta_device(matches, src.device), self.side, self.size, n - k, n)
+        pairs = woven if self._last is None else torch.cat([self._last, woven], 0)
+        sad = _pair_sad_device(pairs, self.side, self.size).cpu().tolist()
+        self._pend_sad += ([-1] if self._last is None else []) + sad
+        pend = woven if self._pend is None else torch.cat([self._pend, woven], 0)
+        self.matches += matches
+        self.seen += k
+        full = (int(pend.shape[0]) // self.cycle) * self.cycle
+        drops = set(pd.drops_from_sad(self._pend_sad[:full], self.cycle, self._base))
+        kept = [j for j in range(self._base, self._base + full) if j not in drops]
+        out = pend.index_select(0, torch.tensor([j - self._base for j in kept], dtype=torch.int64).to(pend.device))
+        self.kept += kept
+        self._pend = pend[full:].clone() if full < int(pend.shape[0]) else None
+        self._pend_sad = self._pend_sad[full:]
+        self._base += full
+        self._ctx, self._last = src[n - 1:].clone(), woven[k - 1:].clone()
+        return out
+
+    def finish(self) -> Optional[torch.Tensor]:
+        pend, self._pend, self._ctx, self._last = self._pend, None, None, None
+        if pend is None:
+            return None
+        self.kept += list(range(self._base, self._base + int(pend.shape[0])))
+        self._base += int(pend.shape[0])
+        self._pend_sad = []
+        return pend
+
+
 def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
                   size=None, cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601",
                   out_colour: Optional[str] = None, depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None,
                   out_siting: Optional[str] = None, chroma_filter: Optional[str] = None, crop=None, crop_limit=24,
-                  bars: str = "keep", fields: Optional[str] = None) -> torch.Tensor:
+                  bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None, pulldown_cycle: int = 5) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
@@ -721,6 +919,9 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     if _check_fields(fields) is not None:          # everything below sees the progressive video of 2N frames
         _field_frames(frames, spec.inp, spec.size)
         n *= 2
+    if _check_pulldown(pulldown, pulldown_cycle, fields) is not None:          # everything below sees the film of N - N // cycle frames
+        _field_frames(frames, spec.inp, spec.size)
+        n -= n // pulldown_cycle
     crop = _check_crop_args(crop, crop_limit, bars)
     if crop is not None and crop != "auto":
         from . import active
@@ -742,6 +943,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     frames = _to_device(frames, dev)
     if fields is not None:             # deinterlacing comes first, before the crop
         frames = _deinterlace_device(frames, fields, spec.inp, spec.size)
+    if pulldown is not None:           # pulldown removal comes first, where deinterlacing comes
+        frames = _remove_pulldown_device(frames, pulldown, spec.inp, spec.size, pulldown_cycle)[0]
     full = spec
     if crop == "auto":
         crop = _detect_device(frames, spec.inp, spec.size, crop_limit)
@@ -797,12 +1000,19 @@ class VideoUpscaler:
     after it has been pushed (its second field reads that frame), so push() holds the last source frame back and finish() flushes it with
     next = cur; the cuts, the crop and the windows operate on the progressive frames as they are produced, and explicit cuts index them.
     Concatenated, the outputs are upscale_video(fields=...) on the whole video for any chunking.  Beside the frames kept without fields
-    the device keeps at most two more source frames between pushes: the held frame and the one before it (savsr_amd.video.FieldSplitter)."""
+    the device keeps at most two more source frames between pushes: the held frame and the one before it (savsr_amd.video.FieldSplitter).
+
+    pulldown="tff" / "bff", pulldown_cycle=5: telecined chunks, as in upscale_video.  The match is causal, so a pushed frame is woven at
+    once; woven frames wait until their cycle is complete, then the kept ones go on as a chunk and finish() flushes the partial last cycle
+    whole.  Concatenated, the outputs are upscale_video(pulldown=...) on the whole video for any chunking; `pulldown_info` has the matches
+    and the kept indices so far.  Beside the frames kept without it the device keeps at most pulldown_cycle + 1 more frames between pushes
+    (savsr_amd.video.PulldownRemover).  Two host synchronisations per push."""
 
     def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb", size=None,
                  cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None,
                  depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
-                 chroma_filter: Optional[str] = None, crop=None, bars: str = "keep", fields: Optional[str] = None):
+                 chroma_filter: Optional[str] = None, crop=None, bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None,
+                 pulldown_cycle: int = 5):
         _check_net(net)
         check_padding(padding)
         check_out(out, net.cfg["num_in_ch"], chroma_filter)          # (speaks before the cuts, video_spec after them: the order of refusals)
@@ -819,6 +1029,8 @@ class VideoUpscaler:
         self.spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter)
         self._full = self.spec                     # the spec of the chunks as pushed; `spec` becomes the cropped size's with a crop
         self._split = None if _check_fields(fields) is None else FieldSplitter(fields, self.spec.inp, self.spec.size)          # None: as it was
+        if _check_pulldown(pulldown, pulldown_cycle, fields) is not None:          # (the two exclude each other: one stage in front of the rest)
+            self._split = PulldownRemover(pulldown, self.spec.inp, self.spec.size, pulldown_cycle)
         self._rect = _check_crop_args(crop, 24, bars, auto_ok=False)          # the rect to crop every chunk to; None: no crop, as it was
         self._place = None                         # active.place's six numbers with bars="keep", once the frame size is known
         self.bars = bars
@@ -846,6 +1058,12 @@ class VideoUpscaler:
             return
         self._rect, self._hw = rect, (h, w)
         self.spec = _cropped_spec(self._full, rect)
+
+    @property
+    def pulldown_info(self) -> Optional[dict]:
+        """{"matches", "kept"} of the frames pushed so far: per source frame -1 (its second field came from its predecessor) or 0, and the
+        indices of the woven frames that went on (None without pulldown=)."""
+        return self._split.info if isinstance(self._split, PulldownRemover) else None
 
     @property
     def cuts(self) -> Optional[List[int]]:
@@ -885,7 +1103,7 @@ class VideoUpscaler:
     def push(self, frames: torch.Tensor) -> torch.Tensor:
         if self._finished:
             raise RuntimeError("push() after finish()")
-        if self._split is not None:                # interlaced chunks: the progressive frames that are final go on as a chunk of their own
+        if self._split is not None:                # interlaced / telecined chunks: the progressive frames that are final go on as a chunk of their own
             _field_frames(frames, self._full.inp, self._full.size)
             k, h, w = self._full.frames_hw(frames)
             dev = self.net.gamma.device
@@ -894,7 +1112,7 @@ class VideoUpscaler:
             if self._shape is not None and (True, h, w) != self._shape:
                 raise ValueError(f"chunk of uint8 {h} x {w} frames after uint8 {self._shape[1]} x {self._shape[2]} ones")
             frames = self._split.push(_to_device(frames, dev))
-            if int(frames.shape[0]) == 0:          # (a first push of one frame: nothing is final yet)
+            if int(frames.shape[0]) == 0:          # (a first push of one frame, or a cycle not complete yet: nothing is final)
                 if self._shape is None and self._rect is not None and not self._full.size:
                     self._set_rect(h, w)
                 self._shape = (True, h, w)
