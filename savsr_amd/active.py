@@ -21,21 +21,13 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from .packing import get_hw
+from .frames import SAMPLE_FORMATS, block_of, check_pixel_format, layout_of          # (block_of: the chroma blocks live with the plane table)
 from .scenes import _samples_of
-from .video import SAMPLE_FORMATS, check_pixel_format, layout_of
 from .yuv import MONO, check_depth, chroma_hw, frame_bytes, is_full_range, luma_plane, split_planes
 
 Rect = Tuple[int, int, int, int]
 BARS = ("keep", "drop")
 DEFAULT_LIMIT = 24          # ffmpeg cropdetect's default, on the 8-bit scale; not validated on real footage
-_BLOCK = {"420": (2, 2), "422": (1, 2), "444": (1, 1), MONO: (1, 1), None: (1, 1)}          # (vertical, horizontal) chroma block of a layout
-
-
-def block_of(layout: Optional[str]) -> Tuple[int, int]:
-    """(vertical, horizontal) luma samples per chroma sample of a layout; (1, 1) for "444", grey-scale ("400") and packed frames (None)."""
-    if layout not in _BLOCK:
-        raise ValueError(f"layout = {layout!r}: one of 420, 422, 444, {MONO} or None (packed frames)")
-    return _BLOCK[layout]
 
 
 # ---- the detector --------------------------------------------------------------------------------------------------------------------

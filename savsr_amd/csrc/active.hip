@@ -17,6 +17,7 @@
 // 16 rows x 255 per field), meet in LDS and leave by one 32-bit vector atomic per column and tile.  One-sample form (any base pointer,
 // stride and size): a lane owns 4 columns 64 apart (LS_ONE_COLS per tile), a wave reads one row per step.
 #include "common.hpp"
+#include "video_samples.hpp"
 
 #include <cstdint>
 
@@ -33,25 +34,6 @@ constexpr int LS_MAX_LINES = 65535 * LS_TILE_ROWS;  // grid.y; a line's sum stay
 static_assert(LS_ONE_COLS == LS_THREADS && LS_TILE_ROWS % 16 == 0 && LS_TILE_ROWS / 4 * 255 < 65536, "a wave's column partial must fit a 16-bit field");
 
 enum { LS_U8 = 0, LS_U16 = 1, LS_F32 = 2 };
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// b0 + b1 + b2 + b3 + acc over the four bytes of a dword: one v_sad_u8 against zero (scene.hip `sad4`)
-__device__ __forceinline__ uint32_t sum4(uint32_t a, uint32_t acc) {
-#if __has_builtin(__builtin_amdgcn_sad_u8)
-    return __builtin_amdgcn_sad_u8(a, 0u, acc);
-#else
-    return acc + (a & 255u) + ((a >> 8) & 255u) + ((a >> 16) & 255u) + (a >> 24);
-#endif
-}
-
-// savsr_video_quantize_u8's value (video.hip `quant_u8`): clamp_(0, 1); (img * 255.0).round(): half to even; fmaxf(NaN, 0) = 0
-__device__ __forceinline__ uint32_t quant_u8(float x) { return (uint32_t)rintf(fminf(fmaxf(x, 0.f), 1.f) * 255.0f); }
-
-// Two 16-bit samples of a dword -> their 8 most significant bits of `d`, each in its half: min(s, top) >> shift (scene.hip `msb8x2`)
-__device__ __forceinline__ uint32_t msb8x2(uint32_t x, uint32_t top, int shift) {
-    return (min(x & 0xffffu, top) >> shift) | ((min(x >> 16, top) >> shift) << 16);
-}
 
 template <int KIND>
 struct Kind {
@@ -151,7 +133,7 @@ __global__ __launch_bounds__(LS_THREADS) void line_sums_vec_kernel(const uint8_t
 template <int KIND>
 __device__ __forceinline__ uint32_t sample_of(const uint8_t* row, long long c, uint32_t top, int shift) {
     if constexpr (KIND == LS_U8) return row[c];
-    else if constexpr (KIND == LS_U16) return min((uint32_t) reinterpret_cast<const uint16_t*>(row)[c], top) >> shift;
+    else if constexpr (KIND == LS_U16) return msb8(reinterpret_cast<const uint16_t*>(row)[c], top, shift);
     else return quant_u8(reinterpret_cast<const float*>(row)[c]);
 }
 

@@ -15,6 +15,7 @@
 // the first use, no LDS).  The pixel step is a template argument, so every sample is a constant bit field of a register.  One-sample
 // form (any pointer, stride and size): a lane owns one sample.  Absolute differences are v_sad_u8 / v_sad_u16 on single samples.
 #include "common.hpp"
+#include "video_samples.hpp"
 
 #include <cstdint>
 
@@ -28,8 +29,6 @@ constexpr int DI_ONE_IROWS = 4;                     // interpolated rows of a on
 constexpr int DI_ONE_COLS = 64;                     // samples of a one-sample tile's row
 constexpr int DI_MAX_Z = 65535;                     // grid.z
 constexpr int DI_MAX_ROWS = 65535 * 2 * DI_ONE_IROWS;          // grid.y of the one-sample form
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 template <int BYTES>
 __device__ __forceinline__ int absdiff(int a, int b) {

@@ -21,6 +21,7 @@
 // n_frames - 1); delta is a device table the entry cannot see, so the kernel clamps.  A byte copy at every depth: a 16-byte form and a
 // byte form, one launch per plane.
 #include "common.hpp"
+#include "video_samples.hpp"
 
 #include <cstdint>
 
@@ -31,39 +32,6 @@ constexpr int PD_THREADS = 256;
 constexpr int PD_ONE_ITERS = 8;                     // samples (bytes, for the weave) per lane in the one-sample forms
 constexpr int PD_MAX_Y = 65535;                     // grid.y: frames per launch
 constexpr long long PD_MAX_PLANE = 0x7fff0000ll;    // bytes of a plane: the lane tiles of a frame fit grid.x and 32-bit counts
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// |a.b0 - b.b0| + ... + |a.b3 - b.b3| + acc over the four bytes of a dword: one v_sad_u8
-__device__ __forceinline__ uint32_t pd_sad4(uint32_t a, uint32_t b, uint32_t acc) {
-#if __has_builtin(__builtin_amdgcn_sad_u8)
-    return __builtin_amdgcn_sad_u8(a, b, acc);
-#else
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int d = (int)((a >> (8 * e)) & 255u) - (int)((b >> (8 * e)) & 255u);
-        acc += (uint32_t)(d < 0 ? -d : d);
-    }
-    return acc;
-#endif
-}
-
-// |a.lo - b.lo| + |a.hi - b.hi| + acc over the two 16-bit halves of a dword: one v_sad_u16
-__device__ __forceinline__ uint32_t pd_sad2(uint32_t a, uint32_t b, uint32_t acc) {
-#if __has_builtin(__builtin_amdgcn_sad_u16)
-    return __builtin_amdgcn_sad_u16(a, b, acc);
-#else
-    const uint32_t al = a & 0xffffu, bl = b & 0xffffu, ah = a >> 16, bh = b >> 16;
-    return acc + (al > bl ? al - bl : bl - al) + (ah > bh ? ah - bh : bh - ah);
-#endif
-}
-
-__device__ __forceinline__ uint32_t pd_absdiff(uint32_t a, uint32_t b) { return a > b ? a - b : b - a; }
-
-// Two 16-bit samples of a dword -> their 8 most significant bits of `depth`, each in its half: min(s, top) >> shift.
-__device__ __forceinline__ uint32_t pd_msb8x2(uint32_t x, uint32_t top, int shift) {
-    return (min(x & 0xffffu, top) >> shift) | ((min(x >> 16, top) >> shift) << 16);
-}
 
 // What a score launch works on.  Rows are `pitch` bytes apart.
 struct ScoreJob {
@@ -125,15 +93,15 @@ __global__ __launch_bounds__(PD_THREADS) void field_scores_vec_kernel(ScoreJob j
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             if constexpr (BYTES == 1) {
-                ac = pd_sad4(a[e], c[e], ac);
-                acc0 = pd_sad4(c[e], b0[e], pd_sad4(a[e], b0[e], acc0));
-                acc1 = pd_sad4(c[e], b1[e], pd_sad4(a[e], b1[e], acc1));
+                ac = sad4(a[e], c[e], ac);
+                acc0 = sad4(c[e], b0[e], sad4(a[e], b0[e], acc0));
+                acc1 = sad4(c[e], b1[e], sad4(a[e], b1[e], acc1));
             } else {
-                const uint32_t ae = pd_msb8x2(a[e], jb.top, jb.shift), ce = pd_msb8x2(c[e], jb.top, jb.shift);
-                const uint32_t p0 = pd_msb8x2(b0[e], jb.top, jb.shift), p1 = pd_msb8x2(b1[e], jb.top, jb.shift);
-                ac = pd_sad2(ae, ce, ac);
-                acc0 = pd_sad2(ce, p0, pd_sad2(ae, p0, acc0));
-                acc1 = pd_sad2(ce, p1, pd_sad2(ae, p1, acc1));
+                const uint32_t ae = msb8x2(a[e], jb.top, jb.shift), ce = msb8x2(c[e], jb.top, jb.shift);
+                const uint32_t p0 = msb8x2(b0[e], jb.top, jb.shift), p1 = msb8x2(b1[e], jb.top, jb.shift);
+                ac = sad2(ae, ce, ac);
+                acc0 = sad2(ce, p0, sad2(ae, p0, acc0));
+                acc1 = sad2(ce, p1, sad2(ae, p1, acc1));
             }
         }
         acc0 -= ac;          // per sample |a - b| + |c - b| >= |a - c|: the sums stay >= 0
@@ -145,7 +113,7 @@ __global__ __launch_bounds__(PD_THREADS) void field_scores_vec_kernel(ScoreJob j
 template <int BYTES>
 __device__ __forceinline__ uint32_t pd_sample(const uint8_t* row, uint32_t x, uint32_t top, int shift) {
     if constexpr (BYTES == 1) return row[x];
-    else return min((uint32_t)reinterpret_cast<const uint16_t*>(row)[x], top) >> shift;
+    else return msb8(reinterpret_cast<const uint16_t*>(row)[x], top, shift);
 }
 
 // One-sample form: sample i = (scored row, x) = (i / cols, i % cols), i = blockIdx.x * (PD_THREADS * PD_ONE_ITERS) + it * PD_THREADS + tid.
@@ -166,9 +134,9 @@ __global__ __launch_bounds__(PD_THREADS) void field_scores_one_kernel(ScoreJob j
             const long long off = (jb.y0 + 2ll * s) * jb.pitch;
             const uint32_t a = pd_sample<BYTES>(cur + off - jb.pitch, x, jb.top, jb.shift), c = pd_sample<BYTES>(cur + off + jb.pitch, x, jb.top, jb.shift);
             const uint32_t b0 = pd_sample<BYTES>(prev + off, x, jb.top, jb.shift), b1 = pd_sample<BYTES>(cur + off, x, jb.top, jb.shift);
-            const uint32_t ac = pd_absdiff(a, c);
-            acc0 += pd_absdiff(a, b0) + pd_absdiff(c, b0) - ac;
-            acc1 += pd_absdiff(a, b1) + pd_absdiff(c, b1) - ac;
+            const uint32_t ac = absdiff(a, c);
+            acc0 += absdiff(a, b0) + absdiff(c, b0) - ac;
+            acc1 += absdiff(a, b1) + absdiff(c, b1) - ac;
         }
     }
     pd_block_add(acc0, acc1, out + 2 * blockIdx.y);

@@ -13,6 +13,7 @@
 //   (ABI 39)           plane is the first h * w samples of a frame in every layout, so savsr_video_pair_sad_yuvp is host work only
 //                      (another frame stride for the same kernels)
 #include "common.hpp"
+#include "video_samples.hpp"
 
 #include <cstdint>
 
@@ -23,31 +24,6 @@ constexpr int SAD_THREADS = 256;
 constexpr int SAD_VEC_ITERS = 4;       // 16-byte chunks (or float4) per thread and frame in the vector forms
 constexpr int SAD_ONE_ITERS = 16;      // samples per thread in the one-sample forms
 constexpr int SAD_MAX_PAIRS_Y = 65535; // grid.y
-
-// |a.b0 - b.b0| + ... + |a.b3 - b.b3| + acc over the four bytes of a dword: one v_sad_u8
-__device__ __forceinline__ uint32_t sad4(uint32_t a, uint32_t b, uint32_t acc) {
-#if __has_builtin(__builtin_amdgcn_sad_u8)
-    return __builtin_amdgcn_sad_u8(a, b, acc);
-#else
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int d = (int)((a >> (8 * e)) & 255u) - (int)((b >> (8 * e)) & 255u);
-        acc += (uint32_t)(d < 0 ? -d : d);
-    }
-    return acc;
-#endif
-}
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t absdiff(uint32_t a, uint32_t b) { return a > b ? a - b : b - a; }
-
-// savsr_video_quantize_u8's value (video.hip `quant_u8`): clamp_(0, 1); (img * 255.0).round(): half to even; fmaxf(NaN, 0) = 0
-__device__ __forceinline__ uint32_t quant_u8(float x) { return (uint32_t)rintf(fminf(fmaxf(x, 0.f), 1.f) * 255.0f); }
-
-__device__ __forceinline__ uint32_t quant4(const f32x4 v) {
-    return quant_u8(v[0]) | (quant_u8(v[1]) << 8) | (quant_u8(v[2]) << 16) | (quant_u8(v[3]) << 24);
-}
 
 // A workgroup's partial sum (a thread adds at most 64 samples of <= 255 each: far below 2^32) -> one 64-bit vector atomic on the pair's cell.
 __device__ __forceinline__ void block_add(uint32_t acc, unsigned long long* cell) {
@@ -140,20 +116,6 @@ __global__ __launch_bounds__(SAD_THREADS) void pair_sad_f32_kernel(const float* 
     block_add(acc, sad + blockIdx.y);
 }
 
-// |a.lo - b.lo| + |a.hi - b.hi| + acc over the two 16-bit halves of a dword: one v_sad_u16
-__device__ __forceinline__ uint32_t sad2(uint32_t a, uint32_t b, uint32_t acc) {
-#if __has_builtin(__builtin_amdgcn_sad_u16)
-    return __builtin_amdgcn_sad_u16(a, b, acc);
-#else
-    return acc + absdiff(a & 0xffffu, b & 0xffffu) + absdiff(a >> 16, b >> 16);
-#endif
-}
-
-// Two 16-bit samples of a dword -> their 8 most significant bits of `d`, each in its half: min(s, top) >> shift.
-__device__ __forceinline__ uint32_t msb8x2(uint32_t x, uint32_t top, int shift) {
-    return (min(x & 0xffffu, top) >> shift) | ((min(x >> 16, top) >> shift) << 16);
-}
-
 // High-depth frames `stride` bytes apart, the first `len` 16-bit samples of each compared (the Y plane); pair blockIdx.y = frames (k, k + 1).
 // VEC: frames and stride 16-byte aligned: 16-byte loads (8 samples) from both frames over len / 8 chunks, the len % 8 samples left over by
 // workgroup 0's first lanes.  Otherwise a sample per lane and iteration (any 2-byte aligned base, any size).
@@ -183,13 +145,13 @@ __global__ __launch_bounds__(SAD_THREADS) void pair_sad_u16_kernel(const uint8_t
             for (int e = 0; e < 4; ++e) acc = sad2(msb8x2(x[it][e], top, shift), msb8x2(y[it][e], top, shift), acc);
         }
         const long long t = (nchunk << 3) + threadIdx.x;
-        if (blockIdx.x == 0 && threadIdx.x < 8 && t < len) acc += absdiff(min((uint32_t)a[t], top) >> shift, min((uint32_t)b[t], top) >> shift);
+        if (blockIdx.x == 0 && threadIdx.x < 8 && t < len) acc += absdiff(msb8(a[t], top, shift), msb8(b[t], top, shift));
     } else {
         const long long i0 = (long long)blockIdx.x * (SAD_THREADS * SAD_ONE_ITERS) + threadIdx.x;
 #pragma unroll 4
         for (int it = 0; it < SAD_ONE_ITERS; ++it) {
             const long long i = i0 + it * SAD_THREADS;
-            if (i < len) acc += absdiff(min((uint32_t)a[i], top) >> shift, min((uint32_t)b[i], top) >> shift);
+            if (i < len) acc += absdiff(msb8(a[i], top, shift), msb8(b[i], top, shift));
         }
     }
     block_add(acc, sad + blockIdx.y);
@@ -244,6 +206,16 @@ int launch_words(const uint8_t* frames, int n_frames, long long stride, long lon
     return 0;
 }
 
+// Planar frames of any chroma layout (SAVSR_CHROMA_*) and depth (8, 10, 12): the Y plane is the first h * w samples of a frame of
+// h * w + 2 * ch * cw samples, so the three planar entries are this one choice of stride and length for the launches above.
+int launch_planar(const uint8_t* frames, int n_frames, int h, int w, int depth, int chroma, int64_t* sad_out, void* stream, const char* what) {
+    const long long ch = chroma == SAVSR_CHROMA_420 ? (h + 1) / 2 : h, cw = chroma == SAVSR_CHROMA_444 ? w : (w + 1) / 2;
+    const long long len = (long long)h * w, samples = len + 2 * ch * cw;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (depth == 8) return launch_bytes(frames, n_frames, samples, len, sad_out, st, what);
+    return launch_words(frames, n_frames, 2 * samples, len, depth, sad_out, st, what);
+}
+
 }  // namespace
 }  // namespace savsr
 
@@ -261,9 +233,7 @@ extern "C" int savsr_video_pair_sad_i420(const uint8_t* frames, int n_frames, in
     if (!frames || (!sad_out && n_frames > 1)) return fail_arg("video_pair_sad_i420: null pointer");
     if (h < 1 || w < 1 || n_frames < 1) return fail_arg("video_pair_sad_i420: h, w, n_frames >= 1");
     if (reinterpret_cast<uintptr_t>(sad_out) & 7) return fail_arg("video_pair_sad_i420: sad_out must be 8-byte aligned");
-    const long long ch = (h + 1) / 2, cw = (w + 1) / 2;
-    const long long len = (long long)h * w;
-    return launch_bytes(frames, n_frames, len + 2 * ch * cw, len, sad_out, static_cast<hipStream_t>(stream), "video_pair_sad_i420");
+    return launch_planar(frames, n_frames, h, w, 8, SAVSR_CHROMA_420, sad_out, stream, "video_pair_sad_i420");
 }
 
 extern "C" int savsr_video_pair_sad_f32(const float* frames, int n_frames, int c, int h, int w, int64_t* sad_out, void* stream) {
@@ -297,13 +267,12 @@ extern "C" int savsr_video_pair_sad_i420_16(const uint8_t* frames, int n_frames,
     if (depth != 10 && depth != 12) return fail_arg("video_pair_sad_i420_16: depth 10 or 12 (8 bits: savsr_video_pair_sad_i420)");
     if (reinterpret_cast<uintptr_t>(frames) & 1) return fail_arg("video_pair_sad_i420_16: frames must be 2-byte aligned (16-bit samples)");
     if (reinterpret_cast<uintptr_t>(sad_out) & 7) return fail_arg("video_pair_sad_i420_16: sad_out must be 8-byte aligned");
-    const long long ch = (h + 1) / 2, cw = (w + 1) / 2;
-    const long long len = (long long)h * w;
-    return launch_words(frames, n_frames, 2 * (len + 2 * ch * cw), len, depth, sad_out, static_cast<hipStream_t>(stream), "video_pair_sad_i420_16");
+    return launch_planar(frames, n_frames, h, w, depth, SAVSR_CHROMA_420, sad_out, stream, "video_pair_sad_i420_16");
 }
 
 // ABI 39: frames of any chroma layout (SAVSR_CHROMA_*) and depth (8, 10, 12): the Y plane, h * w samples at the start of a frame of
-// h * w + 2 * ch * cw samples.  Host work only: the kernels above with the layout's frame stride.
+// h * w + 2 * ch * cw samples.  Host work only: the kernels above with the layout's frame stride (`launch_planar`, which the two I420
+// entries above reach as well after their own checks).
 extern "C" int savsr_video_pair_sad_yuvp(const uint8_t* frames, int n_frames, int h, int w, int depth, int chroma, int64_t* sad_out, void* stream) {
     if (chroma < SAVSR_CHROMA_420 || chroma > SAVSR_CHROMA_444) return fail_arg("video_pair_sad_yuvp: chroma 0 (4:2:0), 1 (4:2:2) or 2 (4:4:4)");
     if (depth != 8 && depth != 10 && depth != 12) return fail_arg("video_pair_sad_yuvp: depth 8, 10 or 12");
@@ -311,9 +280,5 @@ extern "C" int savsr_video_pair_sad_yuvp(const uint8_t* frames, int n_frames, in
     if (h < 1 || w < 1 || n_frames < 1) return fail_arg("video_pair_sad_yuvp: h, w, n_frames >= 1");
     if (depth != 8 && (reinterpret_cast<uintptr_t>(frames) & 1)) return fail_arg("video_pair_sad_yuvp: frames must be 2-byte aligned (16-bit samples)");
     if (reinterpret_cast<uintptr_t>(sad_out) & 7) return fail_arg("video_pair_sad_yuvp: sad_out must be 8-byte aligned");
-    const long long ch = chroma == SAVSR_CHROMA_420 ? (h + 1) / 2 : h, cw = chroma == SAVSR_CHROMA_444 ? w : (w + 1) / 2;
-    const long long len = (long long)h * w, samples = len + 2 * ch * cw;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (depth == 8) return launch_bytes(frames, n_frames, samples, len, sad_out, st, "video_pair_sad_yuvp");
-    return launch_words(frames, n_frames, 2 * samples, len, depth, sad_out, st, "video_pair_sad_yuvp");
+    return launch_planar(frames, n_frames, h, w, depth, chroma, sad_out, stream, "video_pair_sad_yuvp");
 }

@@ -6,6 +6,7 @@
 //   generate_frame_indices      lbasicsr/data/data_util.py:63-112  the window's frame list (the caller's index arguments)
 //   tensor2img                  lbasicsr/utils/img_util.py:66-90   clamp(0, 1) * 255, round half to even, uint8, CHW -> HWC
 #include "common.hpp"
+#include "video_samples.hpp"
 
 #include <cstdint>
 
@@ -75,10 +76,6 @@ __global__ __launch_bounds__(256) void gather_f32_kernel(const float* __restrict
     } else {
         for (int e = 0; e < 4 && i0 + e < nfl; ++e) o[i0 + e] = f[i0 + e];
     }
-}
-
-__device__ __forceinline__ uint32_t quant_u8(float x) {
-    return (uint32_t)rintf(fminf(fmaxf(x, 0.f), 1.f) * 255.0f);      // clamp_(0, 1); (img * 255.0).round(): half to even
 }
 
 // fp32 planar [n][C][H][W] -> uint8 HWC [n][H][W][C].  VEC: a thread quantises 16 pixels -- four float4 per plane in, C 16-byte stores

@@ -22,7 +22,7 @@ repeated pictures: savsr_amd/pulldown.py, `pulldown=`, recovers the film frames 
 and the rule is yadif's, not bwdif or a learned one.
 
 `savsr_amd.deinterlace` names this module and, called, the GPU function: `savsr_amd.deinterlace(frames, order, ...)` is
-`savsr_amd.video.deinterlace` (the module object is callable, below: the package's public surface names both, and a function of that
+`savsr_amd.prepass.deinterlace` (the module object is callable, below: the package's public surface names both, and a function of that
 name in the package would shadow this module).  importlib.reload keeps it callable and its functions pickle by reference
 (tests/test_deinterlace.py).
 """
@@ -34,7 +34,7 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
-from .video import check_pixel_format, layout_of
+from .frames import check_pixel_format, layout_of
 from .yuv import MONO, check_depth, frame_bytes, layout_name, luma_plane, split_planes
 
 FIELD_ORDERS = ("tff", "bff")
@@ -224,10 +224,10 @@ def resolve_fields(flag: Optional[str], tag: Optional[str], fps: Tuple[int, int]
 
 class _CallableModule(types.ModuleType):
     """savsr_amd.deinterlace(frames, order, pixel_format="rgb", size=None, depth=8): 2N progressive frames on the GPU
-    (savsr_amd.video.deinterlace, which `deinterlace_frames` above specifies bit for bit)."""
+    (savsr_amd.prepass.deinterlace, which `deinterlace_frames` above specifies bit for bit)."""
 
     def __call__(self, frames, order, pixel_format: str = "rgb", size=None, depth: int = 8):
-        from .video import deinterlace
+        from .prepass import deinterlace
         return deinterlace(frames, order, pixel_format, size, depth)
 
 

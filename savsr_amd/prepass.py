@@ -1,0 +1,495 @@
+"""Everything that runs on the device in front of the network: the scene detector's scores, the active-picture detector with crop and
+re-insertion, the deinterlacer and the pulldown removal.  Each is a public call on any frames and a `_..._device` form on resident frames
+of a checked input side (what upscale_video calls on the whole video); the two that change the frame count are streaming stages as well
+(`FieldSplitter`, `PulldownRemover`; `make_stage` builds the one a call asks for).  The numpy modules (scenes.py, active.py,
+deinterlace.py, pulldown.py) are the specifications, bit for bit.  Where the byte matrices of a frame lie is `frames.plane_table`'s
+answer alone; fp32 CHW frames have entries of their own (`_f32`) and are one explicit branch in the two stages that accept them.
+"""
+from __future__ import annotations
+
+from dataclasses import replace
+from typing import List, Optional, Tuple
+
+import torch
+
+from . import active
+from . import pulldown as pd
+from .deinterlace import FIELD_ORDERS, check_frame_rows, check_order
+from .frames import Side, VideoSpec, detector_layout, detector_side, plane_table
+from .scenes import check_threshold, cuts_from_sad, sad_samples
+from .yuv import CHROMAS
+
+Size = Optional[Tuple[int, int]]
+
+
+def _to_device(frames: torch.Tensor, device: torch.device) -> torch.Tensor:
+    if frames.device == device:
+        return frames
+    if frames.is_cuda:
+        raise RuntimeError(f"frames on {frames.device}, network on {device}")
+    from ._xfer import h2d
+    return h2d(frames.contiguous(), device)
+
+
+def _sad_device(frames: torch.Tensor) -> torch.device:
+    if frames.is_cuda:
+        return frames.device
+    if not torch.cuda.is_available():
+        raise RuntimeError("savsr_amd runs on an AMD GPU only: the detector's scores are computed there")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _stage_args(frames: torch.Tensor, pixel_format: str, size, depth, layout=detector_layout):
+    """What a public stage call hands its `_..._device` form: (the frames on the GPU, host ones copied there; the side; the size), after
+    `layout` has refused the frames that are none of that side."""
+    side, size = detector_side(pixel_format, size, depth)
+    layout(frames, side, size)
+    return _to_device(frames, _sad_device(frames)), side, size
+
+
+# ---- the scene detector (savsr_amd/scenes.py is the specification) ---------------------------------------------------------------------
+def _pair_sad_device(frames: torch.Tensor, side: Side, size: Size) -> torch.Tensor:
+    """savsr_video_pair_sad_* on frames of the input side already on the GPU: int64 [N - 1] there, enqueued on the current stream (no sync).
+    Planar colour frames of every layout and depth are one entry (_yuvp: the Y plane), packed and grey-scale frames another (_u8)."""
+    from . import _lib
+    n, c, h, w = detector_layout(frames, side, size)
+    lib = _lib.load()
+    u8 = frames.dtype == torch.uint8
+    frames = frames.contiguous() if u8 else frames.to(torch.float32).contiguous()
+    with torch.cuda.device(frames.device):
+        sad = torch.empty(n - 1, dtype=torch.int64, device=frames.device)
+        st = torch.cuda.current_stream().cuda_stream
+        if not u8:
+            _lib.check(lib.savsr_video_pair_sad_f32(frames.data_ptr(), n, c, h, w, sad.data_ptr(), st), "savsr_video_pair_sad_f32")
+        elif side.yuv:
+            _lib.check(lib.savsr_video_pair_sad_yuvp(frames.data_ptr(), n, h, w, side.depth, CHROMAS.index(side.layout), sad.data_ptr(), st),
+                       "savsr_video_pair_sad_yuvp")
+        else:
+            # grey-scale frames are [N, h, w, 1] frames of their samples' 8 most significant bits (host work only: no kernel of their own)
+            if side.depth != 8:
+                words = frames.view(torch.int16).to(torch.int32) & 0xFFFF
+                frames = (words.clamp_(max=(1 << side.depth) - 1) >> (side.depth - 8)).to(torch.uint8)
+            _lib.check(lib.savsr_video_pair_sad_u8(frames.data_ptr(), n, max(c, 1), h, w, sad.data_ptr(), st), "savsr_video_pair_sad_u8")
+    return sad
+
+
+def pair_sad(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8) -> torch.Tensor:
+    """The scene detector's scores: int64 [N - 1] on the GPU, entry j = the sum of absolute differences of the 8-bit samples of frames j
+    and j + 1 (savsr_amd.scenes.pair_sad is the specification).  frames as for SAVSR.upscale_video, with any c in 1 .. 3: [N, h, w, c]
+    uint8 (GPU or host; every byte), [N, c, h, w] float on the GPU (every value after the uint8 output's quantisation), or with
+    pixel_format="i420", size=(h, w): [N, i420_bytes(h, w)] uint8 (the Y plane only).  depth = 10, 12 (I420 only): frames of 16-bit samples,
+    [N, 2 * i420_bytes(h, w)] uint8, compared by their 8 most significant bits, so the scores keep the 8-bit scale.  pixel_format="i422" /
+    "i444": frames of those layouts; the Y plane only, as for I420."""
+    return _pair_sad_device(*_stage_args(frames, pixel_format, size, depth))
+
+
+def detect_cuts(frames: torch.Tensor, threshold=10.0, pixel_format: str = "rgb", size=None, depth: int = 8) -> List[int]:
+    """The scene cuts of a video: the frames k whose change from frame k - 1, damped by the previous pair's, is at least `threshold`
+    per cent of the largest possible one (ffmpeg scdet's rule in exact integer arithmetic, savsr_amd.scenes.cuts_from_sad, on pair_sad's
+    scores; one device -> host copy of N - 1 integers).  The default threshold is scdet's and is not validated on real footage."""
+    check_threshold(threshold)
+    sad = pair_sad(frames, pixel_format, size, depth)
+    return cuts_from_sad(sad.cpu().tolist(), sad_samples(frames.shape, pixel_format, size), threshold)
+
+
+# ---- the active picture (savsr_amd/active.py is the specification) ----------------------------------------------------------------------
+def _line_sums_device(frames: torch.Tensor, side: Side, size: Size) -> Tuple[torch.Tensor, torch.Tensor]:
+    """savsr_video_line_sums_* on frames of the input side already on the GPU: int64 ([N, h], [N, w]) there, enqueued on the current stream
+    (no sync).  Every frame kind is host work over the three entries: which matrix, which stride, and the folding of their sums."""
+    from . import _lib
+    n, c, h, w = detector_layout(frames, side, size)
+    lib = _lib.load()
+    u8 = frames.dtype == torch.uint8
+    frames = frames.contiguous() if u8 else frames.to(torch.float32).contiguous()
+    with torch.cuda.device(frames.device):
+        st = torch.cuda.current_stream().cuda_stream
+        if u8:
+            tab = plane_table(side, size, c, h, w)
+            y = tab.planes[0]
+            mats, width = n, y.row_bytes // tab.sample
+        else:
+            mats, width = n * c, w
+        cells = torch.empty(mats * (h + width), dtype=torch.int32, device=frames.device)          # (one buffer: the entry zeroes it in one memset)
+        rows, cols = cells[:mats * h].view(mats, h), cells[mats * h:].view(mats, width)
+        if not u8:
+            _lib.check(lib.savsr_video_line_sums_f32(frames.data_ptr(), n * c, h, w, rows.data_ptr(), cols.data_ptr(), st), "savsr_video_line_sums_f32")
+            rows, cols = rows.view(n, c, h), cols.view(n, c, w)
+        elif tab.sample == 2:
+            _lib.check(lib.savsr_video_line_sums_u16(frames.data_ptr(), n, tab.stride, h, width, side.depth, rows.data_ptr(), cols.data_ptr(), st),
+                       "savsr_video_line_sums_u16")
+        else:
+            _lib.check(lib.savsr_video_line_sums_u8(frames.data_ptr(), n, tab.stride, h, width, rows.data_ptr(), cols.data_ptr(), st),
+                       "savsr_video_line_sums_u8")
+            if c:
+                cols = cols.view(n, w, c)          # (a cell is below 2^32: as int64 before the channels are folded)
+        rows, cols = (t.to(torch.int64) & 0xFFFFFFFF for t in (rows, cols))          # the cells are unsigned
+        if not u8:
+            rows, cols = rows.sum(1), cols.sum(1)
+        elif c:
+            cols = cols.sum(2)
+    return rows, cols
+
+
+def line_sums(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The active-picture detector's line sums: int64 ([N, h], [N, w]) on the GPU, per frame the sum of the 8-bit samples of every row
+    and of every column (savsr_amd.active.line_sums is the specification), on the caller's current stream, without a sync.  frames as for
+    `pair_sad`, and the same samples: every byte of [N, h, w, c] uint8 frames (GPU or host), every value of [N, c, h, w] float frames on the
+    GPU after the uint8 output's quantisation, the Y plane of planar frames (pixel_format=, size=(h, w); at depth 10 / 12 a sample's 8
+    most significant bits)."""
+    return _line_sums_device(*_stage_args(frames, pixel_format, size, depth))
+
+
+def _detect_device(frames: torch.Tensor, side: Side, size: Size, limit) -> Tuple[int, int, int, int]:
+    """The aligned active rect of frames of the input side on the GPU: the line sums, their maxima over the frames on the device, one
+    device -> host copy of h + w integers, then active_rect and align_rect on the host."""
+    n, c, h, w = detector_layout(frames, side, size)
+    rows, cols = _line_sums_device(frames, side, size)
+    top = torch.cat([rows.amax(0), cols.amax(0)]).cpu().tolist()
+    s_row, s_col = active.line_samples(h, w, max(c, 1))
+    return active.align_rect(active.active_rect(top[:h], top[h:], s_row, s_col, limit), side.layout)
+
+
+def detect_active_area(frames: torch.Tensor, limit=24, pixel_format: str = "rgb", size=None, depth: int = 8) -> Tuple[int, int, int, int]:
+    """The active picture (y0, x0, ah, aw) of a letterboxed, pillarboxed or window-boxed video: ffmpeg cropdetect's rule in exact integer
+    arithmetic (savsr_amd.active.active_rect) on `line_sums`: a row or column whose mean sample stays at or below `limit` (the 8-bit
+    scale) in every frame is bar, the picture spans the first to the last line that is not; the offsets are then moved outwards to the
+    chroma block of the layout (active.align_rect).  No picture, or one below 2 x 2: the whole frame.  The default limit is cropdetect's
+    and is not validated on real footage."""
+    active.check_limit(limit)
+    return _detect_device(*_stage_args(frames, pixel_format, size, depth), limit)
+
+
+def _plane_views(frames: torch.Tensor, side: Side, hw: Tuple[int, int], rect):
+    """Per plane of planar [n, frame_bytes] frames of h x w: (the rect's window of the plane as an [n, rows, bytes] view, the plane of
+    the rect-sized frame in the table of that size).  rect = (y0, x0, ah, aw) in luma samples, divided by each plane's block; bytes, so
+    a 16-bit sample is two of them and the offsets stay even."""
+    y0, x0, ah, aw = rect
+    n = frames.shape[0]
+    tab = plane_table(side, hw)
+    for p, q in zip(tab.planes, plane_table(side, (ah, aw)).planes):
+        py, px = y0 // p.bv, (x0 // p.bh) * tab.sample
+        yield frames[:, p.offset:p.offset + p.rows * p.row_bytes].view(n, p.rows, p.row_bytes)[:, py:py + q.rows, px:px + q.row_bytes], q
+
+
+def _crop_device(frames: torch.Tensor, rect, side: Side, hw: Tuple[int, int]) -> torch.Tensor:
+    """active.crop_frames on a device tensor: strided copies through views.  Planar frames: every plane sliced at the rect divided by its
+    block and the slices concatenated."""
+    y0, x0, ah, aw = rect
+    if not side.planar:
+        if frames.dtype == torch.uint8:
+            return frames[:, y0:y0 + ah, x0:x0 + aw].contiguous()
+        return frames[:, :, y0:y0 + ah, x0:x0 + aw].contiguous()
+    return torch.cat([win.reshape(frames.shape[0], q.rows * q.row_bytes) for win, q in _plane_views(frames, side, hw, rect)], 1)
+
+
+def _insert_device(sr: torch.Tensor, placed, spec: VideoSpec) -> torch.Tensor:
+    """active.insert_frames on a device tensor: full-size frames of active.bars_frame with the picture's planes copied in at (Y0, X0)
+    divided by each plane's block."""
+    Hf, Wf, Ha, Wa, Y0, X0 = placed
+    out, n = spec.out, sr.shape[0]
+    bars = torch.from_numpy(active.bars_frame(Hf, Wf, out.fmt, out.depth, out.colour, spec.nch)).to(sr.device)
+    full = bars.unsqueeze(0).repeat(n, *([1] * bars.dim()))
+    if out.fmt == "float":
+        full[:, :, Y0:Y0 + Ha, X0:X0 + Wa] = sr
+    elif not out.planar:
+        full[:, Y0:Y0 + Ha, X0:X0 + Wa] = sr
+    else:
+        for win, q in _plane_views(full, out, (Hf, Wf), (Y0, X0, Ha, Wa)):
+            win[:] = sr[:, q.offset:q.offset + q.rows * q.row_bytes].view(n, q.rows, q.row_bytes)
+    return full
+
+
+def _check_crop_args(crop, crop_limit, bars, auto_ok: bool = True):
+    """crop is None, "auto" or a rect; bars / crop_limit go with a crop.  The rect itself: active.check_rect, once the frame size is known."""
+    if crop is None:
+        if bars != "keep":
+            raise ValueError(f"bars = {bars!r} goes with crop=: without a crop there are no bars to keep or drop")
+        if isinstance(crop_limit, bool) or crop_limit != active.DEFAULT_LIMIT:
+            raise ValueError(f"crop_limit = {crop_limit!r} goes with crop=: it is the limit of the detector behind crop='auto'")
+        return None
+    active.check_bars(bars)
+    active.check_limit(crop_limit)
+    if isinstance(crop, str):
+        if crop != "auto":
+            raise ValueError(f"crop = {crop!r}: None, 'auto' or a rect (y0, x0, ah, aw) of ints")
+        if not auto_ok:
+            raise ValueError("crop = 'auto' in VideoUpscaler: the decision needs the whole video; detect the rect first "
+                             "(savsr_amd.detect_active_area) and give it, or use python -m savsr_amd.upscale --crop auto")
+        return crop
+    return active.check_rect(crop, None, None, None)
+
+
+def _cropped_spec(spec: VideoSpec, rect) -> VideoSpec:
+    """The VideoSpec of the cropped frames: the same sides at the rect's size."""
+    return replace(spec, size=(rect[2], rect[3])) if spec.size else spec
+
+
+# ---- interlaced video (savsr_amd/deinterlace.py is the specification) -----------------------------------------------------------------------
+def _check_fields(fields) -> Optional[str]:
+    if fields is None:
+        return None
+    check_order(fields, "fields")
+    return fields
+
+
+def _field_frames(frames: torch.Tensor, side: Side, size: Size) -> Tuple[int, int, int, int]:
+    """(N, c, h, w) of frames the deinterlacer takes (`detector_layout`'s, N = 0 allowed); refuses float frames and frames whose matrices
+    have one row."""
+    if isinstance(frames, torch.Tensor) and not size and frames.is_floating_point():
+        raise ValueError("float frames have no integer samples to deinterlace: give [N, h, w, c] uint8 or planar frames (quantise first)")
+    if isinstance(frames, torch.Tensor) and frames.dim() and int(frames.shape[0]) == 0:
+        n, c, h, w = (0,) + detector_layout(frames.new_zeros((1,) + tuple(frames.shape[1:])), side, size)[1:]
+    else:
+        n, c, h, w = detector_layout(frames, side, size)
+    check_frame_rows(h, side.layout)
+    return n, c, h, w
+
+
+def _field_job(frames: torch.Tensor, order: str, side: Side, size: Size, hi: Optional[int]):
+    """What the three field kernels' wrappers share: (the contiguous resident frames, their count, hi (default: all), the channels of
+    packed frames (0: planar), the plane table, the order's id)."""
+    n, c, h, w = _field_frames(frames, side, size)
+    return frames.contiguous(), n, n if hi is None else hi, c, plane_table(side, size, c, h, w), FIELD_ORDERS.index(order)
+
+
+def _deinterlace_device(frames: torch.Tensor, order: str, side: Side, size: Size, lo: int = 0, hi: Optional[int] = None) -> torch.Tensor:
+    """savsr_video_deinterlace_* on resident frames of the input side on the GPU: the 2 (hi - lo) progressive frames of source frames
+    [lo, hi) (default: all), prev / next taken among the resident frames and clamped there.  One call per plane, on the current stream."""
+    from . import _lib
+    frames, n, hi, c, tab, oid = _field_job(frames, order, side, size, hi)
+    out = frames.new_empty((2 * (hi - lo),) + tuple(frames.shape[1:]))
+    if hi <= lo:
+        return out
+    lib = _lib.load()
+    with torch.cuda.device(frames.device):
+        st = torch.cuda.current_stream().cuda_stream
+        for p in tab.planes:          # (the pixel step of packed frames is their channel count: neighbours of a sample are c bytes away)
+            if tab.sample == 1:
+                _lib.check(lib.savsr_video_deinterlace_u8(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes, max(c, 1), oid, lo, hi,
+                                                          out.data_ptr(), tab.stride, p.offset, st), "savsr_video_deinterlace_u8")
+            else:
+                _lib.check(lib.savsr_video_deinterlace_u16(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes // 2, side.depth, oid, lo, hi,
+                                                           out.data_ptr(), tab.stride, p.offset, st), "savsr_video_deinterlace_u16")
+    return out
+
+
+def deinterlace(frames: torch.Tensor, order: str, pixel_format: str = "rgb", size=None, depth: int = 8) -> torch.Tensor:
+    """Interlaced video as progressive frames at the field rate: 2N frames on the GPU in the format of the N given ones
+    (savsr_amd.deinterlace.deinterlace_frames is the specification, bit for bit), on the caller's current stream, without a sync.  Output
+    frame 2n + f keeps field f of source frame n (order "tff": the top field is the earlier one; "bff": the bottom one) and interpolates
+    the other rows by ffmpeg yadif's rule.  frames: [N, h, w, c] uint8 (GPU or host, c in 1 .. 3), or with pixel_format "i420", "i422",
+    "i444", "y400" and size=(h, w): [N, frame_bytes] uint8, every plane on its own, 16-bit samples at depth 10 / 12.  Float frames are
+    refused, and so are frames of one row (three for 4:2:0: the chroma planes need two)."""
+    check_order(order)
+    frames, side, size = _stage_args(frames, pixel_format, size, depth, _field_frames)
+    return _deinterlace_device(frames, order, side, size)
+
+
+class FieldSplitter:
+    """The streaming deinterlacer behind VideoUpscaler(fields=...): push(source frames on the GPU) returns the progressive frames that are
+    final, finish() the last source frame's two.  The second field of the last pushed frame needs the frame after it, so one source frame
+    is held back; with the frame before it (the temporal context) the device keeps at most two source frames between pushes (copies of
+    their own, so that the chunk they came with is released).  Concatenated, the outputs are `deinterlace` on the whole video for any
+    chunking.  finish() without a pushed frame returns None."""
+
+    def __init__(self, order: str, side: Side, size: Size):
+        self.order, self.side, self.size = _check_fields(order), side, size
+        self._src: Optional[torch.Tensor] = None          # source frames [seen - len, seen): the context frame, then the ones not done
+        self._todo = 0                                    # how many of them are not deinterlaced yet (they are the last ones)
+
+    def push(self, frames: torch.Tensor) -> torch.Tensor:
+        k = int(frames.shape[0])
+        src = frames.contiguous() if self._src is None else torch.cat([self._src, frames], 0)
+        n = int(src.shape[0])
+        lo, hi = n - self._todo - k, n - 1                # all but the last frame, whose next is not known yet
+        res = _deinterlace_device(src, self.order, self.side, self.size, lo, max(hi, lo))
+        if hi > lo:
+            self._src, self._todo = src[max(hi - 1, 0):].clone(), 1          # (a copy of two frames: the chunk's storage is released)
+        else:
+            self._src, self._todo = src, self._todo + k
+        return res
+
+    @property
+    def held(self) -> int:
+        """Source frames on the device between pushes: at most two."""
+        return 0 if self._src is None else int(self._src.shape[0])
+
+    def finish(self) -> Optional[torch.Tensor]:
+        src, self._src = self._src, None
+        if src is None or self._todo == 0:          # nothing was pushed (or finish() ran before)
+            return None
+        n = int(src.shape[0])
+        return _deinterlace_device(src, self.order, self.side, self.size, n - self._todo, n)
+
+
+# ---- telecined film (savsr_amd/pulldown.py is the specification) -----------------------------------------------------------------------------
+def _check_pulldown(pulldown, cycle, fields) -> Optional[str]:
+    """pulldown is None or a field order; pulldown_cycle goes with it, and fields= does not."""
+    if pulldown is None:
+        if isinstance(cycle, bool) or cycle != pd.DEFAULT_CYCLE:
+            raise ValueError(f"pulldown_cycle = {cycle!r} goes with pulldown=: it is the decimation cycle of the pulldown removal")
+        return None
+    check_order(pulldown, "pulldown")
+    if fields is not None:
+        raise ValueError(f"pulldown = {pulldown!r} together with fields = {fields!r}: they are two answers to one question (telecined film, "
+                         f"whose frames are recovered, or interlaced video, whose fields are interpolated); give one of them")
+    pd.check_cycle(cycle, "pulldown_cycle")
+    return pulldown
+
+
+def _field_scores_device(frames: torch.Tensor, order: str, side: Side, size: Size, lo: int = 0, hi: Optional[int] = None) -> torch.Tensor:
+    """savsr_video_field_scores_* on resident frames of the input side on the GPU: int64 [hi - lo, 2] there for source frames [lo, hi)
+    (default: all), the previous frame taken among the resident ones and clamped there; enqueued on the current stream (no sync).  Every
+    byte of packed frames, the Y plane of planar ones."""
+    from . import _lib
+    frames, n, hi, c, tab, oid = _field_job(frames, order, side, size, hi)
+    lib = _lib.load()
+    with torch.cuda.device(frames.device):
+        out = torch.empty(max(hi - lo, 0), 2, dtype=torch.int64, device=frames.device)
+        if hi <= lo:
+            return out
+        st = torch.cuda.current_stream().cuda_stream
+        y = tab.planes[0]
+        if tab.sample == 1:
+            _lib.check(lib.savsr_video_field_scores_u8(frames.data_ptr(), n, tab.stride, y.offset, y.rows, y.row_bytes, oid, lo, hi, out.data_ptr(), st),
+                       "savsr_video_field_scores_u8")
+        else:
+            _lib.check(lib.savsr_video_field_scores_u16(frames.data_ptr(), n, tab.stride, y.offset, y.rows, y.row_bytes // 2, side.depth, oid, lo, hi,
+                                                        out.data_ptr(), st), "savsr_video_field_scores_u16")
+    return out
+
+
+def _weave_device(frames: torch.Tensor, order: str, delta: torch.Tensor, side: Side, size: Size, lo: int = 0, hi: Optional[int] = None) -> torch.Tensor:
+    """savsr_video_weave on resident frames of the input side on the GPU: the hi - lo woven frames of source frames [lo, hi) (default:
+    all) with the device table delta (int32 [hi - lo], -1 | 0).  One call per plane, on the current stream."""
+    from . import _lib
+    frames, n, hi, c, tab, oid = _field_job(frames, order, side, size, hi)
+    out = frames.new_empty((max(hi - lo, 0),) + tuple(frames.shape[1:]))
+    if hi <= lo:
+        return out
+    if delta.dtype != torch.int32 or delta.device != frames.device or delta.numel() != hi - lo or not delta.is_contiguous():
+        raise ValueError(f"delta must be {hi - lo} contiguous int32 on {frames.device}, got {delta.dtype} {tuple(delta.shape)} on {delta.device}")
+    lib = _lib.load()
+    with torch.cuda.device(frames.device):
+        st = torch.cuda.current_stream().cuda_stream
+        for p in tab.planes:
+            _lib.check(lib.savsr_video_weave(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes, oid, lo, hi, delta.data_ptr(),
+                                             out.data_ptr(), tab.stride, p.offset, st), "savsr_video_weave")
+    return out
+
+
+def field_scores(frames: torch.Tensor, order: str, pixel_format: str = "rgb", size=None, depth: int = 8) -> torch.Tensor:
+    """The field matcher's scores: int64 [N, 2] on the GPU (savsr_amd.pulldown.frame_scores is the specification, bit for bit), on the
+    caller's current stream, without a sync.  Entry [n, j] is the comb measure of frame n with its second field (the rows of the other
+    parity than `order`'s first field) taken from frame max(n - 1, 0) (j = 0) or from itself (j = 1).  frames as for `deinterlace`:
+    [N, h, w, c] uint8 (every byte), or planar frames with pixel_format=, size=(h, w) (the Y plane; at depth 10 / 12 a sample's 8 most
+    significant bits).  Float frames are refused."""
+    check_order(order)
+    frames, side, size = _stage_args(frames, pixel_format, size, depth, _field_frames)
+    return _field_scores_device(frames, order, side, size)
+
+
+def _delta_device(matches: List[int], device: torch.device) -> torch.Tensor:
+    from ._xfer import h2d
+    return h2d(torch.tensor(matches, dtype=torch.int32), device)
+
+
+def _remove_pulldown_device(frames: torch.Tensor, order: str, side: Side, size: Size, cycle: int):
+    """pulldown.remove_pulldown_frames on frames of the input side on the GPU: (the kept woven frames, info).  Two host synchronisations:
+    the scores come down for the match, the woven frames' pair SADs for the decimation."""
+    n = _field_frames(frames, side, size)[0]
+    if n < 1:
+        raise ValueError("the video has no frames")
+    scores = _field_scores_device(frames, order, side, size).cpu()
+    matches = pd.matches_from_scores(scores.numpy())
+    woven = _weave_device(frames, order, _delta_device(matches, frames.device), side, size)
+    sad = [-1] + _pair_sad_device(woven, side, size).cpu().tolist()
+    kept = pd.kept_from_drops(n, pd.drops_from_sad(sad, cycle))
+    out = woven.index_select(0, torch.tensor(kept, dtype=torch.int64).to(woven.device))
+    return out, {"scores": scores.numpy(), "matches": matches, "sad": torch.tensor(sad, dtype=torch.int64).numpy(), "kept": kept}
+
+
+def remove_pulldown(frames: torch.Tensor, order: str, pixel_format: str = "rgb", size=None, depth: int = 8, cycle: int = 5, return_info: bool = False):
+    """Telecined film (3:2 pulldown) as its film frames: N - N // cycle frames on the GPU in the format of the N given ones
+    (savsr_amd.pulldown.remove_pulldown_frames is the specification, bit for bit).  Every frame keeps its first field (order "tff": the
+    top rows) and takes the second one from itself or from the frame before it, whichever combs less (`field_scores`); of every `cycle`
+    woven frames the one closest to its predecessor (`pair_sad`) is dropped.  frames as for `deinterlace`.  return_info=True: (frames,
+    info), info = {"scores", "matches", "sad", "kept"} as in the specification.  Two host synchronisations per call."""
+    check_order(order)
+    cycle = pd.check_cycle(cycle)
+    frames, side, size = _stage_args(frames, pixel_format, size, depth, _field_frames)
+    out, info = _remove_pulldown_device(frames, order, side, size, cycle)
+    return (out, info) if return_info else out
+
+
+class PulldownRemover:
+    """The streaming pulldown removal behind VideoUpscaler(pulldown=...): push(source frames on the GPU) returns the film frames that are
+    final, finish() the partial last cycle whole (None if there is none).  The match is causal, so a pushed frame is woven at once, with
+    the previous push's last source frame as its context; woven frames wait until their cycle of `cycle` is complete, then the kept ones
+    go on.  Between pushes the device keeps one source frame, at most cycle - 1 woven frames and the last woven frame (the next SAD's
+    predecessor): `held` <= cycle + 1, copies of their own, so that the chunk they came with is released.  Concatenated, the outputs are
+    `remove_pulldown` on the whole video for any chunking; `info` has the matches and the kept indices so far."""
+
+    def __init__(self, order: str, side: Side, size: Size, cycle: int = 5):
+        check_order(order, "pulldown")
+        self.order, self.side, self.size, self.cycle = order, side, size, pd.check_cycle(cycle, "pulldown_cycle")
+        self._ctx: Optional[torch.Tensor] = None           # the last source frame pushed
+        self._last: Optional[torch.Tensor] = None          # the last woven frame
+        self._pend: Optional[torch.Tensor] = None          # the woven frames of the incomplete cycle, frames [_base, seen)
+        self._pend_sad: List[int] = []                     # their pair SADs with their predecessors
+        self._base = 0
+        self.seen = 0
+        self.matches: List[int] = []
+        self.kept: List[int] = []
+
+    @property
+    def held(self) -> int:
+        """Frames on the device between pushes: at most cycle + 1."""
+        return sum(0 if t is None else int(t.shape[0]) for t in (self._ctx, self._last, self._pend))
+
+    @property
+    def info(self) -> dict:
+        return {"matches": list(self.matches), "kept": list(self.kept)}
+
+    def push(self, frames: torch.Tensor) -> torch.Tensor:
+        k = int(frames.shape[0])
+        if k == 0:
+            return frames
+        src = frames.contiguous() if self._ctx is None else torch.cat([self._ctx, frames], 0)
+        n = int(src.shape[0])
+        matches = pd.matches_from_scores(_field_scores_device(src, self.order, self.side, self.size, n - k, n).cpu().numpy())
+        woven = _weave_device(src, self.order, _delta_device(matches, src.device), self.side, self.size, n - k, n)
+        pairs = woven if self._last is None else torch.cat([self._last, woven], 0)
+        sad = _pair_sad_device(pairs, self.side, self.size).cpu().tolist()
+        self._pend_sad += ([-1] if self._last is None else []) + sad
+        pend = woven if self._pend is None else torch.cat([self._pend, woven], 0)
+        self.matches += matches
+        self.seen += k
+        full = (int(pend.shape[0]) // self.cycle) * self.cycle
+        drops = set(pd.drops_from_sad(self._pend_sad[:full], self.cycle, self._base))
+        kept = [j for j in range(self._base, self._base + full) if j not in drops]
+        out = pend.index_select(0, torch.tensor([j - self._base for j in kept], dtype=torch.int64).to(pend.device))
+        self.kept += kept
+        self._pend = pend[full:].clone() if full < int(pend.shape[0]) else None
+        self._pend_sad = self._pend_sad[full:]
+        self._base += full
+        self._ctx, self._last = src[n - 1:].clone(), woven[k - 1:].clone()
+        return out
+
+    def finish(self) -> Optional[torch.Tensor]:
+        pend, self._pend, self._ctx, self._last = self._pend, None, None, None
+        if pend is None:
+            return None
+        self.kept += list(range(self._base, self._base + int(pend.shape[0])))
+        self._base += int(pend.shape[0])
+        self._pend_sad = []
+        return pend
+
+
+def make_stage(fields, pulldown, pulldown_cycle, side: Side, size: Size):
+    """The streaming stage in front of everything else that fields= / pulldown= / pulldown_cycle= ask for, on frames of `side`: None, a
+    FieldSplitter or a PulldownRemover (the two exclude each other), after `_check_fields` and `_check_pulldown`, in that order."""
+    stage = None if _check_fields(fields) is None else FieldSplitter(fields, side, size)
+    if _check_pulldown(pulldown, pulldown_cycle, fields) is not None:
+        stage = PulldownRemover(pulldown, side, size, pulldown_cycle)
+    return stage

@@ -40,7 +40,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .deinterlace import check_frame_rows, check_order
-from .video import check_pixel_format, layout_of
+from .frames import check_pixel_format, layout_of
+from .scenes import pair_sad
 from .yuv import MONO, check_depth, frame_bytes, layout_name, luma_plane, split_planes
 
 CYCLE_MIN, CYCLE_MAX, DEFAULT_CYCLE = 2, 25, 5
@@ -224,7 +225,6 @@ def remove_pulldown_frames(frames, order: str, pixel_format: str = "rgb", size=N
     int64 [N] (pair_sad of the woven frames k - 1, k; entry 0 is -1 and counts as infinite), "kept": the indices of the kept woven
     frames}: the composition of the rules above.  frames: [N, h, w, c] uint8, or with pixel_format "i420", "i422", "i444", "y400" and
     size=(h, w): [N, frame_bytes] uint8, little-endian 16-bit samples at depth 10 / 12.  Float frames are refused."""
-    from .scenes import pair_sad
     check_order(order)
     cycle = check_cycle(cycle)
     frames = _as_numpy(frames)

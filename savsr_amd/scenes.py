@@ -23,7 +23,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from .harness import window_indices
-from .video import check_length, check_padding, check_pixel_format, chroma_of
+from .frames import check_length, check_padding, check_pixel_format, chroma_of
 from .yuv import LUMA_FORMAT, MONO, check_depth, frame_bytes, layout_name, luma_plane, split_planes
 
 

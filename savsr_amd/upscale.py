@@ -479,19 +479,18 @@ def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, de
     """--crop auto's first pass: savsr_amd.line_sums over the input in --chunk-sized pieces with a running maximum on the device, then
     cropdetect's rule and the alignment to the input layout's chroma block.  chunks: the PNG folder's chunk iterator; None: the .y4m file
     named by --input, read through a reader of its own.  order: --fields' field order; the sums are then taken on the deinterlaced frames
-    (a video.FieldSplitter of this pass's own), as the second pass will crop them.  film: --pulldown's field order; the sums are then taken
-    on the recovered film frames (a video.PulldownRemover of this pass's own)."""
+    (a prepass.FieldSplitter of this pass's own), as the second pass will crop them.  film: --pulldown's field order; the sums are then taken
+    on the recovered film frames (a prepass.PulldownRemover of this pass's own)."""
     import torch
 
     from . import active
-    from .video import FieldSplitter, PulldownRemover, _sad_side, layout_of, line_sums
+    from .frames import detector_side, layout_of
+    from .prepass import line_sums, make_stage
     from .y4m import Y4MReader
     from .yuv import CHROMAS
     top = None
     f = None
-    split = None if order is None else FieldSplitter(order, *_sad_side(fmt_in, size, depth))
-    if film is not None:
-        split = PulldownRemover(film, *_sad_side(fmt_in, size, depth), a.pulldown_cycle)
+    split = make_stage(order, film, a.pulldown_cycle, *detector_side(fmt_in, size, depth))
 
     def fold(frames):
         nonlocal top

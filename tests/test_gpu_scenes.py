@@ -127,6 +127,34 @@ def test_pair_sad_f32_equals_the_spec(h, w, c):
         assert np.array_equal(savsr_amd.pair_sad(dv[:n]).cpu().numpy(), want[:n - 1])
 
 
+# every planar layout at two depths and packed uint8, at 5 x 3 (an odd frame stride: the one-sample form) and 16 x 32 (strides and bases
+# are 16-byte multiples: the vector form); one float case
+_KINDS = [(fmt, depth, h, w) for fmt in ("y400", "i420", "i422", "i444") for depth in (8, 10) for h, w in ((5, 3), (16, 32))]
+_KINDS += [("rgb", 8, 5, 3), ("rgb", 8, 16, 32), ("float", 8, 5, 3)]
+
+
+@pytest.mark.parametrize("fmt,depth,h,w", _KINDS)
+def test_public_pair_sad_of_every_frame_kind_equals_the_spec(fmt, depth, h, w):
+    """savsr_amd.pair_sad picks the C entry from the frame kind (planar colour: _yuvp; packed and grey-scale: _u8; float: _f32)."""
+    rng = np.random.RandomState(h + 5 * w + depth + len(fmt))
+    if fmt == "float":
+        v, kw = _float_video(3, 3, h, w, seed=11), {}
+    elif fmt == "rgb":
+        v, kw = rng.randint(0, 256, size=(3, h, w, 3), dtype=np.uint8), {}
+    else:
+        kw = dict(pixel_format=fmt, size=(h, w), depth=depth)
+        samples = yuv.frame_bytes(h, w, 8, savsr_amd.video.layout_of(fmt))
+        if depth == 8:
+            v = rng.randint(0, 256, size=(3, samples), dtype=np.uint8)
+        else:          # 16-bit samples, some above the depth's range (they count as the largest one)
+            v = rng.randint(0, 1 << depth, size=(3, samples)).astype("<u2")
+            v[rng.rand(3, samples) < 0.05] = 0xFFFF
+            v = v.view(np.uint8).reshape(3, -1)
+    want = scenes.pair_sad(v, **kw)
+    got = savsr_amd.pair_sad(torch.from_numpy(v).to(DEV), **kw)
+    assert got.dtype == torch.int64 and got.shape == (2,) and np.array_equal(got.cpu().numpy(), want), (fmt, depth, h, w)
+
+
 def test_pair_sad_covers_every_byte_value_against_every_other():
     a = np.repeat(np.arange(256, dtype=np.uint8)[:, None], 256, 1)               # a[i, j] = i
     pair = np.stack([a, a.T], 0)                                                  # b[i, j] = j

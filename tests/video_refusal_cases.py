@@ -59,6 +59,12 @@ TENSOR_CASES = (
     (1, dict(pixel_format="y400", size=SIZE, out="y400"), lambda: torch.zeros(N, _FB, dtype=torch.uint8)),      # I420 bytes as Y400
     (1, dict(pixel_format="y400", size=SIZE, depth=10), lambda: torch.zeros(N, 2, 12 * 16, dtype=torch.uint8)),
     (1, {}, lambda: torch.zeros(N, 12, 16, 3, dtype=torch.uint8)),                      # channels
+    # a stage in front (fields= / pulldown=): its own refusals speak before the layout's, and the device before the rect
+    (3, dict(fields="tff"), lambda: torch.zeros(N, 3, 12, 16)),                         # float frames: the stage, not "on the GPU"
+    (3, dict(pulldown="tff"), lambda: torch.zeros(N, 1, 16, 3, dtype=torch.uint8)),     # one row: the stage, not h < 2
+    (3, dict(fields="bff"), lambda: torch.zeros(N, 12, 16, 1, dtype=torch.uint8)),      # channels: the stage takes them, the layout not
+    (3, dict(fields="tff", crop=(0, 0, 40, 40)), lambda: torch.zeros(N, 12, 16, 3, dtype=torch.uint8)),      # a rect that does not fit
+    (3, dict(crop=(0, 0, 40, 40)), lambda: torch.zeros(N, 12, 16, 3, dtype=torch.uint8)),                    # the same without a stage
 )
 CASES = GRID_CASES + len(TENSOR_CASES)
 CONSTRUCTED = ["constructed", ""]

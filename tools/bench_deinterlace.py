@@ -39,7 +39,7 @@ def timed(fn, launches):
 def time_kernels(dev, rounds, launches):
     import torch
     from savsr_amd import _lib
-    from savsr_amd.video import _plane_table, _sad_side
+    from savsr_amd.frames import detector_side, plane_table
     from savsr_amd.yuv import i420_bytes
     lib = _lib.load()
     st = torch.cuda.current_stream().cuda_stream
@@ -52,17 +52,16 @@ def time_kernels(dev, rounds, launches):
         o8, oy8, oy10 = (torch.empty((2 * n,) + tuple(t.shape[1:]), dtype=torch.uint8, device=dev) for t in (u8, y8, y10))
 
         def planar(src, dst, depth):
-            side = _sad_side("i420", (h, w), depth)[0]
-            fb = side.frame_bytes(h, w)
-            table = _plane_table(h, w, side)
+            fb, _, planes = plane_table(*detector_side("i420", (h, w), depth))
 
             def call():
                 rc = 0
-                for off, ph, pb, _, _ in table:
+                for p in planes:
                     if depth == 8:
-                        rc |= lib.savsr_video_deinterlace_u8(src.data_ptr(), n, fb, off, ph, pb, 1, 0, 0, n, dst.data_ptr(), fb, off, st)
+                        rc |= lib.savsr_video_deinterlace_u8(src.data_ptr(), n, fb, p.offset, p.rows, p.row_bytes, 1, 0, 0, n, dst.data_ptr(), fb, p.offset, st)
                     else:
-                        rc |= lib.savsr_video_deinterlace_u16(src.data_ptr(), n, fb, off, ph, pb // 2, depth, 0, 0, n, dst.data_ptr(), fb, off, st)
+                        rc |= lib.savsr_video_deinterlace_u16(src.data_ptr(), n, fb, p.offset, p.rows, p.row_bytes // 2, depth, 0, 0, n, dst.data_ptr(), fb,
+                                                              p.offset, st)
                 return rc
             return call
 

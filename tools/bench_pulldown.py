@@ -42,7 +42,7 @@ def timed(fn, launches):
 def time_kernels(dev, rounds, launches):
     import torch
     from savsr_amd import _lib
-    from savsr_amd.video import _plane_table, _sad_side
+    from savsr_amd.frames import detector_side, plane_table
     from savsr_amd.yuv import i420_bytes
     lib = _lib.load()
     st = torch.cuda.current_stream().cuda_stream
@@ -57,14 +57,12 @@ def time_kernels(dev, rounds, launches):
         o8, oy8, oy10 = (torch.empty_like(t) for t in (u8, y8, y10))
 
         def planar_weave(src, dst, depth):
-            side = _sad_side("i420", (h, w), depth)[0]
-            fb = side.frame_bytes(h, w)
-            table = _plane_table(h, w, side)
+            fb, _, planes = plane_table(*detector_side("i420", (h, w), depth))
 
             def call():
                 rc = 0
-                for off, ph, pb, _, _ in table:
-                    rc |= lib.savsr_video_weave(src.data_ptr(), n, fb, off, ph, pb, 0, 0, n, delta.data_ptr(), dst.data_ptr(), fb, off, st)
+                for p in planes:
+                    rc |= lib.savsr_video_weave(src.data_ptr(), n, fb, p.offset, p.rows, p.row_bytes, 0, 0, n, delta.data_ptr(), dst.data_ptr(), fb, p.offset, st)
                 return rc
             return call
 

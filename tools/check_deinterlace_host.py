@@ -26,7 +26,7 @@ def build(cxx: str, work: str) -> str:
     with open(os.path.join(work, "deinterlace_device.inc"), "w") as f:
         f.write(src.replace('#include "common.hpp"', '#include "hip_stub.h"'))
     exe = os.path.join(work, "deinterlace_host")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", work, "-I", HERE,
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", work, "-I", HERE, "-I", os.path.join(ROOT, "savsr_amd", "csrc"),
                     os.path.join(HERE, "deinterlace_main.cpp"), "-o", exe], check=True)
     return exe
 

@@ -1,6 +1,6 @@
-// Host stand-ins for the few HIP names csrc/deinterlace.hip uses, so that its device functions compile unchanged into a stand-alone host
-// program (tools/check_deinterlace_host.py): a launch runs the kernel body one thread at a time over the grid.  Host only; nothing here
-// is loaded into Python or run on a GPU.
+// Host stand-ins for the few HIP and common.hpp names csrc/deinterlace.hip, csrc/pulldown.hip and csrc/video_samples.hpp use, so that
+// their device functions compile unchanged into a stand-alone host program (tools/check_deinterlace_host.py, check_pulldown_host.py):
+// a launch runs the kernel body one thread at a time over the grid.  Host only; nothing here is loaded into Python or run on a GPU.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -23,6 +23,7 @@ typedef void* hipStream_t;
 #define SAVSR_E_ARG (-1)
 static char g_last_error[256];
 namespace savsr {
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 inline int fail_arg(const char* what) {
     snprintf(g_last_error, sizeof g_last_error, "invalid argument: %s", what);
     return SAVSR_E_ARG;
