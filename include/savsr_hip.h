@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 44
+#define SAVSR_ABI_VERSION 45
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -685,6 +685,36 @@ int savsr_video_field_scores_u16(const uint8_t* frames, int n_frames, int64_t fr
                                  int order, int from, int to, int64_t* out, void* stream);
 int savsr_video_weave(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes, int order, int from,
                       int to, const int32_t* delta, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 45) Video surfaces (surface.hip; savsr_amd.unpack_surface, savsr_amd.pack_surface, upscale_video(surface=..., out_surface=...),
+ * VideoUpscaler(surface=..., out_surface=...)): NV12 / NV21 / NV16, P010 / P012 / P210 / P212, UYVY / YUYV and
+ * pitched planar frames <-> the tightly packed planar frames every other video entry takes (savsr_amd/surface.py `unpack_frames` /
+ * `pack_frames` restate them; the kernels equal them bit for bit).  The planar side: n_frames frames of h x w samples, planar_frame_bytes
+ * apart, Y then U and V in layout `chroma` (0: 4:2:0, 1: 4:2:2, 2: 4:4:4, 3: the Y plane alone), a byte per sample at depth 8, a
+ * little-endian 16-bit word at 10 / 12.  The surface side: frames surface_frame_bytes apart, described by `planes`, a HOST array of
+ * n_planes (1 .. 3) x 17 int64 words read before the call returns: the plane's byte offset in a frame, its pitch, rows and groups per
+ * row, its step (1, 2 or 4 samples per group), then (plane, mul, add) of four component streams (those beyond `step` are not read):
+ * group g of a row holds, at sample position k, sample mul * g + add of the same row of planar plane `plane` (0 Y, 1 U, 2 V); a group
+ * whose sample lies past the planar row's end is padding.  msb = 1 (depth 10 / 12): a surface word carries its sample in the high
+ * `depth` bits; unpack writes x >> (16 - depth), pack min(s, 2^depth - 1) << (16 - depth); every other sample is copied verbatim.
+ * One launch for all planes of all frames (the descriptors travel by value in the kernel arguments); the entries only enqueue, allocate
+ * nothing, do not synchronise and are capturable.  Refused before the device is touched with SAVSR_E_ARG, savsr_last_error() naming the
+ * reason: a null pointer, n_frames < 1, h or w outside 1 .. 65536, a depth, chroma, msb, plane count or step outside the lists above, a
+ * negative offset, no rows or groups, a pitch below the row's bytes, an odd pointer, stride, offset or pitch with 16-bit samples, a
+ * stream of a plane the layout has not, a surface plane whose rows are not its planar planes' rows or that has more groups than they
+ * have samples, surface planes that overlap, a frame stride below either side's frame, a frame above 2^31 work items.
+ * 16-byte accesses (and v_perm_b32 to de-interleave) when the surface pointer, its frame stride and the plane's offset and pitch are
+ * multiples of 16, a sample per access otherwise and in the tails of rows.  A row is read inside [row start, row start + row bytes) only.
+ * savsr_video_unpack_surface: surface -> planar.  Bytes of the surface that hold no sample are not read.
+ * savsr_video_pack_surface:   planar -> surface.  surface_bytes (from the planes' last byte to surface_frame_bytes): the resolved bytes
+ *                             of a frame; every one of them that no sample maps to is written as 0 (one hipMemset2DAsync on `stream`
+ *                             first when the planes' rows do not cover them all), nothing is written beyond them. */
+int savsr_video_unpack_surface(const uint8_t* surface, int n_frames, int64_t surface_frame_bytes, int h, int w, int depth, int chroma, int msb,
+                               const int64_t* planes, int n_planes, uint8_t* planar, int64_t planar_frame_bytes, void* stream);
+int savsr_video_pack_surface(const uint8_t* planar, int n_frames, int64_t planar_frame_bytes, int h, int w, int depth, int chroma, int msb,
+                             const int64_t* planes, int n_planes, uint8_t* surface, int64_t surface_frame_bytes, int64_t surface_bytes,
+                             void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 33) Geometric self-ensemble (ensemble.hip; SAVSR.set_self_ensemble).  Variant k = 0 .. 7: fw = k & 1 flips

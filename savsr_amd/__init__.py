@@ -5,7 +5,10 @@ from .archs.savsr_arch import SAVSR  # noqa: F401
 from . import datasets as _datasets, models as _models  # noqa: F401,E402  (register ASVideoTestDataset / ASVSRModel)
 from .datasets import build_dataset  # noqa: F401,E402
 from .models import build_model  # noqa: F401,E402
-from .video import VideoUpscaler, detect_active_area, detect_cuts, field_scores, line_sums, pair_sad, remove_pulldown  # noqa: F401,E402
+from .video import (VideoUpscaler, detect_active_area, detect_cuts, field_scores, line_sums, pack_surface, pair_sad,  # noqa: F401,E402
+                    remove_pulldown, unpack_surface)
+from . import surface  # noqa: F401,E402  (the specification of unpack_surface / pack_surface / upscale_video(surface=..., out_surface=...))
+from .surface import Surface  # noqa: F401,E402
 from . import pulldown  # noqa: F401,E402  (the specification of remove_pulldown / upscale_video(pulldown=...))
 from . import deinterlace  # noqa: F401,E402  (the specification module; calling it is savsr_amd.video.deinterlace, the GPU function)
 

@@ -281,7 +281,7 @@ class SAVSR(nn.Module):
                       size=None, cuts=None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None, depth: int = 8,
                       out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
                       chroma_filter: Optional[str] = None, crop=None, crop_limit=24, bars: str = "keep", fields: Optional[str] = None,
-                      pulldown: Optional[str] = None, pulldown_cycle: int = 5) -> torch.Tensor:
+                      pulldown: Optional[str] = None, pulldown_cycle: int = 5, *, surface=None, out_surface=None) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -342,11 +342,21 @@ class SAVSR(nn.Module):
         for bit, upscale_video on savsr_amd.remove_pulldown(frames, pulldown, ...) with every other argument the same, and explicit cuts
         index the film frames.  Not together with fields.  No cadence tracking; see savsr_amd/pulldown.py for the limits.  None (the
         default) runs what ran before.
+        surface, out_surface (keyword only): None or a savsr_amd.surface.Surface, for planar samples that do not lie as a Y4M file has them:
+        a hardware decoder's NV12 / P010 surfaces with a row pitch and padded lines (Surface.nv12(pitch=..., lines=...), .nv21, .nv16, .p010,
+        .p012, .p210, .p212), a capture card's packed 4:2:2 (Surface.uyvy(), .yuyv()), a software decoder's planar frames with a linesize
+        (Surface.planar(pitch=...)).  pixel_format, size and depth still say which samples a frame has; `surface` says where they lie, and
+        frames are [N, stride] uint8 with stride >= the surface's bytes.  They are unpacked on the GPU in front of everything else and the
+        result is packed behind everything else: the call is, bit for bit, upscale_video on savsr_amd.unpack_surface(frames, surface,
+        pixel_format, size, depth), and its result savsr_amd.pack_surface(result, out_surface, out, (H, W), out_depth), in which every byte
+        no sample maps to is 0.  surface goes with a planar pixel_format ("i420", "i422", "i444", "y400"), out_surface with a planar out;
+        pixel_format="nv12" stays an unknown format.  None (the default) runs what ran before.
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
         return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold, colour, out_colour, depth, out_depth,
-                             siting, out_siting, chroma_filter, crop, crop_limit, bars, fields, pulldown, pulldown_cycle)
+                             siting, out_siting, chroma_filter, crop, crop_limit, bars, fields, pulldown, pulldown_cycle, surface=surface,
+                             out_surface=out_surface)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

@@ -1,6 +1,7 @@
 """Everything that runs on the device in front of the network: the scene detector's scores, the active-picture detector with crop and
-re-insertion, the deinterlacer and the pulldown removal.  Each is a public call on any frames and a `_..._device` form on resident frames
-of a checked input side (what upscale_video calls on the whole video); the two that change the frame count are streaming stages as well
+re-insertion, the deinterlacer and the pulldown removal -- and, at the very boundary, the surface conversion (`unpack_surface` in front of
+all of them, `pack_surface` behind everything; savsr_amd/surface.py is its specification).  Each is a public call on any frames and a
+`_..._device` form on resident frames of a checked input side (what upscale_video calls on the whole video); the two that change the frame count are streaming stages as well
 (`FieldSplitter`, `PulldownRemover`; `make_stage` builds the one a call asks for).  The numpy modules (scenes.py, active.py,
 deinterlace.py, pulldown.py) are the specifications, bit for bit.  Where the byte matrices of a frame lie is `frames.plane_table`'s
 answer alone; fp32 CHW frames have entries of their own (`_f32`) and are one explicit branch in the two stages that accept them.
@@ -15,8 +16,9 @@ import torch
 from . import active
 from . import pulldown as pd
 from .deinterlace import FIELD_ORDERS, check_frame_rows, check_order
-from .frames import Side, VideoSpec, detector_layout, detector_side, plane_table
+from .frames import SAMPLE_FORMATS, Side, VideoSpec, check_sample_alignment, detector_layout, detector_side, plane_table
 from .scenes import check_threshold, cuts_from_sad, sad_samples
+from .surface import LAYOUTS, Surface, SurfaceTable, check_stride, check_surface, descriptor
 from .yuv import CHROMAS
 
 Size = Optional[Tuple[int, int]]
@@ -45,6 +47,100 @@ def _stage_args(frames: torch.Tensor, pixel_format: str, size, depth, layout=det
     side, size = detector_side(pixel_format, size, depth)
     layout(frames, side, size)
     return _to_device(frames, _sad_device(frames)), side, size
+
+
+# ---- video surfaces (savsr_amd/surface.py is the specification) ------------------------------------------------------------------------
+def surface_table(surface: Surface, side: Side, hw: Tuple[int, int], what: str = "surface") -> SurfaceTable:
+    """The table of `surface` for h x w frames of a planar side; refuses, by name, a side that is not planar and what `resolve` refuses."""
+    surface_side(surface, side, what)
+    return surface.resolve(hw[0], hw[1], side.depth, side.layout)
+
+
+def surface_side(surface: Surface, side: Side, what: str = "surface") -> None:
+    """`surface` (or `out_surface`) goes with a planar side: refuses, by name, anything but a Surface, and a side that is not planar."""
+    check_surface(surface, what)
+    if not side.planar:
+        fmt = "pixel_format" if what == "surface" else "out"
+        raise ValueError(f"{what} = Surface.{surface.kind}() goes with {fmt} = {', '.join(repr(f) for f in SAMPLE_FORMATS[:-1])} or "
+                         f"{SAMPLE_FORMATS[-1]!r}: it says where planar samples lie; {side.fmt!r} frames have none")
+
+
+def surface_layout(frames: torch.Tensor, tab: SurfaceTable) -> int:
+    """N of surface frames: [N, stride] uint8 (GPU or host) with stride >= the surface's bytes; refuses anything else, naming both numbers."""
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError(f"frames must be a torch.Tensor, got {type(frames).__name__}")
+    if frames.dtype != torch.uint8 or frames.dim() != 2:
+        raise ValueError(f"surface frames must be [N, bytes] uint8, got {frames.dtype} {tuple(frames.shape)}")
+    check_stride(int(frames.shape[1]), tab, "surface frames")
+    return int(frames.shape[0])
+
+
+def _surface_call(entry: str, src: torch.Tensor, dst: torch.Tensor, tab: SurfaceTable, side: Side, hw: Tuple[int, int], *tail) -> None:
+    """One of the two entries on resident frames, on the current stream: (source, n, its stride, h, w, depth, layout, msb, the planes,
+    destination, its stride[, the surface's bytes])."""
+    from . import _lib
+    import ctypes as C
+    lib = _lib.load()
+    desc = descriptor(tab)
+    with torch.cuda.device(src.device):
+        _lib.check(getattr(lib, entry)(src.data_ptr(), int(src.shape[0]), int(src.shape[1]), hw[0], hw[1], side.depth, LAYOUTS.index(side.layout),
+                                       int(tab.msb), desc.ctypes.data_as(C.POINTER(C.c_int64)), len(tab.planes), dst.data_ptr(), int(dst.shape[1]),
+                                       *tail, torch.cuda.current_stream().cuda_stream), entry)
+
+
+def _unpack_surface_device(frames: torch.Tensor, tab: SurfaceTable, side: Side, hw: Tuple[int, int]) -> torch.Tensor:
+    """savsr_video_unpack_surface on surface frames [n, stride] on the GPU: the planar frames [n, side.frame_bytes(h, w)] there, one
+    launch on the current stream (no sync)."""
+    n = surface_layout(frames, tab)
+    frames = frames.contiguous()
+    check_sample_alignment(frames, side.depth, side.layout)
+    out = torch.empty(n, side.frame_bytes(*hw), dtype=torch.uint8, device=frames.device)
+    if n:
+        _surface_call("savsr_video_unpack_surface", frames, out, tab, side, hw)
+    return out
+
+
+def _pack_surface_device(planar: torch.Tensor, tab: SurfaceTable, side: Side, hw: Tuple[int, int]) -> torch.Tensor:
+    """savsr_video_pack_surface on planar frames [n, side.frame_bytes(h, w)] on the GPU: the surface frames [n, tab.bytes] there, every
+    byte no sample maps to 0; one launch (after one memset when the surface is not tight) on the current stream (no sync)."""
+    fb = side.frame_bytes(*hw)
+    if planar.dtype != torch.uint8 or planar.dim() != 2 or int(planar.shape[1]) != fb:
+        raise ValueError(f"planar frames of {hw[0]} x {hw[1]} are [N, {fb}] uint8, got {planar.dtype} {tuple(planar.shape)}")
+    planar = planar.contiguous()
+    check_sample_alignment(planar, side.depth, side.layout)
+    out = torch.empty(int(planar.shape[0]), tab.bytes, dtype=torch.uint8, device=planar.device)
+    if planar.shape[0]:
+        _surface_call("savsr_video_pack_surface", planar, out, tab, side, hw, tab.bytes)
+    return out
+
+
+def _surface_args(frames, surface, pixel_format, size, depth):
+    side, size = detector_side(pixel_format, size, depth)
+    surface_side(surface, side)
+    tab = surface_table(surface, side, size)
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError(f"frames must be a torch.Tensor, got {type(frames).__name__}")
+    return tab, side, size
+
+
+def unpack_surface(frames: torch.Tensor, surface: Surface, pixel_format: str = "i420", size=None, depth: int = 8) -> torch.Tensor:
+    """Frames in a video surface (NV12, P010, UYVY, pitched planar, ...: savsr_amd.surface.Surface) as the planar frames every other call
+    takes: [N, frame_bytes(h, w, depth, layout)] uint8 on the GPU (savsr_amd.surface.unpack_frames is the specification, bit for bit),
+    on the caller's current stream, without a sync.  frames: [N, stride] uint8, GPU or host (host frames are copied up as they are),
+    stride >= the surface's bytes at size=(h, w); pixel_format ("i420", "i422", "i444", "y400") and depth name the samples, `surface`
+    says where they lie."""
+    tab, side, size = _surface_args(frames, surface, pixel_format, size, depth)
+    surface_layout(frames, tab)
+    return _unpack_surface_device(_to_device(frames, _sad_device(frames)), tab, side, size)
+
+
+def pack_surface(planar: torch.Tensor, surface: Surface, pixel_format: str = "i420", size=None, depth: int = 8) -> torch.Tensor:
+    """Planar frames [N, frame_bytes(h, w, depth, layout)] uint8 (GPU or host) in a video surface: [N, surface bytes] uint8 on the GPU
+    (savsr_amd.surface.pack_frames is the specification, bit for bit), on the caller's current stream, without a sync.  Every byte no
+    sample maps to is 0: row padding, padded lines, the low bits of msb words, the pad Y of an odd-width packed row."""
+    tab, side, size = _surface_args(planar, surface, pixel_format, size, depth)
+    detector_layout(planar, side, size)
+    return _pack_surface_device(_to_device(planar, _sad_device(planar)), tab, side, size)
 
 
 # ---- the scene detector (savsr_amd/scenes.py is the specification) ---------------------------------------------------------------------

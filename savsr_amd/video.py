@@ -22,6 +22,11 @@ film frames), on the hand-cropped video (crop="auto" finds the rect on the devic
 frames of nominal black, bars="drop" returns the picture alone; both are strided copies through torch views).  Each argument at None
 runs exactly the lines that ran before it existed.
 
+surface= / out_surface=: where the samples of planar frames lie in memory on either side (savsr_amd/surface.py: NV12, P010, UYVY, pitched
+planar, ...).  The frames are unpacked right after the host-to-device copy, in front of fields=, pulldown=, crop= and everything else, and
+the result is packed last, after the bars are re-inserted: the call is, bit for bit, the call on `unpack_surface(frames, surface, ...)`,
+and its result `pack_surface(result, out_surface, ...)` at the output's size and depth.  One launch each; nothing between them changes.
+
 Every argument is checked here, on the host, before anything is enqueued on the GPU.
 """
 from __future__ import annotations
@@ -38,8 +43,9 @@ from .harness import window_indices
 from .packing import get_hw
 from .prepass import (FieldSplitter, PulldownRemover, _check_crop_args, _check_fields, _check_pulldown, _crop_device,  # noqa: F401  (re-exported)
                       _cropped_spec, _deinterlace_device, _detect_device, _field_frames, _insert_device, _pair_sad_device,
-                      _remove_pulldown_device, _to_device, deinterlace, detect_active_area, detect_cuts, field_scores, line_sums, make_stage,
-                      pair_sad, remove_pulldown)
+                      _pack_surface_device, _remove_pulldown_device, _to_device, _unpack_surface_device, deinterlace, detect_active_area,
+                      detect_cuts, field_scores, line_sums, make_stage, pack_surface, pair_sad, remove_pulldown, surface_layout,
+                      surface_side, surface_table, unpack_surface)
 
 
 def _check_net(net) -> None:
@@ -68,26 +74,43 @@ def check_cuts_arg(cuts) -> None:
     scenes.check_cuts(cuts, None)
 
 
+def _out_hw(h: int, w: int, crop, bars: str, sc):
+    """The size of the frames a call returns: of the full frame, or of the rect alone with bars="drop"."""
+    return get_hw(*((h, w) if crop is None or bars == "keep" else crop[2:]), sc)
+
+
 def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb",
                   size=None, cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601",
                   out_colour: Optional[str] = None, depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None,
                   out_siting: Optional[str] = None, chroma_filter: Optional[str] = None, crop=None, crop_limit=24,
-                  bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None, pulldown_cycle: int = 5) -> torch.Tensor:
+                  bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None, pulldown_cycle: int = 5, *,
+                  surface=None, out_surface=None) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
     spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter)
     sc = as_scale(net.scale if scale is None else scale)
-    n, h, w = spec.frames_hw(frames)
+    if surface is not None:            # the frames lie in a surface: checked against it, unpacked below, and planar from there on
+        in_tab = surface_table(surface, spec.inp, spec.size)
+        n, (h, w) = surface_layout(frames, in_tab), spec.size
+        shaped = torch.empty(min(n, 1), spec.inp.frame_bytes(h, w), dtype=torch.uint8)          # the frames the stages will be given, by shape
+        spec.frames_hw(shaped)             # (the network's channels, in the planar path's words)
+    else:
+        n, h, w = spec.frames_hw(frames)
+        shaped = frames
+    if out_surface is not None:        # (its table: once the crop is checked, or found)
+        surface_side(out_surface, spec.out, "out_surface")
     if _check_fields(fields) is not None:          # everything below sees the progressive video of 2N frames
-        _field_frames(frames, spec.inp, spec.size)
+        _field_frames(shaped, spec.inp, spec.size)
         n *= 2
     if _check_pulldown(pulldown, pulldown_cycle, fields) is not None:          # everything below sees the film of N - N // cycle frames
-        _field_frames(frames, spec.inp, spec.size)
+        _field_frames(shaped, spec.inp, spec.size)
         n -= n // pulldown_cycle
     crop = _check_crop_args(crop, crop_limit, bars)
     if crop is not None and crop != "auto":
         crop = active.check_rect(crop, h, w, spec.inp.layout)
+    if out_surface is not None and crop != "auto":
+        surface_table(out_surface, spec.out, _out_hw(h, w, crop, bars, sc), "out_surface")
     T = net.num_frame
     if cuts is None:
         check_length(n, T, padding)
@@ -99,6 +122,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         if not _is_auto(cuts):
             cuts = scenes.check_cuts(cuts, n)
     frames = _to_device(frames, _net_device(net))
+    if surface is not None:            # the surface comes first of all: everything below sees planar frames
+        frames = _unpack_surface_device(frames, in_tab, spec.inp, spec.size)
     if fields is not None:             # deinterlacing comes first, before the crop
         frames = _deinterlace_device(frames, fields, spec.inp, spec.size)
     if pulldown is not None:           # pulldown removal comes first, where deinterlacing comes
@@ -122,6 +147,9 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         res = net.engine().forward_video(frames, windows, sc, spec, ensemble=net.self_ensemble)
         if crop is not None and bars == "keep":
             res = _insert_device(res, active.place(crop, h, w, sc, full.out.layout), full)
+        if out_surface is not None:    # the surface comes last of all, after the bars are back
+            HW = _out_hw(h, w, crop, bars, sc)
+            res = _pack_surface_device(res, surface_table(out_surface, full.out, HW, "out_surface"), full.out, HW)
         return res
 
 
@@ -159,13 +187,17 @@ class VideoUpscaler:
     pulldown="tff" / "bff", pulldown_cycle=5: telecined chunks, as in upscale_video, through a prepass.PulldownRemover: a pushed frame is
     woven at once, woven frames wait until their cycle is complete, and finish() flushes the partial last cycle whole (at most
     pulldown_cycle + 1 more frames on the device between pushes; two host synchronisations per push).  `pulldown_info` has the matches
-    and the kept indices so far."""
+    and the kept indices so far.
+
+    surface= / out_surface= (savsr_amd.surface.Surface): as in upscale_video; every pushed chunk is [k, stride] uint8 in `surface` and is
+    unpacked as it arrives, every returned chunk is packed into `out_surface` as it leaves.  The conversion is stateless, so any chunking
+    gives the same frames."""
 
     def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb", size=None,
                  cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None,
                  depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
                  chroma_filter: Optional[str] = None, crop=None, bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None,
-                 pulldown_cycle: int = 5):
+                 pulldown_cycle: int = 5, *, surface=None, out_surface=None):
         _check_net(net)
         check_padding(padding)
         check_out(out, net.cfg["num_in_ch"], chroma_filter)          # (speaks before the cuts, video_spec after them: the order of refusals)
@@ -197,6 +229,14 @@ class VideoUpscaler:
         self.done = 0                                 # frames returned
         self._shape: Optional[tuple] = None           # (dtype is uint8, h, w)
         self._finished = False
+        # surfaces on either side: chunks are unpacked as they arrive and returned frames packed as they leave (stateless: any chunking)
+        self._in_tab = None if surface is None else surface_table(surface, self._full.inp, self._full.size)
+        self._out_tab = None
+        if out_surface is not None:
+            surface_side(out_surface, self._full.out, "out_surface")
+            if self._full.size:            # (packed input carries its size in the first chunk: the table is resolved there)
+                self._set_out_tab(out_surface, *self._full.size)
+        self._out_surface = out_surface
 
     def _set_rect(self, h: int, w: int) -> None:
         """The rect against the full frame size, known now: refused if it does not fit; the whole frame is the uncropped path."""
@@ -206,6 +246,16 @@ class VideoUpscaler:
             return
         self._rect, self._hw = rect, (h, w)
         self.spec = _cropped_spec(self._full, rect)
+
+    def _set_out_tab(self, out_surface, h: int, w: int) -> None:
+        self._out_hw = _out_hw(h, w, self._rect, self.bars, self.scale)
+        self._out_tab = surface_table(out_surface, self._full.out, self._out_hw, "out_surface")
+
+    def _emit(self, res: torch.Tensor) -> torch.Tensor:
+        """What push() and finish() return: the frames as they are, or packed into out_surface."""
+        if self._out_surface is None:
+            return res
+        return _pack_surface_device(res, self._out_tab, self._full.out, self._out_hw)
 
     @property
     def pulldown_info(self) -> Optional[dict]:
@@ -275,12 +325,17 @@ class VideoUpscaler:
     def push(self, frames: torch.Tensor) -> torch.Tensor:
         if self._finished:
             raise RuntimeError("push() after finish()")
+        if self._in_tab is not None:               # a chunk in a surface: checked against it, copied up and unpacked; planar from here on
+            surface_layout(frames, self._in_tab)
+            frames = _unpack_surface_device(_to_device(frames, _net_device(self.net)), self._in_tab, self._full.inp, self._full.size)
         new = self._admit(frames)
+        if self._out_surface is not None and self._out_tab is None:
+            self._set_out_tab(self._out_surface, *self._shape[1:])
         if self._split is not None:                # interlaced / telecined chunks: the progressive frames that are final go on as a chunk of their own
             new = self._split.push(new)
             if int(new.shape[0]) == 0:             # (a first push of one frame, or a cycle not complete yet: nothing is final)
-                return self._empty()
-        return self._take(new)
+                return self._emit(self._empty())
+        return self._emit(self._take(new))
 
     def _take(self, new: torch.Tensor) -> torch.Tensor:
         """Admitted frames on the device (a chunk, or what the stage made of chunks): cropped, buffered, and the windows now complete run."""
@@ -336,8 +391,8 @@ class VideoUpscaler:
         last = None if self._split is None else self._split.finish()          # the held source frame's two fields, then the end as ever
         if last is not None:
             head = self._take(last)
-            return torch.cat([head, self._finish()], 0)
-        return self._finish()
+            return self._emit(torch.cat([head, self._finish()], 0))
+        return self._emit(self._finish())
 
     def _finish(self) -> torch.Tensor:
         if self.seen == 0:
