@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 45
+#define SAVSR_ABI_VERSION 46
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -715,6 +715,29 @@ int savsr_video_unpack_surface(const uint8_t* surface, int n_frames, int64_t sur
 int savsr_video_pack_surface(const uint8_t* planar, int n_frames, int64_t planar_frame_bytes, int h, int w, int depth, int chroma, int msb,
                              const int64_t* planes, int n_planes, uint8_t* surface, int64_t surface_frame_bytes, int64_t surface_bytes,
                              void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 46) Scan detection (scan.hip; savsr_amd.field_stats, savsr_amd.detect_scan, savsr_amd.ScanStats, upscale_video(scan="detect"),
+ * --scan detect of python -m savsr_amd.upscale): the field statistics that tell progressive, interlaced and
+ * telecined video apart (savsr_amd/scan.py `field_stats` restates them; the kernels equal it bit for bit; the decision is host work on
+ * these sums, savsr_amd/scan.py `verdict_from_stats`).  Matrices are addressed as for savsr_video_field_scores_*: matrix k of the
+ * n_frames resident frames starts at frames + k * frame_bytes + plane_offset, its rows follow each other directly.  The entries only
+ * enqueue on `stream` (one hipMemsetAsync of `out`, then one launch for up to 65535 frames) and allocate nothing; arguments are checked
+ * before the device is touched (SAVSR_E_ARG + savsr_last_error()): a null pointer, no frames, rows or samples, a plane above 2147418112
+ * bytes, a range outside 0 <= lo <= hi <= n_frames, a negative offset, a frame stride smaller than the offset plus the plane, an `out`
+ * that is not 8-byte aligned; _u16: a depth other than 10 / 12, an odd pointer, stride or offset.  16-byte accesses when the plane
+ * pointers, the frame strides and a row's bytes are multiples of 16, a sample per access otherwise (any pointer, stride and size).
+ * savsr_video_field_stats_u8:  out[8 (n - lo) + 2 k + q], n in [lo, hi), q the parity of the rows summed over.  k = 0, 1, 2: the sum over
+ *                           the rows y of parity q, 1 <= y <= rows - 2, and all x of |a - b| + |c - b| - |a - c|, a / c = frame n at
+ *                           rows y - 1 / y + 1, b = row y of frame max(n - 1, 0) (k = 0), of frame min(n + 1, n_frames - 1) (k = 1) or of
+ *                           frame n (k = 2).  k = 3: the sum over all rows y of parity q and all x of |frame n - frame max(n - 1, 0)|.
+ *                           The neighbours are taken among the resident frames and clamped there: a streaming caller passes one frame
+ *                           of context on either side and the range.
+ * savsr_video_field_stats_u16: the same on rows x cols little-endian 16-bit samples, each read as min(s, 2^depth - 1) >> (depth - 8). */
+int savsr_video_field_stats_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes, int lo,
+                               int hi, int64_t* out, void* stream);
+int savsr_video_field_stats_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int depth,
+                                int lo, int hi, int64_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 33) Geometric self-ensemble (ensemble.hip; SAVSR.set_self_ensemble).  Variant k = 0 .. 7: fw = k & 1 flips

@@ -281,7 +281,8 @@ class SAVSR(nn.Module):
                       size=None, cuts=None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None, depth: int = 8,
                       out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
                       chroma_filter: Optional[str] = None, crop=None, crop_limit=24, bars: str = "keep", fields: Optional[str] = None,
-                      pulldown: Optional[str] = None, pulldown_cycle: int = 5, *, surface=None, out_surface=None) -> torch.Tensor:
+                      pulldown: Optional[str] = None, pulldown_cycle: int = 5, *, surface=None, out_surface=None,
+                      scan: Optional[str] = None) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -351,12 +352,21 @@ class SAVSR(nn.Module):
         pixel_format, size, depth), and its result savsr_amd.pack_surface(result, out_surface, out, (H, W), out_depth), in which every byte
         no sample maps to is 0.  surface goes with a planar pixel_format ("i420", "i422", "i444", "y400"), out_surface with a planar out;
         pixel_format="nv12" stays an unknown format.  None (the default) runs what ran before.
+        scan (keyword only): None or "detect", for video whose scan the caller does not know (a decoder's tensors carry no tag, and tags
+        are often wrong).  "detect" runs savsr_amd.detect_scan on the unpacked frames on the GPU, right after surface= unpacking and in
+        front of everything else (one more kernel launch and one host synchronisation), and continues exactly as if the verdict's
+        kwargs() had been given: the result is, bit for bit, upscale_video(frames, **savsr_amd.detect_scan(frames, ...).kwargs(), ...)
+        with every other argument the same -- fields=order for interlaced video, pulldown=order for telecined film, neither for
+        progressive video and for video that shows no evidence (static, flat) -- so the length check and the cuts see the frame count the
+        verdict implies.  Not together with fields, pulldown or a pulldown_cycle other than 5; uint8 and planar frames only.  The
+        detector's rule and thresholds are this project's own and are not validated on real footage; one verdict per video
+        (savsr_amd/scan.py has the limits).  None (the default) runs what ran before.
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
         return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold, colour, out_colour, depth, out_depth,
                              siting, out_siting, chroma_filter, crop, crop_limit, bars, fields, pulldown, pulldown_cycle, surface=surface,
-                             out_surface=out_surface)
+                             out_surface=out_surface, scan=scan)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

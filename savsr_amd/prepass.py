@@ -1,9 +1,9 @@
 """Everything that runs on the device in front of the network: the scene detector's scores, the active-picture detector with crop and
-re-insertion, the deinterlacer and the pulldown removal -- and, at the very boundary, the surface conversion (`unpack_surface` in front of
+re-insertion, the deinterlacer, the pulldown removal and the scan detector that chooses between the two -- and, at the very boundary, the surface conversion (`unpack_surface` in front of
 all of them, `pack_surface` behind everything; savsr_amd/surface.py is its specification).  Each is a public call on any frames and a
 `_..._device` form on resident frames of a checked input side (what upscale_video calls on the whole video); the two that change the frame count are streaming stages as well
-(`FieldSplitter`, `PulldownRemover`; `make_stage` builds the one a call asks for).  The numpy modules (scenes.py, active.py,
-deinterlace.py, pulldown.py) are the specifications, bit for bit.  Where the byte matrices of a frame lie is `frames.plane_table`'s
+(`FieldSplitter`, `PulldownRemover`; `make_stage` builds the one a call asks for; `ScanStats` is the detector's streaming form).  The
+numpy modules (scenes.py, active.py, deinterlace.py, pulldown.py, scan.py) are the specifications, bit for bit.  Where the byte matrices of a frame lie is `frames.plane_table`'s
 answer alone; fp32 CHW frames have entries of their own (`_f32`) and are one explicit branch in the two stages that accept them.
 """
 from __future__ import annotations
@@ -15,6 +15,7 @@ import torch
 
 from . import active
 from . import pulldown as pd
+from . import scan as sc
 from .deinterlace import FIELD_ORDERS, check_frame_rows, check_order
 from .frames import SAMPLE_FORMATS, Side, VideoSpec, check_sample_alignment, detector_layout, detector_side, plane_table
 from .scenes import check_threshold, cuts_from_sad, sad_samples
@@ -580,6 +581,121 @@ class PulldownRemover:
         self._base += int(pend.shape[0])
         self._pend_sad = []
         return pend
+
+
+# ---- scan detection (savsr_amd/scan.py is the specification) -----------------------------------------------------------------------------------
+def _field_stats_device(frames: torch.Tensor, side: Side, size: Size, lo: int = 0, hi: Optional[int] = None) -> torch.Tensor:
+    """savsr_video_field_stats_* on resident frames of the input side on the GPU: int64 [hi - lo, 8] there for source frames [lo, hi)
+    (default: all), the previous and the next frame taken among the resident ones and clamped there; one memset and one launch on the
+    current stream (no sync).  Every byte of packed frames, the Y plane of planar ones."""
+    from . import _lib
+    n, c, h, w = _field_frames(frames, side, size)
+    frames, hi, tab = frames.contiguous(), n if hi is None else hi, plane_table(side, size, c, h, w)
+    lib = _lib.load()
+    with torch.cuda.device(frames.device):
+        out = torch.empty(max(hi - lo, 0), sc.STAT_COLUMNS, dtype=torch.int64, device=frames.device)
+        if hi <= lo:
+            return out
+        st = torch.cuda.current_stream().cuda_stream
+        y = tab.planes[0]
+        if tab.sample == 1:
+            _lib.check(lib.savsr_video_field_stats_u8(frames.data_ptr(), n, tab.stride, y.offset, y.rows, y.row_bytes, lo, hi, out.data_ptr(), st),
+                       "savsr_video_field_stats_u8")
+        else:
+            _lib.check(lib.savsr_video_field_stats_u16(frames.data_ptr(), n, tab.stride, y.offset, y.rows, y.row_bytes // 2, side.depth, lo, hi,
+                                                       out.data_ptr(), st), "savsr_video_field_stats_u16")
+    return out
+
+
+def field_stats(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8) -> torch.Tensor:
+    """The scan detector's statistics: int64 [N, 8] on the GPU (savsr_amd.scan.frame_stats is the specification, bit for bit), on the
+    caller's current stream, without a sync.  Row n: the comb measure of frame n with the rows of parity q taken from the previous frame
+    (columns 0, 1 for q = 0, 1), from the next frame (2, 3) and from itself (4, 5), the neighbours clamped at the ends of the video, and
+    the SAD of field q against the previous frame's (6, 7).  frames as for `field_scores`: [N, h, w, c] uint8 (every byte), or planar
+    frames with pixel_format=, size=(h, w) (the Y plane; at depth 10 / 12 a sample's 8 most significant bits).  Float frames and frames
+    of one row are refused."""
+    frames, side, size = _stage_args(frames, pixel_format, size, depth, _field_frames)
+    return _field_stats_device(frames, side, size)
+
+
+def _detect_scan_device(frames: torch.Tensor, side: Side, size: Size, interlace_threshold=sc.DEFAULT_INTERLACE,
+                        progressive_threshold=sc.DEFAULT_PROGRESSIVE, repeat_threshold=sc.DEFAULT_REPEAT) -> "sc.ScanVerdict":
+    """scan.verdict_from_stats on `_field_stats_device` of frames of the input side on the GPU: one device -> host copy of 8 N integers."""
+    n = _field_frames(frames, side, size)[0]
+    stats = _field_stats_device(frames, side, size).cpu().numpy() if n else torch.zeros(0, sc.STAT_COLUMNS, dtype=torch.int64).numpy()
+    return sc.verdict_from_stats(stats, interlace_threshold, progressive_threshold, repeat_threshold)
+
+
+def detect_scan(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8, interlace_threshold=sc.DEFAULT_INTERLACE,
+                progressive_threshold=sc.DEFAULT_PROGRESSIVE, repeat_threshold=sc.DEFAULT_REPEAT) -> "sc.ScanVerdict":
+    """What kind of scan a video has, from its content: a savsr_amd.scan.ScanVerdict with scan = "progressive", "interlaced", "telecine"
+    or "undetermined" and order = "tff" / "bff" / None; `verdict.kwargs()` is the explicit argument of upscale_video / VideoUpscaler
+    that says the same ({"fields": order}, {"pulldown": order} or {}).  `field_stats` on the GPU, one host synchronisation, then
+    savsr_amd.scan.verdict_from_stats in exact arithmetic: the 3:2 cadence of repeated fields first, then whether a frame's two fields
+    fit each other better than the neighbouring frames' (progressive), then which field order makes the temporal neighbours fit
+    (interlaced).  Static or flat video is undetermined.  The rule and its thresholds are this project's own (ffmpeg idet is the idea)
+    and are not validated on real footage; one verdict per video: mixed content, 2:2 PAL film, cadences other than 3:2 and fades are
+    not handled.  frames as for `field_stats`."""
+    sc.check_thresholds(interlace_threshold, progressive_threshold, repeat_threshold)
+    frames, side, size = _stage_args(frames, pixel_format, size, depth, _field_frames)
+    return _detect_scan_device(frames, side, size, interlace_threshold, progressive_threshold, repeat_threshold)
+
+
+class ScanStats:
+    """The streaming form of `field_stats`, beside FieldSplitter: push(source frames on the GPU) returns the rows that are final (int64
+    [k, 8] on the GPU), finish() the last frame's row (None without a pushed frame).  A frame's row needs the frame after it, so the
+    last pushed frame is held back; with the frame before it (the context) the device keeps at most two source frames between pushes
+    (copies of their own, so that the chunk they came with is released).  Concatenated, the rows are `field_stats` on the whole video
+    for any chunking.  stats: the function of (frames, side, size, lo, hi) that computes rows (the kernel's wrapper)."""
+
+    def __init__(self, side: Side, size: Size, stats=None):
+        self.side, self.size = side, size
+        self._stats = _field_stats_device if stats is None else stats
+        self._src: Optional[torch.Tensor] = None          # source frames [seen - len, seen): the context frame, then the ones without a row
+        self._todo = 0                                    # how many of them have no row yet (they are the last ones)
+        self.seen = 0
+
+    @property
+    def held(self) -> int:
+        """Source frames on the device between pushes: at most two."""
+        return 0 if self._src is None else int(self._src.shape[0])
+
+    def push(self, frames: torch.Tensor) -> torch.Tensor:
+        k = int(frames.shape[0])
+        src = frames.contiguous() if self._src is None else torch.cat([self._src, frames], 0)
+        n = int(src.shape[0])
+        self.seen += k
+        lo, hi = n - self._todo - k, n - 1                # all but the last frame, whose next is not known yet
+        res = self._stats(src, self.side, self.size, lo, max(hi, lo))
+        if hi > lo:
+            self._src, self._todo = src[max(hi - 1, 0):].clone(), 1          # (a copy of two frames: the chunk's storage is released)
+        else:
+            self._src, self._todo = src.clone(), self._todo + k
+        return res
+
+    def finish(self) -> Optional[torch.Tensor]:
+        src, self._src = self._src, None
+        if src is None or self._todo == 0:          # nothing was pushed (or finish() ran before)
+            return None
+        n = int(src.shape[0])
+        todo, self._todo = self._todo, 0
+        return self._stats(src, self.side, self.size, n - todo, n)
+
+
+def _check_scan(scan, fields, pulldown, pulldown_cycle, auto_ok: bool = True) -> Optional[str]:
+    """scan is None or "detect"; "detect" excludes fields=, pulldown= and a pulldown_cycle other than 5."""
+    if sc.check_scan(scan) is None:
+        return None
+    if not auto_ok:
+        raise ValueError("scan = 'detect' in VideoUpscaler: the decision needs the video; run savsr_amd.detect_scan on a probe chunk "
+                         "first and give its answer as fields= or pulldown= (verdict.kwargs()), or use python -m savsr_amd.upscale --scan detect")
+    if fields is not None or pulldown is not None:
+        given = f"fields = {fields!r}" if fields is not None else f"pulldown = {pulldown!r}"
+        raise ValueError(f"scan = 'detect' together with {given}: the detector answers the question that argument answers; give one of them")
+    if isinstance(pulldown_cycle, bool) or pulldown_cycle != pd.DEFAULT_CYCLE:
+        raise ValueError(f"scan = 'detect' with pulldown_cycle = {pulldown_cycle!r}: the detector knows the 3:2 cadence only (cycle "
+                         f"{pd.DEFAULT_CYCLE}); give pulldown= with that cycle")
+    return scan
 
 
 def make_stage(fields, pulldown, pulldown_cycle, side: Side, size: Size):

@@ -12,6 +12,7 @@
     python -m savsr_amd.upscale -i in.y4m -o out.y4m --scale 4 --opt <luma_test.yml> --chroma-filter bicubic
     ffmpeg -i pal_dv.avi -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out50p.y4m --scale 4 --checkpoint <net.pth> --fields auto
     python -m savsr_amd.upscale -i letterboxed_sd.y4m -o hd.y4m --scale 4 --checkpoint <net.pth> --crop auto --colour auto --out-colour auto
+    python -m savsr_amd.upscale -i dvd_rip.y4m -o out.y4m --scale 4 --checkpoint <net.pth> --scan detect --scan-out scan.json
     ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out444p10.y4m --scale 4 --checkpoint <net.pth> --out-chroma 444
 
 PNG folder: frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on
@@ -83,6 +84,18 @@ output is tagged Ip at (cycle - 1) / cycle of the frame rate (30000:1001 -> 2400
 (%08d.png).  Not together with --fields tff / bff / auto: they are two answers to one question.  There is no cadence tracking: a cadence
 broken by an edit costs one real frame in that cycle, and a frame that matches neither neighbour stays combed.
 
+--scan detect: footage whose scan is not known, or whose tag is not trusted (encoders tag hard-telecined film and much progressive
+material It; a PNG folder has no tag at all).  A first pass over a .y4m file or a PNG folder in --chunk-sized pieces computes the field
+statistics on the GPU (savsr_amd/scan.py: comb measures of every frame's fields against its own and its neighbours' fields, and the SAD
+of each field against the previous frame's), the host decides -- the 3:2 cadence of repeated fields first, then whether a frame's two
+fields fit each other better than its neighbours' (progressive), then which field order fits (interlaced) -- and one line on stderr
+names the verdict and the equivalent flag, e.g. "--scan detect: telecine, bottom field first: --pulldown bff".  The run then goes on as
+--fields X / --pulldown X would (or as without them for progressive video and for video that shows no evidence: static, flat); when the
+input's I tag says something else, one more line says so.  --scan-out FILE writes the verdict as JSON (scan, order, totals, hits, the
+per-frame repeated field).  Not on stdin (there is no second pass: give --fields or --pulldown there) and not together with --fields or
+--pulldown.  The rule and its thresholds are this project's own and are not validated on real footage; one verdict per video: mixed
+content, 2:2 PAL film, cadences other than 3:2 and fades are not handled.
+
 It ends with one line: frames, seconds, frames/s (on stderr when the video goes to stdout); with --cuts, the scene count as well; with
 --colour / --out-colour, the two colour spaces.
 """
@@ -99,6 +112,7 @@ from typing import List, Optional
 
 from .deinterlace import FIELD_FLAGS, FIELD_ORDERS, resolve_fields
 from .pulldown import DEFAULT_CYCLE, PULLDOWN_FLAGS, check_cycle, resolve_pulldown
+from .scan import SCAN_FLAGS
 from .yuv import COLOURS, SITINGS
 
 MAX_WRITERS = 16
@@ -217,6 +231,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "order; auto: from the Y4M input's I tag (It, Ib; Im is refused); none (default): frames go through as they are")
     p.add_argument("--pulldown-cycle", type=int, default=None, metavar="N",
                    help="--pulldown: one frame in every N is the repeated one and is dropped (default 5; 2 .. 25)")
+    p.add_argument("--scan", default=None, choices=list(SCAN_FLAGS),
+                   help="detect: find out from the content, in a first pass over the input (a file or a folder), whether it is progressive, "
+                        "interlaced or telecined film and with which field order, then run as --fields X / --pulldown X would; the verdict "
+                        "goes to stderr (thresholds not validated on real footage)")
+    p.add_argument("--scan-out", default=None, metavar="FILE", help="--scan detect: write the verdict as JSON")
     p.add_argument("--bars", default=None, choices=["keep", "drop"],
                    help="--crop: keep = full-size output, the picture in nominal black (default); drop = the picture alone")
     return p
@@ -294,6 +313,15 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     elif a.crop_limit is not None or a.bars is not None:
         p.error("--crop-limit and --bars go with --crop")
     a.crop_limit = 24 if a.crop_limit is None else a.crop_limit
+    if a.scan is not None:
+        if a.input == "-":
+            p.error("--scan detect needs a first pass over the input, which stdin does not allow: give --fields tff / bff / progressive or "
+                    "--pulldown tff / bff (savsr_amd.detect_scan on a probe chunk finds them)")
+        if a.fields is not None or a.pulldown is not None:
+            given = f"--fields {a.fields}" if a.fields is not None else f"--pulldown {a.pulldown}"
+            p.error(f"--scan detect together with {given}: the detector answers the question that flag answers; give one of them")
+    elif a.scan_out is not None:
+        p.error("--scan-out goes with --scan detect")
     a.bars = a.bars or "keep"
     a.y4m_in, a.y4m_out = is_y4m(a.input), is_y4m(a.output)
     if not a.y4m_in:
@@ -521,6 +549,41 @@ def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, de
     return active.align_rect(active.active_rect(top[:h], top[h:], s_row, s_col, a.crop_limit), layout_of(fmt_in) if size else None)
 
 
+def detect_scan_pass(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev):
+    """--scan detect's first pass: a prepass.ScanStats over the input in --chunk-sized pieces (the field statistics on the GPU, one row per
+    frame brought to the host), then scan.verdict_from_stats.  chunks: the PNG folder's chunk iterator; None: the .y4m file named by
+    --input, read through a reader of its own."""
+    import numpy as np
+    import torch
+
+    from .frames import detector_side
+    from .prepass import ScanStats
+    from .scan import STAT_COLUMNS, verdict_from_stats
+    from .y4m import Y4MReader
+    from .yuv import CHROMAS
+    f = None
+    acc = ScanStats(*detector_side(fmt_in, size, depth))
+    rows = []
+    try:
+        if chunks is None:
+            f = open(a.input, "rb")
+            chunks = (torch.from_numpy(c) for c in Y4MReader(f, high_depth=True, layouts=CHROMAS, mono=True).chunks(a.chunk))
+        with torch.cuda.device(dev):
+            for chunk in chunks:
+                rows.append(acc.push(chunk.to(dev)).cpu().numpy())
+            last = acc.finish()
+            if last is not None:
+                rows.append(last.cpu().numpy())
+    except ValueError as e:          # (frames the detector does not take: one row)
+        raise SystemExit(f"--scan detect: {e}") from None
+    finally:
+        if f is not None:
+            f.close()
+    if not rows:
+        raise SystemExit("the video has no frames")
+    return verdict_from_stats(np.concatenate(rows, 0).reshape(-1, STAT_COLUMNS))
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     a = parse_args(argv)
     paths = None if a.y4m_in else list_frames(a.input)
@@ -539,11 +602,15 @@ def main(argv: Optional[List[str]] = None) -> int:
     n_png = None if paths is None else len(paths) * (2 if a.fields in FIELD_ORDERS else 1)          # (--fields: two frames per file)
     if paths is not None and a.pulldown in FIELD_ORDERS:
         n_png -= n_png // a.pulldown_cycle                        # (--pulldown: one frame of every cycle is dropped)
-    if paths is not None and a.cuts is None:
-        check_length(n_png, net.num_frame, a.padding)             # (before the GPU is touched; a Y4M stream's length: at its end)
-    elif paths is not None and a.cuts != "auto":
-        from .scenes import check_cuts
-        check_cuts(a.cuts, n_png)
+
+    def check_png_count(n):                                       # (a Y4M stream's length: at its end)
+        if a.cuts is None:
+            check_length(n, net.num_frame, a.padding)
+        elif a.cuts != "auto":
+            from .scenes import check_cuts
+            check_cuts(a.cuts, n)
+    if paths is not None and a.scan is None:
+        check_png_count(n_png)                                    # (before the GPU is touched; --scan detect: once the verdict is known)
     fin = fout = None
     try:
         if a.y4m_in:
@@ -579,6 +646,36 @@ def main(argv: Optional[List[str]] = None) -> int:
                 for c0 in range(0, len(paths), a.chunk):
                     yield torch.from_numpy(np.stack([store.host(p) for p in paths[c0:c0 + a.chunk]], 0))
             chunks = png_chunks()
+        fmt_of = dict(FORMAT_OF, **{MONO: LUMA_FORMAT})
+        fmt_in = fmt_of[chroma] if a.y4m_in else "rgb"
+        verdict = None
+        if a.scan is not None:                      # the first pass of --scan detect: the content says what --fields / --pulldown would have said
+            from .scan import tag_note
+            dev = torch.device(a.device)
+            net = net.to(dev)
+            verdict = detect_scan_pass(a, chunks if paths is not None else None, fmt_in, (h, w) if a.y4m_in else None, depth, dev)
+            if paths is not None:
+                chunks = png_chunks()
+            found = verdict.kwargs()
+            a.pulldown = found.get("pulldown")
+            a.fields = found.get("fields", "progressive" if verdict.scan == "progressive" else None)
+            print(f"--scan detect: {verdict.describe()}: {verdict.flag() or 'no --fields, no --pulldown'}", file=sys.stderr, flush=True)
+            note = tag_note(verdict, interlace if a.y4m_in else None)
+            if note is not None:
+                print(note, file=sys.stderr, flush=True)
+            if a.scan_out is not None:
+                import json
+                with open(a.scan_out, "w") as f:
+                    json.dump(verdict.as_json(), f)
+                    f.write("\n")
+            if paths is not None:
+                n_png = len(paths) * (2 if a.fields in FIELD_ORDERS else 1)
+                if a.pulldown in FIELD_ORDERS:
+                    n_png -= n_png // a.pulldown_cycle
+                try:
+                    check_png_count(n_png)
+                except ValueError as e:
+                    raise SystemExit(str(e)) from None
         try:                                        # --pulldown and the input's I tag: the field order, the output's I tag and frame rate
             film, film_tag, film_fps, film_note = resolve_pulldown(a.pulldown, interlace if a.y4m_in else None, fps, a.pulldown_cycle)
         except ValueError as e:
@@ -596,8 +693,6 @@ def main(argv: Optional[List[str]] = None) -> int:
                 print(note, file=sys.stderr, flush=True)
         dev = torch.device(a.device)
         net = net.to(dev)
-        fmt_of = dict(FORMAT_OF, **{MONO: LUMA_FORMAT})
-        fmt_in = fmt_of[chroma] if a.y4m_in else "rgb"
         rect = a.crop
         if rect == "auto":                          # the first pass: line sums chunk by chunk, a running maximum on the device
             rect = detect_crop(a, chunks if paths is not None else None, fmt_in, (h, w) if a.y4m_in else None, depth, dev, order, film)
@@ -675,6 +770,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         scenes += f", siting {siting or 'none'} -> {out_siting or 'none'}"
     if order is not None:
         scenes += f", fields {order}"
+    if verdict is not None:
+        scenes += f", scan {verdict.describe()}"
     if film is not None:
         info = up.pulldown_info
         scenes += (f", pulldown {film}: {len(info['matches'])} frames in, {len(info['kept'])} out, {info['matches'].count(-1)} matched from "

@@ -22,6 +22,10 @@ film frames), on the hand-cropped video (crop="auto" finds the rect on the devic
 frames of nominal black, bars="drop" returns the picture alone; both are strided copies through torch views).  Each argument at None
 runs exactly the lines that ran before it existed.
 
+scan="detect": the call finds out which of the two the video is (savsr_amd/scan.py: `detect_scan` on the unpacked frames on the device,
+right after surface= unpacking and in front of everything else) and continues exactly as if the verdict's `kwargs()` had been given:
+fields=order for interlaced video, pulldown=order for telecined film, nothing for progressive and undetermined video.
+
 surface= / out_surface=: where the samples of planar frames lie in memory on either side (savsr_amd/surface.py: NV12, P010, UYVY, pitched
 planar, ...).  The frames are unpacked right after the host-to-device copy, in front of fields=, pulldown=, crop= and everything else, and
 the result is packed last, after the bars are re-inserted: the call is, bit for bit, the call on `unpack_surface(frames, surface, ...)`,
@@ -41,11 +45,12 @@ from .frames import (OUT_KINDS, PADDING_MODES, PIXEL_FORMATS, SAMPLE_FORMATS, YU
                      check_sitings, chroma_of, frame_layout, i420_layout, layout_of, luma_mode, video_spec)
 from .harness import window_indices
 from .packing import get_hw
-from .prepass import (FieldSplitter, PulldownRemover, _check_crop_args, _check_fields, _check_pulldown, _crop_device,  # noqa: F401  (re-exported)
-                      _cropped_spec, _deinterlace_device, _detect_device, _field_frames, _insert_device, _pair_sad_device,
-                      _pack_surface_device, _remove_pulldown_device, _to_device, _unpack_surface_device, deinterlace, detect_active_area,
-                      detect_cuts, field_scores, line_sums, make_stage, pack_surface, pair_sad, remove_pulldown, surface_layout,
-                      surface_side, surface_table, unpack_surface)
+from .prepass import (FieldSplitter, PulldownRemover, ScanStats, _check_crop_args, _check_fields, _check_pulldown,  # noqa: F401  (re-exported)
+                      _check_scan, _crop_device, _cropped_spec, _deinterlace_device, _detect_device, _detect_scan_device, _field_frames,
+                      _insert_device, _pair_sad_device, _pack_surface_device, _remove_pulldown_device, _to_device, _unpack_surface_device,
+                      deinterlace, detect_active_area, detect_cuts, detect_scan, field_scores, field_stats, line_sums, make_stage,
+                      pack_surface, pair_sad, remove_pulldown, surface_layout, surface_side, surface_table, unpack_surface)
+from .scan import ScanVerdict, check_thresholds  # noqa: F401  (re-exported)
 
 
 def _check_net(net) -> None:
@@ -84,7 +89,7 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
                   out_colour: Optional[str] = None, depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None,
                   out_siting: Optional[str] = None, chroma_filter: Optional[str] = None, crop=None, crop_limit=24,
                   bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None, pulldown_cycle: int = 5, *,
-                  surface=None, out_surface=None) -> torch.Tensor:
+                  surface=None, out_surface=None, scan: Optional[str] = None) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
@@ -100,6 +105,15 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         shaped = frames
     if out_surface is not None:        # (its table: once the crop is checked, or found)
         surface_side(out_surface, spec.out, "out_surface")
+    if _check_scan(scan, fields, pulldown, pulldown_cycle) is not None:          # the content says what fields= / pulldown= would have said
+        _field_frames(shaped, spec.inp, spec.size)
+        _check_crop_args(crop, crop_limit, bars)          # (what does not depend on the verdict speaks before the GPU is touched)
+        check_cuts_arg(cuts)
+        frames = _to_device(frames, _net_device(net))
+        if surface is not None:            # the surface comes first of all: the detector sees planar frames; unpacked once, here
+            frames, surface = _unpack_surface_device(frames, in_tab, spec.inp, spec.size), None
+        found = _detect_scan_device(frames, spec.inp, spec.size).kwargs()
+        fields, pulldown = found.get("fields"), found.get("pulldown")
     if _check_fields(fields) is not None:          # everything below sees the progressive video of 2N frames
         _field_frames(shaped, spec.inp, spec.size)
         n *= 2
@@ -191,15 +205,19 @@ class VideoUpscaler:
 
     surface= / out_surface= (savsr_amd.surface.Surface): as in upscale_video; every pushed chunk is [k, stride] uint8 in `surface` and is
     unpacked as it arrives, every returned chunk is packed into `out_surface` as it leaves.  The conversion is stateless, so any chunking
-    gives the same frames."""
+    gives the same frames.
+
+    scan="detect" is refused: the decision needs the video.  Run savsr_amd.detect_scan on a probe chunk (or prepass.ScanStats over a
+    first pass, as python -m savsr_amd.upscale --scan detect does) and give its answer as fields= / pulldown=."""
 
     def __init__(self, net, scale=None, padding: str = "reflection", out: str = "float", pixel_format: str = "rgb", size=None,
                  cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None,
                  depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
                  chroma_filter: Optional[str] = None, crop=None, bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None,
-                 pulldown_cycle: int = 5, *, surface=None, out_surface=None):
+                 pulldown_cycle: int = 5, *, surface=None, out_surface=None, scan: Optional[str] = None):
         _check_net(net)
         check_padding(padding)
+        _check_scan(scan, fields, pulldown, pulldown_cycle, auto_ok=False)          # (None is the only value that passes: the path as it was)
         check_out(out, net.cfg["num_in_ch"], chroma_filter)          # (speaks before the cuts, video_spec after them: the order of refusals)
         self._plan = None                          # scenes.ScenePlan when cuts are given; None: the path without cuts, as it was
         if cuts is not None:

@@ -1,6 +1,6 @@
-// Host stand-ins for the few HIP and common.hpp names csrc/deinterlace.hip, csrc/pulldown.hip, csrc/surface.hip and csrc/video_samples.hpp
-// use, so that their device functions compile unchanged into a stand-alone host program (tools/check_deinterlace_host.py,
-// check_pulldown_host.py, check_surface_host.py):
+// Host stand-ins for the few HIP and common.hpp names csrc/deinterlace.hip, csrc/pulldown.hip, csrc/surface.hip, csrc/scan.hip and
+// csrc/video_samples.hpp use, so that their device functions compile unchanged into a stand-alone host program
+// (tools/check_deinterlace_host.py, check_pulldown_host.py, check_surface_host.py, check_scan_host.py):
 // a launch runs the kernel body one thread at a time over the grid.  Host only; nothing here is loaded into Python or run on a GPU.
 #pragma once
 #include <algorithm>
