@@ -3,11 +3,13 @@
 //
 //   D[co][px] = sum_k A[co][k] * B[k][px],   k = (tap, input channel)
 //
-// Every fp32 operand v is split as v = hi + lo + O(2^-17 |v|) with hi = bf16(v), lo = bf16(v - hi),
-// and each product is evaluated as hi*hi + hi*lo + lo*hi with fp32 accumulation on
+// Every fp32 operand v is split as v = hi + lo + r with hi = bf16(v), lo = bf16(v - hi) (RNE): |lo| <= 2^-8 |v|,
+// |r| <= 2^-16 |v|, and each product is evaluated as hi*hi + hi*lo + lo*hi with fp32 accumulation on
 // v_mfma_f32_32x32x16_bf16 (3 MFMAs at 16x the fp32-MFMA rate = 5.3x the fp32 matrix peak).
-// The dropped lo*lo term is O(2^-18); measured end-to-end deviation from the fp32 oracle is
-// ~1e-5 max-abs, 1e-5 dB PSNR (DESIGN.md section "Numerics").
+// Per product the worst case is 3 * 2^-16 |x| |w| (the two residuals and the dropped lo*lo term, 2^-16 each); 2^-17 is the
+// TYPICAL size.  Per output the error is bounded by 3 * 2^-16 S, S = sum |x| |w| of that output, plus fp32 accumulation;
+// measured per output over inputs spanning six decades: <= 2.2 * 2^-17 S (tests/test_gpu_conv_range.py, DESIGN.md section
+// "Numerics"); end-to-end deviation from the fp32 oracle ~1e-5 max-abs, 1e-5 dB PSNR.
 //
 // Layout.  Activations: [h][w][C] fp32 ("channel-last"): the 8 consecutive k an MFMA lane needs
 // are 8 consecutive channels of one pixel, and the 4 consecutive output rows a lane holds per

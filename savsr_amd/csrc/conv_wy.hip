@@ -23,9 +23,12 @@
 // energy, and fewer of them buy clock (1.68 -> 1.80 GHz) on top of cycles (7.85 k -> 7.0 k per phase); fewer LDS fragment bytes at
 // equal MFMAs bought nothing (same skeleton file, "B reuse").
 //
-// Numerics: the same split products and fp32 accumulation as the direct kernel; the transforms add one fp32 rounding on the
-// activations (d0 - d2 ...) and the cancellation of the output transform: measured max-abs error 1.3-1.6 x the direct kernel's
-// (tests/test_gpu_kernels.py::test_conv2d_winograd_y), inside the same per-kernel bound.
+// Numerics: the same split products (worst case 3 * 2^-16 per product, conv_mfma.hip) and fp32 accumulation as the direct kernel,
+// so per output the error is bounded relative to S_wy = |A^T| applied to sum |U| |V|, NOT to the direct form's S = sum |x| |w|: the
+// transforms add one fp32 rounding on the activations (d0 - d2 ...) and the cancellation of the output transform.  On Gaussian inputs
+// S_wy / S <= 3 and the max-abs error is 1.3-1.6 x the direct kernel's (tests/test_gpu_kernels.py::test_conv2d_winograd_y); on sparse or
+// heavy-tailed activations the error relative to S is tens of 2^-17, and hundreds to thousands at outputs whose dominant tap reads
+// zeros or the zero padding (S_wy / S above 1000) -- tests/test_gpu_conv_range.py, table in DESIGN.md section 3.
 //
 // Replaces (when selected by the engine): the static-weight 3x3 convs of savsr_arch.py:388-397,429-442,480-483,541-543,567,723,733.
 #include "conv_common.hpp"
