@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 46
+#define SAVSR_ABI_VERSION 47
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -738,6 +738,36 @@ int savsr_video_field_stats_u8(const uint8_t* frames, int n_frames, int64_t fram
                                int hi, int64_t* out, void* stream);
 int savsr_video_field_stats_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int depth,
                                 int lo, int hi, int64_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 47) Ordered dither in the quantisers behind the network (video.hip, yuv.hip, luma.hip with csrc/dither.hpp; dither= of
+ * SAVSR.upscale_video and VideoUpscaler, --dither of python -m savsr_amd.upscale).  The three entries below take the
+ * arguments of savsr_video_quantize_u8 / _quantize_yuvs / _quantize_luma with dither = one of SAVSR_DITHER_* in front of `out`; the
+ * entries without _d stay as they are.  NONE runs the kernels of the entry without _d and gives its bytes.  ORDERED: where that entry
+ * computes rintf(t), t the float32 value in output code units, the sample is floorf(t + theta(y, x)) with
+ *   B[y][x] = sum over b = 0 .. 3 of 4^(3 - b) (2 (((x ^ y) >> b) & 1) + ((y >> b) & 1))      the 16 x 16 Bayer index matrix, 0 .. 255 once each
+ *   theta(y, x) = (B[y & 15][x & 15] + 0.5) / 256                                              exact in float32, inside (0, 1)
+ * and (y, x) the sample's coordinates in its own plane: pixel coordinates for Y and packed RGB (the channels of a pixel share one
+ * threshold), chroma-sample coordinates (cy, cx) for Cb / Cr.  The sum is one float32 addition (round to nearest even), not contracted
+ * with the multiply in front of it; floorf follows, then the clip that follows rintf (0 .. 255 in the full-range colour spaces, none in
+ * limited range, which stays in 16 k .. 235 k / 240 k by itself).  The clamp in front makes a NaN 0 as before.  The pattern does not
+ * depend on the frame, so any split of a video into calls gives the same bytes; an integer t is written as it is; a constant
+ * t = i + j / 256 gives every aligned 16 x 16 block the sum 256 i + j.  savsr_amd/dither.py restates the rule and yuv.py
+ * (`rgb_to_i420`, `unit_to_luma` with dither=) and dither.py (`rgb_to_u8`) the three entries, bit for bit.  Refused with SAVSR_E_ARG +
+ * savsr_last_error() before the device is touched: a dither other than 0 or 1, and everything the entry without _d refuses (under
+ * this entry's name).  Vector / scalar forms and alignment rules are those of the entries without _d; they only enqueue, allocate
+ * nothing and are capturable.
+ * savsr_video_quantize_u8_d:   the packed quantiser: t = clamp(v, 0, 1) * 255 at pixel (p / W, p % W).
+ * savsr_video_quantize_yuvs_d: every layout, depth, colour space and siting of savsr_video_quantize_yuvs: t = the row's float32 value
+ *                           times k = 2^(depth - 8), Y at its pixel, Cb and Cr at their chroma sample (one threshold for the two).
+ * savsr_video_quantize_luma_d: the luma-only path's Y plane: t = clamp(v, 0, 1) * (255 * 2^(depth - 8)).  The Cb / Cr planes of that path
+ *                           are resampled samples (savsr_video_resample_chroma) and keep rintf. */
+#define SAVSR_DITHER_NONE 0
+#define SAVSR_DITHER_ORDERED 1
+int savsr_video_quantize_u8_d(const float* in, int n, int c, int H, int W, int dither, uint8_t* out, void* stream);
+int savsr_video_quantize_yuvs_d(const float* in, int n, int H, int W, int colour, int depth, int chroma, int siting, int dither, uint8_t* out,
+                                void* stream);
+int savsr_video_quantize_luma_d(const float* in, int n, int H, int W, int depth, int dither, uint8_t* out, int64_t out_frame_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 33) Geometric self-ensemble (ensemble.hip; SAVSR.set_self_ensemble).  Variant k = 0 .. 7: fw = k & 1 flips

@@ -18,7 +18,7 @@ MAX_SRC = 5
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID = 0, 1, 2, 3
 SATU_LRCAT = 160
 SATU_TABLE = 8
-ABI_VERSION = 46
+ABI_VERSION = 47
 CONV_DIRECT, CONV_DIRECT_THROUGHPUT, CONV_WINOGRAD_Y, CONV_WINOGRAD_Y_THROUGHPUT = 0, 2, 3, 4
 CONV_WY_FORMS = (CONV_WINOGRAD_Y, CONV_WINOGRAD_Y_THROUGHPUT)
 SATU_LRCAT_TAIL = 96
@@ -190,6 +190,9 @@ SIGNATURES = {
                                              C.c_int64, C.c_void_p]),
     "savsr_video_pack_surface": (C.c_int, [fptr, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, fptr,
                                            C.c_int64, C.c_int64, C.c_void_p]),
+    "savsr_video_quantize_u8_d": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr, C.c_void_p]),
+    "savsr_video_quantize_yuvs_d": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr, C.c_void_p]),
+    "savsr_video_quantize_luma_d": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr, C.c_int64, C.c_void_p]),
     "savsr_ensemble_gather_u8": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, fptr, C.c_void_p]),
     "savsr_ensemble_gather_f32": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, fptr, C.c_void_p]),
     "savsr_ensemble_merge": (C.c_int, [fptr, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, fptr, C.c_void_p]),

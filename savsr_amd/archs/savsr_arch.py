@@ -282,7 +282,7 @@ class SAVSR(nn.Module):
                       out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
                       chroma_filter: Optional[str] = None, crop=None, crop_limit=24, bars: str = "keep", fields: Optional[str] = None,
                       pulldown: Optional[str] = None, pulldown_cycle: int = 5, *, surface=None, out_surface=None,
-                      scan: Optional[str] = None) -> torch.Tensor:
+                      scan: Optional[str] = None, dither: Optional[str] = None) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -361,12 +361,23 @@ class SAVSR(nn.Module):
         verdict implies.  Not together with fields, pulldown or a pulldown_cycle other than 5; uint8 and planar frames only.  The
         detector's rule and thresholds are this project's own and are not validated on real footage; one verdict per video
         (savsr_amd/scan.py has the limits).  None (the default) runs what ran before.
+        dither (keyword only): None or one of savsr_amd.dither.DITHERS ("ordered"), for the integer outputs (out="uint8", "i420" / "i422" /
+        "i444" at any depth, "y400" and the Y plane of the luma-only path).  None rounds the fp32 result to the nearest code, as ever.
+        "ordered" writes floor(t + theta(y, x)) instead, t the value in output code units and theta a threshold in (0, 1) from a 16 x 16
+        Bayer matrix at the sample's position in its own plane (Cb / Cr at their chroma-sample coordinates; the channels of a packed pixel
+        share one threshold, so the dither is grey): a smooth gradient, which a x4 result stretches over four times as many pixels,
+        keeps its mean over every 16 x 16 block to 1/256 of a code instead of turning into bands.  savsr_amd/dither.py is the
+        specification and the kernels equal it bit for bit: the result is that module's rule applied to the out="float" result.  Exact
+        codes pass unchanged, limited range stays in range without a clip, and the pattern is static in time, so any chunking gives the
+        same bytes.  One pattern (no blue noise, no error diffusion); the luma-only path's resampled Cb / Cr keep rint; not validated on
+        real footage; the gain is largest at 8 bits.  Refused with out="float" (nothing to quantise).  With the self-ensemble the merge
+        stays fp32 and the dithered quantiser runs after it.
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
         return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold, colour, out_colour, depth, out_depth,
                              siting, out_siting, chroma_filter, crop, crop_limit, bars, fields, pulldown, pulldown_cycle, surface=surface,
-                             out_surface=out_surface, scan=scan)
+                             out_surface=out_surface, scan=scan, dither=dither)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

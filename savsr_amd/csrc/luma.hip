@@ -14,6 +14,7 @@
 //             buffers: the vertical sum takes its taps in ascending row order, so cutting it at buffer boundaries changes no bit.
 #pragma clang fp contract(off)
 #include "common.hpp"
+#include "dither.hpp"
 
 #include <cstdint>
 
@@ -66,23 +67,39 @@ __device__ __forceinline__ uint32_t quant_luma(float x, float mul) {
 }
 
 // fp32 [n][H * W] -> the Y plane of every output frame, `stride` bytes from frame to frame.  A thread quantises 4 samples; VEC: one
-// nontemporal float4 in, one dword or 8-byte store out.
-template <typename S, bool VEC>
+// nontemporal float4 in, one dword or 8-byte store out.  DITHER (savsr_video_quantize_luma_d): floor(t + theta) in rint's place
+// (dither.hpp), theta at the sample's (y, x) = (p / W, p % W) (dither_row_col).  VEC has W % 4 == 0, so its 4 samples lie in one row from
+// a multiple of 4 (dither_theta4); the scalar form's 4 may cross row ends and walk (y, x).  Without DITHER, dv is not read.
+template <typename S, bool VEC, bool DITHER>
 __global__ __launch_bounds__(256) void quantize_luma_kernel(const float* __restrict__ in, long long npx, float mul, uint8_t* __restrict__ out,
-                                                            long long stride) {
+                                                            long long stride, DitherDiv dv) {
     const int k = blockIdx.y;
     const float* src = in + (long long)k * npx;
     S* dst = reinterpret_cast<S*>(out + (long long)k * stride);
     const long long p0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
     if (p0 >= npx) return;
+    uint32_t y = 0u, x0 = 0u;
+    if constexpr (DITHER) dither_row_col(p0, dv, y, x0);
     if (VEC) {
         const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + p0));
         uint32_t q[4];
+        float th[4];
+        if constexpr (DITHER) dither_theta4(y, x0, th);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) q[e] = quant_luma(x[e], mul);
+        for (int e = 0; e < 4; ++e) {
+            if constexpr (DITHER) q[e] = dither_quant_unit(x[e], mul, th[e]);
+            else q[e] = quant_luma(x[e], mul);
+        }
         *reinterpret_cast<typename Vec4<S>::type*>(dst + p0) = pack4<S>(q);
     } else {
-        for (int e = 0; e < 4 && p0 + e < npx; ++e) dst[p0 + e] = (S)quant_luma(__builtin_nontemporal_load(src + p0 + e), mul);
+        for (int e = 0; e < 4 && p0 + e < npx; ++e) {
+            if constexpr (DITHER) {
+                dst[p0 + e] = (S)dither_quant_unit(__builtin_nontemporal_load(src + p0 + e), mul, dither_theta(y, x0));
+                if (++x0 == dv.w) { x0 = 0u; ++y; }
+            } else {
+                dst[p0 + e] = (S)quant_luma(__builtin_nontemporal_load(src + p0 + e), mul);
+            }
+        }
     }
 }
 
@@ -219,25 +236,48 @@ extern "C" int savsr_video_gather_luma(const uint8_t* frames, int n_frames, int6
     return check_launch("gather_luma_kernel");
 }
 
-extern "C" int savsr_video_quantize_luma(const float* in, int n, int H, int W, int depth, uint8_t* out, int64_t out_frame_bytes, void* stream) {
-    if (!in || !out) return fail_arg("video_quantize_luma: null pointer");
-    if (n < 1 || n > 65535 || H < 1 || W < 1) return fail_arg("video_quantize_luma: n in 1 .. 65535, H, W >= 1");
-    if (!depth_ok(depth)) return fail_arg("video_quantize_luma: depth is 8, 10 or 12");
+// The body of savsr_video_quantize_luma and savsr_video_quantize_luma_d: `what` names the one called in its messages.
+static int quantize_luma(const char* what, const float* in, int n, int H, int W, int depth, bool dither, uint8_t* out, int64_t out_frame_bytes,
+                         void* stream) {
+    auto refuse = [&](const char* msg) { set_error("invalid argument: %s: %s", what, msg); return SAVSR_E_ARG; };
+    if (!in || !out) return refuse("null pointer");
+    if (n < 1 || n > 65535 || H < 1 || W < 1) return refuse("n in 1 .. 65535, H, W >= 1");
+    if (!depth_ok(depth)) return refuse("depth is 8, 10 or 12");
     const int s = depth == 8 ? 1 : 2;
     const long long npx = (long long)H * W;
-    if (out_frame_bytes < npx * s) return fail_arg("video_quantize_luma: out_frame_bytes is smaller than the Y plane (H * W samples)");
-    if (s == 2 && ((reinterpret_cast<uintptr_t>(out) & 1) || (out_frame_bytes & 1)))
-        return fail_align("video_quantize_luma: 16-bit samples need a 2-byte aligned frame pointer and an even out_frame_bytes");
+    if (out_frame_bytes < npx * s) return refuse("out_frame_bytes is smaller than the Y plane (H * W samples)");
+    if (s == 2 && ((reinterpret_cast<uintptr_t>(out) & 1) || (out_frame_bytes & 1))) {
+        set_error("alignment: %s: 16-bit samples need a 2-byte aligned frame pointer and an even out_frame_bytes", what);
+        return SAVSR_E_ALIGN;
+    }
     const int va = 4 * s;
     const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(out) % va) == 0 && out_frame_bytes % va == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
     const float mul = (float)(255 << (depth - 8));
     const dim3 grid(blocks_for((npx + 3) / 4), n);
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define SAVSR_QUANT_LUMA(S, V) hipLaunchKernelGGL((quantize_luma_kernel<S, V>), grid, dim3(256), 0, st, in, npx, mul, out, (long long)out_frame_bytes)
-    if (s == 1) { if (vec) SAVSR_QUANT_LUMA(uint8_t, true); else SAVSR_QUANT_LUMA(uint8_t, false); }
-    else { if (vec) SAVSR_QUANT_LUMA(uint16_t, true); else SAVSR_QUANT_LUMA(uint16_t, false); }
+    const DitherDiv dv = dither_div(W);
+#define SAVSR_QUANT_LUMA(S, V, D) \
+    hipLaunchKernelGGL((quantize_luma_kernel<S, V, D>), grid, dim3(256), 0, st, in, npx, mul, out, (long long)out_frame_bytes, dv)
+#define SAVSR_QUANT_LUMA_D(S, V) do { if (dither) SAVSR_QUANT_LUMA(S, V, true); else SAVSR_QUANT_LUMA(S, V, false); } while (0)
+    if (s == 1) { if (vec) SAVSR_QUANT_LUMA_D(uint8_t, true); else SAVSR_QUANT_LUMA_D(uint8_t, false); }
+    else { if (vec) SAVSR_QUANT_LUMA_D(uint16_t, true); else SAVSR_QUANT_LUMA_D(uint16_t, false); }
+#undef SAVSR_QUANT_LUMA_D
 #undef SAVSR_QUANT_LUMA
     return check_launch("quantize_luma_kernel");
+}
+
+extern "C" int savsr_video_quantize_luma(const float* in, int n, int H, int W, int depth, uint8_t* out, int64_t out_frame_bytes, void* stream) {
+    return quantize_luma("video_quantize_luma", in, n, H, W, depth, false, out, out_frame_bytes, stream);
+}
+
+// dither 0: the kernels and the bytes of savsr_video_quantize_luma; 1: ordered dither (savsr_amd/dither.py).
+extern "C" int savsr_video_quantize_luma_d(const float* in, int n, int H, int W, int depth, int dither, uint8_t* out, int64_t out_frame_bytes,
+                                           void* stream) {
+    if (dither != SAVSR_DITHER_NONE && dither != SAVSR_DITHER_ORDERED) {
+        set_error("invalid argument: video_quantize_luma_d: dither %d (0 = none, 1 = ordered)", dither);
+        return SAVSR_E_ARG;
+    }
+    return quantize_luma("video_quantize_luma_d", in, n, H, W, depth, dither == SAVSR_DITHER_ORDERED, out, out_frame_bytes, stream);
 }
 
 extern "C" int savsr_video_resample_chroma(const uint8_t* src, int n, int64_t src_frame_bytes, int64_t src_plane_offset, int ch, int cw, int depth_in,

@@ -7,6 +7,7 @@
 //   tensor2img                  lbasicsr/utils/img_util.py:66-90   clamp(0, 1) * 255, round half to even, uint8, CHW -> HWC
 #include "common.hpp"
 #include "video_samples.hpp"
+#include "dither.hpp"
 
 #include <cstdint>
 
@@ -79,9 +80,12 @@ __global__ __launch_bounds__(256) void gather_f32_kernel(const float* __restrict
 }
 
 // fp32 planar [n][C][H][W] -> uint8 HWC [n][H][W][C].  VEC: a thread quantises 16 pixels -- four float4 per plane in, C 16-byte stores
-// out (npx % 16 == 0, 16-byte aligned pointers); otherwise one pixel per thread.
-template <int C, bool VEC>
-__global__ __launch_bounds__(256) void quantize_u8_kernel(const float* __restrict__ in, long long npx, uint8_t* __restrict__ out) {
+// out (npx % 16 == 0, 16-byte aligned pointers); otherwise one pixel per thread.  DITHER (savsr_video_quantize_u8_d): floor(t + theta)
+// in rint's place (dither.hpp), theta at the pixel's (y, x) = (p / W, p % W) and shared by its channels; a vector thread's run of 16
+// pixels crosses row ends whenever W is no multiple of 16, so it splits p once (dither_row_col) and walks (y, x) from there.  Without
+// DITHER, dv is not read.
+template <int C, bool VEC, bool DITHER>
+__global__ __launch_bounds__(256) void quantize_u8_kernel(const float* __restrict__ in, long long npx, uint8_t* __restrict__ out, DitherDiv dv) {
     const int k = blockIdx.y;
     const float* src = in + (long long)k * C * npx;
     uint8_t* dst = out + (long long)k * C * npx;
@@ -89,6 +93,16 @@ __global__ __launch_bounds__(256) void quantize_u8_kernel(const float* __restric
     if (VEC) {
         const long long p0 = g * 16;
         if (p0 >= npx) return;
+        float th[16];
+        if constexpr (DITHER) {
+            uint32_t y, x;
+            dither_row_col(p0, dv, y, x);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                th[i] = dither_theta(y, x);
+                if (++x == dv.w) { x = 0u; ++y; }
+            }
+        }
         uint32_t wv[4 * C];
 #pragma unroll
         for (int j = 0; j < 4 * C; ++j) wv[j] = 0u;
@@ -100,7 +114,8 @@ __global__ __launch_bounds__(256) void quantize_u8_kernel(const float* __restric
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int b = (4 * v4 + e) * C + ch;
-                    wv[b >> 2] |= quant_u8(x[e]) << (8 * (b & 3));
+                    if constexpr (DITHER) wv[b >> 2] |= dither_quant_unit(x[e], 255.0f, th[4 * v4 + e]) << (8 * (b & 3));
+                    else wv[b >> 2] |= quant_u8(x[e]) << (8 * (b & 3));
                 }
             }
         }
@@ -109,8 +124,16 @@ __global__ __launch_bounds__(256) void quantize_u8_kernel(const float* __restric
         for (int j = 0; j < C; ++j) d[j] = make_uint4(wv[4 * j], wv[4 * j + 1], wv[4 * j + 2], wv[4 * j + 3]);
     } else {
         if (g >= npx) return;
+        if constexpr (DITHER) {
+            uint32_t y, x;
+            dither_row_col(g, dv, y, x);
+            const float th = dither_theta(y, x);
 #pragma unroll
-        for (int ch = 0; ch < C; ++ch) dst[g * C + ch] = (uint8_t)quant_u8(src[ch * npx + g]);
+            for (int ch = 0; ch < C; ++ch) dst[g * C + ch] = (uint8_t)dither_quant_unit(src[ch * npx + g], 255.0f, th);
+        } else {
+#pragma unroll
+            for (int ch = 0; ch < C; ++ch) dst[g * C + ch] = (uint8_t)quant_u8(src[ch * npx + g]);
+        }
     }
 }
 
@@ -166,21 +189,41 @@ extern "C" int savsr_video_gather_f32(const float* frames, int n_frames, int c, 
     return check_launch("gather_f32_kernel");
 }
 
-extern "C" int savsr_video_quantize_u8(const float* in, int n, int c, int H, int W, uint8_t* out, void* stream) {
-    if (!in || !out) return fail_arg("video_quantize_u8: null pointer");
-    if (n < 1 || n > 65535 || c < 1 || c > 3 || H < 1 || W < 1) return fail_arg("video_quantize_u8: n in 1 .. 65535, c in 1 .. 3, H, W >= 1");
+// The body of savsr_video_quantize_u8 and savsr_video_quantize_u8_d: `what` names the one called in its messages.
+static int quantize_u8(const char* what, const float* in, int n, int c, int H, int W, bool dither, uint8_t* out, void* stream) {
+    if (!in || !out) { set_error("invalid argument: %s: null pointer", what); return SAVSR_E_ARG; }
+    if (n < 1 || n > 65535 || c < 1 || c > 3 || H < 1 || W < 1) {
+        set_error("invalid argument: %s: n in 1 .. 65535, c in 1 .. 3, H, W >= 1", what);
+        return SAVSR_E_ARG;
+    }
     const long long npx = (long long)H * W;
     const bool vec = npx % 16 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
     const dim3 grid(blocks_for(vec ? npx / 16 : npx), n);
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define SAVSR_QUANT(CC)                                                                                    \
-    if (vec) hipLaunchKernelGGL((quantize_u8_kernel<CC, true>), grid, dim3(256), 0, st, in, npx, out);     \
-    else hipLaunchKernelGGL((quantize_u8_kernel<CC, false>), grid, dim3(256), 0, st, in, npx, out);
+    const DitherDiv dv = dither_div(W);
+#define SAVSR_QUANT_D(CC, D)                                                                                       \
+    if (vec) hipLaunchKernelGGL((quantize_u8_kernel<CC, true, D>), grid, dim3(256), 0, st, in, npx, out, dv);      \
+    else hipLaunchKernelGGL((quantize_u8_kernel<CC, false, D>), grid, dim3(256), 0, st, in, npx, out, dv);
+#define SAVSR_QUANT(CC) if (dither) { SAVSR_QUANT_D(CC, true) } else { SAVSR_QUANT_D(CC, false) }
     switch (c) {
         case 1: SAVSR_QUANT(1) break;
         case 2: SAVSR_QUANT(2) break;
         default: SAVSR_QUANT(3) break;
     }
 #undef SAVSR_QUANT
+#undef SAVSR_QUANT_D
     return check_launch("quantize_u8_kernel");
+}
+
+extern "C" int savsr_video_quantize_u8(const float* in, int n, int c, int H, int W, uint8_t* out, void* stream) {
+    return quantize_u8("video_quantize_u8", in, n, c, H, W, false, out, stream);
+}
+
+// dither 0: the kernels and the bytes of savsr_video_quantize_u8; 1: ordered dither (savsr_amd/dither.py).
+extern "C" int savsr_video_quantize_u8_d(const float* in, int n, int c, int H, int W, int dither, uint8_t* out, void* stream) {
+    if (dither != SAVSR_DITHER_NONE && dither != SAVSR_DITHER_ORDERED) {
+        set_error("invalid argument: video_quantize_u8_d: dither %d (0 = none, 1 = ordered)", dither);
+        return SAVSR_E_ARG;
+    }
+    return quantize_u8("video_quantize_u8_d", in, n, c, H, W, dither == SAVSR_DITHER_ORDERED, out, stream);
 }

@@ -27,6 +27,7 @@
 // savsr_amd/yuv.py restates both kernels in numpy and is what they are tested against, bit for bit: float32, a fixed operation order
 // and no fused multiply-add (contraction is off for this whole file).
 #include "common.hpp"
+#include "dither.hpp"
 
 #include <cstdint>
 #include <type_traits>
@@ -423,30 +424,35 @@ __global__ __launch_bounds__(256) void gather_linear_kernel(const uint8_t* __res
 // rgb2ycbcr's rows in 8-bit steps: every product and every sum rounded to float32 (yuv.py: _row).  Plain operators under this file's
 // `fp contract(off)`: the header's __fmul_rn / __fadd_rn are compiled with contraction allowed and fuse again once inlined.
 // CLIP (full range): the rounded value clipped to 0 .. 255 (yuv.py: rgb_to_i420); limited range stays inside 16 .. 240 by itself.
-template <bool CLIP>
-__device__ __forceinline__ uint32_t row3_u8(const float (&kk)[3], float off, float r, float g, float b) {
-    const float v = rintf(((r * kk[0] + g * kk[1]) + b * kk[2]) + off);
+// DITHER (the entries with _d; dither.hpp, savsr_amd/dither.py): floor(t + th) in rint's place, th the sample's threshold; the clip
+// follows as it follows rint.  Without DITHER th is not read.
+template <bool CLIP, bool DITHER>
+__device__ __forceinline__ uint32_t row3_u8(const float (&kk)[3], float off, float th, float r, float g, float b) {
+    const float t = ((r * kk[0] + g * kk[1]) + b * kk[2]) + off;
+    const float v = DITHER ? dither_add_floor(t, th) : rintf(t);
     return (uint32_t)(CLIP ? fminf(fmaxf(v, 0.f), 255.f) : v);
 }
 // rint(row * k): the 8-bit row's float32 value times k = 2^(d - 8), exact, then half to even.  Limited range stays inside 16 k .. 240 k
 // by itself: no clip.
-__device__ __forceinline__ uint32_t row3_u16(const float (&kk)[3], float off, float k, float r, float g, float b) {
-    return (uint32_t)rintf((((r * kk[0] + g * kk[1]) + b * kk[2]) + off) * k);
+template <bool DITHER>
+__device__ __forceinline__ uint32_t row3_u16(const float (&kk)[3], float off, float k, float th, float r, float g, float b) {
+    const float t = (((r * kk[0] + g * kk[1]) + b * kk[2]) + off) * k;
+    return (uint32_t)(DITHER ? dither_add_floor(t, th) : rintf(t));
 }
 // The policies: the three rows of colour space C, a template argument so that the coefficients are constants of the instantiation
-// (immediates in the code).  k is the kernel's argument; 8 bits has no use for it.
+// (immediates in the code).  k is the kernel's argument; 8 bits has no use for it.  D, th: the kernel's DITHER and the sample's threshold.
 template <int C> struct Quant8 {
     typedef uint8_t Sample;
-    static __device__ __forceinline__ uint32_t y(float, float r, float g, float b) { constexpr YuvMatrix m = kYuv.m[C]; return row3_u8<m.full>(m.ky, m.oy, r, g, b); }
-    static __device__ __forceinline__ uint32_t cb(float, float r, float g, float b) { constexpr YuvMatrix m = kYuv.m[C]; return row3_u8<m.full>(m.kcb, m.oc, r, g, b); }
-    static __device__ __forceinline__ uint32_t cr(float, float r, float g, float b) { constexpr YuvMatrix m = kYuv.m[C]; return row3_u8<m.full>(m.kcr, m.oc, r, g, b); }
+    template <bool D> static __device__ __forceinline__ uint32_t y(float, float th, float r, float g, float b) { constexpr YuvMatrix m = kYuv.m[C]; return row3_u8<m.full, D>(m.ky, m.oy, th, r, g, b); }
+    template <bool D> static __device__ __forceinline__ uint32_t cb(float, float th, float r, float g, float b) { constexpr YuvMatrix m = kYuv.m[C]; return row3_u8<m.full, D>(m.kcb, m.oc, th, r, g, b); }
+    template <bool D> static __device__ __forceinline__ uint32_t cr(float, float th, float r, float g, float b) { constexpr YuvMatrix m = kYuv.m[C]; return row3_u8<m.full, D>(m.kcr, m.oc, th, r, g, b); }
 };
 template <int C> struct Quant16 {
     static_assert(!kYuv.m[C].full, "high depth is defined for limited range only");
     typedef uint16_t Sample;
-    static __device__ __forceinline__ uint32_t y(float k, float r, float g, float b) { constexpr YuvMatrix m = kYuv.m[C]; return row3_u16(m.ky, m.oy, k, r, g, b); }
-    static __device__ __forceinline__ uint32_t cb(float k, float r, float g, float b) { constexpr YuvMatrix m = kYuv.m[C]; return row3_u16(m.kcb, m.oc, k, r, g, b); }
-    static __device__ __forceinline__ uint32_t cr(float k, float r, float g, float b) { constexpr YuvMatrix m = kYuv.m[C]; return row3_u16(m.kcr, m.oc, k, r, g, b); }
+    template <bool D> static __device__ __forceinline__ uint32_t y(float k, float th, float r, float g, float b) { constexpr YuvMatrix m = kYuv.m[C]; return row3_u16<D>(m.ky, m.oy, k, th, r, g, b); }
+    template <bool D> static __device__ __forceinline__ uint32_t cb(float k, float th, float r, float g, float b) { constexpr YuvMatrix m = kYuv.m[C]; return row3_u16<D>(m.kcb, m.oc, k, th, r, g, b); }
+    template <bool D> static __device__ __forceinline__ uint32_t cr(float k, float th, float r, float g, float b) { constexpr YuvMatrix m = kYuv.m[C]; return row3_u16<D>(m.kcr, m.oc, k, th, r, g, b); }
 };
 
 // Mean of one channel over a block's in-image pixels, at(dy, dx) the clamped value (yuv.py: _block_mean): ((a + b) + (c + d)) * 0.25 with
@@ -463,9 +469,12 @@ __device__ __forceinline__ float block_mean(bool two_x, bool two_y, At at) {
 // fp32 planar RGB [n][3][H][W] -> frames [n][fb]: clamp(0, 1); Y per pixel; Cb / Cr from block_mean of the clamped RGB; rintf (round half
 // to even).  VEC: a thread owns SY rows x 4 pixels -- one float4 per plane row in (nontemporal: the result is read once), 4 Y samples per
 // row and the 4 / SX chroma samples under them out in one access per plane; otherwise a chroma sample and its SY x SX in-image pixels, scalar.
-template <int SX, int SY, bool VEC, class Q>
+// DITHER (savsr_video_quantize_yuvs_d): every sample takes floor(t + theta) in rint's place, theta at its coordinates in its own plane --
+// pixel (y, x) for Y, chroma sample (cy, cx) for Cb and Cr, which share it.
+template <int SX, int SY, bool VEC, bool DITHER, class Q>
 __global__ __launch_bounds__(256) void quantize_kernel(const float* __restrict__ in, int H, int W, long long fb, float k, uint8_t* __restrict__ out) {
     typedef typename Q::Sample S;
+    auto th = [](int y, int x) { if constexpr (DITHER) return dither_theta((uint32_t)y, (uint32_t)x); else return 0.f; };
     const int f = blockIdx.y;
     const long long npx = (long long)H * W;
     const int ch = (H + SY - 1) / SY, cw = (W + SX - 1) / SX;
@@ -492,8 +501,10 @@ __global__ __launch_bounds__(256) void quantize_kernel(const float* __restrict__
                 for (int e = 0; e < 4; ++e) px[dy][c][e] = clamp01(x[e]);
             }
             uint32_t yy[4];
+            float ty[4] = {};
+            if constexpr (DITHER) dither_theta4((uint32_t)(SY * cy + dy), (uint32_t)x0, ty);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) yy[e] = Q::y(k, px[dy][0][e], px[dy][1][e], px[dy][2][e]);
+            for (int e = 0; e < 4; ++e) yy[e] = Q::template y<DITHER>(k, ty[e], px[dy][0][e], px[dy][1][e], px[dy][2][e]);
             store_samples(fy + p, yy);
         }
         uint32_t u[NC], v[NC];
@@ -502,8 +513,9 @@ __global__ __launch_bounds__(256) void quantize_kernel(const float* __restrict__
             float m[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) m[c] = block_mean<SX, SY>(true, two_y, [&](int dy, int dx) { return px[dy][c][SX * j + dx]; });
-            u[j] = Q::cb(k, m[0], m[1], m[2]);
-            v[j] = Q::cr(k, m[0], m[1], m[2]);
+            const float tc = th(cy, x0 / SX + j);
+            u[j] = Q::template cb<DITHER>(k, tc, m[0], m[1], m[2]);
+            v[j] = Q::template cr<DITHER>(k, tc, m[0], m[1], m[2]);
         }
         const long long coff = (long long)cy * cw + x0 / SX;
         store_samples(fu + coff, u);
@@ -521,14 +533,15 @@ __global__ __launch_bounds__(256) void quantize_kernel(const float* __restrict__
                 const long long p = (long long)(SY * cy + dy) * W + SX * cx + dx;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) q[dy][dx][c] = clamp01(src[c * npx + p]);
-                fy[p] = (S)Q::y(k, q[dy][dx][0], q[dy][dx][1], q[dy][dx][2]);
+                fy[p] = (S)Q::template y<DITHER>(k, th(SY * cy + dy, SX * cx + dx), q[dy][dx][0], q[dy][dx][1], q[dy][dx][2]);
             }
         }
         float m[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) m[c] = block_mean<SX, SY>(two_x, two_y, [&](int dy, int dx) { return q[dy][dx][c]; });
-        fu[(long long)cy * cw + cx] = (S)Q::cb(k, m[0], m[1], m[2]);
-        fv[(long long)cy * cw + cx] = (S)Q::cr(k, m[0], m[1], m[2]);
+        const float tc = th(cy, cx);
+        fu[(long long)cy * cw + cx] = (S)Q::template cb<DITHER>(k, tc, m[0], m[1], m[2]);
+        fv[(long long)cy * cw + cx] = (S)Q::template cr<DITHER>(k, tc, m[0], m[1], m[2]);
     }
 }
 
@@ -541,11 +554,13 @@ __device__ __forceinline__ float h3(float l, float c, float r) { return ((l + r)
 // Hrow(2 cy) alone on the last row of an odd H; topleft: h3 of Hrow at rows 2 cy - 1, 2 cy, 2 cy + 1, clamped.  Same units and ownership:
 // a thread writes the Y of its SY rows x 4 (VEC) or x 2 pixels and the chroma samples over them, and reads beside its own pixels the one
 // left of them and, for TOP, the row above with plain loads (a neighbour's lines).  A clamped row or column repeats a value the thread
-// already holds, and the same operations on the same values give the same bits, so those are reused and not loaded again.
-template <int SY, bool VEC, bool TOP, class Q>
+// already holds, and the same operations on the same values give the same bits, so those are reused and not loaded again.  DITHER: as in
+// quantize_kernel, the thresholds at the same coordinates.
+template <int SY, bool VEC, bool TOP, bool DITHER, class Q>
 __global__ __launch_bounds__(256) void quantize_cosited_kernel(const float* __restrict__ in, int H, int W, long long fb, float k, uint8_t* __restrict__ out) {
     static_assert(SY == 2 || !TOP, "4:2:2 has no vertical subsampling");
     typedef typename Q::Sample S;
+    auto th = [](int y, int x) { if constexpr (DITHER) return dither_theta((uint32_t)y, (uint32_t)x); else return 0.f; };
     constexpr int SX = 2;
     const int f = blockIdx.y;
     const long long npx = (long long)H * W;
@@ -583,8 +598,10 @@ __global__ __launch_bounds__(256) void quantize_cosited_kernel(const float* __re
                 for (int e = 0; e < 4; ++e) px[c][e] = clamp01(x[e]);
             }
             uint32_t yy[4];
+            float ty[4] = {};
+            if constexpr (DITHER) dither_theta4((uint32_t)y, (uint32_t)x0, ty);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) yy[e] = Q::y(k, px[0][e], px[1][e], px[2][e]);
+            for (int e = 0; e < 4; ++e) yy[e] = Q::template y<DITHER>(k, ty[e], px[0][e], px[1][e], px[2][e]);
             store_samples(fy + p, yy);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
@@ -610,8 +627,9 @@ __global__ __launch_bounds__(256) void quantize_cosited_kernel(const float* __re
             float m[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) m[c] = vertical(two_y, up[c][j], own[0][c][j], own[SY - 1][c][j]);
-            u[j] = Q::cb(k, m[0], m[1], m[2]);
-            v[j] = Q::cr(k, m[0], m[1], m[2]);
+            const float tc = th(cy, x0 / SX + j);
+            u[j] = Q::template cb<DITHER>(k, tc, m[0], m[1], m[2]);
+            v[j] = Q::template cr<DITHER>(k, tc, m[0], m[1], m[2]);
         }
         const long long coff = (long long)cy * cw + x0 / SX;
         store_samples(fu + coff, u);
@@ -633,16 +651,17 @@ __global__ __launch_bounds__(256) void quantize_cosited_kernel(const float* __re
                 q[1][c] = at(c, y, xr);
                 own[dy][c] = h3(at(c, y, xl), q[0][c], q[1][c]);
             }
-            fy[(long long)y * W + xc] = (S)Q::y(k, q[0][0], q[0][1], q[0][2]);
-            if (two_x) fy[(long long)y * W + xr] = (S)Q::y(k, q[1][0], q[1][1], q[1][2]);
+            fy[(long long)y * W + xc] = (S)Q::template y<DITHER>(k, th(y, xc), q[0][0], q[0][1], q[0][2]);
+            if (two_x) fy[(long long)y * W + xr] = (S)Q::template y<DITHER>(k, th(y, xr), q[1][0], q[1][1], q[1][2]);
         }
 #pragma unroll
         for (int c = 0; c < 3; ++c) up[c] = (TOP && cy > 0) ? h3(at(c, 2 * cy - 1, xl), at(c, 2 * cy - 1, xc), at(c, 2 * cy - 1, xr)) : own[0][c];
         float m[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) m[c] = vertical(two_y, up[c], own[0][c], own[SY - 1][c]);
-        fu[(long long)cy * cw + cx] = (S)Q::cb(k, m[0], m[1], m[2]);
-        fv[(long long)cy * cw + cx] = (S)Q::cr(k, m[0], m[1], m[2]);
+        const float tc = th(cy, cx);
+        fu[(long long)cy * cw + cx] = (S)Q::template cb<DITHER>(k, tc, m[0], m[1], m[2]);
+        fv[(long long)cy * cw + cx] = (S)Q::template cr<DITHER>(k, tc, m[0], m[1], m[2]);
     }
 }
 
@@ -751,8 +770,9 @@ int gather(const char* what, Rules rules, const uint8_t* frames, int n_frames, i
     return check_launch("gather_kernel");
 }
 
-// The body of every quantise entry.
-int quantize(const char* what, Rules rules, const float* in, int n, int H, int W, int colour, int depth, int chroma, uint8_t* out, void* stream) {
+// The body of every quantise entry.  dither: the DITHER instantiations (savsr_video_quantize_yuvs_d alone asks for them).
+int quantize(const char* what, Rules rules, const float* in, int n, int H, int W, int colour, int depth, int chroma, uint8_t* out, void* stream,
+             bool dither = false) {
     if (int rc = check_layout(what, rules, depth, chroma)) return rc;
     if (!in || !out) return fail(what, "null pointer");
     if (n < 1 || n > 65535 || H < 1 || W < 1) return fail(what, "n in 1 .. 65535, H, W >= 1");
@@ -768,8 +788,13 @@ int quantize(const char* what, Rules rules, const float* in, int n, int H, int W
         with_block(chroma, [&](auto b) {
             typedef decltype(b) B;
             typedef decltype(q) Q;
-            if (pl.vec) hipLaunchKernelGGL((quantize_kernel<B::SX, B::SY, true, Q>), pl.grid, dim3(256), 0, st, in, H, W, pl.fb, k, out);
-            else hipLaunchKernelGGL((quantize_kernel<B::SX, B::SY, false, Q>), pl.grid, dim3(256), 0, st, in, H, W, pl.fb, k, out);
+            auto go = [&](auto d) {
+                constexpr bool D = decltype(d)::value;
+                if (pl.vec) hipLaunchKernelGGL((quantize_kernel<B::SX, B::SY, true, D, Q>), pl.grid, dim3(256), 0, st, in, H, W, pl.fb, k, out);
+                else hipLaunchKernelGGL((quantize_kernel<B::SX, B::SY, false, D, Q>), pl.grid, dim3(256), 0, st, in, H, W, pl.fb, k, out);
+            };
+            if (dither) go(std::true_type{});
+            else go(std::false_type{});
         });
     };
     switch (depth == 8 ? colour : N_COLOURS + colour) {
@@ -841,12 +866,13 @@ int gather_sited(const char* what, const uint8_t* frames, int n_frames, int h, i
     return check_launch("gather_linear_kernel");
 }
 
-int quantize_sited(const char* what, const float* in, int n, int H, int W, int colour, int depth, int chroma, int siting, uint8_t* out, void* stream) {
+int quantize_sited(const char* what, const float* in, int n, int H, int W, int colour, int depth, int chroma, int siting, uint8_t* out, void* stream,
+                   bool dither = false) {
     if (int rc = check_layout(what, RULES_LAYOUT, depth, chroma)) return rc;
     if (int rc = check_siting(what, chroma, siting)) return rc;
     // not modelled, centre-sited (the box is its filter) or nothing to resample: the box quantiser, its instantiations and its bytes
     if (siting <= SAVSR_SITING_CENTRE || chroma == SAVSR_CHROMA_444)
-        return quantize(what, RULES_LAYOUT, in, n, H, W, colour, depth, chroma, out, stream);
+        return quantize(what, RULES_LAYOUT, in, n, H, W, colour, depth, chroma, out, stream, dither);
     if (!in || !out) return fail(what, "null pointer");
     if (n < 1 || n > 65535 || H < 1 || W < 1) return fail(what, "n in 1 .. 65535, H, W >= 1");
     if (int rc = check_depth_colour(what, RULES_LAYOUT, colour, depth)) return rc;
@@ -860,8 +886,13 @@ int quantize_sited(const char* what, const float* in, int n, int H, int W, int c
         auto go = [&](auto sy, auto top) {
             constexpr int SY = decltype(sy)::value;
             constexpr bool TOP = decltype(top)::value;
-            if (pl.vec) hipLaunchKernelGGL((quantize_cosited_kernel<SY, true, TOP, Q>), pl.grid, dim3(256), 0, st, in, H, W, pl.fb, k, out);
-            else hipLaunchKernelGGL((quantize_cosited_kernel<SY, false, TOP, Q>), pl.grid, dim3(256), 0, st, in, H, W, pl.fb, k, out);
+            auto with = [&](auto d) {
+                constexpr bool D = decltype(d)::value;
+                if (pl.vec) hipLaunchKernelGGL((quantize_cosited_kernel<SY, true, TOP, D, Q>), pl.grid, dim3(256), 0, st, in, H, W, pl.fb, k, out);
+                else hipLaunchKernelGGL((quantize_cosited_kernel<SY, false, TOP, D, Q>), pl.grid, dim3(256), 0, st, in, H, W, pl.fb, k, out);
+            };
+            if (dither) with(std::true_type{});
+            else with(std::false_type{});
         };
         if (chroma == SAVSR_CHROMA_422) go(std::integral_constant<int, 1>{}, std::false_type{});
         else if (siting == SAVSR_SITING_LEFT) go(std::integral_constant<int, 2>{}, std::false_type{});
@@ -931,4 +962,14 @@ extern "C" int savsr_video_gather_yuvs(const uint8_t* frames, int n_frames, int 
 extern "C" int savsr_video_quantize_yuvs(const float* in, int n, int H, int W, int colour, int depth, int chroma, int siting, uint8_t* out,
                                          void* stream) {
     return quantize_sited("video_quantize_yuvs", in, n, H, W, colour, depth, chroma, siting, out, stream);
+}
+
+// savsr_video_quantize_yuvs with a dither (SAVSR_DITHER_*): 0 runs its kernels and gives its bytes, 1 the ordered dither of dither.hpp.
+extern "C" int savsr_video_quantize_yuvs_d(const float* in, int n, int H, int W, int colour, int depth, int chroma, int siting, int dither,
+                                           uint8_t* out, void* stream) {
+    if (dither != SAVSR_DITHER_NONE && dither != SAVSR_DITHER_ORDERED) {
+        set_error("invalid argument: video_quantize_yuvs_d: dither %d (0 = none, 1 = ordered)", dither);
+        return SAVSR_E_ARG;
+    }
+    return quantize_sited("video_quantize_yuvs_d", in, n, H, W, colour, depth, chroma, siting, out, stream, dither == SAVSR_DITHER_ORDERED);
 }

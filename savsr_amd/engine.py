@@ -32,6 +32,7 @@ from . import _lib
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, ConvDesc, OSConvAttnDesc, SatuTiling, SatuWeights      # noqa: F401
 from .cache import ContextCache
 from .config import EngineConfig
+from .dither import dither_id
 from .launch import MAX_SUM_BLOCKS, Launcher, Src, _ptr      # noqa: F401
 from .packing import (BN_EPS, CONV_TH, CONV_TW, WeightPacking, acc_row, conv_pack_geometry, conv_pack_index, conv_wy_pack_index, get_hw,      # noqa: F401  (re-exported:
                       pack_conv_part, pack_conv_weight, pack_conv_weight_wy, satu_axis_tables, split_bf16_image, window_record)                            # tests and tools import them from here)
@@ -815,11 +816,13 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
                              colour space and siting -> fp32 planar RGB
             luma-only        savsr_video_gather_luma: the Y plane of YUV or       savsr_video_quantize_luma: into the Y plane of the
             (spec.luma)      grey-scale frames, c = 1                             output frames, or of [n, H, W, 1] uint8
+        With spec.dither the quantiser is the entry's `_d` form with the dither's id (savsr_amd/dither.py is the specification); without
+        one, the entries above, as ever.
         On the luma-only path the U and V planes of planar output frames never pass the network: `_resample_chroma` fills them first, on
         the caller's stream (savsr_amd/yuv.py "Luma-only checkpoints" is the specification).
         ensemble=True: frame i is the self-ensemble of window i (`_ensemble`, gathered by savsr_ensemble_gather_*).  Planar frames are
         converted once to fp32 (the same gather with the identity list) and take the fp32 path; the merge quantises packed uint8 itself,
-        every other quantiser runs after the fp32 merge.  Chroma never enters the ensemble of a luma-only network."""
+        every other quantiser runs after the fp32 merge, the packed one too when it dithers.  Chroma never enters the ensemble of a luma-only network."""
         if spec is None:
             spec = video_spec(self.nch)
         elif not isinstance(spec, VideoSpec):
@@ -852,6 +855,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
         if T > _lib.VIDEO_MAX_SLOTS:
             raise ValueError(f"num_frame = {T}: the window gather takes at most {_lib.VIDEO_MAX_SLOTS} frames per launch")
         idx_t = _lib.C.c_int32
+        did = dither_id(spec.dither)          # 0: the quantisers as they were
         if luma:
             def gather(idx, to, st):
                 _lib.check(self.lib.savsr_video_gather_luma(frames.data_ptr(), N, fb, h, w, src.depth, (idx_t * len(idx))(*idx), len(idx), to.data_ptr(), st),
@@ -871,16 +875,26 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
             od, ofb = (dst.depth, dst.frame_bytes(H, W)) if kind == "planar" else (8, H * W)          # (uint8: Y planes with nothing between them)
 
             def quantize_frames(x, to, nb, st):
-                _lib.check(self.lib.savsr_video_quantize_luma(x.data_ptr(), nb, H, W, od, to.data_ptr(), ofb, st), "savsr_video_quantize_luma")
+                if did:
+                    _lib.check(self.lib.savsr_video_quantize_luma_d(x.data_ptr(), nb, H, W, od, did, to.data_ptr(), ofb, st), "savsr_video_quantize_luma_d")
+                else:
+                    _lib.check(self.lib.savsr_video_quantize_luma(x.data_ptr(), nb, H, W, od, to.data_ptr(), ofb, st), "savsr_video_quantize_luma")
         elif kind == "planar":
             out_colour, out_chroma, out_siting = _yuv_ids(dst)
 
             def quantize_frames(x, to, nb, st):
-                _lib.check(self.lib.savsr_video_quantize_yuvs(x.data_ptr(), nb, H, W, out_colour, dst.depth, out_chroma, out_siting, to.data_ptr(), st),
-                           "savsr_video_quantize_yuvs")
+                if did:
+                    _lib.check(self.lib.savsr_video_quantize_yuvs_d(x.data_ptr(), nb, H, W, out_colour, dst.depth, out_chroma, out_siting, did,
+                                                                    to.data_ptr(), st), "savsr_video_quantize_yuvs_d")
+                else:
+                    _lib.check(self.lib.savsr_video_quantize_yuvs(x.data_ptr(), nb, H, W, out_colour, dst.depth, out_chroma, out_siting, to.data_ptr(), st),
+                               "savsr_video_quantize_yuvs")
         else:
             def quantize_frames(x, to, nb, st):
-                _lib.check(self.lib.savsr_video_quantize_u8(x.data_ptr(), nb, c, H, W, to.data_ptr(), st), "savsr_video_quantize_u8")
+                if did:
+                    _lib.check(self.lib.savsr_video_quantize_u8_d(x.data_ptr(), nb, c, H, W, did, to.data_ptr(), st), "savsr_video_quantize_u8_d")
+                else:
+                    _lib.check(self.lib.savsr_video_quantize_u8(x.data_ptr(), nb, c, H, W, to.data_ptr(), st), "savsr_video_quantize_u8")
 
         def quantize(x, to, st):
             for a in range(0, int(x.shape[0]), 65535):          # (the entries take 1 .. 65535 frames)
@@ -895,7 +909,7 @@ class HipEngine(WeightPacking, ContextCache, Launcher):
                 for a in range(0, N, _lib.VIDEO_MAX_SLOTS):
                     gather(list(range(a, min(N, a + _lib.VIDEO_MAX_SLOTS))), f32[a:], st)
                 frames = f32
-            fused = kind == "uint8" and not luma          # the merge quantises packed uint8 itself
+            fused = kind == "uint8" and not luma and spec.dither is None          # the merge quantises packed uint8 itself (undithered)
             merged = out if kind == "float" or fused else torch.empty(n, c, H, W, device=self.dev, dtype=torch.float32)
             self._ensemble([(frames, win, tuple(scale), merged[i]) for i, win in enumerate(windows)], fused)
             if merged is not out:

@@ -10,6 +10,7 @@ from typing import NamedTuple, Optional, Tuple
 
 import torch
 
+from .dither import check_dither
 from .harness import window_indices
 from .yuv import (CHROMA_OF, LUMA_FORMAT, MONO, check_chroma_filter, check_colour, check_depth, check_depth_colour, check_siting, chroma_hw, frame_bytes,
                   layout_name)
@@ -241,7 +242,16 @@ class Side:
         return frame_bytes(h, w, self.depth, self.layout)
 
 
-def _resolve(nch: int, out: str, pixel_format: str, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter):
+def check_dither_out(dither, out: str) -> Optional[str]:
+    """`dither` (None or one of dither.DITHERS) goes with an integer output: out = 'float' has nothing to quantise."""
+    check_dither(dither)
+    if dither is not None and out == "float":
+        raise ValueError(f"dither = {dither!r} goes with an integer output (out = 'uint8', {_YUV_LIST} or {LUMA_FORMAT!r}): out = 'float' has "
+                         f"nothing to quantise")
+    return dither
+
+
+def _resolve(nch: int, out: str, pixel_format: str, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter, dither=None):
     """The fields of the VideoSpec of these arguments, after every check of them, in the order and the words the checks always had."""
     check_out(out, nch, chroma_filter)
     size = check_pixel_format(pixel_format, size)
@@ -249,9 +259,10 @@ def _resolve(nch: int, out: str, pixel_format: str, size, colour, out_colour, de
     d, od = check_depths(depth, out_depth, pixel_format, out, colour, out_colour)
     check_sitings(siting, out_siting, pixel_format, out)
     luma = luma_mode(nch, chroma_filter, pixel_format, out, colour, out_colour)
+    check_dither_out(dither, out)
     return (nch, Side(pixel_format, layout_of(pixel_format) if size else None, d, colour, siting),
             Side(out, layout_of(out) if out in SAMPLE_FORMATS else None, od, colour if out_colour is None else out_colour, out_siting),
-            size, luma, chroma_filter)
+            size, luma, chroma_filter, dither)
 
 
 @dataclass(frozen=True)
@@ -265,12 +276,13 @@ class VideoSpec:
     size: Optional[Tuple[int, int]]           # (h, w) of planar input frames; None: packed ones, which carry it in their shape
     luma: bool                                # the luma-only path (`luma_mode`)
     chroma_filter: Optional[str]
+    dither: Optional[str] = None              # the quantiser's dither (dither.DITHERS); None: round to nearest
 
     def __post_init__(self):
-        fields = (self.nch, self.inp, self.out, self.size, self.luma, self.chroma_filter)
+        fields = (self.nch, self.inp, self.out, self.size, self.luma, self.chroma_filter, self.dither)
         if not isinstance(self.inp, Side) or not isinstance(self.out, Side) or _resolve(
                 self.nch, self.out.fmt, self.inp.fmt, self.size, self.inp.colour, self.out.colour if self.out.yuv else None, self.inp.depth,
-                self.out.depth if self.out.planar else None, self.inp.siting, self.out.siting, self.chroma_filter) != fields:
+                self.out.depth if self.out.planar else None, self.inp.siting, self.out.siting, self.chroma_filter, self.dither) != fields:
             raise ValueError(f"not the VideoSpec of its own arguments (video_spec builds one): {fields}")
 
     @property
@@ -287,10 +299,10 @@ class VideoSpec:
 
 def video_spec(nch: int, out: str = "float", pixel_format: str = "rgb", size=None, colour: str = "bt601", out_colour: Optional[str] = None,
                depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
-               chroma_filter: Optional[str] = None) -> VideoSpec:
+               chroma_filter: Optional[str] = None, dither: Optional[str] = None) -> VideoSpec:
     """The VideoSpec of the format arguments of `upscale_video` / `VideoUpscaler` for a num_in_ch = nch network; refuses, by name, what
-    they refuse."""
-    return VideoSpec(*_resolve(nch, out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter))
+    they refuse.  dither: None or one of dither.DITHERS, the rule of every quantiser behind the network (savsr_amd/dither.py)."""
+    return VideoSpec(*_resolve(nch, out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter, dither))
 
 
 def detector_layout(frames: torch.Tensor, side: Side, size: Optional[Tuple[int, int]]) -> Tuple[int, int, int, int]:

@@ -56,6 +56,12 @@ Cb / Cr are resampled from each frame's own chroma planes at the network's scale
 checkpoints"); --out-depth, --out-chroma, --siting and --out-siting apply, the colour space is kept.  The default, none, is what this tool
 has always done.  A grey-scale input (Cmono, Cmono10, Cmono12) needs such a checkpoint and no filter, and is written as grey-scale.
 
+--dither ordered: 8-bit output of smooth gradients (sky, vignettes, fades), which a x4 result stretches into bands four times as wide.
+Every integer output -- the PNG folder, and Y, Cb and Cr of a Y4M output at any depth -- is written as floor(t + theta) instead of
+rint(t), theta a threshold from a 16 x 16 Bayer matrix at the sample's position (savsr_amd/dither.py), so that the mean over every
+16 x 16 block keeps the fp32 result to 1/256 of a code.  The pattern is static in time and the same for any --chunk.  The default, none,
+writes the bytes this tool has always written.  With --chroma-filter the resampled Cb / Cr keep rint.
+
 --cuts: edited footage.  Windows stop at scene cuts (every scene is upscaled as a video of its own, savsr_amd/scenes.py): auto finds
 them on the GPU as the frames arrive (--scene-threshold, per cent of the largest possible frame change; ffmpeg scdet's rule and default,
 not validated on real footage), K,K,... or @FILE (one frame index per line) gives them.  --cuts-out FILE writes the cuts used, one per line.
@@ -110,6 +116,7 @@ import time
 from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional
 
+from .dither import DITHERS
 from .deinterlace import FIELD_FLAGS, FIELD_ORDERS, resolve_fields
 from .pulldown import DEFAULT_CYCLE, PULLDOWN_FLAGS, check_cycle, resolve_pulldown
 from .scan import SCAN_FLAGS
@@ -210,6 +217,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--chroma-filter", default="none", choices=["none", "bicubic"],
                    help="luma-only checkpoints (num_in_ch = 1) on Y4M video: bicubic resamples Cb / Cr from the input's chroma planes at the "
                         "network's scale while Y goes through the network (default none)")
+    p.add_argument("--dither", default="none", choices=["none"] + list(DITHERS),
+                   help="how the fp32 result becomes integer codes (PNG folders and Y4M alike).  none (default): round to nearest; ordered: "
+                        "floor(t + theta) with a 16 x 16 Bayer threshold at the sample's position, which keeps smooth gradients from banding "
+                        "at 8 bits (static in time)")
     p.add_argument("--cuts", default=None, metavar="auto|K,K,...|@FILE",
                    help="scene cuts (first frame of every new scene): auto = found on the GPU, a comma-separated list, or @FILE with one index "
                         "per line; windows stop at cuts")
@@ -357,6 +368,7 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     if a.out_siting is not None and not a.y4m_out:
         p.error("--out-siting goes with a Y4M output (PNG frames are RGB)")
     a.chroma_filter = None if a.chroma_filter == "none" else a.chroma_filter
+    a.dither = None if a.dither == "none" else a.dither
     if a.chroma_filter is not None and not (a.y4m_in and a.y4m_out):
         p.error("--chroma-filter goes with a Y4M input and a Y4M output (the chroma planes come from the one and go to the other)")
     a.siting = a.siting or "none"
@@ -741,7 +753,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                            size=(h, w) if a.y4m_in else None, cuts=a.cuts, scene_threshold=a.scene_threshold,
                            colour="bt601" if chroma == MONO else colour or "bt601",          # (grey-scale frames carry no colour space)
                            out_colour=None if out_chroma == MONO else out_colour, depth=depth, out_depth=out_depth, siting=siting, out_siting=out_siting,
-                           chroma_filter=a.chroma_filter, crop=rect, bars=a.bars, fields=order, pulldown=film, pulldown_cycle=a.pulldown_cycle)
+                           chroma_filter=a.chroma_filter, crop=rect, bars=a.bars, fields=order, pulldown=film, pulldown_cycle=a.pulldown_cycle,
+                           dither=a.dither)
         done = 0
         try:
             for chunk in chunks:
@@ -768,6 +781,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         scenes += f", chroma {chroma if a.y4m_in else 'rgb'} -> {out_chroma or 'rgb'}"
     if siting is not None or out_siting is not None:
         scenes += f", siting {siting or 'none'} -> {out_siting or 'none'}"
+    if a.dither is not None:
+        scenes += f", dither {a.dither}"
     if order is not None:
         scenes += f", fields {order}"
     if verdict is not None:

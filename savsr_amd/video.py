@@ -26,6 +26,11 @@ scan="detect": the call finds out which of the two the video is (savsr_amd/scan.
 right after surface= unpacking and in front of everything else) and continues exactly as if the verdict's `kwargs()` had been given:
 fields=order for interlaced video, pulldown=order for telecined film, nothing for progressive and undetermined video.
 
+dither="ordered": every quantiser behind the network (packed uint8, planar YUV, the luma-only path's Y plane) takes floor(t + theta(y, x))
+in rint's place, theta from a 16 x 16 Bayer matrix at the sample's position in its plane (savsr_amd/dither.py is the specification, the
+`_d` entries of the C ABI the kernels).  It belongs to the quantiser: bars="keep" inserts exact nominal black after it and out_surface
+packs after that.  None runs the quantisers as they were; with out="float" there is nothing to quantise and the argument is refused.
+
 surface= / out_surface=: where the samples of planar frames lie in memory on either side (savsr_amd/surface.py: NV12, P010, UYVY, pitched
 planar, ...).  The frames are unpacked right after the host-to-device copy, in front of fields=, pulldown=, crop= and everything else, and
 the result is packed last, after the bars are re-inserted: the call is, bit for bit, the call on `unpack_surface(frames, surface, ...)`,
@@ -89,11 +94,12 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
                   out_colour: Optional[str] = None, depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None,
                   out_siting: Optional[str] = None, chroma_filter: Optional[str] = None, crop=None, crop_limit=24,
                   bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None, pulldown_cycle: int = 5, *,
-                  surface=None, out_surface=None, scan: Optional[str] = None) -> torch.Tensor:
+                  surface=None, out_surface=None, scan: Optional[str] = None, dither: Optional[str] = None) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
-    spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter)
+    spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter,
+                      dither)
     sc = as_scale(net.scale if scale is None else scale)
     if surface is not None:            # the frames lie in a surface: checked against it, unpacked below, and planar from there on
         in_tab = surface_table(surface, spec.inp, spec.size)
@@ -207,6 +213,9 @@ class VideoUpscaler:
     unpacked as it arrives, every returned chunk is packed into `out_surface` as it leaves.  The conversion is stateless, so any chunking
     gives the same frames.
 
+    dither= (keyword only): as in upscale_video.  The pattern depends on the sample's position in the frame alone, never on the frame's
+    index, so any chunking gives the same frames.
+
     scan="detect" is refused: the decision needs the video.  Run savsr_amd.detect_scan on a probe chunk (or prepass.ScanStats over a
     first pass, as python -m savsr_amd.upscale --scan detect does) and give its answer as fields= / pulldown=."""
 
@@ -214,7 +223,7 @@ class VideoUpscaler:
                  cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None,
                  depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
                  chroma_filter: Optional[str] = None, crop=None, bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None,
-                 pulldown_cycle: int = 5, *, surface=None, out_surface=None, scan: Optional[str] = None):
+                 pulldown_cycle: int = 5, *, surface=None, out_surface=None, scan: Optional[str] = None, dither: Optional[str] = None):
         _check_net(net)
         check_padding(padding)
         _check_scan(scan, fields, pulldown, pulldown_cycle, auto_ok=False)          # (None is the only value that passes: the path as it was)
@@ -228,7 +237,8 @@ class VideoUpscaler:
             self._prev_sad = 0                     # the last pair's score (scdet's damping term), carried from push to push
             self._plan = scenes.ScenePlan(net.num_frame, padding)
         # the frames on both sides, checked once, here; the luma-only path (`luma_mode`) is decided with them
-        self.spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter)
+        self.spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter,
+                               dither)
         self._full = self.spec                     # the spec of the chunks as pushed; `spec` becomes the cropped size's with a crop
         self._split = make_stage(fields, pulldown, pulldown_cycle, self.spec.inp, self.spec.size)          # the stage in front; None: as it was
         self._rect = _check_crop_args(crop, 24, bars, auto_ok=False)          # the rect to crop every chunk to; None: no crop, as it was

@@ -74,6 +74,8 @@ from typing import Tuple
 
 import numpy as np
 
+from .dither import check_dither, dither_floor
+
 # BT.601 limited range, the reference's constants.  to_rgb: ycbcr2rgb's matrix entries (per 8-bit step, result in [0, 1]) and its
 # offsets (in 8-bit steps, / 255 -> [0, 1]).  to_ycbcr: rgb2ycbcr's rows (8-bit steps per unit of RGB in [0, 1]) and offsets.
 BT601 = {
@@ -439,17 +441,19 @@ def ycbcr_f32(x: np.ndarray, colour: str = "bt601", chroma: str = "420", siting=
     return _row(p, t["y"], t["offset"][0]), _row(m, t["cb"], t["offset"][1]), _row(m, t["cr"], t["offset"][2])
 
 
-def rgb_to_i420(x_f32: np.ndarray, colour: str = "bt601", depth: int = 8, chroma: str = "420", siting=None) -> np.ndarray:
+def rgb_to_i420(x_f32: np.ndarray, colour: str = "bt601", depth: int = 8, chroma: str = "420", siting=None, dither=None) -> np.ndarray:
     """float32 [N, 3, H, W] -> uint8 [N, frame_bytes(H, W, depth, chroma)].  Limited range: after the clamp Y lies in 16 .. 235 and
     chroma in 16 .. 240, no clip.  Full range: chroma reaches 255.5, which rounds to 256, so the rounded values are clipped to 0 .. 255.
     depth = 10, 12 (limited range only): rint(ycbcr_f32 * 2^(depth - 8)), written as little-endian 16-bit samples.  chroma: the layout
     (the module's "Chroma layouts"); the default is I420.  siting: where the chroma samples lie (the module's "Chroma siting"); None and
-    "centre" are the block mean."""
+    "centre" are the block mean.  dither: None (rint, the lines above) or one of dither.DITHERS: floor(t + theta) in place of rint(t) in
+    every plane, theta at the sample's own coordinates in its plane (savsr_amd/dither.py; savsr_video_quantize_yuvs_d)."""
+    rnd = np.rint if check_dither(dither) is None else dither_floor
     if depth != 8:
         k = np.float32(1 << (check_depth_colour(depth, colour) - 8))
-        planes = [np.rint(v * k) for v in ycbcr_f32(x_f32, colour, chroma, siting)]
+        planes = [rnd(v * k) for v in ycbcr_f32(x_f32, colour, chroma, siting)]
     else:
-        planes = [np.rint(v) for v in ycbcr_f32(x_f32, colour, chroma, siting)]
+        planes = [rnd(v) for v in ycbcr_f32(x_f32, colour, chroma, siting)]
         if is_full_range(colour):
             planes = [np.fmin(np.fmax(v, np.float32(0.0)), np.float32(255.0)) for v in planes]
     n = planes[0].shape[0]
@@ -493,12 +497,14 @@ def luma_to_unit(samples: np.ndarray, depth: int = 8) -> np.ndarray:
     return s / np.float32(255 << (d - 8))
 
 
-def unit_to_luma(v: np.ndarray, depth: int = 8) -> np.ndarray:
+def unit_to_luma(v: np.ndarray, depth: int = 8, dither=None) -> np.ndarray:
     """The network's float32 luma -> Y samples (uint8 at 8 bits, uint16 at 10 / 12): rint(clamp(v, 0, 1) * float32(255 * 2^(d - 8))),
-    half to even; fmax / fmin, so a NaN becomes 0."""
+    half to even; fmax / fmin, so a NaN becomes 0.  dither: None or one of dither.DITHERS: floor(t + theta) in place of rint(t), theta at
+    the sample's (y, x) in the last two axes (savsr_amd/dither.py; savsr_video_quantize_luma_d)."""
     d = check_depth(depth)
     v = np.asarray(v, dtype=np.float32)
-    q = np.rint(np.fmin(np.fmax(v, np.float32(0.0)), np.float32(1.0)) * np.float32(255 << (d - 8)))
+    rnd = np.rint if check_dither(dither) is None else dither_floor
+    q = rnd(np.fmin(np.fmax(v, np.float32(0.0)), np.float32(1.0)) * np.float32(255 << (d - 8)))
     return q.astype(np.uint8 if d == 8 else np.uint16)
 
 

@@ -27,6 +27,15 @@ fails, times out or dies ends the run (nothing more is started on the GPU) and w
             twice in every round (their spread is the margin); the resampler at x4 from 180x320 for 4:2:0 -> 4:2:0 and 4:2:0 -> 4:4:4 (one
             call per plane; the figure is U and V together).  us, bytes in and out, GB/s = (bytes in + bytes out) / time.  No speed is
             fixed in advance.  `--legs luma --out profiles/bench_y4m_luma.json`
+  dither    the three quantiser entries with a dither argument (savsr_video_quantize_u8_d, _quantize_yuvs_d at 4:2:0 8-bit and 10-bit,
+            _quantize_luma_d at 8 bits) with dither 0 and 1, 7 frames of 720x1280, in one process, interleaved rounds; the dither-0 twin is
+            read twice in every round and the spread between its two readings is the margin (`margin_us`).  us, bytes in and out, GB/s,
+            and the moved-bytes floor at 8 TB/s beside every reading.  Then upscale_video on config 2's clip (180x320 x4) with
+            out="uint8" and out="i420", with and without dither="ordered", interleaved, frames/s.  With --parent CHECKOUT (a checkout of
+            the parent commit with its library built) the entries without a dither argument -- savsr_video_quantize_u8, _quantize_yuvs,
+            _quantize_luma, which both trees have -- are read in fresh processes, parent / this tree / parent / this tree; the margin is
+            the spread between the parent's own processes.  No time is fixed in advance.
+            `--legs dither --parent CHECKOUT --out profiles/bench_y4m_dither.json`
   ceiling   upscale_video on preloaded I420 frames, I420 out (frames/s): what the CLI could reach
   cli       python -m savsr_amd.upscale on one synthetic video, PNG folder -> PNG folder against .y4m -> .y4m, A/B/A/B; files under
             --workdir (name the disk it lies on beside the figures: tmpfs or a scratch disk)
@@ -49,7 +58,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_BYTES_PER_S = 8e12
-LEG_TIMEOUT_S = {"kernels": 240, "depth": 240, "chroma": 240, "siting": 300, "luma": 240, "ceiling": 420, "cli": 420, "psnr": 420}
+LEG_TIMEOUT_S = {"dither": 300, "dither_ab": 120, "kernels": 240, "depth": 240, "chroma": 240, "siting": 300, "luma": 240, "ceiling": 420, "cli": 420, "psnr": 420}
 
 
 def _net(dev):
@@ -407,6 +416,129 @@ def leg_luma(a):
             "timing": "HIP events around `iters` back-to-back launches (launch rate included); a resample reading is its two launches, U and V"}
 
 
+def _time_rounds(torch, fns, rounds, iters):
+    """us per launch of every fn, round by round: HIP events around `iters` back-to-back launches, the fns interleaved in every round."""
+    us = {k: [] for k in fns}
+    for k, fn in fns.items():
+        assert fn() == 0, k
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us[k].append(1e3 * e0.elapsed_time(e1) / iters)
+    return us
+
+
+def leg_dither(a):
+    import torch
+    from savsr_amd import _lib
+    from savsr_amd.yuv import frame_bytes
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    h, w, n = 720, 1280, 7
+    x3, x1 = torch.rand(n, 3, h, w, device=dev), torch.rand(n, 1, h, w, device=dev)
+    q8 = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+    fb = {d: frame_bytes(h, w, d, "420") for d in (8, 10)}
+    q420 = {d: torch.empty(n, fb[d], dtype=torch.uint8, device=dev) for d in (8, 10)}
+    entries = {          # name -> (call(dither), bytes in, bytes out)
+        "quantize_u8_d": (lambda d: lib.savsr_video_quantize_u8_d(x3.data_ptr(), n, 3, h, w, d, q8.data_ptr(), st), n * 12 * h * w, n * 3 * h * w),
+        "quantize_yuvs_d 420 8-bit": (lambda d: lib.savsr_video_quantize_yuvs_d(x3.data_ptr(), n, h, w, 1, 8, 0, 0, d, q420[8].data_ptr(), st),
+                                      n * 12 * h * w, n * fb[8]),
+        "quantize_yuvs_d 420 10-bit": (lambda d: lib.savsr_video_quantize_yuvs_d(x3.data_ptr(), n, h, w, 1, 10, 0, 0, d, q420[10].data_ptr(), st),
+                                       n * 12 * h * w, n * fb[10]),
+        "quantize_luma_d 8-bit": (lambda d: lib.savsr_video_quantize_luma_d(x1.data_ptr(), n, h, w, 8, d, q420[8].data_ptr(), fb[8], st),
+                                  n * 4 * h * w, n * h * w),
+    }
+    fns, moved = {}, {}
+    for name, (call, bi, bo) in entries.items():
+        for tag, d in (("dither 0 (a)", 0), ("dither 1", 1), ("dither 0 (b)", 0)):          # the twin first and last in every round
+            fns[f"{name} {tag}"] = lambda call=call, d=d: call(d)
+            moved[f"{name} {tag}"] = (bi, bo)
+    us = _time_rounds(torch, fns, a.rounds, a.iters)
+    med = {k: statistics.median(v) for k, v in us.items()}
+    rows = []
+    for k in fns:
+        name = k[:k.index(" dither ")]
+        ta, tb = med[f"{name} dither 0 (a)"], med[f"{name} dither 0 (b)"]
+        rows.append({"kernel": k, "size": [h, w], "frames": n, "us": round(med[k], 2), "bytes_in": moved[k][0], "bytes_out": moved[k][1],
+                     "gbs": round(sum(moved[k]) / (med[k] * 1e-6) / 1e9, 1), "floor_us_at_8tbs": round(sum(moved[k]) / HBM_BYTES_PER_S * 1e6, 2),
+                     "us_twin": round(min(ta, tb), 2), "margin_us": round(abs(ta - tb), 2),
+                     "slower_than_twin_by_more_than_the_margin": bool(med[k] > max(ta, tb) + abs(ta - tb)),
+                     "us_rounds": [round(v, 2) for v in us[k]]})
+    # end to end: config 2's clip
+    net = _net(dev)
+    sc = (a.scale, a.scale)
+    frames = torch.from_numpy(_video_i420(a.frames, a.h, a.w)).to(dev)
+    kw = dict(scale=sc, pixel_format="i420", size=(a.h, a.w))
+    plan = [(out, d) for out in ("uint8", "i420") for d in (None, "ordered")]
+    fps = {f"{out} dither={d}": [] for out, d in plan}
+    with torch.no_grad():
+        for out, d in plan:
+            net.upscale_video(frames[:16], out=out, dither=d, **kw)
+        torch.cuda.synchronize()
+        for _ in range(a.reps):
+            for out, d in plan:
+                t0 = time.perf_counter()
+                r = net.upscale_video(frames, out=out, dither=d, **kw)
+                torch.cuda.synchronize()
+                fps[f"{out} dither={d}"].append(round(a.frames / (time.perf_counter() - t0), 2))
+                del r
+    return {"kernels": rows, "rounds": a.rounds, "iters": a.iters, "colour": "bt709",
+            "timing": "HIP events around `iters` back-to-back launches (launch rate included)",
+            "e2e": {"workload": f"{a.frames} frames {a.h}x{a.w} x{a.scale:g}, I420 in", "fps": fps,
+                    "fps_median": {k: statistics.median(v) for k, v in fps.items()}}}
+
+
+def leg_dither_ab(a):
+    """The quantiser entries both trees have, on the tree at --root: one fresh process of the parent / this tree comparison."""
+    root = os.path.abspath(a.root or ROOT)
+    sys.path.insert(0, root)
+    import torch
+    from savsr_amd import _lib
+    from savsr_amd.yuv import frame_bytes
+    lib = _lib.load()
+    assert os.path.samefile(os.path.dirname(os.path.dirname(_lib.LIB_PATH)), os.path.join(root, "savsr_amd")), _lib.LIB_PATH
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    h, w, n = 720, 1280, 7
+    x3, x1 = torch.rand(n, 3, h, w, device=dev), torch.rand(n, 1, h, w, device=dev)
+    q8 = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+    fb = frame_bytes(h, w, 8, "420")
+    q420 = torch.empty(n, fb, dtype=torch.uint8, device=dev)
+    fns = {"savsr_video_quantize_u8": lambda: lib.savsr_video_quantize_u8(x3.data_ptr(), n, 3, h, w, q8.data_ptr(), st),
+           "savsr_video_quantize_yuvs 420 8-bit": lambda: lib.savsr_video_quantize_yuvs(x3.data_ptr(), n, h, w, 1, 8, 0, 0, q420.data_ptr(), st),
+           "savsr_video_quantize_yuvs 420 8-bit left": lambda: lib.savsr_video_quantize_yuvs(x3.data_ptr(), n, h, w, 1, 8, 0, 2, q420.data_ptr(), st),
+           "savsr_video_quantize_luma 8-bit": lambda: lib.savsr_video_quantize_luma(x1.data_ptr(), n, h, w, 8, q420.data_ptr(), fb, st)}
+    us = _time_rounds(torch, fns, a.rounds, a.iters)
+    return {"tree": "this" if os.path.samefile(root, ROOT) else "parent", "abi": int(lib.savsr_abi_version()),
+            "us": {k: round(statistics.median(v), 2) for k, v in us.items()}, "us_rounds": {k: [round(x, 2) for x in v] for k, v in us.items()}}
+
+
+def dither_parent_ab(a, run_child):
+    """parent / this / parent / this in fresh processes; the margin of every kernel is the spread between the parent's own processes."""
+    runs = {"parent": [], "this": []}
+    for _ in range(a.ab_rounds):
+        for tree, root in (("parent", a.parent), ("this", ROOT)):
+            r = run_child("dither_ab", ["--root", os.path.abspath(root)])
+            if r is None:
+                return {"runs": runs, "error": f"the {tree} process failed"}, 1
+            runs[tree].append(r)
+    out = {"runs": runs, "order": "fresh processes, parent / this tree, round after round", "kernels": {}}
+    for k in runs["parent"][0]["us"]:
+        pa, th = [r["us"][k] for r in runs["parent"]], [r["us"][k] for r in runs["this"]]
+        spread = max(pa) - min(pa)
+        out["kernels"][k] = {"parent_us": pa, "this_us": th, "parent_spread_us": round(spread, 2),
+                             "this_median_vs_parent_median": round(statistics.median(th) / statistics.median(pa), 4),
+                             "this_within_the_parents_range_widened_by_its_spread": bool(statistics.median(th) <= max(pa) + spread)}
+    return out, 0
+
+
 def leg_ceiling(a):
     import torch
     dev = torch.device("cuda:0")
@@ -488,7 +620,7 @@ def leg_psnr(a):
                        "note": "against the float result in float64; synthetic weights"}}
 
 
-LEGS = {"kernels": leg_kernels, "depth": leg_depth, "chroma": leg_chroma, "siting": leg_siting, "luma": leg_luma, "ceiling": leg_ceiling, "cli": leg_cli, "psnr": leg_psnr}
+LEGS = {"dither": leg_dither, "dither_ab": leg_dither_ab, "kernels": leg_kernels, "depth": leg_depth, "chroma": leg_chroma, "siting": leg_siting, "luma": leg_luma, "ceiling": leg_ceiling, "cli": leg_cli, "psnr": leg_psnr}
 
 
 def main():
@@ -503,6 +635,10 @@ def main():
     ap.add_argument("--workdir", default=None, help="where the CLI legs keep their files (default: the temporary directory)")
     ap.add_argument("--legs", default="kernels,ceiling,cli,psnr")
     ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)          # (a child process: run one leg, print its JSON)
+    ap.add_argument("--root", default=None, help=argparse.SUPPRESS)         # (a child process of the dither leg: the tree to import savsr_amd from)
+    ap.add_argument("--parent", default=None, help="dither leg: a checkout of the parent commit with its library built (parent / this tree in "
+                                                   "fresh processes); without it that comparison is skipped")
+    ap.add_argument("--ab-rounds", type=int, default=2, help="dither leg: processes per tree of the parent comparison")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.leg:
@@ -527,6 +663,21 @@ def main():
             break                                   # nothing more is started after a leg that failed
         res["legs"][leg] = json.loads(r.stdout.strip().splitlines()[-1])
         print(leg, json.dumps(res["legs"][leg]), flush=True)
+        if leg == "dither" and a.parent:
+            def run_child(name, extra, base=cmd):
+                try:
+                    c = subprocess.run(base[:2] + ["--leg", name] + base[4:] + extra, cwd=ROOT, capture_output=True, text=True, timeout=LEG_TIMEOUT_S[name])
+                except subprocess.TimeoutExpired:
+                    return None
+                if c.returncode != 0:
+                    print(c.stderr[-1500:], file=sys.stderr, flush=True)
+                    return None
+                return json.loads(c.stdout.strip().splitlines()[-1])
+            res["legs"]["dither_vs_parent"], bad = dither_parent_ab(a, run_child)
+            print("dither_vs_parent", json.dumps(res["legs"]["dither_vs_parent"]), flush=True)
+            if bad:
+                rc = 1
+                break                               # nothing more is started after a process that failed
     if "ceiling" in res["legs"] and "cli" in res["legs"] and "error" not in res["legs"]["cli"] and "error" not in res["legs"]["ceiling"]:
         res["y4m_cli_vs_ceiling"] = round(res["legs"]["cli"]["cli"]["y4m_fps_median"] / res["legs"]["ceiling"]["ceiling_fps"], 3)
     print(json.dumps(res), flush=True)
