@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 47
+#define SAVSR_ABI_VERSION 48
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -655,6 +655,21 @@ int savsr_video_deinterlace_u8(const uint8_t* frames, int n_frames, int64_t fram
                                int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
 int savsr_video_deinterlace_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int depth,
                                 int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
+
+/* (ABI 48) The same with a method and a rate (deinterlacer= / field_rate= of upscale_video and VideoUpscaler, method= / rate= of
+ * savsr_amd.deinterlace, --deinterlacer / --field-rate of python -m savsr_amd.upscale).  The argument lists above plus, in front of
+ * `stream`, `method` (0: yadif, the entries above; 1: ffmpeg bwdif's rule, yadif's temporal clamp around the w3fdif interpolation filters --
+ * savsr_amd/deinterlace.py `bwdif_matrix` restates it sample by sample, the kernels equal it bit for bit) and `rate` (0: double, two
+ * output frames per source frame as above; 1: same, output frame n - from is the first field in time of source frame n, so `out`
+ * holds to - from frames and the second fields are not computed).  bwdif has no horizontal taps: `step` is checked as above and then
+ * ignored by method 1.  Method 0 with rate 0 gives the bytes of the entries above.  Refused as above, and: a method or a rate other
+ * than 0 / 1. */
+int savsr_video_deinterlace_u8_m(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes, int step,
+                                 int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, int method, int rate,
+                                 void* stream);
+int savsr_video_deinterlace_u16_m(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int depth,
+                                  int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, int method, int rate,
+                                  void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 44) Inverse 3:2 pulldown (pulldown.hip; savsr_amd.field_scores, savsr_amd.remove_pulldown, upscale_video(pulldown=...),

@@ -282,7 +282,8 @@ class SAVSR(nn.Module):
                       out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
                       chroma_filter: Optional[str] = None, crop=None, crop_limit=24, bars: str = "keep", fields: Optional[str] = None,
                       pulldown: Optional[str] = None, pulldown_cycle: int = 5, *, surface=None, out_surface=None,
-                      scan: Optional[str] = None, dither: Optional[str] = None) -> torch.Tensor:
+                      scan: Optional[str] = None, dither: Optional[str] = None, deinterlacer: str = "yadif",
+                      field_rate: str = "double") -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -372,12 +373,19 @@ class SAVSR(nn.Module):
         same bytes.  One pattern (no blue noise, no error diffusion); the luma-only path's resampled Cb / Cr keep rint; not validated on
         real footage; the gain is largest at 8 bits.  Refused with out="float" (nothing to quantise).  With the self-ensemble the merge
         stays fp32 and the dithered quantiser runs after it.
+        deinterlacer, field_rate (keyword only): how fields= (or an interlaced verdict of scan="detect") is carried out.  deinterlacer:
+        "yadif" (the default) or "bwdif", ffmpeg bwdif's rule (savsr_amd.deinterlace.bwdif_matrix: yadif's temporal clamp around the
+        w3fdif interpolation filters), under which still areas -- captions, logos, locked-off shots -- come back as they are.  field_rate:
+        "double" (the default: 2N frames) or "same": N frames, the first field in time of every source frame, so the network runs
+        once per source frame; explicit cuts then index the N frames (a cut at source frame k is k).  The property holds with both:
+        the result is upscale_video on savsr_amd.deinterlace(frames, fields, ..., method=deinterlacer, rate=field_rate).  Refused when
+        not at their defaults without fields= or scan="detect", and together with pulldown=.  Not validated on real footage.
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
         return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold, colour, out_colour, depth, out_depth,
                              siting, out_siting, chroma_filter, crop, crop_limit, bars, fields, pulldown, pulldown_cycle, surface=surface,
-                             out_surface=out_surface, scan=scan, dither=dither)
+                             out_surface=out_surface, scan=scan, dither=dither, deinterlacer=deinterlacer, field_rate=field_rate)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

@@ -14,6 +14,13 @@
 // the neighbouring lanes issue as well, so they are L1 / L2 hits; 18 loads and 2 stores of 16 bytes per lane, all loads issued before
 // the first use, no LDS).  The pixel step is a template argument, so every sample is a constant bit field of a register.  One-sample
 // form (any pointer, stride and size): a lane owns one sample.  Absolute differences are v_sad_u8 / v_sad_u16 on single samples.
+//
+// (ABI 48) savsr_video_deinterlace_u8_m / _u16_m add a method and a rate.  Method 1 is ffmpeg bwdif's rule (`bwdif_matrix` is its
+// specification): yadif's temporal clamp around the w3fdif filters, a 4-tap vertical filter on cur (rows y +- 1, y +- 3) plus a 3-row
+// high-frequency term of p2 + n2 (rows y, y +- 2, y +- 4).  No horizontal taps, so no pixel step and no neighbour chunks: the vector form
+// issues 18 loads of 16 bytes per lane as yadif's does (cur x 4, p2 / n2 x 10, prev / next x 4), all before the first use, no LDS.  The
+// still case, the three interpolations and the clips are selects; the filter products are 24-bit multiplies (sums below 2^14 by constants
+// below 2^13).  Rate 1 ("same") launches one output frame per source frame, its first field in time: the second fields are not computed.
 #include "common.hpp"
 #include "video_samples.hpp"
 
@@ -45,6 +52,15 @@ __device__ __forceinline__ int absdiff(int a, int b) {
         return a > b ? a - b : b - a;
 #endif
     }
+}
+
+// a * b of values that fit 24 bits: v_mul_i32_i24 on the device.
+__device__ __forceinline__ int mul24(int a, int b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __mul24(a, b);
+#else
+    return a * b;
+#endif
 }
 
 // The samples one interpolated sample reads.  u / l: the rows above and below in cur at x + (k - 3) * step, k = 0 .. 6.
@@ -86,12 +102,46 @@ __device__ __forceinline__ int yadif(const Taps& t, bool edge, bool inner) {
     return min(max(pred, d - diff), d + diff);
 }
 
+// The samples one interpolated sample of bwdif reads.
+struct BTaps {
+    int c, e, c3m, c3p;                       // cur at rows y - 1, y + 1 (mirrored), y - 3, y + 3
+    int p2y, n2y, p2m, n2m, p2p, n2p;          // p2 / n2 at rows y, y - 2, y + 2
+    int p2mm, n2mm, p2pp, n2pp;               // p2 / n2 at rows y - 4, y + 4
+    int pu, pl, nu, nl;                       // prev and next at the rows above and below
+};
+
+// deinterlace.py's `bwdif_matrix` for one sample.  inner: y - 2 >= 0 and y + 2 <= R - 1; line: y - 4 >= 0 and y + 4 <= R - 1.  Every >>
+// is an arithmetic shift of a signed 32-bit value (the floor, as the specification's); every operand of a product is below 2^14.
+template <int BYTES>
+__device__ __forceinline__ int bwdif(const BTaps& t, bool inner, bool line, int top) {
+    constexpr int LF0 = 4309, LF1 = 213, HF0 = 5570, HF1 = 3801, HF2 = 1016, SP0 = 5077, SP1 = 981;
+    const int c = t.c, e = t.e;
+    const int s0 = t.p2y + t.n2y, sm = t.p2m + t.n2m, sp = t.p2p + t.n2p;
+    const int d = s0 >> 1;
+    const int t0 = absdiff<BYTES>(t.p2y, t.n2y);
+    const int t1 = (absdiff<BYTES>(t.pu, c) + absdiff<BYTES>(t.pl, e)) >> 1;
+    const int t2 = (absdiff<BYTES>(t.nu, c) + absdiff<BYTES>(t.nl, e)) >> 1;
+    const int diff = max(max(t0 >> 1, t1), t2);
+    const int b = (sm >> 1) - c, g = (sp >> 1) - e;
+    const int mx = max(max(d - e, d - c), min(b, g));
+    const int mn = min(min(d - e, d - c), max(b, g));
+    const int wide = inner ? max(max(diff, mn), -mx) : diff;
+    const int ce = c + e, c3 = t.c3m + t.c3p, far = t.p2mm + t.n2mm + t.p2pp + t.n2pp;
+    const int hf = ((mul24(HF0, s0) - mul24(HF1, sm + sp) + mul24(HF2, far)) >> 2) + mul24(LF0, ce) - mul24(LF1, c3);
+    const int spat = mul24(SP0, ce) - mul24(SP1, c3);
+    const int filt = (absdiff<BYTES>(c, e) > t0 ? hf : spat) >> 13;
+    const int interp = line ? filt : ce >> 1;
+    const int clamped = min(max(interp, d - wide), d + wide);
+    return diff == 0 ? d : min(max(clamped, 0), top);
+}
+
 // What a launch works on.  Rows are `pitch` bytes apart on both sides.
 struct Job {
     const uint8_t* src;          // plane of resident frame 0
     uint8_t* dst;                // plane of output frame 0
     long long src_stride, dst_stride, pitch;
     int n_frames, from, rows, cols, order, top;          // cols: samples of a row; top: 2^depth - 1
+    int same;                                            // 1: output frame o is field 0 of source frame from + o (rate "same")
 };
 
 // The rows and frames of output frame `o` of the launch and interpolated row index `ri`: false if there is no such row.
@@ -99,11 +149,12 @@ struct Where {
     const uint8_t *cur, *prev, *next, *p2, *n2;
     uint8_t* out;
     int y, up, dn, ym, yp;
-    bool inner;
+    int y3m, y3p, y4m, y4p;          // rows y -+ 3 and y -+ 4 (bwdif)
+    bool inner, line;
 };
 
 __device__ __forceinline__ bool locate(const Job& jb, int o, int ri, Where& w) {
-    const int n = jb.from + (o >> 1), f = o & 1;
+    const int n = jb.from + (jb.same ? o : o >> 1), f = jb.same ? 0 : o & 1;
     const int p = jb.order == 0 ? f : 1 - f;
     const int y = 2 * ri + (1 - p);
     if (y >= jb.rows) return false;
@@ -120,6 +171,11 @@ __device__ __forceinline__ bool locate(const Job& jb, int o, int ri, Where& w) {
     w.inner = y - 2 >= 0 && y + 2 <= jb.rows - 1;
     w.ym = w.inner ? y - 2 : y;          // (not used by the result when !inner: any row that exists)
     w.yp = w.inner ? y + 2 : y;
+    w.line = y - 4 >= 0 && y + 4 <= jb.rows - 1;
+    w.y3m = w.line ? y - 3 : w.up;       // (not used by the result when !line: any row that exists)
+    w.y3p = w.line ? y + 3 : w.dn;
+    w.y4m = w.line ? y - 4 : y;
+    w.y4p = w.line ? y + 4 : y;
     return true;
 }
 
@@ -233,16 +289,103 @@ __global__ __launch_bounds__(DI_THREADS) void deinterlace_one_kernel(Job jb, int
     if (w.y + 1 == jb.rows - 1) put_at<BYTES>(w.out + (w.y + 1) * P, x, cl);
 }
 
+// bwdif, vector form: the geometry of deinterlace_vec_kernel, 18 loads of the lane's own chunk.
 template <int BYTES>
-int launch_deinterlace(Job jb, int step, int n_out, hipStream_t st) {
+__global__ __launch_bounds__(DI_THREADS) void bwdif_vec_kernel(Job jb) {
+    constexpr int SPL = 16 / BYTES;
+    const int chunks = (int)(jb.pitch >> 4);
+    const int chunk = (int)blockIdx.x * 16 + ((int)threadIdx.x & 15);
+    const int ri = (int)blockIdx.y * DI_TILE_IROWS + ((int)threadIdx.x >> 4);
+    Where w;
+    if (chunk >= chunks || !locate(jb, (int)blockIdx.z, ri, w)) return;
+    const long long P = jb.pitch;
+    uint32_t Q[18][4];
+    {
+        const u32x4 v0 = load16(w.cur + w.up * P, chunk), v1 = load16(w.cur + w.dn * P, chunk);
+        const u32x4 v2 = load16(w.cur + w.y3m * P, chunk), v3 = load16(w.cur + w.y3p * P, chunk);
+        const u32x4 v4 = load16(w.p2 + w.y * P, chunk), v5 = load16(w.n2 + w.y * P, chunk);
+        const u32x4 v6 = load16(w.p2 + w.ym * P, chunk), v7 = load16(w.n2 + w.ym * P, chunk);
+        const u32x4 v8 = load16(w.p2 + w.yp * P, chunk), v9 = load16(w.n2 + w.yp * P, chunk);
+        const u32x4 v10 = load16(w.p2 + w.y4m * P, chunk), v11 = load16(w.n2 + w.y4m * P, chunk);
+        const u32x4 v12 = load16(w.p2 + w.y4p * P, chunk), v13 = load16(w.n2 + w.y4p * P, chunk);
+        const u32x4 v14 = load16(w.prev + w.up * P, chunk), v15 = load16(w.prev + w.dn * P, chunk);
+        const u32x4 v16 = load16(w.next + w.up * P, chunk), v17 = load16(w.next + w.dn * P, chunk);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            Q[0][k] = v0[k]; Q[1][k] = v1[k]; Q[2][k] = v2[k]; Q[3][k] = v3[k]; Q[4][k] = v4[k]; Q[5][k] = v5[k];
+            Q[6][k] = v6[k]; Q[7][k] = v7[k]; Q[8][k] = v8[k]; Q[9][k] = v9[k]; Q[10][k] = v10[k]; Q[11][k] = v11[k];
+            Q[12][k] = v12[k]; Q[13][k] = v13[k]; Q[14][k] = v14[k]; Q[15][k] = v15[k]; Q[16][k] = v16[k]; Q[17][k] = v17[k];
+        }
+    }
+    uint32_t res[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) {
+        BTaps t;
+        t.c = field<BYTES>(Q[0], i, jb.top);     t.e = field<BYTES>(Q[1], i, jb.top);
+        t.c3m = field<BYTES>(Q[2], i, jb.top);   t.c3p = field<BYTES>(Q[3], i, jb.top);
+        t.p2y = field<BYTES>(Q[4], i, jb.top);   t.n2y = field<BYTES>(Q[5], i, jb.top);
+        t.p2m = field<BYTES>(Q[6], i, jb.top);   t.n2m = field<BYTES>(Q[7], i, jb.top);
+        t.p2p = field<BYTES>(Q[8], i, jb.top);   t.n2p = field<BYTES>(Q[9], i, jb.top);
+        t.p2mm = field<BYTES>(Q[10], i, jb.top); t.n2mm = field<BYTES>(Q[11], i, jb.top);
+        t.p2pp = field<BYTES>(Q[12], i, jb.top); t.n2pp = field<BYTES>(Q[13], i, jb.top);
+        t.pu = field<BYTES>(Q[14], i, jb.top);   t.pl = field<BYTES>(Q[15], i, jb.top);
+        t.nu = field<BYTES>(Q[16], i, jb.top);   t.nl = field<BYTES>(Q[17], i, jb.top);
+        const int v = bwdif<BYTES>(t, w.inner, w.line, jb.top);
+        if constexpr (BYTES == 1) res[i >> 2] |= (uint32_t)v << (8 * (i & 3));
+        else res[i >> 1] |= (uint32_t)v << (16 * (i & 1));
+    }
+    *(reinterpret_cast<u32x4*>(w.out + w.y * P) + chunk) = u32x4{res[0], res[1], res[2], res[3]};
+    // the kept rows, as they are: the row above, and the matrix's last row where it lies below
+    if (w.y > 0) *(reinterpret_cast<u32x4*>(w.out + (w.y - 1) * P) + chunk) = u32x4{Q[0][0], Q[0][1], Q[0][2], Q[0][3]};
+    if (w.y + 1 == jb.rows - 1) *(reinterpret_cast<u32x4*>(w.out + (w.y + 1) * P) + chunk) = u32x4{Q[1][0], Q[1][1], Q[1][2], Q[1][3]};
+}
+
+// bwdif, one-sample form: the geometry of deinterlace_one_kernel.
+template <int BYTES>
+__global__ __launch_bounds__(DI_THREADS) void bwdif_one_kernel(Job jb) {
+    const int x = (int)blockIdx.x * DI_ONE_COLS + ((int)threadIdx.x & 63);
+    const int ri = (int)blockIdx.y * DI_ONE_IROWS + ((int)threadIdx.x >> 6);
+    Where w;
+    if (x >= jb.cols || !locate(jb, (int)blockIdx.z, ri, w)) return;
+    const long long P = jb.pitch;
+    const int cu = raw_at<BYTES>(w.cur + w.up * P, x), cl = raw_at<BYTES>(w.cur + w.dn * P, x);          // (unclipped: the kept rows' copies)
+    BTaps t;
+    t.c = min(cu, jb.top); t.e = min(cl, jb.top);
+    t.c3m = min(raw_at<BYTES>(w.cur + w.y3m * P, x), jb.top); t.c3p = min(raw_at<BYTES>(w.cur + w.y3p * P, x), jb.top);
+    t.p2y = min(raw_at<BYTES>(w.p2 + w.y * P, x), jb.top);    t.n2y = min(raw_at<BYTES>(w.n2 + w.y * P, x), jb.top);
+    t.p2m = min(raw_at<BYTES>(w.p2 + w.ym * P, x), jb.top);   t.n2m = min(raw_at<BYTES>(w.n2 + w.ym * P, x), jb.top);
+    t.p2p = min(raw_at<BYTES>(w.p2 + w.yp * P, x), jb.top);   t.n2p = min(raw_at<BYTES>(w.n2 + w.yp * P, x), jb.top);
+    t.p2mm = min(raw_at<BYTES>(w.p2 + w.y4m * P, x), jb.top); t.n2mm = min(raw_at<BYTES>(w.n2 + w.y4m * P, x), jb.top);
+    t.p2pp = min(raw_at<BYTES>(w.p2 + w.y4p * P, x), jb.top); t.n2pp = min(raw_at<BYTES>(w.n2 + w.y4p * P, x), jb.top);
+    t.pu = min(raw_at<BYTES>(w.prev + w.up * P, x), jb.top);  t.pl = min(raw_at<BYTES>(w.prev + w.dn * P, x), jb.top);
+    t.nu = min(raw_at<BYTES>(w.next + w.up * P, x), jb.top);  t.nl = min(raw_at<BYTES>(w.next + w.dn * P, x), jb.top);
+    put_at<BYTES>(w.out + w.y * P, x, bwdif<BYTES>(t, w.inner, w.line, jb.top));
+    if (w.y > 0) put_at<BYTES>(w.out + (w.y - 1) * P, x, cu);
+    if (w.y + 1 == jb.rows - 1) put_at<BYTES>(w.out + (w.y + 1) * P, x, cl);
+}
+
+// n_out output frames of source frames jb.from ...: two per source frame, or one with jb.same.  method 0: yadif, 1: bwdif.
+template <int BYTES>
+int launch_deinterlace(Job jb, int step, int n_out, hipStream_t st, int method = 0) {
     const bool vec = ((reinterpret_cast<uintptr_t>(jb.src) | reinterpret_cast<uintptr_t>(jb.dst)) & 15) == 0 && jb.src_stride % 16 == 0 &&
                      jb.dst_stride % 16 == 0 && jb.pitch % 16 == 0;
     const int irows = (jb.rows + 1) / 2;          // of the field with more interpolated rows; the other one's last tile row may be empty
     for (int o0 = 0; o0 < n_out; o0 += DI_MAX_Z - 1) {          // (an even count per launch: a launch starts at field 0 of a source frame)
         const int no = n_out - o0 < DI_MAX_Z - 1 ? n_out - o0 : DI_MAX_Z - 1;
         Job part = jb;
-        part.from = jb.from + o0 / 2;
+        part.from = jb.from + (jb.same ? o0 : o0 / 2);
         part.dst = jb.dst + (long long)o0 * jb.dst_stride;
+        if (method == 1) {
+            if (vec) {
+                const dim3 grid((unsigned)((jb.pitch + DI_TILE_BYTES - 1) / DI_TILE_BYTES), (unsigned)((irows + DI_TILE_IROWS - 1) / DI_TILE_IROWS), (unsigned)no);
+                hipLaunchKernelGGL((bwdif_vec_kernel<BYTES>), grid, dim3(DI_THREADS), 0, st, part);
+            } else {
+                const dim3 grid((unsigned)((jb.cols + DI_ONE_COLS - 1) / DI_ONE_COLS), (unsigned)((irows + DI_ONE_IROWS - 1) / DI_ONE_IROWS), (unsigned)no);
+                hipLaunchKernelGGL((bwdif_one_kernel<BYTES>), grid, dim3(DI_THREADS), 0, st, part);
+            }
+            if (int rc = check_launch(vec ? "bwdif_vec_kernel" : "bwdif_one_kernel")) return rc;
+            continue;
+        }
         if (vec) {
             const dim3 grid((unsigned)((jb.pitch + DI_TILE_BYTES - 1) / DI_TILE_BYTES), (unsigned)((irows + DI_TILE_IROWS - 1) / DI_TILE_IROWS), (unsigned)no);
             if (BYTES == 2) hipLaunchKernelGGL((deinterlace_vec_kernel<2, 1>), grid, dim3(DI_THREADS), 0, st, part);
@@ -291,8 +434,21 @@ extern "C" int savsr_video_deinterlace_u8(const uint8_t* frames, int n_frames, i
                                    out_frame_bytes, out_plane_offset))
         return rc;
     if (step < 1 || step > 4 || row_bytes % step) return fail_arg("video_deinterlace_u8: step 1 .. 4 and a divisor of row_bytes");
-    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, row_bytes, order, 255};
+    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, row_bytes, order, 255, 0};
     return launch_deinterlace<1>(jb, step, 2 * (to - from), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int savsr_video_deinterlace_u8_m(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes,
+                                            int step, int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
+                                            int method, int rate, void* stream) {
+    if (int rc = check_deinterlace("video_deinterlace_u8_m", frames, out, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to,
+                                   out_frame_bytes, out_plane_offset))
+        return rc;
+    if (step < 1 || step > 4 || row_bytes % step) return fail_arg("video_deinterlace_u8_m: step 1 .. 4 and a divisor of row_bytes");
+    if (method != 0 && method != 1) return fail_arg("video_deinterlace_u8_m: method 0 (yadif) or 1 (bwdif)");
+    if (rate != 0 && rate != 1) return fail_arg("video_deinterlace_u8_m: rate 0 (double) or 1 (same)");
+    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, row_bytes, order, 255, rate};
+    return launch_deinterlace<1>(jb, step, (rate ? 1 : 2) * (to - from), static_cast<hipStream_t>(stream), method);
 }
 
 extern "C" int savsr_video_deinterlace_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols,
@@ -304,6 +460,21 @@ extern "C" int savsr_video_deinterlace_u16(const uint8_t* frames, int n_frames, 
     if (depth != 10 && depth != 12) return fail_arg("video_deinterlace_u16: depth 10 or 12 (8 bits: savsr_video_deinterlace_u8)");
     if (((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(out)) & 1) || ((frame_bytes | plane_offset | out_frame_bytes | out_plane_offset) & 1))
         return fail_arg("video_deinterlace_u16: frames, out, the frame strides and the plane offsets must be 2-byte aligned (16-bit samples)");
-    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, 2ll * cols, n_frames, from, rows, cols, order, (1 << depth) - 1};
+    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, 2ll * cols, n_frames, from, rows, cols, order, (1 << depth) - 1, 0};
     return launch_deinterlace<2>(jb, 1, 2 * (to - from), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int savsr_video_deinterlace_u16_m(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols,
+                                             int depth, int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
+                                             int method, int rate, void* stream) {
+    if (int rc = check_deinterlace("video_deinterlace_u16_m", frames, out, n_frames, frame_bytes, plane_offset, rows, 2 * (int64_t)cols, order, from, to,
+                                   out_frame_bytes, out_plane_offset))
+        return rc;
+    if (depth != 10 && depth != 12) return fail_arg("video_deinterlace_u16_m: depth 10 or 12 (8 bits: savsr_video_deinterlace_u8_m)");
+    if (((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(out)) & 1) || ((frame_bytes | plane_offset | out_frame_bytes | out_plane_offset) & 1))
+        return fail_arg("video_deinterlace_u16_m: frames, out, the frame strides and the plane offsets must be 2-byte aligned (16-bit samples)");
+    if (method != 0 && method != 1) return fail_arg("video_deinterlace_u16_m: method 0 (yadif) or 1 (bwdif)");
+    if (rate != 0 && rate != 1) return fail_arg("video_deinterlace_u16_m: rate 0 (double) or 1 (same)");
+    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, 2ll * cols, n_frames, from, rows, cols, order, (1 << depth) - 1, rate};
+    return launch_deinterlace<2>(jb, 1, (rate ? 1 : 2) * (to - from), static_cast<hipStream_t>(stream), method);
 }

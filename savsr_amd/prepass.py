@@ -16,7 +16,7 @@ import torch
 from . import active
 from . import pulldown as pd
 from . import scan as sc
-from .deinterlace import FIELD_ORDERS, check_frame_rows, check_order
+from .deinterlace import DEINTERLACERS, FIELD_ORDERS, FIELD_RATES, check_frame_rows, check_method, check_order, check_rate
 from .frames import SAMPLE_FORMATS, Side, VideoSpec, check_sample_alignment, detector_layout, detector_side, plane_table
 from .scenes import check_threshold, cuts_from_sad, sad_samples
 from .surface import LAYOUTS, Surface, SurfaceTable, check_stride, check_surface, descriptor
@@ -349,19 +349,30 @@ def _field_job(frames: torch.Tensor, order: str, side: Side, size: Size, hi: Opt
     return frames.contiguous(), n, n if hi is None else hi, c, plane_table(side, size, c, h, w), FIELD_ORDERS.index(order)
 
 
-def _deinterlace_device(frames: torch.Tensor, order: str, side: Side, size: Size, lo: int = 0, hi: Optional[int] = None) -> torch.Tensor:
+def _deinterlace_device(frames: torch.Tensor, order: str, side: Side, size: Size, lo: int = 0, hi: Optional[int] = None,
+                        method: str = "yadif", rate: str = "double") -> torch.Tensor:
     """savsr_video_deinterlace_* on resident frames of the input side on the GPU: the 2 (hi - lo) progressive frames of source frames
-    [lo, hi) (default: all), prev / next taken among the resident frames and clamped there.  One call per plane, on the current stream."""
+    [lo, hi) (default: all), prev / next taken among the resident frames and clamped there.  One call per plane, on the current stream.
+    method "bwdif" or rate "same" (hi - lo frames: the first field in time of every source frame, the others are not computed) go
+    through the `_m` entries; the defaults run the entries they ran before."""
     from . import _lib
+    mid, rid = DEINTERLACERS.index(method), FIELD_RATES.index(rate)
     frames, n, hi, c, tab, oid = _field_job(frames, order, side, size, hi)
-    out = frames.new_empty((2 * (hi - lo),) + tuple(frames.shape[1:]))
+    out = frames.new_empty(((1 if rid else 2) * (hi - lo),) + tuple(frames.shape[1:]))
     if hi <= lo:
         return out
     lib = _lib.load()
     with torch.cuda.device(frames.device):
         st = torch.cuda.current_stream().cuda_stream
         for p in tab.planes:          # (the pixel step of packed frames is their channel count: neighbours of a sample are c bytes away)
-            if tab.sample == 1:
+            if mid or rid:
+                if tab.sample == 1:
+                    _lib.check(lib.savsr_video_deinterlace_u8_m(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes, max(c, 1), oid, lo, hi,
+                                                                out.data_ptr(), tab.stride, p.offset, mid, rid, st), "savsr_video_deinterlace_u8_m")
+                else:
+                    _lib.check(lib.savsr_video_deinterlace_u16_m(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes // 2, side.depth, oid, lo,
+                                                                 hi, out.data_ptr(), tab.stride, p.offset, mid, rid, st), "savsr_video_deinterlace_u16_m")
+            elif tab.sample == 1:
                 _lib.check(lib.savsr_video_deinterlace_u8(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes, max(c, 1), oid, lo, hi,
                                                           out.data_ptr(), tab.stride, p.offset, st), "savsr_video_deinterlace_u8")
             else:
@@ -370,16 +381,21 @@ def _deinterlace_device(frames: torch.Tensor, order: str, side: Side, size: Size
     return out
 
 
-def deinterlace(frames: torch.Tensor, order: str, pixel_format: str = "rgb", size=None, depth: int = 8) -> torch.Tensor:
+def deinterlace(frames: torch.Tensor, order: str, pixel_format: str = "rgb", size=None, depth: int = 8, method: str = "yadif",
+                rate: str = "double") -> torch.Tensor:
     """Interlaced video as progressive frames at the field rate: 2N frames on the GPU in the format of the N given ones
     (savsr_amd.deinterlace.deinterlace_frames is the specification, bit for bit), on the caller's current stream, without a sync.  Output
     frame 2n + f keeps field f of source frame n (order "tff": the top field is the earlier one; "bff": the bottom one) and interpolates
     the other rows by ffmpeg yadif's rule.  frames: [N, h, w, c] uint8 (GPU or host, c in 1 .. 3), or with pixel_format "i420", "i422",
     "i444", "y400" and size=(h, w): [N, frame_bytes] uint8, every plane on its own, 16-bit samples at depth 10 / 12.  Float frames are
-    refused, and so are frames of one row (three for 4:2:0: the chroma planes need two)."""
+    refused, and so are frames of one row (three for 4:2:0: the chroma planes need two).  method="bwdif": the other rows by ffmpeg
+    bwdif's rule (savsr_amd.deinterlace.bwdif_matrix), under which static video comes back as it is.  rate="same": N frames, the first
+    field in time of every source frame (the frames [0::2] of the 2N; the others are not computed)."""
     check_order(order)
+    check_method(method)
+    check_rate(rate)
     frames, side, size = _stage_args(frames, pixel_format, size, depth, _field_frames)
-    return _deinterlace_device(frames, order, side, size)
+    return _deinterlace_device(frames, order, side, size, method=method, rate=rate)
 
 
 class FieldSplitter:
@@ -387,10 +403,14 @@ class FieldSplitter:
     final, finish() the last source frame's two.  The second field of the last pushed frame needs the frame after it, so one source frame
     is held back; with the frame before it (the temporal context) the device keeps at most two source frames between pushes (copies of
     their own, so that the chunk they came with is released).  Concatenated, the outputs are `deinterlace` on the whole video for any
-    chunking.  finish() without a pushed frame returns None."""
+    chunking.  finish() without a pushed frame returns None.  method="bwdif" reads the same three frames, and with rate="same" the one
+    field of a frame still reads the frame after it (its t2 term), so the same frame is held back for every method and rate."""
 
-    def __init__(self, order: str, side: Side, size: Size):
+    def __init__(self, order: str, side: Side, size: Size, method: str = "yadif", rate: str = "double"):
         self.order, self.side, self.size = _check_fields(order), side, size
+        check_method(method)
+        check_rate(rate)
+        self.method, self.rate = method, rate
         self._src: Optional[torch.Tensor] = None          # source frames [seen - len, seen): the context frame, then the ones not done
         self._todo = 0                                    # how many of them are not deinterlaced yet (they are the last ones)
 
@@ -399,7 +419,7 @@ class FieldSplitter:
         src = frames.contiguous() if self._src is None else torch.cat([self._src, frames], 0)
         n = int(src.shape[0])
         lo, hi = n - self._todo - k, n - 1                # all but the last frame, whose next is not known yet
-        res = _deinterlace_device(src, self.order, self.side, self.size, lo, max(hi, lo))
+        res = _deinterlace_device(src, self.order, self.side, self.size, lo, max(hi, lo), self.method, self.rate)
         if hi > lo:
             self._src, self._todo = src[max(hi - 1, 0):].clone(), 1          # (a copy of two frames: the chunk's storage is released)
         else:
@@ -416,7 +436,7 @@ class FieldSplitter:
         if src is None or self._todo == 0:          # nothing was pushed (or finish() ran before)
             return None
         n = int(src.shape[0])
-        return _deinterlace_device(src, self.order, self.side, self.size, n - self._todo, n)
+        return _deinterlace_device(src, self.order, self.side, self.size, n - self._todo, n, self.method, self.rate)
 
 
 # ---- telecined film (savsr_amd/pulldown.py is the specification) -----------------------------------------------------------------------------
@@ -698,10 +718,28 @@ def _check_scan(scan, fields, pulldown, pulldown_cycle, auto_ok: bool = True) ->
     return scan
 
 
-def make_stage(fields, pulldown, pulldown_cycle, side: Side, size: Size):
+def _check_field_options(deinterlacer, field_rate, fields, pulldown, detect: bool = False) -> None:
+    """deinterlacer= / field_rate= say how fields= (or an interlaced verdict of scan="detect") is carried out: refused by name when
+    unknown, without either when not at their defaults, and together with pulldown=."""
+    check_method(deinterlacer, "deinterlacer")
+    check_rate(field_rate, "field_rate")
+    for name, value, default in (("deinterlacer", deinterlacer, DEINTERLACERS[0]), ("field_rate", field_rate, FIELD_RATES[0])):
+        if value == default:
+            continue
+        if pulldown is not None:
+            raise ValueError(f"{name} = {value!r} together with pulldown = {pulldown!r}: the pulldown removal weaves fields and interpolates "
+                             f"nothing; {name} goes with fields=")
+        if fields is None and not detect:
+            raise ValueError(f"{name} = {value!r} goes with fields=: without interlaced video there are no fields to interpolate")
+
+
+def make_stage(fields, pulldown, pulldown_cycle, side: Side, size: Size, deinterlacer: str = "yadif", field_rate: str = "double"):
     """The streaming stage in front of everything else that fields= / pulldown= / pulldown_cycle= ask for, on frames of `side`: None, a
-    FieldSplitter or a PulldownRemover (the two exclude each other), after `_check_fields` and `_check_pulldown`, in that order."""
-    stage = None if _check_fields(fields) is None else FieldSplitter(fields, side, size)
-    if _check_pulldown(pulldown, pulldown_cycle, fields) is not None:
-        stage = PulldownRemover(pulldown, side, size, pulldown_cycle)
-    return stage
+    FieldSplitter or a PulldownRemover (the two exclude each other), after `_check_fields`, `_check_pulldown` and
+    `_check_field_options` (deinterlacer= / field_rate=, which the FieldSplitter takes), in that order."""
+    _check_fields(fields)
+    _check_pulldown(pulldown, pulldown_cycle, fields)
+    _check_field_options(deinterlacer, field_rate, fields, pulldown)
+    if fields is not None:
+        return FieldSplitter(fields, side, size, deinterlacer, field_rate)
+    return None if pulldown is None else PulldownRemover(pulldown, side, size, pulldown_cycle)

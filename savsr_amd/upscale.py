@@ -80,6 +80,9 @@ measure the deinterlaced video.  tff / bff name the field order, auto takes it f
 progressive; Im, mixed, is refused).  The output is then tagged Ip at twice the frame rate, and a PNG folder holds twice the files
 (%08d.png).  The default, progressive, is what this tool has always done: the frames go through as they are and the I tag is passed on;
 for an input tagged It / Ib / Im one line on stderr says so.  Telecined film is not interlaced video: see --pulldown.
+--deinterlacer bwdif interpolates by ffmpeg bwdif's rule instead (still areas come back as they are); --field-rate same keeps the first
+field in time of every frame only: the output is tagged Ip at the input's frame rate, a PNG folder holds as many files as were read, and
+the network runs once per input frame.  Both go with --fields or --scan detect.
 
 --pulldown: telecined film (3:2 pulldown: most NTSC film DVDs and broadcast film; four film frames lie in five video frames as the fields
 AA BB BC CD DD).  The film frames are recovered on the GPU before anything else sees them (savsr_amd/pulldown.py: every frame keeps its
@@ -117,7 +120,7 @@ from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional
 
 from .dither import DITHERS
-from .deinterlace import FIELD_FLAGS, FIELD_ORDERS, resolve_fields
+from .deinterlace import DEINTERLACERS, FIELD_FLAGS, FIELD_ORDERS, FIELD_RATES, resolve_fields
 from .pulldown import DEFAULT_CYCLE, PULLDOWN_FLAGS, check_cycle, resolve_pulldown
 from .scan import SCAN_FLAGS
 from .yuv import COLOURS, SITINGS
@@ -237,6 +240,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="interlaced input: deinterlace on the GPU first, every frame giving two progressive ones at the field rate.  tff / bff: "
                         "the field order; auto: from the Y4M input's I tag (It, Ib; Im is refused); progressive (default): frames go through as "
                         "they are, the I tag is passed on")
+    p.add_argument("--deinterlacer", default=None, choices=list(DEINTERLACERS),
+                   help="--fields / --scan detect: the rule that interpolates the missing rows.  yadif (default); bwdif: ffmpeg bwdif's rule "
+                        "(yadif's temporal clamp around the w3fdif filters), which returns still areas as they are")
+    p.add_argument("--field-rate", default=None, choices=list(FIELD_RATES),
+                   help="--fields / --scan detect: double (default) = two progressive frames per input frame at the field rate; same = one, "
+                        "the first field in time, at the input's frame rate (half the network's work)")
     p.add_argument("--pulldown", default=None, choices=list(PULLDOWN_FLAGS),
                    help="telecined film (3:2 pulldown): recover the film frames on the GPU first, 4 for every 5 read.  tff / bff: the field "
                         "order; auto: from the Y4M input's I tag (It, Ib; Im is refused); none (default): frames go through as they are")
@@ -333,6 +342,12 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error(f"--scan detect together with {given}: the detector answers the question that flag answers; give one of them")
     elif a.scan_out is not None:
         p.error("--scan-out goes with --scan detect")
+    if a.scan is None and a.fields not in ("auto",) + FIELD_ORDERS:
+        if a.deinterlacer is not None:
+            p.error("--deinterlacer goes with --fields auto, tff or bff, or --scan detect")
+        if a.field_rate is not None:
+            p.error("--field-rate goes with --fields auto, tff or bff, or --scan detect")
+    a.deinterlacer, a.field_rate = a.deinterlacer or DEINTERLACERS[0], a.field_rate or FIELD_RATES[0]
     a.bars = a.bars or "keep"
     a.y4m_in, a.y4m_out = is_y4m(a.input), is_y4m(a.output)
     if not a.y4m_in:
@@ -530,7 +545,8 @@ def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, de
     from .yuv import CHROMAS
     top = None
     f = None
-    split = make_stage(order, film, a.pulldown_cycle, *detector_side(fmt_in, size, depth))
+    how = (a.deinterlacer, a.field_rate) if order is not None else ()          # (they say how --fields is carried out, and nothing else)
+    split = make_stage(order, film, a.pulldown_cycle, *detector_side(fmt_in, size, depth), *how)
 
     def fold(frames):
         nonlocal top
@@ -611,7 +627,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     net = load_net(a)
     net.set_precision(a.precision)
     net.set_self_ensemble(a.self_ensemble)
-    n_png = None if paths is None else len(paths) * (2 if a.fields in FIELD_ORDERS else 1)          # (--fields: two frames per file)
+    per_file = 1 if a.field_rate == "same" else 2                 # (--fields: two frames per file; --field-rate same: one)
+    n_png = None if paths is None else len(paths) * (per_file if a.fields in FIELD_ORDERS else 1)
     if paths is not None and a.pulldown in FIELD_ORDERS:
         n_png -= n_png // a.pulldown_cycle                        # (--pulldown: one frame of every cycle is dropped)
 
@@ -681,7 +698,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                     json.dump(verdict.as_json(), f)
                     f.write("\n")
             if paths is not None:
-                n_png = len(paths) * (2 if a.fields in FIELD_ORDERS else 1)
+                n_png = len(paths) * (per_file if a.fields in FIELD_ORDERS else 1)
                 if a.pulldown in FIELD_ORDERS:
                     n_png -= n_png // a.pulldown_cycle
                 try:
@@ -698,7 +715,7 @@ def main(argv: Optional[List[str]] = None) -> int:
             order, interlace, fps = None, film_tag, film_fps
         else:
             try:                                    # --fields and the input's I tag: the field order, the output's I tag and frame rate
-                order, interlace, fps, note = resolve_fields(a.fields, interlace if a.y4m_in else None, fps)
+                order, interlace, fps, note = resolve_fields(a.fields, interlace if a.y4m_in else None, fps, a.field_rate)
             except ValueError as e:
                 raise SystemExit(str(e)) from None
             if note is not None:
@@ -754,7 +771,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                            colour="bt601" if chroma == MONO else colour or "bt601",          # (grey-scale frames carry no colour space)
                            out_colour=None if out_chroma == MONO else out_colour, depth=depth, out_depth=out_depth, siting=siting, out_siting=out_siting,
                            chroma_filter=a.chroma_filter, crop=rect, bars=a.bars, fields=order, pulldown=film, pulldown_cycle=a.pulldown_cycle,
-                           dither=a.dither)
+                           dither=a.dither, **(dict(deinterlacer=a.deinterlacer, field_rate=a.field_rate) if order is not None else {}))
         done = 0
         try:
             for chunk in chunks:
@@ -784,7 +801,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     if a.dither is not None:
         scenes += f", dither {a.dither}"
     if order is not None:
-        scenes += f", fields {order}"
+        scenes += f", fields {order}" + (f" ({a.deinterlacer}, {a.field_rate} rate)" if (a.deinterlacer, a.field_rate) != ("yadif", "double") else "")
     if verdict is not None:
         scenes += f", scan {verdict.describe()}"
     if film is not None:

@@ -50,7 +50,7 @@ from .frames import (OUT_KINDS, PADDING_MODES, PIXEL_FORMATS, SAMPLE_FORMATS, YU
                      check_sitings, chroma_of, frame_layout, i420_layout, layout_of, luma_mode, video_spec)
 from .harness import window_indices
 from .packing import get_hw
-from .prepass import (FieldSplitter, PulldownRemover, ScanStats, _check_crop_args, _check_fields, _check_pulldown,  # noqa: F401  (re-exported)
+from .prepass import (FieldSplitter, PulldownRemover, ScanStats, _check_crop_args, _check_field_options, _check_fields, _check_pulldown,  # noqa: F401  (re-exported)
                       _check_scan, _crop_device, _cropped_spec, _deinterlace_device, _detect_device, _detect_scan_device, _field_frames,
                       _insert_device, _pair_sad_device, _pack_surface_device, _remove_pulldown_device, _to_device, _unpack_surface_device,
                       deinterlace, detect_active_area, detect_cuts, detect_scan, field_scores, field_stats, line_sums, make_stage,
@@ -94,7 +94,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
                   out_colour: Optional[str] = None, depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None,
                   out_siting: Optional[str] = None, chroma_filter: Optional[str] = None, crop=None, crop_limit=24,
                   bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None, pulldown_cycle: int = 5, *,
-                  surface=None, out_surface=None, scan: Optional[str] = None, dither: Optional[str] = None) -> torch.Tensor:
+                  surface=None, out_surface=None, scan: Optional[str] = None, dither: Optional[str] = None, deinterlacer: str = "yadif",
+                  field_rate: str = "double") -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
@@ -111,6 +112,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         shaped = frames
     if out_surface is not None:        # (its table: once the crop is checked, or found)
         surface_side(out_surface, spec.out, "out_surface")
+    # (deinterlacer= / field_rate= also go with scan="detect": they say how an interlaced verdict is carried out)
+    _check_field_options(deinterlacer, field_rate, fields, pulldown, scan is not None)
     if _check_scan(scan, fields, pulldown, pulldown_cycle) is not None:          # the content says what fields= / pulldown= would have said
         _field_frames(shaped, spec.inp, spec.size)
         _check_crop_args(crop, crop_limit, bars)          # (what does not depend on the verdict speaks before the GPU is touched)
@@ -120,9 +123,10 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
             frames, surface = _unpack_surface_device(frames, in_tab, spec.inp, spec.size), None
         found = _detect_scan_device(frames, spec.inp, spec.size).kwargs()
         fields, pulldown = found.get("fields"), found.get("pulldown")
-    if _check_fields(fields) is not None:          # everything below sees the progressive video of 2N frames
+    if _check_fields(fields) is not None:          # everything below sees the progressive video of 2N frames (field_rate "same": N)
         _field_frames(shaped, spec.inp, spec.size)
-        n *= 2
+        if field_rate != "same":
+            n *= 2
     if _check_pulldown(pulldown, pulldown_cycle, fields) is not None:          # everything below sees the film of N - N // cycle frames
         _field_frames(shaped, spec.inp, spec.size)
         n -= n // pulldown_cycle
@@ -145,7 +149,7 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     if surface is not None:            # the surface comes first of all: everything below sees planar frames
         frames = _unpack_surface_device(frames, in_tab, spec.inp, spec.size)
     if fields is not None:             # deinterlacing comes first, before the crop
-        frames = _deinterlace_device(frames, fields, spec.inp, spec.size)
+        frames = _deinterlace_device(frames, fields, spec.inp, spec.size, method=deinterlacer, rate=field_rate)
     if pulldown is not None:           # pulldown removal comes first, where deinterlacing comes
         frames = _remove_pulldown_device(frames, pulldown, spec.inp, spec.size, pulldown_cycle)[0]
     full = spec
@@ -202,7 +206,8 @@ class VideoUpscaler:
     fields="tff" / "bff": interlaced chunks, as in upscale_video, through a prepass.FieldSplitter: a source frame becomes two progressive
     frames once the frame after it has been pushed, so push() holds the last source frame back and finish() flushes it (at most two more
     source frames on the device between pushes).  The cuts, the crop and the windows operate on the progressive frames as they are
-    produced, and explicit cuts index them.
+    produced, and explicit cuts index them.  deinterlacer="bwdif" / field_rate="same" (keyword only): as in upscale_video; the same
+    source frame is held back for both, and with "same" a source frame becomes one progressive frame.
 
     pulldown="tff" / "bff", pulldown_cycle=5: telecined chunks, as in upscale_video, through a prepass.PulldownRemover: a pushed frame is
     woven at once, woven frames wait until their cycle is complete, and finish() flushes the partial last cycle whole (at most
@@ -223,7 +228,8 @@ class VideoUpscaler:
                  cuts: Union[None, str, Sequence[int]] = None, scene_threshold=10.0, colour: str = "bt601", out_colour: Optional[str] = None,
                  depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
                  chroma_filter: Optional[str] = None, crop=None, bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None,
-                 pulldown_cycle: int = 5, *, surface=None, out_surface=None, scan: Optional[str] = None, dither: Optional[str] = None):
+                 pulldown_cycle: int = 5, *, surface=None, out_surface=None, scan: Optional[str] = None, dither: Optional[str] = None,
+                 deinterlacer: str = "yadif", field_rate: str = "double"):
         _check_net(net)
         check_padding(padding)
         _check_scan(scan, fields, pulldown, pulldown_cycle, auto_ok=False)          # (None is the only value that passes: the path as it was)
@@ -240,7 +246,7 @@ class VideoUpscaler:
         self.spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter,
                                dither)
         self._full = self.spec                     # the spec of the chunks as pushed; `spec` becomes the cropped size's with a crop
-        self._split = make_stage(fields, pulldown, pulldown_cycle, self.spec.inp, self.spec.size)          # the stage in front; None: as it was
+        self._split = make_stage(fields, pulldown, pulldown_cycle, self.spec.inp, self.spec.size, deinterlacer, field_rate)          # the stage in front; None: as it was
         self._rect = _check_crop_args(crop, 24, bars, auto_ok=False)          # the rect to crop every chunk to; None: no crop, as it was
         self.bars = bars
         if self._rect is not None and self.spec.size:

@@ -10,7 +10,18 @@
             frames deinterlaced beforehand, in output frames per second, interleaved; savsr_amd.deinterlace's own time as a share of
             the call.
 
+  bwdif     the bwdif kernels beside the yadif ones through savsr_video_deinterlace_u8_m / _u16_m: one plane of 576 x 720 and of
+            1080 x 1920 at 8 and 10 bits, 7 frames, in the vector form and (from a pointer one sample off a 16-byte boundary) the
+            one-sample form, at the double and at the same rate.  The yadif kernel of the same form and rate is the yardstick, read
+            twice per round, and the spread of its two readings is the margin; microseconds per call and GB/s of the source bytes
+            once plus the output bytes.
+  fields    upscale_video(fields="tff") end to end on --frames interlaced uint8 frames of 180 x 320 for both deinterlacers and both
+            rates, interleaved, in output frames per second and milliseconds per call.
+  psnr      CPU only, from the numpy specifications: PSNR against the progressive truth of yadif and bwdif on the tests' moving zone
+            plate (output frames 2 .. 13) and on a static random picture.  Synthetic pictures, not footage.
+
     python3 tools/bench_deinterlace.py [--rounds 5 --launches 50 --frames 16 --scale 4 --out profiles/bench_deinterlace.json]
+    python3 tools/bench_deinterlace.py --only bwdif,fields,psnr --out profiles/bench_deinterlace_bwdif.json
 """
 import argparse
 import json
@@ -98,6 +109,50 @@ def time_kernels(dev, rounds, launches):
     return out
 
 
+def time_bwdif(dev, rounds, launches):
+    import torch
+    from savsr_amd import _lib
+    lib = _lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    n, out = N_FRAMES, []
+    for h, w in ((576, 720), (1080, 1920)):
+        for depth in (8, 10):
+            bps = 1 if depth == 8 else 2
+            fb = h * w * bps
+            src = torch.randint(0, 256 if depth == 8 else 4, (n * fb + 16,), dtype=torch.uint8, device=dev)          # (10 bits: high bytes 0 .. 3)
+            dst = torch.empty(2 * n * fb + 16, dtype=torch.uint8, device=dev)
+            assert src.data_ptr() % 16 == 0 and dst.data_ptr() % 16 == 0 and fb % 16 == 0
+            for form, off in (("vector", 0), ("one-sample", bps)):
+                for rate in (0, 1):
+                    def call(method):
+                        if depth == 8:
+                            return lambda: lib.savsr_video_deinterlace_u8_m(src.data_ptr() + off, n, fb, 0, h, w, 1, 0, 0, n, dst.data_ptr() + off, fb, 0,
+                                                                            method, rate, st)
+                        return lambda: lib.savsr_video_deinterlace_u16_m(src.data_ptr() + off, n, fb, 0, h, w, depth, 0, 0, n, dst.data_ptr() + off, fb, 0,
+                                                                         method, rate, st)
+                    yadif, bwdif = call(0), call(1)
+                    moved = (1 + (1 if rate else 2)) * n * fb
+                    _lib.check(yadif(), "yadif")
+                    _lib.check(bwdif(), "bwdif")
+                    torch.cuda.synchronize()
+                    new_us, old_us, margins = [], [], []
+                    for _ in range(rounds):
+                        a = timed(yadif, launches)
+                        x = timed(bwdif, launches)
+                        b = timed(yadif, launches)
+                        new_us.append(x)
+                        old_us += [a, b]
+                        margins.append(abs(a - b) / ((a + b) / 2))
+                    mn, mo = statistics.median(new_us), statistics.median(old_us)
+                    row = {"plane": [h, w], "depth": depth, "n": n, "form": form, "rate": ("double", "same")[rate], "bytes_moved": moved,
+                           "bwdif_us": round(mn, 2), "bwdif_gb_s": round(moved / mn / 1e3, 1), "bwdif_us_rounds": [round(v, 2) for v in new_us],
+                           "yadif_us": round(mo, 2), "yadif_gb_s": round(moved / mo / 1e3, 1), "yadif_us_readings": [round(v, 2) for v in old_us],
+                           "margin": round(max(margins), 4), "bwdif_vs_yadif_time": round(mn / mo, 4)}
+                    out.append(row)
+                    print(json.dumps(row), flush=True)
+    return out
+
+
 def interlaced(n, h=180, w=320, seed=0):
     """[n, h, w, 3] uint8 top-field-first frames: a smooth texture drifting one pixel per field."""
     import numpy as np
@@ -152,6 +207,59 @@ def time_end2end(dev, frames, scale, rounds):
     return res
 
 
+def time_fields(dev, frames, scale, rounds):
+    import torch
+    from savsr_amd.archs.savsr_arch import SAVSR
+    from savsr_amd.utils import synth
+    net = SAVSR()
+    net.load_state_dict(synth.synth_state_dict(synth.manifest_of(net.state_dict()), seed=0), strict=True)
+    net = net.to(dev).eval()
+    u8 = torch.from_numpy(interlaced(frames)).to(dev)
+    calls = {(m, r): (lambda m=m, r=r: net.upscale_video(u8, scale=scale, out="uint8", fields="tff", deinterlacer=m, field_rate=r))
+             for m in ("yadif", "bwdif") for r in ("double", "same")}
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        k = int(r.shape[0])
+        del r
+        return time.perf_counter() - t0, k
+    count = {k: wall(fn)[1] for k, fn in calls.items()}          # warm-up
+    t = {k: [] for k in calls}
+    for _ in range(rounds):
+        for k, fn in calls.items():
+            t[k].append(wall(fn)[0])
+    res = {"workload": f"{frames} interlaced frames 180x320 x{scale:g}, uint8 in and out, fields='tff'", "calls": []}
+    for (m, r), v in t.items():
+        med = statistics.median(v)
+        res["calls"].append({"deinterlacer": m, "field_rate": r, "frames_out": count[(m, r)], "ms": round(1e3 * med, 2),
+                             "fps_out": round(count[(m, r)] / med, 3), "ms_rounds": [round(1e3 * x, 2) for x in v]})
+    print(json.dumps(res), flush=True)
+    return res
+
+
+def synthetic_psnr():
+    """CPU: the numpy specifications on synthetic pictures against the progressive truth."""
+    import numpy as np
+    from savsr_amd.deinterlace import bwdif_matrix, deinterlace_matrix
+    from tests.bwdif_cases import psnr, zone_plate
+    res = {"note": "synthetic pictures from the numpy specifications, not footage"}
+    for order in ("tff", "bff"):
+        truth, woven = zone_plate(order)
+        res[f"zone_plate_{order}"] = {"yadif_db": round(psnr(deinterlace_matrix(woven, order)[0][2:14], truth[2:14]), 2),
+                                      "bwdif_db": round(psnr(bwdif_matrix(woven, order)[0][2:14], truth[2:14]), 2)}
+    pic = np.random.RandomState(3).randint(0, 256, size=(1, 64, 96))
+    still = np.repeat(pic, 3, 0)
+    want = np.repeat(pic, 6, 0)
+    b = psnr(bwdif_matrix(still, "tff")[0], want)
+    res["static_random_picture"] = {"yadif_db": round(psnr(deinterlace_matrix(still, "tff")[0], want), 2),
+                                    "bwdif_db": "exact" if b == float("inf") else round(b, 2)}
+    print(json.dumps(res), flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -161,14 +269,22 @@ def main():
     ap.add_argument("--only", default="kernels,end2end")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    import torch
-    dev = torch.device("cuda:0")
+    only = a.only.split(",")
     res = {"rounds": a.rounds, "launches": a.launches}
-    with torch.no_grad():
-        if "kernels" in a.only:
-            res["kernels"] = time_kernels(dev, a.rounds, a.launches)
-        if "end2end" in a.only:
-            res["end2end"] = time_end2end(dev, a.frames, a.scale, a.rounds)
+    if "psnr" in only:
+        res["psnr"] = synthetic_psnr()
+    if set(only) - {"psnr"}:
+        import torch
+        dev = torch.device("cuda:0")
+        with torch.no_grad():
+            if "kernels" in only:
+                res["kernels"] = time_kernels(dev, a.rounds, a.launches)
+            if "end2end" in only:
+                res["end2end"] = time_end2end(dev, a.frames, a.scale, a.rounds)
+            if "bwdif" in only:
+                res["bwdif"] = time_bwdif(dev, a.rounds, a.launches)
+            if "fields" in only:
+                res["fields"] = time_fields(dev, a.frames, a.scale, a.rounds)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
