@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 48
+#define SAVSR_ABI_VERSION 49
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -700,6 +700,33 @@ int savsr_video_field_scores_u16(const uint8_t* frames, int n_frames, int64_t fr
                                  int order, int from, int to, int64_t* out, void* stream);
 int savsr_video_weave(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes, int order, int from,
                       int to, const int32_t* delta, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
+
+/* (ABI 49) Residual combing after the match (combed= of savsr_amd.remove_pulldown, upscale_video and VideoUpscaler, savsr_amd.comb_windows,
+ * --combed of python -m savsr_amd.upscale; savsr_amd/pulldown.py `comb_windows` restates the measure, the kernels equal it bit for bit).
+ * savsr_video_comb_windows_u8:  matrices addressed and refused as for savsr_video_field_scores_u8, plus `step` (the samples of a pixel,
+ *                           1 .. 4: 1 for a plane, c for packed frames) and `threshold` (0 .. 255).  A sample (y, x) on a second-field
+ *                           row, 1 <= y <= rows - 2, is combed iff |a - b| + |c - b| - |a - c| > 2 * threshold, a / b / c = frame n at
+ *                           rows y - 1 / y / y + 1.  Cells of 8 rows x 8 * step samples anchored at (0, 0) count them; a window is
+ *                           2 x 2 cells, one at every cell origin, counting what lies inside the matrix.  out[2 (n - from)]: the
+ *                           largest window count of frame n, out[2 (n - from) + 1]: its total; zeros when rows < 3.  `out` is zeroed
+ *                           by one hipMemsetAsync on `stream` first; one launch; every grid shape gives the same integers.
+ * savsr_video_comb_windows_u16: the same on rows x cols little-endian 16-bit samples, each read as min(s, 2^depth - 1) >> (depth - 8);
+ *                           step 1.
+ * savsr_video_deinterlace_masked_u8 / _u16: the argument lists of savsr_video_deinterlace_u8_m / _u16_m without `rate`, plus `flags`, a
+ *                           DEVICE table of to - from int32: output frame n - from is the rate 1 ("same") result for source frame n
+ *                           where flags[n - from] != 0 and a byte copy of frame n elsewhere (the workgroups of an unflagged frame copy
+ *                           and do nothing else); neighbours are clamped among the resident frames.  Refused as the _m entries, and:
+ *                           null or misaligned flags, the source frames and the output overlapping. */
+int savsr_video_comb_windows_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes, int step,
+                                int order, int from, int to, int threshold, int64_t* out, void* stream);
+int savsr_video_comb_windows_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int depth,
+                                 int order, int from, int to, int threshold, int64_t* out, void* stream);
+int savsr_video_deinterlace_masked_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes,
+                                      int step, int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
+                                      int method, const int32_t* flags, void* stream);
+int savsr_video_deinterlace_masked_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int depth,
+                                       int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, int method,
+                                       const int32_t* flags, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 45) Video surfaces (surface.hip; savsr_amd.unpack_surface, savsr_amd.pack_surface, upscale_video(surface=..., out_surface=...),

@@ -283,7 +283,7 @@ class SAVSR(nn.Module):
                       chroma_filter: Optional[str] = None, crop=None, crop_limit=24, bars: str = "keep", fields: Optional[str] = None,
                       pulldown: Optional[str] = None, pulldown_cycle: int = 5, *, surface=None, out_surface=None,
                       scan: Optional[str] = None, dither: Optional[str] = None, deinterlacer: str = "yadif",
-                      field_rate: str = "double") -> torch.Tensor:
+                      field_rate: str = "double", combed: Optional[str] = None, comb_threshold: int = 9, comb_pixels: int = 40) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -380,12 +380,25 @@ class SAVSR(nn.Module):
         once per source frame; explicit cuts then index the N frames (a cut at source frame k is k).  The property holds with both:
         the result is upscale_video on savsr_amd.deinterlace(frames, fields, ..., method=deinterlacer, rate=field_rate).  Refused when
         not at their defaults without fields= or scan="detect", and together with pulldown=.  Not validated on real footage.
+        combed, comb_threshold, comb_pixels (keyword only): for hybrid material -- telecined film with video-rate inserts, titles or
+        effects, a stream cut inside a cadence.  combed: None (the default: what ran before), "yadif" or "bwdif".  After the field match
+        every woven frame is measured for residual combing (savsr_amd.comb_windows: a second-field sample is combed iff its match
+        measure exceeds 2 * comb_threshold; a frame is combed iff some 16 x 16 window, one every 8 rows and pixels, holds comb_pixels
+        of them); the combed frames alone are deinterlaced at same rate by that method, from the woven frames beside them, and the
+        decimation reads the cleaned frames (ffmpeg's fieldmatch -> yadif=deint=interlaced -> decimate chain).  The property holds: the
+        result is upscale_video on savsr_amd.remove_pulldown(frames, pulldown, ..., combed=combed, comb_threshold=..., comb_pixels=...).
+        Goes with pulldown= or scan="detect" (where it applies to a telecine verdict and is ignored for the others); refused with
+        fields=, and comb_threshold / comb_pixels are refused without combed=.  Still two host synchronisations.  What remains: the
+        decimation drops one of every pulldown_cycle frames of a true-video insert (judder, not combing); a cleaned frame has half its
+        rows interpolated; small or low-contrast combing stays below the rule; one verdict per video.  The defaults are fieldmatch's
+        cthresh and combpel rescaled to the window; they are not validated on footage.
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
         return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold, colour, out_colour, depth, out_depth,
                              siting, out_siting, chroma_filter, crop, crop_limit, bars, fields, pulldown, pulldown_cycle, surface=surface,
-                             out_surface=out_surface, scan=scan, dither=dither, deinterlacer=deinterlacer, field_rate=field_rate)
+                             out_surface=out_surface, scan=scan, dither=dither, deinterlacer=deinterlacer, field_rate=field_rate, combed=combed,
+                             comb_threshold=comb_threshold, comb_pixels=comb_pixels)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

@@ -142,6 +142,7 @@ struct Job {
     long long src_stride, dst_stride, pitch;
     int n_frames, from, rows, cols, order, top;          // cols: samples of a row; top: 2^depth - 1
     int same;                                            // 1: output frame o is field 0 of source frame from + o (rate "same")
+    const int32_t* flags;                                // masked entries (device, one per output frame of the launch): 0: copy the frame
 };
 
 // The rows and frames of output frame `o` of the launch and interpolated row index `ri`: false if there is no such row.
@@ -188,8 +189,16 @@ __device__ __forceinline__ int field(const uint32_t* w, int i, int top) {
 
 __device__ __forceinline__ u32x4 load16(const uint8_t* row, long long chunk) { return *(reinterpret_cast<const u32x4*>(row) + chunk); }
 
+// An unflagged frame of the masked entries: the lane's rows (its interpolated row, the kept row above, the last row below) as they are.
+__device__ __forceinline__ void copy_vec(const Job& jb, const Where& w, int chunk) {
+    const long long P = jb.pitch;
+    *(reinterpret_cast<u32x4*>(w.out + w.y * P) + chunk) = load16(w.cur + w.y * P, chunk);
+    if (w.y > 0) *(reinterpret_cast<u32x4*>(w.out + (w.y - 1) * P) + chunk) = load16(w.cur + (w.y - 1) * P, chunk);
+    if (w.y + 1 == jb.rows - 1) *(reinterpret_cast<u32x4*>(w.out + (w.y + 1) * P) + chunk) = load16(w.cur + (w.y + 1) * P, chunk);
+}
+
 // Vector form: lane = (interpolated row ri = tile + (tid >> 4), 16-byte chunk = tile + (tid & 15)).
-template <int BYTES, int STEP>
+template <int BYTES, int STEP, bool MASKED = false>
 __global__ __launch_bounds__(DI_THREADS) void deinterlace_vec_kernel(Job jb) {
     constexpr int SPL = 16 / BYTES;          // samples of a chunk
     const int chunks = (int)(jb.pitch >> 4);
@@ -197,6 +206,9 @@ __global__ __launch_bounds__(DI_THREADS) void deinterlace_vec_kernel(Job jb) {
     const int ri = (int)blockIdx.y * DI_TILE_IROWS + ((int)threadIdx.x >> 4);
     Where w;
     if (chunk >= chunks || !locate(jb, (int)blockIdx.z, ri, w)) return;
+    if constexpr (MASKED) {
+        if (!jb.flags[blockIdx.z]) { copy_vec(jb, w, chunk); return; }
+    }
     const long long P = jb.pitch;
     const int cl = chunk > 0 ? chunk - 1 : chunk, cr = chunk + 1 < chunks ? chunk + 1 : chunk;          // (clamped: read, never used, at the row's ends)
     uint32_t U[12], L[12];
@@ -261,13 +273,24 @@ __device__ __forceinline__ void put_at(uint8_t* row, int x, int v) {
     else reinterpret_cast<uint16_t*>(row)[x] = (uint16_t)v;
 }
 
-// One-sample form: lane = (interpolated row ri = tile + wave, sample x = tile + lane).
 template <int BYTES>
+__device__ __forceinline__ void copy_one(const Job& jb, const Where& w, int x) {
+    const long long P = jb.pitch;
+    put_at<BYTES>(w.out + w.y * P, x, raw_at<BYTES>(w.cur + w.y * P, x));
+    if (w.y > 0) put_at<BYTES>(w.out + (w.y - 1) * P, x, raw_at<BYTES>(w.cur + (w.y - 1) * P, x));
+    if (w.y + 1 == jb.rows - 1) put_at<BYTES>(w.out + (w.y + 1) * P, x, raw_at<BYTES>(w.cur + (w.y + 1) * P, x));
+}
+
+// One-sample form: lane = (interpolated row ri = tile + wave, sample x = tile + lane).
+template <int BYTES, bool MASKED = false>
 __global__ __launch_bounds__(DI_THREADS) void deinterlace_one_kernel(Job jb, int step) {
     const int x = (int)blockIdx.x * DI_ONE_COLS + ((int)threadIdx.x & 63);
     const int ri = (int)blockIdx.y * DI_ONE_IROWS + ((int)threadIdx.x >> 6);
     Where w;
     if (x >= jb.cols || !locate(jb, (int)blockIdx.z, ri, w)) return;
+    if constexpr (MASKED) {
+        if (!jb.flags[blockIdx.z]) { copy_one<BYTES>(jb, w, x); return; }
+    }
     const long long P = jb.pitch;
     const uint8_t *ru = w.cur + w.up * P, *rl = w.cur + w.dn * P;
     const bool edge = x - 3 * step >= 0 && x + 3 * step <= jb.cols - 1;
@@ -290,7 +313,7 @@ __global__ __launch_bounds__(DI_THREADS) void deinterlace_one_kernel(Job jb, int
 }
 
 // bwdif, vector form: the geometry of deinterlace_vec_kernel, 18 loads of the lane's own chunk.
-template <int BYTES>
+template <int BYTES, bool MASKED = false>
 __global__ __launch_bounds__(DI_THREADS) void bwdif_vec_kernel(Job jb) {
     constexpr int SPL = 16 / BYTES;
     const int chunks = (int)(jb.pitch >> 4);
@@ -298,6 +321,9 @@ __global__ __launch_bounds__(DI_THREADS) void bwdif_vec_kernel(Job jb) {
     const int ri = (int)blockIdx.y * DI_TILE_IROWS + ((int)threadIdx.x >> 4);
     Where w;
     if (chunk >= chunks || !locate(jb, (int)blockIdx.z, ri, w)) return;
+    if constexpr (MASKED) {
+        if (!jb.flags[blockIdx.z]) { copy_vec(jb, w, chunk); return; }
+    }
     const long long P = jb.pitch;
     uint32_t Q[18][4];
     {
@@ -341,12 +367,15 @@ __global__ __launch_bounds__(DI_THREADS) void bwdif_vec_kernel(Job jb) {
 }
 
 // bwdif, one-sample form: the geometry of deinterlace_one_kernel.
-template <int BYTES>
+template <int BYTES, bool MASKED = false>
 __global__ __launch_bounds__(DI_THREADS) void bwdif_one_kernel(Job jb) {
     const int x = (int)blockIdx.x * DI_ONE_COLS + ((int)threadIdx.x & 63);
     const int ri = (int)blockIdx.y * DI_ONE_IROWS + ((int)threadIdx.x >> 6);
     Where w;
     if (x >= jb.cols || !locate(jb, (int)blockIdx.z, ri, w)) return;
+    if constexpr (MASKED) {
+        if (!jb.flags[blockIdx.z]) { copy_one<BYTES>(jb, w, x); return; }
+    }
     const long long P = jb.pitch;
     const int cu = raw_at<BYTES>(w.cur + w.up * P, x), cl = raw_at<BYTES>(w.cur + w.dn * P, x);          // (unclipped: the kept rows' copies)
     BTaps t;
@@ -365,7 +394,8 @@ __global__ __launch_bounds__(DI_THREADS) void bwdif_one_kernel(Job jb) {
 }
 
 // n_out output frames of source frames jb.from ...: two per source frame, or one with jb.same.  method 0: yadif, 1: bwdif.
-template <int BYTES>
+// MASKED: jb.flags has one entry per output frame (jb.same is 1); the workgroups of a frame whose entry is 0 copy it.
+template <int BYTES, bool MASKED = false>
 int launch_deinterlace(Job jb, int step, int n_out, hipStream_t st, int method = 0) {
     const bool vec = ((reinterpret_cast<uintptr_t>(jb.src) | reinterpret_cast<uintptr_t>(jb.dst)) & 15) == 0 && jb.src_stride % 16 == 0 &&
                      jb.dst_stride % 16 == 0 && jb.pitch % 16 == 0;
@@ -375,27 +405,28 @@ int launch_deinterlace(Job jb, int step, int n_out, hipStream_t st, int method =
         Job part = jb;
         part.from = jb.from + (jb.same ? o0 : o0 / 2);
         part.dst = jb.dst + (long long)o0 * jb.dst_stride;
+        if (MASKED) part.flags = jb.flags + o0;
         if (method == 1) {
             if (vec) {
                 const dim3 grid((unsigned)((jb.pitch + DI_TILE_BYTES - 1) / DI_TILE_BYTES), (unsigned)((irows + DI_TILE_IROWS - 1) / DI_TILE_IROWS), (unsigned)no);
-                hipLaunchKernelGGL((bwdif_vec_kernel<BYTES>), grid, dim3(DI_THREADS), 0, st, part);
+                hipLaunchKernelGGL((bwdif_vec_kernel<BYTES, MASKED>), grid, dim3(DI_THREADS), 0, st, part);
             } else {
                 const dim3 grid((unsigned)((jb.cols + DI_ONE_COLS - 1) / DI_ONE_COLS), (unsigned)((irows + DI_ONE_IROWS - 1) / DI_ONE_IROWS), (unsigned)no);
-                hipLaunchKernelGGL((bwdif_one_kernel<BYTES>), grid, dim3(DI_THREADS), 0, st, part);
+                hipLaunchKernelGGL((bwdif_one_kernel<BYTES, MASKED>), grid, dim3(DI_THREADS), 0, st, part);
             }
             if (int rc = check_launch(vec ? "bwdif_vec_kernel" : "bwdif_one_kernel")) return rc;
             continue;
         }
         if (vec) {
             const dim3 grid((unsigned)((jb.pitch + DI_TILE_BYTES - 1) / DI_TILE_BYTES), (unsigned)((irows + DI_TILE_IROWS - 1) / DI_TILE_IROWS), (unsigned)no);
-            if (BYTES == 2) hipLaunchKernelGGL((deinterlace_vec_kernel<2, 1>), grid, dim3(DI_THREADS), 0, st, part);
-            else if (step == 1) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 1>), grid, dim3(DI_THREADS), 0, st, part);
-            else if (step == 2) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 2>), grid, dim3(DI_THREADS), 0, st, part);
-            else if (step == 3) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 3>), grid, dim3(DI_THREADS), 0, st, part);
-            else hipLaunchKernelGGL((deinterlace_vec_kernel<1, 4>), grid, dim3(DI_THREADS), 0, st, part);
+            if (BYTES == 2) hipLaunchKernelGGL((deinterlace_vec_kernel<2, 1, MASKED>), grid, dim3(DI_THREADS), 0, st, part);
+            else if (step == 1) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 1, MASKED>), grid, dim3(DI_THREADS), 0, st, part);
+            else if (step == 2) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 2, MASKED>), grid, dim3(DI_THREADS), 0, st, part);
+            else if (step == 3) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 3, MASKED>), grid, dim3(DI_THREADS), 0, st, part);
+            else hipLaunchKernelGGL((deinterlace_vec_kernel<1, 4, MASKED>), grid, dim3(DI_THREADS), 0, st, part);
         } else {
             const dim3 grid((unsigned)((jb.cols + DI_ONE_COLS - 1) / DI_ONE_COLS), (unsigned)((irows + DI_ONE_IROWS - 1) / DI_ONE_IROWS), (unsigned)no);
-            hipLaunchKernelGGL((deinterlace_one_kernel<BYTES>), grid, dim3(DI_THREADS), 0, st, part, step);
+            hipLaunchKernelGGL((deinterlace_one_kernel<BYTES, MASKED>), grid, dim3(DI_THREADS), 0, st, part, step);
         }
         if (int rc = check_launch(vec ? "deinterlace_vec_kernel" : "deinterlace_one_kernel")) return rc;
     }
@@ -434,7 +465,7 @@ extern "C" int savsr_video_deinterlace_u8(const uint8_t* frames, int n_frames, i
                                    out_frame_bytes, out_plane_offset))
         return rc;
     if (step < 1 || step > 4 || row_bytes % step) return fail_arg("video_deinterlace_u8: step 1 .. 4 and a divisor of row_bytes");
-    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, row_bytes, order, 255, 0};
+    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, row_bytes, order, 255, 0, nullptr};
     return launch_deinterlace<1>(jb, step, 2 * (to - from), static_cast<hipStream_t>(stream));
 }
 
@@ -447,7 +478,7 @@ extern "C" int savsr_video_deinterlace_u8_m(const uint8_t* frames, int n_frames,
     if (step < 1 || step > 4 || row_bytes % step) return fail_arg("video_deinterlace_u8_m: step 1 .. 4 and a divisor of row_bytes");
     if (method != 0 && method != 1) return fail_arg("video_deinterlace_u8_m: method 0 (yadif) or 1 (bwdif)");
     if (rate != 0 && rate != 1) return fail_arg("video_deinterlace_u8_m: rate 0 (double) or 1 (same)");
-    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, row_bytes, order, 255, rate};
+    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, row_bytes, order, 255, rate, nullptr};
     return launch_deinterlace<1>(jb, step, (rate ? 1 : 2) * (to - from), static_cast<hipStream_t>(stream), method);
 }
 
@@ -460,7 +491,7 @@ extern "C" int savsr_video_deinterlace_u16(const uint8_t* frames, int n_frames, 
     if (depth != 10 && depth != 12) return fail_arg("video_deinterlace_u16: depth 10 or 12 (8 bits: savsr_video_deinterlace_u8)");
     if (((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(out)) & 1) || ((frame_bytes | plane_offset | out_frame_bytes | out_plane_offset) & 1))
         return fail_arg("video_deinterlace_u16: frames, out, the frame strides and the plane offsets must be 2-byte aligned (16-bit samples)");
-    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, 2ll * cols, n_frames, from, rows, cols, order, (1 << depth) - 1, 0};
+    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, 2ll * cols, n_frames, from, rows, cols, order, (1 << depth) - 1, 0, nullptr};
     return launch_deinterlace<2>(jb, 1, 2 * (to - from), static_cast<hipStream_t>(stream));
 }
 
@@ -475,6 +506,54 @@ extern "C" int savsr_video_deinterlace_u16_m(const uint8_t* frames, int n_frames
         return fail_arg("video_deinterlace_u16_m: frames, out, the frame strides and the plane offsets must be 2-byte aligned (16-bit samples)");
     if (method != 0 && method != 1) return fail_arg("video_deinterlace_u16_m: method 0 (yadif) or 1 (bwdif)");
     if (rate != 0 && rate != 1) return fail_arg("video_deinterlace_u16_m: rate 0 (double) or 1 (same)");
-    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, 2ll * cols, n_frames, from, rows, cols, order, (1 << depth) - 1, rate};
+    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, 2ll * cols, n_frames, from, rows, cols, order, (1 << depth) - 1, rate, nullptr};
     return launch_deinterlace<2>(jb, 1, (rate ? 1 : 2) * (to - from), static_cast<hipStream_t>(stream), method);
+}
+
+// (ABI 49) The masked entries: rate 1 ("same") for the frames whose flag is set, a byte copy of the others (the workgroups of an unflagged
+// frame copy their rows and do nothing else); the flags are a device table the entry cannot see.  Behind the pulldown removal's combed=.
+namespace savsr {
+namespace {
+
+int check_masked(const char* who, const uint8_t* frames, const uint8_t* out, int n_frames, int64_t frame_bytes, int from, int to, int64_t out_frame_bytes,
+                 int method, const int32_t* flags) {
+    char msg[160];
+    const char* why = nullptr;
+    if (!flags) why = "null pointer";
+    else if (reinterpret_cast<uintptr_t>(flags) & 3) why = "flags must be 4-byte aligned";
+    else if (method != 0 && method != 1) why = "method 0 (yadif) or 1 (bwdif)";
+    else if (out < frames + (int64_t)n_frames * frame_bytes && frames < out + (int64_t)(to - from) * out_frame_bytes) why = "the source frames and the output overlap";
+    if (!why) return 0;
+    snprintf(msg, sizeof msg, "%s: %s", who, why);
+    return fail_arg(msg);
+}
+
+}  // namespace
+}  // namespace savsr
+
+extern "C" int savsr_video_deinterlace_masked_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes,
+                                                 int step, int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
+                                                 int method, const int32_t* flags, void* stream) {
+    const char* who = "video_deinterlace_masked_u8";
+    if (int rc = check_deinterlace(who, frames, out, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to, out_frame_bytes, out_plane_offset))
+        return rc;
+    if (step < 1 || step > 4 || row_bytes % step) return fail_arg("video_deinterlace_masked_u8: step 1 .. 4 and a divisor of row_bytes");
+    if (int rc = check_masked(who, frames, out, n_frames, frame_bytes, from, to, out_frame_bytes, method, flags)) return rc;
+    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, row_bytes, order, 255, 1, flags};
+    return launch_deinterlace<1, true>(jb, step, to - from, static_cast<hipStream_t>(stream), method);
+}
+
+extern "C" int savsr_video_deinterlace_masked_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols,
+                                                  int depth, int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
+                                                  int method, const int32_t* flags, void* stream) {
+    const char* who = "video_deinterlace_masked_u16";
+    if (int rc = check_deinterlace(who, frames, out, n_frames, frame_bytes, plane_offset, rows, 2 * (int64_t)cols, order, from, to, out_frame_bytes,
+                                   out_plane_offset))
+        return rc;
+    if (depth != 10 && depth != 12) return fail_arg("video_deinterlace_masked_u16: depth 10 or 12 (8 bits: savsr_video_deinterlace_masked_u8)");
+    if (((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(out)) & 1) || ((frame_bytes | plane_offset | out_frame_bytes | out_plane_offset) & 1))
+        return fail_arg("video_deinterlace_masked_u16: frames, out, the frame strides and the plane offsets must be 2-byte aligned (16-bit samples)");
+    if (int rc = check_masked(who, frames, out, n_frames, frame_bytes, from, to, out_frame_bytes, method, flags)) return rc;
+    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, 2ll * cols, n_frames, from, rows, cols, order, (1 << depth) - 1, 1, flags};
+    return launch_deinterlace<2, true>(jb, 1, to - from, static_cast<hipStream_t>(stream), method);
 }

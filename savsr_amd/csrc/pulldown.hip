@@ -20,6 +20,8 @@
 // Weave.  Output frame o of source frame n = from + o: the rows of parity p from frame n, the others from frame clamp(n + delta[o], 0,
 // n_frames - 1); delta is a device table the entry cannot see, so the kernel clamps.  A byte copy at every depth: a 16-byte form and a
 // byte form, one launch per plane.
+//
+// (ABI 49) Comb windows: the residual combing of woven frames, behind combed= (`comb_windows` is the specification); see the section below.
 #include "common.hpp"
 #include "video_samples.hpp"
 
@@ -209,6 +211,180 @@ __global__ __launch_bounds__(PD_THREADS) void weave_one_kernel(WeaveJob jb) {
     }
 }
 
+// ---- residual combing after the match (ABI 49; `comb_windows` is the specification) ---------------------------------------------------------
+// A sample on a second-field row is combed iff its match measure exceeds 2 * threshold; cells of 8 rows x 8 pixels count them; a window is
+// 2 x 2 cells, one at every cell origin; per frame the largest window count and the total.  A workgroup owns a tile of CW_TR x tc cells
+// (the origins of its windows) and reads one more cell row below and one more cell column to the right, so every window's four cells are
+// counted by the workgroup that sums it and no cell count crosses workgroups.  Lanes walk the tile's second-field rows (vector form: 16
+// bytes of a row and its two vertical neighbours, three loads; a chunk meets at most two cells, so two LDS adds per lane and row piece;
+// one-sample form: one sample, one LDS add where it is combed), then the window sums are taken from the LDS cells, reduced over the
+// workgroup, and one 64-bit atomicMax and one 64-bit atomicAdd per workgroup go to the frame's two cells.  Counts are exact integers and
+// max / + commute, so the grid shape changes nothing.
+constexpr int CW_CELL = 8;                 // rows and pixels of a cell
+constexpr int CW_TR = 8;                   // cell rows of a tile: 64 rows of the matrix, 72 with the halo
+constexpr int CW_TILE_BYTES = 512;         // bytes of a tile's row (without the halo cell)
+constexpr int CW_MAX_TC = CW_TILE_BYTES / CW_CELL;          // cell columns of a tile: at most 64 (8-byte cells)
+constexpr int CW_LROWS = (CW_TR + 1) * CW_CELL / 2;         // second-field rows of a tile with its halo
+
+struct CombJob {
+    const uint8_t* src;          // the matrix of resident frame 0
+    long long stride, pitch;     // bytes between frames / rows
+    int from, rows, cols;        // cols: samples of a row
+    int q;                       // the second field's parity
+    int cell_w;                  // samples of a cell's row: 8 * step
+    int ncr, ncc;                // cell rows / columns of the matrix
+    int tc, tiles_x;             // cell columns of a tile; tiles of a cell row
+    uint32_t top;                // 2^depth - 1
+    int shift;                   // depth - 8
+    uint32_t thresh2;            // 2 * threshold
+};
+
+__device__ __forceinline__ bool pd_combed(uint32_t a, uint32_t b, uint32_t c, uint32_t thresh2) {
+    return absdiff(a, b) + absdiff(c, b) - absdiff(a, c) > thresh2;
+}
+
+typedef uint32_t CombCells[CW_TR + 1][CW_MAX_TC + 1];
+
+// Lane `tid`'s share of tile (tx, ty) of frame n: combed counts into the tile's cells (LDS adds).
+template <int BYTES, bool VEC>
+__device__ __forceinline__ void comb_count(const CombJob& jb, int tx, int ty, int n, uint32_t tid, CombCells& cells) {
+    const uint8_t* cur = jb.src + (long long)n * jb.stride;
+    const int cc0 = tx * jb.tc;                                   // the tile's first cell column
+    const int x0 = cc0 * jb.cell_w;                               // its first sample and the one past its last (halo included)
+    const int x1 = min(x0 + (jb.tc + 1) * jb.cell_w, jb.cols);
+    const int yt = ty * CW_TR * CW_CELL;                          // its first row (even, so local parities are the matrix's)
+    if constexpr (VEC) {
+        constexpr int SPL = 16 / BYTES;                           // samples of a chunk
+        const int c0 = x0 / SPL, nch = (x1 + SPL - 1) / SPL - c0; // the chunks that meet the tile (the row is whole chunks: pitch % 16 == 0)
+        for (uint32_t u = tid; u < (uint32_t)(CW_LROWS * nch); u += PD_THREADS) {
+            const int lr = (int)(u / (uint32_t)nch), chunk = c0 + (int)(u - (uint32_t)lr * (uint32_t)nch);
+            const int y = yt + 2 * lr + jb.q;
+            if (y < 1 || y > jb.rows - 2) continue;
+            const uint8_t* row = cur + (long long)y * jb.pitch;
+            const u32x4 a = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row - jb.pitch) + chunk);
+            const u32x4 b = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row) + chunk);
+            const u32x4 c = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row + jb.pitch) + chunk);
+            uint32_t mask = 0;                                    // bit i: sample i of the chunk is combed
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if constexpr (BYTES == 1) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        mask |= (uint32_t)pd_combed((a[e] >> (8 * k)) & 255u, (b[e] >> (8 * k)) & 255u, (c[e] >> (8 * k)) & 255u, jb.thresh2) << (4 * e + k);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 2; ++k)
+                        mask |= (uint32_t)pd_combed(msb8((a[e] >> (16 * k)) & 0xffffu, jb.top, jb.shift), msb8((b[e] >> (16 * k)) & 0xffffu, jb.top, jb.shift),
+                                                    msb8((c[e] >> (16 * k)) & 0xffffu, jb.top, jb.shift), jb.thresh2) << (2 * e + k);
+                }
+            }
+            const int xs = chunk * SPL;                           // the chunk's samples [xs, xs + SPL) lie in cell columns ca and ca + 1
+            const int ca = xs / jb.cell_w;
+            const int na = min((ca + 1) * jb.cell_w - xs, SPL);   // how many of them in ca
+            const uint32_t in_a = __builtin_popcount(mask & ((1u << na) - 1u)), in_b = __builtin_popcount(mask >> na);
+            const int la = ca - cc0;                              // (cells outside the tile with its halo: another tile's)
+            if (in_a && la >= 0 && la <= jb.tc) atomicAdd(&cells[lr >> 2][la], in_a);
+            if (in_b && la + 1 >= 0 && la + 1 <= jb.tc) atomicAdd(&cells[lr >> 2][la + 1], in_b);
+        }
+    } else {
+        const int ns = x1 - x0;
+        for (uint32_t u = tid; u < (uint32_t)(CW_LROWS * ns); u += PD_THREADS) {
+            const int lr = (int)(u / (uint32_t)ns), x = x0 + (int)(u - (uint32_t)lr * (uint32_t)ns);
+            const int y = yt + 2 * lr + jb.q;
+            if (y < 1 || y > jb.rows - 2) continue;
+            const uint8_t* row = cur + (long long)y * jb.pitch;
+            if (pd_combed(pd_sample<BYTES>(row - jb.pitch, (uint32_t)x, jb.top, jb.shift), pd_sample<BYTES>(row, (uint32_t)x, jb.top, jb.shift),
+                          pd_sample<BYTES>(row + jb.pitch, (uint32_t)x, jb.top, jb.shift), jb.thresh2))
+                atomicAdd(&cells[lr >> 2][x / jb.cell_w - cc0], 1u);
+        }
+    }
+}
+
+// Lane `tid`'s windows of tile (tx, ty): the largest window sum into mx, the tile's own cells (not the halo's) into total.
+__device__ __forceinline__ void comb_sum(const CombJob& jb, int tx, int ty, uint32_t tid, const CombCells& cells, uint32_t& mx, uint32_t& total) {
+    for (uint32_t u = tid; u < (uint32_t)(CW_TR * jb.tc); u += PD_THREADS) {
+        const int i = (int)(u / (uint32_t)jb.tc), j = (int)(u - (uint32_t)i * (uint32_t)jb.tc);
+        if (ty * CW_TR + i >= jb.ncr || tx * jb.tc + j >= jb.ncc) continue;          // (no such cell: no window)
+        const uint32_t own = cells[i][j];
+        total += own;
+        mx = max(mx, own + cells[i + 1][j] + cells[i][j + 1] + cells[i + 1][j + 1]);  // (cells past the matrix hold 0)
+    }
+}
+
+// Tile blockIdx.x = ty * tiles_x + tx of frame blockIdx.y of the launch.
+template <int BYTES, bool VEC>
+__global__ __launch_bounds__(PD_THREADS) void comb_windows_kernel(CombJob jb, unsigned long long* __restrict__ out) {
+    const int ty = (int)(blockIdx.x / (uint32_t)jb.tiles_x), tx = (int)(blockIdx.x - (uint32_t)ty * (uint32_t)jb.tiles_x);
+    const int n = jb.from + (int)blockIdx.y;
+    unsigned long long* cell = out + 2 * blockIdx.y;
+    uint32_t mx = 0, total = 0;
+#ifdef SAVSR_HOST_CHECK          // the host check runs one thread at a time: the first clears the cells, the last sums every lane's windows
+    static CombCells cells;
+    if (threadIdx.x == 0) memset(cells, 0, sizeof cells);
+    comb_count<BYTES, VEC>(jb, tx, ty, n, threadIdx.x, cells);
+    if (threadIdx.x + 1 < PD_THREADS) return;
+    for (uint32_t t = 0; t < PD_THREADS; ++t) comb_sum(jb, tx, ty, t, cells, mx, total);
+    if (mx) atomicMax(cell, (unsigned long long)mx);
+    if (total) atomicAdd(cell + 1, (unsigned long long)total);
+#else
+    __shared__ CombCells cells;
+    __shared__ uint32_t part[2][PD_THREADS / 64];
+    for (uint32_t i = threadIdx.x; i < (CW_TR + 1) * (CW_MAX_TC + 1); i += PD_THREADS) (&cells[0][0])[i] = 0u;
+    __syncthreads();
+    comb_count<BYTES, VEC>(jb, tx, ty, n, threadIdx.x, cells);
+    __syncthreads();
+    comb_sum(jb, tx, ty, threadIdx.x, cells, mx, total);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        mx = max(mx, (uint32_t)__shfl_xor(mx, o, 64));
+        total += __shfl_xor(total, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        part[0][threadIdx.x >> 6] = mx;
+        part[1][threadIdx.x >> 6] = total;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long m = 0, s = 0;
+#pragma unroll
+        for (int i = 0; i < PD_THREADS / 64; ++i) {
+            m = max(m, (unsigned long long)part[0][i]);
+            s += part[1][i];
+        }
+        if (m) atomicMax(cell, m);
+        if (s) atomicAdd(cell + 1, s);
+    }
+#endif
+}
+
+template <int BYTES>
+int launch_comb(CombJob jb, int n_out, int64_t* out, hipStream_t st, const char* what) {
+    hipError_t e = hipMemsetAsync(out, 0, sizeof(int64_t) * 2 * (size_t)n_out, st);
+    if (e != hipSuccess) { set_error("%s: hipMemsetAsync failed: %s", what, hipGetErrorString(e)); return (int)e; }
+    if (jb.rows < 3) return 0;          // no second-field row between two others: zeros
+    const bool vec = (reinterpret_cast<uintptr_t>(jb.src) & 15) == 0 && jb.stride % 16 == 0 && jb.pitch % 16 == 0;
+    const unsigned gx = (unsigned)jb.tiles_x * (unsigned)((jb.ncr + CW_TR - 1) / CW_TR);
+    for (int f0 = 0; f0 < n_out; f0 += PD_MAX_Y) {
+        const int nf = n_out - f0 < PD_MAX_Y ? n_out - f0 : PD_MAX_Y;
+        CombJob part = jb;
+        part.from = jb.from + f0;
+        unsigned long long* cells = reinterpret_cast<unsigned long long*>(out) + 2ll * f0;
+        if (vec) hipLaunchKernelGGL((comb_windows_kernel<BYTES, true>), dim3(gx, (unsigned)nf), dim3(PD_THREADS), 0, st, part, cells);
+        else hipLaunchKernelGGL((comb_windows_kernel<BYTES, false>), dim3(gx, (unsigned)nf), dim3(PD_THREADS), 0, st, part, cells);
+        if (int rc = check_launch("comb_windows_kernel")) return rc;
+    }
+    return 0;
+}
+
+// bytes: of a sample; step: the samples of a pixel.
+CombJob comb_job(const uint8_t* frames, int64_t frame_bytes, int64_t plane_offset, int from, int rows, int64_t row_bytes, int cols, int bytes, int step,
+                 int order, int depth, int threshold) {
+    const int cell_w = CW_CELL * step, tc = CW_TILE_BYTES / (cell_w * bytes);
+    const int ncr = (rows + CW_CELL - 1) / CW_CELL, ncc = (cols + cell_w - 1) / cell_w;
+    return CombJob{frames + plane_offset, frame_bytes, row_bytes, from, rows, cols, 1 - order, cell_w, ncr, ncc, tc, (ncc + tc - 1) / tc,
+                   (1u << depth) - 1u, depth - 8, 2u * (uint32_t)threshold};
+}
+
 // The checks of a matrix inside resident frames; nullptr or the reason.
 const char* check_matrix(const void* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int64_t row_bytes, int order, int from,
                          int to) {
@@ -264,6 +440,34 @@ extern "C" int savsr_video_field_scores_u16(const uint8_t* frames, int n_frames,
     if (to == from) return 0;
     return launch_scores<2>(score_job(frames, frame_bytes, plane_offset, n_frames, from, rows, 2 * (int64_t)cols, cols, order, depth), to - from, out,
                             static_cast<hipStream_t>(stream), who);
+}
+
+extern "C" int savsr_video_comb_windows_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes,
+                                           int step, int order, int from, int to, int threshold, int64_t* out, void* stream) {
+    const char* who = "video_comb_windows_u8";
+    if (const char* why = check_matrix(frames, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to)) return refuse(who, why);
+    if (step < 1 || step > 4) return refuse(who, "step 1 .. 4");
+    if (threshold < 0 || threshold > 255) return refuse(who, "threshold 0 .. 255");
+    if (!out && to > from) return refuse(who, "null pointer");
+    if (reinterpret_cast<uintptr_t>(out) & 7) return refuse(who, "out must be 8-byte aligned");
+    if (to == from) return 0;
+    return launch_comb<1>(comb_job(frames, frame_bytes, plane_offset, from, rows, row_bytes, row_bytes, 1, step, order, 8, threshold), to - from, out,
+                          static_cast<hipStream_t>(stream), who);
+}
+
+extern "C" int savsr_video_comb_windows_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols,
+                                            int depth, int order, int from, int to, int threshold, int64_t* out, void* stream) {
+    const char* who = "video_comb_windows_u16";
+    if (const char* why = check_matrix(frames, n_frames, frame_bytes, plane_offset, rows, 2 * (int64_t)cols, order, from, to)) return refuse(who, why);
+    if (depth != 10 && depth != 12) return refuse(who, "depth 10 or 12 (8 bits: savsr_video_comb_windows_u8)");
+    if ((reinterpret_cast<uintptr_t>(frames) & 1) || ((frame_bytes | plane_offset) & 1))
+        return refuse(who, "frames, the frame stride and the plane offset must be 2-byte aligned (16-bit samples)");
+    if (threshold < 0 || threshold > 255) return refuse(who, "threshold 0 .. 255");
+    if (!out && to > from) return refuse(who, "null pointer");
+    if (reinterpret_cast<uintptr_t>(out) & 7) return refuse(who, "out must be 8-byte aligned");
+    if (to == from) return 0;
+    return launch_comb<2>(comb_job(frames, frame_bytes, plane_offset, from, rows, 2 * (int64_t)cols, cols, 2, 1, order, depth, threshold), to - from, out,
+                          static_cast<hipStream_t>(stream), who);
 }
 
 extern "C" int savsr_video_weave(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes, int order,

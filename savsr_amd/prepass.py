@@ -495,6 +495,85 @@ def _weave_device(frames: torch.Tensor, order: str, delta: torch.Tensor, side: S
     return out
 
 
+def _comb_windows_device(frames: torch.Tensor, order: str, side: Side, size: Size, threshold: int = pd.DEFAULT_COMB_THRESHOLD, lo: int = 0,
+                         hi: Optional[int] = None) -> torch.Tensor:
+    """savsr_video_comb_windows_* on resident frames of the input side on the GPU: int64 [hi - lo, 2] there for frames [lo, hi) (default:
+    all): the largest window count and the total of combed samples; enqueued on the current stream (no sync).  Every byte of packed
+    frames with their channel count as the pixel step, the Y plane of planar ones."""
+    from . import _lib
+    frames, n, hi, c, tab, oid = _field_job(frames, order, side, size, hi)
+    lib = _lib.load()
+    with torch.cuda.device(frames.device):
+        out = torch.empty(max(hi - lo, 0), 2, dtype=torch.int64, device=frames.device)
+        if hi <= lo:
+            return out
+        st = torch.cuda.current_stream().cuda_stream
+        y = tab.planes[0]
+        if tab.sample == 1:
+            _lib.check(lib.savsr_video_comb_windows_u8(frames.data_ptr(), n, tab.stride, y.offset, y.rows, y.row_bytes, max(c, 1), oid, lo, hi, threshold,
+                                                       out.data_ptr(), st), "savsr_video_comb_windows_u8")
+        else:
+            _lib.check(lib.savsr_video_comb_windows_u16(frames.data_ptr(), n, tab.stride, y.offset, y.rows, y.row_bytes // 2, side.depth, oid, lo, hi,
+                                                        threshold, out.data_ptr(), st), "savsr_video_comb_windows_u16")
+    return out
+
+
+def _deinterlace_masked_device(frames: torch.Tensor, order: str, flags: torch.Tensor, method: str, side: Side, size: Size, lo: int = 0,
+                               hi: Optional[int] = None) -> torch.Tensor:
+    """savsr_video_deinterlace_masked_* on resident frames of the input side on the GPU: hi - lo frames, frame n - lo the same-rate
+    deinterlaced frame n where the device table flags (int32 [hi - lo]) is not 0 and a copy of frame n elsewhere; prev / next among the
+    resident frames and clamped there.  One call per plane, on the current stream."""
+    from . import _lib
+    mid = DEINTERLACERS.index(method)
+    frames, n, hi, c, tab, oid = _field_job(frames, order, side, size, hi)
+    out = frames.new_empty((max(hi - lo, 0),) + tuple(frames.shape[1:]))
+    if hi <= lo:
+        return out
+    if flags.dtype != torch.int32 or flags.device != frames.device or flags.numel() != hi - lo or not flags.is_contiguous():
+        raise ValueError(f"flags must be {hi - lo} contiguous int32 on {frames.device}, got {flags.dtype} {tuple(flags.shape)} on {flags.device}")
+    lib = _lib.load()
+    with torch.cuda.device(frames.device):
+        st = torch.cuda.current_stream().cuda_stream
+        for p in tab.planes:
+            if tab.sample == 1:
+                _lib.check(lib.savsr_video_deinterlace_masked_u8(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes, max(c, 1), oid, lo, hi,
+                                                                 out.data_ptr(), tab.stride, p.offset, mid, flags.data_ptr(), st),
+                           "savsr_video_deinterlace_masked_u8")
+            else:
+                _lib.check(lib.savsr_video_deinterlace_masked_u16(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes // 2, side.depth, oid, lo,
+                                                                  hi, out.data_ptr(), tab.stride, p.offset, mid, flags.data_ptr(), st),
+                           "savsr_video_deinterlace_masked_u16")
+    return out
+
+
+def _comb_step(frames: torch.Tensor, side: Side, size: Size) -> int:
+    """The samples of a pixel in the matrix the comb measure reads: the channels of packed frames, 1 for planar ones."""
+    return max(_field_frames(frames, side, size)[1], 1)
+
+
+def _clean_combed_device(frames: torch.Tensor, order: str, method: str, threshold: int, pixels: int, side: Side, size: Size, lo: int = 0,
+                         hi: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """pulldown.clean_combed on resident woven frames on the GPU, frames [lo, hi): (the cleaned frames, their comb table int64 [hi - lo, 2]
+    on the device).  The flags never leave the device: no sync."""
+    win = _comb_windows_device(frames, order, side, size, threshold, lo, hi)
+    flags = (win[:, 0] >= pixels * _comb_step(frames, side, size)).to(torch.int32).contiguous()
+    return _deinterlace_masked_device(frames, order, flags, method, side, size, lo, hi), win
+
+
+def comb_windows(frames: torch.Tensor, order: str, pixel_format: str = "rgb", size=None, depth: int = 8,
+                 threshold: int = pd.DEFAULT_COMB_THRESHOLD) -> torch.Tensor:
+    """The residual-comb measure behind combed=: int64 [N, 2] on the GPU (savsr_amd.pulldown.frame_comb_windows is the specification, bit
+    for bit), on the caller's current stream, without a sync.  Entry [n, 0] is the largest number of combed samples in any 16-row x
+    16-pixel window of frame n (one window every 8 rows and 8 pixels), [n, 1] the number in the whole frame; a sample on a second-field
+    row (the rows of the other parity than `order`'s first field) is combed iff |a - b| + |c - b| - |a - c| > 2 * threshold with its
+    vertical neighbours a, c.  frames as for `field_scores`.  The default threshold is ffmpeg fieldmatch's cthresh; it is not validated
+    on footage."""
+    check_order(order)
+    pd.check_comb_threshold(threshold, "threshold")
+    frames, side, size = _stage_args(frames, pixel_format, size, depth, _field_frames)
+    return _comb_windows_device(frames, order, side, size, threshold)
+
+
 def field_scores(frames: torch.Tensor, order: str, pixel_format: str = "rgb", size=None, depth: int = 8) -> torch.Tensor:
     """The field matcher's scores: int64 [N, 2] on the GPU (savsr_amd.pulldown.frame_scores is the specification, bit for bit), on the
     caller's current stream, without a sync.  Entry [n, j] is the comb measure of frame n with its second field (the rows of the other
@@ -511,31 +590,48 @@ def _delta_device(matches: List[int], device: torch.device) -> torch.Tensor:
     return h2d(torch.tensor(matches, dtype=torch.int32), device)
 
 
-def _remove_pulldown_device(frames: torch.Tensor, order: str, side: Side, size: Size, cycle: int):
+def _remove_pulldown_device(frames: torch.Tensor, order: str, side: Side, size: Size, cycle: int, combed: Optional[str] = None,
+                            comb_threshold: int = pd.DEFAULT_COMB_THRESHOLD, comb_pixels: int = pd.DEFAULT_COMB_PIXELS):
     """pulldown.remove_pulldown_frames on frames of the input side on the GPU: (the kept woven frames, info).  Two host synchronisations:
-    the scores come down for the match, the woven frames' pair SADs for the decimation."""
+    the scores come down for the match, the woven frames' pair SADs for the decimation.  combed: the woven frames `comb_windows` flags
+    are deinterlaced between the two (the flags stay on the device; the comb table comes down with the SADs)."""
     n = _field_frames(frames, side, size)[0]
     if n < 1:
         raise ValueError("the video has no frames")
     scores = _field_scores_device(frames, order, side, size).cpu()
     matches = pd.matches_from_scores(scores.numpy())
     woven = _weave_device(frames, order, _delta_device(matches, frames.device), side, size)
-    sad = [-1] + _pair_sad_device(woven, side, size).cpu().tolist()
+    extra = {}
+    if combed is None:
+        sad = [-1] + _pair_sad_device(woven, side, size).cpu().tolist()
+    else:
+        woven, win = _clean_combed_device(woven, order, combed, comb_threshold, comb_pixels, side, size)
+        both = torch.cat([_pair_sad_device(woven, side, size), win.reshape(-1)]).cpu()
+        sad, win = [-1] + both[:n - 1].tolist(), both[n - 1:].reshape(n, 2).numpy()
+        extra = {"comb": win, "combed": [k for k, f in enumerate(pd.combed_from_windows(win, _comb_step(frames, side, size), comb_pixels)) if f]}
     kept = pd.kept_from_drops(n, pd.drops_from_sad(sad, cycle))
     out = woven.index_select(0, torch.tensor(kept, dtype=torch.int64).to(woven.device))
-    return out, {"scores": scores.numpy(), "matches": matches, "sad": torch.tensor(sad, dtype=torch.int64).numpy(), "kept": kept}
+    return out, {"scores": scores.numpy(), "matches": matches, "sad": torch.tensor(sad, dtype=torch.int64).numpy(), "kept": kept, **extra}
 
 
-def remove_pulldown(frames: torch.Tensor, order: str, pixel_format: str = "rgb", size=None, depth: int = 8, cycle: int = 5, return_info: bool = False):
+def remove_pulldown(frames: torch.Tensor, order: str, pixel_format: str = "rgb", size=None, depth: int = 8, cycle: int = 5, return_info: bool = False,
+                    *, combed: Optional[str] = None, comb_threshold: int = pd.DEFAULT_COMB_THRESHOLD, comb_pixels: int = pd.DEFAULT_COMB_PIXELS):
     """Telecined film (3:2 pulldown) as its film frames: N - N // cycle frames on the GPU in the format of the N given ones
     (savsr_amd.pulldown.remove_pulldown_frames is the specification, bit for bit).  Every frame keeps its first field (order "tff": the
     top rows) and takes the second one from itself or from the frame before it, whichever combs less (`field_scores`); of every `cycle`
     woven frames the one closest to its predecessor (`pair_sad`) is dropped.  frames as for `deinterlace`.  return_info=True: (frames,
-    info), info = {"scores", "matches", "sad", "kept"} as in the specification.  Two host synchronisations per call."""
+    info), info = {"scores", "matches", "sad", "kept"} as in the specification.  Two host synchronisations per call.
+    combed="yadif" / "bwdif" (keyword only; hybrid film and video): a woven frame in which some 16 x 16 window still holds comb_pixels
+    combed pixels (`comb_windows` with comb_threshold) -- a video insert, a leading frame whose partner field was cut off, the orphan
+    field of a broken cadence -- is deinterlaced at same rate by that method, its neighbours being the woven frames; the others pass
+    as they are, and the decimation reads the cleaned frames.  info gains "comb" (int64 [N, 2]) and "combed" (the flagged woven
+    indices).  The defaults are ffmpeg fieldmatch's (cthresh 9, combpel 80 / 256 of a window's 128 second-field pixels) and are not
+    validated on footage; still two host synchronisations."""
     check_order(order)
     cycle = pd.check_cycle(cycle)
+    pd.check_comb_options(combed, comb_threshold, comb_pixels, True)
     frames, side, size = _stage_args(frames, pixel_format, size, depth, _field_frames)
-    out, info = _remove_pulldown_device(frames, order, side, size, cycle)
+    out, info = _remove_pulldown_device(frames, order, side, size, cycle, combed, comb_threshold, comb_pixels)
     return (out, info) if return_info else out
 
 
@@ -545,28 +641,42 @@ class PulldownRemover:
     the previous push's last source frame as its context; woven frames wait until their cycle of `cycle` is complete, then the kept ones
     go on.  Between pushes the device keeps one source frame, at most cycle - 1 woven frames and the last woven frame (the next SAD's
     predecessor): `held` <= cycle + 1, copies of their own, so that the chunk they came with is released.  Concatenated, the outputs are
-    `remove_pulldown` on the whole video for any chunking; `info` has the matches and the kept indices so far."""
+    `remove_pulldown` on the whole video for any chunking; `info` has the matches and the kept indices so far.
+    combed="yadif" / "bwdif": as in `remove_pulldown`.  A flagged woven frame is deinterlaced from the woven frames beside it, so a woven
+    frame is final (cleaned, or passed as it is) once the next one exists: the last woven frame is held back until the next push, or
+    finish(), and the one before it stays as its context; the decimation and the waiting cycle hold cleaned frames.  `held` <= cycle + 3:
+    two frames more (one look-ahead, one context).  `info` gains "combed", the flagged woven indices so far."""
 
-    def __init__(self, order: str, side: Side, size: Size, cycle: int = 5):
+    def __init__(self, order: str, side: Side, size: Size, cycle: int = 5, combed: Optional[str] = None,
+                 comb_threshold: int = pd.DEFAULT_COMB_THRESHOLD, comb_pixels: int = pd.DEFAULT_COMB_PIXELS):
         check_order(order, "pulldown")
         self.order, self.side, self.size, self.cycle = order, side, size, pd.check_cycle(cycle, "pulldown_cycle")
+        self.combed = pd.check_comb_options(combed, comb_threshold, comb_pixels, True)
+        self.comb_threshold, self.comb_pixels = comb_threshold, comb_pixels
         self._ctx: Optional[torch.Tensor] = None           # the last source frame pushed
-        self._last: Optional[torch.Tensor] = None          # the last woven frame
-        self._pend: Optional[torch.Tensor] = None          # the woven frames of the incomplete cycle, frames [_base, seen)
+        self._last: Optional[torch.Tensor] = None          # the last woven (combed=: cleaned) frame
+        self._pend: Optional[torch.Tensor] = None          # the woven (cleaned) frames of the incomplete cycle, frames [_base, _base + len)
         self._pend_sad: List[int] = []                     # their pair SADs with their predecessors
+        self._wov: Optional[torch.Tensor] = None           # combed=: the woven context frame, then the woven frames not cleaned yet
+        self._todo = 0                                     # how many of them are not cleaned yet (they are the last ones)
+        self._cleaned = 0                                  # woven frames that went through the cleaning
         self._base = 0
         self.seen = 0
         self.matches: List[int] = []
         self.kept: List[int] = []
+        self.flagged: List[int] = []
 
     @property
     def held(self) -> int:
-        """Frames on the device between pushes: at most cycle + 1."""
-        return sum(0 if t is None else int(t.shape[0]) for t in (self._ctx, self._last, self._pend))
+        """Frames on the device between pushes: at most cycle + 1, cycle + 3 with combed=."""
+        return sum(0 if t is None else int(t.shape[0]) for t in (self._ctx, self._last, self._pend, self._wov))
 
     @property
     def info(self) -> dict:
-        return {"matches": list(self.matches), "kept": list(self.kept)}
+        info = {"matches": list(self.matches), "kept": list(self.kept)}
+        if self.combed is not None:
+            info["combed"] = list(self.flagged)
+        return info
 
     def push(self, frames: torch.Tensor) -> torch.Tensor:
         k = int(frames.shape[0])
@@ -576,12 +686,45 @@ class PulldownRemover:
         n = int(src.shape[0])
         matches = pd.matches_from_scores(_field_scores_device(src, self.order, self.side, self.size, n - k, n).cpu().numpy())
         woven = _weave_device(src, self.order, _delta_device(matches, src.device), self.side, self.size, n - k, n)
-        pairs = woven if self._last is None else torch.cat([self._last, woven], 0)
-        sad = _pair_sad_device(pairs, self.side, self.size).cpu().tolist()
-        self._pend_sad += ([-1] if self._last is None else []) + sad
-        pend = woven if self._pend is None else torch.cat([self._pend, woven], 0)
         self.matches += matches
         self.seen += k
+        self._ctx = src[n - 1:].clone()
+        if self.combed is None:
+            return self._decimate(woven, None)
+        return self._decimate(*self._clean(woven, False))
+
+    def _clean(self, woven: Optional[torch.Tensor], last: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The woven frames that are final now, cleaned, and their comb table on the device: all but the newest one, whose next frame is
+        not known yet (last: all, the newest one's next frame clamped, as at the end of the video)."""
+        k = 0 if woven is None else int(woven.shape[0])
+        buf = woven if self._wov is None else (self._wov if woven is None else torch.cat([self._wov, woven], 0))
+        n = int(buf.shape[0])
+        lo = n - self._todo - k
+        hi = n if last else max(n - 1, lo)
+        out = _clean_combed_device(buf, self.order, self.combed, self.comb_threshold, self.comb_pixels, self.side, self.size, lo, hi)
+        if hi > lo:
+            self._wov, self._todo = buf[max(hi - 1, 0):].clone(), n - hi          # (a copy of two frames: the chunk's storage is released)
+        else:
+            self._wov, self._todo = buf, self._todo + k
+        return out
+
+    def _decimate(self, woven: torch.Tensor, win: Optional[torch.Tensor]) -> torch.Tensor:
+        """The next woven (cleaned) frames -> the kept ones of the cycles they complete; the others wait."""
+        k = int(woven.shape[0])
+        if k == 0:
+            return woven
+        pairs = woven if self._last is None else torch.cat([self._last, woven], 0)
+        sad = _pair_sad_device(pairs, self.side, self.size)
+        if win is None:
+            sad = sad.cpu().tolist()
+        else:          # (the comb table comes down with the SADs: one synchronisation)
+            both = torch.cat([sad, win.reshape(-1)]).cpu()
+            ns = int(sad.shape[0])
+            sad, flags = both[:ns].tolist(), pd.combed_from_windows(both[ns:].numpy(), _comb_step(woven, self.side, self.size), self.comb_pixels)
+            self.flagged += [self._cleaned + j for j, f in enumerate(flags) if f]
+            self._cleaned += k
+        self._pend_sad += ([-1] if self._last is None else []) + sad
+        pend = woven if self._pend is None else torch.cat([self._pend, woven], 0)
         full = (int(pend.shape[0]) // self.cycle) * self.cycle
         drops = set(pd.drops_from_sad(self._pend_sad[:full], self.cycle, self._base))
         kept = [j for j in range(self._base, self._base + full) if j not in drops]
@@ -590,17 +733,20 @@ class PulldownRemover:
         self._pend = pend[full:].clone() if full < int(pend.shape[0]) else None
         self._pend_sad = self._pend_sad[full:]
         self._base += full
-        self._ctx, self._last = src[n - 1:].clone(), woven[k - 1:].clone()
+        self._last = woven[k - 1:].clone()
         return out
 
     def finish(self) -> Optional[torch.Tensor]:
-        pend, self._pend, self._ctx, self._last = self._pend, None, None, None
+        head = None
+        if self.combed is not None and self._wov is not None and self._todo:          # the held woven frame, then the end as ever
+            head = self._decimate(*self._clean(None, True))
+        pend, self._pend, self._ctx, self._last, self._wov, self._todo = self._pend, None, None, None, None, 0
         if pend is None:
-            return None
+            return head if head is not None and int(head.shape[0]) else None
         self.kept += list(range(self._base, self._base + int(pend.shape[0])))
         self._base += int(pend.shape[0])
         self._pend_sad = []
-        return pend
+        return pend if head is None else torch.cat([head, pend], 0)
 
 
 # ---- scan detection (savsr_amd/scan.py is the specification) -----------------------------------------------------------------------------------
@@ -733,13 +879,16 @@ def _check_field_options(deinterlacer, field_rate, fields, pulldown, detect: boo
             raise ValueError(f"{name} = {value!r} goes with fields=: without interlaced video there are no fields to interpolate")
 
 
-def make_stage(fields, pulldown, pulldown_cycle, side: Side, size: Size, deinterlacer: str = "yadif", field_rate: str = "double"):
+def make_stage(fields, pulldown, pulldown_cycle, side: Side, size: Size, deinterlacer: str = "yadif", field_rate: str = "double", combed=None,
+               comb_threshold: int = pd.DEFAULT_COMB_THRESHOLD, comb_pixels: int = pd.DEFAULT_COMB_PIXELS):
     """The streaming stage in front of everything else that fields= / pulldown= / pulldown_cycle= ask for, on frames of `side`: None, a
-    FieldSplitter or a PulldownRemover (the two exclude each other), after `_check_fields`, `_check_pulldown` and
-    `_check_field_options` (deinterlacer= / field_rate=, which the FieldSplitter takes), in that order."""
+    FieldSplitter or a PulldownRemover (the two exclude each other), after `_check_fields`, `_check_pulldown`,
+    `_check_field_options` (deinterlacer= / field_rate=, which the FieldSplitter takes) and `pulldown.check_comb_options` (combed= /
+    comb_threshold= / comb_pixels=, which the PulldownRemover takes), in that order."""
     _check_fields(fields)
     _check_pulldown(pulldown, pulldown_cycle, fields)
     _check_field_options(deinterlacer, field_rate, fields, pulldown)
+    pd.check_comb_options(combed, comb_threshold, comb_pixels, pulldown is not None, fields)
     if fields is not None:
         return FieldSplitter(fields, side, size, deinterlacer, field_rate)
-    return None if pulldown is None else PulldownRemover(pulldown, side, size, pulldown_cycle)
+    return None if pulldown is None else PulldownRemover(pulldown, side, size, pulldown_cycle, combed, comb_threshold, comb_pixels)

@@ -26,11 +26,23 @@ previous and the current frame -- with this project's own comb measure above, no
 (drop the frame closest to its predecessor in each cycle) in exact integers over every sample pair_sad reads, without decimate's block
 metrics or scene threshold.  ffmpeg is not available where this was written, so nothing here is pinned to its output.
 
+  4. Clean (`comb_windows`, `combed_from_windows`; opt-in, `combed="yadif"` / `"bwdif"`).  Between the weave and the decimation every
+     woven frame is measured for residual combing: a second-field sample (y, x), 1 <= y <= R - 2, is combed iff the match measure
+     |a - b| + |c - b| - |a - c| of its own column exceeds 2 * comb_threshold; cells of 8 rows x 8 pixels anchored at (0, 0) count
+     them, and a frame is flagged iff some 2 x 2 cell window (16 rows x 16 pixels, one at every cell origin, clipped at the edges, so
+     windows overlap by half in both axes) holds at least comb_pixels of them.  A flagged frame is replaced by its same-rate
+     deinterlaced form (savsr_amd/deinterlace.py, the temporal neighbours are the woven frames); the others pass as they are; the
+     decimation sees the cleaned frames.  ffmpeg's fieldmatch -> yadif=deint=interlaced -> decimate chain is the idea; the defaults are
+     fieldmatch's cthresh 9 and its combpel 80 of 256 rescaled to the 128 second-field samples of a window (40), and neither is
+     validated on footage.
+
 Limits.  There is no cadence tracking: every frame is matched and every cycle decimated on its own, so a cadence broken by an edit costs
-one real frame in that cycle, as with decimate.  A leading frame whose partner field was cut off (a stream that starts inside BC CD)
-stays combed.  Frames that match neither candidate -- video inserts -- stay combed; `info["scores"]` has both candidates' scores, so a
-caller can find them.  2:2 phase-shifted PAL film and mixed film / video are not handled.  Nothing is validated on real footage or
-trained weights.
+one real frame in that cycle, as with decimate.  Without `combed=`, a leading frame whose partner field was cut off (a stream that starts
+inside BC CD), the orphan field a broken cadence leaves and frames that match neither candidate -- video inserts -- stay combed
+(`info["scores"]` has both candidates' scores); with it they are deinterlaced.  What remains with `combed=`: the decimation still drops
+one of every `cycle` frames of a true-video insert (ffmpeg's constant-rate chain does too: judder, not combing); a cleaned frame has half
+its rows interpolated; combing that is small (the two-pixel bar of the tests reads 32) or of low contrast stays below the rule; one
+field order per video.  2:2 phase-shifted PAL film is not handled.  Nothing is validated on real footage or trained weights.
 """
 from __future__ import annotations
 
@@ -39,12 +51,15 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .deinterlace import check_frame_rows, check_order
+from .deinterlace import DEINTERLACERS, check_frame_rows, check_order, deinterlace_frames
 from .frames import check_pixel_format, layout_of
 from .scenes import pair_sad
 from .yuv import MONO, check_depth, frame_bytes, layout_name, luma_plane, split_planes
 
 CYCLE_MIN, CYCLE_MAX, DEFAULT_CYCLE = 2, 25, 5
+DEFAULT_COMB_THRESHOLD, DEFAULT_COMB_PIXELS = 9, 40          # fieldmatch's cthresh; its combpel 80 / 256 of a window's 128 samples
+COMB_CELL = 8                                                  # rows and pixels of a cell; a window is 2 x 2 cells
+MAX_COMB_STEP = 4
 FLOAT_REFUSAL = "float frames have no integer samples to deinterlace: give [N, h, w, c] uint8 or planar frames (quantise first)"
 
 
@@ -219,25 +234,140 @@ def kept_from_drops(n: int, drops: Sequence[int]) -> List[int]:
     return [k for k in range(n) if k not in gone]
 
 
-def remove_pulldown_frames(frames, order: str, pixel_format: str = "rgb", size=None, depth: int = 8,
-                           cycle: int = DEFAULT_CYCLE) -> Tuple[np.ndarray, Dict[str, object]]:
+# ---- residual combing after the match ----------------------------------------------------------------------------------------------------------
+def check_combed(combed, what: str = "combed") -> Optional[str]:
+    """combed is None or a deinterlacer's name: how woven frames that are still combed are cleaned."""
+    if combed is not None and combed not in DEINTERLACERS:
+        raise ValueError(f"{what} = {combed!r}: None or one of {', '.join(repr(m) for m in DEINTERLACERS)}")
+    return combed
+
+
+def check_comb_threshold(threshold, what: str = "comb_threshold") -> int:
+    """A sample is combed iff its measure exceeds 2 * threshold; an int in 0 .. 255 (the measure is at most 510)."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, np.integer)) or not 0 <= int(threshold) <= 255:
+        raise ValueError(f"{what} = {threshold!r}: an int in 0 .. 255")
+    return int(threshold)
+
+
+def check_comb_pixels(pixels, what: str = "comb_pixels") -> int:
+    """A frame is combed iff a window holds this many combed pixels; an int in 1 .. 128 (a window has 128 second-field pixels)."""
+    if isinstance(pixels, bool) or not isinstance(pixels, (int, np.integer)) or not 1 <= int(pixels) <= 2 * COMB_CELL * COMB_CELL:
+        raise ValueError(f"{what} = {pixels!r}: an int in 1 .. {2 * COMB_CELL * COMB_CELL}")
+    return int(pixels)
+
+
+def check_comb_options(combed, comb_threshold, comb_pixels, have_match: bool, fields=None) -> Optional[str]:
+    """combed= goes with pulldown= (or scan="detect") and not with fields=; comb_threshold= / comb_pixels= go with combed=."""
+    if check_combed(combed) is None:
+        for name, value, default in (("comb_threshold", comb_threshold, DEFAULT_COMB_THRESHOLD), ("comb_pixels", comb_pixels, DEFAULT_COMB_PIXELS)):
+            if isinstance(value, bool) or value != default:
+                raise ValueError(f"{name} = {value!r} goes with combed=: it is a parameter of the comb rule behind it")
+        return None
+    if fields is not None:
+        raise ValueError(f"combed = {combed!r} together with fields = {fields!r}: fields= deinterlaces every frame; combed= cleans the frames "
+                         f"the pulldown removal leaves combed and goes with pulldown=")
+    if not have_match:
+        raise ValueError(f"combed = {combed!r} goes with pulldown= (or scan='detect'): it cleans the frames the pulldown removal leaves combed")
+    check_comb_threshold(comb_threshold)
+    check_comb_pixels(comb_pixels)
+    return combed
+
+
+def comb_windows(mats, order: str, step: int = 1, threshold: int = DEFAULT_COMB_THRESHOLD, depth: int = 8) -> np.ndarray:
+    """[N, R, C] integer samples -> [N, 2] int64: [n, 0] the largest count of combed samples in any window of matrix n, [n, 1] the count
+    in the whole matrix.  A sample (y, x) on a second-field row, 1 <= y <= R - 2, is combed iff |a - b| + |c - b| - |a - c| >
+    2 * threshold with a, b, c the samples at rows y - 1, y, y + 1 (read as `field_scores` reads them).  Cells are 8 rows x 8 * step
+    samples anchored at (0, 0), clipped at the edges; a window is 2 x 2 cells, one at every cell origin, and counts what lies inside
+    the matrix.  R < 3 gives zeros."""
+    p = first_parity(order)
+    m = np.asarray(mats)
+    if m.ndim != 3 or m.dtype.kind not in "iu":
+        raise ValueError(f"matrices must be [N, R, C] integers, got {m.dtype} {tuple(m.shape)}")
+    if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or not 1 <= int(step) <= MAX_COMB_STEP:
+        raise ValueError(f"step = {step!r}: the samples of a pixel, 1 .. {MAX_COMB_STEP}")
+    threshold, depth = check_comb_threshold(threshold, "threshold"), check_depth(depth)
+    v = np.minimum(m.astype(np.int64), (1 << depth) - 1) >> (depth - 8)
+    N, R, C = v.shape
+    out = np.zeros((N, 2), dtype=np.int64)
+    ys = np.arange(1 - p, R, 2)
+    ys = ys[(ys >= 1) & (ys <= R - 2)]
+    if ys.size == 0 or N == 0:
+        return out
+    a, b, c = v[:, ys - 1], v[:, ys], v[:, ys + 1]
+    combed = (np.abs(a - b) + np.abs(c - b) - np.abs(a - c)) > 2 * threshold          # [N, len(ys), C]
+    cw = COMB_CELL * int(step)
+    ncr, ncc = -(-R // COMB_CELL), -(-C // cw)
+    cells = np.zeros((N, ncr + 1, ncc + 1), dtype=np.int64)          # (one cell row and column of zeros: the clipped windows' far halves)
+    rows_of = np.add.reduceat(combed.astype(np.int64), np.arange(0, C, cw), axis=2)          # [N, len(ys), ncc]
+    np.add.at(cells, (slice(None), ys // COMB_CELL, slice(0, ncc)), rows_of)
+    win = cells[:, :-1, :-1] + cells[:, 1:, :-1] + cells[:, :-1, 1:] + cells[:, 1:, 1:]
+    out[:, 0] = win.reshape(N, -1).max(axis=1)
+    out[:, 1] = cells.reshape(N, -1).sum(axis=1)
+    return out
+
+
+def frame_comb_windows(frames, order: str, pixel_format: str = "rgb", size=None, depth: int = 8, threshold: int = DEFAULT_COMB_THRESHOLD) -> np.ndarray:
+    """`comb_windows` of frames: the byte matrix of packed [N, h, w, c] uint8 frames with step c, the Y plane of planar ones."""
+    check_order(order)
+    frames = _as_numpy(frames)
+    hw, layout, depth = _frame_kind(frames, pixel_format, size, depth)
+    return comb_windows(_planes(frames, hw, layout, depth)[0], order, 1 if hw else _comb_step(frames), threshold, depth)
+
+
+def _comb_step(frames: np.ndarray) -> int:
+    c = int(frames.shape[3])
+    if not 1 <= c <= MAX_COMB_STEP:
+        raise ValueError(f"frames have {c} channels: 1 .. {MAX_COMB_STEP}")
+    return c
+
+
+def combed_from_windows(win, step: int = 1, pixels: int = DEFAULT_COMB_PIXELS) -> List[bool]:
+    """Frame n is combed iff its largest window count win[n, 0] reaches pixels * step (a pixel of packed frames is `step` samples)."""
+    return [int(w0) >= int(pixels) * int(step) for w0 in np.asarray(win).reshape(-1, 2)[:, 0].tolist()]
+
+
+def clean_combed(woven, order: str, flags: Sequence[bool], method: str, pixel_format: str = "rgb", size=None, depth: int = 8) -> np.ndarray:
+    """The woven frames with every flagged one replaced by frame n of deinterlace_frames(woven, ..., method, rate="same"): its temporal
+    neighbours are woven frames, not cleaned ones; every plane is cleaned."""
+    woven = _as_numpy(woven)
+    if not any(flags):
+        return woven.copy()
+    clean = deinterlace_frames(woven, order, pixel_format, size, depth, method, "same")
+    out = woven.copy()
+    idx = [k for k, f in enumerate(flags) if f]
+    out[idx] = clean[idx]
+    return out
+
+
+def remove_pulldown_frames(frames, order: str, pixel_format: str = "rgb", size=None, depth: int = 8, cycle: int = DEFAULT_CYCLE, combed=None,
+                           comb_threshold: int = DEFAULT_COMB_THRESHOLD, comb_pixels: int = DEFAULT_COMB_PIXELS) -> Tuple[np.ndarray, Dict[str, object]]:
     """The film frames of a telecined video, in the same format, and info = {"scores": int64 [N, 2], "matches": [N] of -1 | 0, "sad":
     int64 [N] (pair_sad of the woven frames k - 1, k; entry 0 is -1 and counts as infinite), "kept": the indices of the kept woven
     frames}: the composition of the rules above.  frames: [N, h, w, c] uint8, or with pixel_format "i420", "i422", "i444", "y400" and
-    size=(h, w): [N, frame_bytes] uint8, little-endian 16-bit samples at depth 10 / 12.  Float frames are refused."""
+    size=(h, w): [N, frame_bytes] uint8, little-endian 16-bit samples at depth 10 / 12.  Float frames are refused.  combed="yadif" /
+    "bwdif": woven frames that `comb_windows` / `combed_from_windows` (comb_threshold, comb_pixels) flag are deinterlaced at same rate
+    before the decimation, which then reads the cleaned frames; info gains "comb" (int64 [N, 2]) and "combed" (the flagged woven
+    indices)."""
     check_order(order)
     cycle = check_cycle(cycle)
+    check_comb_options(combed, comb_threshold, comb_pixels, True)
     frames = _as_numpy(frames)
-    _frame_kind(frames, pixel_format, size, depth)
+    hw = _frame_kind(frames, pixel_format, size, depth)[0]
     n = frames.shape[0]
     if n < 1:
         raise ValueError("the video has no frames")
     scores = frame_scores(frames, order, pixel_format, size, depth)
     matches = matches_from_scores(scores)
     woven = weave(frames, order, matches, pixel_format, size, depth)
+    extra = {}
+    if combed is not None:
+        win = frame_comb_windows(woven, order, pixel_format, size, depth, comb_threshold)
+        flags = combed_from_windows(win, 1 if hw else _comb_step(frames), comb_pixels)
+        woven = clean_combed(woven, order, flags, combed, pixel_format, size, depth)
+        extra = {"comb": win, "combed": [k for k, f in enumerate(flags) if f]}
     sad = np.concatenate([np.array([-1], dtype=np.int64), pair_sad(woven, pixel_format, size, depth)])
     kept = kept_from_drops(n, drops_from_sad(sad.tolist(), cycle))
-    return woven[kept], {"scores": scores, "matches": matches, "sad": sad, "kept": kept}
+    return woven[kept], {"scores": scores, "matches": matches, "sad": sad, "kept": kept, **extra}
 
 
 # ---- the command line's header decision --------------------------------------------------------------------------------------------------------

@@ -91,7 +91,16 @@ woven frames the one closest to its predecessor is dropped), so the network runs
 film frames.  tff / bff name the field order, auto takes it from the Y4M input's I tag as --fields auto does (Im is refused).  The
 output is tagged Ip at (cycle - 1) / cycle of the frame rate (30000:1001 -> 24000:1001), and a PNG folder holds the kept frames
 (%08d.png).  Not together with --fields tff / bff / auto: they are two answers to one question.  There is no cadence tracking: a cadence
-broken by an edit costs one real frame in that cycle, and a frame that matches neither neighbour stays combed.
+broken by an edit costs one real frame in that cycle, and a frame that matches neither neighbour stays combed unless --combed is given.
+
+--combed yadif / bwdif: hybrid material (film with video-rate titles or effects, series cut on tape, a stream that starts or is cut
+inside a cadence).  After the field match every woven frame is measured for residual combing (savsr_amd.comb_windows: a sample is combed
+when its comb measure exceeds twice --comb-threshold, a frame when some 16 x 16 window, one every 8 rows and pixels, holds --comb-pixels
+of them); the combed frames alone are deinterlaced at same rate by that rule and the decimation reads the cleaned frames (ffmpeg's
+fieldmatch -> yadif=deint=interlaced -> decimate chain).  One line on stderr says how many frames were cleaned.  Goes with --pulldown or
+--scan detect (a telecine verdict; ignored for the others).  The decimation still drops one of every five frames of a true-video insert
+(judder, not combing), a cleaned frame has half its rows interpolated, and small or low-contrast combing stays below the rule; the
+defaults (9, 40) are fieldmatch's and are not validated on footage.
 
 --scan detect: footage whose scan is not known, or whose tag is not trusted (encoders tag hard-telecined film and much progressive
 material It; a PNG folder has no tag at all).  A first pass over a .y4m file or a PNG folder in --chunk-sized pieces computes the field
@@ -121,7 +130,8 @@ from typing import List, Optional
 
 from .dither import DITHERS
 from .deinterlace import DEINTERLACERS, FIELD_FLAGS, FIELD_ORDERS, FIELD_RATES, resolve_fields
-from .pulldown import DEFAULT_CYCLE, PULLDOWN_FLAGS, check_cycle, resolve_pulldown
+from .pulldown import (DEFAULT_COMB_PIXELS, DEFAULT_COMB_THRESHOLD, DEFAULT_CYCLE, PULLDOWN_FLAGS, check_comb_pixels, check_comb_threshold, check_cycle,
+                       resolve_pulldown)
 from .scan import SCAN_FLAGS
 from .yuv import COLOURS, SITINGS
 
@@ -251,6 +261,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "order; auto: from the Y4M input's I tag (It, Ib; Im is refused); none (default): frames go through as they are")
     p.add_argument("--pulldown-cycle", type=int, default=None, metavar="N",
                    help="--pulldown: one frame in every N is the repeated one and is dropped (default 5; 2 .. 25)")
+    p.add_argument("--combed", default=None, choices=["none"] + list(DEINTERLACERS),
+                   help="--pulldown / --scan detect: hybrid film and video.  yadif / bwdif: woven frames that are still combed (video inserts, "
+                        "a stream cut inside a cadence) are deinterlaced at same rate by that rule before the decimation; none (default): "
+                        "they stay as they are")
+    p.add_argument("--comb-threshold", type=int, default=None, metavar="X",
+                   help="--combed: a sample is combed when its comb measure exceeds 2 X (default 9, ffmpeg fieldmatch's cthresh; 0 .. 255; "
+                        "not validated on footage)")
+    p.add_argument("--comb-pixels", type=int, default=None, metavar="N",
+                   help="--combed: a frame is combed when a 16 x 16 window holds N combed pixels (default 40 of 128, fieldmatch's combpel "
+                        "80 / 256; 1 .. 128; not validated on footage)")
     p.add_argument("--scan", default=None, choices=list(SCAN_FLAGS),
                    help="detect: find out from the content, in a first pass over the input (a file or a folder), whether it is progressive, "
                         "interlaced or telecined film and with which field order, then run as --fields X / --pulldown X would; the verdict "
@@ -362,6 +382,19 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error(f"--pulldown {a.pulldown} together with --fields {a.fields}: they are two answers to one question (telecined film, whose "
                 f"frames are recovered, or interlaced video, whose fields are interpolated); give one of them")
     a.pulldown_cycle = DEFAULT_CYCLE if a.pulldown_cycle is None else a.pulldown_cycle
+    a.combed = None if a.combed == "none" else a.combed
+    if a.combed is None:
+        if a.comb_threshold is not None or a.comb_pixels is not None:
+            p.error("--comb-threshold and --comb-pixels go with --combed yadif or bwdif")
+    elif a.scan is None and a.pulldown in (None, "none"):
+        p.error(f"--combed {a.combed} goes with --pulldown auto, tff or bff, or --scan detect: it cleans the frames the pulldown removal leaves combed")
+    a.comb_threshold = DEFAULT_COMB_THRESHOLD if a.comb_threshold is None else a.comb_threshold
+    a.comb_pixels = DEFAULT_COMB_PIXELS if a.comb_pixels is None else a.comb_pixels
+    try:
+        check_comb_threshold(a.comb_threshold, "--comb-threshold")
+        check_comb_pixels(a.comb_pixels, "--comb-pixels")
+    except ValueError as e:
+        p.error(str(e))
     try:
         check_cycle(a.pulldown_cycle, "--pulldown-cycle")
         if not a.y4m_in:
@@ -546,7 +579,8 @@ def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, de
     top = None
     f = None
     how = (a.deinterlacer, a.field_rate) if order is not None else ()          # (they say how --fields is carried out, and nothing else)
-    split = make_stage(order, film, a.pulldown_cycle, *detector_side(fmt_in, size, depth), *how)
+    comb = dict(combed=a.combed, comb_threshold=a.comb_threshold, comb_pixels=a.comb_pixels) if film is not None and a.combed is not None else {}
+    split = make_stage(order, film, a.pulldown_cycle, *detector_side(fmt_in, size, depth), *how, **comb)
 
     def fold(frames):
         nonlocal top
@@ -771,7 +805,10 @@ def main(argv: Optional[List[str]] = None) -> int:
                            colour="bt601" if chroma == MONO else colour or "bt601",          # (grey-scale frames carry no colour space)
                            out_colour=None if out_chroma == MONO else out_colour, depth=depth, out_depth=out_depth, siting=siting, out_siting=out_siting,
                            chroma_filter=a.chroma_filter, crop=rect, bars=a.bars, fields=order, pulldown=film, pulldown_cycle=a.pulldown_cycle,
-                           dither=a.dither, **(dict(deinterlacer=a.deinterlacer, field_rate=a.field_rate) if order is not None else {}))
+                           dither=a.dither, **(dict(deinterlacer=a.deinterlacer, field_rate=a.field_rate) if order is not None else {}),
+                           # (--combed with --scan detect says how a telecine verdict is carried out: ignored for the other verdicts)
+                           **(dict(combed=a.combed, comb_threshold=a.comb_threshold, comb_pixels=a.comb_pixels)
+                              if film is not None and a.combed is not None else {}))
         done = 0
         try:
             for chunk in chunks:
@@ -808,6 +845,9 @@ def main(argv: Optional[List[str]] = None) -> int:
         info = up.pulldown_info
         scenes += (f", pulldown {film}: {len(info['matches'])} frames in, {len(info['kept'])} out, {info['matches'].count(-1)} matched from "
                    f"their predecessor")
+        if "combed" in info:
+            print(f"--combed {a.combed}: {len(info['combed'])} of {len(info['matches'])} woven frames were combed and deinterlaced",
+                  file=sys.stderr, flush=True)
     print(f"upscaled {done} frames in {dt:.2f} s: {done / dt:.2f} frames/s{scenes}", file=sys.stderr if a.output == "-" else sys.stdout, flush=True)
     return 0
 

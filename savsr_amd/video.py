@@ -20,7 +20,8 @@ fields= / pulldown= (one of them), then crop=: stages in front of everything els
 on `deinterlace(frames, fields, ...)` (2N progressive frames), on `remove_pulldown(frames, pulldown, ...)` (the N - N // pulldown_cycle
 film frames), on the hand-cropped video (crop="auto" finds the rect on the device; bars="keep" puts the result back into full-size
 frames of nominal black, bars="drop" returns the picture alone; both are strided copies through torch views).  Each argument at None
-runs exactly the lines that ran before it existed.
+runs exactly the lines that ran before it existed.  combed= / comb_threshold= / comb_pixels= belong to pulldown= (savsr_amd/pulldown.py:
+woven frames that are still combed are deinterlaced before the decimation) and are `remove_pulldown`'s arguments of the same names.
 
 scan="detect": the call finds out which of the two the video is (savsr_amd/scan.py: `detect_scan` on the unpacked frames on the device,
 right after surface= unpacking and in front of everything else) and continues exactly as if the verdict's `kwargs()` had been given:
@@ -53,8 +54,9 @@ from .packing import get_hw
 from .prepass import (FieldSplitter, PulldownRemover, ScanStats, _check_crop_args, _check_field_options, _check_fields, _check_pulldown,  # noqa: F401  (re-exported)
                       _check_scan, _crop_device, _cropped_spec, _deinterlace_device, _detect_device, _detect_scan_device, _field_frames,
                       _insert_device, _pair_sad_device, _pack_surface_device, _remove_pulldown_device, _to_device, _unpack_surface_device,
-                      deinterlace, detect_active_area, detect_cuts, detect_scan, field_scores, field_stats, line_sums, make_stage,
+                      comb_windows, deinterlace, detect_active_area, detect_cuts, detect_scan, field_scores, field_stats, line_sums, make_stage,
                       pack_surface, pair_sad, remove_pulldown, surface_layout, surface_side, surface_table, unpack_surface)
+from .pulldown import check_comb_options
 from .scan import ScanVerdict, check_thresholds  # noqa: F401  (re-exported)
 
 
@@ -95,7 +97,7 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
                   out_siting: Optional[str] = None, chroma_filter: Optional[str] = None, crop=None, crop_limit=24,
                   bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None, pulldown_cycle: int = 5, *,
                   surface=None, out_surface=None, scan: Optional[str] = None, dither: Optional[str] = None, deinterlacer: str = "yadif",
-                  field_rate: str = "double") -> torch.Tensor:
+                  field_rate: str = "double", combed: Optional[str] = None, comb_threshold: int = 9, comb_pixels: int = 40) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
@@ -114,6 +116,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         surface_side(out_surface, spec.out, "out_surface")
     # (deinterlacer= / field_rate= also go with scan="detect": they say how an interlaced verdict is carried out)
     _check_field_options(deinterlacer, field_rate, fields, pulldown, scan is not None)
+    # (combed= also goes with scan="detect": it says how a telecine verdict is carried out, and is ignored for the other verdicts)
+    check_comb_options(combed, comb_threshold, comb_pixels, pulldown is not None or scan is not None, fields)
     if _check_scan(scan, fields, pulldown, pulldown_cycle) is not None:          # the content says what fields= / pulldown= would have said
         _field_frames(shaped, spec.inp, spec.size)
         _check_crop_args(crop, crop_limit, bars)          # (what does not depend on the verdict speaks before the GPU is touched)
@@ -123,6 +127,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
             frames, surface = _unpack_surface_device(frames, in_tab, spec.inp, spec.size), None
         found = _detect_scan_device(frames, spec.inp, spec.size).kwargs()
         fields, pulldown = found.get("fields"), found.get("pulldown")
+        if pulldown is None:
+            combed = None
     if _check_fields(fields) is not None:          # everything below sees the progressive video of 2N frames (field_rate "same": N)
         _field_frames(shaped, spec.inp, spec.size)
         if field_rate != "same":
@@ -151,7 +157,7 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     if fields is not None:             # deinterlacing comes first, before the crop
         frames = _deinterlace_device(frames, fields, spec.inp, spec.size, method=deinterlacer, rate=field_rate)
     if pulldown is not None:           # pulldown removal comes first, where deinterlacing comes
-        frames = _remove_pulldown_device(frames, pulldown, spec.inp, spec.size, pulldown_cycle)[0]
+        frames = _remove_pulldown_device(frames, pulldown, spec.inp, spec.size, pulldown_cycle, combed, comb_threshold, comb_pixels)[0]
     full = spec
     if crop == "auto":
         crop = _detect_device(frames, spec.inp, spec.size, crop_limit)
@@ -212,7 +218,9 @@ class VideoUpscaler:
     pulldown="tff" / "bff", pulldown_cycle=5: telecined chunks, as in upscale_video, through a prepass.PulldownRemover: a pushed frame is
     woven at once, woven frames wait until their cycle is complete, and finish() flushes the partial last cycle whole (at most
     pulldown_cycle + 1 more frames on the device between pushes; two host synchronisations per push).  `pulldown_info` has the matches
-    and the kept indices so far.
+    and the kept indices so far.  combed="yadif" / "bwdif", comb_threshold=9, comb_pixels=40 (keyword only): as in upscale_video; a
+    woven frame is final once the next one exists, so the stage holds two frames more (pulldown_cycle + 3), and `pulldown_info` gains
+    "combed", the woven frames that were deinterlaced.
 
     surface= / out_surface= (savsr_amd.surface.Surface): as in upscale_video; every pushed chunk is [k, stride] uint8 in `surface` and is
     unpacked as it arrives, every returned chunk is packed into `out_surface` as it leaves.  The conversion is stateless, so any chunking
@@ -229,7 +237,8 @@ class VideoUpscaler:
                  depth: int = 8, out_depth: Optional[int] = None, siting: Optional[str] = None, out_siting: Optional[str] = None,
                  chroma_filter: Optional[str] = None, crop=None, bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None,
                  pulldown_cycle: int = 5, *, surface=None, out_surface=None, scan: Optional[str] = None, dither: Optional[str] = None,
-                 deinterlacer: str = "yadif", field_rate: str = "double"):
+                 deinterlacer: str = "yadif", field_rate: str = "double", combed: Optional[str] = None, comb_threshold: int = 9,
+                 comb_pixels: int = 40):
         _check_net(net)
         check_padding(padding)
         _check_scan(scan, fields, pulldown, pulldown_cycle, auto_ok=False)          # (None is the only value that passes: the path as it was)
@@ -246,7 +255,8 @@ class VideoUpscaler:
         self.spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter,
                                dither)
         self._full = self.spec                     # the spec of the chunks as pushed; `spec` becomes the cropped size's with a crop
-        self._split = make_stage(fields, pulldown, pulldown_cycle, self.spec.inp, self.spec.size, deinterlacer, field_rate)          # the stage in front; None: as it was
+        self._split = make_stage(fields, pulldown, pulldown_cycle, self.spec.inp, self.spec.size, deinterlacer, field_rate, combed, comb_threshold,
+                                 comb_pixels)          # the stage in front; None: as it was
         self._rect = _check_crop_args(crop, 24, bars, auto_ok=False)          # the rect to crop every chunk to; None: no crop, as it was
         self.bars = bars
         if self._rect is not None and self.spec.size:
@@ -294,7 +304,7 @@ class VideoUpscaler:
     @property
     def pulldown_info(self) -> Optional[dict]:
         """{"matches", "kept"} of the frames pushed so far: per source frame -1 (its second field came from its predecessor) or 0, and the
-        indices of the woven frames that went on (None without pulldown=)."""
+        indices of the woven frames that went on (None without pulldown=); with combed= also "combed", the woven frames cleaned so far."""
         return self._split.info if isinstance(self._split, PulldownRemover) else None
 
     @property

@@ -22,6 +22,16 @@ inline unsigned long long atomicAdd(unsigned long long* cell, unsigned long long
     *cell = old + v;
     return old;
 }
+inline unsigned long long atomicMax(unsigned long long* cell, unsigned long long v) {          // (the comb kernel's, checked by check_comb_host.py)
+    const unsigned long long old = *cell;
+    *cell = old > v ? old : v;
+    return old;
+}
+inline uint32_t atomicAdd(uint32_t* cell, uint32_t v) {
+    const uint32_t old = *cell;
+    *cell = old + v;
+    return old;
+}
 namespace savsr {
 inline void set_error(const char* fmt, ...) {
     va_list ap;
