@@ -23,6 +23,7 @@
 // below 2^13).  Rate 1 ("same") launches one output frame per source frame, its first field in time: the second fields are not computed.
 #include "common.hpp"
 #include "video_samples.hpp"
+#include "field_matrix.hpp"
 
 #include <cstdint>
 
@@ -34,7 +35,7 @@ constexpr int DI_TILE_IROWS = 16;                   // interpolated rows of a ve
 constexpr int DI_TILE_BYTES = 256;                  // bytes of a vector tile's row: 16 lanes x 16 bytes
 constexpr int DI_ONE_IROWS = 4;                     // interpolated rows of a one-sample tile (one per wave)
 constexpr int DI_ONE_COLS = 64;                     // samples of a one-sample tile's row
-constexpr int DI_MAX_Z = 65535;                     // grid.z
+constexpr int DI_MAX_OUT = FM_MAX_FRAMES - 1;       // output frames of a launch: an even count, so that a launch starts at field 0 of a source frame
 constexpr int DI_MAX_ROWS = 65535 * 2 * DI_ONE_IROWS;          // grid.y of the one-sample form
 
 template <int BYTES>
@@ -136,10 +137,12 @@ __device__ __forceinline__ int bwdif(const BTaps& t, bool inner, bool line, int 
 }
 
 // What a launch works on.  Rows are `pitch` bytes apart on both sides.
+// (Not an extension of FieldMatrix: the kernels read every field here and have no use for its shift, and with the two sides' fields apart
+// every kernel's scalar-register count moved.)
 struct Job {
     const uint8_t* src;          // plane of resident frame 0
     uint8_t* dst;                // plane of output frame 0
-    long long src_stride, dst_stride, pitch;
+    long long stride, dst_stride, pitch;
     int n_frames, from, rows, cols, order, top;          // cols: samples of a row; top: 2^depth - 1
     int same;                                            // 1: output frame o is field 0 of source frame from + o (rate "same")
     const int32_t* flags;                                // masked entries (device, one per output frame of the launch): 0: copy the frame
@@ -160,9 +163,9 @@ __device__ __forceinline__ bool locate(const Job& jb, int o, int ri, Where& w) {
     const int y = 2 * ri + (1 - p);
     if (y >= jb.rows) return false;
     const int np = n > 0 ? n - 1 : 0, nn = n + 1 < jb.n_frames ? n + 1 : jb.n_frames - 1;
-    w.cur = jb.src + (long long)n * jb.src_stride;
-    w.prev = jb.src + (long long)np * jb.src_stride;
-    w.next = jb.src + (long long)nn * jb.src_stride;
+    w.cur = jb.src + (long long)n * jb.stride;
+    w.prev = jb.src + (long long)np * jb.stride;
+    w.next = jb.src + (long long)nn * jb.stride;
     w.p2 = f == 0 ? w.prev : w.cur;
     w.n2 = f == 0 ? w.cur : w.next;
     w.out = jb.dst + (long long)o * jb.dst_stride;
@@ -395,62 +398,58 @@ __global__ __launch_bounds__(DI_THREADS) void bwdif_one_kernel(Job jb) {
 
 // n_out output frames of source frames jb.from ...: two per source frame, or one with jb.same.  method 0: yadif, 1: bwdif.
 // MASKED: jb.flags has one entry per output frame (jb.same is 1); the workgroups of a frame whose entry is 0 copy it.
-template <int BYTES, bool MASKED = false>
-int launch_deinterlace(Job jb, int step, int n_out, hipStream_t st, int method = 0) {
-    const bool vec = ((reinterpret_cast<uintptr_t>(jb.src) | reinterpret_cast<uintptr_t>(jb.dst)) & 15) == 0 && jb.src_stride % 16 == 0 &&
-                     jb.dst_stride % 16 == 0 && jb.pitch % 16 == 0;
+template <int BYTES, bool MASKED>
+int launch_deinterlace(Job jb, int step, int n_out, hipStream_t st, int method) {
+    const bool vec = aligned16(jb.src, jb.stride, jb.pitch) && aligned16(jb.dst, jb.dst_stride, 0);
     const int irows = (jb.rows + 1) / 2;          // of the field with more interpolated rows; the other one's last tile row may be empty
-    for (int o0 = 0; o0 < n_out; o0 += DI_MAX_Z - 1) {          // (an even count per launch: a launch starts at field 0 of a source frame)
-        const int no = n_out - o0 < DI_MAX_Z - 1 ? n_out - o0 : DI_MAX_Z - 1;
+    const unsigned gx = vec ? blocks(jb.pitch, DI_TILE_BYTES) : blocks(jb.cols, DI_ONE_COLS), gy = blocks(irows, vec ? DI_TILE_IROWS : DI_ONE_IROWS);
+    return for_frame_chunks(n_out, DI_MAX_OUT, [&](int o0, int no) {
+        const dim3 grid(gx, gy, (unsigned)no), block(DI_THREADS);
         Job part = jb;
         part.from = jb.from + (jb.same ? o0 : o0 / 2);
         part.dst = jb.dst + (long long)o0 * jb.dst_stride;
         if (MASKED) part.flags = jb.flags + o0;
         if (method == 1) {
-            if (vec) {
-                const dim3 grid((unsigned)((jb.pitch + DI_TILE_BYTES - 1) / DI_TILE_BYTES), (unsigned)((irows + DI_TILE_IROWS - 1) / DI_TILE_IROWS), (unsigned)no);
-                hipLaunchKernelGGL((bwdif_vec_kernel<BYTES, MASKED>), grid, dim3(DI_THREADS), 0, st, part);
-            } else {
-                const dim3 grid((unsigned)((jb.cols + DI_ONE_COLS - 1) / DI_ONE_COLS), (unsigned)((irows + DI_ONE_IROWS - 1) / DI_ONE_IROWS), (unsigned)no);
-                hipLaunchKernelGGL((bwdif_one_kernel<BYTES, MASKED>), grid, dim3(DI_THREADS), 0, st, part);
-            }
-            if (int rc = check_launch(vec ? "bwdif_vec_kernel" : "bwdif_one_kernel")) return rc;
-            continue;
+            if (vec) hipLaunchKernelGGL((bwdif_vec_kernel<BYTES, MASKED>), grid, block, 0, st, part);
+            else hipLaunchKernelGGL((bwdif_one_kernel<BYTES, MASKED>), grid, block, 0, st, part);
+            return check_launch(vec ? "bwdif_vec_kernel" : "bwdif_one_kernel");
         }
-        if (vec) {
-            const dim3 grid((unsigned)((jb.pitch + DI_TILE_BYTES - 1) / DI_TILE_BYTES), (unsigned)((irows + DI_TILE_IROWS - 1) / DI_TILE_IROWS), (unsigned)no);
-            if (BYTES == 2) hipLaunchKernelGGL((deinterlace_vec_kernel<2, 1, MASKED>), grid, dim3(DI_THREADS), 0, st, part);
-            else if (step == 1) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 1, MASKED>), grid, dim3(DI_THREADS), 0, st, part);
-            else if (step == 2) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 2, MASKED>), grid, dim3(DI_THREADS), 0, st, part);
-            else if (step == 3) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 3, MASKED>), grid, dim3(DI_THREADS), 0, st, part);
-            else hipLaunchKernelGGL((deinterlace_vec_kernel<1, 4, MASKED>), grid, dim3(DI_THREADS), 0, st, part);
-        } else {
-            const dim3 grid((unsigned)((jb.cols + DI_ONE_COLS - 1) / DI_ONE_COLS), (unsigned)((irows + DI_ONE_IROWS - 1) / DI_ONE_IROWS), (unsigned)no);
-            hipLaunchKernelGGL((deinterlace_one_kernel<BYTES, MASKED>), grid, dim3(DI_THREADS), 0, st, part, step);
-        }
-        if (int rc = check_launch(vec ? "deinterlace_vec_kernel" : "deinterlace_one_kernel")) return rc;
-    }
-    return 0;
+        if (vec && BYTES == 2) hipLaunchKernelGGL((deinterlace_vec_kernel<2, 1, MASKED>), grid, block, 0, st, part);
+        else if (vec && step == 1) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 1, MASKED>), grid, block, 0, st, part);
+        else if (vec && step == 2) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 2, MASKED>), grid, block, 0, st, part);
+        else if (vec && step == 3) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 3, MASKED>), grid, block, 0, st, part);
+        else if (vec) hipLaunchKernelGGL((deinterlace_vec_kernel<1, 4, MASKED>), grid, block, 0, st, part);
+        else hipLaunchKernelGGL((deinterlace_one_kernel<BYTES, MASKED>), grid, block, 0, st, part, step);
+        return check_launch(vec ? "deinterlace_vec_kernel" : "deinterlace_one_kernel");
+    });
 }
 
-// The checks the two entries share; 0 or SAVSR_E_ARG with the message set.  row_bytes: of the matrix on both sides.
-int check_deinterlace(const char* who, const void* frames, const void* out, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows,
-                      int64_t row_bytes, int order, int from, int to, int64_t out_frame_bytes, int64_t out_plane_offset) {
-    char msg[160];
-    const char* why = nullptr;
-    if (!frames || !out) why = "null pointer";
-    else if (n_frames < 1) why = "n_frames >= 1";
-    else if (rows < 2) why = "rows >= 2 (a matrix of one row has no second field)";
-    else if (rows > DI_MAX_ROWS) why = "rows <= 524280";
-    else if (row_bytes < 1) why = "a row holds at least one sample";
-    else if (order != 0 && order != 1) why = "order 0 (tff) or 1 (bff)";
-    else if (from < 0 || to > n_frames || from >= to) why = "the range needs 0 <= from < to <= n_frames";
-    else if (plane_offset < 0 || out_plane_offset < 0) why = "plane offsets >= 0";
-    else if (frame_bytes < plane_offset + (int64_t)rows * row_bytes) why = "frame_bytes smaller than plane_offset plus the rows x row_bytes plane";
-    else if (out_frame_bytes < out_plane_offset + (int64_t)rows * row_bytes) why = "out_frame_bytes smaller than out_plane_offset plus the rows x row_bytes plane";
-    if (!why) return 0;
-    snprintf(msg, sizeof msg, "%s: %s", who, why);
-    return fail_arg(msg);
+
+// The body of the six entries.  width: row_bytes (_u8) or cols (_u16); sd: the pixel step (_u8) or the depth (_u16).  The plain entries pass
+// method 0, rate 0 and no flags; the masked ones ((ABI 49), behind the pulldown removal's combed=) rate 1 and their flags: rate "same" for
+// the frames whose flag is set, a byte copy of the others; the flags are a device table the entry cannot see.
+template <int BYTES, bool MASKED>
+int deinterlace(const char* who, const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int width, int sd, int order,
+                int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, int method, int rate, const int32_t* flags, void* stream) {
+    constexpr MatrixRule rule{2, DI_MAX_ROWS, "rows <= 524280", "the range needs 0 <= from < to <= n_frames", false};
+    const int64_t row_bytes = (int64_t)BYTES * width;
+    const char* why = check_matrix(rule, frames && out ? frames : nullptr, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to, out_plane_offset);
+    if (!why) why = check_out_plane(out_frame_bytes, out_plane_offset, rows, row_bytes);
+    if (why) return refuse(who, why);
+    if (BYTES == 1) {
+        if (sd < 1 || sd > 4 || width % sd) return refuse(who, "step 1 .. 4 and a divisor of row_bytes");
+    } else if (int rc = check_samples16(who, sd, frames, frame_bytes, plane_offset, true, out, out_frame_bytes, out_plane_offset)) {
+        return rc;
+    }
+    if (MASKED)
+        if (const char* bad = check_table(flags, !flags, "flags must be 4-byte aligned")) return refuse(who, bad);
+    if (method != 0 && method != 1) return refuse(who, "method 0 (yadif) or 1 (bwdif)");
+    if (rate != 0 && rate != 1) return refuse(who, "rate 0 (double) or 1 (same)");
+    if (MASKED && out < frames + (int64_t)n_frames * frame_bytes && frames < out + (int64_t)(to - from) * out_frame_bytes)
+        return refuse(who, "the source frames and the output overlap");
+    const Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, width, order,
+                 BYTES == 1 ? 255 : (1 << sd) - 1, rate, flags};
+    return launch_deinterlace<BYTES, MASKED>(jb, BYTES == 1 ? sd : 1, (rate ? 1 : 2) * (to - from), static_cast<hipStream_t>(stream), method);
 }
 
 }  // namespace
@@ -461,99 +460,41 @@ using namespace savsr;
 extern "C" int savsr_video_deinterlace_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes,
                                           int step, int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
                                           void* stream) {
-    if (int rc = check_deinterlace("video_deinterlace_u8", frames, out, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to,
-                                   out_frame_bytes, out_plane_offset))
-        return rc;
-    if (step < 1 || step > 4 || row_bytes % step) return fail_arg("video_deinterlace_u8: step 1 .. 4 and a divisor of row_bytes");
-    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, row_bytes, order, 255, 0, nullptr};
-    return launch_deinterlace<1>(jb, step, 2 * (to - from), static_cast<hipStream_t>(stream));
+    return deinterlace<1, false>("video_deinterlace_u8", frames, n_frames, frame_bytes, plane_offset, rows, row_bytes, step, order, from, to, out, out_frame_bytes,
+                                 out_plane_offset, 0, 0, nullptr, stream);
 }
 
 extern "C" int savsr_video_deinterlace_u8_m(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes,
                                             int step, int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
                                             int method, int rate, void* stream) {
-    if (int rc = check_deinterlace("video_deinterlace_u8_m", frames, out, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to,
-                                   out_frame_bytes, out_plane_offset))
-        return rc;
-    if (step < 1 || step > 4 || row_bytes % step) return fail_arg("video_deinterlace_u8_m: step 1 .. 4 and a divisor of row_bytes");
-    if (method != 0 && method != 1) return fail_arg("video_deinterlace_u8_m: method 0 (yadif) or 1 (bwdif)");
-    if (rate != 0 && rate != 1) return fail_arg("video_deinterlace_u8_m: rate 0 (double) or 1 (same)");
-    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, row_bytes, order, 255, rate, nullptr};
-    return launch_deinterlace<1>(jb, step, (rate ? 1 : 2) * (to - from), static_cast<hipStream_t>(stream), method);
+    return deinterlace<1, false>("video_deinterlace_u8_m", frames, n_frames, frame_bytes, plane_offset, rows, row_bytes, step, order, from, to, out, out_frame_bytes,
+                                 out_plane_offset, method, rate, nullptr, stream);
 }
 
 extern "C" int savsr_video_deinterlace_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols,
                                            int depth, int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
                                            void* stream) {
-    if (int rc = check_deinterlace("video_deinterlace_u16", frames, out, n_frames, frame_bytes, plane_offset, rows, 2 * (int64_t)cols, order, from, to,
-                                   out_frame_bytes, out_plane_offset))
-        return rc;
-    if (depth != 10 && depth != 12) return fail_arg("video_deinterlace_u16: depth 10 or 12 (8 bits: savsr_video_deinterlace_u8)");
-    if (((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(out)) & 1) || ((frame_bytes | plane_offset | out_frame_bytes | out_plane_offset) & 1))
-        return fail_arg("video_deinterlace_u16: frames, out, the frame strides and the plane offsets must be 2-byte aligned (16-bit samples)");
-    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, 2ll * cols, n_frames, from, rows, cols, order, (1 << depth) - 1, 0, nullptr};
-    return launch_deinterlace<2>(jb, 1, 2 * (to - from), static_cast<hipStream_t>(stream));
+    return deinterlace<2, false>("video_deinterlace_u16", frames, n_frames, frame_bytes, plane_offset, rows, cols, depth, order, from, to, out, out_frame_bytes,
+                                 out_plane_offset, 0, 0, nullptr, stream);
 }
 
 extern "C" int savsr_video_deinterlace_u16_m(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols,
                                              int depth, int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
                                              int method, int rate, void* stream) {
-    if (int rc = check_deinterlace("video_deinterlace_u16_m", frames, out, n_frames, frame_bytes, plane_offset, rows, 2 * (int64_t)cols, order, from, to,
-                                   out_frame_bytes, out_plane_offset))
-        return rc;
-    if (depth != 10 && depth != 12) return fail_arg("video_deinterlace_u16_m: depth 10 or 12 (8 bits: savsr_video_deinterlace_u8_m)");
-    if (((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(out)) & 1) || ((frame_bytes | plane_offset | out_frame_bytes | out_plane_offset) & 1))
-        return fail_arg("video_deinterlace_u16_m: frames, out, the frame strides and the plane offsets must be 2-byte aligned (16-bit samples)");
-    if (method != 0 && method != 1) return fail_arg("video_deinterlace_u16_m: method 0 (yadif) or 1 (bwdif)");
-    if (rate != 0 && rate != 1) return fail_arg("video_deinterlace_u16_m: rate 0 (double) or 1 (same)");
-    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, 2ll * cols, n_frames, from, rows, cols, order, (1 << depth) - 1, rate, nullptr};
-    return launch_deinterlace<2>(jb, 1, (rate ? 1 : 2) * (to - from), static_cast<hipStream_t>(stream), method);
+    return deinterlace<2, false>("video_deinterlace_u16_m", frames, n_frames, frame_bytes, plane_offset, rows, cols, depth, order, from, to, out, out_frame_bytes,
+                                 out_plane_offset, method, rate, nullptr, stream);
 }
-
-// (ABI 49) The masked entries: rate 1 ("same") for the frames whose flag is set, a byte copy of the others (the workgroups of an unflagged
-// frame copy their rows and do nothing else); the flags are a device table the entry cannot see.  Behind the pulldown removal's combed=.
-namespace savsr {
-namespace {
-
-int check_masked(const char* who, const uint8_t* frames, const uint8_t* out, int n_frames, int64_t frame_bytes, int from, int to, int64_t out_frame_bytes,
-                 int method, const int32_t* flags) {
-    char msg[160];
-    const char* why = nullptr;
-    if (!flags) why = "null pointer";
-    else if (reinterpret_cast<uintptr_t>(flags) & 3) why = "flags must be 4-byte aligned";
-    else if (method != 0 && method != 1) why = "method 0 (yadif) or 1 (bwdif)";
-    else if (out < frames + (int64_t)n_frames * frame_bytes && frames < out + (int64_t)(to - from) * out_frame_bytes) why = "the source frames and the output overlap";
-    if (!why) return 0;
-    snprintf(msg, sizeof msg, "%s: %s", who, why);
-    return fail_arg(msg);
-}
-
-}  // namespace
-}  // namespace savsr
 
 extern "C" int savsr_video_deinterlace_masked_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes,
                                                  int step, int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
                                                  int method, const int32_t* flags, void* stream) {
-    const char* who = "video_deinterlace_masked_u8";
-    if (int rc = check_deinterlace(who, frames, out, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to, out_frame_bytes, out_plane_offset))
-        return rc;
-    if (step < 1 || step > 4 || row_bytes % step) return fail_arg("video_deinterlace_masked_u8: step 1 .. 4 and a divisor of row_bytes");
-    if (int rc = check_masked(who, frames, out, n_frames, frame_bytes, from, to, out_frame_bytes, method, flags)) return rc;
-    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, row_bytes, order, 255, 1, flags};
-    return launch_deinterlace<1, true>(jb, step, to - from, static_cast<hipStream_t>(stream), method);
+    return deinterlace<1, true>("video_deinterlace_masked_u8", frames, n_frames, frame_bytes, plane_offset, rows, row_bytes, step, order, from, to, out, out_frame_bytes,
+                                 out_plane_offset, method, 1, flags, stream);
 }
 
 extern "C" int savsr_video_deinterlace_masked_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols,
                                                   int depth, int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
                                                   int method, const int32_t* flags, void* stream) {
-    const char* who = "video_deinterlace_masked_u16";
-    if (int rc = check_deinterlace(who, frames, out, n_frames, frame_bytes, plane_offset, rows, 2 * (int64_t)cols, order, from, to, out_frame_bytes,
-                                   out_plane_offset))
-        return rc;
-    if (depth != 10 && depth != 12) return fail_arg("video_deinterlace_masked_u16: depth 10 or 12 (8 bits: savsr_video_deinterlace_masked_u8)");
-    if (((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(out)) & 1) || ((frame_bytes | plane_offset | out_frame_bytes | out_plane_offset) & 1))
-        return fail_arg("video_deinterlace_masked_u16: frames, out, the frame strides and the plane offsets must be 2-byte aligned (16-bit samples)");
-    if (int rc = check_masked(who, frames, out, n_frames, frame_bytes, from, to, out_frame_bytes, method, flags)) return rc;
-    Job jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, 2ll * cols, n_frames, from, rows, cols, order, (1 << depth) - 1, 1, flags};
-    return launch_deinterlace<2, true>(jb, 1, to - from, static_cast<hipStream_t>(stream), method);
+    return deinterlace<2, true>("video_deinterlace_masked_u16", frames, n_frames, frame_bytes, plane_offset, rows, cols, depth, order, from, to, out, out_frame_bytes,
+                                 out_plane_offset, method, 1, flags, stream);
 }

@@ -14,8 +14,9 @@
 // (plane base pointer, frame stride and row bytes multiples of 16): a lane owns 16 bytes of one second-field row and issues its four
 // 16-byte nontemporal loads (a, c, the frame's own b and the previous frame's b) before the first use; v_sad_u8 per dword, |a - c|
 // shared by both candidates; no LDS staging of rows: the rows above and below are read by the two neighbouring scored rows as well and
-// come from L2.  One-sample form (any pointer, stride and row length): a lane owns PD_ONE_ITERS samples.  Lane sums are 32-bit, reduced
-// over the wave by __shfl_xor, over the workgroup through 8 LDS words, then one 64-bit vector atomic per workgroup and candidate.
+// come from L2.  One-sample form (any pointer, stride and row length): a lane owns PD_ONE_ITERS samples.  Lane sums are 32-bit and leave
+// the workgroup through field_matrix.hpp's block_reduce: one 64-bit vector atomic per workgroup and candidate.  The matrix, its checks
+// and the launch chunking are that header's.
 //
 // Weave.  Output frame o of source frame n = from + o: the rows of parity p from frame n, the others from frame clamp(n + delta[o], 0,
 // n_frames - 1); delta is a device table the entry cannot see, so the kernel clamps.  A byte copy at every depth: a 16-byte form and a
@@ -24,18 +25,19 @@
 // (ABI 49) Comb windows: the residual combing of woven frames, behind combed= (`comb_windows` is the specification); see the section below.
 #include "common.hpp"
 #include "video_samples.hpp"
+#include "field_matrix.hpp"
 
 #include <cstdint>
 
 namespace savsr {
 namespace {
 
-constexpr int PD_THREADS = 256;
+constexpr int PD_THREADS = FM_THREADS;
 constexpr int PD_ONE_ITERS = 8;                     // samples (bytes, for the weave) per lane in the one-sample forms
-constexpr int PD_MAX_Y = 65535;                     // grid.y: frames per launch
-constexpr long long PD_MAX_PLANE = 0x7fff0000ll;    // bytes of a plane: the lane tiles of a frame fit grid.x and 32-bit counts
+constexpr MatrixRule PD_RULE{1, 0, nullptr, "the range needs 0 <= from <= to <= n_frames", true};
 
-// What a score launch works on.  Rows are `pitch` bytes apart.
+// What a score launch works on.  A lane sum is at most PD_ONE_ITERS (or 16, the bytes of a vector lane's row piece) x 3 x 255 <= 12240.
+// (Not an extension of FieldMatrix: the scored rows stand for its rows, and behind it they moved a kernel's scalar-register count.)
 struct ScoreJob {
     const uint8_t* src;          // the matrix of resident frame 0
     long long stride, pitch;     // bytes between frames / rows
@@ -44,34 +46,6 @@ struct ScoreJob {
     uint32_t top;                // 2^depth - 1
     int shift;                   // depth - 8
 };
-
-// The two lane sums of a workgroup -> one 64-bit vector atomic per candidate on cell[0] / cell[1].  A lane sum is at most
-// PD_ONE_ITERS (or 16, the bytes of a vector lane's row piece) x 3 x 255 <= 12240, a workgroup's at most 256 x 12240 < 2^22: the 32-bit
-// partials cannot overflow whatever the frame size, because a lane never holds more than one row piece.
-__device__ __forceinline__ void pd_block_add(uint32_t acc0, uint32_t acc1, unsigned long long* cell) {
-#ifdef SAVSR_HOST_CHECK          // the host check runs one thread at a time: every thread adds its own sums
-    if (acc0) atomicAdd(cell, (unsigned long long)acc0);
-    if (acc1) atomicAdd(cell + 1, (unsigned long long)acc1);
-#else
-    __shared__ uint32_t part[2][PD_THREADS / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        acc0 += __shfl_xor(acc0, o, 64);
-        acc1 += __shfl_xor(acc1, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        part[0][threadIdx.x >> 6] = acc0;
-        part[1][threadIdx.x >> 6] = acc1;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        unsigned long long s = 0;
-#pragma unroll
-        for (int i = 0; i < PD_THREADS / 64; ++i) s += part[threadIdx.x][i];
-        if (s) atomicAdd(cell + threadIdx.x, s);
-    }
-#endif
-}
 
 // Vector form: lane = (scored row s, 16-byte chunk) = (idx / chunks, idx % chunks), idx = blockIdx.x * PD_THREADS + threadIdx.x; frame
 // blockIdx.y of the launch.  BYTES: of a sample.
@@ -109,13 +83,8 @@ __global__ __launch_bounds__(PD_THREADS) void field_scores_vec_kernel(ScoreJob j
         acc0 -= ac;          // per sample |a - b| + |c - b| >= |a - c|: the sums stay >= 0
         acc1 -= ac;
     }
-    pd_block_add(acc0, acc1, out + 2 * blockIdx.y);
-}
-
-template <int BYTES>
-__device__ __forceinline__ uint32_t pd_sample(const uint8_t* row, uint32_t x, uint32_t top, int shift) {
-    if constexpr (BYTES == 1) return row[x];
-    else return msb8(reinterpret_cast<const uint16_t*>(row)[x], top, shift);
+    const uint32_t acc[2] = {acc0, acc1};
+    block_reduce<2, 1>(acc, out + 2 * blockIdx.y);
 }
 
 // One-sample form: sample i = (scored row, x) = (i / cols, i % cols), i = blockIdx.x * (PD_THREADS * PD_ONE_ITERS) + it * PD_THREADS + tid.
@@ -134,45 +103,39 @@ __global__ __launch_bounds__(PD_THREADS) void field_scores_one_kernel(ScoreJob j
         if (i < total) {
             const uint32_t s = i / (uint32_t)jb.cols, x = i - s * (uint32_t)jb.cols;
             const long long off = (jb.y0 + 2ll * s) * jb.pitch;
-            const uint32_t a = pd_sample<BYTES>(cur + off - jb.pitch, x, jb.top, jb.shift), c = pd_sample<BYTES>(cur + off + jb.pitch, x, jb.top, jb.shift);
-            const uint32_t b0 = pd_sample<BYTES>(prev + off, x, jb.top, jb.shift), b1 = pd_sample<BYTES>(cur + off, x, jb.top, jb.shift);
+            const uint32_t a = sample8<BYTES>(cur + off - jb.pitch, x, jb.top, jb.shift), c = sample8<BYTES>(cur + off + jb.pitch, x, jb.top, jb.shift);
+            const uint32_t b0 = sample8<BYTES>(prev + off, x, jb.top, jb.shift), b1 = sample8<BYTES>(cur + off, x, jb.top, jb.shift);
             const uint32_t ac = absdiff(a, c);
             acc0 += absdiff(a, b0) + absdiff(c, b0) - ac;
             acc1 += absdiff(a, b1) + absdiff(c, b1) - ac;
         }
     }
-    pd_block_add(acc0, acc1, out + 2 * blockIdx.y);
+    const uint32_t acc[2] = {acc0, acc1};
+    block_reduce<2, 1>(acc, out + 2 * blockIdx.y);
 }
-
-inline unsigned pd_blocks(long long units, int per_block) { return (unsigned)((units + per_block - 1) / per_block); }
 
 template <int BYTES>
 int launch_scores(ScoreJob jb, int n_out, int64_t* out, hipStream_t st, const char* what) {
-    hipError_t e = hipMemsetAsync(out, 0, sizeof(int64_t) * 2 * (size_t)n_out, st);
-    if (e != hipSuccess) { set_error("%s: hipMemsetAsync failed: %s", what, hipGetErrorString(e)); return (int)e; }
+    if (int rc = clear_cells(out, 2, n_out, st, what)) return rc;
     if (jb.srows < 1) return 0;          // fewer than three rows, or no second-field row between two others: zeros
-    const bool vec = (reinterpret_cast<uintptr_t>(jb.src) & 15) == 0 && jb.stride % 16 == 0 && jb.pitch % 16 == 0;
-    const unsigned gx = vec ? pd_blocks((long long)jb.srows * (jb.pitch >> 4), PD_THREADS)
-                            : pd_blocks((long long)jb.srows * jb.cols, PD_THREADS * PD_ONE_ITERS);
-    for (int f0 = 0; f0 < n_out; f0 += PD_MAX_Y) {
-        const int nf = n_out - f0 < PD_MAX_Y ? n_out - f0 : PD_MAX_Y;
+    const bool vec = aligned16(jb.src, jb.stride, jb.pitch);
+    const unsigned gx = vec ? blocks((long long)jb.srows * (jb.pitch >> 4), PD_THREADS) : blocks((long long)jb.srows * jb.cols, PD_THREADS * PD_ONE_ITERS);
+    return for_frame_chunks(n_out, FM_MAX_FRAMES, [&](int f0, int nf) {
         ScoreJob part = jb;
         part.from = jb.from + f0;
         unsigned long long* cells = reinterpret_cast<unsigned long long*>(out) + 2ll * f0;
         if (vec) hipLaunchKernelGGL((field_scores_vec_kernel<BYTES>), dim3(gx, (unsigned)nf), dim3(PD_THREADS), 0, st, part, cells);
         else hipLaunchKernelGGL((field_scores_one_kernel<BYTES>), dim3(gx, (unsigned)nf), dim3(PD_THREADS), 0, st, part, cells);
-        if (int rc = check_launch(vec ? "field_scores_vec_kernel" : "field_scores_one_kernel")) return rc;
-    }
-    return 0;
+        return check_launch(vec ? "field_scores_vec_kernel" : "field_scores_one_kernel");
+    });
 }
 
 // What a weave launch works on.  Rows are `pitch` bytes apart on both sides.
-struct WeaveJob {
-    const uint8_t* src;          // the plane of resident frame 0
+struct WeaveJob : FieldMatrix {
     uint8_t* dst;                // the plane of output frame 0
     const int32_t* delta;        // device: one of -1, 0 per output frame of the launch
-    long long src_stride, dst_stride, pitch;
-    int n_frames, from, rows, parity;
+    long long dst_stride;
+    int parity;
 };
 
 // The source row of output row y of output frame o: frame n where y has the first field's parity, else frame clamp(n + delta[o]).
@@ -183,7 +146,7 @@ __device__ __forceinline__ const uint8_t* weave_row(const WeaveJob& jb, int o, u
         m = n + jb.delta[o];
         m = m < 0 ? 0 : (m > jb.n_frames - 1 ? jb.n_frames - 1 : m);
     }
-    return jb.src + (long long)m * jb.src_stride + (long long)y * jb.pitch;
+    return jb.src + (long long)m * jb.stride + (long long)y * jb.pitch;
 }
 
 // 16-byte form: lane = (row, chunk) = (idx / chunks, idx % chunks); output frame blockIdx.y of the launch.
@@ -226,6 +189,7 @@ constexpr int CW_TILE_BYTES = 512;         // bytes of a tile's row (without the
 constexpr int CW_MAX_TC = CW_TILE_BYTES / CW_CELL;          // cell columns of a tile: at most 64 (8-byte cells)
 constexpr int CW_LROWS = (CW_TR + 1) * CW_CELL / 2;         // second-field rows of a tile with its halo
 
+// (Not an extension of FieldMatrix, like ScoreJob: the kernels have no use for n_frames, and with it their argument loads changed.)
 struct CombJob {
     const uint8_t* src;          // the matrix of resident frame 0
     long long stride, pitch;     // bytes between frames / rows
@@ -293,8 +257,8 @@ __device__ __forceinline__ void comb_count(const CombJob& jb, int tx, int ty, in
             const int y = yt + 2 * lr + jb.q;
             if (y < 1 || y > jb.rows - 2) continue;
             const uint8_t* row = cur + (long long)y * jb.pitch;
-            if (pd_combed(pd_sample<BYTES>(row - jb.pitch, (uint32_t)x, jb.top, jb.shift), pd_sample<BYTES>(row, (uint32_t)x, jb.top, jb.shift),
-                          pd_sample<BYTES>(row + jb.pitch, (uint32_t)x, jb.top, jb.shift), jb.thresh2))
+            if (pd_combed(sample8<BYTES>(row - jb.pitch, (uint32_t)x, jb.top, jb.shift), sample8<BYTES>(row, (uint32_t)x, jb.top, jb.shift),
+                          sample8<BYTES>(row + jb.pitch, (uint32_t)x, jb.top, jb.shift), jb.thresh2))
                 atomicAdd(&cells[lr >> 2][x / jb.cell_w - cc0], 1u);
         }
     }
@@ -318,6 +282,7 @@ __global__ __launch_bounds__(PD_THREADS) void comb_windows_kernel(CombJob jb, un
     const int n = jb.from + (int)blockIdx.y;
     unsigned long long* cell = out + 2 * blockIdx.y;
     uint32_t mx = 0, total = 0;
+    // (The reduction stays here, not in block_reduce: a maximum beside a sum, both sent by thread 0; sent by two threads the kernels' code changed.)
 #ifdef SAVSR_HOST_CHECK          // the host check runs one thread at a time: the first clears the cells, the last sums every lane's windows
     static CombCells cells;
     if (threadIdx.x == 0) memset(cells, 0, sizeof cells);
@@ -359,57 +324,53 @@ __global__ __launch_bounds__(PD_THREADS) void comb_windows_kernel(CombJob jb, un
 
 template <int BYTES>
 int launch_comb(CombJob jb, int n_out, int64_t* out, hipStream_t st, const char* what) {
-    hipError_t e = hipMemsetAsync(out, 0, sizeof(int64_t) * 2 * (size_t)n_out, st);
-    if (e != hipSuccess) { set_error("%s: hipMemsetAsync failed: %s", what, hipGetErrorString(e)); return (int)e; }
+    if (int rc = clear_cells(out, 2, n_out, st, what)) return rc;
     if (jb.rows < 3) return 0;          // no second-field row between two others: zeros
-    const bool vec = (reinterpret_cast<uintptr_t>(jb.src) & 15) == 0 && jb.stride % 16 == 0 && jb.pitch % 16 == 0;
+    const bool vec = aligned16(jb.src, jb.stride, jb.pitch);
     const unsigned gx = (unsigned)jb.tiles_x * (unsigned)((jb.ncr + CW_TR - 1) / CW_TR);
-    for (int f0 = 0; f0 < n_out; f0 += PD_MAX_Y) {
-        const int nf = n_out - f0 < PD_MAX_Y ? n_out - f0 : PD_MAX_Y;
+    return for_frame_chunks(n_out, FM_MAX_FRAMES, [&](int f0, int nf) {
         CombJob part = jb;
         part.from = jb.from + f0;
         unsigned long long* cells = reinterpret_cast<unsigned long long*>(out) + 2ll * f0;
         if (vec) hipLaunchKernelGGL((comb_windows_kernel<BYTES, true>), dim3(gx, (unsigned)nf), dim3(PD_THREADS), 0, st, part, cells);
         else hipLaunchKernelGGL((comb_windows_kernel<BYTES, false>), dim3(gx, (unsigned)nf), dim3(PD_THREADS), 0, st, part, cells);
-        if (int rc = check_launch("comb_windows_kernel")) return rc;
-    }
-    return 0;
+        return check_launch("comb_windows_kernel");
+    });
 }
 
-// bytes: of a sample; step: the samples of a pixel.
-CombJob comb_job(const uint8_t* frames, int64_t frame_bytes, int64_t plane_offset, int from, int rows, int64_t row_bytes, int cols, int bytes, int step,
-                 int order, int depth, int threshold) {
-    const int cell_w = CW_CELL * step, tc = CW_TILE_BYTES / (cell_w * bytes);
-    const int ncr = (rows + CW_CELL - 1) / CW_CELL, ncc = (cols + cell_w - 1) / cell_w;
-    return CombJob{frames + plane_offset, frame_bytes, row_bytes, from, rows, cols, 1 - order, cell_w, ncr, ncc, tc, (ncc + tc - 1) / tc,
-                   (1u << depth) - 1u, depth - 8, 2u * (uint32_t)threshold};
+// The checks the reducing entries share (`samples16`: the entry is a _u16 one); the cells' own come after the entry's.
+int check_reducing(const char* who, bool samples16, const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows,
+                   int64_t row_bytes, int depth, int order, int from, int to) {
+    if (const char* why = check_matrix(PD_RULE, frames, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to)) return refuse(who, why);
+    return samples16 ? check_samples16(who, depth, frames, frame_bytes, plane_offset) : 0;
 }
 
-// The checks of a matrix inside resident frames; nullptr or the reason.
-const char* check_matrix(const void* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int64_t row_bytes, int order, int from,
-                         int to) {
-    if (!frames) return "null pointer";
-    if (n_frames < 1) return "n_frames >= 1";
-    if (rows < 1) return "rows >= 1";
-    if (row_bytes < 1) return "a row holds at least one sample";
-    if ((long long)rows * row_bytes > PD_MAX_PLANE) return "a plane of at most 2147418112 bytes";
-    if (order != 0 && order != 1) return "order 0 (tff) or 1 (bff)";
-    if (from < 0 || to > n_frames || from > to) return "the range needs 0 <= from <= to <= n_frames";
-    if (plane_offset < 0) return "plane offsets >= 0";
-    if (frame_bytes < plane_offset + (int64_t)rows * row_bytes) return "frame_bytes smaller than plane_offset plus the rows x row_bytes plane";
-    return nullptr;
-}
-
-int refuse(const char* who, const char* why) {
-    char msg[192];
-    snprintf(msg, sizeof msg, "%s: %s", who, why);
-    return fail_arg(msg);
-}
-
-ScoreJob score_job(const uint8_t* frames, int64_t frame_bytes, int64_t plane_offset, int n_frames, int from, int rows, int64_t row_bytes, int cols,
-                   int order, int depth) {
+// The body of the two score entries.  width: row_bytes (_u8) or cols (_u16).
+template <int BYTES>
+int field_scores(const char* who, const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int width, int depth,
+                 int order, int from, int to, int64_t* out, void* stream) {
+    if (int rc = check_reducing(who, BYTES == 2, frames, n_frames, frame_bytes, plane_offset, rows, (int64_t)BYTES * width, depth, order, from, to)) return rc;
+    if (const char* why = check_cells(out, to > from)) return refuse(who, why);
+    if (to == from) return 0;
     const int srows = rows - 1 - order > 0 ? (rows - 1 - order) / 2 : 0;
-    return ScoreJob{frames + plane_offset, frame_bytes, row_bytes, n_frames, from, cols, 1 + order, srows, (1u << depth) - 1u, depth - 8};
+    const ScoreJob jb{frames + plane_offset, frame_bytes, (long long)BYTES * width, n_frames, from, width, 1 + order, srows, (1u << depth) - 1u, depth - 8};
+    return launch_scores<BYTES>(jb, to - from, out, static_cast<hipStream_t>(stream), who);
+}
+
+// The body of the two comb entries.  step: the samples of a pixel (1 for _u16).
+template <int BYTES>
+int comb_windows(const char* who, const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int width, int step,
+                 int depth, int order, int from, int to, int threshold, int64_t* out, void* stream) {
+    if (int rc = check_reducing(who, BYTES == 2, frames, n_frames, frame_bytes, plane_offset, rows, (int64_t)BYTES * width, depth, order, from, to)) return rc;
+    if (step < 1 || step > 4) return refuse(who, "step 1 .. 4");
+    if (threshold < 0 || threshold > 255) return refuse(who, "threshold 0 .. 255");
+    if (const char* why = check_cells(out, to > from)) return refuse(who, why);
+    if (to == from) return 0;
+    const int cell_w = CW_CELL * step, tc = CW_TILE_BYTES / (cell_w * BYTES);
+    const int ncr = (rows + CW_CELL - 1) / CW_CELL, ncc = (width + cell_w - 1) / cell_w;
+    const CombJob jb{frames + plane_offset, frame_bytes, (long long)BYTES * width, from, rows, width, 1 - order, cell_w, ncr, ncc, tc, (ncc + tc - 1) / tc,
+                     (1u << depth) - 1u, depth - 8, 2u * (uint32_t)threshold};
+    return launch_comb<BYTES>(jb, to - from, out, static_cast<hipStream_t>(stream), who);
 }
 
 }  // namespace
@@ -419,81 +380,47 @@ using namespace savsr;
 
 extern "C" int savsr_video_field_scores_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes,
                                            int order, int from, int to, int64_t* out, void* stream) {
-    const char* who = "video_field_scores_u8";
-    if (const char* why = check_matrix(frames, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to)) return refuse(who, why);
-    if (!out && to > from) return refuse(who, "null pointer");
-    if (reinterpret_cast<uintptr_t>(out) & 7) return refuse(who, "out must be 8-byte aligned");
-    if (to == from) return 0;
-    return launch_scores<1>(score_job(frames, frame_bytes, plane_offset, n_frames, from, rows, row_bytes, row_bytes, order, 8), to - from, out,
-                            static_cast<hipStream_t>(stream), who);
+    return field_scores<1>("video_field_scores_u8", frames, n_frames, frame_bytes, plane_offset, rows, row_bytes, 8, order, from, to, out, stream);
 }
 
 extern "C" int savsr_video_field_scores_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols,
                                             int depth, int order, int from, int to, int64_t* out, void* stream) {
-    const char* who = "video_field_scores_u16";
-    if (const char* why = check_matrix(frames, n_frames, frame_bytes, plane_offset, rows, 2 * (int64_t)cols, order, from, to)) return refuse(who, why);
-    if (depth != 10 && depth != 12) return refuse(who, "depth 10 or 12 (8 bits: savsr_video_field_scores_u8)");
-    if ((reinterpret_cast<uintptr_t>(frames) & 1) || ((frame_bytes | plane_offset) & 1))
-        return refuse(who, "frames, the frame stride and the plane offset must be 2-byte aligned (16-bit samples)");
-    if (!out && to > from) return refuse(who, "null pointer");
-    if (reinterpret_cast<uintptr_t>(out) & 7) return refuse(who, "out must be 8-byte aligned");
-    if (to == from) return 0;
-    return launch_scores<2>(score_job(frames, frame_bytes, plane_offset, n_frames, from, rows, 2 * (int64_t)cols, cols, order, depth), to - from, out,
-                            static_cast<hipStream_t>(stream), who);
+    return field_scores<2>("video_field_scores_u16", frames, n_frames, frame_bytes, plane_offset, rows, cols, depth, order, from, to, out, stream);
 }
 
 extern "C" int savsr_video_comb_windows_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes,
                                            int step, int order, int from, int to, int threshold, int64_t* out, void* stream) {
-    const char* who = "video_comb_windows_u8";
-    if (const char* why = check_matrix(frames, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to)) return refuse(who, why);
-    if (step < 1 || step > 4) return refuse(who, "step 1 .. 4");
-    if (threshold < 0 || threshold > 255) return refuse(who, "threshold 0 .. 255");
-    if (!out && to > from) return refuse(who, "null pointer");
-    if (reinterpret_cast<uintptr_t>(out) & 7) return refuse(who, "out must be 8-byte aligned");
-    if (to == from) return 0;
-    return launch_comb<1>(comb_job(frames, frame_bytes, plane_offset, from, rows, row_bytes, row_bytes, 1, step, order, 8, threshold), to - from, out,
-                          static_cast<hipStream_t>(stream), who);
+    return comb_windows<1>("video_comb_windows_u8", frames, n_frames, frame_bytes, plane_offset, rows, row_bytes, step, 8, order, from, to, threshold, out,
+                           stream);
 }
 
 extern "C" int savsr_video_comb_windows_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols,
                                             int depth, int order, int from, int to, int threshold, int64_t* out, void* stream) {
-    const char* who = "video_comb_windows_u16";
-    if (const char* why = check_matrix(frames, n_frames, frame_bytes, plane_offset, rows, 2 * (int64_t)cols, order, from, to)) return refuse(who, why);
-    if (depth != 10 && depth != 12) return refuse(who, "depth 10 or 12 (8 bits: savsr_video_comb_windows_u8)");
-    if ((reinterpret_cast<uintptr_t>(frames) & 1) || ((frame_bytes | plane_offset) & 1))
-        return refuse(who, "frames, the frame stride and the plane offset must be 2-byte aligned (16-bit samples)");
-    if (threshold < 0 || threshold > 255) return refuse(who, "threshold 0 .. 255");
-    if (!out && to > from) return refuse(who, "null pointer");
-    if (reinterpret_cast<uintptr_t>(out) & 7) return refuse(who, "out must be 8-byte aligned");
-    if (to == from) return 0;
-    return launch_comb<2>(comb_job(frames, frame_bytes, plane_offset, from, rows, 2 * (int64_t)cols, cols, 2, 1, order, depth, threshold), to - from, out,
-                          static_cast<hipStream_t>(stream), who);
+    return comb_windows<2>("video_comb_windows_u16", frames, n_frames, frame_bytes, plane_offset, rows, cols, 1, depth, order, from, to, threshold, out,
+                           stream);
 }
 
+// A byte copy at every depth, so one entry: the _u8 body of a pair without a _u16 sibling.
 extern "C" int savsr_video_weave(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes, int order,
                                  int from, int to, const int32_t* delta, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
                                  void* stream) {
     const char* who = "video_weave";
-    if (const char* why = check_matrix(frames, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to)) return refuse(who, why);
-    if (to > from && (!delta || !out)) return refuse(who, "null pointer");
-    if (reinterpret_cast<uintptr_t>(delta) & 3) return refuse(who, "delta must be 4-byte aligned");
-    if (out_plane_offset < 0) return refuse(who, "plane offsets >= 0");
-    if (out_frame_bytes < out_plane_offset + (int64_t)rows * row_bytes) return refuse(who, "out_frame_bytes smaller than out_plane_offset plus the rows x row_bytes plane");
+    if (const char* why = check_matrix(PD_RULE, frames, n_frames, frame_bytes, plane_offset, rows, row_bytes, order, from, to)) return refuse(who, why);
+    if (const char* why = check_table(delta, to > from && (!delta || !out), "delta must be 4-byte aligned")) return refuse(who, why);
+    if (const char* why = check_out_plane(out_frame_bytes, out_plane_offset, rows, row_bytes)) return refuse(who, why);
     if (to == from) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    WeaveJob jb{frames + plane_offset, out + out_plane_offset, delta, frame_bytes, out_frame_bytes, row_bytes, n_frames, from, rows, order};
-    const bool vec = ((reinterpret_cast<uintptr_t>(jb.src) | reinterpret_cast<uintptr_t>(jb.dst)) & 15) == 0 && frame_bytes % 16 == 0 &&
-                     out_frame_bytes % 16 == 0 && row_bytes % 16 == 0;
-    const unsigned gx = vec ? pd_blocks((long long)rows * (row_bytes >> 4), PD_THREADS) : pd_blocks((long long)rows * row_bytes, PD_THREADS * PD_ONE_ITERS);
-    for (int f0 = 0; f0 < to - from; f0 += PD_MAX_Y) {
-        const int nf = to - from - f0 < PD_MAX_Y ? to - from - f0 : PD_MAX_Y;
+    const WeaveJob jb{field_matrix<1>(frames, n_frames, frame_bytes, plane_offset, rows, row_bytes, 8, from), out + out_plane_offset, delta, out_frame_bytes,
+                      order};
+    const bool vec = aligned16(jb.src, jb.stride, jb.pitch) && aligned16(jb.dst, jb.dst_stride, 0);
+    const unsigned gx = vec ? blocks((long long)rows * (row_bytes >> 4), PD_THREADS) : blocks((long long)rows * row_bytes, PD_THREADS * PD_ONE_ITERS);
+    return for_frame_chunks(to - from, FM_MAX_FRAMES, [&](int f0, int nf) {
         WeaveJob part = jb;
         part.from = from + f0;
         part.delta = delta + f0;
         part.dst = jb.dst + (long long)f0 * out_frame_bytes;
         if (vec) hipLaunchKernelGGL(weave_vec_kernel, dim3(gx, (unsigned)nf), dim3(PD_THREADS), 0, st, part);
         else hipLaunchKernelGGL(weave_one_kernel, dim3(gx, (unsigned)nf), dim3(PD_THREADS), 0, st, part);
-        if (int rc = check_launch(vec ? "weave_vec_kernel" : "weave_one_kernel")) return rc;
-    }
-    return 0;
+        return check_launch(vec ? "weave_vec_kernel" : "weave_one_kernel");
+    });
 }

@@ -342,11 +342,34 @@ def _field_frames(frames: torch.Tensor, side: Side, size: Size) -> Tuple[int, in
     return n, c, h, w
 
 
-def _field_job(frames: torch.Tensor, order: str, side: Side, size: Size, hi: Optional[int]):
-    """What the three field kernels' wrappers share: (the contiguous resident frames, their count, hi (default: all), the channels of
-    packed frames (0: planar), the plane table, the order's id)."""
+def _field_job(frames: torch.Tensor, order: Optional[str], side: Side, size: Size, hi: Optional[int]):
+    """What the field kernels' wrappers share: (the contiguous resident frames, their count, hi (default: all), the channels of
+    packed frames (0: planar), the plane table, the order's id (None without an order))."""
     n, c, h, w = _field_frames(frames, side, size)
-    return frames.contiguous(), n, n if hi is None else hi, c, plane_table(side, size, c, h, w), FIELD_ORDERS.index(order)
+    return frames.contiguous(), n, n if hi is None else hi, c, plane_table(side, size, c, h, w), None if order is None else FIELD_ORDERS.index(order)
+
+
+def _entry_call(name: str, frames: torch.Tensor, n: int, tab, p, head: tuple, tail: tuple) -> None:
+    """One call of a matrix entry on the current stream (no sync): (frames, their count and stride, the plane's offset and rows, *head,
+    *tail, the stream), the return code checked under the entry's name."""
+    from . import _lib
+    with torch.cuda.device(frames.device):
+        _lib.check(getattr(_lib.load(), name)(frames.data_ptr(), n, tab.stride, p.offset, p.rows, *head, *tail, torch.cuda.current_stream().cuda_stream), name)
+
+
+def _matrix_call(stem: str, frames: torch.Tensor, n: int, tab, p, side: Side, tail: tuple, step: Optional[int] = None, variant: str = "") -> None:
+    """savsr_video_<stem>_u8<variant> or _u16<variant> on plane p, by the table's sample size.  The head is (row_bytes[, step]) for bytes --
+    the step slot only on the entries that have one -- and (cols, depth) for 16-bit samples; `tail` is what follows it."""
+    if tab.sample == 1:
+        _entry_call(f"savsr_video_{stem}_u8{variant}", frames, n, tab, p, (p.row_bytes,) + (() if step is None else (step,)), tail)
+    else:
+        _entry_call(f"savsr_video_{stem}_u16{variant}", frames, n, tab, p, (p.row_bytes // 2, side.depth), tail)
+
+
+def _check_table(table: torch.Tensor, name: str, count: int, device: torch.device) -> None:
+    """A device table of the masked deinterlacer (flags) or the weave (delta): `count` contiguous int32 on the frames' device."""
+    if table.dtype != torch.int32 or table.device != device or table.numel() != count or not table.is_contiguous():
+        raise ValueError(f"{name} must be {count} contiguous int32 on {device}, got {table.dtype} {tuple(table.shape)} on {table.device}")
 
 
 def _deinterlace_device(frames: torch.Tensor, order: str, side: Side, size: Size, lo: int = 0, hi: Optional[int] = None,
@@ -355,29 +378,12 @@ def _deinterlace_device(frames: torch.Tensor, order: str, side: Side, size: Size
     [lo, hi) (default: all), prev / next taken among the resident frames and clamped there.  One call per plane, on the current stream.
     method "bwdif" or rate "same" (hi - lo frames: the first field in time of every source frame, the others are not computed) go
     through the `_m` entries; the defaults run the entries they ran before."""
-    from . import _lib
     mid, rid = DEINTERLACERS.index(method), FIELD_RATES.index(rate)
     frames, n, hi, c, tab, oid = _field_job(frames, order, side, size, hi)
-    out = frames.new_empty(((1 if rid else 2) * (hi - lo),) + tuple(frames.shape[1:]))
-    if hi <= lo:
-        return out
-    lib = _lib.load()
-    with torch.cuda.device(frames.device):
-        st = torch.cuda.current_stream().cuda_stream
-        for p in tab.planes:          # (the pixel step of packed frames is their channel count: neighbours of a sample are c bytes away)
-            if mid or rid:
-                if tab.sample == 1:
-                    _lib.check(lib.savsr_video_deinterlace_u8_m(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes, max(c, 1), oid, lo, hi,
-                                                                out.data_ptr(), tab.stride, p.offset, mid, rid, st), "savsr_video_deinterlace_u8_m")
-                else:
-                    _lib.check(lib.savsr_video_deinterlace_u16_m(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes // 2, side.depth, oid, lo,
-                                                                 hi, out.data_ptr(), tab.stride, p.offset, mid, rid, st), "savsr_video_deinterlace_u16_m")
-            elif tab.sample == 1:
-                _lib.check(lib.savsr_video_deinterlace_u8(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes, max(c, 1), oid, lo, hi,
-                                                          out.data_ptr(), tab.stride, p.offset, st), "savsr_video_deinterlace_u8")
-            else:
-                _lib.check(lib.savsr_video_deinterlace_u16(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes // 2, side.depth, oid, lo, hi,
-                                                           out.data_ptr(), tab.stride, p.offset, st), "savsr_video_deinterlace_u16")
+    out = frames.new_empty(((1 if rid else 2) * max(hi - lo, 0),) + tuple(frames.shape[1:]))
+    variant, extra = ("_m", (mid, rid)) if mid or rid else ("", ())
+    for p in tab.planes if hi > lo else ():          # (the pixel step of packed frames is their channel count: neighbours of a sample are c bytes away)
+        _matrix_call("deinterlace", frames, n, tab, p, side, (oid, lo, hi, out.data_ptr(), tab.stride, p.offset) + extra, max(c, 1), variant)
     return out
 
 
@@ -398,6 +404,42 @@ def deinterlace(frames: torch.Tensor, order: str, pixel_format: str = "rgb", siz
     return _deinterlace_device(frames, order, side, size, method=method, rate=rate)
 
 
+class _LookAhead:
+    """The window of the streaming stages whose result for a frame needs the frame after it.  take(frames) appends the pushed frames and
+    hands back (buffer, lo, hi): the frames [lo, hi) of `buffer` are final now -- all but the newest one, whose next frame is not known
+    yet; take(None, last=True) hands back everything, the newest frame's next one clamped as at the end of the video, and (None, 0, 0)
+    when nothing is left.  buffer[lo - 1] is the frame before the range where the video has one, buffer[hi] the frame after it where one
+    was pushed.  Afterwards the window keeps that context frame and the frames not done yet, always as copies of its own, so that the
+    chunk they came with is released: at most two frames once a range was handed back."""
+
+    def __init__(self):
+        self.buf: Optional[torch.Tensor] = None          # the context frame (where there is one), then the frames not done yet
+        self.todo = 0                                    # how many of them are not done yet (they are the last ones)
+
+    @property
+    def held(self) -> int:
+        return 0 if self.buf is None else int(self.buf.shape[0])
+
+    def take(self, frames: Optional[torch.Tensor], last: bool = False) -> Tuple[Optional[torch.Tensor], int, int]:
+        k = 0 if frames is None else int(frames.shape[0])
+        if self.buf is None:
+            if frames is None:
+                return None, 0, 0
+            buf = frames.contiguous()
+        else:
+            buf = self.buf if frames is None else torch.cat([self.buf, frames], 0)
+        n = int(buf.shape[0])
+        lo = n - self.todo - k
+        hi = n if last else max(n - 1, lo)
+        if last:
+            self.buf, self.todo = None, 0
+        elif hi > lo:
+            self.buf, self.todo = buf[hi - 1:].clone(), n - hi
+        else:          # (nothing final yet: the pushed frames wait; a first push is the caller's storage and is copied)
+            self.buf, self.todo = buf.clone() if self.buf is None else buf, self.todo + k
+        return buf, lo, hi
+
+
 class FieldSplitter:
     """The streaming deinterlacer behind VideoUpscaler(fields=...): push(source frames on the GPU) returns the progressive frames that are
     final, finish() the last source frame's two.  The second field of the last pushed frame needs the frame after it, so one source frame
@@ -411,32 +453,26 @@ class FieldSplitter:
         check_method(method)
         check_rate(rate)
         self.method, self.rate = method, rate
-        self._src: Optional[torch.Tensor] = None          # source frames [seen - len, seen): the context frame, then the ones not done
-        self._todo = 0                                    # how many of them are not deinterlaced yet (they are the last ones)
+        self._win = _LookAhead()
 
     def push(self, frames: torch.Tensor) -> torch.Tensor:
-        k = int(frames.shape[0])
-        src = frames.contiguous() if self._src is None else torch.cat([self._src, frames], 0)
-        n = int(src.shape[0])
-        lo, hi = n - self._todo - k, n - 1                # all but the last frame, whose next is not known yet
-        res = _deinterlace_device(src, self.order, self.side, self.size, lo, max(hi, lo), self.method, self.rate)
-        if hi > lo:
-            self._src, self._todo = src[max(hi - 1, 0):].clone(), 1          # (a copy of two frames: the chunk's storage is released)
-        else:
-            self._src, self._todo = src, self._todo + k
-        return res
+        src, lo, hi = self._win.take(frames)
+        return _deinterlace_device(src, self.order, self.side, self.size, lo, hi, self.method, self.rate)
+
+    @property
+    def _src(self) -> Optional[torch.Tensor]:
+        return self._win.buf
 
     @property
     def held(self) -> int:
         """Source frames on the device between pushes: at most two."""
-        return 0 if self._src is None else int(self._src.shape[0])
+        return self._win.held
 
     def finish(self) -> Optional[torch.Tensor]:
-        src, self._src = self._src, None
-        if src is None or self._todo == 0:          # nothing was pushed (or finish() ran before)
+        src, lo, hi = self._win.take(None, True)
+        if hi <= lo:          # nothing was pushed (or finish() ran before)
             return None
-        n = int(src.shape[0])
-        return _deinterlace_device(src, self.order, self.side, self.size, n - self._todo, n, self.method, self.rate)
+        return _deinterlace_device(src, self.order, self.side, self.size, lo, hi, self.method, self.rate)
 
 
 # ---- telecined film (savsr_amd/pulldown.py is the specification) -----------------------------------------------------------------------------
@@ -454,44 +490,33 @@ def _check_pulldown(pulldown, cycle, fields) -> Optional[str]:
     return pulldown
 
 
+def _cells(frames: torch.Tensor, lo: int, hi: int, columns: int) -> torch.Tensor:
+    """The output of a reducing entry: int64 [hi - lo, columns] on the frames' device."""
+    return torch.empty(max(hi - lo, 0), columns, dtype=torch.int64, device=frames.device)
+
+
 def _field_scores_device(frames: torch.Tensor, order: str, side: Side, size: Size, lo: int = 0, hi: Optional[int] = None) -> torch.Tensor:
     """savsr_video_field_scores_* on resident frames of the input side on the GPU: int64 [hi - lo, 2] there for source frames [lo, hi)
     (default: all), the previous frame taken among the resident ones and clamped there; enqueued on the current stream (no sync).  Every
     byte of packed frames, the Y plane of planar ones."""
-    from . import _lib
     frames, n, hi, c, tab, oid = _field_job(frames, order, side, size, hi)
-    lib = _lib.load()
-    with torch.cuda.device(frames.device):
-        out = torch.empty(max(hi - lo, 0), 2, dtype=torch.int64, device=frames.device)
-        if hi <= lo:
-            return out
-        st = torch.cuda.current_stream().cuda_stream
-        y = tab.planes[0]
-        if tab.sample == 1:
-            _lib.check(lib.savsr_video_field_scores_u8(frames.data_ptr(), n, tab.stride, y.offset, y.rows, y.row_bytes, oid, lo, hi, out.data_ptr(), st),
-                       "savsr_video_field_scores_u8")
-        else:
-            _lib.check(lib.savsr_video_field_scores_u16(frames.data_ptr(), n, tab.stride, y.offset, y.rows, y.row_bytes // 2, side.depth, oid, lo, hi,
-                                                        out.data_ptr(), st), "savsr_video_field_scores_u16")
+    out = _cells(frames, lo, hi, 2)
+    if hi > lo:
+        _matrix_call("field_scores", frames, n, tab, tab.planes[0], side, (oid, lo, hi, out.data_ptr()))
     return out
 
 
 def _weave_device(frames: torch.Tensor, order: str, delta: torch.Tensor, side: Side, size: Size, lo: int = 0, hi: Optional[int] = None) -> torch.Tensor:
     """savsr_video_weave on resident frames of the input side on the GPU: the hi - lo woven frames of source frames [lo, hi) (default:
-    all) with the device table delta (int32 [hi - lo], -1 | 0).  One call per plane, on the current stream."""
-    from . import _lib
+    all) with the device table delta (int32 [hi - lo], -1 | 0).  One call per plane, on the current stream; a byte copy at every depth,
+    so one entry with the head of a `_u8` one."""
     frames, n, hi, c, tab, oid = _field_job(frames, order, side, size, hi)
     out = frames.new_empty((max(hi - lo, 0),) + tuple(frames.shape[1:]))
     if hi <= lo:
         return out
-    if delta.dtype != torch.int32 or delta.device != frames.device or delta.numel() != hi - lo or not delta.is_contiguous():
-        raise ValueError(f"delta must be {hi - lo} contiguous int32 on {frames.device}, got {delta.dtype} {tuple(delta.shape)} on {delta.device}")
-    lib = _lib.load()
-    with torch.cuda.device(frames.device):
-        st = torch.cuda.current_stream().cuda_stream
-        for p in tab.planes:
-            _lib.check(lib.savsr_video_weave(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes, oid, lo, hi, delta.data_ptr(),
-                                             out.data_ptr(), tab.stride, p.offset, st), "savsr_video_weave")
+    _check_table(delta, "delta", hi - lo, frames.device)
+    for p in tab.planes:
+        _entry_call("savsr_video_weave", frames, n, tab, p, (p.row_bytes,), (oid, lo, hi, delta.data_ptr(), out.data_ptr(), tab.stride, p.offset))
     return out
 
 
@@ -500,21 +525,10 @@ def _comb_windows_device(frames: torch.Tensor, order: str, side: Side, size: Siz
     """savsr_video_comb_windows_* on resident frames of the input side on the GPU: int64 [hi - lo, 2] there for frames [lo, hi) (default:
     all): the largest window count and the total of combed samples; enqueued on the current stream (no sync).  Every byte of packed
     frames with their channel count as the pixel step, the Y plane of planar ones."""
-    from . import _lib
     frames, n, hi, c, tab, oid = _field_job(frames, order, side, size, hi)
-    lib = _lib.load()
-    with torch.cuda.device(frames.device):
-        out = torch.empty(max(hi - lo, 0), 2, dtype=torch.int64, device=frames.device)
-        if hi <= lo:
-            return out
-        st = torch.cuda.current_stream().cuda_stream
-        y = tab.planes[0]
-        if tab.sample == 1:
-            _lib.check(lib.savsr_video_comb_windows_u8(frames.data_ptr(), n, tab.stride, y.offset, y.rows, y.row_bytes, max(c, 1), oid, lo, hi, threshold,
-                                                       out.data_ptr(), st), "savsr_video_comb_windows_u8")
-        else:
-            _lib.check(lib.savsr_video_comb_windows_u16(frames.data_ptr(), n, tab.stride, y.offset, y.rows, y.row_bytes // 2, side.depth, oid, lo, hi,
-                                                        threshold, out.data_ptr(), st), "savsr_video_comb_windows_u16")
+    out = _cells(frames, lo, hi, 2)
+    if hi > lo:
+        _matrix_call("comb_windows", frames, n, tab, tab.planes[0], side, (oid, lo, hi, threshold, out.data_ptr()), max(c, 1))
     return out
 
 
@@ -523,26 +537,14 @@ def _deinterlace_masked_device(frames: torch.Tensor, order: str, flags: torch.Te
     """savsr_video_deinterlace_masked_* on resident frames of the input side on the GPU: hi - lo frames, frame n - lo the same-rate
     deinterlaced frame n where the device table flags (int32 [hi - lo]) is not 0 and a copy of frame n elsewhere; prev / next among the
     resident frames and clamped there.  One call per plane, on the current stream."""
-    from . import _lib
     mid = DEINTERLACERS.index(method)
     frames, n, hi, c, tab, oid = _field_job(frames, order, side, size, hi)
     out = frames.new_empty((max(hi - lo, 0),) + tuple(frames.shape[1:]))
     if hi <= lo:
         return out
-    if flags.dtype != torch.int32 or flags.device != frames.device or flags.numel() != hi - lo or not flags.is_contiguous():
-        raise ValueError(f"flags must be {hi - lo} contiguous int32 on {frames.device}, got {flags.dtype} {tuple(flags.shape)} on {flags.device}")
-    lib = _lib.load()
-    with torch.cuda.device(frames.device):
-        st = torch.cuda.current_stream().cuda_stream
-        for p in tab.planes:
-            if tab.sample == 1:
-                _lib.check(lib.savsr_video_deinterlace_masked_u8(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes, max(c, 1), oid, lo, hi,
-                                                                 out.data_ptr(), tab.stride, p.offset, mid, flags.data_ptr(), st),
-                           "savsr_video_deinterlace_masked_u8")
-            else:
-                _lib.check(lib.savsr_video_deinterlace_masked_u16(frames.data_ptr(), n, tab.stride, p.offset, p.rows, p.row_bytes // 2, side.depth, oid, lo,
-                                                                  hi, out.data_ptr(), tab.stride, p.offset, mid, flags.data_ptr(), st),
-                           "savsr_video_deinterlace_masked_u16")
+    _check_table(flags, "flags", hi - lo, frames.device)
+    for p in tab.planes:
+        _matrix_call("deinterlace_masked", frames, n, tab, p, side, (oid, lo, hi, out.data_ptr(), tab.stride, p.offset, mid, flags.data_ptr()), max(c, 1))
     return out
 
 
@@ -657,8 +659,7 @@ class PulldownRemover:
         self._last: Optional[torch.Tensor] = None          # the last woven (combed=: cleaned) frame
         self._pend: Optional[torch.Tensor] = None          # the woven (cleaned) frames of the incomplete cycle, frames [_base, _base + len)
         self._pend_sad: List[int] = []                     # their pair SADs with their predecessors
-        self._wov: Optional[torch.Tensor] = None           # combed=: the woven context frame, then the woven frames not cleaned yet
-        self._todo = 0                                     # how many of them are not cleaned yet (they are the last ones)
+        self._win = _LookAhead()                           # combed=: the woven context frame, then the woven frames not cleaned yet
         self._cleaned = 0                                  # woven frames that went through the cleaning
         self._base = 0
         self.seen = 0
@@ -670,6 +671,10 @@ class PulldownRemover:
     def held(self) -> int:
         """Frames on the device between pushes: at most cycle + 1, cycle + 3 with combed=."""
         return sum(0 if t is None else int(t.shape[0]) for t in (self._ctx, self._last, self._pend, self._wov))
+
+    @property
+    def _wov(self) -> Optional[torch.Tensor]:
+        return self._win.buf
 
     @property
     def info(self) -> dict:
@@ -696,17 +701,8 @@ class PulldownRemover:
     def _clean(self, woven: Optional[torch.Tensor], last: bool) -> Tuple[torch.Tensor, torch.Tensor]:
         """The woven frames that are final now, cleaned, and their comb table on the device: all but the newest one, whose next frame is
         not known yet (last: all, the newest one's next frame clamped, as at the end of the video)."""
-        k = 0 if woven is None else int(woven.shape[0])
-        buf = woven if self._wov is None else (self._wov if woven is None else torch.cat([self._wov, woven], 0))
-        n = int(buf.shape[0])
-        lo = n - self._todo - k
-        hi = n if last else max(n - 1, lo)
-        out = _clean_combed_device(buf, self.order, self.combed, self.comb_threshold, self.comb_pixels, self.side, self.size, lo, hi)
-        if hi > lo:
-            self._wov, self._todo = buf[max(hi - 1, 0):].clone(), n - hi          # (a copy of two frames: the chunk's storage is released)
-        else:
-            self._wov, self._todo = buf, self._todo + k
-        return out
+        buf, lo, hi = self._win.take(woven, last)
+        return _clean_combed_device(buf, self.order, self.combed, self.comb_threshold, self.comb_pixels, self.side, self.size, lo, hi)
 
     def _decimate(self, woven: torch.Tensor, win: Optional[torch.Tensor]) -> torch.Tensor:
         """The next woven (cleaned) frames -> the kept ones of the cycles they complete; the others wait."""
@@ -738,9 +734,9 @@ class PulldownRemover:
 
     def finish(self) -> Optional[torch.Tensor]:
         head = None
-        if self.combed is not None and self._wov is not None and self._todo:          # the held woven frame, then the end as ever
+        if self.combed is not None and self._win.todo:          # the held woven frame, then the end as ever
             head = self._decimate(*self._clean(None, True))
-        pend, self._pend, self._ctx, self._last, self._wov, self._todo = self._pend, None, None, None, None, 0
+        pend, self._pend, self._ctx, self._last, self._win = self._pend, None, None, None, _LookAhead()
         if pend is None:
             return head if head is not None and int(head.shape[0]) else None
         self.kept += list(range(self._base, self._base + int(pend.shape[0])))
@@ -754,22 +750,10 @@ def _field_stats_device(frames: torch.Tensor, side: Side, size: Size, lo: int = 
     """savsr_video_field_stats_* on resident frames of the input side on the GPU: int64 [hi - lo, 8] there for source frames [lo, hi)
     (default: all), the previous and the next frame taken among the resident ones and clamped there; one memset and one launch on the
     current stream (no sync).  Every byte of packed frames, the Y plane of planar ones."""
-    from . import _lib
-    n, c, h, w = _field_frames(frames, side, size)
-    frames, hi, tab = frames.contiguous(), n if hi is None else hi, plane_table(side, size, c, h, w)
-    lib = _lib.load()
-    with torch.cuda.device(frames.device):
-        out = torch.empty(max(hi - lo, 0), sc.STAT_COLUMNS, dtype=torch.int64, device=frames.device)
-        if hi <= lo:
-            return out
-        st = torch.cuda.current_stream().cuda_stream
-        y = tab.planes[0]
-        if tab.sample == 1:
-            _lib.check(lib.savsr_video_field_stats_u8(frames.data_ptr(), n, tab.stride, y.offset, y.rows, y.row_bytes, lo, hi, out.data_ptr(), st),
-                       "savsr_video_field_stats_u8")
-        else:
-            _lib.check(lib.savsr_video_field_stats_u16(frames.data_ptr(), n, tab.stride, y.offset, y.rows, y.row_bytes // 2, side.depth, lo, hi,
-                                                       out.data_ptr(), st), "savsr_video_field_stats_u16")
+    frames, n, hi, c, tab, _ = _field_job(frames, None, side, size, hi)
+    out = _cells(frames, lo, hi, sc.STAT_COLUMNS)
+    if hi > lo:
+        _matrix_call("field_stats", frames, n, tab, tab.planes[0], side, (lo, hi, out.data_ptr()))
     return out
 
 
@@ -817,35 +801,28 @@ class ScanStats:
     def __init__(self, side: Side, size: Size, stats=None):
         self.side, self.size = side, size
         self._stats = _field_stats_device if stats is None else stats
-        self._src: Optional[torch.Tensor] = None          # source frames [seen - len, seen): the context frame, then the ones without a row
-        self._todo = 0                                    # how many of them have no row yet (they are the last ones)
+        self._win = _LookAhead()                          # source frames [seen - held, seen)
         self.seen = 0
+
+    @property
+    def _src(self) -> Optional[torch.Tensor]:
+        return self._win.buf
 
     @property
     def held(self) -> int:
         """Source frames on the device between pushes: at most two."""
-        return 0 if self._src is None else int(self._src.shape[0])
+        return self._win.held
 
     def push(self, frames: torch.Tensor) -> torch.Tensor:
-        k = int(frames.shape[0])
-        src = frames.contiguous() if self._src is None else torch.cat([self._src, frames], 0)
-        n = int(src.shape[0])
-        self.seen += k
-        lo, hi = n - self._todo - k, n - 1                # all but the last frame, whose next is not known yet
-        res = self._stats(src, self.side, self.size, lo, max(hi, lo))
-        if hi > lo:
-            self._src, self._todo = src[max(hi - 1, 0):].clone(), 1          # (a copy of two frames: the chunk's storage is released)
-        else:
-            self._src, self._todo = src.clone(), self._todo + k
-        return res
+        self.seen += int(frames.shape[0])
+        src, lo, hi = self._win.take(frames)
+        return self._stats(src, self.side, self.size, lo, hi)
 
     def finish(self) -> Optional[torch.Tensor]:
-        src, self._src = self._src, None
-        if src is None or self._todo == 0:          # nothing was pushed (or finish() ran before)
+        src, lo, hi = self._win.take(None, True)
+        if hi <= lo:          # nothing was pushed (or finish() ran before)
             return None
-        n = int(src.shape[0])
-        todo, self._todo = self._todo, 0
-        return self._stats(src, self.side, self.size, n - todo, n)
+        return self._stats(src, self.side, self.size, lo, hi)
 
 
 def _check_scan(scan, fields, pulldown, pulldown_cycle, auto_ok: bool = True) -> Optional[str]:

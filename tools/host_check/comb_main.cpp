@@ -8,42 +8,9 @@
 // lie in one of exactly its size, so an access outside any of them is a sanitizer report.  SAVSR_HOST_CHECK: a launch runs one thread at
 // a time, so the comb kernel's LDS cells are a static array that the workgroup's first thread clears and whose windows its last thread
 // sums; everything else is the code the GPU runs.
-#define SAVSR_HOST_CHECK 1
-#include <cstdarg>
-
 #include "hip_stub.h"
 
 #if COMB_PART == 1
-typedef int hipError_t;
-constexpr hipError_t hipSuccess = 0;
-inline hipError_t hipMemsetAsync(void* p, int v, size_t bytes, hipStream_t) {
-    memset(p, v, bytes);
-    return hipSuccess;
-}
-inline const char* hipGetErrorString(hipError_t) { return "host"; }
-inline unsigned long long atomicAdd(unsigned long long* cell, unsigned long long v) {
-    const unsigned long long old = *cell;
-    *cell = old + v;
-    return old;
-}
-inline unsigned long long atomicMax(unsigned long long* cell, unsigned long long v) {
-    const unsigned long long old = *cell;
-    *cell = old > v ? old : v;
-    return old;
-}
-inline uint32_t atomicAdd(uint32_t* cell, uint32_t v) {
-    const uint32_t old = *cell;
-    *cell = old + v;
-    return old;
-}
-namespace savsr {
-inline void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_last_error, sizeof g_last_error, fmt, ap);
-    va_end(ap);
-}
-}  // namespace savsr
 #include "pulldown_device.inc"          // csrc/pulldown.hip with its include of common.hpp replaced by hip_stub.h
 #else
 #include "deinterlace_device.inc"       // csrc/deinterlace.hip, likewise

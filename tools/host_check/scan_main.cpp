@@ -4,31 +4,7 @@
 // boundary; the sums go to a block of exactly their size, so an access outside either of them is a sanitizer report.
 // SAVSR_HOST_CHECK: a launch runs one thread at a time, so scan.hip's workgroup reduction is replaced by its per-thread branch;
 // everything else is the code the GPU runs.
-#define SAVSR_HOST_CHECK 1
-#include <cstdarg>
-
 #include "hip_stub.h"
-
-typedef int hipError_t;
-constexpr hipError_t hipSuccess = 0;
-inline hipError_t hipMemsetAsync(void* p, int v, size_t bytes, hipStream_t) {
-    memset(p, v, bytes);
-    return hipSuccess;
-}
-inline const char* hipGetErrorString(hipError_t) { return "host"; }
-inline unsigned long long atomicAdd(unsigned long long* cell, unsigned long long v) {
-    const unsigned long long old = *cell;
-    *cell = old + v;
-    return old;
-}
-namespace savsr {
-inline void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_last_error, sizeof g_last_error, fmt, ap);
-    va_end(ap);
-}
-}  // namespace savsr
 
 #include "scan_device.inc"          // csrc/scan.hip with its include of common.hpp replaced by hip_stub.h
 

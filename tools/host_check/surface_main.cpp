@@ -4,25 +4,7 @@
 // last byte that holds a sample (`span` bytes into it) and starts `misalign` bytes past a 16-byte boundary; the planar frames go to a
 // block of exactly their size.  Pack: the planar frames lie in a block of exactly their size, the surface frames go to a block that ends
 // with the last frame's resolved bytes (surface_bytes), prefilled with 0xA5.  An access outside any block is a sanitizer report.
-#include <cstdarg>
-
 #include "hip_stub.h"
-
-typedef int hipError_t;
-constexpr hipError_t hipSuccess = 0;
-inline hipError_t hipMemset2DAsync(void* p, size_t pitch, int v, size_t width, size_t height, hipStream_t) {
-    for (size_t r = 0; r < height; ++r) memset((uint8_t*)p + r * pitch, v, width);
-    return hipSuccess;
-}
-inline const char* hipGetErrorString(hipError_t) { return "host"; }
-namespace savsr {
-inline void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_last_error, sizeof g_last_error, fmt, ap);
-    va_end(ap);
-}
-}  // namespace savsr
 
 #include "surface_device.inc"          // csrc/surface.hip with its include of common.hpp removed
 
