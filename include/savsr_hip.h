@@ -160,7 +160,13 @@ int savsr_conv2d_batch(const savsr_conv_desc* descs, int n, void* stream);
  * fp16 operands -- the activations rounded to fp16 (RNE) in the staging (after the Winograd-y input transform, in fp32), `wpacked` an fp16
  * image: ONE part of savsr_conv_packed_elems / savsr_conv_wy_packed_elems elements holding fp16(W) (fp16(U)) at position p of
  * savsr_conv_pack_index / savsr_conv_wy_pack_index, no hi/lo interleave; unaddressed entries zero.  One v_mfma_f32_32x32x16_f16 per
- * product, fp32 accumulation, the same fp32 epilogue.  Operands beyond +-65504 become infinities: the caller checks its weights. */
+ * product, fp32 accumulation, the same fp32 epilogue.  The operand range: a magnitude from 65520 on becomes an infinity (65504 .. 65520
+ * rounds to 65504) -- the caller checks its weights (and U); the activations are NOT checked, and the two forms differ: the direct form
+ * needs |x| < 65520, the Winograd-y form the same of V = x_a + x_b and x_a - x_b for rows one and two apart, so |x| <= 32752 is safe in
+ * both.  An infinity reaches exactly the outputs whose receptive field holds it (Winograd-y: the row pair's four input rows x 3 columns)
+ * with IEEE classes (+inf, -inf, NaN); every other output, and every other conv of the launch, is unaffected.  No lower limit: operands
+ * below 2^-14 are kept as fp16 subnormals (steps of 2^-24, zero below 2^-25) by the staging's conversion and multiplied as such by the
+ * matrix cores (tests/test_gpu_conv_range_f16.py, regimes `w_sub` / `x_sub` / `edge`). */
 int savsr_conv2d_batch_f16(const savsr_conv_desc* descs, int n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -209,8 +215,9 @@ int savsr_osconv_weights(const savsr_osconv_attn_desc* d, void* stream);
  * launches (the two propagation directions of a ResidualBlock pair, savsr_arch.py:399-415, x up to four clips of a batched launch sequence). */
 int savsr_osconv_weights_max_batch(void);     /* 8 */
 int savsr_osconv_weights_batch(const savsr_osconv_attn_desc* descs, int n, void* stream);
-/* (ABI 32) The same, with wimg_out receiving the fp16 image savsr_conv2d_batch_f16 consumes: W'' computed in fp32 exactly as above and
- * rounded once to fp16 (RNE), one part (half the bytes of the split image; the same buffer may serve both). */
+/* (ABI 32) The same, with wimg_out receiving the fp16 image savsr_conv2d_batch_f16 consumes: W'' (U) of the same fp32 gates computed in float64,
+ * rounded to fp32 and then to fp16 (RNE; within one fp16 step of the exact value at any bank scale, subnormals kept), one part (half
+ * the bytes of the split image; the same buffer may serve both). */
 int savsr_osconv_weights_batch_f16(const savsr_osconv_attn_desc* descs, int n, void* stream);
 
 /* RCAN ChannelAttention gate (savsr_arch.py:514-520): gate = sigmoid(W2 ReLU(W1 mean + b1) + b2) */

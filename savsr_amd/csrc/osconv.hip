@@ -237,7 +237,8 @@ __device__ __forceinline__ void osconv_route_in_workgroup(const savsr_osconv_att
 // then  W''[co][ci][tap] = fa[co] ca[ci] sa[tap] sum_k ka[k] W[k][co][ci][tap]  (:156-163,171
 // folded, :148-149) for this workgroup's slice, split to (hi, lo) bf16 and written in the conv
 // weight-image order.
-// F16 (the precision mode "fp16", savsr_osconv_weights_batch_f16): the same fp32 W'' rounded ONCE to fp16 (RNE), one part at the pack index.
+// F16 (the precision mode "fp16", savsr_osconv_weights_batch_f16): W'' of the same fp32 gates in float64, rounded to fp32 and then to fp16 (RNE
+// both: within one fp16 step of the exact value, subnormals kept), one part at the pack index.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 template <bool F16>
@@ -353,6 +354,32 @@ __global__ __launch_bounds__(512) void osconv_aggregate_kernel(const OscBatch bt
     const int cob = (int)(g2 / nchunk);
     const int co = cob * cot + 32 * t + row;
     const int ci0 = chunk * 16 + kh * 8;
+    if constexpr (F16) {
+        // float64 from the fp32 gates and banks to the entry: where sum_k ka W cancels, an fp32 sum is off by 2^-24 of sum |ka W| -- tens of
+        // fp16 steps of an entry that small once the bank is large enough for the entry to be fp16-normal (at unit scale fp16's subnormal
+        // step hides it).  The entry is fp16(fp32(W'')), within one fp16 step of the exact W'' of these gates at any bank scale.
+        double sd[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
+#pragma unroll
+        for (int k = 0; k < OSC_MAX_KNUM; ++k)
+            if (k < d.knum) {
+                const double kk = (double)ka[k];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) sd[j] += kk * (double)bw[k][j >> 2][j & 3];
+            }
+        for (int k = OSC_MAX_KNUM; k < d.knum; ++k) {
+            const f32x4* b = reinterpret_cast<const f32x4*>(d.bank + ((long long)k * d.nunits + unit) * 8);
+            const f32x4 w0 = b[0], w1 = b[1];
+            const double kk = (double)ka[k];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { sd[j] += kk * (double)w0[j]; sd[4 + j] += kk * (double)w1[j]; }
+        }
+        const double gco = (co < d.cout) ? (double)gates[d.cin + co] * (double)gates[d.cin + d.cout + tap] : 0.;
+        f16x8 h;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) h[j] = (_Float16)(float)(sd[j] * (gco * (double)gates[ci0 + j]));
+        reinterpret_cast<f16x8*>(d.wimg_out)[group * 64 + ln] = h;
+        return;
+    }
     f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
 #pragma unroll
     for (int k = 0; k < OSC_MAX_KNUM; ++k)
@@ -374,13 +401,6 @@ __global__ __launch_bounds__(512) void osconv_aggregate_kernel(const OscBatch bt
     s0[0] *= gco * ca[0]; s0[1] *= gco * ca[1]; s0[2] *= gco * ca[2]; s0[3] *= gco * ca[3];
     s1[0] *= gco * ca[4]; s1[1] *= gco * ca[5]; s1[2] *= gco * ca[6]; s1[3] *= gco * ca[7];
     const float x[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
-    if constexpr (F16) {
-        f16x8 h;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) h[j] = (_Float16)x[j];
-        reinterpret_cast<f16x8*>(d.wimg_out)[group * 64 + ln] = h;
-        return;
-    }
     bf16x8 hi, lo;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -512,6 +532,45 @@ __global__ __launch_bounds__(512) void osconv_aggregate_wy_kernel(const OscBatch
     const int ci0 = chunk * 16 + kh * 8 + 4 * h4;
     const float* ka_ = gates + d.cin + d.cout + 9;
     const float* ca = gates + ci0;
+    if constexpr (F16) {
+        // float64 from the fp32 gates and banks to U (see osconv_aggregate_kernel): both sum_k ka W and g0 +- g1 + g2 cancel
+        double gd[3][4];
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+            double sd[4] = {0., 0., 0., 0.};
+#pragma unroll
+            for (int k = 0; k < OSC_MAX_KNUM; ++k)
+                if (k < d.knum) {
+                    const double kk = (double)ka_[k];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) sd[j] += kk * (double)bw[ky][k][j];
+                }
+            for (int k = OSC_MAX_KNUM; k < d.knum; ++k) {
+                const long long unit = ((((long long)(cob * nchunk + chunk) * 9 + (ky * 3 + kx)) * nt + t) << 6) + ln;
+                const f32x4 w0 = reinterpret_cast<const f32x4*>(d.bank + ((long long)k * d.nunits + unit) * 8)[h4];
+                const double kk = (double)ka_[k];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) sd[j] += kk * (double)w0[j];
+            }
+            const double gco = (double)gates[d.cin + co] * (double)gates[d.cin + d.cout + ky * 3 + kx];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) gd[ky][j] = sd[j] * (gco * (double)ca[j]);
+        }
+#pragma unroll
+        for (int pos = 0; pos < 4; ++pos) {
+            const int hf = pos >> 1, vr = pos & 1;
+            const long long group = ((((long long)(cob * nchunk + chunk) * 2 + hf) * 6 + (vr * 3 + kx)) * nt + t);
+            f16x4 h;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double sgl = gd[0][j] + gd[2][j];
+                const double u = pos == 0 ? gd[0][j] : pos == 3 ? gd[2][j] : 0.5 * (pos == 1 ? sgl + gd[1][j] : sgl - gd[1][j]);
+                h[j] = (_Float16)(float)u;
+            }
+            reinterpret_cast<f16x4*>(d.wimg_out)[(group * 64 + ln) * 2 + h4] = h;      // units of 8 B
+        }
+        return;
+    }
     f32x4 g[3];
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky) {
@@ -546,13 +605,6 @@ __global__ __launch_bounds__(512) void osconv_aggregate_wy_kernel(const OscBatch
     for (int pos = 0; pos < 4; ++pos) {
         const int hf = pos >> 1, vr = pos & 1;
         const long long group = ((((long long)(cob * nchunk + chunk) * 2 + hf) * 6 + (vr * 3 + kx)) * nt + t);
-        if constexpr (F16) {
-            f16x4 h;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) h[j] = (_Float16)uu[pos][j];
-            reinterpret_cast<f16x4*>(d.wimg_out)[(group * 64 + ln) * 2 + h4] = h;      // units of 8 B
-            continue;
-        }
         bf16x4 hi, lo;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {

@@ -242,7 +242,8 @@ def pack_conv_weight_wy_f16(w: torch.Tensor) -> torch.Tensor:
 
 
 def check_f16_range(name: str, a: np.ndarray) -> None:
-    """Refuse an operand outside the fp16 range (it would become an infinity in the precision mode "fp16"), naming it."""
+    """Refuse an operand outside the fp16 range (it would become an infinity in the precision mode "fp16"), naming it.  Nothing is refused
+    at the low side: below 2^-14 a weight is an fp16 subnormal, which the kernels keep and multiply as such."""
     m = float(np.abs(a).max()) if a.size else 0.0
     if not m <= FP16_MAX:
         raise ValueError(f"precision 'fp16': {name} has a weight of magnitude {m:.6g}, beyond the fp16 range (+-{FP16_MAX:g}); "

@@ -165,3 +165,161 @@ def ratio(err: torch.Tensor, s: torch.Tensor) -> float:
     """max over the outputs with s > 0 of err / s (0 if there are none)."""
     m = s > 0
     return float((err[m] / s[m]).max()) if bool(m.any()) else 0.0
+
+
+# ----------------------------------------------------------------------------- the precision mode "fp16": regimes and emulations
+# The fp16 forms of the same kernels (savsr_conv2d_batch_f16) round every operand ONCE to fp16 (RNE, subnormals kept, +-inf from 65520) and
+# multiply exactly on the fp16 matrix cores; tests/test_range_cases_f16.py and tests/test_gpu_conv_range_f16.py hold them to per-output bounds
+# as above.  fp16 has 5 exponent bits: the +-3 decades of `decades` leave its range, so F16_REGIMES carries `decades16` in its place, and three
+# regimes at the range's ends -- `w_sub` / `x_sub` (every weight / activation fp16-subnormal, outputs of magnitude ~1) and `edge` (values at and
+# beyond 65504 planted in Gaussian data: the only regime with non-finite outputs).
+F16_NEW = ("decades16", "w_sub", "x_sub", "edge")
+F16_REGIMES = tuple("decades16" if r == "decades" else r for r in REGIMES) + F16_NEW[1:]
+F16_FINITE = F16_REGIMES[:-1]
+F16_MIN_NORMAL = 2.0 ** -14
+F16_INF_FROM = 65520.0           # the smallest magnitude RNE takes to infinity (65504 + half an ulp of 32)
+
+# `edge`: (what, input channel, ((row, column, value), ...)); rows 4 / 5 are the two output rows of one Winograd row pair, 2 / 3 of another,
+# 1 / 3 are d0 and d2 of the pair at 2, 7 / 8 lie in different pairs.  A plant is made where all its rows and its column are interior.
+EDGE_PLANTS = (("65504", 0, ((2, 3, 65504.0),)), ("65519", 1, ((2, 7, 65519.0),)), ("65520", 2, ((2, 11, 65520.0),)),
+               ("-70000", 3, ((2, 15, -70000.0),)), ("pair ++", 4, ((4, 19, 40000.0), (5, 19, 40000.0))),
+               ("pair +-", 5, ((2, 23, 40000.0), (3, 23, -40000.0))), ("d0 - d2", 6, ((1, 27, 40000.0), (3, 27, -40000.0))),
+               ("across pairs", 7, ((7, 31, 40000.0), (8, 31, 40000.0))))
+
+
+def edge_plants(h: int, w: int, skip=()):
+    """The plants of EDGE_PLANTS that fit a h x w image (every row <= h - 2, column <= w - 2), less those named in `skip`."""
+    return [p for p in EDGE_PLANTS if p[0] not in skip and all(r <= h - 2 and c <= w - 2 for r, c, _ in p[2])]
+
+
+def regimes_f16(cin: int, cout: int, ks: int, h: int, w: int, seed: int, only=None, skip_plants=()):
+    """`regimes` for F16_REGIMES: the eight shared regimes are the SAME draws; a new regime's draw depends on (seed, its name) only."""
+    fan = cin * ks * ks
+    for name in F16_REGIMES:
+        if only is not None and name not in only:
+            continue
+        if name in REGIMES:
+            yield from regimes(cin, cout, ks, h, w, seed, only=(name,))
+            continue
+        g = np.random.RandomState([seed, len(REGIMES) + F16_NEW.index(name)])
+        x = g.standard_normal((cin, h, w))
+        wt = g.standard_normal((cout, cin, ks, ks))
+        if name == "decades16":
+            x = x * (10.0 ** g.uniform(-2, 2, cin))[:, None, None]
+            wt = wt / np.sqrt(fan) * (10.0 ** g.uniform(-1.5, 1.5, cout))[:, None, None, None] * (10.0 ** g.uniform(-1.5, 1.5, cin))[None, :, None, None]
+        elif name == "w_sub":
+            x, wt = x * 2.0 ** 10, wt * 2.0 ** -17
+        elif name == "x_sub":
+            x, wt = x * 2.0 ** -17, wt * 2.0 ** 10
+        else:
+            wt = wt / np.sqrt(fan)
+            for _, ch, pts in edge_plants(h, w, skip_plants):
+                for r, c, v in pts:
+                    x[ch, r, c] = v
+        yield name, _f32(x), _f32(wt)
+
+
+def f16_round(v, flush: bool = False) -> np.ndarray:
+    """float64 array of fp16(v): numpy's RNE straight from float64 (packing._f16_image), subnormals kept, +-inf from 65520.  flush: results below
+    2^-14 become zero instead (what a matrix core that does not take subnormal operands would compute with)."""
+    with np.errstate(over="ignore"):
+        r = np.asarray(v, dtype=np.float64).astype(np.float16).astype(np.float64)
+    return np.where(np.abs(r) < F16_MIN_NORMAL, 0.0, r) if flush else r
+
+
+def f16_toward_zero(v) -> np.ndarray:
+    """fp16 array of v rounded TOWARD ZERO (the sharpness tests' defect): where RNE rounded away from zero, one fp16 step back."""
+    v = np.asarray(v, dtype=np.float64)
+    r = v.astype(np.float16)
+    return np.where(np.abs(r.astype(np.float64)) > np.abs(v), np.nextafter(r, np.float16(0)), r)
+
+
+def _r16(t: torch.Tensor, flush: bool = False) -> torch.Tensor:
+    return torch.from_numpy(f16_round(t.double().numpy(), flush))
+
+
+def f16_err(v: torch.Tensor) -> torch.Tensor:
+    """e(v) >= |fp16(v) - v|: 2^-11 |v| in the normal range, 2^-25 (half a subnormal step) below 2^-14; 0 from 65520 on, where fp16(v) is
+    an infinity and no bound is claimed."""
+    a = v.double().abs()
+    return torch.where(a < F16_MIN_NORMAL, torch.full_like(a, 2.0 ** -25), torch.where(a < F16_INF_FROM, 2.0 ** -11 * a, torch.zeros_like(a)))
+
+
+def _bound16(x, ex, wt, ew, pad):
+    """conv(e(x), |w|) + conv(|x|, e(w)) + conv(e(x), e(w)) as one convolution."""
+    return _conv(torch.cat([ex, x.double().abs(), ex], 0), torch.cat([wt.double().abs(), ew, ew], 1), pad)
+
+
+def nonfinite_class(t: torch.Tensor) -> torch.Tensor:
+    """0 finite, 1 +inf, 2 -inf, 3 NaN."""
+    return torch.isposinf(t).to(torch.int8) + 2 * torch.isneginf(t).to(torch.int8) + 3 * torch.isnan(t).to(torch.int8)
+
+
+def f16_direct_emulation(x, wt, ks: int, acc32: bool = False, drop=None, flush: bool = False):
+    """The direct form in the precision mode "fp16".  Returns [cout, h, w] float64 tensors: `exact` (float64 conv of the fp32 operands), `emul`
+    (float64 conv of fp16(x), fp16(w)), `S` = conv(|x|, |w|), `S16` = conv(|fp16 x|, |fp16 w|), `B` (the derived bound on |emul - exact|, see
+    f16_err) and with acc32 `acc32` (the same products accumulated in fp32 by ATen).
+    drop = (chunk, tap): the simulated defect, fp16(w) rounded toward zero for the 16 input channels of `chunk` at `tap`.
+    flush: subnormal fp16 operands taken as zero."""
+    pad = ks // 2
+    xh, wh = _r16(x, flush), _r16(wt, flush)
+    if drop is not None:
+        chunk, tap = drop
+        sl = (slice(None), slice(16 * chunk, 16 * chunk + 16), tap // ks, tap % ks)
+        wh[sl] = torch.from_numpy(f16_toward_zero(wt[sl].double().numpy()).astype(np.float64))
+    out = dict(exact=_conv(x, wt, pad), emul=_conv(xh, wh, pad), S=_conv(x.abs(), wt.abs(), pad), S16=_conv(xh.abs(), wh.abs(), pad),
+               B=_bound16(x, f16_err(x), wt, f16_err(wt), pad))
+    if acc32:
+        out["acc32"] = F.conv2d(xh.float()[None], wh.float(), None, padding=pad)[0].double()
+    return out
+
+
+def f16_wy_emulation(x, wt, acc32: bool = False, drop=None, flush: bool = False):
+    """The Winograd F(2,3)-along-y form in the precision mode "fp16", structured as wy_emulation: V formed in fp32, then rounded to fp16;
+    U = packing.wy_transform_f64(wt) rounded once to fp16; exact products, float64 sums, the output transform in float64.  Returns `emul`,
+    `S_wy` (|A^T| applied to the per-position conv(|V|, |U|)), `S16_wy` (the same of the rounded operands), `B_wy` (|A^T| applied to the
+    per-position bound of f16_direct_emulation on (V, U), plus 2^-23 S_wy for the fp32 rounding of V itself), `V_bad` ([4 pos, npair, w] bool:
+    some channel's V of that position is not finite in fp16) and with acc32 `acc32` (fp32 accumulation and fp32 output transform).
+    drop = (chunk, pos, kx): fp16(U) rounded toward zero for the 16 input channels of `chunk` at (pos, kx)."""
+    from savsr_amd.packing import wy_transform_f64
+    cin, h, w = x.shape
+    cout = wt.shape[0]
+    npair = (h + 1) // 2
+    xp = torch.zeros(cin, 2 * npair + 2, w)
+    xp[:, 1:h + 1] = x
+    d = [xp[:, i:i + 2 * npair:2] for i in range(4)]                   # rows Y-1 .. Y+2 of every pair: [cin, npair, w] each, fp32
+    v = [d[0] - d[2], d[1] + d[2], d[2] - d[1], d[1] - d[3]]           # fp32 arithmetic, as the staging
+    u = torch.from_numpy(wy_transform_f64(wt))                         # [4 pos][cout][cin][3 kx], float64
+    m, a, a16, b, m32 = [], [], [], [], []
+    for i in range(4):
+        ui = u[i].unsqueeze(2)                                         # [cout][cin][1][3]
+        vh, uh = _r16(v[i], flush), _r16(ui, flush)
+        if drop is not None and drop[1] == i:
+            sl = (slice(None), slice(16 * drop[0], 16 * drop[0] + 16), 0, drop[2])
+            uh[sl] = torch.from_numpy(f16_toward_zero(ui[sl].numpy()).astype(np.float64))
+        m.append(_conv(vh, uh, (0, 1)))
+        a.append(_conv(v[i].abs(), ui.abs(), (0, 1)))
+        a16.append(_conv(vh.abs(), uh.abs(), (0, 1)))
+        b.append(_bound16(v[i], f16_err(v[i]), ui, f16_err(ui), (0, 1)))
+        if acc32:
+            m32.append(F.conv2d(vh.float()[None], uh.float(), None, padding=(0, 1))[0])
+    rows = lambda r0, r1: torch.stack([r0, r1], 2).reshape(cout, 2 * npair, w)[:, :h]      # noqa: E731
+    s_wy = rows(a[0] + a[1] + a[2], a[1] + a[2] + a[3])
+    out = dict(emul=rows(m[0] + m[1] + m[2], m[1] - m[2] - m[3]), S_wy=s_wy, S16_wy=rows(a16[0] + a16[1] + a16[2], a16[1] + a16[2] + a16[3]),
+               B_wy=rows(b[0] + b[1] + b[2], b[1] + b[2] + b[3]) + 2.0 ** -23 * s_wy,
+               V_bad=torch.stack([(vi.abs() >= F16_INF_FROM).any(0) for vi in v]))
+    if acc32:
+        out["acc32"] = rows(m32[0] + m32[1] + m32[2], m32[1] - m32[2] - m32[3]).double()
+    return out
+
+
+@lru_cache(maxsize=None)
+def case16(cin: int, cout: int, ks: int, h: int, w: int, regime: str, wy: bool = False):
+    """`case` for the precision mode "fp16" (the same seeds): x, wt and the keys of f16_direct_emulation; with wy also emul_wy, S_wy, S16_wy,
+    B_wy and V_bad.  Shared: callers must not modify it."""
+    (_, x, wt), = regimes_f16(cin, cout, ks, h, w, seed=cin * 7 + cout + h, only=(regime,))
+    c = dict(x=x, wt=wt, **f16_direct_emulation(x, wt, ks))
+    if wy:
+        e = f16_wy_emulation(x, wt)
+        c.update(emul_wy=e["emul"], S_wy=e["S_wy"], S16_wy=e["S16_wy"], B_wy=e["B_wy"], V_bad=e["V_bad"])
+    return c

@@ -120,3 +120,17 @@ def test_golden_manifest_and_drift():
         mx, mean = g[f"{name}/drift"]
         assert 0 < mean < mx < 2e-3
     assert abs(float(g["gt/psnr_fp16emu"]) - float(g["gt/psnr_fp32"])) < 0.01
+
+
+def test_golden_clips_manifest_and_drift():
+    """precision_clips.npz (tools/gen_golden_precision.py --clips): made on the shipped constructor's manifest; one fp32 output and one
+    non-negative (max-abs, mean-abs) drift per clip that is not noise."""
+    from savsr_amd.archs.savsr_arch import SAVSR
+    g = np.load(os.path.join(ROOT, "tests", "golden", "precision_clips.npz"))
+    assert str(g["manifest"]) == manifest_hash(synth.manifest_of(SAVSR().state_dict()))
+    for clip in ("lowpass", "const", "zero"):
+        assert g[f"{clip}/fp32"].shape == (3, round(13 * 2.5), round(18 * 3.5)) and g[f"{clip}/fp32"].dtype == np.float32
+        assert bool(np.isfinite(g[f"{clip}/fp32"]).all())
+        mx, mean = g[f"{clip}/drift"]
+        assert 0 <= mean <= mx < 2e-3
+    assert sorted(g.files) == sorted(["manifest"] + [f"{c}/{k}" for c in ("lowpass", "const", "zero") for k in ("fp32", "drift")])

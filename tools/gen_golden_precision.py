@@ -4,7 +4,7 @@ against the fp32 outputs, case table in tests/precision_cases.py.
 The emulation runs the oracle with its convs wrapped: exactly the convs the engine sends through savsr_conv2d_batch_f16 get fp16 (RNE)
 operands and float64 products -- every static 3x3 / 1x1 conv of the propagation, pyramid, trunk and OSAdapt mask, and the OSConvs, whose
 operands are the input x and W'' = fa ca sa sum_k ka W computed in fp32 and rounded once (the engine folds the channel gate into the
-weights).  SATU (kernel_conv, the coordinate heads, fusion), the tail, the SE and attention MLPs keep fp32 operands.  oracle/ itself is
+weights; its fp16 kernels carry W'' in float64, which moves an entry by an fp16 step only where the sum cancels).  SATU (kernel_conv, the coordinate heads, fusion), the tail, the SE and attention MLPs keep fp32 operands.  oracle/ itself is
 unchanged.  Writes tests/golden/precision_outputs.npz:
     <case>/fp32, <case>/fp16emu             outputs [c, H, W]
     <case>/drift                            [max-abs, mean-abs] of fp16emu against fp32
@@ -12,6 +12,12 @@ unchanged.  Writes tests/golden/precision_outputs.npz:
     gt/psnr_fp32, gt/psnr_fp16emu           PSNR-Y of GT_CASE against the synthetic GT (tests/precision_cases.py)
 
     PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_precision.py
+
+--clips writes tests/golden/precision_clips.npz instead and leaves precision_outputs.npz alone: the same two runs on the clips that are not
+noise (tests/test_gpu_conv_range.py::_clips -- `lowpass`, `const`, `zero`) at 13 x 18, scale (2.5, 3.5), shipped configuration:
+    <clip>/fp32                             the fp32 oracle's output [3, H, W]
+    <clip>/drift                            [max-abs, mean-abs] of the fp16 emulation against it
+    manifest                                manifest_hash of the state_dict the weights were synthesised for
 """
 import os
 import sys
@@ -122,5 +128,26 @@ def main():
     print("wrote", os.path.getsize(os.path.join(GOLD, "precision_outputs.npz")) / 1e3, "KB")
 
 
+CLIPS_CASE = (13, 18, (2.5, 3.5))      # (h, w, scale) of tests/test_gpu_conv_range.py::test_network_on_non_noise_clips
+
+
+def main_clips():
+    from tests.test_gpu_conv_range import _clips
+    torch.set_num_threads(8)
+    h, w, sc = CLIPS_CASE
+    net = SAVSR()
+    sd = synth.synth_state_dict(synth.manifest_of(net.state_dict()), seed=WEIGHT_SEED)
+    out = {"manifest": np.array(manifest_hash(synth.manifest_of(net.state_dict())))}
+    with torch.no_grad():
+        for name, lq in _clips(h, w).items():
+            ref = run(sd, lq, sc, dict(net.cfg), False).numpy()
+            emu = run(sd, lq, sc, dict(net.cfg), True).numpy()
+            d = np.abs(emu.astype(np.float64) - ref)
+            out[f"{name}/fp32"], out[f"{name}/drift"] = ref, np.array([d.max(), d.mean()])
+            print(name, tuple(ref.shape), "max-abs %.3e mean-abs %.3e" % (d.max(), d.mean()), flush=True)
+    np.savez_compressed(os.path.join(GOLD, "precision_clips.npz"), **out)
+    print("wrote", os.path.getsize(os.path.join(GOLD, "precision_clips.npz")) / 1e3, "KB")
+
+
 if __name__ == "__main__":
-    main()
+    main_clips() if "--clips" in sys.argv[1:] else main()
