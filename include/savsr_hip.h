@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 49
+#define SAVSR_ABI_VERSION 50
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -734,6 +734,30 @@ int savsr_video_deinterlace_masked_u8(const uint8_t* frames, int n_frames, int64
 int savsr_video_deinterlace_masked_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int depth,
                                        int order, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, int method,
                                        const int32_t* flags, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 50) Temporal noise reduction (denoise.hip; savsr_amd.denoise_video, prepass.TemporalDenoiser, upscale_video(denoise="ata", ...),
+ * VideoUpscaler(denoise=...), --denoise of python -m savsr_amd.upscale): ffmpeg atadenoise's serial rule in 32-bit
+ * integers (savsr_amd/denoise.py `denoise_matrix` restates it sample by sample; the kernels equal it bit for bit).  Matrices are addressed
+ * as for savsr_video_deinterlace_*: matrix k of the n_frames resident frames starts at frames + k * frame_bytes + plane_offset, its rows
+ * follow each other directly.  Output frame n - from, n in [from, to), at out + (n - from) * out_frame_bytes + out_plane_offset: every
+ * sample x of frame n becomes (x + the taken taps + (k >> 1)) / k, k = 1 + the number of taken taps.  Taps are the same sample of frames
+ * n - 1, n - 2, ... and, in a walk of its own, n + 1, n + 2, ...: a walk takes the tap at distance d = 1 .. radius while
+ * |x - tap| <= A and its sum of these differences <= B, A = thr_a << (depth - 8), B = thr_b << (depth - 8), and ends at the first tap
+ * that fails or where the resident frames [0, n_frames) end, so a streaming caller passes `radius` frames of context on either side
+ * and the range.  The source and the output must not overlap.  The entries only enqueue (one launch for up to 65535 frames), allocate
+ * nothing, do not synchronise and are capturable.  Refused before the device is touched with SAVSR_E_ARG, savsr_last_error() naming
+ * the reason: a null pointer, n_frames < 1, rows < 1, an empty row, a plane above 2147418112 bytes, a range outside
+ * 0 <= from < to <= n_frames, a negative plane offset, a frame stride smaller than the offset plus the plane (either side), a radius
+ * outside 1 .. 16, thresholds outside 0 <= thr_a <= thr_b <= 255 (8-bit code units at every depth), overlapping source and output;
+ * _u16: a depth other than 10 / 12, an odd pointer, stride or offset.  16-byte accesses when the plane pointers and the frame strides
+ * of both sides and the plane's bytes are multiples of 16, a sample per access otherwise (any pointer, stride and size).
+ * savsr_video_denoise_u8:  matrices of rows x row_bytes bytes (a plane, or the h x (w * c) bytes of packed frames).
+ * savsr_video_denoise_u16: matrices of rows x cols little-endian 16-bit samples, every one read as min(s, 2^depth - 1). */
+int savsr_video_denoise_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int row_bytes, int radius,
+                           int thr_a, int thr_b, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
+int savsr_video_denoise_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int depth, int radius,
+                            int thr_a, int thr_b, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 45) Video surfaces (surface.hip; savsr_amd.unpack_surface, savsr_amd.pack_surface, upscale_video(surface=..., out_surface=...),

@@ -283,7 +283,9 @@ class SAVSR(nn.Module):
                       chroma_filter: Optional[str] = None, crop=None, crop_limit=24, bars: str = "keep", fields: Optional[str] = None,
                       pulldown: Optional[str] = None, pulldown_cycle: int = 5, *, surface=None, out_surface=None,
                       scan: Optional[str] = None, dither: Optional[str] = None, deinterlacer: str = "yadif",
-                      field_rate: str = "double", combed: Optional[str] = None, comb_threshold: int = 9, comb_pixels: int = 40) -> torch.Tensor:
+                      field_rate: str = "double", combed: Optional[str] = None, comb_threshold: int = 9, comb_pixels: int = 40,
+                      denoise: Optional[str] = None, denoise_radius: int = 4, denoise_strength=(4, 9),
+                      denoise_chroma_strength=None) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -392,13 +394,29 @@ class SAVSR(nn.Module):
         decimation drops one of every pulldown_cycle frames of a true-video insert (judder, not combing); a cleaned frame has half its
         rows interpolated; small or low-contrast combing stays below the rule; one verdict per video.  The defaults are fieldmatch's
         cthresh and combpel rescaled to the window; they are not validated on footage.
+        denoise, denoise_radius, denoise_strength, denoise_chroma_strength (keyword only): temporal noise reduction in front of the
+        network, for tape, tuner and sensor noise and MPEG-2 flicker, which a network trained on clean downsamples would enlarge as
+        detail.  denoise: None (the default: what ran before) or "ata": every sample becomes the rounded mean of itself and the same
+        sample of up to denoise_radius (1 .. 16, default 4: nine frames) frames on either side -- two independent walks, each taking
+        the next frame's sample while it differs by at most a and the walk's differences sum to at most b, denoise_strength = (a, b)
+        in 8-bit code units at every depth, 0 <= a <= b <= 255, default (4, 9) (savsr_amd/denoise.py: ffmpeg atadenoise's serial rule
+        in integers, on the GPU; the walks end at the video's ends).  Chroma planes take denoise_chroma_strength (None: the same).
+        The stage runs after surface= unpacking, scan="detect" and fields= / pulldown= (it needs progressive frames) and in front of
+        the crop, the cuts and the windows: the result is, bit for bit, upscale_video on savsr_amd.denoise_video(v', ...) with every
+        other argument the same, v' the deinterlaced or pulldown-removed video; the rule is per sample, so it commutes with crop=
+        exactly, and cuts="auto" scores the denoised frames.  uint8 and planar frames only; the denoise_ options are refused without
+        denoise=.  Static samples pass unchanged and no sample moves by more than min(a, b).  Temporal only -- no spatial or
+        motion-compensated filtering, so moving texture is not denoised at all; the taps read across scene cuts, where only the
+        thresholds stop them; one strength per video.  The defaults are parameters: nothing is validated on footage or on trained
+        weights.
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
         return upscale_video(self, frames, scale, padding, out, pixel_format, size, cuts, scene_threshold, colour, out_colour, depth, out_depth,
                              siting, out_siting, chroma_filter, crop, crop_limit, bars, fields, pulldown, pulldown_cycle, surface=surface,
                              out_surface=out_surface, scan=scan, dither=dither, deinterlacer=deinterlacer, field_rate=field_rate, combed=combed,
-                             comb_threshold=comb_threshold, comb_pixels=comb_pixels)
+                             comb_threshold=comb_threshold, comb_pixels=comb_pixels, denoise=denoise, denoise_radius=denoise_radius,
+                             denoise_strength=denoise_strength, denoise_chroma_strength=denoise_chroma_strength)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

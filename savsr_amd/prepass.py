@@ -2,7 +2,8 @@
 re-insertion, the deinterlacer, the pulldown removal and the scan detector that chooses between the two -- and, at the very boundary, the surface conversion (`unpack_surface` in front of
 all of them, `pack_surface` behind everything; savsr_amd/surface.py is its specification).  Each is a public call on any frames and a
 `_..._device` form on resident frames of a checked input side (what upscale_video calls on the whole video); the two that change the frame count are streaming stages as well
-(`FieldSplitter`, `PulldownRemover`; `make_stage` builds the one a call asks for; `ScanStats` is the detector's streaming form).  The
+(`FieldSplitter`, `PulldownRemover`; `make_stage` builds the one a call asks for; `ScanStats` is the detector's streaming form), and the temporal
+denoiser behind them is a third (`denoise_video`, `TemporalDenoiser`, `make_denoiser`; savsr_amd/denoise.py is its specification).  The
 numpy modules (scenes.py, active.py, deinterlace.py, pulldown.py, scan.py) are the specifications, bit for bit.  Where the byte matrices of a frame lie is `frames.plane_table`'s
 answer alone; fp32 CHW frames have entries of their own (`_f32`) and are one explicit branch in the two stages that accept them.
 """
@@ -14,6 +15,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import active
+from . import denoise as dn
 from . import pulldown as pd
 from . import scan as sc
 from .deinterlace import DEINTERLACERS, FIELD_ORDERS, FIELD_RATES, check_frame_rows, check_method, check_order, check_rate
@@ -329,15 +331,20 @@ def _check_fields(fields) -> Optional[str]:
     return fields
 
 
+def _sample_frames(frames: torch.Tensor, side: Side, size: Size, verb: str = "deinterlace") -> Tuple[int, int, int, int]:
+    """(N, c, h, w) of frames of integer samples (`detector_layout`'s, N = 0 allowed); refuses float frames, which the stage `verb`
+    names cannot take."""
+    if isinstance(frames, torch.Tensor) and not size and frames.is_floating_point():
+        raise ValueError(f"float frames have no integer samples to {verb}: give [N, h, w, c] uint8 or planar frames (quantise first)")
+    if isinstance(frames, torch.Tensor) and frames.dim() and int(frames.shape[0]) == 0:
+        return (0,) + detector_layout(frames.new_zeros((1,) + tuple(frames.shape[1:])), side, size)[1:]
+    return detector_layout(frames, side, size)
+
+
 def _field_frames(frames: torch.Tensor, side: Side, size: Size) -> Tuple[int, int, int, int]:
     """(N, c, h, w) of frames the deinterlacer takes (`detector_layout`'s, N = 0 allowed); refuses float frames and frames whose matrices
     have one row."""
-    if isinstance(frames, torch.Tensor) and not size and frames.is_floating_point():
-        raise ValueError("float frames have no integer samples to deinterlace: give [N, h, w, c] uint8 or planar frames (quantise first)")
-    if isinstance(frames, torch.Tensor) and frames.dim() and int(frames.shape[0]) == 0:
-        n, c, h, w = (0,) + detector_layout(frames.new_zeros((1,) + tuple(frames.shape[1:])), side, size)[1:]
-    else:
-        n, c, h, w = detector_layout(frames, side, size)
+    n, c, h, w = _sample_frames(frames, side, size)
     check_frame_rows(h, side.layout)
     return n, c, h, w
 
@@ -410,10 +417,14 @@ class _LookAhead:
     yet; take(None, last=True) hands back everything, the newest frame's next one clamped as at the end of the video, and (None, 0, 0)
     when nothing is left.  buffer[lo - 1] is the frame before the range where the video has one, buffer[hi] the frame after it where one
     was pushed.  Afterwards the window keeps that context frame and the frames not done yet, always as copies of its own, so that the
-    chunk they came with is released: at most two frames once a range was handed back."""
+    chunk they came with is released: at most two frames once a range was handed back.
+    ahead, behind (the temporal denoiser's radius; 1 and 1 above): a frame is final once `ahead` frames after it were pushed, and
+    `behind` frames before the range stay as its context, where the video has them: at most ahead + behind frames between pushes
+    (savsr_amd.denoise.stream_ranges is the numpy model of this indexing)."""
 
-    def __init__(self):
-        self.buf: Optional[torch.Tensor] = None          # the context frame (where there is one), then the frames not done yet
+    def __init__(self, ahead: int = 1, behind: int = 1):
+        self.ahead, self.behind = ahead, behind
+        self.buf: Optional[torch.Tensor] = None          # the context frames (where there are any), then the frames not done yet
         self.todo = 0                                    # how many of them are not done yet (they are the last ones)
 
     @property
@@ -430,11 +441,11 @@ class _LookAhead:
             buf = self.buf if frames is None else torch.cat([self.buf, frames], 0)
         n = int(buf.shape[0])
         lo = n - self.todo - k
-        hi = n if last else max(n - 1, lo)
+        hi = n if last else max(n - self.ahead, lo)
         if last:
             self.buf, self.todo = None, 0
         elif hi > lo:
-            self.buf, self.todo = buf[hi - 1:].clone(), n - hi
+            self.buf, self.todo = buf[max(hi - self.behind, 0):].clone(), n - hi
         else:          # (nothing final yet: the pushed frames wait; a first push is the caller's storage and is copied)
             self.buf, self.todo = buf.clone() if self.buf is None else buf, self.todo + k
         return buf, lo, hi
@@ -473,6 +484,82 @@ class FieldSplitter:
         if hi <= lo:          # nothing was pushed (or finish() ran before)
             return None
         return _deinterlace_device(src, self.order, self.side, self.size, lo, hi, self.method, self.rate)
+
+
+# ---- temporal noise reduction (savsr_amd/denoise.py is the specification) ------------------------------------------------------------------
+def _denoise_frames(frames: torch.Tensor, side: Side, size: Size) -> Tuple[int, int, int, int]:
+    """(N, c, h, w) of frames the denoiser takes: what the deinterlacer takes, frames of one row included."""
+    return _sample_frames(frames, side, size, "denoise")
+
+
+def _denoise_device(frames: torch.Tensor, side: Side, size: Size, radius: int = dn.DEFAULT_RADIUS, strength=dn.DEFAULT_STRENGTH,
+                    chroma_strength=None, lo: int = 0, hi: Optional[int] = None) -> torch.Tensor:
+    """savsr_video_denoise_* on resident frames of the input side on the GPU: the hi - lo denoised frames of frames [lo, hi) (default:
+    all), the taps taken among the resident frames, where the walks end.  One call per plane, on the current stream (no sync): the Y
+    plane and the bytes of packed frames with `strength`, the chroma planes with `chroma_strength` (None: `strength`)."""
+    n, c, h, w = _denoise_frames(frames, side, size)
+    frames, hi, tab = frames.contiguous(), n if hi is None else hi, plane_table(side, size, c, h, w)
+    out = frames.new_empty((max(hi - lo, 0),) + tuple(frames.shape[1:]))
+    for i, p in enumerate(tab.planes if hi > lo else ()):
+        a, b = strength if i == 0 or chroma_strength is None else chroma_strength
+        _matrix_call("denoise", frames, n, tab, p, side, (radius, a, b, lo, hi, out.data_ptr(), tab.stride, p.offset))
+    return out
+
+
+def denoise_video(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8, radius: int = dn.DEFAULT_RADIUS,
+                  strength=dn.DEFAULT_STRENGTH, chroma_strength=None) -> torch.Tensor:
+    """Temporal noise reduction: N frames on the GPU in the format of the N given ones (savsr_amd.denoise.denoise_frames is the
+    specification, bit for bit), on the caller's current stream, without a sync.  Every sample becomes the rounded mean of itself and
+    the same sample of up to `radius` frames on either side: two independent walks, each taking the next frame's sample while it
+    differs by at most a and the walk's differences sum to at most b (ffmpeg atadenoise's serial rule; strength = (a, b) in 8-bit code
+    units at every depth, 0 <= a <= b <= 255; 1 <= radius <= 16), ending at the video's ends.  frames as for `deinterlace`: [N, h, w, c]
+    uint8 (GPU or host, every byte with `strength`), or with pixel_format "i420", "i422", "i444", "y400" and size=(h, w): [N, frame_bytes]
+    uint8, every plane on its own, 16-bit samples at depth 10 / 12, the chroma planes with `chroma_strength` (None: `strength`).  Float
+    frames are refused.  Static samples come back as they are, no sample moves by more than min(a, b) codes (shifted to the depth), and
+    (0, 0) is the identity.  The defaults are parameters: nothing is validated on footage.  Temporal only: moving texture is not
+    denoised, and the taps read across scene cuts, where only the thresholds stop them."""
+    radius = dn.check_radius(radius)
+    strength = dn.check_strength(strength)
+    chroma_strength = None if chroma_strength is None else dn.check_strength(chroma_strength, "chroma_strength")
+    frames, side, size = _stage_args(frames, pixel_format, size, depth, _denoise_frames)
+    return _denoise_device(frames, side, size, radius, strength, chroma_strength)
+
+
+class TemporalDenoiser:
+    """The streaming denoiser behind VideoUpscaler(denoise=...): push(frames on the GPU) returns the denoised frames that are final --
+    frame n once frame n + radius has been pushed -- and finish() the rest (None without a pushed frame).  Between pushes the device
+    keeps at most 2 * radius frames: `radius` behind as context and `radius` not done yet, copies of their own, so that the chunk they
+    came with is released.  Concatenated, the outputs are `denoise_video` on the whole video for any chunking."""
+
+    def __init__(self, side: Side, size: Size, radius: int = dn.DEFAULT_RADIUS, strength=dn.DEFAULT_STRENGTH, chroma_strength=None):
+        self.side, self.size = side, size
+        self.radius, self.strength = dn.check_radius(radius), dn.check_strength(strength)
+        self.chroma_strength = None if chroma_strength is None else dn.check_strength(chroma_strength, "chroma_strength")
+        self._win = _LookAhead(self.radius, self.radius)
+
+    @property
+    def held(self) -> int:
+        """Frames on the device between pushes: at most 2 * radius."""
+        return self._win.held
+
+    def _run(self, src: torch.Tensor, lo: int, hi: int) -> torch.Tensor:
+        return _denoise_device(src, self.side, self.size, self.radius, self.strength, self.chroma_strength, lo, hi)
+
+    def push(self, frames: torch.Tensor) -> torch.Tensor:
+        return self._run(*self._win.take(frames))
+
+    def finish(self) -> Optional[torch.Tensor]:
+        src, lo, hi = self._win.take(None, True)
+        if hi <= lo:          # nothing was pushed (or finish() ran before)
+            return None
+        return self._run(src, lo, hi)
+
+
+def make_denoiser(denoise, radius, strength, chroma_strength, side: Side, size: Size) -> Optional[TemporalDenoiser]:
+    """The streaming stage denoise= / denoise_radius= / denoise_strength= / denoise_chroma_strength= ask for, on frames of `side`, behind
+    `make_stage`'s: None without denoise= (after `denoise.check_denoise_options` has refused options without it)."""
+    opts = dn.check_denoise_options(denoise, radius, strength, chroma_strength)
+    return None if opts is None else TemporalDenoiser(side, size, *opts)
 
 
 # ---- telecined film (savsr_amd/pulldown.py is the specification) -----------------------------------------------------------------------------

@@ -13,6 +13,7 @@
     ffmpeg -i pal_dv.avi -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out50p.y4m --scale 4 --checkpoint <net.pth> --fields auto
     python -m savsr_amd.upscale -i letterboxed_sd.y4m -o hd.y4m --scale 4 --checkpoint <net.pth> --crop auto --colour auto --out-colour auto
     python -m savsr_amd.upscale -i dvd_rip.y4m -o out.y4m --scale 4 --checkpoint <net.pth> --scan detect --scan-out scan.json
+    ffmpeg -i vhs_capture.avi -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out.y4m --scale 4 --checkpoint <net.pth> --fields auto --denoise ata --denoise-strength 4,9
     ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out444p10.y4m --scale 4 --checkpoint <net.pth> --out-chroma 444
 
 PNG folder: frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on
@@ -114,6 +115,16 @@ per-frame repeated field).  Not on stdin (there is no second pass: give --fields
 --pulldown.  The rule and its thresholds are this project's own and are not validated on real footage; one verdict per video: mixed
 content, 2:2 PAL film, cadences other than 3:2 and fades are not handled.
 
+--denoise ata: noisy footage (tape and tuner noise, sensor noise, the temporal flicker MPEG-2 quantisation leaves), which a network
+trained on clean downsamples enlarges as detail.  Every sample is averaged on the GPU with the same sample of up to --denoise-radius N
+(default 4: nine frames; 1 .. 16) frames on either side, in two independent walks that each take the next frame's sample while it
+differs by at most A and the walk's differences sum to at most B (--denoise-strength A,B in 8-bit code units at every depth, default
+4,9; ffmpeg atadenoise's serial rule, savsr_amd/denoise.py); --denoise-chroma-strength A,B sets the chroma planes of a Y4M input apart.
+The stage runs behind --fields / --pulldown / --scan detect (it needs progressive frames) and in front of --crop and --cuts, which see
+the denoised frames; N frames are held back and flushed at the end, and one line on stderr names the stage and its parameters.  Works
+for PNG folders and for .y4m files and pipes.  Temporal only: moving texture is not denoised, the taps read across scene cuts (only the
+thresholds stop them), one strength per video; the defaults are parameters and nothing is validated on footage.
+
 It ends with one line: frames, seconds, frames/s (on stderr when the video goes to stdout); with --cuts, the scene count as well; with
 --colour / --out-colour, the two colour spaces.
 """
@@ -128,6 +139,7 @@ import time
 from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional
 
+from .denoise import DEFAULT_RADIUS, DEFAULT_STRENGTH, DENOISERS, MAX_RADIUS, check_radius, check_strength
 from .dither import DITHERS
 from .deinterlace import DEINTERLACERS, FIELD_FLAGS, FIELD_ORDERS, FIELD_RATES, resolve_fields
 from .pulldown import (DEFAULT_COMB_PIXELS, DEFAULT_COMB_THRESHOLD, DEFAULT_CYCLE, PULLDOWN_FLAGS, check_comb_pixels, check_comb_threshold, check_cycle,
@@ -271,6 +283,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--comb-pixels", type=int, default=None, metavar="N",
                    help="--combed: a frame is combed when a 16 x 16 window holds N combed pixels (default 40 of 128, fieldmatch's combpel "
                         "80 / 256; 1 .. 128; not validated on footage)")
+    p.add_argument("--denoise", default=None, choices=["none"] + list(DENOISERS),
+                   help="temporal noise reduction on the GPU in front of the network.  ata: every sample is averaged with the same sample of "
+                        "the frames around it while they stay close to it (ffmpeg atadenoise's serial rule); none (default): the frames go "
+                        "through as they are")
+    p.add_argument("--denoise-radius", type=int, default=None, metavar="N",
+                   help=f"--denoise: the frames averaged on either side (default {DEFAULT_RADIUS}: nine frames; 1 .. {MAX_RADIUS})")
+    p.add_argument("--denoise-strength", default=None, metavar="A,B",
+                   help=f"--denoise: a tap is taken while it differs by at most A and the differences of its side sum to at most B, in 8-bit "
+                        f"code units at every depth (default {DEFAULT_STRENGTH[0]},{DEFAULT_STRENGTH[1]}; 0 <= A <= B <= 255; not validated on footage)")
+    p.add_argument("--denoise-chroma-strength", default=None, metavar="A,B",
+                   help="--denoise: the same for the chroma planes of a Y4M input (default: --denoise-strength)")
     p.add_argument("--scan", default=None, choices=list(SCAN_FLAGS),
                    help="detect: find out from the content, in a first pass over the input (a file or a folder), whether it is progressive, "
                         "interlaced or telecined film and with which field order, then run as --fields X / --pulldown X would; the verdict "
@@ -293,6 +316,17 @@ def parse_crop(text: str):
     if len(rect) != 4:
         raise ValueError(f"auto or Y0,X0,H,W, got {text!r}")
     return check_rect(rect, None, None, None)
+
+
+def parse_strength(text: str, what: str):
+    """--denoise-strength / --denoise-chroma-strength: "A,B" -> the checked (a, b)."""
+    try:
+        pair = tuple(int(t.strip()) for t in text.split(","))
+    except ValueError:
+        raise ValueError(f"{what}: A,B with integers, got {text!r}") from None
+    if len(pair) != 2:
+        raise ValueError(f"{what}: A,B, got {text!r}")
+    return check_strength(pair, what)
 
 
 def parse_cuts(text: str):
@@ -393,6 +427,19 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     try:
         check_comb_threshold(a.comb_threshold, "--comb-threshold")
         check_comb_pixels(a.comb_pixels, "--comb-pixels")
+    except ValueError as e:
+        p.error(str(e))
+    a.denoise = None if a.denoise == "none" else a.denoise
+    if a.denoise is None:
+        if a.denoise_radius is not None or a.denoise_strength is not None or a.denoise_chroma_strength is not None:
+            p.error("--denoise-radius, --denoise-strength and --denoise-chroma-strength go with --denoise ata")
+    elif a.denoise_chroma_strength is not None and not a.y4m_in:
+        p.error("--denoise-chroma-strength goes with a Y4M input (PNG frames are RGB: every byte takes --denoise-strength)")
+    try:
+        a.denoise_radius = check_radius(DEFAULT_RADIUS if a.denoise_radius is None else a.denoise_radius, "--denoise-radius")
+        a.denoise_strength = DEFAULT_STRENGTH if a.denoise_strength is None else parse_strength(a.denoise_strength, "--denoise-strength")
+        if a.denoise_chroma_strength is not None:
+            a.denoise_chroma_strength = parse_strength(a.denoise_chroma_strength, "--denoise-chroma-strength")
     except ValueError as e:
         p.error(str(e))
     try:
@@ -563,6 +610,14 @@ def written_lr(h, w, rect, bars: str):
     return (h, w) if rect is None or bars == "keep" else (rect[2], rect[3])
 
 
+def denoise_kwargs(a: argparse.Namespace) -> dict:
+    """--denoise and its options as the keyword arguments of VideoUpscaler; nothing without --denoise."""
+    if a.denoise is None:
+        return {}
+    return dict(denoise=a.denoise, denoise_radius=a.denoise_radius, denoise_strength=a.denoise_strength,
+                denoise_chroma_strength=a.denoise_chroma_strength)
+
+
 def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev, order: Optional[str] = None, film: Optional[str] = None):
     """--crop auto's first pass: savsr_amd.line_sums over the input in --chunk-sized pieces with a running maximum on the device, then
     cropdetect's rule and the alignment to the input layout's chroma block.  chunks: the PNG folder's chunk iterator; None: the .y4m file
@@ -573,7 +628,7 @@ def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, de
 
     from . import active
     from .frames import detector_side, layout_of
-    from .prepass import line_sums, make_stage
+    from .prepass import line_sums, make_denoiser, make_stage
     from .y4m import Y4MReader
     from .yuv import CHROMAS
     top = None
@@ -581,9 +636,15 @@ def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, de
     how = (a.deinterlacer, a.field_rate) if order is not None else ()          # (they say how --fields is carried out, and nothing else)
     comb = dict(combed=a.combed, comb_threshold=a.comb_threshold, comb_pixels=a.comb_pixels) if film is not None and a.combed is not None else {}
     split = make_stage(order, film, a.pulldown_cycle, *detector_side(fmt_in, size, depth), *how, **comb)
+    # (--denoise: the sums are taken on the denoised frames, as upscale_video's crop="auto" takes them)
+    noise = make_denoiser(a.denoise, a.denoise_radius, a.denoise_strength, a.denoise_chroma_strength, *detector_side(fmt_in, size, depth))
 
-    def fold(frames):
+    def fold(frames, final: bool = False):
         nonlocal top
+        if noise is not None and not final:
+            if int(frames.shape[0]):
+                fold(noise.push(frames), True)
+            return
         if int(frames.shape[0]):
             rows, cols = line_sums(frames, fmt_in, size, depth)
             now = torch.cat([rows.amax(0), cols.amax(0)])
@@ -601,6 +662,9 @@ def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, de
             last = None if split is None else split.finish()
             if last is not None:
                 fold(last)
+            last = None if noise is None else noise.finish()
+            if last is not None:
+                fold(last, True)
     finally:
         if f is not None:
             f.close()
@@ -808,7 +872,13 @@ def main(argv: Optional[List[str]] = None) -> int:
                            dither=a.dither, **(dict(deinterlacer=a.deinterlacer, field_rate=a.field_rate) if order is not None else {}),
                            # (--combed with --scan detect says how a telecine verdict is carried out: ignored for the other verdicts)
                            **(dict(combed=a.combed, comb_threshold=a.comb_threshold, comb_pixels=a.comb_pixels)
-                              if film is not None and a.combed is not None else {}))
+                              if film is not None and a.combed is not None else {}),
+                           **denoise_kwargs(a))
+        if a.denoise is not None:
+            cs = a.denoise_chroma_strength or a.denoise_strength
+            print(f"--denoise {a.denoise}: radius {a.denoise_radius} ({2 * a.denoise_radius + 1} frames), strength {a.denoise_strength[0]},"
+                  f"{a.denoise_strength[1]}" + (f", chroma strength {cs[0]},{cs[1]}" if a.y4m_in else "")
+                  + " (8-bit code units; not validated on footage)", file=sys.stderr, flush=True)
         done = 0
         try:
             for chunk in chunks:

@@ -27,6 +27,12 @@ scan="detect": the call finds out which of the two the video is (savsr_amd/scan.
 right after surface= unpacking and in front of everything else) and continues exactly as if the verdict's `kwargs()` had been given:
 fields=order for interlaced video, pulldown=order for telecined film, nothing for progressive and undetermined video.
 
+denoise="ata": temporal noise reduction (savsr_amd/denoise.py: ffmpeg atadenoise's serial rule, two independent walks over the frames
+before and after) behind surface= unpacking, scan="detect" and fields= / pulldown= -- it needs progressive frames -- and in front of the
+crop, the cuts and the windows: the call is, bit for bit, the call on `denoise_video(v', ...)`, v' the deinterlaced or pulldown-removed
+video.  The rule is per sample, so it commutes with crop= exactly; cuts="auto" scores the denoised frames.  None runs the lines that ran
+before.
+
 dither="ordered": every quantiser behind the network (packed uint8, planar YUV, the luma-only path's Y plane) takes floor(t + theta(y, x))
 in rint's place, theta from a 16 x 16 Bayer matrix at the sample's position in its plane (savsr_amd/dither.py is the specification, the
 `_d` entries of the C ABI the kernels).  It belongs to the quantiser: bars="keep" inserts exact nominal black after it and out_surface
@@ -51,10 +57,12 @@ from .frames import (OUT_KINDS, PADDING_MODES, PIXEL_FORMATS, SAMPLE_FORMATS, YU
                      check_sitings, chroma_of, frame_layout, i420_layout, layout_of, luma_mode, video_spec)
 from .harness import window_indices
 from .packing import get_hw
-from .prepass import (FieldSplitter, PulldownRemover, ScanStats, _check_crop_args, _check_field_options, _check_fields, _check_pulldown,  # noqa: F401  (re-exported)
-                      _check_scan, _crop_device, _cropped_spec, _deinterlace_device, _detect_device, _detect_scan_device, _field_frames,
-                      _insert_device, _pair_sad_device, _pack_surface_device, _remove_pulldown_device, _to_device, _unpack_surface_device,
-                      comb_windows, deinterlace, detect_active_area, detect_cuts, detect_scan, field_scores, field_stats, line_sums, make_stage,
+from .denoise import check_denoise_options
+from .prepass import (FieldSplitter, PulldownRemover, ScanStats, TemporalDenoiser, _check_crop_args, _check_field_options, _check_fields,  # noqa: F401  (re-exported)
+                      _check_pulldown, _check_scan, _crop_device, _cropped_spec, _deinterlace_device, _denoise_device, _denoise_frames,
+                      _detect_device, _detect_scan_device, _field_frames, _insert_device, _pair_sad_device, _pack_surface_device,
+                      _remove_pulldown_device, _to_device, _unpack_surface_device, comb_windows, deinterlace, denoise_video,
+                      detect_active_area, detect_cuts, detect_scan, field_scores, field_stats, line_sums, make_denoiser, make_stage,
                       pack_surface, pair_sad, remove_pulldown, surface_layout, surface_side, surface_table, unpack_surface)
 from .pulldown import check_comb_options
 from .scan import ScanVerdict, check_thresholds  # noqa: F401  (re-exported)
@@ -97,13 +105,15 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
                   out_siting: Optional[str] = None, chroma_filter: Optional[str] = None, crop=None, crop_limit=24,
                   bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None, pulldown_cycle: int = 5, *,
                   surface=None, out_surface=None, scan: Optional[str] = None, dither: Optional[str] = None, deinterlacer: str = "yadif",
-                  field_rate: str = "double", combed: Optional[str] = None, comb_threshold: int = 9, comb_pixels: int = 40) -> torch.Tensor:
+                  field_rate: str = "double", combed: Optional[str] = None, comb_threshold: int = 9, comb_pixels: int = 40,
+                  denoise: Optional[str] = None, denoise_radius: int = 4, denoise_strength=(4, 9), denoise_chroma_strength=None) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
     spec = video_spec(net.cfg["num_in_ch"], out, pixel_format, size, colour, out_colour, depth, out_depth, siting, out_siting, chroma_filter,
                       dither)
     sc = as_scale(net.scale if scale is None else scale)
+    noise = check_denoise_options(denoise, denoise_radius, denoise_strength, denoise_chroma_strength)          # None: the path as it was
     if surface is not None:            # the frames lie in a surface: checked against it, unpacked below, and planar from there on
         in_tab = surface_table(surface, spec.inp, spec.size)
         n, (h, w) = surface_layout(frames, in_tab), spec.size
@@ -114,6 +124,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         shaped = frames
     if out_surface is not None:        # (its table: once the crop is checked, or found)
         surface_side(out_surface, spec.out, "out_surface")
+    if noise is not None:              # (integer samples only: float frames are refused here, before the GPU is touched)
+        _denoise_frames(shaped, spec.inp, spec.size)
     # (deinterlacer= / field_rate= also go with scan="detect": they say how an interlaced verdict is carried out)
     _check_field_options(deinterlacer, field_rate, fields, pulldown, scan is not None)
     # (combed= also goes with scan="detect": it says how a telecine verdict is carried out, and is ignored for the other verdicts)
@@ -158,6 +170,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         frames = _deinterlace_device(frames, fields, spec.inp, spec.size, method=deinterlacer, rate=field_rate)
     if pulldown is not None:           # pulldown removal comes first, where deinterlacing comes
         frames = _remove_pulldown_device(frames, pulldown, spec.inp, spec.size, pulldown_cycle, combed, comb_threshold, comb_pixels)[0]
+    if noise is not None:              # the denoiser sees progressive frames, and the crop, the cuts and the windows see its output
+        frames = _denoise_device(frames, spec.inp, spec.size, *noise)
     full = spec
     if crop == "auto":
         crop = _detect_device(frames, spec.inp, spec.size, crop_limit)
@@ -229,6 +243,12 @@ class VideoUpscaler:
     dither= (keyword only): as in upscale_video.  The pattern depends on the sample's position in the frame alone, never on the frame's
     index, so any chunking gives the same frames.
 
+    denoise="ata", denoise_radius=4, denoise_strength=(4, 9), denoise_chroma_strength=None (keyword only): temporal noise reduction, as in
+    upscale_video, through a prepass.TemporalDenoiser chained behind the fields= / pulldown= stage: a progressive frame goes on once
+    denoise_radius frames after it have arrived, so push() holds that many back and finish() flushes them; the device keeps at most
+    2 * denoise_radius more frames between pushes (denoise_radius behind as context, denoise_radius not done yet).  The cuts, the crop
+    and the windows operate on the denoised frames; any chunking gives the same frames.
+
     scan="detect" is refused: the decision needs the video.  Run savsr_amd.detect_scan on a probe chunk (or prepass.ScanStats over a
     first pass, as python -m savsr_amd.upscale --scan detect does) and give its answer as fields= / pulldown=."""
 
@@ -238,7 +258,8 @@ class VideoUpscaler:
                  chroma_filter: Optional[str] = None, crop=None, bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None,
                  pulldown_cycle: int = 5, *, surface=None, out_surface=None, scan: Optional[str] = None, dither: Optional[str] = None,
                  deinterlacer: str = "yadif", field_rate: str = "double", combed: Optional[str] = None, comb_threshold: int = 9,
-                 comb_pixels: int = 40):
+                 comb_pixels: int = 40, denoise: Optional[str] = None, denoise_radius: int = 4, denoise_strength=(4, 9),
+                 denoise_chroma_strength=None):
         _check_net(net)
         check_padding(padding)
         _check_scan(scan, fields, pulldown, pulldown_cycle, auto_ok=False)          # (None is the only value that passes: the path as it was)
@@ -257,6 +278,8 @@ class VideoUpscaler:
         self._full = self.spec                     # the spec of the chunks as pushed; `spec` becomes the cropped size's with a crop
         self._split = make_stage(fields, pulldown, pulldown_cycle, self.spec.inp, self.spec.size, deinterlacer, field_rate, combed, comb_threshold,
                                  comb_pixels)          # the stage in front; None: as it was
+        # the temporal denoiser, behind that stage (it needs progressive frames) and in front of the crop; None: as it was
+        self._noise = make_denoiser(denoise, denoise_radius, denoise_strength, denoise_chroma_strength, self.spec.inp, self.spec.size)
         self._rect = _check_crop_args(crop, 24, bars, auto_ok=False)          # the rect to crop every chunk to; None: no crop, as it was
         self.bars = bars
         if self._rect is not None and self.spec.size:
@@ -351,6 +374,8 @@ class VideoUpscaler:
         staged = self._split is not None
         if staged:
             _field_frames(frames, self._full.inp, self._full.size)
+        if self._noise is not None:
+            _denoise_frames(frames, self._full.inp, self._full.size)
         _, h, w = self._full.frames_hw(frames)
         shape = (frames.dtype == torch.uint8, h, w)
         if staged:
@@ -378,6 +403,10 @@ class VideoUpscaler:
         if self._split is not None:                # interlaced / telecined chunks: the progressive frames that are final go on as a chunk of their own
             new = self._split.push(new)
             if int(new.shape[0]) == 0:             # (a first push of one frame, or a cycle not complete yet: nothing is final)
+                return self._emit(self._empty())
+        if self._noise is not None:                # the frames whose `denoise_radius` successors have arrived go on, denoised
+            new = self._noise.push(new)
+            if int(new.shape[0]) == 0:
                 return self._emit(self._empty())
         return self._emit(self._take(new))
 
@@ -433,6 +462,10 @@ class VideoUpscaler:
             raise RuntimeError("finish() called twice")
         self._finished = True
         last = None if self._split is None else self._split.finish()          # the held source frame's two fields, then the end as ever
+        if self._noise is not None:                # they go through the denoiser, which then hands back the frames it held
+            parts = [] if last is None or int(last.shape[0]) == 0 else [self._noise.push(last)]
+            parts = [p for p in parts + [self._noise.finish()] if p is not None and int(p.shape[0])]
+            last = torch.cat(parts, 0) if parts else None
         if last is not None:
             head = self._take(last)
             return self._emit(torch.cat([head, self._finish()], 0))
