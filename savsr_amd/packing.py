@@ -339,6 +339,22 @@ def lanes_wbe(wbe: np.ndarray, r0: int = 0) -> np.ndarray:
     return wbe[2 * ks + _LH, r0 + _LI, _J]
 
 
+def group_kconv(tap: int, cg: int, ks: int, c: int) -> int:
+    """Index of the 512-element (hi | lo) group of lanes_kconv's (tap, cg, ks) in the kconv_w image."""
+    return (tap * (c // 32) + cg) * (c // 16) + ks
+
+
+def group_proj_tuned(part: int, tile: int, ks: int, ntiles: int) -> int:
+    """Group of k step ks of a tile of pack_satu_tuned's proj_w image: part 0 = Wa (lanes_acc), 1 = Wb, 2 = the C-stack (lanes_a; tile 0);
+    ntiles 32-row tiles per projection (2: "plain", 1: "p27" / "q")."""
+    return ((part * ntiles + tile) if part < 2 else 2 * ntiles) * 4 + ks
+
+
+def group_wbe(tile: int, ks: int) -> int:
+    """Group of k step ks (k = 8 n + j) of lanes_wbe's tile in the wbe_w image."""
+    return 2 * tile + ks
+
+
 def bias_acc_order(b: np.ndarray) -> np.ndarray:
     """A bias of 32 T rows in accumulator-register order: [2 half][16 t + r] = b[32 t + acc_row(r, half)], r < 16."""
     half, t, r = np.arange(2)[:, None, None], np.arange(len(b) // 32)[:, None], np.arange(16)
