@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 50
+#define SAVSR_ABI_VERSION 51
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -758,6 +758,29 @@ int savsr_video_denoise_u8(const uint8_t* frames, int n_frames, int64_t frame_by
                            int thr_a, int thr_b, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
 int savsr_video_denoise_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int depth, int radius,
                             int thr_a, int thr_b, int from, int to, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 51) Spatial noise reduction (nlmeans.hip; savsr_amd.denoise_spatial, upscale_video(spatial_denoise="nlm", ...),
+ * VideoUpscaler(spatial_denoise=...), --spatial-denoise of python -m savsr_amd.upscale): non-local means in 32-bit
+ * integers, every frame on its own (savsr_amd/nlmeans.py `nlm_matrix` restates it; the kernels equal it bit for bit).  The plane of frame
+ * k starts at frames + k * frame_bytes + plane_offset and has rows rows of cols * step samples that follow each other directly; sample x
+ * of a row meets the samples x +- j * step only, so step = 1 filters a plane and step = c filters every channel of packed frames of c
+ * samples per pixel (cols pixels a row) as a plane of its own.  Output frame k at out + k * out_frame_bytes + out_plane_offset, laid out
+ * alike: sample p becomes (sum of w * v[q] + (sum of w >> 1)) / sum of w over the candidates q = p + (dy, dx), |dy|, |dx| <= search,
+ * inside the plane, w = W[((SSD >> 2 (depth - 8)) * 64) / divisor] for an index below 577 and 0 above, W[i] = rint(4096 exp(-i / 64)),
+ * SSD the sum of squared differences of the (2 patch + 1)^2 patches around p and q with coordinates clamped to the plane.  The callers'
+ * divisor is rint((2 patch + 1)^2 h^2), h the strength in 8-bit code units; their defaults (patch 3, search 7, h 3.0) are parameters,
+ * nothing is validated on footage.  The entries only enqueue (one launch for up to 16383 frames), allocate nothing, do not synchronise
+ * and are capturable.  Refused before the device is touched with SAVSR_E_ARG, savsr_last_error() naming the reason: a null pointer,
+ * n_frames < 1, rows < 1, cols < 1, a step outside 1 .. 4, a plane above 2147418112 bytes, a negative plane offset, a frame stride
+ * smaller than the offset plus the plane (either side), a patch outside 1 .. 3, a search outside 1 .. 7, a divisor outside 1 .. 65536,
+ * overlapping source and output; _u16: a depth other than 10 / 12, an odd pointer, stride or offset.
+ * savsr_video_nlmeans_u8:  planes of rows x (cols * step) bytes.
+ * savsr_video_nlmeans_u16: the same in little-endian 16-bit samples, every one read as min(s, 2^depth - 1). */
+int savsr_video_nlmeans_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step, int patch,
+                           int search, int divisor, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
+int savsr_video_nlmeans_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step, int depth,
+                            int patch, int search, int divisor, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 45) Video surfaces (surface.hip; savsr_amd.unpack_surface, savsr_amd.pack_surface, upscale_video(surface=..., out_surface=...),

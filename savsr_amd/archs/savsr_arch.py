@@ -285,7 +285,8 @@ class SAVSR(nn.Module):
                       scan: Optional[str] = None, dither: Optional[str] = None, deinterlacer: str = "yadif",
                       field_rate: str = "double", combed: Optional[str] = None, comb_threshold: int = 9, comb_pixels: int = 40,
                       denoise: Optional[str] = None, denoise_radius: int = 4, denoise_strength=(4, 9),
-                      denoise_chroma_strength=None) -> torch.Tensor:
+                      denoise_chroma_strength=None, spatial_denoise: Optional[str] = None, spatial_patch: int = 3, spatial_search: int = 7,
+                      spatial_strength=3.0, spatial_chroma_strength=None) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -409,6 +410,21 @@ class SAVSR(nn.Module):
         motion-compensated filtering, so moving texture is not denoised at all; the taps read across scene cuts, where only the
         thresholds stop them; one strength per video.  The defaults are parameters: nothing is validated on footage or on trained
         weights.
+        spatial_denoise, spatial_patch, spatial_search, spatial_strength, spatial_chroma_strength (keyword only): spatial noise
+        reduction in front of the network, for grain, tuner and sensor noise on what moves, which denoise= leaves untouched.
+        spatial_denoise: None (the default: what ran before) or "nlm": non-local means on the GPU, every frame on its own -- a sample
+        becomes the weighted mean of the samples within spatial_search (1 .. 7, default 7: a 15 x 15 window) of it inside the plane,
+        weighted by exp(-SSD / ((2 P + 1)^2 h^2)) from an integer table, SSD the squared difference of the (2 P + 1)^2 patches around
+        the two, P = spatial_patch (1 .. 3, default 3), h = spatial_strength in 8-bit code units at every depth (0 < h <= 32, default
+        3.0; savsr_amd/nlmeans.py is the rule in integers).  Chroma planes take spatial_chroma_strength (None: the same); every
+        channel of packed frames is a plane of its own.  The stage runs after denoise= and after the crop, in front of the cuts and
+        the windows: with crop=None the result is, bit for bit, upscale_video on savsr_amd.denoise_spatial(v', ...), v' the video
+        after fields= / pulldown= / denoise=; with crop=rect and bars="drop" it is upscale_video on
+        denoise_spatial(crop_frames(v', rect), ...), and with bars="keep" the picture inside the bars is those bytes (the rule does
+        not commute with a crop: the bars never enter a patch).  cuts="auto" scores the filtered frames, crop="auto" reads the
+        unfiltered ones.  uint8 and planar frames only; the spatial_ options are refused without spatial_denoise=.  One strength per
+        video, no joint-channel weights, the centre weight is not corrected for noise, the search stops at 15 x 15.  The defaults are
+        parameters: nothing is validated on footage or on trained weights, and nothing is pinned to ffmpeg's output.
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
@@ -416,7 +432,9 @@ class SAVSR(nn.Module):
                              siting, out_siting, chroma_filter, crop, crop_limit, bars, fields, pulldown, pulldown_cycle, surface=surface,
                              out_surface=out_surface, scan=scan, dither=dither, deinterlacer=deinterlacer, field_rate=field_rate, combed=combed,
                              comb_threshold=comb_threshold, comb_pixels=comb_pixels, denoise=denoise, denoise_radius=denoise_radius,
-                             denoise_strength=denoise_strength, denoise_chroma_strength=denoise_chroma_strength)
+                             denoise_strength=denoise_strength, denoise_chroma_strength=denoise_chroma_strength,
+                             spatial_denoise=spatial_denoise, spatial_patch=spatial_patch, spatial_search=spatial_search,
+                             spatial_strength=spatial_strength, spatial_chroma_strength=spatial_chroma_strength)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

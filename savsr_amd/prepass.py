@@ -3,7 +3,8 @@ re-insertion, the deinterlacer, the pulldown removal and the scan detector that 
 all of them, `pack_surface` behind everything; savsr_amd/surface.py is its specification).  Each is a public call on any frames and a
 `_..._device` form on resident frames of a checked input side (what upscale_video calls on the whole video); the two that change the frame count are streaming stages as well
 (`FieldSplitter`, `PulldownRemover`; `make_stage` builds the one a call asks for; `ScanStats` is the detector's streaming form), and the temporal
-denoiser behind them is a third (`denoise_video`, `TemporalDenoiser`, `make_denoiser`; savsr_amd/denoise.py is its specification).  The
+denoiser behind them is a third (`denoise_video`, `TemporalDenoiser`, `make_denoiser`; savsr_amd/denoise.py is its specification); the spatial
+denoiser behind the crop is stateless (`denoise_spatial`; savsr_amd/nlmeans.py is its specification).  The
 numpy modules (scenes.py, active.py, deinterlace.py, pulldown.py, scan.py) are the specifications, bit for bit.  Where the byte matrices of a frame lie is `frames.plane_table`'s
 answer alone; fp32 CHW frames have entries of their own (`_f32`) and are one explicit branch in the two stages that accept them.
 """
@@ -16,6 +17,7 @@ import torch
 
 from . import active
 from . import denoise as dn
+from . import nlmeans as nl
 from . import pulldown as pd
 from . import scan as sc
 from .deinterlace import DEINTERLACERS, FIELD_ORDERS, FIELD_RATES, check_frame_rows, check_method, check_order, check_rate
@@ -560,6 +562,44 @@ def make_denoiser(denoise, radius, strength, chroma_strength, side: Side, size: 
     `make_stage`'s: None without denoise= (after `denoise.check_denoise_options` has refused options without it)."""
     opts = dn.check_denoise_options(denoise, radius, strength, chroma_strength)
     return None if opts is None else TemporalDenoiser(side, size, *opts)
+
+
+# ---- spatial noise reduction (savsr_amd/nlmeans.py is the specification) --------------------------------------------------------------------
+def _denoise_spatial_device(frames: torch.Tensor, side: Side, size: Size, patch: int = nl.DEFAULT_PATCH, search: int = nl.DEFAULT_SEARCH,
+                            strength=nl.DEFAULT_STRENGTH, chroma_strength=None) -> torch.Tensor:
+    """savsr_video_nlmeans_* on resident frames of the input side on the GPU: as many filtered frames, every frame on its own.  One call
+    per plane, on the current stream (no sync): the Y plane with `strength`, the chroma planes with `chroma_strength` (None:
+    `strength`); packed frames in one call, every channel a plane of its own (the channel count is the entry's sample step)."""
+    n, c, h, w = _denoise_frames(frames, side, size)          # (what the temporal denoiser takes)
+    frames, tab = frames.contiguous(), plane_table(side, size, c, h, w)
+    out = torch.empty_like(frames)
+    step = max(c, 1)
+    for i, p in enumerate(tab.planes if n else ()):
+        d = nl.divisor(patch, strength if i == 0 or chroma_strength is None else chroma_strength)
+        head = (p.row_bytes // (tab.sample * step), step) + (() if tab.sample == 1 else (side.depth,))
+        _entry_call("savsr_video_nlmeans_u8" if tab.sample == 1 else "savsr_video_nlmeans_u16", frames, n, tab, p, head,
+                    (patch, search, d, out.data_ptr(), tab.stride, p.offset))
+    return out
+
+
+def denoise_spatial(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8, patch: int = nl.DEFAULT_PATCH,
+                    search: int = nl.DEFAULT_SEARCH, strength=nl.DEFAULT_STRENGTH, chroma_strength=None) -> torch.Tensor:
+    """Spatial noise reduction (non-local means): N frames on the GPU in the format of the N given ones (savsr_amd.nlmeans.nlm_frames is
+    the specification, bit for bit), on the caller's current stream, without a sync.  Every frame is filtered on its own: a sample
+    becomes the weighted mean of the samples within `search` (1 .. 7) of it that lie inside the plane, each weighted by
+    exp(-SSD / ((2 patch + 1)^2 h^2)) from a 577-entry integer table, SSD the squared difference of the (2 patch + 1)^2 patches
+    (patch 1 .. 3) around the two, h = `strength` in 8-bit code units at every depth (0 < h <= 32).  frames as for `denoise_video`:
+    [N, h, w, c] uint8 (GPU or host; every channel a plane of its own), or with pixel_format "i420", "i422", "i444", "y400" and
+    size=(h, w): [N, frame_bytes] uint8, every plane on its own, 16-bit samples at depth 10 / 12, the chroma planes with
+    `chroma_strength` (None: `strength`).  Float frames are refused.  A constant plane comes back as it is and every output lies
+    within the range of its candidates.  The defaults (patch 3, search 7, strength 3.0) are parameters: nothing is validated on
+    footage.  One strength per video, no joint-channel weights, no noise correction of the centre weight."""
+    patch, search = nl.check_patch(patch), nl.check_search(search)
+    nl.divisor(patch, strength)
+    if chroma_strength is not None:
+        nl.divisor(patch, chroma_strength, "chroma_strength")
+    frames, side, size = _stage_args(frames, pixel_format, size, depth, _denoise_frames)
+    return _denoise_spatial_device(frames, side, size, patch, search, strength, chroma_strength)
 
 
 # ---- telecined film (savsr_amd/pulldown.py is the specification) -----------------------------------------------------------------------------

@@ -14,6 +14,7 @@
     python -m savsr_amd.upscale -i letterboxed_sd.y4m -o hd.y4m --scale 4 --checkpoint <net.pth> --crop auto --colour auto --out-colour auto
     python -m savsr_amd.upscale -i dvd_rip.y4m -o out.y4m --scale 4 --checkpoint <net.pth> --scan detect --scan-out scan.json
     ffmpeg -i vhs_capture.avi -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out.y4m --scale 4 --checkpoint <net.pth> --fields auto --denoise ata --denoise-strength 4,9
+    ffmpeg -i grainy_sd.avi -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out.y4m --scale 4 --checkpoint <net.pth> --spatial-denoise nlm --spatial-strength 3
     ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out444p10.y4m --scale 4 --checkpoint <net.pth> --out-chroma 444
 
 PNG folder: frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on
@@ -125,6 +126,15 @@ the denoised frames; N frames are held back and flushed at the end, and one line
 for PNG folders and for .y4m files and pipes.  Temporal only: moving texture is not denoised, the taps read across scene cuts (only the
 thresholds stop them), one strength per video; the defaults are parameters and nothing is validated on footage.
 
+--spatial-denoise nlm: grain, tuner and sensor noise on what moves, which --denoise (temporal only) leaves untouched.  Non-local means
+on the GPU, every frame on its own: a sample becomes the weighted mean of the samples within --spatial-search N (default 7: a 15 x 15
+window; 1 .. 7) of it, each weighted by how alike the (2 P + 1)^2 patches around the two are (--spatial-patch P, default 3; 1 .. 3);
+--spatial-strength H (default 3.0, 0 < H <= 32, 8-bit code units at every depth) is the root mean squared patch difference at which the
+weight is 1 / e (savsr_amd/nlmeans.py); --spatial-chroma-strength H sets the chroma planes of a Y4M input apart.  The stage runs behind
+--denoise and behind --crop (the bars never enter a patch), in front of --cuts; no frame is held back, and one line on stderr names the
+stage and its parameters.  Works for PNG folders and for .y4m files and pipes.  One strength per video, no joint-channel weights, the
+search stops at 15 x 15; the defaults are parameters, nothing is validated on footage and nothing is pinned to ffmpeg's nlmeans.
+
 It ends with one line: frames, seconds, frames/s (on stderr when the video goes to stdout); with --cuts, the scene count as well; with
 --colour / --out-colour, the two colour spaces.
 """
@@ -141,6 +151,7 @@ from typing import List, Optional
 
 from .denoise import DEFAULT_RADIUS, DEFAULT_STRENGTH, DENOISERS, MAX_RADIUS, check_radius, check_strength
 from .dither import DITHERS
+from . import nlmeans as nlm
 from .deinterlace import DEINTERLACERS, FIELD_FLAGS, FIELD_ORDERS, FIELD_RATES, resolve_fields
 from .pulldown import (DEFAULT_COMB_PIXELS, DEFAULT_COMB_THRESHOLD, DEFAULT_CYCLE, PULLDOWN_FLAGS, check_comb_pixels, check_comb_threshold, check_cycle,
                        resolve_pulldown)
@@ -294,6 +305,18 @@ def build_parser() -> argparse.ArgumentParser:
                         f"code units at every depth (default {DEFAULT_STRENGTH[0]},{DEFAULT_STRENGTH[1]}; 0 <= A <= B <= 255; not validated on footage)")
     p.add_argument("--denoise-chroma-strength", default=None, metavar="A,B",
                    help="--denoise: the same for the chroma planes of a Y4M input (default: --denoise-strength)")
+    p.add_argument("--spatial-denoise", default=None, choices=["none"] + list(nlm.SPATIAL_DENOISERS),
+                   help="spatial noise reduction on the GPU in front of the network, behind --denoise and --crop.  nlm: non-local means, every "
+                        "frame on its own; none (default): the frames go through as they are")
+    p.add_argument("--spatial-patch", type=int, default=None, metavar="N",
+                   help=f"--spatial-denoise: the patch radius (default {nlm.DEFAULT_PATCH}: 7 x 7 patches; 1 .. {nlm.MAX_PATCH})")
+    p.add_argument("--spatial-search", type=int, default=None, metavar="N",
+                   help=f"--spatial-denoise: the search radius (default {nlm.DEFAULT_SEARCH}: a 15 x 15 window; 1 .. {nlm.MAX_SEARCH})")
+    p.add_argument("--spatial-strength", type=float, default=None, metavar="H",
+                   help=f"--spatial-denoise: the root mean squared patch difference at which the weight is 1 / e, in 8-bit code units at every "
+                        f"depth (default {nlm.DEFAULT_STRENGTH}; 0 < H <= {nlm.MAX_STRENGTH}; not validated on footage)")
+    p.add_argument("--spatial-chroma-strength", type=float, default=None, metavar="H",
+                   help="--spatial-denoise: the same for the chroma planes of a Y4M input (default: --spatial-strength)")
     p.add_argument("--scan", default=None, choices=list(SCAN_FLAGS),
                    help="detect: find out from the content, in a first pass over the input (a file or a folder), whether it is progressive, "
                         "interlaced or telecined film and with which field order, then run as --fields X / --pulldown X would; the verdict "
@@ -442,6 +465,23 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             a.denoise_chroma_strength = parse_strength(a.denoise_chroma_strength, "--denoise-chroma-strength")
     except ValueError as e:
         p.error(str(e))
+    a.spatial_denoise = None if a.spatial_denoise == "none" else a.spatial_denoise
+    if a.spatial_denoise is None:
+        if any(v is not None for v in (a.spatial_patch, a.spatial_search, a.spatial_strength, a.spatial_chroma_strength)):
+            p.error("--spatial-patch, --spatial-search, --spatial-strength and --spatial-chroma-strength go with --spatial-denoise nlm")
+    else:
+        if a.spatial_chroma_strength is not None and not a.y4m_in:
+            p.error("--spatial-chroma-strength goes with a Y4M input (PNG frames are RGB: every channel takes --spatial-strength)")
+        try:
+            a.spatial_patch = nlm.check_patch(nlm.DEFAULT_PATCH if a.spatial_patch is None else a.spatial_patch, "--spatial-patch")
+            a.spatial_search = nlm.check_search(nlm.DEFAULT_SEARCH if a.spatial_search is None else a.spatial_search, "--spatial-search")
+            a.spatial_strength = nlm.check_strength(nlm.DEFAULT_STRENGTH if a.spatial_strength is None else a.spatial_strength, "--spatial-strength")
+            nlm.divisor(a.spatial_patch, a.spatial_strength, "--spatial-strength")
+            if a.spatial_chroma_strength is not None:
+                a.spatial_chroma_strength = nlm.check_strength(a.spatial_chroma_strength, "--spatial-chroma-strength")
+                nlm.divisor(a.spatial_patch, a.spatial_chroma_strength, "--spatial-chroma-strength")
+        except ValueError as e:
+            p.error(str(e))
     try:
         check_cycle(a.pulldown_cycle, "--pulldown-cycle")
         if not a.y4m_in:
@@ -616,6 +656,14 @@ def denoise_kwargs(a: argparse.Namespace) -> dict:
         return {}
     return dict(denoise=a.denoise, denoise_radius=a.denoise_radius, denoise_strength=a.denoise_strength,
                 denoise_chroma_strength=a.denoise_chroma_strength)
+
+
+def spatial_kwargs(a: argparse.Namespace) -> dict:
+    """--spatial-denoise and its options as the keyword arguments of VideoUpscaler; nothing without --spatial-denoise."""
+    if a.spatial_denoise is None:
+        return {}
+    return dict(spatial_denoise=a.spatial_denoise, spatial_patch=a.spatial_patch, spatial_search=a.spatial_search,
+                spatial_strength=a.spatial_strength, spatial_chroma_strength=a.spatial_chroma_strength)
 
 
 def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev, order: Optional[str] = None, film: Optional[str] = None):
@@ -873,7 +921,12 @@ def main(argv: Optional[List[str]] = None) -> int:
                            # (--combed with --scan detect says how a telecine verdict is carried out: ignored for the other verdicts)
                            **(dict(combed=a.combed, comb_threshold=a.comb_threshold, comb_pixels=a.comb_pixels)
                               if film is not None and a.combed is not None else {}),
-                           **denoise_kwargs(a))
+                           **denoise_kwargs(a), **spatial_kwargs(a))
+        if a.spatial_denoise is not None:
+            ch = a.spatial_strength if a.spatial_chroma_strength is None else a.spatial_chroma_strength
+            print(f"--spatial-denoise {a.spatial_denoise}: patch {a.spatial_patch} ({2 * a.spatial_patch + 1} x {2 * a.spatial_patch + 1}), search "
+                  f"{a.spatial_search} ({2 * a.spatial_search + 1} x {2 * a.spatial_search + 1}), strength {a.spatial_strength:g}"
+                  + (f", chroma strength {ch:g}" if a.y4m_in else "") + " (8-bit code units; not validated on footage)", file=sys.stderr, flush=True)
         if a.denoise is not None:
             cs = a.denoise_chroma_strength or a.denoise_strength
             print(f"--denoise {a.denoise}: radius {a.denoise_radius} ({2 * a.denoise_radius + 1} frames), strength {a.denoise_strength[0]},"

@@ -33,6 +33,13 @@ crop, the cuts and the windows: the call is, bit for bit, the call on `denoise_v
 video.  The rule is per sample, so it commutes with crop= exactly; cuts="auto" scores the denoised frames.  None runs the lines that ran
 before.
 
+spatial_denoise="nlm": spatial noise reduction (savsr_amd/nlmeans.py: non-local means in integers, every frame on its own) behind
+denoise= and behind the crop, in front of the cuts and the windows.  The rule does not commute with a crop, so the place is part of the
+contract: with crop=None the call is, bit for bit, the call on `denoise_spatial(v', ...)`, v' the video after fields= / pulldown= /
+denoise=; with crop=rect and bars="drop" it is the call on `denoise_spatial(crop_frames(v', rect), ...)`, and with bars="keep" the
+picture inside the bars is those bytes.  cuts="auto" scores the filtered frames; crop="auto" still reads the unfiltered ones.  None runs
+the lines that ran before.
+
 dither="ordered": every quantiser behind the network (packed uint8, planar YUV, the luma-only path's Y plane) takes floor(t + theta(y, x))
 in rint's place, theta from a 16 x 16 Bayer matrix at the sample's position in its plane (savsr_amd/dither.py is the specification, the
 `_d` entries of the C ABI the kernels).  It belongs to the quantiser: bars="keep" inserts exact nominal black after it and out_surface
@@ -58,10 +65,11 @@ from .frames import (OUT_KINDS, PADDING_MODES, PIXEL_FORMATS, SAMPLE_FORMATS, YU
 from .harness import window_indices
 from .packing import get_hw
 from .denoise import check_denoise_options
+from .nlmeans import check_spatial_options
 from .prepass import (FieldSplitter, PulldownRemover, ScanStats, TemporalDenoiser, _check_crop_args, _check_field_options, _check_fields,  # noqa: F401  (re-exported)
-                      _check_pulldown, _check_scan, _crop_device, _cropped_spec, _deinterlace_device, _denoise_device, _denoise_frames,
+                      _check_pulldown, _check_scan, _crop_device, _cropped_spec, _deinterlace_device, _denoise_device, _denoise_frames, _denoise_spatial_device,
                       _detect_device, _detect_scan_device, _field_frames, _insert_device, _pair_sad_device, _pack_surface_device,
-                      _remove_pulldown_device, _to_device, _unpack_surface_device, comb_windows, deinterlace, denoise_video,
+                      _remove_pulldown_device, _to_device, _unpack_surface_device, comb_windows, deinterlace, denoise_spatial, denoise_video,
                       detect_active_area, detect_cuts, detect_scan, field_scores, field_stats, line_sums, make_denoiser, make_stage,
                       pack_surface, pair_sad, remove_pulldown, surface_layout, surface_side, surface_table, unpack_surface)
 from .pulldown import check_comb_options
@@ -106,7 +114,9 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
                   bars: str = "keep", fields: Optional[str] = None, pulldown: Optional[str] = None, pulldown_cycle: int = 5, *,
                   surface=None, out_surface=None, scan: Optional[str] = None, dither: Optional[str] = None, deinterlacer: str = "yadif",
                   field_rate: str = "double", combed: Optional[str] = None, comb_threshold: int = 9, comb_pixels: int = 40,
-                  denoise: Optional[str] = None, denoise_radius: int = 4, denoise_strength=(4, 9), denoise_chroma_strength=None) -> torch.Tensor:
+                  denoise: Optional[str] = None, denoise_radius: int = 4, denoise_strength=(4, 9), denoise_chroma_strength=None,
+                  spatial_denoise: Optional[str] = None, spatial_patch: int = 3, spatial_search: int = 7, spatial_strength=3.0,
+                  spatial_chroma_strength=None) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
@@ -114,6 +124,7 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
                       dither)
     sc = as_scale(net.scale if scale is None else scale)
     noise = check_denoise_options(denoise, denoise_radius, denoise_strength, denoise_chroma_strength)          # None: the path as it was
+    grain = check_spatial_options(spatial_denoise, spatial_patch, spatial_search, spatial_strength, spatial_chroma_strength)          # likewise
     if surface is not None:            # the frames lie in a surface: checked against it, unpacked below, and planar from there on
         in_tab = surface_table(surface, spec.inp, spec.size)
         n, (h, w) = surface_layout(frames, in_tab), spec.size
@@ -124,7 +135,7 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         shaped = frames
     if out_surface is not None:        # (its table: once the crop is checked, or found)
         surface_side(out_surface, spec.out, "out_surface")
-    if noise is not None:              # (integer samples only: float frames are refused here, before the GPU is touched)
+    if noise is not None or grain is not None:          # (integer samples only: float frames are refused here, before the GPU is touched)
         _denoise_frames(shaped, spec.inp, spec.size)
     # (deinterlacer= / field_rate= also go with scan="detect": they say how an interlaced verdict is carried out)
     _check_field_options(deinterlacer, field_rate, fields, pulldown, scan is not None)
@@ -180,6 +191,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     if crop is not None:               # the crop comes first: everything below sees the cropped video
         frames = _crop_device(frames, crop, spec.inp, (h, w))
         spec = _cropped_spec(spec, crop)
+    if grain is not None:              # the spatial denoiser sees the cropped picture (the bars never enter a patch); the cuts and the windows see its output
+        frames = _denoise_spatial_device(frames, spec.inp, spec.size, *grain)
     if cuts is None:
         windows = [window_indices(i, n, T, padding) for i in range(n)]
     else:
@@ -249,6 +262,11 @@ class VideoUpscaler:
     2 * denoise_radius more frames between pushes (denoise_radius behind as context, denoise_radius not done yet).  The cuts, the crop
     and the windows operate on the denoised frames; any chunking gives the same frames.
 
+    spatial_denoise="nlm", spatial_patch=3, spatial_search=7, spatial_strength=3.0, spatial_chroma_strength=None (keyword only): spatial
+    noise reduction, as in upscale_video.  The stage is stateless -- every frame is filtered on its own -- so it runs on the frames as
+    they are cropped and buffered, holds no frame back and keeps none; any chunking gives the same frames.  The default strength is a
+    parameter: nothing is validated on footage.
+
     scan="detect" is refused: the decision needs the video.  Run savsr_amd.detect_scan on a probe chunk (or prepass.ScanStats over a
     first pass, as python -m savsr_amd.upscale --scan detect does) and give its answer as fields= / pulldown=."""
 
@@ -259,7 +277,8 @@ class VideoUpscaler:
                  pulldown_cycle: int = 5, *, surface=None, out_surface=None, scan: Optional[str] = None, dither: Optional[str] = None,
                  deinterlacer: str = "yadif", field_rate: str = "double", combed: Optional[str] = None, comb_threshold: int = 9,
                  comb_pixels: int = 40, denoise: Optional[str] = None, denoise_radius: int = 4, denoise_strength=(4, 9),
-                 denoise_chroma_strength=None):
+                 denoise_chroma_strength=None, spatial_denoise: Optional[str] = None, spatial_patch: int = 3, spatial_search: int = 7,
+                 spatial_strength=3.0, spatial_chroma_strength=None):
         _check_net(net)
         check_padding(padding)
         _check_scan(scan, fields, pulldown, pulldown_cycle, auto_ok=False)          # (None is the only value that passes: the path as it was)
@@ -280,6 +299,8 @@ class VideoUpscaler:
                                  comb_pixels)          # the stage in front; None: as it was
         # the temporal denoiser, behind that stage (it needs progressive frames) and in front of the crop; None: as it was
         self._noise = make_denoiser(denoise, denoise_radius, denoise_strength, denoise_chroma_strength, self.spec.inp, self.spec.size)
+        # the spatial denoiser, behind the crop: stateless, every frame on its own; None: as it was
+        self._grain = check_spatial_options(spatial_denoise, spatial_patch, spatial_search, spatial_strength, spatial_chroma_strength)
         self._rect = _check_crop_args(crop, 24, bars, auto_ok=False)          # the rect to crop every chunk to; None: no crop, as it was
         self.bars = bars
         if self._rect is not None and self.spec.size:
@@ -374,7 +395,7 @@ class VideoUpscaler:
         staged = self._split is not None
         if staged:
             _field_frames(frames, self._full.inp, self._full.size)
-        if self._noise is not None:
+        if self._noise is not None or self._grain is not None:
             _denoise_frames(frames, self._full.inp, self._full.size)
         _, h, w = self._full.frames_hw(frames)
         shape = (frames.dtype == torch.uint8, h, w)
@@ -416,6 +437,8 @@ class VideoUpscaler:
         new = new.contiguous() if self._shape[0] else new.to(torch.float32).contiguous()
         if self._rect is not None:
             new = _crop_device(new, self._rect, self._full.inp, self._shape[1:])
+        if self._grain is not None:                # the frames as the network will see them, filtered one by one: no frame is held for it
+            new = _denoise_spatial_device(new, self.spec.inp, self.spec.size, *self._grain)
         self._buf = new if self._buf is None else torch.cat([self._buf, new], 0)
         if self._plan is not None:
             return self._push_scenes(k)
