@@ -158,6 +158,9 @@ __global__ __launch_bounds__(512) void osconv_l2_kernel(const OscBatch bt) {
 // L2-resident reads per workgroup at cin = 192) instead of waiting for two more launches: the chain was three latency-bound launches of a few dozen
 // workgroups each (12.6 + 5.1 + 15 us per OSConv set, 21 sets per frame); no inter-workgroup hand-off, so nothing to synchronise.
 // scr: [4 + cin | OSC_PARTS x cin | 2 cin] floats of LDS scratch (v0 with its two scale entries at +2, the partial-sum slices, v1).
+// Where that scratch starts in the aggregation kernels' dynamic LDS: behind [v2 | a | gates] = 2 cin + hidden + cout + 9 + knum floats, rounded up to
+// a multiple of 4 floats -- the partial-sum slices are stored as f32x4 (for every OSConv of the network the unrounded offset is 1 modulo 4).
+__host__ __device__ inline int osc_scratch_base(const savsr_osconv_attn_desc& d) { return (2 * d.cin + d.hidden + d.cout + 9 + d.knum + 3) & ~3; }
 __device__ __forceinline__ void osconv_route_in_workgroup(const savsr_osconv_attn_desc& d, float* scr, float* v2) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float* v0 = scr + 2;
@@ -244,7 +247,7 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 template <bool F16>
 __global__ __launch_bounds__(512) void osconv_aggregate_kernel(const OscBatch bt) {
     const savsr_osconv_attn_desc& d = bt.d[blockIdx.y];
-    extern __shared__ float sm[];
+    extern __shared__ __attribute__((aligned(16))) float sm[];
     float* v2 = sm;                        // [cin]
     float* a = v2 + d.cin;                 // [hidden]
     float* gates = a + d.hidden;           // [cin + cout + 9 + knum]
@@ -294,7 +297,7 @@ __global__ __launch_bounds__(512) void osconv_aggregate_kernel(const OscBatch bt
         for (int k = 0; k < GH; ++k) gw[k] = (wr && k < d.hidden) ? wr[k] : 0.f;
     }
     if (d.fused) {
-        osconv_route_in_workgroup(d, gates + (d.cin + d.cout + 9 + d.knum), v2);     // (LDS scratch behind the gates; ends with a barrier)
+        osconv_route_in_workgroup(d, sm + osc_scratch_base(d), v2);     // (LDS scratch behind the gates, 16-B aligned; ends with a barrier)
         if (blockIdx.x == 0 && d.v2) for (int i = tid; i < d.cin; i += 512) d.v2[i] = v2[i];      // (kept observable for tests / tools)
     } else {
         for (int i = tid; i < d.cin; i += 512) v2[i] = d.v2[i];
@@ -420,7 +423,7 @@ __global__ __launch_bounds__(512) void osconv_aggregate_kernel(const OscBatch bt
 template <bool F16>
 __global__ __launch_bounds__(512) void osconv_aggregate_wy_kernel(const OscBatch bt) {
     const savsr_osconv_attn_desc& d = bt.d[blockIdx.y];
-    extern __shared__ float sm[];
+    extern __shared__ __attribute__((aligned(16))) float sm[];
     float* v2 = sm;                        // [cin]
     float* a = v2 + d.cin;                 // [hidden]
     float* gates = a + d.hidden;           // [cin + cout + 9 + knum]
@@ -478,7 +481,7 @@ __global__ __launch_bounds__(512) void osconv_aggregate_wy_kernel(const OscBatch
         for (int k = 0; k < GH; ++k) gw[k] = (wr && k < d.hidden) ? wr[k] : 0.f;
     }
     if (d.fused) {
-        osconv_route_in_workgroup(d, gates + (d.cin + d.cout + 9 + d.knum), v2);     // (LDS scratch behind the gates; ends with a barrier)
+        osconv_route_in_workgroup(d, sm + osc_scratch_base(d), v2);     // (LDS scratch behind the gates, 16-B aligned; ends with a barrier)
         if (blockIdx.x == 0 && d.v2) for (int i = tid; i < d.cin; i += 512) d.v2[i] = v2[i];      // (kept observable for tests / tools)
     } else {
         for (int i = tid; i < d.cin; i += 512) v2[i] = d.v2[i];
@@ -989,6 +992,8 @@ static int osconv_weights_batch(const savsr_osconv_attn_desc* descs, int n, void
     const savsr_osconv_attn_desc* d = descs;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int rc = 0;
+    // (refused before anything is enqueued: the unfused chain used to run its two routing launches first and leave v1 / v2 written)
+    if (d->wy && (d->cout % 64 || d->cin % 16)) return fail_arg("osconv_weights: the Winograd-y image needs cout % 64 == 0 and cin % 16 == 0");
     if (!d->fused) {
         hipLaunchKernelGGL(osconv_l1_kernel, dim3((2 * d->cin + OSC_L1_ROWS - 1) / OSC_L1_ROWS, n), dim3(512), sizeof(float) * ((OSC_PARTS + 1) * d->cin + 4), st, bt);
         rc = check_launch("osconv_l1_kernel");
@@ -998,9 +1003,8 @@ static int osconv_weights_batch(const savsr_osconv_attn_desc* descs, int n, void
         if (rc) return rc;
     }
     // (fused: + the routing scratch [4 + cin | OSC_PARTS x cin | 2 cin] behind the gates: 46 KB at cin = 320)
-    const size_t lds = sizeof(float) * ((size_t)d->cin + d->hidden + d->cin + d->cout + 9 + d->knum + (d->fused ? 4 + (size_t)(OSC_PARTS + 3) * d->cin : 0));
+    const size_t lds = sizeof(float) * (d->fused ? (size_t)osc_scratch_base(*d) + 4 + (size_t)(OSC_PARTS + 3) * d->cin : (size_t)2 * d->cin + d->hidden + d->cout + 9 + d->knum);
     if (d->wy) {
-        if (d->cout % 64 || d->cin % 16) return fail_arg("osconv_weights: the Winograd-y image needs cout % 64 == 0 and cin % 16 == 0");
         const long long nitems = (long long)(d->cout / 64) * (d->cin / 16) * 3 * 2 * 64 * 2;
         if (f16) hipLaunchKernelGGL(osconv_aggregate_wy_kernel<true>, dim3((unsigned)((nitems + 511) / 512), n), dim3(512), lds, st, bt);
         else hipLaunchKernelGGL(osconv_aggregate_wy_kernel<false>, dim3((unsigned)((nitems + 511) / 512), n), dim3(512), lds, st, bt);
