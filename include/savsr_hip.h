@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 51
+#define SAVSR_ABI_VERSION 52
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -781,6 +781,31 @@ int savsr_video_nlmeans_u8(const uint8_t* frames, int n_frames, int64_t frame_by
                            int search, int divisor, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
 int savsr_video_nlmeans_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step, int depth,
                             int patch, int search, int divisor, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 52) Deblocking (deblock.hip; savsr_amd.deblock_video, upscale_video(deblock="weak" | "strong", ...), VideoUpscaler(deblock=...),
+ * --deblock of python -m savsr_amd.upscale): a weak / strong filter across the edges of a block grid anchored at
+ * the plane's origin, pass X (vertical edges, every row) then pass Y (horizontal edges, every column, reading pass X's result), in
+ * integers, every frame on its own (savsr_amd/deblock.py `deblock_matrix` / `deblock_fields` restate it; the kernels equal them bit for
+ * bit).  Planes are addressed as for savsr_video_nlmeans_*: rows rows of cols * step samples, sample x meeting x +- j * step only; the
+ * output frames are laid out the same way and only the plane is written (out of place).  block: 4, 8 or 16 samples.  strong: 0 weak
+ * (2 samples a side), 1 strong (3 a side; a direction whose block is below 8 takes the weak filter).  interlaced: 1 filters the rows
+ * 0::2 and 1::2 as planes of their own with a vertical block of block / 2 (no pass Y at block 4).  thr_a, thr_b: the thresholds A (on
+ * the step across the edge) and Bt (on the steps beside it) in the depth's codes, 0 .. 255 << (depth - 8); A = 0 copies min(s, top).
+ * One launch for all frames (at most 65535 a launch) with both passes in it: a workgroup stages a tile of 32 rows x 256 / step samples
+ * (64 at step 3) plus a halo of 3 samples and 3 field rows in LDS and pass X's result never reaches global memory.
+ * Refused (SAVSR_E_ARG, before anything is launched, the message naming the entry): a null pointer, n_frames < 1, rows < 1, cols < 1,
+ * a step outside 1 .. 4, a plane above 2147418112 bytes, a negative plane offset, a frame stride smaller than the offset plus the plane
+ * (either side), a block other than 4 / 8 / 16, strong or interlaced other than 0 / 1, a threshold out of range, overlapping source and
+ * output; _u16: a depth other than 10 / 12, an odd pointer, stride or offset.
+ * savsr_video_deblock_u8:  planes of rows x (cols * step) bytes.
+ * savsr_video_deblock_u16: the same in little-endian 16-bit samples, every one read as min(s, 2^depth - 1). */
+int savsr_video_deblock_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step, int block,
+                           int strong, int interlaced, int thr_a, int thr_b, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
+                           void* stream);
+int savsr_video_deblock_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step, int depth,
+                            int block, int strong, int interlaced, int thr_a, int thr_b, uint8_t* out, int64_t out_frame_bytes,
+                            int64_t out_plane_offset, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 45) Video surfaces (surface.hip; savsr_amd.unpack_surface, savsr_amd.pack_surface, upscale_video(surface=..., out_surface=...),

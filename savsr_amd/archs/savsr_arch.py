@@ -286,7 +286,8 @@ class SAVSR(nn.Module):
                       field_rate: str = "double", combed: Optional[str] = None, comb_threshold: int = 9, comb_pixels: int = 40,
                       denoise: Optional[str] = None, denoise_radius: int = 4, denoise_strength=(4, 9),
                       denoise_chroma_strength=None, spatial_denoise: Optional[str] = None, spatial_patch: int = 3, spatial_search: int = 7,
-                      spatial_strength=3.0, spatial_chroma_strength=None) -> torch.Tensor:
+                      spatial_strength=3.0, spatial_chroma_strength=None, deblock: Optional[str] = None, deblock_block: int = 8,
+                      deblock_strength=(25, 13), deblock_chroma_strength=None) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -425,6 +426,24 @@ class SAVSR(nn.Module):
         unfiltered ones.  uint8 and planar frames only; the spatial_ options are refused without spatial_denoise=.  One strength per
         video, no joint-channel weights, the centre weight is not corrected for noise, the search stops at 15 x 15.  The defaults are
         parameters: nothing is validated on footage or on trained weights, and nothing is pinned to ffmpeg's output.
+        deblock, deblock_block, deblock_strength, deblock_chroma_strength (keyword only): deblocking in front of the network, for the
+        8 x 8 block edges of MPEG-2 and low-bitrate H.264 sources, which neither denoiser removes and a x4 network enlarges onto a
+        32-pixel grid.  deblock: None (the default: what ran before), "weak" or "strong": across the vertical edges of a grid of
+        deblock_block (4, 8 or 16, default 8) samples anchored at the frame's origin, then across the horizontal ones, the 2 ("weak")
+        or 3 ("strong") samples on either side of an edge move towards each other by 1/2, (1/4,) 1/8 of the step across it where that
+        step is below a and the steps beside it are below b, deblock_strength = (a, b), ints in 0 .. 255 in 8-bit code units at every
+        depth, default (25, 13) (savsr_amd/deblock.py is the rule in integers).  Chroma planes take deblock_chroma_strength (None: the
+        same) and the same block in their own samples; every channel of packed frames is a plane of its own.  The block grid belongs
+        to the coded frame, so the stage runs on the frames as decoded: right after surface= unpacking and after scan="detect" has
+        read the unfiltered frames, in front of fields= / pulldown=, denoise=, the crop, spatial_denoise= and the cuts.  It filters
+        the two fields as planes of their own (vertical block deblock_block // 2: weak below 8, no vertical pass at block 4) exactly
+        when the video is treated as interlaced -- fields= or pulldown= given, or an interlaced or telecine verdict of scan="detect".
+        The result is, bit for bit, upscale_video on savsr_amd.deblock_video(frames, ..., interlaced=I) with every other argument the
+        same, I as just said; crop= then crops the filtered frames, so crop="auto" reads filtered frames.  uint8 and planar frames
+        only; the deblock_ options are refused without deblock=.  The grid's origin is the frame's (a video cropped or scaled before
+        it arrives has its edges elsewhere), one block size and one strength per video, no adaptation to the stream's quantiser,
+        ringing and mosquito noise are not addressed.  The defaults are ffmpeg deblock's thresholds as parameters: nothing is
+        validated on footage or on trained weights, and nothing is pinned to ffmpeg's output.
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
@@ -434,7 +453,8 @@ class SAVSR(nn.Module):
                              comb_threshold=comb_threshold, comb_pixels=comb_pixels, denoise=denoise, denoise_radius=denoise_radius,
                              denoise_strength=denoise_strength, denoise_chroma_strength=denoise_chroma_strength,
                              spatial_denoise=spatial_denoise, spatial_patch=spatial_patch, spatial_search=spatial_search,
-                             spatial_strength=spatial_strength, spatial_chroma_strength=spatial_chroma_strength)
+                             spatial_strength=spatial_strength, spatial_chroma_strength=spatial_chroma_strength, deblock=deblock,
+                             deblock_block=deblock_block, deblock_strength=deblock_strength, deblock_chroma_strength=deblock_chroma_strength)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

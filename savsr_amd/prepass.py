@@ -4,7 +4,8 @@ all of them, `pack_surface` behind everything; savsr_amd/surface.py is its speci
 `_..._device` form on resident frames of a checked input side (what upscale_video calls on the whole video); the two that change the frame count are streaming stages as well
 (`FieldSplitter`, `PulldownRemover`; `make_stage` builds the one a call asks for; `ScanStats` is the detector's streaming form), and the temporal
 denoiser behind them is a third (`denoise_video`, `TemporalDenoiser`, `make_denoiser`; savsr_amd/denoise.py is its specification); the spatial
-denoiser behind the crop is stateless (`denoise_spatial`; savsr_amd/nlmeans.py is its specification).  The
+denoiser behind the crop is stateless (`denoise_spatial`; savsr_amd/nlmeans.py is its specification), and so is the deblocking stage on the
+frames as decoded, in front of all of these but the surface conversion and the scan detector (`deblock_video`; savsr_amd/deblock.py).  The
 numpy modules (scenes.py, active.py, deinterlace.py, pulldown.py, scan.py) are the specifications, bit for bit.  Where the byte matrices of a frame lie is `frames.plane_table`'s
 answer alone; fp32 CHW frames have entries of their own (`_f32`) and are one explicit branch in the two stages that accept them.
 """
@@ -16,6 +17,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import active
+from . import deblock as db
 from . import denoise as dn
 from . import nlmeans as nl
 from . import pulldown as pd
@@ -600,6 +602,46 @@ def denoise_spatial(frames: torch.Tensor, pixel_format: str = "rgb", size=None, 
         nl.divisor(patch, chroma_strength, "chroma_strength")
     frames, side, size = _stage_args(frames, pixel_format, size, depth, _denoise_frames)
     return _denoise_spatial_device(frames, side, size, patch, search, strength, chroma_strength)
+
+
+# ---- deblocking (savsr_amd/deblock.py is the specification) ----------------------------------------------------------------------------------
+def _deblock_device(frames: torch.Tensor, side: Side, size: Size, block: int = db.DEFAULT_BLOCK, mode: str = "weak",
+                    strength=db.DEFAULT_STRENGTH, chroma_strength=None, interlaced: bool = False) -> torch.Tensor:
+    """savsr_video_deblock_* on resident frames of the input side on the GPU: as many filtered frames, every frame on its own.  One call
+    (one launch, both passes in it) per plane, on the current stream (no sync): the Y plane with `strength`, the chroma planes with
+    `chroma_strength` (None: `strength`), the thresholds shifted to the depth here; packed frames in one call, every channel a plane of
+    its own (the channel count is the entry's sample step).  interlaced: every plane field by field."""
+    n, c, h, w = _sample_frames(frames, side, size, "deblock")
+    frames, tab = frames.contiguous(), plane_table(side, size, c, h, w)
+    out = torch.empty_like(frames)
+    step, shift = max(c, 1), side.depth - 8
+    for i, p in enumerate(tab.planes if n else ()):
+        a, b = strength if i == 0 or chroma_strength is None else chroma_strength
+        head = (p.row_bytes // (tab.sample * step), step) + (() if tab.sample == 1 else (side.depth,))
+        _entry_call("savsr_video_deblock_u8" if tab.sample == 1 else "savsr_video_deblock_u16", frames, n, tab, p, head,
+                    (block, int(mode == "strong"), int(bool(interlaced)), a << shift, b << shift, out.data_ptr(), tab.stride, p.offset))
+    return out
+
+
+def deblock_video(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8, block: int = db.DEFAULT_BLOCK, mode: str = "weak",
+                  strength=db.DEFAULT_STRENGTH, chroma_strength=None, interlaced: bool = False) -> torch.Tensor:
+    """Deblocking: N frames on the GPU in the format of the N given ones (savsr_amd.deblock.deblock_frames is the specification, bit for
+    bit), on the caller's current stream, without a sync.  Every frame is filtered on its own: across the vertical edges of a grid of
+    `block` (4, 8 or 16) samples anchored at the frame's origin, then across the horizontal ones, the samples next to an edge move
+    towards each other by 1/2, (1/4,) 1/8 of the step across it -- 2 samples a side with mode "weak", 3 with "strong" -- where the step
+    is below a and the steps beside it are below b, strength = (a, b) in 8-bit code units at every depth (ints in 0 .. 255).
+    interlaced=True filters the two fields as planes of their own (vertical block `block` // 2, weak below 8, no vertical pass at block
+    4), so that no filter mixes two moments.  frames as for `denoise_video`: [N, h, w, c] uint8 (GPU or host; every channel a plane of
+    its own), or with pixel_format "i420", "i422", "i444", "y400" and size=(h, w): [N, frame_bytes] uint8, every plane on its own with
+    the same block in its own samples, 16-bit samples at depth 10 / 12, the chroma planes with `chroma_strength` (None: `strength`).
+    Float frames are refused.  A constant plane comes back as it is, a = 0 is the identity and a pass moves no sample by more than
+    (a - 1) // 2 codes (shifted to the depth).  The defaults (block 8, (25, 13)) are parameters: nothing is validated on footage.  The
+    grid starts at the frame's origin: a video cropped or scaled before it arrives has its edges elsewhere."""
+    block, mode = db.check_block(block), db.check_mode(mode)
+    strength = db.check_strength(strength)
+    chroma_strength = None if chroma_strength is None else db.check_strength(chroma_strength, "chroma_strength")
+    frames, side, size = _stage_args(frames, pixel_format, size, depth, lambda f, s, z: _sample_frames(f, s, z, "deblock"))
+    return _deblock_device(frames, side, size, block, mode, strength, chroma_strength, interlaced)
 
 
 # ---- telecined film (savsr_amd/pulldown.py is the specification) -----------------------------------------------------------------------------

@@ -15,6 +15,7 @@
     python -m savsr_amd.upscale -i dvd_rip.y4m -o out.y4m --scale 4 --checkpoint <net.pth> --scan detect --scan-out scan.json
     ffmpeg -i vhs_capture.avi -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out.y4m --scale 4 --checkpoint <net.pth> --fields auto --denoise ata --denoise-strength 4,9
     ffmpeg -i grainy_sd.avi -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out.y4m --scale 4 --checkpoint <net.pth> --spatial-denoise nlm --spatial-strength 3
+    python -m savsr_amd.upscale -i blocky_dvd.y4m -o out.y4m --scale 4 --checkpoint <net.pth> --scan detect --deblock strong --deblock-strength 25,13
     ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out444p10.y4m --scale 4 --checkpoint <net.pth> --out-chroma 444
 
 PNG folder: frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on
@@ -135,6 +136,18 @@ weight is 1 / e (savsr_amd/nlmeans.py); --spatial-chroma-strength H sets the chr
 stage and its parameters.  Works for PNG folders and for .y4m files and pipes.  One strength per video, no joint-channel weights, the
 search stops at 15 x 15; the defaults are parameters, nothing is validated on footage and nothing is pinned to ffmpeg's nlmeans.
 
+--deblock weak|strong: the 8 x 8 block edges of MPEG-2 and low-bitrate H.264 sources, which neither denoiser removes.  On the GPU, every
+frame on its own: across the vertical edges of a grid of --deblock-block N (default 8; 4, 8 or 16) samples anchored at the frame's
+origin, then across the horizontal ones, the 2 (weak) or 3 (strong) samples on either side of an edge move towards each other where the
+step across it is below A and the steps beside it are below B (--deblock-strength A,B in 8-bit code units at every depth, default
+25,13, ints in 0 .. 255; savsr_amd/deblock.py); --deblock-chroma-strength A,B sets the chroma planes of a Y4M input apart.  The grid
+belongs to the coded frame, so the stage runs on the frames as read, in front of --fields / --pulldown, --denoise, --crop (auto reads
+the filtered frames), --spatial-denoise and --cuts, and field by field where the video is treated as interlaced: with --fields or
+--pulldown, or an interlaced or telecine verdict of --scan detect, whose first pass reads the unfiltered frames.  No frame is held back,
+and one line on stderr names the stage, its parameters and whether it ran field-wise.  Works for PNG folders and for .y4m files and
+pipes.  The grid's origin is the frame's, one block size and one strength per video, no adaptation to the stream's quantiser; the
+defaults are parameters, nothing is validated on footage and nothing is pinned to ffmpeg's deblock.
+
 It ends with one line: frames, seconds, frames/s (on stderr when the video goes to stdout); with --cuts, the scene count as well; with
 --colour / --out-colour, the two colour spaces.
 """
@@ -149,6 +162,7 @@ import time
 from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional
 
+from . import deblock as dbk
 from .denoise import DEFAULT_RADIUS, DEFAULT_STRENGTH, DENOISERS, MAX_RADIUS, check_radius, check_strength
 from .dither import DITHERS
 from . import nlmeans as nlm
@@ -317,6 +331,16 @@ def build_parser() -> argparse.ArgumentParser:
                         f"depth (default {nlm.DEFAULT_STRENGTH}; 0 < H <= {nlm.MAX_STRENGTH}; not validated on footage)")
     p.add_argument("--spatial-chroma-strength", type=float, default=None, metavar="H",
                    help="--spatial-denoise: the same for the chroma planes of a Y4M input (default: --spatial-strength)")
+    p.add_argument("--deblock", default=None, choices=["none"] + list(dbk.DEBLOCKERS),
+                   help="deblocking on the GPU in front of the network, on the frames as read.  weak: 2 samples on either side of a block edge; "
+                        "strong: 3; none (default): the frames go through as they are")
+    p.add_argument("--deblock-block", type=int, default=None, metavar="N",
+                   help=f"--deblock: the block's size in samples (default {dbk.DEFAULT_BLOCK}; 4, 8 or 16; the grid starts at the frame's origin)")
+    p.add_argument("--deblock-strength", default=None, metavar="A,B",
+                   help=f"--deblock: an edge is filtered where its step is below A and the steps beside it are below B, in 8-bit code units at "
+                        f"every depth (default {dbk.DEFAULT_STRENGTH[0]},{dbk.DEFAULT_STRENGTH[1]}; ints in 0 .. 255; not validated on footage)")
+    p.add_argument("--deblock-chroma-strength", default=None, metavar="A,B",
+                   help="--deblock: the same for the chroma planes of a Y4M input (default: --deblock-strength)")
     p.add_argument("--scan", default=None, choices=list(SCAN_FLAGS),
                    help="detect: find out from the content, in a first pass over the input (a file or a folder), whether it is progressive, "
                         "interlaced or telecined film and with which field order, then run as --fields X / --pulldown X would; the verdict "
@@ -350,6 +374,17 @@ def parse_strength(text: str, what: str):
     if len(pair) != 2:
         raise ValueError(f"{what}: A,B, got {text!r}")
     return check_strength(pair, what)
+
+
+def parse_deblock_strength(text: str, what: str):
+    """--deblock-strength / --deblock-chroma-strength: "A,B" -> the checked (a, b)."""
+    try:
+        pair = tuple(int(t.strip()) for t in text.split(","))
+    except ValueError:
+        raise ValueError(f"{what}: A,B with integers, got {text!r}") from None
+    if len(pair) != 2:
+        raise ValueError(f"{what}: A,B, got {text!r}")
+    return dbk.check_strength(pair, what)
 
 
 def parse_cuts(text: str):
@@ -480,6 +515,21 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             if a.spatial_chroma_strength is not None:
                 a.spatial_chroma_strength = nlm.check_strength(a.spatial_chroma_strength, "--spatial-chroma-strength")
                 nlm.divisor(a.spatial_patch, a.spatial_chroma_strength, "--spatial-chroma-strength")
+        except ValueError as e:
+            p.error(str(e))
+    a.deblock = None if a.deblock == "none" else a.deblock
+    if a.deblock is None:
+        if any(v is not None for v in (a.deblock_block, a.deblock_strength, a.deblock_chroma_strength)):
+            p.error("--deblock-block, --deblock-strength and --deblock-chroma-strength go with --deblock weak or strong")
+    else:
+        if a.deblock_chroma_strength is not None and not a.y4m_in:
+            p.error("--deblock-chroma-strength goes with a Y4M input (PNG frames are RGB: every channel takes --deblock-strength)")
+        try:
+            a.deblock_block = dbk.check_block(dbk.DEFAULT_BLOCK if a.deblock_block is None else a.deblock_block, "--deblock-block")
+            a.deblock_strength = (dbk.DEFAULT_STRENGTH if a.deblock_strength is None
+                                  else parse_deblock_strength(a.deblock_strength, "--deblock-strength"))
+            if a.deblock_chroma_strength is not None:
+                a.deblock_chroma_strength = parse_deblock_strength(a.deblock_chroma_strength, "--deblock-chroma-strength")
         except ValueError as e:
             p.error(str(e))
     try:
@@ -666,17 +716,26 @@ def spatial_kwargs(a: argparse.Namespace) -> dict:
                 spatial_strength=a.spatial_strength, spatial_chroma_strength=a.spatial_chroma_strength)
 
 
+def deblock_kwargs(a: argparse.Namespace) -> dict:
+    """--deblock and its options as the keyword arguments of VideoUpscaler; nothing without --deblock."""
+    if a.deblock is None:
+        return {}
+    return dict(deblock=a.deblock, deblock_block=a.deblock_block, deblock_strength=a.deblock_strength,
+                deblock_chroma_strength=a.deblock_chroma_strength)
+
+
 def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev, order: Optional[str] = None, film: Optional[str] = None):
     """--crop auto's first pass: savsr_amd.line_sums over the input in --chunk-sized pieces with a running maximum on the device, then
     cropdetect's rule and the alignment to the input layout's chroma block.  chunks: the PNG folder's chunk iterator; None: the .y4m file
     named by --input, read through a reader of its own.  order: --fields' field order; the sums are then taken on the deinterlaced frames
     (a prepass.FieldSplitter of this pass's own), as the second pass will crop them.  film: --pulldown's field order; the sums are then taken
-    on the recovered film frames (a prepass.PulldownRemover of this pass's own)."""
+    on the recovered film frames (a prepass.PulldownRemover of this pass's own).  --deblock: the chunks are filtered first, field by field
+    with either, as the second pass will filter them."""
     import torch
 
     from . import active
     from .frames import detector_side, layout_of
-    from .prepass import line_sums, make_denoiser, make_stage
+    from .prepass import deblock_video, line_sums, make_denoiser, make_stage
     from .y4m import Y4MReader
     from .yuv import CHROMAS
     top = None
@@ -706,7 +765,11 @@ def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, de
             for chunk in chunks:
                 c = 1 if size else int(chunk.shape[3])
                 h, w = size if size else (int(chunk.shape[1]), int(chunk.shape[2]))
-                fold(chunk.to(dev) if split is None else split.push(chunk.to(dev)))
+                chunk = chunk.to(dev)
+                if a.deblock is not None:
+                    chunk = deblock_video(chunk, fmt_in, size, depth, a.deblock_block, a.deblock, a.deblock_strength, a.deblock_chroma_strength,
+                                          order is not None or film is not None)
+                fold(chunk if split is None else split.push(chunk))
             last = None if split is None else split.finish()
             if last is not None:
                 fold(last)
@@ -921,7 +984,13 @@ def main(argv: Optional[List[str]] = None) -> int:
                            # (--combed with --scan detect says how a telecine verdict is carried out: ignored for the other verdicts)
                            **(dict(combed=a.combed, comb_threshold=a.comb_threshold, comb_pixels=a.comb_pixels)
                               if film is not None and a.combed is not None else {}),
-                           **denoise_kwargs(a), **spatial_kwargs(a))
+                           **denoise_kwargs(a), **spatial_kwargs(a), **deblock_kwargs(a))
+        if a.deblock is not None:
+            cs = a.deblock_chroma_strength or a.deblock_strength
+            print(f"--deblock {a.deblock}: block {a.deblock_block}, strength {a.deblock_strength[0]},{a.deblock_strength[1]}"
+                  + (f", chroma strength {cs[0]},{cs[1]}" if a.y4m_in else "") + " (8-bit code units; not validated on footage), "
+                  + ("field-wise (the fields as planes of their own)" if order is not None or film is not None else "progressive"),
+                  file=sys.stderr, flush=True)
         if a.spatial_denoise is not None:
             ch = a.spatial_strength if a.spatial_chroma_strength is None else a.spatial_chroma_strength
             print(f"--spatial-denoise {a.spatial_denoise}: patch {a.spatial_patch} ({2 * a.spatial_patch + 1} x {2 * a.spatial_patch + 1}), search "

@@ -40,6 +40,13 @@ denoise=; with crop=rect and bars="drop" it is the call on `denoise_spatial(crop
 picture inside the bars is those bytes.  cuts="auto" scores the filtered frames; crop="auto" still reads the unfiltered ones.  None runs
 the lines that ran before.
 
+deblock="weak" / "strong": deblocking (savsr_amd/deblock.py: a filter across the edges of a fixed block grid, pass X then pass Y, every
+frame on its own).  The grid belongs to the coded frame, so the stage runs on the frames as decoded: right after surface= unpacking and
+after scan="detect" has read the unfiltered frames, in front of fields= / pulldown=, denoise=, the crop, spatial_denoise= and the cuts, and
+field by field exactly when the video is treated as interlaced (fields= or pulldown= given, or an interlaced / telecine verdict).  The
+call is, bit for bit, the call on `deblock_video(v, ..., interlaced=I)`; crop= crops the filtered frames, so crop="auto" reads filtered
+frames.  None runs the lines that ran before.
+
 dither="ordered": every quantiser behind the network (packed uint8, planar YUV, the luma-only path's Y plane) takes floor(t + theta(y, x))
 in rint's place, theta from a 16 x 16 Bayer matrix at the sample's position in its plane (savsr_amd/dither.py is the specification, the
 `_d` entries of the C ABI the kernels).  It belongs to the quantiser: bars="keep" inserts exact nominal black after it and out_surface
@@ -64,12 +71,13 @@ from .frames import (OUT_KINDS, PADDING_MODES, PIXEL_FORMATS, SAMPLE_FORMATS, YU
                      check_sitings, chroma_of, frame_layout, i420_layout, layout_of, luma_mode, video_spec)
 from .harness import window_indices
 from .packing import get_hw
+from .deblock import check_deblock_options
 from .denoise import check_denoise_options
 from .nlmeans import check_spatial_options
 from .prepass import (FieldSplitter, PulldownRemover, ScanStats, TemporalDenoiser, _check_crop_args, _check_field_options, _check_fields,  # noqa: F401  (re-exported)
-                      _check_pulldown, _check_scan, _crop_device, _cropped_spec, _deinterlace_device, _denoise_device, _denoise_frames, _denoise_spatial_device,
+                      _check_pulldown, _check_scan, _crop_device, _cropped_spec, _deblock_device, _deinterlace_device, _denoise_device, _denoise_frames, _denoise_spatial_device,
                       _detect_device, _detect_scan_device, _field_frames, _insert_device, _pair_sad_device, _pack_surface_device,
-                      _remove_pulldown_device, _to_device, _unpack_surface_device, comb_windows, deinterlace, denoise_spatial, denoise_video,
+                      _remove_pulldown_device, _sample_frames, _to_device, _unpack_surface_device, comb_windows, deblock_video, deinterlace, denoise_spatial, denoise_video,
                       detect_active_area, detect_cuts, detect_scan, field_scores, field_stats, line_sums, make_denoiser, make_stage,
                       pack_surface, pair_sad, remove_pulldown, surface_layout, surface_side, surface_table, unpack_surface)
 from .pulldown import check_comb_options
@@ -116,7 +124,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
                   field_rate: str = "double", combed: Optional[str] = None, comb_threshold: int = 9, comb_pixels: int = 40,
                   denoise: Optional[str] = None, denoise_radius: int = 4, denoise_strength=(4, 9), denoise_chroma_strength=None,
                   spatial_denoise: Optional[str] = None, spatial_patch: int = 3, spatial_search: int = 7, spatial_strength=3.0,
-                  spatial_chroma_strength=None) -> torch.Tensor:
+                  spatial_chroma_strength=None, deblock: Optional[str] = None, deblock_block: int = 8, deblock_strength=(25, 13),
+                  deblock_chroma_strength=None) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
@@ -125,6 +134,7 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     sc = as_scale(net.scale if scale is None else scale)
     noise = check_denoise_options(denoise, denoise_radius, denoise_strength, denoise_chroma_strength)          # None: the path as it was
     grain = check_spatial_options(spatial_denoise, spatial_patch, spatial_search, spatial_strength, spatial_chroma_strength)          # likewise
+    edges = check_deblock_options(deblock, deblock_block, deblock_strength, deblock_chroma_strength)          # likewise
     if surface is not None:            # the frames lie in a surface: checked against it, unpacked below, and planar from there on
         in_tab = surface_table(surface, spec.inp, spec.size)
         n, (h, w) = surface_layout(frames, in_tab), spec.size
@@ -135,6 +145,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         shaped = frames
     if out_surface is not None:        # (its table: once the crop is checked, or found)
         surface_side(out_surface, spec.out, "out_surface")
+    if edges is not None:              # (integer samples only, and the stage comes first: its refusal of float frames speaks first)
+        _sample_frames(shaped, spec.inp, spec.size, "deblock")
     if noise is not None or grain is not None:          # (integer samples only: float frames are refused here, before the GPU is touched)
         _denoise_frames(shaped, spec.inp, spec.size)
     # (deinterlacer= / field_rate= also go with scan="detect": they say how an interlaced verdict is carried out)
@@ -177,6 +189,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     frames = _to_device(frames, _net_device(net))
     if surface is not None:            # the surface comes first of all: everything below sees planar frames
         frames = _unpack_surface_device(frames, in_tab, spec.inp, spec.size)
+    if edges is not None:              # the block grid belongs to the frames as decoded: field by field where the video is treated as interlaced
+        frames = _deblock_device(frames, spec.inp, spec.size, *edges, fields is not None or pulldown is not None)
     if fields is not None:             # deinterlacing comes first, before the crop
         frames = _deinterlace_device(frames, fields, spec.inp, spec.size, method=deinterlacer, rate=field_rate)
     if pulldown is not None:           # pulldown removal comes first, where deinterlacing comes
@@ -267,6 +281,11 @@ class VideoUpscaler:
     they are cropped and buffered, holds no frame back and keeps none; any chunking gives the same frames.  The default strength is a
     parameter: nothing is validated on footage.
 
+    deblock="weak" / "strong", deblock_block=8, deblock_strength=(25, 13), deblock_chroma_strength=None (keyword only): deblocking, as in
+    upscale_video, on every pushed chunk as it arrives (after surface= unpacking, in front of the fields= / pulldown= stage), field by
+    field exactly when fields= or pulldown= is given.  The stage is stateless -- every frame is filtered on its own -- so it holds
+    nothing back and any chunking gives the same frames.  The defaults are parameters: nothing is validated on footage.
+
     scan="detect" is refused: the decision needs the video.  Run savsr_amd.detect_scan on a probe chunk (or prepass.ScanStats over a
     first pass, as python -m savsr_amd.upscale --scan detect does) and give its answer as fields= / pulldown=."""
 
@@ -278,7 +297,8 @@ class VideoUpscaler:
                  deinterlacer: str = "yadif", field_rate: str = "double", combed: Optional[str] = None, comb_threshold: int = 9,
                  comb_pixels: int = 40, denoise: Optional[str] = None, denoise_radius: int = 4, denoise_strength=(4, 9),
                  denoise_chroma_strength=None, spatial_denoise: Optional[str] = None, spatial_patch: int = 3, spatial_search: int = 7,
-                 spatial_strength=3.0, spatial_chroma_strength=None):
+                 spatial_strength=3.0, spatial_chroma_strength=None, deblock: Optional[str] = None, deblock_block: int = 8,
+                 deblock_strength=(25, 13), deblock_chroma_strength=None):
         _check_net(net)
         check_padding(padding)
         _check_scan(scan, fields, pulldown, pulldown_cycle, auto_ok=False)          # (None is the only value that passes: the path as it was)
@@ -301,6 +321,9 @@ class VideoUpscaler:
         self._noise = make_denoiser(denoise, denoise_radius, denoise_strength, denoise_chroma_strength, self.spec.inp, self.spec.size)
         # the spatial denoiser, behind the crop: stateless, every frame on its own; None: as it was
         self._grain = check_spatial_options(spatial_denoise, spatial_patch, spatial_search, spatial_strength, spatial_chroma_strength)
+        # deblocking, on the chunks as pushed: stateless, field by field where the video is interlaced or telecined; None: as it was
+        self._edges = check_deblock_options(deblock, deblock_block, deblock_strength, deblock_chroma_strength)
+        self._fieldwise = fields is not None or pulldown is not None
         self._rect = _check_crop_args(crop, 24, bars, auto_ok=False)          # the rect to crop every chunk to; None: no crop, as it was
         self.bars = bars
         if self._rect is not None and self.spec.size:
@@ -393,6 +416,8 @@ class VideoUpscaler:
         layout (with a stage in front the stage's own refusals first: float frames, one-row matrices), shape continuity, the first
         chunk's rect, the device.  With a stage the device and the copy to it speak before continuity and the rect, as they did."""
         staged = self._split is not None
+        if self._edges is not None:
+            _sample_frames(frames, self._full.inp, self._full.size, "deblock")
         if staged:
             _field_frames(frames, self._full.inp, self._full.size)
         if self._noise is not None or self._grain is not None:
@@ -421,6 +446,8 @@ class VideoUpscaler:
         new = self._admit(frames)
         if self._out_surface is not None and self._out_tab is None:
             self._set_out_tab(self._out_surface, *self._shape[1:])
+        if self._edges is not None:                # the frames as decoded, filtered one by one: no frame is held for it
+            new = _deblock_device(new, self._full.inp, self._full.size, *self._edges, self._fieldwise)
         if self._split is not None:                # interlaced / telecined chunks: the progressive frames that are final go on as a chunk of their own
             new = self._split.push(new)
             if int(new.shape[0]) == 0:             # (a first push of one frame, or a cycle not complete yet: nothing is final)
