@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 52
+#define SAVSR_ABI_VERSION 53
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -806,6 +806,41 @@ int savsr_video_deblock_u8(const uint8_t* frames, int n_frames, int64_t frame_by
 int savsr_video_deblock_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step, int depth,
                             int block, int strong, int interlaced, int thr_a, int thr_b, uint8_t* out, int64_t out_frame_bytes,
                             int64_t out_plane_offset, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 53) Deblocking on a grid with an origin, and the statistics that find block size and origin (deblock.hip, grid.hip;
+ * savsr_amd.deblock_video(origin=...), savsr_amd.grid_stats, savsr_amd.detect_grid, upscale_video(deblock_origin=..., deblock_grid="auto"),
+ * --deblock-origin / --deblock-grid of python -m savsr_amd.upscale).
+ * savsr_video_deblock_u8_o / _u16_o: savsr_video_deblock_u8 / _u16 with the grid's origin: pass X filters the edges e = origin_x + k block,
+ * 1 <= e <= cols - 1, pass Y those at origin_y + k block (field-wise: origin_y / 2 + k block / 2 in either field); reads beyond the plane
+ * clamp to it on either side, writes beyond it are dropped.  The result is that of origin (0, 0) on the plane padded by
+ * (block - origin) % block copies of its first row and column, without the padding: the kernel works in coordinates shifted by that
+ * much, its tile grid starting before the plane.  The entries without `_o` are these at (0, 0) and write the bytes they wrote.
+ * Refused beyond what they refuse: an origin outside 0 .. block - 1, an odd origin_y with interlaced (it would swap the fields).
+ * savsr_video_grid_stats_u8 / _u16: planes addressed as for savsr_video_deblock_* (rows rows of cols pixels of step samples, sample x
+ * meeting x +- j * step only), every sample on the 8-bit scale (min(s, 2^depth - 1) >> (depth - 8)).  Along a line v, at every boundary
+ * x with 2 <= x <= L - 2: s = |v[x] - v[x-1]|, l = |v[x-1] - v[x-2]|, r = |v[x+1] - v[x]|; a hit iff s > l + r and s <= cap.
+ * out[32 n + x mod 16] += the hits along the rows of frame n (x in pixels), out[32 n + 16 + y mod 16] += those along its columns;
+ * interlaced = 1 takes the rows 0::2 and 1::2 as planes of their own for the columns, y the field row (the rows' counts do not change).
+ * out (n_frames x 32 int64, device) is ADDED to: the caller zeroes it once, so that several planes land in one table
+ * (savsr_amd/grid.py `grid_stats_matrix` restates it; the kernels equal it bit for bit; the decision is host work).
+ * One launch for up to 65535 frames; the entry only enqueues, allocates nothing, does not synchronise and is capturable.  16-byte loads
+ * when the plane's base pointer, the frame stride and the row bytes are multiples of 16, a sample per access otherwise; a lane walks
+ * 4 rows keeping the four a column boundary reads; at most 32 64-bit atomics leave a workgroup.
+ * Refused (SAVSR_E_ARG, before anything is launched, the message naming the entry): a null pointer, n_frames < 1, rows < 1, cols < 1, a
+ * step outside 1 .. 4, a plane above 2147418112 bytes, a negative plane offset, a frame stride smaller than the offset plus the plane,
+ * an out that is not 8-byte aligned, interlaced other than 0 / 1, cap outside 0 .. 255; _u16: a depth other than 10 / 12, an odd
+ * pointer, stride or offset. */
+int savsr_video_deblock_u8_o(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step, int block,
+                             int strong, int interlaced, int thr_a, int thr_b, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
+                             int origin_y, int origin_x, void* stream);
+int savsr_video_deblock_u16_o(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step, int depth,
+                              int block, int strong, int interlaced, int thr_a, int thr_b, uint8_t* out, int64_t out_frame_bytes,
+                              int64_t out_plane_offset, int origin_y, int origin_x, void* stream);
+int savsr_video_grid_stats_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step,
+                              int interlaced, int cap, int64_t* out, void* stream);
+int savsr_video_grid_stats_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step, int depth,
+                               int interlaced, int cap, int64_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 45) Video surfaces (surface.hip; savsr_amd.unpack_surface, savsr_amd.pack_surface, upscale_video(surface=..., out_surface=...),

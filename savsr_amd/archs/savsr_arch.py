@@ -287,7 +287,8 @@ class SAVSR(nn.Module):
                       denoise: Optional[str] = None, denoise_radius: int = 4, denoise_strength=(4, 9),
                       denoise_chroma_strength=None, spatial_denoise: Optional[str] = None, spatial_patch: int = 3, spatial_search: int = 7,
                       spatial_strength=3.0, spatial_chroma_strength=None, deblock: Optional[str] = None, deblock_block: int = 8,
-                      deblock_strength=(25, 13), deblock_chroma_strength=None) -> torch.Tensor:
+                      deblock_strength=(25, 13), deblock_chroma_strength=None, deblock_origin=(0, 0), deblock_chroma_origin=None,
+                      deblock_grid: Optional[str] = None) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -429,7 +430,7 @@ class SAVSR(nn.Module):
         deblock, deblock_block, deblock_strength, deblock_chroma_strength (keyword only): deblocking in front of the network, for the
         8 x 8 block edges of MPEG-2 and low-bitrate H.264 sources, which neither denoiser removes and a x4 network enlarges onto a
         32-pixel grid.  deblock: None (the default: what ran before), "weak" or "strong": across the vertical edges of a grid of
-        deblock_block (4, 8 or 16, default 8) samples anchored at the frame's origin, then across the horizontal ones, the 2 ("weak")
+        deblock_block (4, 8 or 16, default 8) samples whose first edges lie at deblock_origin, then across the horizontal ones, the 2 ("weak")
         or 3 ("strong") samples on either side of an edge move towards each other by 1/2, (1/4,) 1/8 of the step across it where that
         step is below a and the steps beside it are below b, deblock_strength = (a, b), ints in 0 .. 255 in 8-bit code units at every
         depth, default (25, 13) (savsr_amd/deblock.py is the rule in integers).  Chroma planes take deblock_chroma_strength (None: the
@@ -440,8 +441,18 @@ class SAVSR(nn.Module):
         when the video is treated as interlaced -- fields= or pulldown= given, or an interlaced or telecine verdict of scan="detect".
         The result is, bit for bit, upscale_video on savsr_amd.deblock_video(frames, ..., interlaced=I) with every other argument the
         same, I as just said; crop= then crops the filtered frames, so crop="auto" reads filtered frames.  uint8 and planar frames
-        only; the deblock_ options are refused without deblock=.  The grid's origin is the frame's (a video cropped or scaled before
-        it arrives has its edges elsewhere), one block size and one strength per video, no adaptation to the stream's quantiser,
+        only; the deblock_ options are refused without deblock=.  deblock_origin = (oy, ox), deblock_chroma_origin (keyword only): the
+        grid's first edges, 0 <= o < deblock_block, default (0, 0): a video whose bars or overscan were cropped by c samples before it
+        arrived has them at (-c) mod block.  oy must be even where the stage runs field by field.  The chroma planes of 4:2:0 / 4:2:2
+        frames have an origin of their own, in chroma samples, which must be named beside a luma origin other than (0, 0); elsewhere
+        None means the same origin.  deblock_grid="auto" (keyword only) finds block and origins from the frames instead
+        (savsr_amd/grid.py; savsr_amd.detect_grid is the call): the statistics of the frames the deblocker will read, summed over the
+        video on the GPU, one more host synchronisation, an exact rule on the host.  The result is, bit for bit, the call with
+        `verdict.kwargs()` given, and with a "no grid" verdict the call with deblock=None, so a clean source passes through
+        untouched; chroma planes that show no grid of the luma's block are left alone.  It is refused together with a deblock_block or
+        an origin other than the defaults.  The detector's rule and defaults are this project's own and are not validated on footage;
+        grids of scaled video, block sizes other than 4 / 8 / 16 and block 4 on noise-free material are not found, and periodic
+        picture content can fake a grid.  One grid and one strength per video, no adaptation to the stream's quantiser,
         ringing and mosquito noise are not addressed.  The defaults are ffmpeg deblock's thresholds as parameters: nothing is
         validated on footage or on trained weights, and nothing is pinned to ffmpeg's output.
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
@@ -454,7 +465,8 @@ class SAVSR(nn.Module):
                              denoise_strength=denoise_strength, denoise_chroma_strength=denoise_chroma_strength,
                              spatial_denoise=spatial_denoise, spatial_patch=spatial_patch, spatial_search=spatial_search,
                              spatial_strength=spatial_strength, spatial_chroma_strength=spatial_chroma_strength, deblock=deblock,
-                             deblock_block=deblock_block, deblock_strength=deblock_strength, deblock_chroma_strength=deblock_chroma_strength)
+                             deblock_block=deblock_block, deblock_strength=deblock_strength, deblock_chroma_strength=deblock_chroma_strength,
+                             deblock_origin=deblock_origin, deblock_chroma_origin=deblock_chroma_origin, deblock_grid=deblock_grid)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

@@ -7,7 +7,10 @@
 // One launch per call, both passes in it, grid = (tile column, tile row, frame), 256 lanes; global memory is read once (plus the halo)
 // and written once, and pass X's result never leaves LDS.  A workgroup owns a tile of 32 frame rows x T samples whose origin lies on the
 // block grid (T = 256 / step, 64 at step 3: a multiple of 16, and 32 is one, so every block's edges and both fields' edges fall on the
-// same places in every tile).  Four phases with a barrier between them:
+// same places in every tile).  A grid origin (oy, ox) (ABI 53, the `_o` entries) keeps that: the kernel works in coordinates shifted by
+// (block - o) % block, so the tile grid starts up to block - 1 samples before the plane -- tile origins tx0, ty0 may be negative, the
+// staging clamp reads the plane's first row and column there, nothing of it is stored -- and every edge test and LDS index is what it
+// was.  Four phases with a barrier between them:
 //   stage   the tile plus its halo into LDS as 16-bit values, coordinates clamped to the plane (to the field, row-wise, in field mode),
 //           so the border rule costs nothing afterwards.  A lane loads a dword (4 bytes / 2 words) where the dword lies inside the row
 //           and is aligned, and single samples elsewhere (the clamped halo, rows of a plane whose pitch or base is not a multiple of 4).
@@ -43,6 +46,7 @@ constexpr int DBK_LEFT = DBK_HALO * DBK_MAX_STEP;                      // words 
 constexpr int DBK_PITCH = 290;                  // words of a staged row (>= 12 + 256 + 12), 145 dwords
 constexpr int DBK_LDS_ROWS = DBK_TILE_ROWS + 4 * DBK_HALO;            // the tile and 6 halo frame rows either way (field mode)
 constexpr int DBK_LDS_WORDS = DBK_LDS_ROWS * DBK_PITCH;
+constexpr int DBK_BIAS = 32;                    // samples added before a division by step so that it rounds down (> 15 + 3 + 3)
 
 struct DeblockJob {
     const uint8_t* src;          // the plane of frame 0
@@ -52,6 +56,7 @@ struct DeblockJob {
     int block, lb, strong;       // lb: log2 block
     int a, b;                    // A and Bt, in the depth's codes
     int top;                     // 2^depth - 1
+    int shift_x, shift_y;        // (block - origin) % block: the tile grid starts this many samples / frame rows before the plane
 };
 
 // Samples of a tile's row at `step` samples a pixel: 256 / step, 64 at step 3.
@@ -117,7 +122,7 @@ __device__ __forceinline__ void dbk_stage(const DeblockJob& jb, const uint8_t* p
         } else {
 #pragma unroll
             for (int k = 0; k < GE; ++k) {          // element g is channel g mod step of sample g div step, the sample clamped to the row
-                const int gs = g0 + k + DBK_MAX_STEP * step, x = min(max(gs / step - DBK_MAX_STEP, 0), jb.cols - 1), ch = gs % step;
+                const int gs = g0 + k + DBK_BIAS * step, x = min(max(gs / step - DBK_BIAS, 0), jb.cols - 1), ch = gs % step;
                 const long long e = (long long)x * step + ch;
                 if constexpr (BYTES == 1) v[k] = row[e];
                 else v[k] = min((uint32_t)reinterpret_cast<const uint16_t*>(row)[e], (uint32_t)jb.top);
@@ -162,17 +167,18 @@ __device__ __forceinline__ void dbk_pass_y(const DeblockJob& jb, uint16_t* tile,
     }
 }
 
-// Phase 4: the tile's own samples.
-template <int BYTES, int STEP, int G>
+// Phase 4: the tile's own samples.  SHIFTED: the tile grid starts before the plane (a grid origin), so a tile's first rows and samples may
+// lie in front of it; without it the code is what it was.
+template <int BYTES, int STEP, int G, bool SHIFTED>
 __device__ __forceinline__ void dbk_store(const DeblockJob& jb, uint8_t* plane, const uint16_t* tile, int tid, int tx0, int ty0) {
     constexpr int GE = 4 / BYTES, te = dbk_tile_cols(STEP) * STEP, ngroups = te / GE;
     const int E0 = tx0 * STEP, row_elems = jb.cols * STEP;
     for (int i = tid; i < DBK_TILE_ROWS * ngroups; i += DBK_THREADS) {
         const int r = i / ngroups, c0 = (i - r * ngroups) * GE, y = ty0 + r, g0 = E0 + c0;
-        if (y >= jb.rows || g0 >= row_elems) continue;
+        if (y >= jb.rows || g0 >= row_elems || (SHIFTED && (y < 0 || g0 + GE <= 0))) continue;
         const uint16_t* in = tile + (DBK_HALO * G + r) * DBK_PITCH + DBK_LEFT + c0;
         uint8_t* row = plane + (long long)y * jb.pitch;
-        if (g0 + GE <= row_elems && ((reinterpret_cast<uintptr_t>(row) + (uintptr_t)g0 * BYTES) & 3) == 0) {
+        if ((!SHIFTED || g0 >= 0) && g0 + GE <= row_elems && ((reinterpret_cast<uintptr_t>(row) + (uintptr_t)g0 * BYTES) & 3) == 0) {
             const dbk_dword* pair = reinterpret_cast<const dbk_dword*>(in);          // (LEFT, c0 and the pitch are even: two words a read)
             uint32_t w = pair[0];
             if constexpr (BYTES == 1) {
@@ -184,6 +190,7 @@ __device__ __forceinline__ void dbk_store(const DeblockJob& jb, uint8_t* plane, 
 #pragma unroll
             for (int k = 0; k < GE; ++k) {
                 if (g0 + k >= row_elems) break;
+                if (SHIFTED && g0 + k < 0) continue;
                 if constexpr (BYTES == 1) row[g0 + k] = (uint8_t)in[k];
                 else reinterpret_cast<uint16_t*>(row)[g0 + k] = in[k];
             }
@@ -194,39 +201,41 @@ __device__ __forceinline__ void dbk_store(const DeblockJob& jb, uint8_t* plane, 
 #ifdef SAVSR_HOST_CHECK
 // The host check's form: the four phases as they are, lane after lane where the GPU has a barrier, on a heap tile of the exact size
 // (the launch has one thread per workgroup).
-template <int BYTES, int STEP, int G>
+template <int BYTES, int STEP, int G, bool SHIFTED>
 __global__ void deblock_kernel(DeblockJob jb) {
     uint16_t* tile = new uint16_t[DBK_LDS_WORDS];
     for (int i = 0; i < DBK_LDS_WORDS; ++i) tile[i] = 0xDEAD;
-    const int tx0 = (int)blockIdx.x * dbk_tile_cols(STEP), ty0 = (int)blockIdx.y * DBK_TILE_ROWS;
+    const int tx0 = (int)blockIdx.x * dbk_tile_cols(STEP) - (SHIFTED ? jb.shift_x : 0), ty0 = (int)blockIdx.y * DBK_TILE_ROWS - (SHIFTED ? jb.shift_y : 0);
     const uint8_t* plane = jb.src + (long long)blockIdx.z * jb.stride;
     for (int tid = 0; tid < DBK_THREADS; ++tid) dbk_stage<BYTES, STEP, G>(jb, plane, tile, tid, tx0, ty0);
     for (int tid = 0; tid < DBK_THREADS; ++tid) dbk_pass_x<STEP, G>(jb, tile, tid, tx0);
     for (int tid = 0; tid < DBK_THREADS; ++tid) dbk_pass_y<STEP, G>(jb, tile, tid, tx0, ty0);
-    for (int tid = 0; tid < DBK_THREADS; ++tid) dbk_store<BYTES, STEP, G>(jb, jb.dst + (long long)blockIdx.z * jb.dst_stride, tile, tid, tx0, ty0);
+    for (int tid = 0; tid < DBK_THREADS; ++tid) dbk_store<BYTES, STEP, G, SHIFTED>(jb, jb.dst + (long long)blockIdx.z * jb.dst_stride, tile, tid, tx0, ty0);
     delete[] tile;
 }
 constexpr int DBK_LAUNCH_THREADS = 1;
 #else
-template <int BYTES, int STEP, int G>
+template <int BYTES, int STEP, int G, bool SHIFTED>
 __global__ __launch_bounds__(DBK_THREADS) void deblock_kernel(DeblockJob jb) {
     __shared__ __attribute__((aligned(16))) uint16_t tile[DBK_LDS_WORDS];
-    const int tid = (int)threadIdx.x, tx0 = (int)blockIdx.x * dbk_tile_cols(STEP), ty0 = (int)blockIdx.y * DBK_TILE_ROWS;
+    const int tid = (int)threadIdx.x, tx0 = (int)blockIdx.x * dbk_tile_cols(STEP) - (SHIFTED ? jb.shift_x : 0);
+    const int ty0 = (int)blockIdx.y * DBK_TILE_ROWS - (SHIFTED ? jb.shift_y : 0);
     dbk_stage<BYTES, STEP, G>(jb, jb.src + (long long)blockIdx.z * jb.stride, tile, tid, tx0, ty0);
     __syncthreads();
     dbk_pass_x<STEP, G>(jb, tile, tid, tx0);
     __syncthreads();
     dbk_pass_y<STEP, G>(jb, tile, tid, tx0, ty0);
     __syncthreads();
-    dbk_store<BYTES, STEP, G>(jb, jb.dst + (long long)blockIdx.z * jb.dst_stride, tile, tid, tx0, ty0);
+    dbk_store<BYTES, STEP, G, SHIFTED>(jb, jb.dst + (long long)blockIdx.z * jb.dst_stride, tile, tid, tx0, ty0);
 }
 constexpr int DBK_LAUNCH_THREADS = DBK_THREADS;
 #endif
 
 template <int BYTES, int STEP, int G>
 int dbk_launch(const DeblockJob& jb, int nf, hipStream_t st) {
-    hipLaunchKernelGGL((deblock_kernel<BYTES, STEP, G>), dim3(blocks(jb.cols, dbk_tile_cols(STEP)), blocks(jb.rows, DBK_TILE_ROWS), (unsigned)nf),
-                       dim3(DBK_LAUNCH_THREADS), 0, st, jb);
+    const dim3 grid(blocks(jb.cols + jb.shift_x, dbk_tile_cols(STEP)), blocks(jb.rows + jb.shift_y, DBK_TILE_ROWS), (unsigned)nf);
+    if (jb.shift_x || jb.shift_y) hipLaunchKernelGGL((deblock_kernel<BYTES, STEP, G, true>), grid, dim3(DBK_LAUNCH_THREADS), 0, st, jb);
+    else hipLaunchKernelGGL((deblock_kernel<BYTES, STEP, G, false>), grid, dim3(DBK_LAUNCH_THREADS), 0, st, jb);          // the kernel as it was
     return check_launch("deblock_kernel");
 }
 
@@ -240,10 +249,12 @@ int dbk_launch_step(const DeblockJob& jb, int nf, hipStream_t st) {
     }
 }
 
-// The body of the two entries.  cols: pixels of a row; step: samples of a pixel.
+// The body of the four entries.  cols: pixels of a row; step: samples of a pixel; (origin_y, origin_x): the grid's origin, (0, 0) from the
+// entries that have none.
 template <int BYTES>
 int deblock(const char* who, const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step, int depth,
-            int block, int strong, int interlaced, int thr_a, int thr_b, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream) {
+            int block, int strong, int interlaced, int thr_a, int thr_b, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset, void* stream,
+            int origin_y = 0, int origin_x = 0) {
     constexpr MatrixRule rule{1, 0, nullptr, "", false};
     if (step < 1 || step > DBK_MAX_STEP) return refuse(who, "step 1 .. 4 (the samples of a pixel)");
     if (cols < 1) return refuse(who, "a row holds at least one sample");
@@ -257,10 +268,13 @@ int deblock(const char* who, const uint8_t* frames, int n_frames, int64_t frame_
     if ((strong != 0 && strong != 1) || (interlaced != 0 && interlaced != 1)) return refuse(who, "strong and interlaced 0 or 1");
     const int max_thr = 255 << (depth - 8);
     if (thr_a < 0 || thr_a > max_thr || thr_b < 0 || thr_b > max_thr) return refuse(who, "thresholds 0 .. 255 << (depth - 8)");
+    if (origin_y < 0 || origin_y >= block || origin_x < 0 || origin_x >= block) return refuse(who, "origin_y and origin_x 0 .. block - 1");
+    if (interlaced && (origin_y & 1)) return refuse(who, "origin_y even with interlaced (an odd origin swaps the fields' parity)");
     if (out < frames + (int64_t)n_frames * frame_bytes && frames < out + (int64_t)n_frames * out_frame_bytes)
         return refuse(who, "the source frames and the output overlap");
     const DeblockJob jb{frames + plane_offset, out + out_plane_offset, frame_bytes, out_frame_bytes, row_bytes, rows, cols, step,
-                        block, block == 4 ? 2 : block == 8 ? 3 : 4, strong, thr_a, thr_b, (1 << depth) - 1};
+                        block, block == 4 ? 2 : block == 8 ? 3 : 4, strong, thr_a, thr_b, (1 << depth) - 1,
+                        (block - origin_x) % block, (block - origin_y) % block};
     hipStream_t st = static_cast<hipStream_t>(stream);
     return for_frame_chunks(n_frames, FM_MAX_FRAMES, [&](int f0, int nf) {
         DeblockJob part = jb;
@@ -287,4 +301,18 @@ extern "C" int savsr_video_deblock_u16(const uint8_t* frames, int n_frames, int6
                                        int64_t out_plane_offset, void* stream) {
     return deblock<2>("video_deblock_u16", frames, n_frames, frame_bytes, plane_offset, rows, cols, step, depth, block, strong, interlaced, thr_a, thr_b,
                       out, out_frame_bytes, out_plane_offset, stream);
+}
+
+extern "C" int savsr_video_deblock_u8_o(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step,
+                                        int block, int strong, int interlaced, int thr_a, int thr_b, uint8_t* out, int64_t out_frame_bytes,
+                                        int64_t out_plane_offset, int origin_y, int origin_x, void* stream) {
+    return deblock<1>("video_deblock_u8_o", frames, n_frames, frame_bytes, plane_offset, rows, cols, step, 8, block, strong, interlaced, thr_a, thr_b, out,
+                      out_frame_bytes, out_plane_offset, stream, origin_y, origin_x);
+}
+
+extern "C" int savsr_video_deblock_u16_o(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step,
+                                         int depth, int block, int strong, int interlaced, int thr_a, int thr_b, uint8_t* out, int64_t out_frame_bytes,
+                                         int64_t out_plane_offset, int origin_y, int origin_x, void* stream) {
+    return deblock<2>("video_deblock_u16_o", frames, n_frames, frame_bytes, plane_offset, rows, cols, step, depth, block, strong, interlaced, thr_a, thr_b,
+                      out, out_frame_bytes, out_plane_offset, stream, origin_y, origin_x);
 }

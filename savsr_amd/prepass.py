@@ -19,11 +19,12 @@ import torch
 from . import active
 from . import deblock as db
 from . import denoise as dn
+from . import grid as gr
 from . import nlmeans as nl
 from . import pulldown as pd
 from . import scan as sc
 from .deinterlace import DEINTERLACERS, FIELD_ORDERS, FIELD_RATES, check_frame_rows, check_method, check_order, check_rate
-from .frames import SAMPLE_FORMATS, Side, VideoSpec, check_sample_alignment, detector_layout, detector_side, plane_table
+from .frames import SAMPLE_FORMATS, Side, VideoSpec, check_sample_alignment, detector_layout, detector_side, layout_of, plane_table
 from .scenes import check_threshold, cuts_from_sad, sad_samples
 from .surface import LAYOUTS, Surface, SurfaceTable, check_stride, check_surface, descriptor
 from .yuv import CHROMAS
@@ -606,28 +607,34 @@ def denoise_spatial(frames: torch.Tensor, pixel_format: str = "rgb", size=None, 
 
 # ---- deblocking (savsr_amd/deblock.py is the specification) ----------------------------------------------------------------------------------
 def _deblock_device(frames: torch.Tensor, side: Side, size: Size, block: int = db.DEFAULT_BLOCK, mode: str = "weak",
-                    strength=db.DEFAULT_STRENGTH, chroma_strength=None, interlaced: bool = False) -> torch.Tensor:
+                    strength=db.DEFAULT_STRENGTH, chroma_strength=None, interlaced: bool = False, origin=(0, 0), chroma_origin=None) -> torch.Tensor:
     """savsr_video_deblock_* on resident frames of the input side on the GPU: as many filtered frames, every frame on its own.  One call
     (one launch, both passes in it) per plane, on the current stream (no sync): the Y plane with `strength`, the chroma planes with
     `chroma_strength` (None: `strength`), the thresholds shifted to the depth here; packed frames in one call, every channel a plane of
-    its own (the channel count is the entry's sample step).  interlaced: every plane field by field."""
+    its own (the channel count is the entry's sample step).  interlaced: every plane field by field.  origin / chroma_origin (None:
+    the origin): the grid's origin in the Y plane's / the chroma planes' samples; a plane whose origin is (0, 0) goes through the entry
+    it went through before, the others through the `_o` entries."""
     n, c, h, w = _sample_frames(frames, side, size, "deblock")
     frames, tab = frames.contiguous(), plane_table(side, size, c, h, w)
     out = torch.empty_like(frames)
     step, shift = max(c, 1), side.depth - 8
     for i, p in enumerate(tab.planes if n else ()):
         a, b = strength if i == 0 or chroma_strength is None else chroma_strength
+        oy, ox = origin if i == 0 or chroma_origin is None else chroma_origin
         head = (p.row_bytes // (tab.sample * step), step) + (() if tab.sample == 1 else (side.depth,))
-        _entry_call("savsr_video_deblock_u8" if tab.sample == 1 else "savsr_video_deblock_u16", frames, n, tab, p, head,
-                    (block, int(mode == "strong"), int(bool(interlaced)), a << shift, b << shift, out.data_ptr(), tab.stride, p.offset))
+        tail = (block, int(mode == "strong"), int(bool(interlaced)), a << shift, b << shift, out.data_ptr(), tab.stride, p.offset)
+        name = "savsr_video_deblock_u8" if tab.sample == 1 else "savsr_video_deblock_u16"
+        if (oy, ox) != (0, 0):
+            name, tail = name + "_o", tail + (int(oy), int(ox))
+        _entry_call(name, frames, n, tab, p, head, tail)
     return out
 
 
 def deblock_video(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8, block: int = db.DEFAULT_BLOCK, mode: str = "weak",
-                  strength=db.DEFAULT_STRENGTH, chroma_strength=None, interlaced: bool = False) -> torch.Tensor:
+                  strength=db.DEFAULT_STRENGTH, chroma_strength=None, interlaced: bool = False, origin=(0, 0), chroma_origin=None) -> torch.Tensor:
     """Deblocking: N frames on the GPU in the format of the N given ones (savsr_amd.deblock.deblock_frames is the specification, bit for
     bit), on the caller's current stream, without a sync.  Every frame is filtered on its own: across the vertical edges of a grid of
-    `block` (4, 8 or 16) samples anchored at the frame's origin, then across the horizontal ones, the samples next to an edge move
+    `block` (4, 8 or 16) samples whose first edges lie at `origin` = (oy, ox), then across the horizontal ones, the samples next to an edge move
     towards each other by 1/2, (1/4,) 1/8 of the step across it -- 2 samples a side with mode "weak", 3 with "strong" -- where the step
     is below a and the steps beside it are below b, strength = (a, b) in 8-bit code units at every depth (ints in 0 .. 255).
     interlaced=True filters the two fields as planes of their own (vertical block `block` // 2, weak below 8, no vertical pass at block
@@ -635,13 +642,74 @@ def deblock_video(frames: torch.Tensor, pixel_format: str = "rgb", size=None, de
     its own), or with pixel_format "i420", "i422", "i444", "y400" and size=(h, w): [N, frame_bytes] uint8, every plane on its own with
     the same block in its own samples, 16-bit samples at depth 10 / 12, the chroma planes with `chroma_strength` (None: `strength`).
     Float frames are refused.  A constant plane comes back as it is, a = 0 is the identity and a pass moves no sample by more than
-    (a - 1) // 2 codes (shifted to the depth).  The defaults (block 8, (25, 13)) are parameters: nothing is validated on footage.  The
-    grid starts at the frame's origin: a video cropped or scaled before it arrives has its edges elsewhere."""
+    (a - 1) // 2 codes (shifted to the depth).  The defaults (block 8, (25, 13)) are parameters: nothing is validated on footage.
+    origin = (oy, ox), 0 <= o < block (oy even with interlaced=True): a video cropped by c samples before it arrived has its edges at
+    (-c) mod block; chroma_origin: the same for the Cb / Cr planes in chroma samples (None: the origin; 4:2:0 and 4:2:2 frames with
+    an origin other than (0, 0) must name it).  `detect_grid` finds block and origins from the frames.  A video scaled before it
+    arrives has no grid this stage knows."""
     block, mode = db.check_block(block), db.check_mode(mode)
     strength = db.check_strength(strength)
     chroma_strength = None if chroma_strength is None else db.check_strength(chroma_strength, "chroma_strength")
+    origin, chroma_origin = db.check_origins(origin, chroma_origin, block, interlaced, layout_of(pixel_format) if size else None)
     frames, side, size = _stage_args(frames, pixel_format, size, depth, lambda f, s, z: _sample_frames(f, s, z, "deblock"))
-    return _deblock_device(frames, side, size, block, mode, strength, chroma_strength, interlaced)
+    return _deblock_device(frames, side, size, block, mode, strength, chroma_strength, interlaced, origin, chroma_origin)
+
+
+# ---- the block grid (savsr_amd/grid.py is the specification) --------------------------------------------------------------------------------
+def _grid_stats_device(frames: torch.Tensor, side: Side, size: Size, interlaced: bool = False, cap: int = gr.DEFAULT_CAP) -> torch.Tensor:
+    """savsr_video_grid_stats_* on resident frames of the input side on the GPU: int64 [N, 2, 2, 16] there (a view of [2, N, 2, 16]), one
+    memset and one launch per plane on the current stream (no sync).  Class 0: the Y plane, or all channels of packed frames in one call (the channel count
+    is the entry's sample step); class 1: the chroma planes, both added into the same cells."""
+    n, c, h, w = _sample_frames(frames, side, size, "find a grid in")
+    frames, tab = frames.contiguous(), plane_table(side, size, c, h, w)
+    out = torch.zeros(2, n, 2, gr.CELLS, dtype=torch.int64, device=frames.device)          # by class: a class's frames are 32 cells apart, as the entry adds them
+    step = max(c, 1)
+    for i, p in enumerate(tab.planes if n else ()):
+        head = (p.row_bytes // (tab.sample * step), step) + (() if tab.sample == 1 else (side.depth,))
+        _entry_call("savsr_video_grid_stats_u8" if tab.sample == 1 else "savsr_video_grid_stats_u16", frames, n, tab, p, head,
+                    (int(bool(interlaced)), cap, out[min(i, 1)].data_ptr()))
+    return out.permute(1, 0, 2, 3)
+
+
+def grid_stats(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8, interlaced: bool = False,
+               cap: int = gr.DEFAULT_CAP) -> torch.Tensor:
+    """The grid detector's statistics: int64 [N, 2, 2, 16] on the GPU (savsr_amd.grid.grid_stats_frames is the specification, bit for
+    bit), on the caller's current stream, without a sync.  [n, k, 0, x mod 16] counts, along the rows of class k of frame n, the
+    boundaries whose step is larger than the two steps beside it together and at most `cap` (8-bit codes); [n, k, 1, y mod 16] the same
+    along the columns, field by field with interlaced=True.  Class 0: the Y plane of planar frames, or every channel of [N, h, w, c]
+    uint8 frames; class 1: Cb + Cr, zeros where there is none.  Float frames are refused.  cap is a parameter of this project's own:
+    nothing is validated on footage."""
+    cap = gr.check_cap(cap)
+    frames, side, size = _stage_args(frames, pixel_format, size, depth, lambda f, s, z: _sample_frames(f, s, z, "find a grid in"))
+    return _grid_stats_device(frames, side, size, interlaced, cap)
+
+
+def _frame_pairs(frames: torch.Tensor, side: Side, size: Size, interlaced: bool):
+    return gr.frame_pairs(tuple(frames.shape), side.fmt, size, side.depth, interlaced)
+
+
+def _detect_grid_device(frames: torch.Tensor, side: Side, size: Size, interlaced: bool = False, ratio=gr.DEFAULT_RATIO,
+                        min_count: int = gr.DEFAULT_MIN_COUNT, cap: int = gr.DEFAULT_CAP) -> "gr.GridVerdict":
+    """grid.verdict_from_stats on `_grid_stats_device` of frames of the input side on the GPU, summed over the frames there: one device
+    -> host copy of 64 integers."""
+    n = _sample_frames(frames, side, size, "find a grid in")[0]
+    table = _grid_stats_device(frames, side, size, interlaced, cap).sum(0).cpu().numpy()
+    return gr.verdict_from_stats(table, n * _frame_pairs(frames, side, size, interlaced), interlaced, ratio, min_count)
+
+
+def detect_grid(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8, interlaced: bool = False, ratio=gr.DEFAULT_RATIO,
+                min_count: int = gr.DEFAULT_MIN_COUNT, cap: int = gr.DEFAULT_CAP) -> "gr.GridVerdict":
+    """The block grid of a video, from its content: a savsr_amd.grid.GridVerdict with block = 4, 8, 16 or None (no grid), origin =
+    (oy, ox) and chroma_origin (None where the chroma planes show no grid of the luma's block); `verdict.kwargs()` is the explicit
+    argument set of upscale_video / VideoUpscaler beside deblock= that says the same, {} without a grid.  `grid_stats` on the GPU summed
+    over the frames, one host synchronisation, then savsr_amd.grid.verdict_from_stats in exact arithmetic: a cell of the 16 is a peak
+    where it holds at least `min_count` hits and its hit rate is at least `ratio` times the median rate, and the peaks must be exactly
+    those of one block size in both directions.  interlaced=True reads the columns field by field, as the deblocker will filter them.
+    The rule and its defaults are this project's own and are not validated on footage; one grid per video; grids of scaled video,
+    other block sizes and block 4 on noise-free material are not found; periodic picture content can fake a grid."""
+    ratio, min_count, cap = gr.check_ratio(ratio), gr.check_min_count(min_count), gr.check_cap(cap)
+    frames, side, size = _stage_args(frames, pixel_format, size, depth, lambda f, s, z: _sample_frames(f, s, z, "find a grid in"))
+    return _detect_grid_device(frames, side, size, interlaced, ratio, min_count, cap)
 
 
 # ---- telecined film (savsr_amd/pulldown.py is the specification) -----------------------------------------------------------------------------

@@ -137,15 +137,23 @@ stage and its parameters.  Works for PNG folders and for .y4m files and pipes.  
 search stops at 15 x 15; the defaults are parameters, nothing is validated on footage and nothing is pinned to ffmpeg's nlmeans.
 
 --deblock weak|strong: the 8 x 8 block edges of MPEG-2 and low-bitrate H.264 sources, which neither denoiser removes.  On the GPU, every
-frame on its own: across the vertical edges of a grid of --deblock-block N (default 8; 4, 8 or 16) samples anchored at the frame's
-origin, then across the horizontal ones, the 2 (weak) or 3 (strong) samples on either side of an edge move towards each other where the
+frame on its own: across the vertical edges of a grid of --deblock-block N (default 8; 4, 8 or 16) samples whose first edges lie at
+--deblock-origin Y,X (default 0,0), then across the horizontal ones, the 2 (weak) or 3 (strong) samples on either side of an edge move towards each other where the
 step across it is below A and the steps beside it are below B (--deblock-strength A,B in 8-bit code units at every depth, default
 25,13, ints in 0 .. 255; savsr_amd/deblock.py); --deblock-chroma-strength A,B sets the chroma planes of a Y4M input apart.  The grid
 belongs to the coded frame, so the stage runs on the frames as read, in front of --fields / --pulldown, --denoise, --crop (auto reads
 the filtered frames), --spatial-denoise and --cuts, and field by field where the video is treated as interlaced: with --fields or
 --pulldown, or an interlaced or telecine verdict of --scan detect, whose first pass reads the unfiltered frames.  No frame is held back,
 and one line on stderr names the stage, its parameters and whether it ran field-wise.  Works for PNG folders and for .y4m files and
-pipes.  The grid's origin is the frame's, one block size and one strength per video, no adaptation to the stream's quantiser; the
+pipes.  A video whose bars or overscan were cropped by c samples before it arrived has its edges at (-c) mod N: --deblock-origin Y,X says
+so (Y even where the stage runs field-wise), --deblock-chroma-origin Y,X for the chroma planes of a Y4M input in chroma samples (4:2:0 /
+4:2:2 input with an origin other than 0,0 must name it).  --deblock-grid auto finds block size and origins from the frames instead
+(savsr_amd/grid.py): a first pass over a .y4m file or a PNG folder in --chunk pieces, the statistics summed on the GPU -- behind
+--scan detect's pass, whose verdict says whether to count field-wise, and in front of --crop auto's -- then an exact rule on the host;
+one line on stderr gives the verdict and the equivalent flags, --grid-out FILE writes it as JSON (block, origins, the summed table, the
+peaks); no grid found: the stage is left out; chroma planes that show no grid of the luma's block are left alone.  It is refused on
+stdin and together with --deblock-block / --deblock-origin.  The detector's rule and defaults are this project's own and are not
+validated on footage; grids of scaled video, other block sizes and block 4 on noise-free material are not found.  One grid and one strength per video, no adaptation to the stream's quantiser; the
 defaults are parameters, nothing is validated on footage and nothing is pinned to ffmpeg's deblock.
 
 It ends with one line: frames, seconds, frames/s (on stderr when the video goes to stdout); with --cuts, the scene count as well; with
@@ -345,6 +353,16 @@ def build_parser() -> argparse.ArgumentParser:
                    help="detect: find out from the content, in a first pass over the input (a file or a folder), whether it is progressive, "
                         "interlaced or telecined film and with which field order, then run as --fields X / --pulldown X would; the verdict "
                         "goes to stderr (thresholds not validated on real footage)")
+    p.add_argument("--deblock-origin", default=None, metavar="Y,X",
+                   help="--deblock: the grid's first edges, 0 <= Y, X < the block (default 0,0; a video cropped by c samples before it arrived "
+                        "has them at (-c) mod block; Y even where the stage runs field-wise)")
+    p.add_argument("--deblock-chroma-origin", default=None, metavar="Y,X",
+                   help="--deblock: the same for the chroma planes of a Y4M input, in chroma samples (4:2:0 / 4:2:2 input with an origin other "
+                        "than 0,0 must name it; default: --deblock-origin)")
+    p.add_argument("--deblock-grid", default=None, choices=["auto"],
+                   help="--deblock: find the block size and the origins from the frames in a first pass over the input (savsr_amd/grid.py; the "
+                        "rule's defaults are this project's own and are not validated on footage); no grid found: the stage is left out")
+    p.add_argument("--grid-out", default=None, metavar="FILE", help="--deblock-grid auto: write the verdict as JSON")
     p.add_argument("--scan-out", default=None, metavar="FILE", help="--scan detect: write the verdict as JSON")
     p.add_argument("--bars", default=None, choices=["keep", "drop"],
                    help="--crop: keep = full-size output, the picture in nominal black (default); drop = the picture alone")
@@ -374,6 +392,18 @@ def parse_strength(text: str, what: str):
     if len(pair) != 2:
         raise ValueError(f"{what}: A,B, got {text!r}")
     return check_strength(pair, what)
+
+
+def parse_deblock_origin(text: str, block: int, what: str):
+    """--deblock-origin / --deblock-chroma-origin: "Y,X" -> the checked (oy, ox)."""
+    parts = text.split(",")
+    try:
+        origin = tuple(int(v) for v in parts)
+    except ValueError:
+        origin = None
+    if origin is None or len(origin) != 2:
+        raise ValueError(f"{what} = {text!r}: Y,X, two ints in 0 .. {block - 1}")
+    return dbk.check_origin(origin, block, False, what)
 
 
 def parse_deblock_strength(text: str, what: str):
@@ -521,7 +551,21 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     if a.deblock is None:
         if any(v is not None for v in (a.deblock_block, a.deblock_strength, a.deblock_chroma_strength)):
             p.error("--deblock-block, --deblock-strength and --deblock-chroma-strength go with --deblock weak or strong")
+        if any(v is not None for v in (a.deblock_origin, a.deblock_chroma_origin, a.deblock_grid)):
+            p.error("--deblock-origin, --deblock-chroma-origin and --deblock-grid go with --deblock weak or strong")
+        if a.grid_out is not None:
+            p.error("--grid-out goes with --deblock-grid auto")
     else:
+        if a.deblock_grid is None and a.grid_out is not None:
+            p.error("--grid-out goes with --deblock-grid auto")
+        if a.deblock_grid is not None:
+            if any(v is not None for v in (a.deblock_block, a.deblock_origin, a.deblock_chroma_origin)):
+                p.error("--deblock-grid auto finds what --deblock-block, --deblock-origin and --deblock-chroma-origin say: give one or the other")
+            if a.input == "-":
+                p.error("--deblock-grid auto needs a first pass over the input, which stdin does not allow: find the grid first "
+                        "(savsr_amd.detect_grid) and give --deblock-block / --deblock-origin")
+        if a.deblock_chroma_origin is not None and not a.y4m_in:
+            p.error("--deblock-chroma-origin goes with a Y4M input (PNG frames are RGB: every channel takes --deblock-origin)")
         if a.deblock_chroma_strength is not None and not a.y4m_in:
             p.error("--deblock-chroma-strength goes with a Y4M input (PNG frames are RGB: every channel takes --deblock-strength)")
         try:
@@ -530,6 +574,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
                                   else parse_deblock_strength(a.deblock_strength, "--deblock-strength"))
             if a.deblock_chroma_strength is not None:
                 a.deblock_chroma_strength = parse_deblock_strength(a.deblock_chroma_strength, "--deblock-chroma-strength")
+            a.deblock_origin = (0, 0) if a.deblock_origin is None else parse_deblock_origin(a.deblock_origin, a.deblock_block, "--deblock-origin")
+            if a.deblock_chroma_origin is not None:
+                a.deblock_chroma_origin = parse_deblock_origin(a.deblock_chroma_origin, a.deblock_block, "--deblock-chroma-origin")
         except ValueError as e:
             p.error(str(e))
     try:
@@ -720,8 +767,46 @@ def deblock_kwargs(a: argparse.Namespace) -> dict:
     """--deblock and its options as the keyword arguments of VideoUpscaler; nothing without --deblock."""
     if a.deblock is None:
         return {}
-    return dict(deblock=a.deblock, deblock_block=a.deblock_block, deblock_strength=a.deblock_strength,
-                deblock_chroma_strength=a.deblock_chroma_strength)
+    kw = dict(deblock=a.deblock, deblock_block=a.deblock_block, deblock_strength=a.deblock_strength,
+              deblock_chroma_strength=a.deblock_chroma_strength)
+    if tuple(a.deblock_origin) != (0, 0) or a.deblock_chroma_origin is not None:          # (an origin at its default: the call as it was)
+        kw.update(deblock_origin=a.deblock_origin, deblock_chroma_origin=a.deblock_chroma_origin)
+    return kw
+
+
+def detect_grid_pass(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev, fieldwise: bool):
+    """--deblock-grid auto's first pass: savsr_amd.grid_stats over the input in --chunk-sized pieces, summed on the device (one copy of 64
+    integers at the end), then grid.verdict_from_stats.  It reads the frames the deblocker will read -- as decoded, field-wise exactly
+    when the stage will run field-wise -- so it comes after --scan detect's pass, whose verdict says which, and in front of --crop
+    auto's, which reads the filtered frames.  chunks: the PNG folder's chunk iterator; None: the .y4m file named by --input, read
+    through a reader of its own."""
+    import torch
+
+    from .grid import frame_pairs, verdict_from_stats
+    from .prepass import grid_stats
+    from .y4m import Y4MReader
+    from .yuv import CHROMAS
+    f = None
+    table, pairs = None, None
+    try:
+        if chunks is None:
+            f = open(a.input, "rb")
+            chunks = (torch.from_numpy(c) for c in Y4MReader(f, high_depth=True, layouts=CHROMAS, mono=True).chunks(a.chunk))
+        with torch.cuda.device(dev):
+            for chunk in chunks:
+                if not int(chunk.shape[0]):
+                    continue
+                part = grid_stats(chunk.to(dev), fmt_in, size, depth, fieldwise).sum(0)
+                more = int(chunk.shape[0]) * frame_pairs(tuple(chunk.shape), fmt_in, size, depth, fieldwise)
+                table, pairs = (part, more) if table is None else (table + part, pairs + more)
+    except ValueError as e:
+        raise SystemExit(f"--deblock-grid auto: {e}") from None
+    finally:
+        if f is not None:
+            f.close()
+    if table is None:
+        raise SystemExit("the video has no frames")
+    return verdict_from_stats(table.cpu().numpy(), pairs, fieldwise)
 
 
 def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev, order: Optional[str] = None, film: Optional[str] = None):
@@ -768,7 +853,7 @@ def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, de
                 chunk = chunk.to(dev)
                 if a.deblock is not None:
                     chunk = deblock_video(chunk, fmt_in, size, depth, a.deblock_block, a.deblock, a.deblock_strength, a.deblock_chroma_strength,
-                                          order is not None or film is not None)
+                                          order is not None or film is not None, a.deblock_origin, a.deblock_chroma_origin)
                 fold(chunk if split is None else split.push(chunk))
             last = None if split is None else split.finish()
             if last is not None:
@@ -931,6 +1016,37 @@ def main(argv: Optional[List[str]] = None) -> int:
                 print(note, file=sys.stderr, flush=True)
         dev = torch.device(a.device)
         net = net.to(dev)
+        fieldwise = order is not None or film is not None
+        if a.deblock is not None and a.deblock_grid is not None:          # the grid's pass: behind the scan's, whose verdict it needs, in front of the crop's
+            found = detect_grid_pass(a, chunks if paths is not None else None, fmt_in, (h, w) if a.y4m_in else None, depth, dev, fieldwise)
+            if paths is not None:
+                chunks = png_chunks()
+            if a.grid_out is not None:
+                import json
+                with open(a.grid_out, "w") as f:
+                    json.dump(found.as_json(), f)
+                    f.write("\n")
+            kw = found.kwargs()
+            if not kw:
+                print("--deblock-grid auto: no grid found: --deblock none (the rule is not validated on footage)", file=sys.stderr, flush=True)
+                a.deblock = None
+            else:
+                a.deblock_block, a.deblock_origin = kw["deblock_block"], kw["deblock_origin"]
+                a.deblock_chroma_origin = kw.get("deblock_chroma_origin")
+                a.deblock_chroma_strength = kw.get("deblock_chroma_strength", a.deblock_chroma_strength)
+                flags = f"--deblock-block {a.deblock_block} --deblock-origin {a.deblock_origin[0]},{a.deblock_origin[1]}"
+                if a.deblock_chroma_origin is not None:
+                    flags += f" --deblock-chroma-origin {a.deblock_chroma_origin[0]},{a.deblock_chroma_origin[1]}"
+                if "deblock_chroma_strength" in kw:
+                    flags += " --deblock-chroma-strength 0,0 (no chroma grid of that block: the chroma planes are left alone)"
+                print(f"--deblock-grid auto: block {a.deblock_block} at origin {a.deblock_origin[0]},{a.deblock_origin[1]}"
+                      f"{' (field-wise)' if fieldwise else ''}: {flags} (the rule is not validated on footage)", file=sys.stderr, flush=True)
+        if a.deblock is not None:
+            try:          # (an odd Y on a field-wise run, a subsampled input without a chroma origin: known only now)
+                dbk.check_origins(a.deblock_origin, a.deblock_chroma_origin, a.deblock_block, fieldwise,
+                                  chroma if a.y4m_in and chroma != MONO else None, "--deblock-")
+            except ValueError as e:
+                raise SystemExit(str(e)) from None
         rect = a.crop
         if rect == "auto":                          # the first pass: line sums chunk by chunk, a running maximum on the device
             rect = detect_crop(a, chunks if paths is not None else None, fmt_in, (h, w) if a.y4m_in else None, depth, dev, order, film)
@@ -987,7 +1103,10 @@ def main(argv: Optional[List[str]] = None) -> int:
                            **denoise_kwargs(a), **spatial_kwargs(a), **deblock_kwargs(a))
         if a.deblock is not None:
             cs = a.deblock_chroma_strength or a.deblock_strength
-            print(f"--deblock {a.deblock}: block {a.deblock_block}, strength {a.deblock_strength[0]},{a.deblock_strength[1]}"
+            at = "" if a.deblock_origin == (0, 0) and a.deblock_chroma_origin is None else (
+                f" at origin {a.deblock_origin[0]},{a.deblock_origin[1]}"
+                + ("" if a.deblock_chroma_origin is None else f" (chroma {a.deblock_chroma_origin[0]},{a.deblock_chroma_origin[1]})"))
+            print(f"--deblock {a.deblock}: block {a.deblock_block}{at}, strength {a.deblock_strength[0]},{a.deblock_strength[1]}"
                   + (f", chroma strength {cs[0]},{cs[1]}" if a.y4m_in else "") + " (8-bit code units; not validated on footage), "
                   + ("field-wise (the fields as planes of their own)" if order is not None or film is not None else "progressive"),
                   file=sys.stderr, flush=True)

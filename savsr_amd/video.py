@@ -45,7 +45,14 @@ frame on its own).  The grid belongs to the coded frame, so the stage runs on th
 after scan="detect" has read the unfiltered frames, in front of fields= / pulldown=, denoise=, the crop, spatial_denoise= and the cuts, and
 field by field exactly when the video is treated as interlaced (fields= or pulldown= given, or an interlaced / telecine verdict).  The
 call is, bit for bit, the call on `deblock_video(v, ..., interlaced=I)`; crop= crops the filtered frames, so crop="auto" reads filtered
-frames.  None runs the lines that ran before.
+frames.  None runs the lines that ran before.  deblock_origin=(oy, ox) / deblock_chroma_origin= say where the grid's first edges lie
+(a video cropped by c samples before it arrived has them at (-c) mod block; the chroma planes of 4:2:0 / 4:2:2 frames have an origin of
+their own, in chroma samples, which must be named beside a luma origin other than (0, 0)).  deblock_grid="auto" asks the frames instead
+(savsr_amd/grid.py: `grid_stats` on the frames the deblocker will read -- after surface= unpacking and after scan="detect", field-wise
+exactly when the deblocker runs field-wise -- summed over the video, one more host synchronisation, then an exact rule on the host): the
+call is, bit for bit, the call with `verdict.kwargs()` given, and with a "no grid" verdict the call with deblock=None; chroma planes whose
+grid was not found at the luma's block are left alone (chroma threshold a = 0).  One grid per video; the rule's defaults are this
+project's own and are not validated on footage.
 
 dither="ordered": every quantiser behind the network (packed uint8, planar YUV, the luma-only path's Y plane) takes floor(t + theta(y, x))
 in rint's place, theta from a 16 x 16 Bayer matrix at the sample's position in its plane (savsr_amd/dither.py is the specification, the
@@ -71,16 +78,17 @@ from .frames import (OUT_KINDS, PADDING_MODES, PIXEL_FORMATS, SAMPLE_FORMATS, YU
                      check_sitings, chroma_of, frame_layout, i420_layout, layout_of, luma_mode, video_spec)
 from .harness import window_indices
 from .packing import get_hw
-from .deblock import check_deblock_options
+from .deblock import check_deblock_options, check_origins
 from .denoise import check_denoise_options
 from .nlmeans import check_spatial_options
 from .prepass import (FieldSplitter, PulldownRemover, ScanStats, TemporalDenoiser, _check_crop_args, _check_field_options, _check_fields,  # noqa: F401  (re-exported)
                       _check_pulldown, _check_scan, _crop_device, _cropped_spec, _deblock_device, _deinterlace_device, _denoise_device, _denoise_frames, _denoise_spatial_device,
-                      _detect_device, _detect_scan_device, _field_frames, _insert_device, _pair_sad_device, _pack_surface_device,
+                      _detect_device, _detect_grid_device, _detect_scan_device, _field_frames, _insert_device, _pair_sad_device, _pack_surface_device,
                       _remove_pulldown_device, _sample_frames, _to_device, _unpack_surface_device, comb_windows, deblock_video, deinterlace, denoise_spatial, denoise_video,
-                      detect_active_area, detect_cuts, detect_scan, field_scores, field_stats, line_sums, make_denoiser, make_stage,
+                      detect_active_area, detect_cuts, detect_grid, detect_scan, field_scores, field_stats, grid_stats, line_sums, make_denoiser, make_stage,
                       pack_surface, pair_sad, remove_pulldown, surface_layout, surface_side, surface_table, unpack_surface)
 from .pulldown import check_comb_options
+from .grid import GridVerdict  # noqa: F401  (re-exported)
 from .scan import ScanVerdict, check_thresholds  # noqa: F401  (re-exported)
 
 
@@ -125,7 +133,7 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
                   denoise: Optional[str] = None, denoise_radius: int = 4, denoise_strength=(4, 9), denoise_chroma_strength=None,
                   spatial_denoise: Optional[str] = None, spatial_patch: int = 3, spatial_search: int = 7, spatial_strength=3.0,
                   spatial_chroma_strength=None, deblock: Optional[str] = None, deblock_block: int = 8, deblock_strength=(25, 13),
-                  deblock_chroma_strength=None) -> torch.Tensor:
+                  deblock_chroma_strength=None, deblock_origin=(0, 0), deblock_chroma_origin=None, deblock_grid: Optional[str] = None) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
@@ -134,7 +142,12 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     sc = as_scale(net.scale if scale is None else scale)
     noise = check_denoise_options(denoise, denoise_radius, denoise_strength, denoise_chroma_strength)          # None: the path as it was
     grain = check_spatial_options(spatial_denoise, spatial_patch, spatial_search, spatial_strength, spatial_chroma_strength)          # likewise
-    edges = check_deblock_options(deblock, deblock_block, deblock_strength, deblock_chroma_strength)          # likewise
+    edges = check_deblock_options(deblock, deblock_block, deblock_strength, deblock_chroma_strength, origin=deblock_origin,
+                                  chroma_origin=deblock_chroma_origin, grid=deblock_grid)          # likewise
+    grid = None          # (origin, chroma origin) of the deblocker's grid, or "auto": found below, on the frames the deblocker will read
+    if edges is not None:              # (an odd oy is refused here where the run is known to be field-wise, and below once scan= has said so)
+        grid = "auto" if deblock_grid == "auto" else check_origins(deblock_origin, deblock_chroma_origin, edges[0], fields is not None or pulldown
+                                                                   is not None, spec.inp.layout, "deblock_")
     if surface is not None:            # the frames lie in a surface: checked against it, unpacked below, and planar from there on
         in_tab = surface_table(surface, spec.inp, spec.size)
         n, (h, w) = surface_layout(frames, in_tab), spec.size
@@ -190,7 +203,13 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     if surface is not None:            # the surface comes first of all: everything below sees planar frames
         frames = _unpack_surface_device(frames, in_tab, spec.inp, spec.size)
     if edges is not None:              # the block grid belongs to the frames as decoded: field by field where the video is treated as interlaced
-        frames = _deblock_device(frames, spec.inp, spec.size, *edges, fields is not None or pulldown is not None)
+        fieldwise = fields is not None or pulldown is not None
+        if grid == "auto":             # block and origins from the frames the deblocker will read; no grid: the stage is left out
+            edges, grid = _auto_grid(_detect_grid_device(frames, spec.inp, spec.size, fieldwise), edges, fieldwise, spec.inp.layout)
+        else:
+            grid = check_origins(*grid, edges[0], fieldwise, spec.inp.layout, "deblock_")
+        if edges is not None:
+            frames = _deblock_device(frames, spec.inp, spec.size, *edges, fieldwise, *grid)
     if fields is not None:             # deinterlacing comes first, before the crop
         frames = _deinterlace_device(frames, fields, spec.inp, spec.size, method=deinterlacer, rate=field_rate)
     if pulldown is not None:           # pulldown removal comes first, where deinterlacing comes
@@ -222,6 +241,16 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
             HW = _out_hw(h, w, crop, bars, sc)
             res = _pack_surface_device(res, surface_table(out_surface, full.out, HW, "out_surface"), full.out, HW)
         return res
+
+
+def _auto_grid(verdict, edges, fieldwise: bool, layout):
+    """What deblock_grid="auto" continues with: ((block, mode, strength, chroma strength), (origin, chroma origin)) as if
+    `verdict.kwargs()` had been given beside deblock=, or (None, None) without a grid (the call with deblock=None)."""
+    found = verdict.kwargs()
+    if not found:
+        return None, None
+    edges = (found["deblock_block"], edges[1], edges[2], found.get("deblock_chroma_strength", edges[3]))
+    return edges, check_origins(found["deblock_origin"], found.get("deblock_chroma_origin"), edges[0], fieldwise, layout, "deblock_")
 
 
 class VideoUpscaler:
@@ -285,6 +314,9 @@ class VideoUpscaler:
     upscale_video, on every pushed chunk as it arrives (after surface= unpacking, in front of the fields= / pulldown= stage), field by
     field exactly when fields= or pulldown= is given.  The stage is stateless -- every frame is filtered on its own -- so it holds
     nothing back and any chunking gives the same frames.  The defaults are parameters: nothing is validated on footage.
+    deblock_origin=(0, 0), deblock_chroma_origin=None: the grid's origin, as in upscale_video.  deblock_grid="auto" is refused: the
+    decision needs the video.  Run savsr_amd.detect_grid on a probe chunk (or sum savsr_amd.grid_stats over a first pass, as
+    python -m savsr_amd.upscale --deblock-grid auto does) and give `verdict.kwargs()`.
 
     scan="detect" is refused: the decision needs the video.  Run savsr_amd.detect_scan on a probe chunk (or prepass.ScanStats over a
     first pass, as python -m savsr_amd.upscale --scan detect does) and give its answer as fields= / pulldown=."""
@@ -298,7 +330,8 @@ class VideoUpscaler:
                  comb_pixels: int = 40, denoise: Optional[str] = None, denoise_radius: int = 4, denoise_strength=(4, 9),
                  denoise_chroma_strength=None, spatial_denoise: Optional[str] = None, spatial_patch: int = 3, spatial_search: int = 7,
                  spatial_strength=3.0, spatial_chroma_strength=None, deblock: Optional[str] = None, deblock_block: int = 8,
-                 deblock_strength=(25, 13), deblock_chroma_strength=None):
+                 deblock_strength=(25, 13), deblock_chroma_strength=None, deblock_origin=(0, 0), deblock_chroma_origin=None,
+                 deblock_grid: Optional[str] = None):
         _check_net(net)
         check_padding(padding)
         _check_scan(scan, fields, pulldown, pulldown_cycle, auto_ok=False)          # (None is the only value that passes: the path as it was)
@@ -322,8 +355,14 @@ class VideoUpscaler:
         # the spatial denoiser, behind the crop: stateless, every frame on its own; None: as it was
         self._grain = check_spatial_options(spatial_denoise, spatial_patch, spatial_search, spatial_strength, spatial_chroma_strength)
         # deblocking, on the chunks as pushed: stateless, field by field where the video is interlaced or telecined; None: as it was
-        self._edges = check_deblock_options(deblock, deblock_block, deblock_strength, deblock_chroma_strength)
+        if deblock_grid == "auto":
+            raise ValueError("deblock_grid = 'auto' in VideoUpscaler: the decision needs the whole video; find the grid first "
+                             "(savsr_amd.detect_grid) and give its kwargs(), or use python -m savsr_amd.upscale --deblock-grid auto")
+        self._edges = check_deblock_options(deblock, deblock_block, deblock_strength, deblock_chroma_strength, origin=deblock_origin,
+                                            chroma_origin=deblock_chroma_origin, grid=deblock_grid)
         self._fieldwise = fields is not None or pulldown is not None
+        self._grid = None if self._edges is None else check_origins(deblock_origin, deblock_chroma_origin, self._edges[0], self._fieldwise,
+                                                                    self.spec.inp.layout, "deblock_")
         self._rect = _check_crop_args(crop, 24, bars, auto_ok=False)          # the rect to crop every chunk to; None: no crop, as it was
         self.bars = bars
         if self._rect is not None and self.spec.size:
@@ -447,7 +486,7 @@ class VideoUpscaler:
         if self._out_surface is not None and self._out_tab is None:
             self._set_out_tab(self._out_surface, *self._shape[1:])
         if self._edges is not None:                # the frames as decoded, filtered one by one: no frame is held for it
-            new = _deblock_device(new, self._full.inp, self._full.size, *self._edges, self._fieldwise)
+            new = _deblock_device(new, self._full.inp, self._full.size, *self._edges, self._fieldwise, *self._grid)
         if self._split is not None:                # interlaced / telecined chunks: the progressive frames that are final go on as a chunk of their own
             new = self._split.push(new)
             if int(new.shape[0]) == 0:             # (a first push of one frame, or a cycle not complete yet: nothing is final)
