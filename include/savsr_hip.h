@@ -164,7 +164,12 @@ int savsr_conv2d_batch(const savsr_conv_desc* descs, int n, void* stream);
  * rounds to 65504) -- the caller checks its weights (and U); the activations are NOT checked, and the two forms differ: the direct form
  * needs |x| < 65520, the Winograd-y form the same of V = x_a + x_b and x_a - x_b for rows one and two apart, so |x| <= 32752 is safe in
  * both.  An infinity reaches exactly the outputs whose receptive field holds it (Winograd-y: the row pair's four input rows x 3 columns)
- * with IEEE classes (+inf, -inf, NaN); every other output, and every other conv of the launch, is unaffected.  No lower limit: operands
+ * with IEEE classes (+inf, -inf, NaN); every other output, and every other conv of the launch, is unaffected.  The epilogue's effect on
+ * such an accumulator, the same on every path of both forms: bias, mask and residuals are IEEE; SAVSR_ACT_NONE, _RELU and _LRELU never
+ * make it finite -- a NaN stays a NaN, RELU(+inf) = +inf and RELU(-inf) = -inf, NOT 0 (ReLU is v_max_f32(v, v * 0), and -inf * 0 is a NaN
+ * the maximum ignores; LRELU with slope 0 likewise), otherwise LRELU(-inf) = slope * (-inf): -inf, or +inf for a negative slope;
+ * SAVSR_ACT_SIGMOID gives exactly 0 for -inf, 1 for +inf and NaN for a NaN.  No finite value is affected: for finite v, ReLU is
+ * max(v, 0) up to the sign of a zero (tests/test_gpu_conv_epilogue.py).  No lower limit: operands
  * below 2^-14 are kept as fp16 subnormals (steps of 2^-24, zero below 2^-25) by the staging's conversion and multiplied as such by the
  * matrix cores (tests/test_gpu_conv_range_f16.py, regimes `w_sub` / `x_sub` / `edge`). */
 int savsr_conv2d_batch_f16(const savsr_conv_desc* descs, int n, void* stream);

@@ -728,9 +728,10 @@ __global__ __launch_bounds__(512) void conv_bf16x3_kernel(const MultiConvParams 
                 const int pidx = y * W + x;
                 const f32x4 a4 = *reinterpret_cast<const f32x4*>(ep + pl * EPS + 4 * c4);
                 float v[4] = {a4[0] + b4[0], a4[1] + b4[1], a4[2] + b4[2], a4[3] + b4[3]};
-                if (e_act == SAVSR_ACT_RELU) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.f);
+                if (e_act == SAVSR_ACT_NONE) {
+                } else if (act_as_max) {             // the max form of the path above, not fmaxf(v, 0) / a select: the same bits for every
+#pragma unroll                                       // finite v (up to the sign of a ReLU zero), and a non-finite accumulator (fp16 mode)
+                    for (int q = 0; q < 4; ++q) v[q] = vmax_raw(v[q], v[q] * slope_eff);      // keeps its class on both paths (savsr_hip.h)
                 } else if (e_act == SAVSR_ACT_LRELU) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) v[q] = v[q] > 0.f ? v[q] : v[q] * e_slope;
