@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 53
+#define SAVSR_ABI_VERSION 54
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -846,6 +846,32 @@ int savsr_video_grid_stats_u8(const uint8_t* frames, int n_frames, int64_t frame
                               int interlaced, int cap, int64_t* out, void* stream);
 int savsr_video_grid_stats_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step, int depth,
                                int interlaced, int cap, int64_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 54) Deringing (dering.hip; savsr_amd.dering_video, upscale_video(dering="cdef", ...), VideoUpscaler(dering=...), --dering of
+ * python -m savsr_amd.upscale): per 8 x 8 block of the plane (the grid starts at the plane's origin, the last blocks
+ * may be partial) a direction search on eight sets of line sums, then for every sample a constrained filter of four taps along the
+ * block's direction (strength P, scaled by the block's directional variance) and eight taps across it (strength S), the result clamped
+ * to the minimum and maximum of the sample and the taps read, in integers, every frame on its own (savsr_amd/dering.py `dering_matrix` /
+ * `dering_fields` restate it; the kernels equal them bit for bit).  Planes are addressed as for savsr_video_deblock_*: rows rows of
+ * cols * step samples, sample x meeting x +- j * step only; the output frames are laid out the same way and only the plane is written
+ * (out of place).  interlaced: 1 filters the rows 0::2 and 1::2 as planes of their own, each with its own blocks and clamp.  pri, sec:
+ * the strengths p and s in the depth's codes, multiples of 1 << (depth - 8), 0 .. 15 << (depth - 8) and 0 .. 4 << (depth - 8); both 0
+ * copies min(s, top).  damping: 3 .. 6 in 8-bit code units (depth - 8 is added inside).
+ * One launch for all frames (at most 65535 a launch): a workgroup stages a tile of 32 rows x 256 / step pixels (64 at step 3) plus a halo
+ * of 2 samples and 2 field rows in LDS, finds dir and the primary strength once per block into LDS, filters from LDS and writes once.
+ * Refused (SAVSR_E_ARG, before anything is launched, the message naming the entry): a null pointer, n_frames < 1, rows < 1, cols < 1,
+ * a step outside 1 .. 4, a plane above 2147418112 bytes, a negative plane offset, a frame stride smaller than the offset plus the plane
+ * (either side), interlaced other than 0 / 1, a strength out of range or not a multiple of 1 << (depth - 8), a damping outside 3 .. 6,
+ * overlapping source and output; _u16: a depth other than 10 / 12, an odd pointer, stride or offset.
+ * savsr_video_dering_u8:  planes of rows x (cols * step) bytes.
+ * savsr_video_dering_u16: the same in little-endian 16-bit samples, every one read as min(s, 2^depth - 1). */
+int savsr_video_dering_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step,
+                          int interlaced, int pri, int sec, int damping, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
+                          void* stream);
+int savsr_video_dering_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step, int depth,
+                           int interlaced, int pri, int sec, int damping, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 45) Video surfaces (surface.hip; savsr_amd.unpack_surface, savsr_amd.pack_surface, upscale_video(surface=..., out_surface=...),

@@ -288,7 +288,8 @@ class SAVSR(nn.Module):
                       denoise_chroma_strength=None, spatial_denoise: Optional[str] = None, spatial_patch: int = 3, spatial_search: int = 7,
                       spatial_strength=3.0, spatial_chroma_strength=None, deblock: Optional[str] = None, deblock_block: int = 8,
                       deblock_strength=(25, 13), deblock_chroma_strength=None, deblock_origin=(0, 0), deblock_chroma_origin=None,
-                      deblock_grid: Optional[str] = None) -> torch.Tensor:
+                      deblock_grid: Optional[str] = None, dering: Optional[str] = None, dering_strength=(4, 2),
+                      dering_chroma_strength=None, dering_damping: int = 5) -> torch.Tensor:
         """A whole LR video -> its SR video.  frames: [N, c, h, w] float on the GPU, or [N, h, w, c] uint8 on the GPU or the host
         (c = num_in_ch).  Frame i is SAVSR.forward on its num_frame window by generate_frame_indices with `padding` (replicate,
         reflection, reflection_circle, circle; lbasicsr/data/data_util.py:63-112).  scale: a number or (sh, sw), default set_scale's.
@@ -453,8 +454,27 @@ class SAVSR(nn.Module):
         an origin other than the defaults.  The detector's rule and defaults are this project's own and are not validated on footage;
         grids of scaled video, block sizes other than 4 / 8 / 16 and block 4 on noise-free material are not found, and periodic
         picture content can fake a grid.  One grid and one strength per video, no adaptation to the stream's quantiser,
-        ringing and mosquito noise are not addressed.  The defaults are ffmpeg deblock's thresholds as parameters: nothing is
+        ringing and mosquito noise are left to dering= (next).  The defaults are ffmpeg deblock's thresholds as parameters: nothing is
         validated on footage or on trained weights, and nothing is pinned to ffmpeg's output.
+        dering, dering_strength, dering_chroma_strength, dering_damping (keyword only): deringing in front of the network, for the
+        oscillations a coarsely quantised 8 x 8 DCT puts around every sharp edge inside a block (ringing, mosquito noise), which the
+        deblocker and both denoisers leave and a x4 network enlarges as texture.  dering: None (the default: what ran before) or
+        "cdef": every 8 x 8 block of a plane, on a grid at the plane's origin, gets one of eight directions from its line sums; every
+        sample then moves by a constrained sum of four taps along its block's direction and eight across it, clamped to the minimum
+        and maximum of the sample and its taps.  dering_strength = (p, s), ints 0 <= p <= 15 (along; scaled by the block's directional
+        variance, nothing on a flat block) and 0 <= s <= 4 (across), default (4, 2); dering_damping, an int in 3 .. 6, default 5: a
+        tap whose difference is large against its strength counts less, then not at all; all in 8-bit code units at every depth
+        (savsr_amd/dering.py is the rule in integers; the idea is that of AV1's CDEF, the definition this project's).  Chroma planes
+        take dering_chroma_strength (None: the same); every channel of packed frames is a plane of its own.  Ringing belongs to the
+        coded frame as the block grid does, and codecs dering after they deblock: the stage runs right behind deblock= on the frames
+        as decoded -- after surface= unpacking and after scan="detect" and deblock_grid="auto" have read their frames, in front of
+        fields= / pulldown=, denoise=, the crop, spatial_denoise= and the cuts -- field by field (each field with blocks of its own)
+        exactly when the deblocker would.  The result is, bit for bit, upscale_video on savsr_amd.dering_video(
+        savsr_amd.deblock_video(frames, ...), ..., interlaced=I) with every other argument the same.  uint8 and planar frames only;
+        the dering_ options are refused without dering=.  One strength per video and no per-block signalling such as a bitstream
+        carries; the 8 x 8 analysis grid starts at the plane's origin and does not follow deblock_origin; chroma gets a direction of
+        its own rather than the luma's; the stage also smooths fine noise.  The defaults are parameters: nothing is validated on
+        footage or on trained weights, and nothing is pinned to libaom's or ffmpeg's output.
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video
@@ -466,7 +486,8 @@ class SAVSR(nn.Module):
                              spatial_denoise=spatial_denoise, spatial_patch=spatial_patch, spatial_search=spatial_search,
                              spatial_strength=spatial_strength, spatial_chroma_strength=spatial_chroma_strength, deblock=deblock,
                              deblock_block=deblock_block, deblock_strength=deblock_strength, deblock_chroma_strength=deblock_chroma_strength,
-                             deblock_origin=deblock_origin, deblock_chroma_origin=deblock_chroma_origin, deblock_grid=deblock_grid)
+                             deblock_origin=deblock_origin, deblock_chroma_origin=deblock_chroma_origin, deblock_grid=deblock_grid, dering=dering,
+                             dering_strength=dering_strength, dering_chroma_strength=dering_chroma_strength, dering_damping=dering_damping)
 
     def forward(self, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.training:

@@ -5,7 +5,8 @@ all of them, `pack_surface` behind everything; savsr_amd/surface.py is its speci
 (`FieldSplitter`, `PulldownRemover`; `make_stage` builds the one a call asks for; `ScanStats` is the detector's streaming form), and the temporal
 denoiser behind them is a third (`denoise_video`, `TemporalDenoiser`, `make_denoiser`; savsr_amd/denoise.py is its specification); the spatial
 denoiser behind the crop is stateless (`denoise_spatial`; savsr_amd/nlmeans.py is its specification), and so is the deblocking stage on the
-frames as decoded, in front of all of these but the surface conversion and the scan detector (`deblock_video`; savsr_amd/deblock.py).  The
+frames as decoded, in front of all of these but the surface conversion and the scan detector (`deblock_video`; savsr_amd/deblock.py), with
+the deringing stage right behind it (`dering_video`; savsr_amd/dering.py).  The
 numpy modules (scenes.py, active.py, deinterlace.py, pulldown.py, scan.py) are the specifications, bit for bit.  Where the byte matrices of a frame lie is `frames.plane_table`'s
 answer alone; fp32 CHW frames have entries of their own (`_f32`) and are one explicit branch in the two stages that accept them.
 """
@@ -19,6 +20,7 @@ import torch
 from . import active
 from . import deblock as db
 from . import denoise as dn
+from . import dering as dr
 from . import grid as gr
 from . import nlmeans as nl
 from . import pulldown as pd
@@ -653,6 +655,46 @@ def deblock_video(frames: torch.Tensor, pixel_format: str = "rgb", size=None, de
     origin, chroma_origin = db.check_origins(origin, chroma_origin, block, interlaced, layout_of(pixel_format) if size else None)
     frames, side, size = _stage_args(frames, pixel_format, size, depth, lambda f, s, z: _sample_frames(f, s, z, "deblock"))
     return _deblock_device(frames, side, size, block, mode, strength, chroma_strength, interlaced, origin, chroma_origin)
+
+
+# ---- deringing (savsr_amd/dering.py is the specification) -----------------------------------------------------------------------------------
+def _dering_device(frames: torch.Tensor, side: Side, size: Size, strength=dr.DEFAULT_STRENGTH, chroma_strength=None,
+                   damping: int = dr.DEFAULT_DAMPING, interlaced: bool = False) -> torch.Tensor:
+    """savsr_video_dering_* on resident frames of the input side on the GPU: as many filtered frames, every frame on its own.  One call
+    (one launch) per plane, on the current stream (no sync): the Y plane with `strength`, the chroma planes with `chroma_strength`
+    (None: `strength`), the strengths shifted to the depth here; packed frames in one call, every channel a plane of its own (the
+    channel count is the entry's sample step).  interlaced: every plane field by field."""
+    n, c, h, w = _sample_frames(frames, side, size, "dering")
+    frames, tab = frames.contiguous(), plane_table(side, size, c, h, w)
+    out = torch.empty_like(frames)
+    step, shift = max(c, 1), side.depth - 8
+    for i, p in enumerate(tab.planes if n else ()):
+        pri, sec = strength if i == 0 or chroma_strength is None else chroma_strength
+        head = (p.row_bytes // (tab.sample * step), step) + (() if tab.sample == 1 else (side.depth,))
+        _entry_call("savsr_video_dering_u8" if tab.sample == 1 else "savsr_video_dering_u16", frames, n, tab, p, head,
+                    (int(bool(interlaced)), pri << shift, sec << shift, damping, out.data_ptr(), tab.stride, p.offset))
+    return out
+
+
+def dering_video(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8, strength=dr.DEFAULT_STRENGTH, chroma_strength=None,
+                 damping: int = dr.DEFAULT_DAMPING, interlaced: bool = False) -> torch.Tensor:
+    """Deringing: N frames on the GPU in the format of the N given ones (savsr_amd.dering.dering_frames is the specification, bit for
+    bit), on the caller's current stream, without a sync.  Every frame is filtered on its own: every 8 x 8 block of a plane (the grid
+    starts at the plane's origin) gets a direction from eight sets of line sums, and every sample moves by a constrained sum of four taps
+    along its block's direction and eight across it -- strength = (p, s), 0 <= p <= 15 along (scaled by the block's directional
+    variance; nothing on a flat block) and 0 <= s <= 4 across, damping 3 .. 6, all in 8-bit code units at every depth -- clamped to the
+    minimum and maximum of the sample and its taps.  interlaced=True filters the two fields as planes of their own, each with its own
+    blocks, so that no filter mixes two moments.  frames as for `deblock_video`: [N, h, w, c] uint8 (GPU or host; every channel a
+    plane of its own), or with pixel_format "i420", "i422", "i444", "y400" and size=(h, w): [N, frame_bytes] uint8, every plane on its
+    own, 16-bit samples at depth 10 / 12, the chroma planes with `chroma_strength` (None: `strength`).  Float frames are refused.  A
+    constant plane comes back as it is, (0, 0) is the identity and no sample moves by more than (12 (p + s) + 8) >> 4 codes (shifted
+    to the depth).  The defaults ((4, 2), damping 5) are parameters: nothing is validated on footage.  The grid does not follow a
+    deblocker's origin, chroma gets a direction of its own, and the stage also smooths fine noise."""
+    strength = dr.check_strength(strength)
+    chroma_strength = None if chroma_strength is None else dr.check_strength(chroma_strength, "chroma_strength")
+    damping = dr.check_damping(damping)
+    frames, side, size = _stage_args(frames, pixel_format, size, depth, lambda f, s, z: _sample_frames(f, s, z, "dering"))
+    return _dering_device(frames, side, size, strength, chroma_strength, damping, interlaced)
 
 
 # ---- the block grid (savsr_amd/grid.py is the specification) --------------------------------------------------------------------------------

@@ -16,6 +16,7 @@
     ffmpeg -i vhs_capture.avi -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out.y4m --scale 4 --checkpoint <net.pth> --fields auto --denoise ata --denoise-strength 4,9
     ffmpeg -i grainy_sd.avi -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out.y4m --scale 4 --checkpoint <net.pth> --spatial-denoise nlm --spatial-strength 3
     python -m savsr_amd.upscale -i blocky_dvd.y4m -o out.y4m --scale 4 --checkpoint <net.pth> --scan detect --deblock strong --deblock-strength 25,13
+    python -m savsr_amd.upscale -i ringing_dvd.y4m -o out.y4m --scale 4 --checkpoint <net.pth> --deblock strong --dering cdef --dering-strength 4,2
     ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 -f yuv4mpegpipe - | python -m savsr_amd.upscale -i - -o out444p10.y4m --scale 4 --checkpoint <net.pth> --out-chroma 444
 
 PNG folder: frames are taken in the order read_img_seq reads a folder (sorted scandir, lbasicsr/data/data_util.py:29-60), decoded on
@@ -156,6 +157,19 @@ stdin and together with --deblock-block / --deblock-origin.  The detector's rule
 validated on footage; grids of scaled video, other block sizes and block 4 on noise-free material are not found.  One grid and one strength per video, no adaptation to the stream's quantiser; the
 defaults are parameters, nothing is validated on footage and nothing is pinned to ffmpeg's deblock.
 
+--dering cdef: the ringing and mosquito noise a coarsely quantised 8 x 8 DCT puts around sharp edges, which --deblock and both denoisers
+leave.  On the GPU, every frame on its own: every 8 x 8 block of a plane (the grid starts at the plane's origin) gets one of eight
+directions from its line sums, and every sample moves by a constrained sum of four taps along its block's direction and eight across it,
+clamped to the minimum and maximum of the sample and its taps (--dering-strength P,S in 8-bit code units at every depth, default 4,2,
+0 <= P <= 15 along and 0 <= S <= 4 across; --dering-damping N, default 5, 3 .. 6: a tap whose difference is large against its strength
+counts less; savsr_amd/dering.py; the idea is that of AV1's CDEF, the definition this project's); --dering-chroma-strength P,S sets the
+chroma planes of a Y4M input apart.  Ringing belongs to the coded frame, so the stage runs on the frames as read right behind --deblock,
+in front of --fields / --pulldown, --denoise, --crop (auto reads the filtered frames), --spatial-denoise and --cuts, and field by field
+where the video is treated as interlaced, as --deblock does.  No frame is held back, and one line on stderr names the stage, its
+parameters and whether it ran field-wise.  Works for PNG folders and for .y4m files and pipes.  One strength per video, no per-block
+signalling such as a bitstream carries, the 8 x 8 grid does not follow --deblock-origin, chroma gets a direction of its own, fine noise
+is smoothed too; the defaults are parameters, nothing is validated on footage and nothing is pinned to libaom's or ffmpeg's output.
+
 It ends with one line: frames, seconds, frames/s (on stderr when the video goes to stdout); with --cuts, the scene count as well; with
 --colour / --out-colour, the two colour spaces.
 """
@@ -171,6 +185,7 @@ from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional
 
 from . import deblock as dbk
+from . import dering as drg
 from .denoise import DEFAULT_RADIUS, DEFAULT_STRENGTH, DENOISERS, MAX_RADIUS, check_radius, check_strength
 from .dither import DITHERS
 from . import nlmeans as nlm
@@ -349,6 +364,17 @@ def build_parser() -> argparse.ArgumentParser:
                         f"every depth (default {dbk.DEFAULT_STRENGTH[0]},{dbk.DEFAULT_STRENGTH[1]}; ints in 0 .. 255; not validated on footage)")
     p.add_argument("--deblock-chroma-strength", default=None, metavar="A,B",
                    help="--deblock: the same for the chroma planes of a Y4M input (default: --deblock-strength)")
+    p.add_argument("--dering", default=None, choices=["none"] + list(drg.DERINGERS),
+                   help="deringing on the GPU in front of the network, on the frames as read, right behind --deblock.  cdef: a direction per "
+                        "8 x 8 block, a constrained filter along and across it; none (default): the frames go through as they are")
+    p.add_argument("--dering-strength", default=None, metavar="P,S",
+                   help=f"--dering: the strength along a block's direction (0 .. {drg.MAX_PRIMARY}) and across it (0 .. {drg.MAX_SECONDARY}), in "
+                        f"8-bit code units at every depth (default {drg.DEFAULT_STRENGTH[0]},{drg.DEFAULT_STRENGTH[1]}; not validated on footage)")
+    p.add_argument("--dering-chroma-strength", default=None, metavar="P,S",
+                   help="--dering: the same for the chroma planes of a Y4M input (default: --dering-strength)")
+    p.add_argument("--dering-damping", type=int, default=None, metavar="N",
+                   help=f"--dering: a tap whose difference is large against its strength counts less, then not at all; larger N lets larger "
+                        f"differences count (default {drg.DEFAULT_DAMPING}; {drg.MIN_DAMPING} .. {drg.MAX_DAMPING})")
     p.add_argument("--scan", default=None, choices=list(SCAN_FLAGS),
                    help="detect: find out from the content, in a first pass over the input (a file or a folder), whether it is progressive, "
                         "interlaced or telecined film and with which field order, then run as --fields X / --pulldown X would; the verdict "
@@ -415,6 +441,17 @@ def parse_deblock_strength(text: str, what: str):
     if len(pair) != 2:
         raise ValueError(f"{what}: A,B, got {text!r}")
     return dbk.check_strength(pair, what)
+
+
+def parse_dering_strength(text: str, what: str):
+    """--dering-strength / --dering-chroma-strength: "P,S" -> the checked (p, s)."""
+    try:
+        pair = tuple(int(t.strip()) for t in text.split(","))
+    except ValueError:
+        raise ValueError(f"{what}: P,S with integers, got {text!r}") from None
+    if len(pair) != 2:
+        raise ValueError(f"{what}: P,S, got {text!r}")
+    return drg.check_strength(pair, what)
 
 
 def parse_cuts(text: str):
@@ -577,6 +614,20 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             a.deblock_origin = (0, 0) if a.deblock_origin is None else parse_deblock_origin(a.deblock_origin, a.deblock_block, "--deblock-origin")
             if a.deblock_chroma_origin is not None:
                 a.deblock_chroma_origin = parse_deblock_origin(a.deblock_chroma_origin, a.deblock_block, "--deblock-chroma-origin")
+        except ValueError as e:
+            p.error(str(e))
+    a.dering = None if a.dering == "none" else a.dering
+    if a.dering is None:
+        if any(v is not None for v in (a.dering_strength, a.dering_chroma_strength, a.dering_damping)):
+            p.error("--dering-strength, --dering-chroma-strength and --dering-damping go with --dering cdef")
+    else:
+        if a.dering_chroma_strength is not None and not a.y4m_in:
+            p.error("--dering-chroma-strength goes with a Y4M input (PNG frames are RGB: every channel takes --dering-strength)")
+        try:
+            a.dering_strength = drg.DEFAULT_STRENGTH if a.dering_strength is None else parse_dering_strength(a.dering_strength, "--dering-strength")
+            if a.dering_chroma_strength is not None:
+                a.dering_chroma_strength = parse_dering_strength(a.dering_chroma_strength, "--dering-chroma-strength")
+            a.dering_damping = drg.check_damping(drg.DEFAULT_DAMPING if a.dering_damping is None else a.dering_damping, "--dering-damping")
         except ValueError as e:
             p.error(str(e))
     try:
@@ -774,6 +825,14 @@ def deblock_kwargs(a: argparse.Namespace) -> dict:
     return kw
 
 
+def dering_kwargs(a: argparse.Namespace) -> dict:
+    """--dering and its options as the keyword arguments of VideoUpscaler; nothing without --dering."""
+    if a.dering is None:
+        return {}
+    return dict(dering=a.dering, dering_strength=a.dering_strength, dering_chroma_strength=a.dering_chroma_strength,
+                dering_damping=a.dering_damping)
+
+
 def detect_grid_pass(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev, fieldwise: bool):
     """--deblock-grid auto's first pass: savsr_amd.grid_stats over the input in --chunk-sized pieces, summed on the device (one copy of 64
     integers at the end), then grid.verdict_from_stats.  It reads the frames the deblocker will read -- as decoded, field-wise exactly
@@ -815,12 +874,12 @@ def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, de
     named by --input, read through a reader of its own.  order: --fields' field order; the sums are then taken on the deinterlaced frames
     (a prepass.FieldSplitter of this pass's own), as the second pass will crop them.  film: --pulldown's field order; the sums are then taken
     on the recovered film frames (a prepass.PulldownRemover of this pass's own).  --deblock: the chunks are filtered first, field by field
-    with either, as the second pass will filter them."""
+    with either, as the second pass will filter them; --dering likewise, behind it."""
     import torch
 
     from . import active
     from .frames import detector_side, layout_of
-    from .prepass import deblock_video, line_sums, make_denoiser, make_stage
+    from .prepass import deblock_video, dering_video, line_sums, make_denoiser, make_stage
     from .y4m import Y4MReader
     from .yuv import CHROMAS
     top = None
@@ -854,6 +913,9 @@ def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, de
                 if a.deblock is not None:
                     chunk = deblock_video(chunk, fmt_in, size, depth, a.deblock_block, a.deblock, a.deblock_strength, a.deblock_chroma_strength,
                                           order is not None or film is not None, a.deblock_origin, a.deblock_chroma_origin)
+                if a.dering is not None:
+                    chunk = dering_video(chunk, fmt_in, size, depth, a.dering_strength, a.dering_chroma_strength, a.dering_damping,
+                                         order is not None or film is not None)
                 fold(chunk if split is None else split.push(chunk))
             last = None if split is None else split.finish()
             if last is not None:
@@ -1100,7 +1162,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                            # (--combed with --scan detect says how a telecine verdict is carried out: ignored for the other verdicts)
                            **(dict(combed=a.combed, comb_threshold=a.comb_threshold, comb_pixels=a.comb_pixels)
                               if film is not None and a.combed is not None else {}),
-                           **denoise_kwargs(a), **spatial_kwargs(a), **deblock_kwargs(a))
+                           **denoise_kwargs(a), **spatial_kwargs(a), **deblock_kwargs(a), **dering_kwargs(a))
         if a.deblock is not None:
             cs = a.deblock_chroma_strength or a.deblock_strength
             at = "" if a.deblock_origin == (0, 0) and a.deblock_chroma_origin is None else (
@@ -1109,6 +1171,12 @@ def main(argv: Optional[List[str]] = None) -> int:
             print(f"--deblock {a.deblock}: block {a.deblock_block}{at}, strength {a.deblock_strength[0]},{a.deblock_strength[1]}"
                   + (f", chroma strength {cs[0]},{cs[1]}" if a.y4m_in else "") + " (8-bit code units; not validated on footage), "
                   + ("field-wise (the fields as planes of their own)" if order is not None or film is not None else "progressive"),
+                  file=sys.stderr, flush=True)
+        if a.dering is not None:
+            cs = a.dering_chroma_strength or a.dering_strength
+            print(f"--dering {a.dering}: strength {a.dering_strength[0]},{a.dering_strength[1]}"
+                  + (f", chroma strength {cs[0]},{cs[1]}" if a.y4m_in else "") + f", damping {a.dering_damping} (8-bit code units; not validated on "
+                  + "footage), " + ("field-wise (the fields as planes of their own)" if order is not None or film is not None else "progressive"),
                   file=sys.stderr, flush=True)
         if a.spatial_denoise is not None:
             ch = a.spatial_strength if a.spatial_chroma_strength is None else a.spatial_chroma_strength

@@ -54,6 +54,12 @@ call is, bit for bit, the call with `verdict.kwargs()` given, and with a "no gri
 grid was not found at the luma's block are left alone (chroma threshold a = 0).  One grid per video; the rule's defaults are this
 project's own and are not validated on footage.
 
+dering="cdef": deringing (savsr_amd/dering.py: a direction per 8 x 8 block, a constrained filter along and across it, every frame on its
+own).  Ringing belongs to the coded frame as the block grid does, and codecs dering after they deblock: the stage runs right behind
+deblock= on the frames as decoded -- after surface= unpacking and after scan="detect" and deblock_grid="auto" have read their frames, in
+front of fields= / pulldown=, denoise=, the crop, spatial_denoise= and the cuts -- and field by field exactly when the deblocker would.
+The call is, bit for bit, the call on `dering_video(deblock_video(v, ...), ..., interlaced=I)`.  None runs the lines that ran before.
+
 dither="ordered": every quantiser behind the network (packed uint8, planar YUV, the luma-only path's Y plane) takes floor(t + theta(y, x))
 in rint's place, theta from a 16 x 16 Bayer matrix at the sample's position in its plane (savsr_amd/dither.py is the specification, the
 `_d` entries of the C ABI the kernels).  It belongs to the quantiser: bars="keep" inserts exact nominal black after it and out_surface
@@ -80,11 +86,12 @@ from .harness import window_indices
 from .packing import get_hw
 from .deblock import check_deblock_options, check_origins
 from .denoise import check_denoise_options
+from .dering import check_dering_options
 from .nlmeans import check_spatial_options
 from .prepass import (FieldSplitter, PulldownRemover, ScanStats, TemporalDenoiser, _check_crop_args, _check_field_options, _check_fields,  # noqa: F401  (re-exported)
-                      _check_pulldown, _check_scan, _crop_device, _cropped_spec, _deblock_device, _deinterlace_device, _denoise_device, _denoise_frames, _denoise_spatial_device,
+                      _check_pulldown, _check_scan, _crop_device, _cropped_spec, _deblock_device, _deinterlace_device, _dering_device, _denoise_device, _denoise_frames, _denoise_spatial_device,
                       _detect_device, _detect_grid_device, _detect_scan_device, _field_frames, _insert_device, _pair_sad_device, _pack_surface_device,
-                      _remove_pulldown_device, _sample_frames, _to_device, _unpack_surface_device, comb_windows, deblock_video, deinterlace, denoise_spatial, denoise_video,
+                      _remove_pulldown_device, _sample_frames, _to_device, _unpack_surface_device, comb_windows, deblock_video, deinterlace, denoise_spatial, denoise_video, dering_video,
                       detect_active_area, detect_cuts, detect_grid, detect_scan, field_scores, field_stats, grid_stats, line_sums, make_denoiser, make_stage,
                       pack_surface, pair_sad, remove_pulldown, surface_layout, surface_side, surface_table, unpack_surface)
 from .pulldown import check_comb_options
@@ -133,7 +140,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
                   denoise: Optional[str] = None, denoise_radius: int = 4, denoise_strength=(4, 9), denoise_chroma_strength=None,
                   spatial_denoise: Optional[str] = None, spatial_patch: int = 3, spatial_search: int = 7, spatial_strength=3.0,
                   spatial_chroma_strength=None, deblock: Optional[str] = None, deblock_block: int = 8, deblock_strength=(25, 13),
-                  deblock_chroma_strength=None, deblock_origin=(0, 0), deblock_chroma_origin=None, deblock_grid: Optional[str] = None) -> torch.Tensor:
+                  deblock_chroma_strength=None, deblock_origin=(0, 0), deblock_chroma_origin=None, deblock_grid: Optional[str] = None,
+                  dering: Optional[str] = None, dering_strength=(4, 2), dering_chroma_strength=None, dering_damping: int = 5) -> torch.Tensor:
     """SAVSR.upscale_video (see there)."""
     _check_net(net)
     check_padding(padding)
@@ -144,6 +152,7 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     grain = check_spatial_options(spatial_denoise, spatial_patch, spatial_search, spatial_strength, spatial_chroma_strength)          # likewise
     edges = check_deblock_options(deblock, deblock_block, deblock_strength, deblock_chroma_strength, origin=deblock_origin,
                                   chroma_origin=deblock_chroma_origin, grid=deblock_grid)          # likewise
+    rings = check_dering_options(dering, dering_strength, dering_chroma_strength, dering_damping)          # likewise
     grid = None          # (origin, chroma origin) of the deblocker's grid, or "auto": found below, on the frames the deblocker will read
     if edges is not None:              # (an odd oy is refused here where the run is known to be field-wise, and below once scan= has said so)
         grid = "auto" if deblock_grid == "auto" else check_origins(deblock_origin, deblock_chroma_origin, edges[0], fields is not None or pulldown
@@ -160,6 +169,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         surface_side(out_surface, spec.out, "out_surface")
     if edges is not None:              # (integer samples only, and the stage comes first: its refusal of float frames speaks first)
         _sample_frames(shaped, spec.inp, spec.size, "deblock")
+    if rings is not None:
+        _sample_frames(shaped, spec.inp, spec.size, "dering")
     if noise is not None or grain is not None:          # (integer samples only: float frames are refused here, before the GPU is touched)
         _denoise_frames(shaped, spec.inp, spec.size)
     # (deinterlacer= / field_rate= also go with scan="detect": they say how an interlaced verdict is carried out)
@@ -210,6 +221,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
             grid = check_origins(*grid, edges[0], fieldwise, spec.inp.layout, "deblock_")
         if edges is not None:
             frames = _deblock_device(frames, spec.inp, spec.size, *edges, fieldwise, *grid)
+    if rings is not None:              # ringing belongs to the frames as decoded too: right behind the deblocker, field by field when it would be
+        frames = _dering_device(frames, spec.inp, spec.size, *rings, fields is not None or pulldown is not None)
     if fields is not None:             # deinterlacing comes first, before the crop
         frames = _deinterlace_device(frames, fields, spec.inp, spec.size, method=deinterlacer, rate=field_rate)
     if pulldown is not None:           # pulldown removal comes first, where deinterlacing comes
@@ -318,6 +331,11 @@ class VideoUpscaler:
     decision needs the video.  Run savsr_amd.detect_grid on a probe chunk (or sum savsr_amd.grid_stats over a first pass, as
     python -m savsr_amd.upscale --deblock-grid auto does) and give `verdict.kwargs()`.
 
+    dering="cdef", dering_strength=(4, 2), dering_chroma_strength=None, dering_damping=5 (keyword only): deringing, as in upscale_video,
+    on every pushed chunk right behind the deblocker (in front of the fields= / pulldown= stage), field by field exactly when fields= or
+    pulldown= is given.  The stage is stateless -- every frame is filtered on its own -- so it holds nothing back and any chunking
+    gives the same frames.  The defaults are parameters: nothing is validated on footage.
+
     scan="detect" is refused: the decision needs the video.  Run savsr_amd.detect_scan on a probe chunk (or prepass.ScanStats over a
     first pass, as python -m savsr_amd.upscale --scan detect does) and give its answer as fields= / pulldown=."""
 
@@ -331,7 +349,8 @@ class VideoUpscaler:
                  denoise_chroma_strength=None, spatial_denoise: Optional[str] = None, spatial_patch: int = 3, spatial_search: int = 7,
                  spatial_strength=3.0, spatial_chroma_strength=None, deblock: Optional[str] = None, deblock_block: int = 8,
                  deblock_strength=(25, 13), deblock_chroma_strength=None, deblock_origin=(0, 0), deblock_chroma_origin=None,
-                 deblock_grid: Optional[str] = None):
+                 deblock_grid: Optional[str] = None, dering: Optional[str] = None, dering_strength=(4, 2), dering_chroma_strength=None,
+                 dering_damping: int = 5):
         _check_net(net)
         check_padding(padding)
         _check_scan(scan, fields, pulldown, pulldown_cycle, auto_ok=False)          # (None is the only value that passes: the path as it was)
@@ -363,6 +382,8 @@ class VideoUpscaler:
         self._fieldwise = fields is not None or pulldown is not None
         self._grid = None if self._edges is None else check_origins(deblock_origin, deblock_chroma_origin, self._edges[0], self._fieldwise,
                                                                     self.spec.inp.layout, "deblock_")
+        # deringing, right behind it: stateless, field by field when the deblocker would be; None: as it was
+        self._rings = check_dering_options(dering, dering_strength, dering_chroma_strength, dering_damping)
         self._rect = _check_crop_args(crop, 24, bars, auto_ok=False)          # the rect to crop every chunk to; None: no crop, as it was
         self.bars = bars
         if self._rect is not None and self.spec.size:
@@ -457,6 +478,8 @@ class VideoUpscaler:
         staged = self._split is not None
         if self._edges is not None:
             _sample_frames(frames, self._full.inp, self._full.size, "deblock")
+        if self._rings is not None:
+            _sample_frames(frames, self._full.inp, self._full.size, "dering")
         if staged:
             _field_frames(frames, self._full.inp, self._full.size)
         if self._noise is not None or self._grain is not None:
@@ -487,6 +510,8 @@ class VideoUpscaler:
             self._set_out_tab(self._out_surface, *self._shape[1:])
         if self._edges is not None:                # the frames as decoded, filtered one by one: no frame is held for it
             new = _deblock_device(new, self._full.inp, self._full.size, *self._edges, self._fieldwise, *self._grid)
+        if self._rings is not None:                # right behind the deblocker, stateless as well
+            new = _dering_device(new, self._full.inp, self._full.size, *self._rings, self._fieldwise)
         if self._split is not None:                # interlaced / telecined chunks: the progressive frames that are final go on as a chunk of their own
             new = self._split.push(new)
             if int(new.shape[0]) == 0:             # (a first push of one frame, or a cycle not complete yet: nothing is final)
