@@ -58,4 +58,10 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// One level of the tail's bilinear residual, (1 - l) a + l b, with its roundings written out: l b rounds, the sum is ONE fma.  Left as
+// `(1.f - l) * a + l * b` the contraction is the compiler's choice per instantiation: the 16-byte paths of tail.hip got this form, the
+// one-pixel paths (and satu_nf.hip's tail) had their two products packed into a v_pk_mul_f32 and added unfused, and the same planes gave
+// outputs up to 4 ulp apart depending on the alignment of a pointer (tests/test_gpu_tail.py).
+__device__ __forceinline__ float lerp_fma(float l, float a, float b) { return __builtin_fmaf(1.f - l, a, l * b); }
+
 }  // namespace savsr

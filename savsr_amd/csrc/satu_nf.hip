@@ -322,8 +322,8 @@ __global__ __launch_bounds__(256) void satu_nf_hr_kernel(const NfHrParams p) {
 
 // What is left of savsr_arch.py:738-739 for an nch-channel tail (nch = num_in_ch in 1 .. 3) after an NP = 9 nch HR stage:
 //     out[o][Y][X] = tail_b[o] + sum_{ky,kx} P[nch (3 ky + kx) + o][Y + ky - 1][X + kx - 1]  (zero outside)  + bilinear(center[o])
-// One thread = one pixel of one output channel (grid z = nch), summed in savsr_tail_gather's order (ky, then kx); at nch = 3 the two
-// agree to rounding.
+// One thread = one pixel of one output channel (grid z = nch), summed in savsr_tail_gather's order (ky, then kx) with the residual's
+// roundings written out (lerp_fma): at nch = 3 the two agree bit for bit.
 __device__ __forceinline__ void nf_bil_src(int dst, float scale, int in_size, int& i0, int& i1, float& l1) {
     float s = scale * ((float)dst + 0.5f) - 0.5f;                      // area_pixel_compute_source_index (F.interpolate, align_corners=False)
     if (s < 0.f) s = 0.f;
@@ -355,9 +355,9 @@ __global__ __launch_bounds__(256) void tail_gather_nch_kernel(const float* __res
     nf_bil_src(Y, (float)h / (float)H, h, y0, y1, ly);
     nf_bil_src(X, (float)w / (float)W, w, x0, x1, lx);
     const float* c = center + (long long)o * h * w;
-    const float top = (1.f - lx) * c[y0 * w + x0] + lx * c[y0 * w + x1];
-    const float bot = (1.f - lx) * c[y1 * w + x0] + lx * c[y1 * w + x1];
-    out[(long long)o * H * W + (long long)Y * W + X] = (acc + bias[o]) + ((1.f - ly) * top + ly * bot);
+    const float top = lerp_fma(lx, c[y0 * w + x0], c[y0 * w + x1]);
+    const float bot = lerp_fma(lx, c[y1 * w + x0], c[y1 * w + x1]);
+    out[(long long)o * H * W + (long long)Y * W + X] = (acc + bias[o]) + lerp_fma(ly, top, bot);
 }
 
 template <int C>

@@ -124,9 +124,9 @@ __global__ __launch_bounds__(256) void tail_kernel(const float* __restrict__ fea
 #pragma unroll
         for (int o = 0; o < 3; ++o) {
             const float* c = center + (long long)o * h * w;
-            const float top = (1.f - lx) * c[y0 * w + x0] + lx * c[y0 * w + x1];
-            const float bot = (1.f - lx) * c[y1 * w + x0] + lx * c[y1 * w + x1];
-            out[(long long)o * HW + (long long)Y * W + X] = (a[q][o] + bias[o]) + ((1.f - ly) * top + ly * bot);
+            const float top = lerp_fma(lx, c[y0 * w + x0], c[y0 * w + x1]);
+            const float bot = lerp_fma(lx, c[y1 * w + x0], c[y1 * w + x1]);
+            out[(long long)o * HW + (long long)Y * W + X] = (a[q][o] + bias[o]) + lerp_fma(ly, top, bot);
         }
     }
 }
@@ -207,9 +207,9 @@ __global__ __launch_bounds__(256) void tail_gather_kernel(const float* __restric
 #pragma unroll
         for (int o = 0; o < NO; ++o) {
             const float* c = center + (long long)(O0 + o) * h * w;
-            const float top = (1.f - lx) * c[y0 * w + x0] + lx * c[y0 * w + x1];
-            const float bot = (1.f - lx) * c[y1 * w + x0] + lx * c[y1 * w + x1];
-            res[o][i] = (acc[o][i] + bias[O0 + o]) + ((1.f - ly) * top + ly * bot);
+            const float top = lerp_fma(lx, c[y0 * w + x0], c[y0 * w + x1]);
+            const float bot = lerp_fma(lx, c[y1 * w + x0], c[y1 * w + x1]);
+            res[o][i] = (acc[o][i] + bias[O0 + o]) + lerp_fma(ly, top, bot);
         }
     }
 #pragma unroll
@@ -273,9 +273,9 @@ __global__ __launch_bounds__(256) void tail_gather_q_kernel(const float* __restr
         int x0, x1;
         float lx;
         bil_src(X + i, (float)w / (float)W, w, x0, x1, lx);
-        const float top = (1.f - lx) * c[y0 * w + x0] + lx * c[y0 * w + x1];
-        const float bot = (1.f - lx) * c[y1 * w + x0] + lx * c[y1 * w + x1];
-        res[i] = (acc[i] + bias[o]) + ((1.f - ly) * top + ly * bot);
+        const float top = lerp_fma(lx, c[y0 * w + x0], c[y0 * w + x1]);
+        const float bot = lerp_fma(lx, c[y1 * w + x0], c[y1 * w + x1]);
+        res[i] = (acc[i] + bias[o]) + lerp_fma(ly, top, bot);
     }
     float* dst = out + (long long)o * HW + (long long)Y * W + X;
     if (VEC) *reinterpret_cast<f32x4*>(dst) = f32x4{res[0], res[VEC ? 1 : 0], res[VEC ? 2 : 0], res[VEC ? 3 : 0]};
