@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAVSR_ABI_VERSION 54
+#define SAVSR_ABI_VERSION 55
 
 #define SAVSR_E_ARG   (-1)   /* bad shape / null pointer / unsupported combination */
 #define SAVSR_E_ALIGN (-2)   /* pointer or stride alignment requirement violated  */
@@ -872,6 +872,30 @@ int savsr_video_dering_u8(const uint8_t* frames, int n_frames, int64_t frame_byt
 int savsr_video_dering_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step, int depth,
                            int interlaced, int pri, int sec, int damping, uint8_t* out, int64_t out_frame_bytes, int64_t out_plane_offset,
                            void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 55) Noise statistics (noise.hip; savsr_amd.noise_stats, savsr_amd.estimate_noise, upscale_video(denoise_strength="auto",
+ * spatial_strength="auto"), --denoise-strength auto / --spatial-strength auto of python -m savsr_amd.upscale).
+ * Planes are addressed as for savsr_video_grid_stats_* (rows rows of cols pixels of step samples, sample x meeting x +- j * step only),
+ * every sample v = min(s, 2^depth - 1) at its own depth.  h[y][x] = v[y][x-1] - 2 v[y][x] + v[y][x+1],
+ * L[y][x] = |h[y-1][x] - 2 h[y][x] + h[y+1][x]| for 1 <= y <= rows - 2, 1 <= x <= cols - 2; cell (i, j), i < (rows - 2) / 8,
+ * j < (cols - 2) / 8, holds the 64 values L[8i+1 .. 8i+8][8j+1 .. 8j+8] (a plane below 10 x 10 has no cell).  A cell one of whose 8 row
+ * sums or 8 column sums is 0 is flat: out[512 n + 510] += 1.  Any other cell has S = (sum of L) >> (depth - 8), b = min(S >> 4, 254):
+ * out[512 n + 2 b] += 1, out[512 n + 2 b + 1] += S.  interlaced = 1 takes the rows 0::2 and 1::2 as planes of their own, both adding
+ * into the frame's table.  out (n_frames x 256 x 2 int64, device) is ADDED to: the caller zeroes it once, so that several planes land in
+ * one table (savsr_amd/noise.py `noise_stats_matrix` restates it; the kernels equal it bit for bit; the decision is host work).
+ * One launch for up to 65535 frames (none where no plane holds a cell); the entry only enqueues, allocates nothing, does not
+ * synchronise and is capturable.  A lane owns one cell and walks its 10 rows; at step 1 it loads 8 samples and the dword behind them
+ * when the plane's base pointer, the frame stride and the row bytes are multiples of 8 (_u16: of 16), a sample per access otherwise;
+ * a per-wave LDS table, then 64-bit atomics on the rows that are not zero.
+ * Refused (SAVSR_E_ARG, before anything is launched, the message naming the entry): a null pointer, n_frames < 1, rows < 1, cols < 1, a
+ * step outside 1 .. 4, a plane above 2147418112 bytes, a negative plane offset, a frame stride smaller than the offset plus the plane,
+ * an out that is not 8-byte aligned, interlaced other than 0 / 1; _u16: a depth other than 10 / 12, an odd pointer, stride or
+ * offset. */
+int savsr_video_noise_stats_u8(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step,
+                               int interlaced, int64_t* out, void* stream);
+int savsr_video_noise_stats_u16(const uint8_t* frames, int n_frames, int64_t frame_bytes, int64_t plane_offset, int rows, int cols, int step, int depth,
+                                int interlaced, int64_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 45) Video surfaces (surface.hip; savsr_amd.unpack_surface, savsr_amd.pack_surface, upscale_video(surface=..., out_surface=...),

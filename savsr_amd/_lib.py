@@ -18,7 +18,7 @@ MAX_SRC = 5
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID = 0, 1, 2, 3
 SATU_LRCAT = 160
 SATU_TABLE = 8
-ABI_VERSION = 54
+ABI_VERSION = 55
 CONV_DIRECT, CONV_DIRECT_THROUGHPUT, CONV_WINOGRAD_Y, CONV_WINOGRAD_Y_THROUGHPUT = 0, 2, 3, 4
 CONV_WY_FORMS = (CONV_WINOGRAD_Y, CONV_WINOGRAD_Y_THROUGHPUT)
 SATU_LRCAT_TAIL = 96
@@ -218,6 +218,8 @@ SIGNATURES = {
                                          fptr, C.c_int64, C.c_int64, C.c_void_p]),
     "savsr_video_grid_stats_u8": (C.c_int, [fptr, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr, C.c_void_p]),
     "savsr_video_grid_stats_u16": (C.c_int, [fptr, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr, C.c_void_p]),
+    "savsr_video_noise_stats_u8": (C.c_int, [fptr, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, fptr, C.c_void_p]),
+    "savsr_video_noise_stats_u16": (C.c_int, [fptr, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr, C.c_void_p]),
     "savsr_video_field_stats_u8": (C.c_int, [fptr, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, fptr, C.c_void_p]),
     "savsr_video_field_stats_u16": (C.c_int, [fptr, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr, C.c_void_p]),
     "savsr_video_unpack_surface": (C.c_int, [fptr, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, fptr,

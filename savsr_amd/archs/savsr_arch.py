@@ -475,6 +475,17 @@ class SAVSR(nn.Module):
         carries; the 8 x 8 analysis grid starts at the plane's origin and does not follow deblock_origin; chroma gets a direction of
         its own rather than the luma's; the stage also smooths fine noise.  The defaults are parameters: nothing is validated on
         footage or on trained weights, and nothing is pinned to libaom's or ffmpeg's output.
+        denoise_strength="auto" / spatial_strength="auto" (beside denoise= / spatial_denoise=): the strength from the noise level of the
+        frames (savsr_amd/noise.py; savsr_amd.estimate_noise is the call): the 8 x 8 cell sums of the absolute second difference
+        [1 -2 1]^T (x) [1 -2 1], summed over the video on the GPU, one launch per plane and one more host synchronisation each, then
+        an exact rule on the host (the mean of the quietest quarter of the cells that are not flat, over 245).  Each is measured on the
+        frames its stage will read: the temporal one right in front of the temporal denoiser, the spatial one right in front of the
+        spatial denoiser, behind denoise= and the crop.  The result is, bit for bit, the call with `verdict.denoise_kwargs()` /
+        `verdict.spatial_kwargs()` given, and where no noise is found (sigma below 1/2 code, or too few cells) the call without that
+        stage, so a clean source passes through untouched; an explicit chroma strength beside "auto" wins over the found one.  One
+        figure per video, a white-noise model (coarse grain, subsampled chroma and clipped levels read low, texture over most of the
+        frame reads high); the measure, its constants and the gains are this project's own and are not validated on footage or on
+        trained weights.
         With set_self_ensemble(True) every frame is the self-ensemble of its window.  Arguments are checked before anything runs on the
         GPU.  Streaming form: savsr_amd.VideoUpscaler."""
         from ..video import upscale_video

@@ -24,7 +24,7 @@ OBJDIR=${OBJDIR:-.}
 mkdir -p "$OBJDIR"
 # savsr_source_hash(): sha256 over the kernel sources + headers + flags this library is built from (first 16 hex digits), compiled into
 # api.cpp, so that a measurement file (profiles/satu_traffic.json) can name the build it was taken on and bench.py can tell a stale one
-SRC_HASH=$( (cat conv_mfma.hip conv_wy.hip osconv.hip elementwise.hip satu.hip satu_nf.hip tail.hip metrics.hip resize.hip video.hip ensemble.hip yuv.hip scene.hip luma.hip active.hip deinterlace.hip pulldown.hip surface.hip scan.hip denoise.hip nlmeans.hip deblock.hip grid.hip dering.hip api.cpp common.hpp conv_common.hpp video_samples.hpp field_matrix.hpp dither.hpp nlmeans_weights.hpp ../../include/savsr_hip.h; printf '%s' "$BASE_FLAGS ${EXTRA_FLAGS:-} ${EXTRA_ONLY:-}") | sha256sum | cut -c1-16)
+SRC_HASH=$( (cat conv_mfma.hip conv_wy.hip osconv.hip elementwise.hip satu.hip satu_nf.hip tail.hip metrics.hip resize.hip video.hip ensemble.hip yuv.hip scene.hip luma.hip active.hip deinterlace.hip pulldown.hip surface.hip scan.hip denoise.hip nlmeans.hip deblock.hip grid.hip dering.hip noise.hip api.cpp common.hpp conv_common.hpp video_samples.hpp field_matrix.hpp dither.hpp nlmeans_weights.hpp ../../include/savsr_hip.h; printf '%s' "$BASE_FLAGS ${EXTRA_FLAGS:-} ${EXTRA_ONLY:-}") | sha256sum | cut -c1-16)
 # the SATU + tail kernels alone (not the header: it changes with every other kernel's interface) -- with the EXTRA_FLAGS that reach them: an
 # experiment / DIAG build that changes these kernels through -D switches must not report the product's hash (profiles/satu_traffic.json and
 # savsr_amd/hr_plans.json are attached to a library by this stamp)
@@ -62,7 +62,7 @@ compile() { # compile <src> <obj> [extra hipcc args]
 
 OBJS=()
 PIDS=()
-for f in conv_mfma.hip conv_wy.hip osconv.hip elementwise.hip satu.hip satu_nf.hip tail.hip metrics.hip resize.hip video.hip ensemble.hip yuv.hip scene.hip luma.hip active.hip deinterlace.hip pulldown.hip surface.hip scan.hip denoise.hip nlmeans.hip deblock.hip grid.hip dering.hip; do
+for f in conv_mfma.hip conv_wy.hip osconv.hip elementwise.hip satu.hip satu_nf.hip tail.hip metrics.hip resize.hip video.hip ensemble.hip yuv.hip scene.hip luma.hip active.hip deinterlace.hip pulldown.hip surface.hip scan.hip denoise.hip nlmeans.hip deblock.hip grid.hip dering.hip noise.hip; do
   o="$OBJDIR/${f%.hip}.o"
   if stale "$f" "$o"; then
     compile "$f" "$o" &

@@ -43,6 +43,7 @@ DEFAULT_RADIUS = 4
 DEFAULT_STRENGTH = (4, 9)
 MAX_RADIUS = 16
 MAX_STRENGTH = 255
+AUTO = "auto"                     # denoise_strength="auto": from the frames' noise level (savsr_amd/noise.py)
 
 
 def check_denoiser(denoise, what: str = "denoise") -> Optional[str]:
@@ -80,7 +81,8 @@ def _at_default(value, default) -> bool:
 
 def check_denoise_options(denoise, radius, strength, chroma_strength, prefix: str = "denoise_"):
     """The denoise= arguments of upscale_video / VideoUpscaler: None without denoise= (the options must then be at their defaults), else
-    (radius, strength, chroma strength) checked; chroma_strength None: the strength."""
+    (radius, strength, chroma strength) checked; chroma_strength None: the strength.  strength "auto" (upscale_video alone: the noise
+    level is measured on the frames, savsr_amd/noise.py) comes back as it is, beside the chroma strength as given."""
     if check_denoiser(denoise) is None:
         for name, value, default in ((f"{prefix}radius", radius, DEFAULT_RADIUS), (f"{prefix}strength", strength, DEFAULT_STRENGTH),
                                      (f"{prefix}chroma_strength", chroma_strength, None)):
@@ -88,6 +90,8 @@ def check_denoise_options(denoise, radius, strength, chroma_strength, prefix: st
                 raise ValueError(f"{name} = {value!r} goes with denoise=: without the stage there is nothing to set")
         return None
     r = check_radius(radius, f"{prefix}radius")
+    if isinstance(strength, str) and strength == AUTO:          # found from the frames by the caller; an explicit chroma strength wins
+        return r, AUTO, None if chroma_strength is None else check_strength(chroma_strength, f"{prefix}chroma_strength")
     s = check_strength(strength, f"{prefix}strength")
     return r, s, s if chroma_strength is None else check_strength(chroma_strength, f"{prefix}chroma_strength")
 

@@ -56,6 +56,7 @@ DEFAULT_STRENGTH = 3.0          # a parameter: nothing is validated on footage
 MAX_PATCH = 3
 MAX_SEARCH = 7
 MAX_STRENGTH = 32
+AUTO = "auto"                     # spatial_strength="auto": from the frames' noise level (savsr_amd/noise.py)
 N_WEIGHTS = 577
 WEIGHTS = tuple(int(np.rint(4096.0 * np.exp(-i / 64.0))) for i in range(N_WEIGHTS))
 
@@ -107,7 +108,8 @@ def divisor(patch: int = DEFAULT_PATCH, strength=DEFAULT_STRENGTH, what: str = "
 
 def check_spatial_options(spatial_denoise, patch, search, strength, chroma_strength, prefix: str = "spatial_"):
     """The spatial_denoise= arguments of upscale_video / VideoUpscaler: None without spatial_denoise= (the options must then be at their
-    defaults), else (patch, search, strength, chroma strength) checked; chroma_strength None: the strength."""
+    defaults), else (patch, search, strength, chroma strength) checked; chroma_strength None: the strength.  strength "auto" (upscale_video alone:
+    the noise level is measured on the frames, savsr_amd/noise.py) comes back as it is, beside the chroma strength as given."""
     if check_spatial_denoiser(spatial_denoise, f"{prefix}denoise") is None:
         for name, value, default in ((f"{prefix}patch", patch, DEFAULT_PATCH), (f"{prefix}search", search, DEFAULT_SEARCH),
                                      (f"{prefix}strength", strength, DEFAULT_STRENGTH), (f"{prefix}chroma_strength", chroma_strength, None)):
@@ -118,6 +120,10 @@ def check_spatial_options(spatial_denoise, patch, search, strength, chroma_stren
         return None
     p = check_patch(patch, f"{prefix}patch")
     s = check_search(search, f"{prefix}search")
+    if isinstance(strength, str) and strength == AUTO:          # found from the frames by the caller; an explicit chroma strength wins
+        if chroma_strength is not None:
+            divisor(p, chroma_strength, f"{prefix}chroma_strength")
+        return p, s, AUTO, None if chroma_strength is None else check_strength(chroma_strength, f"{prefix}chroma_strength")
     h = check_strength(strength, f"{prefix}strength")
     divisor(p, h, f"{prefix}strength")
     ch = h if chroma_strength is None else check_strength(chroma_strength, f"{prefix}chroma_strength")

@@ -23,6 +23,7 @@ from . import denoise as dn
 from . import dering as dr
 from . import grid as gr
 from . import nlmeans as nl
+from . import noise as nz
 from . import pulldown as pd
 from . import scan as sc
 from .deinterlace import DEINTERLACERS, FIELD_ORDERS, FIELD_RATES, check_frame_rows, check_method, check_order, check_rate
@@ -752,6 +753,59 @@ def detect_grid(frames: torch.Tensor, pixel_format: str = "rgb", size=None, dept
     ratio, min_count, cap = gr.check_ratio(ratio), gr.check_min_count(min_count), gr.check_cap(cap)
     frames, side, size = _stage_args(frames, pixel_format, size, depth, lambda f, s, z: _sample_frames(f, s, z, "find a grid in"))
     return _detect_grid_device(frames, side, size, interlaced, ratio, min_count, cap)
+
+
+# ---- the noise level (savsr_amd/noise.py is the specification) ------------------------------------------------------------------------------
+def _noise_frames(frames: torch.Tensor, side: Side, size: Size) -> Tuple[int, int, int, int]:
+    return _sample_frames(frames, side, size, "measure noise in")
+
+
+def _noise_stats_device(frames: torch.Tensor, side: Side, size: Size, interlaced: bool = False) -> torch.Tensor:
+    """savsr_video_noise_stats_* on resident frames of the input side on the GPU: int64 [N, 2, 256, 2] there (a view of [2, N, 256, 2]),
+    one memset and one launch per plane on the current stream (no sync).  Class 0: the Y plane, or all channels of packed frames in one
+    call (the channel count is the entry's sample step); class 1: the chroma planes, both added into the same table."""
+    n, c, h, w = _noise_frames(frames, side, size)
+    frames, tab = frames.contiguous(), plane_table(side, size, c, h, w)
+    out = torch.zeros(2, n, nz.ROWS, 2, dtype=torch.int64, device=frames.device)          # by class: a class's frames are 512 cells apart, as the entry adds them
+    step = max(c, 1)
+    for i, p in enumerate(tab.planes if n else ()):
+        head = (p.row_bytes // (tab.sample * step), step) + (() if tab.sample == 1 else (side.depth,))
+        _entry_call("savsr_video_noise_stats_u8" if tab.sample == 1 else "savsr_video_noise_stats_u16", frames, n, tab, p, head,
+                    (int(bool(interlaced)), out[min(i, 1)].data_ptr()))
+    return out.permute(1, 0, 2, 3)
+
+
+def noise_stats(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8, interlaced: bool = False) -> torch.Tensor:
+    """The noise estimator's statistics: int64 [N, 2, 256, 2] on the GPU (savsr_amd.noise.noise_stats_frames is the specification, bit
+    for bit), on the caller's current stream, without a sync.  Every 8 x 8 cell of the absolute 3 x 3 second difference
+    [1 -2 1]^T (x) [1 -2 1] of a plane adds, with its sum S in 8-bit code units, [n, k, min(S >> 4, 254)] += (1, S), or, where one of its
+    rows or columns sums to 0, [n, k, 255, 0] += 1 (a flat cell); field by field with interlaced=True.  Class 0: the Y plane of planar
+    frames, or every channel of [N, h, w, c] uint8 frames; class 1: Cb + Cr, zeros where there is none.  Float frames are refused."""
+    frames, side, size = _stage_args(frames, pixel_format, size, depth, _noise_frames)
+    return _noise_stats_device(frames, side, size, interlaced)
+
+
+def _estimate_noise_device(frames: torch.Tensor, side: Side, size: Size, interlaced: bool = False, quantile=nz.DEFAULT_QUANTILE,
+                           min_cells: int = nz.DEFAULT_MIN_CELLS, floor=nz.DEFAULT_FLOOR) -> "nz.NoiseVerdict":
+    """noise.verdict_from_stats on `_noise_stats_device` of frames of the input side on the GPU, summed over the frames there: one device
+    -> host copy of 1024 integers."""
+    table = _noise_stats_device(frames, side, size, interlaced).sum(0).cpu().numpy()
+    return nz.verdict_from_stats(table, quantile, min_cells, floor)
+
+
+def estimate_noise(frames: torch.Tensor, pixel_format: str = "rgb", size=None, depth: int = 8, interlaced: bool = False,
+                   quantile=nz.DEFAULT_QUANTILE, min_cells: int = nz.DEFAULT_MIN_CELLS, floor=nz.DEFAULT_FLOOR) -> "nz.NoiseVerdict":
+    """The noise level of a video, from its content: a savsr_amd.noise.NoiseVerdict with sigma and chroma_sigma as exact fractions in
+    8-bit code units (None where fewer than `min_cells` cells are not flat, or where there is no chroma); `verdict.spatial_kwargs()` and
+    `verdict.denoise_kwargs()` are the explicit arguments of upscale_video beside spatial_denoise= / denoise= that say the same, {} where
+    sigma is unknown or below `floor`.  `noise_stats` on the GPU summed over the frames, one host synchronisation, then
+    savsr_amd.noise.verdict_from_stats in exact arithmetic: the mean of the quietest `quantile` of the cells, scaled by the constant
+    that maps it to sigma for white Gaussian noise.  interlaced=True measures field by field.  The measure, its constants and the gains
+    of the two maps are this project's own and are not validated on footage or on trained weights; one figure per video; coarse grain,
+    the noise of subsampled chroma and clipped shadows read low, texture over three quarters of the frame reads high."""
+    quantile, min_cells, floor = nz.check_quantile(quantile), nz.check_min_cells(min_cells), nz.check_floor(floor)
+    frames, side, size = _stage_args(frames, pixel_format, size, depth, _noise_frames)
+    return _estimate_noise_device(frames, side, size, interlaced, quantile, min_cells, floor)
 
 
 # ---- telecined film (savsr_amd/pulldown.py is the specification) -----------------------------------------------------------------------------

@@ -137,6 +137,16 @@ weight is 1 / e (savsr_amd/nlmeans.py); --spatial-chroma-strength H sets the chr
 stage and its parameters.  Works for PNG folders and for .y4m files and pipes.  One strength per video, no joint-channel weights, the
 search stops at 15 x 15; the defaults are parameters, nothing is validated on footage and nothing is pinned to ffmpeg's nlmeans.
 
+--denoise-strength auto / --spatial-strength auto: the strength from the noise level of the input (savsr_amd/noise.py: the 8 x 8 cell
+sums of an absolute 3 x 3 second difference on the GPU, the mean of the quietest quarter of the cells on the host).  Each is a first
+pass of its own over a .y4m file or a PNG folder, in --chunk pieces, through the stages in front of its measuring point as the second
+pass will run them (--deblock, --dering, --fields / --pulldown; for the spatial one also --denoise at the strength just found, and the
+crop): the passes run in the order scan, grid, temporal noise, crop, spatial noise.  One line on stderr per pass gives the verdict and
+the equivalent flags; where no noise is found (sigma below half a code) that is --denoise none / --spatial-denoise none and the stage is
+left out.  --noise-out FILE writes both verdicts as JSON (sigma per class, cells, flat cells, the summed tables, the chosen flags).  An
+explicit --denoise-chroma-strength / --spatial-chroma-strength wins over the found one.  Not on stdin (there is no second pass).  The
+measure, its constants and the gains are this project's own and are not validated on footage.
+
 --deblock weak|strong: the 8 x 8 block edges of MPEG-2 and low-bitrate H.264 sources, which neither denoiser removes.  On the GPU, every
 frame on its own: across the vertical edges of a grid of --deblock-block N (default 8; 4, 8 or 16) samples whose first edges lie at
 --deblock-origin Y,X (default 0,0), then across the horizontal ones, the 2 (weak) or 3 (strong) samples on either side of an edge move towards each other where the
@@ -339,7 +349,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help=f"--denoise: the frames averaged on either side (default {DEFAULT_RADIUS}: nine frames; 1 .. {MAX_RADIUS})")
     p.add_argument("--denoise-strength", default=None, metavar="A,B",
                    help=f"--denoise: a tap is taken while it differs by at most A and the differences of its side sum to at most B, in 8-bit "
-                        f"code units at every depth (default {DEFAULT_STRENGTH[0]},{DEFAULT_STRENGTH[1]}; 0 <= A <= B <= 255; not validated on footage)")
+                        f"code units at every depth (default {DEFAULT_STRENGTH[0]},{DEFAULT_STRENGTH[1]}; 0 <= A <= B <= 255; not validated on footage); "
+                        f"auto: from the noise level measured in a first pass over the input (savsr_amd/noise.py), no noise found: the stage "
+                        f"is left out")
     p.add_argument("--denoise-chroma-strength", default=None, metavar="A,B",
                    help="--denoise: the same for the chroma planes of a Y4M input (default: --denoise-strength)")
     p.add_argument("--spatial-denoise", default=None, choices=["none"] + list(nlm.SPATIAL_DENOISERS),
@@ -349,9 +361,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help=f"--spatial-denoise: the patch radius (default {nlm.DEFAULT_PATCH}: 7 x 7 patches; 1 .. {nlm.MAX_PATCH})")
     p.add_argument("--spatial-search", type=int, default=None, metavar="N",
                    help=f"--spatial-denoise: the search radius (default {nlm.DEFAULT_SEARCH}: a 15 x 15 window; 1 .. {nlm.MAX_SEARCH})")
-    p.add_argument("--spatial-strength", type=float, default=None, metavar="H",
+    p.add_argument("--spatial-strength", type=float_or_auto, default=None, metavar="H",
                    help=f"--spatial-denoise: the root mean squared patch difference at which the weight is 1 / e, in 8-bit code units at every "
-                        f"depth (default {nlm.DEFAULT_STRENGTH}; 0 < H <= {nlm.MAX_STRENGTH}; not validated on footage)")
+                        f"depth (default {nlm.DEFAULT_STRENGTH}; 0 < H <= {nlm.MAX_STRENGTH}; not validated on footage); auto: from the noise level "
+                        f"measured in a first pass over the input, behind --denoise and --crop (savsr_amd/noise.py), no noise found: the stage "
+                        f"is left out")
     p.add_argument("--spatial-chroma-strength", type=float, default=None, metavar="H",
                    help="--spatial-denoise: the same for the chroma planes of a Y4M input (default: --spatial-strength)")
     p.add_argument("--deblock", default=None, choices=["none"] + list(dbk.DEBLOCKERS),
@@ -389,10 +403,21 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--deblock: find the block size and the origins from the frames in a first pass over the input (savsr_amd/grid.py; the "
                         "rule's defaults are this project's own and are not validated on footage); no grid found: the stage is left out")
     p.add_argument("--grid-out", default=None, metavar="FILE", help="--deblock-grid auto: write the verdict as JSON")
+    p.add_argument("--noise-out", default=None, metavar="FILE",
+                   help="--denoise-strength auto / --spatial-strength auto: write the verdicts as JSON (sigma per class, cells, flat cells, the "
+                        "summed tables, the chosen flags)")
     p.add_argument("--scan-out", default=None, metavar="FILE", help="--scan detect: write the verdict as JSON")
     p.add_argument("--bars", default=None, choices=["keep", "drop"],
                    help="--crop: keep = full-size output, the picture in nominal black (default); drop = the picture alone")
     return p
+
+
+def float_or_auto(text: str):
+    """--spatial-strength: "auto" or a number."""
+    return text if text == "auto" else float(text)
+
+
+float_or_auto.__name__ = "float"          # (argparse names the type in its refusal: "invalid float value")
 
 
 def parse_crop(text: str):
@@ -562,7 +587,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--denoise-chroma-strength goes with a Y4M input (PNG frames are RGB: every byte takes --denoise-strength)")
     try:
         a.denoise_radius = check_radius(DEFAULT_RADIUS if a.denoise_radius is None else a.denoise_radius, "--denoise-radius")
-        a.denoise_strength = DEFAULT_STRENGTH if a.denoise_strength is None else parse_strength(a.denoise_strength, "--denoise-strength")
+        if a.denoise_strength != "auto":
+            a.denoise_strength = DEFAULT_STRENGTH if a.denoise_strength is None else parse_strength(a.denoise_strength, "--denoise-strength")
         if a.denoise_chroma_strength is not None:
             a.denoise_chroma_strength = parse_strength(a.denoise_chroma_strength, "--denoise-chroma-strength")
     except ValueError as e:
@@ -577,13 +603,20 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         try:
             a.spatial_patch = nlm.check_patch(nlm.DEFAULT_PATCH if a.spatial_patch is None else a.spatial_patch, "--spatial-patch")
             a.spatial_search = nlm.check_search(nlm.DEFAULT_SEARCH if a.spatial_search is None else a.spatial_search, "--spatial-search")
-            a.spatial_strength = nlm.check_strength(nlm.DEFAULT_STRENGTH if a.spatial_strength is None else a.spatial_strength, "--spatial-strength")
-            nlm.divisor(a.spatial_patch, a.spatial_strength, "--spatial-strength")
+            if a.spatial_strength != "auto":
+                a.spatial_strength = nlm.check_strength(nlm.DEFAULT_STRENGTH if a.spatial_strength is None else a.spatial_strength, "--spatial-strength")
+                nlm.divisor(a.spatial_patch, a.spatial_strength, "--spatial-strength")
             if a.spatial_chroma_strength is not None:
                 a.spatial_chroma_strength = nlm.check_strength(a.spatial_chroma_strength, "--spatial-chroma-strength")
                 nlm.divisor(a.spatial_patch, a.spatial_chroma_strength, "--spatial-chroma-strength")
         except ValueError as e:
             p.error(str(e))
+    autos = [flag for flag, v in (("--denoise-strength", a.denoise_strength), ("--spatial-strength", a.spatial_strength)) if v == "auto"]
+    if autos and a.input == "-":
+        p.error(f"{autos[0]} auto needs a first pass over the input, which stdin does not allow: measure the noise first "
+                f"(savsr_amd.estimate_noise) and give the strength")
+    if a.noise_out is not None and not autos:
+        p.error("--noise-out goes with --denoise-strength auto or --spatial-strength auto")
     a.deblock = None if a.deblock == "none" else a.deblock
     if a.deblock is None:
         if any(v is not None for v in (a.deblock_block, a.deblock_strength, a.deblock_chroma_strength)):
@@ -868,38 +901,33 @@ def detect_grid_pass(a: argparse.Namespace, chunks, fmt_in: str, size, depth: in
     return verdict_from_stats(table.cpu().numpy(), pairs, fieldwise)
 
 
-def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev, order: Optional[str] = None, film: Optional[str] = None):
-    """--crop auto's first pass: savsr_amd.line_sums over the input in --chunk-sized pieces with a running maximum on the device, then
-    cropdetect's rule and the alignment to the input layout's chroma block.  chunks: the PNG folder's chunk iterator; None: the .y4m file
-    named by --input, read through a reader of its own.  order: --fields' field order; the sums are then taken on the deinterlaced frames
-    (a prepass.FieldSplitter of this pass's own), as the second pass will crop them.  film: --pulldown's field order; the sums are then taken
-    on the recovered film frames (a prepass.PulldownRemover of this pass's own).  --deblock: the chunks are filtered first, field by field
-    with either, as the second pass will filter them; --dering likewise, behind it."""
+def front_frames(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev, order: Optional[str] = None, film: Optional[str] = None,
+                 denoise: bool = True):
+    """The front chain of a first pass, as the second pass will run it: the input in --chunk-sized pieces through --deblock, --dering
+    (field by field with `order` / `film`), the --fields / --pulldown stage (a prepass.FieldSplitter / PulldownRemover of this pass's
+    own) and, with `denoise`, --denoise (a prepass.TemporalDenoiser of its own); yields the chunks of progressive frames that come out,
+    on the device.  chunks: the PNG folder's chunk iterator; None: the .y4m file named by --input, read through a reader of its own."""
     import torch
 
-    from . import active
-    from .frames import detector_side, layout_of
-    from .prepass import deblock_video, dering_video, line_sums, make_denoiser, make_stage
+    from .frames import detector_side
+    from .prepass import deblock_video, dering_video, make_denoiser, make_stage
     from .y4m import Y4MReader
     from .yuv import CHROMAS
-    top = None
     f = None
     how = (a.deinterlacer, a.field_rate) if order is not None else ()          # (they say how --fields is carried out, and nothing else)
     comb = dict(combed=a.combed, comb_threshold=a.comb_threshold, comb_pixels=a.comb_pixels) if film is not None and a.combed is not None else {}
     split = make_stage(order, film, a.pulldown_cycle, *detector_side(fmt_in, size, depth), *how, **comb)
-    # (--denoise: the sums are taken on the denoised frames, as upscale_video's crop="auto" takes them)
-    noise = make_denoiser(a.denoise, a.denoise_radius, a.denoise_strength, a.denoise_chroma_strength, *detector_side(fmt_in, size, depth))
+    noise = None
+    if denoise and a.denoise is not None:          # (None also where --denoise-strength auto found no noise: its options then say nothing)
+        noise = make_denoiser(a.denoise, a.denoise_radius, a.denoise_strength, a.denoise_chroma_strength, *detector_side(fmt_in, size, depth))
 
-    def fold(frames, final: bool = False):
-        nonlocal top
-        if noise is not None and not final:
-            if int(frames.shape[0]):
-                fold(noise.push(frames), True)
+    def behind(frames, final: bool = False):          # the chunks behind the denoiser: what it lets go of
+        if frames is None or not int(frames.shape[0]):
             return
+        if noise is not None and not final:
+            frames = noise.push(frames)
         if int(frames.shape[0]):
-            rows, cols = line_sums(frames, fmt_in, size, depth)
-            now = torch.cat([rows.amax(0), cols.amax(0)])
-            top = now if top is None else torch.maximum(top, now)
+            yield frames
 
     try:
         if chunks is None:
@@ -907,8 +935,6 @@ def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, de
             chunks = (torch.from_numpy(c) for c in Y4MReader(f, high_depth=True, layouts=CHROMAS, mono=True).chunks(a.chunk))
         with torch.cuda.device(dev):
             for chunk in chunks:
-                c = 1 if size else int(chunk.shape[3])
-                h, w = size if size else (int(chunk.shape[1]), int(chunk.shape[2]))
                 chunk = chunk.to(dev)
                 if a.deblock is not None:
                     chunk = deblock_video(chunk, fmt_in, size, depth, a.deblock_block, a.deblock, a.deblock_strength, a.deblock_chroma_strength,
@@ -916,21 +942,79 @@ def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, de
                 if a.dering is not None:
                     chunk = dering_video(chunk, fmt_in, size, depth, a.dering_strength, a.dering_chroma_strength, a.dering_damping,
                                          order is not None or film is not None)
-                fold(chunk if split is None else split.push(chunk))
-            last = None if split is None else split.finish()
-            if last is not None:
-                fold(last)
-            last = None if noise is None else noise.finish()
-            if last is not None:
-                fold(last, True)
+                yield from behind(chunk if split is None else split.push(chunk))
+            yield from behind(None if split is None else split.finish())
+            yield from behind(None if noise is None else noise.finish(), True)
     finally:
         if f is not None:
             f.close()
+
+
+def detect_crop(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev, order: Optional[str] = None, film: Optional[str] = None):
+    """--crop auto's first pass: savsr_amd.line_sums over the input in --chunk-sized pieces with a running maximum on the device, then
+    cropdetect's rule and the alignment to the input layout's chroma block.  The sums are taken behind `front_frames`: on the frames the
+    second pass will crop -- filtered by --deblock / --dering, deinterlaced with `order` (--fields' field order) or recovered with `film`
+    (--pulldown's), denoised by --denoise, as upscale_video's crop="auto" takes them."""
+    import torch
+
+    from . import active
+    from .frames import layout_of
+    from .prepass import line_sums
+    top = None
+    with torch.cuda.device(dev):
+        for frames in front_frames(a, chunks, fmt_in, size, depth, dev, order, film):
+            c = 1 if size else int(frames.shape[3])
+            h, w = size if size else (int(frames.shape[1]), int(frames.shape[2]))
+            rows, cols = line_sums(frames, fmt_in, size, depth)
+            now = torch.cat([rows.amax(0), cols.amax(0)])
+            top = now if top is None else torch.maximum(top, now)
     if top is None:
         raise SystemExit("the video has no frames")
     top = top.cpu().tolist()
     s_row, s_col = active.line_samples(h, w, c)
     return active.align_rect(active.active_rect(top[:h], top[h:], s_row, s_col, a.crop_limit), layout_of(fmt_in) if size else None)
+
+
+def describe_noise(verdict) -> str:
+    """A NoiseVerdict in a few words for stderr: sigma per class in 8-bit code units, the cells behind it and the flat ones."""
+    def one(s):
+        return "unknown (too few cells)" if s is None else f"{float(s):.3f}"
+    text = f"sigma {one(verdict.sigma)} from {verdict.cells[0]} cells ({verdict.flat[0]} flat)"
+    if verdict.cells[1] or verdict.flat[1]:
+        text += f", chroma sigma {one(verdict.chroma_sigma)} from {verdict.cells[1]} cells ({verdict.flat[1]} flat)"
+    return text
+
+
+def noise_pass(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev, order: Optional[str] = None, film: Optional[str] = None,
+               rect=None, spatial: bool = False):
+    """The first pass of --denoise-strength auto (spatial False) or --spatial-strength auto (spatial True): savsr_amd.noise_stats over
+    the frames its stage will read, summed on the device (one copy of 1024 integers at the end), then noise.verdict_from_stats.  The
+    temporal one measures behind `front_frames` without the denoiser; the spatial one behind the denoiser, at the strength just found,
+    and behind the crop to `rect`, so it sees the noise that is left inside the picture."""
+    import torch
+
+    from .active import check_rect
+    from .frames import detector_side, layout_of
+    from .noise import verdict_from_stats
+    from .prepass import _crop_device, noise_stats
+    side, hw = detector_side(fmt_in, size, depth)
+    table = None
+    try:
+        with torch.cuda.device(dev):
+            for frames in front_frames(a, chunks, fmt_in, size, depth, dev, order, film, denoise=spatial):
+                at = size
+                if spatial and rect is not None:
+                    h, w = size if size else (int(frames.shape[1]), int(frames.shape[2]))
+                    rect = check_rect(rect, h, w, layout_of(fmt_in) if size else None)
+                    if tuple(rect) != (0, 0, h, w):
+                        frames, at = _crop_device(frames, rect, side, (h, w)), ((rect[2], rect[3]) if size else None)
+                part = noise_stats(frames, fmt_in, at, depth).sum(0)
+                table = part if table is None else table + part
+    except ValueError as e:
+        raise SystemExit(f"--{'spatial' if spatial else 'denoise'}-strength auto: {e}") from None
+    if table is None:
+        raise SystemExit("the video has no frames")
+    return verdict_from_stats(table.cpu().numpy())
 
 
 def detect_scan_pass(a: argparse.Namespace, chunks, fmt_in: str, size, depth: int, dev):
@@ -1109,6 +1193,23 @@ def main(argv: Optional[List[str]] = None) -> int:
                                   chroma if a.y4m_in and chroma != MONO else None, "--deblock-")
             except ValueError as e:
                 raise SystemExit(str(e)) from None
+        noise_report = {}                           # what --noise-out writes: the verdict and the chosen flags of each measuring point
+        if a.denoise is not None and a.denoise_strength == "auto":          # the temporal noise's pass: behind the grid's, in front of the crop's
+            found = noise_pass(a, chunks if paths is not None else None, fmt_in, (h, w) if a.y4m_in else None, depth, dev, order, film)
+            if paths is not None:
+                chunks = png_chunks()
+            kw = found.denoise_kwargs()
+            if not kw:
+                flags, a.denoise = "--denoise none", None
+            else:
+                a.denoise_strength = kw["denoise_strength"]
+                if a.denoise_chroma_strength is None and a.y4m_in:
+                    a.denoise_chroma_strength = kw.get("denoise_chroma_strength")
+                flags = f"--denoise {a.denoise} --denoise-strength {a.denoise_strength[0]},{a.denoise_strength[1]}"
+                if a.denoise_chroma_strength is not None:
+                    flags += f" --denoise-chroma-strength {a.denoise_chroma_strength[0]},{a.denoise_chroma_strength[1]}"
+            print(f"--denoise-strength auto: {describe_noise(found)}: {flags} (the measure is not validated on footage)", file=sys.stderr, flush=True)
+            noise_report["denoise"] = dict(found.as_json(), flags=flags)
         rect = a.crop
         if rect == "auto":                          # the first pass: line sums chunk by chunk, a running maximum on the device
             rect = detect_crop(a, chunks if paths is not None else None, fmt_in, (h, w) if a.y4m_in else None, depth, dev, order, film)
@@ -1123,6 +1224,27 @@ def main(argv: Optional[List[str]] = None) -> int:
                 rect = check_rect(rect, h, w, layout_of(fmt_in) if a.y4m_in else None)
             except ValueError as e:
                 raise SystemExit(f"--crop: {e}") from None
+        if a.spatial_denoise is not None and a.spatial_strength == "auto":          # the spatial noise's pass: behind --denoise as found and the crop
+            found = noise_pass(a, chunks if paths is not None else None, fmt_in, (h, w) if a.y4m_in else None, depth, dev, order, film, rect, True)
+            if paths is not None:
+                chunks = png_chunks()
+            kw = found.spatial_kwargs()
+            if not kw:
+                flags, a.spatial_denoise = "--spatial-denoise none", None
+            else:
+                a.spatial_strength = kw["spatial_strength"]
+                if a.spatial_chroma_strength is None and a.y4m_in:
+                    a.spatial_chroma_strength = kw.get("spatial_chroma_strength")
+                flags = f"--spatial-denoise {a.spatial_denoise} --spatial-strength {a.spatial_strength:g}"
+                if a.spatial_chroma_strength is not None:
+                    flags += f" --spatial-chroma-strength {a.spatial_chroma_strength:g}"
+            print(f"--spatial-strength auto: {describe_noise(found)}: {flags} (the measure is not validated on footage)", file=sys.stderr, flush=True)
+            noise_report["spatial"] = dict(found.as_json(), flags=flags)
+        if a.noise_out is not None:
+            import json
+            with open(a.noise_out, "w") as f:
+                json.dump(noise_report, f)
+                f.write("\n")
         lr = written_lr(h, w, rect, a.bars)
         hr = get_hw(lr[0], lr[1], a.scale) if a.y4m_out else None
         colour, out_colour = resolve_colours(a.colour, a.out_colour, (h, w) if a.y4m_in else None, hr, in_range)

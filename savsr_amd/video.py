@@ -60,6 +60,15 @@ deblock= on the frames as decoded -- after surface= unpacking and after scan="de
 front of fields= / pulldown=, denoise=, the crop, spatial_denoise= and the cuts -- and field by field exactly when the deblocker would.
 The call is, bit for bit, the call on `dering_video(deblock_video(v, ...), ..., interlaced=I)`.  None runs the lines that ran before.
 
+denoise_strength="auto" / spatial_strength="auto" (beside denoise= / spatial_denoise=): the strength from the frames' noise level
+(savsr_amd/noise.py: `noise_stats` summed over the video on the GPU, one launch per plane and one host synchronisation each, an exact
+rule on the host).  Each is measured on the frames its stage will read: the temporal one right in front of the temporal denoiser (after
+surface=, deblock=, dering= and fields= / pulldown=, on progressive frames), the spatial one right in front of the spatial denoiser
+(after denoise= and the crop, so it sees the noise that is left).  The call is, bit for bit, the call with `verdict.denoise_kwargs()` /
+`verdict.spatial_kwargs()` given, and where no noise is found the call without that stage; an explicit chroma strength beside "auto"
+wins over the found one.  One figure per video; the measure, its constants and the gains are this project's own and are not validated
+on footage.
+
 dither="ordered": every quantiser behind the network (packed uint8, planar YUV, the luma-only path's Y plane) takes floor(t + theta(y, x))
 in rint's place, theta from a 16 x 16 Bayer matrix at the sample's position in its plane (savsr_amd/dither.py is the specification, the
 `_d` entries of the C ABI the kernels).  It belongs to the quantiser: bars="keep" inserts exact nominal black after it and out_surface
@@ -90,12 +99,13 @@ from .dering import check_dering_options
 from .nlmeans import check_spatial_options
 from .prepass import (FieldSplitter, PulldownRemover, ScanStats, TemporalDenoiser, _check_crop_args, _check_field_options, _check_fields,  # noqa: F401  (re-exported)
                       _check_pulldown, _check_scan, _crop_device, _cropped_spec, _deblock_device, _deinterlace_device, _dering_device, _denoise_device, _denoise_frames, _denoise_spatial_device,
-                      _detect_device, _detect_grid_device, _detect_scan_device, _field_frames, _insert_device, _pair_sad_device, _pack_surface_device,
+                      _detect_device, _detect_grid_device, _detect_scan_device, _estimate_noise_device, _field_frames, _insert_device, _pair_sad_device, _pack_surface_device,
                       _remove_pulldown_device, _sample_frames, _to_device, _unpack_surface_device, comb_windows, deblock_video, deinterlace, denoise_spatial, denoise_video, dering_video,
-                      detect_active_area, detect_cuts, detect_grid, detect_scan, field_scores, field_stats, grid_stats, line_sums, make_denoiser, make_stage,
+                      detect_active_area, detect_cuts, detect_grid, detect_scan, estimate_noise, field_scores, field_stats, grid_stats, line_sums, make_denoiser, make_stage, noise_stats,
                       pack_surface, pair_sad, remove_pulldown, surface_layout, surface_side, surface_table, unpack_surface)
 from .pulldown import check_comb_options
 from .grid import GridVerdict  # noqa: F401  (re-exported)
+from .noise import NoiseVerdict, is_auto as _auto_strength  # noqa: F401  (re-exported)
 from .scan import ScanVerdict, check_thresholds  # noqa: F401  (re-exported)
 
 
@@ -227,6 +237,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
         frames = _deinterlace_device(frames, fields, spec.inp, spec.size, method=deinterlacer, rate=field_rate)
     if pulldown is not None:           # pulldown removal comes first, where deinterlacing comes
         frames = _remove_pulldown_device(frames, pulldown, spec.inp, spec.size, pulldown_cycle, combed, comb_threshold, comb_pixels)[0]
+    if noise is not None and noise[1] == "auto":          # the strength from the frames the denoiser will read; no noise: the stage is left out
+        noise = _auto_denoise(_estimate_noise_device(frames, spec.inp, spec.size), noise)
     if noise is not None:              # the denoiser sees progressive frames, and the crop, the cuts and the windows see its output
         frames = _denoise_device(frames, spec.inp, spec.size, *noise)
     full = spec
@@ -237,6 +249,8 @@ def upscale_video(net, frames: torch.Tensor, scale=None, padding: str = "reflect
     if crop is not None:               # the crop comes first: everything below sees the cropped video
         frames = _crop_device(frames, crop, spec.inp, (h, w))
         spec = _cropped_spec(spec, crop)
+    if grain is not None and grain[2] == "auto":          # likewise, on what the temporal denoiser and the crop have left
+        grain = _auto_spatial(_estimate_noise_device(frames, spec.inp, spec.size), grain)
     if grain is not None:              # the spatial denoiser sees the cropped picture (the bars never enter a patch); the cuts and the windows see its output
         frames = _denoise_spatial_device(frames, spec.inp, spec.size, *grain)
     if cuts is None:
@@ -264,6 +278,26 @@ def _auto_grid(verdict, edges, fieldwise: bool, layout):
         return None, None
     edges = (found["deblock_block"], edges[1], edges[2], found.get("deblock_chroma_strength", edges[3]))
     return edges, check_origins(found["deblock_origin"], found.get("deblock_chroma_origin"), edges[0], fieldwise, layout, "deblock_")
+
+
+def _auto_denoise(verdict, noise):
+    """What denoise_strength="auto" continues with: (radius, strength, chroma strength) as if `verdict.denoise_kwargs()` had been
+    given beside denoise=, an explicit chroma strength before the found one; None where no noise was found (the call with denoise=None)."""
+    found = verdict.denoise_kwargs()
+    if not found:
+        return None
+    chroma = found.get("denoise_chroma_strength") if noise[2] is None else noise[2]
+    return check_denoise_options("ata", noise[0], found["denoise_strength"], chroma)
+
+
+def _auto_spatial(verdict, grain):
+    """What spatial_strength="auto" continues with: (patch, search, strength, chroma strength) as if `verdict.spatial_kwargs()` had
+    been given beside spatial_denoise=, an explicit chroma strength before the found one; None where no noise was found."""
+    found = verdict.spatial_kwargs()
+    if not found:
+        return None
+    chroma = found.get("spatial_chroma_strength") if grain[3] is None else grain[3]
+    return check_spatial_options("nlm", grain[0], grain[1], found["spatial_strength"], chroma)
 
 
 class VideoUpscaler:
@@ -336,6 +370,10 @@ class VideoUpscaler:
     pulldown= is given.  The stage is stateless -- every frame is filtered on its own -- so it holds nothing back and any chunking
     gives the same frames.  The defaults are parameters: nothing is validated on footage.
 
+    denoise_strength="auto" and spatial_strength="auto" are refused: the decision needs the video.  Run savsr_amd.estimate_noise on a
+    probe chunk (or sum savsr_amd.noise_stats over a first pass, as python -m savsr_amd.upscale --denoise-strength auto does) and give
+    `verdict.denoise_kwargs()` / `verdict.spatial_kwargs()`.
+
     scan="detect" is refused: the decision needs the video.  Run savsr_amd.detect_scan on a probe chunk (or prepass.ScanStats over a
     first pass, as python -m savsr_amd.upscale --scan detect does) and give its answer as fields= / pulldown=."""
 
@@ -369,6 +407,12 @@ class VideoUpscaler:
         self._full = self.spec                     # the spec of the chunks as pushed; `spec` becomes the cropped size's with a crop
         self._split = make_stage(fields, pulldown, pulldown_cycle, self.spec.inp, self.spec.size, deinterlacer, field_rate, combed, comb_threshold,
                                  comb_pixels)          # the stage in front; None: as it was
+        for name, value, stage, call in (("denoise_strength", denoise_strength, denoise, "denoise_kwargs"),
+                                         ("spatial_strength", spatial_strength, spatial_denoise, "spatial_kwargs")):
+            if _auto_strength(value) and stage is not None:          # (without the stage: the options' own refusal, below)
+                raise ValueError(f"{name} = 'auto' in VideoUpscaler: the decision needs the whole video; measure the noise first "
+                                 f"(savsr_amd.estimate_noise on a probe chunk) and give its {call}(), or use python -m savsr_amd.upscale "
+                                 f"--{name.replace('_', '-')} auto")
         # the temporal denoiser, behind that stage (it needs progressive frames) and in front of the crop; None: as it was
         self._noise = make_denoiser(denoise, denoise_radius, denoise_strength, denoise_chroma_strength, self.spec.inp, self.spec.size)
         # the spatial denoiser, behind the crop: stateless, every frame on its own; None: as it was
